@@ -29,6 +29,9 @@ overlap and a launch's wall time is shared).  HBM appears as `hbm_frac` = counte
 SURVEY-8d algorithmic bytes are reported as a rate (`algorithmic_gbs`), never as a fraction of HBM peak: most are served by L2 / LDS.
 `cpu_baseline` -- the CPU oracle (the port of the reference's ThreadPool path) timed on this box's host cores on a bounded
 sample; reported, not a target.
+
+`--dump-outputs DIR` writes the framebuffer the last timed step produced to DIR/*.npy (dump_outputs).  The scene, seeds and
+sample counts follow from the arguments alone, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -44,7 +47,8 @@ import numpy as np
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
-HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md "Chip-level parameters"
+HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000 - 4096     # --dump-outputs: 64 MB in all, less room for the .npy headers
 
 
 def parse_args():
@@ -80,7 +84,11 @@ def parse_args():
     ap.add_argument("--pools", type=int, default=0, help="sample batches in flight in the timed region (0 = the library default)")
     ap.add_argument("--no-roofline-pass", action="store_true", help="skip the single-pool pass and the issue-rate measurement")
     ap.add_argument("--issue-table", action="store_true", help="print the measured issue rates for every kind and 1..8 waves/SIMD to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's framebuffer to DIR/*.npy (see dump_outputs) for output-for-output comparison of two builds")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     a.scene = "standin"
     if a.config == "C1":
         a.width, a.height, a.spp, a.level, a.material = 256, 256, 1, 6, 1
@@ -181,6 +189,26 @@ def device_code_hash():
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
     return h.hexdigest()[:16]
+
+
+def dump_outputs(out_dir, acc, pixels):
+    """--dump-outputs: what a caller of the timed path receives after its last step, as .npy files in float32 / float64.
+    accumulator.npy: the float4 running sums (rows, width, 4); pixels_rgb.npy: the packed 8-bit display pixels split into
+    R, G, B (rows, width, 3), when this process holds them for the whole frame.  Beyond DUMP_BUDGET_BYTES in all, the same
+    fixed, seeded sample of pixels is kept of every array (rows flattened to (n, ...)), with its flat pixel indices in
+    pixel_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"accumulator": np.ascontiguousarray(acc, np.float32)}
+    if pixels is not None:
+        arrays["pixels_rgb"] = np.stack([(pixels >> s) & 0xFF for s in (0, 8, 16)], axis=-1).astype(np.float32)
+    n_px = acc.shape[0] * acc.shape[1]
+    per_px = sum(a.nbytes for a in arrays.values()) // n_px
+    if per_px * n_px > DUMP_BUDGET_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n_px, DUMP_BUDGET_BYTES // (per_px + 8), replace=False))
+        arrays = {k: a.reshape(n_px, -1)[idx] for k, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 KERNEL_NAMES = {1: "megakernel", 2: "wf_trace", 3: "pt_persistent"}     # cgpt_stats.last_kernel -> the dominant kernel's name
@@ -303,6 +331,12 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     st = renderer.stats()
+    if args.dump_outputs and rank == 0:
+        # before the rehearsal check and the roofline pass below render into the same accumulator again
+        if gather is not None:
+            dump_outputs(args.dump_outputs, step.full.cpu().numpy(), renderer.pixels() if world == 1 else None)
+        else:
+            dump_outputs(args.dump_outputs, renderer.accumulator(), renderer.pixels())
 
     total_rays = float(st.traced_rays)
     if dist is not None:

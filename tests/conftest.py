@@ -8,7 +8,7 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "oracle"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-REFERENCE_DIR = "/root/reference"
+GOLDEN_MODELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "models")
 
 
 def pytest_configure(config):
@@ -34,11 +34,8 @@ def pytest_collection_modifyitems(config, items):
 
 @pytest.fixture(scope="session")
 def reference_assets():
-    """Cube/Duck glTF assets of the reference checkout (absent on the GPU box)."""
-    p = os.path.join(REFERENCE_DIR, "Assets", "Models")
-    if not os.path.isdir(p):
-        pytest.skip("/root/reference is not present here")
-    return p
+    """The reference's Cube / Duck glTF assets (and the Dragon's .gltf without its buffer), stored under tests/golden/models."""
+    return GOLDEN_MODELS
 
 
 @pytest.fixture(scope="session", autouse=True)

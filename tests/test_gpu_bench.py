@@ -44,6 +44,26 @@ def test_bench_line_contract():
     assert "workload" in d["config"] and "model" not in d["config"]
 
 
+def test_dump_outputs_hold_the_last_timed_step(tmp_path):
+    """--dump-outputs writes the framebuffer of the last timed step.  Every step starts from a reset accumulator with the same
+    seed, so the dump does not depend on --steps / --warmup, and its display pixels are the packing of its accumulator."""
+    import numpy as np
+    from cpugpupathtracing_amd import distributed as D
+    dumps = []
+    for k, (steps, warmup) in enumerate(((1, 1), (3, 2))):
+        out = tmp_path / str(k)
+        d, _ = run_bench(["--cpu-seconds", "0", "--no-roofline-pass", "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(out)])
+        assert d["steps"] == steps and d["ms_per_step"] > 0
+        assert sorted(os.listdir(out)) == ["accumulator.npy", "pixels_rgb.npy"]
+        dumps.append({n: np.load(out / f"{n}.npy") for n in ("accumulator", "pixels_rgb")})
+    a, b = dumps
+    assert a["accumulator"].dtype == np.float32 and a["accumulator"].shape == (144, 256, 4) and a["accumulator"][..., :3].any()
+    assert np.array_equal(a["accumulator"].view(np.uint32), b["accumulator"].view(np.uint32))
+    assert np.array_equal(a["pixels_rgb"], b["pixels_rgb"])
+    px = D.pack_pixels(a["accumulator"], 4)
+    assert np.array_equal(a["pixels_rgb"], np.stack([(px >> s) & 0xFF for s in (0, 8, 16)], axis=-1).astype(np.float32))
+
+
 def _run_raw(extra, env_extra=None):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(env_extra or {})

@@ -4,8 +4,8 @@ These are NOT pins in the rules' sense (parity stays "unpinned": the numbers com
 headers, which cannot be re-run here, and the reference itself holds no fixtures) -- they are the strongest anchor available.
 The reference cannot be built in this image (DESIGN.md "Oracle"), so these recorded vectors -- BVH statistics of the
 reference's Cube and Duck assets for all three build options, areas, and the 4- / 16-frame Duck render in the
-reference's own RNG/tile order -- are what anchor the oracle.  They need the reference's asset files and therefore run
-only where /root/reference exists (not on the GPU box).
+reference's own RNG/tile order -- are what anchor the oracle.  They read the reference's asset files, stored as data
+fixtures under tests/golden/models.
 """
 import os
 
