@@ -425,11 +425,12 @@ __device__ __forceinline__ Ray camera_ray(const DevCamera& cam, float u, float v
 }
 
 // ---- wave-level reduction of a per-lane counter, then one atomic per wave ---------------------------------------------
-__device__ __forceinline__ void wave_add_u64(unsigned long long* dst, uint32_t v)
+// `scale`: every counted event stands for that many (wave-uniform; the product is formed in 64 bits, after the sum)
+__device__ __forceinline__ void wave_add_u64(unsigned long long* dst, uint32_t v, uint32_t scale = 1u)
 {
     unsigned long long s = v;
     for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    if ((threadIdx.x & 63u) == 0u && s) atomicAdd(dst, s);
+    if ((threadIdx.x & 63u) == 0u && s) atomicAdd(dst, s * scale);
 }
 __device__ __forceinline__ void wave_add_f64(double* dst, double v)
 {

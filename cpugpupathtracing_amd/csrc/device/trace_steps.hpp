@@ -184,15 +184,31 @@ __device__ __forceinline__ bool pixel_of_index(const DevRenderArgs& a, const Pat
     py = GlobalRow(local_row, a.band_first, a.band_h, a.band_stride);
     return px < a.width && local_row < a.n_rows;
 }
-// primary ray + RNG stream of path `pid` (ref: Main.cpp:713-716, Camera::GetRay :133-140); false for the padded indices
-__device__ __forceinline__ bool primary_ray(const DevRenderArgs& args, const PathGrid& g, uint32_t pid, uint32_t batch_first, Ray& ray, uint32_t& rng, uint32_t& px_out)
+// primary ray + RNG stream of path `pid` (ref: Main.cpp:713-716, Camera::GetRay :133-140); false for the padded indices.
+// `pixel_out`: the path's pixel index (padded ones included)
+__device__ __forceinline__ bool primary_ray(const DevRenderArgs& args, const PathGrid& g, uint32_t pid, uint32_t batch_first, Ray& ray, uint32_t& rng, uint32_t& px_out,
+                                            uint32_t& pixel_out)
 {
     uint32_t s, p;
     path_split(g, pid, s, p);
+    pixel_out = p;
     uint32_t px, py, local_row;
     if (!pixel_of_index(args, g, p, px, py, local_row)) return false;
     px_out = px;
     rng = pcg_seed(py * args.width + px, batch_first + s, args.seed);
+    ray = camera_ray(args.camera, (float)px * (1.0f / (float)args.width), (float)py * (1.0f / (float)args.height));
+    return true;
+}
+__device__ __forceinline__ bool primary_ray(const DevRenderArgs& args, const PathGrid& g, uint32_t pid, uint32_t batch_first, Ray& ray, uint32_t& rng, uint32_t& px_out)
+{
+    uint32_t pixel_unused;
+    return primary_ray(args, g, pid, batch_first, ray, rng, px_out, pixel_unused);
+}
+// the primary ray of pixel index p: the same for every sample (no jitter, SURVEY A-14); false for the padded indices
+__device__ __forceinline__ bool pixel_ray(const DevRenderArgs& args, const PathGrid& g, uint32_t p, Ray& ray)
+{
+    uint32_t px, py, local_row;
+    if (!pixel_of_index(args, g, p, px, py, local_row)) return false;
     ray = camera_ray(args.camera, (float)px * (1.0f / (float)args.width), (float)py * (1.0f / (float)args.height));
     return true;
 }

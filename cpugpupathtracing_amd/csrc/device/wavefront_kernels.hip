@@ -22,8 +22,10 @@
 // Slot entry (48 B, three float4 planes, extend slot = path id, shadow slot = cap + path id):
 //   A = {o.xyz, t_max}  B = {d.xyz, bits(depth | spec << 8)}  C = extend: hit record {bits obj, tri, bvh_depth, t} written by trace
 //   (read by trace only when the same ray is traced again after total internal reflection, SURVEY A-3) | shadow: {pending.xyz, -}.
-// Round 0 has no generate kernel and no slot traffic for the rays: trace and shade both recompute the primary ray from the
-// path id (ref: Main.cpp:713-716, Camera::GetRay :133-140), trace stores only the 16-byte hit record, shade initialises the path state.
+// Round 0 has no generate kernel and no slot traffic for the rays: trace and shade both recompute the primary ray (ref: Main.cpp:713-716,
+// Camera::GetRay :133-140).  The reference does not jitter (SURVEY A-14), so trace walks the band's pixels, not the paths: one ray per
+// pixel, its 16-byte hit record in px_hit[pixel], counted once per sample.  Shade reads the record of the path's pixel and initialises
+// the path state.
 // TracePath (brute force, ref: Main.cpp:581-689) paths -- RENDER_MODE_BRUTE_FORCE, or the left half of the image in the reference's default
 // RENDER_MODE_COMPARISON (ref: Main.cpp:215,719-725) -- run through the same rounds: shade<BRUTE> records the level's operation in
 // brute[level][path] instead of updating a throughput, and folds the recorded chain over the leaf's radiance, innermost level first
@@ -64,6 +66,7 @@ static constexpr uint32_t kMaxKeys = 128;   // most runs per segment (image band
 struct WfDev {
     float4* A; float4* B; float4* C;   // 2 * cap slots each: [0, cap) extend, [cap, 2 cap) shadow
     float4* st_tp; float4* st_en;      // cap paths
+    float4* px_hit;                    // n_pixels: round 0's hit record {bits obj, tri, bvh_depth, t} per pixel of the band, shared by all samples of the batch
     float4* brute;                     // TracePath / COMPARISON renders only: [level][path][2] BruteLevel records (shade_device.hpp), max_ray_depth + 1 levels
     uint8_t* hit_flag;                 // cap paths: did the path's extend ray of this round hit anything (retire_misses only; written by trace)
     uint32_t* list_ext; uint32_t* list_sh;     // dense lists of path ids for the next trace / shade (cap entries each)
@@ -88,7 +91,9 @@ struct WfDev {
 };
 
 // ---- K2/K4 trace: persistent closest-hit traversal with per-lane refill ------------------------------------------------
-// `first_round`: the extend list is the identity over all paths and there are no shadow rays yet.
+// `first_round`: the list is the identity over the PIXELS of the band (not the paths) and there are no shadow rays yet.  The reference
+// does not jitter (SURVEY A-14): every sample of a pixel traces the same primary ray to the same hit, so round 0 traces it once, stores
+// the hit record to px_hit[pixel] and counts it as the batch's n_samples IntersectScene calls.
 // The traversal states, their voted steps and the LDS layout are in trace_steps.hpp.
 #ifndef CGPT_TRACE_WAVES_PER_SIMD
 #define CGPT_TRACE_WAVES_PER_SIMD 1
@@ -107,7 +112,7 @@ __global__ void __launch_bounds__(kTraceBlock, (!COUNT && !FIRST) ? CGPT_TRACE_W
     const TravCtx ctx = trav_setup(sc, lds_dyn, tune.top_records, wf.stack_overflow, gridDim.x * kTraceBlock, tune.lds_tris);
     lds_u32* const ring = ctx.ring;
 
-    const uint32_t n_ext = first_round ? wf.n_paths : wf.plan[0];
+    const uint32_t n_ext = first_round ? wf.g.n_pixels : wf.plan[0];
     const uint32_t n_sh = first_round ? 0u : wf.plan[1];
     const uint32_t blocks_ext = (n_ext + 63u) / 64u, n_blocks = blocks_ext + (n_sh + 63u) / 64u;
     const uint32_t n_waves = gridDim.x * (kTraceBlock / 64u);
@@ -144,7 +149,10 @@ __global__ void __launch_bounds__(kTraceBlock, (!COUNT && !FIRST) ? CGPT_TRACE_W
         // (loop-invariant for the whole traversal) and six 64-bit addresses ride along through every step -- ten registers of the budget.
         uint32_t slot = slot_of_lane;
         asm volatile("" : "+v"(slot));
-        if (slot >= wf.cap) {                                                 // connect epilogue, ref: Main.cpp:454-463
+        if (first_round) {                                                    // slot = pixel index: the hit record of all its samples
+            float4 c; c.x = __uint_as_float(r.obj); c.y = __uint_as_float(r.tri); c.z = __uint_as_float(trav_depth(r)); c.w = r.t;
+            st_stream(&wf.px_hit[slot], c);
+        } else if (slot >= wf.cap) {                                                 // connect epilogue, ref: Main.cpp:454-463
             if (r.obj == kNoHit) {
                 const float4 pe = ld_stream(&wf.C[slot]);
                 const uint32_t pid = slot - wf.cap;
@@ -157,8 +165,8 @@ __global__ void __launch_bounds__(kTraceBlock, (!COUNT && !FIRST) ? CGPT_TRACE_W
             // read the last depth, so they take the full path): ~40 % of the later rounds' rays.  Shade never sees them: it reads
             // this byte per ray and queues only the hits.
             const bool hit = r.obj != kNoHit;
-            if (!first_round && wf.retire_misses) wf.hit_flag[slot] = hit ? (uint8_t)1 : (uint8_t)0;
-            if (first_round || !wf.retire_misses || hit) {
+            if (wf.retire_misses) wf.hit_flag[slot] = hit ? (uint8_t)1 : (uint8_t)0;
+            if (!wf.retire_misses || hit) {
                 float4 c; c.x = __uint_as_float(r.obj); c.y = __uint_as_float(r.tri); c.z = __uint_as_float(trav_depth(r)); c.w = r.t;
                 st_stream(&wf.C[slot], c);                                    // hit record
             }
@@ -198,10 +206,9 @@ __global__ void __launch_bounds__(kTraceBlock, (!COUNT && !FIRST) ? CGPT_TRACE_W
                 slot_of_lane = slot;
                 bool ok = true;
                 V3 o, d; float t; uint32_t obj = kNoHit, tri = 0, depth = 0;      // fresh ray (extend or shadow, ref: Primitives.h:79-81)
-                if (first_round) {                                            // primary ray from the path id, nothing to load
-                    uint32_t rng_unused, px_unused;
+                if (first_round) {                                            // primary ray from the pixel index, nothing to load
                     Ray pr;
-                    ok = primary_ray(args, wf.g, slot, batch_first, pr, rng_unused, px_unused);   // false: padding of an edge tile
+                    ok = pixel_ray(args, wf.g, slot, pr);                     // false: padding of an edge tile
                     o = pr.o; d = pr.d; t = pr.t;
                 } else {
                     const float4 a = ld_stream(&wf.A[slot]), b = ld_stream(&wf.B[slot]);
@@ -222,7 +229,7 @@ __global__ void __launch_bounds__(kTraceBlock, (!COUNT && !FIRST) ? CGPT_TRACE_W
             if (!first_round) wave_rays += take;
         }
         // Done when nothing is in flight and nothing is left to fetch.  Nothing in flight alone is not enough: every id just handed
-        // out may have been padding of an edge tile (pixel-major ids put a padded pixel's samples side by side); the step loop below
+        // out may have been padding of an edge tile (round 0: a padded row of a tile; later rounds never list one); the step loop below
         // then falls straight through and the wave fetches on.
         CYC_END(cy_refill);
         if (__builtin_amdgcn_ballot_w64(r.code != kIdle) == 0ull && ring_count == 0u && block >= n_blocks) break;
@@ -238,10 +245,10 @@ __global__ void __launch_bounds__(kTraceBlock, (!COUNT && !FIRST) ? CGPT_TRACE_W
             if (can_refill && 64u - n_busy >= tune.refill_idle) break;        // enough idle lanes: go refill them
             const uint32_t w_obj = n_obj << tune.obj_shift;
             if (COUNT) ph_votes++;
-            // Round 0: the 64 lanes of a wave carry the SAME primary ray (samples of one pixel, no jitter: SURVEY A-14), so there is no
-            // divergence for the voted branch-free steps to buy off; every lane walks its meshes in the lean loop (the reference's own
-            // control flow, trace_steps.hpp: lean_traverse -- ~50 instructions per node instead of ~75 and no votes), then takes the
-            // object step.  Same results, same counters.
+            // Round 0: the 64 lanes of a wave carry the primary rays of one 8x8 tile -- neighbouring rays that walk nearly the same
+            // nodes, so there is little divergence for the voted branch-free steps to buy off; every lane walks its meshes in the lean
+            // loop (the reference's own control flow, trace_steps.hpp: lean_traverse -- ~50 instructions per node instead of ~75 and no
+            // votes), then takes the object step.  Same results, same counters.
             if (FIRST && tune.first_lean) {
                 if (r.code < kStartObject || (int32_t)r.code < 0) lean_traverse<COUNT, !FIRST>(ctx, r, cnt);
                 if (r.code == kStartObject && object_step<COUNT, !FIRST>(ctx, r, cnt)) finish_ray();
@@ -294,12 +301,15 @@ __global__ void __launch_bounds__(kTraceBlock, (!COUNT && !FIRST) ? CGPT_TRACE_W
         wave_add_u64(&wf.phase_stats[23], cnt.xy_both_miss); wave_add_u64(&wf.phase_stats[24], cnt.x_both_miss);
     }
 #endif
-    if (first_round) wave_add_u64(&counters->traced_rays, cnt.rays);
+    // round 0: every traced pixel ray is the IntersectScene call of each of the batch's samples (the reference's counts); the lanes'
+    // 32-bit sums are of per-pixel counts and the product is formed in 64 bits
+    const uint32_t per_ray = first_round ? wf.g.n_samples : 1u;
+    if (first_round) wave_add_u64(&counters->traced_rays, cnt.rays, per_ray);
     else if (lane_id() == 0u && wave_rays) atomicAdd(&counters->traced_rays, (unsigned long long)wave_rays);
     if (COUNT) {
-        wave_add_u64(&counters->inner_steps, cnt.inner);
-        wave_add_u64(&counters->tri_tests, cnt.tris);
-        wave_add_u64(&counters->bvh_depth_sum, cnt.depth);
+        wave_add_u64(&counters->inner_steps, cnt.inner, per_ray);
+        wave_add_u64(&counters->tri_tests, cnt.tris, per_ray);
+        wave_add_u64(&counters->bvh_depth_sum, cnt.depth, per_ray);
         if (wf.phase_stats && lane_id() == 0u) {
             atomicAdd(&wf.phase_stats[0], (unsigned long long)ph_inner); atomicAdd(&wf.phase_stats[1], (unsigned long long)ph_leaf);
             atomicAdd(&wf.phase_stats[2], (unsigned long long)ph_obj); atomicAdd(&wf.phase_stats[3], (unsigned long long)ph_obj_lanes);
@@ -392,14 +402,16 @@ __global__ void __launch_bounds__(256, CGPT_SHADE_WAVES_PER_SIMD) wf_shade(const
             queued = rest;
         }
         if (active) {
-            const float4 c = ld_stream(&wf.C[pid]);                           // hit record written by trace
+            float4 c;                                                         // hit record written by trace
             Ray ray, shadow;
             PathState ps;
             bool is_pixel = true;
             bool brute_path = false;                                          // this path runs TracePath
             if (first_round) {                                                // primary ray and fresh path state from the path id
-                uint32_t px = 0;
-                is_pixel = primary_ray(args, wf.g, pid, batch_first, ray, ps.rng, px);
+                uint32_t px = 0, pixel = 0;
+                is_pixel = primary_ray(args, wf.g, pid, batch_first, ray, ps.rng, px, pixel);
+                c = wf.px_hit[pixel];                                         // the pixel's hit, one record for all its samples (cached:
+                                                                              // with pixel-major ids a wave's lanes share a few records)
                 ps.throughput = mk(1.0f); ps.energy = mk(0.0f); ps.depth = 0; ps.is_specular = false;
                 if (BRUTE) brute_path = args.settings.render_mode == 1u || (args.settings.render_mode == 0u && px < args.width / 2u);   // ref: Main.cpp:719-729
             } else {
@@ -411,6 +423,7 @@ __global__ void __launch_bounds__(256, CGPT_SHADE_WAVES_PER_SIMD) wf_shade(const
                 const uint32_t fl = __float_as_uint(b.w);
                 ps.depth = fl & 0xFFu; ps.is_specular = (fl & 0x100u) != 0u;
                 if (BRUTE) brute_path = (fl & 0x200u) != 0u;
+                c = ld_stream(&wf.C[pid]);
             }
             ray.t = c.w; ray.obj = __float_as_uint(c.x); ray.tri = __float_as_uint(c.y); ray.bvh_depth = __float_as_uint(c.z);
             shadow = ray;
@@ -476,6 +489,8 @@ __global__ void __launch_bounds__(256, CGPT_SHADE_WAVES_PER_SIMD) wf_shade(const
                 nb.x = ray.d.x; nb.y = ray.d.y; nb.z = ray.d.z;
                 nb.w = __uint_as_float((ps.depth & 0xFFu) | (ps.is_specular ? 0x100u : 0u) | ((BRUTE && brute_path) ? 0x200u : 0u));
                 st_stream(&wf.A[pid], na); st_stream(&wf.B[pid], nb);         // C keeps the hit record (payload of a re-traced ray)
+                if (first_round && ray.t != 1e34f) st_stream(&wf.C[pid], c);  // round 0 kept it per pixel: the re-traced ray's payload goes to
+                                                                              // its slot (trace reads C exactly when A.w != 1e34)
                 key_ext = (ray.d.x < 0.0f ? 1u : 0u) | (ray.d.y < 0.0f ? 2u : 0u) | (ray.d.z < 0.0f ? 4u : 0u);
             }
             if (emit_sh) {                                                    // NEE connection, slot cap + pid
@@ -690,7 +705,8 @@ struct WfTuning {               // defaults measured on MI355X (profiles/r01); o
     uint32_t trace_chunk = 1;         // consecutive blocks per trace work item
     uint32_t shadow_any_hit = 1;      // shadow rays stop at their first hit (not in the counting kernels)
     uint32_t lds_tris = 1;            // the small meshes' triangles (the ground quad) are read from an LDS copy
-    uint32_t first_lean = 1;          // round 0 (identical rays per wave) walks in the lean per-lane loop instead of voted steps
+    uint32_t first_lean = 1;          // round 0 walks in the lean per-lane loop instead of voted steps (per-pixel rays: 0.68-0.71 ms
+                                      // against 0.72-0.74 voted, frame level; profiles/r04)
     uint32_t trace_events = 1;        // time every trace launch with its own hipEvent pair (cgpt_stats.dominant_ms)
     uint32_t path_order = 2;          // PathOrder of the path ids (trace_steps.hpp PathGrid): 2 pixel-major, 1 tile-major, 0 sample-major
     uint32_t retire_misses = 1;       // shade skips the state loads of later-round rays that hit nothing
@@ -724,7 +740,7 @@ struct WfHost {
     hipStream_t streams[kMaxPools] = {};
     hipEvent_t acc_done[kMaxPools] = {};
     hipEvent_t begin = nullptr;
-    uint32_t alloc_cap = 0, alloc_segs = 0, alloc_seg_cap = 0, alloc_pools = 0, alloc_overflow = 0, alloc_brute_levels = 0;
+    uint32_t alloc_cap = 0, alloc_segs = 0, alloc_seg_cap = 0, alloc_pools = 0, alloc_overflow = 0, alloc_brute_levels = 0, alloc_pixels = 0;
     bool alloc_sort = false;
     uint32_t n_cus = 0;
     uint32_t trace_blocks_per_cu[2][2] = {}, shade_blocks_per_cu[2][2] = {};   // trace: [COUNT][FIRST]; shade: [COUNT][BRUTE]
@@ -739,13 +755,13 @@ static void WfRelease(WfHost* h)
     for (uint32_t p = 0; p < kMaxPools; ++p) {
         WfDev& d = h->dev[p];
         (void)hipFree(d.A); (void)hipFree(d.B); (void)hipFree(d.C);
-        (void)hipFree(d.st_tp); (void)hipFree(d.st_en); (void)hipFree(d.hit_flag); (void)hipFree(d.brute);
+        (void)hipFree(d.st_tp); (void)hipFree(d.st_en); (void)hipFree(d.hit_flag); (void)hipFree(d.brute); (void)hipFree(d.px_hit);
         (void)hipFree(d.list_ext); (void)hipFree(d.list_sh); (void)hipFree(d.seg_ext); (void)hipFree(d.seg_sh);
         (void)hipFree(d.seg_count); (void)hipFree(d.seg_prefix); (void)hipFree(d.plan); (void)hipFree(d.stack_overflow);
         (void)hipFree(d.seg_key_ext); (void)hipFree(d.seg_key_sh);
         d = WfDev{};
     }
-    h->alloc_cap = 0; h->alloc_segs = 0; h->alloc_seg_cap = 0; h->alloc_pools = 0; h->alloc_overflow = 0; h->alloc_sort = false; h->alloc_brute_levels = 0;
+    h->alloc_cap = 0; h->alloc_segs = 0; h->alloc_seg_cap = 0; h->alloc_pools = 0; h->alloc_overflow = 0; h->alloc_sort = false; h->alloc_brute_levels = 0; h->alloc_pixels = 0;
 }
 
 void WavefrontFree(void* state)
@@ -952,7 +968,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
         const bool banded = !h->tune.sort && h->tune.bands > 1u && cap >= h->tune.bands_min_paths;   // (the last, shorter batch of a render may still fall below: it keeps this chunk)
         shade_chunk = banded ? h->tune.shade_chunk_banded : h->tune.shade_chunk;
         seg_cap = ((((cap + 63u) / 64u + shade_chunk - 1u) / shade_chunk + min_shade_waves - 1u) / min_shade_waves) * shade_chunk * 64u;   // whole chunks per wave
-        if (h->alloc_overflow >= overflow_words && h->alloc_cap >= cap && h->alloc_segs >= n_segs && h->alloc_seg_cap >= seg_cap && h->alloc_pools >= n_pools && (!h->tune.sort || h->alloc_sort) && h->alloc_brute_levels >= brute_levels) break;
+        if (h->alloc_overflow >= overflow_words && h->alloc_cap >= cap && h->alloc_segs >= n_segs && h->alloc_seg_cap >= seg_cap && h->alloc_pools >= n_pools && (!h->tune.sort || h->alloc_sort) && h->alloc_brute_levels >= brute_levels && h->alloc_pixels >= n_pixels) break;
         WF_TRY(hipDeviceSynchronize());
         WfRelease(h);
         const size_t q = 2 * (size_t)cap * sizeof(float4);
@@ -964,6 +980,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
             get((void**)&d.st_tp, (size_t)cap * sizeof(float4));
             get((void**)&d.st_en, (size_t)cap * sizeof(float4));
             get((void**)&d.hit_flag, (size_t)cap);
+            get((void**)&d.px_hit, (size_t)n_pixels * sizeof(float4));
             if (brute_levels) get((void**)&d.brute, (size_t)brute_levels * cap * 2u * sizeof(float4));
             get((void**)&d.list_ext, (size_t)cap * sizeof(uint32_t));
             get((void**)&d.list_sh, (size_t)cap * sizeof(uint32_t));
@@ -977,6 +994,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
         }
         if (err == hipSuccess) {
             h->alloc_cap = cap; h->alloc_segs = n_segs; h->alloc_seg_cap = seg_cap; h->alloc_pools = n_pools; h->alloc_overflow = overflow_words; h->alloc_sort = h->tune.sort != 0u; h->alloc_brute_levels = brute_levels;
+            h->alloc_pixels = n_pixels;
             break;
         }
         (void)hipGetLastError();                                              // out of memory: give everything back and ask for half
