@@ -12,7 +12,7 @@ from ._paths import LIB_PATH
 
 ABI_VERSION = 2
 CGPT_OK, CGPT_ERR_INVALID, CGPT_ERR_HIP, CGPT_ERR_NO_SCENE, CGPT_ERR_UNSUPPORTED, CGPT_ERR_NO_DEVICE = range(6)
-OBJECT_MESH, OBJECT_SPHERE, OBJECT_PLANE = 0, 1, 2
+OBJECT_MESH, OBJECT_SPHERE, OBJECT_PLANE, OBJECT_TRIANGLE = 0, 1, 2, 3
 MODE_COMPARISON, MODE_BRUTE_FORCE, MODE_ADVANCED = 0, 1, 2
 DEBUG_NONE, DEBUG_RAY_DEPTH, DEBUG_BVH_DEPTH = 0, 1, 2
 KERNEL_AUTO, KERNEL_MEGAKERNEL, KERNEL_WAVEFRONT, KERNEL_PERSISTENT = 0, 1, 2, 3
@@ -140,6 +140,7 @@ PROTOTYPES = {
     "cgpth_scene_rebuild_bvh_device": (C.c_int, [_vp, C.c_uint32, C.c_int, _vp]),
     "cgpth_scene_add_sphere": (C.c_int, [_vp, _fp, C.c_float, C.c_uint32]),
     "cgpth_scene_add_plane": (C.c_int, [_vp, _fp, _fp, C.c_uint32]),
+    "cgpth_scene_add_triangle": (C.c_int, [_vp, C.POINTER(Triangle), C.c_uint32]),
     "cgpth_scene_add_light": (C.c_int, [_vp, C.c_uint32]),
     "cgpth_scene_set_camera": (C.c_int, [_vp, _fp, _fp, C.c_float, C.c_float]),
     "cgpth_scene_set_settings": (C.c_int, [_vp, C.POINTER(Settings)]),

@@ -127,6 +127,22 @@ void PackMaterial(const cgpt_material& m, float4 out[4])
     out[3] = F4(m.intensity, AsFloat(m.is_light ? 1u : 0u), 0.0f, 0.0f);
 }
 
+// leaf-ordered triangle record (device_scene.h: tri_leaf) and original-order record (tri_orig) of one triangle
+void PackLeafTri(const cgpt_triangle& tr, uint32_t tri_idx, float4 rec[3])
+{
+    const float e1[3] = { tr.v1.pos[0] - tr.v0.pos[0], tr.v1.pos[1] - tr.v0.pos[1], tr.v1.pos[2] - tr.v0.pos[2] };   // ref: Primitives.cpp:9
+    const float e2[3] = { tr.v2.pos[0] - tr.v0.pos[0], tr.v2.pos[1] - tr.v0.pos[1], tr.v2.pos[2] - tr.v0.pos[2] };   // ref: Primitives.cpp:10
+    rec[0] = F4(tr.v0.pos[0], tr.v0.pos[1], tr.v0.pos[2], e1[0]);
+    rec[1] = F4(e1[1], e1[2], e2[0], e2[1]);
+    rec[2] = F4(0.0f, e2[2], AsFloat(tri_idx), AsFloat(0u));                                        // last_in_leaf set by the caller
+}
+void PackOrigTri(const cgpt_triangle& tr, float4 rec[3])
+{
+    rec[0] = F4(tr.v0.pos[0], tr.v0.pos[1], tr.v0.pos[2], tr.v0.normal[0]);
+    rec[1] = F4(tr.v1.pos[0], tr.v1.pos[1], tr.v1.pos[2], tr.v0.normal[1]);
+    rec[2] = F4(tr.v2.pos[0], tr.v2.pos[1], tr.v2.pos[2], tr.v0.normal[2]);
+}
+
 // Re-lays the reference's AoS scene into the device layout of device_scene.h, validating everything a kernel will
 // index with (a malformed tree must fail here, not fault on the GPU).
 int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
@@ -139,22 +155,26 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
     std::vector<DevObject> objs(sd.n_objects);
     uint32_t max_tree_depth = 0;
 
-    // leaf-record order (device_scene.h): the triangles of the small meshes first, then the rest in object order
+    // leaf-record order (device_scene.h): the triangles of the small meshes first, then the rest in object order; a triangle
+    // object has one leaf record, like a one-triangle mesh
     std::vector<uint32_t> leaf_base_of(sd.n_objects, 0);
     uint32_t n_small_tris = 0;
     {
+        auto leaf_records = [&](uint32_t oi) -> uint32_t {
+            const cgpt_object& o = sd.objects[oi];
+            return o.kind == CGPT_OBJECT_MESH ? o.tri_count : (o.kind == CGPT_OBJECT_TRIANGLE ? 1u : 0u);
+        };
         uint64_t total = 0;
         std::vector<uint8_t> small(sd.n_objects, 0);
         for (uint32_t oi = 0; oi < sd.n_objects; ++oi) {
-            const cgpt_object& o = sd.objects[oi];
-            if (o.kind != CGPT_OBJECT_MESH) continue;
-            total += o.tri_count;
-            if (o.tri_count > 0 && o.tri_count <= kSmallMeshTris && n_small_tris + o.tri_count <= kLdsTrisMax) { small[oi] = 1; leaf_base_of[oi] = n_small_tris; n_small_tris += o.tri_count; }
+            const uint32_t n = leaf_records(oi);
+            total += n;
+            if (n > 0 && n <= kSmallMeshTris && n_small_tris + n <= kLdsTrisMax) { small[oi] = 1; leaf_base_of[oi] = n_small_tris; n_small_tris += n; }
         }
         if (total >= (1u << 26)) return Fail(ctx, CGPT_ERR_INVALID, "scene too large: more than 2^26 triangles or inner nodes");
         uint32_t next = n_small_tris;
         for (uint32_t oi = 0; oi < sd.n_objects; ++oi)
-            if (sd.objects[oi].kind == CGPT_OBJECT_MESH && !small[oi]) { leaf_base_of[oi] = next; next += sd.objects[oi].tri_count; }
+            if (!small[oi]) { leaf_base_of[oi] = next; next += leaf_records(oi); }
         tri_leaf.resize(3 * (size_t)total);
     }
 
@@ -175,8 +195,27 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
             memcpy(d.plane_point, o.plane_point, 12);
             continue;
         }
+        if (o.kind == CGPT_OBJECT_TRIANGLE) {
+            // Primitive(const Triangle&) (ref: Primitives.h:84-89): one leaf record as the root, so the trace kernels test it with
+            // their leaf step -- IntersectTriangle (ref: Primitives.cpp:292-305) -- and its shading normal is v0.normal (:308-321)
+            if (!sd.triangles) return Fail(ctx, CGPT_ERR_INVALID, "triangle object %u but triangles is null", oi);
+            if (o.tri_count != 1 || o.node_count != 0)
+                return Fail(ctx, CGPT_ERR_INVALID, "object %u: a triangle object has tri_count 1 and node_count 0, got %u and %u", oi, o.tri_count, o.node_count);
+            if (o.tri_offset >= sd.n_triangles) return Fail(ctx, CGPT_ERR_INVALID, "object %u: triangle %u out of range", oi, o.tri_offset);
+            const cgpt_triangle& tr = sd.triangles[o.tri_offset];
+            const uint32_t leaf_base = leaf_base_of[oi];
+            const uint32_t orig_base = (uint32_t)(tri_orig.size() / 3);
+            float4* leaf = tri_leaf.data() + 3 * (size_t)leaf_base;          // sized above
+            PackLeafTri(tr, 0u, leaf);
+            leaf[2].w = AsFloat(1u);                                          // last_in_leaf
+            tri_orig.resize(tri_orig.size() + 3);
+            PackOrigTri(tr, tri_orig.data() + 3 * (size_t)orig_base);
+            tri_normal.push_back(F4(tr.v0.normal[0], tr.v0.normal[1], tr.v0.normal[2], 0.0f));   // TriangleNormal, ref: Primitives.cpp:148-151
+            d.root_code = kLeafBit | leaf_base; d.tri_base = orig_base; d.n_tris = 1;
+            continue;
+        }
         if (o.kind != CGPT_OBJECT_MESH)
-            return Fail(ctx, CGPT_ERR_UNSUPPORTED, "object %u: primitive kind %u has no intersector (the reference EXCEPTs too, Primitives.cpp:304)", oi, o.kind);
+            return Fail(ctx, CGPT_ERR_UNSUPPORTED, "object %u: primitive kind %u has no intersector (the reference EXCEPTs on AABB too, Primitives.cpp:302-305)", oi, o.kind);
 
         // ---- mesh: validate the slices ----
         if (!sd.nodes || !sd.triangles || !sd.tri_indices) return Fail(ctx, CGPT_ERR_INVALID, "mesh object %u but nodes/triangles/tri_indices is null", oi);
@@ -216,21 +255,14 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
         for (uint32_t i = 0; i < o.tri_count; ++i) {
             const uint32_t t = tidx[i];
             if (t >= o.tri_count) return Fail(ctx, CGPT_ERR_INVALID, "object %u: tri_indices[%u] = %u out of range", oi, i, t);
-            const cgpt_triangle& tr = tris[t];
-            const float e1[3] = { tr.v1.pos[0] - tr.v0.pos[0], tr.v1.pos[1] - tr.v0.pos[1], tr.v1.pos[2] - tr.v0.pos[2] };   // ref: Primitives.cpp:9
-            const float e2[3] = { tr.v2.pos[0] - tr.v0.pos[0], tr.v2.pos[1] - tr.v0.pos[1], tr.v2.pos[2] - tr.v0.pos[2] };   // ref: Primitives.cpp:10
-            leaf[3 * (size_t)i + 0] = F4(tr.v0.pos[0], tr.v0.pos[1], tr.v0.pos[2], e1[0]);
-            leaf[3 * (size_t)i + 1] = F4(e1[1], e1[2], e2[0], e2[1]);
-            leaf[3 * (size_t)i + 2] = F4(0.0f, e2[2], AsFloat(t), AsFloat(0u));
+            PackLeafTri(tris[t], t, leaf + 3 * (size_t)i);
         }
         // original-order records for GetTriangle users
         tri_orig.resize(tri_orig.size() + 3 * (size_t)o.tri_count);
         float4* orig = tri_orig.data() + 3 * (size_t)orig_base;
         for (uint32_t t = 0; t < o.tri_count; ++t) {
             const cgpt_triangle& tr = tris[t];
-            orig[3 * (size_t)t + 0] = F4(tr.v0.pos[0], tr.v0.pos[1], tr.v0.pos[2], tr.v0.normal[0]);
-            orig[3 * (size_t)t + 1] = F4(tr.v1.pos[0], tr.v1.pos[1], tr.v1.pos[2], tr.v0.normal[1]);
-            orig[3 * (size_t)t + 2] = F4(tr.v2.pos[0], tr.v2.pos[1], tr.v2.pos[2], tr.v0.normal[2]);
+            PackOrigTri(tr, orig + 3 * (size_t)t);
             tri_normal.push_back(F4(tr.v0.normal[0], tr.v0.normal[1], tr.v0.normal[2], 0.0f));   // TriangleNormal, ref: Primitives.cpp:148-151
         }
 
@@ -275,8 +307,9 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
     for (uint32_t i = 0; i < sd.n_lights; ++i) {
         const uint32_t li = sd.light_indices[i];
         if (li >= sd.n_objects) return Fail(ctx, CGPT_ERR_INVALID, "light_indices[%u] = %u out of range", i, li);
-        if (sd.objects[li].kind != CGPT_OBJECT_MESH && sd.objects[li].kind != CGPT_OBJECT_SPHERE)
-            return Fail(ctx, CGPT_ERR_UNSUPPORTED, "light %u: only mesh and sphere lights can be sampled (the reference EXCEPTs, Main.cpp:383)", i);
+        if (sd.objects[li].kind != CGPT_OBJECT_MESH && sd.objects[li].kind != CGPT_OBJECT_SPHERE)   // planes and triangle objects
+            return Fail(ctx, CGPT_ERR_UNSUPPORTED, "light %u (object %u, kind %u): only mesh and sphere lights can be sampled (the reference EXCEPTs, Main.cpp:383)",
+                        i, li, sd.objects[li].kind);
     }
 
     const uint32_t stack_depth = max_tree_depth + 1;
@@ -335,7 +368,7 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
         const DevObject& d = objs[oi];
         float4& q0 = obj_trace[2 * (size_t)oi]; float4& q1 = obj_trace[2 * (size_t)oi + 1];
         q0 = F4(AsFloat(d.kind), 0.0f, 0.0f, 0.0f); q1 = F4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (d.kind == CGPT_OBJECT_MESH) q0.y = AsFloat(d.root_code);
+        if (d.kind == CGPT_OBJECT_MESH || d.kind == CGPT_OBJECT_TRIANGLE) { q0.x = AsFloat(CGPT_OBJECT_MESH); q0.y = AsFloat(d.root_code); }   // a triangle: a leaf-rooted mesh (device_scene.h)
         else if (d.kind == CGPT_OBJECT_SPHERE) { q0.y = d.sphere_center[0]; q0.z = d.sphere_center[1]; q0.w = d.sphere_center[2]; q1.x = d.sphere_radius_sq; }
         else { q0.y = d.plane_normal[0]; q0.z = d.plane_normal[1]; q0.w = d.plane_normal[2]; q1.x = d.plane_point[0]; q1.y = d.plane_point[1]; q1.z = d.plane_point[2]; }
     }

@@ -26,22 +26,28 @@
 //  objects     DevObject[n]         read with wave-uniform indices (scalar loads)
 //  obj_trace   float4[2 * n]        what IntersectScene's object loop needs of object i, for per-lane object indices:
 //                                   {kind, p0, p1, p2 | p3, p4, p5, -}: mesh p0 = root code; sphere p0..2 = centre, p3 = radius^2;
-//                                   plane p0..2 = normal, p3..5 = point
+//                                   plane p0..2 = normal, p3..5 = point.  A triangle object is written as kind 0 (mesh) whose
+//                                   root code is a leaf: its one leaf-triangle record (tri_idx 0, last_in_leaf 1), so every
+//                                   trace kernel tests it with the leaf step it already runs -- IntersectTriangle with no bounds
+//                                   test and no bvh_depth increment, as a leaf-rooted mesh is walked (ref: BVH.cpp:68-90).
+//                                   DevObject.kind keeps CGPT_OBJECT_TRIANGLE for shading and the COUNT walks.
 //
 // record order: a child-pair record's index is only a name (the codes inside the records and the root codes are the only
 // references to it), so the upload renumbers them: records [0, n_top_records) are the top levels of all meshes' trees in
 // breadth-first order -- the part of the tree every ray walks; the trace kernel keeps a copy of them in LDS -- and the rest
 // follow in the reference's depth-first allocation order (a parent next to its left subtree).
 // Leaf-triangle records: the triangles of SMALL meshes (at most kSmallMeshTris triangles each, kLdsTrisMax in total -- the ground quad
-// of the reference scene, ref: Main.cpp:789-800, whose two triangles every ray of the scene tests) come first, records
-// [0, n_small_tris); the voted trace kernels read those from an LDS copy, which takes two of the ~2.8 triangle fetches per ray off
-// the vector-memory path.  Larger meshes follow in object order.
+// of the reference scene, ref: Main.cpp:789-800, whose two triangles every ray of the scene tests; a triangle object counts as a
+// one-triangle mesh) come first, records [0, n_small_tris); the voted trace kernels read those from an LDS copy, which takes two of
+// the ~2.8 triangle fetches per ray off the vector-memory path.  Larger meshes follow in object order.
 //
 // traversal code: bit 31 clear -> index of a child-pair record; bit 31 set -> index (into tri_leaf records) of the first
 // triangle of a leaf, whose last triangle carries last_in_leaf = 1.
 #pragma once
 #include <cstdint>
 #include <hip/hip_runtime.h>
+
+#include "cpugpupt_abi.h"
 
 namespace cgpt {
 
@@ -57,8 +63,8 @@ static constexpr uint32_t kTopRecords = CGPT_TOP_RECORDS_MAX;   // most records 
 struct DevObject {
     uint32_t kind;        // cgpt_object_kind
     uint32_t mat_index;
-    uint32_t root_code;   // traversal code of the root (a leaf code when the root never split)
-    uint32_t tri_base;    // first record of this mesh in tri_orig (object-local tri_idx + tri_base)
+    uint32_t root_code;   // traversal code of the root (a leaf code when the root never split; a triangle object's one leaf record)
+    uint32_t tri_base;    // first record of this mesh in tri_orig (object-local tri_idx + tri_base; a triangle object's own record)
     uint32_t n_tris;
     float total_area;
     float sphere_radius, sphere_radius_sq;

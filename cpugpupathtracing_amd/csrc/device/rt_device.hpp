@@ -356,7 +356,11 @@ __device__ __forceinline__ void intersect_scene(const DevScene& sc, Ray& ray, ui
         bool hit;
         if (obj.kind == 0u) hit = traverse_mesh<COUNT>(sc, obj.root_code, ray.o, ray.d, inv, ray.t, ray.tri, ray.bvh_depth, stack, stack_stride, cnt);
         else if (obj.kind == 1u) hit = intersect_sphere(mk(obj.sphere_center), obj.sphere_radius_sq, ray.o, ray.d, ray.t);
-        else hit = intersect_plane(mk(obj.plane_normal), mk(obj.plane_point), ray.o, ray.d, ray.t);
+        else if (obj.kind == 2u) hit = intersect_plane(mk(obj.plane_normal), mk(obj.plane_point), ray.o, ray.d, ray.t);
+        else {                                                                // triangle object: IntersectTriangle on its leaf record
+            const LeafTri lt = load_leaf_tri(sc.tri_leaf, obj.root_code & ~kLeafBit);   // (ref: Primitives.cpp:292-296); ray.tri keeps
+            hit = intersect_triangle(lt.v0, lt.e1, lt.e2, ray.o, ray.d, ray.t);          // what an earlier mesh wrote, as payload.tri_idx does
+        }
         if (hit) ray.obj = obj_idx;
     }
 }

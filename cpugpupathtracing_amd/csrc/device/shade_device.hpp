@@ -14,17 +14,18 @@ namespace dev {
 
 struct Hit { V3 pos, normal; uint32_t mat; };
 
-// GetRayHitResult (ref: Main.cpp:325-338): flat shading normal = v0.normal of the hit triangle (SURVEY A-8)
+// GetRayHitResult (ref: Main.cpp:325-338): flat shading normal = v0.normal of the hit triangle (SURVEY A-8).  A triangle object's
+// normal is its own record's (TriangleNormal, ref: Primitives.cpp:308-321): ray.tri may be left over from an earlier mesh's hit.
 template <bool COUNT>
 __device__ __forceinline__ Hit get_hit(const DevScene& sc, const Ray& ray, Counters& cnt)
 {
     Hit h;
     h.pos = ray.o + ray.d * ray.t;
     const DevObject& obj = sc.objects[ray.obj];
-    if (obj.kind == 0u) {
-        const float4 n = sc.tri_normal[obj.tri_base + ray.tri];
+    if (obj.kind == 0u || obj.kind == CGPT_OBJECT_TRIANGLE) {
+        const float4 n = sc.tri_normal[obj.tri_base + (obj.kind == 0u ? ray.tri : 0u)];
         h.normal = mk(n.x, n.y, n.z);
-        if (COUNT) cnt.hits++;
+        if (COUNT) cnt.hits += obj.kind == 0u ? 1u : 0u;                      // mesh hits only (ref: Main.cpp:332)
     } else if (obj.kind == 1u) {
         h.normal = normalize(h.pos - mk(obj.sphere_center));                 // ref: Primitives.cpp:153-156
     } else {

@@ -33,7 +33,8 @@ static constexpr uint32_t kTraceBlock = CGPT_TRACE_BLOCK;   // threads per block
                                                          // copy of the tree top; 1024: one block per CU sharing one large copy -- profiles/r02/experiments.md)
 static constexpr uint32_t kRing = 128;                   // per-wave LDS ring of work items: up to 63 left over + one 64-item block
 static constexpr uint32_t kLdsObjects = 31;              // scene objects whose trace records are mirrored in LDS (+ one end marker)
-static constexpr uint32_t kKindEnd = 3u;                 // object kind of the end marker (0 mesh, 1 sphere, 2 plane: cgpt_object_kind)
+static constexpr uint32_t kKindEnd = 0xFFFFFFFFu;        // object kind of the end marker (no cgpt_object_kind; obj_trace holds 0 mesh or
+                                                         // triangle object, 1 sphere, 2 plane: device_scene.h)
 static constexpr uint32_t kTopStride = 20;               // dwords per record in the LDS copy of the top of the tree: 80 bytes, so that
                                                          // consecutive records start 20 banks apart and 16-byte reads of random
                                                          // records spread over all 32 banks (64-byte records would use 8 of them)
@@ -556,7 +557,7 @@ __device__ __forceinline__ void leaf_step(const TravCtx& c, Trav& r, Counters& c
         next_code = next_object_code(c, r.cur_obj);
     }
 #endif
-    if (COUNT) cnt.tris++;
+    if (COUNT) cnt.tris += c.sc->objects[r.cur_obj].kind == CGPT_OBJECT_TRIANGLE ? 0u : 1u;   // BVH.cpp:76-77 only: a triangle object is no mesh
     float t_hit;
     const bool hit = intersect_triangle_flags(lt.v0, lt.e1, lt.e2, trav_origin(r), r.d, r.t, t_hit);
     r.t = hit ? t_hit : r.t;
@@ -590,7 +591,7 @@ __device__ __forceinline__ void lean_traverse(const TravCtx& c, Trav& r, Counter
             for (;;) {
                 LeafTri lt;
                 if (i < c.n_lds_tris) lt = load_leaf_tri_lds(c.tri_cache, i); else lt = load_leaf_tri(sc.tri_leaf, i);
-                if (COUNT) cnt.tris++;
+                if (COUNT) cnt.tris += sc.objects[r.cur_obj].kind == CGPT_OBJECT_TRIANGLE ? 0u : 1u;   // as in leaf_step
                 if (intersect_triangle(lt.v0, lt.e1, lt.e2, o, r.d, r.t)) {
                     r.tri = lt.tri_idx; r.obj = r.cur_obj;                    // ref: Main.cpp:313-314
                     if (!COUNT && ANY_HIT && trav_any_hit(r)) { occluded = true; break; }

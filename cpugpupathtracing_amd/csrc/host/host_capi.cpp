@@ -231,6 +231,15 @@ int cgpth_scene_add_plane(cgpth_scene* scene, const float normal[3], const float
     });
 }
 
+int cgpth_scene_add_triangle(cgpth_scene* scene, const cgpt_triangle* triangle, uint32_t mat_index)
+{
+    return Guarded<int>(-CGPT_ERR_INVALID, [&]() -> int {
+        if (!scene || !triangle) return -Fail("null argument");
+        scene->scene.objects.emplace_back("triangle", *triangle, mat_index);
+        return (int)scene->scene.objects.size() - 1;
+    });
+}
+
 int cgpth_scene_add_light(cgpth_scene* scene, uint32_t obj_index)
 {
     return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {

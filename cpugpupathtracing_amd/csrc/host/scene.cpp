@@ -59,6 +59,12 @@ cgpt_scene_desc Scene::Flatten(FlatStorage& st) const
             st.nodes.insert(st.nodes.end(), o.bvh.Nodes(), o.bvh.Nodes() + d.node_count);
             st.triangles.insert(st.triangles.end(), o.bvh.Triangles(), o.bvh.Triangles() + d.tri_count);
             st.tri_indices.insert(st.tri_indices.end(), o.bvh.TriIndices(), o.bvh.TriIndices() + d.tri_count);
+        } else if (o.kind == CGPT_OBJECT_TRIANGLE) {
+            d.kind = CGPT_OBJECT_TRIANGLE;                                   // one entry of the scene-wide triangle array
+            d.tri_offset = (uint32_t)st.triangles.size();
+            d.tri_count = 1;
+            st.triangles.push_back(o.triangle);
+            st.tri_indices.push_back(0u);                                    // keeps tri_indices parallel to triangles; unused
         } else if (o.kind == CGPT_OBJECT_SPHERE) {
             d.kind = CGPT_OBJECT_SPHERE;
             d.sphere_center[0] = o.sphere.center.x; d.sphere_center[1] = o.sphere.center.y; d.sphere_center[2] = o.sphere.center.z;

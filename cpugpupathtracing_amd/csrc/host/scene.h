@@ -68,6 +68,8 @@ struct Object {  // ref: Main.cpp:245-275
         : name(name_), mat_index(mat), has_bvh(true) { valid = bvh.BuildWith(mesh.vertices, mesh.indices, build_option, builder); }
     Object(const char* name_, const Sphere& s, uint32_t mat) : name(name_), mat_index(mat), kind(CGPT_OBJECT_SPHERE), sphere(s) {}
     Object(const char* name_, const Plane& p, uint32_t mat) : name(name_), mat_index(mat), kind(CGPT_OBJECT_PLANE), plane(p) {}
+    // Primitive(const Triangle&) (ref: Include/Primitives.h:84-89): a stand-alone triangle, no BVH
+    Object(const char* name_, const cgpt_triangle& t, uint32_t mat) : name(name_), mat_index(mat), kind(CGPT_OBJECT_TRIANGLE), triangle(t) {}
 
     std::string name;
     uint32_t mat_index = 0;
@@ -77,6 +79,7 @@ struct Object {  // ref: Main.cpp:245-275
     uint32_t kind = CGPT_OBJECT_MESH;
     Sphere sphere;
     Plane plane;
+    cgpt_triangle triangle{};
 };
 
 struct Settings {  // ref: Main.cpp:228-235

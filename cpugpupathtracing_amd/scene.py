@@ -182,6 +182,21 @@ class Scene:
     def add_plane(self, normal, point, mat_index: int) -> int:
         return N.lib().cgpth_scene_add_plane(self._h, _f3(normal), _f3(point), mat_index)
 
+    def add_triangle(self, positions, normals, mat_index: int) -> int:
+        """Primitive(const Triangle&) (ref: Include/Primitives.h:84-89): a stand-alone triangle object without a BVH.
+        positions: 3x3 (v0, v1, v2); normals: 3x3 per vertex, or one normal for all three.  The shading normal is v0's
+        (ref: Primitives.cpp:148-151).  Returns the object index."""
+        p = np.asarray(positions, dtype=np.float32).reshape(3, 3)
+        n = np.asarray(normals, dtype=np.float32)
+        n = np.broadcast_to(n.reshape(3), (3, 3)) if n.size == 3 else n.reshape(3, 3)
+        tri = N.Triangle()
+        for k, v in enumerate((tri.v0, tri.v1, tri.v2)):
+            v.pos = _f3(p[k]); v.normal = _f3(n[k])
+        rc = N.lib().cgpth_scene_add_triangle(self._h, C.byref(tri), mat_index)
+        if rc < 0:
+            raise HostError(N.lib().cgpth_last_error().decode())
+        return rc
+
     def add_light(self, obj_index: int):
         _host_check(N.lib().cgpth_scene_add_light(self._h, obj_index), "add_light")
 

@@ -24,15 +24,16 @@
 extern "C" {
 #endif
 
-#define CGPT_ABI_VERSION 2u   /* 2: cgpt_stats grew (gather_ms .. last_kernel), CGPT_KERNEL_* / CGPT_CTX_* values added since 1 */
+#define CGPT_ABI_VERSION 2u   /* 2: cgpt_stats grew (gather_ms .. last_kernel), CGPT_KERNEL_* / CGPT_CTX_* values added since 1;
+                                 CGPT_OBJECT_TRIANGLE is a new enum value only, no layout changed */
 
 enum cgpt_status {
     CGPT_OK = 0,
     CGPT_ERR_INVALID = 1,      /* bad argument / inconsistent scene description */
     CGPT_ERR_HIP = 2,          /* a HIP runtime call failed (message has hipGetErrorString) */
     CGPT_ERR_NO_SCENE = 3,     /* render before cgpt_scene_upload */
-    CGPT_ERR_UNSUPPORTED = 4,  /* valid in the reference's type system but EXCEPTs there too (e.g. AABB objects,
-                                  non-sphere primitive lights: ref Main.cpp:383, Primitives.cpp:304) */
+    CGPT_ERR_UNSUPPORTED = 4,  /* valid in the reference's type system but EXCEPTs there too (AABB objects, ref
+                                  Primitives.cpp:302-305; lights that are neither a mesh nor a sphere, ref Main.cpp:383) */
     CGPT_ERR_NO_DEVICE = 5     /* no usable gfx950 device: the product never falls back to a CPU path */
 };
 
@@ -55,16 +56,19 @@ typedef struct cgpt_material {
     uint32_t is_light;
 } cgpt_material;
 
-enum cgpt_object_kind {        /* ref: Main.cpp:245-275 (Object = mesh-with-BVH | Primitive) */
+enum cgpt_object_kind {        /* ref: Main.cpp:245-275 (Object = mesh-with-BVH | Primitive); the one other Primitive kind, AABB,
+                                  EXCEPTs in the reference (Primitives.cpp:302-305) and is CGPT_ERR_UNSUPPORTED here */
     CGPT_OBJECT_MESH = 0,
     CGPT_OBJECT_SPHERE = 1,    /* ref: Primitives.h:36-44 */
-    CGPT_OBJECT_PLANE = 2      /* ref: Primitives.h:30-34 */
+    CGPT_OBJECT_PLANE = 2,     /* ref: Primitives.h:30-34 */
+    CGPT_OBJECT_TRIANGLE = 3   /* a stand-alone triangle, no BVH: Primitive(const Triangle&), ref: Primitives.h:84-89 */
 };
 
 typedef struct cgpt_object {
     uint32_t kind;             /* cgpt_object_kind */
     uint32_t mat_index;        /* ref: Main.cpp:268 */
-    /* mesh: slices of the scene-wide arrays below (BVH internals, ref: BVH.h:46-52) */
+    /* mesh: slices of the scene-wide arrays below (BVH internals, ref: BVH.h:46-52)
+     * triangle: tri_offset names its entry of `triangles`, tri_count = 1, node_count = 0; its tri_indices entry is ignored */
     uint32_t node_offset, node_count;   /* m_nodes[0 .. m_current_node) ; node 0 is the root */
     uint32_t tri_offset, tri_count;     /* m_triangles and m_tri_indices (indices are object-local) */
     uint32_t max_depth;                 /* BVH::GetMaxDepth, ref: BVH.cpp:139-142 */

@@ -58,6 +58,9 @@ int cgpth_scene_add_mesh_device_built(cgpth_scene* scene, const cgpth_mesh* mesh
 int cgpth_scene_add_mesh_device_built_ex(cgpth_scene* scene, const cgpth_mesh* mesh, uint32_t mat_index, cgpt_ctx* ctx, int build_option);
 int cgpth_scene_add_sphere(cgpth_scene* scene, const float center[3], float radius, uint32_t mat_index);
 int cgpth_scene_add_plane(cgpth_scene* scene, const float normal[3], const float point[3], uint32_t mat_index);
+/* a stand-alone triangle object, Primitive(const Triangle&) (ref: Include/Primitives.h:84-89); returns object index.  It has no BVH
+ * (bvh_info / bvh_export / rebuild_bvh refuse it) and cannot be a light (the reference EXCEPTs, Main.cpp:383) */
+int cgpth_scene_add_triangle(cgpth_scene* scene, const cgpt_triangle* triangle, uint32_t mat_index);
 int cgpth_scene_add_light(cgpth_scene* scene, uint32_t obj_index);                            /* ref: Main.cpp:817 */
 int cgpth_scene_set_camera(cgpth_scene* scene, const float pos[3], const float view_dir[3], float fov_deg, float aspect);
 int cgpth_scene_set_settings(cgpth_scene* scene, const cgpt_settings* settings);
