@@ -107,6 +107,7 @@ __host__ __device__ inline uint32_t GlobalRow(uint32_t l, uint32_t band_first, u
 struct DevCounters {  // device-side totals, 64-bit atomics
     unsigned long long traced_rays, inner_steps, tri_tests, bvh_depth_sum, closest_hits;
     double total_energy;
+    unsigned long long chain_followers;   // wavefront later rounds: extend rays whose specular-chain leader traced them
 };
 
 struct DevRenderArgs {

@@ -80,6 +80,8 @@ struct PathState {
 };
 
 enum : uint32_t { kBounceTerminate = 1u, kBounceShadow = 2u, kBounceEnergy = 4u, kBounceBruteDone = 8u };   // kBounceEnergy: ps.energy was added to; kBounceBruteDone (wavefront shade): ps.energy is a finished TracePath's radiance
+// bits 4-5: the lobe that made the next ray when it is a function of the traced ray and its hit alone (wavefront shade: specular chains)
+enum : uint32_t { kBounceChainShift = 4u, kChainReflect = 1u, kChainRefract = 2u, kChainTir = 3u };
 
 // Processes the hit of `ray` (already traced).  On return: `ray` is the next extend ray unless kBounceTerminate is set;
 // if kBounceShadow is set, `shadow` / `pending` describe the NEE connection to trace (energy += pending when unoccluded,
@@ -133,6 +135,7 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
         ray = make_ray(hit.pos + sd * kNudge, sd, 1e34f);
         ps.throughput = ps.throughput * mat.albedo;
         ps.is_specular = true;
+        result |= kChainReflect << kBounceChainShift;
     } else if (r < mat.specular + mat.refractivity) {                         // dielectric, ref: Main.cpp:488-546
         V3 N = hit.normal;
         float cosi = clamp_std(dot(N, ray.d), -1.0f, 1.0f);
@@ -158,15 +161,19 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
                 }
                 ray = make_ray(hit.pos + rd * kNudge, rd, 1e34f);
                 ps.is_specular = true;
-            } else {
+                result |= kChainRefract << kBounceChainShift;
+            } else {                                                          // the same ray as the mirror lobe's
                 const V3 sd = reflect(ray.d, hit.normal);
                 ray = make_ray(hit.pos + sd * kNudge, sd, 1e34f);
                 ps.throughput = ps.throughput * mat.albedo;
                 ps.is_specular = true;
+                result |= kChainReflect << kBounceChainShift;
             }
+        } else {
+            // k < 0 (total internal reflection): the ray is left as it is -- t, obj, tri included -- and is traced again
+            // next iteration (SURVEY A-3)
+            result |= kChainTir << kBounceChainShift;
         }
-        // k < 0 (total internal reflection): the ray is left as it is -- t, obj, tri included -- and is traced again
-        // next iteration (SURVEY A-3)
     } else {                                                                  // diffuse, ref: Main.cpp:547-570
         V3 dd; float NdotR, pdf;
         if (st.cosine) {

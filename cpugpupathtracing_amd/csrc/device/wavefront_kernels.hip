@@ -20,8 +20,9 @@
 // byte per slot scanned by strided waves -- correct but waves own unequal numbers of live rays (59 % wave residency);
 // (3) the same with 64 partitioned head counters -- the atomics cost more than the imbalance they removed.
 // Slot entry (48 B, three float4 planes, extend slot = path id, shadow slot = cap + path id):
-//   A = {o.xyz, t_max}  B = {d.xyz, bits(depth | spec << 8)}  C = extend: hit record {bits obj, tri, bvh_depth, t} written by trace
-//   (read by trace only when the same ray is traced again after total internal reflection, SURVEY A-3) | shadow: {pending.xyz, -}.
+//   A = {o.xyz, t_max}  B = {d.xyz, bits(depth | spec << 8 | brute << 9 | chain << 10 | follower << 31)}  C = extend: hit record
+//   {bits obj, tri, bvh_depth, t} written by trace (read by trace only when the same ray is traced again after total internal
+//   reflection, SURVEY A-3) | shadow: {pending.xyz, -}.  A follower's A.w is its leader's path id instead of t_max (see wf_shade).
 // Round 0 has no generate kernel and no slot traffic for the rays: trace and shade both recompute the primary ray (ref: Main.cpp:713-716,
 // Camera::GetRay :133-140).  The reference does not jitter (SURVEY A-14), so trace walks the band's pixels, not the paths: one ray per
 // pixel, its 16-byte hit record in px_hit[pixel], counted once per sample.  Shade reads the record of the path's pixel and initialises
@@ -88,7 +89,54 @@ struct WfDev {
     uint32_t trace_chunk;              // same for a trace wave
     uint32_t retire_misses;            // later rounds: trace leaves one byte per extend ray (hit or not) and shade takes only the hits (off for the debug views)
     uint32_t rot_trace[2], rot_shade;  // rotation of the wave order from one row of blocks to the next ([FIRST] for trace): see next_block()
+    unsigned long long* spec_tab;      // specular-chain election (wf_shade): spec_keys entries {bits(epoch << 16 | chain), leader path id << 32} per
+                                       // pixel of the band; null: no election (the COUNT and TracePath renders, spec_dedupe 0)
+    uint32_t spec_keys;                // entries per pixel
+    uint32_t spec_epoch;               // 1..0xFFFF, new for every shade launch: entries of other epochs are free
 };
+
+// Specular chains.  The reference does not jitter (SURVEY A-14), so all samples of a pixel share the primary ray and its hit, and
+// after a mirror or dielectric bounce the next ray is a function of the traced ray and its hit alone: the RNG only picks WHICH of
+// reflect (the mirror lobe and the dielectric's reflection make the same ray), refract or total internal reflection (the same ray
+// again) follows.  So within a batch the ray of a path whose bounces were all specular is fixed by (pixel, chain): the base-3 code of
+// its choices with a leading 1 (1 at the primary hit; 0 = not a chain: a diffuse bounce, a code past 16 bits).  wf_shade elects one
+// leader per (pixel, chain) among the rays it emits; the followers stay in the extend list (lists, plans and bands are unchanged),
+// trace skips them, and the next shade reads the leader's hit record (C and hit_flag of the leader's slot: neither changes between
+// that trace and the next).  Each follower still shades with its own RNG stream, throughput and Beer factor.
+static constexpr uint32_t kChainShift = 10u, kChainMax = 0xFFFFu, kFollowerBit = 0x80000000u, kNoLeader = 0xFFFFFFFFu;
+
+// Called by the lanes that emit an extend ray; `chain` = 0: no election for this lane.  Returns the path id of the leader of the
+// lane's (pixel, chain) -- the lane's own when it leads -- or kNoLeader when the pixel's entries are all taken (traced as usual).
+// Inside the wave the first lane of every distinct key probes for all lanes of that key (with pixel-major ids a wave holds a few
+// keys); across waves one load + CAS per probed entry.
+__device__ __forceinline__ uint32_t elect_chain_leader(const WfDev& wf, uint32_t chain, uint32_t pid)
+{
+    const bool want = chain != 0u;
+    uint32_t pixel = 0;
+    if (want) { uint32_t sample_unused; path_split(wf.g, pid, sample_unused, pixel); }
+    uint32_t src = lane_id();                                                 // the lane that probes for this lane's key
+    for (unsigned long long pend = __builtin_amdgcn_ballot_w64(want); pend != 0ull;) {
+        const uint32_t f = (uint32_t)__builtin_ctzll(pend);
+        const bool m = want && pixel == __builtin_amdgcn_readlane(pixel, f) && chain == __builtin_amdgcn_readlane(chain, f);
+        if (m) src = f;
+        pend &= ~__builtin_amdgcn_ballot_w64(m);
+    }
+    uint32_t leader = kNoLeader;
+    if (want && src == lane_id()) {
+        unsigned long long* const row = wf.spec_tab + (size_t)pixel * wf.spec_keys;
+        const uint32_t tag = (wf.spec_epoch << 16) | chain;
+        const unsigned long long mine = ((unsigned long long)pid << 32) | tag;
+        for (uint32_t k = 0; k < wf.spec_keys; ++k) {
+            unsigned long long cur = __hip_atomic_load(&row[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            while (((uint32_t)cur >> 16) != wf.spec_epoch) {                  // free: claim it (an entry changes once per epoch)
+                const unsigned long long prev = atomicCAS(&row[k], cur, mine);
+                cur = prev == cur ? mine : prev;
+            }
+            if ((uint32_t)cur == tag) { leader = (uint32_t)(cur >> 32); break; }
+        }
+    }
+    return __shfl(leader, (int)src);
+}
 
 // ---- K2/K4 trace: persistent closest-hit traversal with per-lane refill ------------------------------------------------
 // `first_round`: the list is the identity over the PIXELS of the band (not the paths) and there are no shadow rays yet.  The reference
@@ -129,6 +177,7 @@ __global__ void __launch_bounds__(kTraceBlock, (!COUNT && !FIRST) ? CGPT_TRACE_W
     r.obj = kNoHit; r.tri = 0; r.depth = 0; r.cur_obj = 0; r.code = kIdle; r.sp = 0; r.fast_levels = kLdsStackLevels;
     uint32_t slot_of_lane = 0;
     uint32_t wave_rays = 0;                                                   // wave-uniform: rays this wave started (later rounds)
+    uint32_t wave_followers = 0;                                              // wave-uniform: of those, followers of a specular chain (not traced)
     Counters cnt = { 0, 0, 0, 0, 0 };
     uint32_t ph_inner = 0, ph_leaf = 0, ph_leaf_lanes = 0, ph_obj = 0, ph_obj_lanes = 0, ph_votes = 0, ph_refills = 0;   // wave-uniform, COUNT only
 #ifdef CGPT_PHASE_CYCLES
@@ -201,6 +250,7 @@ __global__ void __launch_bounds__(kTraceBlock, (!COUNT && !FIRST) ? CGPT_TRACE_W
         if (n_need && ring_count) {
             const uint32_t take = min(n_need, ring_count);
             const uint32_t rank = rank_in_mask(need);
+            bool followed = false;
             if (r.code == kIdle && rank < take) {
                 const uint32_t slot = ring[ring_count - 1u - rank];
                 slot_of_lane = slot;
@@ -213,7 +263,10 @@ __global__ void __launch_bounds__(kTraceBlock, (!COUNT && !FIRST) ? CGPT_TRACE_W
                 } else {
                     const float4 a = ld_stream(&wf.A[slot]), b = ld_stream(&wf.B[slot]);
                     o = mk(a.x, a.y, a.z); t = a.w; d = mk(b.x, b.y, b.z);
-                    if (slot < wf.cap && t != 1e34f) {                        // the same ray again after total internal reflection:
+                    if (!COUNT && slot < wf.cap && (__float_as_uint(b.w) & kFollowerBit)) {   // its leader traces this ray (wf_shade: specular chains)
+                        ok = false; followed = true;
+                        if (wf.retire_misses) wf.hit_flag[slot] = 1;          // shade reads the leader's hit or miss
+                    } else if (slot < wf.cap && t != 1e34f) {                 // the same ray again after total internal reflection:
                         const float4 c = ld_stream(&wf.C[slot]);              // it keeps its previous hit as payload (SURVEY A-3)
                         obj = __float_as_uint(c.x); tri = __float_as_uint(c.y); depth = __float_as_uint(c.z);
                     }
@@ -227,6 +280,7 @@ __global__ void __launch_bounds__(kTraceBlock, (!COUNT && !FIRST) ? CGPT_TRACE_W
             __builtin_amdgcn_wave_barrier();
             ring_count -= take;
             if (!first_round) wave_rays += take;
+            if (!COUNT && !first_round) wave_followers += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(followed));
         }
         // Done when nothing is in flight and nothing is left to fetch.  Nothing in flight alone is not enough: every id just handed
         // out may have been padding of an edge tile (round 0: a padded row of a tile; later rounds never list one); the step loop below
@@ -306,6 +360,7 @@ __global__ void __launch_bounds__(kTraceBlock, (!COUNT && !FIRST) ? CGPT_TRACE_W
     const uint32_t per_ray = first_round ? wf.g.n_samples : 1u;
     if (first_round) wave_add_u64(&counters->traced_rays, cnt.rays, per_ray);
     else if (lane_id() == 0u && wave_rays) atomicAdd(&counters->traced_rays, (unsigned long long)wave_rays);
+    if (!COUNT && !first_round && lane_id() == 0u && wave_followers) atomicAdd(&counters->chain_followers, (unsigned long long)wave_followers);
     if (COUNT) {
         wave_add_u64(&counters->inner_steps, cnt.inner, per_ray);
         wave_add_u64(&counters->tri_tests, cnt.tris, per_ray);
@@ -326,6 +381,7 @@ template <bool COUNT, bool FIRST, bool BRUTE = false>
 __global__ void __launch_bounds__(256, CGPT_SHADE_WAVES_PER_SIMD) wf_shade(const DevRenderArgs args, const WfDev wf, uint32_t batch_first)
 {
     constexpr bool first_round = FIRST;
+    constexpr bool kChains = !COUNT && !BRUTE;                                // specular chains are tracked (and elected when wf.spec_tab is set)
     const DevScene& sc = args.scene;
     const uint32_t n_ext = first_round ? wf.n_paths : wf.plan[0];
     const uint32_t n_blocks = (n_ext + 63u) / 64u;
@@ -407,12 +463,15 @@ __global__ void __launch_bounds__(256, CGPT_SHADE_WAVES_PER_SIMD) wf_shade(const
             PathState ps;
             bool is_pixel = true;
             bool brute_path = false;                                          // this path runs TracePath
+            uint32_t chain = 0;                                               // kChains: the specular-chain code of the path's ray
+            bool followed = false;                                            // c is the leader's: this path's own C slot is stale
             if (first_round) {                                                // primary ray and fresh path state from the path id
                 uint32_t px = 0, pixel = 0;
                 is_pixel = primary_ray(args, wf.g, pid, batch_first, ray, ps.rng, px, pixel);
                 c = wf.px_hit[pixel];                                         // the pixel's hit, one record for all its samples (cached:
                                                                               // with pixel-major ids a wave's lanes share a few records)
                 ps.throughput = mk(1.0f); ps.energy = mk(0.0f); ps.depth = 0; ps.is_specular = false;
+                chain = 1u;
                 if (BRUTE) brute_path = args.settings.render_mode == 1u || (args.settings.render_mode == 0u && px < args.width / 2u);   // ref: Main.cpp:719-729
             } else {
                 const float4 a = ld_stream(&wf.A[pid]), b = ld_stream(&wf.B[pid]);
@@ -423,7 +482,13 @@ __global__ void __launch_bounds__(256, CGPT_SHADE_WAVES_PER_SIMD) wf_shade(const
                 const uint32_t fl = __float_as_uint(b.w);
                 ps.depth = fl & 0xFFu; ps.is_specular = (fl & 0x100u) != 0u;
                 if (BRUTE) brute_path = (fl & 0x200u) != 0u;
-                c = ld_stream(&wf.C[pid]);
+                if (kChains) chain = (fl >> kChainShift) & kChainMax;
+                if (kChains && (fl & kFollowerBit)) {                         // the leader's hit is this ray's
+                    const uint32_t lead = __float_as_uint(a.w);
+                    followed = true;
+                    if (!wf.retire_misses || wf.hit_flag[lead]) c = ld_stream(&wf.C[lead]);
+                    else { c.x = __uint_as_float(kNoHit); c.y = 0.0f; c.z = 0.0f; c.w = 0.0f; }   // the leader left the scene: a miss
+                } else c = ld_stream(&wf.C[pid]);
             }
             ray.t = c.w; ray.obj = __float_as_uint(c.x); ray.tri = __float_as_uint(c.y); ray.bvh_depth = __float_as_uint(c.z);
             shadow = ray;
@@ -487,10 +552,21 @@ __global__ void __launch_bounds__(256, CGPT_SHADE_WAVES_PER_SIMD) wf_shade(const
                 float4 na, nb;
                 na.x = ray.o.x; na.y = ray.o.y; na.z = ray.o.z; na.w = ray.t;    // 1e34 for a fresh ray, the hit t for a re-traced one
                 nb.x = ray.d.x; nb.y = ray.d.y; nb.z = ray.d.z;
-                nb.w = __uint_as_float((ps.depth & 0xFFu) | (ps.is_specular ? 0x100u : 0u) | ((BRUTE && brute_path) ? 0x200u : 0u));
+                uint32_t fl = (ps.depth & 0xFFu) | (ps.is_specular ? 0x100u : 0u) | ((BRUTE && brute_path) ? 0x200u : 0u);
+                if (kChains) {
+                    const uint32_t choice = (flags >> kBounceChainShift) & 3u;   // 0: diffuse, else 1 + base-3 digit
+                    chain = choice != 0u && chain != 0u && chain <= (kChainMax - 2u) / 3u ? chain * 3u + choice - 1u : 0u;
+                    fl |= chain << kChainShift;
+                    if (wf.spec_tab) {
+                        const uint32_t lead = elect_chain_leader(wf, chain, pid);
+                        if (lead != kNoLeader && lead != pid) { na.w = __uint_as_float(lead); fl |= kFollowerBit; }
+                    }
+                }
+                nb.w = __uint_as_float(fl);
                 st_stream(&wf.A[pid], na); st_stream(&wf.B[pid], nb);         // C keeps the hit record (payload of a re-traced ray)
-                if (first_round && ray.t != 1e34f) st_stream(&wf.C[pid], c);  // round 0 kept it per pixel: the re-traced ray's payload goes to
-                                                                              // its slot (trace reads C exactly when A.w != 1e34)
+                if ((first_round || followed) && ray.t != 1e34f) st_stream(&wf.C[pid], c);   // round 0 kept it per pixel, a follower's came from
+                                                                              // its leader: the re-traced ray's payload goes to its slot (trace reads
+                                                                              // C exactly when A.w != 1e34)
                 key_ext = (ray.d.x < 0.0f ? 1u : 0u) | (ray.d.y < 0.0f ? 2u : 0u) | (ray.d.z < 0.0f ? 4u : 0u);
             }
             if (emit_sh) {                                                    // NEE connection, slot cap + pid
@@ -714,6 +790,9 @@ struct WfTuning {               // defaults measured on MI355X (profiles/r01); o
     uint32_t sort = 0;                // 1: bin every round's ray lists by direction octant (measured in profiles/r02/k7_sort.md)
     uint32_t bands = 32;              // > 1: every round's ray lists ordered by image band (wf_shade: "Image bands"); at most kMaxKeys.  C3: 1 band 89.1-89.4 ms,
                                       // 8: 87.3-87.6, 16: 88.0-88.2, 32: 87.1-87.5, 64: 87.8-88.4 (profiles/r03/image_bands.md)
+    uint32_t spec_dedupe = 1;         // later rounds trace one ray per (pixel, specular chain) and batch (wf_shade: "Specular chains")
+    uint32_t spec_keys = 8;           // election entries per pixel; a ray whose pixel has none left is traced as usual
+    uint32_t spec_epochs = 0xFFFF;    // shade launches between two clears of a pool's election table (the 16-bit tag's range; fewer: tests)
 };
 
 static uint32_t Gcd(uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; }
@@ -741,6 +820,8 @@ struct WfHost {
     hipEvent_t acc_done[kMaxPools] = {};
     hipEvent_t begin = nullptr;
     uint32_t alloc_cap = 0, alloc_segs = 0, alloc_seg_cap = 0, alloc_pools = 0, alloc_overflow = 0, alloc_brute_levels = 0, alloc_pixels = 0;
+    size_t alloc_spec = 0;                       // entries of every pool's spec_tab (0: none)
+    uint32_t spec_epoch[kMaxPools] = {};         // last epoch used in each pool's spec_tab
     bool alloc_sort = false;
     uint32_t n_cus = 0;
     uint32_t trace_blocks_per_cu[2][2] = {}, shade_blocks_per_cu[2][2] = {};   // trace: [COUNT][FIRST]; shade: [COUNT][BRUTE]
@@ -755,13 +836,13 @@ static void WfRelease(WfHost* h)
     for (uint32_t p = 0; p < kMaxPools; ++p) {
         WfDev& d = h->dev[p];
         (void)hipFree(d.A); (void)hipFree(d.B); (void)hipFree(d.C);
-        (void)hipFree(d.st_tp); (void)hipFree(d.st_en); (void)hipFree(d.hit_flag); (void)hipFree(d.brute); (void)hipFree(d.px_hit);
+        (void)hipFree(d.st_tp); (void)hipFree(d.st_en); (void)hipFree(d.hit_flag); (void)hipFree(d.brute); (void)hipFree(d.px_hit); (void)hipFree(d.spec_tab);
         (void)hipFree(d.list_ext); (void)hipFree(d.list_sh); (void)hipFree(d.seg_ext); (void)hipFree(d.seg_sh);
         (void)hipFree(d.seg_count); (void)hipFree(d.seg_prefix); (void)hipFree(d.plan); (void)hipFree(d.stack_overflow);
         (void)hipFree(d.seg_key_ext); (void)hipFree(d.seg_key_sh);
         d = WfDev{};
     }
-    h->alloc_cap = 0; h->alloc_segs = 0; h->alloc_seg_cap = 0; h->alloc_pools = 0; h->alloc_overflow = 0; h->alloc_sort = false; h->alloc_brute_levels = 0; h->alloc_pixels = 0;
+    h->alloc_cap = 0; h->alloc_segs = 0; h->alloc_seg_cap = 0; h->alloc_pools = 0; h->alloc_overflow = 0; h->alloc_sort = false; h->alloc_brute_levels = 0; h->alloc_pixels = 0; h->alloc_spec = 0;
 }
 
 void WavefrontFree(void* state)
@@ -817,6 +898,8 @@ static const KnobDesc kKnobs[] = {
     { "shadow_any_hit", &WfTuning::shadow_any_hit, 0, 1 },     { "trace_events", &WfTuning::trace_events, 0, 1 },
     { "sort", &WfTuning::sort, 0, 1 },                     { "path_order", &WfTuning::path_order, 0, 2 },                     { "retire_misses", &WfTuning::retire_misses, 0, 1 },
     { "lds_tris", &WfTuning::lds_tris, 0, 1 },             { "first_lean", &WfTuning::first_lean, 0, 1 },                     { "bands", &WfTuning::bands, 1, kMaxKeys },             { "bands_min_paths", &WfTuning::bands_min_paths, 0, 0x7FFFFFFF },
+    { "spec_dedupe", &WfTuning::spec_dedupe, 0, 1 },       { "spec_keys", &WfTuning::spec_keys, 1, 16 },
+    { "spec_epochs", &WfTuning::spec_epochs, 1, 0xFFFF },
 };
 
 static WfHost* WfGetHost(cgpt_ctx* ctx)
@@ -944,10 +1027,12 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
     // of HBM is what makes that possible: a pool is ~150 B per path, 128 spp of a 1080p frame is 265 M paths = 40 GB per pool.
     // So: the largest power-of-two batch up to max_batch that fits the pool limit and leaves at least two batches (two
     // pools overlap each other's tails), within a memory budget of half the free HBM (at most budget_gib).
+    const bool chains = h->tune.spec_dedupe && !count && !brute;             // specular-chain election (wf_shade)
+    const size_t spec_entries = chains ? (size_t)n_pixels * h->tune.spec_keys : 0u;
     const size_t kBytesPerPath = 160 + 32 * (size_t)brute_levels;             // slots 96, state 32, lists 8, segments ~8-16; TracePath levels 32 each
     size_t free_b = 0, total_b = 0;
     WF_TRY(hipMemGetInfo(&free_b, &total_b));
-    const size_t held = (size_t)h->alloc_pools * h->alloc_cap * (160 + 32 * (size_t)h->alloc_brute_levels);
+    const size_t held = (size_t)h->alloc_pools * ((size_t)h->alloc_cap * (160 + 32 * (size_t)h->alloc_brute_levels) + h->alloc_spec * sizeof(unsigned long long));
     const size_t budget = std::min<size_t>((size_t)h->tune.budget_gib << 30, (free_b + held) / 2);
     uint32_t batch = h->tune.batch;
     if (batch == 0) {
@@ -960,7 +1045,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
         for (;;) {
             cap = n_pixels * batch;
             n_batches = (args_in.n_samples + batch - 1u) / batch;
-            const uint32_t afford = (uint32_t)std::min<size_t>(kMaxPools, budget / ((size_t)cap * kBytesPerPath));
+            const uint32_t afford = (uint32_t)std::min<size_t>(kMaxPools, budget / ((size_t)cap * kBytesPerPath + spec_entries * sizeof(unsigned long long)));
             n_pools = std::max(1u, std::min({ h->tune.pools, n_batches, afford }));
             if (batch == 1u || (afford >= 1u && n_pools >= std::min({ 2u, n_batches, h->tune.pools }))) break;
             batch /= 2u;                                                      // smaller batches: room for a second pool
@@ -968,7 +1053,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
         const bool banded = !h->tune.sort && h->tune.bands > 1u && cap >= h->tune.bands_min_paths;   // (the last, shorter batch of a render may still fall below: it keeps this chunk)
         shade_chunk = banded ? h->tune.shade_chunk_banded : h->tune.shade_chunk;
         seg_cap = ((((cap + 63u) / 64u + shade_chunk - 1u) / shade_chunk + min_shade_waves - 1u) / min_shade_waves) * shade_chunk * 64u;   // whole chunks per wave
-        if (h->alloc_overflow >= overflow_words && h->alloc_cap >= cap && h->alloc_segs >= n_segs && h->alloc_seg_cap >= seg_cap && h->alloc_pools >= n_pools && (!h->tune.sort || h->alloc_sort) && h->alloc_brute_levels >= brute_levels && h->alloc_pixels >= n_pixels) break;
+        if (h->alloc_overflow >= overflow_words && h->alloc_cap >= cap && h->alloc_segs >= n_segs && h->alloc_seg_cap >= seg_cap && h->alloc_pools >= n_pools && (!h->tune.sort || h->alloc_sort) && h->alloc_brute_levels >= brute_levels && h->alloc_pixels >= n_pixels && h->alloc_spec >= spec_entries) break;
         WF_TRY(hipDeviceSynchronize());
         WfRelease(h);
         const size_t q = 2 * (size_t)cap * sizeof(float4);
@@ -991,10 +1076,15 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
             if (h->tune.sort) { get((void**)&d.seg_key_ext, (size_t)n_segs * seg_cap); get((void**)&d.seg_key_sh, (size_t)n_segs * seg_cap); }
             get((void**)&d.plan, (2 + 2 * (size_t)kMaxKeys) * sizeof(uint32_t));
             get((void**)&d.stack_overflow, (size_t)overflow_words * sizeof(uint32_t));
+            if (spec_entries) {                                               // epoch 0 is never current: all entries free
+                get((void**)&d.spec_tab, spec_entries * sizeof(unsigned long long));
+                if (err == hipSuccess) err = hipMemset(d.spec_tab, 0, spec_entries * sizeof(unsigned long long));
+            }
+            h->spec_epoch[p] = 0;
         }
         if (err == hipSuccess) {
             h->alloc_cap = cap; h->alloc_segs = n_segs; h->alloc_seg_cap = seg_cap; h->alloc_pools = n_pools; h->alloc_overflow = overflow_words; h->alloc_sort = h->tune.sort != 0u; h->alloc_brute_levels = brute_levels;
-            h->alloc_pixels = n_pixels;
+            h->alloc_pixels = n_pixels; h->alloc_spec = spec_entries;
             break;
         }
         (void)hipGetLastError();                                              // out of memory: give everything back and ask for half
@@ -1049,6 +1139,8 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
             wf.band_magic = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, (((uint64_t)wf.n_bands << 32) + wf.n_paths - 1u) / wf.n_paths);   // ceil(2^32 * bands / paths)
         }
         wf.retire_misses = h->tune.retire_misses && args_in.settings.debug_mode == 0u ? 1u : 0u;
+        if (!chains) wf.spec_tab = nullptr;
+        wf.spec_keys = h->tune.spec_keys;
         if (k < n_pools) WF_TRY(hipMemsetAsync(wf.seg_count, 0, 2 * (size_t)kMaxKeys * wf.n_segs * sizeof(uint32_t), st));
         for (uint32_t r = 0; r < rounds; ++r) {
             const bool first = r == 0u;
@@ -1061,6 +1153,14 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
             if (h->tune.trace_events) WF_TRY(hipEventRecord(h->trace_ev[h->trace_ev_used++], st));
             ++launches;
             if (r + 1u < rounds) {
+                if (wf.spec_tab) {                                            // a fresh epoch frees every entry; after spec_epochs of them, clear
+                    if (++h->spec_epoch[p] > h->tune.spec_epochs) {           // the whole table: entries past this call's n_pixels * spec_keys
+                                                                              // hold tags of the old epochs too, written by larger layouts
+                        WF_TRY(hipMemsetAsync(wf.spec_tab, 0, h->alloc_spec * sizeof(unsigned long long), st));
+                        h->spec_epoch[p] = 1u;
+                    }
+                    wf.spec_epoch = h->spec_epoch[p];
+                }
                 if (brute) {
                     if (count && first) hipLaunchKernelGGL((wf_shade<true, true, true>), shade_grid, block, 0, st, args, wf, bfirst);
                     else if (count) hipLaunchKernelGGL((wf_shade<true, false, true>), shade_grid, block, 0, st, args, wf, bfirst);

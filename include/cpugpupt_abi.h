@@ -157,7 +157,8 @@ typedef struct cgpt_stats {
        identical, SURVEY A-14) are a different population from the later rounds': their share of dominant_ms / dominant_launches */
     double dominant_round0_ms;
     uint32_t dominant_round0_launches;
-    uint32_t reserved_;
+    uint32_t chain_followers;      /* wavefront later-round extend rays not traced because the leader of their pixel's specular chain
+                                      traced the same ray (the election of wavefront_kernels.hip); saturates at 2^32 - 1 */
 } cgpt_stats;
 
 typedef struct cgpt_ctx cgpt_ctx;
