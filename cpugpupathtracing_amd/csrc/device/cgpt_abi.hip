@@ -373,16 +373,6 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
         else { q0.y = d.plane_normal[0]; q0.z = d.plane_normal[1]; q0.w = d.plane_normal[2]; q1.x = d.plane_point[0]; q1.y = d.plane_point[1]; q1.z = d.plane_point[2]; }
     }
 
-#ifdef CGPT_NODE_SOA
-    {   // experiment build: component planes instead of 64-byte records (rt_device.hpp: load_pair_soa)
-        std::vector<float4> planes(pairs.size());
-        const float* src = reinterpret_cast<const float*>(pairs.data());
-        float* dst = reinterpret_cast<float*>(planes.data());
-        for (uint32_t r = 0; r < n_records; ++r)
-            for (uint32_t c = 0; c < 16u; ++c) dst[(size_t)c * n_records + r] = src[(size_t)r * 16u + c];
-        pairs.swap(planes);
-    }
-#endif
     FreeScene(ctx);
     int rc;
     if ((rc = UploadArray(ctx, &ctx->d_node_pairs, pairs)) != CGPT_OK) return rc;

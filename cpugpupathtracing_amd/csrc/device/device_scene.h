@@ -87,7 +87,7 @@ struct DevScene {
     uint32_t n_lights;
     uint32_t stack_depth;  // LDS stack entries per lane (max BVH depth + 1 over all meshes)
     uint32_t n_top_records; // records [0, n_top_records) are the breadth-first top of the trees
-    uint32_t n_pair_records; // child-pair records in node_pairs (the plane stride of the -DCGPT_NODE_SOA experiment build)
+    uint32_t n_pair_records; // child-pair records in node_pairs (read by no kernel; kept so the argument layout stays put)
     uint32_t n_small_tris;  // tri_leaf records [0, n_small_tris) are the triangles of the scene's small meshes (device_scene.h "record order")
 };
 

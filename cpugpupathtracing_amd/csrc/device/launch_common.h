@@ -1,0 +1,144 @@
+// launch_common.h -- host plumbing shared by the voted launchers, LaunchWavefront (wavefront_kernels.hip) and LaunchPersistent
+// (persistent_kernel.hip).  Host code only.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cctype>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+
+#include "cpugpupt_abi.h"
+
+namespace cgpt {
+
+int CtxFail(cgpt_ctx* ctx, int code, const char* fmt, ...);
+
+// a HIP call of a launcher: on failure the context's error names the call and the launcher returns -1
+#define LAUNCH_TRY(expr)                                                                                 \
+    do {                                                                                                 \
+        hipError_t e_ = (expr);                                                                          \
+        if (e_ != hipSuccess) { CtxFail(ctx, CGPT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); return -1; } \
+    } while (0)
+
+// One knob table per launcher, for cgpt_set_tuning (per context, any time between renders) and the environment (process-wide
+// defaults, read when a context first needs the launcher's state: prefix + name in upper case, clamped into the range)
+template <typename T> struct Knob { const char* name; uint32_t T::*field; uint32_t lo, hi; };
+
+template <typename T, size_t N> void LoadKnobsFromEnv(const Knob<T> (&knobs)[N], const char* prefix, T& tune)
+{
+    for (const Knob<T>& k : knobs) {
+        char env[64];
+        size_t n = 0;
+        for (const char* c = prefix; *c && n + 1 < sizeof(env); ++c) env[n++] = *c;
+        for (const char* c = k.name; *c && n + 1 < sizeof(env); ++c) env[n++] = (char)toupper((unsigned char)*c);
+        env[n] = 0;
+        const char* v = getenv(env);
+        if (v && *v) tune.*(k.field) = (uint32_t)std::min<long>(std::max<long>(strtol(v, nullptr, 10), k.lo), k.hi);
+    }
+}
+
+template <typename T, size_t N> const Knob<T>* FindKnob(const Knob<T> (&knobs)[N], const char* name)
+{
+    for (const Knob<T>& k : knobs)
+        if (strcmp(k.name, name) == 0) return &k;
+    return nullptr;
+}
+
+template <typename T> int SetKnob(cgpt_ctx* ctx, const Knob<T>* k, T& tune, const char* name, uint32_t value)
+{
+    if (!k) return CtxFail(ctx, CGPT_ERR_INVALID, "unknown tuning knob '%s'", name);
+    if (value < k->lo || value > k->hi) return CtxFail(ctx, CGPT_ERR_INVALID, "tuning knob %s: %u outside [%u, %u]", name, value, k->lo, k->hi);
+    tune.*(k->field) = value;
+    return CGPT_OK;
+}
+
+inline hipError_t QueryCuCount(uint32_t& n_cus)                              // once per launcher state
+{
+    if (n_cus) return hipSuccess;
+    int dev = 0, cus = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess) n_cus = (uint32_t)cus;
+    return e;
+}
+
+// resident blocks per CU (at least 1) of n kernels of a table with `lds` bytes of dynamic LDS; beyond the default 48 KiB a kernel opts in
+template <typename F> hipError_t QueryOccupancy(const F* kernels, uint32_t* blocks_per_cu, size_t n, int block_threads, size_t lds)
+{
+    hipError_t e = hipSuccess;
+    for (size_t i = 0; i < n && e == hipSuccess; ++i) {
+        int b = 0;
+        if (lds > 48u * 1024u) e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernels[i]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kernels[i], block_threads, lds);
+        blocks_per_cu[i] = (uint32_t)std::max(1, b);
+    }
+    return e;
+}
+
+// a device buffer that only grows; reallocating waits for the device first (earlier launches may still use the old one)
+template <typename T> struct DevBuf { T* p = nullptr; size_t n = 0; };
+
+template <typename T> hipError_t Grow(DevBuf<T>& b, size_t n)
+{
+    if (b.n >= n) return hipSuccess;
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) { (void)hipFree(b.p); b.p = nullptr; b.n = 0; e = hipMalloc((void**)&b.p, n * sizeof(T)); }
+    if (e == hipSuccess) b.n = n;
+    return e;
+}
+
+// hipEvent pairs around the launches of the last render, grow-only: ReserveEvents before it, hipEventRecord(NextEvent()) before and
+// after each launch, ForEachPair once its device work has completed
+struct EventPairs { hipEvent_t* ev = nullptr; uint32_t cap = 0, used = 0; };
+
+inline int ReserveEvents(cgpt_ctx* ctx, EventPairs& e, uint32_t n)
+{
+    if (e.cap < n) {
+        hipEvent_t* grown = static_cast<hipEvent_t*>(realloc(e.ev, (size_t)n * sizeof(hipEvent_t)));
+        if (!grown) { CtxFail(ctx, CGPT_ERR_INVALID, "out of host memory"); return -1; }
+        e.ev = grown;
+        for (; e.cap < n; ++e.cap) LAUNCH_TRY(hipEventCreate(&e.ev[e.cap]));
+    }
+    e.used = 0;
+    return 0;
+}
+
+inline hipEvent_t NextEvent(EventPairs& e) { return e.ev[e.used++]; }
+
+template <typename F> void ForEachPair(EventPairs& e, F&& each)             // each(pair index, ms) of every pair that could be timed
+{
+    for (uint32_t i = 0; i + 1u < e.used; i += 2u) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, e.ev[i], e.ev[i + 1u]) == hipSuccess) each(i / 2u, ms);
+    }
+    e.used = 0;
+}
+
+inline void FreeEvents(EventPairs& e)
+{
+    for (uint32_t i = 0; i < e.cap; ++i) (void)hipEventDestroy(e.ev[i]);
+    free(e.ev);
+    e = EventPairs{};
+}
+
+// CGPT_WF_PROFILE: step statistics of the COUNT kernels (of every kernel in the CGPT_PHASE_CYCLES diagnostic build), allocated on
+// first use and zeroed before every render; PhaseStatsArg is what the kernels of a render get
+#ifdef CGPT_PHASE_CYCLES
+inline bool PhaseStatsOn(bool) { return true; }
+#else
+inline bool PhaseStatsOn(bool count) { return count; }
+#endif
+inline unsigned long long* PhaseStatsArg(unsigned long long* stats, bool count) { return PhaseStatsOn(count) ? stats : nullptr; }
+
+inline hipError_t ResetPhaseStats(unsigned long long*& stats, size_t words, bool count, hipStream_t stream)
+{
+    hipError_t e = hipSuccess;
+    if (PhaseStatsOn(count) && getenv("CGPT_WF_PROFILE") != nullptr && !stats) e = hipMalloc((void**)&stats, words * sizeof(unsigned long long));
+    if (e == hipSuccess && stats) e = hipMemsetAsync(stats, 0, words * sizeof(unsigned long long), stream);
+    return e;
+}
+
+}  // namespace cgpt

@@ -27,7 +27,7 @@ extern __shared__ uint32_t lds_stack[];
 // live in per-lane scratch, so the plain TracePathAdvanced instantiation carries no scratch at all.
 // Block shape: 256 threads = a 16x16-pixel tile (the reference's job size, ref: Main.cpp:705-711), or -- one-sample calls -- 64 threads =
 // one 8x8 tile per single-wave block: the wave's slot and its LDS are free the moment its own longest path ends instead of its block's,
-// and the dispatcher places single waves (1080p, one sample: 1.71 -> 1.5x ms, profiles/r03/one_sample.md).
+// and the dispatcher places single waves (1080p, one sample: 1.71 -> 1.68 ms, profiles/r03/one_sample.md).
 template <bool COUNT, bool BRUTE>
 __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
 {
@@ -128,9 +128,6 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
             } else {
                 args.pixels[local_index] = vec4_to_uint(last_color.x, last_color.y, last_color.z);
             }
-#ifdef CGPT_STEP_MAP
-            if (COUNT) args.pixels[local_index] = cnt.inner + cnt.tris;       // diagnostic build (scripts/gpu_step_map.py): dependent fetches of this pixel's paths
-#endif
         }
     }
 
@@ -146,13 +143,18 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
 }
 
 // host-side launcher (the ABI translation unit calls plain C++ functions, kernels stay in this one)
-static uint32_t MegakernelBlockThreads(const DevRenderArgs& args) { return args.n_samples == 1u ? 64u : 256u; }
+// threads per block, for the launch and the occupancy query alike
+static uint32_t MegakernelBlockThreads(const DevRenderArgs& args)
+{
+    static const uint32_t env_block = getenv("CGPT_MEGA_BLOCK") ? (uint32_t)atoi(getenv("CGPT_MEGA_BLOCK")) : 0u;   // experiments: 64 or 256 for every call
+    if (env_block == 64u || env_block == 256u) return env_block;
+    return args.n_samples == 1u ? 64u : 256u;
+}
 
 hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, hipStream_t stream)
 {
     const bool brute = args.settings.render_mode != 2u;
-    static const uint32_t env_block = getenv("CGPT_MEGA_BLOCK") ? (uint32_t)atoi(getenv("CGPT_MEGA_BLOCK")) : 0u;   // experiments: 64 or 256 for every call
-    const uint32_t bt = env_block == 64u || env_block == 256u ? env_block : MegakernelBlockThreads(args);
+    const uint32_t bt = MegakernelBlockThreads(args);
     const uint32_t edge = bt == 64u ? 8u : 16u;
     const uint32_t tiles_x = (args.width + edge - 1u) / edge, tiles_y = (args.n_rows + edge - 1u) / edge;
     const dim3 grid(tiles_x * tiles_y), block(bt);

@@ -14,11 +14,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cctype>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <new>
 
 #include "cpugpupt_abi.h"
@@ -28,6 +26,7 @@
 #include "shade_device.hpp"
 #include "trace_steps.hpp"
 #include "accumulate.hpp"
+#include "launch_common.h"
 
 namespace cgpt {
 
@@ -37,7 +36,6 @@ hipStream_t CtxStream(cgpt_ctx* ctx);
 void** CtxPersistentSlot(cgpt_ctx* ctx);
 hipEvent_t CtxStartEvent(cgpt_ctx* ctx);
 void PersistentFree(void* state);
-int CtxFail(cgpt_ctx* ctx, int code, const char* fmt, ...);
 
 extern __shared__ uint32_t pt_lds[];
 
@@ -64,15 +62,12 @@ enum : uint32_t {                      // per-lane path flags
     kPfBrute = 0x800u                  // this path runs TracePath (brute force)
 };
 
-#ifndef CGPT_PT_WAVES_PER_SIMD
-#define CGPT_PT_WAVES_PER_SIMD 1
-#endif
 // TAIL: the instantiation for small calls (few samples per call -- the reference's own main loop renders ONE per Render(), ref:
 // Main.cpp:702,825-942), which are mostly drain: once nothing is left to fetch, a wave with few busy lanes runs their rays in the lean
 // per-lane loop (trace_steps.hpp: lean_traverse) instead of voted steps, because the call ends when its longest chain does (1080p, one
 // sample: 2.47 -> 2.21 ms).  Kept out of the throughput instantiations, which it costs registers and SGPR spills (profiles/r03/one_sample.md).
 template <bool COUNT, bool BRUTE, bool TAIL>
-__global__ void __launch_bounds__(kTraceBlock, (!COUNT && !BRUTE && !TAIL) ? CGPT_PT_WAVES_PER_SIMD : 1) pt_persistent(const DevRenderArgs args, const PtDev pt, uint32_t batch_first, const TraceTune tune)
+__global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderArgs args, const PtDev pt, uint32_t batch_first, const TraceTune tune)
 {
     const DevScene& sc = args.scene;
     const DevSettings& st = args.settings;
@@ -313,24 +308,28 @@ struct PtTuning {
     uint32_t fine_rounds = 2;     // fine fetches (one id per idle lane) once fewer than this many ids per lane of the grid are left
 };
 
+// every instantiation, [COUNT][BRUTE][TAIL]
+static decltype(&pt_persistent<false, false, false>) const kPtKernels[2][2][2] = {
+    { { pt_persistent<false, false, false>, pt_persistent<false, false, true> }, { pt_persistent<false, true, false>, pt_persistent<false, true, true> } },
+    { { pt_persistent<true, false, false>, pt_persistent<true, false, true> }, { pt_persistent<true, true, false>, pt_persistent<true, true, true> } },
+};
+
 struct PtHost {
     PtTuning tune;
-    float4* st_en[2] = { nullptr, nullptr };
-    size_t st_en_paths = 0;
-    float4* brute = nullptr; size_t brute_floats4 = 0;
-    uint32_t* overflow = nullptr; size_t overflow_words = 0;
-    uint32_t* work_counters = nullptr; uint32_t n_work_counters = 0;         // one zeroed word per launch of a render
+    DevBuf<float4> st_en[2];                  // [stream]
+    DevBuf<float4> brute;
+    DevBuf<uint32_t> overflow;
+    DevBuf<uint32_t> work_counters;           // kWorkCounters counters of 8 words per launch of a render, zeroed before it
     unsigned long long* phase_stats = nullptr;
     hipStream_t streams[2] = { nullptr, nullptr };
     hipEvent_t begin = nullptr, acc_done[2] = { nullptr, nullptr };
-    hipEvent_t* ev = nullptr; uint32_t ev_cap = 0, ev_used = 0;
+    EventPairs ev;
     uint32_t n_cus = 0;
     uint32_t blocks_per_cu[2][2][2] = {};    // [COUNT][BRUTE][TAIL]
     size_t occupancy_lds = 0;
 };
 
-struct PtKnob { const char* name; uint32_t PtTuning::*field; uint32_t lo, hi; };
-static const PtKnob kPtKnobs[] = {
+static const Knob<PtTuning> kPtKnobs[] = {
     { "pt_budget_gib", &PtTuning::budget_gib, 1, 256 },   { "pt_max_paths_mi", &PtTuning::max_paths_mi, 1, 2047 },
     { "pt_refill", &PtTuning::refill_idle, 1, 64 },       { "pt_inner_repeat", &PtTuning::inner_repeat, 1, 65 },
     { "pt_leaf_repeat", &PtTuning::leaf_repeat, 1, 65 },  { "pt_obj_shift", &PtTuning::obj_shift, 0, 6 },
@@ -348,14 +347,7 @@ static PtHost* PtGetHost(cgpt_ctx* ctx)
     if (*slot) return static_cast<PtHost*>(*slot);
     PtHost* h = new (std::nothrow) PtHost;
     if (!h) { CtxFail(ctx, CGPT_ERR_INVALID, "out of host memory"); return nullptr; }
-    for (const PtKnob& k : kPtKnobs) {
-        char env[64] = "CGPT_";
-        size_t n = strlen(env);
-        for (const char* c = k.name; *c && n + 1 < sizeof(env); ++c) env[n++] = (char)toupper((unsigned char)*c);
-        env[n] = 0;
-        const char* v = getenv(env);
-        if (v && *v) h->tune.*(k.field) = (uint32_t)std::min<long>(std::max<long>(strtol(v, nullptr, 10), k.lo), k.hi);
-    }
+    LoadKnobsFromEnv(kPtKnobs, "CGPT_", h->tune);
     hipError_t e = hipEventCreateWithFlags(&h->begin, hipEventDisableTiming);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) {
         e = hipStreamCreateWithFlags(&h->streams[i], hipStreamNonBlocking);
@@ -372,31 +364,24 @@ static PtHost* PtGetHost(cgpt_ctx* ctx)
 
 int PersistentSetTuning(cgpt_ctx* ctx, const char* name, uint32_t value, bool* known)
 {
-    *known = false;
-    for (const PtKnob& k : kPtKnobs)
-        if (strcmp(k.name, name) == 0) {
-            *known = true;
-            PtHost* h = PtGetHost(ctx);
-            if (!h) return CGPT_ERR_HIP;
-            if (value < k.lo || value > k.hi) return CtxFail(ctx, CGPT_ERR_INVALID, "tuning knob %s: %u outside [%u, %u]", name, value, k.lo, k.hi);
-            h->tune.*(k.field) = value;
-            return CGPT_OK;
-        }
-    return CGPT_OK;
+    const Knob<PtTuning>* k = FindKnob(kPtKnobs, name);
+    *known = k != nullptr;
+    if (!k) return CGPT_OK;
+    PtHost* h = PtGetHost(ctx);
+    return h ? SetKnob(ctx, k, h->tune, name, value) : CGPT_ERR_HIP;
 }
 
 void PersistentFree(void* state)
 {
     if (!state) return;
     PtHost* h = static_cast<PtHost*>(state);
-    (void)hipFree(h->st_en[0]); (void)hipFree(h->st_en[1]); (void)hipFree(h->brute); (void)hipFree(h->overflow); (void)hipFree(h->phase_stats); (void)hipFree(h->work_counters);
+    (void)hipFree(h->st_en[0].p); (void)hipFree(h->st_en[1].p); (void)hipFree(h->brute.p); (void)hipFree(h->overflow.p); (void)hipFree(h->phase_stats); (void)hipFree(h->work_counters.p);
     for (int i = 0; i < 2; ++i) {
         if (h->streams[i]) (void)hipStreamDestroy(h->streams[i]);
         if (h->acc_done[i]) (void)hipEventDestroy(h->acc_done[i]);
     }
     if (h->begin) (void)hipEventDestroy(h->begin);
-    for (uint32_t i = 0; i < h->ev_cap; ++i) (void)hipEventDestroy(h->ev[i]);
-    free(h->ev);
+    FreeEvents(h->ev);
     delete h;
 }
 
@@ -405,11 +390,7 @@ void PersistentCollectTiming(void* state, double* ms, uint32_t* launches, uint32
     *ms = 0.0; *launches = 0; *waves_per_simd = 0;
     if (!state) return;
     PtHost* h = static_cast<PtHost*>(state);
-    for (uint32_t i = 0; i + 1u < h->ev_used; i += 2u) {
-        float t = 0.0f;
-        if (hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1u]) == hipSuccess) { *ms += t; *launches += 1; }
-    }
-    h->ev_used = 0;
+    ForEachPair(h->ev, [&](uint32_t, float t) { *ms += t; *launches += 1; });
     *waves_per_simd = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[0][0][0]) * (kTraceBlock / 256u);
 }
 
@@ -418,36 +399,17 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
     hipStream_t stream = CtxStream(ctx);
     PtHost* h = PtGetHost(ctx);
     if (!h) return -1;
-#define PT_TRY(expr)                                                                                     \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) { CtxFail(ctx, CGPT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); return -1; } \
-    } while (0)
 
     const bool brute = args_in.settings.render_mode != 2u;
-    if (h->n_cus == 0) {
-        int dev = 0, cus = 0;
-        PT_TRY(hipGetDevice(&dev));
-        PT_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        h->n_cus = (uint32_t)cus;
-    }
+    LAUNCH_TRY(QueryCuCount(h->n_cus));
     const uint32_t top_records = std::min(h->tune.top_records, args_in.scene.n_top_records);
     const size_t lds = trace_lds_bytes(top_records);
     if (h->occupancy_lds != lds) {
-        int b = 0;
-#define PT_EACH_KERNEL(X) X(false, false, false) X(false, true, false) X(true, false, false) X(true, true, false) X(false, false, true) X(false, true, true) X(true, false, true) X(true, true, true)
-        if (lds > 48u * 1024u) {                                              // more dynamic LDS than the default limit: opt in per kernel
-#define PT_OPT_IN(C, B, O) PT_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&pt_persistent<C, B, O>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            PT_EACH_KERNEL(PT_OPT_IN)
-#undef PT_OPT_IN
-        }
-#define PT_OCCUPANCY(C, B, O) PT_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (pt_persistent<C, B, O>), kTraceBlock, lds)); h->blocks_per_cu[C][B][O] = (uint32_t)std::max(1, b);
-        PT_EACH_KERNEL(PT_OCCUPANCY)
-#undef PT_OCCUPANCY
+        LAUNCH_TRY(QueryOccupancy(&kPtKernels[0][0][0], &h->blocks_per_cu[0][0][0], 8, kTraceBlock, lds));
         h->occupancy_lds = lds;
     }
     const bool tail = args_in.n_samples <= h->tune.tail_samples;              // a small call: mostly drain
-    const uint32_t blocks_per_cu = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[count ? 1 : 0][brute ? 1 : 0][tail ? 1 : 0]);
+    const uint32_t blocks_per_cu = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[count][brute][tail]);
     // the resident capacity of the chip, or fewer blocks when there are fewer than 64 paths per wave (a small call ends sooner when
     // its paths are spread thin than when the tail of a launch waits for 4 096 waves to find out that there is nothing to do)
     const uint32_t n_tiles = ((args_in.width + 7u) / 8u) * ((args_in.n_rows + 7u) / 8u);
@@ -466,8 +428,8 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
 
     // ---- samples per batch: as many as the radiance buffers hold; two buffers when there is more than one batch ----
     size_t free_b = 0, total_b = 0;
-    PT_TRY(hipMemGetInfo(&free_b, &total_b));
-    const size_t held = (h->st_en[0] ? h->st_en_paths * sizeof(float4) : 0) + (h->st_en[1] ? h->st_en_paths * sizeof(float4) : 0);
+    LAUNCH_TRY(hipMemGetInfo(&free_b, &total_b));
+    const size_t held = (h->st_en[0].n + h->st_en[1].n) * sizeof(float4);
     const size_t budget = std::min<size_t>((size_t)h->tune.budget_gib << 30, (free_b + held) / 2);
     uint32_t batch = (uint32_t)std::min<uint64_t>(args_in.n_samples, std::min<uint64_t>(max_paths / n_pixels, budget / sizeof(float4) / n_pixels));
     if (batch == 0) { CtxFail(ctx, CGPT_ERR_HIP, "not enough free HBM for one sample of %u pixels", n_pixels); return -1; }
@@ -479,60 +441,22 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
         n_batches = (args_in.n_samples + batch - 1u) / batch;
     }
     const size_t cap = (size_t)n_pixels * batch;
-    if (h->st_en_paths < cap || (n_streams == 2 && !h->st_en[1])) {
-        PT_TRY(hipDeviceSynchronize());
-        (void)hipFree(h->st_en[0]); (void)hipFree(h->st_en[1]); h->st_en[0] = h->st_en[1] = nullptr; h->st_en_paths = 0;
-        PT_TRY(hipMalloc((void**)&h->st_en[0], cap * sizeof(float4)));
-        if (n_streams == 2) PT_TRY(hipMalloc((void**)&h->st_en[1], cap * sizeof(float4)));
-        h->st_en_paths = cap;
-    }
+    LAUNCH_TRY(Grow(h->st_en[0], cap));
+    if (n_streams == 2) LAUNCH_TRY(Grow(h->st_en[1], cap));
     const uint32_t deep_levels = args_in.scene.stack_depth > kLdsStackLevels ? args_in.scene.stack_depth - kLdsStackLevels : 0u;
-    const size_t overflow_words = std::max<size_t>(1, (size_t)deep_levels * max_threads) * n_streams;
-    if (h->overflow_words < overflow_words) {
-        PT_TRY(hipDeviceSynchronize());
-        (void)hipFree(h->overflow); h->overflow = nullptr;
-        PT_TRY(hipMalloc((void**)&h->overflow, overflow_words * sizeof(uint32_t)));
-        h->overflow_words = overflow_words;
-    }
-    if (brute) {
-        const size_t need = (size_t)(args_in.settings.max_ray_depth + 1) * max_threads * 2u * n_streams;
-        if (h->brute_floats4 < need) {
-            PT_TRY(hipDeviceSynchronize());
-            (void)hipFree(h->brute); h->brute = nullptr;
-            PT_TRY(hipMalloc((void**)&h->brute, need * sizeof(float4)));
-            h->brute_floats4 = need;
-        }
-    }
-#ifdef CGPT_PHASE_CYCLES
-    const bool want_phase_stats = getenv("CGPT_WF_PROFILE") != nullptr;
-#else
-    const bool want_phase_stats = count && getenv("CGPT_WF_PROFILE") != nullptr;
-#endif
-    if (want_phase_stats && !h->phase_stats) PT_TRY(hipMalloc((void**)&h->phase_stats, 48 * sizeof(unsigned long long)));
-    if (h->phase_stats) PT_TRY(hipMemsetAsync(h->phase_stats, 0, 48 * sizeof(unsigned long long), stream));
-
-    const uint32_t ev_needed = 2u * n_batches;
-    if (h->ev_cap < ev_needed) {
-        hipEvent_t* grown = static_cast<hipEvent_t*>(realloc(h->ev, (size_t)ev_needed * sizeof(hipEvent_t)));
-        if (!grown) { CtxFail(ctx, CGPT_ERR_INVALID, "out of host memory"); return -1; }
-        h->ev = grown;
-        for (; h->ev_cap < ev_needed; ++h->ev_cap) PT_TRY(hipEventCreate(&h->ev[h->ev_cap]));
-    }
-    h->ev_used = 0;
-
-    if (h->n_work_counters < n_batches) {
-        PT_TRY(hipDeviceSynchronize());
-        (void)hipFree(h->work_counters); h->work_counters = nullptr;
-        PT_TRY(hipMalloc((void**)&h->work_counters, (size_t)n_batches * kWorkCounters * 8u * sizeof(uint32_t)));
-        h->n_work_counters = n_batches;
-    }
-    PT_TRY(hipEventRecord(CtxStartEvent(ctx), stream));                       // one-time host setup is over: the render's device time starts here
-    PT_TRY(hipMemsetAsync(h->work_counters, 0, (size_t)n_batches * kWorkCounters * 8u * sizeof(uint32_t), stream));   // before `begin`: ordered ahead of both streams
+    LAUNCH_TRY(Grow(h->overflow, std::max<size_t>(1, (size_t)deep_levels * max_threads) * n_streams));
+    if (brute) LAUNCH_TRY(Grow(h->brute, (size_t)(args_in.settings.max_ray_depth + 1) * max_threads * 2u * n_streams));
+    LAUNCH_TRY(ResetPhaseStats(h->phase_stats, 48, count, stream));
+    if (ReserveEvents(ctx, h->ev, 2u * n_batches) != 0) return -1;
+    const size_t work_words = (size_t)n_batches * kWorkCounters * 8u;
+    LAUNCH_TRY(Grow(h->work_counters, work_words));
+    LAUNCH_TRY(hipEventRecord(CtxStartEvent(ctx), stream));                   // one-time host setup is over: the render's device time starts here
+    LAUNCH_TRY(hipMemsetAsync(h->work_counters.p, 0, work_words * sizeof(uint32_t), stream));   // before `begin`: ordered ahead of both streams
     const TraceTune tt = { h->tune.refill_idle, h->tune.inner_repeat, h->tune.leaf_repeat, 1u, h->tune.obj_shift, top_records, 0u, h->tune.lds_tris, h->tune.tail_lanes, 0u };   // shadow rays to the end here: stopping them early (wf_trace does) cost this kernel 2 % in registers
 
     if (n_streams == 2) {
-        PT_TRY(hipEventRecord(h->begin, stream));
-        for (int i = 0; i < 2; ++i) PT_TRY(hipStreamWaitEvent(h->streams[i], h->begin, 0));
+        LAUNCH_TRY(hipEventRecord(h->begin, stream));
+        for (int i = 0; i < 2; ++i) LAUNCH_TRY(hipStreamWaitEvent(h->streams[i], h->begin, 0));
     }
     int launches = 0;
     uint32_t k = 0;
@@ -542,39 +466,33 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
         const uint32_t bn = std::min(batch, args_in.n_samples - done);
         const uint32_t bfirst = args_in.first_sample + done;
         PtDev pt{};
-        pt.st_en = h->st_en[s];
-        pt.brute = brute ? h->brute + (size_t)s * (h->brute_floats4 / n_streams) : nullptr;
-        pt.stack_overflow = h->overflow + (size_t)s * (h->overflow_words / n_streams);
-#ifdef CGPT_PHASE_CYCLES
-        pt.phase_stats = h->phase_stats;
-#else
-        pt.phase_stats = count ? h->phase_stats : nullptr;
-#endif
+        pt.st_en = h->st_en[s].p;
+        pt.brute = brute ? h->brute.p + (size_t)s * (h->brute.n / n_streams) : nullptr;
+        pt.stack_overflow = h->overflow.p + (size_t)s * (h->overflow.n / n_streams);
+        pt.phase_stats = PhaseStatsArg(h->phase_stats, count);
         pt.n_paths = n_pixels * bn;
         pt.g.n_pixels = n_pixels; pt.g.tiles_x = tiles_x; pt.g.div_tiles_x = MakeFastDiv(tiles_x); pt.g.div_n_pixels = MakeFastDiv(n_pixels);
         pt.shade_shift = h->tune.shade_shift;
         pt.g.order = h->tune.path_order; pt.g.n_samples = bn; pt.g.div_samples = MakeFastDiv(bn);
-        pt.work = h->work_counters + (size_t)k * kWorkCounters * 8u;
+        pt.work = h->work_counters.p + (size_t)k * kWorkCounters * 8u;
         work_sizes(pt.n_paths, grid.x * (kTraceBlock / 64u), h->tune.fine_rounds, h->tune.chunk, pt.coarse, pt.fine_below);
         // the buffer's previous batch must have been accumulated (same stream: implicit)
-        PT_TRY(hipEventRecord(h->ev[h->ev_used++], st));
-#define PT_LAUNCH(C, B, O) if (count == C && brute == B && tail == O) hipLaunchKernelGGL((pt_persistent<C, B, O>), grid, trace_block, lds, st, args_in, pt, bfirst, tt);
-        PT_EACH_KERNEL(PT_LAUNCH)
-#undef PT_LAUNCH
-        PT_TRY(hipEventRecord(h->ev[h->ev_used++], st));
+        LAUNCH_TRY(hipEventRecord(NextEvent(h->ev), st));
+        hipLaunchKernelGGL(kPtKernels[count][brute][tail], grid, trace_block, lds, st, args_in, pt, bfirst, tt);
+        LAUNCH_TRY(hipEventRecord(NextEvent(h->ev), st));
         // accumulate in sample order: batch k after batch k-1
-        if (n_streams == 2 && k > 0) PT_TRY(hipStreamWaitEvent(st, h->acc_done[(k - 1u) & 1u], 0));
+        if (n_streams == 2 && k > 0) LAUNCH_TRY(hipStreamWaitEvent(st, h->acc_done[(k - 1u) & 1u], 0));
         hipLaunchKernelGGL(pt_accumulate, dim3(std::min((n_pixels + 255u) / 256u, h->n_cus * 8u)), block, 0, st, args_in, (const float4*)pt.st_en, pt.g, bfirst, bn);
-        if (n_streams == 2) PT_TRY(hipEventRecord(h->acc_done[s], st));
-        PT_TRY(hipGetLastError());
+        if (n_streams == 2) LAUNCH_TRY(hipEventRecord(h->acc_done[s], st));
+        LAUNCH_TRY(hipGetLastError());
         launches += 2;
     }
-    if (n_streams == 2 && k > 0) PT_TRY(hipStreamWaitEvent(stream, h->acc_done[(k - 1u) & 1u], 0));
+    if (n_streams == 2 && k > 0) LAUNCH_TRY(hipStreamWaitEvent(stream, h->acc_done[(k - 1u) & 1u], 0));
 #ifdef CGPT_PHASE_CYCLES
     if (!count && h->phase_stats) {
         unsigned long long ps[48];
-        PT_TRY(hipStreamSynchronize(stream));
-        PT_TRY(hipMemcpy(ps, h->phase_stats, sizeof(ps), hipMemcpyDeviceToHost));
+        LAUNCH_TRY(hipStreamSynchronize(stream));
+        LAUNCH_TRY(hipMemcpy(ps, h->phase_stats, sizeof(ps), hipMemcpyDeviceToHost));
         const double tot = (double)ps[16], waves = (double)ps[17];
         static const char* names[6] = { "refill", "inner", "leaf", "object", "shade", "lean" };
         fprintf(stderr, "[pt cycles] %.0f waves, mean life %.0f kcyc, longest %.0f kcyc, mean drain after the last refill %.0f kcyc |", waves, tot / waves / 1e3, ps[19] / 1e3, ps[18] / waves / 1e3);
@@ -588,16 +506,14 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
 #endif
     if (count && h->phase_stats) {                                            // development aid: how full the steps were
         unsigned long long ps[16];
-        PT_TRY(hipStreamSynchronize(stream));
-        PT_TRY(hipMemcpy(ps, h->phase_stats, sizeof(ps), hipMemcpyDeviceToHost));
+        LAUNCH_TRY(hipStreamSynchronize(stream));
+        LAUNCH_TRY(hipMemcpy(ps, h->phase_stats, sizeof(ps), hipMemcpyDeviceToHost));
         DevCounters c;
-        PT_TRY(hipMemcpy(&c, args_in.counters, sizeof(c), hipMemcpyDeviceToHost));
+        LAUNCH_TRY(hipMemcpy(&c, args_in.counters, sizeof(c), hipMemcpyDeviceToHost));
         fprintf(stderr, "[pt profile] rays %llu | inner: %llu wave steps, %.1f lanes/step | leaf: %llu, %.1f | object: %llu, %.1f | shade: %llu, %.1f | votes %llu refills %llu\n",
                 c.traced_rays, ps[0], ps[0] ? (double)c.inner_steps / ps[0] : 0.0, ps[1], ps[1] ? (double)ps[8] / ps[1] : 0.0,
                 ps[2], ps[2] ? (double)ps[4] / ps[2] : 0.0, ps[3], ps[3] ? (double)ps[5] / ps[3] : 0.0, ps[6], ps[7]);
     }
-#undef PT_EACH_KERNEL
-#undef PT_TRY
     return launches;
 }
 

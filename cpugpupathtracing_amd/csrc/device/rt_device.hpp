@@ -163,19 +163,6 @@ typedef float f4v __attribute__((ext_vector_type(4)));
 typedef uint32_t u2v __attribute__((ext_vector_type(2)));
 
 struct NodePair { f4v q0, q1, q2; uint32_t lcode, rcode; };                 // 56 useful bytes of the 64-byte record
-#ifdef CGPT_NODE_SOA
-// Experiment build (north_star suggests SoA node planes "for coalesced HBM reads"; measured in profiles/r02/node_layout_ab.md):
-// component plane p of record r at dword p * n_records + r, so a lane's record is 14 separate 4-byte fetches from 14 lines.
-__device__ __forceinline__ void load_pair_soa(const float4* node_pairs, uint32_t n_records, uint32_t code, NodePair& n)
-{
-    const float* p = reinterpret_cast<const float*>(node_pairs) + code;
-    const size_t s = n_records;
-    n.q0 = f4v{ p[0], p[s], p[2 * s], p[3 * s] };
-    n.q1 = f4v{ p[4 * s], p[5 * s], p[6 * s], p[7 * s] };
-    n.q2 = f4v{ p[8 * s], p[9 * s], p[10 * s], p[11 * s] };
-    n.lcode = __float_as_uint(p[14 * s]); n.rcode = __float_as_uint(p[15 * s]);
-}
-#endif
 __device__ __forceinline__ void load_pair(const float4* node_pairs, uint32_t code, NodePair& n)
 {
     // byte offset in 32 bits (2^26 records = 4 GB): global_load with a scalar base and a 32-bit VGPR offset, no 64-bit address math
@@ -218,18 +205,9 @@ __device__ __forceinline__ f2v pk_sub_mul_lo_hi(f2v p, f2v oi_pair)             
     asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(r) : "v"(d), "v"(oi_pair));
     return r;
 }
-__device__ __forceinline__ f2v sc_sub_mul(f2v p, float o, float i)          // the scalar form: four full-rate instructions
-{
-    f2v r; r.x = (p.x - o) * i; r.y = (p.y - o) * i; return r;
-}
 __device__ __forceinline__ SlabProducts slab_products(const NodePair& n, const RaySlab& r)
 {
     SlabProducts s;
-#ifdef CGPT_SLAB_SCALAR
-    s.t1x = sc_sub_mul(n.q0.xy, r.oxy.x, r.ixy.x); s.t1y = sc_sub_mul(n.q0.zw, r.oxy.y, r.ixy.y); s.t1z = sc_sub_mul(n.q1.xy, r.ozi.x, r.ozi.y);
-    s.t2x = sc_sub_mul(n.q1.zw, r.oxy.x, r.ixy.x); s.t2y = sc_sub_mul(n.q2.xy, r.oxy.y, r.ixy.y); s.t2z = sc_sub_mul(n.q2.zw, r.ozi.x, r.ozi.y);
-    return s;
-#endif
     s.t1x = pk_sub_mul_lo_lo(n.q0.xy, r.oxy, r.ixy); s.t1y = pk_sub_mul_hi_hi(n.q0.zw, r.oxy, r.ixy); s.t1z = pk_sub_mul_lo_hi(n.q1.xy, r.ozi);
     s.t2x = pk_sub_mul_lo_lo(n.q1.zw, r.oxy, r.ixy); s.t2y = pk_sub_mul_hi_hi(n.q2.xy, r.oxy, r.ixy); s.t2z = pk_sub_mul_lo_hi(n.q2.zw, r.ozi);
     return s;
@@ -319,11 +297,7 @@ __device__ __forceinline__ bool traverse_mesh(const DevScene& sc, uint32_t root_
             continue;
         }
         NodePair n;
-#ifdef CGPT_NODE_SOA
-        load_pair_soa(sc.node_pairs, sc.n_pair_records, code, n);
-#else
         load_pair(sc.node_pairs, code, n);
-#endif
         if (COUNT) cnt.inner++;
         float left_dist, right_dist;
         slab_pair(n, rs, ray_t, __builtin_amdgcn_ballot_w64(exact_slab) != 0ull, left_dist, right_dist);   // wave-uniform: NaN-exact form only if somebody needs it

@@ -267,7 +267,7 @@ __device__ __forceinline__ TravCtx trav_setup(const DevScene& sc, uint32_t* lds_
             if ((i & 7u) == 7u) v = (i < n_words && src[i - 7u] == 0u) ? src[i - 6u] : kStartObject;
             objtab[i] = v;
         }
-    } else if (threadIdx.x == 0u) objtab[7] = kStartObject;                   // the one word the fetch sequences read when the table is not in LDS
+    } else if (threadIdx.x == 0u) objtab[7] = kStartObject;                   // (no step reads it: without the table next_object_code answers itself)
     lds_u32* const tri_cache = objtab + (kLdsObjects + 1u) * 8u;
     c.n_lds_tris = lds_tris ? min(sc.n_small_tris, kLdsTrisMax) : 0u;
     // LDS copy of a triangle record: dwords 0..7 as in HBM, the tail {e2.z, tri_idx, last} moved from dwords 9..11 to 8..10, where it is
@@ -280,11 +280,7 @@ __device__ __forceinline__ TravCtx trav_setup(const DevScene& sc, uint32_t* lds_
     lds_u32* const top_cache = tri_cache + kLdsTrisMax * 12u;
     c.n_top = min(top_records, sc.n_top_records);
     for (uint32_t i = threadIdx.x; i < c.n_top * 16u; i += kTraceBlock)
-#ifdef CGPT_NODE_SOA
-        top_cache[(i >> 4) * kTopStride + (i & 15u)] = reinterpret_cast<const uint32_t*>(sc.node_pairs)[(size_t)(i & 15u) * sc.n_pair_records + (i >> 4)];
-#else
         top_cache[(i >> 4) * kTopStride + (i & 15u)] = reinterpret_cast<const uint32_t*>(sc.node_pairs)[i];
-#endif
     __syncthreads();
     c.objtab = objtab; c.top_cache = top_cache;
     c.first_code = kStartObject;
@@ -343,90 +339,6 @@ __device__ __forceinline__ LeafTri load_leaf_tri_lds(const lds_u32* tri_cache, u
     return t;
 }
 
-// ---- one fetch sequence per voted step (experiment build -DCGPT_FETCH_SEQ; measured slower, not the default) -----------------
-// A voted step needs a record (child pair or leaf triangle: from the LDS copy for some lanes, from HBM for the others), the stack
-// entry below the lane's stack pointer and the object-table entry after the lane's object.  Left to the compiler the two halves of
-// the record fetch share their destination registers, and its wait-count bookkeeping is per register, not per lane: it waits for the
-// HBM loads before it lets the LDS reads of the OTHER lanes issue, and reads the stack entry after both -- global latency + two LDS
-// round trips in series, every step.  Here all of them are issued back to back under their lane masks and waited for once.
-// Measured (profiles/r03/ab_fetch_sequence.txt): later-round trace 70.6-71.6 ms with the compiler's serial fetch, 72.9-73.6 ms with
-// this one, with or without skipping the empty half.  A step is not bound by its own latency (five waves per SIMD cover it); what the
-// sequence costs is the work the compiler used to put in the loads' shadow, which now sits behind the wait.
-typedef uint32_t u3v __attribute__((ext_vector_type(3)));
-typedef uint64_t exec_mask_t;
-template <typename P> __device__ __forceinline__ uint32_t lds_addr(P* p) { return (uint32_t)(uintptr_t)p; }
-
-struct StepAux { uint32_t top, next; };                                       // stack entry below sp; the code object cur_obj + 1 begins with (objtab word 7)
-
-__device__ __forceinline__ void fetch_pair_seq(const TravCtx& c, const Trav& r, NodePair& n, StepAux& aux)
-{
-    const uint32_t goff = r.code << 6;                                        // byte offset of the 64-byte record (r.code < 2^26)
-    const uint32_t laddr = lds_addr(c.top_cache) + goff + (r.code << 4);      // code * 80 bytes (kTopStride dwords)
-    static_assert(kTopStride == 20u, "LDS record stride as shifts");
-    aux.top = lds_addr(c.stack) + (r.sp - (r.sp != 0u ? 1u : 0u)) * (kTraceBlock * 4u);   // address in, entry out (same register)
-    aux.next = lds_addr(c.objtab) + 28u + (c.tab ? (r.cur_obj + 1u) * 32u : 0u);
-    exec_mask_t save;
-    u2v cd;
-    asm volatile(
-        "ds_read_b32 %[top], %[top]\n\t"
-        "ds_read_b32 %[nxt], %[nxt]\n\t"
-        "v_cmp_gt_u32_e32 vcc, %[ntop], %[code]\n\t"                          // lanes whose record is in the LDS copy of the tree top
-        "s_and_saveexec_b64 %[save], vcc\n\t"
-        "s_cbranch_execz .Lpair_no_lds_%=\n\t"                                // (a memory instruction with no lane still makes its round trip)
-        "ds_read_b128 %[q0], %[laddr]\n\t"
-        "ds_read_b128 %[q1], %[laddr] offset:16\n\t"
-        "ds_read_b128 %[q2], %[laddr] offset:32\n\t"
-        "ds_read_b64 %[cd], %[laddr] offset:56\n"
-        ".Lpair_no_lds_%=:\n\t"
-        "s_andn2_b64 exec, %[save], vcc\n\t"                                  // the other lanes: HBM (L2)
-        "s_cbranch_execz .Lpair_no_hbm_%=\n\t"
-        "global_load_dwordx4 %[q0], %[goff], %[base]\n\t"
-        "global_load_dwordx4 %[q1], %[goff], %[base] offset:16\n\t"
-        "global_load_dwordx4 %[q2], %[goff], %[base] offset:32\n\t"
-        "global_load_dwordx2 %[cd], %[goff], %[base] offset:56\n"
-        ".Lpair_no_hbm_%=:\n\t"
-        "s_mov_b64 exec, %[save]\n\t"
-        "s_waitcnt vmcnt(0) lgkmcnt(0)"
-        : [q0] "=&v"(n.q0), [q1] "=&v"(n.q1), [q2] "=&v"(n.q2), [cd] "=&v"(cd), [top] "+v"(aux.top), [nxt] "+v"(aux.next), [save] "=&s"(save)
-        : [ntop] "s"(c.n_top), [code] "v"(r.code), [laddr] "v"(laddr), [goff] "v"(goff), [base] "s"(c.sc->node_pairs)
-        : "vcc", "memory");
-    n.lcode = cd.x; n.rcode = cd.y;
-}
-
-__device__ __forceinline__ void fetch_leaf_seq(const TravCtx& c, const Trav& r, LeafTri& t, StepAux& aux)
-{
-    const uint32_t index = r.code & ~kLeafBit;
-    const uint32_t goff = (index << 5) + (index << 4);                        // index * 48 bytes (index < 2^26)
-    const uint32_t laddr = lds_addr(c.tri_cache) + goff;
-    aux.top = lds_addr(c.stack) + (r.sp - (r.sp != 0u ? 1u : 0u)) * (kTraceBlock * 4u);
-    aux.next = lds_addr(c.objtab) + 28u + (c.tab ? (r.cur_obj + 1u) * 32u : 0u);
-    exec_mask_t save;
-    f4v a, b; u3v tail;
-    asm volatile(
-        "ds_read_b32 %[top], %[top]\n\t"
-        "ds_read_b32 %[nxt], %[nxt]\n\t"
-        "v_cmp_gt_u32_e32 vcc, %[nlds], %[index]\n\t"                         // a small mesh's triangle (the ground quad): LDS copy
-        "s_and_saveexec_b64 %[save], vcc\n\t"
-        "s_cbranch_execz .Lleaf_no_lds_%=\n\t"
-        "ds_read_b128 %[a], %[laddr]\n\t"
-        "ds_read_b128 %[b], %[laddr] offset:16\n\t"
-        "ds_read_b96 %[tail], %[laddr] offset:32\n"
-        ".Lleaf_no_lds_%=:\n\t"
-        "s_andn2_b64 exec, %[save], vcc\n\t"
-        "s_cbranch_execz .Lleaf_no_hbm_%=\n\t"
-        "global_load_dwordx4 %[a], %[goff], %[base]\n\t"
-        "global_load_dwordx4 %[b], %[goff], %[base] offset:16\n\t"
-        "global_load_dwordx3 %[tail], %[goff], %[base] offset:36\n"
-        ".Lleaf_no_hbm_%=:\n\t"
-        "s_mov_b64 exec, %[save]\n\t"
-        "s_waitcnt vmcnt(0) lgkmcnt(0)"
-        : [a] "=&v"(a), [b] "=&v"(b), [tail] "=&v"(tail), [top] "+v"(aux.top), [nxt] "+v"(aux.next), [save] "=&s"(save)
-        : [nlds] "s"(c.n_lds_tris), [index] "v"(index), [laddr] "v"(laddr), [goff] "v"(goff), [base] "s"(c.sc->tri_leaf)
-        : "vcc", "memory");
-    t.v0 = mk(a.x, a.y, a.z); t.e1 = mk(a.w, b.x, b.y); t.e2 = mk(b.z, b.w, __uint_as_float(tail.x));
-    t.tri_idx = tail.y; t.last = tail.z != 0u;
-}
-__device__ __forceinline__ uint32_t next_code_of(const TravCtx&, const StepAux& aux) { return aux.next; }
 
 // Traversal code a lane continues with when the object it is in ends: the root of object cur_obj + 1 if that is a mesh,
 // otherwise kStartObject (analytic primitive or end of the list: the object step takes over).
@@ -436,6 +348,7 @@ __device__ __forceinline__ uint32_t next_object_code(const TravCtx& c, uint32_t 
     return c.objtab[(cur_obj + 1u) * 8u + 7u];                               // word 7: trav_setup; entry n_objects is the end marker
 }
 
+template <typename P> __device__ __forceinline__ uint32_t lds_addr(P* p) { return (uint32_t)(uintptr_t)p; }
 __device__ __forceinline__ uint32_t* deep_column(const TravCtx& c)             // this thread's column: c.stack = LDS base + 4 * threadIdx.x
 {
     uint32_t a = lds_addr(c.stack);
@@ -462,30 +375,14 @@ __device__ __forceinline__ void inner_step(const TravCtx& c, Trav& r, Counters& 
     const DevScene& sc = *c.sc;
     NodePair n;
     const bool general = __builtin_amdgcn_ballot_w64(r.sp >= r.fast_levels) != 0ull;   // wave-uniform, rare: a deep stack or an axis-parallel ray
-#if defined(CGPT_NODE_SOA) || !defined(CGPT_FETCH_SEQ)
     if (r.code < c.n_top) load_pair_lds(c.top_cache, r.code, n);
-#ifdef CGPT_NODE_SOA
-    else load_pair_soa(sc.node_pairs, sc.n_pair_records, r.code, n);
-#else
     else load_pair(sc.node_pairs, r.code, n);
-#endif
-#else
-    StepAux aux;
-    if (!general) fetch_pair_seq(c, r, n, aux);                               // record + stack entry + object table entry, one wait
-    else if (r.code < c.n_top) load_pair_lds(c.top_cache, r.code, n);
-    else load_pair(sc.node_pairs, r.code, n);
-#endif
     if (COUNT) cnt.inner++;
     float left_dist, right_dist;
     if (!general) {
         // the entry below the stack pointer, read next to the node (LDS is faster): a pop is then a select
-#if defined(CGPT_NODE_SOA) || !defined(CGPT_FETCH_SEQ)
         const uint32_t top = c.stack[(r.sp - (r.sp != 0u ? 1u : 0u)) * kTraceBlock];   // unused when sp == 0
         const uint32_t next_code = next_object_code(c, r.cur_obj);            // used when this object ends here
-#else
-        const uint32_t top = aux.top;                                         // unused when sp == 0
-        const uint32_t next_code = next_code_of(c, aux);                      // used when this object ends here
-#endif
         slab_pair(n, r.rs, r.t, false, left_dist, right_dist);
         const bool swap = left_dist > right_dist;                             // ref: BVH.cpp:101-105
         const uint32_t near_code = swap ? n.rcode : n.lcode, far_code = swap ? n.lcode : n.rcode;
@@ -539,24 +436,11 @@ __device__ __forceinline__ void leaf_step(const TravCtx& c, Trav& r, Counters& c
     LeafTri lt;
     const uint32_t leaf_index = r.code & ~kLeafBit;
     uint32_t top, next_code;                                                  // entry below the stack pointer, code after this object: read next to the triangle
-#ifndef CGPT_FETCH_SEQ
     if (leaf_index < c.n_lds_tris) lt = load_leaf_tri_lds(c.tri_cache, leaf_index);   // a small mesh's triangle (the ground quad): LDS copy
     else lt = load_leaf_tri(c.sc->tri_leaf, leaf_index);
     if (__builtin_amdgcn_ballot_w64(r.sp > kLdsStackLevels) == 0ull) top = c.stack[(r.sp - (r.sp != 0u ? 1u : 0u)) * kTraceBlock];
     else top = stack_peek_any(c, r.sp);
     next_code = next_object_code(c, r.cur_obj);
-#else
-    if (__builtin_amdgcn_ballot_w64(r.sp > kLdsStackLevels) == 0ull) {
-        StepAux aux;
-        fetch_leaf_seq(c, r, lt, aux);
-        top = aux.top; next_code = next_code_of(c, aux);
-    } else {
-        if (leaf_index < c.n_lds_tris) lt = load_leaf_tri_lds(c.tri_cache, leaf_index);
-        else lt = load_leaf_tri(c.sc->tri_leaf, leaf_index);
-        top = stack_peek_any(c, r.sp);
-        next_code = next_object_code(c, r.cur_obj);
-    }
-#endif
     if (COUNT) cnt.tris += c.sc->objects[r.cur_obj].kind == CGPT_OBJECT_TRIANGLE ? 0u : 1u;   // BVH.cpp:76-77 only: a triangle object is no mesh
     float t_hit;
     const bool hit = intersect_triangle_flags(lt.v0, lt.e1, lt.e2, trav_origin(r), r.d, r.t, t_hit);
@@ -606,11 +490,7 @@ __device__ __forceinline__ void lean_traverse(const TravCtx& c, Trav& r, Counter
         }
         NodePair n;
         if (r.code < c.n_top) load_pair_lds(c.top_cache, r.code, n);
-#ifdef CGPT_NODE_SOA
-        else load_pair_soa(sc.node_pairs, sc.n_pair_records, r.code, n);
-#else
         else load_pair(sc.node_pairs, r.code, n);
-#endif
         if (COUNT) cnt.inner++;
         float left_dist, right_dist;
         slab_pair(n, r.rs, r.t, r.fast_levels == 0u, left_dist, right_dist);

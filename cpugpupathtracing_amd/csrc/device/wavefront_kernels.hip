@@ -38,9 +38,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
-#include <cctype>
 #include <cstdlib>
-#include <cstring>
 #include <new>
 
 #include "cpugpupt_abi.h"
@@ -50,6 +48,7 @@
 #include "shade_device.hpp"
 #include "trace_steps.hpp"
 #include "accumulate.hpp"
+#include "launch_common.h"
 
 namespace cgpt {
 
@@ -58,7 +57,6 @@ using namespace dev;
 hipStream_t CtxStream(cgpt_ctx* ctx);
 void** CtxWavefrontSlot(cgpt_ctx* ctx);
 hipEvent_t CtxStartEvent(cgpt_ctx* ctx);
-int CtxFail(cgpt_ctx* ctx, int code, const char* fmt, ...);
 
 extern __shared__ uint32_t lds_dyn[];
 
@@ -143,16 +141,10 @@ __device__ __forceinline__ uint32_t elect_chain_leader(const WfDev& wf, uint32_t
 // does not jitter (SURVEY A-14): every sample of a pixel traces the same primary ray to the same hit, so round 0 traces it once, stores
 // the hit record to px_hit[pixel] and counts it as the batch's n_samples IntersectScene calls.
 // The traversal states, their voted steps and the LDS layout are in trace_steps.hpp.
-#ifndef CGPT_TRACE_WAVES_PER_SIMD
-#define CGPT_TRACE_WAVES_PER_SIMD 1
-#endif
-#ifndef CGPT_SHADE_WAVES_PER_SIMD
-#define CGPT_SHADE_WAVES_PER_SIMD 1
-#endif
 
 // FIRST (round 0) is a separate instantiation so the later rounds carry neither its code nor its registers.
 template <bool COUNT, bool FIRST>
-__global__ void __launch_bounds__(kTraceBlock, (!COUNT && !FIRST) ? CGPT_TRACE_WAVES_PER_SIMD : 1) wf_trace(const DevRenderArgs args, const WfDev wf, uint32_t batch_first, const TraceTune tune)
+__global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs args, const WfDev wf, uint32_t batch_first, const TraceTune tune)
 {
     constexpr bool first_round = FIRST;
     const DevScene& sc = args.scene;
@@ -378,7 +370,7 @@ __global__ void __launch_bounds__(kTraceBlock, (!COUNT && !FIRST) ? CGPT_TRACE_W
 // BRUTE: the render has TracePath paths (RENDER_MODE_BRUTE_FORCE / COMPARISON); a separate instantiation, so the TracePathAdvanced
 // renders carry neither its code nor its registers.
 template <bool COUNT, bool FIRST, bool BRUTE = false>
-__global__ void __launch_bounds__(256, CGPT_SHADE_WAVES_PER_SIMD) wf_shade(const DevRenderArgs args, const WfDev wf, uint32_t batch_first)
+__global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, const WfDev wf, uint32_t batch_first)
 {
     constexpr bool first_round = FIRST;
     constexpr bool kChains = !COUNT && !BRUTE;                                // specular chains are tracked (and elected when wf.spec_tab is set)
@@ -805,13 +797,14 @@ static uint32_t CoprimeRotation(uint32_t n_waves, uint32_t n_tiles)
     return 0u;
 }
 
-static uint32_t EnvU32(const char* name, uint32_t fallback, uint32_t lo, uint32_t hi)
-{
-    const char* v = getenv(name);
-    if (!v || !*v) return fallback;
-    const long x = strtol(v, nullptr, 10);
-    return (uint32_t)std::min<long>(std::max<long>(x, lo), hi);
-}
+// every instantiation: trace [COUNT][FIRST], shade [COUNT][FIRST][BRUTE]
+static decltype(&wf_trace<false, false>) const kTraceKernels[2][2] = {
+    { wf_trace<false, false>, wf_trace<false, true> }, { wf_trace<true, false>, wf_trace<true, true> },
+};
+static decltype(&wf_shade<false, false>) const kShadeKernels[2][2][2] = {
+    { { wf_shade<false, false, false>, wf_shade<false, false, true> }, { wf_shade<false, true, false>, wf_shade<false, true, true> } },
+    { { wf_shade<true, false, false>, wf_shade<true, false, true> }, { wf_shade<true, true, false>, wf_shade<true, true, true> } },
+};
 
 struct WfHost {
     WfTuning tune;
@@ -828,7 +821,8 @@ struct WfHost {
     size_t occupancy_lds = 0;
     unsigned long long* phase_stats = nullptr;   // CGPT_WF_PROFILE=1: step counts of the COUNT trace kernels, printed after the render
     // hipEvent pairs around every trace launch of the last render (roofline accounting: the dominant kernel's own duration)
-    hipEvent_t* trace_ev = nullptr; uint32_t trace_ev_cap = 0, trace_ev_used = 0, trace_rounds = 0;
+    EventPairs trace_ev;
+    uint32_t trace_rounds = 0;
 };
 
 static void WfRelease(WfHost* h)
@@ -856,8 +850,7 @@ void WavefrontFree(void* state)
     }
     if (h->begin) (void)hipEventDestroy(h->begin);
     (void)hipFree(h->phase_stats);
-    for (uint32_t i = 0; i < h->trace_ev_cap; ++i) (void)hipEventDestroy(h->trace_ev[i]);
-    free(h->trace_ev);
+    FreeEvents(h->trace_ev);
     delete h;
 }
 
@@ -875,19 +868,14 @@ void WavefrontCollectTiming(void* state, double* trace_ms, uint32_t* trace_launc
     *trace_ms = 0.0; *trace_launches = 0; *round0_ms = 0.0; *round0_launches = 0;
     if (!state) return;
     WfHost* h = static_cast<WfHost*>(state);
-    for (uint32_t i = 0; i + 1u < h->trace_ev_used; i += 2u) {
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, h->trace_ev[i], h->trace_ev[i + 1u]) != hipSuccess) continue;
+    ForEachPair(h->trace_ev, [&](uint32_t i, float ms) {
         *trace_ms += ms; *trace_launches += 1;
-        if (h->trace_rounds && (i / 2u) % h->trace_rounds == 0u) { *round0_ms += ms; *round0_launches += 1; }   // launches are recorded batch by batch, round by round
-    }
-    h->trace_ev_used = 0;
+        if (h->trace_rounds && i % h->trace_rounds == 0u) { *round0_ms += ms; *round0_launches += 1; }   // launches are recorded batch by batch, round by round
+    });
 }
 
-// One knob table for the CGPT_WF_* environment variables (process-wide defaults, read when the context first needs its
-// wavefront state) and cgpt_set_tuning (per context, any time between renders).
-struct KnobDesc { const char* name; uint32_t WfTuning::*field; uint32_t lo, hi; };
-static const KnobDesc kKnobs[] = {
+// environment: CGPT_WF_<NAME>
+static const Knob<WfTuning> kKnobs[] = {
     { "pools", &WfTuning::pools, 1, kMaxPools },           { "batch", &WfTuning::batch, 0, 4096 },
     { "max_batch", &WfTuning::max_batch, 1, 4096 },         { "pool_paths_mi", &WfTuning::pool_paths_mi, 1, 1024 },
     { "budget_gib", &WfTuning::budget_gib, 1, 256 },       { "refill", &WfTuning::refill_idle, 1, 64 },
@@ -908,13 +896,7 @@ static WfHost* WfGetHost(cgpt_ctx* ctx)
     if (*slot) return static_cast<WfHost*>(*slot);
     WfHost* fresh = new (std::nothrow) WfHost;
     if (!fresh) { CtxFail(ctx, CGPT_ERR_INVALID, "out of host memory"); return nullptr; }
-    for (const KnobDesc& k : kKnobs) {
-        char env[64] = "CGPT_WF_";
-        size_t n = strlen(env);
-        for (const char* c = k.name; *c && n + 1 < sizeof(env); ++c) env[n++] = (char)toupper((unsigned char)*c);
-        env[n] = 0;
-        fresh->tune.*(k.field) = EnvU32(env, fresh->tune.*(k.field), k.lo, k.hi);
-    }
+    LoadKnobsFromEnv(kKnobs, "CGPT_WF_", fresh->tune);
     hipError_t e = hipEventCreateWithFlags(&fresh->begin, hipEventDisableTiming);
     for (uint32_t p = 0; p < kMaxPools && e == hipSuccess; ++p) {
         e = hipStreamCreateWithFlags(&fresh->streams[p], hipStreamNonBlocking);
@@ -931,37 +913,16 @@ static WfHost* WfGetHost(cgpt_ctx* ctx)
 
 int WavefrontSetTuning(cgpt_ctx* ctx, const char* name, uint32_t value)
 {
-    WfHost* h = WfGetHost(ctx);
-    if (!h) return CGPT_ERR_HIP;
-    for (const KnobDesc& k : kKnobs)
-        if (strcmp(k.name, name) == 0) {
-            if (value < k.lo || value > k.hi) return CtxFail(ctx, CGPT_ERR_INVALID, "tuning knob %s: %u outside [%u, %u]", name, value, k.lo, k.hi);
-            h->tune.*(k.field) = value;
-            return CGPT_OK;
-        }
-    return CtxFail(ctx, CGPT_ERR_INVALID, "unknown tuning knob '%s'", name);
+    WfHost* h = WfGetHost(ctx);                                               // created even for an unknown name
+    return h ? SetKnob(ctx, FindKnob(kKnobs, name), h->tune, name, value) : CGPT_ERR_HIP;
 }
 
 int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
 {
     hipStream_t stream = CtxStream(ctx);
-    void** slot = CtxWavefrontSlot(ctx);
-
-#define WF_TRY(expr)                                                                                     \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) { CtxFail(ctx, CGPT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); return -1; } \
-    } while (0)
-
-    if (!WfGetHost(ctx)) return -1;
-    WfHost* h = static_cast<WfHost*>(*slot);
-#ifdef CGPT_PHASE_CYCLES
-    const bool want_phase_stats = getenv("CGPT_WF_PROFILE") != nullptr;
-#else
-    const bool want_phase_stats = count && getenv("CGPT_WF_PROFILE") != nullptr;
-#endif
-    if (want_phase_stats && !h->phase_stats) WF_TRY(hipMalloc((void**)&h->phase_stats, 32 * sizeof(unsigned long long)));
-    if (h->phase_stats) WF_TRY(hipMemsetAsync(h->phase_stats, 0, 32 * sizeof(unsigned long long), stream));
+    WfHost* h = WfGetHost(ctx);
+    if (!h) return -1;
+    LAUNCH_TRY(ResetPhaseStats(h->phase_stats, 32, count, stream));
     const uint32_t rows = args_in.n_rows;
     const uint32_t tiles_x = (args_in.width + 7u) / 8u, tiles_y = (rows + 7u) / 8u;
     const uint64_t n_pixels64 = (uint64_t)tiles_x * tiles_y * 64u;             // padded to whole 8x8 tiles
@@ -970,46 +931,26 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
     const uint32_t n_pixels = (uint32_t)n_pixels64;
     const uint32_t rounds = (uint32_t)args_in.settings.max_ray_depth + 2u;    // extend rounds 0..max_depth, + the trailing shadow rays
 
-    if (h->n_cus == 0) {
-        int n_dev = 0, cus = 0;
-        WF_TRY(hipGetDevice(&n_dev));
-        WF_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, n_dev));
-        h->n_cus = (uint32_t)cus;
-    }
+    LAUNCH_TRY(QueryCuCount(h->n_cus));
     const uint32_t n_cus = h->n_cus;
     const uint32_t top_records = std::min(h->tune.top_records, args_in.scene.n_top_records);
     const size_t trace_lds = trace_lds_bytes(top_records);
     // persistent grids = the resident capacity of the chip for each kernel
     if (h->occupancy_lds != trace_lds) {
-        int b = 0;
-        if (trace_lds > 48u * 1024u) {                                        // more dynamic LDS than the default limit: opt in per kernel
-            WF_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&wf_trace<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)trace_lds));
-            WF_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&wf_trace<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)trace_lds));
-            WF_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&wf_trace<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)trace_lds));
-            WF_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&wf_trace<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)trace_lds));
-        }
+        LAUNCH_TRY(QueryOccupancy(&kTraceKernels[0][0], &h->trace_blocks_per_cu[0][0], 4, kTraceBlock, trace_lds));
         // shade: the round-0 and later-round instantiations share one grid size (one output segment per wave)
-        int b2 = 0;
-        WF_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (wf_trace<false, false>), kTraceBlock, trace_lds)); h->trace_blocks_per_cu[0][0] = (uint32_t)std::max(1, b);
-        WF_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (wf_trace<false, true>), kTraceBlock, trace_lds)); h->trace_blocks_per_cu[0][1] = (uint32_t)std::max(1, b);
-        WF_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (wf_trace<true, false>), kTraceBlock, trace_lds)); h->trace_blocks_per_cu[1][0] = (uint32_t)std::max(1, b);
-        WF_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (wf_trace<true, true>), kTraceBlock, trace_lds)); h->trace_blocks_per_cu[1][1] = (uint32_t)std::max(1, b);
-        WF_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (wf_shade<false, false>), 256, 0));
-        WF_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b2, (wf_shade<false, true>), 256, 0)); h->shade_blocks_per_cu[0][0] = (uint32_t)std::max(1, std::min(b, b2));
-        WF_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (wf_shade<true, false>), 256, 0));
-        WF_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b2, (wf_shade<true, true>), 256, 0)); h->shade_blocks_per_cu[1][0] = (uint32_t)std::max(1, std::min(b, b2));
-        WF_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (wf_shade<false, false, true>), 256, 0));
-        WF_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b2, (wf_shade<false, true, true>), 256, 0)); h->shade_blocks_per_cu[0][1] = (uint32_t)std::max(1, std::min(b, b2));
-        WF_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (wf_shade<true, false, true>), 256, 0));
-        WF_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b2, (wf_shade<true, true, true>), 256, 0)); h->shade_blocks_per_cu[1][1] = (uint32_t)std::max(1, std::min(b, b2));
+        uint32_t shade[2][2][2];
+        LAUNCH_TRY(QueryOccupancy(&kShadeKernels[0][0][0], &shade[0][0][0], 8, 256, 0));
+        for (int c = 0; c < 2; ++c)
+            for (int b = 0; b < 2; ++b) h->shade_blocks_per_cu[c][b] = std::min(shade[c][0][b], shade[c][1][b]);
         h->occupancy_lds = trace_lds;
     }
     const dim3 block(256);
-    const dim3 trace_grid_first(n_cus * std::min(h->tune.max_trace_blocks, h->trace_blocks_per_cu[count ? 1 : 0][1]));
-    const dim3 trace_grid_later(n_cus * std::min(h->tune.max_trace_blocks, h->trace_blocks_per_cu[count ? 1 : 0][0]));
+    const dim3 trace_grid_first(n_cus * std::min(h->tune.max_trace_blocks, h->trace_blocks_per_cu[count][1]));
+    const dim3 trace_grid_later(n_cus * std::min(h->tune.max_trace_blocks, h->trace_blocks_per_cu[count][0]));
     const bool brute = args_in.settings.render_mode != 2u;                    // the render has TracePath paths (ref: Main.cpp:719-729)
     const uint32_t brute_levels = brute ? (uint32_t)args_in.settings.max_ray_depth + 1u : 0u;
-    const dim3 shade_grid(n_cus * h->shade_blocks_per_cu[count ? 1 : 0][brute ? 1 : 0]);
+    const dim3 shade_grid(n_cus * h->shade_blocks_per_cu[count][brute]);
     // one output segment per shade wave, sized for the most 64-item blocks a wave can be handed
     const uint32_t n_segs = n_cus * std::max({ h->shade_blocks_per_cu[0][0], h->shade_blocks_per_cu[1][0], h->shade_blocks_per_cu[0][1], h->shade_blocks_per_cu[1][1] }) * 4u;
     const uint32_t min_shade_waves = n_cus * std::min({ h->shade_blocks_per_cu[0][0], h->shade_blocks_per_cu[1][0], h->shade_blocks_per_cu[0][1], h->shade_blocks_per_cu[1][1] }) * 4u;
@@ -1031,7 +972,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
     const size_t spec_entries = chains ? (size_t)n_pixels * h->tune.spec_keys : 0u;
     const size_t kBytesPerPath = 160 + 32 * (size_t)brute_levels;             // slots 96, state 32, lists 8, segments ~8-16; TracePath levels 32 each
     size_t free_b = 0, total_b = 0;
-    WF_TRY(hipMemGetInfo(&free_b, &total_b));
+    LAUNCH_TRY(hipMemGetInfo(&free_b, &total_b));
     const size_t held = (size_t)h->alloc_pools * ((size_t)h->alloc_cap * (160 + 32 * (size_t)h->alloc_brute_levels) + h->alloc_spec * sizeof(unsigned long long));
     const size_t budget = std::min<size_t>((size_t)h->tune.budget_gib << 30, (free_b + held) / 2);
     uint32_t batch = h->tune.batch;
@@ -1054,7 +995,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
         shade_chunk = banded ? h->tune.shade_chunk_banded : h->tune.shade_chunk;
         seg_cap = ((((cap + 63u) / 64u + shade_chunk - 1u) / shade_chunk + min_shade_waves - 1u) / min_shade_waves) * shade_chunk * 64u;   // whole chunks per wave
         if (h->alloc_overflow >= overflow_words && h->alloc_cap >= cap && h->alloc_segs >= n_segs && h->alloc_seg_cap >= seg_cap && h->alloc_pools >= n_pools && (!h->tune.sort || h->alloc_sort) && h->alloc_brute_levels >= brute_levels && h->alloc_pixels >= n_pixels && h->alloc_spec >= spec_entries) break;
-        WF_TRY(hipDeviceSynchronize());
+        LAUNCH_TRY(hipDeviceSynchronize());
         WfRelease(h);
         const size_t q = 2 * (size_t)cap * sizeof(float4);
         hipError_t err = hipSuccess;
@@ -1094,20 +1035,14 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
     }
 
     // event pairs for the trace launches of this render
-    const uint32_t ev_needed = 2u * n_batches * rounds;
-    if (h->trace_ev_cap < ev_needed) {
-        hipEvent_t* grown = static_cast<hipEvent_t*>(realloc(h->trace_ev, (size_t)ev_needed * sizeof(hipEvent_t)));
-        if (!grown) { CtxFail(ctx, CGPT_ERR_INVALID, "out of host memory"); return -1; }
-        h->trace_ev = grown;
-        for (; h->trace_ev_cap < ev_needed; ++h->trace_ev_cap) WF_TRY(hipEventCreate(&h->trace_ev[h->trace_ev_cap]));
-    }
-    h->trace_ev_used = 0; h->trace_rounds = rounds;
+    if (ReserveEvents(ctx, h->trace_ev, 2u * n_batches * rounds) != 0) return -1;
+    h->trace_rounds = rounds;
 
     // one-time host setup is over: the render's device time starts here (cgpt_stats.kernel_ms).  The pool streams start after
     // whatever the caller queued on the context's stream.
-    WF_TRY(hipEventRecord(CtxStartEvent(ctx), stream));
-    WF_TRY(hipEventRecord(h->begin, stream));
-    for (uint32_t p = 0; p < n_pools; ++p) WF_TRY(hipStreamWaitEvent(h->streams[p], h->begin, 0));
+    LAUNCH_TRY(hipEventRecord(CtxStartEvent(ctx), stream));
+    LAUNCH_TRY(hipEventRecord(h->begin, stream));
+    for (uint32_t p = 0; p < n_pools; ++p) LAUNCH_TRY(hipStreamWaitEvent(h->streams[p], h->begin, 0));
 
     int launches = 0;
     DevRenderArgs args = args_in;
@@ -1120,11 +1055,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
         const uint32_t bfirst = args_in.first_sample + done;
         WfDev wf = h->dev[p];
         wf.cap = h->alloc_cap; wf.g.n_pixels = n_pixels; wf.n_paths = n_pixels * bn;
-#ifdef CGPT_PHASE_CYCLES
-        wf.phase_stats = h->phase_stats;
-#else
-        wf.phase_stats = count ? h->phase_stats : nullptr;
-#endif
+        wf.phase_stats = PhaseStatsArg(h->phase_stats, count);
         wf.rot_trace[0] = CoprimeRotation(trace_grid_later.x * (kTraceBlock / 64u), std::max(1u, tiles_x * tiles_y / h->tune.trace_chunk));
         wf.rot_trace[1] = CoprimeRotation(trace_grid_first.x * (kTraceBlock / 64u), std::max(1u, tiles_x * tiles_y / h->tune.trace_chunk));
         wf.rot_shade = CoprimeRotation(shade_grid.x * 4u, std::max(1u, tiles_x * tiles_y / shade_chunk));
@@ -1141,55 +1072,42 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
         wf.retire_misses = h->tune.retire_misses && args_in.settings.debug_mode == 0u ? 1u : 0u;
         if (!chains) wf.spec_tab = nullptr;
         wf.spec_keys = h->tune.spec_keys;
-        if (k < n_pools) WF_TRY(hipMemsetAsync(wf.seg_count, 0, 2 * (size_t)kMaxKeys * wf.n_segs * sizeof(uint32_t), st));
+        if (k < n_pools) LAUNCH_TRY(hipMemsetAsync(wf.seg_count, 0, 2 * (size_t)kMaxKeys * wf.n_segs * sizeof(uint32_t), st));
         for (uint32_t r = 0; r < rounds; ++r) {
             const bool first = r == 0u;
-            if (h->tune.trace_events) WF_TRY(hipEventRecord(h->trace_ev[h->trace_ev_used++], st));
-            const dim3 trace_grid = first ? trace_grid_first : trace_grid_later;
-            if (count && first) hipLaunchKernelGGL((wf_trace<true, true>), trace_grid, dim3(kTraceBlock), trace_lds, st, args, wf, bfirst, tt);
-            else if (count) hipLaunchKernelGGL((wf_trace<true, false>), trace_grid, dim3(kTraceBlock), trace_lds, st, args, wf, bfirst, tt);
-            else if (first) hipLaunchKernelGGL((wf_trace<false, true>), trace_grid, dim3(kTraceBlock), trace_lds, st, args, wf, bfirst, tt);
-            else hipLaunchKernelGGL((wf_trace<false, false>), trace_grid, dim3(kTraceBlock), trace_lds, st, args, wf, bfirst, tt);
-            if (h->tune.trace_events) WF_TRY(hipEventRecord(h->trace_ev[h->trace_ev_used++], st));
+            if (h->tune.trace_events) LAUNCH_TRY(hipEventRecord(NextEvent(h->trace_ev), st));
+            hipLaunchKernelGGL(kTraceKernels[count][first], first ? trace_grid_first : trace_grid_later, dim3(kTraceBlock), trace_lds, st, args, wf, bfirst, tt);
+            if (h->tune.trace_events) LAUNCH_TRY(hipEventRecord(NextEvent(h->trace_ev), st));
             ++launches;
             if (r + 1u < rounds) {
                 if (wf.spec_tab) {                                            // a fresh epoch frees every entry; after spec_epochs of them, clear
                     if (++h->spec_epoch[p] > h->tune.spec_epochs) {           // the whole table: entries past this call's n_pixels * spec_keys
                                                                               // hold tags of the old epochs too, written by larger layouts
-                        WF_TRY(hipMemsetAsync(wf.spec_tab, 0, h->alloc_spec * sizeof(unsigned long long), st));
+                        LAUNCH_TRY(hipMemsetAsync(wf.spec_tab, 0, h->alloc_spec * sizeof(unsigned long long), st));
                         h->spec_epoch[p] = 1u;
                     }
                     wf.spec_epoch = h->spec_epoch[p];
                 }
-                if (brute) {
-                    if (count && first) hipLaunchKernelGGL((wf_shade<true, true, true>), shade_grid, block, 0, st, args, wf, bfirst);
-                    else if (count) hipLaunchKernelGGL((wf_shade<true, false, true>), shade_grid, block, 0, st, args, wf, bfirst);
-                    else if (first) hipLaunchKernelGGL((wf_shade<false, true, true>), shade_grid, block, 0, st, args, wf, bfirst);
-                    else hipLaunchKernelGGL((wf_shade<false, false, true>), shade_grid, block, 0, st, args, wf, bfirst);
-                }
-                else if (count && first) hipLaunchKernelGGL((wf_shade<true, true>), shade_grid, block, 0, st, args, wf, bfirst);
-                else if (count) hipLaunchKernelGGL((wf_shade<true, false>), shade_grid, block, 0, st, args, wf, bfirst);
-                else if (first) hipLaunchKernelGGL((wf_shade<false, true>), shade_grid, block, 0, st, args, wf, bfirst);
-                else hipLaunchKernelGGL((wf_shade<false, false>), shade_grid, block, 0, st, args, wf, bfirst);
+                hipLaunchKernelGGL(kShadeKernels[count][first][brute], shade_grid, block, 0, st, args, wf, bfirst);
                 hipLaunchKernelGGL(wf_plan, dim3(2u * wf.n_keys), dim3(256), 0, st, wf);
                 hipLaunchKernelGGL(wf_gather, dim3(std::min(2u * wf.n_segs, n_cus * 16u)), block, 0, st, wf);
                 launches += 3;
             }
         }
         // accumulate in sample order: batch k after batch k-1
-        if (k > 0) WF_TRY(hipStreamWaitEvent(st, h->acc_done[(k - 1u) % n_pools], 0));
+        if (k > 0) LAUNCH_TRY(hipStreamWaitEvent(st, h->acc_done[(k - 1u) % n_pools], 0));
         hipLaunchKernelGGL(wf_accumulate, dim3(std::min((n_pixels + 255u) / 256u, n_cus * 8u)), block, 0, st, args, wf, bfirst, bn);
         ++launches;
-        WF_TRY(hipEventRecord(h->acc_done[p], st));
-        WF_TRY(hipGetLastError());
+        LAUNCH_TRY(hipEventRecord(h->acc_done[p], st));
+        LAUNCH_TRY(hipGetLastError());
     }
     // the context's stream continues after the last accumulate (which transitively follows all the others)
-    if (k > 0) WF_TRY(hipStreamWaitEvent(stream, h->acc_done[(k - 1u) % n_pools], 0));
+    if (k > 0) LAUNCH_TRY(hipStreamWaitEvent(stream, h->acc_done[(k - 1u) % n_pools], 0));
 #ifdef CGPT_PHASE_CYCLES
     if (!count && h->phase_stats) {                                           // diagnostic build: cycles of the later-round trace waves by phase
         unsigned long long ps[32];
-        WF_TRY(hipStreamSynchronize(stream));
-        WF_TRY(hipMemcpy(ps, h->phase_stats, sizeof(ps), hipMemcpyDeviceToHost));
+        LAUNCH_TRY(hipStreamSynchronize(stream));
+        LAUNCH_TRY(hipMemcpy(ps, h->phase_stats, sizeof(ps), hipMemcpyDeviceToHost));
         const double tot = (double)ps[8];
         fprintf(stderr, "[wf cycles] later-round trace: %llu waves, %.0f Mcyc/wave | refill %.3f inner %.3f leaf %.3f object %.3f other %.3f | cycles per wave-step: inner %.0f (%.1f lanes, %.2f from LDS) leaf %.0f (%.1f lanes) object %.0f (%.1f lanes)\n",
                 ps[20], ps[20] ? tot / ps[20] / 1e6 : 0.0, ps[9] / tot, ps[10] / tot, ps[11] / tot, ps[12] / tot, 1.0 - (ps[9] + ps[10] + ps[11] + ps[12]) / tot,
@@ -1202,15 +1120,14 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
 #endif
     if (count && h->phase_stats) {                                            // development aid: how full the steps were
         unsigned long long ps[8];
-        WF_TRY(hipStreamSynchronize(stream));
-        WF_TRY(hipMemcpy(ps, h->phase_stats, sizeof(ps), hipMemcpyDeviceToHost));
+        LAUNCH_TRY(hipStreamSynchronize(stream));
+        LAUNCH_TRY(hipMemcpy(ps, h->phase_stats, sizeof(ps), hipMemcpyDeviceToHost));
         DevCounters c;
-        WF_TRY(hipMemcpy(&c, args_in.counters, sizeof(c), hipMemcpyDeviceToHost));
+        LAUNCH_TRY(hipMemcpy(&c, args_in.counters, sizeof(c), hipMemcpyDeviceToHost));
         fprintf(stderr, "[wf profile] rays %llu | inner: %llu wave steps, %.1f lanes/step | leaf: %llu wave steps, %.1f lanes/step | object: %llu wave steps, %.1f lanes/step | votes %llu refills %llu\n",
                 c.traced_rays, ps[0], ps[0] ? (double)c.inner_steps / ps[0] : 0.0, ps[1], ps[1] ? (double)ps[6] / ps[1] : 0.0,
                 ps[2], ps[2] ? (double)ps[3] / ps[2] : 0.0, ps[4], ps[5]);
     }
-#undef WF_TRY
     return launches;
 }
 
