@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "cpugpupt_abi.h"
+#include "minmax_std.h"
 
 namespace cgpt {
 
@@ -47,8 +48,6 @@ namespace {
 constexpr uint32_t kBuildThreads = 256;
 
 struct F3 { float x, y, z; };
-__device__ __host__ inline float min_std(float a, float b) { return (b < a) ? b : a; }   // std::min(a,b), ref: MathLib.h:95
-__device__ __host__ inline float max_std(float a, float b) { return (a < b) ? b : a; }   // std::max(a,b), ref: MathLib.h:96
 __device__ inline F3 f3min(F3 a, F3 b) { return { min_std(a.x, b.x), min_std(a.y, b.y), min_std(a.z, b.z) }; }
 __device__ inline F3 f3max(F3 a, F3 b) { return { max_std(a.x, b.x), max_std(a.y, b.y), max_std(a.z, b.z) }; }
 __device__ inline float axis_of(F3 v, uint32_t a) { return a == 0 ? v.x : (a == 1 ? v.y : v.z); }
@@ -594,15 +593,15 @@ __global__ void __launch_bounds__(kBuildThreads) root_bounds(BuildArrays A, uint
     }
 }
 
-float HostTriangleArea(const cgpt_triangle& t)                                // Heron, ref: Primitives.cpp:270-278
+}  // namespace
+
+float HostTriangleArea(const cgpt_triangle& t)                                // Heron, ref: Primitives.cpp:270-278 (also refit.hip)
 {
     auto len = [](const float a[3], const float b[3]) { const float x = a[0] - b[0], y = a[1] - b[1], z = a[2] - b[2]; return sqrtf(x * x + y * y + z * z); };
     const float a = len(t.v1.pos, t.v0.pos), b = len(t.v2.pos, t.v0.pos), c = len(t.v2.pos, t.v1.pos);
     const float s = (a + b + c) / 2.0f;
     return sqrtf(s * (s - a) * (s - b) * (s - c));
 }
-
-}  // namespace
 
 }  // namespace cgpt
 

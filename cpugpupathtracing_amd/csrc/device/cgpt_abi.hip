@@ -106,6 +106,9 @@ void FreeScene(cgpt_ctx* ctx)
     (void)hipFree(ctx->d_materials); (void)hipFree(ctx->d_objects); (void)hipFree(ctx->d_obj_trace); (void)hipFree(ctx->d_lights);
     ctx->d_node_pairs = ctx->d_tri_leaf = ctx->d_tri_orig = ctx->d_tri_normal = ctx->d_materials = nullptr;
     ctx->d_objects = nullptr; ctx->d_obj_trace = nullptr; ctx->d_lights = nullptr;
+    (void)hipFree(ctx->d_refit_levels); (void)hipFree(ctx->d_refit_staging);
+    ctx->d_refit_levels = nullptr; ctx->d_refit_staging = nullptr; ctx->refit_staging_tris = 0;
+    ctx->h_objects.clear(); ctx->refit_objects.clear(); ctx->record_perm.clear();
     ctx->has_scene = false;
 }
 
@@ -154,6 +157,9 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
     std::vector<float4> pairs, tri_leaf, tri_orig, tri_normal, mats;
     std::vector<DevObject> objs(sd.n_objects);
     uint32_t max_tree_depth = 0;
+    // for in-place edits (refit.hip): per object where its records live, and the depth of every child-pair record (0xFF: not reached)
+    std::vector<RefitObject> refit(sd.n_objects);
+    std::vector<uint8_t> rec_depth;
 
     // leaf-record order (device_scene.h): the triangles of the small meshes first, then the rest in object order; a triangle
     // object has one leaf record, like a one-triangle mesh
@@ -212,6 +218,7 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
             PackOrigTri(tr, tri_orig.data() + 3 * (size_t)orig_base);
             tri_normal.push_back(F4(tr.v0.normal[0], tr.v0.normal[1], tr.v0.normal[2], 0.0f));   // TriangleNormal, ref: Primitives.cpp:148-151
             d.root_code = kLeafBit | leaf_base; d.tri_base = orig_base; d.n_tris = 1;
+            refit[oi].tri_count = 1; refit[oi].leaf_base = leaf_base;
             continue;
         }
         if (o.kind != CGPT_OBJECT_MESH)
@@ -249,6 +256,7 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
         uint32_t root_code;
         if (!code_of(0, root_code)) return Fail(ctx, CGPT_ERR_INVALID, "object %u: malformed BVH root", oi);
         d.root_code = root_code; d.tri_base = orig_base; d.n_tris = o.tri_count; d.total_area = o.total_area;
+        refit[oi].node_count = o.node_count; refit[oi].tri_count = o.tri_count; refit[oi].leaf_base = leaf_base; refit[oi].pair_base = pair_base;
 
         // leaf-ordered triangle records
         float4* leaf = tri_leaf.data() + 3 * (size_t)leaf_base;            // sized above
@@ -268,6 +276,7 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
 
         // child-pair records + leaf terminators; iterative DFS from the root also measures the real depth
         pairs.resize(pairs.size() + 4 * (size_t)(o.node_count / 2), F4(0, 0, 0, 0));
+        rec_depth.resize(pairs.size() / 4, 0xFF);
         float4* pr = pairs.data() + 4 * (size_t)pair_base;
         std::vector<uint8_t> covered(o.tri_count, 0);
         struct Item { uint32_t node, depth; };
@@ -293,6 +302,7 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
             const uint32_t L = n.left_first;
             if (!code_of(L, lc) || !code_of(L + 1, rc)) return Fail(ctx, CGPT_ERR_INVALID, "object %u: malformed children of node %u", oi, it.node);
             float4* rec = pr + 4 * (size_t)((L - 1) / 2);
+            rec_depth[pair_base + (L - 1) / 2] = (uint8_t)std::min<uint32_t>(it.depth, 0xFEu);   // > 63 is refused below
             const cgpt_bvh_node& l = nodes[L]; const cgpt_bvh_node& r = nodes[L + 1];
             // left / right interleaved per component: one packed-f32 instruction handles both children (device_scene.h)
             rec[0] = F4(l.aabb_min[0], r.aabb_min[0], l.aabb_min[1], r.aabb_min[1]);
@@ -326,6 +336,7 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
     // everything breadth-first; =dfs: nothing renumbered, for experiments).
     const uint32_t n_records = (uint32_t)(pairs.size() / 4);
     uint32_t n_top_records = 0;
+    std::vector<uint32_t> perm;                                                 // stays empty when nothing is renumbered
     {
         const char* mode_env = getenv("CGPT_NODE_ORDER");
         const std::string mode = mode_env ? mode_env : "top";
@@ -341,7 +352,7 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
             if ((rc & kLeafBit) == 0u) bfs.push_back(rc);
         }
         if (mode != "dfs" && n_records > 0) {
-            std::vector<uint32_t> perm(n_records, 0xFFFFFFFFu);
+            perm.assign(n_records, 0xFFFFFFFFu);
             uint32_t next = 0;
             for (size_t i = 0; i < bfs.size() && i < bfs_limit; ++i) perm[bfs[i]] = next++;
             for (uint32_t r = 0; r < n_records; ++r) if (perm[r] == 0xFFFFFFFFu) perm[r] = next++;
@@ -362,15 +373,31 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
         }
     }
 
+    // each mesh's child-pair records grouped by depth, in their final numbering: the refit's bound pass runs one level after the other,
+    // deepest first (refit.hip)
+    std::vector<uint32_t> levels;
+    levels.reserve(n_records);
+    for (uint32_t oi = 0; oi < sd.n_objects; ++oi) {
+        RefitObject& ro = refit[oi];
+        if (objs[oi].kind != CGPT_OBJECT_MESH || ro.node_count < 3) continue;   // a leaf-rooted mesh has no records
+        uint32_t count[66] = { 0 };
+        uint32_t n_levels = 0;
+        const uint32_t r0 = ro.pair_base, r1 = ro.pair_base + ro.node_count / 2;
+        for (uint32_t r = r0; r < r1; ++r)
+            if (rec_depth[r] != 0xFF) { ++count[rec_depth[r] + 1]; n_levels = std::max<uint32_t>(n_levels, rec_depth[r] + 1u); }
+        for (uint32_t d = 0; d < n_levels; ++d) count[d + 1] += count[d];
+        ro.level_begin = (uint32_t)levels.size();
+        ro.level_offsets.assign(count, count + n_levels + 1);
+        levels.resize(levels.size() + count[n_levels]);
+        uint32_t* out = levels.data() + ro.level_begin;
+        for (uint32_t r = r0; r < r1; ++r)
+            if (rec_depth[r] != 0xFF) out[count[rec_depth[r]]++] = perm.empty() ? r : perm[r];
+    }
+
     // per-object records for the trace kernel's object phase (device_scene.h: obj_trace)
     std::vector<float4> obj_trace(2 * (size_t)sd.n_objects);
     for (uint32_t oi = 0; oi < sd.n_objects; ++oi) {
-        const DevObject& d = objs[oi];
-        float4& q0 = obj_trace[2 * (size_t)oi]; float4& q1 = obj_trace[2 * (size_t)oi + 1];
-        q0 = F4(AsFloat(d.kind), 0.0f, 0.0f, 0.0f); q1 = F4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (d.kind == CGPT_OBJECT_MESH || d.kind == CGPT_OBJECT_TRIANGLE) { q0.x = AsFloat(CGPT_OBJECT_MESH); q0.y = AsFloat(d.root_code); }   // a triangle: a leaf-rooted mesh (device_scene.h)
-        else if (d.kind == CGPT_OBJECT_SPHERE) { q0.y = d.sphere_center[0]; q0.z = d.sphere_center[1]; q0.w = d.sphere_center[2]; q1.x = d.sphere_radius_sq; }
-        else { q0.y = d.plane_normal[0]; q0.z = d.plane_normal[1]; q0.w = d.plane_normal[2]; q1.x = d.plane_point[0]; q1.y = d.plane_point[1]; q1.z = d.plane_point[2]; }
+        PackObjTrace(objs[oi], obj_trace[2 * (size_t)oi], obj_trace[2 * (size_t)oi + 1]);
     }
 
     FreeScene(ctx);
@@ -383,6 +410,8 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
     if ((rc = UploadArray(ctx, &ctx->d_objects, objs)) != CGPT_OK) return rc;
     if ((rc = UploadArray(ctx, &ctx->d_obj_trace, obj_trace)) != CGPT_OK) return rc;
     if ((rc = UploadArray(ctx, &ctx->d_lights, lights)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, &ctx->d_refit_levels, levels)) != CGPT_OK) return rc;
+    ctx->h_objects.swap(objs); ctx->refit_objects.swap(refit); ctx->record_perm.swap(perm);
 
     ctx->scene.node_pairs = ctx->d_node_pairs; ctx->scene.tri_leaf = ctx->d_tri_leaf; ctx->scene.tri_orig = ctx->d_tri_orig; ctx->scene.tri_normal = ctx->d_tri_normal;
     ctx->scene.materials = ctx->d_materials; ctx->scene.objects = ctx->d_objects; ctx->scene.obj_trace = ctx->d_obj_trace; ctx->scene.lights = ctx->d_lights;

@@ -355,6 +355,35 @@ int GroupUpdateMaterials(cgpt_ctx* ctx, const cgpt_material* materials, uint32_t
     return CGPT_OK;
 }
 
+// In-place scene edits run on every member.  A member validates before its first device write and all hold the same scene, so only the
+// first member can refuse the call; any later failure (or a first member that dropped its scene) leaves the members with different
+// geometry, and the whole group's scene is dropped: the next render returns CGPT_ERR_NO_SCENE.
+template <class F>
+int GroupEdit(cgpt_ctx* ctx, F&& edit)
+{
+    std::vector<cgpt_ctx*>& ms = ctx->group->members;
+    for (size_t r = 0; r < ms.size(); ++r) {
+        const int rc = edit(ms[r], r == 0);
+        if (rc == CGPT_OK) continue;
+        if (r > 0 || !ms[0]->has_scene) {
+            for (cgpt_ctx* m : ms) m->has_scene = false;
+            ctx->has_scene = false;
+        }
+        return Propagate(ctx, ms[r], rc);
+    }
+    return CGPT_OK;
+}
+
+int GroupRefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris, float* total_area_out)
+{
+    return GroupEdit(ctx, [&](cgpt_ctx* m, bool first) { return cgpt_scene_refit_mesh(m, obj_index, triangles, n_tris, first ? total_area_out : nullptr); });
+}
+
+int GroupUpdatePrimitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_object* obj)
+{
+    return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_update_primitive(m, obj_index, obj); });
+}
+
 int GroupRender(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p)
 {
     DeviceGroup* g = ctx->group;

@@ -285,6 +285,49 @@ int cgpth_scene_rebuild_bvh(cgpth_scene* scene, uint32_t obj_index, int build_op
     });
 }
 
+static const char* KindName(const Object& o)
+{
+    return o.has_bvh ? "mesh" : o.kind == CGPT_OBJECT_SPHERE ? "sphere" : o.kind == CGPT_OBJECT_PLANE ? "plane" : "triangle object";
+}
+
+int cgpth_scene_refit_mesh(cgpth_scene* scene, uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris)
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        if (!scene) return Fail("scene is null");
+        if (obj_index >= scene->scene.objects.size())
+            return Fail("object " + std::to_string(obj_index) + " out of range (" + std::to_string(scene->scene.objects.size()) + " objects)");
+        Object& o = scene->scene.objects[obj_index];
+        if (!o.has_bvh && o.kind != CGPT_OBJECT_TRIANGLE)
+            return Fail("object " + std::to_string(obj_index) + " is a " + KindName(o) + ": it has no triangles (update_primitive edits it)");
+        if (!triangles) return Fail("triangles is null");
+        const uint32_t n = o.has_bvh ? o.bvh.NumTriangles() : 1u;
+        if (n_tris != n)
+            return Fail("object " + std::to_string(obj_index) + " has " + std::to_string(n) + " triangles, got " + std::to_string(n_tris) + " (a refit keeps the topology)");
+        if (o.has_bvh) { if (!o.bvh.Refit(triangles, n_tris)) return Fail("refit failed"); }
+        else o.triangle = triangles[0];
+        return CGPT_OK;
+    });
+}
+
+int cgpth_scene_update_primitive(cgpth_scene* scene, uint32_t obj_index, const cgpt_object* obj)
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        if (!scene) return Fail("scene is null");
+        if (obj_index >= scene->scene.objects.size())
+            return Fail("object " + std::to_string(obj_index) + " out of range (" + std::to_string(scene->scene.objects.size()) + " objects)");
+        Object& o = scene->scene.objects[obj_index];
+        if (!obj) return Fail("obj is null");
+        if (o.has_bvh || (o.kind != CGPT_OBJECT_SPHERE && o.kind != CGPT_OBJECT_PLANE))
+            return Fail("object " + std::to_string(obj_index) + " is a " + KindName(o) + ": refit_mesh edits it");
+        if (obj->kind != o.kind) return Fail("object " + std::to_string(obj_index) + " is a " + KindName(o) + ", got kind " + std::to_string(obj->kind));
+        if (obj->mat_index != o.mat_index)
+            return Fail("object " + std::to_string(obj_index) + " has material " + std::to_string(o.mat_index) + ", got " + std::to_string(obj->mat_index) + " (materials are not changed here)");
+        if (o.kind == CGPT_OBJECT_SPHERE) o.sphere = Sphere{ V(obj->sphere_center), obj->sphere_radius };
+        else o.plane = Plane{ V(obj->plane_normal), V(obj->plane_point) };
+        return CGPT_OK;
+    });
+}
+
 int cgpth_scene_bvh_info(const cgpth_scene* scene, uint32_t obj_index, cgpth_bvh_info* out)
 {
     return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {

@@ -54,12 +54,42 @@ bool MeshBVH::SetTriangles(const std::vector<cgpt_vertex>& vertices, const std::
         t.v2 = vertices[indices[3 * i + 2]];
         total_area_ += TriangleArea(t);                                       // ref: BVH.cpp:22
         tri_indices_[i] = (uint32_t)i;
-        Vec3 p0 = P(t.v0.pos), p1 = P(t.v1.pos), p2 = P(t.v2.pos);
-        centroids_[i] = (p0 + p1 + p2) * 0.3333f;                             // ref: Primitives.cpp:255-258 (SURVEY A-10)
-        tri_bounds_[i].lo = vmin(vmin(p0, p1), p2);                           // ref: Primitives.cpp:232-243
-        tri_bounds_[i].hi = vmax(vmax(p0, p1), p2);
+        CacheTriangle((uint32_t)i);
     }
     nodes_.assign(2 * n - 1, cgpt_bvh_node{});                                // ref: BVH.cpp:37
+    return true;
+}
+
+void MeshBVH::CacheTriangle(uint32_t i)
+{
+    const cgpt_triangle& t = triangles_[i];
+    Vec3 p0 = P(t.v0.pos), p1 = P(t.v1.pos), p2 = P(t.v2.pos);
+    centroids_[i] = (p0 + p1 + p2) * 0.3333f;                                 // ref: Primitives.cpp:255-258 (SURVEY A-10)
+    tri_bounds_[i].lo = vmin(vmin(p0, p1), p2);                               // ref: Primitives.cpp:232-243
+    tri_bounds_[i].hi = vmax(vmax(p0, p1), p2);
+}
+
+bool MeshBVH::Refit(const cgpt_triangle* triangles, uint32_t n)
+{
+    if (!triangles || triangles_.empty() || n != triangles_.size()) return false;
+    float area = 0.0f;
+    for (uint32_t i = 0; i < n; ++i) {
+        triangles_[i] = triangles[i];
+        area += TriangleArea(triangles_[i]);                                  // ref: BVH.cpp:22
+        CacheTriangle(i);
+    }
+    total_area_ = area;
+    // children have larger indices than their parent (WellFormed): a reverse sweep sees both children of a node before the node
+    for (uint32_t i = nodes_used_; i-- > 0;) {
+        cgpt_bvh_node& node = nodes_[i];
+        if (node.prim_count > 0) { FitNode(i); continue; }
+        const cgpt_bvh_node& l = nodes_[node.left_first];
+        const cgpt_bvh_node& r = nodes_[node.left_first + 1];
+        for (int k = 0; k < 3; ++k) {
+            node.aabb_min[k] = min_std(l.aabb_min[k], r.aabb_min[k]);
+            node.aabb_max[k] = max_std(l.aabb_max[k], r.aabb_max[k]);
+        }
+    }
     return true;
 }
 

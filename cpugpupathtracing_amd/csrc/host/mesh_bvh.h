@@ -41,6 +41,11 @@ public:
     bool RebuildWith(BuildOption option, const TreeBuilder& build);
     // ref: BVH.cpp:47-59: re-split over the current triangle order (the order is NOT reset, as in the reference)
     void Rebuild(BuildOption option);
+    // BVH refit (the reference's README, "Planned"): n new triangles in original order (n == NumTriangles()), tree kept.  Triangles,
+    // per-triangle bounds, centroids and total_area follow them; every node's bounds become CalculateNodeBounds (ref: BVH.cpp:188-202)
+    // over its current range, computed bottom-up: an inner node's is min_std / max_std of its children's, left first, which is the
+    // sequential fold bit for bit.  Returns false (tree unchanged) on a count mismatch.
+    bool Refit(const cgpt_triangle* triangles, uint32_t n);
 
     const cgpt_triangle& GetTriangle(uint32_t index) const { return triangles_[index]; }
     uint32_t NumTriangles() const { return (uint32_t)triangles_.size(); }
@@ -57,6 +62,7 @@ public:
 private:
     struct Bounds { Vec3 lo{ 1e30f }, hi{ -1e30f }; };
     bool SetTriangles(const std::vector<cgpt_vertex>& vertices, const std::vector<uint32_t>& indices);
+    void CacheTriangle(uint32_t i);   // centroid and bounds of triangles_[i]
     static bool WellFormed(const cgpt_bvh_node* nodes, uint32_t n_nodes, const uint32_t* tri_indices, uint32_t n);
     void BuildTree();
     void FitNode(uint32_t node_index);

@@ -11,7 +11,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _native as N
-from .scene import Scene, Settings
+from .scene import Scene, Settings, _triangle_ptr, _triangle_rows, primitive_abi
 
 
 class DeviceError(RuntimeError):
@@ -34,6 +34,7 @@ class Renderer:
         self.devices = devices
         self.is_group = len(devices) > 1 or bool(flags & N.CTX_FORCE_COLLECTIVE)
         self.scene: Optional[Scene] = None
+        self._node_counts = []
         self.width = self.height = 0
         self.rows: Tuple[int, int] = (0, 0)
         self.interleave: Optional[Tuple[int, int, int]] = None
@@ -51,10 +52,35 @@ class Renderer:
         desc = scene.flatten()
         self._check(self.L.cgpt_scene_upload(self._ctx, C.byref(desc)))
         self.scene = scene
+        self._node_counts = [desc.objects[k].node_count for k in range(desc.n_objects)]   # the uploaded trees (export_bvh)
 
     def update_materials(self, scene: Scene):
         desc = scene.flatten()
         self._check(self.L.cgpt_scene_update_materials(self._ctx, desc.materials, desc.n_materials))
+
+    def refit_mesh(self, obj_index: int, triangles) -> float:
+        """BVH refit on the device (cgpt_scene_refit_mesh): new triangles for uploaded mesh `obj_index` (or triangle object), in its
+        original order, as many as were uploaded (scene.triangles_from_arrays); the tree is kept, its bounds follow.  Returns the new
+        total_area.  Only the device copy changes: the host Scene is not touched (Scene.refit_mesh does the same there).  Call
+        reset_accumulator() before the next frame, as the reference does after an edit."""
+        rows = _triangle_rows(triangles)
+        area = C.c_float()
+        self._check(self.L.cgpt_scene_refit_mesh(self._ctx, obj_index, _triangle_ptr(rows), rows.shape[0], C.byref(area)))
+        return area.value
+
+    def export_bvh(self, obj_index: int) -> np.ndarray:
+        """The device's tree of mesh `obj_index` as it is now (after refits): nodes[n,8] uint32 words in the reference's 32-byte layout
+        and numbering, as Scene.bvh_export returns them.  Reads the device only; the host Scene is not touched."""
+        nodes = np.zeros((self._node_counts[obj_index] if obj_index < len(self._node_counts) else 0, 8), np.uint32)
+        self._check(self.L.cgpt_scene_export_bvh(self._ctx, obj_index, nodes.ctypes.data_as(C.POINTER(N.BvhNode)), nodes.shape[0]))
+        return nodes
+
+    def update_primitive(self, obj_index: int, mat_index: int, center=None, radius=None, normal=None, point=None):
+        """cgpt_scene_update_primitive: a sphere's center and radius, or a plane's normal and point (mat_index: the object's
+        uploaded material, which does not change).  Only the device copy changes: the host Scene is not touched."""
+        kind = N.OBJECT_SPHERE if center is not None or radius is not None else N.OBJECT_PLANE
+        abi = primitive_abi(kind, mat_index, center, radius, normal, point)
+        self._check(self.L.cgpt_scene_update_primitive(self._ctx, obj_index, C.byref(abi)))
 
     def render(self, width: int, height: int, n_samples: int = 1, seed: int = 0x12345678, rows: Optional[Tuple[int, int]] = None,
                kernel: int = N.KERNEL_AUTO, counters: bool = False, settings: Optional[Settings] = None,

@@ -72,6 +72,47 @@ REFERENCE_MATERIALS = (
 )
 
 
+def triangles_from_arrays(vertices, indices) -> np.ndarray:
+    """The cgpt_triangle array (n x 18 float32: v0, v1, v2, each pos.xyz + normal.xyz, 72 bytes a row) of a mesh given as vertices
+    (m x 6: pos.xyz, normal.xyz) and indices (3n), in the mesh's original triangle order -- what Mesh + BVH::Build turn into
+    m_triangles (ref: Source/BVH.cpp:15-20) and what refit_mesh takes."""
+    v = np.ascontiguousarray(vertices, dtype=np.float32)
+    i = np.ascontiguousarray(indices, dtype=np.uint32).ravel()
+    if v.ndim != 2 or v.shape[1] != 6 or i.size % 3:
+        raise ValueError("vertices must be m x 6 (pos, normal) and indices a multiple of 3")
+    if i.size and int(i.max()) >= v.shape[0]:
+        raise ValueError("index out of range")
+    return np.ascontiguousarray(v[i].reshape(-1, 18))
+
+
+def _triangle_rows(triangles) -> np.ndarray:
+    t = np.ascontiguousarray(triangles, dtype=np.float32)
+    if t.ndim < 1 or t.size % 18:
+        raise ValueError("triangles must hold 18 floats per triangle (see triangles_from_arrays)")
+    return t.reshape(-1, 18)
+
+
+def _triangle_ptr(rows: np.ndarray):
+    return rows.ctypes.data_as(C.POINTER(N.Triangle))
+
+
+def primitive_abi(kind: int, mat_index: int, center=None, radius=None, normal=None, point=None) -> N.Object:
+    """A cgpt_object for update_primitive: a sphere (center, radius) or a plane (normal, point)."""
+    o = N.Object()
+    o.kind, o.mat_index = kind, mat_index
+    if kind == N.OBJECT_SPHERE:
+        if center is None or radius is None:
+            raise ValueError("a sphere takes center and radius")
+        o.sphere_center = _f3(center); o.sphere_radius = float(radius)
+    elif kind == N.OBJECT_PLANE:
+        if normal is None or point is None:
+            raise ValueError("a plane takes normal and point")
+        o.plane_normal = _f3(normal); o.plane_point = _f3(point)
+    else:
+        raise ValueError(f"update_primitive edits spheres and planes, not kind {kind}")
+    return o
+
+
 class Mesh:
     """ref: Include/Primitives.h:24-28; vertices = n x (pos.xyz, normal.xyz) float32, indices uint32"""
 
@@ -213,6 +254,31 @@ class Scene:
             _host_check(N.lib().cgpth_scene_rebuild_bvh_device(self._h, obj_index, build_option, device_builder._ctx), "rebuild_bvh")
         else:
             _host_check(N.lib().cgpth_scene_rebuild_bvh(self._h, obj_index, build_option), "rebuild_bvh")
+
+    def refit_mesh(self, obj_index: int, triangles):
+        """BVH refit of a mesh (or the replacement of a triangle object): triangles in the object's original order, as many as it has
+        (triangles_from_arrays).  The tree is kept; node bounds, total_area, centroids follow the new triangles (cgpth_scene_refit_mesh)."""
+        rows = _triangle_rows(triangles)
+        _host_check(N.lib().cgpth_scene_refit_mesh(self._h, obj_index, _triangle_ptr(rows), rows.shape[0]), "refit_mesh")
+
+    def update_primitive(self, obj_index: int, center=None, radius=None, normal=None, point=None):
+        """Primitive::RenderImGui's sliders (ref: Primitives.cpp:385-410): a sphere's center / radius or a plane's normal / point;
+        what is not given keeps its current value."""
+        desc = self.flatten()
+        if not 0 <= obj_index < desc.n_objects:
+            raise HostError(f"update_primitive: object {obj_index} out of range ({desc.n_objects} objects)")
+        cur = desc.objects[obj_index]
+        if cur.kind == N.OBJECT_SPHERE:
+            center = tuple(cur.sphere_center) if center is None else center
+            radius = cur.sphere_radius if radius is None else radius
+        elif cur.kind == N.OBJECT_PLANE:
+            normal = tuple(cur.plane_normal) if normal is None else normal
+            point = tuple(cur.plane_point) if point is None else point
+        if cur.kind in (N.OBJECT_SPHERE, N.OBJECT_PLANE):
+            abi = primitive_abi(cur.kind, cur.mat_index, center, radius, normal, point)
+        else:
+            abi = N.Object(kind=cur.kind, mat_index=cur.mat_index)      # refused by the library, with its message
+        _host_check(N.lib().cgpth_scene_update_primitive(self._h, obj_index, C.byref(abi)), "update_primitive")
 
     def bvh_info(self, obj_index: int) -> N.BvhInfo:
         info = N.BvhInfo()

@@ -189,6 +189,24 @@ int cgpt_scene_upload(cgpt_ctx* ctx, const cgpt_scene_desc* scene);
 /* replaces Material::RenderImGui edits (ref: Main.cpp:71-91,263-265); the caller resets the accumulator as the reference does */
 int cgpt_scene_update_materials(cgpt_ctx* ctx, const cgpt_material* materials, uint32_t n_materials);
 
+/* ---- in-place geometry edits of the uploaded scene (no re-upload; the caller resets the accumulator, as with the materials) ----
+ * Every call validates before its first device write: a refused call leaves the device scene as it was.  If a HIP call fails after
+ * the writes began, the scene is dropped (the next render returns CGPT_ERR_NO_SCENE) instead of a half-edited one being rendered.
+ * A multi-device context edits every device's copy (and drops every copy on such a failure); the export reads the first device's. */
+/* BVH refitting (reference README, "Planned"): new positions and normals for mesh `obj_index` with its tree kept -- node numbering,
+ * left_first / prim_count and tri_indices stay; each node's bounds become BVH::CalculateNodeBounds (ref: BVH.cpp:188-202) over its
+ * current leaf range of the new triangles, and total_area the sum of GetTriangleArea in original order (ref: BVH.cpp:22).
+ * triangles: n_tris == the uploaded tri_count, in the object's original order.  A triangle object takes n_tris = 1 (it has no bounds
+ * and no total_area: 0 is reported).  Spheres and planes: CGPT_ERR_INVALID.  total_area_out may be NULL.
+ * The tree was built for the old positions: after a large deformation rebuild on the host and upload instead. */
+int cgpt_scene_refit_mesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris, float* total_area_out);
+/* the mesh's tree as it is now on the device, in the reference's 32-byte layout and node numbering (n_nodes == the uploaded node_count):
+ * what a host that keeps its own BVH (the BVH panel, a later Rebuild) copies back after a refit */
+int cgpt_scene_export_bvh(cgpt_ctx* ctx, uint32_t obj_index, cgpt_bvh_node* nodes_out, uint32_t n_nodes);
+/* Primitive::RenderImGui's sliders (ref: Primitives.cpp:385-410): a sphere's centre and radius (radius^2 = r*r, as at upload) or a
+ * plane's normal and point.  obj->kind and obj->mat_index must equal the uploaded ones; the other fields of *obj are ignored. */
+int cgpt_scene_update_primitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_object* obj);
+
 /* UpdateScreenPlane (ref: Main.cpp:98-102,143-149): fov in degrees, plane at distance fov-in-radians (SURVEY A-13) */
 int cgpt_camera_from_view(const float pos[3], const float view_dir[3], float fov_deg, float aspect, cgpt_camera* out);
 

@@ -68,6 +68,12 @@ int cgpth_scene_rebuild_bvh(cgpth_scene* scene, uint32_t obj_index, int build_op
 /* BVH::Rebuild with the re-split on the GPU: starts from the tree's current triangle order, as the reference does (ref: BVH.cpp:47-59);
  * on failure the BVH is left unchanged */
 int cgpth_scene_rebuild_bvh_device(cgpth_scene* scene, uint32_t obj_index, int build_option, cgpt_ctx* ctx);
+/* the host statement of cgpt_scene_refit_mesh (same contract, validation and errors): a mesh keeps its tree, its triangles, per-triangle
+ * bounds and centroids (a later Rebuild re-splits on them), total_area and node bounds follow the new triangles; a triangle object
+ * (n_tris = 1) is replaced.  On failure the scene is unchanged. */
+int cgpth_scene_refit_mesh(cgpth_scene* scene, uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris);
+/* the host statement of cgpt_scene_update_primitive: a sphere's centre and radius, or a plane's normal and point */
+int cgpth_scene_update_primitive(cgpth_scene* scene, uint32_t obj_index, const cgpt_object* obj);
 int cgpth_scene_bvh_info(const cgpth_scene* scene, uint32_t obj_index, cgpth_bvh_info* out);
 /* nodes: nodes_used x cgpt_bvh_node; tri_indices: num_triangles */
 int cgpth_scene_bvh_export(const cgpth_scene* scene, uint32_t obj_index, cgpt_bvh_node* nodes, uint32_t* tri_indices);
