@@ -332,46 +332,37 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
     // ---- record order (device_scene.h: "record order") ----
     // The reference allocates nodes depth-first; a record's index is only a name here (codes are rewritten), so the records are
     // renumbered: the first kTopRecords in breadth-first order over all meshes (the top of every tree, which every ray walks:
-    // the trace kernel mirrors records [0, n_top_records) in LDS), the rest in the reference's order (CGPT_NODE_ORDER=bfs:
-    // everything breadth-first; =dfs: nothing renumbered, for experiments).
+    // the trace kernel mirrors records [0, n_top_records) in LDS), the rest in the reference's order.
     const uint32_t n_records = (uint32_t)(pairs.size() / 4);
-    uint32_t n_top_records = 0;
-    std::vector<uint32_t> perm;                                                 // stays empty when nothing is renumbered
-    {
-        const char* mode_env = getenv("CGPT_NODE_ORDER");
-        const std::string mode = mode_env ? mode_env : "top";
-        std::vector<uint32_t> bfs; bfs.reserve(n_records);
-        for (uint32_t oi = 0; oi < sd.n_objects; ++oi)
-            if (objs[oi].kind == CGPT_OBJECT_MESH && (objs[oi].root_code & kLeafBit) == 0u) bfs.push_back(objs[oi].root_code);
-        const size_t bfs_limit = mode == "bfs" ? n_records : std::min<size_t>(n_records, kTopRecords);
-        for (size_t head = 0; head < bfs.size() && bfs.size() < n_records; ++head) {
-            if (mode != "bfs" && bfs.size() >= bfs_limit + 2 * kTopRecords) break;   // enough: only the first bfs_limit are used
-            const float4& cc = pairs[4 * (size_t)bfs[head] + 3];
-            uint32_t lc, rc; memcpy(&lc, &cc.z, 4); memcpy(&rc, &cc.w, 4);
-            if ((lc & kLeafBit) == 0u) bfs.push_back(lc);
-            if ((rc & kLeafBit) == 0u) bfs.push_back(rc);
-        }
-        if (mode != "dfs" && n_records > 0) {
-            perm.assign(n_records, 0xFFFFFFFFu);
-            uint32_t next = 0;
-            for (size_t i = 0; i < bfs.size() && i < bfs_limit; ++i) perm[bfs[i]] = next++;
-            for (uint32_t r = 0; r < n_records; ++r) if (perm[r] == 0xFFFFFFFFu) perm[r] = next++;
-            std::vector<float4> moved(pairs.size());
-            for (uint32_t r = 0; r < n_records; ++r) {
-                float4* dst = moved.data() + 4 * (size_t)perm[r];
-                const float4* src = pairs.data() + 4 * (size_t)r;
-                dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; dst[3] = src[3];
-                uint32_t lc, rc; memcpy(&lc, &src[3].z, 4); memcpy(&rc, &src[3].w, 4);
-                if ((lc & kLeafBit) == 0u) lc = perm[lc];
-                if ((rc & kLeafBit) == 0u) rc = perm[rc];
-                dst[3].z = AsFloat(lc); dst[3].w = AsFloat(rc);
-            }
-            pairs.swap(moved);
-            for (uint32_t oi = 0; oi < sd.n_objects; ++oi)
-                if (objs[oi].kind == CGPT_OBJECT_MESH && (objs[oi].root_code & kLeafBit) == 0u) objs[oi].root_code = perm[objs[oi].root_code];
-            n_top_records = (uint32_t)std::min<size_t>(bfs.size(), std::min<size_t>(n_records, kTopRecords));
-        }
+    std::vector<uint32_t> perm(n_records, 0xFFFFFFFFu);
+    std::vector<uint32_t> bfs; bfs.reserve(n_records);
+    for (uint32_t oi = 0; oi < sd.n_objects; ++oi)
+        if (objs[oi].kind == CGPT_OBJECT_MESH && (objs[oi].root_code & kLeafBit) == 0u) bfs.push_back(objs[oi].root_code);
+    const size_t bfs_limit = std::min<size_t>(n_records, kTopRecords);
+    for (size_t head = 0; head < bfs.size() && bfs.size() < n_records; ++head) {
+        if (bfs.size() >= bfs_limit + 2 * kTopRecords) break;                  // enough: only the first bfs_limit are used
+        const float4& cc = pairs[4 * (size_t)bfs[head] + 3];
+        uint32_t lc, rc; memcpy(&lc, &cc.z, 4); memcpy(&rc, &cc.w, 4);
+        if ((lc & kLeafBit) == 0u) bfs.push_back(lc);
+        if ((rc & kLeafBit) == 0u) bfs.push_back(rc);
     }
+    uint32_t next = 0;
+    for (size_t i = 0; i < bfs.size() && i < bfs_limit; ++i) perm[bfs[i]] = next++;
+    for (uint32_t r = 0; r < n_records; ++r) if (perm[r] == 0xFFFFFFFFu) perm[r] = next++;
+    std::vector<float4> moved(pairs.size());
+    for (uint32_t r = 0; r < n_records; ++r) {
+        float4* dst = moved.data() + 4 * (size_t)perm[r];
+        const float4* src = pairs.data() + 4 * (size_t)r;
+        dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; dst[3] = src[3];
+        uint32_t lc, rc; memcpy(&lc, &src[3].z, 4); memcpy(&rc, &src[3].w, 4);
+        if ((lc & kLeafBit) == 0u) lc = perm[lc];
+        if ((rc & kLeafBit) == 0u) rc = perm[rc];
+        dst[3].z = AsFloat(lc); dst[3].w = AsFloat(rc);
+    }
+    pairs.swap(moved);
+    for (uint32_t oi = 0; oi < sd.n_objects; ++oi)
+        if (objs[oi].kind == CGPT_OBJECT_MESH && (objs[oi].root_code & kLeafBit) == 0u) objs[oi].root_code = perm[objs[oi].root_code];
+    const uint32_t n_top_records = (uint32_t)std::min(bfs.size(), bfs_limit);
 
     // each mesh's child-pair records grouped by depth, in their final numbering: the refit's bound pass runs one level after the other,
     // deepest first (refit.hip)
@@ -391,7 +382,7 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
         levels.resize(levels.size() + count[n_levels]);
         uint32_t* out = levels.data() + ro.level_begin;
         for (uint32_t r = r0; r < r1; ++r)
-            if (rec_depth[r] != 0xFF) out[count[rec_depth[r]]++] = perm.empty() ? r : perm[r];
+            if (rec_depth[r] != 0xFF) out[count[rec_depth[r]]++] = perm[r];
     }
 
     // per-object records for the trace kernel's object phase (device_scene.h: obj_trace)

@@ -202,7 +202,7 @@ int ExportBvh(cgpt_ctx* ctx, uint32_t obj_index, cgpt_bvh_node* nodes_out, uint3
     uint32_t lo = 0xFFFFFFFFu, hi = 0;
     for (uint32_t k = 0; k < n_pairs; ++k) {
         const uint32_t r = ro.pair_base + k;
-        stored[k] = ctx->record_perm.empty() ? r : ctx->record_perm[r];
+        stored[k] = ctx->record_perm[r];
         lo = std::min(lo, stored[k]); hi = std::max(hi, stored[k]);
     }
     std::vector<float4> span(n_pairs ? 4 * (size_t)(hi - lo + 1) : 0);

@@ -60,7 +60,7 @@ hipEvent_t CtxStartEvent(cgpt_ctx* ctx);
 
 extern __shared__ uint32_t lds_dyn[];
 
-static constexpr uint32_t kMaxKeys = 128;   // most runs per segment (image bands) the count / prefix tables are sized for
+static constexpr uint32_t kMaxBands = 128;  // most runs per segment (image bands) the count / prefix tables are sized for
 
 struct WfDev {
     float4* A; float4* B; float4* C;   // 2 * cap slots each: [0, cap) extend, [cap, 2 cap) shadow
@@ -70,11 +70,9 @@ struct WfDev {
     uint8_t* hit_flag;                 // cap paths: did the path's extend ray of this round hit anything (retire_misses only; written by trace)
     uint32_t* list_ext; uint32_t* list_sh;     // dense lists of path ids for the next trace / shade (cap entries each)
     uint32_t* seg_ext; uint32_t* seg_sh;       // per-wave output segments of shade (n_segs * seg_cap entries each)
-    uint8_t* seg_key_ext; uint8_t* seg_key_sh; // sort keys of the segment entries (n_keys > 1 only)
-    uint32_t* seg_count;               // [kind][key][segment]: extend counts, then shadow counts (n_keys = 1: [2 * n_segs])
-    uint32_t* seg_prefix;              // exclusive prefix of the above, per kind, key-major: where each (key, segment) run starts in the list
-    uint32_t n_keys;                   // runs per segment: 1; 8 with sort (lists binned by the octant of the ray direction); n_bands with bands
-    uint32_t n_bands;                  // > 1: the next round's lists are ordered by image band (see wf_shade); 0 / 1: off
+    uint32_t* seg_count;               // [kind][band][segment]: extend counts, then shadow counts (plain lists: [2 * n_segs])
+    uint32_t* seg_prefix;              // exclusive prefix of the above, per kind, band-major: where each (band, segment) run starts in the list
+    uint32_t n_bands;                  // runs per segment: > 1, the next round's lists are ordered by image band (see wf_shade); 1: plain lists
     uint32_t band_magic;               // band of path id p = min(n_bands - 1, umulhi(p, band_magic))
     uint32_t* plan;                    // {n_ext, n_sh}
     uint32_t* stack_overflow;          // [level - kLdsStackLevels][thread of the trace grid]: the rarely used deep end of the stack
@@ -84,7 +82,6 @@ struct WfDev {
     PathGrid g;                        // path id <-> pixel of the band (trace_steps.hpp)
     uint32_t n_segs, seg_cap;
     uint32_t shade_chunk;              // consecutive 64-path blocks a shade wave takes at a time
-    uint32_t trace_chunk;              // same for a trace wave
     uint32_t retire_misses;            // later rounds: trace leaves one byte per extend ray (hit or not) and shade takes only the hits (off for the debug views)
     uint32_t rot_trace[2], rot_shade;  // rotation of the wave order from one row of blocks to the next ([FIRST] for trace): see next_block()
     unsigned long long* spec_tab;      // specular-chain election (wf_shade): spec_keys entries {bits(epoch << 16 | chain), leader path id << 32} per
@@ -156,11 +153,9 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
     const uint32_t n_sh = first_round ? 0u : wf.plan[1];
     const uint32_t blocks_ext = (n_ext + 63u) / 64u, n_blocks = blocks_ext + (n_sh + 63u) / 64u;
     const uint32_t n_waves = gridDim.x * (kTraceBlock / 64u);
-    // wave-uniform: the wave's next 64-item block.  Runs of trace_chunk consecutive blocks (the same and neighbouring pixels) are dealt
-    // out over the waves, so the rays a wave refills its idle lanes with come from where its other lanes' rays came from
+    // wave-uniform: the wave's next 64-item block of the dense list
     BlockWalk walk = first_block(blockIdx.x * (kTraceBlock / 64u) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));   // wave-uniform: scalar registers
-    const uint32_t tchunk = wf.trace_chunk;
-    uint32_t block = block_of(walk) * tchunk, chunk_left = tchunk;
+    uint32_t block = block_of(walk);
     const uint32_t rot = wf.rot_trace[first_round ? 1 : 0];
     uint32_t ring_count = 0;
 
@@ -235,8 +230,8 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
             const unsigned long long m = __builtin_amdgcn_ballot_w64(valid);
             if (valid) ring[ring_count + rank_in_mask(m)] = s;
             ring_count += (uint32_t)__popcll(m);
-            if (--chunk_left) ++block;
-            else { next_block(walk, n_waves, rot); block = block_of(walk) * tchunk; chunk_left = tchunk; }
+            next_block(walk, n_waves, rot);
+            block = block_of(walk);
             __builtin_amdgcn_wave_barrier();
         }
         if (n_need && ring_count) {
@@ -382,8 +377,6 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
     uint32_t* const out_ext = wf.seg_ext + (size_t)wave * wf.seg_cap;
     uint32_t* const out_sh = wf.seg_sh + (size_t)wave * wf.seg_cap;
     uint32_t count_ext = 0, count_sh = 0;                                     // wave-uniform
-    uint32_t kc_ext[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, kc_sh[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };   // per-key counts (wave-uniform; n_keys == 8 only)
-    const bool sorted = wf.n_keys > 1u && wf.n_bands <= 1u;
     // Image bands: a wave walks its chunks in ascending list order and the lists are band-major (round 0: path ids in image order), so
     // the entries it appends are already grouped by the band of their pixel -- contiguous runs inside its segment, with no per-entry key.
     // The wave only notes where each band's run ends; plan + gather then put all segments' runs of band 0 first, then band 1, ...
@@ -421,7 +414,7 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
     for (;;) {
         bool active = false;
         bool emit_ext = false, emit_sh = false;
-        uint32_t pid = 0, key_ext = 0, key_sh = 0;
+        uint32_t pid = 0;
         if (!hits_only) {
             if (!more) break;
             const uint32_t i = block * 64u + lane_id();
@@ -559,7 +552,6 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
                 if ((first_round || followed) && ray.t != 1e34f) st_stream(&wf.C[pid], c);   // round 0 kept it per pixel, a follower's came from
                                                                               // its leader: the re-traced ray's payload goes to its slot (trace reads
                                                                               // C exactly when A.w != 1e34)
-                key_ext = (ray.d.x < 0.0f ? 1u : 0u) | (ray.d.y < 0.0f ? 2u : 0u) | (ray.d.z < 0.0f ? 4u : 0u);
             }
             if (emit_sh) {                                                    // NEE connection, slot cap + pid
                 const uint32_t ss = wf.cap + pid;
@@ -568,7 +560,6 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
                 sb.x = shadow.d.x; sb.y = shadow.d.y; sb.z = shadow.d.z; sb.w = 0.0f;
                 scc.x = pending.x; scc.y = pending.y; scc.z = pending.z; scc.w = 0.0f;
                 st_stream(&wf.A[ss], sa); st_stream(&wf.B[ss], sb); st_stream(&wf.C[ss], scc);
-                key_sh = (shadow.d.x < 0.0f ? 1u : 0u) | (shadow.d.y < 0.0f ? 2u : 0u) | (shadow.d.z < 0.0f ? 4u : 0u);
             }
         }
         // active-lane compaction into the wave's own segments: __ballot + mbcnt, no atomics
@@ -589,15 +580,6 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
         }
         if (emit_ext) st_stream(&out_ext[count_ext + rank_in_mask(m_ext)], pid);
         if (emit_sh) st_stream(&out_sh[count_sh + rank_in_mask(m_sh)], pid);
-        if (sorted) {                                                         // the direction octants, for the binning in wf_gather
-            if (emit_ext) wf.seg_key_ext[(size_t)wave * wf.seg_cap + count_ext + rank_in_mask(m_ext)] = (uint8_t)key_ext;
-            if (emit_sh) wf.seg_key_sh[(size_t)wave * wf.seg_cap + count_sh + rank_in_mask(m_sh)] = (uint8_t)key_sh;
-#pragma unroll
-            for (uint32_t k = 0; k < 8u; ++k) {
-                kc_ext[k] += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(emit_ext && key_ext == k));
-                kc_sh[k] += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(emit_sh && key_sh == k));
-            }
-        }
         count_ext += (uint32_t)__popcll(m_ext);
         count_sh += (uint32_t)__popcll(m_sh);
     }
@@ -608,26 +590,22 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
                 wf.seg_count[(wf.n_bands + b) * wf.n_segs + wave] = b == cur_band ? count_sh - band_start_sh : 0u;
             }
     } else if (lane_id() == 0) {
-        if (!sorted) { wf.seg_count[wave] = count_ext; wf.seg_count[wf.n_segs + wave] = count_sh; }
-        else {
-#pragma unroll
-            for (uint32_t k = 0; k < 8u; ++k) { wf.seg_count[k * wf.n_segs + wave] = kc_ext[k]; wf.seg_count[(8u + k) * wf.n_segs + wave] = kc_sh[k]; }
-        }
+        wf.seg_count[wave] = count_ext; wf.seg_count[wf.n_segs + wave] = count_sh;
     }
     if (COUNT) wave_add_u64(&args.counters->closest_hits, cnt.hits);
 }
 
 // ---- plan: exclusive scan of the segment counts -------------------------------------------------------------------------------
-// One 256-thread block per (kind, key): the exclusive prefix of that key's n_segs counts (a few thousand) goes to seg_prefix, the key's
-// total to plan[2 + kind * n_keys + key]; wf_gather adds the totals of the keys before (and sums them into plan[kind] for the next
-// round's kernels).  One key: plan[kind] directly.  Small blocks with 1 KB of LDS start in the wave slots a resident persistent kernel
-// of another batch leaves free (a 1024-thread block had to wait for a whole CU to drain: 0.4 ms average in the 8-pool profile); one
-// block scanning all keys in turn took 100 us with 8 keys, on the critical path of its batch.
+// One 256-thread block per (kind, band): the exclusive prefix of that band's n_segs counts (a few thousand) goes to seg_prefix, the
+// band's total to plan[2 + kind * n_bands + band]; wf_gather adds the totals of the bands before (and sums them into plan[kind] for the
+// next round's kernels).  Plain lists: plan[kind] directly.  Small blocks with 1 KB of LDS start in the wave slots a resident persistent
+// kernel of another batch leaves free (a 1024-thread block had to wait for a whole CU to drain: 0.4 ms average in the 8-pool profile);
+// one block scanning all runs in turn took 100 us with 8 of them, on the critical path of its batch.
 __global__ void __launch_bounds__(256) wf_plan(const WfDev wf)
 {
     __shared__ uint32_t partial[256];
     const uint32_t n = wf.n_segs;
-    const uint32_t kk = blockIdx.x;                                           // kind * n_keys + key
+    const uint32_t kk = blockIdx.x;                                           // kind * n_bands + band
     const uint32_t* cnt = wf.seg_count + (size_t)kk * n;
     uint32_t* pre = wf.seg_prefix + (size_t)kk * n;
     const uint32_t per = (n + 255u) / 256u;
@@ -646,96 +624,66 @@ __global__ void __launch_bounds__(256) wf_plan(const WfDev wf)
     for (uint32_t i = begin; i < end; ++i) { pre[i] = run; run += cnt[i]; }
     if (threadIdx.x == 255u) {
         wf.plan[2u + kk] = partial[255];
-        if (wf.n_keys == 1u) wf.plan[kk] = partial[255];
+        if (wf.n_bands == 1u) wf.plan[kk] = partial[255];
     }
 }
 
 // ---- gather: segments -> dense lists -------------------------------------------------------------------------------------------
+// 16 bytes per lane: a segment starts on a 16-byte boundary, its place in the list on a 4-byte one (global dwordx4 accesses only
+// need dword alignment).  Round 0 moves ~1 GB per batch here while the other batch's shade streams its state.
 __global__ void __launch_bounds__(256) wf_gather(const WfDev wf)
 {
-    if (wf.n_keys == 1u) {
+    typedef uint32_t u4a4 __attribute__((ext_vector_type(4), aligned(4)));
+    if (wf.n_bands == 1u) {
         for (uint32_t s = blockIdx.x; s < 2u * wf.n_segs; s += gridDim.x) {
             const bool sh = s >= wf.n_segs;
             const uint32_t seg = sh ? s - wf.n_segs : s;
             const uint32_t n = wf.seg_count[s], base = wf.seg_prefix[s];
             const uint32_t* src = (sh ? wf.seg_sh : wf.seg_ext) + (size_t)seg * wf.seg_cap;
             uint32_t* dst = (sh ? wf.list_sh : wf.list_ext) + base;
-            // 16 bytes per lane: the segment starts on a 16-byte boundary, its place in the list on a 4-byte one (global dwordx4
-            // accesses only need dword alignment).  Round 0 moves ~1 GB per batch here while the other batch's shade streams its state.
-            typedef uint32_t u4a4 __attribute__((ext_vector_type(4), aligned(4)));
             const uint32_t n4 = n & ~3u;
             for (uint32_t i = threadIdx.x * 4u; i < n4; i += blockDim.x * 4u) *reinterpret_cast<u4a4*>(dst + i) = *reinterpret_cast<const u4a4*>(src + i);
             if (threadIdx.x < n - n4) dst[n4 + threadIdx.x] = src[n4 + threadIdx.x];
         }
         return;
     }
-    if (wf.n_bands > 1u) {                                                    // band runs: contiguous in the segment, each copied to its place in the list
-        // One block per segment.  The run table of the segment (where each band's run starts in the segment and in the list) is built
-        // once in LDS -- all counts, prefixes and band totals fetched in parallel, then one short serial pass -- and the four waves copy
-        // runs side by side; read one after the other from HBM, 32 bands were 32 dependent round trips per segment.
-        __shared__ uint32_t s_n[kMaxKeys], s_dst[kMaxKeys], s_src[kMaxKeys];
-        typedef uint32_t u4a4 __attribute__((ext_vector_type(4), aligned(4)));
-        const uint32_t lane = threadIdx.x & 63u, wave_in_block = threadIdx.x >> 6;
-        for (uint32_t s = blockIdx.x; s < 2u * wf.n_segs; s += gridDim.x) {
-            const bool sh = s >= wf.n_segs;
-            const uint32_t seg = sh ? s - wf.n_segs : s;
-            const uint32_t* cnt = wf.seg_count + (sh ? wf.n_bands * wf.n_segs : 0u);
-            const uint32_t* pre = wf.seg_prefix + (sh ? wf.n_bands * wf.n_segs : 0u);
-            const uint32_t* key_total = wf.plan + 2u + (sh ? wf.n_bands : 0u);
-            __syncthreads();                                                  // the previous segment's table is no longer read
-            if (threadIdx.x < wf.n_bands) {
-                s_n[threadIdx.x] = cnt[threadIdx.x * wf.n_segs + seg];
-                s_dst[threadIdx.x] = pre[threadIdx.x * wf.n_segs + seg];     // + the totals of the bands before, below
-                s_src[threadIdx.x] = key_total[threadIdx.x];
-            }
-            __syncthreads();
-            if (threadIdx.x == 0u) {
-                uint32_t off = 0, base = 0;                                   // base: entries of the bands before this one, all segments
-                for (uint32_t b = 0; b < wf.n_bands; ++b) {
-                    const uint32_t n = s_n[b], total = s_src[b];
-                    s_dst[b] += base; s_src[b] = off;
-                    off += n; base += total;
-                }
-                if (seg == 0u) wf.plan[sh ? 1 : 0] = base;                    // the list's length, for the next round's kernels
-            }
-            __syncthreads();
-            const uint32_t* src = (sh ? wf.seg_sh : wf.seg_ext) + (size_t)seg * wf.seg_cap;
-            uint32_t* const list = sh ? wf.list_sh : wf.list_ext;
-            for (uint32_t b = wave_in_block; b < wf.n_bands; b += 4u) {
-                const uint32_t n = s_n[b], n4 = n & ~3u;
-                uint32_t* dst = list + s_dst[b];
-                const uint32_t* run = src + s_src[b];                         // 16 bytes per lane, dword-aligned at both ends
-                for (uint32_t i = lane * 4u; i < n4; i += 256u) *reinterpret_cast<u4a4*>(dst + i) = *reinterpret_cast<const u4a4*>(run + i);
-                if (lane < n - n4) dst[n4 + lane] = run[n4 + lane];
-            }
-        }
-        return;
-    }
-    // binned by key (a counting sort whose counts shade already took): one wave per segment, entries in order, each to the next
-    // free place of its (key, segment) run -- stable, so rays of one key keep the image-neighbourhood order of their segment
-    const uint32_t n_waves = gridDim.x * 4u;
-    for (uint32_t s = blockIdx.x * 4u + (threadIdx.x >> 6); s < 2u * wf.n_segs; s += n_waves) {
+    // Band runs: contiguous in the segment, each copied to its place in the list.  One block per segment.  The run table of the
+    // segment (where each band's run starts in the segment and in the list) is built once in LDS -- all counts, prefixes and band
+    // totals fetched in parallel, then one short serial pass -- and the four waves copy runs side by side; read one after the other
+    // from HBM, 32 bands were 32 dependent round trips per segment.
+    __shared__ uint32_t s_n[kMaxBands], s_dst[kMaxBands], s_src[kMaxBands];
+    const uint32_t lane = threadIdx.x & 63u, wave_in_block = threadIdx.x >> 6;
+    for (uint32_t s = blockIdx.x; s < 2u * wf.n_segs; s += gridDim.x) {
         const bool sh = s >= wf.n_segs;
         const uint32_t seg = sh ? s - wf.n_segs : s;
-        const uint32_t* cnt = wf.seg_count + (sh ? 8u * wf.n_segs : 0u);
-        const uint32_t* pre = wf.seg_prefix + (sh ? 8u * wf.n_segs : 0u);
-        uint32_t n = 0, next[8], base = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 8u; ++k) { n += cnt[k * wf.n_segs + seg]; next[k] = base + pre[k * wf.n_segs + seg]; base += wf.plan[2u + (sh ? 8u : 0u) + k]; }
-        if (seg == 0u && lane_id() == 0u) wf.plan[sh ? 1 : 0] = base;
-        const uint32_t* src = (sh ? wf.seg_sh : wf.seg_ext) + (size_t)seg * wf.seg_cap;
-        const uint8_t* keys = (sh ? wf.seg_key_sh : wf.seg_key_ext) + (size_t)seg * wf.seg_cap;
-        uint32_t* dst = sh ? wf.list_sh : wf.list_ext;
-        for (uint32_t base = 0; base < n; base += 64u) {
-            const uint32_t i = base + lane_id();
-            const bool valid = i < n;
-            const uint32_t pid = valid ? src[i] : 0u, key = valid ? keys[i] : 8u;
-#pragma unroll
-            for (uint32_t k = 0; k < 8u; ++k) {
-                const unsigned long long m = __builtin_amdgcn_ballot_w64(key == k);
-                if (key == k) dst[next[k] + rank_in_mask(m)] = pid;
-                next[k] += (uint32_t)__popcll(m);
+        const uint32_t* cnt = wf.seg_count + (sh ? wf.n_bands * wf.n_segs : 0u);
+        const uint32_t* pre = wf.seg_prefix + (sh ? wf.n_bands * wf.n_segs : 0u);
+        const uint32_t* band_total = wf.plan + 2u + (sh ? wf.n_bands : 0u);
+        __syncthreads();                                                      // the previous segment's table is no longer read
+        if (threadIdx.x < wf.n_bands) {
+            s_n[threadIdx.x] = cnt[threadIdx.x * wf.n_segs + seg];
+            s_dst[threadIdx.x] = pre[threadIdx.x * wf.n_segs + seg];         // + the totals of the bands before, below
+            s_src[threadIdx.x] = band_total[threadIdx.x];
+        }
+        __syncthreads();
+        if (threadIdx.x == 0u) {
+            uint32_t off = 0, base = 0;                                       // base: entries of the bands before this one, all segments
+            for (uint32_t b = 0; b < wf.n_bands; ++b) {
+                const uint32_t n = s_n[b], total = s_src[b];
+                s_dst[b] += base; s_src[b] = off;
+                off += n; base += total;
             }
+            if (seg == 0u) wf.plan[sh ? 1 : 0] = base;                        // the list's length, for the next round's kernels
+        }
+        __syncthreads();
+        const uint32_t* src = (sh ? wf.seg_sh : wf.seg_ext) + (size_t)seg * wf.seg_cap;
+        uint32_t* const list = sh ? wf.list_sh : wf.list_ext;
+        for (uint32_t b = wave_in_block; b < wf.n_bands; b += 4u) {
+            const uint32_t n = s_n[b], n4 = n & ~3u;
+            uint32_t* dst = list + s_dst[b];
+            const uint32_t* run = src + s_src[b];                             // 16 bytes per lane, dword-aligned at both ends
+            for (uint32_t i = lane * 4u; i < n4; i += 256u) *reinterpret_cast<u4a4*>(dst + i) = *reinterpret_cast<const u4a4*>(run + i);
+            if (lane < n - n4) dst[n4 + lane] = run[n4 + lane];
         }
     }
 }
@@ -770,7 +718,6 @@ struct WfTuning {               // defaults measured on MI355X (profiles/r01); o
     uint32_t shade_chunk_banded = 32; // the same when the lists are ordered by image band: a longer piece of one band per work item (C3 86.8-87.3 -> 85.8-86.0 ms,
                                       // C4 rank share 33.7-34.4 -> 33.4-33.6 ms; 8: 86.4-87.0, 16: 86.4-86.9, 64: 86.1, 128: 86.8-87.3, 256: 91.8-92.0).  Plain lists
                                       // lose with it (C3 rank share of 8, 33 M-path batches: 13.07 -> 13.30 ms)
-    uint32_t trace_chunk = 1;         // consecutive blocks per trace work item
     uint32_t shadow_any_hit = 1;      // shadow rays stop at their first hit (not in the counting kernels)
     uint32_t lds_tris = 1;            // the small meshes' triangles (the ground quad) are read from an LDS copy
     uint32_t first_lean = 1;          // round 0 walks in the lean per-lane loop instead of voted steps (per-pixel rays: 0.68-0.71 ms
@@ -779,8 +726,7 @@ struct WfTuning {               // defaults measured on MI355X (profiles/r01); o
     uint32_t path_order = 2;          // PathOrder of the path ids (trace_steps.hpp PathGrid): 2 pixel-major, 1 tile-major, 0 sample-major
     uint32_t retire_misses = 1;       // shade skips the state loads of later-round rays that hit nothing
     uint32_t bands_min_paths = 32u << 20;  // batches of fewer paths keep plain lists (1080p, 8 samples per call: 4.81 ms plain, 5.21 banded; 33 M-path batches: level)
-    uint32_t sort = 0;                // 1: bin every round's ray lists by direction octant (measured in profiles/r02/k7_sort.md)
-    uint32_t bands = 32;              // > 1: every round's ray lists ordered by image band (wf_shade: "Image bands"); at most kMaxKeys.  C3: 1 band 89.1-89.4 ms,
+    uint32_t bands = 32;              // > 1: every round's ray lists ordered by image band (wf_shade: "Image bands"); at most kMaxBands.  C3: 1 band 89.1-89.4 ms,
                                       // 8: 87.3-87.6, 16: 88.0-88.2, 32: 87.1-87.5, 64: 87.8-88.4 (profiles/r03/image_bands.md)
     uint32_t spec_dedupe = 1;         // later rounds trace one ray per (pixel, specular chain) and batch (wf_shade: "Specular chains")
     uint32_t spec_keys = 8;           // election entries per pixel; a ray whose pixel has none left is traced as usual
@@ -791,7 +737,6 @@ static uint32_t Gcd(uint32_t a, uint32_t b) { while (b) { const uint32_t t = a %
 // smallest rot in [0, n_waves) with gcd(n_waves + rot, n_tiles) == 1 (device: next_block)
 static uint32_t CoprimeRotation(uint32_t n_waves, uint32_t n_tiles)
 {
-    if (getenv("CGPT_WF_NO_ROTATION")) return 0u;
     for (uint32_t rot = 0; rot < n_waves && rot < 4096u; ++rot)
         if (Gcd(n_waves + rot, std::max(1u, n_tiles)) == 1u) return rot;
     return 0u;
@@ -806,16 +751,54 @@ static decltype(&wf_shade<false, false>) const kShadeKernels[2][2][2] = {
     { { wf_shade<true, false, false>, wf_shade<true, false, true> }, { wf_shade<true, true, false>, wf_shade<true, true, true> } },
 };
 
+// What a pool's buffers are sized for (one record per render; the pools of a render are alike)
+struct WfSizes {
+    uint32_t cap = 0, n_pixels = 0, n_segs = 0, seg_cap = 0;
+    uint32_t overflow_words = 0;                 // stack_overflow
+    uint32_t brute_levels = 0;                   // TracePath levels of `brute` (0: none)
+    size_t spec = 0;                             // entries of spec_tab (0: none)
+    bool Holds(const WfSizes& n) const
+    {
+        return cap >= n.cap && n_pixels >= n.n_pixels && n_segs >= n.n_segs && seg_cap >= n.seg_cap && overflow_words >= n.overflow_words &&
+               brute_levels >= n.brute_levels && spec >= n.spec;
+    }
+};
+
+// Every device buffer of a pool with its bytes at the sizes s (0 bytes: not allocated).  Allocation, release and the bytes the pools
+// hold in the memory budget all go through this one list.
+template <typename F> static void ForEachBuffer(WfDev& d, const WfSizes& s, F&& f)
+{
+    const size_t slots = 2 * (size_t)s.cap * sizeof(float4), paths = s.cap, segs = (size_t)s.n_segs * s.seg_cap * sizeof(uint32_t);
+    const size_t runs = 2 * (size_t)kMaxBands * s.n_segs * sizeof(uint32_t);
+    f(d.A, slots); f(d.B, slots); f(d.C, slots);
+    f(d.st_tp, paths * sizeof(float4)); f(d.st_en, paths * sizeof(float4)); f(d.hit_flag, paths);
+    f(d.px_hit, (size_t)s.n_pixels * sizeof(float4));
+    f(d.brute, (size_t)s.brute_levels * paths * 2u * sizeof(float4));
+    f(d.list_ext, paths * sizeof(uint32_t)); f(d.list_sh, paths * sizeof(uint32_t));
+    f(d.seg_ext, segs); f(d.seg_sh, segs);
+    f(d.seg_count, runs); f(d.seg_prefix, runs);
+    f(d.plan, (2 + 2 * (size_t)kMaxBands) * sizeof(uint32_t));
+    f(d.stack_overflow, (size_t)s.overflow_words * sizeof(uint32_t));
+    f(d.spec_tab, s.spec * sizeof(unsigned long long));
+}
+
+static size_t PoolBytes(const WfSizes& s)                                 // device memory of one pool at the sizes s
+{
+    WfDev d{};
+    size_t n = 0;
+    ForEachBuffer(d, s, [&](auto*&, size_t bytes) { n += bytes; });
+    return n;
+}
+
 struct WfHost {
     WfTuning tune;
     WfDev dev[kMaxPools] = {};
     hipStream_t streams[kMaxPools] = {};
     hipEvent_t acc_done[kMaxPools] = {};
     hipEvent_t begin = nullptr;
-    uint32_t alloc_cap = 0, alloc_segs = 0, alloc_seg_cap = 0, alloc_pools = 0, alloc_overflow = 0, alloc_brute_levels = 0, alloc_pixels = 0;
-    size_t alloc_spec = 0;                       // entries of every pool's spec_tab (0: none)
+    WfSizes held;                                // what the pools [0, held_pools) are allocated for
+    uint32_t held_pools = 0;
     uint32_t spec_epoch[kMaxPools] = {};         // last epoch used in each pool's spec_tab
-    bool alloc_sort = false;
     uint32_t n_cus = 0;
     uint32_t trace_blocks_per_cu[2][2] = {}, shade_blocks_per_cu[2][2] = {};   // trace: [COUNT][FIRST]; shade: [COUNT][BRUTE]
     size_t occupancy_lds = 0;
@@ -827,16 +810,11 @@ struct WfHost {
 
 static void WfRelease(WfHost* h)
 {
-    for (uint32_t p = 0; p < kMaxPools; ++p) {
-        WfDev& d = h->dev[p];
-        (void)hipFree(d.A); (void)hipFree(d.B); (void)hipFree(d.C);
-        (void)hipFree(d.st_tp); (void)hipFree(d.st_en); (void)hipFree(d.hit_flag); (void)hipFree(d.brute); (void)hipFree(d.px_hit); (void)hipFree(d.spec_tab);
-        (void)hipFree(d.list_ext); (void)hipFree(d.list_sh); (void)hipFree(d.seg_ext); (void)hipFree(d.seg_sh);
-        (void)hipFree(d.seg_count); (void)hipFree(d.seg_prefix); (void)hipFree(d.plan); (void)hipFree(d.stack_overflow);
-        (void)hipFree(d.seg_key_ext); (void)hipFree(d.seg_key_sh);
-        d = WfDev{};
+    for (uint32_t p = 0; p < kMaxPools; ++p) {                               // every pointer, whatever its size: also a failed, partial allocation
+        ForEachBuffer(h->dev[p], h->held, [](auto*& ptr, size_t) { (void)hipFree(ptr); });
+        h->dev[p] = WfDev{};
     }
-    h->alloc_cap = 0; h->alloc_segs = 0; h->alloc_seg_cap = 0; h->alloc_pools = 0; h->alloc_overflow = 0; h->alloc_sort = false; h->alloc_brute_levels = 0; h->alloc_pixels = 0; h->alloc_spec = 0;
+    h->held = WfSizes{}; h->held_pools = 0;
 }
 
 void WavefrontFree(void* state)
@@ -882,10 +860,10 @@ static const Knob<WfTuning> kKnobs[] = {
     { "leaf_repeat", &WfTuning::leaf_repeat, 1, 65 },      { "inner_repeat", &WfTuning::inner_repeat, 1, 65 },
     { "obj_repeat", &WfTuning::obj_repeat, 1, 65 },        { "obj_shift", &WfTuning::obj_shift, 0, 6 },
     { "top_records", &WfTuning::top_records, 0, 4096 },     { "trace_blocks", &WfTuning::max_trace_blocks, 1, 64 },
-    { "shade_chunk", &WfTuning::shade_chunk, 1, 256 },     { "shade_chunk_banded", &WfTuning::shade_chunk_banded, 1, 256 },     { "trace_chunk", &WfTuning::trace_chunk, 1, 256 },
+    { "shade_chunk", &WfTuning::shade_chunk, 1, 256 },     { "shade_chunk_banded", &WfTuning::shade_chunk_banded, 1, 256 },
     { "shadow_any_hit", &WfTuning::shadow_any_hit, 0, 1 },     { "trace_events", &WfTuning::trace_events, 0, 1 },
-    { "sort", &WfTuning::sort, 0, 1 },                     { "path_order", &WfTuning::path_order, 0, 2 },                     { "retire_misses", &WfTuning::retire_misses, 0, 1 },
-    { "lds_tris", &WfTuning::lds_tris, 0, 1 },             { "first_lean", &WfTuning::first_lean, 0, 1 },                     { "bands", &WfTuning::bands, 1, kMaxKeys },             { "bands_min_paths", &WfTuning::bands_min_paths, 0, 0x7FFFFFFF },
+    { "path_order", &WfTuning::path_order, 0, 2 },         { "retire_misses", &WfTuning::retire_misses, 0, 1 },
+    { "lds_tris", &WfTuning::lds_tris, 0, 1 },             { "first_lean", &WfTuning::first_lean, 0, 1 },                     { "bands", &WfTuning::bands, 1, kMaxBands },             { "bands_min_paths", &WfTuning::bands_min_paths, 0, 0x7FFFFFFF },
     { "spec_dedupe", &WfTuning::spec_dedupe, 0, 1 },       { "spec_keys", &WfTuning::spec_keys, 1, 16 },
     { "spec_epochs", &WfTuning::spec_epochs, 1, 0xFFFF },
 };
@@ -973,61 +951,40 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
     const size_t kBytesPerPath = 160 + 32 * (size_t)brute_levels;             // slots 96, state 32, lists 8, segments ~8-16; TracePath levels 32 each
     size_t free_b = 0, total_b = 0;
     LAUNCH_TRY(hipMemGetInfo(&free_b, &total_b));
-    const size_t held = (size_t)h->alloc_pools * ((size_t)h->alloc_cap * (160 + 32 * (size_t)h->alloc_brute_levels) + h->alloc_spec * sizeof(unsigned long long));
-    const size_t budget = std::min<size_t>((size_t)h->tune.budget_gib << 30, (free_b + held) / 2);
+    const size_t held_bytes = (size_t)h->held_pools * PoolBytes(h->held);  // what releasing the pools gives back: counted as free
+    const size_t budget = std::min<size_t>((size_t)h->tune.budget_gib << 30, (free_b + held_bytes) / 2);
     uint32_t batch = h->tune.batch;
     if (batch == 0) {
         batch = 1;
         while (batch < h->tune.max_batch && (uint64_t)n_pixels * batch * 2u <= (uint64_t)pool_paths) batch *= 2u;
     }
     batch = std::max(1u, std::min({ batch, std::max(1u, args_in.n_samples / 2u), args_in.n_samples, pool_paths / n_pixels }));
-    uint32_t cap = 0, n_pools = 0, seg_cap = 0, n_batches = 0;
+    WfSizes need;
+    need.n_pixels = n_pixels; need.n_segs = n_segs; need.overflow_words = overflow_words; need.brute_levels = brute_levels; need.spec = spec_entries;
+    uint32_t n_pools = 0, n_batches = 0;
     for (int attempt = 0;; ++attempt) {
         for (;;) {
-            cap = n_pixels * batch;
+            need.cap = n_pixels * batch;
             n_batches = (args_in.n_samples + batch - 1u) / batch;
-            const uint32_t afford = (uint32_t)std::min<size_t>(kMaxPools, budget / ((size_t)cap * kBytesPerPath + spec_entries * sizeof(unsigned long long)));
+            const uint32_t afford = (uint32_t)std::min<size_t>(kMaxPools, budget / ((size_t)need.cap * kBytesPerPath + spec_entries * sizeof(unsigned long long)));
             n_pools = std::max(1u, std::min({ h->tune.pools, n_batches, afford }));
             if (batch == 1u || (afford >= 1u && n_pools >= std::min({ 2u, n_batches, h->tune.pools }))) break;
             batch /= 2u;                                                      // smaller batches: room for a second pool
         }
-        const bool banded = !h->tune.sort && h->tune.bands > 1u && cap >= h->tune.bands_min_paths;   // (the last, shorter batch of a render may still fall below: it keeps this chunk)
+        const bool banded = h->tune.bands > 1u && need.cap >= h->tune.bands_min_paths;   // (the last, shorter batch of a render may still fall below: it keeps this chunk)
         shade_chunk = banded ? h->tune.shade_chunk_banded : h->tune.shade_chunk;
-        seg_cap = ((((cap + 63u) / 64u + shade_chunk - 1u) / shade_chunk + min_shade_waves - 1u) / min_shade_waves) * shade_chunk * 64u;   // whole chunks per wave
-        if (h->alloc_overflow >= overflow_words && h->alloc_cap >= cap && h->alloc_segs >= n_segs && h->alloc_seg_cap >= seg_cap && h->alloc_pools >= n_pools && (!h->tune.sort || h->alloc_sort) && h->alloc_brute_levels >= brute_levels && h->alloc_pixels >= n_pixels && h->alloc_spec >= spec_entries) break;
+        need.seg_cap = ((((need.cap + 63u) / 64u + shade_chunk - 1u) / shade_chunk + min_shade_waves - 1u) / min_shade_waves) * shade_chunk * 64u;   // whole chunks per wave
+        if (h->held_pools >= n_pools && h->held.Holds(need)) break;
         LAUNCH_TRY(hipDeviceSynchronize());
         WfRelease(h);
-        const size_t q = 2 * (size_t)cap * sizeof(float4);
         hipError_t err = hipSuccess;
-        auto get = [&](void** ptr, size_t bytes) { if (err == hipSuccess) err = hipMalloc(ptr, bytes); };
         for (uint32_t p = 0; p < n_pools; ++p) {
             WfDev& d = h->dev[p];
-            get((void**)&d.A, q); get((void**)&d.B, q); get((void**)&d.C, q);
-            get((void**)&d.st_tp, (size_t)cap * sizeof(float4));
-            get((void**)&d.st_en, (size_t)cap * sizeof(float4));
-            get((void**)&d.hit_flag, (size_t)cap);
-            get((void**)&d.px_hit, (size_t)n_pixels * sizeof(float4));
-            if (brute_levels) get((void**)&d.brute, (size_t)brute_levels * cap * 2u * sizeof(float4));
-            get((void**)&d.list_ext, (size_t)cap * sizeof(uint32_t));
-            get((void**)&d.list_sh, (size_t)cap * sizeof(uint32_t));
-            get((void**)&d.seg_ext, (size_t)n_segs * seg_cap * sizeof(uint32_t));
-            get((void**)&d.seg_sh, (size_t)n_segs * seg_cap * sizeof(uint32_t));
-            get((void**)&d.seg_count, 2 * (size_t)kMaxKeys * n_segs * sizeof(uint32_t));
-            get((void**)&d.seg_prefix, 2 * (size_t)kMaxKeys * n_segs * sizeof(uint32_t));
-            if (h->tune.sort) { get((void**)&d.seg_key_ext, (size_t)n_segs * seg_cap); get((void**)&d.seg_key_sh, (size_t)n_segs * seg_cap); }
-            get((void**)&d.plan, (2 + 2 * (size_t)kMaxKeys) * sizeof(uint32_t));
-            get((void**)&d.stack_overflow, (size_t)overflow_words * sizeof(uint32_t));
-            if (spec_entries) {                                               // epoch 0 is never current: all entries free
-                get((void**)&d.spec_tab, spec_entries * sizeof(unsigned long long));
-                if (err == hipSuccess) err = hipMemset(d.spec_tab, 0, spec_entries * sizeof(unsigned long long));
-            }
+            ForEachBuffer(d, need, [&](auto*& ptr, size_t bytes) { if (err == hipSuccess && bytes) err = hipMalloc((void**)&ptr, bytes); });
+            if (err == hipSuccess && d.spec_tab) err = hipMemset(d.spec_tab, 0, need.spec * sizeof(unsigned long long));   // epoch 0 is never current: all entries free
             h->spec_epoch[p] = 0;
         }
-        if (err == hipSuccess) {
-            h->alloc_cap = cap; h->alloc_segs = n_segs; h->alloc_seg_cap = seg_cap; h->alloc_pools = n_pools; h->alloc_overflow = overflow_words; h->alloc_sort = h->tune.sort != 0u; h->alloc_brute_levels = brute_levels;
-            h->alloc_pixels = n_pixels; h->alloc_spec = spec_entries;
-            break;
-        }
+        if (err == hipSuccess) { h->held = need; h->held_pools = n_pools; break; }
         (void)hipGetLastError();                                              // out of memory: give everything back and ask for half
         WfRelease(h);
         if (batch == 1u || attempt >= 8) { CtxFail(ctx, CGPT_ERR_HIP, "wavefront pools: %s", hipGetErrorString(err)); return -1; }
@@ -1054,25 +1011,22 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
         const uint32_t bn = std::min(batch, args_in.n_samples - done);
         const uint32_t bfirst = args_in.first_sample + done;
         WfDev wf = h->dev[p];
-        wf.cap = h->alloc_cap; wf.g.n_pixels = n_pixels; wf.n_paths = n_pixels * bn;
+        wf.cap = h->held.cap; wf.g.n_pixels = n_pixels; wf.n_paths = n_pixels * bn;
         wf.phase_stats = PhaseStatsArg(h->phase_stats, count);
-        wf.rot_trace[0] = CoprimeRotation(trace_grid_later.x * (kTraceBlock / 64u), std::max(1u, tiles_x * tiles_y / h->tune.trace_chunk));
-        wf.rot_trace[1] = CoprimeRotation(trace_grid_first.x * (kTraceBlock / 64u), std::max(1u, tiles_x * tiles_y / h->tune.trace_chunk));
+        wf.rot_trace[0] = CoprimeRotation(trace_grid_later.x * (kTraceBlock / 64u), tiles_x * tiles_y);
+        wf.rot_trace[1] = CoprimeRotation(trace_grid_first.x * (kTraceBlock / 64u), tiles_x * tiles_y);
         wf.rot_shade = CoprimeRotation(shade_grid.x * 4u, std::max(1u, tiles_x * tiles_y / shade_chunk));
-        wf.shade_chunk = shade_chunk; wf.trace_chunk = h->tune.trace_chunk;
+        wf.shade_chunk = shade_chunk;
         wf.g.tiles_x = tiles_x; wf.g.div_tiles_x = MakeFastDiv(tiles_x); wf.g.div_n_pixels = MakeFastDiv(n_pixels);
-        wf.g.n_samples = bn; wf.g.div_samples = MakeFastDiv(bn); wf.g.order = h->tune.path_order; wf.n_segs = h->alloc_segs; wf.seg_cap = h->alloc_seg_cap;
-        // segments of waves that a smaller shade grid does not launch must read as empty
-        wf.n_keys = h->tune.sort && wf.seg_key_ext ? 8u : 1u;
-        wf.n_bands = wf.n_keys == 1u && h->tune.bands > 1u && wf.n_paths >= h->tune.bands_min_paths ? h->tune.bands : 1u;   // short lists: nothing to order, and every band is a run per segment to plan and copy
-        if (wf.n_bands > 1u) {
-            wf.n_keys = wf.n_bands;
+        wf.g.n_samples = bn; wf.g.div_samples = MakeFastDiv(bn); wf.g.order = h->tune.path_order; wf.n_segs = h->held.n_segs; wf.seg_cap = h->held.seg_cap;
+        wf.n_bands = h->tune.bands > 1u && wf.n_paths >= h->tune.bands_min_paths ? h->tune.bands : 1u;   // short lists: nothing to order, and every band is a run per segment to plan and copy
+        if (wf.n_bands > 1u)
             wf.band_magic = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, (((uint64_t)wf.n_bands << 32) + wf.n_paths - 1u) / wf.n_paths);   // ceil(2^32 * bands / paths)
-        }
         wf.retire_misses = h->tune.retire_misses && args_in.settings.debug_mode == 0u ? 1u : 0u;
         if (!chains) wf.spec_tab = nullptr;
         wf.spec_keys = h->tune.spec_keys;
-        if (k < n_pools) LAUNCH_TRY(hipMemsetAsync(wf.seg_count, 0, 2 * (size_t)kMaxKeys * wf.n_segs * sizeof(uint32_t), st));
+        // segments of waves that a smaller shade grid does not launch must read as empty
+        if (k < n_pools) LAUNCH_TRY(hipMemsetAsync(wf.seg_count, 0, 2 * (size_t)kMaxBands * wf.n_segs * sizeof(uint32_t), st));
         for (uint32_t r = 0; r < rounds; ++r) {
             const bool first = r == 0u;
             if (h->tune.trace_events) LAUNCH_TRY(hipEventRecord(NextEvent(h->trace_ev), st));
@@ -1083,13 +1037,13 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
                 if (wf.spec_tab) {                                            // a fresh epoch frees every entry; after spec_epochs of them, clear
                     if (++h->spec_epoch[p] > h->tune.spec_epochs) {           // the whole table: entries past this call's n_pixels * spec_keys
                                                                               // hold tags of the old epochs too, written by larger layouts
-                        LAUNCH_TRY(hipMemsetAsync(wf.spec_tab, 0, h->alloc_spec * sizeof(unsigned long long), st));
+                        LAUNCH_TRY(hipMemsetAsync(wf.spec_tab, 0, h->held.spec * sizeof(unsigned long long), st));
                         h->spec_epoch[p] = 1u;
                     }
                     wf.spec_epoch = h->spec_epoch[p];
                 }
                 hipLaunchKernelGGL(kShadeKernels[count][first][brute], shade_grid, block, 0, st, args, wf, bfirst);
-                hipLaunchKernelGGL(wf_plan, dim3(2u * wf.n_keys), dim3(256), 0, st, wf);
+                hipLaunchKernelGGL(wf_plan, dim3(2u * wf.n_bands), dim3(256), 0, st, wf);
                 hipLaunchKernelGGL(wf_gather, dim3(std::min(2u * wf.n_segs, n_cus * 16u)), block, 0, st, wf);
                 launches += 3;
             }

@@ -608,9 +608,11 @@ def test_wavefront_equals_megakernel_on_odd_sizes(renderer, W, H, spp):
     assert np.all(a[..., 3] == spp)
 
 
-def test_wavefront_octant_binned_lists_give_the_same_image(renderer):
-    """SURVEY K7 experiment (tuning knob sort=1): every round's ray lists binned by direction octant; the order in which rays are
-    traced never changes a path, so the image, the ray count and the traversal counters are identical"""
+def test_wavefront_list_orders_give_the_same_image(renderer):
+    """The order in which rays are traced never changes a path, so the image, the ray count and the traversal counters are identical
+    for every order of the path ids (pixel-major by default; tile-major, sample-major), for misses dropped early or late in shade and
+    for ray lists ordered by image band (default for batches of 32 Mi paths and more; forced on here), alone and with the other knobs.
+    9 samples per call in batches of 5 and 4: the pixel-major accumulate stages 8 samples per pass (accumulate.hpp)"""
     v, i = standin_mesh(3)
     o, s = reference_layout_pair(v, i, 3, aspect=130 / 70)
     a = P.Renderer(0)
@@ -618,17 +620,6 @@ def test_wavefront_octant_binned_lists_give_the_same_image(renderer):
     a.render(130, 70, 9, seed=3, kernel=P.KERNEL_WAVEFRONT, counters=True)
     want, st0 = a.accumulator().copy(), a.stats()
     a.close()
-    b = P.Renderer(0)
-    b.upload(s)
-    b.set_tuning(sort=1, batch=4)
-    b.render(130, 70, 9, seed=3, kernel=P.KERNEL_WAVEFRONT, counters=True)
-    st1 = b.stats()
-    assert np.array_equal(b.accumulator().view(np.uint32), want.view(np.uint32))
-    assert (st0.traced_rays, st0.inner_steps, st0.tri_tests, st0.closest_hits) == (st1.traced_rays, st1.inner_steps, st1.tri_tests, st1.closest_hits)
-    b.close()
-    # the same for every order of the path ids (pixel-major by default; tile-major, sample-major) and for misses dropped early or late
-    # in shade.  9 samples per call in batches of 5 and 4: the pixel-major accumulate stages 8 samples per pass (accumulate.hpp)
-    # ... and for ray lists ordered by image band (default for batches of 32 Mi paths and more; forced on here), alone and with the other knobs
     for knobs in ({"path_order": 0, "retire_misses": 0, "batch": 5}, {"path_order": 1, "batch": 5}, {"path_order": 2, "batch": 9},
                   {"bands": 8, "bands_min_paths": 0, "batch": 4}, {"bands": 32, "bands_min_paths": 0, "path_order": 0, "batch": 5},
                   {"bands": 5, "bands_min_paths": 0, "retire_misses": 0, "pools": 1}):

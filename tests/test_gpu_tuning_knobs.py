@@ -25,7 +25,7 @@ WF_KNOBS = {
     "pools": (1, 8), "batch": (0, 4096), "max_batch": (1, 4096), "pool_paths_mi": (1, 1024), "budget_gib": (1, 256),
     "refill": (1, 64), "leaf_repeat": (1, 65), "inner_repeat": (1, 65), "obj_repeat": (1, 65), "obj_shift": (0, 6),
     "top_records": (0, 4096), "trace_blocks": (1, 64), "shade_chunk": (1, 256), "shade_chunk_banded": (1, 256),
-    "trace_chunk": (1, 256), "shadow_any_hit": (0, 1), "trace_events": (0, 1), "sort": (0, 1), "path_order": (0, 2),
+    "shadow_any_hit": (0, 1), "trace_events": (0, 1), "path_order": (0, 2),
     "retire_misses": (0, 1), "lds_tris": (0, 1), "first_lean": (0, 1), "bands": (1, 128), "bands_min_paths": (0, 0x7FFFFFFF),
     "spec_dedupe": (0, 1), "spec_keys": (1, 16), "spec_epochs": (1, 0xFFFF),
 }
@@ -55,9 +55,9 @@ def test_knob_range(renderer, name):
         _rejects(renderer, name, lo - 1, f"tuning knob {name}: {lo - 1} outside [{lo}, {hi}]")
 
 
-@pytest.mark.parametrize("name", ["no_such_knob", "pt_no_such_knob", "band_rows"])
+@pytest.mark.parametrize("name", ["no_such_knob", "pt_no_such_knob", "band_rows", "sort", "trace_chunk"])
 def test_unknown_knob(renderer, name):
-    """band_rows is a knob of multi-device contexts only"""
+    """band_rows is a knob of multi-device contexts only; sort and trace_chunk were removed"""
     _rejects(renderer, name, 1, f"unknown tuning knob '{name}'")
 
 
