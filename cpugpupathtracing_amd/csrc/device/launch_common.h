@@ -124,21 +124,4 @@ inline void FreeEvents(EventPairs& e)
     e = EventPairs{};
 }
 
-// CGPT_WF_PROFILE: step statistics of the COUNT kernels (of every kernel in the CGPT_PHASE_CYCLES diagnostic build), allocated on
-// first use and zeroed before every render; PhaseStatsArg is what the kernels of a render get
-#ifdef CGPT_PHASE_CYCLES
-inline bool PhaseStatsOn(bool) { return true; }
-#else
-inline bool PhaseStatsOn(bool count) { return count; }
-#endif
-inline unsigned long long* PhaseStatsArg(unsigned long long* stats, bool count) { return PhaseStatsOn(count) ? stats : nullptr; }
-
-inline hipError_t ResetPhaseStats(unsigned long long*& stats, size_t words, bool count, hipStream_t stream)
-{
-    hipError_t e = hipSuccess;
-    if (PhaseStatsOn(count) && getenv("CGPT_WF_PROFILE") != nullptr && !stats) e = hipMalloc((void**)&stats, words * sizeof(unsigned long long));
-    if (e == hipSuccess && stats) e = hipMemsetAsync(stats, 0, words * sizeof(unsigned long long), stream);
-    return e;
-}
-
 }  // namespace cgpt

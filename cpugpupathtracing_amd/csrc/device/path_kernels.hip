@@ -10,7 +10,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "device_scene.h"
 #include "rt_device.hpp"
@@ -146,8 +145,6 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
 // threads per block, for the launch and the occupancy query alike
 static uint32_t MegakernelBlockThreads(const DevRenderArgs& args)
 {
-    static const uint32_t env_block = getenv("CGPT_MEGA_BLOCK") ? (uint32_t)atoi(getenv("CGPT_MEGA_BLOCK")) : 0u;   // experiments: 64 or 256 for every call
-    if (env_block == 64u || env_block == 256u) return env_block;
     return args.n_samples == 1u ? 64u : 256u;
 }
 

@@ -15,7 +15,6 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstdio>
 #include <cstdlib>
 #include <new>
 
@@ -45,7 +44,6 @@ struct PtDev {
     float4* st_en;                     // [n_paths] {energy.xyz, bits(final depth)}: the finished paths' radiance
     float4* brute;                     // [level][thread][2] BruteLevel records of the brute-force paths (BRUTE kernels only)
     uint32_t* stack_overflow;          // [level - kLdsStackLevels][thread]: the rarely used deep end of the traversal stack
-    unsigned long long* phase_stats;   // COUNT kernels only: wave / lane steps per state
     uint32_t n_paths;                  // path ids 0 .. n_paths-1 of this batch
     PathGrid g;
     uint32_t* work;                    // the launch's kWorkCounters work counters, 32 bytes apart (zeroed before the launch)
@@ -90,19 +88,6 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
     float park_t = 0.0f;
     uint32_t park_obj = kNoHit, park_tri = 0, park_depth = 0;                 // its payload: a ray traced again after total internal reflection keeps its hit (SURVEY A-3)
     Counters cnt = { 0, 0, 0, 0, 0 };
-    uint32_t ph[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };                           // COUNT only: wave steps inner / leaf / object / shade, lanes object / shade, votes, refills, lanes leaf
-#ifdef CGPT_PHASE_CYCLES
-    // diagnostic build (scripts/build_variant.sh cyc -DCGPT_PHASE_CYCLES): where a wave's cycles go, by phase
-    constexpr bool kCyc = !COUNT;
-    unsigned long long cy[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, cy_mark = 0, cy_start = 0, cy_last_work = 0;   // refill, inner, leaf, object, shade, lean
-    uint32_t cn[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, cl[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    if (kCyc) cy_start = __builtin_readcyclecounter();
-#define PT_CYC_BEGIN() do { if (kCyc) cy_mark = __builtin_readcyclecounter(); } while (0)
-#define PT_CYC_END(i, lanes) do { if (kCyc) { cy[i] += __builtin_readcyclecounter() - cy_mark; cn[i]++; cl[i] += (lanes); } } while (0)
-#else
-#define PT_CYC_BEGIN() do { } while (0)
-#define PT_CYC_END(i, lanes) do { } while (0)
-#endif
 
     auto finish_path = [&](V3 energy) {                                       // ref: Main.cpp:575-578: the path's radiance leaves the kernel
         float4 o4; o4.x = energy.x; o4.y = energy.y; o4.z = energy.z; o4.w = __uint_as_float(pf & kPfDepthMask);
@@ -186,11 +171,9 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
     };
 
     for (;;) {
-        if (COUNT) ph[7]++;
         // ---- idle lanes take new paths: consecutive ids from the wave's fetched range ----
         const unsigned long long need = __builtin_amdgcn_ballot_w64(r.code == kIdle);
         uint32_t n_need = (uint32_t)__popcll(need);
-        PT_CYC_BEGIN();
         if (n_need) {
             work_fetch(work, pt.work, pt.n_paths, pt.coarse, pt.fine_below, n_need);
             const uint32_t take = min(n_need, work.loc_end - work.loc_next);
@@ -206,11 +189,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
                 }
             }
             work.loc_next += take;
-#ifdef CGPT_PHASE_CYCLES
-            if (kCyc && take) cy_last_work = __builtin_readcyclecounter();
-#endif
         }
-        PT_CYC_END(0, n_need);
         // Done when nothing is in flight and nothing is left to fetch (nothing in flight alone is not enough: every id just handed out
         // may have been padding of an edge tile; the step loop below then falls straight through and the wave fetches on)
         if (__builtin_amdgcn_ballot_w64(r.code != kIdle) == 0ull && work.exhausted && work.loc_next == work.loc_end) break;
@@ -226,63 +205,37 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
             if (n_busy == 0u) break;
             if (can_refill && 64u - n_busy >= tune.refill_idle) break;
             const uint32_t w_obj = n_obj << tune.obj_shift, w_shade = n_shade << pt.shade_shift;
-            if (COUNT) ph[6]++;
             // ---- the tail of the launch: a few rays left in this wave and no path to hand to the idle lanes: every lane runs its ray to
             //      the next object boundary in the lean loop (trace_steps.hpp: lean_traverse) -- the launch ends when its longest chain does
             if (TAIL && !can_refill && n_busy <= tune.tail_lanes && n_inner + n_leaf != 0u) {
-                PT_CYC_BEGIN();
                 if (r.code < kStartObject || (int32_t)r.code < 0) lean_traverse<COUNT, false>(ctx, r, cnt);
-                PT_CYC_END(5, n_inner + n_leaf);
                 continue;
             }
 
             if (n_inner >= n_leaf && n_inner >= w_obj && n_inner >= w_shade) {
                 do {
-                    if (COUNT) ph[0]++;
-                    PT_CYC_BEGIN();
                     if (r.code < kStartObject) inner_step<COUNT>(ctx, r, cnt);
-                    PT_CYC_END(1, n_inner);
                 } while ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64(r.code < kStartObject)) >= tune.inner_repeat);
             } else if (n_leaf >= w_obj && n_leaf >= w_shade) {
                 do {
-                    if (COUNT) { ph[1]++; ph[8] += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64((int32_t)r.code < 0)); }
-                    PT_CYC_BEGIN();
                     if ((int32_t)r.code < 0) leaf_step<COUNT, false>(ctx, r, cnt);
-                    PT_CYC_END(2, n_leaf);
                 } while ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64((int32_t)r.code < 0)) >= tune.leaf_repeat);
             } else if (w_obj >= w_shade) {
                 // ---- object step; a finished ray is dispatched on the spot ----
-                if (COUNT) { ph[2]++; ph[4] += n_obj; }
-                PT_CYC_BEGIN();
                 if (r.code == kStartObject && object_step<COUNT, false>(ctx, r, cnt)) ray_done();
-                PT_CYC_END(3, n_obj);
             } else {
                 // ---- shade step: one bounce of the path on the hit of its extend ray ----
-                if (COUNT) { ph[3]++; ph[5] += n_shade; }
-                PT_CYC_BEGIN();
                 if (r.code == kShade) shade_hit();
-                PT_CYC_END(4, n_shade);
             }
         }
     }
 
-#ifdef CGPT_PHASE_CYCLES
-    if (kCyc && pt.phase_stats && lane_id() == 0u) {
-        const unsigned long long now = __builtin_readcyclecounter();
-        atomicAdd(&pt.phase_stats[16], now - cy_start); atomicAdd(&pt.phase_stats[17], 1ull);
-        atomicAdd(&pt.phase_stats[18], now - (cy_last_work ? cy_last_work : cy_start));       // cycles after the wave's last refill: its drain
-        atomicMax(&pt.phase_stats[19], now - cy_start);
-        for (int i = 0; i < 6; ++i) { atomicAdd(&pt.phase_stats[20 + i], cy[i]); atomicAdd(&pt.phase_stats[28 + i], (unsigned long long)cn[i]); atomicAdd(&pt.phase_stats[36 + i], (unsigned long long)cl[i]); }
-    }
-#endif
     wave_add_u64(&args.counters->traced_rays, cnt.rays);
     if (COUNT) {
         wave_add_u64(&args.counters->inner_steps, cnt.inner);
         wave_add_u64(&args.counters->tri_tests, cnt.tris);
         wave_add_u64(&args.counters->bvh_depth_sum, cnt.depth);
         wave_add_u64(&args.counters->closest_hits, cnt.hits);
-        if (pt.phase_stats && lane_id() == 0u)
-            for (int i = 0; i < 9; ++i) atomicAdd(&pt.phase_stats[i], (unsigned long long)ph[i]);
     }
 }
 
@@ -320,7 +273,6 @@ struct PtHost {
     DevBuf<float4> brute;
     DevBuf<uint32_t> overflow;
     DevBuf<uint32_t> work_counters;           // kWorkCounters counters of 8 words per launch of a render, zeroed before it
-    unsigned long long* phase_stats = nullptr;
     hipStream_t streams[2] = { nullptr, nullptr };
     hipEvent_t begin = nullptr, acc_done[2] = { nullptr, nullptr };
     EventPairs ev;
@@ -375,7 +327,7 @@ void PersistentFree(void* state)
 {
     if (!state) return;
     PtHost* h = static_cast<PtHost*>(state);
-    (void)hipFree(h->st_en[0].p); (void)hipFree(h->st_en[1].p); (void)hipFree(h->brute.p); (void)hipFree(h->overflow.p); (void)hipFree(h->phase_stats); (void)hipFree(h->work_counters.p);
+    (void)hipFree(h->st_en[0].p); (void)hipFree(h->st_en[1].p); (void)hipFree(h->brute.p); (void)hipFree(h->overflow.p); (void)hipFree(h->work_counters.p);
     for (int i = 0; i < 2; ++i) {
         if (h->streams[i]) (void)hipStreamDestroy(h->streams[i]);
         if (h->acc_done[i]) (void)hipEventDestroy(h->acc_done[i]);
@@ -446,7 +398,6 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
     const uint32_t deep_levels = args_in.scene.stack_depth > kLdsStackLevels ? args_in.scene.stack_depth - kLdsStackLevels : 0u;
     LAUNCH_TRY(Grow(h->overflow, std::max<size_t>(1, (size_t)deep_levels * max_threads) * n_streams));
     if (brute) LAUNCH_TRY(Grow(h->brute, (size_t)(args_in.settings.max_ray_depth + 1) * max_threads * 2u * n_streams));
-    LAUNCH_TRY(ResetPhaseStats(h->phase_stats, 48, count, stream));
     if (ReserveEvents(ctx, h->ev, 2u * n_batches) != 0) return -1;
     const size_t work_words = (size_t)n_batches * kWorkCounters * 8u;
     LAUNCH_TRY(Grow(h->work_counters, work_words));
@@ -469,7 +420,6 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
         pt.st_en = h->st_en[s].p;
         pt.brute = brute ? h->brute.p + (size_t)s * (h->brute.n / n_streams) : nullptr;
         pt.stack_overflow = h->overflow.p + (size_t)s * (h->overflow.n / n_streams);
-        pt.phase_stats = PhaseStatsArg(h->phase_stats, count);
         pt.n_paths = n_pixels * bn;
         pt.g.n_pixels = n_pixels; pt.g.tiles_x = tiles_x; pt.g.div_tiles_x = MakeFastDiv(tiles_x); pt.g.div_n_pixels = MakeFastDiv(n_pixels);
         pt.shade_shift = h->tune.shade_shift;
@@ -488,32 +438,6 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
         launches += 2;
     }
     if (n_streams == 2 && k > 0) LAUNCH_TRY(hipStreamWaitEvent(stream, h->acc_done[(k - 1u) & 1u], 0));
-#ifdef CGPT_PHASE_CYCLES
-    if (!count && h->phase_stats) {
-        unsigned long long ps[48];
-        LAUNCH_TRY(hipStreamSynchronize(stream));
-        LAUNCH_TRY(hipMemcpy(ps, h->phase_stats, sizeof(ps), hipMemcpyDeviceToHost));
-        const double tot = (double)ps[16], waves = (double)ps[17];
-        static const char* names[6] = { "refill", "inner", "leaf", "object", "shade", "lean" };
-        fprintf(stderr, "[pt cycles] %.0f waves, mean life %.0f kcyc, longest %.0f kcyc, mean drain after the last refill %.0f kcyc |", waves, tot / waves / 1e3, ps[19] / 1e3, ps[18] / waves / 1e3);
-        double acc = 0;
-        for (int i = 0; i < 6; ++i) {
-            acc += ps[20 + i];
-            fprintf(stderr, " %s %.3f (%llu steps, %.0f cyc/step, %.1f lanes)", names[i], ps[20 + i] / tot, ps[28 + i], ps[28 + i] ? (double)ps[20 + i] / ps[28 + i] : 0.0, ps[28 + i] ? (double)ps[36 + i] / ps[28 + i] : 0.0);
-        }
-        fprintf(stderr, " other %.3f\n", 1.0 - acc / tot);
-    }
-#endif
-    if (count && h->phase_stats) {                                            // development aid: how full the steps were
-        unsigned long long ps[16];
-        LAUNCH_TRY(hipStreamSynchronize(stream));
-        LAUNCH_TRY(hipMemcpy(ps, h->phase_stats, sizeof(ps), hipMemcpyDeviceToHost));
-        DevCounters c;
-        LAUNCH_TRY(hipMemcpy(&c, args_in.counters, sizeof(c), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[pt profile] rays %llu | inner: %llu wave steps, %.1f lanes/step | leaf: %llu, %.1f | object: %llu, %.1f | shade: %llu, %.1f | votes %llu refills %llu\n",
-                c.traced_rays, ps[0], ps[0] ? (double)c.inner_steps / ps[0] : 0.0, ps[1], ps[1] ? (double)ps[8] / ps[1] : 0.0,
-                ps[2], ps[2] ? (double)ps[4] / ps[2] : 0.0, ps[3], ps[3] ? (double)ps[5] / ps[3] : 0.0, ps[6], ps[7]);
-    }
     return launches;
 }
 

@@ -389,21 +389,6 @@ __device__ __forceinline__ void inner_step(const TravCtx& c, Trav& r, Counters& 
         const float near_dist = swap ? right_dist : left_dist, far_dist = swap ? left_dist : right_dist;
         const bool miss = near_dist == 1e30f;                                 // ref: BVH.cpp:108-114
         const bool empty = r.sp == 0u;
-#ifdef CGPT_PHASE_CYCLES
-        if (r.code >= c.n_top) {                                              // diagnostic: how often would a partial record have been enough?
-            const SlabProducts sp_ = slab_products(n, r.rs);
-            auto xy_hit = [&](float t1x, float t2x, float t1y, float t2y) {
-                const float hx = fmaxf(t1x, t2x), lx = fminf(t1x, t2x), hy = fmaxf(t1y, t2y), ly = fminf(t1y, t2y);
-                const float tmax = fminf(hx, hy), tmin = fmaxf(lx, ly);
-                return tmax >= tmin && tmin < r.t && tmax > 0.0f;
-            };
-            auto x_hit = [&](float t1x, float t2x) { const float hx = fmaxf(t1x, t2x), lx = fminf(t1x, t2x); return lx < r.t && hx > 0.0f; };
-            cnt.global_inner++;
-            cnt.both_miss += miss ? 1u : 0u;
-            cnt.xy_both_miss += (!xy_hit(sp_.t1x.x, sp_.t2x.x, sp_.t1y.x, sp_.t2y.x) && !xy_hit(sp_.t1x.y, sp_.t2x.y, sp_.t1y.y, sp_.t2y.y)) ? 1u : 0u;
-            cnt.x_both_miss += (!x_hit(sp_.t1x.x, sp_.t2x.x) && !x_hit(sp_.t1x.y, sp_.t2x.y)) ? 1u : 0u;
-        }
-#endif
         c.stack[r.sp * kTraceBlock] = far_code;                                      // the free slot above the top: counts only if sp moves up
         r.code = miss ? (empty ? next_code : top) : near_code;
         r.cur_obj += (miss & empty) ? 1u : 0u;

@@ -37,7 +37,6 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstdio>
 #include <cstdlib>
 #include <new>
 
@@ -76,7 +75,6 @@ struct WfDev {
     uint32_t band_magic;               // band of path id p = min(n_bands - 1, umulhi(p, band_magic))
     uint32_t* plan;                    // {n_ext, n_sh}
     uint32_t* stack_overflow;          // [level - kLdsStackLevels][thread of the trace grid]: the rarely used deep end of the stack
-    unsigned long long* phase_stats;   // COUNT kernels only: {wave steps, lane steps} of the inner / leaf / object step, votes, refills
     uint32_t cap;                      // slots per kind
     uint32_t n_paths;                  // paths of this batch (path ids 0 .. n_paths-1, all valid)
     PathGrid g;                        // path id <-> pixel of the band (trace_steps.hpp)
@@ -166,19 +164,6 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
     uint32_t wave_rays = 0;                                                   // wave-uniform: rays this wave started (later rounds)
     uint32_t wave_followers = 0;                                              // wave-uniform: of those, followers of a specular chain (not traced)
     Counters cnt = { 0, 0, 0, 0, 0 };
-    uint32_t ph_inner = 0, ph_leaf = 0, ph_leaf_lanes = 0, ph_obj = 0, ph_obj_lanes = 0, ph_votes = 0, ph_refills = 0;   // wave-uniform, COUNT only
-#ifdef CGPT_PHASE_CYCLES
-    // diagnostic build (scripts/build_variant.sh cyc -DCGPT_PHASE_CYCLES): where a later-round wave's cycles go, by phase
-    constexpr bool kCyc = !COUNT && !FIRST;
-    unsigned long long cy_refill = 0, cy_inner = 0, cy_leaf = 0, cy_obj = 0, cy_start = 0, cy_mark = 0;
-    uint32_t cn_inner = 0, cn_leaf = 0, cn_obj = 0, cl_inner = 0, cl_leaf = 0, cl_obj = 0, cn_inner_lds = 0;
-    if (kCyc) cy_start = __builtin_readcyclecounter();
-#define CYC_BEGIN() do { if (kCyc) cy_mark = __builtin_readcyclecounter(); } while (0)
-#define CYC_END(acc) do { if (kCyc) acc += __builtin_readcyclecounter() - cy_mark; } while (0)
-#else
-#define CYC_BEGIN() do { } while (0)
-#define CYC_END(acc) do { } while (0)
-#endif
 
     auto finish_ray = [&]() {                                                 // the ray of this lane has seen every object of the scene
         // The slot's addresses are formed here, when the ray ends: left to the optimiser they are hoisted to where the slot is assigned
@@ -211,8 +196,6 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
     };
 
     for (;;) {
-        if (COUNT) ph_refills++;
-        CYC_BEGIN();
         // ---- refill idle lanes from the ring; top the ring up with this wave's next blocks of the dense list ----
         const unsigned long long need = __builtin_amdgcn_ballot_w64(r.code == kIdle);
         const uint32_t n_need = (uint32_t)__popcll(need);
@@ -272,7 +255,6 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
         // Done when nothing is in flight and nothing is left to fetch.  Nothing in flight alone is not enough: every id just handed
         // out may have been padding of an edge tile (round 0: a padded row of a tile; later rounds never list one); the step loop below
         // then falls straight through and the wave fetches on.
-        CYC_END(cy_refill);
         if (__builtin_amdgcn_ballot_w64(r.code != kIdle) == 0ull && ring_count == 0u && block >= n_blocks) break;
         const bool can_refill = ring_count != 0u || block < n_blocks;
 
@@ -285,7 +267,6 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
             if (n_busy == 0u) break;
             if (can_refill && 64u - n_busy >= tune.refill_idle) break;        // enough idle lanes: go refill them
             const uint32_t w_obj = n_obj << tune.obj_shift;
-            if (COUNT) ph_votes++;
             // Round 0: the 64 lanes of a wave carry the primary rays of one 8x8 tile -- neighbouring rays that walk nearly the same
             // nodes, so there is little divergence for the voted branch-free steps to buy off; every lane walks its meshes in the lean
             // loop (the reference's own control flow, trace_steps.hpp: lean_traverse -- ~50 instructions per node instead of ~75 and no
@@ -297,51 +278,21 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
             }
 
             if (n_inner >= n_leaf && n_inner >= w_obj) {
-                CYC_BEGIN();
                 do {
-                    if (COUNT) ph_inner++;
-#ifdef CGPT_PHASE_CYCLES
-                    if (kCyc) { cn_inner++; cl_inner += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(r.code < kStartObject)); cn_inner_lds += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(r.code < ctx.n_top)); }
-#endif
                     if (r.code < kStartObject) inner_step<COUNT>(ctx, r, cnt);
                 } while ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64(r.code < kStartObject)) >= tune.inner_repeat);
-                CYC_END(cy_inner);
             } else if (n_leaf >= w_obj) {
-                CYC_BEGIN();
                 do {
-                    if (COUNT) { ph_leaf++; ph_leaf_lanes += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64((int32_t)r.code < 0)); }
-#ifdef CGPT_PHASE_CYCLES
-                    if (kCyc) { cn_leaf++; cl_leaf += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64((int32_t)r.code < 0)); }
-#endif
                     if ((int32_t)r.code < 0) leaf_step<COUNT, !FIRST>(ctx, r, cnt);
                 } while ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64((int32_t)r.code < 0)) >= tune.leaf_repeat);
-                CYC_END(cy_leaf);
             } else {
-                CYC_BEGIN();
                 do {
-                    if (COUNT) { ph_obj++; ph_obj_lanes += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(r.code == kStartObject)); }
-#ifdef CGPT_PHASE_CYCLES
-                    if (kCyc) { cn_obj++; cl_obj += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(r.code == kStartObject)); }
-#endif
                     if (r.code == kStartObject && object_step<COUNT, !FIRST>(ctx, r, cnt)) finish_ray();
                 } while ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64(r.code == kStartObject)) >= tune.obj_repeat);
-                CYC_END(cy_obj);
             }
         }
     }
 
-#ifdef CGPT_PHASE_CYCLES
-    if (kCyc && wf.phase_stats && lane_id() == 0u) {
-        const unsigned long long total = __builtin_readcyclecounter() - cy_start;
-        const unsigned long long v[12] = { total, cy_refill, cy_inner, cy_leaf, cy_obj, cn_inner, cn_leaf, cn_obj, cl_inner, cl_leaf, cl_obj, cn_inner_lds };
-        for (int i = 0; i < 12; ++i) atomicAdd(&wf.phase_stats[8 + i], v[i]);
-        atomicAdd(&wf.phase_stats[20], 1ull);
-    }
-    if (kCyc && wf.phase_stats) {
-        wave_add_u64(&wf.phase_stats[21], cnt.global_inner); wave_add_u64(&wf.phase_stats[22], cnt.both_miss);
-        wave_add_u64(&wf.phase_stats[23], cnt.xy_both_miss); wave_add_u64(&wf.phase_stats[24], cnt.x_both_miss);
-    }
-#endif
     // round 0: every traced pixel ray is the IntersectScene call of each of the batch's samples (the reference's counts); the lanes'
     // 32-bit sums are of per-pixel counts and the product is formed in 64 bits
     const uint32_t per_ray = first_round ? wf.g.n_samples : 1u;
@@ -352,12 +303,6 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
         wave_add_u64(&counters->inner_steps, cnt.inner, per_ray);
         wave_add_u64(&counters->tri_tests, cnt.tris, per_ray);
         wave_add_u64(&counters->bvh_depth_sum, cnt.depth, per_ray);
-        if (wf.phase_stats && lane_id() == 0u) {
-            atomicAdd(&wf.phase_stats[0], (unsigned long long)ph_inner); atomicAdd(&wf.phase_stats[1], (unsigned long long)ph_leaf);
-            atomicAdd(&wf.phase_stats[2], (unsigned long long)ph_obj); atomicAdd(&wf.phase_stats[3], (unsigned long long)ph_obj_lanes);
-            atomicAdd(&wf.phase_stats[4], (unsigned long long)ph_votes); atomicAdd(&wf.phase_stats[5], (unsigned long long)ph_refills);
-            atomicAdd(&wf.phase_stats[6], (unsigned long long)ph_leaf_lanes);
-        }
     }
 }
 
@@ -802,7 +747,6 @@ struct WfHost {
     uint32_t n_cus = 0;
     uint32_t trace_blocks_per_cu[2][2] = {}, shade_blocks_per_cu[2][2] = {};   // trace: [COUNT][FIRST]; shade: [COUNT][BRUTE]
     size_t occupancy_lds = 0;
-    unsigned long long* phase_stats = nullptr;   // CGPT_WF_PROFILE=1: step counts of the COUNT trace kernels, printed after the render
     // hipEvent pairs around every trace launch of the last render (roofline accounting: the dominant kernel's own duration)
     EventPairs trace_ev;
     uint32_t trace_rounds = 0;
@@ -827,7 +771,6 @@ void WavefrontFree(void* state)
         if (h->acc_done[p]) (void)hipEventDestroy(h->acc_done[p]);
     }
     if (h->begin) (void)hipEventDestroy(h->begin);
-    (void)hipFree(h->phase_stats);
     FreeEvents(h->trace_ev);
     delete h;
 }
@@ -900,7 +843,6 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
     hipStream_t stream = CtxStream(ctx);
     WfHost* h = WfGetHost(ctx);
     if (!h) return -1;
-    LAUNCH_TRY(ResetPhaseStats(h->phase_stats, 32, count, stream));
     const uint32_t rows = args_in.n_rows;
     const uint32_t tiles_x = (args_in.width + 7u) / 8u, tiles_y = (rows + 7u) / 8u;
     const uint64_t n_pixels64 = (uint64_t)tiles_x * tiles_y * 64u;             // padded to whole 8x8 tiles
@@ -1012,7 +954,6 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
         const uint32_t bfirst = args_in.first_sample + done;
         WfDev wf = h->dev[p];
         wf.cap = h->held.cap; wf.g.n_pixels = n_pixels; wf.n_paths = n_pixels * bn;
-        wf.phase_stats = PhaseStatsArg(h->phase_stats, count);
         wf.rot_trace[0] = CoprimeRotation(trace_grid_later.x * (kTraceBlock / 64u), tiles_x * tiles_y);
         wf.rot_trace[1] = CoprimeRotation(trace_grid_first.x * (kTraceBlock / 64u), tiles_x * tiles_y);
         wf.rot_shade = CoprimeRotation(shade_grid.x * 4u, std::max(1u, tiles_x * tiles_y / shade_chunk));
@@ -1057,31 +998,6 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
     }
     // the context's stream continues after the last accumulate (which transitively follows all the others)
     if (k > 0) LAUNCH_TRY(hipStreamWaitEvent(stream, h->acc_done[(k - 1u) % n_pools], 0));
-#ifdef CGPT_PHASE_CYCLES
-    if (!count && h->phase_stats) {                                           // diagnostic build: cycles of the later-round trace waves by phase
-        unsigned long long ps[32];
-        LAUNCH_TRY(hipStreamSynchronize(stream));
-        LAUNCH_TRY(hipMemcpy(ps, h->phase_stats, sizeof(ps), hipMemcpyDeviceToHost));
-        const double tot = (double)ps[8];
-        fprintf(stderr, "[wf cycles] later-round trace: %llu waves, %.0f Mcyc/wave | refill %.3f inner %.3f leaf %.3f object %.3f other %.3f | cycles per wave-step: inner %.0f (%.1f lanes, %.2f from LDS) leaf %.0f (%.1f lanes) object %.0f (%.1f lanes)\n",
-                ps[20], ps[20] ? tot / ps[20] / 1e6 : 0.0, ps[9] / tot, ps[10] / tot, ps[11] / tot, ps[12] / tot, 1.0 - (ps[9] + ps[10] + ps[11] + ps[12]) / tot,
-                ps[13] ? (double)ps[10] / ps[13] : 0.0, ps[13] ? (double)ps[16] / ps[13] : 0.0, ps[16] ? (double)ps[19] / ps[16] : 0.0,
-                ps[14] ? (double)ps[11] / ps[14] : 0.0, ps[14] ? (double)ps[17] / ps[14] : 0.0,
-                ps[15] ? (double)ps[12] / ps[15] : 0.0, ps[15] ? (double)ps[18] / ps[15] : 0.0);
-        fprintf(stderr, "[wf cycles] inner lane-steps served from global memory: %llu; both children missed %.3f; both missed on the x,y slabs alone %.3f; on the x slab alone %.3f\n",
-                ps[21], ps[21] ? (double)ps[22] / ps[21] : 0.0, ps[21] ? (double)ps[23] / ps[21] : 0.0, ps[21] ? (double)ps[24] / ps[21] : 0.0);
-    }
-#endif
-    if (count && h->phase_stats) {                                            // development aid: how full the steps were
-        unsigned long long ps[8];
-        LAUNCH_TRY(hipStreamSynchronize(stream));
-        LAUNCH_TRY(hipMemcpy(ps, h->phase_stats, sizeof(ps), hipMemcpyDeviceToHost));
-        DevCounters c;
-        LAUNCH_TRY(hipMemcpy(&c, args_in.counters, sizeof(c), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[wf profile] rays %llu | inner: %llu wave steps, %.1f lanes/step | leaf: %llu wave steps, %.1f lanes/step | object: %llu wave steps, %.1f lanes/step | votes %llu refills %llu\n",
-                c.traced_rays, ps[0], ps[0] ? (double)c.inner_steps / ps[0] : 0.0, ps[1], ps[1] ? (double)ps[6] / ps[1] : 0.0,
-                ps[2], ps[2] ? (double)ps[3] / ps[2] : 0.0, ps[4], ps[5]);
-    }
     return launches;
 }
 
