@@ -19,6 +19,7 @@ KERNEL_AUTO, KERNEL_MEGAKERNEL, KERNEL_WAVEFRONT, KERNEL_PERSISTENT = 0, 1, 2, 3
 RENDER_COUNTERS = 1
 CTX_FORCE_COLLECTIVE, CTX_GATHER_PEER_COPY = 1, 2
 BUILD_NAIVE, BUILD_SAH_INTERVALS, BUILD_SAH_PRIMITIVES = 0, 1, 2
+DENOISE_DEMODULATE_ALBEDO = 1
 
 f3 = C.c_float * 3
 
@@ -82,6 +83,11 @@ class Stats(C.Structure):
                 ("dominant_round0_ms", C.c_double), ("dominant_round0_launches", C.c_uint32), ("chain_followers", C.c_uint32)]
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("flags", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_position", C.c_float)]
+
+
 class BvhInfo(C.Structure):
     _fields_ = [("num_triangles", C.c_uint32), ("nodes_used", C.c_uint32), ("num_leaves", C.c_uint32),
                 ("max_leaf_size", C.c_uint32), ("max_depth", C.c_uint32), ("total_area", C.c_float)]
@@ -119,6 +125,8 @@ PROTOTYPES = {
     "cgpt_synchronize": (C.c_int, [_vp]),
     "cgpt_write_accumulator": (C.c_int, [_vp, C.POINTER(RenderParams), _fp, C.c_size_t, C.c_uint32]),
     "cgpt_set_tuning": (C.c_int, [_vp, C.c_char_p, C.c_uint32]),
+    "cgpt_read_guides": (C.c_int, [_vp, C.POINTER(Camera), _fp, C.c_size_t]),
+    "cgpt_denoise": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(DenoiseParams), _fp, C.c_size_t, _up, C.c_size_t]),
     "cgpt_measure_issue_rate": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     # cpugpupt_host.h
     "cgpth_last_error": (C.c_char_p, []),

@@ -504,6 +504,7 @@ int cgpt_ctx_destroy(cgpt_ctx* ctx)
     (void)hipFree(ctx->d_counters);
     WavefrontFree(ctx->wavefront_state);
     PersistentFree(ctx->persistent_state);
+    DenoiseFree(ctx);
     (void)hipEventDestroy(ctx->ev_start); (void)hipEventDestroy(ctx->ev_stop);
     (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -526,6 +527,7 @@ int cgpt_scene_upload(cgpt_ctx* ctx, const cgpt_scene_desc* scene)
     if (!scene) return Fail(ctx, CGPT_ERR_INVALID, "scene is null");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->scene_generation++;                                                   // the denoiser's guides are stale (denoise.hip)
     try {                                                                      // the re-layout allocates host vectors: nothing may unwind through the C ABI
         return BuildDeviceScene(ctx, *scene);
     } catch (const std::exception& e) {
@@ -546,6 +548,7 @@ int cgpt_scene_update_materials(cgpt_ctx* ctx, const cgpt_material* materials, u
     for (uint32_t i = 0; i < n_materials; ++i) PackMaterial(materials[i], mats.data() + 4 * (size_t)i);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->scene_generation++;
     HIP_TRY(ctx, hipMemcpy(ctx->d_materials, mats.data(), mats.size() * sizeof(float4), hipMemcpyHostToDevice));
     return CGPT_OK;
 }
@@ -753,6 +756,7 @@ int cgpt_write_accumulator(cgpt_ctx* ctx, const cgpt_render_params* p, const flo
     HIP_TRY(ctx, LaunchPackPixels(ctx->d_accumulator, ctx->d_pixels, n, num_accumulated, ctx->stream));   // data.pixels, ref: Main.cpp:741
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->num_accumulated = num_accumulated;                                    // ref: Main.cpp:205
+    ctx->last_debug_mode = 0;                                                  // data.pixels are the packed sums again
     return CGPT_OK;
 }
 

@@ -80,6 +80,19 @@ struct cgpt_ctx {
 
     // n_devices > 1 (or CGPT_CTX_FORCE_COLLECTIVE): this context is a group; the members are ordinary one-device contexts
     cgpt::DeviceGroup* group = nullptr;
+
+    // the denoiser (denoise.hip): first-hit guides cached per camera, band and scene, and the filter's ping-pong buffers
+    uint64_t scene_generation = 0;                // bumped by every scene upload and in-place edit
+    float4* d_guides = nullptr;                   // 3 float4 per pixel, the cgpt_read_guides layout
+    float4* d_guide_demod = nullptr;              // per pixel: the albedo the filter divides by ({1,1,1} where it does not)
+    size_t guide_pixels = 0;                      // pixels allocated in the two above
+    bool guides_valid = false;
+    uint64_t guide_generation = 0;                // what the guides were computed for
+    cgpt_camera guide_camera{};
+    uint32_t guide_frame[4] = { 0, 0, 0, 0 };     // width, height, first global row, rows
+    float4* d_denoise[2] = { nullptr, nullptr };
+    uint32_t* d_denoise_pixels = nullptr;
+    size_t denoise_pixels = 0;                    // pixels allocated in the three above
 };
 
 
@@ -121,4 +134,10 @@ int GroupSynchronize(cgpt_ctx* ctx);
 cgpt_ctx* GroupFirstMember(cgpt_ctx* ctx);
 cgpt_ctx* GroupFirstMemberOrNull(cgpt_ctx* ctx);
 int GroupForwarded(cgpt_ctx* ctx, int rc);     // a call forwarded to the first member returned rc: its message becomes the group's
+// the denoiser's view of a group's frame: its size, samples and the debug mode of the last render; and the gathered full frame on
+// device_ids[0] (the gather cgpt_read_accumulator does), with the group's gather state and statistics left as they were
+void GroupFrameInfo(cgpt_ctx* ctx, uint32_t* width, uint32_t* height, uint32_t* num_accumulated, uint32_t* last_debug_mode);
+int GroupGatherUncounted(cgpt_ctx* ctx, const float4** frame);
+
+void DenoiseFree(cgpt_ctx* ctx);               // denoise.hip: the guide cache and filter buffers of a one-device context
 }  // namespace cgpt

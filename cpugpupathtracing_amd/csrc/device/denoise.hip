@@ -1,0 +1,369 @@
+// denoise.hip -- an edge-avoiding a-trous filter guided by first-hit buffers (gfx950): cgpt_read_guides, cgpt_denoise.
+//
+// Guides: the reference does not jitter primary rays (SURVEY A-14), so every sample of a pixel has the same first hit, and one primary
+// trace per camera gives each pixel's position, normal and albedo.  guides_kernel computes that hit with the render paths' own device
+// functions -- camera_ray with primary_ray's u, v (trace_steps.hpp), intersect_scene with the LDS stack set up as intersect_rays_kernel
+// does, get_hit, load_material -- so the guides are the render's primary hit bit for bit.  The context keeps them until the camera, the
+// band or the scene changes (every upload and in-place edit bumps cgpt_ctx::scene_generation).
+//
+// Filter (tests/denoise_ref.py states it in numpy): pass i = 0 .. I-1 has step s = 2^i and taps q = p + s (dx, dy),
+// dx, dy in -2..2, skipped outside the band; weight h(dx) h(dy) exp(-|c(q) - c(p)|^2 / (sigma_c 2^-i)^2) times, when p and q both hit,
+// exp(-|n(q) - n(p)|^2 / sigma_n^2) exp(-(n(p).(x(q) - x(p)))^2 / sigma_x^2); a hit and a miss never mix.  denoise_prepare divides the
+// accumulator by num_accumulated (data.pixels' division) and by the albedo (demodulation); the last pass multiplies the albedo back and
+// packs the pixels as data.pixels are packed.  One launch per pass, 16x16-pixel blocks, ping-pong float4 buffers of the context.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+
+#include "cpugpupt_abi.h"
+#include "ctx_internal.h"
+#include "device_scene.h"
+#include "rt_device.hpp"
+#include "shade_device.hpp"
+
+namespace cgpt {
+
+using namespace dev;
+
+extern __shared__ uint32_t denoise_lds[];
+
+namespace {
+
+constexpr uint32_t kTile = 16;                   // 16x16 pixels = one 256-thread block
+constexpr uint32_t kMaxIterations = 10;
+constexpr cgpt_denoise_params kDefaults = { 5u, CGPT_DENOISE_DEMODULATE_ALBEDO, 4.0f, 0.2f, 0.3f };
+
+// pixel of a thread: 16x16 tiles in row-major tile order (a 1-D grid: no limit on the frame's height)
+__device__ __forceinline__ void tile_pixel(uint32_t width, uint32_t& px, uint32_t& row)
+{
+    const uint32_t tiles_x = (width + kTile - 1u) / kTile;
+    const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    px = tx * kTile + (threadIdx.x & (kTile - 1u));
+    row = ty * kTile + threadIdx.x / kTile;
+}
+
+// One thread per pixel of the band (global rows first_row ..): {x.xyz, t | n.xyz, bits(obj) | albedo.xyz, bits(mat_index)} and the
+// demodulation albedo (the albedo per channel where it is >= 1e-3 on a hit that is not a light, else 1).
+__global__ void __launch_bounds__(256) guides_kernel(const DevScene sc, const DevCamera cam, uint32_t width, uint32_t height, uint32_t first_row,
+                                                     uint32_t n_rows, float4* __restrict__ guides, float4* __restrict__ demod)
+{
+    uint32_t px, row;
+    tile_pixel(width, px, row);
+    if (px >= width || row >= n_rows) return;
+    uint32_t* const stack = denoise_lds + threadIdx.x;
+    const uint32_t py = first_row + row;
+    Ray ray = camera_ray(cam, (float)px * (1.0f / (float)width), (float)py * (1.0f / (float)height));   // primary_ray's u, v
+    Counters cnt = { 0, 0, 0, 0, 0 };                                          // not booked: cgpt_stats does not grow
+    intersect_scene<false>(sc, ray, stack, blockDim.x, cnt);
+    float4 g0 = make_float4(0.0f, 0.0f, 0.0f, 1e34f);
+    float4 g1 = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kNoHit));
+    float4 g2 = g1;
+    float4 m = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+    if (ray.obj != kNoHit) {
+        const Hit h = get_hit<false>(sc, ray, cnt);
+        const Mat mat = load_material(sc, h.mat);
+        g0 = make_float4(h.pos.x, h.pos.y, h.pos.z, ray.t);
+        g1 = make_float4(h.normal.x, h.normal.y, h.normal.z, __uint_as_float(ray.obj));
+        g2 = make_float4(mat.albedo.x, mat.albedo.y, mat.albedo.z, __uint_as_float(h.mat));
+        if (!mat.is_light) {
+            m.x = mat.albedo.x >= 1e-3f ? mat.albedo.x : 1.0f;
+            m.y = mat.albedo.y >= 1e-3f ? mat.albedo.y : 1.0f;
+            m.z = mat.albedo.z >= 1e-3f ? mat.albedo.z : 1.0f;
+        }
+    }
+    const size_t i = (size_t)row * width + px;
+    guides[3 * i] = g0; guides[3 * i + 1] = g1; guides[3 * i + 2] = g2;
+    demod[i] = m;
+}
+
+struct PassArgs {
+    const float4* src;        // the previous pass's output (pass 0: denoise_prepare's)
+    float4* dst;
+    uint32_t* pixels;         // last pass
+    const float4* guides;
+    const float4* demod;
+    uint32_t width, n_rows, step, demodulate;
+    float inv_color, inv_normal, inv_position;   // 1 / sigma^2 of this pass
+};
+
+// c_0 = acc / num_accumulated (data.pixels' division, ref: Main.cpp:741), divided by the albedo with demodulation.  Once per pixel here
+// rather than in each of pass 0's 25 taps: 150 IEEE divisions per pixel took that pass to 256 VGPRs, one wave per SIMD.
+__global__ void __launch_bounds__(256) denoise_prepare(const float4* __restrict__ acc, const float4* __restrict__ demod, float4* __restrict__ dst,
+                                                       size_t n_pixels, float n, uint32_t demodulate)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pixels) return;
+    const float4 a = acc[i];
+    float4 c = make_float4(a.x / n, a.y / n, a.z / n, 0.0f);
+    if (demodulate) {
+        const float4 m = demod[i];
+        c.x = c.x / m.x; c.y = c.y / m.y; c.z = c.z / m.z;
+    }
+    dst[i] = c;
+}
+
+// h(d) of the B3 spline 1/16 (1, 4, 6, 4, 1): 3/8, 1/4, 1/16
+__device__ __forceinline__ constexpr float tap(int d) { return d == 0 ? 0.375f : (d == 1 || d == -1 ? 0.25f : 0.0625f); }
+
+template <bool LAST>
+__global__ void __launch_bounds__(256) atrous_pass(const PassArgs a)
+{
+    uint32_t px, row;
+    tile_pixel(a.width, px, row);
+    if (px >= a.width || row >= a.n_rows) return;
+    const size_t i = (size_t)row * a.width + px;
+    const float4 xp4 = a.guides[3 * i], np4 = a.guides[3 * i + 1];
+    const V3 x_p = mk(xp4.x, xp4.y, xp4.z), n_p = mk(np4.x, np4.y, np4.z);
+    const bool hit_p = __float_as_uint(np4.w) != kNoHit;
+    const float4 cp4 = a.src[i];
+    const V3 c_p = mk(cp4.x, cp4.y, cp4.z);
+    float sr = 0.0f, sg = 0.0f, sb = 0.0f, wsum = 0.0f;
+    // A row of five taps at a time: first all their loads, each from the tap's position clamped into the band, then the weights, where a
+    // tap outside the band (skipped, not clamped) or across a hit / miss edge gets none.  Selects, not branches: a branch would pull the
+    // loads after it, and every tap would wait for its own.
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const long long qy = (long long)row + (long long)dy * a.step;
+        const bool row_in = qy >= 0 && qy < (long long)a.n_rows;
+        const size_t qy_c = (size_t)(qy < 0 ? 0 : (row_in ? qy : (long long)a.n_rows - 1));
+        float4 xq[5], nq[5];
+        V3 cq[5];
+        bool in[5];
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+            const long long qx = (long long)px + (long long)(t - 2) * a.step;
+            in[t] = row_in && qx >= 0 && qx < (long long)a.width;
+            const size_t j = qy_c * a.width + (size_t)(qx < 0 ? 0 : (qx < (long long)a.width ? qx : (long long)a.width - 1));
+            xq[t] = a.guides[3 * j]; nq[t] = a.guides[3 * j + 1];
+            const float4 c4 = a.src[j];
+            cq[t] = mk(c4.x, c4.y, c4.z);
+        }
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+            const bool hit_q = __float_as_uint(nq[t].w) != kNoHit;
+            const V3 dc = cq[t] - c_p;
+            const V3 dn = mk(nq[t].x, nq[t].y, nq[t].z) - n_p;
+            const float dplane = dot(n_p, mk(xq[t].x, xq[t].y, xq[t].z) - x_p);   // distance to p's tangent plane
+            const float e_geo = dot(dn, dn) * a.inv_normal + dplane * dplane * a.inv_position;
+            const float e = dot(dc, dc) * a.inv_color + (hit_p && hit_q ? e_geo : 0.0f);
+            const float w = (tap(t - 2) * tap(dy)) * __expf(-e);                // the centre tap: e = 0, w = h
+            const bool use = in[t] && hit_q == hit_p;                         // a hit and a miss never mix
+            sr = use ? sr + cq[t].x * w : sr;
+            sg = use ? sg + cq[t].y * w : sg;
+            sb = use ? sb + cq[t].z * w : sb;
+            wsum = use ? wsum + w : wsum;
+        }
+        __builtin_amdgcn_sched_barrier(0);                                    // one row's loads in flight at a time: the registers of five taps
+    }
+    V3 r = mk(sr / wsum, sg / wsum, sb / wsum);
+    if (LAST) {
+        if (a.demodulate) {
+            const float4 m = a.demod[i];
+            r = mk(r.x * m.x, r.y * m.y, r.z * m.z);
+        }
+        a.dst[i] = make_float4(r.x, r.y, r.z, 1.0f);
+        a.pixels[i] = vec4_to_uint(r.x, r.y, r.z);
+    } else {
+        a.dst[i] = make_float4(r.x, r.y, r.z, 0.0f);
+    }
+}
+
+// iterations = 0: the accumulator / num_accumulated, packed as data.pixels is (the same division and packing: the same bits)
+__global__ void __launch_bounds__(256) denoise_identity(const float4* __restrict__ acc, float4* __restrict__ dst, uint32_t* __restrict__ pixels,
+                                                        size_t n_pixels, float n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pixels) return;
+    const float4 a = acc[i];
+    const float r = a.x / n, g = a.y / n, b = a.z / n;
+    dst[i] = make_float4(r, g, b, 1.0f);
+    pixels[i] = vec4_to_uint(r, g, b);
+}
+
+#define DN_HIP(ctx, expr)                                                                                         \
+    do {                                                                                                          \
+        hipError_t e_ = (expr);                                                                                   \
+        if (e_ != hipSuccess) return CtxFail((ctx), CGPT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+// what a call works on: a one-device context's contiguous band, or a multi-device context's full frame on its first member
+struct Frame {
+    cgpt_ctx* dev;            // the one-device context whose device, stream, scene and buffers do the work
+    uint32_t width, height, first_row, n_rows, num_accumulated;
+};
+
+int ResolveFrame(cgpt_ctx* ctx, bool denoise, const cgpt_camera* camera, Frame& f)
+{
+    uint32_t width, height, num_accumulated, debug;
+    if (ctx->group) {
+        if (!ctx->has_scene || !GroupFirstMember(ctx)->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
+        GroupFrameInfo(ctx, &width, &height, &num_accumulated, &debug);
+        if (width == 0) return CtxFail(ctx, CGPT_ERR_INVALID, "nothing rendered yet");
+        f.dev = GroupFirstMember(ctx); f.first_row = 0; f.n_rows = height;
+    } else {
+        if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
+        if (!ctx->d_accumulator) return CtxFail(ctx, CGPT_ERR_INVALID, "nothing rendered yet");
+        width = ctx->width; height = ctx->height; num_accumulated = ctx->num_accumulated; debug = ctx->last_debug_mode;
+        f.dev = ctx; f.first_row = ctx->band_key[0]; f.n_rows = ctx->n_rows;
+    }
+    if (denoise && num_accumulated == 0) return CtxFail(ctx, CGPT_ERR_INVALID, "nothing accumulated (num_accumulated is 0)");
+    if (debug != 0u) return CtxFail(ctx, CGPT_ERR_INVALID, "the last render was a debug view (debug_render_mode %u): its pixels are not radiance", debug);
+    if (!ctx->group && (ctx->band_key[2] != 0u || ctx->band_key[3] != 0u))
+        return CtxFail(ctx, CGPT_ERR_INVALID, "an interleaved band: its rows are not neighbours (a multi-device context filters the gathered frame)");
+    if (!camera) return CtxFail(ctx, CGPT_ERR_INVALID, "camera is null");
+    f.width = width; f.height = height; f.num_accumulated = num_accumulated;
+    return CGPT_OK;
+}
+
+int EnsureGuides(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera)
+{
+    cgpt_ctx* d = f.dev;
+    const uint32_t key[4] = { f.width, f.height, f.first_row, f.n_rows };
+    if (d->guides_valid && d->guide_generation == d->scene_generation && memcmp(d->guide_frame, key, sizeof(key)) == 0 &&
+        memcmp(&d->guide_camera, camera, sizeof(cgpt_camera)) == 0)
+        return CGPT_OK;
+    d->guides_valid = false;
+    const size_t n = (size_t)f.width * f.n_rows;
+    if (d->guide_pixels != n) {
+        (void)hipFree(d->d_guides); (void)hipFree(d->d_guide_demod);
+        d->d_guides = d->d_guide_demod = nullptr; d->guide_pixels = 0;
+        DN_HIP(ctx, hipMalloc((void**)&d->d_guides, 3 * n * sizeof(float4)));
+        DN_HIP(ctx, hipMalloc((void**)&d->d_guide_demod, n * sizeof(float4)));
+        d->guide_pixels = n;
+    }
+    DevCamera cam;
+    static_assert(sizeof(DevCamera) == sizeof(cgpt_camera), "camera layouts");
+    memcpy(&cam, camera, sizeof(cam));
+    const uint32_t tiles = ((f.width + kTile - 1u) / kTile) * ((f.n_rows + kTile - 1u) / kTile);
+    const size_t lds = (size_t)d->scene.stack_depth * 256u * sizeof(uint32_t);   // intersect_rays_kernel's stack
+    hipLaunchKernelGGL(guides_kernel, dim3(tiles), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
+                       d->d_guides, d->d_guide_demod);
+    DN_HIP(ctx, hipGetLastError());
+    memcpy(d->guide_frame, key, sizeof(key));
+    memcpy(&d->guide_camera, camera, sizeof(cgpt_camera));
+    d->guide_generation = d->scene_generation;
+    d->guides_valid = true;
+    return CGPT_OK;
+}
+
+int EnsureFilterBuffers(cgpt_ctx* ctx, cgpt_ctx* d, size_t n)
+{
+    if (d->denoise_pixels == n) return CGPT_OK;
+    (void)hipFree(d->d_denoise[0]); (void)hipFree(d->d_denoise[1]); (void)hipFree(d->d_denoise_pixels);
+    d->d_denoise[0] = d->d_denoise[1] = nullptr; d->d_denoise_pixels = nullptr; d->denoise_pixels = 0;
+    DN_HIP(ctx, hipMalloc((void**)&d->d_denoise[0], n * sizeof(float4)));
+    DN_HIP(ctx, hipMalloc((void**)&d->d_denoise[1], n * sizeof(float4)));
+    DN_HIP(ctx, hipMalloc((void**)&d->d_denoise_pixels, n * sizeof(uint32_t)));
+    d->denoise_pixels = n;
+    return CGPT_OK;
+}
+
+int Denoise(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, const cgpt_denoise_params& p, const float4* acc, float* dst_rgba,
+            uint32_t* dst_pixels)
+{
+    cgpt_ctx* d = f.dev;
+    const size_t n = (size_t)f.width * f.n_rows;
+    int rc;
+    DN_HIP(ctx, hipSetDevice(d->device));
+    if ((rc = EnsureFilterBuffers(ctx, d, n)) != CGPT_OK) return rc;
+    float4* out = d->d_denoise[0];
+    if (p.iterations == 0) {
+        hipLaunchKernelGGL(denoise_identity, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, d->stream, acc, out, d->d_denoise_pixels, n,
+                           (float)f.num_accumulated);
+        DN_HIP(ctx, hipGetLastError());
+    } else {
+        if ((rc = EnsureGuides(ctx, f, camera)) != CGPT_OK) return rc;
+        const uint32_t demodulate = (p.flags & CGPT_DENOISE_DEMODULATE_ALBEDO) ? 1u : 0u;
+        hipLaunchKernelGGL(denoise_prepare, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, d->stream, acc, d->d_guide_demod, d->d_denoise[0], n,
+                           (float)f.num_accumulated, demodulate);
+        DN_HIP(ctx, hipGetLastError());
+        const uint32_t tiles = ((f.width + kTile - 1u) / kTile) * ((f.n_rows + kTile - 1u) / kTile);
+        for (uint32_t it = 0; it < p.iterations; ++it) {
+            PassArgs a;
+            a.src = d->d_denoise[it & 1u];
+            a.dst = out = d->d_denoise[(it + 1u) & 1u];
+            a.pixels = d->d_denoise_pixels;
+            a.guides = d->d_guides; a.demod = d->d_guide_demod;
+            a.width = f.width; a.n_rows = f.n_rows; a.step = 1u << it; a.demodulate = demodulate;
+            const double sc = (double)p.sigma_color / (double)(1u << it);       // sigma_c 2^-i
+            a.inv_color = (float)(1.0 / (sc * sc));
+            a.inv_normal = (float)(1.0 / ((double)p.sigma_normal * p.sigma_normal));
+            a.inv_position = (float)(1.0 / ((double)p.sigma_position * p.sigma_position));
+            if (it + 1u == p.iterations) hipLaunchKernelGGL(atrous_pass<true>, dim3(tiles), dim3(256), 0, d->stream, a);
+            else hipLaunchKernelGGL(atrous_pass<false>, dim3(tiles), dim3(256), 0, d->stream, a);
+            DN_HIP(ctx, hipGetLastError());
+        }
+    }
+    if (dst_rgba) DN_HIP(ctx, hipMemcpyAsync(dst_rgba, out, n * sizeof(float4), hipMemcpyDeviceToHost, d->stream));
+    if (dst_pixels) DN_HIP(ctx, hipMemcpyAsync(dst_pixels, d->d_denoise_pixels, n * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    DN_HIP(ctx, hipStreamSynchronize(d->stream));
+    return CGPT_OK;
+}
+
+int CheckParams(cgpt_ctx* ctx, const cgpt_denoise_params& p)
+{
+    if (p.iterations > kMaxIterations) return CtxFail(ctx, CGPT_ERR_INVALID, "iterations %u outside [0, %u]", p.iterations, kMaxIterations);
+    if (p.flags & ~(uint32_t)CGPT_DENOISE_DEMODULATE_ALBEDO) return CtxFail(ctx, CGPT_ERR_INVALID, "unknown denoise flags 0x%x", p.flags);
+    const float s[3] = { p.sigma_color, p.sigma_normal, p.sigma_position };
+    for (float v : s)
+        if (!std::isfinite(v) || !(v > 0.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "sigmas must be finite and > 0, got %g, %g, %g", s[0], s[1], s[2]);
+    return CGPT_OK;
+}
+
+}  // namespace
+
+void DenoiseFree(cgpt_ctx* ctx)
+{
+    (void)hipFree(ctx->d_guides); (void)hipFree(ctx->d_guide_demod);
+    (void)hipFree(ctx->d_denoise[0]); (void)hipFree(ctx->d_denoise[1]); (void)hipFree(ctx->d_denoise_pixels);
+    ctx->d_guides = ctx->d_guide_demod = nullptr; ctx->guide_pixels = 0; ctx->guides_valid = false;
+    ctx->d_denoise[0] = ctx->d_denoise[1] = nullptr; ctx->d_denoise_pixels = nullptr; ctx->denoise_pixels = 0;
+}
+
+}  // namespace cgpt
+
+using namespace cgpt;
+
+extern "C" {
+
+int cgpt_read_guides(cgpt_ctx* ctx, const cgpt_camera* camera, float* dst, size_t n_floats)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    Frame f;
+    int rc = ResolveFrame(ctx, false, camera, f);
+    if (rc != CGPT_OK) return rc;
+    const size_t n = (size_t)f.width * f.n_rows;
+    if (!dst || n_floats != 12 * n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats (12 per pixel)", 12 * n);
+    cgpt_ctx* d = f.dev;
+    DN_HIP(ctx, hipSetDevice(d->device));
+    if ((rc = EnsureGuides(ctx, f, camera)) == CGPT_OK) {
+        hipError_t e = hipMemcpyAsync(dst, d->d_guides, n * 3 * sizeof(float4), hipMemcpyDeviceToHost, d->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+        if (e != hipSuccess) rc = CtxFail(ctx, CGPT_ERR_HIP, "cgpt_read_guides: %s", hipGetErrorString(e));
+    }
+    if (rc != CGPT_OK) d->guides_valid = false;
+    return rc;
+}
+
+int cgpt_denoise(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_params* params, float* dst_rgba, size_t n_floats,
+                 uint32_t* dst_pixels, size_t n_pixels)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    Frame f;
+    int rc = ResolveFrame(ctx, true, camera, f);
+    if (rc != CGPT_OK) return rc;
+    const cgpt_denoise_params p = params ? *params : kDefaults;
+    if ((rc = CheckParams(ctx, p)) != CGPT_OK) return rc;
+    const size_t n = (size_t)f.width * f.n_rows;
+    if (!dst_rgba && !dst_pixels) return CtxFail(ctx, CGPT_ERR_INVALID, "both outputs are null");
+    if (dst_rgba && n_floats != 4 * n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats (4 per pixel)", 4 * n);
+    if (dst_pixels && n_pixels != n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu pixels", n);
+    const float4* acc = ctx->d_accumulator;
+    if (ctx->group && (rc = GroupGatherUncounted(ctx, &acc)) != CGPT_OK) return rc;
+    rc = Denoise(ctx, f, camera, p, acc, dst_rgba, dst_pixels);
+    if (rc != CGPT_OK) f.dev->guides_valid = false;
+    return rc;
+}
+
+}  // extern "C"

@@ -454,6 +454,28 @@ int GroupReadPixels(cgpt_ctx* ctx, uint32_t* dst, size_t n_pixels)
     return CGPT_OK;
 }
 
+void GroupFrameInfo(cgpt_ctx* ctx, uint32_t* width, uint32_t* height, uint32_t* num_accumulated, uint32_t* last_debug_mode)
+{
+    const DeviceGroup* g = ctx->group;
+    *width = g->width; *height = g->height; *num_accumulated = g->num_accumulated; *last_debug_mode = g->last_debug_mode;
+}
+
+// cgpt_denoise reads the frame without being a read-back: cgpt_stats (gathers, gather_ms) does not grow, and a frame that was not
+// gathered before counts as not gathered afterwards, so the next read-back gathers and counts as it would have without this call
+int GroupGatherUncounted(cgpt_ctx* ctx, const float4** frame)
+{
+    DeviceGroup* g = ctx->group;
+    const bool gathered = g->gathered, pixels_valid = g->pixels_valid;
+    const uint32_t gathers = g->gathers;
+    const double gather_ms = g->gather_ms;
+    const int rc = Gather(ctx, false);
+    g->gathers = gathers; g->gather_ms = gather_ms;
+    if (rc != CGPT_OK) { g->gathered = false; g->pixels_valid = false; return rc; }
+    g->gathered = gathered; g->pixels_valid = gathered && pixels_valid;
+    *frame = g->d_full;
+    return CGPT_OK;
+}
+
 int GroupWriteAccumulator(cgpt_ctx* ctx, const cgpt_render_params* p, const float* src, size_t n_floats, uint32_t num_accumulated)
 {
     DeviceGroup* g = ctx->group;

@@ -150,6 +150,27 @@ class Renderer:
         self._check(self.L.cgpt_read_pixels(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size))
         return out
 
+    def guides(self, camera: Optional[N.Camera] = None) -> np.ndarray:
+        """The denoiser's first-hit guides of this context's band (cgpt_read_guides): (rows, width, 12) float32 per pixel
+        {x.xyz, t, n.xyz, bits(obj), albedo.xyz, bits(mat_index)}; a miss is zeros, t = 1e34 and obj = mat = 0xFFFFFFFF.
+        camera: the one the accumulator was rendered with (default: the uploaded scene's)."""
+        cam = camera if camera is not None else self.scene.camera()
+        out = np.empty((self.n_rows, self.width, 12), np.float32)
+        self._check(self.L.cgpt_read_guides(self._ctx, C.byref(cam), out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
+    def denoise(self, iterations: int = 5, sigma_color: float = 4.0, sigma_normal: float = 0.2, sigma_position: float = 0.3,
+                demodulate: bool = True, camera: Optional[N.Camera] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """The accumulated image through the edge-avoiding a-trous filter (cgpt_denoise): (rows, width, 4) float32 radiance {rgb, 1}
+        and (rows, width) uint32 pixels packed as data.pixels is.  The accumulator, pixels and statistics are left as they are."""
+        cam = camera if camera is not None else self.scene.camera()
+        p = N.DenoiseParams(iterations, N.DENOISE_DEMODULATE_ALBEDO if demodulate else 0, sigma_color, sigma_normal, sigma_position)
+        rgba = np.empty((self.n_rows, self.width, 4), np.float32)
+        px = np.empty((self.n_rows, self.width), np.uint32)
+        self._check(self.L.cgpt_denoise(self._ctx, C.byref(cam), C.byref(p), rgba.ctypes.data_as(C.POINTER(C.c_float)), rgba.size,
+                                        px.ctypes.data_as(C.POINTER(C.c_uint32)), px.size))
+        return rgba, px
+
     def accumulator_device_ptr(self) -> Tuple[int, int]:
         ptr = C.c_void_p(); nbytes = C.c_size_t()
         self._check(self.L.cgpt_accumulator_device_ptr(self._ctx, C.byref(ptr), C.byref(nbytes)))

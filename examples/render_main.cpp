@@ -4,12 +4,14 @@
 //
 //   g++ -std=c++17 -Iinclude -Icpugpupathtracing_amd/csrc/host examples/render_main.cpp
 //       -Lcpugpupathtracing_amd/lib -lcpugpupt -Wl,-rpath,$PWD/cpugpupathtracing_amd/lib -o render_main   (one command line)
-//   ./render_main [--gpus N [--collective]] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
+//   ./render_main [--gpus N [--collective]] [--denoise] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
 // --gpus N: ONE context over the first N GPUs of the node (cgpt_ctx_create with n_devices = N): every frame is spread over them in
 // interleaved row bands and the read-back gathers the float4 bands with one RCCL exchange over xGMI; the loop below does not
 // change.  --collective: take that code path with N = 1 too (what a one-GPU box can test).
 // preview_every > 0 writes preview_NNNN.ppm every that many samples: the progressive display the reference gets from
 // presenting data.pixels after every Render() (ref: Main.cpp:935-936, Source/DX12.cpp:277-322).
+// --denoise: also write the image through cgpt_denoise (default parameters) next to each preview (preview_NNNN_denoised.ppm) and at the
+// end (render_denoised.ppm) -- what a viewer with a "Denoise" toggle presents; the accumulator and the raw dumps are not affected.
 // move_at > 0 scripts the input half of Update(dt) (ref: Main.cpp:277-297, Camera::Update :104-131): after that many samples the
 // camera is translated by (right, up, forward) as the A/D, Space/Shift, W/S keys would, the view changes, and the accumulator
 // is reset (ref: ResetAccumulator, Main.cpp:238-243) before the remaining samples are rendered from the new position.
@@ -35,10 +37,11 @@ using namespace cgpt;
 
 int main(int argc, char** argv)
 {
-    int n_gpus = 1; uint32_t ctx_flags = 0;
+    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false;
     while (argc > 1 && std::string(argv[1]).rfind("--", 0) == 0) {
         if (std::string(argv[1]) == "--gpus" && argc > 2) { n_gpus = atoi(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--collective") { ctx_flags |= CGPT_CTX_FORCE_COLLECTIVE; argv += 1; argc -= 1; }
+        else if (std::string(argv[1]) == "--denoise") { denoise = true; argv += 1; argc -= 1; }
         else { fprintf(stderr, "unknown option %s\n", argv[1]); return 2; }
     }
     std::string model = argc > 1 && std::string(argv[1]).find(".gltf") != std::string::npos ? argv[1] : "";
@@ -65,7 +68,7 @@ int main(int argc, char** argv)
     const cgpt_settings settings = scene.AbiSettings();
     uint32_t num_accumulated = 0;                                        // data.num_accumulated
     const auto t0 = std::chrono::steady_clock::now();
-    std::vector<uint32_t> pixels((size_t)W * H);
+    std::vector<uint32_t> pixels((size_t)W * H), denoised(denoise ? (size_t)W * H : 0);
     const uint32_t chunk = preview_every ? preview_every : 16;           // Render() calls folded into one launch
     bool moved = false;
     for (uint32_t frame = 0; frame < spp; frame += chunk) {              // the frame loop
@@ -86,6 +89,11 @@ int main(int argc, char** argv)
             CHECK(cgpt_read_pixels(ctx, pixels.data(), pixels.size()));
             char name[64]; snprintf(name, sizeof(name), "preview_%04u.ppm", num_accumulated);
             std::string err; WritePPM(name, pixels.data(), W, H, err);
+            if (denoise) {                                               // the "Denoise" toggle: the filtered image instead of data.pixels
+                CHECK(cgpt_denoise(ctx, &scene.camera.Abi(), nullptr, nullptr, 0, denoised.data(), denoised.size()));
+                snprintf(name, sizeof(name), "preview_%04u_denoised.ppm", num_accumulated);
+                WritePPM(name, denoised.data(), W, H, err);
+            }
         }
     }
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -101,6 +109,10 @@ int main(int argc, char** argv)
     WritePPM("render.ppm", pixels.data(), W, H, err);
     WritePFM("render.pfm", acc.data(), num_accumulated, W, H, err);
     WriteAccumulator("render.acc", acc.data(), num_accumulated, W, H, err);
+    if (denoise) {
+        CHECK(cgpt_denoise(ctx, &scene.camera.Abi(), nullptr, nullptr, 0, denoised.data(), denoised.size()));
+        WritePPM("render_denoised.ppm", denoised.data(), W, H, err);
+    }
     cgpt_ctx_destroy(ctx);                                               // ThreadPool::Exit
     return 0;
 }

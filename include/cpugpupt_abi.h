@@ -25,7 +25,8 @@ extern "C" {
 #endif
 
 #define CGPT_ABI_VERSION 2u   /* 2: cgpt_stats grew (gather_ms .. last_kernel), CGPT_KERNEL_* / CGPT_CTX_* values added since 1;
-                                 CGPT_OBJECT_TRIANGLE is a new enum value only, no layout changed */
+                                 CGPT_OBJECT_TRIANGLE is a new enum value only, no layout changed; the denoiser added new symbols
+                                 (cgpt_read_guides, cgpt_denoise) and a new struct (cgpt_denoise_params) only */
 
 enum cgpt_status {
     CGPT_OK = 0,
@@ -256,6 +257,33 @@ int cgpt_bvh_build_ex(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t n_
                       cgpt_bvh_node* nodes_out, uint32_t* n_nodes_out, uint32_t* tri_indices_out, uint32_t* max_depth_out, float* total_area_out);
 
 int cgpt_synchronize(cgpt_ctx* ctx);
+
+/* ---- denoising (reference README, "Planned"): an edge-avoiding a-trous filter guided by first-hit buffers ----
+ * The reference does not jitter primary rays (every sample of a pixel has the same first hit), so the guides -- position, normal and
+ * albedo of each pixel's primary hit, computed by the render paths' own device functions -- take one primary trace per camera; the
+ * context keeps them until the camera, the band or the scene (upload, material update, refit, primitive update) changes.
+ * `camera` is the one the accumulator was rendered with (so the calls also work after cgpt_write_accumulator on a fresh context).
+ * Both calls run on the context's stream and block; they leave the accumulator, data.pixels, num_accumulated and cgpt_stats alone.
+ * Bands: a one-device context works on its contiguous band (the filter sees only its rows; an interleaved band is CGPT_ERR_INVALID);
+ * a multi-device context works on the full frame on device_ids[0], after the gather cgpt_read_accumulator does.
+ * Refusals (checked before any device work; a refused call changes nothing): no scene CGPT_ERR_NO_SCENE; no band yet, the last render
+ * a debug view, num_accumulated == 0 (denoise only), iterations > 10, a sigma not finite and > 0, unknown flag bits, wrong sizes or
+ * both outputs NULL: CGPT_ERR_INVALID. */
+enum cgpt_denoise_flags { CGPT_DENOISE_DEMODULATE_ALBEDO = 1u };   /* filter radiance / albedo, multiply the albedo back afterwards */
+typedef struct cgpt_denoise_params {
+    uint32_t iterations;   /* 0..10 passes of step 1, 2, 4, ...; 0 returns accumulator / num_accumulated unchanged */
+    uint32_t flags;        /* cgpt_denoise_flags */
+    float sigma_color, sigma_normal, sigma_position;
+} cgpt_denoise_params;
+/* NULL params = the defaults: iterations 5, CGPT_DENOISE_DEMODULATE_ALBEDO, sigma_color 4.0, sigma_normal 0.2, sigma_position 0.3
+ * (tuned on the reference layout at 4 spp) */
+/* 12 floats per pixel of the band, row-major: {x.xyz, t | n.xyz, bits(obj) | albedo.xyz, bits(mat_index)} of the primary hit;
+ * a miss is x = n = albedo = 0, t = 1e34, obj = mat_index = 0xFFFFFFFF */
+int cgpt_read_guides(cgpt_ctx* ctx, const cgpt_camera* camera, float* dst, size_t n_floats);
+/* the filtered radiance of the band as float4 {rgb, 1} (dst_rgba, 4 floats per pixel) and/or packed as data.pixels is (dst_pixels);
+ * either output may be NULL, not both */
+int cgpt_denoise(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_params* params, float* dst_rgba, size_t n_floats,
+                 uint32_t* dst_pixels, size_t n_pixels);
 
 /* ---- tuning and measurement aids (no reference counterpart) ------------------------------------------------------- */
 /* Overrides one tuning knob of the wavefront pipeline for this context (the CGPT_WF_* environment variables set the same
