@@ -17,19 +17,19 @@
 #include "device_scene.h"
 
 namespace cgpt {
-hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, hipStream_t stream);                    // path_kernels.hip
+hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, bool glossy, hipStream_t stream);       // path_kernels.hip
 hipError_t LaunchIntersectRays(const DevScene& sc, const float* origins, const float* dirs, const float* tmax, uint32_t n, float* out_t,
                                uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, DevCounters* counters, hipStream_t stream);
-int LaunchWavefront(struct ::cgpt_ctx* ctx, const DevRenderArgs& args, bool count);                       // wavefront_kernels.hip
+int LaunchWavefront(struct ::cgpt_ctx* ctx, const DevRenderArgs& args, bool count, bool glossy);          // wavefront_kernels.hip
 void WavefrontFree(void* state);
 void WavefrontCollectTiming(void* state, double* trace_ms, uint32_t* trace_launches, double* round0_ms, uint32_t* round0_launches);
 int WavefrontSetTuning(struct ::cgpt_ctx* ctx, const char* name, uint32_t value);
 uint32_t WavefrontTraceWavesPerSimd(void* state);
-int LaunchPersistent(struct ::cgpt_ctx* ctx, const DevRenderArgs& args, bool count);                          // persistent_kernel.hip
+int LaunchPersistent(struct ::cgpt_ctx* ctx, const DevRenderArgs& args, bool count, bool glossy);             // persistent_kernel.hip
 void PersistentFree(void* state);
-void PersistentCollectTiming(void* state, double* ms, uint32_t* launches, uint32_t* waves_per_simd);
+void PersistentCollectTiming(void* state, bool glossy, double* ms, uint32_t* launches, uint32_t* waves_per_simd);
 int PersistentSetTuning(struct ::cgpt_ctx* ctx, const char* name, uint32_t value, bool* known);
-uint32_t MegakernelWavesPerSimd(const DevRenderArgs& args);                                                   // path_kernels.hip
+uint32_t MegakernelWavesPerSimd(const DevRenderArgs& args, bool glossy);                                      // path_kernels.hip
 }  // namespace cgpt
 
 using namespace cgpt;
@@ -109,6 +109,7 @@ void FreeScene(cgpt_ctx* ctx)
     (void)hipFree(ctx->d_refit_levels); (void)hipFree(ctx->d_refit_staging);
     ctx->d_refit_levels = nullptr; ctx->d_refit_staging = nullptr; ctx->refit_staging_tris = 0;
     ctx->h_objects.clear(); ctx->refit_objects.clear(); ctx->record_perm.clear();
+    ctx->h_roughness.clear(); ctx->h_materials.clear(); ctx->glossy = false;
     ctx->has_scene = false;
 }
 
@@ -122,12 +123,13 @@ void FreeFramebuffer(cgpt_ctx* ctx)
 float4 F4(float x, float y, float z, float w) { float4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
 float AsFloat(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 
-void PackMaterial(const cgpt_material& m, float4 out[4])
+// roughness: the specular lobe's (cgpt_scene_update_roughness); the record holds alpha = roughness^2, formed here once
+void PackMaterial(const cgpt_material& m, float roughness, float4 out[4])
 {
     out[0] = F4(m.albedo[0], m.albedo[1], m.albedo[2], m.specular);
     out[1] = F4(m.refractivity, m.absorption[0], m.absorption[1], m.absorption[2]);
     out[2] = F4(m.ior, m.emissive[0], m.emissive[1], m.emissive[2]);
-    out[3] = F4(m.intensity, AsFloat(m.is_light ? 1u : 0u), 0.0f, 0.0f);
+    out[3] = F4(m.intensity, AsFloat(m.is_light ? 1u : 0u), roughness * roughness, 0.0f);
 }
 
 // leaf-ordered triangle record (device_scene.h: tri_leaf) and original-order record (tri_orig) of one triangle
@@ -326,7 +328,7 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
     if (stack_depth > 64) return Fail(ctx, CGPT_ERR_UNSUPPORTED, "BVH depth %u exceeds the traversal stack of 64 (ref: BVH.cpp:66)", max_tree_depth);
 
     mats.resize(4 * (size_t)sd.n_materials);
-    for (uint32_t i = 0; i < sd.n_materials; ++i) PackMaterial(sd.materials[i], mats.data() + 4 * (size_t)i);
+    for (uint32_t i = 0; i < sd.n_materials; ++i) PackMaterial(sd.materials[i], 0.0f, mats.data() + 4 * (size_t)i);   // an upload resets roughness
     std::vector<uint32_t> lights(sd.light_indices, sd.light_indices + sd.n_lights);
 
     // ---- record order (device_scene.h: "record order") ----
@@ -403,6 +405,7 @@ int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
     if ((rc = UploadArray(ctx, &ctx->d_lights, lights)) != CGPT_OK) return rc;
     if ((rc = UploadArray(ctx, &ctx->d_refit_levels, levels)) != CGPT_OK) return rc;
     ctx->h_objects.swap(objs); ctx->refit_objects.swap(refit); ctx->record_perm.swap(perm);
+    ctx->h_roughness.assign(sd.n_materials, 0.0f); ctx->h_materials.swap(mats); ctx->glossy = false;
 
     ctx->scene.node_pairs = ctx->d_node_pairs; ctx->scene.tri_leaf = ctx->d_tri_leaf; ctx->scene.tri_orig = ctx->d_tri_orig; ctx->scene.tri_normal = ctx->d_tri_normal;
     ctx->scene.materials = ctx->d_materials; ctx->scene.objects = ctx->d_objects; ctx->scene.obj_trace = ctx->d_obj_trace; ctx->scene.lights = ctx->d_lights;
@@ -545,11 +548,40 @@ int cgpt_scene_update_materials(cgpt_ctx* ctx, const cgpt_material* materials, u
     if (!materials || n_materials != ctx->n_materials) return Fail(ctx, CGPT_ERR_INVALID, "expected %u materials", ctx->n_materials);
     std::vector<float4> mats;
     try { mats.resize(4 * (size_t)n_materials); } catch (const std::exception& e) { return Fail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
-    for (uint32_t i = 0; i < n_materials; ++i) PackMaterial(materials[i], mats.data() + 4 * (size_t)i);
+    for (uint32_t i = 0; i < n_materials; ++i) PackMaterial(materials[i], ctx->h_roughness[i], mats.data() + 4 * (size_t)i);   // roughness is kept
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->scene_generation++;
     HIP_TRY(ctx, hipMemcpy(ctx->d_materials, mats.data(), mats.size() * sizeof(float4), hipMemcpyHostToDevice));
+    ctx->h_materials.swap(mats);
+    return CGPT_OK;
+}
+
+int cgpt_scene_update_roughness(cgpt_ctx* ctx, const float* roughness, uint32_t n_materials)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) GROUP_CALL(ctx, GroupUpdateRoughness(ctx, roughness, n_materials));
+    if (!ctx->has_scene) return Fail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!roughness || n_materials != ctx->n_materials) return Fail(ctx, CGPT_ERR_INVALID, "expected %u roughness values", ctx->n_materials);
+    bool glossy = false;
+    for (uint32_t i = 0; i < n_materials; ++i) {
+        if (!(roughness[i] >= 0.0f && roughness[i] <= 1.0f)) return Fail(ctx, CGPT_ERR_INVALID, "material %u: roughness %g outside [0, 1]", i, (double)roughness[i]);
+        glossy = glossy || roughness[i] > 0.0f;
+    }
+    std::vector<float4> mats;
+    try { mats = ctx->h_materials; } catch (const std::exception& e) { return Fail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
+    for (uint32_t i = 0; i < n_materials; ++i) mats[4 * (size_t)i + 3].z = roughness[i] * roughness[i];   // PackMaterial's alpha
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // first hits and albedo do not depend on roughness: the denoiser's guides stay valid (scene_generation is left as it is)
+    const hipError_t e = hipMemcpy(ctx->d_materials, mats.data(), mats.size() * sizeof(float4), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {                                                     // the records may be half written: drop the scene (refit.hip: SceneLost)
+        ctx->has_scene = false;
+        return Fail(ctx, CGPT_ERR_HIP, "hipMemcpy of the material records failed: %s (the device scene is dropped; upload it again)", hipGetErrorString(e));
+    }
+    ctx->h_materials.swap(mats);
+    ctx->h_roughness.assign(roughness, roughness + n_materials);
+    ctx->glossy = glossy;
     return CGPT_OK;
 }
 
@@ -638,21 +670,21 @@ int RenderEnqueue(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings*
 
     if (kernel == CGPT_KERNEL_MEGAKERNEL) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-        HIP_TRY(ctx, LaunchMegakernel(args, count, ctx->stream));
+        HIP_TRY(ctx, LaunchMegakernel(args, count, ctx->glossy, ctx->stream));
         ctx->kernel_launches += 1;
     } else if (kernel == CGPT_KERNEL_WAVEFRONT) {
-        rc = LaunchWavefront(ctx, args, count);
+        rc = LaunchWavefront(ctx, args, count, ctx->glossy);
         if (rc < 0) return ctx->error.empty() ? Fail(ctx, CGPT_ERR_HIP, "wavefront launch failed") : CGPT_ERR_HIP;
         ctx->kernel_launches += (uint32_t)rc;
     } else if (kernel == CGPT_KERNEL_PERSISTENT) {
-        rc = LaunchPersistent(ctx, args, count);
+        rc = LaunchPersistent(ctx, args, count, ctx->glossy);
         if (rc < 0) return ctx->error.empty() ? Fail(ctx, CGPT_ERR_HIP, "persistent kernel launch failed") : CGPT_ERR_HIP;
         ctx->kernel_launches += (uint32_t)rc;
     } else {
         return Fail(ctx, CGPT_ERR_INVALID, "unknown kernel %u", p->kernel);
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
-    ctx->pending_kernel = kernel; ctx->pending_args = args; ctx->pending_num_accumulated = p->first_sample + p->n_samples;
+    ctx->pending_kernel = kernel; ctx->pending_args = args; ctx->pending_num_accumulated = p->first_sample + p->n_samples; ctx->pending_glossy = ctx->glossy;
     ctx->last_debug_mode = settings->debug_render_mode;
     ctx->last_kernel = kernel;
     return CGPT_OK;
@@ -669,10 +701,10 @@ int RenderFinish(cgpt_ctx* ctx)
     float ms = 0.0f;
     HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
     ctx->kernel_ms += ms;
-    if (kernel == CGPT_KERNEL_MEGAKERNEL) { ctx->dominant_ms += ms; ctx->dominant_launches += 1; ctx->dominant_waves_per_simd = MegakernelWavesPerSimd(args); }
+    if (kernel == CGPT_KERNEL_MEGAKERNEL) { ctx->dominant_ms += ms; ctx->dominant_launches += 1; ctx->dominant_waves_per_simd = MegakernelWavesPerSimd(args, ctx->pending_glossy); }
     else if (kernel == CGPT_KERNEL_PERSISTENT) {
         double tms = 0.0; uint32_t tl = 0, w = 0;
-        PersistentCollectTiming(ctx->persistent_state, &tms, &tl, &w);
+        PersistentCollectTiming(ctx->persistent_state, ctx->pending_glossy, &tms, &tl, &w);
         ctx->dominant_ms += tms; ctx->dominant_launches += tl; ctx->dominant_waves_per_simd = w;
     } else {
         ctx->dominant_waves_per_simd = WavefrontTraceWavesPerSimd(ctx->wavefront_state);

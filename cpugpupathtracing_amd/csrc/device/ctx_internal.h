@@ -41,6 +41,12 @@ struct cgpt_ctx {
     cgpt::DevScene scene{};
     uint32_t n_materials = 0;
     bool has_scene = false;
+    // the specular lobe's roughness per material (cgpt_scene_update_roughness; 0 after every upload), the packed material records as they
+    // are on the device (a roughness or material update re-packs them), and whether any roughness is > 0: the renders then run the GLOSSY
+    // instantiations of the render kernels
+    std::vector<float> h_roughness;
+    std::vector<float4> h_materials;
+    bool glossy = false;
 
     // in-place edits of the uploaded scene (refit.hip): host copies of the objects, each mesh's child-pair records grouped by
     // depth, and where the renumbering put every record
@@ -74,6 +80,7 @@ struct cgpt_ctx {
     // a render that has been enqueued and not yet finished (RenderEnqueue / RenderFinish)
     uint32_t pending_kernel = 0;
     uint32_t pending_num_accumulated = 0;
+    bool pending_glossy = false;
     cgpt::DevRenderArgs pending_args{};
     uint32_t last_debug_mode = 0;
     uint32_t last_kernel = 0;                     // cgpt_kernel the last render ran (AUTO resolved)
@@ -119,6 +126,7 @@ int GroupCreate(const int* device_ids, int n_devices, uint32_t flags, cgpt_ctx**
 void GroupDestroy(cgpt_ctx* ctx);
 int GroupSceneUpload(cgpt_ctx* ctx, const cgpt_scene_desc* scene);
 int GroupUpdateMaterials(cgpt_ctx* ctx, const cgpt_material* materials, uint32_t n);
+int GroupUpdateRoughness(cgpt_ctx* ctx, const float* roughness, uint32_t n);
 int GroupRefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris, float* total_area_out);
 int GroupUpdatePrimitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_object* obj);
 int GroupRender(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p);

@@ -384,6 +384,11 @@ int GroupUpdatePrimitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_object* o
     return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_update_primitive(m, obj_index, obj); });
 }
 
+int GroupUpdateRoughness(cgpt_ctx* ctx, const float* roughness, uint32_t n)
+{
+    return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_update_roughness(m, roughness, n); });
+}
+
 int GroupRender(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p)
 {
     DeviceGroup* g = ctx->group;

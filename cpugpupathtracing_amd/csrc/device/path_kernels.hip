@@ -27,7 +27,8 @@ extern __shared__ uint32_t lds_stack[];
 // Block shape: 256 threads = a 16x16-pixel tile (the reference's job size, ref: Main.cpp:705-711), or -- one-sample calls -- 64 threads =
 // one 8x8 tile per single-wave block: the wave's slot and its LDS are free the moment its own longest path ends instead of its block's,
 // and the dispatcher places single waves (1080p, one sample: 1.71 -> 1.68 ms, profiles/r03/one_sample.md).
-template <bool COUNT, bool BRUTE>
+// GLOSSY: the scene has a rough specular material (shade_device.hpp: ggx_sample); the mirror-only scenes keep the code without it.
+template <bool COUNT, bool BRUTE, bool GLOSSY>
 __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
 {
     const DevScene& sc = args.scene;
@@ -86,7 +87,7 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
             if (BRUTE && use_brute) {
                 ray.t = cur.t; ray.obj = cur.obj; ray.tri = cur.tri; ray.bvh_depth = cur.bvh_depth;
                 BruteLevel lv; V3 leaf = mk(0.0f);
-                finalize = brute_bounce<COUNT>(sc, st, ray, ps.rng, ps.depth, lv, leaf, cnt) == kBruteLeaf;
+                finalize = brute_bounce<COUNT, GLOSSY>(sc, st, ray, ps.rng, ps.depth, lv, leaf, cnt) == kBruteLeaf;
                 if (!finalize) {
                     levels[n_levels++] = lv;
                     ps.depth++;
@@ -103,7 +104,7 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
                 finalize = dead;
             } else {
                 ray.t = cur.t; ray.obj = cur.obj; ray.tri = cur.tri; ray.bvh_depth = cur.bvh_depth;
-                const uint32_t flags = shade_bounce<COUNT>(sc, st, ray, ps, sray, pending, cnt);
+                const uint32_t flags = shade_bounce<COUNT, GLOSSY>(sc, st, ray, ps, sray, pending, cnt);
                 dead = (flags & kBounceTerminate) != 0;
                 shadow_kind = (flags & kBounceShadow) != 0;
                 finalize = dead && !shadow_kind;
@@ -148,7 +149,13 @@ static uint32_t MegakernelBlockThreads(const DevRenderArgs& args)
     return args.n_samples == 1u ? 64u : 256u;
 }
 
-hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, hipStream_t stream)
+// every instantiation, [COUNT][BRUTE][GLOSSY]
+static decltype(&megakernel<false, false, false>) const kMegakernels[2][2][2] = {
+    { { megakernel<false, false, false>, megakernel<false, false, true> }, { megakernel<false, true, false>, megakernel<false, true, true> } },
+    { { megakernel<true, false, false>, megakernel<true, false, true> }, { megakernel<true, true, false>, megakernel<true, true, true> } },
+};
+
+hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, bool glossy, hipStream_t stream)
 {
     const bool brute = args.settings.render_mode != 2u;
     const uint32_t bt = MegakernelBlockThreads(args);
@@ -156,23 +163,16 @@ hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, hipStream_t s
     const uint32_t tiles_x = (args.width + edge - 1u) / edge, tiles_y = (args.n_rows + edge - 1u) / edge;
     const dim3 grid(tiles_x * tiles_y), block(bt);
     const size_t lds = (size_t)args.scene.stack_depth * bt * sizeof(uint32_t);
-    if (brute) {
-        if (count) hipLaunchKernelGGL((megakernel<true, true>), grid, block, lds, stream, args);
-        else hipLaunchKernelGGL((megakernel<false, true>), grid, block, lds, stream, args);
-    } else {
-        if (count) hipLaunchKernelGGL((megakernel<true, false>), grid, block, lds, stream, args);
-        else hipLaunchKernelGGL((megakernel<false, false>), grid, block, lds, stream, args);
-    }
+    hipLaunchKernelGGL(kMegakernels[count][brute][glossy], grid, block, lds, stream, args);
     return hipGetLastError();
 }
 
-uint32_t MegakernelWavesPerSimd(const DevRenderArgs& args)
+uint32_t MegakernelWavesPerSimd(const DevRenderArgs& args, bool glossy)
 {
     int b = 0;
     const uint32_t bt = MegakernelBlockThreads(args);
     const size_t lds = (size_t)args.scene.stack_depth * bt * sizeof(uint32_t);
-    const hipError_t e = args.settings.render_mode != 2u ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (megakernel<false, true>), (int)bt, lds)
-                                                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (megakernel<false, false>), (int)bt, lds);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kMegakernels[0][args.settings.render_mode != 2u][glossy], (int)bt, lds);
     return e == hipSuccess && b > 0 ? std::max(1u, (uint32_t)b * bt / 256u) : 1u;    // blocks per CU -> waves per SIMD (4 SIMDs)
 }
 

@@ -64,7 +64,8 @@ enum : uint32_t {                      // per-lane path flags
 // Main.cpp:702,825-942), which are mostly drain: once nothing is left to fetch, a wave with few busy lanes runs their rays in the lean
 // per-lane loop (trace_steps.hpp: lean_traverse) instead of voted steps, because the call ends when its longest chain does (1080p, one
 // sample: 2.47 -> 2.21 ms).  Kept out of the throughput instantiations, which it costs registers and SGPR spills (profiles/r03/one_sample.md).
-template <bool COUNT, bool BRUTE, bool TAIL>
+// GLOSSY: the scene has a rough specular material (shade_device.hpp: ggx_sample); the mirror-only scenes keep the code without it.
+template <bool COUNT, bool BRUTE, bool TAIL, bool GLOSSY>
 __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderArgs args, const PtDev pt, uint32_t batch_first, const TraceTune tune)
 {
     const DevScene& sc = args.scene;
@@ -121,7 +122,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
             // the recorded chain over the leaf's radiance, innermost level first
             uint32_t depth = pf & kPfDepthMask;
             BruteLevel lv; V3 leaf = mk(0.0f);
-            bool fold = brute_bounce<COUNT>(sc, st, ray, rng, depth, lv, leaf, cnt) == kBruteLeaf;
+            bool fold = brute_bounce<COUNT, GLOSSY>(sc, st, ray, rng, depth, lv, leaf, cnt) == kBruteLeaf;
             if (!fold) {
                 float4* rec = pt.brute + ((size_t)depth * grid_threads + tid) * 2u;
                 float4 r0, r1;
@@ -151,7 +152,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
             ps.throughput = tp; ps.energy = en; ps.rng = rng; ps.depth = pf & kPfDepthMask; ps.is_specular = (pf & kPfSpecular) != 0u;
             Ray shadow = ray;
             V3 pend = mk(0.0f);
-            const uint32_t flags = shade_bounce<COUNT>(sc, st, ray, ps, shadow, pend, cnt);
+            const uint32_t flags = shade_bounce<COUNT, GLOSSY>(sc, st, ray, ps, shadow, pend, cnt);
             tp = ps.throughput; en = ps.energy; rng = ps.rng;
             pf = (ps.depth & kPfDepthMask) | (ps.is_specular ? kPfSpecular : 0u);
             const bool dead = (flags & kBounceTerminate) != 0u;
@@ -261,10 +262,12 @@ struct PtTuning {
     uint32_t fine_rounds = 2;     // fine fetches (one id per idle lane) once fewer than this many ids per lane of the grid are left
 };
 
-// every instantiation, [COUNT][BRUTE][TAIL]
-static decltype(&pt_persistent<false, false, false>) const kPtKernels[2][2][2] = {
-    { { pt_persistent<false, false, false>, pt_persistent<false, false, true> }, { pt_persistent<false, true, false>, pt_persistent<false, true, true> } },
-    { { pt_persistent<true, false, false>, pt_persistent<true, false, true> }, { pt_persistent<true, true, false>, pt_persistent<true, true, true> } },
+// every instantiation, [GLOSSY][COUNT][BRUTE][TAIL]
+static decltype(&pt_persistent<false, false, false, false>) const kPtKernels[2][2][2][2] = {
+    { { { pt_persistent<false, false, false, false>, pt_persistent<false, false, true, false> }, { pt_persistent<false, true, false, false>, pt_persistent<false, true, true, false> } },
+      { { pt_persistent<true, false, false, false>, pt_persistent<true, false, true, false> }, { pt_persistent<true, true, false, false>, pt_persistent<true, true, true, false> } } },
+    { { { pt_persistent<false, false, false, true>, pt_persistent<false, false, true, true> }, { pt_persistent<false, true, false, true>, pt_persistent<false, true, true, true> } },
+      { { pt_persistent<true, false, false, true>, pt_persistent<true, false, true, true> }, { pt_persistent<true, true, false, true>, pt_persistent<true, true, true, true> } } },
 };
 
 struct PtHost {
@@ -277,7 +280,7 @@ struct PtHost {
     hipEvent_t begin = nullptr, acc_done[2] = { nullptr, nullptr };
     EventPairs ev;
     uint32_t n_cus = 0;
-    uint32_t blocks_per_cu[2][2][2] = {};    // [COUNT][BRUTE][TAIL]
+    uint32_t blocks_per_cu[2][2][2][2] = {};  // [GLOSSY][COUNT][BRUTE][TAIL]
     size_t occupancy_lds = 0;
 };
 
@@ -337,16 +340,16 @@ void PersistentFree(void* state)
     delete h;
 }
 
-void PersistentCollectTiming(void* state, double* ms, uint32_t* launches, uint32_t* waves_per_simd)
+void PersistentCollectTiming(void* state, bool glossy, double* ms, uint32_t* launches, uint32_t* waves_per_simd)
 {
     *ms = 0.0; *launches = 0; *waves_per_simd = 0;
     if (!state) return;
     PtHost* h = static_cast<PtHost*>(state);
     ForEachPair(h->ev, [&](uint32_t, float t) { *ms += t; *launches += 1; });
-    *waves_per_simd = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[0][0][0]) * (kTraceBlock / 256u);
+    *waves_per_simd = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[glossy][0][0][0]) * (kTraceBlock / 256u);
 }
 
-int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
+int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, bool glossy)
 {
     hipStream_t stream = CtxStream(ctx);
     PtHost* h = PtGetHost(ctx);
@@ -357,11 +360,11 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
     const uint32_t top_records = std::min(h->tune.top_records, args_in.scene.n_top_records);
     const size_t lds = trace_lds_bytes(top_records);
     if (h->occupancy_lds != lds) {
-        LAUNCH_TRY(QueryOccupancy(&kPtKernels[0][0][0], &h->blocks_per_cu[0][0][0], 8, kTraceBlock, lds));
+        LAUNCH_TRY(QueryOccupancy(&kPtKernels[0][0][0][0], &h->blocks_per_cu[0][0][0][0], 16, kTraceBlock, lds));
         h->occupancy_lds = lds;
     }
     const bool tail = args_in.n_samples <= h->tune.tail_samples;              // a small call: mostly drain
-    const uint32_t blocks_per_cu = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[count][brute][tail]);
+    const uint32_t blocks_per_cu = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[glossy][count][brute][tail]);
     // the resident capacity of the chip, or fewer blocks when there are fewer than 64 paths per wave (a small call ends sooner when
     // its paths are spread thin than when the tail of a launch waits for 4 096 waves to find out that there is nothing to do)
     const uint32_t n_tiles = ((args_in.width + 7u) / 8u) * ((args_in.n_rows + 7u) / 8u);
@@ -369,7 +372,7 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
     const uint32_t blocks_wanted = (uint32_t)std::min<uint64_t>(h->n_cus * blocks_per_cu, std::max<uint64_t>(1, paths_in_call / (16u * (kTraceBlock / 64u))));
     const dim3 grid(blocks_wanted), block(256), trace_block(kTraceBlock);
     uint32_t max_blocks = 1;
-    for (int i = 0; i < 8; ++i) max_blocks = std::max(max_blocks, h->blocks_per_cu[i >> 2][(i >> 1) & 1][i & 1]);
+    for (int i = 0; i < 16; ++i) max_blocks = std::max(max_blocks, h->blocks_per_cu[i >> 3][(i >> 2) & 1][(i >> 1) & 1][i & 1]);
     const uint32_t max_threads = h->n_cus * max_blocks * kTraceBlock;
 
     const uint32_t tiles_x = (args_in.width + 7u) / 8u;
@@ -428,7 +431,7 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count)
         work_sizes(pt.n_paths, grid.x * (kTraceBlock / 64u), h->tune.fine_rounds, h->tune.chunk, pt.coarse, pt.fine_below);
         // the buffer's previous batch must have been accumulated (same stream: implicit)
         LAUNCH_TRY(hipEventRecord(NextEvent(h->ev), st));
-        hipLaunchKernelGGL(kPtKernels[count][brute][tail], grid, trace_block, lds, st, args_in, pt, bfirst, tt);
+        hipLaunchKernelGGL(kPtKernels[glossy][count][brute][tail], grid, trace_block, lds, st, args_in, pt, bfirst, tt);
         LAUNCH_TRY(hipEventRecord(NextEvent(h->ev), st));
         // accumulate in sample order: batch k after batch k-1
         if (n_streams == 2 && k > 0) LAUNCH_TRY(hipStreamWaitEvent(st, h->acc_done[(k - 1u) & 1u], 0));

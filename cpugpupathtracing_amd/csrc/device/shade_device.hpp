@@ -73,6 +73,44 @@ __device__ __forceinline__ LightSample sample_light(const DevScene& sc, uint32_t
     return ls;
 }
 
+// ---- rough specular lobe (GLOSSY instantiations) ----------------------------------------------------------------
+// Isotropic GGX reflection with the constant Fresnel `albedo` the mirror lobe has.  n is the shading normal turned to face the ray.
+// The microfacet normal h is drawn from the visible normals of wo (Heitz 2018, JCGT 7(4)) with u1, u2 -- the two draws after the lobe
+// choice -- and wi = reflect(-wo, h).  D and the sampling pdf cancel: the estimator's factor is G2 / G1 with the height-correlated
+// Smith G2 = 1 / (1 + L(wo) + L(wi)), G1 = 1 / (1 + L(wo)), L(w) = (-1 + sqrt(1 + alpha^2 tan^2(theta_w))) / 2.
+// Returns false when wi lies at or below the horizon of n (or wo grazes it): the lobe has no energy there.
+__device__ __forceinline__ bool ggx_sample(uint32_t& rng, V3 d, V3 normal, float alpha, V3& wi, float& weight)
+{
+    const float u1 = random_float(rng);
+    const float u2 = random_float(rng);
+    const V3 n = dot(d, normal) > 0.0f ? -normal : normal;
+    const float sign = copysignf(1.0f, n.z);                                  // orthonormal basis around n (Duff et al. 2017)
+    const float a = -1.0f / (sign + n.z), b = n.x * n.y * a;
+    const V3 tx = mk(1.0f + sign * n.x * n.x * a, sign * b, -sign * n.x);
+    const V3 ty = mk(b, sign + n.y * n.y * a, -n.y);
+    const V3 wo = -d;
+    const float ox = dot(wo, tx), oy = dot(wo, ty), oz = dot(wo, n);
+    if (!(oz > 0.0f)) return false;
+    const V3 vh = normalize(mk(alpha * ox, alpha * oy, oz));                  // stretch wo to the alpha = 1 configuration
+    const float lensq = vh.x * vh.x + vh.y * vh.y;
+    const V3 t1 = lensq > 0.0f ? mk(-vh.y, vh.x, 0.0f) * (1.0f / sqrtf(lensq)) : mk(1.0f, 0.0f, 0.0f);
+    const V3 t2 = cross(vh, t1);
+    const float rad = sqrtf(u1), phi = 2.0f * kPi * u2;                       // a point on the projected visible hemisphere
+    const float p1 = rad * cosf(phi);
+    const float s = 0.5f * (1.0f + vh.z);
+    const float p2 = (1.0f - s) * sqrtf(max_std(0.0f, 1.0f - p1 * p1)) + s * (rad * sinf(phi));
+    const V3 nh = p1 * t1 + p2 * t2 + sqrtf(max_std(0.0f, 1.0f - p1 * p1 - p2 * p2)) * vh;
+    const V3 hl = normalize(mk(alpha * nh.x, alpha * nh.y, max_std(0.0f, nh.z)));   // unstretch
+    wi = reflect(d, hl.x * tx + hl.y * ty + hl.z * n);
+    const float iz = dot(wi, n);
+    if (!(iz > 0.0f)) return false;
+    const float a2 = alpha * alpha;
+    const float lambda_o = 0.5f * (-1.0f + sqrtf(1.0f + a2 * (max_std(0.0f, 1.0f - oz * oz) / (oz * oz))));
+    const float lambda_i = 0.5f * (-1.0f + sqrtf(1.0f + a2 * (max_std(0.0f, 1.0f - iz * iz) / (iz * iz))));
+    weight = (1.0f + lambda_o) / (1.0f + lambda_o + lambda_i);
+    return true;
+}
+
 struct PathState {
     V3 throughput, energy;
     uint32_t rng, depth;
@@ -86,7 +124,8 @@ enum : uint32_t { kBounceChainShift = 4u, kChainReflect = 1u, kChainRefract = 2u
 // Processes the hit of `ray` (already traced).  On return: `ray` is the next extend ray unless kBounceTerminate is set;
 // if kBounceShadow is set, `shadow` / `pending` describe the NEE connection to trace (energy += pending when unoccluded,
 // ref: Main.cpp:452-463).  Emissive energy is added here; the final debug-view overrides are applied by the caller.
-template <bool COUNT>
+// GLOSSY: the scene has a material with roughness > 0 (ggx_sample); without it the instantiation is the mirror-only code.
+template <bool COUNT, bool GLOSSY = false>
 __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSettings& st, Ray& ray, PathState& ps, Ray& shadow,
                                                  V3& pending, Counters& cnt)
 {
@@ -130,7 +169,13 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
     }
 
     const float r = random_float(ps.rng);                                     // ref: Main.cpp:478
-    if (r < mat.specular) {                                                   // mirror, ref: Main.cpp:480-487
+    if (GLOSSY && r < mat.specular && mat.alpha > 0.0f) {                     // rough specular lobe
+        V3 gd; float g;
+        if (!ggx_sample(ps.rng, ray.d, hit.normal, mat.alpha, gd, g)) return result | kBounceTerminate;   // below the horizon: ends as RR ends it
+        ray = make_ray(hit.pos + gd * kNudge, gd, 1e34f);
+        ps.throughput = ps.throughput * (mat.albedo * g);
+        ps.is_specular = true;                                                // light hits count, as after the mirror; chain choice 0
+    } else if (r < mat.specular) {                                            // mirror, ref: Main.cpp:480-487
         const V3 sd = reflect(ray.d, hit.normal);
         ray = make_ray(hit.pos + sd * kNudge, sd, 1e34f);
         ps.throughput = ps.throughput * mat.albedo;
@@ -209,8 +254,9 @@ static constexpr uint32_t kMaxBruteLevels = 32;   // max_ray_depth + 1 levels ar
 enum : uint32_t { kBruteContinue = 0u, kBruteLeaf = 1u };
 
 // One TracePath level after IntersectScene(ray): either a leaf (returns its radiance in `leaf`) or a bounce (fills `level`,
-// replaces `ray` by the child ray).  RNG draw order as in the reference: r, then Fresnel choice or the hemisphere sample.
-template <bool COUNT>
+// replaces `ray` by the child ray).  RNG draw order as in the reference: r, then Fresnel choice or the hemisphere sample (or, GLOSSY, the
+// two draws of ggx_sample; a rough lobe below the horizon is a black leaf, as total internal reflection is).
+template <bool COUNT, bool GLOSSY = false>
 __device__ __forceinline__ uint32_t brute_bounce(const DevScene& sc, const DevSettings& st, Ray& ray, uint32_t& rng, uint32_t depth,
                                                  BruteLevel& level, V3& leaf, Counters& cnt)
 {
@@ -225,7 +271,12 @@ __device__ __forceinline__ uint32_t brute_bounce(const DevScene& sc, const DevSe
 
     const float r = random_float(rng);                                        // ref: Main.cpp:611
     level.cosi = 0.0f; level.absorb = mk(1.0f);
-    if (r < mat.specular) {                                                   // ref: Main.cpp:614-619
+    if (GLOSSY && r < mat.specular && mat.alpha > 0.0f) {                     // rough specular lobe: L = 0 + (albedo * G2/G1) * L
+        V3 gd; float g;
+        if (!ggx_sample(rng, ray.d, hit.normal, mat.alpha, gd, g)) { leaf = mk(0.0f); return kBruteLeaf; }
+        ray = make_ray(hit.pos + gd * kNudge, gd, 1e34f);
+        level.kind = 0u; level.a = mat.albedo * g;
+    } else if (r < mat.specular) {                                            // ref: Main.cpp:614-619
         const V3 sd = reflect(ray.d, hit.normal);
         ray = make_ray(hit.pos + sd * kNudge, sd, 1e34f);
         level.kind = 0u; level.a = mat.albedo;

@@ -40,6 +40,7 @@ class Renderer:
         self.interleave: Optional[Tuple[int, int, int]] = None
         self.n_rows = 0               # rows of this context's band
         self.num_accumulated = 0      # ref: Main.cpp:205
+        self._glossy = False          # the device holds a roughness > 0 (cgpt_scene_update_roughness)
 
     def _check(self, rc: int):
         if rc != 0:
@@ -49,14 +50,30 @@ class Renderer:
         self._check(self.L.cgpt_set_stream(self._ctx, C.c_void_p(hip_stream)))
 
     def upload(self, scene: Scene):
+        """cgpt_scene_upload, then the scene's roughness (cgpt_scene_update_roughness) when any is nonzero."""
         desc = scene.flatten()
         self._check(self.L.cgpt_scene_upload(self._ctx, C.byref(desc)))
+        self._glossy = False                                         # the upload reset every roughness to 0
         self.scene = scene
         self._node_counts = [desc.objects[k].node_count for k in range(desc.n_objects)]   # the uploaded trees (export_bvh)
+        rough = scene.roughness(desc.n_materials)
+        if rough.any():
+            self.update_roughness(rough)
 
     def update_materials(self, scene: Scene):
+        """cgpt_scene_update_materials, then the scene's roughness when it or the device's is nonzero."""
         desc = scene.flatten()
         self._check(self.L.cgpt_scene_update_materials(self._ctx, desc.materials, desc.n_materials))
+        rough = scene.roughness(desc.n_materials)
+        if rough.any() or self._glossy:
+            self.update_roughness(rough)
+
+    def update_roughness(self, values):
+        """cgpt_scene_update_roughness: the specular lobe's roughness of every uploaded material (0: mirror, > 0: GGX with
+        alpha = roughness^2).  Only the device copy changes; call reset_accumulator() before the next frame."""
+        v = np.ascontiguousarray(values, np.float32).ravel()
+        self._check(self.L.cgpt_scene_update_roughness(self._ctx, v.ctypes.data_as(C.POINTER(C.c_float)), v.size))
+        self._glossy = bool((v > 0.0).any())
 
     def refit_mesh(self, obj_index: int, triangles) -> float:
         """BVH refit on the device (cgpt_scene_refit_mesh): new triangles for uploaded mesh `obj_index` (or triangle object), in its
@@ -84,17 +101,18 @@ class Renderer:
 
     def render(self, width: int, height: int, n_samples: int = 1, seed: int = 0x12345678, rows: Optional[Tuple[int, int]] = None,
                kernel: int = N.KERNEL_AUTO, counters: bool = False, settings: Optional[Settings] = None,
-               interleave: Optional[Tuple[int, int, int]] = None):
+               interleave: Optional[Tuple[int, int, int]] = None, camera: Optional[N.Camera] = None):
         """Render() x n_samples (ref: Main.cpp:691-755).  Accumulates; call reset_accumulator() to start over.
         rows = (begin, end): a contiguous band.  interleave = (band_rows, count, index): every count-th band of band_rows
-        rows starting at band `index` (load-balanced multi-GPU tiling); the band is stored compactly in that order."""
+        rows starting at band `index` (load-balanced multi-GPU tiling); the band is stored compactly in that order.
+        camera: a cgpt_camera (default: the uploaded scene's)."""
         assert self.scene is not None, "upload a scene first"
         assert rows is None or interleave is None
         r0, r1 = rows if rows is not None else (0, height)
         il = interleave if interleave is not None else (0, 0, 0)
         if (width, height, (r0, r1), interleave) != (self.width, self.height, self.rows, self.interleave):
             self.num_accumulated = 0          # the library re-allocates (zeroed) on a size/band change
-        cam = self.scene.camera()
+        cam = camera if camera is not None else self.scene.camera()
         st = settings.to_abi() if settings is not None else self.scene.settings()
         p = N.RenderParams(width, height, r0, r1, self.num_accumulated, n_samples, seed & 0xFFFFFFFF, kernel,
                            N.RENDER_COUNTERS if counters else 0, il[0], il[1], il[2])

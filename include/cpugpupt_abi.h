@@ -26,7 +26,8 @@ extern "C" {
 
 #define CGPT_ABI_VERSION 2u   /* 2: cgpt_stats grew (gather_ms .. last_kernel), CGPT_KERNEL_* / CGPT_CTX_* values added since 1;
                                  CGPT_OBJECT_TRIANGLE is a new enum value only, no layout changed; the denoiser added new symbols
-                                 (cgpt_read_guides, cgpt_denoise) and a new struct (cgpt_denoise_params) only */
+                                 (cgpt_read_guides, cgpt_denoise) and a new struct (cgpt_denoise_params) only; the microfacet specular
+                                 lobe added one new symbol (cgpt_scene_update_roughness) only */
 
 enum cgpt_status {
     CGPT_OK = 0,
@@ -189,6 +190,15 @@ int cgpt_set_stream(cgpt_ctx* ctx, void* hip_stream);
 int cgpt_scene_upload(cgpt_ctx* ctx, const cgpt_scene_desc* scene);
 /* replaces Material::RenderImGui edits (ref: Main.cpp:71-91,263-265); the caller resets the accumulator as the reference does */
 int cgpt_scene_update_materials(cgpt_ctx* ctx, const cgpt_material* materials, uint32_t n_materials);
+/* Microfacet BRDF (reference README, "Planned"): the roughness in [0, 1] of every material's specular lobe (the `r < specular` branch),
+ * one value per uploaded material.  0 is the reference's perfect mirror, bit for bit; r > 0 is isotropic GGX reflection with
+ * alpha = r^2, visible-normal sampling, height-correlated Smith masking and the constant Fresnel `albedo`.  Light
+ * materials and the dielectric lobe ignore it.  cgpt_scene_upload resets every roughness to 0; cgpt_scene_update_materials keeps it.
+ * Refused, with nothing changed: no scene (CGPT_ERR_NO_SCENE); roughness NULL, n_materials other than the uploaded count, or a value
+ * that is not finite or lies outside [0, 1] (CGPT_ERR_INVALID).  The caller resets the accumulator, as with the materials.  The
+ * denoiser's cached guides stay valid: first hits and albedo do not depend on roughness.  A HIP failure during the write drops the
+ * scene, as the geometry edits below do; a multi-device context updates every device. */
+int cgpt_scene_update_roughness(cgpt_ctx* ctx, const float* roughness, uint32_t n_materials);
 
 /* ---- in-place geometry edits of the uploaded scene (no re-upload; the caller resets the accumulator, as with the materials) ----
  * Every call validates before its first device write: a refused call leaves the device scene as it was.  If a HIP call fails after
