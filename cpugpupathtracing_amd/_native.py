@@ -80,7 +80,8 @@ class Stats(C.Structure):
                 ("dominant_launches", C.c_uint32), ("dominant_waves_per_simd", C.c_uint32), ("dominant_ms", C.c_double),
                 ("gather_ms", C.c_double), ("gathers", C.c_uint32), ("n_devices", C.c_uint32), ("rccl_ranks", C.c_uint32),
                 ("last_kernel", C.c_uint32), ("device_ms", C.c_double * 8),
-                ("dominant_round0_ms", C.c_double), ("dominant_round0_launches", C.c_uint32), ("chain_followers", C.c_uint32)]
+                ("dominant_round0_ms", C.c_double), ("dominant_round0_launches", C.c_uint32), ("chain_followers", C.c_uint32),
+                ("probe_resolved", C.c_uint64)]
 
 
 class DenoiseParams(C.Structure):

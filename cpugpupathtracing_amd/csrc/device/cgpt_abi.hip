@@ -840,6 +840,7 @@ int cgpt_get_stats(cgpt_ctx* ctx, cgpt_stats* out)
     out->gather_ms = 0.0; out->gathers = 0; out->n_devices = 1; out->rccl_ranks = 0; out->last_kernel = ctx->last_kernel;
     memset(out->device_ms, 0, sizeof(out->device_ms)); out->device_ms[0] = ctx->kernel_ms;
     out->dominant_round0_ms = ctx->dominant_round0_ms; out->dominant_round0_launches = ctx->dominant_round0_launches; out->chain_followers = (uint32_t)std::min<unsigned long long>(c.chain_followers, 0xFFFFFFFFull);
+    out->probe_resolved = c.probe_resolved;
     return CGPT_OK;
 }
 

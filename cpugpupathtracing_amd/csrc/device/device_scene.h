@@ -109,6 +109,7 @@ struct DevCounters {  // device-side totals, 64-bit atomics
     unsigned long long traced_rays, inner_steps, tri_tests, bvh_depth_sum, closest_hits;
     double total_energy;
     unsigned long long chain_followers;   // wavefront later rounds: extend rays whose specular-chain leader traced them
+    unsigned long long probe_resolved;    // wavefront shade: rays decided by probe_scene() and never listed (counted in traced_rays too)
 };
 
 struct DevRenderArgs {

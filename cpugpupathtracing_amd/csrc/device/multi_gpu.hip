@@ -542,6 +542,7 @@ int GroupGetStats(cgpt_ctx* ctx, cgpt_stats* out)
         out->dominant_waves_per_simd = s.dominant_waves_per_simd;
         out->dominant_round0_ms += s.dominant_round0_ms; out->dominant_round0_launches += s.dominant_round0_launches;
         out->chain_followers = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, (uint64_t)out->chain_followers + s.chain_followers);
+        out->probe_resolved += s.probe_resolved;
         out->device_ms[r++] = s.kernel_ms;
     }
     out->num_accumulated = g->num_accumulated;

@@ -339,6 +339,93 @@ __device__ __forceinline__ void intersect_scene(const DevScene& sc, Ray& ray, ui
     }
 }
 
+// ---- probe: the top of IntersectScene and nothing below it (wavefront shade: "Probe") ---------------------------------------
+// Walks the objects in order with the running t, as intersect_scene does, with the same loads and intersectors, but never enters a
+// mesh below its root: a mesh whose root is an inner node gets the slab test of the root's two children, a child that is hit is walked
+// only when it is a leaf (near one first, then the far one if it was hit too: what traverse_mesh pushes and pops), and a hit child that
+// is an inner node makes the ray kProbeUndecided -- it needs the real traversal.  Otherwise the answer is IntersectScene's own: did the
+// ray hit anything (ray_t is then the closest hit's t).  The object and root records sit at wave-uniform addresses.
+// A direction with a zero component is undecided as well: its slab test is the NaN-exact form (SURVEY A-18).
+enum : uint32_t { kProbeMiss = 0u, kProbeHit = 1u, kProbeUndecided = 2u };
+// The records the probe reads for every ray are the same for the whole wave, so they are fetched through the constant address space: scalar
+// loads into scalar registers, off the vector-memory path the shading loads take.  (Same bytes as load_pair / load_leaf_tri return.)
+#define CGPT_UNIFORM __attribute__((address_space(4)))
+__device__ __forceinline__ void load_pair_uniform(const float4* node_pairs, uint32_t code, NodePair& n)
+{
+    const CGPT_UNIFORM char* rec = (const CGPT_UNIFORM char*)node_pairs + (size_t)(code << 6);
+    n.q0 = *reinterpret_cast<const CGPT_UNIFORM f4v*>(rec);
+    n.q1 = *reinterpret_cast<const CGPT_UNIFORM f4v*>(rec + 16);
+    n.q2 = *reinterpret_cast<const CGPT_UNIFORM f4v*>(rec + 32);
+    const u2v codes = *reinterpret_cast<const CGPT_UNIFORM u2v*>(rec + 56);
+    n.lcode = codes.x; n.rcode = codes.y;
+}
+__device__ __forceinline__ LeafTri load_leaf_tri_uniform(const float4* tri_leaf, uint32_t index)
+{
+    const CGPT_UNIFORM char* rec = (const CGPT_UNIFORM char*)tri_leaf + (size_t)index * 48u;
+    const f4v a = *reinterpret_cast<const CGPT_UNIFORM f4v*>(rec), b = *reinterpret_cast<const CGPT_UNIFORM f4v*>(rec + 16);
+    const f4v c = *reinterpret_cast<const CGPT_UNIFORM f4v*>(rec + 32);      // {-, e2.z, tri_idx, last_in_leaf}
+    LeafTri t;
+    t.v0 = mk(a.x, a.y, a.z); t.e1 = mk(a.w, b.x, b.y); t.e2 = mk(b.z, b.w, c.y);
+    t.tri_idx = __float_as_uint(c.z); t.last = __float_as_uint(c.w) != 0u;
+    return t;
+}
+template <bool UNIFORM>
+__device__ __forceinline__ bool probe_leaf(const DevScene& sc, uint32_t code, V3 o, V3 d, float& ray_t)   // ref: BVH.cpp:74-90
+{
+    bool hit = false;
+    for (uint32_t i = code & ~kLeafBit;; ++i) {
+        const LeafTri lt = UNIFORM ? load_leaf_tri_uniform(sc.tri_leaf, i) : load_leaf_tri(sc.tri_leaf, i);
+        if (intersect_triangle(lt.v0, lt.e1, lt.e2, o, d, ray_t)) hit = true;
+        if (lt.last) break;
+    }
+    return hit;
+}
+// The walk's control flow is wave-uniform (object kinds, root codes and leaf ends are scalars): a lane that turns undecided walks on
+// with the others and its answer is dropped; the wave stops early once every lane is undecided.
+__device__ __forceinline__ uint32_t probe_scene(const DevScene& sc, V3 o, V3 d, float& ray_t)
+{
+    const V3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);                    // Ray ctor, ref: Primitives.h:64
+    bool undecided = has_infinite_component(inv);
+    const RaySlab rs = make_ray_slab(o, inv);
+    bool any = false;
+    const CGPT_UNIFORM DevObject* const objects = (const CGPT_UNIFORM DevObject*)sc.objects;
+    for (uint32_t obj_idx = 0; obj_idx < sc.n_objects; ++obj_idx) {
+        if (__builtin_amdgcn_ballot_w64(!undecided) == 0ull) break;
+        const CGPT_UNIFORM DevObject& obj = objects[obj_idx];
+        const uint32_t kind = obj.kind, root = obj.root_code;
+        bool hit = false;
+        if (kind == 0u) {
+            if (root & kLeafBit) hit = probe_leaf<true>(sc, root, o, d, ray_t);
+            else {
+                NodePair n;
+                load_pair_uniform(sc.node_pairs, root, n);
+                float left_dist, right_dist;
+                slab_pair(n, rs, ray_t, false, left_dist, right_dist);
+                uint32_t left_code = n.lcode, right_code = n.rcode;
+                if (left_dist > right_dist) {                                 // ref: BVH.cpp:101-105
+                    const float td = left_dist; left_dist = right_dist; right_dist = td;
+                    const uint32_t tc = left_code; left_code = right_code; right_code = tc;
+                }
+                if (left_dist != 1e30f) {                                     // ref: BVH.cpp:108-123
+                    const bool below = !(left_code & kLeafBit) || (right_dist != 1e30f && !(right_code & kLeafBit));
+                    undecided = undecided || below;
+                    if (((n.lcode | n.rcode) & kLeafBit) && !below) {         // (wave-uniform first: most roots have no leaf child)
+                        hit = probe_leaf<false>(sc, left_code, o, d, ray_t);
+                        if (right_dist != 1e30f && probe_leaf<false>(sc, right_code, o, d, ray_t)) hit = true;
+                    }
+                }
+            }
+        } else if (kind == 1u) hit = intersect_sphere(mk(obj.sphere_center[0], obj.sphere_center[1], obj.sphere_center[2]), obj.sphere_radius_sq, o, d, ray_t);
+        else if (kind == 2u) hit = intersect_plane(mk(obj.plane_normal[0], obj.plane_normal[1], obj.plane_normal[2]), mk(obj.plane_point[0], obj.plane_point[1], obj.plane_point[2]), o, d, ray_t);
+        else {
+            const LeafTri lt = load_leaf_tri_uniform(sc.tri_leaf, root & ~kLeafBit);
+            hit = intersect_triangle(lt.v0, lt.e1, lt.e2, o, d, ray_t);
+        }
+        any = any || hit;
+    }
+    return undecided ? kProbeUndecided : (any ? kProbeHit : kProbeMiss);
+}
+
 // ---- sampling / optics (ref: Source/Util.cpp:7-54) -------------------------------------------------------------------
 __device__ __forceinline__ V3 ball_sample(uint32_t& rng)              // rejection loop of Util.cpp:10-13; draw order x, y, z
 {

@@ -86,6 +86,7 @@ struct WfDev {
                                        // pixel of the band; null: no election (the COUNT and TracePath renders, spec_dedupe 0)
     uint32_t spec_keys;                // entries per pixel
     uint32_t spec_epoch;               // 1..0xFFFF, new for every shade launch: entries of other epochs are free
+    uint32_t probe;                    // wf_shade resolves the rays that probe_scene() decides itself (wf_shade: "Probe")
 };
 
 // Specular chains.  The reference does not jitter (SURVEY A-14), so all samples of a pixel share the primary ray and its hit, and
@@ -331,6 +332,16 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
     const bool banded = wf.n_bands > 1u;
     uint32_t cur_band = 0, band_start_ext = 0, band_start_sh = 0;             // wave-uniform
     Counters cnt = { 0, 0, 0, 0, 0 };
+    // Probe.  More than half of the later rounds' rays of the reference scene are decided by the top of IntersectScene alone: they miss both
+    // halves of the mesh's box, the ground quad and the light spheres -- shadow rays of ground pixels towards the lights, their bounce
+    // rays into the sky.  probe_scene() (rt_device.hpp) answers those here, from the registers that hold the ray, with the trace kernels'
+    // own intersectors: a decided shadow ray is never listed (unoccluded: its pending radiance goes to st_en now, the connect epilogue's
+    // read-modify-write moved; occluded: dropped), an extend ray decided as a miss ends its path now instead of in the next round.  Each
+    // is still one IntersectScene call of the reference and is counted as one.  Not probed: the counting kernels (they walk as the oracle
+    // walks), TracePath lanes, the debug views (they read the last depth), rays of a specular chain (the election and its followers stay
+    // as they are) and a ray re-traced after total internal reflection (it carries its payload).
+    const bool probe = !COUNT && wf.probe != 0u;                              // wave-uniform
+    uint32_t wave_probed = 0;                                                 // wave-uniform: rays this wave decided
 
     // The order in which a wave appends its survivors is the order of the next round's ray list.  Taking runs of `chunk`
     // consecutive blocks (the samples of one pixel and of its neighbours in round 0, and their descendants later) keeps the rays of
@@ -360,6 +371,7 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
     for (;;) {
         bool active = false;
         bool emit_ext = false, emit_sh = false;
+        bool decided_sh = false, decided_ext = false;                         // probe: the ray is resolved here and not listed
         uint32_t pid = 0;
         if (!hits_only) {
             if (!more) break;
@@ -464,16 +476,37 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
             } else if (is_pixel) flags = shade_bounce<COUNT, GLOSSY>(sc, args.settings, ray, ps, shadow, pending, cnt);
             emit_ext = (flags & kBounceTerminate) == 0u;
             emit_sh = (flags & kBounceShadow) != 0u;
+            if (kChains && emit_ext) {
+                const uint32_t choice = (flags >> kBounceChainShift) & 3u;    // 0: diffuse, else 1 + base-3 digit
+                chain = choice != 0u && chain != 0u && chain <= (kChainMax - 2u) / 3u ? chain * 3u + choice - 1u : 0u;
+            }
+            bool connect = false;                                             // the shadow ray is decided and reaches its light
+            if (probe && !(BRUTE && brute_path)) {
+                if (emit_sh) {
+                    float t = shadow.t;
+                    const uint32_t seen = probe_scene(sc, shadow.o, shadow.d, t);
+                    decided_sh = seen != kProbeUndecided;
+                    connect = seen == kProbeMiss;
+                }
+                if (emit_ext && !(kChains && chain != 0u) && ray.t == 1e34f) {
+                    float t = ray.t;
+                    decided_ext = probe_scene(sc, ray.o, ray.d, t) == kProbeMiss;
+                }
+                emit_sh = emit_sh && !decided_sh;
+                emit_ext = emit_ext && !decided_ext;
+            }
 
             // radiance added by this bounce (emissive hit / BVH-depth view): energy_old + x, the reference's single addition
             const bool final_depth_needed = args.settings.debug_mode == 1u && !emit_ext;      // ray-depth view reads the last depth
-            if (is_pixel && (first_round || (flags & (kBounceEnergy | kBounceBruteDone)) || final_depth_needed)) {
+            const bool own_energy = is_pixel && (first_round || (flags & (kBounceEnergy | kBounceBruteDone)) || final_depth_needed);
+            if (own_energy || connect) {
                 float4 en;
                 if (first_round || (BRUTE && (flags & kBounceBruteDone))) { en.x = 0.0f; en.y = 0.0f; en.z = 0.0f; en.w = 0.0f; }
                 else en = ld_stream(&wf.st_en[pid]);
                 if (BRUTE && (flags & kBounceBruteDone)) { en.x = ps.energy.x; en.y = ps.energy.y; en.z = ps.energy.z; }   // TracePath's return value, as it is
                 if (flags & kBounceEnergy) { en.x += ps.energy.x; en.y += ps.energy.y; en.z += ps.energy.z; }
-                en.w = __uint_as_float(ps.depth & 0xFFu);
+                if (own_energy) en.w = __uint_as_float(ps.depth & 0xFFu);
+                if (connect) { en.x += pending.x; en.y += pending.y; en.z += pending.z; }   // ref: Main.cpp:454-463, as wf_trace's connect epilogue adds it
                 st_stream(&wf.st_en[pid], en);
             }
             if (emit_ext) {                                                   // the path lives on: state + next extend ray, same slot
@@ -485,8 +518,6 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
                 nb.x = ray.d.x; nb.y = ray.d.y; nb.z = ray.d.z;
                 uint32_t fl = (ps.depth & 0xFFu) | (ps.is_specular ? 0x100u : 0u) | ((BRUTE && brute_path) ? 0x200u : 0u);
                 if (kChains) {
-                    const uint32_t choice = (flags >> kBounceChainShift) & 3u;   // 0: diffuse, else 1 + base-3 digit
-                    chain = choice != 0u && chain != 0u && chain <= (kChainMax - 2u) / 3u ? chain * 3u + choice - 1u : 0u;
                     fl |= chain << kChainShift;
                     if (wf.spec_tab) {
                         const uint32_t lead = elect_chain_leader(wf, chain, pid);
@@ -510,6 +541,7 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
         }
         // active-lane compaction into the wave's own segments: __ballot + mbcnt, no atomics
         const unsigned long long m_ext = __builtin_amdgcn_ballot_w64(emit_ext), m_sh = __builtin_amdgcn_ballot_w64(emit_sh);
+        if (probe) wave_probed += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(decided_sh)) + (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(decided_ext));
         if (banded) {                                                         // close the runs of the bands this pass has left behind
             const uint32_t band = min(wf.n_bands - 1u, __umulhi(pid, wf.band_magic));
             const bool emits = emit_ext | emit_sh;
@@ -539,6 +571,10 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
         wf.seg_count[wave] = count_ext; wf.seg_count[wf.n_segs + wave] = count_sh;
     }
     if (COUNT) wave_add_u64(&args.counters->closest_hits, cnt.hits);
+    if (!COUNT && lane_id() == 0u && wave_probed) {                           // every decided ray is an IntersectScene call of the reference
+        atomicAdd(&args.counters->traced_rays, (unsigned long long)wave_probed);
+        atomicAdd(&args.counters->probe_resolved, (unsigned long long)wave_probed);
+    }
 }
 
 // ---- plan: exclusive scan of the segment counts -------------------------------------------------------------------------------
@@ -677,6 +713,10 @@ struct WfTuning {               // defaults measured on MI355X (profiles/r01); o
     uint32_t spec_dedupe = 1;         // later rounds trace one ray per (pixel, specular chain) and batch (wf_shade: "Specular chains")
     uint32_t spec_keys = 8;           // election entries per pixel; a ray whose pixel has none left is traced as usual
     uint32_t spec_epochs = 0xFFFF;    // shade launches between two clears of a pool's election table (the 16-bit tag's range; fewer: tests)
+    uint32_t probe = 1;               // shade resolves the rays that the top of IntersectScene decides (wf_shade: "Probe")
+    uint32_t probe_max_objects = 128; // ... in scenes of at most this many objects: the probe walks all of them for every ray, as trace does; with 4 to
+                                      // 128 objects (the bench scene + far-away spheres) probe 1 took 0.87-0.91 of probe 0's time at every count
+                                      // (profiles/r10/probe_objects.txt), so the default is the largest count measured
 };
 
 static uint32_t Gcd(uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; }
@@ -811,7 +851,8 @@ static const Knob<WfTuning> kKnobs[] = {
     { "path_order", &WfTuning::path_order, 0, 2 },         { "retire_misses", &WfTuning::retire_misses, 0, 1 },
     { "lds_tris", &WfTuning::lds_tris, 0, 1 },             { "first_lean", &WfTuning::first_lean, 0, 1 },                     { "bands", &WfTuning::bands, 1, kMaxBands },             { "bands_min_paths", &WfTuning::bands_min_paths, 0, 0x7FFFFFFF },
     { "spec_dedupe", &WfTuning::spec_dedupe, 0, 1 },       { "spec_keys", &WfTuning::spec_keys, 1, 16 },
-    { "spec_epochs", &WfTuning::spec_epochs, 1, 0xFFFF },
+    { "spec_epochs", &WfTuning::spec_epochs, 1, 0xFFFF },   { "probe", &WfTuning::probe, 0, 1 },
+    { "probe_max_objects", &WfTuning::probe_max_objects, 0, 4096 },
 };
 
 static WfHost* WfGetHost(cgpt_ctx* ctx)
@@ -971,6 +1012,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, boo
         wf.retire_misses = h->tune.retire_misses && args_in.settings.debug_mode == 0u ? 1u : 0u;
         if (!chains) wf.spec_tab = nullptr;
         wf.spec_keys = h->tune.spec_keys;
+        wf.probe = h->tune.probe && !count && args_in.settings.debug_mode == 0u && args_in.scene.n_objects <= h->tune.probe_max_objects ? 1u : 0u;
         // segments of waves that a smaller shade grid does not launch must read as empty
         if (k < n_pools) LAUNCH_TRY(hipMemsetAsync(wf.seg_count, 0, 2 * (size_t)kMaxBands * wf.n_segs * sizeof(uint32_t), st));
         for (uint32_t r = 0; r < rounds; ++r) {

@@ -161,6 +161,9 @@ typedef struct cgpt_stats {
     uint32_t dominant_round0_launches;
     uint32_t chain_followers;      /* wavefront later-round extend rays not traced because the leader of their pixel's specular chain
                                       traced the same ray (the election of wavefront_kernels.hip); saturates at 2^32 - 1 */
+    uint64_t probe_resolved;       /* wavefront rays that the shade kernel decided itself from the top of IntersectScene (object list, mesh
+                                      roots, analytic primitives) and never queued for the trace kernel; each is counted in traced_rays too.
+                                      0 with CGPT_RENDER_COUNTERS, in the debug views and with the tuning knob probe = 0 */
 } cgpt_stats;
 
 typedef struct cgpt_ctx cgpt_ctx;
