@@ -98,6 +98,19 @@ _vp = C.c_void_p
 _fp = C.POINTER(C.c_float)
 _up = C.POINTER(C.c_uint32)
 
+
+class SceneLayoutView(C.Structure):
+    """cgpth_scene_layout_view: counts are elements (float4s for the float arrays, object_size bytes for objects)."""
+    _fields_ = [("node_pairs", _fp), ("n_node_pairs", C.c_size_t), ("tri_leaf", _fp), ("n_tri_leaf", C.c_size_t),
+                ("tri_orig", _fp), ("n_tri_orig", C.c_size_t), ("tri_normal", _fp), ("n_tri_normal", C.c_size_t),
+                ("materials", _fp), ("n_materials", C.c_size_t), ("obj_trace", _fp), ("n_obj_trace", C.c_size_t),
+                ("objects", _vp), ("n_objects", C.c_size_t), ("object_size", C.c_size_t),
+                ("lights", _up), ("n_lights", C.c_size_t), ("refit_levels", _up), ("n_refit_levels", C.c_size_t),
+                ("record_perm", _up), ("n_record_perm", C.c_size_t),
+                ("stack_depth", C.c_uint32), ("n_top_records", C.c_uint32), ("n_pair_records", C.c_uint32), ("n_small_tris", C.c_uint32),
+                ("leaf_base", _up), ("pair_base", _up), ("level_begin", _up), ("level_offsets", _up), ("level_offsets_start", _up)]
+
+
 # name -> (restype, argtypes).  Every symbol declared in include/*.h is listed; tests check the list against the headers.
 PROTOTYPES = {
     # cpugpupt_abi.h
@@ -172,6 +185,7 @@ PROTOTYPES = {
     "cgpth_write_accumulator": (C.c_int, [C.c_char_p, _fp, C.c_uint32, C.c_uint32, C.c_uint32]),
     "cgpth_read_accumulator": (C.c_int, [C.c_char_p, _fp, _up, C.c_uint32, C.c_uint32]),
     "cgpth_fast_div": (C.c_uint32, [C.c_uint32, C.c_uint32]),
+    "cgpth_scene_layout": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(SceneLayoutView)]),
 }
 
 _lib = None

@@ -1,5 +1,5 @@
 // cgpt_abi.hip -- implementation of the C ABI in include/cpugpupt_abi.h on HIP (gfx950).
-// Context management, the AoS -> device-layout upload (device_scene.h), kernel launches, statistics.
+// Context management, the upload of a laid-out scene (scene_layout.h -> device_scene.h), kernel launches, statistics.
 // There is no CPU fallback anywhere in this file: without a gfx950 device every entry point fails loudly.
 #include <hip/hip_runtime.h>
 
@@ -15,6 +15,7 @@
 
 #include "cpugpupt_abi.h"
 #include "device_scene.h"
+#include "scene_layout.h"
 
 namespace cgpt {
 hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, bool glossy, hipStream_t stream);       // path_kernels.hip
@@ -118,301 +119,6 @@ void FreeFramebuffer(cgpt_ctx* ctx)
     (void)hipFree(ctx->d_accumulator);
     (void)hipFree(ctx->d_pixels);
     ctx->d_accumulator = nullptr; ctx->d_pixels = nullptr;
-}
-
-float4 F4(float x, float y, float z, float w) { float4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
-float AsFloat(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-
-// roughness: the specular lobe's (cgpt_scene_update_roughness); the record holds alpha = roughness^2, formed here once
-void PackMaterial(const cgpt_material& m, float roughness, float4 out[4])
-{
-    out[0] = F4(m.albedo[0], m.albedo[1], m.albedo[2], m.specular);
-    out[1] = F4(m.refractivity, m.absorption[0], m.absorption[1], m.absorption[2]);
-    out[2] = F4(m.ior, m.emissive[0], m.emissive[1], m.emissive[2]);
-    out[3] = F4(m.intensity, AsFloat(m.is_light ? 1u : 0u), roughness * roughness, 0.0f);
-}
-
-// leaf-ordered triangle record (device_scene.h: tri_leaf) and original-order record (tri_orig) of one triangle
-void PackLeafTri(const cgpt_triangle& tr, uint32_t tri_idx, float4 rec[3])
-{
-    const float e1[3] = { tr.v1.pos[0] - tr.v0.pos[0], tr.v1.pos[1] - tr.v0.pos[1], tr.v1.pos[2] - tr.v0.pos[2] };   // ref: Primitives.cpp:9
-    const float e2[3] = { tr.v2.pos[0] - tr.v0.pos[0], tr.v2.pos[1] - tr.v0.pos[1], tr.v2.pos[2] - tr.v0.pos[2] };   // ref: Primitives.cpp:10
-    rec[0] = F4(tr.v0.pos[0], tr.v0.pos[1], tr.v0.pos[2], e1[0]);
-    rec[1] = F4(e1[1], e1[2], e2[0], e2[1]);
-    rec[2] = F4(0.0f, e2[2], AsFloat(tri_idx), AsFloat(0u));                                        // last_in_leaf set by the caller
-}
-void PackOrigTri(const cgpt_triangle& tr, float4 rec[3])
-{
-    rec[0] = F4(tr.v0.pos[0], tr.v0.pos[1], tr.v0.pos[2], tr.v0.normal[0]);
-    rec[1] = F4(tr.v1.pos[0], tr.v1.pos[1], tr.v1.pos[2], tr.v0.normal[1]);
-    rec[2] = F4(tr.v2.pos[0], tr.v2.pos[1], tr.v2.pos[2], tr.v0.normal[2]);
-}
-
-// Re-lays the reference's AoS scene into the device layout of device_scene.h, validating everything a kernel will
-// index with (a malformed tree must fail here, not fault on the GPU).
-int BuildDeviceScene(cgpt_ctx* ctx, const cgpt_scene_desc& sd)
-{
-    if (sd.n_objects == 0 || !sd.objects) return Fail(ctx, CGPT_ERR_INVALID, "scene has no objects");
-    if (sd.n_materials == 0 || !sd.materials) return Fail(ctx, CGPT_ERR_INVALID, "scene has no materials");
-    if (sd.n_lights && !sd.light_indices) return Fail(ctx, CGPT_ERR_INVALID, "light_indices is null");
-
-    std::vector<float4> pairs, tri_leaf, tri_orig, tri_normal, mats;
-    std::vector<DevObject> objs(sd.n_objects);
-    uint32_t max_tree_depth = 0;
-    // for in-place edits (refit.hip): per object where its records live, and the depth of every child-pair record (0xFF: not reached)
-    std::vector<RefitObject> refit(sd.n_objects);
-    std::vector<uint8_t> rec_depth;
-
-    // leaf-record order (device_scene.h): the triangles of the small meshes first, then the rest in object order; a triangle
-    // object has one leaf record, like a one-triangle mesh
-    std::vector<uint32_t> leaf_base_of(sd.n_objects, 0);
-    uint32_t n_small_tris = 0;
-    {
-        auto leaf_records = [&](uint32_t oi) -> uint32_t {
-            const cgpt_object& o = sd.objects[oi];
-            return o.kind == CGPT_OBJECT_MESH ? o.tri_count : (o.kind == CGPT_OBJECT_TRIANGLE ? 1u : 0u);
-        };
-        uint64_t total = 0;
-        std::vector<uint8_t> small(sd.n_objects, 0);
-        for (uint32_t oi = 0; oi < sd.n_objects; ++oi) {
-            const uint32_t n = leaf_records(oi);
-            total += n;
-            if (n > 0 && n <= kSmallMeshTris && n_small_tris + n <= kLdsTrisMax) { small[oi] = 1; leaf_base_of[oi] = n_small_tris; n_small_tris += n; }
-        }
-        if (total >= (1u << 26)) return Fail(ctx, CGPT_ERR_INVALID, "scene too large: more than 2^26 triangles or inner nodes");
-        uint32_t next = n_small_tris;
-        for (uint32_t oi = 0; oi < sd.n_objects; ++oi)
-            if (!small[oi]) { leaf_base_of[oi] = next; next += leaf_records(oi); }
-        tri_leaf.resize(3 * (size_t)total);
-    }
-
-    for (uint32_t oi = 0; oi < sd.n_objects; ++oi) {
-        const cgpt_object& o = sd.objects[oi];
-        DevObject& d = objs[oi];
-        memset(&d, 0, sizeof(d));
-        d.kind = o.kind; d.mat_index = o.mat_index;
-        if (o.mat_index >= sd.n_materials) return Fail(ctx, CGPT_ERR_INVALID, "object %u: mat_index %u out of range", oi, o.mat_index);
-        if (o.kind == CGPT_OBJECT_SPHERE) {
-            memcpy(d.sphere_center, o.sphere_center, 12);
-            d.sphere_radius = o.sphere_radius;
-            d.sphere_radius_sq = o.sphere_radius * o.sphere_radius;                  // Sphere ctor, ref: Primitives.h:38-39
-            continue;
-        }
-        if (o.kind == CGPT_OBJECT_PLANE) {
-            memcpy(d.plane_normal, o.plane_normal, 12);
-            memcpy(d.plane_point, o.plane_point, 12);
-            continue;
-        }
-        if (o.kind == CGPT_OBJECT_TRIANGLE) {
-            // Primitive(const Triangle&) (ref: Primitives.h:84-89): one leaf record as the root, so the trace kernels test it with
-            // their leaf step -- IntersectTriangle (ref: Primitives.cpp:292-305) -- and its shading normal is v0.normal (:308-321)
-            if (!sd.triangles) return Fail(ctx, CGPT_ERR_INVALID, "triangle object %u but triangles is null", oi);
-            if (o.tri_count != 1 || o.node_count != 0)
-                return Fail(ctx, CGPT_ERR_INVALID, "object %u: a triangle object has tri_count 1 and node_count 0, got %u and %u", oi, o.tri_count, o.node_count);
-            if (o.tri_offset >= sd.n_triangles) return Fail(ctx, CGPT_ERR_INVALID, "object %u: triangle %u out of range", oi, o.tri_offset);
-            const cgpt_triangle& tr = sd.triangles[o.tri_offset];
-            const uint32_t leaf_base = leaf_base_of[oi];
-            const uint32_t orig_base = (uint32_t)(tri_orig.size() / 3);
-            float4* leaf = tri_leaf.data() + 3 * (size_t)leaf_base;          // sized above
-            PackLeafTri(tr, 0u, leaf);
-            leaf[2].w = AsFloat(1u);                                          // last_in_leaf
-            tri_orig.resize(tri_orig.size() + 3);
-            PackOrigTri(tr, tri_orig.data() + 3 * (size_t)orig_base);
-            tri_normal.push_back(F4(tr.v0.normal[0], tr.v0.normal[1], tr.v0.normal[2], 0.0f));   // TriangleNormal, ref: Primitives.cpp:148-151
-            d.root_code = kLeafBit | leaf_base; d.tri_base = orig_base; d.n_tris = 1;
-            refit[oi].tri_count = 1; refit[oi].leaf_base = leaf_base;
-            continue;
-        }
-        if (o.kind != CGPT_OBJECT_MESH)
-            return Fail(ctx, CGPT_ERR_UNSUPPORTED, "object %u: primitive kind %u has no intersector (the reference EXCEPTs on AABB too, Primitives.cpp:302-305)", oi, o.kind);
-
-        // ---- mesh: validate the slices ----
-        if (!sd.nodes || !sd.triangles || !sd.tri_indices) return Fail(ctx, CGPT_ERR_INVALID, "mesh object %u but nodes/triangles/tri_indices is null", oi);
-        if (o.node_count == 0 || (uint64_t)o.node_offset + o.node_count > sd.n_nodes) return Fail(ctx, CGPT_ERR_INVALID, "object %u: node slice out of range", oi);
-        if (o.tri_count == 0 || (uint64_t)o.tri_offset + o.tri_count > sd.n_triangles) return Fail(ctx, CGPT_ERR_INVALID, "object %u: triangle slice out of range", oi);
-        if ((o.node_count & 1u) == 0) return Fail(ctx, CGPT_ERR_INVALID, "object %u: a binary BVH has an odd node count, got %u", oi, o.node_count);
-        const cgpt_bvh_node* nodes = sd.nodes + o.node_offset;
-        const cgpt_triangle* tris = sd.triangles + o.tri_offset;
-        const uint32_t* tidx = sd.tri_indices + o.tri_offset;
-
-        const uint32_t pair_base = (uint32_t)(pairs.size() / 4);
-        const uint32_t leaf_base = leaf_base_of[oi];
-        const uint32_t orig_base = (uint32_t)(tri_orig.size() / 3);
-        // record byte offsets are computed in 32 bits on the device (64-byte pairs, 48-byte leaf triangles)
-        if ((uint64_t)leaf_base + o.tri_count >= (1u << 26) || (uint64_t)pair_base + o.node_count / 2 >= (1u << 26))
-            return Fail(ctx, CGPT_ERR_INVALID, "scene too large: more than 2^26 triangles or inner nodes");
-
-        auto code_of = [&](uint32_t node_index, uint32_t& code) -> bool {
-            const cgpt_bvh_node& n = nodes[node_index];
-            if (n.prim_count > 0) {
-                if ((uint64_t)n.left_first + n.prim_count > o.tri_count) return false;
-                code = kLeafBit | (leaf_base + n.left_first);
-                return true;
-            }
-            // children were allocated as a pair after the parent: odd index, both in range, both beyond the parent
-            if ((n.left_first & 1u) == 0 || n.left_first <= node_index || (uint64_t)n.left_first + 1 >= o.node_count) return false;
-            code = pair_base + (n.left_first - 1) / 2;
-            return true;
-        };
-
-        uint32_t root_code;
-        if (!code_of(0, root_code)) return Fail(ctx, CGPT_ERR_INVALID, "object %u: malformed BVH root", oi);
-        d.root_code = root_code; d.tri_base = orig_base; d.n_tris = o.tri_count; d.total_area = o.total_area;
-        refit[oi].node_count = o.node_count; refit[oi].tri_count = o.tri_count; refit[oi].leaf_base = leaf_base; refit[oi].pair_base = pair_base;
-
-        // leaf-ordered triangle records
-        float4* leaf = tri_leaf.data() + 3 * (size_t)leaf_base;            // sized above
-        for (uint32_t i = 0; i < o.tri_count; ++i) {
-            const uint32_t t = tidx[i];
-            if (t >= o.tri_count) return Fail(ctx, CGPT_ERR_INVALID, "object %u: tri_indices[%u] = %u out of range", oi, i, t);
-            PackLeafTri(tris[t], t, leaf + 3 * (size_t)i);
-        }
-        // original-order records for GetTriangle users
-        tri_orig.resize(tri_orig.size() + 3 * (size_t)o.tri_count);
-        float4* orig = tri_orig.data() + 3 * (size_t)orig_base;
-        for (uint32_t t = 0; t < o.tri_count; ++t) {
-            const cgpt_triangle& tr = tris[t];
-            PackOrigTri(tr, orig + 3 * (size_t)t);
-            tri_normal.push_back(F4(tr.v0.normal[0], tr.v0.normal[1], tr.v0.normal[2], 0.0f));   // TriangleNormal, ref: Primitives.cpp:148-151
-        }
-
-        // child-pair records + leaf terminators; iterative DFS from the root also measures the real depth
-        pairs.resize(pairs.size() + 4 * (size_t)(o.node_count / 2), F4(0, 0, 0, 0));
-        rec_depth.resize(pairs.size() / 4, 0xFF);
-        float4* pr = pairs.data() + 4 * (size_t)pair_base;
-        std::vector<uint8_t> covered(o.tri_count, 0);
-        struct Item { uint32_t node, depth; };
-        std::vector<Item> todo;
-        todo.push_back({ 0, 0 });
-        uint32_t visited = 0;
-        while (!todo.empty()) {
-            const Item it = todo.back(); todo.pop_back();
-            if (++visited > o.node_count) return Fail(ctx, CGPT_ERR_INVALID, "object %u: BVH is not a tree", oi);
-            if (it.depth > max_tree_depth) max_tree_depth = it.depth;
-            const cgpt_bvh_node& n = nodes[it.node];
-            if (n.prim_count > 0) {
-                if ((uint64_t)n.left_first + n.prim_count > o.tri_count) return Fail(ctx, CGPT_ERR_INVALID, "object %u: leaf %u out of range", oi, it.node);
-                for (uint32_t i = n.left_first; i < n.left_first + n.prim_count; ++i) {
-                    if (covered[i]) return Fail(ctx, CGPT_ERR_INVALID, "object %u: triangle slot %u is in two leaves", oi, i);
-                    covered[i] = 1;
-                }
-                leaf[3 * (size_t)(n.left_first + n.prim_count - 1) + 2].w = AsFloat(1u);     // last_in_leaf
-                continue;
-            }
-            uint32_t lc, rc, dummy;
-            if (!code_of(it.node, dummy)) return Fail(ctx, CGPT_ERR_INVALID, "object %u: malformed inner node %u", oi, it.node);
-            const uint32_t L = n.left_first;
-            if (!code_of(L, lc) || !code_of(L + 1, rc)) return Fail(ctx, CGPT_ERR_INVALID, "object %u: malformed children of node %u", oi, it.node);
-            float4* rec = pr + 4 * (size_t)((L - 1) / 2);
-            rec_depth[pair_base + (L - 1) / 2] = (uint8_t)std::min<uint32_t>(it.depth, 0xFEu);   // > 63 is refused below
-            const cgpt_bvh_node& l = nodes[L]; const cgpt_bvh_node& r = nodes[L + 1];
-            // left / right interleaved per component: one packed-f32 instruction handles both children (device_scene.h)
-            rec[0] = F4(l.aabb_min[0], r.aabb_min[0], l.aabb_min[1], r.aabb_min[1]);
-            rec[1] = F4(l.aabb_min[2], r.aabb_min[2], l.aabb_max[0], r.aabb_max[0]);
-            rec[2] = F4(l.aabb_max[1], r.aabb_max[1], l.aabb_max[2], r.aabb_max[2]);
-            rec[3] = F4(0.0f, 0.0f, AsFloat(lc), AsFloat(rc));
-            todo.push_back({ L + 1, it.depth + 1 });
-            todo.push_back({ L, it.depth + 1 });
-        }
-    }
-
-    for (uint32_t i = 0; i < sd.n_lights; ++i) {
-        const uint32_t li = sd.light_indices[i];
-        if (li >= sd.n_objects) return Fail(ctx, CGPT_ERR_INVALID, "light_indices[%u] = %u out of range", i, li);
-        if (sd.objects[li].kind != CGPT_OBJECT_MESH && sd.objects[li].kind != CGPT_OBJECT_SPHERE)   // planes and triangle objects
-            return Fail(ctx, CGPT_ERR_UNSUPPORTED, "light %u (object %u, kind %u): only mesh and sphere lights can be sampled (the reference EXCEPTs, Main.cpp:383)",
-                        i, li, sd.objects[li].kind);
-    }
-
-    const uint32_t stack_depth = max_tree_depth + 1;
-    if (stack_depth > 64) return Fail(ctx, CGPT_ERR_UNSUPPORTED, "BVH depth %u exceeds the traversal stack of 64 (ref: BVH.cpp:66)", max_tree_depth);
-
-    mats.resize(4 * (size_t)sd.n_materials);
-    for (uint32_t i = 0; i < sd.n_materials; ++i) PackMaterial(sd.materials[i], 0.0f, mats.data() + 4 * (size_t)i);   // an upload resets roughness
-    std::vector<uint32_t> lights(sd.light_indices, sd.light_indices + sd.n_lights);
-
-    // ---- record order (device_scene.h: "record order") ----
-    // The reference allocates nodes depth-first; a record's index is only a name here (codes are rewritten), so the records are
-    // renumbered: the first kTopRecords in breadth-first order over all meshes (the top of every tree, which every ray walks:
-    // the trace kernel mirrors records [0, n_top_records) in LDS), the rest in the reference's order.
-    const uint32_t n_records = (uint32_t)(pairs.size() / 4);
-    std::vector<uint32_t> perm(n_records, 0xFFFFFFFFu);
-    std::vector<uint32_t> bfs; bfs.reserve(n_records);
-    for (uint32_t oi = 0; oi < sd.n_objects; ++oi)
-        if (objs[oi].kind == CGPT_OBJECT_MESH && (objs[oi].root_code & kLeafBit) == 0u) bfs.push_back(objs[oi].root_code);
-    const size_t bfs_limit = std::min<size_t>(n_records, kTopRecords);
-    for (size_t head = 0; head < bfs.size() && bfs.size() < n_records; ++head) {
-        if (bfs.size() >= bfs_limit + 2 * kTopRecords) break;                  // enough: only the first bfs_limit are used
-        const float4& cc = pairs[4 * (size_t)bfs[head] + 3];
-        uint32_t lc, rc; memcpy(&lc, &cc.z, 4); memcpy(&rc, &cc.w, 4);
-        if ((lc & kLeafBit) == 0u) bfs.push_back(lc);
-        if ((rc & kLeafBit) == 0u) bfs.push_back(rc);
-    }
-    uint32_t next = 0;
-    for (size_t i = 0; i < bfs.size() && i < bfs_limit; ++i) perm[bfs[i]] = next++;
-    for (uint32_t r = 0; r < n_records; ++r) if (perm[r] == 0xFFFFFFFFu) perm[r] = next++;
-    std::vector<float4> moved(pairs.size());
-    for (uint32_t r = 0; r < n_records; ++r) {
-        float4* dst = moved.data() + 4 * (size_t)perm[r];
-        const float4* src = pairs.data() + 4 * (size_t)r;
-        dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; dst[3] = src[3];
-        uint32_t lc, rc; memcpy(&lc, &src[3].z, 4); memcpy(&rc, &src[3].w, 4);
-        if ((lc & kLeafBit) == 0u) lc = perm[lc];
-        if ((rc & kLeafBit) == 0u) rc = perm[rc];
-        dst[3].z = AsFloat(lc); dst[3].w = AsFloat(rc);
-    }
-    pairs.swap(moved);
-    for (uint32_t oi = 0; oi < sd.n_objects; ++oi)
-        if (objs[oi].kind == CGPT_OBJECT_MESH && (objs[oi].root_code & kLeafBit) == 0u) objs[oi].root_code = perm[objs[oi].root_code];
-    const uint32_t n_top_records = (uint32_t)std::min(bfs.size(), bfs_limit);
-
-    // each mesh's child-pair records grouped by depth, in their final numbering: the refit's bound pass runs one level after the other,
-    // deepest first (refit.hip)
-    std::vector<uint32_t> levels;
-    levels.reserve(n_records);
-    for (uint32_t oi = 0; oi < sd.n_objects; ++oi) {
-        RefitObject& ro = refit[oi];
-        if (objs[oi].kind != CGPT_OBJECT_MESH || ro.node_count < 3) continue;   // a leaf-rooted mesh has no records
-        uint32_t count[66] = { 0 };
-        uint32_t n_levels = 0;
-        const uint32_t r0 = ro.pair_base, r1 = ro.pair_base + ro.node_count / 2;
-        for (uint32_t r = r0; r < r1; ++r)
-            if (rec_depth[r] != 0xFF) { ++count[rec_depth[r] + 1]; n_levels = std::max<uint32_t>(n_levels, rec_depth[r] + 1u); }
-        for (uint32_t d = 0; d < n_levels; ++d) count[d + 1] += count[d];
-        ro.level_begin = (uint32_t)levels.size();
-        ro.level_offsets.assign(count, count + n_levels + 1);
-        levels.resize(levels.size() + count[n_levels]);
-        uint32_t* out = levels.data() + ro.level_begin;
-        for (uint32_t r = r0; r < r1; ++r)
-            if (rec_depth[r] != 0xFF) out[count[rec_depth[r]]++] = perm[r];
-    }
-
-    // per-object records for the trace kernel's object phase (device_scene.h: obj_trace)
-    std::vector<float4> obj_trace(2 * (size_t)sd.n_objects);
-    for (uint32_t oi = 0; oi < sd.n_objects; ++oi) {
-        PackObjTrace(objs[oi], obj_trace[2 * (size_t)oi], obj_trace[2 * (size_t)oi + 1]);
-    }
-
-    FreeScene(ctx);
-    int rc;
-    if ((rc = UploadArray(ctx, &ctx->d_node_pairs, pairs)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, &ctx->d_tri_leaf, tri_leaf)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, &ctx->d_tri_orig, tri_orig)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, &ctx->d_tri_normal, tri_normal)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, &ctx->d_materials, mats)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, &ctx->d_objects, objs)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, &ctx->d_obj_trace, obj_trace)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, &ctx->d_lights, lights)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, &ctx->d_refit_levels, levels)) != CGPT_OK) return rc;
-    ctx->h_objects.swap(objs); ctx->refit_objects.swap(refit); ctx->record_perm.swap(perm);
-    ctx->h_roughness.assign(sd.n_materials, 0.0f); ctx->h_materials.swap(mats); ctx->glossy = false;
-
-    ctx->scene.node_pairs = ctx->d_node_pairs; ctx->scene.tri_leaf = ctx->d_tri_leaf; ctx->scene.tri_orig = ctx->d_tri_orig; ctx->scene.tri_normal = ctx->d_tri_normal;
-    ctx->scene.materials = ctx->d_materials; ctx->scene.objects = ctx->d_objects; ctx->scene.obj_trace = ctx->d_obj_trace; ctx->scene.lights = ctx->d_lights;
-    ctx->scene.n_objects = sd.n_objects; ctx->scene.n_lights = sd.n_lights; ctx->scene.stack_depth = stack_depth; ctx->scene.n_top_records = n_top_records; ctx->scene.n_pair_records = n_records; ctx->scene.n_small_tris = n_small_tris;
-    ctx->n_materials = sd.n_materials;
-    ctx->has_scene = true;
-    return CGPT_OK;
 }
 
 int EnsureFramebuffer(cgpt_ctx* ctx, uint32_t W, uint32_t H, uint32_t n_rows, const uint32_t key[5])
@@ -532,7 +238,9 @@ int cgpt_scene_upload(cgpt_ctx* ctx, const cgpt_scene_desc* scene)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->scene_generation++;                                                   // the denoiser's guides are stale (denoise.hip)
     try {                                                                      // the re-layout allocates host vectors: nothing may unwind through the C ABI
-        return BuildDeviceScene(ctx, *scene);
+        SceneLayout layout;
+        const int rc = LayoutScene(*scene, layout, ctx->error);
+        return rc != CGPT_OK ? rc : SceneInstall(ctx, layout);
     } catch (const std::exception& e) {
         return Fail(ctx, CGPT_ERR_INVALID, "scene upload: %s", e.what());
     } catch (...) {
@@ -601,6 +309,33 @@ int cgpt_camera_from_view(const float pos[3], const float view_dir[3], float fov
 }  // extern "C"
 
 namespace cgpt {
+
+// The device half of a scene upload: replaces the context's scene by the arrays of `layout` (scene_layout.h).  Only called with a
+// layout that LayoutScene accepted, so a refused scene leaves the previous one installed.
+int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout)
+{
+    FreeScene(ctx);
+    int rc;
+    if ((rc = UploadArray(ctx, &ctx->d_node_pairs, layout.node_pairs)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, &ctx->d_tri_leaf, layout.tri_leaf)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, &ctx->d_tri_orig, layout.tri_orig)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, &ctx->d_tri_normal, layout.tri_normal)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, &ctx->d_materials, layout.materials)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, &ctx->d_objects, layout.objects)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, &ctx->d_obj_trace, layout.obj_trace)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, &ctx->d_lights, layout.lights)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, &ctx->d_refit_levels, layout.refit_levels)) != CGPT_OK) return rc;
+    ctx->h_objects = layout.objects; ctx->refit_objects = layout.refit_objects; ctx->record_perm = layout.record_perm;
+    ctx->h_roughness.assign(layout.n_materials, 0.0f); ctx->h_materials = layout.materials; ctx->glossy = false;
+
+    ctx->scene.node_pairs = ctx->d_node_pairs; ctx->scene.tri_leaf = ctx->d_tri_leaf; ctx->scene.tri_orig = ctx->d_tri_orig; ctx->scene.tri_normal = ctx->d_tri_normal;
+    ctx->scene.materials = ctx->d_materials; ctx->scene.objects = ctx->d_objects; ctx->scene.obj_trace = ctx->d_obj_trace; ctx->scene.lights = ctx->d_lights;
+    ctx->scene.n_objects = (uint32_t)layout.objects.size(); ctx->scene.n_lights = (uint32_t)layout.lights.size(); ctx->scene.stack_depth = layout.stack_depth;
+    ctx->scene.n_top_records = layout.n_top_records; ctx->scene.n_pair_records = layout.n_pair_records; ctx->scene.n_small_tris = layout.n_small_tris;
+    ctx->n_materials = layout.n_materials;
+    ctx->has_scene = true;
+    return CGPT_OK;
+}
 
 int RenderEnqueue(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p)
 {

@@ -2,24 +2,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cstring>
 #include <string>
 #include <vector>
 
 #include "cpugpupt_abi.h"
 #include "device_scene.h"
+#include "scene_layout.h"
 
 namespace cgpt {
 struct DeviceGroup;
-
-// what an in-place edit of the uploaded scene needs of one object (cgpt_abi.hip: BuildDeviceScene fills it, refit.hip reads it)
-struct RefitObject {
-    uint32_t node_count = 0, tri_count = 0;   // as uploaded (a triangle object: 0 and 1)
-    uint32_t leaf_base = 0;                    // first tri_leaf record of the object
-    uint32_t pair_base = 0;                    // first child-pair record of the object before the renumbering (index into record_perm)
-    uint32_t level_begin = 0;                  // first entry of the object's records in d_refit_levels ...
-    std::vector<uint32_t> level_offsets;       // ... records of depth d at [level_begin + level_offsets[d], level_begin + level_offsets[d + 1])
-};
 }  // namespace cgpt
 
 struct cgpt_ctx {
@@ -104,16 +95,9 @@ struct cgpt_ctx {
 
 
 namespace cgpt {
-// obj_trace entry of an object (device_scene.h): what IntersectScene's object loop reads; upload and cgpt_scene_update_primitive
-inline void PackObjTrace(const DevObject& d, float4& q0, float4& q1)
-{
-    auto bits = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
-    q0 = make_float4(bits(d.kind), 0.0f, 0.0f, 0.0f); q1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (d.kind == CGPT_OBJECT_MESH || d.kind == CGPT_OBJECT_TRIANGLE) { q0.x = bits(CGPT_OBJECT_MESH); q0.y = bits(d.root_code); }   // a triangle: a leaf-rooted mesh
-    else if (d.kind == CGPT_OBJECT_SPHERE) { q0.y = d.sphere_center[0]; q0.z = d.sphere_center[1]; q0.w = d.sphere_center[2]; q1.x = d.sphere_radius_sq; }
-    else { q0.y = d.plane_normal[0]; q0.z = d.plane_normal[1]; q0.w = d.plane_normal[2]; q1.x = d.plane_point[0]; q1.y = d.plane_point[1]; q1.z = d.plane_point[2]; }
-}
-
+// the device half of a scene upload (cgpt_abi.hip): frees the context's scene and installs the arrays and bookkeeping of a layout that
+// LayoutScene (scene_layout.h) accepted; the caller has selected the device and drained the stream
+int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout);
 // the two halves of cgpt_render: enqueue the kernels of one context without waiting, then wait and book the timings
 int RenderEnqueue(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p);
 int RenderFinish(cgpt_ctx* ctx);

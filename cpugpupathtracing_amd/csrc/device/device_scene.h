@@ -1,7 +1,7 @@
 // device_scene.h -- how the scene lives in HBM (gfx950), shared by the upload code and the kernels.
 //
 // The C ABI hands over the reference's own AoS layouts (32-byte BVHNode, 72-byte Triangle, 56-byte Material).
-// The upload step (cgpt_abi.hip: BuildDeviceScene) re-lays them for per-lane gathers:
+// The upload's host half (scene_layout.hip: LayoutScene, with the record packers in scene_layout.h) re-lays them for per-lane gathers:
 //
 //  node_pairs  float4[4 * n_pairs]  one 64-byte, 64-byte-aligned record per INNER node = its two children, left / right
 //                                   interleaved per component:

@@ -344,7 +344,17 @@ void GroupDestroy(cgpt_ctx* ctx)
 
 int GroupSceneUpload(cgpt_ctx* ctx, const cgpt_scene_desc* scene)
 {
-    for (cgpt_ctx* m : ctx->group->members) { const int rc = cgpt_scene_upload(m, scene); if (rc != CGPT_OK) return Propagate(ctx, m, rc); }
+    // laid out once (a refusal touches no member's scene), installed on every member in rank order as its cgpt_scene_upload would
+    cgpt_ctx* first = ctx->group->members[0];
+    if (!scene) return Propagate(ctx, first, CtxFail(first, CGPT_ERR_INVALID, "scene is null"));
+    SceneLayout layout;
+    int rc = LayoutScene(*scene, layout, first->error);
+    if (rc != CGPT_OK) return Propagate(ctx, first, rc);
+    for (cgpt_ctx* m : ctx->group->members) {
+        if ((rc = cgpt_synchronize(m)) != CGPT_OK) return Propagate(ctx, m, rc);   // selects the member's device and drains its stream
+        m->scene_generation++;
+        if ((rc = SceneInstall(m, layout)) != CGPT_OK) return Propagate(ctx, m, rc);
+    }
     ctx->has_scene = true;
     return CGPT_OK;
 }

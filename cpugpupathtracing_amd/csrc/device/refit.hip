@@ -7,9 +7,9 @@
 // order by std::min / std::max.  For an inner node that equals min_std(left, right) / max_std(left, right) of its children in every
 // bit (signed zeros, NaN, values beyond 1e30 included): the left range comes first and a tie keeps the first operand.  So:
 //   * triangle pass (refit_triangles): one thread per leaf slot of the object.  Its tri_leaf record names the triangle (tri_idx),
-//     which the thread gathers from the staging copy of the host triangles; it rewrites v0 / e1 / e2 (PackLeafTri's subtraction),
+//     which the thread gathers from the staging copy of the host triangles; it rewrites v0 / e1 / e2 (scene_layout.h: PackLeafTri's subtraction),
 //     keeps tri_idx, last_in_leaf and the pad word, and writes the original-order record (tri_orig) and tri_normal;
-//   * bound pass (refit_level): the object's child-pair records grouped by depth at upload (BuildDeviceScene), one launch per level,
+//   * bound pass (refit_level): the object's child-pair records grouped by depth at upload (scene_layout.hip: LayoutScene), one launch per level,
 //     deepest first, a thread per record.  A leaf side folds its triangles' positions from tri_orig (v0 + e1 is not v1 in floating
 //     point); an inner side is the union of the child record's two sides, written by the previous launch (stream order is the only
 //     synchronisation).  The codes float4 is not written.
@@ -28,6 +28,7 @@
 #include "ctx_internal.h"
 #include "device_scene.h"
 #include "minmax_std.h"
+#include "scene_layout.h"
 
 namespace cgpt {
 

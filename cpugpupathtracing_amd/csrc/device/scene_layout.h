@@ -1,0 +1,77 @@
+// scene_layout.h -- the host half of a scene upload: the reference's AoS scene (cgpt_scene_desc) validated and re-laid into the
+// device layout of device_scene.h, as plain host vectors.  No HIP runtime call and no context: cgpt_abi.hip (SceneInstall) and
+// multi_gpu.hip copy the result to their devices, cgpth_scene_layout (cpugpupt_host.h) shows it to the CPU tests.
+// The record packers are here too: the in-place edits (material and roughness updates, refit.hip) write the same records.
+#pragma once
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "cpugpupt_abi.h"
+#include "device_scene.h"
+
+namespace cgpt {
+
+// what an in-place edit of the uploaded scene needs of one object (LayoutScene fills it, refit.hip reads it)
+struct RefitObject {
+    uint32_t node_count = 0, tri_count = 0;   // as uploaded (a triangle object: 0 and 1)
+    uint32_t leaf_base = 0;                    // first tri_leaf record of the object
+    uint32_t pair_base = 0;                    // first child-pair record of the object before the renumbering (index into record_perm)
+    uint32_t level_begin = 0;                  // first entry of the object's records in refit_levels ...
+    std::vector<uint32_t> level_offsets;       // ... records of depth d at [level_begin + level_offsets[d], level_begin + level_offsets[d + 1])
+};
+
+struct SceneLayout {
+    // the arrays of device_scene.h, and each mesh's child-pair records grouped by depth (refit.hip's bound pass)
+    std::vector<float4> node_pairs, tri_leaf, tri_orig, tri_normal, materials;
+    std::vector<DevObject> objects;
+    std::vector<float4> obj_trace;
+    std::vector<uint32_t> lights;
+    std::vector<uint32_t> refit_levels;
+    // host bookkeeping of the in-place edits
+    std::vector<RefitObject> refit_objects;
+    std::vector<uint32_t> record_perm;         // record index in the reference's depth-first order -> index in node_pairs
+    uint32_t stack_depth = 0, n_top_records = 0, n_pair_records = 0, n_small_tris = 0, n_materials = 0;
+};
+
+// Validates everything a kernel will index with (a malformed tree must fail here, not fault on the GPU) and fills `out`.
+// CGPT_OK, or CGPT_ERR_INVALID / CGPT_ERR_UNSUPPORTED with the reason in `error`; `out` is only meaningful on CGPT_OK.
+int LayoutScene(const cgpt_scene_desc& sd, SceneLayout& out, std::string& error);
+
+inline float AsFloat(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+
+// roughness: the specular lobe's (cgpt_scene_update_roughness); the record holds alpha = roughness^2, formed here once
+inline void PackMaterial(const cgpt_material& m, float roughness, float4 out[4])
+{
+    out[0] = make_float4(m.albedo[0], m.albedo[1], m.albedo[2], m.specular);
+    out[1] = make_float4(m.refractivity, m.absorption[0], m.absorption[1], m.absorption[2]);
+    out[2] = make_float4(m.ior, m.emissive[0], m.emissive[1], m.emissive[2]);
+    out[3] = make_float4(m.intensity, AsFloat(m.is_light ? 1u : 0u), roughness * roughness, 0.0f);
+}
+
+// leaf-ordered triangle record (device_scene.h: tri_leaf) and original-order record (tri_orig) of one triangle
+inline void PackLeafTri(const cgpt_triangle& tr, uint32_t tri_idx, float4 rec[3])
+{
+    const float e1[3] = { tr.v1.pos[0] - tr.v0.pos[0], tr.v1.pos[1] - tr.v0.pos[1], tr.v1.pos[2] - tr.v0.pos[2] };   // ref: Primitives.cpp:9
+    const float e2[3] = { tr.v2.pos[0] - tr.v0.pos[0], tr.v2.pos[1] - tr.v0.pos[1], tr.v2.pos[2] - tr.v0.pos[2] };   // ref: Primitives.cpp:10
+    rec[0] = make_float4(tr.v0.pos[0], tr.v0.pos[1], tr.v0.pos[2], e1[0]);
+    rec[1] = make_float4(e1[1], e1[2], e2[0], e2[1]);
+    rec[2] = make_float4(0.0f, e2[2], AsFloat(tri_idx), AsFloat(0u));                               // last_in_leaf set by the caller
+}
+inline void PackOrigTri(const cgpt_triangle& tr, float4 rec[3])
+{
+    rec[0] = make_float4(tr.v0.pos[0], tr.v0.pos[1], tr.v0.pos[2], tr.v0.normal[0]);
+    rec[1] = make_float4(tr.v1.pos[0], tr.v1.pos[1], tr.v1.pos[2], tr.v0.normal[1]);
+    rec[2] = make_float4(tr.v2.pos[0], tr.v2.pos[1], tr.v2.pos[2], tr.v0.normal[2]);
+}
+
+// obj_trace entry of an object (device_scene.h): what IntersectScene's object loop reads; upload and cgpt_scene_update_primitive
+inline void PackObjTrace(const DevObject& d, float4& q0, float4& q1)
+{
+    q0 = make_float4(AsFloat(d.kind), 0.0f, 0.0f, 0.0f); q1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (d.kind == CGPT_OBJECT_MESH || d.kind == CGPT_OBJECT_TRIANGLE) { q0.x = AsFloat(CGPT_OBJECT_MESH); q0.y = AsFloat(d.root_code); }   // a triangle: a leaf-rooted mesh
+    else if (d.kind == CGPT_OBJECT_SPHERE) { q0.y = d.sphere_center[0]; q0.z = d.sphere_center[1]; q0.w = d.sphere_center[2]; q1.x = d.sphere_radius_sq; }
+    else { q0.y = d.plane_normal[0]; q0.z = d.plane_normal[1]; q0.w = d.plane_normal[2]; q1.x = d.plane_point[0]; q1.y = d.plane_point[1]; q1.z = d.plane_point[2]; }
+}
+
+}  // namespace cgpt

@@ -50,6 +50,11 @@ R Guarded(R on_error, F&& body) noexcept
 }
 }  // namespace
 
+namespace cgpt {
+// for cgpth_scene_layout, the one entry point of cpugpupt_host.h that lives beside the device code (csrc/device/scene_layout.hip)
+void HostSetError(const char* msg) { try { g_error = msg; } catch (...) {} }
+}  // namespace cgpt
+
 extern "C" {
 
 const char* cgpth_last_error(void) { return g_error.c_str(); }

@@ -98,6 +98,30 @@ int cgpth_read_accumulator(const char* path, float* accumulator_rgba, uint32_t* 
  * the host: equals n / d for every 32-bit n and every d >= 1 (tests/test_host.py checks it against integer division) */
 uint32_t cgpth_fast_div(uint32_t n, uint32_t d);
 
+/* the device layout a cgpt_scene_upload of `scene` would install (csrc/device/device_scene.h), computed on the host with the same
+ * validation, status and message (from cgpth_last_error()) as the upload; no GPU is touched.  tests/test_host_scene_layout.py checks
+ * it against the layout's documentation.  The arrays live in thread-local storage of the library and stay valid until the next
+ * call on the same thread.  Counts are elements: float4s (4 floats) for the float arrays, object_size bytes for `objects`. */
+typedef struct cgpth_scene_layout_view {
+    const float* node_pairs; size_t n_node_pairs;
+    const float* tri_leaf; size_t n_tri_leaf;
+    const float* tri_orig; size_t n_tri_orig;
+    const float* tri_normal; size_t n_tri_normal;
+    const float* materials; size_t n_materials;
+    const float* obj_trace; size_t n_obj_trace;
+    const void* objects; size_t n_objects; size_t object_size;     /* DevObject records */
+    const uint32_t* lights; size_t n_lights;
+    const uint32_t* refit_levels; size_t n_refit_levels;
+    const uint32_t* record_perm; size_t n_record_perm;             /* child-pair record in the input's node order -> index in node_pairs */
+    uint32_t stack_depth, n_top_records, n_pair_records, n_small_tris;
+    /* per object (n_objects each): first tri_leaf record, first child-pair record before the renumbering (index into record_perm),
+     * first entry in refit_levels; object i's records of depth d are refit_levels[level_begin[i] + o[d] .. level_begin[i] + o[d + 1])
+     * with o = level_offsets + level_offsets_start[i], which has level_offsets_start[i + 1] - level_offsets_start[i] entries */
+    const uint32_t* leaf_base; const uint32_t* pair_base; const uint32_t* level_begin;
+    const uint32_t* level_offsets; const uint32_t* level_offsets_start;
+} cgpth_scene_layout_view;
+int cgpth_scene_layout(const cgpt_scene_desc* scene, cgpth_scene_layout_view* out);
+
 #ifdef __cplusplus
 }
 #endif
