@@ -19,6 +19,7 @@ KERNEL_AUTO, KERNEL_MEGAKERNEL, KERNEL_WAVEFRONT, KERNEL_PERSISTENT = 0, 1, 2, 3
 RENDER_COUNTERS = 1
 CTX_FORCE_COLLECTIVE, CTX_GATHER_PEER_COPY = 1, 2
 BUILD_NAIVE, BUILD_SAH_INTERVALS, BUILD_SAH_PRIMITIVES = 0, 1, 2
+BUILD_SAH_BINNED = 3        # not in the reference: 16 bins per axis, stable partition (include/cpugpupt_abi.h)
 DENOISE_DEMODULATE_ALBEDO = 1
 
 f3 = C.c_float * 3

@@ -1,4 +1,5 @@
-// bvh_build.hip -- GPU BVH::Build / BVH::Rebuild for the reference's three BuildOptions, bit-identical to the host build.
+// bvh_build.hip -- GPU BVH::Build / BVH::Rebuild for the reference's three BuildOptions, bit-identical to the host build,
+// and for CGPT_BUILD_SAH_BINNED (not in the reference; see "BuildOption_SAHBinned" below), word for word the host mirror's tree.
 //
 // Options (ref: Source/BVH.cpp:204-297): SAH split intervals (the default, BVH.h:43-44; described below), naive split (midpoint of the
 // longest axis, stop at <= 2 triangles, :208-224 -- the same level kernels with the 24-candidate sweep replaced by one plane), and
@@ -544,6 +545,325 @@ __global__ void __launch_bounds__(64) wide_children(BuildArrays A, uint32_t leve
     A.nodes[node_id].left = left_id;
 }
 
+// ---- BuildOption_SAHBinned (not in the reference; specification: csrc/host/mesh_bvh.cpp BuildTreeBinned, include/cpugpupt_abi.h) ----------
+// One read of a node's triangles per level: each goes into one of 16 centroid bins per axis; a bin keeps a count, the union of its
+// triangles' boxes and the bounds of their centroids.  The 45 candidates (axis outer, s = 1..15 inner, left = bins [0, s)), the leaf
+// test, the children's boxes and the children's centroid bounds all come from the bins; the triangles are read once more by the
+// stable partition.  Every bound is folded as a KEY under the total order on floats in which -0 < +0 (negative floats: all bits
+// flipped, the others: the sign bit), with integer atomicMin / atomicMax in LDS: the fold does not depend on the order of the
+// operands, down to the sign of a zero, so there is no ordered reduction and no piece-ordered combination anywhere below.  (Float LDS
+// min / max treat -0 and +0 as equal: not this order.)
+// Level shapes as for the other options: a workgroup / a wavefront / a quarter wavefront per node (binned_level<G>), and for the few
+// huge nodes at the top many workgroups per node (binned_wide_*): each bins its piece in LDS and issues one global atomic per word
+// of a non-empty bin; one wavefront per node then sweeps, decides, creates the children and prefixes the pieces' left counts.
+// The node counter is taken once per wavefront for all the children it creates (binned_sweep), and the tree's depth is the number of
+// levels, read off by the driver: no per-node atomic on a single word.
+constexpr uint32_t kBins = 16;
+constexpr uint32_t kBinWords = 13;                           // count, box lo[3], box hi[3], centroid lo[3], centroid hi[3]
+constexpr uint32_t kNodeBinWords = 3 * kBins * kBinWords;    // 624 words = 2496 bytes per node
+constexpr uint32_t kBinnedCandidates = 3 * (kBins - 1);
+
+__device__ inline uint32_t order_key(float f)
+{
+    const uint32_t u = __float_as_uint(f);
+    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ inline float key_float(uint32_t k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
+// a product that is not below 16 (the last bin's upper edge, an overflowed scale) is bin 15; c >= lo always
+__device__ inline uint32_t bin_of(float c, float lo, float scale)
+{
+    const float f = (c - lo) * scale;
+    return f < 16.0f ? (uint32_t)f : kBins - 1u;
+}
+__device__ inline bool bin_word_is_min(uint32_t field) { return (field >= 1u && field <= 3u) || (field >= 7u && field <= 9u); }
+
+struct BinnedDecision { uint32_t split, axis, s, n_left; float lo, scale; };
+struct BinnedArrays {
+    Bounds* cbounds;             // per BuildNode: the bounds of its triangles' centroids
+    uint32_t* root_keys;         // [12]: root box and centroid bounds as keys, the lower bounds complemented (every word folds with max from 0)
+    // wide levels only (index j = node of the level, b = piece of the node)
+    uint32_t* gbins;             // [j][kNodeBinWords]
+    uint32_t* piece_count;       // [j][b][3 * kBins]: the piece's bin counts
+    uint32_t* piece_left;        // [j][b]: lefts before the piece
+    BinnedDecision* decision;    // [j]
+};
+struct BinScale { F3 lo; F3 scale; uint32_t usable; };       // usable: bit a = axis a has a positive centroid extent
+__device__ inline BinScale bin_scale(const Bounds& cb)
+{
+    BinScale q;
+    q.lo = cb.lo; q.usable = 0u; q.scale = { 0.0f, 0.0f, 0.0f };
+    if (cb.hi.x > cb.lo.x) { q.usable |= 1u; q.scale.x = 16.0f / (cb.hi.x - cb.lo.x); }
+    if (cb.hi.y > cb.lo.y) { q.usable |= 2u; q.scale.y = 16.0f / (cb.hi.y - cb.lo.y); }
+    if (cb.hi.z > cb.lo.z) { q.usable |= 4u; q.scale.z = 16.0f / (cb.hi.z - cb.lo.z); }
+    return q;
+}
+__device__ inline void bins_clear(uint32_t* bins, uint32_t t, uint32_t stride)
+{
+    for (uint32_t w = t; w < kNodeBinWords; w += stride) bins[w] = bin_word_is_min(w % kBinWords) ? 0xFFFFFFFFu : 0u;
+}
+// one triangle into its bin of every usable axis (LDS atomics)
+__device__ inline void bins_add(uint32_t* bins, const BuildArrays& A, uint32_t tri, const BinScale& q)
+{
+    const F3 lo = A.tri_lo[tri], hi = A.tri_hi[tri], c = A.centroid[tri];
+    const uint32_t k[12] = { order_key(lo.x), order_key(lo.y), order_key(lo.z), order_key(hi.x), order_key(hi.y), order_key(hi.z),
+                             order_key(c.x), order_key(c.y), order_key(c.z), order_key(c.x), order_key(c.y), order_key(c.z) };
+#pragma unroll
+    for (uint32_t a = 0; a < 3; ++a) {
+        if (!(q.usable & (1u << a))) continue;
+        uint32_t* const w = bins + (a * kBins + bin_of(axis_of(c, a), axis_of(q.lo, a), axis_of(q.scale, a))) * kBinWords;
+        atomicAdd(w, 1u);
+#pragma unroll
+        for (uint32_t f = 0; f < 12; ++f) {
+            if (bin_word_is_min(f + 1u)) atomicMin(w + 1u + f, k[f]); else atomicMax(w + 1u + f, k[f]);
+        }
+    }
+}
+
+struct BinSide { uint32_t count; uint32_t k[12]; };          // k: a bin's twelve bound words
+__device__ inline void side_add(BinSide& s, const uint32_t* w)
+{
+    s.count += w[0];
+#pragma unroll
+    for (uint32_t f = 0; f < 12; ++f) s.k[f] = bin_word_is_min(f + 1u) ? min(s.k[f], w[1u + f]) : max(s.k[f], w[1u + f]);
+}
+__device__ inline BinSide side_empty()
+{
+    BinSide s; s.count = 0u;
+#pragma unroll
+    for (uint32_t f = 0; f < 12; ++f) s.k[f] = bin_word_is_min(f + 1u) ? 0xFFFFFFFFu : 0u;
+    return s;
+}
+__device__ inline float side_half_area(const BinSide& s)
+{
+    return half_area({ key_float(s.k[0]), key_float(s.k[1]), key_float(s.k[2]) }, { key_float(s.k[3]), key_float(s.k[4]), key_float(s.k[5]) });
+}
+
+// The sweep of one node by the W lanes t = 0 .. W-1 of one wavefront (W = 64 or 16): lane t evaluates candidates t, t + W, ...; the
+// cheapest (lowest candidate number among equals = the first strictly cheaper in axis-outer, s-inner order) is found with a butterfly.
+// Costs are sums of non-negative products, never NaN, so their bit patterns compare as the floats do.  Every lane returns the
+// decision; the lane that evaluated the winner creates the children from its two sides.
+template <uint32_t W>
+__device__ inline BinnedDecision binned_sweep(const uint32_t* bins, uint32_t t, const BuildArrays& A, const BinnedArrays& Bn, uint32_t node_id,
+                                              const BuildNode& node, const BinScale& q)
+{
+    BinSide best_l = side_empty(), best_r = side_empty();
+    uint32_t best_cost = 0x7F800000u, best_c = 0xFFFFFFFFu;                     // +inf, none
+    for (uint32_t c = t; c < kBinnedCandidates; c += W) {
+        const uint32_t a = c / (kBins - 1u), s = c % (kBins - 1u) + 1u;
+        const uint32_t* const w = bins + a * kBins * kBinWords;
+        BinSide l = side_empty(), r = side_empty();
+        for (uint32_t b = 0; b < s; ++b) side_add(l, w + b * kBinWords);        // an empty bin is the identity
+        for (uint32_t b = s; b < kBins; ++b) side_add(r, w + b * kBinWords);
+        if (l.count == 0u || r.count == 0u) continue;
+        const float cost = (float)l.count * side_half_area(l) + (float)r.count * side_half_area(r);
+        if (cost < __uint_as_float(best_cost)) { best_cost = __float_as_uint(cost); best_c = c; best_l = l; best_r = r; }
+    }
+    uint32_t win_cost = best_cost, win_c = best_c;
+    for (int off = (int)W / 2; off > 0; off >>= 1) {
+        const uint32_t o_cost = __shfl_xor(win_cost, off, (int)W), o_c = __shfl_xor(win_c, off, (int)W);
+        if (o_cost < win_cost || (o_cost == win_cost && o_c < win_c)) { win_cost = o_cost; win_c = o_c; }
+    }
+    BinnedDecision d{};
+    d.split = (__uint_as_float(win_cost) < half_area(node.lo, node.hi) * (float)node.count) ? 1u : 0u;     // ref: BVH.cpp:253; no candidate: +inf
+    if (d.split == 0u) return d;
+    d.axis = win_c / (kBins - 1u); d.s = win_c % (kBins - 1u) + 1u;
+    d.lo = axis_of(q.lo, d.axis); d.scale = axis_of(q.scale, d.axis);
+    d.n_left = __shfl(best_l.count, (int)(win_c % W), (int)W);
+    if (best_c == win_c) {                                                      // exactly one lane per node: candidate numbers are distinct
+        // One returning atomic on the node counter per wavefront, not per node: the lanes in this branch are the winners of the
+        // wavefront's splitting nodes (four nodes per wavefront in the deepest levels, where a level creates hundreds of thousands of
+        // nodes and a single word takes some 90 returning atomics per microsecond).  Ids inside a level are in no particular order anyway.
+        const uint64_t winners = __ballot(1);
+        const uint32_t lane = threadIdx.x & 63u;
+        uint32_t base = 0;
+        if (lane == (uint32_t)__ffsll((long long)winners) - 1u) base = atomicAdd(&A.counters[0], 2u * (uint32_t)__popcll(winners));
+        base = __builtin_amdgcn_readfirstlane(base);                            // the first active lane is the one that asked
+        const uint32_t left_id = base + 2u * (uint32_t)__popcll(winners & ((1ull << lane) - 1ull));
+        BuildNode l{}, r{};
+        l.lo = { key_float(best_l.k[0]), key_float(best_l.k[1]), key_float(best_l.k[2]) }; l.hi = { key_float(best_l.k[3]), key_float(best_l.k[4]), key_float(best_l.k[5]) };
+        r.lo = { key_float(best_r.k[0]), key_float(best_r.k[1]), key_float(best_r.k[2]) }; r.hi = { key_float(best_r.k[3]), key_float(best_r.k[4]), key_float(best_r.k[5]) };
+        l.first = node.first; l.count = best_l.count; l.depth = node.depth + 1u;
+        r.first = node.first + best_l.count; r.count = best_r.count; r.depth = node.depth + 1u;
+        A.nodes[left_id] = l; A.nodes[left_id + 1u] = r;
+        Bn.cbounds[left_id] = { { key_float(best_l.k[6]), key_float(best_l.k[7]), key_float(best_l.k[8]) }, { key_float(best_l.k[9]), key_float(best_l.k[10]), key_float(best_l.k[11]) } };
+        Bn.cbounds[left_id + 1u] = { { key_float(best_r.k[6]), key_float(best_r.k[7]), key_float(best_r.k[8]) }, { key_float(best_r.k[9]), key_float(best_r.k[10]), key_float(best_r.k[11]) } };
+        A.nodes[node_id].left = left_id;
+    }
+    return d;
+}
+
+// One tile of the stable partition: position p of the node (valid lanes only) goes to the front in the order of the lefts, or behind
+// the n_left lefts in the order of the rights.  `run`: lefts before the tile.
+template <uint32_t G>
+__device__ inline void binned_scatter_tile(const BuildArrays& A, const BinnedDecision& d, const uint32_t* idx, uint32_t* out, uint32_t p, bool valid,
+                                           uint32_t& run, uint32_t* s_u32)
+{
+    const uint32_t tri = valid ? idx[p] : 0u;
+    const uint32_t is_left = (valid && bin_of(axis_of(A.centroid[tri], d.axis), d.lo, d.scale) < d.s) ? 1u : 0u;
+    uint32_t total = 0;
+    const uint32_t lefts_before = run + group_exclusive_scan<G>(is_left, s_u32, &total);
+    if (valid) out[is_left ? lefts_before : d.n_left + (p - lefts_before)] = tri;
+    run += total;
+}
+
+template <uint32_t G>
+__global__ void __launch_bounds__(kBuildThreads) binned_level(BuildArrays A, BinnedArrays Bn, uint32_t level_first, uint32_t level_count)
+{
+    constexpr uint32_t groups = kBuildThreads / G, W = G < 64u ? G : 64u;
+    __shared__ uint32_t s_bins[groups * kNodeBinWords];
+    __shared__ uint32_t s_u32[5];
+    __shared__ BinnedDecision s_decision;
+
+    const uint32_t group = threadIdx.x / G, in_level = blockIdx.x * groups + group, t = threadIdx.x % G;
+    if (in_level >= level_count) return;                                       // group-uniform
+    const uint32_t node_id = level_first + in_level;
+    const BuildNode node = A.nodes[node_id];
+    const uint32_t n = node.count;
+    if (n == 1u) return;                                                        // one centroid: no axis has an extent, no candidate
+    const BinScale q = bin_scale(Bn.cbounds[node_id]);
+    if (q.usable == 0u) return;
+    uint32_t* const bins = s_bins + group * kNodeBinWords;
+    uint32_t* const idx = A.tri_indices + node.first;
+
+    bins_clear(bins, t, G);
+    group_sync<G>();
+    for (uint32_t i = t; i < n; i += G) bins_add(bins, A, idx[i], q);
+    group_sync<G>();
+
+    BinnedDecision d{};
+    if (G == kBuildThreads) {                                                   // the first wavefront sweeps
+        if (t < W) { d = binned_sweep<W>(bins, t, A, Bn, node_id, node, q); if (t == 0) s_decision = d; }
+        __syncthreads();
+        d = s_decision;
+    } else {
+        d = binned_sweep<W>(bins, t, A, Bn, node_id, node, q);
+    }
+    if (d.split == 0u) return;                                                  // leaf
+
+    uint32_t* const out = A.scratch_idx + node.first;
+    uint32_t run = 0;
+    for (uint32_t base = 0; base < n; base += G) binned_scatter_tile<G>(A, d, idx, out, base + t, base + t < n, run, s_u32);
+    group_sync<G>();                                                            // every read of the old order is done
+    for (uint32_t p = t; p < n; p += G) idx[p] = out[p];
+}
+
+__device__ inline void binned_piece(const BuildNode& node, uint32_t pieces, uint32_t b, uint32_t& p0, uint32_t& p1)
+{
+    const uint32_t per_piece = (node.count + pieces - 1u) / pieces;
+    p0 = min(b * per_piece, node.count); p1 = min(p0 + per_piece, node.count);
+}
+
+__global__ void binned_wide_clear(uint32_t* gbins, uint32_t n_words)
+{
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w < n_words) gbins[w] = bin_word_is_min(w % kBinWords) ? 0xFFFFFFFFu : 0u;
+}
+
+__global__ void __launch_bounds__(kBuildThreads) binned_wide_hist(BuildArrays A, BinnedArrays Bn, uint32_t level_first, uint32_t pieces)
+{
+    __shared__ uint32_t s_bins[kNodeBinWords];
+    const uint32_t j = blockIdx.x / pieces, b = blockIdx.x - j * pieces;
+    const BuildNode node = A.nodes[level_first + j];
+    const BinScale q = bin_scale(Bn.cbounds[level_first + j]);
+    uint32_t p0, p1;
+    binned_piece(node, pieces, b, p0, p1);
+    const uint32_t* const idx = A.tri_indices + node.first;
+    bins_clear(s_bins, threadIdx.x, kBuildThreads);
+    __syncthreads();
+    for (uint32_t p = p0 + threadIdx.x; p < p1; p += kBuildThreads) bins_add(s_bins, A, idx[p], q);
+    __syncthreads();
+    uint32_t* const g = Bn.gbins + (size_t)j * kNodeBinWords;
+    for (uint32_t w = threadIdx.x; w < kNodeBinWords; w += kBuildThreads) {
+        const uint32_t bin = w / kBinWords, field = w - bin * kBinWords;
+        const uint32_t count = s_bins[bin * kBinWords];
+        if (field == 0u) Bn.piece_count[((size_t)j * pieces + b) * (3u * kBins) + bin] = count;
+        if (count == 0u) continue;                                              // one global atomic per word of a non-empty bin
+        if (field == 0u) atomicAdd(g + w, count);
+        else if (bin_word_is_min(field)) atomicMin(g + w, s_bins[w]);
+        else atomicMax(g + w, s_bins[w]);
+    }
+}
+
+__global__ void __launch_bounds__(64) binned_wide_decide(BuildArrays A, BinnedArrays Bn, uint32_t level_first, uint32_t pieces)
+{
+    __shared__ uint32_t s_bins[kNodeBinWords];
+    const uint32_t j = blockIdx.x, node_id = level_first + j, t = threadIdx.x;
+    const BuildNode node = A.nodes[node_id];
+    const BinScale q = bin_scale(Bn.cbounds[node_id]);
+    for (uint32_t w = t; w < kNodeBinWords; w += 64u) s_bins[w] = Bn.gbins[(size_t)j * kNodeBinWords + w];
+    __syncthreads();
+    const BinnedDecision d = binned_sweep<64>(s_bins, t, A, Bn, node_id, node, q);
+    if (t == 0) Bn.decision[j] = d;
+    if (d.split == 0u) return;
+    uint32_t run = 0;                                                           // lefts before each piece, for the partition
+    for (uint32_t base = 0; base < pieces; base += 64u) {
+        const uint32_t b = base + t;
+        uint32_t lefts = 0;
+        if (b < pieces) for (uint32_t k = 0; k < d.s; ++k) lefts += Bn.piece_count[((size_t)j * pieces + b) * (3u * kBins) + d.axis * kBins + k];
+        uint32_t total = 0;
+        const uint32_t before = group_exclusive_scan<64>(lefts, nullptr, &total);
+        if (b < pieces) Bn.piece_left[(size_t)j * pieces + b] = run + before;
+        run += total;
+    }
+}
+
+__global__ void __launch_bounds__(kBuildThreads) binned_wide_scatter(BuildArrays A, BinnedArrays Bn, uint32_t level_first, uint32_t pieces)
+{
+    __shared__ uint32_t s_u32[5];
+    const uint32_t j = blockIdx.x / pieces, b = blockIdx.x - j * pieces;
+    const BinnedDecision d = Bn.decision[j];
+    if (d.split == 0u) return;
+    const BuildNode node = A.nodes[level_first + j];
+    uint32_t p0, p1;
+    binned_piece(node, pieces, b, p0, p1);
+    const uint32_t* const idx = A.tri_indices + node.first;
+    uint32_t* const out = A.scratch_idx + node.first;
+    uint32_t run = Bn.piece_left[(size_t)j * pieces + b];
+    for (uint32_t base = p0; base < p1; base += kBuildThreads) binned_scatter_tile<kBuildThreads>(A, d, idx, out, base + threadIdx.x, base + threadIdx.x < p1, run, s_u32);
+}
+
+__global__ void __launch_bounds__(kBuildThreads) binned_wide_copy(BuildArrays A, BinnedArrays Bn, uint32_t level_first, uint32_t pieces)
+{
+    const uint32_t j = blockIdx.x / pieces, b = blockIdx.x - j * pieces;
+    if (Bn.decision[j].split == 0u) return;
+    const BuildNode node = A.nodes[level_first + j];
+    uint32_t p0, p1;
+    binned_piece(node, pieces, b, p0, p1);
+    for (uint32_t p = p0 + threadIdx.x; p < p1; p += kBuildThreads) A.tri_indices[node.first + p] = A.scratch_idx[node.first + p];
+}
+
+// root box and centroid bounds over all triangles (any order): per thread in registers, per wavefront with shuffles, then one global
+// atomicMax per word and wavefront on root_keys (zeroed; the lower bounds are complemented so that every word folds with max)
+__global__ void __launch_bounds__(kBuildThreads) binned_root_fold(BuildArrays A, BinnedArrays Bn, uint32_t n)
+{
+    uint32_t k[12];
+#pragma unroll
+    for (uint32_t f = 0; f < 12; ++f) k[f] = 0u;
+    for (uint32_t i = blockIdx.x * kBuildThreads + threadIdx.x; i < n; i += gridDim.x * kBuildThreads) {
+        const F3 lo = A.tri_lo[i], hi = A.tri_hi[i], c = A.centroid[i];
+        const uint32_t v[12] = { ~order_key(lo.x), ~order_key(lo.y), ~order_key(lo.z), order_key(hi.x), order_key(hi.y), order_key(hi.z),
+                                 ~order_key(c.x), ~order_key(c.y), ~order_key(c.z), order_key(c.x), order_key(c.y), order_key(c.z) };
+#pragma unroll
+        for (uint32_t f = 0; f < 12; ++f) k[f] = max(k[f], v[f]);
+    }
+#pragma unroll
+    for (uint32_t f = 0; f < 12; ++f) {
+        for (int off = 32; off > 0; off >>= 1) k[f] = max(k[f], (uint32_t)__shfl_xor(k[f], off, 64));
+        if ((threadIdx.x & 63u) == 0u) atomicMax(&Bn.root_keys[f], k[f]);
+    }
+}
+__global__ void binned_root_node(BuildArrays A, BinnedArrays Bn, uint32_t n)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const uint32_t* const k = Bn.root_keys;
+    BuildNode root{};
+    root.lo = { key_float(~k[0]), key_float(~k[1]), key_float(~k[2]) }; root.hi = { key_float(k[3]), key_float(k[4]), key_float(k[5]) };
+    root.first = 0; root.count = n; root.depth = 0; root.rank = 0; root.new_id = 0;
+    A.nodes[0] = root;
+    Bn.cbounds[0] = { { key_float(~k[6]), key_float(~k[7]), key_float(~k[8]) }, { key_float(k[9]), key_float(k[10]), key_float(k[11]) } };
+    A.counters[0] = 1u; A.counters[1] = 0u;
+}
+
 // ---- renumbering into the reference's allocation order --------------------------------------------------------------------------
 __global__ void count_splits_level(BuildNode* nodes, uint32_t level_first, uint32_t level_count)
 {
@@ -634,7 +954,17 @@ static int BuildOnDevice(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t
     if (!triangles || n_tris == 0 || !nodes_out || !n_nodes_out || !tri_indices_out || !max_depth_out || !total_area_out)
         return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: null argument or empty mesh");
     if (n_tris > 0x3FFFFFFFu) return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: too many triangles");
-    if (build_option > CGPT_BUILD_SAH_SPLIT_PRIMITIVES) return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: unknown build option %u", build_option);
+    if (build_option > CGPT_BUILD_SAH_BINNED) return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: unknown build option %u", build_option);
+    const bool binned = build_option == CGPT_BUILD_SAH_BINNED;
+    if (binned) {                                                             // its input domain (include/cpugpupt_abi.h): the bin index must stay defined
+        for (uint32_t i = 0; i < n_tris; ++i) {
+            const cgpt_vertex* const v[3] = { &triangles[i].v0, &triangles[i].v1, &triangles[i].v2 };
+            for (int k = 0; k < 3; ++k)
+                for (int a = 0; a < 3; ++a)
+                    if (!(fabsf(v[k]->pos[a]) <= 1e30f))
+                        return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: the binned build needs finite positions of magnitude <= 1e30 (triangle %u)", i);
+        }
+    }
     if (initial_tri_indices) {                                                // a Rebuild's starting order must be a permutation: the kernels index with it
         std::vector<uint8_t> seen(n_tris, 0);
         for (uint32_t i = 0; i < n_tris; ++i) {
@@ -657,6 +987,8 @@ static int BuildOnDevice(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t
     uint32_t *d_idx = nullptr, *d_scratch = nullptr, *d_sa = nullptr, *d_sb = nullptr, *d_counters = nullptr;
     BuildNode* d_nodes = nullptr; cgpt_bvh_node* d_out = nullptr;
     WidePartial* d_partial = nullptr; WideDecision* d_decision = nullptr; uint32_t *d_piece_left = nullptr, *d_piece_front = nullptr; WideChild* d_piece_child = nullptr;
+    Bounds* d_cbounds = nullptr; uint32_t *d_root_keys = nullptr, *d_gbins = nullptr, *d_piece_count = nullptr; BinnedDecision* d_bdecision = nullptr;
+    BinnedArrays Bn{};
     uint32_t quarter_tris = 32;                                               // ... and one quarter wavefront per node
     uint32_t wave_tris = 2048;                                                // average triangles per node up to which a level runs one wavefront per node
     uint32_t piece_tris = 512;                                                // average triangles per piece below which a level goes to one workgroup per node
@@ -671,14 +1003,23 @@ static int BuildOnDevice(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t
         BV_TRY(hipMalloc((void**)&d_hi, (size_t)n_tris * sizeof(F3)));
         BV_TRY(hipMalloc((void**)&d_c, (size_t)n_tris * sizeof(F3)));
         BV_TRY(hipMalloc((void**)&d_idx, (size_t)n_tris * 4)); BV_TRY(hipMalloc((void**)&d_scratch, (size_t)n_tris * 4));
-        BV_TRY(hipMalloc((void**)&d_sa, (size_t)n_tris * 4)); BV_TRY(hipMalloc((void**)&d_sb, (size_t)n_tris * 4));
+        if (!binned) { BV_TRY(hipMalloc((void**)&d_sa, (size_t)n_tris * 4)); BV_TRY(hipMalloc((void**)&d_sb, (size_t)n_tris * 4)); }
         BV_TRY(hipMalloc((void**)&d_counters, 2 * 4));
         BV_TRY(hipMalloc((void**)&d_nodes, (size_t)max_nodes * sizeof(BuildNode)));
         BV_TRY(hipMalloc((void**)&d_out, (size_t)max_nodes * sizeof(cgpt_bvh_node)));
-        BV_TRY(hipMalloc((void**)&d_partial, (size_t)kWideBlocks * kCandidates * sizeof(WidePartial)));
-        BV_TRY(hipMalloc((void**)&d_decision, (size_t)kWideBlocks * sizeof(WideDecision)));
-        BV_TRY(hipMalloc((void**)&d_piece_left, (size_t)kWideBlocks * 4)); BV_TRY(hipMalloc((void**)&d_piece_front, (size_t)kWideBlocks * 4));
-        BV_TRY(hipMalloc((void**)&d_piece_child, (size_t)kWideBlocks * sizeof(WideChild)));
+        BV_TRY(hipMalloc((void**)&d_piece_left, (size_t)kWideBlocks * 4));
+        if (!binned) {
+            BV_TRY(hipMalloc((void**)&d_partial, (size_t)kWideBlocks * kCandidates * sizeof(WidePartial)));
+            BV_TRY(hipMalloc((void**)&d_decision, (size_t)kWideBlocks * sizeof(WideDecision)));
+            BV_TRY(hipMalloc((void**)&d_piece_front, (size_t)kWideBlocks * 4));
+            BV_TRY(hipMalloc((void**)&d_piece_child, (size_t)kWideBlocks * sizeof(WideChild)));
+        } else {
+            BV_TRY(hipMalloc((void**)&d_cbounds, (size_t)max_nodes * sizeof(Bounds)));
+            BV_TRY(hipMalloc((void**)&d_root_keys, 12 * 4));
+            BV_TRY(hipMalloc((void**)&d_gbins, (size_t)kWideBlocks * kNodeBinWords * 4));
+            BV_TRY(hipMalloc((void**)&d_piece_count, (size_t)kWideBlocks * 3 * kBins * 4));
+            BV_TRY(hipMalloc((void**)&d_bdecision, (size_t)kWideBlocks * sizeof(BinnedDecision)));
+        }
         if (const char* e = getenv("CGPT_BVH_WAVE_TRIS")) wave_tris = (uint32_t)std::max(0l, strtol(e, nullptr, 10));     // tests: 0 = workgroups only
         if (const char* e = getenv("CGPT_BVH_QUARTER_TRIS")) quarter_tris = (uint32_t)std::max(0l, strtol(e, nullptr, 10));
         if (const char* e = getenv("CGPT_BVH_PIECE_TRIS")) piece_tris = (uint32_t)std::max(1l, strtol(e, nullptr, 10));   // tests: the wide path on small meshes
@@ -689,7 +1030,14 @@ static int BuildOnDevice(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t
         A.nodes = d_nodes; A.counters = d_counters;
         A.partial = d_partial; A.decision = d_decision; A.piece_left = d_piece_left; A.piece_front = d_piece_front; A.piece_child = d_piece_child;
         hipLaunchKernelGGL(prepare_triangles, dim3((n_tris + 255u) / 256u), dim3(256), 0, stream, d_tris, n_tris, d_lo, d_hi, d_c, d_idx, initial_tri_indices ? 0u : 1u);
-        hipLaunchKernelGGL(root_bounds, dim3(1), dim3(kBuildThreads), 0, stream, A, n_tris);
+        Bn.cbounds = d_cbounds; Bn.root_keys = d_root_keys; Bn.gbins = d_gbins; Bn.piece_count = d_piece_count; Bn.piece_left = d_piece_left; Bn.decision = d_bdecision;
+        if (binned) {
+            BV_TRY(hipMemsetAsync(d_root_keys, 0, 12 * 4, stream));
+            hipLaunchKernelGGL(binned_root_fold, dim3(std::min(1024u, (n_tris + kBuildThreads - 1u) / kBuildThreads)), dim3(kBuildThreads), 0, stream, A, Bn, n_tris);
+            hipLaunchKernelGGL(binned_root_node, dim3(1), dim3(1), 0, stream, A, Bn, n_tris);
+        } else {
+            hipLaunchKernelGGL(root_bounds, dim3(1), dim3(kBuildThreads), 0, stream, A, n_tris);
+        }
         // SAH split primitives (ref: BVH.cpp:260-297): cheapest_cost stays 1e30 because the loop never assigns it (SURVEY A-5), so
         // "cheapest_cost >= parent_cost" ends the build at the root whenever the root's cost is an ordinary number.  A root cost
         // of NaN or beyond 1e30 (bounds near the float limit) would take the reference into Split with the last candidate plane:
@@ -712,7 +1060,22 @@ static int BuildOnDevice(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t
             level_first.push_back(first);
             // few, big nodes: pieces of ~piece_tris triangles or more, at most kWideBlocks of them per level
             const uint32_t pieces = std::min(kWideBlocks / std::min(count, kWideBlocks), std::max(1u, n_tris / count / piece_tris));
-            if (count <= kWideBlocks && pieces >= 2u) {
+            if (binned) {
+                if (count <= kWideBlocks && pieces >= 2u) {
+                    const dim3 grid(count * pieces), per_node(count), block(kBuildThreads);
+                    hipLaunchKernelGGL(binned_wide_clear, dim3((count * kNodeBinWords + 255u) / 256u), dim3(256), 0, stream, d_gbins, count * kNodeBinWords);
+                    hipLaunchKernelGGL(binned_wide_hist, grid, block, 0, stream, A, Bn, first, pieces);
+                    hipLaunchKernelGGL(binned_wide_decide, per_node, dim3(64), 0, stream, A, Bn, first, pieces);
+                    hipLaunchKernelGGL(binned_wide_scatter, grid, block, 0, stream, A, Bn, first, pieces);
+                    hipLaunchKernelGGL(binned_wide_copy, grid, block, 0, stream, A, Bn, first, pieces);
+                } else if ((uint64_t)count * wave_tris < n_tris) {
+                    hipLaunchKernelGGL(binned_level<kBuildThreads>, dim3(count), dim3(kBuildThreads), 0, stream, A, Bn, first, count);
+                } else if ((uint64_t)count * quarter_tris < n_tris) {
+                    hipLaunchKernelGGL(binned_level<64>, dim3((count + 3u) / 4u), dim3(kBuildThreads), 0, stream, A, Bn, first, count);
+                } else {
+                    hipLaunchKernelGGL(binned_level<16>, dim3((count + 15u) / 16u), dim3(kBuildThreads), 0, stream, A, Bn, first, count);
+                }
+            } else if (count <= kWideBlocks && pieces >= 2u) {
                 const dim3 grid(count * pieces), per_node(count), block(kBuildThreads);
                 hipLaunchKernelGGL(wide_sah_partial, grid, block, 0, stream, A, first, pieces);
                 hipLaunchKernelGGL(wide_decide, per_node, dim3(64), 0, stream, A, first, pieces);
@@ -750,7 +1113,7 @@ static int BuildOnDevice(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t
         BV_TRY(hipMemcpyAsync(tri_indices_out, d_idx, (size_t)n_tris * 4, hipMemcpyDeviceToHost, stream));
         BV_TRY(hipStreamSynchronize(stream));
         *n_nodes_out = n_nodes;
-        *max_depth_out = counters[1];
+        *max_depth_out = binned ? (uint32_t)level_first.size() - 2u : counters[1];   // binned: level L holds the nodes of depth L (no atomicMax per node)
         float area = 0.0f;                                                    // m_total_area: a sequential float sum (ref: BVH.cpp:22)
         for (uint32_t i = 0; i < n_tris; ++i) area += HostTriangleArea(triangles[i]);
         *total_area_out = area;
@@ -759,6 +1122,7 @@ done:
     (void)hipFree(d_tris); (void)hipFree(d_lo); (void)hipFree(d_hi); (void)hipFree(d_c); (void)hipFree(d_idx); (void)hipFree(d_scratch);
     (void)hipFree(d_sa); (void)hipFree(d_sb); (void)hipFree(d_counters); (void)hipFree(d_nodes); (void)hipFree(d_out);
     (void)hipFree(d_partial); (void)hipFree(d_decision); (void)hipFree(d_piece_left); (void)hipFree(d_piece_front); (void)hipFree(d_piece_child);
+    (void)hipFree(d_cbounds); (void)hipFree(d_root_keys); (void)hipFree(d_gbins); (void)hipFree(d_piece_count); (void)hipFree(d_bdecision);
 #undef BV_TRY
     return rc;
 }

@@ -190,7 +190,8 @@ int cgpth_scene_add_mesh(cgpth_scene* scene, const cgpth_mesh* mesh, uint32_t ma
         scene->scene.objects.emplace_back("mesh", mesh->mesh, mat_index, (MeshBVH::BuildOption)build_option);
         if (!scene->scene.objects.back().valid) {
             scene->scene.objects.pop_back();
-            return -Fail("mesh is empty or has out-of-range indices");
+            return -Fail(build_option == MeshBVH::BuildOption_SAHBinned ? "mesh is empty, has out-of-range indices, or a position is not finite or beyond 1e30"
+                                                                         : "mesh is empty or has out-of-range indices");
         }
         return (int)scene->scene.objects.size() - 1;
     });
@@ -307,7 +308,8 @@ int cgpth_scene_rebuild_bvh(cgpth_scene* scene, uint32_t obj_index, int build_op
     return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
         if (!scene || obj_index >= scene->scene.objects.size() || !scene->scene.objects[obj_index].has_bvh || !ValidOption(build_option))
             return Fail("bad argument to cgpth_scene_rebuild_bvh");
-        scene->scene.objects[obj_index].bvh.Rebuild((MeshBVH::BuildOption)build_option);
+        if (!scene->scene.objects[obj_index].bvh.Rebuild((MeshBVH::BuildOption)build_option))
+            return Fail("the binned build needs finite positions of magnitude <= 1e30 (the BVH is unchanged)");
         return CGPT_OK;
     });
 }

@@ -6,6 +6,9 @@
 // exact and return the left-most tied operand under any grouping, so no bit changes).
 #include "mesh_bvh.h"
 
+#include <cmath>
+#include <cstring>
+#include <algorithm>
 #include <utility>
 
 namespace cgpt {
@@ -31,7 +34,63 @@ inline float HalfArea(const Vec3& lo, const Vec3& hi)
     return e.x * e.y + e.y * e.z + e.z * e.x;
 }
 
+// BuildOption_SAHBinned folds bounds under the total order on floats in which -0 < +0: the usual monotone map to uint32 (negative
+// floats have all bits flipped, the others the sign bit).  min / max of the keys do not depend on the order of the operands, down to
+// the sign of a zero, which is what lets the device build fold with integer atomics (csrc/device/bvh_build.hip).
+inline uint32_t OrderKey(float f)
+{
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+inline float KeyFloat(uint32_t k)
+{
+    const uint32_t u = k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu);
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+struct KeyBounds {              // a box as keys; empty = (all ones, zero), never converted back
+    uint32_t lo[3] = { ~0u, ~0u, ~0u }, hi[3] = { 0u, 0u, 0u };
+    void Add(const Vec3& l, const Vec3& h)
+    {
+        for (int k = 0; k < 3; ++k) {
+            const uint32_t a = OrderKey(l[k]), b = OrderKey(h[k]);
+            if (a < lo[k]) lo[k] = a;
+            if (b > hi[k]) hi[k] = b;
+        }
+    }
+    void Add(const KeyBounds& o)
+    {
+        for (int k = 0; k < 3; ++k) {
+            if (o.lo[k] < lo[k]) lo[k] = o.lo[k];
+            if (o.hi[k] > hi[k]) hi[k] = o.hi[k];
+        }
+    }
+    Vec3 Lo() const { return { KeyFloat(lo[0]), KeyFloat(lo[1]), KeyFloat(lo[2]) }; }
+    Vec3 Hi() const { return { KeyFloat(hi[0]), KeyFloat(hi[1]), KeyFloat(hi[2]) }; }
+};
+
+constexpr uint32_t kBins = 16;
+// the bin of a centroid coordinate c >= lo; a product that is not below 16 (the last bin's upper edge, an overflowed scale) is bin 15
+inline uint32_t BinOf(float c, float lo, float scale)
+{
+    const float f = (c - lo) * scale;
+    return f < 16.0f ? (uint32_t)f : kBins - 1u;
+}
+
 }  // namespace
+
+bool MeshBVH::InBinnedDomain(const cgpt_triangle* triangles, uint32_t n)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        const cgpt_vertex* v[3] = { &triangles[i].v0, &triangles[i].v1, &triangles[i].v2 };
+        for (int k = 0; k < 3; ++k)
+            for (int a = 0; a < 3; ++a)
+                if (!(fabsf(v[k]->pos[a]) <= 1e30f)) return false;                // NaN fails every comparison
+    }
+    return true;
+}
 
 bool MeshBVH::SetTriangles(const std::vector<cgpt_vertex>& vertices, const std::vector<uint32_t>& indices)
 {
@@ -55,6 +114,11 @@ bool MeshBVH::SetTriangles(const std::vector<cgpt_vertex>& vertices, const std::
         total_area_ += TriangleArea(t);                                       // ref: BVH.cpp:22
         tri_indices_[i] = (uint32_t)i;
         CacheTriangle((uint32_t)i);
+    }
+    if (option_ == BuildOption_SAHBinned && !InBinnedDomain(triangles_.data(), (uint32_t)n)) {
+        triangles_.clear(); tri_indices_.clear(); centroids_.clear(); tri_bounds_.clear();
+        total_area_ = 0.0f;
+        return false;
     }
     nodes_.assign(2 * n - 1, cgpt_bvh_node{});                                // ref: BVH.cpp:37
     return true;
@@ -97,7 +161,7 @@ bool MeshBVH::Build(const std::vector<cgpt_vertex>& vertices, const std::vector<
 {
     option_ = option;
     if (!SetTriangles(vertices, indices)) return false;
-    BuildTree();
+    if (option_ == BuildOption_SAHBinned) BuildTreeBinned(); else BuildTree();
     return true;
 }
 
@@ -153,13 +217,15 @@ bool MeshBVH::RebuildWith(BuildOption option, const TreeBuilder& build)       //
     return true;
 }
 
-void MeshBVH::Rebuild(BuildOption option)
+bool MeshBVH::Rebuild(BuildOption option)
 {
-    if (triangles_.empty()) return;
+    if (triangles_.empty()) return true;
+    if (option == BuildOption_SAHBinned && !InBinnedDomain(triangles_.data(), (uint32_t)triangles_.size())) return false;
     option_ = option;
     nodes_used_ = 0;
     max_depth_ = 0;
-    BuildTree();
+    if (option_ == BuildOption_SAHBinned) BuildTreeBinned(); else BuildTree();
+    return true;
 }
 
 void MeshBVH::FitNode(uint32_t node_index)                                    // ref: BVH.cpp:188-202
@@ -275,6 +341,102 @@ void MeshBVH::BuildTree()
         FitNode(right);
         todo.push_back({ right, w.depth + 1 });                               // left subtree is numbered first
         todo.push_back({ left, w.depth + 1 });
+    }
+}
+
+// ---- BuildOption_SAHBinned (the reference's README, "Planned: Binned BVH build"; the specification of the device build) ----------
+// Per node: the bounds of its triangles' centroids give, per axis with a positive extent, 16 equal bins; each bin keeps a count, the
+// union of its triangles' boxes and the bounds of their centroids.  Candidates: axis outer, split s = 1..15 inner, left = bins [0, s);
+// an empty side is skipped; the reference's cost expression (ref: BVH.cpp:325) and leaf criterion (:253); the first strictly cheaper
+// candidate wins.  The partition is stable and the children's bounds are the unions of the bins on each side, so nothing but the
+// partition reads the triangles a second time.  Every min / max is taken on OrderKey, so no result depends on the order of the fold.
+void MeshBVH::BuildTreeBinned()
+{
+    struct Bin {
+        uint32_t count = 0; KeyBounds box, cen;
+        void Add(const Bin& o) { count += o.count; box.Add(o.box); cen.Add(o.cen); }
+    };
+    struct Work { uint32_t node, depth; KeyBounds cen; };
+
+    const uint32_t n_all = (uint32_t)triangles_.size();
+    std::vector<uint32_t> left_part, right_part;
+    std::vector<Work> todo;
+    {
+        KeyBounds box, cen;
+        for (uint32_t i = 0; i < n_all; ++i) {
+            const uint32_t tri = tri_indices_[i];
+            box.Add(tri_bounds_[tri].lo, tri_bounds_[tri].hi);
+            cen.Add(centroids_[tri], centroids_[tri]);
+        }
+        cgpt_bvh_node& root = nodes_[nodes_used_++];
+        root.left_first = 0;
+        root.prim_count = n_all;
+        const Vec3 lo = box.Lo(), hi = box.Hi();
+        for (int k = 0; k < 3; ++k) { root.aabb_min[k] = lo[k]; root.aabb_max[k] = hi[k]; }
+        todo.push_back({ 0, 0, cen });
+    }
+    while (!todo.empty()) {
+        const Work w = todo.back();
+        todo.pop_back();
+        if (w.depth > max_depth_) max_depth_ = w.depth;
+
+        cgpt_bvh_node& node = nodes_[w.node];
+        const uint32_t first = node.left_first, n = node.prim_count;
+        const Vec3 cmin = w.cen.Lo(), cmax = w.cen.Hi();
+        Bin bins[3][kBins];
+        float scale[3] = { 0.0f, 0.0f, 0.0f };
+        for (uint32_t a = 0; a < 3; ++a)
+            if (cmax[a] > cmin[a]) scale[a] = 16.0f / (cmax[a] - cmin[a]);
+        for (uint32_t i = first; i < first + n; ++i) {
+            const uint32_t tri = tri_indices_[i];
+            for (uint32_t a = 0; a < 3; ++a) {
+                if (!(cmax[a] > cmin[a])) continue;
+                Bin& b = bins[a][BinOf(centroids_[tri][a], cmin[a], scale[a])];
+                ++b.count;
+                b.box.Add(tri_bounds_[tri].lo, tri_bounds_[tri].hi);
+                b.cen.Add(centroids_[tri], centroids_[tri]);
+            }
+        }
+
+        float best = INFINITY;
+        uint32_t best_axis = 0, best_s = 0;
+        Bin best_l, best_r;
+        for (uint32_t a = 0; a < 3; ++a) {
+            if (!(cmax[a] > cmin[a])) continue;
+            Bin suffix[kBins + 1];                                                // suffix[b]: bins [b, 16); an empty bin is the identity
+            for (uint32_t b = kBins; b-- > 1;) { suffix[b] = suffix[b + 1]; suffix[b].Add(bins[a][b]); }
+            Bin l;
+            for (uint32_t s = 1; s < kBins; ++s) {
+                l.Add(bins[a][s - 1]);
+                const Bin& r = suffix[s];
+                if (l.count == 0 || r.count == 0) continue;
+                const float cost = (float)l.count * HalfArea(l.box.Lo(), l.box.Hi()) + (float)r.count * HalfArea(r.box.Lo(), r.box.Hi());
+                if (cost < best) { best = cost; best_axis = a; best_s = s; best_l = l; best_r = r; }
+            }
+        }
+        if (!(best < HalfArea(P(node.aabb_min), P(node.aabb_max)) * (float)n)) continue;     // leaf (ref: BVH.cpp:253); also: no candidate
+
+        left_part.clear(); right_part.clear();                                    // stable: both sides keep their relative order
+        for (uint32_t i = first; i < first + n; ++i) {
+            const uint32_t tri = tri_indices_[i];
+            (BinOf(centroids_[tri][best_axis], cmin[best_axis], scale[best_axis]) < best_s ? left_part : right_part).push_back(tri);
+        }
+        std::copy(left_part.begin(), left_part.end(), tri_indices_.begin() + first);
+        std::copy(right_part.begin(), right_part.end(), tri_indices_.begin() + first + left_part.size());
+
+        const uint32_t left = nodes_used_++, right = nodes_used_++;             // the other options' numbering (ref: BVH.cpp:350-359)
+        const Bin* side[2] = { &best_l, &best_r };
+        for (uint32_t c = 0; c < 2; ++c) {
+            cgpt_bvh_node& child = nodes_[left + c];
+            child.left_first = c == 0 ? first : first + best_l.count;
+            child.prim_count = side[c]->count;
+            const Vec3 lo = side[c]->box.Lo(), hi = side[c]->box.Hi();
+            for (int k = 0; k < 3; ++k) { child.aabb_min[k] = lo[k]; child.aabb_max[k] = hi[k]; }
+        }
+        node.left_first = left;
+        node.prim_count = 0;
+        todo.push_back({ right, w.depth + 1, best_r.cen });                       // left subtree is numbered first
+        todo.push_back({ left, w.depth + 1, best_l.cen });
     }
 }
 

@@ -27,10 +27,14 @@ public:
         BuildOption_NaiveSplit = 0,
         BuildOption_SAHSplitIntervals = 1,
         BuildOption_SAHSplitPrimitives = 2,
+        // not in the reference (its README, "Planned: Binned BVH build"): 16 centroid bins per axis, 45 candidate planes swept from the
+        // bins, a stable partition.  Defined in mesh_bvh.cpp (BuildTreeBinned); the fold does not depend on the triangle order.
+        BuildOption_SAHBinned = 3,
         BuildOption_NumOptions
     };
 
-    // ref: BVH.cpp:11-45.  Returns false (and leaves the BVH empty) on an empty mesh or an out-of-range index.
+    // ref: BVH.cpp:11-45.  Returns false (and leaves the BVH empty) on an empty mesh or an out-of-range index, and for
+    // BuildOption_SAHBinned on a position that is not finite or beyond 1e30 in magnitude (the bin index must stay defined).
     bool Build(const std::vector<cgpt_vertex>& vertices, const std::vector<uint32_t>& indices, BuildOption option);
     // Same as Build(..., option) with the tree construction delegated (the GPU build, cgpt_bvh_build_ex):
     // build(triangles, n, option, initial_tri_indices or nullptr, nodes[2n-1], &n_nodes, tri_indices[n], &max_depth) returns false on
@@ -39,8 +43,11 @@ public:
     bool BuildWith(const std::vector<cgpt_vertex>& vertices, const std::vector<uint32_t>& indices, BuildOption option, const TreeBuilder& build);
     // Rebuild (below) with the re-split delegated: the builder starts from the current triangle order.  On failure the tree is unchanged.
     bool RebuildWith(BuildOption option, const TreeBuilder& build);
-    // ref: BVH.cpp:47-59: re-split over the current triangle order (the order is NOT reset, as in the reference)
-    void Rebuild(BuildOption option);
+    // ref: BVH.cpp:47-59: re-split over the current triangle order (the order is NOT reset, as in the reference).  Returns false (tree
+    // unchanged) only for BuildOption_SAHBinned on triangles outside its input domain.
+    bool Rebuild(BuildOption option);
+    // BuildOption_SAHBinned's input domain: every position finite with |x| <= 1e30
+    static bool InBinnedDomain(const cgpt_triangle* triangles, uint32_t n);
     // BVH refit (the reference's README, "Planned"): n new triangles in original order (n == NumTriangles()), tree kept.  Triangles,
     // per-triangle bounds, centroids and total_area follow them; every node's bounds become CalculateNodeBounds (ref: BVH.cpp:188-202)
     // over its current range, computed bottom-up: an inner node's is min_std / max_std of its children's, left first, which is the
@@ -65,6 +72,7 @@ private:
     void CacheTriangle(uint32_t i);   // centroid and bounds of triangles_[i]
     static bool WellFormed(const cgpt_bvh_node* nodes, uint32_t n_nodes, const uint32_t* tri_indices, uint32_t n);
     void BuildTree();
+    void BuildTreeBinned();
     void FitNode(uint32_t node_index);
     bool ChooseSplit(uint32_t node_index, uint32_t& axis, float& pos) const;
     float SplitCost(const cgpt_bvh_node& node, uint32_t axis, float pos) const;

@@ -217,7 +217,8 @@ class Renderer:
 
     def build_bvh(self, triangles, n_tris: int, build_option: int = N.BUILD_SAH_INTERVALS, initial_tri_indices=None):
         """BVH::Build (or, with initial_tri_indices = the current m_tri_indices, BVH::Rebuild) on the GPU for any BuildOption
-        (ref: Source/BVH.cpp:11-59,204-297): returns (nodes[n,8] uint32 words in the reference's 32-byte layout, tri_indices[n_tris],
+        (ref: Source/BVH.cpp:11-59,204-297) and for BUILD_SAH_BINNED (not in the reference: DESIGN.md 5.10; finite positions of magnitude
+        <= 1e30 only): returns (nodes[n,8] uint32 words in the reference's 32-byte layout, tri_indices[n_tris],
         max_depth, total_area).  triangles: ctypes pointer to n_tris cgpt_triangle (e.g. SceneDesc.triangles + tri_offset)."""
         nodes = np.zeros((max(2 * n_tris - 1, 1), 8), np.uint32)
         tri = np.zeros(n_tris, np.uint32)

@@ -229,7 +229,8 @@ class Scene:
         return out
 
     def add_mesh(self, mesh: Mesh, mat_index: int, build_option: int = N.BUILD_SAH_INTERVALS, device_builder=None) -> int:
-        """Object ctor (ref: Main.cpp:247-251).  device_builder: a Renderer whose GPU builds the (bit-identical) tree, any option."""
+        """Object ctor (ref: Main.cpp:247-251).  device_builder: a Renderer whose GPU builds the (bit-identical) tree, any option.
+        build_option: BUILD_NAIVE, BUILD_SAH_INTERVALS (the reference's default), BUILD_SAH_PRIMITIVES or BUILD_SAH_BINNED."""
         if device_builder is not None:
             rc = N.lib().cgpth_scene_add_mesh_device_built_ex(self._h, mesh._h, mat_index, device_builder._ctx, build_option)
         else:

@@ -4,7 +4,7 @@
 //
 //   g++ -std=c++17 -Iinclude -Icpugpupathtracing_amd/csrc/host examples/render_main.cpp
 //       -Lcpugpupathtracing_amd/lib -lcpugpupt -Wl,-rpath,$PWD/cpugpupathtracing_amd/lib -o render_main   (one command line)
-//   ./render_main [--gpus N [--collective]] [--denoise] [--ground-roughness R] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
+//   ./render_main [--gpus N [--collective]] [--denoise] [--ground-roughness R] [--bvh intervals|binned] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
 // --gpus N: ONE context over the first N GPUs of the node (cgpt_ctx_create with n_devices = N): every frame is spread over them in
 // interleaved row bands and the read-back gathers the float4 bands with one RCCL exchange over xGMI; the loop below does not
 // change.  --collective: take that code path with N = 1 too (what a one-GPU box can test).
@@ -14,6 +14,8 @@
 // end (render_denoised.ppm) -- what a viewer with a "Denoise" toggle presents; the accumulator and the raw dumps are not affected.
 // --ground-roughness R: a glossy ground -- its material (1) gets specular 0.5 and roughness R in [0, 1] (cgpt_scene_update_roughness after
 // the upload; 0 keeps the mirror half of the lobe perfect).
+// --bvh binned: build the mesh's tree with BuildOption_SAHBinned (16 bins per axis) on the host instead of the reference's
+// SAH split intervals (the default; image parity with the reference is defined on that tree).
 // move_at > 0 scripts the input half of Update(dt) (ref: Main.cpp:277-297, Camera::Update :104-131): after that many samples the
 // camera is translated by (right, up, forward) as the A/D, Space/Shift, W/S keys would, the view changes, and the accumulator
 // is reset (ref: ResetAccumulator, Main.cpp:238-243) before the remaining samples are rendered from the new position.
@@ -40,11 +42,15 @@ using namespace cgpt;
 int main(int argc, char** argv)
 {
     int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; float ground_roughness = -1.0f;
+    MeshBVH::BuildOption bvh_option = MeshBVH::BuildOption_SAHSplitIntervals;
     while (argc > 1 && std::string(argv[1]).rfind("--", 0) == 0) {
         if (std::string(argv[1]) == "--gpus" && argc > 2) { n_gpus = atoi(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--collective") { ctx_flags |= CGPT_CTX_FORCE_COLLECTIVE; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--denoise") { denoise = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--ground-roughness" && argc > 2) { ground_roughness = (float)atof(argv[2]); argv += 2; argc -= 2; }
+        else if (std::string(argv[1]) == "--bvh" && argc > 2 && (std::string(argv[2]) == "binned" || std::string(argv[2]) == "intervals")) {
+            bvh_option = std::string(argv[2]) == "binned" ? MeshBVH::BuildOption_SAHBinned : MeshBVH::BuildOption_SAHSplitIntervals; argv += 2; argc -= 2;
+        }
         else { fprintf(stderr, "unknown option %s\n", argv[1]); return 2; }
     }
     std::string model = argc > 1 && std::string(argv[1]).find(".gltf") != std::string::npos ? argv[1] : "";
@@ -59,7 +65,8 @@ int main(int argc, char** argv)
     Mesh mesh;
     if (model.empty()) mesh = MakeDragonStandIn(6);
     else { std::string err; if (!GLTFLoader::Load(model, mesh, err)) { fprintf(stderr, "%s\n", err.c_str()); return 1; } }   // ref: Main.cpp:785
-    Scene scene = MakeReferenceScene(mesh, 3, (float)W / (float)H, MeshBVH::BuildOption_SAHSplitIntervals);            // ref: Main.cpp:777-819
+    Scene scene = MakeReferenceScene(mesh, 3, (float)W / (float)H, bvh_option);            // ref: Main.cpp:777-819
+    if (!scene.objects[0].valid) { fprintf(stderr, "the mesh is empty, or (--bvh binned) has a position that is not finite or beyond 1e30\n"); return 1; }
     if (ground_roughness >= 0.0f) { scene.materials[1].specular = 0.5f; scene.materials[1].roughness = ground_roughness; }
 
     cgpt_ctx* ctx = nullptr;

@@ -27,7 +27,8 @@ extern "C" {
 #define CGPT_ABI_VERSION 2u   /* 2: cgpt_stats grew (gather_ms .. last_kernel), CGPT_KERNEL_* / CGPT_CTX_* values added since 1;
                                  CGPT_OBJECT_TRIANGLE is a new enum value only, no layout changed; the denoiser added new symbols
                                  (cgpt_read_guides, cgpt_denoise) and a new struct (cgpt_denoise_params) only; the microfacet specular
-                                 lobe added one new symbol (cgpt_scene_update_roughness) only */
+                                 lobe added one new symbol (cgpt_scene_update_roughness) only; CGPT_BUILD_SAH_BINNED is a new enum
+                                 value only */
 
 enum cgpt_status {
     CGPT_OK = 0,
@@ -265,7 +266,21 @@ int cgpt_bvh_build(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t n_tri
  * initial_tri_indices = NULL starts from the identity order as Build does (:25-29); otherwise it is the tree's CURRENT m_tri_indices
  * (a permutation of 0..n_tris-1), which Rebuild does not reset -- the swap partition is order-sensitive, so the result differs from a
  * fresh Build and equals the reference's Rebuild. */
-enum cgpt_bvh_build_option { CGPT_BUILD_NAIVE_SPLIT = 0, CGPT_BUILD_SAH_SPLIT_INTERVALS = 1, CGPT_BUILD_SAH_SPLIT_PRIMITIVES = 2 };
+/* CGPT_BUILD_SAH_BINNED is not one of the reference's options (its README, "Planned: Binned BVH build"); the host mirror
+ * (csrc/host/mesh_bvh.cpp, BuildTreeBinned) is its specification and the device build equals it word for word.  Per node of n triangles,
+ * with each triangle's box and centroid ((p0 + p1 + p2) * 0.3333f) as in the other options:
+ *   - cmin, cmax: the bounds of the node's centroids.  Per axis a with cmax[a] > cmin[a]: scale = 16.0f / (cmax[a] - cmin[a]) and a
+ *     triangle's bin is min(15, (uint32_t)((c[a] - cmin[a]) * scale)) (a product that is not below 16, an overflowed scale included, is
+ *     bin 15).  Each of the 16 bins keeps a count, the union of its triangles' boxes and the bounds of their centroids;
+ *   - every min / max is taken under the total order on floats in which -0 < +0, so no bound depends on the order of the fold;
+ *   - candidates: axis outer, split s = 1..15 inner; left = bins [0, s), right = bins [s, 16); a candidate with an empty side is skipped;
+ *     cost = (float)lc * half_area(left) + (float)rc * half_area(right); the first strictly cheaper candidate wins;
+ *   - the node is a leaf if there is no candidate or !(best < half_area(node) * (float)n) (the reference's criterion, BVH.cpp:253);
+ *   - the partition is stable (left iff the bin on the chosen axis is < s); the children's bounds are the unions of the bins of each side;
+ *   - node numbering, left_first / prim_count, max_depth and total_area as for the other options; initial_tri_indices as for Rebuild.
+ * Input domain of this option only: every position finite with |x| <= 1e30, otherwise CGPT_ERR_INVALID and nothing is built (the bin
+ * index must stay defined).  The three reference options keep their behaviour on such inputs. */
+enum cgpt_bvh_build_option { CGPT_BUILD_NAIVE_SPLIT = 0, CGPT_BUILD_SAH_SPLIT_INTERVALS = 1, CGPT_BUILD_SAH_SPLIT_PRIMITIVES = 2, CGPT_BUILD_SAH_BINNED = 3 };
 int cgpt_bvh_build_ex(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t n_tris, uint32_t build_option, const uint32_t* initial_tri_indices,
                       cgpt_bvh_node* nodes_out, uint32_t* n_nodes_out, uint32_t* tri_indices_out, uint32_t* max_depth_out, float* total_area_out);
 

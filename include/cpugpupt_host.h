@@ -17,7 +17,8 @@ extern "C" {
 #endif
 
 /* ref: Include/BVH.h:7-13 */
-enum cgpth_build_option { CGPTH_BUILD_NAIVE = 0, CGPTH_BUILD_SAH_INTERVALS = 1, CGPTH_BUILD_SAH_PRIMITIVES = 2 };
+enum cgpth_build_option { CGPTH_BUILD_NAIVE = 0, CGPTH_BUILD_SAH_INTERVALS = 1, CGPTH_BUILD_SAH_PRIMITIVES = 2,
+                          CGPTH_BUILD_SAH_BINNED = 3 /* CGPT_BUILD_SAH_BINNED: not in the reference; positions must be finite, |x| <= 1e30 */ };
 
 typedef struct cgpth_mesh cgpth_mesh;    /* ref: Include/Primitives.h:24-28 (Mesh) */
 typedef struct cgpth_scene cgpth_scene;  /* ref: Source/Main.cpp:200-236 (the parts of `data` Render() reads) */
