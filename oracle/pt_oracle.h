@@ -17,7 +17,10 @@
  *     tests/test_oracle_pins.py reproduces to the last printed digit -- they cover the BVH build and ONE
  *     diffuse TracePathAdvanced render; dielectric / Beer / total internal reflection, mesh lights,
  *     TracePath (brute force), COMPARISON and the debug views have no recorded reference output at all;
- *   - analytic known-answer tests (tests/test_oracle_kat.py).
+ *   - analytic known-answer tests (tests/test_oracle_kat.py);
+ *   - closed forms of both integrators' expectations in plane-and-light scenes (tests/integrator_ref.py, float64, sharing nothing
+ *     with this file): NEE on sphere and mesh lights, dielectric / Beer / TIR, the lobe mix and COMPARISON, checked on this oracle by
+ *     tests/test_integrator_reference.py and on every kernel by tests/test_gpu_integrator_kat.py.
  * Every "bit-identical" claim in this repository is GPU vs THIS oracle, not GPU vs the reference.
  *
  * Float discipline: every expression keeps the reference's operand order; the file is compiled
