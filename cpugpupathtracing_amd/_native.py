@@ -123,6 +123,7 @@ PROTOTYPES = {
     "cgpt_scene_upload": (C.c_int, [_vp, C.POINTER(SceneDesc)]),
     "cgpt_scene_update_materials": (C.c_int, [_vp, C.POINTER(Material), C.c_uint32]),
     "cgpt_scene_update_roughness": (C.c_int, [_vp, _fp, C.c_uint32]),
+    "cgpt_scene_update_transmission_roughness": (C.c_int, [_vp, _fp, C.c_uint32]),
     "cgpt_scene_refit_mesh": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), C.c_uint32, _fp]),
     "cgpt_scene_export_bvh": (C.c_int, [_vp, C.c_uint32, C.POINTER(BvhNode), C.c_uint32]),
     "cgpt_scene_update_primitive": (C.c_int, [_vp, C.c_uint32, C.POINTER(Object)]),
@@ -163,6 +164,8 @@ PROTOTYPES = {
     "cgpth_scene_set_material": (C.c_int, [_vp, C.c_uint32, C.POINTER(Material)]),
     "cgpth_scene_set_roughness": (C.c_int, [_vp, C.c_uint32, C.c_float]),
     "cgpth_scene_get_roughness": (C.c_int, [_vp, _fp, C.c_uint32]),
+    "cgpth_scene_set_transmission_roughness": (C.c_int, [_vp, C.c_uint32, C.c_float]),
+    "cgpth_scene_get_transmission_roughness": (C.c_int, [_vp, _fp, C.c_uint32]),
     "cgpth_scene_add_mesh": (C.c_int, [_vp, _vp, C.c_uint32, C.c_int]),
     "cgpth_scene_add_mesh_device_built": (C.c_int, [_vp, _vp, C.c_uint32, _vp]),
     "cgpth_scene_add_mesh_device_built_ex": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_int]),

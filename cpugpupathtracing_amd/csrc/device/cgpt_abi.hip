@@ -18,19 +18,19 @@
 #include "scene_layout.h"
 
 namespace cgpt {
-hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, bool glossy, hipStream_t stream);       // path_kernels.hip
+hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, uint32_t lobe_level, hipStream_t stream);       // path_kernels.hip
 hipError_t LaunchIntersectRays(const DevScene& sc, const float* origins, const float* dirs, const float* tmax, uint32_t n, float* out_t,
                                uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, DevCounters* counters, hipStream_t stream);
-int LaunchWavefront(struct ::cgpt_ctx* ctx, const DevRenderArgs& args, bool count, bool glossy);          // wavefront_kernels.hip
+int LaunchWavefront(struct ::cgpt_ctx* ctx, const DevRenderArgs& args, bool count, uint32_t lobe_level);          // wavefront_kernels.hip
 void WavefrontFree(void* state);
 void WavefrontCollectTiming(void* state, double* trace_ms, uint32_t* trace_launches, double* round0_ms, uint32_t* round0_launches);
 int WavefrontSetTuning(struct ::cgpt_ctx* ctx, const char* name, uint32_t value);
 uint32_t WavefrontTraceWavesPerSimd(void* state);
-int LaunchPersistent(struct ::cgpt_ctx* ctx, const DevRenderArgs& args, bool count, bool glossy);             // persistent_kernel.hip
+int LaunchPersistent(struct ::cgpt_ctx* ctx, const DevRenderArgs& args, bool count, uint32_t lobe_level);             // persistent_kernel.hip
 void PersistentFree(void* state);
-void PersistentCollectTiming(void* state, bool glossy, double* ms, uint32_t* launches, uint32_t* waves_per_simd);
+void PersistentCollectTiming(void* state, uint32_t lobe_level, double* ms, uint32_t* launches, uint32_t* waves_per_simd);
 int PersistentSetTuning(struct ::cgpt_ctx* ctx, const char* name, uint32_t value, bool* known);
-uint32_t MegakernelWavesPerSimd(const DevRenderArgs& args, bool glossy);                                      // path_kernels.hip
+uint32_t MegakernelWavesPerSimd(const DevRenderArgs& args, uint32_t lobe_level);                                      // path_kernels.hip
 }  // namespace cgpt
 
 using namespace cgpt;
@@ -110,7 +110,7 @@ void FreeScene(cgpt_ctx* ctx)
     (void)hipFree(ctx->d_refit_levels); (void)hipFree(ctx->d_refit_staging);
     ctx->d_refit_levels = nullptr; ctx->d_refit_staging = nullptr; ctx->refit_staging_tris = 0;
     ctx->h_objects.clear(); ctx->refit_objects.clear(); ctx->record_perm.clear();
-    ctx->h_roughness.clear(); ctx->h_materials.clear(); ctx->glossy = false;
+    ctx->h_roughness.clear(); ctx->h_transmission_roughness.clear(); ctx->h_materials.clear(); ctx->lobe_level = 0;
     ctx->has_scene = false;
 }
 
@@ -155,6 +155,39 @@ int ResolveBand(cgpt_ctx* ctx, const cgpt_render_params& p, Band& b)
     }
     const uint32_t key[5] = { p.row_begin, p.row_end, p.interleave_rows, p.interleave_count, p.interleave_index };
     memcpy(b.key, key, sizeof(key));
+    return CGPT_OK;
+}
+
+// cgpt_scene_update_roughness (transmission false: PackMaterial's alpha, materials[4i+3].z) and cgpt_scene_update_transmission_roughness
+// (true: alpha_t, .w) of a one-device context.  Everything is refused before the device write; the other lobe's values are kept.
+int UpdateRoughnessWord(cgpt_ctx* ctx, const float* roughness, uint32_t n_materials, bool transmission)
+{
+    const char* const what = transmission ? "transmission roughness" : "roughness";
+    if (!ctx->has_scene) return Fail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!roughness || n_materials != ctx->n_materials) return Fail(ctx, CGPT_ERR_INVALID, "expected %u %s values", ctx->n_materials, what);
+    bool rough = false;
+    for (uint32_t i = 0; i < n_materials; ++i) {
+        if (!(roughness[i] >= 0.0f && roughness[i] <= 1.0f)) return Fail(ctx, CGPT_ERR_INVALID, "material %u: %s %g outside [0, 1]", i, what, (double)roughness[i]);
+        rough = rough || roughness[i] > 0.0f;
+    }
+    std::vector<float4> mats;
+    std::vector<float> values;
+    try { mats = ctx->h_materials; values.assign(roughness, roughness + n_materials); } catch (const std::exception& e) { return Fail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
+    for (uint32_t i = 0; i < n_materials; ++i) (transmission ? mats[4 * (size_t)i + 3].w : mats[4 * (size_t)i + 3].z) = roughness[i] * roughness[i];
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // first hits and albedo do not depend on either roughness: the denoiser's guides stay valid (scene_generation is left as it is)
+    const hipError_t e = hipMemcpy(ctx->d_materials, mats.data(), mats.size() * sizeof(float4), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {                                                     // the records may be half written: drop the scene (refit.hip: SceneLost)
+        ctx->has_scene = false;
+        return Fail(ctx, CGPT_ERR_HIP, "hipMemcpy of the material records failed: %s (the device scene is dropped; upload it again)", hipGetErrorString(e));
+    }
+    ctx->h_materials.swap(mats);
+    (transmission ? ctx->h_transmission_roughness : ctx->h_roughness).swap(values);
+    bool other = false;
+    for (const float v : transmission ? ctx->h_roughness : ctx->h_transmission_roughness) other = other || v > 0.0f;
+    const bool specular = transmission ? other : rough, glass = transmission ? rough : other;
+    ctx->lobe_level = glass ? 2u : (specular ? 1u : 0u);
     return CGPT_OK;
 }
 
@@ -256,7 +289,7 @@ int cgpt_scene_update_materials(cgpt_ctx* ctx, const cgpt_material* materials, u
     if (!materials || n_materials != ctx->n_materials) return Fail(ctx, CGPT_ERR_INVALID, "expected %u materials", ctx->n_materials);
     std::vector<float4> mats;
     try { mats.resize(4 * (size_t)n_materials); } catch (const std::exception& e) { return Fail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
-    for (uint32_t i = 0; i < n_materials; ++i) PackMaterial(materials[i], ctx->h_roughness[i], mats.data() + 4 * (size_t)i);   // roughness is kept
+    for (uint32_t i = 0; i < n_materials; ++i) PackMaterial(materials[i], ctx->h_roughness[i], ctx->h_transmission_roughness[i], mats.data() + 4 * (size_t)i);   // both roughnesses are kept
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->scene_generation++;
@@ -269,28 +302,14 @@ int cgpt_scene_update_roughness(cgpt_ctx* ctx, const float* roughness, uint32_t 
 {
     if (!ctx) return CGPT_ERR_INVALID;
     if (ctx->group) GROUP_CALL(ctx, GroupUpdateRoughness(ctx, roughness, n_materials));
-    if (!ctx->has_scene) return Fail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
-    if (!roughness || n_materials != ctx->n_materials) return Fail(ctx, CGPT_ERR_INVALID, "expected %u roughness values", ctx->n_materials);
-    bool glossy = false;
-    for (uint32_t i = 0; i < n_materials; ++i) {
-        if (!(roughness[i] >= 0.0f && roughness[i] <= 1.0f)) return Fail(ctx, CGPT_ERR_INVALID, "material %u: roughness %g outside [0, 1]", i, (double)roughness[i]);
-        glossy = glossy || roughness[i] > 0.0f;
-    }
-    std::vector<float4> mats;
-    try { mats = ctx->h_materials; } catch (const std::exception& e) { return Fail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
-    for (uint32_t i = 0; i < n_materials; ++i) mats[4 * (size_t)i + 3].z = roughness[i] * roughness[i];   // PackMaterial's alpha
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    // first hits and albedo do not depend on roughness: the denoiser's guides stay valid (scene_generation is left as it is)
-    const hipError_t e = hipMemcpy(ctx->d_materials, mats.data(), mats.size() * sizeof(float4), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {                                                     // the records may be half written: drop the scene (refit.hip: SceneLost)
-        ctx->has_scene = false;
-        return Fail(ctx, CGPT_ERR_HIP, "hipMemcpy of the material records failed: %s (the device scene is dropped; upload it again)", hipGetErrorString(e));
-    }
-    ctx->h_materials.swap(mats);
-    ctx->h_roughness.assign(roughness, roughness + n_materials);
-    ctx->glossy = glossy;
-    return CGPT_OK;
+    return UpdateRoughnessWord(ctx, roughness, n_materials, false);
+}
+
+int cgpt_scene_update_transmission_roughness(cgpt_ctx* ctx, const float* roughness, uint32_t n_materials)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) GROUP_CALL(ctx, GroupUpdateTransmissionRoughness(ctx, roughness, n_materials));
+    return UpdateRoughnessWord(ctx, roughness, n_materials, true);
 }
 
 int cgpt_camera_from_view(const float pos[3], const float view_dir[3], float fov_deg, float aspect, cgpt_camera* out)
@@ -326,7 +345,7 @@ int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout)
     if ((rc = UploadArray(ctx, &ctx->d_lights, layout.lights)) != CGPT_OK) return rc;
     if ((rc = UploadArray(ctx, &ctx->d_refit_levels, layout.refit_levels)) != CGPT_OK) return rc;
     ctx->h_objects = layout.objects; ctx->refit_objects = layout.refit_objects; ctx->record_perm = layout.record_perm;
-    ctx->h_roughness.assign(layout.n_materials, 0.0f); ctx->h_materials = layout.materials; ctx->glossy = false;
+    ctx->h_roughness.assign(layout.n_materials, 0.0f); ctx->h_transmission_roughness.assign(layout.n_materials, 0.0f); ctx->h_materials = layout.materials; ctx->lobe_level = 0;
 
     ctx->scene.node_pairs = ctx->d_node_pairs; ctx->scene.tri_leaf = ctx->d_tri_leaf; ctx->scene.tri_orig = ctx->d_tri_orig; ctx->scene.tri_normal = ctx->d_tri_normal;
     ctx->scene.materials = ctx->d_materials; ctx->scene.objects = ctx->d_objects; ctx->scene.obj_trace = ctx->d_obj_trace; ctx->scene.lights = ctx->d_lights;
@@ -405,21 +424,21 @@ int RenderEnqueue(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings*
 
     if (kernel == CGPT_KERNEL_MEGAKERNEL) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-        HIP_TRY(ctx, LaunchMegakernel(args, count, ctx->glossy, ctx->stream));
+        HIP_TRY(ctx, LaunchMegakernel(args, count, ctx->lobe_level, ctx->stream));
         ctx->kernel_launches += 1;
     } else if (kernel == CGPT_KERNEL_WAVEFRONT) {
-        rc = LaunchWavefront(ctx, args, count, ctx->glossy);
+        rc = LaunchWavefront(ctx, args, count, ctx->lobe_level);
         if (rc < 0) return ctx->error.empty() ? Fail(ctx, CGPT_ERR_HIP, "wavefront launch failed") : CGPT_ERR_HIP;
         ctx->kernel_launches += (uint32_t)rc;
     } else if (kernel == CGPT_KERNEL_PERSISTENT) {
-        rc = LaunchPersistent(ctx, args, count, ctx->glossy);
+        rc = LaunchPersistent(ctx, args, count, ctx->lobe_level);
         if (rc < 0) return ctx->error.empty() ? Fail(ctx, CGPT_ERR_HIP, "persistent kernel launch failed") : CGPT_ERR_HIP;
         ctx->kernel_launches += (uint32_t)rc;
     } else {
         return Fail(ctx, CGPT_ERR_INVALID, "unknown kernel %u", p->kernel);
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
-    ctx->pending_kernel = kernel; ctx->pending_args = args; ctx->pending_num_accumulated = p->first_sample + p->n_samples; ctx->pending_glossy = ctx->glossy;
+    ctx->pending_kernel = kernel; ctx->pending_args = args; ctx->pending_num_accumulated = p->first_sample + p->n_samples; ctx->pending_lobe_level = ctx->lobe_level;
     ctx->last_debug_mode = settings->debug_render_mode;
     ctx->last_kernel = kernel;
     return CGPT_OK;
@@ -436,10 +455,10 @@ int RenderFinish(cgpt_ctx* ctx)
     float ms = 0.0f;
     HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
     ctx->kernel_ms += ms;
-    if (kernel == CGPT_KERNEL_MEGAKERNEL) { ctx->dominant_ms += ms; ctx->dominant_launches += 1; ctx->dominant_waves_per_simd = MegakernelWavesPerSimd(args, ctx->pending_glossy); }
+    if (kernel == CGPT_KERNEL_MEGAKERNEL) { ctx->dominant_ms += ms; ctx->dominant_launches += 1; ctx->dominant_waves_per_simd = MegakernelWavesPerSimd(args, ctx->pending_lobe_level); }
     else if (kernel == CGPT_KERNEL_PERSISTENT) {
         double tms = 0.0; uint32_t tl = 0, w = 0;
-        PersistentCollectTiming(ctx->persistent_state, ctx->pending_glossy, &tms, &tl, &w);
+        PersistentCollectTiming(ctx->persistent_state, ctx->pending_lobe_level, &tms, &tl, &w);
         ctx->dominant_ms += tms; ctx->dominant_launches += tl; ctx->dominant_waves_per_simd = w;
     } else {
         ctx->dominant_waves_per_simd = WavefrontTraceWavesPerSimd(ctx->wavefront_state);

@@ -32,12 +32,13 @@ struct cgpt_ctx {
     cgpt::DevScene scene{};
     uint32_t n_materials = 0;
     bool has_scene = false;
-    // the specular lobe's roughness per material (cgpt_scene_update_roughness; 0 after every upload), the packed material records as they
-    // are on the device (a roughness or material update re-packs them), and whether any roughness is > 0: the renders then run the GLOSSY
-    // instantiations of the render kernels
-    std::vector<float> h_roughness;
+    // the specular lobe's roughness and the dielectric lobe's transmission roughness per material (cgpt_scene_update_roughness,
+    // cgpt_scene_update_transmission_roughness; 0 after every upload), the packed material records as they are on the device (a roughness
+    // or material update re-packs them), and the lobe level = the GLOSSY instantiation of the render kernels the renders run: 2 when any
+    // transmission roughness is > 0, else 1 when any roughness is > 0, else 0 (UpdateLobeLevel, cgpt_abi.hip)
+    std::vector<float> h_roughness, h_transmission_roughness;
     std::vector<float4> h_materials;
-    bool glossy = false;
+    uint32_t lobe_level = 0;
 
     // in-place edits of the uploaded scene (refit.hip): host copies of the objects, each mesh's child-pair records grouped by
     // depth, and where the renumbering put every record
@@ -71,7 +72,7 @@ struct cgpt_ctx {
     // a render that has been enqueued and not yet finished (RenderEnqueue / RenderFinish)
     uint32_t pending_kernel = 0;
     uint32_t pending_num_accumulated = 0;
-    bool pending_glossy = false;
+    uint32_t pending_lobe_level = 0;
     cgpt::DevRenderArgs pending_args{};
     uint32_t last_debug_mode = 0;
     uint32_t last_kernel = 0;                     // cgpt_kernel the last render ran (AUTO resolved)
@@ -111,6 +112,7 @@ void GroupDestroy(cgpt_ctx* ctx);
 int GroupSceneUpload(cgpt_ctx* ctx, const cgpt_scene_desc* scene);
 int GroupUpdateMaterials(cgpt_ctx* ctx, const cgpt_material* materials, uint32_t n);
 int GroupUpdateRoughness(cgpt_ctx* ctx, const float* roughness, uint32_t n);
+int GroupUpdateTransmissionRoughness(cgpt_ctx* ctx, const float* roughness, uint32_t n);
 int GroupRefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris, float* total_area_out);
 int GroupUpdatePrimitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_object* obj);
 int GroupRender(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p);

@@ -22,8 +22,10 @@
 //                                   = v0.normal (ref: Primitives.cpp:148-151) and mesh-light sampling (ref: Primitives.cpp:170-186):
 //                                   {p0.xyz, n0.x | p1.xyz, n0.y | p2.xyz, n0.z}
 //  tri_normal  float4[n_tris]       {n0.xyz, -} in ORIGINAL order: the shading normal of a hit is one 16-byte load
-//  materials   float4[4 * n_mat]    {albedo.xyz, specular | refractivity, absorption.xyz | ior, emissive.xyz | intensity, is_light, alpha, -}
-//                                   (alpha = roughness^2 of the specular lobe, cgpt_scene_update_roughness; 0 = the mirror)
+//  materials   float4[4 * n_mat]    {albedo.xyz, specular | refractivity, absorption.xyz | ior, emissive.xyz | intensity, is_light, alpha, alpha_t}
+//                                   (alpha = roughness^2 of the specular lobe, cgpt_scene_update_roughness; 0 = the mirror;
+//                                    alpha_t = transmission roughness^2 of the dielectric lobe,
+//                                    cgpt_scene_update_transmission_roughness; 0 = polished)
 //  objects     DevObject[n]         read with wave-uniform indices (scalar loads)
 //  obj_trace   float4[2 * n]        what IntersectScene's object loop needs of object i, for per-lane object indices:
 //                                   {kind, p0, p1, p2 | p3, p4, p5, -}: mesh p0 = root code; sphere p0..2 = centre, p3 = radius^2;

@@ -399,6 +399,11 @@ int GroupUpdateRoughness(cgpt_ctx* ctx, const float* roughness, uint32_t n)
     return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_update_roughness(m, roughness, n); });
 }
 
+int GroupUpdateTransmissionRoughness(cgpt_ctx* ctx, const float* roughness, uint32_t n)
+{
+    return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_update_transmission_roughness(m, roughness, n); });
+}
+
 int GroupRender(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p)
 {
     DeviceGroup* g = ctx->group;

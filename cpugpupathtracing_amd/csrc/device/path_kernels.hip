@@ -27,8 +27,9 @@ extern __shared__ uint32_t lds_stack[];
 // Block shape: 256 threads = a 16x16-pixel tile (the reference's job size, ref: Main.cpp:705-711), or -- one-sample calls -- 64 threads =
 // one 8x8 tile per single-wave block: the wave's slot and its LDS are free the moment its own longest path ends instead of its block's,
 // and the dispatcher places single waves (1080p, one sample: 1.71 -> 1.68 ms, profiles/r03/one_sample.md).
-// GLOSSY: the scene has a rough specular material (shade_device.hpp: ggx_sample); the mirror-only scenes keep the code without it.
-template <bool COUNT, bool BRUTE, bool GLOSSY>
+// GLOSSY (the lobe level): 0 no rough lobe; 1 the scene has a rough specular material (shade_device.hpp: ggx_sample); 2 it has a rough dielectric (rough_glass_sample; carries the rough specular lobe too).
+// The scenes without a rough lobe keep the code without it.
+template <bool COUNT, bool BRUTE, int GLOSSY>
 __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
 {
     const DevScene& sc = args.scene;
@@ -150,12 +151,12 @@ static uint32_t MegakernelBlockThreads(const DevRenderArgs& args)
 }
 
 // every instantiation, [COUNT][BRUTE][GLOSSY]
-static decltype(&megakernel<false, false, false>) const kMegakernels[2][2][2] = {
-    { { megakernel<false, false, false>, megakernel<false, false, true> }, { megakernel<false, true, false>, megakernel<false, true, true> } },
-    { { megakernel<true, false, false>, megakernel<true, false, true> }, { megakernel<true, true, false>, megakernel<true, true, true> } },
+static decltype(&megakernel<false, false, 0>) const kMegakernels[2][2][3] = {
+    { { megakernel<false, false, 0>, megakernel<false, false, 1>, megakernel<false, false, 2> }, { megakernel<false, true, 0>, megakernel<false, true, 1>, megakernel<false, true, 2> } },
+    { { megakernel<true, false, 0>, megakernel<true, false, 1>, megakernel<true, false, 2> }, { megakernel<true, true, 0>, megakernel<true, true, 1>, megakernel<true, true, 2> } },
 };
 
-hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, bool glossy, hipStream_t stream)
+hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, uint32_t lobe_level, hipStream_t stream)
 {
     const bool brute = args.settings.render_mode != 2u;
     const uint32_t bt = MegakernelBlockThreads(args);
@@ -163,16 +164,16 @@ hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, bool glossy, 
     const uint32_t tiles_x = (args.width + edge - 1u) / edge, tiles_y = (args.n_rows + edge - 1u) / edge;
     const dim3 grid(tiles_x * tiles_y), block(bt);
     const size_t lds = (size_t)args.scene.stack_depth * bt * sizeof(uint32_t);
-    hipLaunchKernelGGL(kMegakernels[count][brute][glossy], grid, block, lds, stream, args);
+    hipLaunchKernelGGL(kMegakernels[count][brute][lobe_level], grid, block, lds, stream, args);
     return hipGetLastError();
 }
 
-uint32_t MegakernelWavesPerSimd(const DevRenderArgs& args, bool glossy)
+uint32_t MegakernelWavesPerSimd(const DevRenderArgs& args, uint32_t lobe_level)
 {
     int b = 0;
     const uint32_t bt = MegakernelBlockThreads(args);
     const size_t lds = (size_t)args.scene.stack_depth * bt * sizeof(uint32_t);
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kMegakernels[0][args.settings.render_mode != 2u][glossy], (int)bt, lds);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kMegakernels[0][args.settings.render_mode != 2u][lobe_level], (int)bt, lds);
     return e == hipSuccess && b > 0 ? std::max(1u, (uint32_t)b * bt / 256u) : 1u;    // blocks per CU -> waves per SIMD (4 SIMDs)
 }
 

@@ -64,8 +64,9 @@ enum : uint32_t {                      // per-lane path flags
 // Main.cpp:702,825-942), which are mostly drain: once nothing is left to fetch, a wave with few busy lanes runs their rays in the lean
 // per-lane loop (trace_steps.hpp: lean_traverse) instead of voted steps, because the call ends when its longest chain does (1080p, one
 // sample: 2.47 -> 2.21 ms).  Kept out of the throughput instantiations, which it costs registers and SGPR spills (profiles/r03/one_sample.md).
-// GLOSSY: the scene has a rough specular material (shade_device.hpp: ggx_sample); the mirror-only scenes keep the code without it.
-template <bool COUNT, bool BRUTE, bool TAIL, bool GLOSSY>
+// GLOSSY (the lobe level): 0 no rough lobe; 1 the scene has a rough specular material (shade_device.hpp: ggx_sample); 2 it has a rough dielectric (rough_glass_sample; carries the rough specular lobe too).
+// The scenes without a rough lobe keep the code without it.
+template <bool COUNT, bool BRUTE, bool TAIL, int GLOSSY>
 __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderArgs args, const PtDev pt, uint32_t batch_first, const TraceTune tune)
 {
     const DevScene& sc = args.scene;
@@ -263,11 +264,13 @@ struct PtTuning {
 };
 
 // every instantiation, [GLOSSY][COUNT][BRUTE][TAIL]
-static decltype(&pt_persistent<false, false, false, false>) const kPtKernels[2][2][2][2] = {
-    { { { pt_persistent<false, false, false, false>, pt_persistent<false, false, true, false> }, { pt_persistent<false, true, false, false>, pt_persistent<false, true, true, false> } },
-      { { pt_persistent<true, false, false, false>, pt_persistent<true, false, true, false> }, { pt_persistent<true, true, false, false>, pt_persistent<true, true, true, false> } } },
-    { { { pt_persistent<false, false, false, true>, pt_persistent<false, false, true, true> }, { pt_persistent<false, true, false, true>, pt_persistent<false, true, true, true> } },
-      { { pt_persistent<true, false, false, true>, pt_persistent<true, false, true, true> }, { pt_persistent<true, true, false, true>, pt_persistent<true, true, true, true> } } },
+static decltype(&pt_persistent<false, false, false, 0>) const kPtKernels[3][2][2][2] = {
+    { { { pt_persistent<false, false, false, 0>, pt_persistent<false, false, true, 0> }, { pt_persistent<false, true, false, 0>, pt_persistent<false, true, true, 0> } },
+      { { pt_persistent<true, false, false, 0>, pt_persistent<true, false, true, 0> }, { pt_persistent<true, true, false, 0>, pt_persistent<true, true, true, 0> } } },
+    { { { pt_persistent<false, false, false, 1>, pt_persistent<false, false, true, 1> }, { pt_persistent<false, true, false, 1>, pt_persistent<false, true, true, 1> } },
+      { { pt_persistent<true, false, false, 1>, pt_persistent<true, false, true, 1> }, { pt_persistent<true, true, false, 1>, pt_persistent<true, true, true, 1> } } },
+    { { { pt_persistent<false, false, false, 2>, pt_persistent<false, false, true, 2> }, { pt_persistent<false, true, false, 2>, pt_persistent<false, true, true, 2> } },
+      { { pt_persistent<true, false, false, 2>, pt_persistent<true, false, true, 2> }, { pt_persistent<true, true, false, 2>, pt_persistent<true, true, true, 2> } } },
 };
 
 struct PtHost {
@@ -280,7 +283,7 @@ struct PtHost {
     hipEvent_t begin = nullptr, acc_done[2] = { nullptr, nullptr };
     EventPairs ev;
     uint32_t n_cus = 0;
-    uint32_t blocks_per_cu[2][2][2][2] = {};  // [GLOSSY][COUNT][BRUTE][TAIL]
+    uint32_t blocks_per_cu[3][2][2][2] = {};  // [GLOSSY][COUNT][BRUTE][TAIL]
     size_t occupancy_lds = 0;
 };
 
@@ -340,16 +343,16 @@ void PersistentFree(void* state)
     delete h;
 }
 
-void PersistentCollectTiming(void* state, bool glossy, double* ms, uint32_t* launches, uint32_t* waves_per_simd)
+void PersistentCollectTiming(void* state, uint32_t lobe_level, double* ms, uint32_t* launches, uint32_t* waves_per_simd)
 {
     *ms = 0.0; *launches = 0; *waves_per_simd = 0;
     if (!state) return;
     PtHost* h = static_cast<PtHost*>(state);
     ForEachPair(h->ev, [&](uint32_t, float t) { *ms += t; *launches += 1; });
-    *waves_per_simd = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[glossy][0][0][0]) * (kTraceBlock / 256u);
+    *waves_per_simd = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[lobe_level][0][0][0]) * (kTraceBlock / 256u);
 }
 
-int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, bool glossy)
+int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, uint32_t lobe_level)
 {
     hipStream_t stream = CtxStream(ctx);
     PtHost* h = PtGetHost(ctx);
@@ -360,11 +363,11 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, bo
     const uint32_t top_records = std::min(h->tune.top_records, args_in.scene.n_top_records);
     const size_t lds = trace_lds_bytes(top_records);
     if (h->occupancy_lds != lds) {
-        LAUNCH_TRY(QueryOccupancy(&kPtKernels[0][0][0][0], &h->blocks_per_cu[0][0][0][0], 16, kTraceBlock, lds));
+        LAUNCH_TRY(QueryOccupancy(&kPtKernels[0][0][0][0], &h->blocks_per_cu[0][0][0][0], 24, kTraceBlock, lds));
         h->occupancy_lds = lds;
     }
     const bool tail = args_in.n_samples <= h->tune.tail_samples;              // a small call: mostly drain
-    const uint32_t blocks_per_cu = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[glossy][count][brute][tail]);
+    const uint32_t blocks_per_cu = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[lobe_level][count][brute][tail]);
     // the resident capacity of the chip, or fewer blocks when there are fewer than 64 paths per wave (a small call ends sooner when
     // its paths are spread thin than when the tail of a launch waits for 4 096 waves to find out that there is nothing to do)
     const uint32_t n_tiles = ((args_in.width + 7u) / 8u) * ((args_in.n_rows + 7u) / 8u);
@@ -431,7 +434,7 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, bo
         work_sizes(pt.n_paths, grid.x * (kTraceBlock / 64u), h->tune.fine_rounds, h->tune.chunk, pt.coarse, pt.fine_below);
         // the buffer's previous batch must have been accumulated (same stream: implicit)
         LAUNCH_TRY(hipEventRecord(NextEvent(h->ev), st));
-        hipLaunchKernelGGL(kPtKernels[glossy][count][brute][tail], grid, trace_block, lds, st, args_in, pt, bfirst, tt);
+        hipLaunchKernelGGL(kPtKernels[lobe_level][count][brute][tail], grid, trace_block, lds, st, args_in, pt, bfirst, tt);
         LAUNCH_TRY(hipEventRecord(NextEvent(h->ev), st));
         // accumulate in sample order: batch k after batch k-1
         if (n_streams == 2 && k > 0) LAUNCH_TRY(hipStreamWaitEvent(st, h->acc_done[(k - 1u) & 1u], 0));

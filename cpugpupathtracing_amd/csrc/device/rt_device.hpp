@@ -469,6 +469,7 @@ __device__ __forceinline__ V3 refract(V3 dir, V3 normal, float eta, float cosi, 
 struct Mat {
     V3 albedo; float specular, refractivity; V3 absorption; float ior; V3 emissive; float intensity; bool is_light;
     float alpha;          // GGX alpha = roughness^2 of the specular lobe (0: the mirror); read by the GLOSSY instantiations only
+    float alpha_t;        // GGX alpha = transmission roughness^2 of the dielectric lobe (0: polished); read by the GLOSSY == 2 instantiations only
 };
 __device__ __forceinline__ Mat load_material(const DevScene& sc, uint32_t index)
 {
@@ -478,7 +479,7 @@ __device__ __forceinline__ Mat load_material(const DevScene& sc, uint32_t index)
     m.albedo = mk(a.x, a.y, a.z); m.specular = a.w;
     m.refractivity = b.x; m.absorption = mk(b.y, b.z, b.w);
     m.ior = c.x; m.emissive = mk(c.y, c.z, c.w);
-    m.intensity = d.x; m.is_light = __float_as_uint(d.y) != 0u; m.alpha = d.z;
+    m.intensity = d.x; m.is_light = __float_as_uint(d.y) != 0u; m.alpha = d.z; m.alpha_t = d.w;
     return m;
 }
 

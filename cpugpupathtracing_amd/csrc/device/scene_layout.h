@@ -40,13 +40,14 @@ int LayoutScene(const cgpt_scene_desc& sd, SceneLayout& out, std::string& error)
 
 inline float AsFloat(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 
-// roughness: the specular lobe's (cgpt_scene_update_roughness); the record holds alpha = roughness^2, formed here once
-inline void PackMaterial(const cgpt_material& m, float roughness, float4 out[4])
+// roughness: the specular lobe's (cgpt_scene_update_roughness); transmission_roughness: the dielectric lobe's
+// (cgpt_scene_update_transmission_roughness); the record holds alpha = roughness^2 of each, formed here once
+inline void PackMaterial(const cgpt_material& m, float roughness, float transmission_roughness, float4 out[4])
 {
     out[0] = make_float4(m.albedo[0], m.albedo[1], m.albedo[2], m.specular);
     out[1] = make_float4(m.refractivity, m.absorption[0], m.absorption[1], m.absorption[2]);
     out[2] = make_float4(m.ior, m.emissive[0], m.emissive[1], m.emissive[2]);
-    out[3] = make_float4(m.intensity, AsFloat(m.is_light ? 1u : 0u), roughness * roughness, 0.0f);
+    out[3] = make_float4(m.intensity, AsFloat(m.is_light ? 1u : 0u), roughness * roughness, transmission_roughness * transmission_roughness);
 }
 
 // leaf-ordered triangle record (device_scene.h: tri_leaf) and original-order record (tri_orig) of one triangle

@@ -280,7 +280,7 @@ int LayoutScene(const cgpt_scene_desc& sd, SceneLayout& out, std::string& error)
 
     out.n_materials = sd.n_materials;
     out.materials.resize(4 * (size_t)sd.n_materials);
-    for (uint32_t i = 0; i < sd.n_materials; ++i) PackMaterial(sd.materials[i], 0.0f, out.materials.data() + 4 * (size_t)i);   // an upload resets roughness
+    for (uint32_t i = 0; i < sd.n_materials; ++i) PackMaterial(sd.materials[i], 0.0f, 0.0f, out.materials.data() + 4 * (size_t)i);   // an upload resets both roughnesses
     out.lights.assign(sd.light_indices, sd.light_indices + sd.n_lights);
 
     RenumberRecords(out);

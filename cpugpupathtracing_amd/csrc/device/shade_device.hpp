@@ -73,23 +73,25 @@ __device__ __forceinline__ LightSample sample_light(const DevScene& sc, uint32_t
     return ls;
 }
 
-// ---- rough specular lobe (GLOSSY instantiations) ----------------------------------------------------------------
-// Isotropic GGX reflection with the constant Fresnel `albedo` the mirror lobe has.  n is the shading normal turned to face the ray.
-// The microfacet normal h is drawn from the visible normals of wo (Heitz 2018, JCGT 7(4)) with u1, u2 -- the two draws after the lobe
-// choice -- and wi = reflect(-wo, h).  D and the sampling pdf cancel: the estimator's factor is G2 / G1 with the height-correlated
-// Smith G2 = 1 / (1 + L(wo) + L(wi)), G1 = 1 / (1 + L(wo)), L(w) = (-1 + sqrt(1 + alpha^2 tan^2(theta_w))) / 2.
-// Returns false when wi lies at or below the horizon of n (or wo grazes it): the lobe has no energy there.
-__device__ __forceinline__ bool ggx_sample(uint32_t& rng, V3 d, V3 normal, float alpha, V3& wi, float& weight)
+// ---- rough lobes (GLOSSY instantiations) ------------------------------------------------------------------
+// Smith L(w) = (-1 + sqrt(1 + alpha^2 tan^2(theta_w))) / 2 of a direction whose cosine to n is z (a2 = alpha^2).
+__device__ __forceinline__ float ggx_lambda(float a2, float z)
 {
-    const float u1 = random_float(rng);
-    const float u2 = random_float(rng);
-    const V3 n = dot(d, normal) > 0.0f ? -normal : normal;
+    return 0.5f * (-1.0f + sqrtf(1.0f + a2 * (max_std(0.0f, 1.0f - z * z) / (z * z))));
+}
+
+// A microfacet normal h from the visible normals of wo = -d (Heitz 2018, JCGT 7(4)) around n, the shading normal turned to face the ray,
+// with the two floats u1, u2.  oz = wo.n.  Returns false when wo lies at or below the horizon of n (h is then not set).
+__device__ __forceinline__ bool ggx_visible_normal(float u1, float u2, V3 d, V3 normal, float alpha, V3& n, float& oz, V3& h)
+{
+    n = dot(d, normal) > 0.0f ? -normal : normal;
     const float sign = copysignf(1.0f, n.z);                                  // orthonormal basis around n (Duff et al. 2017)
     const float a = -1.0f / (sign + n.z), b = n.x * n.y * a;
     const V3 tx = mk(1.0f + sign * n.x * n.x * a, sign * b, -sign * n.x);
     const V3 ty = mk(b, sign + n.y * n.y * a, -n.y);
     const V3 wo = -d;
-    const float ox = dot(wo, tx), oy = dot(wo, ty), oz = dot(wo, n);
+    const float ox = dot(wo, tx), oy = dot(wo, ty);
+    oz = dot(wo, n);
     if (!(oz > 0.0f)) return false;
     const V3 vh = normalize(mk(alpha * ox, alpha * oy, oz));                  // stretch wo to the alpha = 1 configuration
     const float lensq = vh.x * vh.x + vh.y * vh.y;
@@ -101,14 +103,64 @@ __device__ __forceinline__ bool ggx_sample(uint32_t& rng, V3 d, V3 normal, float
     const float p2 = (1.0f - s) * sqrtf(max_std(0.0f, 1.0f - p1 * p1)) + s * (rad * sinf(phi));
     const V3 nh = p1 * t1 + p2 * t2 + sqrtf(max_std(0.0f, 1.0f - p1 * p1 - p2 * p2)) * vh;
     const V3 hl = normalize(mk(alpha * nh.x, alpha * nh.y, max_std(0.0f, nh.z)));   // unstretch
-    wi = reflect(d, hl.x * tx + hl.y * ty + hl.z * n);
+    h = hl.x * tx + hl.y * ty + hl.z * n;
+    return true;
+}
+
+// Rough specular lobe (GLOSSY >= 1): isotropic GGX reflection with the constant Fresnel `albedo` the mirror lobe has.  h is drawn with
+// u1, u2 -- the two draws after the lobe choice -- and wi = reflect(-wo, h).  D and the sampling pdf cancel: the estimator's factor is
+// G2 / G1 with the height-correlated Smith G2 = 1 / (1 + L(wo) + L(wi)), G1 = 1 / (1 + L(wo)).
+// Returns false when wi lies at or below the horizon of n (or wo grazes it): the lobe has no energy there.
+__device__ __forceinline__ bool ggx_sample(uint32_t& rng, V3 d, V3 normal, float alpha, V3& wi, float& weight)
+{
+    const float u1 = random_float(rng);
+    const float u2 = random_float(rng);
+    V3 n, h; float oz;
+    if (!ggx_visible_normal(u1, u2, d, normal, alpha, n, oz, h)) return false;
+    wi = reflect(d, h);
     const float iz = dot(wi, n);
     if (!(iz > 0.0f)) return false;
     const float a2 = alpha * alpha;
-    const float lambda_o = 0.5f * (-1.0f + sqrtf(1.0f + a2 * (max_std(0.0f, 1.0f - oz * oz) / (oz * oz))));
-    const float lambda_i = 0.5f * (-1.0f + sqrtf(1.0f + a2 * (max_std(0.0f, 1.0f - iz * iz) / (iz * iz))));
+    const float lambda_o = ggx_lambda(a2, oz);
+    const float lambda_i = ggx_lambda(a2, iz);
     weight = (1.0f + lambda_o) / (1.0f + lambda_o + lambda_i);
     return true;
+}
+
+// Rough dielectric lobe (GLOSSY == 2, Walter et al. 2007): the smooth lobe's interface with the microfacet normal h in the role of the
+// normal.  Sides and indices are the smooth lobe's, from dot(normal, d); h comes from the visible normals with u1, u2; with c = wo.h and
+// k = 1 - eta^2 (1 - c^2), a facet with k >= 0 draws one more float against the reference's fresnel() and refracts when it is greater,
+// and a facet with k < 0 reflects totally (no draw) -- physical TIR, not the smooth lobe's re-traced ray or black leaf.  The factor is
+// G2 / G1 as in ggx_sample, L taken at |w.n|, for the reflected and the refracted w alike; no eta^2 scaling.
+// Returns kRoughGlassNone when w lies on the wrong side of n for its kind (or wo grazes it): no energy.
+enum : uint32_t { kRoughGlassNone = 0u, kRoughGlassReflect = 1u, kRoughGlassRefract = 2u };
+__device__ __forceinline__ uint32_t rough_glass_sample(uint32_t& rng, V3 d, V3 normal, float alpha, float ior, V3& w, float& weight, bool& inside)
+{
+    const float u1 = random_float(rng);
+    const float u2 = random_float(rng);
+    float etai = 1.0f, etat = ior;
+    inside = !(clamp_std(dot(normal, d), -1.0f, 1.0f) < 0.0f);
+    if (inside) { etai = ior; etat = 1.0f; }
+    const float eta = etai / etat;
+    V3 n, h; float oz;
+    if (!ggx_visible_normal(u1, u2, d, normal, alpha, n, oz, h)) return kRoughGlassNone;
+    const float dh = dot(d, h), c = -dh;
+    const float k = 1.0f - eta * eta * (1.0f - c * c);
+    bool refracts = false;
+    V3 wt = mk(0.0f);
+    if (k >= 0.0f) {
+        wt = refract(d, h, eta, c, k);
+        const float Fr = fresnel(dh, dot(wt, h), etai, etat);
+        refracts = random_float(rng) > Fr;
+    }
+    w = refracts ? wt : reflect(d, h);
+    const float wz = dot(w, n);
+    if (refracts ? !(wz < 0.0f) : !(wz > 0.0f)) return kRoughGlassNone;
+    const float a2 = alpha * alpha;
+    const float lambda_o = ggx_lambda(a2, oz);
+    const float lambda_w = ggx_lambda(a2, fabsf(wz));
+    weight = (1.0f + lambda_o) / (1.0f + lambda_o + lambda_w);
+    return refracts ? kRoughGlassRefract : kRoughGlassReflect;
 }
 
 struct PathState {
@@ -124,8 +176,9 @@ enum : uint32_t { kBounceChainShift = 4u, kChainReflect = 1u, kChainRefract = 2u
 // Processes the hit of `ray` (already traced).  On return: `ray` is the next extend ray unless kBounceTerminate is set;
 // if kBounceShadow is set, `shadow` / `pending` describe the NEE connection to trace (energy += pending when unoccluded,
 // ref: Main.cpp:452-463).  Emissive energy is added here; the final debug-view overrides are applied by the caller.
-// GLOSSY: the scene has a material with roughness > 0 (ggx_sample); without it the instantiation is the mirror-only code.
-template <bool COUNT, bool GLOSSY = false>
+// GLOSSY: 0 no rough lobe (the mirror-only code); 1 the scene has a material with roughness > 0 (ggx_sample); 2 it has one with a
+// transmission roughness > 0 (rough_glass_sample; this instantiation carries the rough specular lobe too).
+template <bool COUNT, int GLOSSY = 0>
 __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSettings& st, Ray& ray, PathState& ps, Ray& shadow,
                                                  V3& pending, Counters& cnt)
 {
@@ -169,7 +222,7 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
     }
 
     const float r = random_float(ps.rng);                                     // ref: Main.cpp:478
-    if (GLOSSY && r < mat.specular && mat.alpha > 0.0f) {                     // rough specular lobe
+    if (GLOSSY >= 1 && r < mat.specular && mat.alpha > 0.0f) {                     // rough specular lobe
         V3 gd; float g;
         if (!ggx_sample(ps.rng, ray.d, hit.normal, mat.alpha, gd, g)) return result | kBounceTerminate;   // below the horizon: ends as RR ends it
         ray = make_ray(hit.pos + gd * kNudge, gd, 1e34f);
@@ -181,6 +234,20 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
         ps.throughput = ps.throughput * mat.albedo;
         ps.is_specular = true;
         result |= kChainReflect << kBounceChainShift;
+    } else if (GLOSSY >= 2 && r < mat.specular + mat.refractivity && mat.alpha_t > 0.0f) {   // rough dielectric lobe
+        V3 gd; float g; bool inside;
+        const uint32_t kind = rough_glass_sample(ps.rng, ray.d, hit.normal, mat.alpha_t, mat.ior, gd, g, inside);
+        if (kind == kRoughGlassNone) return result | kBounceTerminate;       // the wrong side: ends as RR ends it
+        ps.throughput = ps.throughput * (mat.albedo * g);
+        if (kind == kRoughGlassRefract && inside) {                           // Beer's law on the way out only, as in the smooth lobe
+            V3 ab;
+            ab.x = expf(-mat.absorption.x * ray.t);
+            ab.y = expf(-mat.absorption.y * ray.t);
+            ab.z = expf(-mat.absorption.z * ray.t);
+            ps.throughput = ps.throughput * ab;
+        }
+        ray = make_ray(hit.pos + gd * kNudge, gd, 1e34f);
+        ps.is_specular = true;                                                // chain choice 0
     } else if (r < mat.specular + mat.refractivity) {                         // dielectric, ref: Main.cpp:488-546
         V3 N = hit.normal;
         float cosi = clamp_std(dot(N, ray.d), -1.0f, 1.0f);
@@ -255,8 +322,9 @@ enum : uint32_t { kBruteContinue = 0u, kBruteLeaf = 1u };
 
 // One TracePath level after IntersectScene(ray): either a leaf (returns its radiance in `leaf`) or a bounce (fills `level`,
 // replaces `ray` by the child ray).  RNG draw order as in the reference: r, then Fresnel choice or the hemisphere sample (or, GLOSSY, the
-// two draws of ggx_sample; a rough lobe below the horizon is a black leaf, as total internal reflection is).
-template <bool COUNT, bool GLOSSY = false>
+// draws of ggx_sample / rough_glass_sample; a rough lobe on the wrong side of the horizon is a black leaf, as the smooth lobe's total
+// internal reflection is).
+template <bool COUNT, int GLOSSY = 0>
 __device__ __forceinline__ uint32_t brute_bounce(const DevScene& sc, const DevSettings& st, Ray& ray, uint32_t& rng, uint32_t depth,
                                                  BruteLevel& level, V3& leaf, Counters& cnt)
 {
@@ -271,7 +339,7 @@ __device__ __forceinline__ uint32_t brute_bounce(const DevScene& sc, const DevSe
 
     const float r = random_float(rng);                                        // ref: Main.cpp:611
     level.cosi = 0.0f; level.absorb = mk(1.0f);
-    if (GLOSSY && r < mat.specular && mat.alpha > 0.0f) {                     // rough specular lobe: L = 0 + (albedo * G2/G1) * L
+    if (GLOSSY >= 1 && r < mat.specular && mat.alpha > 0.0f) {                     // rough specular lobe: L = 0 + (albedo * G2/G1) * L
         V3 gd; float g;
         if (!ggx_sample(rng, ray.d, hit.normal, mat.alpha, gd, g)) { leaf = mk(0.0f); return kBruteLeaf; }
         ray = make_ray(hit.pos + gd * kNudge, gd, 1e34f);
@@ -280,6 +348,17 @@ __device__ __forceinline__ uint32_t brute_bounce(const DevScene& sc, const DevSe
         const V3 sd = reflect(ray.d, hit.normal);
         ray = make_ray(hit.pos + sd * kNudge, sd, 1e34f);
         level.kind = 0u; level.a = mat.albedo;
+    } else if (GLOSSY >= 2 && r < mat.specular + mat.refractivity && mat.alpha_t > 0.0f) {   // rough dielectric lobe
+        V3 gd; float g; bool inside;
+        const uint32_t kind = rough_glass_sample(rng, ray.d, hit.normal, mat.alpha_t, mat.ior, gd, g, inside);
+        if (kind == kRoughGlassNone) { leaf = mk(0.0f); return kBruteLeaf; }
+        level.kind = kind == kRoughGlassRefract && inside ? 1u : 0u; level.a = mat.albedo * g;
+        if (level.kind == 1u) {
+            level.absorb.x = expf(-mat.absorption.x * ray.t);
+            level.absorb.y = expf(-mat.absorption.y * ray.t);
+            level.absorb.z = expf(-mat.absorption.z * ray.t);
+        }
+        ray = make_ray(hit.pos + gd * kNudge, gd, 1e34f);
     } else if (r < mat.specular + mat.refractivity) {                         // ref: Main.cpp:621-675
         V3 N = hit.normal;
         float cosi = clamp_std(dot(N, ray.d), -1.0f, 1.0f);

@@ -309,9 +309,9 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
 
 // ---- K3 shade: one bounce per extend hit; survivors compacted into this wave's output segment ---------------------------
 // BRUTE: the render has TracePath paths (RENDER_MODE_BRUTE_FORCE / COMPARISON); a separate instantiation, so the TracePathAdvanced
-// renders carry neither its code nor its registers.  GLOSSY: the scene has a rough specular material (shade_device.hpp: ggx_sample); a glossy
-// bounce reports lobe choice 0, so its ray is never elected or followed as a specular chain.
-template <bool COUNT, bool FIRST, bool BRUTE = false, bool GLOSSY = false>
+// renders carry neither its code nor its registers.  GLOSSY (the lobe level): 0 no rough lobe; 1 the scene has a rough specular material (shade_device.hpp: ggx_sample); 2 it has a rough dielectric (rough_glass_sample; carries the rough specular lobe too).
+// A rough bounce reports lobe choice 0, so its ray is never elected or followed as a specular chain.
+template <bool COUNT, bool FIRST, bool BRUTE = false, int GLOSSY = 0>
 __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, const WfDev wf, uint32_t batch_first)
 {
     constexpr bool first_round = FIRST;
@@ -732,11 +732,13 @@ static uint32_t CoprimeRotation(uint32_t n_waves, uint32_t n_tiles)
 static decltype(&wf_trace<false, false>) const kTraceKernels[2][2] = {
     { wf_trace<false, false>, wf_trace<false, true> }, { wf_trace<true, false>, wf_trace<true, true> },
 };
-static decltype(&wf_shade<false, false>) const kShadeKernels[2][2][2][2] = {
-    { { { wf_shade<false, false, false>, wf_shade<false, false, true> }, { wf_shade<false, true, false>, wf_shade<false, true, true> } },
-      { { wf_shade<true, false, false>, wf_shade<true, false, true> }, { wf_shade<true, true, false>, wf_shade<true, true, true> } } },
-    { { { wf_shade<false, false, false, true>, wf_shade<false, false, true, true> }, { wf_shade<false, true, false, true>, wf_shade<false, true, true, true> } },
-      { { wf_shade<true, false, false, true>, wf_shade<true, false, true, true> }, { wf_shade<true, true, false, true>, wf_shade<true, true, true, true> } } },
+static decltype(&wf_shade<false, false>) const kShadeKernels[3][2][2][2] = {
+    { { { wf_shade<false, false, false, 0>, wf_shade<false, false, true, 0> }, { wf_shade<false, true, false, 0>, wf_shade<false, true, true, 0> } },
+      { { wf_shade<true, false, false, 0>, wf_shade<true, false, true, 0> }, { wf_shade<true, true, false, 0>, wf_shade<true, true, true, 0> } } },
+    { { { wf_shade<false, false, false, 1>, wf_shade<false, false, true, 1> }, { wf_shade<false, true, false, 1>, wf_shade<false, true, true, 1> } },
+      { { wf_shade<true, false, false, 1>, wf_shade<true, false, true, 1> }, { wf_shade<true, true, false, 1>, wf_shade<true, true, true, 1> } } },
+    { { { wf_shade<false, false, false, 2>, wf_shade<false, false, true, 2> }, { wf_shade<false, true, false, 2>, wf_shade<false, true, true, 2> } },
+      { { wf_shade<true, false, false, 2>, wf_shade<true, false, true, 2> }, { wf_shade<true, true, false, 2>, wf_shade<true, true, true, 2> } } },
 };
 
 // What a pool's buffers are sized for (one record per render; the pools of a render are alike)
@@ -788,7 +790,7 @@ struct WfHost {
     uint32_t held_pools = 0;
     uint32_t spec_epoch[kMaxPools] = {};         // last epoch used in each pool's spec_tab
     uint32_t n_cus = 0;
-    uint32_t trace_blocks_per_cu[2][2] = {}, shade_blocks_per_cu[2][2][2] = {};   // trace: [COUNT][FIRST]; shade: [GLOSSY][COUNT][BRUTE]
+    uint32_t trace_blocks_per_cu[2][2] = {}, shade_blocks_per_cu[3][2][2] = {};   // trace: [COUNT][FIRST]; shade: [GLOSSY][COUNT][BRUTE]
     size_t occupancy_lds = 0;
     // hipEvent pairs around every trace launch of the last render (roofline accounting: the dominant kernel's own duration)
     EventPairs trace_ev;
@@ -882,7 +884,7 @@ int WavefrontSetTuning(cgpt_ctx* ctx, const char* name, uint32_t value)
     return h ? SetKnob(ctx, FindKnob(kKnobs, name), h->tune, name, value) : CGPT_ERR_HIP;
 }
 
-int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, bool glossy)
+int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, uint32_t lobe_level)
 {
     hipStream_t stream = CtxStream(ctx);
     WfHost* h = WfGetHost(ctx);
@@ -903,9 +905,9 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, boo
     if (h->occupancy_lds != trace_lds) {
         LAUNCH_TRY(QueryOccupancy(&kTraceKernels[0][0], &h->trace_blocks_per_cu[0][0], 4, kTraceBlock, trace_lds));
         // shade: the round-0 and later-round instantiations share one grid size (one output segment per wave)
-        uint32_t shade[2][2][2][2];
-        LAUNCH_TRY(QueryOccupancy(&kShadeKernels[0][0][0][0], &shade[0][0][0][0], 16, 256, 0));
-        for (int g = 0; g < 2; ++g)
+        uint32_t shade[3][2][2][2];
+        LAUNCH_TRY(QueryOccupancy(&kShadeKernels[0][0][0][0], &shade[0][0][0][0], 24, 256, 0));
+        for (int g = 0; g < 3; ++g)
             for (int c = 0; c < 2; ++c)
                 for (int b = 0; b < 2; ++b) h->shade_blocks_per_cu[g][c][b] = std::min(shade[g][c][0][b], shade[g][c][1][b]);
         h->occupancy_lds = trace_lds;
@@ -915,7 +917,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, boo
     const dim3 trace_grid_later(n_cus * std::min(h->tune.max_trace_blocks, h->trace_blocks_per_cu[count][0]));
     const bool brute = args_in.settings.render_mode != 2u;                    // the render has TracePath paths (ref: Main.cpp:719-729)
     const uint32_t brute_levels = brute ? (uint32_t)args_in.settings.max_ray_depth + 1u : 0u;
-    const uint32_t (&shade_blocks)[2][2] = h->shade_blocks_per_cu[glossy];   // the glossy scenes' shade kernels have grids of their own
+    const uint32_t (&shade_blocks)[2][2] = h->shade_blocks_per_cu[lobe_level];   // every lobe level's shade kernels have grids of their own
     const dim3 shade_grid(n_cus * shade_blocks[count][brute]);
     // one output segment per shade wave, sized for the most 64-item blocks a wave can be handed
     const uint32_t n_segs = n_cus * std::max({ shade_blocks[0][0], shade_blocks[1][0], shade_blocks[0][1], shade_blocks[1][1] }) * 4u;
@@ -1030,7 +1032,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, boo
                     }
                     wf.spec_epoch = h->spec_epoch[p];
                 }
-                hipLaunchKernelGGL(kShadeKernels[glossy][count][first][brute], shade_grid, block, 0, st, args, wf, bfirst);
+                hipLaunchKernelGGL(kShadeKernels[lobe_level][count][first][brute], shade_grid, block, 0, st, args, wf, bfirst);
                 hipLaunchKernelGGL(wf_plan, dim3(2u * wf.n_bands), dim3(256), 0, st, wf);
                 hipLaunchKernelGGL(wf_gather, dim3(std::min(2u * wf.n_segs, n_cus * 16u)), block, 0, st, wf);
                 launches += 3;

@@ -157,8 +157,10 @@ int cgpth_scene_set_material(cgpth_scene* scene, uint32_t index, const cgpt_mate
     return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
         if (!scene || !material || index >= scene->scene.materials.size()) return Fail("bad material index");
         const float roughness = scene->scene.materials[index].roughness;
+        const float transmission_roughness = scene->scene.materials[index].transmission_roughness;
         scene->scene.materials[index] = FromAbi(*material);
         scene->scene.materials[index].roughness = roughness;
+        scene->scene.materials[index].transmission_roughness = transmission_roughness;
         return CGPT_OK;
     });
 }
@@ -179,6 +181,26 @@ int cgpth_scene_get_roughness(const cgpth_scene* scene, float* out, uint32_t n)
         if (!scene || !out) return Fail("null argument");
         if (n != scene->scene.materials.size()) return Fail("expected " + std::to_string(scene->scene.materials.size()) + " values, got " + std::to_string(n));
         for (uint32_t i = 0; i < n; ++i) out[i] = scene->scene.materials[i].roughness;
+        return CGPT_OK;
+    });
+}
+
+int cgpth_scene_set_transmission_roughness(cgpth_scene* scene, uint32_t index, float roughness)
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        if (!scene || index >= scene->scene.materials.size()) return Fail("bad material index");
+        if (!(roughness >= 0.0f && roughness <= 1.0f)) return Fail("transmission roughness " + std::to_string(roughness) + " outside [0, 1]");
+        scene->scene.materials[index].transmission_roughness = roughness;
+        return CGPT_OK;
+    });
+}
+
+int cgpth_scene_get_transmission_roughness(const cgpth_scene* scene, float* out, uint32_t n)
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        if (!scene || !out) return Fail("null argument");
+        if (n != scene->scene.materials.size()) return Fail("expected " + std::to_string(scene->scene.materials.size()) + " values, got " + std::to_string(n));
+        for (uint32_t i = 0; i < n; ++i) out[i] = scene->scene.materials[i].transmission_roughness;
         return CGPT_OK;
     });
 }

@@ -25,6 +25,7 @@ struct Material {  // ref: Main.cpp:51-69
     float intensity = 0.0f;
     bool is_light = false;
     float roughness = 0.0f;   // the specular lobe's (microfacet BRDF, cgpt_scene_update_roughness); not part of cgpt_material
+    float transmission_roughness = 0.0f;   // the dielectric lobe's (rough glass, cgpt_scene_update_transmission_roughness); not part of cgpt_material
 
     Material() = default;
     Material(const Vec3& albedo_, float spec) : albedo(albedo_), specular(spec) {}

@@ -41,6 +41,7 @@ class Renderer:
         self.n_rows = 0               # rows of this context's band
         self.num_accumulated = 0      # ref: Main.cpp:205
         self._glossy = False          # the device holds a roughness > 0 (cgpt_scene_update_roughness)
+        self._rough_glass = False     # the device holds a transmission roughness > 0 (cgpt_scene_update_transmission_roughness)
 
     def _check(self, rc: int):
         if rc != 0:
@@ -50,23 +51,30 @@ class Renderer:
         self._check(self.L.cgpt_set_stream(self._ctx, C.c_void_p(hip_stream)))
 
     def upload(self, scene: Scene):
-        """cgpt_scene_upload, then the scene's roughness (cgpt_scene_update_roughness) when any is nonzero."""
+        """cgpt_scene_upload, then the scene's roughness (cgpt_scene_update_roughness) and transmission roughness
+        (cgpt_scene_update_transmission_roughness) when any is nonzero."""
         desc = scene.flatten()
         self._check(self.L.cgpt_scene_upload(self._ctx, C.byref(desc)))
-        self._glossy = False                                         # the upload reset every roughness to 0
+        self._glossy = self._rough_glass = False                     # the upload reset every roughness to 0
         self.scene = scene
         self._node_counts = [desc.objects[k].node_count for k in range(desc.n_objects)]   # the uploaded trees (export_bvh)
         rough = scene.roughness(desc.n_materials)
         if rough.any():
             self.update_roughness(rough)
+        rough_t = scene.transmission_roughness(desc.n_materials)
+        if rough_t.any():
+            self.update_transmission_roughness(rough_t)
 
     def update_materials(self, scene: Scene):
-        """cgpt_scene_update_materials, then the scene's roughness when it or the device's is nonzero."""
+        """cgpt_scene_update_materials, then each of the scene's two roughnesses when it or the device's is nonzero."""
         desc = scene.flatten()
         self._check(self.L.cgpt_scene_update_materials(self._ctx, desc.materials, desc.n_materials))
         rough = scene.roughness(desc.n_materials)
         if rough.any() or self._glossy:
             self.update_roughness(rough)
+        rough_t = scene.transmission_roughness(desc.n_materials)
+        if rough_t.any() or self._rough_glass:
+            self.update_transmission_roughness(rough_t)
 
     def update_roughness(self, values):
         """cgpt_scene_update_roughness: the specular lobe's roughness of every uploaded material (0: mirror, > 0: GGX with
@@ -74,6 +82,13 @@ class Renderer:
         v = np.ascontiguousarray(values, np.float32).ravel()
         self._check(self.L.cgpt_scene_update_roughness(self._ctx, v.ctypes.data_as(C.POINTER(C.c_float)), v.size))
         self._glossy = bool((v > 0.0).any())
+
+    def update_transmission_roughness(self, values):
+        """cgpt_scene_update_transmission_roughness: the dielectric lobe's transmission roughness of every uploaded material (0: polished
+        glass, > 0: GGX refraction with alpha_t = value^2).  Only the device copy changes; call reset_accumulator() before the next frame."""
+        v = np.ascontiguousarray(values, np.float32).ravel()
+        self._check(self.L.cgpt_scene_update_transmission_roughness(self._ctx, v.ctypes.data_as(C.POINTER(C.c_float)), v.size))
+        self._rough_glass = bool((v > 0.0).any())
 
     def refit_mesh(self, obj_index: int, triangles) -> float:
         """BVH refit on the device (cgpt_scene_refit_mesh): new triangles for uploaded mesh `obj_index` (or triangle object), in its

@@ -30,7 +30,9 @@ def _f3(v: Sequence[float]):
 @dataclass
 class Material:
     """ref: Source/Main.cpp:51-69, plus the specular lobe's roughness in [0, 1] (0: the reference's mirror; > 0: GGX reflection with
-    alpha = roughness^2, cgpt_scene_update_roughness).  to_abi() carries no roughness: the Scene forwards it through the host mirror."""
+    alpha = roughness^2, cgpt_scene_update_roughness) and the dielectric lobe's transmission roughness in [0, 1] (0: the reference's
+    polished glass; > 0: GGX refraction with alpha_t = transmission_roughness^2, cgpt_scene_update_transmission_roughness).  to_abi()
+    carries neither: the Scene forwards them through the host mirror."""
     albedo: Tuple[float, float, float] = (0.0, 0.0, 0.0)
     specular: float = 0.0
     refractivity: float = 0.0
@@ -40,6 +42,7 @@ class Material:
     intensity: float = 0.0
     is_light: bool = False
     roughness: float = 0.0
+    transmission_roughness: float = 0.0
 
     def to_abi(self) -> N.Material:
         m = N.Material()
@@ -201,21 +204,28 @@ class Scene:
     def add_material(self, m: Material) -> int:
         if not 0.0 <= m.roughness <= 1.0:               # (NaN fails too) refused before the material is added
             raise HostError(f"add_material: roughness {m.roughness} outside [0, 1]")
+        if not 0.0 <= m.transmission_roughness <= 1.0:
+            raise HostError(f"add_material: transmission_roughness {m.transmission_roughness} outside [0, 1]")
         abi = m.to_abi()
         rc = N.lib().cgpth_scene_add_material(self._h, C.byref(abi))
         if rc < 0:
             raise HostError(N.lib().cgpth_last_error().decode())
         if m.roughness != 0.0:
             self.set_roughness(rc, m.roughness)
+        if m.transmission_roughness != 0.0:
+            self.set_transmission_roughness(rc, m.transmission_roughness)
         return rc
 
     def set_material(self, index: int, m: Material):
-        """The whole material, roughness included."""
+        """The whole material, both roughnesses included."""
         if not 0.0 <= m.roughness <= 1.0:
             raise HostError(f"set_material: roughness {m.roughness} outside [0, 1]")
+        if not 0.0 <= m.transmission_roughness <= 1.0:
+            raise HostError(f"set_material: transmission_roughness {m.transmission_roughness} outside [0, 1]")
         abi = m.to_abi()
         _host_check(N.lib().cgpth_scene_set_material(self._h, index, C.byref(abi)), "set_material")
         self.set_roughness(index, m.roughness)
+        self.set_transmission_roughness(index, m.transmission_roughness)
 
     def set_roughness(self, index: int, roughness: float):
         """The specular lobe's roughness of material `index` (cgpth_scene_set_roughness)."""
@@ -226,6 +236,17 @@ class Scene:
         n = self.flatten().n_materials if n_materials is None else n_materials
         out = np.zeros(n, np.float32)
         _host_check(N.lib().cgpth_scene_get_roughness(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), n), "get_roughness")
+        return out
+
+    def set_transmission_roughness(self, index: int, transmission_roughness: float):
+        """The dielectric lobe's transmission roughness of material `index` (cgpth_scene_set_transmission_roughness)."""
+        _host_check(N.lib().cgpth_scene_set_transmission_roughness(self._h, index, float(transmission_roughness)), "set_transmission_roughness")
+
+    def transmission_roughness(self, n_materials=None) -> np.ndarray:
+        """Every material's transmission roughness, float32 (cgpth_scene_get_transmission_roughness)."""
+        n = self.flatten().n_materials if n_materials is None else n_materials
+        out = np.zeros(n, np.float32)
+        _host_check(N.lib().cgpth_scene_get_transmission_roughness(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), n), "get_transmission_roughness")
         return out
 
     def add_mesh(self, mesh: Mesh, mat_index: int, build_option: int = N.BUILD_SAH_INTERVALS, device_builder=None) -> int:

@@ -4,7 +4,7 @@
 //
 //   g++ -std=c++17 -Iinclude -Icpugpupathtracing_amd/csrc/host examples/render_main.cpp
 //       -Lcpugpupathtracing_amd/lib -lcpugpupt -Wl,-rpath,$PWD/cpugpupathtracing_amd/lib -o render_main   (one command line)
-//   ./render_main [--gpus N [--collective]] [--denoise] [--ground-roughness R] [--bvh intervals|binned] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
+//   ./render_main [--gpus N [--collective]] [--denoise] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
 // --gpus N: ONE context over the first N GPUs of the node (cgpt_ctx_create with n_devices = N): every frame is spread over them in
 // interleaved row bands and the read-back gathers the float4 bands with one RCCL exchange over xGMI; the loop below does not
 // change.  --collective: take that code path with N = 1 too (what a one-GPU box can test).
@@ -14,6 +14,8 @@
 // end (render_denoised.ppm) -- what a viewer with a "Denoise" toggle presents; the accumulator and the raw dumps are not affected.
 // --ground-roughness R: a glossy ground -- its material (1) gets specular 0.5 and roughness R in [0, 1] (cgpt_scene_update_roughness after
 // the upload; 0 keeps the mirror half of the lobe perfect).
+// --glass-roughness R: a frosted mesh -- its material (3, the glass) gets the transmission roughness R in [0, 1]
+// (cgpt_scene_update_transmission_roughness after the upload; 0 is the reference's polished glass).
 // --bvh binned: build the mesh's tree with BuildOption_SAHBinned (16 bins per axis) on the host instead of the reference's
 // SAH split intervals (the default; image parity with the reference is defined on that tree).
 // move_at > 0 scripts the input half of Update(dt) (ref: Main.cpp:277-297, Camera::Update :104-131): after that many samples the
@@ -41,13 +43,14 @@ using namespace cgpt;
 
 int main(int argc, char** argv)
 {
-    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; float ground_roughness = -1.0f;
+    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; float ground_roughness = -1.0f, glass_roughness = -1.0f;
     MeshBVH::BuildOption bvh_option = MeshBVH::BuildOption_SAHSplitIntervals;
     while (argc > 1 && std::string(argv[1]).rfind("--", 0) == 0) {
         if (std::string(argv[1]) == "--gpus" && argc > 2) { n_gpus = atoi(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--collective") { ctx_flags |= CGPT_CTX_FORCE_COLLECTIVE; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--denoise") { denoise = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--ground-roughness" && argc > 2) { ground_roughness = (float)atof(argv[2]); argv += 2; argc -= 2; }
+        else if (std::string(argv[1]) == "--glass-roughness" && argc > 2) { glass_roughness = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--bvh" && argc > 2 && (std::string(argv[2]) == "binned" || std::string(argv[2]) == "intervals")) {
             bvh_option = std::string(argv[2]) == "binned" ? MeshBVH::BuildOption_SAHBinned : MeshBVH::BuildOption_SAHSplitIntervals; argv += 2; argc -= 2;
         }
@@ -68,6 +71,7 @@ int main(int argc, char** argv)
     Scene scene = MakeReferenceScene(mesh, 3, (float)W / (float)H, bvh_option);            // ref: Main.cpp:777-819
     if (!scene.objects[0].valid) { fprintf(stderr, "the mesh is empty, or (--bvh binned) has a position that is not finite or beyond 1e30\n"); return 1; }
     if (ground_roughness >= 0.0f) { scene.materials[1].specular = 0.5f; scene.materials[1].roughness = ground_roughness; }
+    if (glass_roughness >= 0.0f) scene.materials[3].transmission_roughness = glass_roughness;
 
     cgpt_ctx* ctx = nullptr;
     // ThreadPool::Init: device_ids = NULL means devices 0 .. n_gpus-1
@@ -79,6 +83,11 @@ int main(int argc, char** argv)
         std::vector<float> roughness;
         for (const Material& m : scene.materials) roughness.push_back(m.roughness);
         CHECK(cgpt_scene_update_roughness(ctx, roughness.data(), (uint32_t)roughness.size()));
+    }
+    if (glass_roughness >= 0.0f) {                                       // nor is the transmission roughness
+        std::vector<float> roughness;
+        for (const Material& m : scene.materials) roughness.push_back(m.transmission_roughness);
+        CHECK(cgpt_scene_update_transmission_roughness(ctx, roughness.data(), (uint32_t)roughness.size()));
     }
 
     const cgpt_settings settings = scene.AbiSettings();

@@ -28,7 +28,8 @@ extern "C" {
                                  CGPT_OBJECT_TRIANGLE is a new enum value only, no layout changed; the denoiser added new symbols
                                  (cgpt_read_guides, cgpt_denoise) and a new struct (cgpt_denoise_params) only; the microfacet specular
                                  lobe added one new symbol (cgpt_scene_update_roughness) only; CGPT_BUILD_SAH_BINNED is a new enum
-                                 value only */
+                                 value only; the rough dielectric lobe added one new symbol
+                                 (cgpt_scene_update_transmission_roughness) only */
 
 enum cgpt_status {
     CGPT_OK = 0,
@@ -203,6 +204,17 @@ int cgpt_scene_update_materials(cgpt_ctx* ctx, const cgpt_material* materials, u
  * denoiser's cached guides stay valid: first hits and albedo do not depend on roughness.  A HIP failure during the write drops the
  * scene, as the geometry edits below do; a multi-device context updates every device. */
 int cgpt_scene_update_roughness(cgpt_ctx* ctx, const float* roughness, uint32_t n_materials);
+/* Rough dielectrics (frosted glass, Walter et al. 2007): the transmission roughness in [0, 1] of every material's dielectric lobe (the
+ * `specular <= r < specular + refractivity` branch), one value per uploaded material.  0 is the reference's polished interface, bit for
+ * bit; t > 0 refracts and reflects about a GGX microfacet normal with alpha_t = t^2, visible-normal sampling, the reference's Fresnel
+ * term at the facet, height-correlated Smith masking and physical total internal reflection at the facet.  It is
+ * separate from the roughness above: the specular lobe, the diffuse lobe and light materials ignore it, and the dielectric lobe ignores
+ * `roughness`.  cgpt_scene_upload resets every value to 0; cgpt_scene_update_materials and cgpt_scene_update_roughness keep it, and it
+ * keeps theirs.  Refused, with nothing changed: no scene (CGPT_ERR_NO_SCENE); the array NULL, n_materials other than the uploaded count,
+ * or a value that is not finite or lies outside [0, 1] (CGPT_ERR_INVALID).  The caller resets the accumulator, as with the materials.
+ * The denoiser's cached guides stay valid.  A HIP failure during the write drops the scene; a multi-device context updates every
+ * device. */
+int cgpt_scene_update_transmission_roughness(cgpt_ctx* ctx, const float* transmission_roughness, uint32_t n_materials);
 
 /* ---- in-place geometry edits of the uploaded scene (no re-upload; the caller resets the accumulator, as with the materials) ----
  * Every call validates before its first device write: a refused call leaves the device scene as it was.  If a HIP call fails after

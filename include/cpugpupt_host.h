@@ -50,12 +50,16 @@ void cgpth_scene_free(cgpth_scene* scene);
 /* the shipped scene (ref: Main.cpp:777-819) with `mesh` in place of the dragon and material `mesh_material` on it */
 cgpth_scene* cgpth_scene_reference_layout(const cgpth_mesh* mesh, uint32_t mesh_material, float aspect, int build_option);
 int cgpth_scene_add_material(cgpth_scene* scene, const cgpt_material* material);            /* returns index */
-int cgpth_scene_set_material(cgpth_scene* scene, uint32_t index, const cgpt_material* material);   /* keeps the material's roughness */
+int cgpth_scene_set_material(cgpth_scene* scene, uint32_t index, const cgpt_material* material);   /* keeps the material's roughness and transmission roughness */
 /* the specular lobe's roughness of material `index` (cgpt_scene_update_roughness holds the meaning and the validation: finite, in [0, 1]);
  * a new material has 0.  It is not part of cgpt_scene_desc: a host uploads the scene, then hands get_roughness's values to the device */
 int cgpth_scene_set_roughness(cgpth_scene* scene, uint32_t index, float roughness);
 /* out: n values, n == the scene's material count */
 int cgpth_scene_get_roughness(const cgpth_scene* scene, float* out, uint32_t n);
+/* the dielectric lobe's transmission roughness of material `index` (cgpt_scene_update_transmission_roughness holds the meaning and the
+ * validation: finite, in [0, 1]); a new material has 0; handed to the device after the upload, as the roughness is */
+int cgpth_scene_set_transmission_roughness(cgpth_scene* scene, uint32_t index, float transmission_roughness);
+int cgpth_scene_get_transmission_roughness(const cgpth_scene* scene, float* out, uint32_t n);
 int cgpth_scene_add_mesh(cgpth_scene* scene, const cgpth_mesh* mesh, uint32_t mat_index, int build_option);  /* Object ctor, ref: Main.cpp:247-251; returns object index */
 /* same result as cgpth_scene_add_mesh(..., CGPTH_BUILD_SAH_INTERVALS) with the tree built on the GPU by cgpt_bvh_build
  * (bit-identical tree; the host keeps validating and owning it) */
