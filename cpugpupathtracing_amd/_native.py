@@ -192,6 +192,11 @@ PROTOTYPES = {
     "cgpth_scene_layout": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(SceneLayoutView)]),
 }
 
+# exported for the tests, declared in csrc/device/ctx_internal.h: not part of the ABI that include/*.h declares
+DEBUG_PROTOTYPES = {
+    "cgpt_debug_live_device_bytes": (C.c_uint64, []),
+}
+
 _lib = None
 
 
@@ -209,7 +214,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} is missing: run `python -m cpugpupathtracing_amd.build` (hipcc, gfx950). "
             "There is no CPU or Python fallback for the render path.")
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **DEBUG_PROTOTYPES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError as e:

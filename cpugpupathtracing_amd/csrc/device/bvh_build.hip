@@ -34,13 +34,13 @@
 #include <vector>
 
 #include "cpugpupt_abi.h"
+#include "device_memory.h"
 #include "minmax_std.h"
 
 namespace cgpt {
 
 hipStream_t CtxStream(cgpt_ctx* ctx);
 int CtxDevice(cgpt_ctx* ctx);
-int CtxFail(cgpt_ctx* ctx, int code, const char* fmt, ...);
 cgpt_ctx* GroupFirstMemberOrNull(cgpt_ctx* ctx);
 int GroupForwarded(cgpt_ctx* ctx, int rc);
 
@@ -936,9 +936,9 @@ extern "C" int cgpt_bvh_build_ex(cgpt_ctx* ctx, const cgpt_triangle* triangles, 
     if (!ctx) return CGPT_ERR_INVALID;
     cgpt_ctx* const first = GroupFirstMemberOrNull(ctx);                       // a multi-device context builds on its first device
     cgpt_ctx* const target = first ? first : ctx;
-    int rc;
-    try { rc = BuildOnDevice(target, triangles, n_tris, build_option, initial_tri_indices, nodes_out, n_nodes_out, tri_indices_out, max_depth_out, total_area_out); }
-    catch (const std::exception& e) { rc = CtxFail(target, CGPT_ERR_INVALID, "cgpt_bvh_build: %s", e.what()); }   // host vectors: nothing unwinds through the C ABI
+    const int rc = Guarded(target, "cgpt_bvh_build", [&] {                    // host vectors
+        return BuildOnDevice(target, triangles, n_tris, build_option, initial_tri_indices, nodes_out, n_nodes_out, tri_indices_out, max_depth_out, total_area_out);
+    });
     return first ? GroupForwarded(ctx, rc) : rc;
 }
 
@@ -976,18 +976,11 @@ static int BuildOnDevice(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t
     hipStream_t stream = CtxStream(ctx);
     if (hipSetDevice(CtxDevice(ctx)) != hipSuccess) return CtxFail(ctx, CGPT_ERR_HIP, "cgpt_bvh_build: hipSetDevice failed");
 
-#define BV_TRY(expr)                                                                                                          \
-    do {                                                                                                                      \
-        hipError_t e_ = (expr);                                                                                               \
-        if (e_ != hipSuccess) { rc = CtxFail(ctx, CGPT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); goto done; } \
-    } while (0)
-
-    int rc = CGPT_OK;
-    cgpt_triangle* d_tris = nullptr; F3 *d_lo = nullptr, *d_hi = nullptr, *d_c = nullptr;
-    uint32_t *d_idx = nullptr, *d_scratch = nullptr, *d_sa = nullptr, *d_sb = nullptr, *d_counters = nullptr;
-    BuildNode* d_nodes = nullptr; cgpt_bvh_node* d_out = nullptr;
-    WidePartial* d_partial = nullptr; WideDecision* d_decision = nullptr; uint32_t *d_piece_left = nullptr, *d_piece_front = nullptr; WideChild* d_piece_child = nullptr;
-    Bounds* d_cbounds = nullptr; uint32_t *d_root_keys = nullptr, *d_gbins = nullptr, *d_piece_count = nullptr; BinnedDecision* d_bdecision = nullptr;
+    DevBuf<cgpt_triangle> d_tris; DevBuf<F3> d_lo, d_hi, d_c;
+    DevBuf<uint32_t> d_idx, d_scratch, d_sa, d_sb, d_counters;
+    DevBuf<BuildNode> d_nodes; DevBuf<cgpt_bvh_node> d_out;
+    DevBuf<WidePartial> d_partial; DevBuf<WideDecision> d_decision; DevBuf<uint32_t> d_piece_left, d_piece_front; DevBuf<WideChild> d_piece_child;
+    DevBuf<Bounds> d_cbounds; DevBuf<uint32_t> d_root_keys, d_gbins, d_piece_count; DevBuf<BinnedDecision> d_bdecision;
     BinnedArrays Bn{};
     uint32_t quarter_tris = 32;                                               // ... and one quarter wavefront per node
     uint32_t wave_tris = 2048;                                                // average triangles per node up to which a level runs one wavefront per node
@@ -997,132 +990,124 @@ static int BuildOnDevice(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t
     uint32_t counters[2] = { 0, 0 };
     uint32_t n_nodes = 0;
     BuildArrays A{};
-    {
-        BV_TRY(hipMalloc((void**)&d_tris, (size_t)n_tris * sizeof(cgpt_triangle)));
-        BV_TRY(hipMalloc((void**)&d_lo, (size_t)n_tris * sizeof(F3)));
-        BV_TRY(hipMalloc((void**)&d_hi, (size_t)n_tris * sizeof(F3)));
-        BV_TRY(hipMalloc((void**)&d_c, (size_t)n_tris * sizeof(F3)));
-        BV_TRY(hipMalloc((void**)&d_idx, (size_t)n_tris * 4)); BV_TRY(hipMalloc((void**)&d_scratch, (size_t)n_tris * 4));
-        if (!binned) { BV_TRY(hipMalloc((void**)&d_sa, (size_t)n_tris * 4)); BV_TRY(hipMalloc((void**)&d_sb, (size_t)n_tris * 4)); }
-        BV_TRY(hipMalloc((void**)&d_counters, 2 * 4));
-        BV_TRY(hipMalloc((void**)&d_nodes, (size_t)max_nodes * sizeof(BuildNode)));
-        BV_TRY(hipMalloc((void**)&d_out, (size_t)max_nodes * sizeof(cgpt_bvh_node)));
-        BV_TRY(hipMalloc((void**)&d_piece_left, (size_t)kWideBlocks * 4));
-        if (!binned) {
-            BV_TRY(hipMalloc((void**)&d_partial, (size_t)kWideBlocks * kCandidates * sizeof(WidePartial)));
-            BV_TRY(hipMalloc((void**)&d_decision, (size_t)kWideBlocks * sizeof(WideDecision)));
-            BV_TRY(hipMalloc((void**)&d_piece_front, (size_t)kWideBlocks * 4));
-            BV_TRY(hipMalloc((void**)&d_piece_child, (size_t)kWideBlocks * sizeof(WideChild)));
-        } else {
-            BV_TRY(hipMalloc((void**)&d_cbounds, (size_t)max_nodes * sizeof(Bounds)));
-            BV_TRY(hipMalloc((void**)&d_root_keys, 12 * 4));
-            BV_TRY(hipMalloc((void**)&d_gbins, (size_t)kWideBlocks * kNodeBinWords * 4));
-            BV_TRY(hipMalloc((void**)&d_piece_count, (size_t)kWideBlocks * 3 * kBins * 4));
-            BV_TRY(hipMalloc((void**)&d_bdecision, (size_t)kWideBlocks * sizeof(BinnedDecision)));
-        }
-        if (const char* e = getenv("CGPT_BVH_WAVE_TRIS")) wave_tris = (uint32_t)std::max(0l, strtol(e, nullptr, 10));     // tests: 0 = workgroups only
-        if (const char* e = getenv("CGPT_BVH_QUARTER_TRIS")) quarter_tris = (uint32_t)std::max(0l, strtol(e, nullptr, 10));
-        if (const char* e = getenv("CGPT_BVH_PIECE_TRIS")) piece_tris = (uint32_t)std::max(1l, strtol(e, nullptr, 10));   // tests: the wide path on small meshes
-        BV_TRY(hipMemcpyAsync(d_tris, triangles, (size_t)n_tris * sizeof(cgpt_triangle), hipMemcpyHostToDevice, stream));
-        if (initial_tri_indices) BV_TRY(hipMemcpyAsync(d_idx, initial_tri_indices, (size_t)n_tris * 4, hipMemcpyHostToDevice, stream));   // Rebuild: the current order
-        A.naive = build_option == CGPT_BUILD_NAIVE_SPLIT ? 1u : 0u;
-        A.tri_lo = d_lo; A.tri_hi = d_hi; A.centroid = d_c; A.tri_indices = d_idx; A.scratch_idx = d_scratch; A.sel_a = d_sa; A.sel_b = d_sb;
-        A.nodes = d_nodes; A.counters = d_counters;
-        A.partial = d_partial; A.decision = d_decision; A.piece_left = d_piece_left; A.piece_front = d_piece_front; A.piece_child = d_piece_child;
-        hipLaunchKernelGGL(prepare_triangles, dim3((n_tris + 255u) / 256u), dim3(256), 0, stream, d_tris, n_tris, d_lo, d_hi, d_c, d_idx, initial_tri_indices ? 0u : 1u);
-        Bn.cbounds = d_cbounds; Bn.root_keys = d_root_keys; Bn.gbins = d_gbins; Bn.piece_count = d_piece_count; Bn.piece_left = d_piece_left; Bn.decision = d_bdecision;
-        if (binned) {
-            BV_TRY(hipMemsetAsync(d_root_keys, 0, 12 * 4, stream));
-            hipLaunchKernelGGL(binned_root_fold, dim3(std::min(1024u, (n_tris + kBuildThreads - 1u) / kBuildThreads)), dim3(kBuildThreads), 0, stream, A, Bn, n_tris);
-            hipLaunchKernelGGL(binned_root_node, dim3(1), dim3(1), 0, stream, A, Bn, n_tris);
-        } else {
-            hipLaunchKernelGGL(root_bounds, dim3(1), dim3(kBuildThreads), 0, stream, A, n_tris);
-        }
-        // SAH split primitives (ref: BVH.cpp:260-297): cheapest_cost stays 1e30 because the loop never assigns it (SURVEY A-5), so
-        // "cheapest_cost >= parent_cost" ends the build at the root whenever the root's cost is an ordinary number.  A root cost
-        // of NaN or beyond 1e30 (bounds near the float limit) would take the reference into Split with the last candidate plane:
-        // that corner is left to the host build.
-        bool root_only = false;
-        if (build_option == CGPT_BUILD_SAH_SPLIT_PRIMITIVES) {
-            BuildNode root{};
-            BV_TRY(hipMemcpyAsync(&root, d_nodes, sizeof(root), hipMemcpyDeviceToHost, stream));
-            BV_TRY(hipStreamSynchronize(stream));
-            const float ex = root.hi.x - root.lo.x, ey = root.hi.y - root.lo.y, ez = root.hi.z - root.lo.z;
-            const float parent_cost = (ex * ey + ey * ez + ez * ex) * (float)n_tris;
-            if (!(1e30f >= parent_cost)) { rc = CtxFail(ctx, CGPT_ERR_UNSUPPORTED, "cgpt_bvh_build: SAH-split-primitives on bounds whose cost is not below 1e30: use the host build"); goto done; }
-            root_only = true;
-        }
-
-        // level by level: the nodes created while level L is processed are exactly level L + 1
-        uint32_t first = 0, count = 1;
-        if (root_only) { level_first.push_back(0); counters[0] = 1; counters[1] = 0; count = 0; }
-        while (count > 0) {
-            level_first.push_back(first);
-            // few, big nodes: pieces of ~piece_tris triangles or more, at most kWideBlocks of them per level
-            const uint32_t pieces = std::min(kWideBlocks / std::min(count, kWideBlocks), std::max(1u, n_tris / count / piece_tris));
-            if (binned) {
-                if (count <= kWideBlocks && pieces >= 2u) {
-                    const dim3 grid(count * pieces), per_node(count), block(kBuildThreads);
-                    hipLaunchKernelGGL(binned_wide_clear, dim3((count * kNodeBinWords + 255u) / 256u), dim3(256), 0, stream, d_gbins, count * kNodeBinWords);
-                    hipLaunchKernelGGL(binned_wide_hist, grid, block, 0, stream, A, Bn, first, pieces);
-                    hipLaunchKernelGGL(binned_wide_decide, per_node, dim3(64), 0, stream, A, Bn, first, pieces);
-                    hipLaunchKernelGGL(binned_wide_scatter, grid, block, 0, stream, A, Bn, first, pieces);
-                    hipLaunchKernelGGL(binned_wide_copy, grid, block, 0, stream, A, Bn, first, pieces);
-                } else if ((uint64_t)count * wave_tris < n_tris) {
-                    hipLaunchKernelGGL(binned_level<kBuildThreads>, dim3(count), dim3(kBuildThreads), 0, stream, A, Bn, first, count);
-                } else if ((uint64_t)count * quarter_tris < n_tris) {
-                    hipLaunchKernelGGL(binned_level<64>, dim3((count + 3u) / 4u), dim3(kBuildThreads), 0, stream, A, Bn, first, count);
-                } else {
-                    hipLaunchKernelGGL(binned_level<16>, dim3((count + 15u) / 16u), dim3(kBuildThreads), 0, stream, A, Bn, first, count);
-                }
-            } else if (count <= kWideBlocks && pieces >= 2u) {
-                const dim3 grid(count * pieces), per_node(count), block(kBuildThreads);
-                hipLaunchKernelGGL(wide_sah_partial, grid, block, 0, stream, A, first, pieces);
-                hipLaunchKernelGGL(wide_decide, per_node, dim3(64), 0, stream, A, first, pieces);
-                hipLaunchKernelGGL(wide_tables, grid, block, 0, stream, A, first, pieces);
-                hipLaunchKernelGGL(wide_write, grid, block, 0, stream, A, first, pieces);
-                hipLaunchKernelGGL(wide_finish_piece, grid, block, 0, stream, A, first, pieces);
-                hipLaunchKernelGGL(wide_children, per_node, dim3(64), 0, stream, A, first, pieces);
-            } else if ((uint64_t)count * wave_tris < n_tris) {                  // big nodes on average: a workgroup per node
-                hipLaunchKernelGGL(subdivide_level<kBuildThreads>, dim3(count), dim3(kBuildThreads), 0, stream, A, first, count);
-            } else if ((uint64_t)count * quarter_tris < n_tris) {               // the deep levels: a wavefront per node
-                hipLaunchKernelGGL(subdivide_level<64>, dim3((count + 3u) / 4u), dim3(kBuildThreads), 0, stream, A, first, count);
-            } else {                                                          // the deepest: a handful of triangles per node, 16 lanes each
-                hipLaunchKernelGGL(subdivide_level<16>, dim3((count + 15u) / 16u), dim3(kBuildThreads), 0, stream, A, first, count);
-            }
-            BV_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, stream));
-            BV_TRY(hipStreamSynchronize(stream));
-            first += count;
-            count = counters[0] - first;
-            if (level_first.size() > 4096) { rc = CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: tree deeper than 4096 levels"); goto done; }
-        }
-        n_nodes = counters[0];
-        level_first.push_back(n_nodes);
-        // splitting-node counts bottom-up, preorder ranks and final ids top-down
-        for (size_t l = level_first.size() - 1; l-- > 0;) {
-            const uint32_t c = level_first[l + 1] - level_first[l];
-            hipLaunchKernelGGL(count_splits_level, dim3((c + 255u) / 256u), dim3(256), 0, stream, d_nodes, level_first[l], c);
-        }
-        for (size_t l = 0; l + 1 < level_first.size(); ++l) {
-            const uint32_t c = level_first[l + 1] - level_first[l];
-            hipLaunchKernelGGL(assign_ids_level, dim3((c + 255u) / 256u), dim3(256), 0, stream, d_nodes, level_first[l], c);
-        }
-        hipLaunchKernelGGL(emit_nodes, dim3((n_nodes + 255u) / 256u), dim3(256), 0, stream, d_nodes, n_nodes, d_out);
-        BV_TRY(hipGetLastError());
-        BV_TRY(hipMemcpyAsync(nodes_out, d_out, (size_t)n_nodes * sizeof(cgpt_bvh_node), hipMemcpyDeviceToHost, stream));
-        BV_TRY(hipMemcpyAsync(tri_indices_out, d_idx, (size_t)n_tris * 4, hipMemcpyDeviceToHost, stream));
-        BV_TRY(hipStreamSynchronize(stream));
-        *n_nodes_out = n_nodes;
-        *max_depth_out = binned ? (uint32_t)level_first.size() - 2u : counters[1];   // binned: level L holds the nodes of depth L (no atomicMax per node)
-        float area = 0.0f;                                                    // m_total_area: a sequential float sum (ref: BVH.cpp:22)
-        for (uint32_t i = 0; i < n_tris; ++i) area += HostTriangleArea(triangles[i]);
-        *total_area_out = area;
+    HIP_TRY(ctx, d_tris.Alloc(n_tris));
+    HIP_TRY(ctx, d_lo.Alloc(n_tris));
+    HIP_TRY(ctx, d_hi.Alloc(n_tris));
+    HIP_TRY(ctx, d_c.Alloc(n_tris));
+    HIP_TRY(ctx, d_idx.Alloc(n_tris)); HIP_TRY(ctx, d_scratch.Alloc(n_tris));
+    if (!binned) { HIP_TRY(ctx, d_sa.Alloc(n_tris)); HIP_TRY(ctx, d_sb.Alloc(n_tris)); }
+    HIP_TRY(ctx, d_counters.Alloc(2));
+    HIP_TRY(ctx, d_nodes.Alloc(max_nodes));
+    HIP_TRY(ctx, d_out.Alloc(max_nodes));
+    HIP_TRY(ctx, d_piece_left.Alloc(kWideBlocks));
+    if (!binned) {
+        HIP_TRY(ctx, d_partial.Alloc((size_t)kWideBlocks * kCandidates));
+        HIP_TRY(ctx, d_decision.Alloc(kWideBlocks));
+        HIP_TRY(ctx, d_piece_front.Alloc(kWideBlocks));
+        HIP_TRY(ctx, d_piece_child.Alloc(kWideBlocks));
+    } else {
+        HIP_TRY(ctx, d_cbounds.Alloc(max_nodes));
+        HIP_TRY(ctx, d_root_keys.Alloc(12));
+        HIP_TRY(ctx, d_gbins.Alloc((size_t)kWideBlocks * kNodeBinWords));
+        HIP_TRY(ctx, d_piece_count.Alloc((size_t)kWideBlocks * 3 * kBins));
+        HIP_TRY(ctx, d_bdecision.Alloc(kWideBlocks));
     }
-done:
-    (void)hipFree(d_tris); (void)hipFree(d_lo); (void)hipFree(d_hi); (void)hipFree(d_c); (void)hipFree(d_idx); (void)hipFree(d_scratch);
-    (void)hipFree(d_sa); (void)hipFree(d_sb); (void)hipFree(d_counters); (void)hipFree(d_nodes); (void)hipFree(d_out);
-    (void)hipFree(d_partial); (void)hipFree(d_decision); (void)hipFree(d_piece_left); (void)hipFree(d_piece_front); (void)hipFree(d_piece_child);
-    (void)hipFree(d_cbounds); (void)hipFree(d_root_keys); (void)hipFree(d_gbins); (void)hipFree(d_piece_count); (void)hipFree(d_bdecision);
-#undef BV_TRY
-    return rc;
+    if (const char* e = getenv("CGPT_BVH_WAVE_TRIS")) wave_tris = (uint32_t)std::max(0l, strtol(e, nullptr, 10));     // tests: 0 = workgroups only
+    if (const char* e = getenv("CGPT_BVH_QUARTER_TRIS")) quarter_tris = (uint32_t)std::max(0l, strtol(e, nullptr, 10));
+    if (const char* e = getenv("CGPT_BVH_PIECE_TRIS")) piece_tris = (uint32_t)std::max(1l, strtol(e, nullptr, 10));   // tests: the wide path on small meshes
+    HIP_TRY(ctx, hipMemcpyAsync(d_tris.p, triangles, (size_t)n_tris * sizeof(cgpt_triangle), hipMemcpyHostToDevice, stream));
+    if (initial_tri_indices) HIP_TRY(ctx, hipMemcpyAsync(d_idx.p, initial_tri_indices, (size_t)n_tris * 4, hipMemcpyHostToDevice, stream));   // Rebuild: the current order
+    A.naive = build_option == CGPT_BUILD_NAIVE_SPLIT ? 1u : 0u;
+    A.tri_lo = d_lo.p; A.tri_hi = d_hi.p; A.centroid = d_c.p; A.tri_indices = d_idx.p; A.scratch_idx = d_scratch.p; A.sel_a = d_sa.p; A.sel_b = d_sb.p;
+    A.nodes = d_nodes.p; A.counters = d_counters.p;
+    A.partial = d_partial.p; A.decision = d_decision.p; A.piece_left = d_piece_left.p; A.piece_front = d_piece_front.p; A.piece_child = d_piece_child.p;
+    hipLaunchKernelGGL(prepare_triangles, dim3((n_tris + 255u) / 256u), dim3(256), 0, stream, d_tris.p, n_tris, d_lo.p, d_hi.p, d_c.p, d_idx.p, initial_tri_indices ? 0u : 1u);
+    Bn.cbounds = d_cbounds.p; Bn.root_keys = d_root_keys.p; Bn.gbins = d_gbins.p; Bn.piece_count = d_piece_count.p; Bn.piece_left = d_piece_left.p; Bn.decision = d_bdecision.p;
+    if (binned) {
+        HIP_TRY(ctx, hipMemsetAsync(d_root_keys.p, 0, 12 * 4, stream));
+        hipLaunchKernelGGL(binned_root_fold, dim3(std::min(1024u, (n_tris + kBuildThreads - 1u) / kBuildThreads)), dim3(kBuildThreads), 0, stream, A, Bn, n_tris);
+        hipLaunchKernelGGL(binned_root_node, dim3(1), dim3(1), 0, stream, A, Bn, n_tris);
+    } else {
+        hipLaunchKernelGGL(root_bounds, dim3(1), dim3(kBuildThreads), 0, stream, A, n_tris);
+    }
+    // SAH split primitives (ref: BVH.cpp:260-297): cheapest_cost stays 1e30 because the loop never assigns it (SURVEY A-5), so
+    // "cheapest_cost >= parent_cost" ends the build at the root whenever the root's cost is an ordinary number.  A root cost
+    // of NaN or beyond 1e30 (bounds near the float limit) would take the reference into Split with the last candidate plane:
+    // that corner is left to the host build.
+    bool root_only = false;
+    if (build_option == CGPT_BUILD_SAH_SPLIT_PRIMITIVES) {
+        BuildNode root{};
+        HIP_TRY(ctx, hipMemcpyAsync(&root, d_nodes.p, sizeof(root), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+        const float ex = root.hi.x - root.lo.x, ey = root.hi.y - root.lo.y, ez = root.hi.z - root.lo.z;
+        const float parent_cost = (ex * ey + ey * ez + ez * ex) * (float)n_tris;
+        if (!(1e30f >= parent_cost)) return CtxFail(ctx, CGPT_ERR_UNSUPPORTED, "cgpt_bvh_build: SAH-split-primitives on bounds whose cost is not below 1e30: use the host build");
+        root_only = true;
+    }
+
+    // level by level: the nodes created while level L is processed are exactly level L + 1
+    uint32_t first = 0, count = 1;
+    if (root_only) { level_first.push_back(0); counters[0] = 1; counters[1] = 0; count = 0; }
+    while (count > 0) {
+        level_first.push_back(first);
+        // few, big nodes: pieces of ~piece_tris triangles or more, at most kWideBlocks of them per level
+        const uint32_t pieces = std::min(kWideBlocks / std::min(count, kWideBlocks), std::max(1u, n_tris / count / piece_tris));
+        if (binned) {
+            if (count <= kWideBlocks && pieces >= 2u) {
+                const dim3 grid(count * pieces), per_node(count), block(kBuildThreads);
+                hipLaunchKernelGGL(binned_wide_clear, dim3((count * kNodeBinWords + 255u) / 256u), dim3(256), 0, stream, d_gbins.p, count * kNodeBinWords);
+                hipLaunchKernelGGL(binned_wide_hist, grid, block, 0, stream, A, Bn, first, pieces);
+                hipLaunchKernelGGL(binned_wide_decide, per_node, dim3(64), 0, stream, A, Bn, first, pieces);
+                hipLaunchKernelGGL(binned_wide_scatter, grid, block, 0, stream, A, Bn, first, pieces);
+                hipLaunchKernelGGL(binned_wide_copy, grid, block, 0, stream, A, Bn, first, pieces);
+            } else if ((uint64_t)count * wave_tris < n_tris) {
+                hipLaunchKernelGGL(binned_level<kBuildThreads>, dim3(count), dim3(kBuildThreads), 0, stream, A, Bn, first, count);
+            } else if ((uint64_t)count * quarter_tris < n_tris) {
+                hipLaunchKernelGGL(binned_level<64>, dim3((count + 3u) / 4u), dim3(kBuildThreads), 0, stream, A, Bn, first, count);
+            } else {
+                hipLaunchKernelGGL(binned_level<16>, dim3((count + 15u) / 16u), dim3(kBuildThreads), 0, stream, A, Bn, first, count);
+            }
+        } else if (count <= kWideBlocks && pieces >= 2u) {
+            const dim3 grid(count * pieces), per_node(count), block(kBuildThreads);
+            hipLaunchKernelGGL(wide_sah_partial, grid, block, 0, stream, A, first, pieces);
+            hipLaunchKernelGGL(wide_decide, per_node, dim3(64), 0, stream, A, first, pieces);
+            hipLaunchKernelGGL(wide_tables, grid, block, 0, stream, A, first, pieces);
+            hipLaunchKernelGGL(wide_write, grid, block, 0, stream, A, first, pieces);
+            hipLaunchKernelGGL(wide_finish_piece, grid, block, 0, stream, A, first, pieces);
+            hipLaunchKernelGGL(wide_children, per_node, dim3(64), 0, stream, A, first, pieces);
+        } else if ((uint64_t)count * wave_tris < n_tris) {                  // big nodes on average: a workgroup per node
+            hipLaunchKernelGGL(subdivide_level<kBuildThreads>, dim3(count), dim3(kBuildThreads), 0, stream, A, first, count);
+        } else if ((uint64_t)count * quarter_tris < n_tris) {               // the deep levels: a wavefront per node
+            hipLaunchKernelGGL(subdivide_level<64>, dim3((count + 3u) / 4u), dim3(kBuildThreads), 0, stream, A, first, count);
+        } else {                                                          // the deepest: a handful of triangles per node, 16 lanes each
+            hipLaunchKernelGGL(subdivide_level<16>, dim3((count + 15u) / 16u), dim3(kBuildThreads), 0, stream, A, first, count);
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(counters, d_counters.p, sizeof(counters), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+        first += count;
+        count = counters[0] - first;
+        if (level_first.size() > 4096) return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: tree deeper than 4096 levels");
+    }
+    n_nodes = counters[0];
+    level_first.push_back(n_nodes);
+    // splitting-node counts bottom-up, preorder ranks and final ids top-down
+    for (size_t l = level_first.size() - 1; l-- > 0;) {
+        const uint32_t c = level_first[l + 1] - level_first[l];
+        hipLaunchKernelGGL(count_splits_level, dim3((c + 255u) / 256u), dim3(256), 0, stream, d_nodes.p, level_first[l], c);
+    }
+    for (size_t l = 0; l + 1 < level_first.size(); ++l) {
+        const uint32_t c = level_first[l + 1] - level_first[l];
+        hipLaunchKernelGGL(assign_ids_level, dim3((c + 255u) / 256u), dim3(256), 0, stream, d_nodes.p, level_first[l], c);
+    }
+    hipLaunchKernelGGL(emit_nodes, dim3((n_nodes + 255u) / 256u), dim3(256), 0, stream, d_nodes.p, n_nodes, d_out.p);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(nodes_out, d_out.p, (size_t)n_nodes * sizeof(cgpt_bvh_node), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(tri_indices_out, d_idx.p, (size_t)n_tris * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    *n_nodes_out = n_nodes;
+    *max_depth_out = binned ? (uint32_t)level_first.size() - 2u : counters[1];   // binned: level L holds the nodes of depth L (no atomicMax per node)
+    float area = 0.0f;                                                    // m_total_area: a sequential float sum (ref: BVH.cpp:22)
+    for (uint32_t i = 0; i < n_tris; ++i) area += HostTriangleArea(triangles[i]);
+    *total_area_out = area;
+    return CGPT_OK;
 }

@@ -49,87 +49,45 @@ void** CtxWavefrontSlot(cgpt_ctx* ctx) { return &ctx->wavefront_state; }
 void** CtxPersistentSlot(cgpt_ctx* ctx) { return &ctx->persistent_state; }
 // the launchers of the multi-launch kernels record the render's start event themselves, after their one-time host setup
 // (allocations, occupancy queries), so that cgpt_stats.kernel_ms of a first call is device time
-hipEvent_t CtxStartEvent(cgpt_ctx* ctx) { return ctx->ev_start; }
-int CreateFail(int code, const char* fmt, ...)                               // failure of cgpt_ctx_create: there is no context to hold the text
-{
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
-    g_create_error = buf;
-    return code;
-}
-int CtxFail(cgpt_ctx* ctx, int code, const char* fmt, ...)
-{
-    if (!ctx) return code;
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
-    ctx->error = buf;
-    return code;
-}
-}  // namespace cgpt
-
-namespace {
-
-int Fail(cgpt_ctx* ctx, int code, const char* fmt, ...)
+hipEvent_t CtxStartEvent(cgpt_ctx* ctx) { return ctx->ev_start.e; }
+int CtxFail(cgpt_ctx* ctx, int code, const char* fmt, ...)                   // ctx null: cgpt_ctx_create failed, and there is no context to hold the text
 {
     char buf[512];
     va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
     if (ctx) ctx->error = buf; else g_create_error = buf;
     return code;
 }
+}  // namespace cgpt
 
-#define HIP_TRY(ctx, expr)                                                                                        \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return Fail((ctx), CGPT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-
-// Calls into the multi-device context (multi_gpu.hip: host vectors, worker threads): nothing may unwind through the C ABI
-#define GROUP_CALL(ctx, expr)                                                                                     \
-    do {                                                                                                          \
-        try { return (expr); }                                                                                    \
-        catch (const std::exception& e_) { return Fail((ctx), CGPT_ERR_INVALID, "%s: %s", __func__, e_.what()); } \
-        catch (...) { return Fail((ctx), CGPT_ERR_INVALID, "%s: unknown exception", __func__); }                  \
-    } while (0)
+namespace {
 
 template <typename T>
-int UploadArray(cgpt_ctx* ctx, T** dst, const std::vector<T>& src)
+int UploadArray(cgpt_ctx* ctx, DevBuf<T>& dst, const std::vector<T>& src)   // an empty vector still gets one element: no kernel argument is null
 {
-    if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
-    const size_t bytes = sizeof(T) * (src.empty() ? 1 : src.size());
-    HIP_TRY(ctx, hipMalloc((void**)dst, bytes));
-    if (!src.empty()) HIP_TRY(ctx, hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, dst.Alloc(src.empty() ? 1 : src.size()));
+    if (!src.empty()) HIP_TRY(ctx, hipMemcpy(dst.p, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
     return CGPT_OK;
 }
 
 void FreeScene(cgpt_ctx* ctx)
 {
-    (void)hipFree(ctx->d_node_pairs); (void)hipFree(ctx->d_tri_leaf); (void)hipFree(ctx->d_tri_orig); (void)hipFree(ctx->d_tri_normal);
-    (void)hipFree(ctx->d_materials); (void)hipFree(ctx->d_objects); (void)hipFree(ctx->d_obj_trace); (void)hipFree(ctx->d_lights);
-    ctx->d_node_pairs = ctx->d_tri_leaf = ctx->d_tri_orig = ctx->d_tri_normal = ctx->d_materials = nullptr;
-    ctx->d_objects = nullptr; ctx->d_obj_trace = nullptr; ctx->d_lights = nullptr;
-    (void)hipFree(ctx->d_refit_levels); (void)hipFree(ctx->d_refit_staging);
-    ctx->d_refit_levels = nullptr; ctx->d_refit_staging = nullptr; ctx->refit_staging_tris = 0;
+    ctx->sb = SceneBuffers{};
     ctx->h_objects.clear(); ctx->refit_objects.clear(); ctx->record_perm.clear();
     ctx->h_roughness.clear(); ctx->h_transmission_roughness.clear(); ctx->h_materials.clear(); ctx->lobe_level = 0;
     ctx->has_scene = false;
 }
 
-void FreeFramebuffer(cgpt_ctx* ctx)
-{
-    (void)hipFree(ctx->d_accumulator);
-    (void)hipFree(ctx->d_pixels);
-    ctx->d_accumulator = nullptr; ctx->d_pixels = nullptr;
-}
+void FreeFramebuffer(cgpt_ctx* ctx) { ctx->fb = FrameBuffers{}; }
 
 int EnsureFramebuffer(cgpt_ctx* ctx, uint32_t W, uint32_t H, uint32_t n_rows, const uint32_t key[5])
 {
-    if (ctx->d_accumulator && ctx->width == W && ctx->height == H && memcmp(ctx->band_key, key, sizeof(ctx->band_key)) == 0) return CGPT_OK;
+    if (ctx->fb.accumulator.p && ctx->width == W && ctx->height == H && memcmp(ctx->band_key, key, sizeof(ctx->band_key)) == 0) return CGPT_OK;
     FreeFramebuffer(ctx);
     const size_t n = (size_t)W * n_rows;
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_accumulator, n * sizeof(float4)));
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_pixels, n * sizeof(uint32_t)));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_accumulator, 0, n * sizeof(float4), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_pixels, 0, n * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, ctx->fb.accumulator.Alloc(n));
+    HIP_TRY(ctx, ctx->fb.pixels.Alloc(n));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->fb.accumulator.p, 0, n * sizeof(float4), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->fb.pixels.p, 0, n * sizeof(uint32_t), ctx->stream));
     ctx->width = W; ctx->height = H; ctx->n_rows = n_rows; memcpy(ctx->band_key, key, sizeof(ctx->band_key));
     ctx->num_accumulated = 0;
     return CGPT_OK;
@@ -140,18 +98,18 @@ struct Band { uint32_t n_rows, first, h, stride; uint32_t key[5]; };
 int ResolveBand(cgpt_ctx* ctx, const cgpt_render_params& p, Band& b)
 {
     if (p.width == 0 || p.height == 0 || p.row_begin >= p.row_end || p.row_end > p.height)
-        return Fail(ctx, CGPT_ERR_INVALID, "bad framebuffer/rows: %ux%u rows [%u,%u)", p.width, p.height, p.row_begin, p.row_end);
-    if ((uint64_t)p.width * p.height > 0xFFFFFFFFull) return Fail(ctx, CGPT_ERR_INVALID, "framebuffer too large");
+        return CtxFail(ctx, CGPT_ERR_INVALID, "bad framebuffer/rows: %ux%u rows [%u,%u)", p.width, p.height, p.row_begin, p.row_end);
+    if ((uint64_t)p.width * p.height > 0xFFFFFFFFull) return CtxFail(ctx, CGPT_ERR_INVALID, "framebuffer too large");
     if (p.interleave_rows == 0 && p.interleave_count == 0) {
         b.n_rows = p.row_end - p.row_begin; b.first = p.row_begin; b.h = b.n_rows; b.stride = 0;
     } else {
         const uint32_t h = p.interleave_rows, R = p.interleave_count, r = p.interleave_index;
         if (h == 0 || R == 0 || r >= R || p.row_begin != 0 || p.row_end != p.height)
-            return Fail(ctx, CGPT_ERR_INVALID, "bad interleave: rows %u count %u index %u (row_begin/row_end must be 0/height)", h, R, r);
+            return CtxFail(ctx, CGPT_ERR_INVALID, "bad interleave: rows %u count %u index %u (row_begin/row_end must be 0/height)", h, R, r);
         b.first = r * h; b.h = h; b.stride = R * h;
         b.n_rows = 0;
         for (uint64_t first = b.first; first < p.height; first += b.stride) b.n_rows += std::min<uint32_t>(h, p.height - (uint32_t)first);
-        if (b.n_rows == 0) return Fail(ctx, CGPT_ERR_INVALID, "interleave index %u owns no rows of a %u-row image", r, p.height);
+        if (b.n_rows == 0) return CtxFail(ctx, CGPT_ERR_INVALID, "interleave index %u owns no rows of a %u-row image", r, p.height);
     }
     const uint32_t key[5] = { p.row_begin, p.row_end, p.interleave_rows, p.interleave_count, p.interleave_index };
     memcpy(b.key, key, sizeof(key));
@@ -163,24 +121,24 @@ int ResolveBand(cgpt_ctx* ctx, const cgpt_render_params& p, Band& b)
 int UpdateRoughnessWord(cgpt_ctx* ctx, const float* roughness, uint32_t n_materials, bool transmission)
 {
     const char* const what = transmission ? "transmission roughness" : "roughness";
-    if (!ctx->has_scene) return Fail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
-    if (!roughness || n_materials != ctx->n_materials) return Fail(ctx, CGPT_ERR_INVALID, "expected %u %s values", ctx->n_materials, what);
+    if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!roughness || n_materials != ctx->n_materials) return CtxFail(ctx, CGPT_ERR_INVALID, "expected %u %s values", ctx->n_materials, what);
     bool rough = false;
     for (uint32_t i = 0; i < n_materials; ++i) {
-        if (!(roughness[i] >= 0.0f && roughness[i] <= 1.0f)) return Fail(ctx, CGPT_ERR_INVALID, "material %u: %s %g outside [0, 1]", i, what, (double)roughness[i]);
+        if (!(roughness[i] >= 0.0f && roughness[i] <= 1.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "material %u: %s %g outside [0, 1]", i, what, (double)roughness[i]);
         rough = rough || roughness[i] > 0.0f;
     }
     std::vector<float4> mats;
     std::vector<float> values;
-    try { mats = ctx->h_materials; values.assign(roughness, roughness + n_materials); } catch (const std::exception& e) { return Fail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
+    try { mats = ctx->h_materials; values.assign(roughness, roughness + n_materials); } catch (const std::exception& e) { return CtxFail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
     for (uint32_t i = 0; i < n_materials; ++i) (transmission ? mats[4 * (size_t)i + 3].w : mats[4 * (size_t)i + 3].z) = roughness[i] * roughness[i];
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // first hits and albedo do not depend on either roughness: the denoiser's guides stay valid (scene_generation is left as it is)
-    const hipError_t e = hipMemcpy(ctx->d_materials, mats.data(), mats.size() * sizeof(float4), hipMemcpyHostToDevice);
+    const hipError_t e = hipMemcpy(ctx->sb.materials.p, mats.data(), mats.size() * sizeof(float4), hipMemcpyHostToDevice);
     if (e != hipSuccess) {                                                     // the records may be half written: drop the scene (refit.hip: SceneLost)
         ctx->has_scene = false;
-        return Fail(ctx, CGPT_ERR_HIP, "hipMemcpy of the material records failed: %s (the device scene is dropped; upload it again)", hipGetErrorString(e));
+        return CtxFail(ctx, CGPT_ERR_HIP, "hipMemcpy of the material records failed: %s (the device scene is dropped; upload it again)", hipGetErrorString(e));
     }
     ctx->h_materials.swap(mats);
     (transmission ? ctx->h_transmission_roughness : ctx->h_roughness).swap(values);
@@ -201,36 +159,34 @@ const char* cgpt_last_error(const cgpt_ctx* ctx) { return ctx ? ctx->error.c_str
 
 int cgpt_ctx_create(const int* device_ids, int n_devices, uint32_t flags, cgpt_ctx** out)
 {
-    if (!out) return Fail(nullptr, CGPT_ERR_INVALID, "out is null");
+    if (!out) return CtxFail(nullptr, CGPT_ERR_INVALID, "out is null");
     *out = nullptr;
-    if (n_devices < 1 || n_devices > 8) return Fail(nullptr, CGPT_ERR_INVALID, "n_devices %d outside [1, 8] (one node)", n_devices);
+    if (n_devices < 1 || n_devices > 8) return CtxFail(nullptr, CGPT_ERR_INVALID, "n_devices %d outside [1, 8] (one node)", n_devices);
     if (n_devices > 1 || (flags & CGPT_CTX_FORCE_COLLECTIVE)) {
-        try { return GroupCreate(device_ids, n_devices, flags, out); }
-        catch (const std::exception& e) { return Fail(nullptr, CGPT_ERR_INVALID, "cgpt_ctx_create: %s", e.what()); }
+        return Guarded(nullptr, "cgpt_ctx_create", [&] { return GroupCreate(device_ids, n_devices, flags, out); });
     }
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count == 0)
-        return Fail(nullptr, CGPT_ERR_NO_DEVICE, "no HIP device available (%s); this library has no CPU path", e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
+        return CtxFail(nullptr, CGPT_ERR_NO_DEVICE, "no HIP device available (%s); this library has no CPU path", e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
     const int dev = device_ids ? device_ids[0] : 0;
-    if (dev < 0 || dev >= count) return Fail(nullptr, CGPT_ERR_INVALID, "device id %d out of range (%d devices)", dev, count);
+    if (dev < 0 || dev >= count) return CtxFail(nullptr, CGPT_ERR_INVALID, "device id %d out of range (%d devices)", dev, count);
     hipDeviceProp_t prop;
-    if ((e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return Fail(nullptr, CGPT_ERR_HIP, "hipGetDeviceProperties: %s", hipGetErrorString(e));
+    if ((e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return CtxFail(nullptr, CGPT_ERR_HIP, "hipGetDeviceProperties: %s", hipGetErrorString(e));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return Fail(nullptr, CGPT_ERR_NO_DEVICE, "device %d is %s; the kernels are built for gfx950 (MI355X) only", dev, prop.gcnArchName);
+        return CtxFail(nullptr, CGPT_ERR_NO_DEVICE, "device %d is %s; the kernels are built for gfx950 (MI355X) only", dev, prop.gcnArchName);
 
     cgpt_ctx* ctx = new (std::nothrow) cgpt_ctx;
-    if (!ctx) return Fail(nullptr, CGPT_ERR_INVALID, "out of host memory");
+    if (!ctx) return CtxFail(nullptr, CGPT_ERR_INVALID, "out of host memory");
     ctx->device = dev;
-    if ((e = hipSetDevice(dev)) != hipSuccess || (e = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipEventCreate(&ctx->ev_start)) != hipSuccess || (e = hipEventCreate(&ctx->ev_stop)) != hipSuccess ||
-        (e = hipMalloc((void**)&ctx->d_counters, sizeof(DevCounters))) != hipSuccess ||
-        (e = hipMemset(ctx->d_counters, 0, sizeof(DevCounters))) != hipSuccess) {
-        int rc = Fail(nullptr, CGPT_ERR_HIP, "context setup failed: %s", hipGetErrorString(e));
-        delete ctx;
-        return rc;
+    if ((e = hipSetDevice(dev)) != hipSuccess || (e = ctx->own_stream.Create(hipStreamNonBlocking)) != hipSuccess ||
+        (e = ctx->ev_start.Create()) != hipSuccess || (e = ctx->ev_stop.Create()) != hipSuccess ||
+        (e = ctx->counters.Alloc(1)) != hipSuccess ||
+        (e = hipMemset(ctx->counters.p, 0, sizeof(DevCounters))) != hipSuccess) {
+        delete ctx;                                                            // gives back whatever the earlier steps created
+        return CtxFail(nullptr, CGPT_ERR_HIP, "context setup failed: %s", hipGetErrorString(e));
     }
-    ctx->stream = ctx->own_stream;
+    ctx->stream = ctx->own_stream.s;
     *out = ctx;
     return CGPT_OK;
 }
@@ -243,57 +199,51 @@ int cgpt_ctx_destroy(cgpt_ctx* ctx)
     (void)hipStreamSynchronize(ctx->stream);
     FreeScene(ctx);
     FreeFramebuffer(ctx);
-    (void)hipFree(ctx->d_counters);
+    ctx->counters.Reset();
     WavefrontFree(ctx->wavefront_state);
     PersistentFree(ctx->persistent_state);
     DenoiseFree(ctx);
-    (void)hipEventDestroy(ctx->ev_start); (void)hipEventDestroy(ctx->ev_stop);
-    (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    delete ctx;                                                                // the events, then the stream
     return CGPT_OK;
 }
 
 int cgpt_set_stream(cgpt_ctx* ctx, void* hip_stream)
 {
     if (!ctx) return CGPT_ERR_INVALID;
-    if (ctx->group) return Fail(ctx, CGPT_ERR_UNSUPPORTED, "cgpt_set_stream: a multi-device context owns its streams");
+    if (ctx->group) return CtxFail(ctx, CGPT_ERR_UNSUPPORTED, "cgpt_set_stream: a multi-device context owns its streams");
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
+    ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream.s;
     return CGPT_OK;
 }
 
 int cgpt_scene_upload(cgpt_ctx* ctx, const cgpt_scene_desc* scene)
 {
     if (!ctx) return CGPT_ERR_INVALID;
-    if (ctx->group) GROUP_CALL(ctx, GroupSceneUpload(ctx, scene));
-    if (!scene) return Fail(ctx, CGPT_ERR_INVALID, "scene is null");
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupSceneUpload(ctx, scene); });
+    if (!scene) return CtxFail(ctx, CGPT_ERR_INVALID, "scene is null");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->scene_generation++;                                                   // the denoiser's guides are stale (denoise.hip)
-    try {                                                                      // the re-layout allocates host vectors: nothing may unwind through the C ABI
+    return Guarded(ctx, "scene upload", [&] {                                  // the re-layout allocates host vectors
         SceneLayout layout;
         const int rc = LayoutScene(*scene, layout, ctx->error);
         return rc != CGPT_OK ? rc : SceneInstall(ctx, layout);
-    } catch (const std::exception& e) {
-        return Fail(ctx, CGPT_ERR_INVALID, "scene upload: %s", e.what());
-    } catch (...) {
-        return Fail(ctx, CGPT_ERR_INVALID, "scene upload: unknown exception");
-    }
+    });
 }
 
 int cgpt_scene_update_materials(cgpt_ctx* ctx, const cgpt_material* materials, uint32_t n_materials)
 {
     if (!ctx) return CGPT_ERR_INVALID;
-    if (ctx->group) GROUP_CALL(ctx, GroupUpdateMaterials(ctx, materials, n_materials));
-    if (!ctx->has_scene) return Fail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
-    if (!materials || n_materials != ctx->n_materials) return Fail(ctx, CGPT_ERR_INVALID, "expected %u materials", ctx->n_materials);
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupUpdateMaterials(ctx, materials, n_materials); });
+    if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!materials || n_materials != ctx->n_materials) return CtxFail(ctx, CGPT_ERR_INVALID, "expected %u materials", ctx->n_materials);
     std::vector<float4> mats;
-    try { mats.resize(4 * (size_t)n_materials); } catch (const std::exception& e) { return Fail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
+    try { mats.resize(4 * (size_t)n_materials); } catch (const std::exception& e) { return CtxFail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
     for (uint32_t i = 0; i < n_materials; ++i) PackMaterial(materials[i], ctx->h_roughness[i], ctx->h_transmission_roughness[i], mats.data() + 4 * (size_t)i);   // both roughnesses are kept
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->scene_generation++;
-    HIP_TRY(ctx, hipMemcpy(ctx->d_materials, mats.data(), mats.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->sb.materials.p, mats.data(), mats.size() * sizeof(float4), hipMemcpyHostToDevice));
     ctx->h_materials.swap(mats);
     return CGPT_OK;
 }
@@ -301,14 +251,14 @@ int cgpt_scene_update_materials(cgpt_ctx* ctx, const cgpt_material* materials, u
 int cgpt_scene_update_roughness(cgpt_ctx* ctx, const float* roughness, uint32_t n_materials)
 {
     if (!ctx) return CGPT_ERR_INVALID;
-    if (ctx->group) GROUP_CALL(ctx, GroupUpdateRoughness(ctx, roughness, n_materials));
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupUpdateRoughness(ctx, roughness, n_materials); });
     return UpdateRoughnessWord(ctx, roughness, n_materials, false);
 }
 
 int cgpt_scene_update_transmission_roughness(cgpt_ctx* ctx, const float* roughness, uint32_t n_materials)
 {
     if (!ctx) return CGPT_ERR_INVALID;
-    if (ctx->group) GROUP_CALL(ctx, GroupUpdateTransmissionRoughness(ctx, roughness, n_materials));
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupUpdateTransmissionRoughness(ctx, roughness, n_materials); });
     return UpdateRoughnessWord(ctx, roughness, n_materials, true);
 }
 
@@ -335,20 +285,20 @@ int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout)
 {
     FreeScene(ctx);
     int rc;
-    if ((rc = UploadArray(ctx, &ctx->d_node_pairs, layout.node_pairs)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, &ctx->d_tri_leaf, layout.tri_leaf)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, &ctx->d_tri_orig, layout.tri_orig)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, &ctx->d_tri_normal, layout.tri_normal)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, &ctx->d_materials, layout.materials)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, &ctx->d_objects, layout.objects)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, &ctx->d_obj_trace, layout.obj_trace)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, &ctx->d_lights, layout.lights)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, &ctx->d_refit_levels, layout.refit_levels)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, ctx->sb.node_pairs, layout.node_pairs)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, ctx->sb.tri_leaf, layout.tri_leaf)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, ctx->sb.tri_orig, layout.tri_orig)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, ctx->sb.tri_normal, layout.tri_normal)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, ctx->sb.materials, layout.materials)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, ctx->sb.objects, layout.objects)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, ctx->sb.obj_trace, layout.obj_trace)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, ctx->sb.lights, layout.lights)) != CGPT_OK) return rc;
+    if ((rc = UploadArray(ctx, ctx->sb.refit_levels, layout.refit_levels)) != CGPT_OK) return rc;
     ctx->h_objects = layout.objects; ctx->refit_objects = layout.refit_objects; ctx->record_perm = layout.record_perm;
     ctx->h_roughness.assign(layout.n_materials, 0.0f); ctx->h_transmission_roughness.assign(layout.n_materials, 0.0f); ctx->h_materials = layout.materials; ctx->lobe_level = 0;
 
-    ctx->scene.node_pairs = ctx->d_node_pairs; ctx->scene.tri_leaf = ctx->d_tri_leaf; ctx->scene.tri_orig = ctx->d_tri_orig; ctx->scene.tri_normal = ctx->d_tri_normal;
-    ctx->scene.materials = ctx->d_materials; ctx->scene.objects = ctx->d_objects; ctx->scene.obj_trace = ctx->d_obj_trace; ctx->scene.lights = ctx->d_lights;
+    ctx->scene.node_pairs = ctx->sb.node_pairs.p; ctx->scene.tri_leaf = ctx->sb.tri_leaf.p; ctx->scene.tri_orig = ctx->sb.tri_orig.p; ctx->scene.tri_normal = ctx->sb.tri_normal.p;
+    ctx->scene.materials = ctx->sb.materials.p; ctx->scene.objects = ctx->sb.objects.p; ctx->scene.obj_trace = ctx->sb.obj_trace.p; ctx->scene.lights = ctx->sb.lights.p;
     ctx->scene.n_objects = (uint32_t)layout.objects.size(); ctx->scene.n_lights = (uint32_t)layout.lights.size(); ctx->scene.stack_depth = layout.stack_depth;
     ctx->scene.n_top_records = layout.n_top_records; ctx->scene.n_pair_records = layout.n_pair_records; ctx->scene.n_small_tris = layout.n_small_tris;
     ctx->n_materials = layout.n_materials;
@@ -359,19 +309,19 @@ int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout)
 int RenderEnqueue(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p)
 {
     ctx->pending_kernel = 0;
-    if (!camera || !settings || !p) return Fail(ctx, CGPT_ERR_INVALID, "null argument");
-    if (!ctx->has_scene) return Fail(ctx, CGPT_ERR_NO_SCENE, "cgpt_render before cgpt_scene_upload");
+    if (!camera || !settings || !p) return CtxFail(ctx, CGPT_ERR_INVALID, "null argument");
+    if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "cgpt_render before cgpt_scene_upload");
     if (settings->max_ray_depth < 0 || settings->max_ray_depth > 254)
-        return Fail(ctx, CGPT_ERR_INVALID, "max_ray_depth %d outside [0,254] (ray_depth is a uint8_t in the reference, Main.cpp:401)", settings->max_ray_depth);
+        return CtxFail(ctx, CGPT_ERR_INVALID, "max_ray_depth %d outside [0,254] (ray_depth is a uint8_t in the reference, Main.cpp:401)", settings->max_ray_depth);
     if (settings->render_mode > CGPT_MODE_ADVANCED || settings->debug_render_mode > CGPT_DEBUG_BVH_DEPTH)
-        return Fail(ctx, CGPT_ERR_INVALID, "bad render_mode/debug_render_mode");
+        return CtxFail(ctx, CGPT_ERR_INVALID, "bad render_mode/debug_render_mode");
     if (settings->render_mode != CGPT_MODE_ADVANCED) {
         // TracePath (brute force) keeps its per-level operations in HBM in the persistent kernel (per lane) and in the wavefront
         // pipeline (per path), any depth; the megakernel keeps them in per-lane scratch of 32 levels
         if (p->kernel == CGPT_KERNEL_MEGAKERNEL && settings->max_ray_depth + 1 > 32)
-            return Fail(ctx, CGPT_ERR_UNSUPPORTED, "brute-force / comparison modes in the megakernel support max_ray_depth <= 31 (got %d)", settings->max_ray_depth);
+            return CtxFail(ctx, CGPT_ERR_UNSUPPORTED, "brute-force / comparison modes in the megakernel support max_ray_depth <= 31 (got %d)", settings->max_ray_depth);
     }
-    if ((uint64_t)p->first_sample + p->n_samples > 0xFFFFFFFFull) return Fail(ctx, CGPT_ERR_INVALID, "sample index overflow");
+    if ((uint64_t)p->first_sample + p->n_samples > 0xFFFFFFFFull) return CtxFail(ctx, CGPT_ERR_INVALID, "sample index overflow");
 
     Band band;
     int rc = ResolveBand(ctx, *p, band);
@@ -395,7 +345,7 @@ int RenderEnqueue(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings*
     args.width = p->width; args.height = p->height;
     args.n_rows = n_rows; args.band_first = band_first; args.band_h = band_h; args.band_stride = band_stride;
     args.first_sample = p->first_sample; args.n_samples = p->n_samples; args.seed = p->seed;
-    args.accumulator = ctx->d_accumulator; args.pixels = ctx->d_pixels; args.counters = ctx->d_counters;
+    args.accumulator = ctx->fb.accumulator.p; args.pixels = ctx->fb.pixels.p; args.counters = ctx->counters.p;
 
     const bool count = (p->flags & CGPT_RENDER_COUNTERS) != 0;
     // AUTO: all three kernels give bit-identical images, so the choice is speed alone.  MI355X, glass scene, ms per call
@@ -423,21 +373,21 @@ int RenderEnqueue(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings*
     }
 
     if (kernel == CGPT_KERNEL_MEGAKERNEL) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_start.e, ctx->stream));
         HIP_TRY(ctx, LaunchMegakernel(args, count, ctx->lobe_level, ctx->stream));
         ctx->kernel_launches += 1;
     } else if (kernel == CGPT_KERNEL_WAVEFRONT) {
         rc = LaunchWavefront(ctx, args, count, ctx->lobe_level);
-        if (rc < 0) return ctx->error.empty() ? Fail(ctx, CGPT_ERR_HIP, "wavefront launch failed") : CGPT_ERR_HIP;
+        if (rc < 0) return ctx->error.empty() ? CtxFail(ctx, CGPT_ERR_HIP, "wavefront launch failed") : CGPT_ERR_HIP;
         ctx->kernel_launches += (uint32_t)rc;
     } else if (kernel == CGPT_KERNEL_PERSISTENT) {
         rc = LaunchPersistent(ctx, args, count, ctx->lobe_level);
-        if (rc < 0) return ctx->error.empty() ? Fail(ctx, CGPT_ERR_HIP, "persistent kernel launch failed") : CGPT_ERR_HIP;
+        if (rc < 0) return ctx->error.empty() ? CtxFail(ctx, CGPT_ERR_HIP, "persistent kernel launch failed") : CGPT_ERR_HIP;
         ctx->kernel_launches += (uint32_t)rc;
     } else {
-        return Fail(ctx, CGPT_ERR_INVALID, "unknown kernel %u", p->kernel);
+        return CtxFail(ctx, CGPT_ERR_INVALID, "unknown kernel %u", p->kernel);
     }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop.e, ctx->stream));
     ctx->pending_kernel = kernel; ctx->pending_args = args; ctx->pending_num_accumulated = p->first_sample + p->n_samples; ctx->pending_lobe_level = ctx->lobe_level;
     ctx->last_debug_mode = settings->debug_render_mode;
     ctx->last_kernel = kernel;
@@ -451,9 +401,9 @@ int RenderFinish(cgpt_ctx* ctx)
     ctx->pending_kernel = 0;
     const DevRenderArgs& args = ctx->pending_args;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_stop));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_stop.e));
     float ms = 0.0f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start.e, ctx->ev_stop.e));
     ctx->kernel_ms += ms;
     if (kernel == CGPT_KERNEL_MEGAKERNEL) { ctx->dominant_ms += ms; ctx->dominant_launches += 1; ctx->dominant_waves_per_simd = MegakernelWavesPerSimd(args, ctx->pending_lobe_level); }
     else if (kernel == CGPT_KERNEL_PERSISTENT) {
@@ -478,7 +428,7 @@ extern "C" {
 int cgpt_render(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p)
 {
     if (!ctx) return CGPT_ERR_INVALID;
-    if (ctx->group) GROUP_CALL(ctx, GroupRender(ctx, camera, settings, p));
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupRender(ctx, camera, settings, p); });
     const int rc = RenderEnqueue(ctx, camera, settings, p);
     return rc != CGPT_OK ? rc : RenderFinish(ctx);
 }
@@ -486,60 +436,60 @@ int cgpt_render(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* s
 int cgpt_reset_accumulator(cgpt_ctx* ctx)
 {
     if (!ctx) return CGPT_ERR_INVALID;
-    if (ctx->group) GROUP_CALL(ctx, GroupResetAccumulator(ctx));
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupResetAccumulator(ctx); });
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->num_accumulated = 0;                                                  // ref: Main.cpp:240-242
-    if (ctx->d_accumulator) {
+    if (ctx->fb.accumulator.p) {
         const size_t n = (size_t)ctx->width * ctx->n_rows;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_accumulator, 0, n * sizeof(float4), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->fb.accumulator.p, 0, n * sizeof(float4), ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     double zero = 0.0;
-    HIP_TRY(ctx, hipMemcpy(&ctx->d_counters->total_energy, &zero, sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(&ctx->counters.p->total_energy, &zero, sizeof(double), hipMemcpyHostToDevice));
     return CGPT_OK;
 }
 
 int cgpt_read_accumulator(cgpt_ctx* ctx, float* dst, size_t n_floats)
 {
     if (!ctx) return CGPT_ERR_INVALID;
-    if (ctx->group) GROUP_CALL(ctx, GroupReadAccumulator(ctx, dst, n_floats));
-    if (!ctx->d_accumulator) return Fail(ctx, CGPT_ERR_INVALID, "nothing rendered yet");
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupReadAccumulator(ctx, dst, n_floats); });
+    if (!ctx->fb.accumulator.p) return CtxFail(ctx, CGPT_ERR_INVALID, "nothing rendered yet");
     const size_t n = (size_t)ctx->width * ctx->n_rows * 4;
-    if (!dst || n_floats != n) return Fail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats", n);
+    if (!dst || n_floats != n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats", n);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(dst, ctx->d_accumulator, n * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(dst, ctx->fb.accumulator.p, n * sizeof(float), hipMemcpyDeviceToHost));
     return CGPT_OK;
 }
 
 int cgpt_read_pixels(cgpt_ctx* ctx, uint32_t* dst, size_t n_pixels)
 {
     if (!ctx) return CGPT_ERR_INVALID;
-    if (ctx->group) GROUP_CALL(ctx, GroupReadPixels(ctx, dst, n_pixels));
-    if (!ctx->d_pixels) return Fail(ctx, CGPT_ERR_INVALID, "nothing rendered yet");
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupReadPixels(ctx, dst, n_pixels); });
+    if (!ctx->fb.pixels.p) return CtxFail(ctx, CGPT_ERR_INVALID, "nothing rendered yet");
     const size_t n = (size_t)ctx->width * ctx->n_rows;
-    if (!dst || n_pixels != n) return Fail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu pixels", n);
+    if (!dst || n_pixels != n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu pixels", n);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(dst, ctx->d_pixels, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(dst, ctx->fb.pixels.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return CGPT_OK;
 }
 
 int cgpt_write_accumulator(cgpt_ctx* ctx, const cgpt_render_params* p, const float* src, size_t n_floats, uint32_t num_accumulated)
 {
     if (!ctx) return CGPT_ERR_INVALID;
-    if (ctx->group) GROUP_CALL(ctx, GroupWriteAccumulator(ctx, p, src, n_floats, num_accumulated));
-    if (!p || !src) return Fail(ctx, CGPT_ERR_INVALID, "null argument");
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupWriteAccumulator(ctx, p, src, n_floats, num_accumulated); });
+    if (!p || !src) return CtxFail(ctx, CGPT_ERR_INVALID, "null argument");
     Band band;
     int rc = ResolveBand(ctx, *p, band);
     if (rc != CGPT_OK) return rc;
     const size_t n = (size_t)p->width * band.n_rows;
-    if (n_floats != 4 * n) return Fail(ctx, CGPT_ERR_INVALID, "expected %zu floats for %u rows of %u pixels, got %zu", 4 * n, band.n_rows, p->width, n_floats);
+    if (n_floats != 4 * n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected %zu floats for %u rows of %u pixels, got %zu", 4 * n, band.n_rows, p->width, n_floats);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if ((rc = EnsureFramebuffer(ctx, p->width, p->height, band.n_rows, band.key)) != CGPT_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_accumulator, src, n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, LaunchPackPixels(ctx->d_accumulator, ctx->d_pixels, n, num_accumulated, ctx->stream));   // data.pixels, ref: Main.cpp:741
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->fb.accumulator.p, src, n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, LaunchPackPixels(ctx->fb.accumulator.p, ctx->fb.pixels.p, n, num_accumulated, ctx->stream));   // data.pixels, ref: Main.cpp:741
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->num_accumulated = num_accumulated;                                    // ref: Main.cpp:205
     ctx->last_debug_mode = 0;                                                  // data.pixels are the packed sums again
@@ -549,8 +499,8 @@ int cgpt_write_accumulator(cgpt_ctx* ctx, const cgpt_render_params* p, const flo
 int cgpt_set_tuning(cgpt_ctx* ctx, const char* name, uint32_t value)
 {
     if (!ctx) return CGPT_ERR_INVALID;
-    if (ctx->group) GROUP_CALL(ctx, GroupSetTuning(ctx, name, value));
-    if (!name) return Fail(ctx, CGPT_ERR_INVALID, "null knob name");
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupSetTuning(ctx, name, value); });
+    if (!name) return CtxFail(ctx, CGPT_ERR_INVALID, "null knob name");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     bool known = false;
@@ -562,9 +512,9 @@ int cgpt_set_tuning(cgpt_ctx* ctx, const char* name, uint32_t value)
 int cgpt_accumulator_device_ptr(cgpt_ctx* ctx, void** ptr, size_t* n_bytes)
 {
     if (!ctx || !ptr || !n_bytes) return CGPT_ERR_INVALID;
-    if (ctx->group) GROUP_CALL(ctx, GroupDevicePtr(ctx, false, ptr, n_bytes));
-    if (!ctx->d_accumulator) return Fail(ctx, CGPT_ERR_INVALID, "nothing rendered yet");
-    *ptr = ctx->d_accumulator;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupDevicePtr(ctx, false, ptr, n_bytes); });
+    if (!ctx->fb.accumulator.p) return CtxFail(ctx, CGPT_ERR_INVALID, "nothing rendered yet");
+    *ptr = ctx->fb.accumulator.p;
     *n_bytes = (size_t)ctx->width * ctx->n_rows * sizeof(float4);
     return CGPT_OK;
 }
@@ -572,9 +522,9 @@ int cgpt_accumulator_device_ptr(cgpt_ctx* ctx, void** ptr, size_t* n_bytes)
 int cgpt_pixels_device_ptr(cgpt_ctx* ctx, void** ptr, size_t* n_bytes)
 {
     if (!ctx || !ptr || !n_bytes) return CGPT_ERR_INVALID;
-    if (ctx->group) GROUP_CALL(ctx, GroupDevicePtr(ctx, true, ptr, n_bytes));
-    if (!ctx->d_pixels) return Fail(ctx, CGPT_ERR_INVALID, "nothing rendered yet");
-    *ptr = ctx->d_pixels;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupDevicePtr(ctx, true, ptr, n_bytes); });
+    if (!ctx->fb.pixels.p) return CtxFail(ctx, CGPT_ERR_INVALID, "nothing rendered yet");
+    *ptr = ctx->fb.pixels.p;
     *n_bytes = (size_t)ctx->width * ctx->n_rows * sizeof(uint32_t);
     return CGPT_OK;
 }
@@ -582,11 +532,11 @@ int cgpt_pixels_device_ptr(cgpt_ctx* ctx, void** ptr, size_t* n_bytes)
 int cgpt_get_stats(cgpt_ctx* ctx, cgpt_stats* out)
 {
     if (!ctx || !out) return CGPT_ERR_INVALID;
-    if (ctx->group) GROUP_CALL(ctx, GroupGetStats(ctx, out));
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupGetStats(ctx, out); });
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     DevCounters c;
-    HIP_TRY(ctx, hipMemcpy(&c, ctx->d_counters, sizeof(c), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(&c, ctx->counters.p, sizeof(c), hipMemcpyDeviceToHost));
     out->traced_rays = c.traced_rays; out->inner_steps = c.inner_steps; out->tri_tests = c.tri_tests;
     out->bvh_depth_sum = c.bvh_depth_sum; out->closest_hits = c.closest_hits; out->total_energy_received = c.total_energy;
     out->num_accumulated = ctx->num_accumulated; out->kernel_launches = ctx->kernel_launches; out->kernel_ms = ctx->kernel_ms;
@@ -601,10 +551,10 @@ int cgpt_get_stats(cgpt_ctx* ctx, cgpt_stats* out)
 int cgpt_reset_stats(cgpt_ctx* ctx)
 {
     if (!ctx) return CGPT_ERR_INVALID;
-    if (ctx->group) GROUP_CALL(ctx, GroupResetStats(ctx));
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupResetStats(ctx); });
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemset(ctx->d_counters, 0, sizeof(DevCounters)));
+    HIP_TRY(ctx, hipMemset(ctx->counters.p, 0, sizeof(DevCounters)));
     ctx->kernel_launches = 0; ctx->kernel_ms = 0.0; ctx->dominant_launches = 0; ctx->dominant_ms = 0.0;
     ctx->dominant_round0_launches = 0; ctx->dominant_round0_ms = 0.0;
     return CGPT_OK;
@@ -615,41 +565,35 @@ int cgpt_intersect_rays(cgpt_ctx* ctx, const float* origins, const float* dirs, 
 {
     if (!ctx) return CGPT_ERR_INVALID;
     if (ctx->group) return GroupForwarded(ctx, cgpt_intersect_rays(GroupFirstMember(ctx), origins, dirs, tmax, n, out_t, out_obj, out_tri, out_depth));
-    if (!ctx->has_scene) return Fail(ctx, CGPT_ERR_NO_SCENE, "cgpt_intersect_rays before cgpt_scene_upload");
+    if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "cgpt_intersect_rays before cgpt_scene_upload");
     if (n == 0) return CGPT_OK;
-    if (!origins || !dirs || !out_t || !out_obj || !out_tri || !out_depth) return Fail(ctx, CGPT_ERR_INVALID, "null argument");
+    if (!origins || !dirs || !out_t || !out_obj || !out_tri || !out_depth) return CtxFail(ctx, CGPT_ERR_INVALID, "null argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    float *d_o = nullptr, *d_d = nullptr, *d_tm = nullptr, *d_t = nullptr;
-    uint32_t *d_obj = nullptr, *d_tri = nullptr, *d_dep = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_o); (void)hipFree(d_d); (void)hipFree(d_tm); (void)hipFree(d_t); (void)hipFree(d_obj); (void)hipFree(d_tri); (void)hipFree(d_dep); };
-    hipError_t e = hipSuccess;
-    auto ok = [&](hipError_t r) { if (e == hipSuccess) e = r; return r == hipSuccess; };
-    ok(hipMalloc((void**)&d_o, 12 * (size_t)n)); ok(hipMalloc((void**)&d_d, 12 * (size_t)n));
-    if (tmax) ok(hipMalloc((void**)&d_tm, 4 * (size_t)n));
-    ok(hipMalloc((void**)&d_t, 4 * (size_t)n)); ok(hipMalloc((void**)&d_obj, 4 * (size_t)n));
-    ok(hipMalloc((void**)&d_tri, 4 * (size_t)n)); ok(hipMalloc((void**)&d_dep, 4 * (size_t)n));
-    if (e == hipSuccess) {
-        ok(hipMemcpyAsync(d_o, origins, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-        ok(hipMemcpyAsync(d_d, dirs, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-        if (tmax) ok(hipMemcpyAsync(d_tm, tmax, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (e == hipSuccess) {
-        ok(LaunchIntersectRays(ctx->scene, d_o, d_d, d_tm, n, d_t, d_obj, d_tri, d_dep, ctx->d_counters, ctx->stream));
-        ok(hipMemcpyAsync(out_t, d_t, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        ok(hipMemcpyAsync(out_obj, d_obj, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        ok(hipMemcpyAsync(out_tri, d_tri, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        ok(hipMemcpyAsync(out_depth, d_dep, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        ok(hipStreamSynchronize(ctx->stream));
-    }
-    cleanup();
-    if (e != hipSuccess) return Fail(ctx, CGPT_ERR_HIP, "cgpt_intersect_rays: %s", hipGetErrorString(e));
+    const size_t n3 = 3 * (size_t)n;
+    DevBuf<float> d_o, d_d, d_tm, d_t;
+    DevBuf<uint32_t> d_obj, d_tri, d_dep;
+    HIP_TRY(ctx, d_o.Alloc(n3)); HIP_TRY(ctx, d_d.Alloc(n3));
+    if (tmax) HIP_TRY(ctx, d_tm.Alloc(n));
+    HIP_TRY(ctx, d_t.Alloc(n)); HIP_TRY(ctx, d_obj.Alloc(n));
+    HIP_TRY(ctx, d_tri.Alloc(n)); HIP_TRY(ctx, d_dep.Alloc(n));
+    HIP_TRY(ctx, hipMemcpyAsync(d_o.p, origins, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_d.p, dirs, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    if (tmax) HIP_TRY(ctx, hipMemcpyAsync(d_tm.p, tmax, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, LaunchIntersectRays(ctx->scene, d_o.p, d_d.p, d_tm.p, n, d_t.p, d_obj.p, d_tri.p, d_dep.p, ctx->counters.p, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out_t, d_t.p, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out_obj, d_obj.p, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out_tri, d_tri.p, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out_depth, d_dep.p, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CGPT_OK;
 }
+
+uint64_t cgpt_debug_live_device_bytes(void) { return Ledger().live.load(); }
 
 int cgpt_synchronize(cgpt_ctx* ctx)
 {
     if (!ctx) return CGPT_ERR_INVALID;
-    if (ctx->group) GROUP_CALL(ctx, GroupSynchronize(ctx));
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupSynchronize(ctx); });
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CGPT_OK;

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "cpugpupt_abi.h"
+#include "device_memory.h"
 #include "device_scene.h"
 #include "scene_layout.h"
 
@@ -13,22 +14,38 @@ namespace cgpt {
 struct DeviceGroup;
 }  // namespace cgpt
 
+namespace cgpt {
+// The device memory of a one-device context, by subsystem.  The kernel-argument structs (DevScene, DevRenderArgs) are filled from these.
+struct SceneBuffers {                             // cgpt_scene_upload installs them (SceneInstall); refit.hip edits them in place
+    DevBuf<float4> node_pairs, tri_leaf, tri_orig, tri_normal, materials;
+    DevBuf<DevObject> objects;
+    DevBuf<float4> obj_trace;
+    DevBuf<uint32_t> lights;
+    DevBuf<uint32_t> refit_levels;
+    DevBuf<cgpt_triangle> refit_staging;          // host triangles of the last refit, grown on demand
+};
+struct FrameBuffers {                             // the framebuffer band (EnsureFramebuffer)
+    DevBuf<float4> accumulator;
+    DevBuf<uint32_t> pixels;
+};
+struct DenoiseBuffers {                           // denoise.hip; each group is reallocated when its pixel count changes
+    DevBuf<float4> guides;                        // 3 float4 per pixel, the cgpt_read_guides layout
+    DevBuf<float4> guide_demod;                   // per pixel: the albedo the filter divides by ({1,1,1} where it does not)
+    DevBuf<float4> filter[2];                     // the filter's ping-pong buffers
+    DevBuf<uint32_t> filter_pixels;
+};
+template <class... B> void ResetAll(B&... b) { (b.Reset(), ...); }
+}  // namespace cgpt
+
 struct cgpt_ctx {
     int device = 0;
-    hipStream_t own_stream = nullptr;
+    cgpt::DevStream own_stream;
     hipStream_t stream = nullptr;
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+    cgpt::DevEvent ev_start, ev_stop;
     std::string error;
 
     // device scene
-    float4* d_node_pairs = nullptr;
-    float4* d_tri_leaf = nullptr;
-    float4* d_tri_orig = nullptr;
-    float4* d_tri_normal = nullptr;
-    float4* d_materials = nullptr;
-    cgpt::DevObject* d_objects = nullptr;
-    float4* d_obj_trace = nullptr;
-    uint32_t* d_lights = nullptr;
+    cgpt::SceneBuffers sb;
     cgpt::DevScene scene{};
     uint32_t n_materials = 0;
     bool has_scene = false;
@@ -45,18 +62,14 @@ struct cgpt_ctx {
     std::vector<cgpt::DevObject> h_objects;
     std::vector<cgpt::RefitObject> refit_objects;
     std::vector<uint32_t> record_perm;            // record index in the reference's depth-first order -> index in node_pairs
-    uint32_t* d_refit_levels = nullptr;
-    cgpt_triangle* d_refit_staging = nullptr;     // host triangles of the last refit, grown on demand
-    size_t refit_staging_tris = 0;
 
     // framebuffer band
-    float4* d_accumulator = nullptr;
-    uint32_t* d_pixels = nullptr;
+    cgpt::FrameBuffers fb;
     uint32_t width = 0, height = 0, n_rows = 0;
     uint32_t band_key[5] = { 0, 0, 0, 0, 0 };     // row_begin, row_end, interleave rows/count/index of the allocated band
     uint32_t num_accumulated = 0;
 
-    cgpt::DevCounters* d_counters = nullptr;
+    cgpt::DevBuf<cgpt::DevCounters> counters;
     uint32_t kernel_launches = 0;
     double kernel_ms = 0.0;
     uint32_t dominant_launches = 0;
@@ -82,16 +95,11 @@ struct cgpt_ctx {
 
     // the denoiser (denoise.hip): first-hit guides cached per camera, band and scene, and the filter's ping-pong buffers
     uint64_t scene_generation = 0;                // bumped by every scene upload and in-place edit
-    float4* d_guides = nullptr;                   // 3 float4 per pixel, the cgpt_read_guides layout
-    float4* d_guide_demod = nullptr;              // per pixel: the albedo the filter divides by ({1,1,1} where it does not)
-    size_t guide_pixels = 0;                      // pixels allocated in the two above
+    cgpt::DenoiseBuffers dn;
     bool guides_valid = false;
     uint64_t guide_generation = 0;                // what the guides were computed for
     cgpt_camera guide_camera{};
     uint32_t guide_frame[4] = { 0, 0, 0, 0 };     // width, height, first global row, rows
-    float4* d_denoise[2] = { nullptr, nullptr };
-    uint32_t* d_denoise_pixels = nullptr;
-    size_t denoise_pixels = 0;                    // pixels allocated in the three above
 };
 
 
@@ -102,8 +110,6 @@ int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout);
 // the two halves of cgpt_render: enqueue the kernels of one context without waiting, then wait and book the timings
 int RenderEnqueue(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p);
 int RenderFinish(cgpt_ctx* ctx);
-int CtxFail(cgpt_ctx* ctx, int code, const char* fmt, ...);
-int CreateFail(int code, const char* fmt, ...);
 hipError_t LaunchPackPixels(const float4* accumulator, uint32_t* pixels, size_t n_pixels, uint32_t num_accumulated, hipStream_t stream);   // path_kernels.hip
 
 // multi_gpu.hip: the group behind a multi-device context
@@ -135,3 +141,6 @@ int GroupGatherUncounted(cgpt_ctx* ctx, const float4** frame);
 
 void DenoiseFree(cgpt_ctx* ctx);               // denoise.hip: the guide cache and filter buffers of a one-device context
 }  // namespace cgpt
+
+// Not part of the ABI (include/cpugpupt_abi.h): the bytes this library holds on all devices, for the tests of device_memory.h
+extern "C" uint64_t cgpt_debug_live_device_bytes(void);

@@ -181,12 +181,6 @@ __global__ void __launch_bounds__(256) denoise_identity(const float4* __restrict
     pixels[i] = vec4_to_uint(r, g, b);
 }
 
-#define DN_HIP(ctx, expr)                                                                                         \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return CtxFail((ctx), CGPT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 // what a call works on: a one-device context's contiguous band, or a multi-device context's full frame on its first member
 struct Frame {
     cgpt_ctx* dev;            // the one-device context whose device, stream, scene and buffers do the work
@@ -203,7 +197,7 @@ int ResolveFrame(cgpt_ctx* ctx, bool denoise, const cgpt_camera* camera, Frame& 
         f.dev = GroupFirstMember(ctx); f.first_row = 0; f.n_rows = height;
     } else {
         if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
-        if (!ctx->d_accumulator) return CtxFail(ctx, CGPT_ERR_INVALID, "nothing rendered yet");
+        if (!ctx->fb.accumulator.p) return CtxFail(ctx, CGPT_ERR_INVALID, "nothing rendered yet");
         width = ctx->width; height = ctx->height; num_accumulated = ctx->num_accumulated; debug = ctx->last_debug_mode;
         f.dev = ctx; f.first_row = ctx->band_key[0]; f.n_rows = ctx->n_rows;
     }
@@ -225,12 +219,10 @@ int EnsureGuides(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera)
         return CGPT_OK;
     d->guides_valid = false;
     const size_t n = (size_t)f.width * f.n_rows;
-    if (d->guide_pixels != n) {
-        (void)hipFree(d->d_guides); (void)hipFree(d->d_guide_demod);
-        d->d_guides = d->d_guide_demod = nullptr; d->guide_pixels = 0;
-        DN_HIP(ctx, hipMalloc((void**)&d->d_guides, 3 * n * sizeof(float4)));
-        DN_HIP(ctx, hipMalloc((void**)&d->d_guide_demod, n * sizeof(float4)));
-        d->guide_pixels = n;
+    if (d->dn.guide_demod.n != n) {                                            // any other size: both anew (the second one's count is the key)
+        ResetAll(d->dn.guides, d->dn.guide_demod);
+        HIP_TRY(ctx, d->dn.guides.Alloc(3 * n));
+        HIP_TRY(ctx, d->dn.guide_demod.Alloc(n));
     }
     DevCamera cam;
     static_assert(sizeof(DevCamera) == sizeof(cgpt_camera), "camera layouts");
@@ -238,8 +230,8 @@ int EnsureGuides(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera)
     const uint32_t tiles = ((f.width + kTile - 1u) / kTile) * ((f.n_rows + kTile - 1u) / kTile);
     const size_t lds = (size_t)d->scene.stack_depth * 256u * sizeof(uint32_t);   // intersect_rays_kernel's stack
     hipLaunchKernelGGL(guides_kernel, dim3(tiles), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
-                       d->d_guides, d->d_guide_demod);
-    DN_HIP(ctx, hipGetLastError());
+                       d->dn.guides.p, d->dn.guide_demod.p);
+    HIP_TRY(ctx, hipGetLastError());
     memcpy(d->guide_frame, key, sizeof(key));
     memcpy(&d->guide_camera, camera, sizeof(cgpt_camera));
     d->guide_generation = d->scene_generation;
@@ -249,13 +241,11 @@ int EnsureGuides(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera)
 
 int EnsureFilterBuffers(cgpt_ctx* ctx, cgpt_ctx* d, size_t n)
 {
-    if (d->denoise_pixels == n) return CGPT_OK;
-    (void)hipFree(d->d_denoise[0]); (void)hipFree(d->d_denoise[1]); (void)hipFree(d->d_denoise_pixels);
-    d->d_denoise[0] = d->d_denoise[1] = nullptr; d->d_denoise_pixels = nullptr; d->denoise_pixels = 0;
-    DN_HIP(ctx, hipMalloc((void**)&d->d_denoise[0], n * sizeof(float4)));
-    DN_HIP(ctx, hipMalloc((void**)&d->d_denoise[1], n * sizeof(float4)));
-    DN_HIP(ctx, hipMalloc((void**)&d->d_denoise_pixels, n * sizeof(uint32_t)));
-    d->denoise_pixels = n;
+    if (d->dn.filter_pixels.n == n) return CGPT_OK;                            // any other size: all three anew (the last one's count is the key)
+    ResetAll(d->dn.filter[0], d->dn.filter[1], d->dn.filter_pixels);
+    HIP_TRY(ctx, d->dn.filter[0].Alloc(n));
+    HIP_TRY(ctx, d->dn.filter[1].Alloc(n));
+    HIP_TRY(ctx, d->dn.filter_pixels.Alloc(n));
     return CGPT_OK;
 }
 
@@ -265,26 +255,26 @@ int Denoise(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, const cgpt
     cgpt_ctx* d = f.dev;
     const size_t n = (size_t)f.width * f.n_rows;
     int rc;
-    DN_HIP(ctx, hipSetDevice(d->device));
+    HIP_TRY(ctx, hipSetDevice(d->device));
     if ((rc = EnsureFilterBuffers(ctx, d, n)) != CGPT_OK) return rc;
-    float4* out = d->d_denoise[0];
+    float4* out = d->dn.filter[0].p;
     if (p.iterations == 0) {
-        hipLaunchKernelGGL(denoise_identity, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, d->stream, acc, out, d->d_denoise_pixels, n,
+        hipLaunchKernelGGL(denoise_identity, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, d->stream, acc, out, d->dn.filter_pixels.p, n,
                            (float)f.num_accumulated);
-        DN_HIP(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipGetLastError());
     } else {
         if ((rc = EnsureGuides(ctx, f, camera)) != CGPT_OK) return rc;
         const uint32_t demodulate = (p.flags & CGPT_DENOISE_DEMODULATE_ALBEDO) ? 1u : 0u;
-        hipLaunchKernelGGL(denoise_prepare, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, d->stream, acc, d->d_guide_demod, d->d_denoise[0], n,
+        hipLaunchKernelGGL(denoise_prepare, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, d->stream, acc, d->dn.guide_demod.p, d->dn.filter[0].p, n,
                            (float)f.num_accumulated, demodulate);
-        DN_HIP(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipGetLastError());
         const uint32_t tiles = ((f.width + kTile - 1u) / kTile) * ((f.n_rows + kTile - 1u) / kTile);
         for (uint32_t it = 0; it < p.iterations; ++it) {
             PassArgs a;
-            a.src = d->d_denoise[it & 1u];
-            a.dst = out = d->d_denoise[(it + 1u) & 1u];
-            a.pixels = d->d_denoise_pixels;
-            a.guides = d->d_guides; a.demod = d->d_guide_demod;
+            a.src = d->dn.filter[it & 1u].p;
+            a.dst = out = d->dn.filter[(it + 1u) & 1u].p;
+            a.pixels = d->dn.filter_pixels.p;
+            a.guides = d->dn.guides.p; a.demod = d->dn.guide_demod.p;
             a.width = f.width; a.n_rows = f.n_rows; a.step = 1u << it; a.demodulate = demodulate;
             const double sc = (double)p.sigma_color / (double)(1u << it);       // sigma_c 2^-i
             a.inv_color = (float)(1.0 / (sc * sc));
@@ -292,12 +282,12 @@ int Denoise(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, const cgpt
             a.inv_position = (float)(1.0 / ((double)p.sigma_position * p.sigma_position));
             if (it + 1u == p.iterations) hipLaunchKernelGGL(atrous_pass<true>, dim3(tiles), dim3(256), 0, d->stream, a);
             else hipLaunchKernelGGL(atrous_pass<false>, dim3(tiles), dim3(256), 0, d->stream, a);
-            DN_HIP(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipGetLastError());
         }
     }
-    if (dst_rgba) DN_HIP(ctx, hipMemcpyAsync(dst_rgba, out, n * sizeof(float4), hipMemcpyDeviceToHost, d->stream));
-    if (dst_pixels) DN_HIP(ctx, hipMemcpyAsync(dst_pixels, d->d_denoise_pixels, n * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
-    DN_HIP(ctx, hipStreamSynchronize(d->stream));
+    if (dst_rgba) HIP_TRY(ctx, hipMemcpyAsync(dst_rgba, out, n * sizeof(float4), hipMemcpyDeviceToHost, d->stream));
+    if (dst_pixels) HIP_TRY(ctx, hipMemcpyAsync(dst_pixels, d->dn.filter_pixels.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(d->stream));
     return CGPT_OK;
 }
 
@@ -315,10 +305,8 @@ int CheckParams(cgpt_ctx* ctx, const cgpt_denoise_params& p)
 
 void DenoiseFree(cgpt_ctx* ctx)
 {
-    (void)hipFree(ctx->d_guides); (void)hipFree(ctx->d_guide_demod);
-    (void)hipFree(ctx->d_denoise[0]); (void)hipFree(ctx->d_denoise[1]); (void)hipFree(ctx->d_denoise_pixels);
-    ctx->d_guides = ctx->d_guide_demod = nullptr; ctx->guide_pixels = 0; ctx->guides_valid = false;
-    ctx->d_denoise[0] = ctx->d_denoise[1] = nullptr; ctx->d_denoise_pixels = nullptr; ctx->denoise_pixels = 0;
+    ctx->dn = DenoiseBuffers{};
+    ctx->guides_valid = false;
 }
 
 }  // namespace cgpt
@@ -336,9 +324,9 @@ int cgpt_read_guides(cgpt_ctx* ctx, const cgpt_camera* camera, float* dst, size_
     const size_t n = (size_t)f.width * f.n_rows;
     if (!dst || n_floats != 12 * n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats (12 per pixel)", 12 * n);
     cgpt_ctx* d = f.dev;
-    DN_HIP(ctx, hipSetDevice(d->device));
+    HIP_TRY(ctx, hipSetDevice(d->device));
     if ((rc = EnsureGuides(ctx, f, camera)) == CGPT_OK) {
-        hipError_t e = hipMemcpyAsync(dst, d->d_guides, n * 3 * sizeof(float4), hipMemcpyDeviceToHost, d->stream);
+        hipError_t e = hipMemcpyAsync(dst, d->dn.guides.p, n * 3 * sizeof(float4), hipMemcpyDeviceToHost, d->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
         if (e != hipSuccess) rc = CtxFail(ctx, CGPT_ERR_HIP, "cgpt_read_guides: %s", hipGetErrorString(e));
     }
@@ -359,7 +347,7 @@ int cgpt_denoise(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_pa
     if (!dst_rgba && !dst_pixels) return CtxFail(ctx, CGPT_ERR_INVALID, "both outputs are null");
     if (dst_rgba && n_floats != 4 * n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats (4 per pixel)", 4 * n);
     if (dst_pixels && n_pixels != n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu pixels", n);
-    const float4* acc = ctx->d_accumulator;
+    const float4* acc = ctx->fb.accumulator.p;
     if (ctx->group && (rc = GroupGatherUncounted(ctx, &acc)) != CGPT_OK) return rc;
     rc = Denoise(ctx, f, camera, p, acc, dst_rgba, dst_pixels);
     if (rc != CGPT_OK) f.dev->guides_valid = false;

@@ -20,12 +20,12 @@
 #include <cstdint>
 
 #include "cpugpupt_abi.h"
+#include "device_memory.h"
 
 namespace cgpt {
 
 hipStream_t CtxStream(cgpt_ctx* ctx);
 int CtxDevice(cgpt_ctx* ctx);
-int CtxFail(cgpt_ctx* ctx, int code, const char* fmt, ...);
 cgpt_ctx* GroupFirstMemberOrNull(cgpt_ctx* ctx);
 int GroupForwarded(cgpt_ctx* ctx, int rc);
 
@@ -137,14 +137,15 @@ static int MeasureOnDevice(cgpt_ctx* ctx, uint32_t kind, uint32_t waves_per_simd
 {
     if (!wave_insts_per_sec || kind > 12u || waves_per_simd == 0u || waves_per_simd > 8u || iters == 0u || iters > (1u << 24))
         return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_measure_issue_rate: kind <= 12, 1 <= waves_per_simd <= 8, 1 <= iters <= 2^24");
-#define MB_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return CtxFail(ctx, CGPT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
-    MB_TRY(hipSetDevice(CtxDevice(ctx)));
+    HIP_TRY(ctx, hipSetDevice(CtxDevice(ctx)));
     int cus = 0;
-    MB_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, CtxDevice(ctx)));
-    float* sink = nullptr;
-    MB_TRY(hipMalloc((void**)&sink, sizeof(float)));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    MB_TRY(hipEventCreate(&e0)); MB_TRY(hipEventCreate(&e1));
+    HIP_TRY(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, CtxDevice(ctx)));
+    DevBuf<float> sink_buf;
+    HIP_TRY(ctx, sink_buf.Alloc(1));
+    float* const sink = sink_buf.p;
+    DevEvent ev0, ev1;
+    HIP_TRY(ctx, ev0.Create()); HIP_TRY(ctx, ev1.Create());
+    const hipEvent_t e0 = ev0.e, e1 = ev1.e;
     hipStream_t st = CtxStream(ctx);
     // one 256-thread block = one wave on each of a CU's 4 SIMDs; waves_per_simd blocks per CU, all resident at once
     const dim3 grid((uint32_t)cus * waves_per_simd), block(256);
@@ -168,17 +169,15 @@ static int MeasureOnDevice(cgpt_ctx* ctx, uint32_t kind, uint32_t waves_per_simd
     launch(iters);                                                            // warm-up: code object load, clocks
     float ms = 0.0f;
     for (int rep = 0; rep < 3; ++rep) {                                       // fastest of three (the clock settles during the first)
-        MB_TRY(hipEventRecord(e0, st));
+        HIP_TRY(ctx, hipEventRecord(e0, st));
         launch(iters);
-        MB_TRY(hipEventRecord(e1, st));
-        MB_TRY(hipEventSynchronize(e1));
-        MB_TRY(hipGetLastError());
+        HIP_TRY(ctx, hipEventRecord(e1, st));
+        HIP_TRY(ctx, hipEventSynchronize(e1));
+        HIP_TRY(ctx, hipGetLastError());
         float t = 0.0f;
-        MB_TRY(hipEventElapsedTime(&t, e0, e1));
+        HIP_TRY(ctx, hipEventElapsedTime(&t, e0, e1));
         if (rep == 0 || t < ms) ms = t;
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(sink);
-#undef MB_TRY
     const double insts = (double)grid.x * 4.0 * (double)iters * (double)kInstsPerIter;
     *wave_insts_per_sec = insts / ((double)ms * 1e-3);
     if (ms_out) *ms_out = ms;

@@ -11,16 +11,15 @@
 #include <cstring>
 
 #include "cpugpupt_abi.h"
+#include "device_memory.h"
 
 namespace cgpt {
 
-int CtxFail(cgpt_ctx* ctx, int code, const char* fmt, ...);
-
-// a HIP call of a launcher: on failure the context's error names the call and the launcher returns -1
-#define LAUNCH_TRY(expr)                                                                                 \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) { CtxFail(ctx, CGPT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); return -1; } \
+// a HIP call of a launcher: on failure the context's error names the call (as HIP_TRY's does) and the launcher returns -1
+#define LAUNCH_TRY(expr)                                                     \
+    do {                                                                     \
+        hipError_t e_ = (expr);                                              \
+        if (e_ != hipSuccess) { HipFail(ctx, #expr, e_); return -1; }        \
     } while (0)
 
 // One knob table per launcher, for cgpt_set_tuning (per context, any time between renders) and the environment (process-wide
@@ -78,16 +77,12 @@ template <typename F> hipError_t QueryOccupancy(const F* kernels, uint32_t* bloc
     return e;
 }
 
-// a device buffer that only grows; reallocating waits for the device first (earlier launches may still use the old one)
-template <typename T> struct DevBuf { T* p = nullptr; size_t n = 0; };
-
+// a launcher's buffer only grows; reallocating waits for the device first (earlier launches may still use the old one)
 template <typename T> hipError_t Grow(DevBuf<T>& b, size_t n)
 {
     if (b.n >= n) return hipSuccess;
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) { (void)hipFree(b.p); b.p = nullptr; b.n = 0; e = hipMalloc((void**)&b.p, n * sizeof(T)); }
-    if (e == hipSuccess) b.n = n;
-    return e;
+    const hipError_t e = hipDeviceSynchronize();
+    return e == hipSuccess ? b.Alloc(n) : e;
 }
 
 // hipEvent pairs around the launches of the last render, grow-only: ReserveEvents before it, hipEventRecord(NextEvent()) before and

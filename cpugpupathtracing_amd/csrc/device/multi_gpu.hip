@@ -106,22 +106,15 @@ struct DeviceGroup {
     uint32_t last_debug_mode = 0;
     uint32_t last_kernel = 0;
     // device 0: staging (all bands, rank after rank) and the gathered full frame
-    float4* d_staging = nullptr; float4* d_full = nullptr; uint32_t* d_pix_staging = nullptr; uint32_t* d_full_pixels = nullptr;
-    uint32_t* d_rank_base = nullptr;       // first staging row of every rank (8 words)
-    size_t alloc_pixels = 0;
+    DevBuf<float4> staging, full; DevBuf<uint32_t> pix_staging, full_pixels;
+    DevBuf<uint32_t> rank_base;            // first staging row of every rank (8 words)
     bool gathered = false, pixels_valid = false;
     uint32_t gathers = 0;
     double gather_ms = 0.0;                // summed duration of the exchanges (hipEvents on device 0's stream)
-    hipEvent_t ev_gather0 = nullptr, ev_gather1 = nullptr;
+    DevEvent ev_gather0, ev_gather1;
 };
 
 namespace {
-
-#define G_HIP(ctx, expr)                                                                                        \
-    do {                                                                                                        \
-        hipError_t e_ = (expr);                                                                                 \
-        if (e_ != hipSuccess) return CtxFail((ctx), CGPT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 // band-ordered rows of all ranks (rank after rank, each in its own compact order) -> image order
 __global__ void __launch_bounds__(256) reorder_rows_f4(const float4* __restrict__ staging, float4* __restrict__ full, uint32_t width, uint32_t height,
@@ -169,12 +162,6 @@ void SetTiling(DeviceGroup* g, uint32_t width, uint32_t height)
     for (uint32_t r = 0; r < n; ++r) g->n_rows[r] = RowsOfRank(height, g->band_rows, n, r);
 }
 
-void FreeGathered(DeviceGroup* g)
-{
-    (void)hipFree(g->d_staging); (void)hipFree(g->d_full); (void)hipFree(g->d_pix_staging); (void)hipFree(g->d_full_pixels); (void)hipFree(g->d_rank_base);
-    g->d_staging = g->d_full = nullptr; g->d_pix_staging = g->d_full_pixels = nullptr; g->d_rank_base = nullptr; g->alloc_pixels = 0;
-}
-
 // copies the members' message (if any) into the group context and returns rc
 int Propagate(cgpt_ctx* ctx, cgpt_ctx* member, int rc)
 {
@@ -192,26 +179,20 @@ int Gather(cgpt_ctx* ctx, bool pixels)
     if (g->gathered && (!pixels || g->pixels_valid)) return CGPT_OK;
     cgpt_ctx* root = g->members[0];
     const size_t n_px = (size_t)g->width * g->height;
-    G_HIP(ctx, hipSetDevice(root->device));
-    if (g->alloc_pixels < n_px) {
-        FreeGathered(g);
-        G_HIP(ctx, hipMalloc((void**)&g->d_staging, n_px * sizeof(float4)));
-        G_HIP(ctx, hipMalloc((void**)&g->d_full, n_px * sizeof(float4)));
-        G_HIP(ctx, hipMalloc((void**)&g->d_pix_staging, n_px * sizeof(uint32_t)));
-        G_HIP(ctx, hipMalloc((void**)&g->d_full_pixels, n_px * sizeof(uint32_t)));
-        G_HIP(ctx, hipMalloc((void**)&g->d_rank_base, kMaxRanks * sizeof(uint32_t)));
-        g->alloc_pixels = n_px;
-    }
+    HIP_TRY(ctx, hipSetDevice(root->device));
+    HIP_TRY(ctx, g->staging.Grow(n_px)); HIP_TRY(ctx, g->full.Grow(n_px));   // grow-only, each on its own count
+    HIP_TRY(ctx, g->pix_staging.Grow(n_px)); HIP_TRY(ctx, g->full_pixels.Grow(n_px));
+    HIP_TRY(ctx, g->rank_base.Grow(kMaxRanks));
     uint32_t base[kMaxRanks] = { 0 };
     for (uint32_t r = 1; r < n; ++r) base[r] = base[r - 1] + g->n_rows[r - 1];
 
-    G_HIP(ctx, hipEventRecord(g->ev_gather0, root->stream));
+    HIP_TRY(ctx, hipEventRecord(g->ev_gather0.e, root->stream));
     if (g->peer_copy) {
         for (uint32_t r = 0; r < n; ++r) {
             cgpt_ctx* m = g->members[r];
             const size_t count = (size_t)g->n_rows[r] * g->width;
-            G_HIP(ctx, hipMemcpyPeerAsync(g->d_staging + (size_t)base[r] * g->width, root->device, m->d_accumulator, m->device, count * sizeof(float4), root->stream));
-            if (pixels) G_HIP(ctx, hipMemcpyPeerAsync(g->d_pix_staging + (size_t)base[r] * g->width, root->device, m->d_pixels, m->device, count * sizeof(uint32_t), root->stream));
+            HIP_TRY(ctx, hipMemcpyPeerAsync(g->staging.p + (size_t)base[r] * g->width, root->device, m->fb.accumulator.p, m->device, count * sizeof(float4), root->stream));
+            if (pixels) HIP_TRY(ctx, hipMemcpyPeerAsync(g->pix_staging.p + (size_t)base[r] * g->width, root->device, m->fb.pixels.p, m->device, count * sizeof(uint32_t), root->stream));
         }
     } else {
         // one grouped exchange: rank r sends on its own stream, rank 0 receives all of them (its own band included) on its stream.
@@ -223,33 +204,33 @@ int Gather(cgpt_ctx* ctx, bool pixels)
             for (uint32_t r = 0; r < n && first == ncclSuccess; ++r) {
                 cgpt_ctx* m = g->members[r];
                 const size_t count = (size_t)g->n_rows[r] * g->width;
-                keep(ncclSend(m->d_accumulator, count * 4, ncclFloat, 0, g->comms[r], m->stream), "ncclSend");
-                keep(ncclRecv(g->d_staging + (size_t)base[r] * g->width, count * 4, ncclFloat, (int)r, g->comms[0], root->stream), "ncclRecv");
+                keep(ncclSend(m->fb.accumulator.p, count * 4, ncclFloat, 0, g->comms[r], m->stream), "ncclSend");
+                keep(ncclRecv(g->staging.p + (size_t)base[r] * g->width, count * 4, ncclFloat, (int)r, g->comms[0], root->stream), "ncclRecv");
                 if (pixels) {
-                    keep(ncclSend(m->d_pixels, count, ncclUint32, 0, g->comms[r], m->stream), "ncclSend");
-                    keep(ncclRecv(g->d_pix_staging + (size_t)base[r] * g->width, count, ncclUint32, (int)r, g->comms[0], root->stream), "ncclRecv");
+                    keep(ncclSend(m->fb.pixels.p, count, ncclUint32, 0, g->comms[r], m->stream), "ncclSend");
+                    keep(ncclRecv(g->pix_staging.p + (size_t)base[r] * g->width, count, ncclUint32, (int)r, g->comms[0], root->stream), "ncclRecv");
                 }
             }
             keep(ncclGroupEnd(), "ncclGroupEnd");
         }
         if (first != ncclSuccess) return CtxFail(ctx, CGPT_ERR_HIP, "%s failed: %s", what, ncclGetErrorString(first));
     }
-    G_HIP(ctx, hipSetDevice(root->device));
-    uint32_t* const d_base = g->d_rank_base;
-    G_HIP(ctx, hipMemcpyAsync(d_base, base, n * sizeof(uint32_t), hipMemcpyHostToDevice, root->stream));
+    HIP_TRY(ctx, hipSetDevice(root->device));
+    uint32_t* const d_base = g->rank_base.p;
+    HIP_TRY(ctx, hipMemcpyAsync(d_base, base, n * sizeof(uint32_t), hipMemcpyHostToDevice, root->stream));
     const dim3 grid((uint32_t)((n_px + 255u) / 256u)), block(256);
-    hipLaunchKernelGGL(reorder_rows_f4, grid, block, 0, root->stream, (const float4*)g->d_staging, g->d_full, g->width, g->height, g->band_rows, n, (const uint32_t*)d_base);
-    if (pixels) hipLaunchKernelGGL(reorder_rows_u32, grid, block, 0, root->stream, (const uint32_t*)g->d_pix_staging, g->d_full_pixels, g->width, g->height, g->band_rows, n, (const uint32_t*)d_base);
-    G_HIP(ctx, hipGetLastError());
-    G_HIP(ctx, hipEventRecord(g->ev_gather1, root->stream));
+    hipLaunchKernelGGL(reorder_rows_f4, grid, block, 0, root->stream, (const float4*)g->staging.p, g->full.p, g->width, g->height, g->band_rows, n, (const uint32_t*)d_base);
+    if (pixels) hipLaunchKernelGGL(reorder_rows_u32, grid, block, 0, root->stream, (const uint32_t*)g->pix_staging.p, g->full_pixels.p, g->width, g->height, g->band_rows, n, (const uint32_t*)d_base);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(g->ev_gather1.e, root->stream));
     for (uint32_t r = 0; r < n; ++r) {                                         // the senders' streams too: their bands are free again
-        G_HIP(ctx, hipSetDevice(g->members[r]->device));
-        G_HIP(ctx, hipStreamSynchronize(g->members[r]->stream));
+        HIP_TRY(ctx, hipSetDevice(g->members[r]->device));
+        HIP_TRY(ctx, hipStreamSynchronize(g->members[r]->stream));
     }
-    G_HIP(ctx, hipSetDevice(root->device));
-    G_HIP(ctx, hipStreamSynchronize(root->stream));
+    HIP_TRY(ctx, hipSetDevice(root->device));
+    HIP_TRY(ctx, hipStreamSynchronize(root->stream));
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, g->ev_gather0, g->ev_gather1) == hipSuccess) g->gather_ms += ms;
+    if (hipEventElapsedTime(&ms, g->ev_gather0.e, g->ev_gather1.e) == hipSuccess) g->gather_ms += ms;
     g->gathered = true; g->pixels_valid = pixels;
     g->gathers++;
     return CGPT_OK;
@@ -264,15 +245,11 @@ void EnqueueRank(void* arg, uint32_t r)                                       //
 {
     EnqueueJob* j = static_cast<EnqueueJob*>(arg);
     cgpt_ctx* m = j->g->members[r];
-    try {
+    j->rcs[r] = Guarded(m, "render enqueue", [&] {
         cgpt_render_params q = *j->p;
         q.interleave_rows = j->g->band_rows; q.interleave_count = (uint32_t)j->g->members.size(); q.interleave_index = r;
-        j->rcs[r] = RenderEnqueue(m, j->camera, j->settings, &q);
-    } catch (const std::exception& e) {
-        j->rcs[r] = CtxFail(m, CGPT_ERR_INVALID, "render enqueue: %s", e.what());
-    } catch (...) {
-        j->rcs[r] = CtxFail(m, CGPT_ERR_INVALID, "render enqueue: unknown exception");
-    }
+        return RenderEnqueue(m, j->camera, j->settings, &q);
+    });
 }
 
 }  // namespace
@@ -285,7 +262,7 @@ int GroupCreate(const int* device_ids, int n_devices, uint32_t flags, cgpt_ctx**
 {
     cgpt_ctx* ctx = new (std::nothrow) cgpt_ctx;
     DeviceGroup* g = new (std::nothrow) DeviceGroup;
-    if (!ctx || !g) { delete ctx; delete g; return CreateFail(CGPT_ERR_INVALID, "out of host memory"); }
+    if (!ctx || !g) { delete ctx; delete g; return CtxFail(nullptr, CGPT_ERR_INVALID, "out of host memory"); }
     ctx->group = g;
     g->peer_copy = (flags & CGPT_CTX_GATHER_PEER_COPY) != 0;
     auto fail = [&](int rc) { GroupDestroy(ctx); delete ctx; return rc; };
@@ -296,7 +273,7 @@ int GroupCreate(const int* device_ids, int n_devices, uint32_t flags, cgpt_ctx**
             for (int i = 0; i < n_devices; ++i)
                 for (int j = 0; j < i; ++j)
                     if (devs[i] == devs[j])
-                        return fail(CreateFail(CGPT_ERR_INVALID, "device %d listed twice (only a CGPT_CTX_GATHER_PEER_COPY context may share a device between ranks)", devs[i]));
+                        return fail(CtxFail(nullptr, CGPT_ERR_INVALID, "device %d listed twice (only a CGPT_CTX_GATHER_PEER_COPY context may share a device between ranks)", devs[i]));
         g->members.reserve(n_devices);
         g->n_rows.assign(n_devices, 0);
         for (int i = 0; i < n_devices; ++i) {
@@ -306,20 +283,20 @@ int GroupCreate(const int* device_ids, int n_devices, uint32_t flags, cgpt_ctx**
             g->members.push_back(m);
         }
         hipError_t e = hipSetDevice(g->members[0]->device);
-        if (e == hipSuccess) e = hipEventCreate(&g->ev_gather0);
-        if (e == hipSuccess) e = hipEventCreate(&g->ev_gather1);
-        if (e != hipSuccess) return fail(CreateFail(CGPT_ERR_HIP, "multi-device context events: %s", hipGetErrorString(e)));
+        if (e == hipSuccess) e = g->ev_gather0.Create();
+        if (e == hipSuccess) e = g->ev_gather1.Create();
+        if (e != hipSuccess) return fail(CtxFail(nullptr, CGPT_ERR_HIP, "multi-device context events: %s", hipGetErrorString(e)));
         if (!g->peer_copy) {
             g->comms.assign(n_devices, nullptr);
             const ncclResult_t r = ncclCommInitAll(g->comms.data(), n_devices, devs.data());
             if (r != ncclSuccess) {
                 g->comms.clear();
-                return fail(CreateFail(CGPT_ERR_HIP, "ncclCommInitAll over %d devices failed: %s", n_devices, ncclGetErrorString(r)));
+                return fail(CtxFail(nullptr, CGPT_ERR_HIP, "ncclCommInitAll over %d devices failed: %s", n_devices, ncclGetErrorString(r)));
             }
         }
         g->workers.Start((uint32_t)n_devices);
     } catch (const std::exception& e) {
-        return fail(CreateFail(CGPT_ERR_INVALID, "cgpt_ctx_create: %s", e.what()));
+        return fail(CtxFail(nullptr, CGPT_ERR_INVALID, "cgpt_ctx_create: %s", e.what()));
     }
     *out = ctx;
     return CGPT_OK;
@@ -332,13 +309,11 @@ void GroupDestroy(cgpt_ctx* ctx)
     g->workers.Stop();
     for (cgpt_ctx* m : g->members) { (void)hipSetDevice(m->device); (void)hipStreamSynchronize(m->stream); }
     for (ncclComm_t c : g->comms) if (c) (void)ncclCommDestroy(c);
-    if (!g->members.empty()) {
-        (void)hipSetDevice(g->members[0]->device); FreeGathered(g);
-        if (g->ev_gather0) (void)hipEventDestroy(g->ev_gather0);
-        if (g->ev_gather1) (void)hipEventDestroy(g->ev_gather1);
-    }
-    for (cgpt_ctx* m : g->members) (void)cgpt_ctx_destroy(m);
-    delete g;
+    std::vector<cgpt_ctx*> members;
+    members.swap(g->members);
+    if (!members.empty()) (void)hipSetDevice(members[0]->device);
+    delete g;                                                                  // the gathered frame and its events, before the contexts they live on
+    for (cgpt_ctx* m : members) (void)cgpt_ctx_destroy(m);
     ctx->group = nullptr;
 }
 
@@ -448,8 +423,8 @@ int GroupReadAccumulator(cgpt_ctx* ctx, float* dst, size_t n_floats)
     if (!dst || n_floats != n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats", n);
     const int rc = Gather(ctx, false);
     if (rc != CGPT_OK) return rc;
-    G_HIP(ctx, hipSetDevice(g->members[0]->device));
-    G_HIP(ctx, hipMemcpy(dst, g->d_full, n * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipSetDevice(g->members[0]->device));
+    HIP_TRY(ctx, hipMemcpy(dst, g->full.p, n * sizeof(float), hipMemcpyDeviceToHost));
     return CGPT_OK;
 }
 
@@ -465,12 +440,12 @@ int GroupReadPixels(cgpt_ctx* ctx, uint32_t* dst, size_t n_pixels)
     const int rc = Gather(ctx, debug);
     if (rc != CGPT_OK) return rc;
     cgpt_ctx* root = g->members[0];
-    G_HIP(ctx, hipSetDevice(root->device));
+    HIP_TRY(ctx, hipSetDevice(root->device));
     if (!debug) {
-        G_HIP(ctx, LaunchPackPixels(g->d_full, g->d_full_pixels, n, g->num_accumulated, root->stream));
-        G_HIP(ctx, hipStreamSynchronize(root->stream));
+        HIP_TRY(ctx, LaunchPackPixels(g->full.p, g->full_pixels.p, n, g->num_accumulated, root->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(root->stream));
     }
-    G_HIP(ctx, hipMemcpy(dst, g->d_full_pixels, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(dst, g->full_pixels.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return CGPT_OK;
 }
 
@@ -492,7 +467,7 @@ int GroupGatherUncounted(cgpt_ctx* ctx, const float4** frame)
     g->gathers = gathers; g->gather_ms = gather_ms;
     if (rc != CGPT_OK) { g->gathered = false; g->pixels_valid = false; return rc; }
     g->gathered = gathered; g->pixels_valid = gathered && pixels_valid;
-    *frame = g->d_full;
+    *frame = g->full.p;
     return CGPT_OK;
 }
 
@@ -531,11 +506,11 @@ int GroupDevicePtr(cgpt_ctx* ctx, bool pixels, void** ptr, size_t* n_bytes)
     const size_t n = (size_t)g->width * g->height;
     if (pixels && g->last_debug_mode == 0u) {
         cgpt_ctx* root = g->members[0];
-        G_HIP(ctx, hipSetDevice(root->device));
-        G_HIP(ctx, LaunchPackPixels(g->d_full, g->d_full_pixels, n, g->num_accumulated, root->stream));
-        G_HIP(ctx, hipStreamSynchronize(root->stream));
+        HIP_TRY(ctx, hipSetDevice(root->device));
+        HIP_TRY(ctx, LaunchPackPixels(g->full.p, g->full_pixels.p, n, g->num_accumulated, root->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(root->stream));
     }
-    *ptr = pixels ? (void*)g->d_full_pixels : (void*)g->d_full;               // on device_ids[0]
+    *ptr = pixels ? (void*)g->full_pixels.p : (void*)g->full.p;               // on device_ids[0]
     *n_bytes = n * (pixels ? sizeof(uint32_t) : sizeof(float4));
     return CGPT_OK;
 }

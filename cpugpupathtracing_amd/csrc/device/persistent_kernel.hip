@@ -333,14 +333,13 @@ void PersistentFree(void* state)
 {
     if (!state) return;
     PtHost* h = static_cast<PtHost*>(state);
-    (void)hipFree(h->st_en[0].p); (void)hipFree(h->st_en[1].p); (void)hipFree(h->brute.p); (void)hipFree(h->overflow.p); (void)hipFree(h->work_counters.p);
     for (int i = 0; i < 2; ++i) {
         if (h->streams[i]) (void)hipStreamDestroy(h->streams[i]);
         if (h->acc_done[i]) (void)hipEventDestroy(h->acc_done[i]);
     }
     if (h->begin) (void)hipEventDestroy(h->begin);
     FreeEvents(h->ev);
-    delete h;
+    delete h;                                                                 // and its buffers
 }
 
 void PersistentCollectTiming(void* state, uint32_t lobe_level, double* ms, uint32_t* launches, uint32_t* waves_per_simd)

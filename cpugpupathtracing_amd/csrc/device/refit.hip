@@ -129,11 +129,7 @@ int SceneLost(cgpt_ctx* ctx, const char* what, hipError_t e)
     return CtxFail(ctx, CGPT_ERR_HIP, "%s failed: %s (the device scene is dropped; upload it again)", what, hipGetErrorString(e));
 }
 
-#define REFIT_HIP(ctx, expr)                                                                                            \
-    do {                                                                                                                \
-        hipError_t e_ = (expr);                                                                                         \
-        if (e_ != hipSuccess) return CtxFail((ctx), CGPT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));      \
-    } while (0)
+// HIP_TRY once the device scene has begun to change
 #define REFIT_HIP_WRITING(ctx, expr)                                                                                    \
     do {                                                                                                                \
         hipError_t e_ = (expr);                                                                                         \
@@ -156,31 +152,26 @@ int RefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles,
     if (d.kind == CGPT_OBJECT_MESH)
         for (uint32_t i = 0; i < n_tris; ++i) area += HostTriangleArea(triangles[i]);
 
-    REFIT_HIP(ctx, hipSetDevice(ctx->device));
-    REFIT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->refit_staging_tris < n_tris) {
-        (void)hipFree(ctx->d_refit_staging);
-        ctx->d_refit_staging = nullptr; ctx->refit_staging_tris = 0;
-        REFIT_HIP(ctx, hipMalloc((void**)&ctx->d_refit_staging, sizeof(cgpt_triangle) * (size_t)n_tris));
-        ctx->refit_staging_tris = n_tris;
-    }
-    REFIT_HIP(ctx, hipMemcpyAsync(ctx->d_refit_staging, triangles, sizeof(cgpt_triangle) * (size_t)n_tris, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, ctx->sb.refit_staging.Grow(n_tris));                          // the stream was just drained: nothing uses the old one
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->sb.refit_staging.p, triangles, sizeof(cgpt_triangle) * (size_t)n_tris, hipMemcpyHostToDevice, ctx->stream));
 
     // from here on the scene changes
     const uint32_t tri_base = d.tri_base;
     hipLaunchKernelGGL(refit_triangles, dim3((n_tris + kRefitThreads - 1) / kRefitThreads), dim3(kRefitThreads), 0, ctx->stream,
-                       reinterpret_cast<const float*>(ctx->d_refit_staging), ctx->d_tri_leaf, ctx->d_tri_orig, ctx->d_tri_normal, ro.leaf_base, tri_base, n_tris);
+                       reinterpret_cast<const float*>(ctx->sb.refit_staging.p), ctx->sb.tri_leaf.p, ctx->sb.tri_orig.p, ctx->sb.tri_normal.p, ro.leaf_base, tri_base, n_tris);
     REFIT_HIP_WRITING(ctx, hipGetLastError());
     for (size_t level = ro.level_offsets.empty() ? 0 : ro.level_offsets.size() - 1; level-- > 0;) {
         const uint32_t first = ro.level_offsets[level], n = ro.level_offsets[level + 1] - first;
         if (n == 0) continue;
         hipLaunchKernelGGL(refit_level, dim3((n + kRefitThreads - 1) / kRefitThreads), dim3(kRefitThreads), 0, ctx->stream,
-                           ctx->d_node_pairs, ctx->d_tri_leaf, ctx->d_tri_orig, ctx->d_refit_levels + ro.level_begin + first, n, tri_base);
+                           ctx->sb.node_pairs.p, ctx->sb.tri_leaf.p, ctx->sb.tri_orig.p, ctx->sb.refit_levels.p + ro.level_begin + first, n, tri_base);
         REFIT_HIP_WRITING(ctx, hipGetLastError());
     }
     if (d.kind == CGPT_OBJECT_MESH) {
         d.total_area = area;
-        REFIT_HIP_WRITING(ctx, hipMemcpyAsync(&ctx->d_objects[obj_index].total_area, &d.total_area, sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        REFIT_HIP_WRITING(ctx, hipMemcpyAsync(&ctx->sb.objects.p[obj_index].total_area, &d.total_area, sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     }
     REFIT_HIP_WRITING(ctx, hipStreamSynchronize(ctx->stream));
     if (total_area_out) *total_area_out = area;
@@ -208,10 +199,10 @@ int ExportBvh(cgpt_ctx* ctx, uint32_t obj_index, cgpt_bvh_node* nodes_out, uint3
     }
     std::vector<float4> span(n_pairs ? 4 * (size_t)(hi - lo + 1) : 0);
     std::vector<float4> leaf_tail(n_tris);                                    // {pad, e2.z, tri_idx, last_in_leaf} of every leaf slot
-    REFIT_HIP(ctx, hipSetDevice(ctx->device));
-    REFIT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (n_pairs) REFIT_HIP(ctx, hipMemcpy(span.data(), ctx->d_node_pairs + 4 * (size_t)lo, span.size() * sizeof(float4), hipMemcpyDeviceToHost));
-    REFIT_HIP(ctx, hipMemcpy2D(leaf_tail.data(), sizeof(float4), ctx->d_tri_leaf + 3 * (size_t)ro.leaf_base + 2, 3 * sizeof(float4),
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_pairs) HIP_TRY(ctx, hipMemcpy(span.data(), ctx->sb.node_pairs.p + 4 * (size_t)lo, span.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy2D(leaf_tail.data(), sizeof(float4), ctx->sb.tri_leaf.p + 3 * (size_t)ro.leaf_base + 2, 3 * sizeof(float4),
                                sizeof(float4), n_tris, hipMemcpyDeviceToHost));
 
     std::vector<uint32_t> pair_of(n_pairs ? hi - lo + 1 : 0, 0xFFFFFFFFu);    // stored record -> depth-first pair index k (nodes 2k+1, 2k+2)
@@ -245,7 +236,7 @@ int ExportBvh(cgpt_ctx* ctx, uint32_t obj_index, cgpt_bvh_node* nodes_out, uint3
     if (!words(d.root_code, root)) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u: malformed root", obj_index);
     if (d.root_code & kLeafBit) {                                             // a leaf-rooted mesh: CalculateNodeBounds over every slot
         std::vector<float4> orig(3 * (size_t)n_tris);
-        REFIT_HIP(ctx, hipMemcpy(orig.data(), ctx->d_tri_orig + 3 * (size_t)d.tri_base, orig.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(orig.data(), ctx->sb.tri_orig.p + 3 * (size_t)d.tri_base, orig.size() * sizeof(float4), hipMemcpyDeviceToHost));
         float b[6] = { 1e30f, 1e30f, 1e30f, -1e30f, -1e30f, -1e30f };
         for (uint32_t s = 0; s < n_tris; ++s) {
             const uint32_t t = bits(leaf_tail[s].z);
@@ -285,26 +276,13 @@ int UpdatePrimitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_object* obj)
     }
     float4 q[2];
     PackObjTrace(nd, q[0], q[1]);
-    REFIT_HIP(ctx, hipSetDevice(ctx->device));
-    REFIT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    REFIT_HIP_WRITING(ctx, hipMemcpyAsync(ctx->d_objects + obj_index, &nd, sizeof(DevObject), hipMemcpyHostToDevice, ctx->stream));
-    REFIT_HIP_WRITING(ctx, hipMemcpyAsync(ctx->d_obj_trace + 2 * (size_t)obj_index, q, sizeof(q), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    REFIT_HIP_WRITING(ctx, hipMemcpyAsync(ctx->sb.objects.p + obj_index, &nd, sizeof(DevObject), hipMemcpyHostToDevice, ctx->stream));
+    REFIT_HIP_WRITING(ctx, hipMemcpyAsync(ctx->sb.obj_trace.p + 2 * (size_t)obj_index, q, sizeof(q), hipMemcpyHostToDevice, ctx->stream));
     REFIT_HIP_WRITING(ctx, hipStreamSynchronize(ctx->stream));
     d = nd;
     return CGPT_OK;
-}
-
-// nothing may unwind through the C ABI (the host side allocates vectors)
-template <class F>
-int Guarded(cgpt_ctx* ctx, const char* what, F&& body)
-{
-    try {
-        return body();
-    } catch (const std::exception& e) {
-        return CtxFail(ctx, CGPT_ERR_INVALID, "%s: %s", what, e.what());
-    } catch (...) {
-        return CtxFail(ctx, CGPT_ERR_INVALID, "%s: unknown exception", what);
-    }
 }
 
 }  // namespace

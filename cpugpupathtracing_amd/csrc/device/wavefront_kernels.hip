@@ -800,7 +800,7 @@ struct WfHost {
 static void WfRelease(WfHost* h)
 {
     for (uint32_t p = 0; p < kMaxPools; ++p) {                               // every pointer, whatever its size: also a failed, partial allocation
-        ForEachBuffer(h->dev[p], h->held, [](auto*& ptr, size_t) { (void)hipFree(ptr); });
+        ForEachBuffer(h->dev[p], h->held, [](auto*& ptr, size_t) { DevFree(ptr); });
         h->dev[p] = WfDev{};
     }
     h->held = WfSizes{}; h->held_pools = 0;
@@ -970,7 +970,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, uin
         hipError_t err = hipSuccess;
         for (uint32_t p = 0; p < n_pools; ++p) {
             WfDev& d = h->dev[p];
-            ForEachBuffer(d, need, [&](auto*& ptr, size_t bytes) { if (err == hipSuccess && bytes) err = hipMalloc((void**)&ptr, bytes); });
+            ForEachBuffer(d, need, [&](auto*& ptr, size_t bytes) { if (err == hipSuccess && bytes) err = DevAlloc((void**)&ptr, bytes); });
             if (err == hipSuccess && d.spec_tab) err = hipMemset(d.spec_tab, 0, need.spec * sizeof(unsigned long long));   // epoch 0 is never current: all entries free
             h->spec_epoch[p] = 0;
         }
