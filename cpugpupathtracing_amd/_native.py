@@ -120,6 +120,7 @@ PROTOTYPES = {
     "cgpt_ctx_destroy": (C.c_int, [_vp]),
     "cgpt_last_error": (C.c_char_p, [_vp]),
     "cgpt_set_stream": (C.c_int, [_vp, _vp]),
+    "cgpt_set_nee_candidates": (C.c_int, [_vp, C.c_uint32]),
     "cgpt_scene_upload": (C.c_int, [_vp, C.POINTER(SceneDesc)]),
     "cgpt_scene_update_materials": (C.c_int, [_vp, C.POINTER(Material), C.c_uint32]),
     "cgpt_scene_update_roughness": (C.c_int, [_vp, _fp, C.c_uint32]),

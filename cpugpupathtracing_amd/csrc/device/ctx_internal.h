@@ -56,6 +56,9 @@ struct cgpt_ctx {
     std::vector<float> h_roughness, h_transmission_roughness;
     std::vector<float4> h_materials;
     uint32_t lobe_level = 0;
+    // cgpt_set_nee_candidates: context state like the stream (an upload keeps it).  A render with more than one candidate, NEE on and
+    // TracePathAdvanced paths runs the RIS instantiations of the render kernels
+    uint32_t nee_candidates = 1;
 
     // in-place edits of the uploaded scene (refit.hip): host copies of the objects, each mesh's child-pair records grouped by
     // depth, and where the renumbering put every record
@@ -86,6 +89,7 @@ struct cgpt_ctx {
     uint32_t pending_kernel = 0;
     uint32_t pending_num_accumulated = 0;
     uint32_t pending_lobe_level = 0;
+    bool pending_ris = false;
     cgpt::DevRenderArgs pending_args{};
     uint32_t last_debug_mode = 0;
     uint32_t last_kernel = 0;                     // cgpt_kernel the last render ran (AUTO resolved)
@@ -119,6 +123,7 @@ int GroupSceneUpload(cgpt_ctx* ctx, const cgpt_scene_desc* scene);
 int GroupUpdateMaterials(cgpt_ctx* ctx, const cgpt_material* materials, uint32_t n);
 int GroupUpdateRoughness(cgpt_ctx* ctx, const float* roughness, uint32_t n);
 int GroupUpdateTransmissionRoughness(cgpt_ctx* ctx, const float* roughness, uint32_t n);
+int GroupSetNeeCandidates(cgpt_ctx* ctx, uint32_t candidates);
 int GroupRefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris, float* total_area_out);
 int GroupUpdatePrimitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_object* obj);
 int GroupRender(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p);

@@ -98,9 +98,12 @@ struct DevCamera { float pos[3], top_left[3], top_right[3], bottom_left[3]; };
 
 struct DevSettings {
     int32_t max_ray_depth;
-    uint32_t nee, cosine, rr;
+    uint32_t nee, cosine, rr;  // nee: 0 off; in the RIS instantiations of the render kernels the number of NEE candidates M > 1 (DESIGN.md 5.12:
+                               // the struct keeps its size, so every kernel argument stays where it was); the others read it as a flag.
+                               // Test it for zero only: `nee == 1u` or a one-bit field breaks at M > 1
     uint32_t render_mode, debug_mode;
 };
+static_assert(sizeof(DevSettings) == 24, "DevSettings sits inside DevRenderArgs: a new word moves every kernel argument behind it (M travels in nee)");
 
 __host__ __device__ inline uint32_t GlobalRow(uint32_t l, uint32_t band_first, uint32_t band_h, uint32_t band_stride)
 {

@@ -379,6 +379,13 @@ int GroupUpdateTransmissionRoughness(cgpt_ctx* ctx, const float* roughness, uint
     return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_update_transmission_roughness(m, roughness, n); });
 }
 
+int GroupSetNeeCandidates(cgpt_ctx* ctx, uint32_t candidates)              // the range was checked: no member can refuse, none is left behind
+{
+    for (cgpt_ctx* m : ctx->group->members) { const int rc = cgpt_set_nee_candidates(m, candidates); if (rc != CGPT_OK) return Propagate(ctx, m, rc); }
+    ctx->nee_candidates = candidates;
+    return CGPT_OK;
+}
+
 int GroupRender(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p)
 {
     DeviceGroup* g = ctx->group;

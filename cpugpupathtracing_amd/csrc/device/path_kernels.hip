@@ -29,7 +29,8 @@ extern __shared__ uint32_t lds_stack[];
 // and the dispatcher places single waves (1080p, one sample: 1.71 -> 1.68 ms, profiles/r03/one_sample.md).
 // GLOSSY (the lobe level): 0 no rough lobe; 1 the scene has a rough specular material (shade_device.hpp: ggx_sample); 2 it has a rough dielectric (rough_glass_sample; carries the rough specular lobe too).
 // The scenes without a rough lobe keep the code without it.
-template <bool COUNT, bool BRUTE, int GLOSSY>
+// RIS: the render resamples its NEE light sample (cgpt_set_nee_candidates > 1, shade_device.hpp); the renders with one candidate keep the code without it.
+template <bool COUNT, bool BRUTE, int GLOSSY, bool RIS>
 __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
 {
     const DevScene& sc = args.scene;
@@ -105,7 +106,7 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
                 finalize = dead;
             } else {
                 ray.t = cur.t; ray.obj = cur.obj; ray.tri = cur.tri; ray.bvh_depth = cur.bvh_depth;
-                const uint32_t flags = shade_bounce<COUNT, GLOSSY>(sc, st, ray, ps, sray, pending, cnt);
+                const uint32_t flags = shade_bounce<COUNT, GLOSSY, RIS>(sc, st, ray, ps, sray, pending, cnt);
                 dead = (flags & kBounceTerminate) != 0;
                 shadow_kind = (flags & kBounceShadow) != 0;
                 finalize = dead && !shadow_kind;
@@ -150,13 +151,14 @@ static uint32_t MegakernelBlockThreads(const DevRenderArgs& args)
     return args.n_samples == 1u ? 64u : 256u;
 }
 
-// every instantiation, [COUNT][BRUTE][GLOSSY]
-static decltype(&megakernel<false, false, 0>) const kMegakernels[2][2][3] = {
-    { { megakernel<false, false, 0>, megakernel<false, false, 1>, megakernel<false, false, 2> }, { megakernel<false, true, 0>, megakernel<false, true, 1>, megakernel<false, true, 2> } },
-    { { megakernel<true, false, 0>, megakernel<true, false, 1>, megakernel<true, false, 2> }, { megakernel<true, true, 0>, megakernel<true, true, 1>, megakernel<true, true, 2> } },
-};
+// every instantiation, [RIS][COUNT][BRUTE][GLOSSY]
+#define CGPT_MEGAKERNELS(R) \
+    { { { megakernel<false, false, 0, R>, megakernel<false, false, 1, R>, megakernel<false, false, 2, R> }, { megakernel<false, true, 0, R>, megakernel<false, true, 1, R>, megakernel<false, true, 2, R> } }, \
+      { { megakernel<true, false, 0, R>, megakernel<true, false, 1, R>, megakernel<true, false, 2, R> }, { megakernel<true, true, 0, R>, megakernel<true, true, 1, R>, megakernel<true, true, 2, R> } } }
+static decltype(&megakernel<false, false, 0, false>) const kMegakernels[2][2][2][3] = { CGPT_MEGAKERNELS(false), CGPT_MEGAKERNELS(true) };
+#undef CGPT_MEGAKERNELS
 
-hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, uint32_t lobe_level, hipStream_t stream)
+hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, uint32_t lobe_level, bool ris, hipStream_t stream)
 {
     const bool brute = args.settings.render_mode != 2u;
     const uint32_t bt = MegakernelBlockThreads(args);
@@ -164,16 +166,16 @@ hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, uint32_t lobe
     const uint32_t tiles_x = (args.width + edge - 1u) / edge, tiles_y = (args.n_rows + edge - 1u) / edge;
     const dim3 grid(tiles_x * tiles_y), block(bt);
     const size_t lds = (size_t)args.scene.stack_depth * bt * sizeof(uint32_t);
-    hipLaunchKernelGGL(kMegakernels[count][brute][lobe_level], grid, block, lds, stream, args);
+    hipLaunchKernelGGL(kMegakernels[ris][count][brute][lobe_level], grid, block, lds, stream, args);
     return hipGetLastError();
 }
 
-uint32_t MegakernelWavesPerSimd(const DevRenderArgs& args, uint32_t lobe_level)
+uint32_t MegakernelWavesPerSimd(const DevRenderArgs& args, uint32_t lobe_level, bool ris)
 {
     int b = 0;
     const uint32_t bt = MegakernelBlockThreads(args);
     const size_t lds = (size_t)args.scene.stack_depth * bt * sizeof(uint32_t);
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kMegakernels[0][args.settings.render_mode != 2u][lobe_level], (int)bt, lds);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kMegakernels[ris][0][args.settings.render_mode != 2u][lobe_level], (int)bt, lds);
     return e == hipSuccess && b > 0 ? std::max(1u, (uint32_t)b * bt / 256u) : 1u;    // blocks per CU -> waves per SIMD (4 SIMDs)
 }
 

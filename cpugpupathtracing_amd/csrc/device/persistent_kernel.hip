@@ -66,7 +66,7 @@ enum : uint32_t {                      // per-lane path flags
 // sample: 2.47 -> 2.21 ms).  Kept out of the throughput instantiations, which it costs registers and SGPR spills (profiles/r03/one_sample.md).
 // GLOSSY (the lobe level): 0 no rough lobe; 1 the scene has a rough specular material (shade_device.hpp: ggx_sample); 2 it has a rough dielectric (rough_glass_sample; carries the rough specular lobe too).
 // The scenes without a rough lobe keep the code without it.
-template <bool COUNT, bool BRUTE, bool TAIL, int GLOSSY>
+template <bool COUNT, bool BRUTE, bool TAIL, int GLOSSY, bool RIS>
 __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderArgs args, const PtDev pt, uint32_t batch_first, const TraceTune tune)
 {
     const DevScene& sc = args.scene;
@@ -153,7 +153,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
             ps.throughput = tp; ps.energy = en; ps.rng = rng; ps.depth = pf & kPfDepthMask; ps.is_specular = (pf & kPfSpecular) != 0u;
             Ray shadow = ray;
             V3 pend = mk(0.0f);
-            const uint32_t flags = shade_bounce<COUNT, GLOSSY>(sc, st, ray, ps, shadow, pend, cnt);
+            const uint32_t flags = shade_bounce<COUNT, GLOSSY, RIS>(sc, st, ray, ps, shadow, pend, cnt);
             tp = ps.throughput; en = ps.energy; rng = ps.rng;
             pf = (ps.depth & kPfDepthMask) | (ps.is_specular ? kPfSpecular : 0u);
             const bool dead = (flags & kBounceTerminate) != 0u;
@@ -263,15 +263,15 @@ struct PtTuning {
     uint32_t fine_rounds = 2;     // fine fetches (one id per idle lane) once fewer than this many ids per lane of the grid are left
 };
 
-// every instantiation, [GLOSSY][COUNT][BRUTE][TAIL]
-static decltype(&pt_persistent<false, false, false, 0>) const kPtKernels[3][2][2][2] = {
-    { { { pt_persistent<false, false, false, 0>, pt_persistent<false, false, true, 0> }, { pt_persistent<false, true, false, 0>, pt_persistent<false, true, true, 0> } },
-      { { pt_persistent<true, false, false, 0>, pt_persistent<true, false, true, 0> }, { pt_persistent<true, true, false, 0>, pt_persistent<true, true, true, 0> } } },
-    { { { pt_persistent<false, false, false, 1>, pt_persistent<false, false, true, 1> }, { pt_persistent<false, true, false, 1>, pt_persistent<false, true, true, 1> } },
-      { { pt_persistent<true, false, false, 1>, pt_persistent<true, false, true, 1> }, { pt_persistent<true, true, false, 1>, pt_persistent<true, true, true, 1> } } },
-    { { { pt_persistent<false, false, false, 2>, pt_persistent<false, false, true, 2> }, { pt_persistent<false, true, false, 2>, pt_persistent<false, true, true, 2> } },
-      { { pt_persistent<true, false, false, 2>, pt_persistent<true, false, true, 2> }, { pt_persistent<true, true, false, 2>, pt_persistent<true, true, true, 2> } } },
+// every instantiation, [RIS][GLOSSY][COUNT][BRUTE][TAIL]
+#define CGPT_PT_LEVEL(G, R) \
+    { { { pt_persistent<false, false, false, G, R>, pt_persistent<false, false, true, G, R> }, { pt_persistent<false, true, false, G, R>, pt_persistent<false, true, true, G, R> } }, \
+      { { pt_persistent<true, false, false, G, R>, pt_persistent<true, false, true, G, R> }, { pt_persistent<true, true, false, G, R>, pt_persistent<true, true, true, G, R> } } }
+static decltype(&pt_persistent<false, false, false, 0, false>) const kPtKernels[2][3][2][2][2] = {
+    { CGPT_PT_LEVEL(0, false), CGPT_PT_LEVEL(1, false), CGPT_PT_LEVEL(2, false) },
+    { CGPT_PT_LEVEL(0, true), CGPT_PT_LEVEL(1, true), CGPT_PT_LEVEL(2, true) },
 };
+#undef CGPT_PT_LEVEL
 
 struct PtHost {
     PtTuning tune;
@@ -283,7 +283,7 @@ struct PtHost {
     hipEvent_t begin = nullptr, acc_done[2] = { nullptr, nullptr };
     EventPairs ev;
     uint32_t n_cus = 0;
-    uint32_t blocks_per_cu[3][2][2][2] = {};  // [GLOSSY][COUNT][BRUTE][TAIL]
+    uint32_t blocks_per_cu[2][3][2][2][2] = {};  // [RIS][GLOSSY][COUNT][BRUTE][TAIL]
     size_t occupancy_lds = 0;
 };
 
@@ -342,16 +342,16 @@ void PersistentFree(void* state)
     delete h;                                                                 // and its buffers
 }
 
-void PersistentCollectTiming(void* state, uint32_t lobe_level, double* ms, uint32_t* launches, uint32_t* waves_per_simd)
+void PersistentCollectTiming(void* state, uint32_t lobe_level, bool ris, double* ms, uint32_t* launches, uint32_t* waves_per_simd)
 {
     *ms = 0.0; *launches = 0; *waves_per_simd = 0;
     if (!state) return;
     PtHost* h = static_cast<PtHost*>(state);
     ForEachPair(h->ev, [&](uint32_t, float t) { *ms += t; *launches += 1; });
-    *waves_per_simd = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[lobe_level][0][0][0]) * (kTraceBlock / 256u);
+    *waves_per_simd = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[ris][lobe_level][0][0][0]) * (kTraceBlock / 256u);
 }
 
-int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, uint32_t lobe_level)
+int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, uint32_t lobe_level, bool ris)
 {
     hipStream_t stream = CtxStream(ctx);
     PtHost* h = PtGetHost(ctx);
@@ -362,11 +362,11 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, ui
     const uint32_t top_records = std::min(h->tune.top_records, args_in.scene.n_top_records);
     const size_t lds = trace_lds_bytes(top_records);
     if (h->occupancy_lds != lds) {
-        LAUNCH_TRY(QueryOccupancy(&kPtKernels[0][0][0][0], &h->blocks_per_cu[0][0][0][0], 24, kTraceBlock, lds));
+        LAUNCH_TRY(QueryOccupancy(&kPtKernels[0][0][0][0][0], &h->blocks_per_cu[0][0][0][0][0], 48, kTraceBlock, lds));
         h->occupancy_lds = lds;
     }
     const bool tail = args_in.n_samples <= h->tune.tail_samples;              // a small call: mostly drain
-    const uint32_t blocks_per_cu = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[lobe_level][count][brute][tail]);
+    const uint32_t blocks_per_cu = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[ris][lobe_level][count][brute][tail]);
     // the resident capacity of the chip, or fewer blocks when there are fewer than 64 paths per wave (a small call ends sooner when
     // its paths are spread thin than when the tail of a launch waits for 4 096 waves to find out that there is nothing to do)
     const uint32_t n_tiles = ((args_in.width + 7u) / 8u) * ((args_in.n_rows + 7u) / 8u);
@@ -374,7 +374,8 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, ui
     const uint32_t blocks_wanted = (uint32_t)std::min<uint64_t>(h->n_cus * blocks_per_cu, std::max<uint64_t>(1, paths_in_call / (16u * (kTraceBlock / 64u))));
     const dim3 grid(blocks_wanted), block(256), trace_block(kTraceBlock);
     uint32_t max_blocks = 1;
-    for (int i = 0; i < 16; ++i) max_blocks = std::max(max_blocks, h->blocks_per_cu[i >> 3][(i >> 2) & 1][(i >> 1) & 1][i & 1]);
+    // every instantiation (the loop used to stop after lobe level 1; level 2 and RIS never have the higher occupancy, so the sizes below are what they were)
+    for (int i = 0; i < 48; ++i) max_blocks = std::max(max_blocks, (&h->blocks_per_cu[0][0][0][0][0])[i]);
     const uint32_t max_threads = h->n_cus * max_blocks * kTraceBlock;
 
     const uint32_t tiles_x = (args_in.width + 7u) / 8u;
@@ -433,7 +434,7 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, ui
         work_sizes(pt.n_paths, grid.x * (kTraceBlock / 64u), h->tune.fine_rounds, h->tune.chunk, pt.coarse, pt.fine_below);
         // the buffer's previous batch must have been accumulated (same stream: implicit)
         LAUNCH_TRY(hipEventRecord(NextEvent(h->ev), st));
-        hipLaunchKernelGGL(kPtKernels[lobe_level][count][brute][tail], grid, trace_block, lds, st, args_in, pt, bfirst, tt);
+        hipLaunchKernelGGL(kPtKernels[ris][lobe_level][count][brute][tail], grid, trace_block, lds, st, args_in, pt, bfirst, tt);
         LAUNCH_TRY(hipEventRecord(NextEvent(h->ev), st));
         // accumulate in sample order: batch k after batch k-1
         if (n_streams == 2 && k > 0) LAUNCH_TRY(hipStreamWaitEvent(st, h->acc_done[(k - 1u) & 1u], 0));

@@ -178,7 +178,9 @@ enum : uint32_t { kBounceChainShift = 4u, kChainReflect = 1u, kChainRefract = 2u
 // ref: Main.cpp:452-463).  Emissive energy is added here; the final debug-view overrides are applied by the caller.
 // GLOSSY: 0 no rough lobe (the mirror-only code); 1 the scene has a material with roughness > 0 (ggx_sample); 2 it has one with a
 // transmission roughness > 0 (rough_glass_sample; this instantiation carries the rough specular lobe too).
-template <bool COUNT, int GLOSSY = 0>
+// RIS: the NEE light sample is the survivor of M = st.nee > 1 candidates (resampled importance sampling); the
+// instantiations without it keep the one-sample code.
+template <bool COUNT, int GLOSSY = 0, bool RIS = false>
 __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSettings& st, Ray& ray, PathState& ps, Ray& shadow,
                                                  V3& pending, Counters& cnt)
 {
@@ -200,7 +202,36 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
 
     uint32_t result = 0;
     const float diffuse_weight = max_std(0.0f, 1.0f - mat.specular - mat.refractivity);
-    if (sc.n_lights > 0 && st.nee && diffuse_weight > 0.001f) {               // ref: Main.cpp:439-465
+    if (RIS && sc.n_lights > 0 && st.nee && diffuse_weight > 0.001f) {
+        // M candidates, each drawn as sample_light draws and weighed by its unshadowed contribution c_j (the one-sample code's `pending`,
+        // 0 when a cosine test fails): w_j = c_j.x + c_j.y + c_j.z.  One float u_j follows every candidate's draws, the first and the
+        // weightless ones included, and decides the streaming reservoir; a candidate that finds it empty is taken whatever u_j is
+        // (random_float can return 1.0f).  The survivor y gets the one shadow ray and pending = c_y * wsum / (M w_y).
+        // No early exit and no branch around a draw, so the loop is the same for every lane; but the candidates are serial: the light index
+        // of j + 1 comes from the RNG state after j, whose draw count depends on objects[].kind (and ball_sample rejects), so a lane pays
+        // about M x the dependent chain lights[] -> objects[] -> materials[] (+ three triangle records for a mesh light) per bounce.
+        const uint32_t M = st.nee;
+        const V3 brdf_diffuse = mat.albedo * kInvPi;
+        float wsum = 0.0f, w_y = 0.0f, dist_y = 0.0f;
+        V3 c_y = mk(0.0f), dir_y = mk(0.0f);
+        for (uint32_t j = 0; j < M; ++j) {
+            const LightSample ls = sample_light(sc, ps.rng, hit.pos);
+            const float u = random_float(ps.rng);
+            const float NdotL = dot(hit.normal, ls.to_light);
+            const float NLdotL = dot(ls.normal, -ls.to_light);
+            const float solid_angle = (NLdotL * ls.area) / (ls.distance * ls.distance);
+            const float light_pdf = 1.0f / solid_angle;
+            const V3 c = ps.throughput * (NdotL / light_pdf) * brdf_diffuse * ls.emission * (float)sc.n_lights * diffuse_weight;
+            const float w = (NdotL > 0.0f && NLdotL > 0.0f) ? c.x + c.y + c.z : 0.0f;
+            wsum += w;
+            if (w > 0.0f && (w_y == 0.0f || u * wsum < w)) { c_y = c; w_y = w; dir_y = ls.to_light; dist_y = ls.distance; }   // w_y == 0: empty
+        }
+        if (wsum > 0.0f) {
+            shadow = make_ray(hit.pos + dir_y * kNudge, dir_y, dist_y - 2.0f * kNudge);
+            pending = c_y * (wsum / ((float)M * w_y));
+            result |= kBounceShadow;
+        }
+    } else if (sc.n_lights > 0 && st.nee && diffuse_weight > 0.001f) {        // ref: Main.cpp:439-465
         const LightSample ls = sample_light(sc, ps.rng, hit.pos);
         const float NdotL = dot(hit.normal, ls.to_light);
         const float NLdotL = dot(ls.normal, -ls.to_light);

@@ -311,7 +311,8 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
 // BRUTE: the render has TracePath paths (RENDER_MODE_BRUTE_FORCE / COMPARISON); a separate instantiation, so the TracePathAdvanced
 // renders carry neither its code nor its registers.  GLOSSY (the lobe level): 0 no rough lobe; 1 the scene has a rough specular material (shade_device.hpp: ggx_sample); 2 it has a rough dielectric (rough_glass_sample; carries the rough specular lobe too).
 // A rough bounce reports lobe choice 0, so its ray is never elected or followed as a specular chain.
-template <bool COUNT, bool FIRST, bool BRUTE = false, int GLOSSY = 0>
+// RIS: the render resamples its NEE light sample (cgpt_set_nee_candidates > 1, shade_device.hpp); one shadow ray and one pending contribution per bounce either way.
+template <bool COUNT, bool FIRST, bool BRUTE = false, int GLOSSY = 0, bool RIS = false>
 __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, const WfDev wf, uint32_t batch_first)
 {
     constexpr bool first_round = FIRST;
@@ -473,7 +474,7 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
                         flags = 0u;
                     }
                 }
-            } else if (is_pixel) flags = shade_bounce<COUNT, GLOSSY>(sc, args.settings, ray, ps, shadow, pending, cnt);
+            } else if (is_pixel) flags = shade_bounce<COUNT, GLOSSY, RIS>(sc, args.settings, ray, ps, shadow, pending, cnt);
             emit_ext = (flags & kBounceTerminate) == 0u;
             emit_sh = (flags & kBounceShadow) != 0u;
             if (kChains && emit_ext) {
@@ -728,18 +729,18 @@ static uint32_t CoprimeRotation(uint32_t n_waves, uint32_t n_tiles)
     return 0u;
 }
 
-// every instantiation: trace [COUNT][FIRST], shade [GLOSSY][COUNT][FIRST][BRUTE]
+// every instantiation: trace [COUNT][FIRST], shade [RIS][GLOSSY][COUNT][FIRST][BRUTE]
 static decltype(&wf_trace<false, false>) const kTraceKernels[2][2] = {
     { wf_trace<false, false>, wf_trace<false, true> }, { wf_trace<true, false>, wf_trace<true, true> },
 };
-static decltype(&wf_shade<false, false>) const kShadeKernels[3][2][2][2] = {
-    { { { wf_shade<false, false, false, 0>, wf_shade<false, false, true, 0> }, { wf_shade<false, true, false, 0>, wf_shade<false, true, true, 0> } },
-      { { wf_shade<true, false, false, 0>, wf_shade<true, false, true, 0> }, { wf_shade<true, true, false, 0>, wf_shade<true, true, true, 0> } } },
-    { { { wf_shade<false, false, false, 1>, wf_shade<false, false, true, 1> }, { wf_shade<false, true, false, 1>, wf_shade<false, true, true, 1> } },
-      { { wf_shade<true, false, false, 1>, wf_shade<true, false, true, 1> }, { wf_shade<true, true, false, 1>, wf_shade<true, true, true, 1> } } },
-    { { { wf_shade<false, false, false, 2>, wf_shade<false, false, true, 2> }, { wf_shade<false, true, false, 2>, wf_shade<false, true, true, 2> } },
-      { { wf_shade<true, false, false, 2>, wf_shade<true, false, true, 2> }, { wf_shade<true, true, false, 2>, wf_shade<true, true, true, 2> } } },
+#define CGPT_SHADE_LEVEL(G, R) \
+    { { { wf_shade<false, false, false, G, R>, wf_shade<false, false, true, G, R> }, { wf_shade<false, true, false, G, R>, wf_shade<false, true, true, G, R> } }, \
+      { { wf_shade<true, false, false, G, R>, wf_shade<true, false, true, G, R> }, { wf_shade<true, true, false, G, R>, wf_shade<true, true, true, G, R> } } }
+static decltype(&wf_shade<false, false>) const kShadeKernels[2][3][2][2][2] = {
+    { CGPT_SHADE_LEVEL(0, false), CGPT_SHADE_LEVEL(1, false), CGPT_SHADE_LEVEL(2, false) },
+    { CGPT_SHADE_LEVEL(0, true), CGPT_SHADE_LEVEL(1, true), CGPT_SHADE_LEVEL(2, true) },
 };
+#undef CGPT_SHADE_LEVEL
 
 // What a pool's buffers are sized for (one record per render; the pools of a render are alike)
 struct WfSizes {
@@ -790,7 +791,7 @@ struct WfHost {
     uint32_t held_pools = 0;
     uint32_t spec_epoch[kMaxPools] = {};         // last epoch used in each pool's spec_tab
     uint32_t n_cus = 0;
-    uint32_t trace_blocks_per_cu[2][2] = {}, shade_blocks_per_cu[3][2][2] = {};   // trace: [COUNT][FIRST]; shade: [GLOSSY][COUNT][BRUTE]
+    uint32_t trace_blocks_per_cu[2][2] = {}, shade_blocks_per_cu[2][3][2][2] = {};   // trace: [COUNT][FIRST]; shade: [RIS][GLOSSY][COUNT][BRUTE]
     size_t occupancy_lds = 0;
     // hipEvent pairs around every trace launch of the last render (roofline accounting: the dominant kernel's own duration)
     EventPairs trace_ev;
@@ -884,7 +885,7 @@ int WavefrontSetTuning(cgpt_ctx* ctx, const char* name, uint32_t value)
     return h ? SetKnob(ctx, FindKnob(kKnobs, name), h->tune, name, value) : CGPT_ERR_HIP;
 }
 
-int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, uint32_t lobe_level)
+int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, uint32_t lobe_level, bool ris)
 {
     hipStream_t stream = CtxStream(ctx);
     WfHost* h = WfGetHost(ctx);
@@ -905,11 +906,12 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, uin
     if (h->occupancy_lds != trace_lds) {
         LAUNCH_TRY(QueryOccupancy(&kTraceKernels[0][0], &h->trace_blocks_per_cu[0][0], 4, kTraceBlock, trace_lds));
         // shade: the round-0 and later-round instantiations share one grid size (one output segment per wave)
-        uint32_t shade[3][2][2][2];
-        LAUNCH_TRY(QueryOccupancy(&kShadeKernels[0][0][0][0], &shade[0][0][0][0], 24, 256, 0));
-        for (int g = 0; g < 3; ++g)
-            for (int c = 0; c < 2; ++c)
-                for (int b = 0; b < 2; ++b) h->shade_blocks_per_cu[g][c][b] = std::min(shade[g][c][0][b], shade[g][c][1][b]);
+        uint32_t shade[2][3][2][2][2];
+        LAUNCH_TRY(QueryOccupancy(&kShadeKernels[0][0][0][0][0], &shade[0][0][0][0][0], 48, 256, 0));
+        for (int r = 0; r < 2; ++r)
+            for (int g = 0; g < 3; ++g)
+                for (int c = 0; c < 2; ++c)
+                    for (int b = 0; b < 2; ++b) h->shade_blocks_per_cu[r][g][c][b] = std::min(shade[r][g][c][0][b], shade[r][g][c][1][b]);
         h->occupancy_lds = trace_lds;
     }
     const dim3 block(256);
@@ -917,7 +919,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, uin
     const dim3 trace_grid_later(n_cus * std::min(h->tune.max_trace_blocks, h->trace_blocks_per_cu[count][0]));
     const bool brute = args_in.settings.render_mode != 2u;                    // the render has TracePath paths (ref: Main.cpp:719-729)
     const uint32_t brute_levels = brute ? (uint32_t)args_in.settings.max_ray_depth + 1u : 0u;
-    const uint32_t (&shade_blocks)[2][2] = h->shade_blocks_per_cu[lobe_level];   // every lobe level's shade kernels have grids of their own
+    const uint32_t (&shade_blocks)[2][2] = h->shade_blocks_per_cu[ris][lobe_level];   // every lobe level's shade kernels, with and without RIS, have grids of their own
     const dim3 shade_grid(n_cus * shade_blocks[count][brute]);
     // one output segment per shade wave, sized for the most 64-item blocks a wave can be handed
     const uint32_t n_segs = n_cus * std::max({ shade_blocks[0][0], shade_blocks[1][0], shade_blocks[0][1], shade_blocks[1][1] }) * 4u;
@@ -1032,7 +1034,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, uin
                     }
                     wf.spec_epoch = h->spec_epoch[p];
                 }
-                hipLaunchKernelGGL(kShadeKernels[lobe_level][count][first][brute], shade_grid, block, 0, st, args, wf, bfirst);
+                hipLaunchKernelGGL(kShadeKernels[ris][lobe_level][count][first][brute], shade_grid, block, 0, st, args, wf, bfirst);
                 hipLaunchKernelGGL(wf_plan, dim3(2u * wf.n_bands), dim3(256), 0, st, wf);
                 hipLaunchKernelGGL(wf_gather, dim3(std::min(2u * wf.n_segs, n_cus * 16u)), block, 0, st, wf);
                 launches += 3;

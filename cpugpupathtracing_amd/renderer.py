@@ -42,6 +42,7 @@ class Renderer:
         self.num_accumulated = 0      # ref: Main.cpp:205
         self._glossy = False          # the device holds a roughness > 0 (cgpt_scene_update_roughness)
         self._rough_glass = False     # the device holds a transmission roughness > 0 (cgpt_scene_update_transmission_roughness)
+        self._nee_candidates = 1      # cgpt_set_nee_candidates
 
     def _check(self, rc: int):
         if rc != 0:
@@ -49,6 +50,17 @@ class Renderer:
 
     def set_stream(self, hip_stream: int):
         self._check(self.L.cgpt_set_stream(self._ctx, C.c_void_p(hip_stream)))
+
+    def set_nee_candidates(self, m: int):
+        """cgpt_set_nee_candidates: the NEE light sample of the renders that follow is the survivor of m candidates (resampled importance
+        sampling; 1..32, 1 = the reference's single sample, bit for bit).  State of the renderer, kept across upload(); call
+        reset_accumulator() before the next frame."""
+        self._check(self.L.cgpt_set_nee_candidates(self._ctx, int(m)))
+        self._nee_candidates = int(m)
+
+    @property
+    def nee_candidates(self) -> int:
+        return self._nee_candidates
 
     def upload(self, scene: Scene):
         """cgpt_scene_upload, then the scene's roughness (cgpt_scene_update_roughness) and transmission roughness

@@ -29,7 +29,8 @@ extern "C" {
                                  (cgpt_read_guides, cgpt_denoise) and a new struct (cgpt_denoise_params) only; the microfacet specular
                                  lobe added one new symbol (cgpt_scene_update_roughness) only; CGPT_BUILD_SAH_BINNED is a new enum
                                  value only; the rough dielectric lobe added one new symbol
-                                 (cgpt_scene_update_transmission_roughness) only */
+                                 (cgpt_scene_update_transmission_roughness) only; resampled light sampling added one new symbol
+                                 only (cgpt_set_nee_candidates) */
 
 enum cgpt_status {
     CGPT_OK = 0,
@@ -190,6 +191,15 @@ int cgpt_ctx_destroy(cgpt_ctx* ctx);
 const char* cgpt_last_error(const cgpt_ctx* ctx);
 /* run on a caller-provided hipStream_t (e.g. torch's current stream); NULL restores the context's own stream */
 int cgpt_set_stream(cgpt_ctx* ctx, void* hip_stream);
+/* Resampled importance sampling of the NEE light sample (Talbot et al. 2005): at every bounce that samples a light,
+ * `candidates` light samples are drawn as the reference draws its one, each is weighed by its unshadowed contribution, and one survivor
+ * gets the shadow ray -- one shadow ray and the same expectation as before, at close to the variance of `candidates` NEE samples.
+ * Context state like the stream, not scene state: the default is 1 (the reference's estimator, bit for bit), cgpt_scene_upload keeps the
+ * value, and it may be set before a scene exists.  Range 1..32; 0 or more than 32 is refused with CGPT_ERR_INVALID and nothing changed.
+ * Read by the renders that follow; ignored where there is no NEE (next_event_estimation_enabled == 0, CGPT_MODE_BRUTE_FORCE and the
+ * TracePath half of CGPT_MODE_COMPARISON).  The caller resets the accumulator; the denoiser's cached guides stay valid (first hits do
+ * not depend on it); a multi-device context sets every device. */
+int cgpt_set_nee_candidates(cgpt_ctx* ctx, uint32_t candidates);
 
 /* replaces the implicit use of data.objects / materials / light_source_indices (ref: Main.cpp:209-212, 303-315) */
 int cgpt_scene_upload(cgpt_ctx* ctx, const cgpt_scene_desc* scene);
