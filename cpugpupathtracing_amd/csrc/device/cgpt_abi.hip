@@ -74,6 +74,7 @@ void FreeScene(cgpt_ctx* ctx)
     ctx->sb = SceneBuffers{};
     ctx->h_objects.clear(); ctx->refit_objects.clear(); ctx->record_perm.clear();
     ctx->h_roughness.clear(); ctx->h_transmission_roughness.clear(); ctx->h_materials.clear(); ctx->lobe_level = 0;
+    ctx->any_smooth = false; ctx->h_lights.clear();
     ctx->has_scene = false;
 }
 
@@ -116,6 +117,15 @@ int ResolveBand(cgpt_ctx* ctx, const cgpt_render_params& p, Band& b)
     return CGPT_OK;
 }
 
+// the GLOSSY instantiation the renders run (ctx_internal.h: lobe_level), from the two roughness arrays and the smooth flags
+void UpdateLobeLevel(cgpt_ctx* ctx)
+{
+    bool specular = false, glass = false;
+    for (const float v : ctx->h_roughness) specular = specular || v > 0.0f;
+    for (const float v : ctx->h_transmission_roughness) glass = glass || v > 0.0f;
+    ctx->lobe_level = ctx->any_smooth ? 3u : (glass ? 2u : (specular ? 1u : 0u));
+}
+
 // cgpt_scene_update_roughness (transmission false: PackMaterial's alpha, materials[4i+3].z) and cgpt_scene_update_transmission_roughness
 // (true: alpha_t, .w) of a one-device context.  Everything is refused before the device write; the other lobe's values are kept.
 int UpdateRoughnessWord(cgpt_ctx* ctx, const float* roughness, uint32_t n_materials, bool transmission)
@@ -123,11 +133,8 @@ int UpdateRoughnessWord(cgpt_ctx* ctx, const float* roughness, uint32_t n_materi
     const char* const what = transmission ? "transmission roughness" : "roughness";
     if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
     if (!roughness || n_materials != ctx->n_materials) return CtxFail(ctx, CGPT_ERR_INVALID, "expected %u %s values", ctx->n_materials, what);
-    bool rough = false;
-    for (uint32_t i = 0; i < n_materials; ++i) {
+    for (uint32_t i = 0; i < n_materials; ++i)
         if (!(roughness[i] >= 0.0f && roughness[i] <= 1.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "material %u: %s %g outside [0, 1]", i, what, (double)roughness[i]);
-        rough = rough || roughness[i] > 0.0f;
-    }
     std::vector<float4> mats;
     std::vector<float> values;
     try { mats = ctx->h_materials; values.assign(roughness, roughness + n_materials); } catch (const std::exception& e) { return CtxFail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
@@ -142,10 +149,36 @@ int UpdateRoughnessWord(cgpt_ctx* ctx, const float* roughness, uint32_t n_materi
     }
     ctx->h_materials.swap(mats);
     (transmission ? ctx->h_transmission_roughness : ctx->h_roughness).swap(values);
-    bool other = false;
-    for (const float v : transmission ? ctx->h_roughness : ctx->h_transmission_roughness) other = other || v > 0.0f;
-    const bool specular = transmission ? other : rough, glass = transmission ? rough : other;
-    ctx->lobe_level = glass ? 2u : (specular ? 1u : 0u);
+    UpdateLobeLevel(ctx);
+    return CGPT_OK;
+}
+
+// cgpt_scene_update_smooth_normals of a one-device context: DevObject.smooth of every object.  Everything is refused before the device write.
+int UpdateSmoothNormals(cgpt_ctx* ctx, const uint32_t* smooth, uint32_t n_objects)
+{
+    if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!smooth || n_objects != ctx->h_objects.size()) return CtxFail(ctx, CGPT_ERR_INVALID, "expected %zu smooth-normal flags", ctx->h_objects.size());
+    bool any = false;
+    for (uint32_t i = 0; i < n_objects; ++i) {
+        if (smooth[i] > 1u) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u: smooth-normal flag %u is neither 0 nor 1", i, smooth[i]);
+        any = any || smooth[i] != 0u;
+    }
+    for (const uint32_t li : ctx->h_lights)
+        if (smooth[li] != 0u) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u is a light: its sampled normal is v0.normal, so it cannot shade with smooth normals", li);
+    std::vector<DevObject> objects;
+    try { objects = ctx->h_objects; } catch (const std::exception& e) { return CtxFail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
+    for (uint32_t i = 0; i < n_objects; ++i) objects[i].smooth = smooth[i];
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->scene_generation++;                                                   // the denoiser's guides hold the normal (denoise.hip)
+    const hipError_t e = hipMemcpy(ctx->sb.objects.p, objects.data(), objects.size() * sizeof(DevObject), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {                                                     // the records may be half written: drop the scene (refit.hip: SceneLost)
+        ctx->has_scene = false;
+        return CtxFail(ctx, CGPT_ERR_HIP, "hipMemcpy of the object records failed: %s (the device scene is dropped; upload it again)", hipGetErrorString(e));
+    }
+    ctx->h_objects.swap(objects);
+    ctx->any_smooth = any;
+    UpdateLobeLevel(ctx);
     return CGPT_OK;
 }
 
@@ -271,6 +304,13 @@ int cgpt_scene_update_transmission_roughness(cgpt_ctx* ctx, const float* roughne
     return UpdateRoughnessWord(ctx, roughness, n_materials, true);
 }
 
+int cgpt_scene_update_smooth_normals(cgpt_ctx* ctx, const uint32_t* smooth, uint32_t n_objects)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupUpdateSmoothNormals(ctx, smooth, n_objects); });
+    return UpdateSmoothNormals(ctx, smooth, n_objects);
+}
+
 int cgpt_camera_from_view(const float pos[3], const float view_dir[3], float fov_deg, float aspect, cgpt_camera* out)
 {
     if (!pos || !view_dir || !out) return CGPT_ERR_INVALID;
@@ -297,7 +337,14 @@ int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout)
     if ((rc = UploadArray(ctx, ctx->sb.node_pairs, layout.node_pairs)) != CGPT_OK) return rc;
     if ((rc = UploadArray(ctx, ctx->sb.tri_leaf, layout.tri_leaf)) != CGPT_OK) return rc;
     if ((rc = UploadArray(ctx, ctx->sb.tri_orig, layout.tri_orig)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, ctx->sb.tri_normal, layout.tri_normal)) != CGPT_OK) return rc;
+    // tri_normal: the n0 records, then the {n1, n2} pairs (device_scene.h)
+    const size_t n_tris_total = layout.tri_normal.size();
+    if (layout.tri_normal12.size() != 2 * n_tris_total) return CtxFail(ctx, CGPT_ERR_INVALID, "layout: %zu normal pairs for %zu triangles", layout.tri_normal12.size() / 2, n_tris_total);
+    HIP_TRY(ctx, ctx->sb.tri_normal.Alloc(n_tris_total ? 3 * n_tris_total : 1));
+    if (n_tris_total) {
+        HIP_TRY(ctx, hipMemcpy(ctx->sb.tri_normal.p, layout.tri_normal.data(), sizeof(float4) * n_tris_total, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(ctx->sb.tri_normal.p + n_tris_total, layout.tri_normal12.data(), sizeof(float4) * 2 * n_tris_total, hipMemcpyHostToDevice));
+    }
     if ((rc = UploadArray(ctx, ctx->sb.materials, layout.materials)) != CGPT_OK) return rc;
     if ((rc = UploadArray(ctx, ctx->sb.objects, layout.objects)) != CGPT_OK) return rc;
     if ((rc = UploadArray(ctx, ctx->sb.obj_trace, layout.obj_trace)) != CGPT_OK) return rc;
@@ -305,11 +352,12 @@ int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout)
     if ((rc = UploadArray(ctx, ctx->sb.refit_levels, layout.refit_levels)) != CGPT_OK) return rc;
     ctx->h_objects = layout.objects; ctx->refit_objects = layout.refit_objects; ctx->record_perm = layout.record_perm;
     ctx->h_roughness.assign(layout.n_materials, 0.0f); ctx->h_transmission_roughness.assign(layout.n_materials, 0.0f); ctx->h_materials = layout.materials; ctx->lobe_level = 0;
+    ctx->any_smooth = false; ctx->h_lights = layout.lights;                    // an upload resets every smooth-normal flag (LayoutScene writes 0)
 
     ctx->scene.node_pairs = ctx->sb.node_pairs.p; ctx->scene.tri_leaf = ctx->sb.tri_leaf.p; ctx->scene.tri_orig = ctx->sb.tri_orig.p; ctx->scene.tri_normal = ctx->sb.tri_normal.p;
     ctx->scene.materials = ctx->sb.materials.p; ctx->scene.objects = ctx->sb.objects.p; ctx->scene.obj_trace = ctx->sb.obj_trace.p; ctx->scene.lights = ctx->sb.lights.p;
     ctx->scene.n_objects = (uint32_t)layout.objects.size(); ctx->scene.n_lights = (uint32_t)layout.lights.size(); ctx->scene.stack_depth = layout.stack_depth;
-    ctx->scene.n_top_records = layout.n_top_records; ctx->scene.n_pair_records = layout.n_pair_records; ctx->scene.n_small_tris = layout.n_small_tris;
+    ctx->scene.n_top_records = layout.n_top_records; ctx->scene.n_tris_total = (uint32_t)n_tris_total; ctx->scene.n_small_tris = layout.n_small_tris;
     ctx->n_materials = layout.n_materials;
     ctx->has_scene = true;
     return CGPT_OK;

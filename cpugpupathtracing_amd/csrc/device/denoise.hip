@@ -45,6 +45,8 @@ __device__ __forceinline__ void tile_pixel(uint32_t width, uint32_t& px, uint32_
 
 // One thread per pixel of the band (global rows first_row ..): {x.xyz, t | n.xyz, bits(obj) | albedo.xyz, bits(mat_index)} and the
 // demodulation albedo (the albedo per channel where it is >= 1e-3 on a hit that is not a light, else 1).
+// SMOOTH: the scene has an object with smooth normals (cgpt_scene_update_smooth_normals): n is get_hit's interpolated normal there.
+template <bool SMOOTH>
 __global__ void __launch_bounds__(256) guides_kernel(const DevScene sc, const DevCamera cam, uint32_t width, uint32_t height, uint32_t first_row,
                                                      uint32_t n_rows, float4* __restrict__ guides, float4* __restrict__ demod)
 {
@@ -61,7 +63,7 @@ __global__ void __launch_bounds__(256) guides_kernel(const DevScene sc, const De
     float4 g2 = g1;
     float4 m = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
     if (ray.obj != kNoHit) {
-        const Hit h = get_hit<false>(sc, ray, cnt);
+        const Hit h = get_hit<false, SMOOTH>(sc, ray, cnt);
         const Mat mat = load_material(sc, h.mat);
         g0 = make_float4(h.pos.x, h.pos.y, h.pos.z, ray.t);
         g1 = make_float4(h.normal.x, h.normal.y, h.normal.z, __uint_as_float(ray.obj));
@@ -229,8 +231,10 @@ int EnsureGuides(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera)
     memcpy(&cam, camera, sizeof(cam));
     const uint32_t tiles = ((f.width + kTile - 1u) / kTile) * ((f.n_rows + kTile - 1u) / kTile);
     const size_t lds = (size_t)d->scene.stack_depth * 256u * sizeof(uint32_t);   // intersect_rays_kernel's stack
-    hipLaunchKernelGGL(guides_kernel, dim3(tiles), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
-                       d->dn.guides.p, d->dn.guide_demod.p);
+    if (d->any_smooth) hipLaunchKernelGGL(guides_kernel<true>, dim3(tiles), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
+                                          d->dn.guides.p, d->dn.guide_demod.p);
+    else hipLaunchKernelGGL(guides_kernel<false>, dim3(tiles), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
+                            d->dn.guides.p, d->dn.guide_demod.p);
     HIP_TRY(ctx, hipGetLastError());
     memcpy(d->guide_frame, key, sizeof(key));
     memcpy(&d->guide_camera, camera, sizeof(cgpt_camera));

@@ -21,7 +21,11 @@
 //  tri_orig    float4[3 * n_tris]   triangles in ORIGINAL order for GetTriangle() users (ref: BVH.cpp:129-132): shading normal
 //                                   = v0.normal (ref: Primitives.cpp:148-151) and mesh-light sampling (ref: Primitives.cpp:170-186):
 //                                   {p0.xyz, n0.x | p1.xyz, n0.y | p2.xyz, n0.z}
-//  tri_normal  float4[n_tris]       {n0.xyz, -} in ORIGINAL order: the shading normal of a hit is one 16-byte load
+//  tri_normal  float4[3 * n_tris]   {n0.xyz, -} in ORIGINAL order, records [0, n_tris): the flat shading normal of a hit is one 16-byte load.
+//                                   Behind them the other two vertex normals, {n1.xyz, -} at n_tris + 2 i and {n2.xyz, -} at n_tris + 2 i + 1
+//                                   (one 32-byte pair per triangle, original order; n_tris = DevScene.n_tris_total): read only by the
+//                                   SMOOTH instantiations, for a hit on an object whose DevObject.smooth is set (shade_device.hpp: get_hit,
+//                                   cgpt_scene_update_smooth_normals).  Always uploaded and refitted, so the flag update is one small write.
 //  materials   float4[4 * n_mat]    {albedo.xyz, specular | refractivity, absorption.xyz | ior, emissive.xyz | intensity, is_light, alpha, alpha_t}
 //                                   (alpha = roughness^2 of the specular lobe, cgpt_scene_update_roughness; 0 = the mirror;
 //                                    alpha_t = transmission roughness^2 of the dielectric lobe,
@@ -74,7 +78,7 @@ struct DevObject {
     float sphere_center[3];
     float plane_normal[3];
     float plane_point[3];
-    uint32_t pad_;
+    uint32_t smooth;      // cgpt_scene_update_smooth_normals: 1 = interpolated vertex normals on this mesh / triangle object (0 after an upload)
 };
 
 struct DevScene {
@@ -90,7 +94,8 @@ struct DevScene {
     uint32_t n_lights;
     uint32_t stack_depth;  // LDS stack entries per lane (max BVH depth + 1 over all meshes)
     uint32_t n_top_records; // records [0, n_top_records) are the breadth-first top of the trees
-    uint32_t n_pair_records; // child-pair records in node_pairs (read by no kernel; kept so the argument layout stays put)
+    uint32_t n_tris_total;  // records in tri_orig = where the {n1, n2} pairs begin in tri_normal (read by the SMOOTH instantiations only; the word
+                            // held n_pair_records, which no kernel read: the argument layout stays put)
     uint32_t n_small_tris;  // tri_leaf records [0, n_small_tris) are the triangles of the scene's small meshes (device_scene.h "record order")
 };
 

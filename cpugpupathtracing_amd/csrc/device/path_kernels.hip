@@ -27,7 +27,7 @@ extern __shared__ uint32_t lds_stack[];
 // Block shape: 256 threads = a 16x16-pixel tile (the reference's job size, ref: Main.cpp:705-711), or -- one-sample calls -- 64 threads =
 // one 8x8 tile per single-wave block: the wave's slot and its LDS are free the moment its own longest path ends instead of its block's,
 // and the dispatcher places single waves (1080p, one sample: 1.71 -> 1.68 ms, profiles/r03/one_sample.md).
-// GLOSSY (the lobe level): 0 no rough lobe; 1 the scene has a rough specular material (shade_device.hpp: ggx_sample); 2 it has a rough dielectric (rough_glass_sample; carries the rough specular lobe too).
+// GLOSSY (the lobe level): 0 no rough lobe; 1 the scene has a rough specular material (shade_device.hpp: ggx_sample); 2 it has a rough dielectric (rough_glass_sample; carries the rough specular lobe too); 3 it has an object with smooth normals (get_hit's SMOOTH, cgpt_scene_update_smooth_normals; carries both rough lobes too).
 // The scenes without a rough lobe keep the code without it.
 // RIS: the render resamples its NEE light sample (cgpt_set_nee_candidates > 1, shade_device.hpp); the renders with one candidate keep the code without it.
 template <bool COUNT, bool BRUTE, int GLOSSY, bool RIS>
@@ -153,9 +153,11 @@ static uint32_t MegakernelBlockThreads(const DevRenderArgs& args)
 
 // every instantiation, [RIS][COUNT][BRUTE][GLOSSY]
 #define CGPT_MEGAKERNELS(R) \
-    { { { megakernel<false, false, 0, R>, megakernel<false, false, 1, R>, megakernel<false, false, 2, R> }, { megakernel<false, true, 0, R>, megakernel<false, true, 1, R>, megakernel<false, true, 2, R> } }, \
-      { { megakernel<true, false, 0, R>, megakernel<true, false, 1, R>, megakernel<true, false, 2, R> }, { megakernel<true, true, 0, R>, megakernel<true, true, 1, R>, megakernel<true, true, 2, R> } } }
-static decltype(&megakernel<false, false, 0, false>) const kMegakernels[2][2][2][3] = { CGPT_MEGAKERNELS(false), CGPT_MEGAKERNELS(true) };
+    { { { megakernel<false, false, 0, R>, megakernel<false, false, 1, R>, megakernel<false, false, 2, R>, megakernel<false, false, 3, R> },     \
+        { megakernel<false, true, 0, R>, megakernel<false, true, 1, R>, megakernel<false, true, 2, R>, megakernel<false, true, 3, R> } },         \
+      { { megakernel<true, false, 0, R>, megakernel<true, false, 1, R>, megakernel<true, false, 2, R>, megakernel<true, false, 3, R> },         \
+        { megakernel<true, true, 0, R>, megakernel<true, true, 1, R>, megakernel<true, true, 2, R>, megakernel<true, true, 3, R> } } }
+static decltype(&megakernel<false, false, 0, false>) const kMegakernels[2][2][2][4] = { CGPT_MEGAKERNELS(false), CGPT_MEGAKERNELS(true) };
 #undef CGPT_MEGAKERNELS
 
 hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, uint32_t lobe_level, bool ris, hipStream_t stream)

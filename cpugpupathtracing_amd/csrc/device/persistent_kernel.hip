@@ -64,7 +64,7 @@ enum : uint32_t {                      // per-lane path flags
 // Main.cpp:702,825-942), which are mostly drain: once nothing is left to fetch, a wave with few busy lanes runs their rays in the lean
 // per-lane loop (trace_steps.hpp: lean_traverse) instead of voted steps, because the call ends when its longest chain does (1080p, one
 // sample: 2.47 -> 2.21 ms).  Kept out of the throughput instantiations, which it costs registers and SGPR spills (profiles/r03/one_sample.md).
-// GLOSSY (the lobe level): 0 no rough lobe; 1 the scene has a rough specular material (shade_device.hpp: ggx_sample); 2 it has a rough dielectric (rough_glass_sample; carries the rough specular lobe too).
+// GLOSSY (the lobe level): 0 no rough lobe; 1 the scene has a rough specular material (shade_device.hpp: ggx_sample); 2 it has a rough dielectric (rough_glass_sample; carries the rough specular lobe too); 3 it has an object with smooth normals (get_hit's SMOOTH, cgpt_scene_update_smooth_normals; carries both rough lobes too).
 // The scenes without a rough lobe keep the code without it.
 template <bool COUNT, bool BRUTE, bool TAIL, int GLOSSY, bool RIS>
 __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderArgs args, const PtDev pt, uint32_t batch_first, const TraceTune tune)
@@ -267,9 +267,9 @@ struct PtTuning {
 #define CGPT_PT_LEVEL(G, R) \
     { { { pt_persistent<false, false, false, G, R>, pt_persistent<false, false, true, G, R> }, { pt_persistent<false, true, false, G, R>, pt_persistent<false, true, true, G, R> } }, \
       { { pt_persistent<true, false, false, G, R>, pt_persistent<true, false, true, G, R> }, { pt_persistent<true, true, false, G, R>, pt_persistent<true, true, true, G, R> } } }
-static decltype(&pt_persistent<false, false, false, 0, false>) const kPtKernels[2][3][2][2][2] = {
-    { CGPT_PT_LEVEL(0, false), CGPT_PT_LEVEL(1, false), CGPT_PT_LEVEL(2, false) },
-    { CGPT_PT_LEVEL(0, true), CGPT_PT_LEVEL(1, true), CGPT_PT_LEVEL(2, true) },
+static decltype(&pt_persistent<false, false, false, 0, false>) const kPtKernels[2][4][2][2][2] = {
+    { CGPT_PT_LEVEL(0, false), CGPT_PT_LEVEL(1, false), CGPT_PT_LEVEL(2, false), CGPT_PT_LEVEL(3, false) },
+    { CGPT_PT_LEVEL(0, true), CGPT_PT_LEVEL(1, true), CGPT_PT_LEVEL(2, true), CGPT_PT_LEVEL(3, true) },
 };
 #undef CGPT_PT_LEVEL
 
@@ -283,7 +283,7 @@ struct PtHost {
     hipEvent_t begin = nullptr, acc_done[2] = { nullptr, nullptr };
     EventPairs ev;
     uint32_t n_cus = 0;
-    uint32_t blocks_per_cu[2][3][2][2][2] = {};  // [RIS][GLOSSY][COUNT][BRUTE][TAIL]
+    uint32_t blocks_per_cu[2][4][2][2][2] = {};  // [RIS][GLOSSY][COUNT][BRUTE][TAIL]
     size_t occupancy_lds = 0;
 };
 
@@ -362,7 +362,7 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, ui
     const uint32_t top_records = std::min(h->tune.top_records, args_in.scene.n_top_records);
     const size_t lds = trace_lds_bytes(top_records);
     if (h->occupancy_lds != lds) {
-        LAUNCH_TRY(QueryOccupancy(&kPtKernels[0][0][0][0][0], &h->blocks_per_cu[0][0][0][0][0], 48, kTraceBlock, lds));
+        LAUNCH_TRY(QueryOccupancy(&kPtKernels[0][0][0][0][0], &h->blocks_per_cu[0][0][0][0][0], 64, kTraceBlock, lds));
         h->occupancy_lds = lds;
     }
     const bool tail = args_in.n_samples <= h->tune.tail_samples;              // a small call: mostly drain
@@ -374,8 +374,8 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, ui
     const uint32_t blocks_wanted = (uint32_t)std::min<uint64_t>(h->n_cus * blocks_per_cu, std::max<uint64_t>(1, paths_in_call / (16u * (kTraceBlock / 64u))));
     const dim3 grid(blocks_wanted), block(256), trace_block(kTraceBlock);
     uint32_t max_blocks = 1;
-    // every instantiation (the loop used to stop after lobe level 1; level 2 and RIS never have the higher occupancy, so the sizes below are what they were)
-    for (int i = 0; i < 48; ++i) max_blocks = std::max(max_blocks, (&h->blocks_per_cu[0][0][0][0][0])[i]);
+    // every instantiation (the loop used to stop after lobe level 1; levels 2 and 3 and RIS never have the higher occupancy, so the sizes below are what they were)
+    for (int i = 0; i < 64; ++i) max_blocks = std::max(max_blocks, (&h->blocks_per_cu[0][0][0][0][0])[i]);
     const uint32_t max_threads = h->n_cus * max_blocks * kTraceBlock;
 
     const uint32_t tiles_x = (args_in.width + 7u) / 8u;

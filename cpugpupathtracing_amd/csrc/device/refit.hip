@@ -8,7 +8,7 @@
 // bit (signed zeros, NaN, values beyond 1e30 included): the left range comes first and a tie keeps the first operand.  So:
 //   * triangle pass (refit_triangles): one thread per leaf slot of the object.  Its tri_leaf record names the triangle (tri_idx),
 //     which the thread gathers from the staging copy of the host triangles; it rewrites v0 / e1 / e2 (scene_layout.h: PackLeafTri's subtraction),
-//     keeps tri_idx, last_in_leaf and the pad word, and writes the original-order record (tri_orig) and tri_normal;
+//     keeps tri_idx, last_in_leaf and the pad word, and writes the original-order record (tri_orig) and tri_normal (n0 and the {n1, n2} pair);
 //   * bound pass (refit_level): the object's child-pair records grouped by depth at upload (scene_layout.hip: LayoutScene), one launch per level,
 //     deepest first, a thread per record.  A leaf side folds its triangles' positions from tri_orig (v0 + e1 is not v1 in floating
 //     point); an inner side is the union of the child record's two sides, written by the previous launch (stream order is the only
@@ -40,7 +40,7 @@ constexpr uint32_t kRefitThreads = 256;
 
 __global__ __launch_bounds__(kRefitThreads) void refit_triangles(const float* __restrict__ staging, float4* __restrict__ tri_leaf,
                                                                  float4* __restrict__ tri_orig, float4* __restrict__ tri_normal,
-                                                                 uint32_t leaf_base, uint32_t tri_base, uint32_t n)
+                                                                 uint32_t leaf_base, uint32_t tri_base, uint32_t n, uint32_t n_tris_total)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -50,8 +50,8 @@ __global__ __launch_bounds__(kRefitThreads) void refit_triangles(const float* __
     if (t >= n) return;                                                       // validated at upload
     const float* tr = staging + 18 * (size_t)t;                               // cgpt_triangle: v0 {pos, normal}, v1, v2 (72 B, 8-byte aligned)
     const float p0x = tr[0], p0y = tr[1], p0z = tr[2], n0x = tr[3], n0y = tr[4], n0z = tr[5];
-    const float p1x = tr[6], p1y = tr[7], p1z = tr[8];
-    const float p2x = tr[12], p2y = tr[13], p2z = tr[14];
+    const float p1x = tr[6], p1y = tr[7], p1z = tr[8], n1x = tr[9], n1y = tr[10], n1z = tr[11];
+    const float p2x = tr[12], p2y = tr[13], p2z = tr[14], n2x = tr[15], n2y = tr[16], n2z = tr[17];
     const float e1x = p1x - p0x, e1y = p1y - p0y, e1z = p1z - p0z;            // ref: Primitives.cpp:9 (PackLeafTri)
     const float e2x = p2x - p0x, e2y = p2y - p0y, e2z = p2z - p0z;            // ref: Primitives.cpp:10
     leaf[0] = make_float4(p0x, p0y, p0z, e1x);
@@ -62,6 +62,9 @@ __global__ __launch_bounds__(kRefitThreads) void refit_triangles(const float* __
     orig[1] = make_float4(p1x, p1y, p1z, n0y);
     orig[2] = make_float4(p2x, p2y, p2z, n0z);
     tri_normal[tri_base + t] = make_float4(n0x, n0y, n0z, 0.0f);              // TriangleNormal, ref: Primitives.cpp:148-151
+    float4* pair = tri_normal + n_tris_total + 2 * (size_t)(tri_base + t);    // PackNormalPair (device_scene.h: tri_normal)
+    pair[0] = make_float4(n1x, n1y, n1z, 0.0f);
+    pair[1] = make_float4(n2x, n2y, n2z, 0.0f);
 }
 
 struct Box { float lo[3], hi[3]; };
@@ -160,7 +163,7 @@ int RefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles,
     // from here on the scene changes
     const uint32_t tri_base = d.tri_base;
     hipLaunchKernelGGL(refit_triangles, dim3((n_tris + kRefitThreads - 1) / kRefitThreads), dim3(kRefitThreads), 0, ctx->stream,
-                       reinterpret_cast<const float*>(ctx->sb.refit_staging.p), ctx->sb.tri_leaf.p, ctx->sb.tri_orig.p, ctx->sb.tri_normal.p, ro.leaf_base, tri_base, n_tris);
+                       reinterpret_cast<const float*>(ctx->sb.refit_staging.p), ctx->sb.tri_leaf.p, ctx->sb.tri_orig.p, ctx->sb.tri_normal.p, ro.leaf_base, tri_base, n_tris, ctx->scene.n_tris_total);
     REFIT_HIP_WRITING(ctx, hipGetLastError());
     for (size_t level = ro.level_offsets.empty() ? 0 : ro.level_offsets.size() - 1; level-- > 0;) {
         const uint32_t first = ro.level_offsets[level], n = ro.level_offsets[level + 1] - first;

@@ -24,6 +24,7 @@ struct RefitObject {
 struct SceneLayout {
     // the arrays of device_scene.h, and each mesh's child-pair records grouped by depth (refit.hip's bound pass)
     std::vector<float4> node_pairs, tri_leaf, tri_orig, tri_normal, materials;
+    std::vector<float4> tri_normal12;          // {n1.xyz, -}, {n2.xyz, -} per triangle, original order: installed behind tri_normal's n0 records
     std::vector<DevObject> objects;
     std::vector<float4> obj_trace;
     std::vector<uint32_t> lights;
@@ -64,6 +65,13 @@ inline void PackOrigTri(const cgpt_triangle& tr, float4 rec[3])
     rec[0] = make_float4(tr.v0.pos[0], tr.v0.pos[1], tr.v0.pos[2], tr.v0.normal[0]);
     rec[1] = make_float4(tr.v1.pos[0], tr.v1.pos[1], tr.v1.pos[2], tr.v0.normal[1]);
     rec[2] = make_float4(tr.v2.pos[0], tr.v2.pos[1], tr.v2.pos[2], tr.v0.normal[2]);
+}
+
+// the other two vertex normals of a triangle (device_scene.h: tri_normal, the pairs behind the n0 records)
+inline void PackNormalPair(const cgpt_triangle& tr, float4 rec[2])
+{
+    rec[0] = make_float4(tr.v1.normal[0], tr.v1.normal[1], tr.v1.normal[2], 0.0f);
+    rec[1] = make_float4(tr.v2.normal[0], tr.v2.normal[1], tr.v2.normal[2], 0.0f);
 }
 
 // obj_trace entry of an object (device_scene.h): what IntersectScene's object loop reads; upload and cgpt_scene_update_primitive

@@ -101,6 +101,9 @@ int LayoutMesh(const cgpt_scene_desc& sd, uint32_t oi, uint32_t leaf_base, Scene
         const cgpt_triangle& tr = tris[t];
         PackOrigTri(tr, orig + 3 * (size_t)t);
         out.tri_normal.push_back(make_float4(tr.v0.normal[0], tr.v0.normal[1], tr.v0.normal[2], 0.0f));   // TriangleNormal, ref: Primitives.cpp:148-151
+        float4 pair[2];
+        PackNormalPair(tr, pair);
+        out.tri_normal12.push_back(pair[0]); out.tri_normal12.push_back(pair[1]);
     }
 
     // child-pair records + leaf terminators; iterative DFS from the root also measures the real depth
@@ -223,6 +226,7 @@ int LayoutScene(const cgpt_scene_desc& sd, SceneLayout& out, std::string& error)
     const std::vector<uint32_t> leaf_base_of = LeafRecordOrder(sd, out.n_small_tris, n_leaf_records);
     if (n_leaf_records >= (1u << 26)) return Refuse(error, CGPT_ERR_INVALID, "scene too large: more than 2^26 triangles or inner nodes");
     out.tri_leaf.resize(3 * (size_t)n_leaf_records);
+    out.tri_normal12.reserve(2 * (size_t)n_leaf_records);                      // one {n1, n2} pair per leaf record: no regrowth while the objects are laid out
 
     out.objects.resize(sd.n_objects);
     out.refit_objects.resize(sd.n_objects);
@@ -257,6 +261,9 @@ int LayoutScene(const cgpt_scene_desc& sd, SceneLayout& out, std::string& error)
             out.tri_orig.resize(out.tri_orig.size() + 3);
             PackOrigTri(tr, out.tri_orig.data() + 3 * (size_t)orig_base);
             out.tri_normal.push_back(make_float4(tr.v0.normal[0], tr.v0.normal[1], tr.v0.normal[2], 0.0f));   // TriangleNormal, ref: Primitives.cpp:148-151
+            float4 pair[2];
+            PackNormalPair(tr, pair);
+            out.tri_normal12.push_back(pair[0]); out.tri_normal12.push_back(pair[1]);
             d.root_code = kLeafBit | leaf_base; d.tri_base = orig_base; d.n_tris = 1;
             out.refit_objects[oi].tri_count = 1; out.refit_objects[oi].leaf_base = leaf_base;
         } else if (o.kind == CGPT_OBJECT_MESH) {
@@ -327,6 +334,7 @@ extern "C" int cgpth_scene_layout(const cgpt_scene_desc* scene, cgpth_scene_layo
         view->stack_depth = l.stack_depth; view->n_top_records = l.n_top_records; view->n_pair_records = l.n_pair_records; view->n_small_tris = l.n_small_tris;
         view->leaf_base = st.leaf_base.data(); view->pair_base = st.pair_base.data(); view->level_begin = st.level_begin.data();
         view->level_offsets = st.level_offsets.data(); view->level_offsets_start = st.level_offsets_start.data();
+        view->tri_normal12 = f4(l.tri_normal12); view->n_tri_normal12 = l.tri_normal12.size();
         return CGPT_OK;
     } catch (const std::exception& e) {
         HostSetError(e.what());

@@ -14,17 +14,58 @@ namespace dev {
 
 struct Hit { V3 pos, normal; uint32_t mat; };
 
+// The interpolated shading normal of a hit at P on triangle (p0, p1, p2) with vertex normals (n0, n1, n2), ray direction d (DESIGN.md 5.14;
+// tests/smooth_ref.py states the same operations in numpy and is the specification).  float32, no contraction, in this order:
+//  1. n0, n1, n2 bitwise equal -> n0, nothing else computed (decided by the caller, before the position records are read);
+//  2. e1 = p1 - p0, e2 = p2 - p0, w = P - p0, g = cross(e1, e2), gg = dot(g, g);
+//  3. u = dot(cross(w, e2), g) / gg, v = dot(cross(e1, w), g) / gg: the projection of P onto the triangle's plane, independent of d;
+//  4. m = (1 - u - v) n0 + u n1 + v n2, l2 = dot(m, m); !(l2 > 1e-12) (NaN, a degenerate triangle, cancelling normals) -> n0; else ns = m / sqrt(l2);
+//  5. the side stays the geometry's: g is flipped so that dot(g, ns) >= 0; if d sees ns and g from different sides (dot(d, ns) dot(d, g) < 0)
+//     or grazes ns (dot(d, ns) == 0), the normal is normalize(g) -- the integrator decides inside / outside and the reflection side from
+//     dot(d, normal), and that sign must be the real surface's.
+__device__ __forceinline__ V3 smooth_normal(V3 p0, V3 p1, V3 p2, V3 n0, V3 n1, V3 n2, V3 P, V3 d)
+{
+    const V3 e1 = p1 - p0, e2 = p2 - p0, w = P - p0;
+    V3 g = cross(e1, e2);
+    const float gg = dot(g, g);
+    const float u = dot(cross(w, e2), g) / gg;
+    const float v = dot(cross(e1, w), g) / gg;
+    const V3 m = (1.0f - u - v) * n0 + u * n1 + v * n2;
+    const float l2 = dot(m, m);
+    if (!(l2 > 1e-12f)) return n0;
+    const float len = sqrtf(l2);
+    V3 ns = mk(m.x / len, m.y / len, m.z / len);
+    if (dot(g, ns) < 0.0f) g = -g;
+    const float dn = dot(d, ns);
+    if (dn * dot(d, g) < 0.0f || dn == 0.0f) ns = normalize(g);
+    return ns;
+}
+
 // GetRayHitResult (ref: Main.cpp:325-338): flat shading normal = v0.normal of the hit triangle (SURVEY A-8).  A triangle object's
 // normal is its own record's (TriangleNormal, ref: Primitives.cpp:308-321): ray.tri may be left over from an earlier mesh's hit.
-template <bool COUNT>
+// SMOOTH: the scene has an object with DevObject.smooth set (cgpt_scene_update_smooth_normals); a hit on such a mesh or triangle object
+// gets smooth_normal() above.  The instantiations without it read neither the flag nor the {n1, n2} records: the code they had.
+template <bool COUNT, bool SMOOTH = false>
 __device__ __forceinline__ Hit get_hit(const DevScene& sc, const Ray& ray, Counters& cnt)
 {
     Hit h;
     h.pos = ray.o + ray.d * ray.t;
     const DevObject& obj = sc.objects[ray.obj];
     if (obj.kind == 0u || obj.kind == CGPT_OBJECT_TRIANGLE) {
-        const float4 n = sc.tri_normal[obj.tri_base + (obj.kind == 0u ? ray.tri : 0u)];
+        const uint32_t t = obj.tri_base + (obj.kind == 0u ? ray.tri : 0u);
+        const float4 n = sc.tri_normal[t];
         h.normal = mk(n.x, n.y, n.z);
+        if (SMOOTH && obj.smooth != 0u) {
+            const float4* pair = sc.tri_normal + sc.n_tris_total + 2u * (size_t)t;
+            const float4 a = pair[0], b = pair[1];
+            const bool same = __float_as_uint(a.x) == __float_as_uint(n.x) && __float_as_uint(a.y) == __float_as_uint(n.y) && __float_as_uint(a.z) == __float_as_uint(n.z) &&
+                              __float_as_uint(b.x) == __float_as_uint(n.x) && __float_as_uint(b.y) == __float_as_uint(n.y) && __float_as_uint(b.z) == __float_as_uint(n.z);
+            if (!same) {
+                const float4* rec = sc.tri_orig + 3u * (size_t)t;
+                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
+                h.normal = smooth_normal(mk(r0.x, r0.y, r0.z), mk(r1.x, r1.y, r1.z), mk(r2.x, r2.y, r2.z), h.normal, mk(a.x, a.y, a.z), mk(b.x, b.y, b.z), h.pos, ray.d);
+            }
+        }
         if (COUNT) cnt.hits += obj.kind == 0u ? 1u : 0u;                      // mesh hits only (ref: Main.cpp:332)
     } else if (obj.kind == 1u) {
         h.normal = normalize(h.pos - mk(obj.sphere_center));                 // ref: Primitives.cpp:153-156
@@ -177,7 +218,8 @@ enum : uint32_t { kBounceChainShift = 4u, kChainReflect = 1u, kChainRefract = 2u
 // if kBounceShadow is set, `shadow` / `pending` describe the NEE connection to trace (energy += pending when unoccluded,
 // ref: Main.cpp:452-463).  Emissive energy is added here; the final debug-view overrides are applied by the caller.
 // GLOSSY: 0 no rough lobe (the mirror-only code); 1 the scene has a material with roughness > 0 (ggx_sample); 2 it has one with a
-// transmission roughness > 0 (rough_glass_sample; this instantiation carries the rough specular lobe too).
+// transmission roughness > 0 (rough_glass_sample; this instantiation carries the rough specular lobe too); 3 it has an object with smooth
+// normals (get_hit's SMOOTH; carries both rough lobes, so the tables grow by one level and not by a factor of two -- DESIGN.md 5.14).
 // RIS: the NEE light sample is the survivor of M = st.nee > 1 candidates (resampled importance sampling); the
 // instantiations without it keep the one-sample code.
 template <bool COUNT, int GLOSSY = 0, bool RIS = false>
@@ -190,7 +232,7 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
     }
     if (ray.obj == kNoHit) return kBounceTerminate;                           // ref: Main.cpp:415-416
 
-    const Hit hit = get_hit<COUNT>(sc, ray, cnt);
+    const Hit hit = get_hit<COUNT, (GLOSSY >= 3)>(sc, ray, cnt);
     const Mat mat = load_material(sc, hit.mat);
     if (mat.is_light) {                                                       // ref: Main.cpp:424-431
         if (!st.nee || ps.depth == 0 || ps.is_specular) {
@@ -364,7 +406,7 @@ __device__ __forceinline__ uint32_t brute_bounce(const DevScene& sc, const DevSe
         return kBruteLeaf;
     }
     if (ray.obj == kNoHit) { leaf = mk(0.0f); return kBruteLeaf; }            // ref: Main.cpp:600-601
-    const Hit hit = get_hit<COUNT>(sc, ray, cnt);
+    const Hit hit = get_hit<COUNT, (GLOSSY >= 3)>(sc, ray, cnt);
     const Mat mat = load_material(sc, hit.mat);
     if (mat.is_light) { leaf = mat.emissive * mat.intensity; return kBruteLeaf; }   // ref: Main.cpp:606-609
 

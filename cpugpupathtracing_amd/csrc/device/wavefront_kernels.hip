@@ -309,7 +309,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
 
 // ---- K3 shade: one bounce per extend hit; survivors compacted into this wave's output segment ---------------------------
 // BRUTE: the render has TracePath paths (RENDER_MODE_BRUTE_FORCE / COMPARISON); a separate instantiation, so the TracePathAdvanced
-// renders carry neither its code nor its registers.  GLOSSY (the lobe level): 0 no rough lobe; 1 the scene has a rough specular material (shade_device.hpp: ggx_sample); 2 it has a rough dielectric (rough_glass_sample; carries the rough specular lobe too).
+// renders carry neither its code nor its registers.  GLOSSY (the lobe level): 0 no rough lobe; 1 the scene has a rough specular material (shade_device.hpp: ggx_sample); 2 it has a rough dielectric (rough_glass_sample; carries the rough specular lobe too); 3 it has an object with smooth normals (get_hit's SMOOTH, cgpt_scene_update_smooth_normals; carries both rough lobes too).
 // A rough bounce reports lobe choice 0, so its ray is never elected or followed as a specular chain.
 // RIS: the render resamples its NEE light sample (cgpt_set_nee_candidates > 1, shade_device.hpp); one shadow ray and one pending contribution per bounce either way.
 template <bool COUNT, bool FIRST, bool BRUTE = false, int GLOSSY = 0, bool RIS = false>
@@ -736,9 +736,9 @@ static decltype(&wf_trace<false, false>) const kTraceKernels[2][2] = {
 #define CGPT_SHADE_LEVEL(G, R) \
     { { { wf_shade<false, false, false, G, R>, wf_shade<false, false, true, G, R> }, { wf_shade<false, true, false, G, R>, wf_shade<false, true, true, G, R> } }, \
       { { wf_shade<true, false, false, G, R>, wf_shade<true, false, true, G, R> }, { wf_shade<true, true, false, G, R>, wf_shade<true, true, true, G, R> } } }
-static decltype(&wf_shade<false, false>) const kShadeKernels[2][3][2][2][2] = {
-    { CGPT_SHADE_LEVEL(0, false), CGPT_SHADE_LEVEL(1, false), CGPT_SHADE_LEVEL(2, false) },
-    { CGPT_SHADE_LEVEL(0, true), CGPT_SHADE_LEVEL(1, true), CGPT_SHADE_LEVEL(2, true) },
+static decltype(&wf_shade<false, false>) const kShadeKernels[2][4][2][2][2] = {
+    { CGPT_SHADE_LEVEL(0, false), CGPT_SHADE_LEVEL(1, false), CGPT_SHADE_LEVEL(2, false), CGPT_SHADE_LEVEL(3, false) },
+    { CGPT_SHADE_LEVEL(0, true), CGPT_SHADE_LEVEL(1, true), CGPT_SHADE_LEVEL(2, true), CGPT_SHADE_LEVEL(3, true) },
 };
 #undef CGPT_SHADE_LEVEL
 
@@ -791,7 +791,7 @@ struct WfHost {
     uint32_t held_pools = 0;
     uint32_t spec_epoch[kMaxPools] = {};         // last epoch used in each pool's spec_tab
     uint32_t n_cus = 0;
-    uint32_t trace_blocks_per_cu[2][2] = {}, shade_blocks_per_cu[2][3][2][2] = {};   // trace: [COUNT][FIRST]; shade: [RIS][GLOSSY][COUNT][BRUTE]
+    uint32_t trace_blocks_per_cu[2][2] = {}, shade_blocks_per_cu[2][4][2][2] = {};   // trace: [COUNT][FIRST]; shade: [RIS][GLOSSY][COUNT][BRUTE]
     size_t occupancy_lds = 0;
     // hipEvent pairs around every trace launch of the last render (roofline accounting: the dominant kernel's own duration)
     EventPairs trace_ev;
@@ -906,10 +906,10 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, uin
     if (h->occupancy_lds != trace_lds) {
         LAUNCH_TRY(QueryOccupancy(&kTraceKernels[0][0], &h->trace_blocks_per_cu[0][0], 4, kTraceBlock, trace_lds));
         // shade: the round-0 and later-round instantiations share one grid size (one output segment per wave)
-        uint32_t shade[2][3][2][2][2];
-        LAUNCH_TRY(QueryOccupancy(&kShadeKernels[0][0][0][0][0], &shade[0][0][0][0][0], 48, 256, 0));
+        uint32_t shade[2][4][2][2][2];
+        LAUNCH_TRY(QueryOccupancy(&kShadeKernels[0][0][0][0][0], &shade[0][0][0][0][0], 64, 256, 0));
         for (int r = 0; r < 2; ++r)
-            for (int g = 0; g < 3; ++g)
+            for (int g = 0; g < 4; ++g)
                 for (int c = 0; c < 2; ++c)
                     for (int b = 0; b < 2; ++b) h->shade_blocks_per_cu[r][g][c][b] = std::min(shade[r][g][c][0][b], shade[r][g][c][1][b]);
         h->occupancy_lds = trace_lds;

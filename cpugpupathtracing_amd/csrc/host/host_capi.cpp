@@ -297,7 +297,33 @@ int cgpth_scene_add_light(cgpth_scene* scene, uint32_t obj_index)
         const Object& o = scene->scene.objects[obj_index];
         // ref: Main.cpp:371-384: only meshes and sphere primitives can be sampled, anything else EXCEPTs
         if (!o.has_bvh && o.kind != CGPT_OBJECT_SPHERE) { g_error = "only meshes and spheres can be light sources"; return CGPT_ERR_UNSUPPORTED; }
+        if (o.smooth) return Fail("object " + std::to_string(obj_index) + " has smooth normals: a light's sampled normal is v0.normal");
         scene->scene.light_source_indices.push_back(obj_index);
+        return CGPT_OK;
+    });
+}
+
+int cgpth_scene_set_smooth_normals(cgpth_scene* scene, uint32_t obj_index, uint32_t flag)
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        if (!scene) return Fail("scene is null");
+        if (obj_index >= scene->scene.objects.size())
+            return Fail("object " + std::to_string(obj_index) + " out of range (" + std::to_string(scene->scene.objects.size()) + " objects)");
+        if (flag > 1u) return Fail("smooth-normal flag " + std::to_string(flag) + " is neither 0 nor 1");
+        if (flag)
+            for (const uint32_t li : scene->scene.light_source_indices)
+                if (li == obj_index) return Fail("object " + std::to_string(obj_index) + " is a light: its sampled normal is v0.normal, so it cannot shade with smooth normals");
+        scene->scene.objects[obj_index].smooth = flag != 0u;
+        return CGPT_OK;
+    });
+}
+
+int cgpth_scene_get_smooth_normals(const cgpth_scene* scene, uint32_t* out, uint32_t n)
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        if (!scene || !out) return Fail("null argument");
+        if (n != scene->scene.objects.size()) return Fail("expected " + std::to_string(scene->scene.objects.size()) + " values, got " + std::to_string(n));
+        for (uint32_t i = 0; i < n; ++i) out[i] = scene->scene.objects[i].smooth ? 1u : 0u;
         return CGPT_OK;
     });
 }

@@ -82,6 +82,7 @@ struct Object {  // ref: Main.cpp:245-275
     Sphere sphere;
     Plane plane;
     cgpt_triangle triangle{};
+    bool smooth = false;      // interpolated vertex normals (cgpt_scene_update_smooth_normals); not part of cgpt_object
 };
 
 struct Settings {  // ref: Main.cpp:228-235

@@ -43,6 +43,7 @@ class Renderer:
         self._glossy = False          # the device holds a roughness > 0 (cgpt_scene_update_roughness)
         self._rough_glass = False     # the device holds a transmission roughness > 0 (cgpt_scene_update_transmission_roughness)
         self._nee_candidates = 1      # cgpt_set_nee_candidates
+        self._smooth = False          # the device holds a smooth-normal flag (cgpt_scene_update_smooth_normals)
 
     def _check(self, rc: int):
         if rc != 0:
@@ -63,11 +64,11 @@ class Renderer:
         return self._nee_candidates
 
     def upload(self, scene: Scene):
-        """cgpt_scene_upload, then the scene's roughness (cgpt_scene_update_roughness) and transmission roughness
-        (cgpt_scene_update_transmission_roughness) when any is nonzero."""
+        """cgpt_scene_upload, then the scene's roughness (cgpt_scene_update_roughness), transmission roughness
+        (cgpt_scene_update_transmission_roughness) and smooth-normal flags (cgpt_scene_update_smooth_normals) when any is nonzero."""
         desc = scene.flatten()
         self._check(self.L.cgpt_scene_upload(self._ctx, C.byref(desc)))
-        self._glossy = self._rough_glass = False                     # the upload reset every roughness to 0
+        self._glossy = self._rough_glass = self._smooth = False      # the upload reset every roughness and smooth-normal flag to 0
         self.scene = scene
         self._node_counts = [desc.objects[k].node_count for k in range(desc.n_objects)]   # the uploaded trees (export_bvh)
         rough = scene.roughness(desc.n_materials)
@@ -76,6 +77,9 @@ class Renderer:
         rough_t = scene.transmission_roughness(desc.n_materials)
         if rough_t.any():
             self.update_transmission_roughness(rough_t)
+        smooth = scene.smooth_normals(desc.n_objects)
+        if smooth.any():
+            self.update_smooth_normals(smooth)
 
     def update_materials(self, scene: Scene):
         """cgpt_scene_update_materials, then each of the scene's two roughnesses when it or the device's is nonzero."""
@@ -101,6 +105,13 @@ class Renderer:
         v = np.ascontiguousarray(values, np.float32).ravel()
         self._check(self.L.cgpt_scene_update_transmission_roughness(self._ctx, v.ctypes.data_as(C.POINTER(C.c_float)), v.size))
         self._rough_glass = bool((v > 0.0).any())
+
+    def update_smooth_normals(self, flags):
+        """cgpt_scene_update_smooth_normals: one flag per uploaded object (0: the reference's flat v0.normal, 1: interpolated vertex
+        normals on a mesh or triangle object).  Only the device copy changes; call reset_accumulator() before the next frame."""
+        v = np.ascontiguousarray(flags, np.uint32).ravel()
+        self._check(self.L.cgpt_scene_update_smooth_normals(self._ctx, v.ctypes.data_as(C.POINTER(C.c_uint32)), v.size))
+        self._smooth = bool(v.any())
 
     def refit_mesh(self, obj_index: int, triangles) -> float:
         """BVH refit on the device (cgpt_scene_refit_mesh): new triangles for uploaded mesh `obj_index` (or triangle object), in its

@@ -249,15 +249,30 @@ class Scene:
         _host_check(N.lib().cgpth_scene_get_transmission_roughness(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), n), "get_transmission_roughness")
         return out
 
-    def add_mesh(self, mesh: Mesh, mat_index: int, build_option: int = N.BUILD_SAH_INTERVALS, device_builder=None) -> int:
+    def set_smooth_normals(self, obj_index: int, smooth: bool):
+        """Smooth shading of object `obj_index` (cgpth_scene_set_smooth_normals): True interpolates the hit triangle's three vertex
+        normals, False is the reference's flat v0.normal.  Spheres and planes ignore it; a light refuses True."""
+        _host_check(N.lib().cgpth_scene_set_smooth_normals(self._h, obj_index, 1 if smooth else 0), "set_smooth_normals")
+
+    def smooth_normals(self, n_objects=None) -> np.ndarray:
+        """Every object's smooth-normal flag, uint32 (cgpth_scene_get_smooth_normals).  n_objects: the scene's count when the caller has it."""
+        n = self.flatten().n_objects if n_objects is None else n_objects
+        out = np.zeros(n, np.uint32)
+        _host_check(N.lib().cgpth_scene_get_smooth_normals(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), n), "get_smooth_normals")
+        return out
+
+    def add_mesh(self, mesh: Mesh, mat_index: int, build_option: int = N.BUILD_SAH_INTERVALS, device_builder=None, smooth: bool = False) -> int:
         """Object ctor (ref: Main.cpp:247-251).  device_builder: a Renderer whose GPU builds the (bit-identical) tree, any option.
-        build_option: BUILD_NAIVE, BUILD_SAH_INTERVALS (the reference's default), BUILD_SAH_PRIMITIVES or BUILD_SAH_BINNED."""
+        build_option: BUILD_NAIVE, BUILD_SAH_INTERVALS (the reference's default), BUILD_SAH_PRIMITIVES or BUILD_SAH_BINNED.
+        smooth: shade with interpolated vertex normals (set_smooth_normals)."""
         if device_builder is not None:
             rc = N.lib().cgpth_scene_add_mesh_device_built_ex(self._h, mesh._h, mat_index, device_builder._ctx, build_option)
         else:
             rc = N.lib().cgpth_scene_add_mesh(self._h, mesh._h, mat_index, build_option)
         if rc < 0:
             raise HostError(N.lib().cgpth_last_error().decode())
+        if smooth:
+            self.set_smooth_normals(rc, True)
         return rc
 
     def add_sphere(self, center, radius: float, mat_index: int) -> int:
@@ -266,10 +281,10 @@ class Scene:
     def add_plane(self, normal, point, mat_index: int) -> int:
         return N.lib().cgpth_scene_add_plane(self._h, _f3(normal), _f3(point), mat_index)
 
-    def add_triangle(self, positions, normals, mat_index: int) -> int:
+    def add_triangle(self, positions, normals, mat_index: int, smooth: bool = False) -> int:
         """Primitive(const Triangle&) (ref: Include/Primitives.h:84-89): a stand-alone triangle object without a BVH.
         positions: 3x3 (v0, v1, v2); normals: 3x3 per vertex, or one normal for all three.  The shading normal is v0's
-        (ref: Primitives.cpp:148-151).  Returns the object index."""
+        (ref: Primitives.cpp:148-151), or with smooth=True the three interpolated (set_smooth_normals).  Returns the object index."""
         p = np.asarray(positions, dtype=np.float32).reshape(3, 3)
         n = np.asarray(normals, dtype=np.float32)
         n = np.broadcast_to(n.reshape(3), (3, 3)) if n.size == 3 else n.reshape(3, 3)
@@ -279,6 +294,8 @@ class Scene:
         rc = N.lib().cgpth_scene_add_triangle(self._h, C.byref(tri), mat_index)
         if rc < 0:
             raise HostError(N.lib().cgpth_last_error().decode())
+        if smooth:
+            self.set_smooth_normals(rc, True)
         return rc
 
     def add_light(self, obj_index: int):

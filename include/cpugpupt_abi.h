@@ -30,7 +30,8 @@ extern "C" {
                                  lobe added one new symbol (cgpt_scene_update_roughness) only; CGPT_BUILD_SAH_BINNED is a new enum
                                  value only; the rough dielectric lobe added one new symbol
                                  (cgpt_scene_update_transmission_roughness) only; resampled light sampling added one new symbol
-                                 only (cgpt_set_nee_candidates) */
+                                 only (cgpt_set_nee_candidates); smooth shading added one new symbol only
+                                 (cgpt_scene_update_smooth_normals) */
 
 enum cgpt_status {
     CGPT_OK = 0,
@@ -225,6 +226,16 @@ int cgpt_scene_update_roughness(cgpt_ctx* ctx, const float* roughness, uint32_t 
  * The denoiser's cached guides stay valid.  A HIP failure during the write drops the scene; a multi-device context updates every
  * device. */
 int cgpt_scene_update_transmission_roughness(cgpt_ctx* ctx, const float* transmission_roughness, uint32_t n_materials);
+/* Smooth shading: one word per uploaded object.  0 is the reference's flat shading normal, v0.normal of the hit triangle (ref:
+ * Primitives.cpp:148-151), bit for bit; 1 shades a mesh or a stand-alone triangle object with the three vertex normals of the hit
+ * triangle interpolated at the hit point and normalised, kept on the geometric side the ray sees (tests/smooth_ref.py
+ * states the operations).  A triangle whose three normals are bitwise equal shades as with 0.  Spheres and planes ignore their entry.
+ * cgpt_scene_upload resets every flag to 0; the material, roughness, refit and primitive edits keep the flags.  Refused, with nothing
+ * changed: no scene (CGPT_ERR_NO_SCENE); smooth NULL, n_objects other than the uploaded count, or a value that is neither 0 nor 1
+ * (CGPT_ERR_INVALID); a 1 on an object listed in light_indices (CGPT_ERR_INVALID: light sampling uses v0.normal, and the two must not
+ * disagree).  The caller resets the accumulator.  The denoiser's cached guides are recomputed: they hold the normal.  A HIP failure
+ * during the write drops the scene; a multi-device context updates every device. */
+int cgpt_scene_update_smooth_normals(cgpt_ctx* ctx, const uint32_t* smooth, uint32_t n_objects);
 
 /* ---- in-place geometry edits of the uploaded scene (no re-upload; the caller resets the accumulator, as with the materials) ----
  * Every call validates before its first device write: a refused call leaves the device scene as it was.  If a HIP call fails after

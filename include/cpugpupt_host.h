@@ -71,7 +71,13 @@ int cgpth_scene_add_plane(cgpth_scene* scene, const float normal[3], const float
 /* a stand-alone triangle object, Primitive(const Triangle&) (ref: Include/Primitives.h:84-89); returns object index.  It has no BVH
  * (bvh_info / bvh_export / rebuild_bvh refuse it) and cannot be a light (the reference EXCEPTs, Main.cpp:383) */
 int cgpth_scene_add_triangle(cgpth_scene* scene, const cgpt_triangle* triangle, uint32_t mat_index);
-int cgpth_scene_add_light(cgpth_scene* scene, uint32_t obj_index);                            /* ref: Main.cpp:817 */
+int cgpth_scene_add_light(cgpth_scene* scene, uint32_t obj_index);                            /* ref: Main.cpp:817; refuses an object with smooth normals */
+/* smooth shading of object `obj_index` (cgpt_scene_update_smooth_normals holds the meaning): flag 0 or 1, a new object has 0.  Refused
+ * with CGPT_ERR_INVALID and nothing changed: a bad index, a flag that is neither 0 nor 1, a 1 on a light.  Spheres and planes keep the
+ * flag and ignore it.  Not part of cgpt_scene_desc: a host uploads the scene, then hands get_smooth_normals's values to the device */
+int cgpth_scene_set_smooth_normals(cgpth_scene* scene, uint32_t obj_index, uint32_t flag);
+/* out: n values, n == the scene's object count */
+int cgpth_scene_get_smooth_normals(const cgpth_scene* scene, uint32_t* out, uint32_t n);
 int cgpth_scene_set_camera(cgpth_scene* scene, const float pos[3], const float view_dir[3], float fov_deg, float aspect);
 int cgpth_scene_set_settings(cgpth_scene* scene, const cgpt_settings* settings);
 int cgpth_scene_rebuild_bvh(cgpth_scene* scene, uint32_t obj_index, int build_option);       /* ref: BVH.cpp:47-59 */
@@ -124,6 +130,9 @@ typedef struct cgpth_scene_layout_view {
      * with o = level_offsets + level_offsets_start[i], which has level_offsets_start[i + 1] - level_offsets_start[i] entries */
     const uint32_t* leaf_base; const uint32_t* pair_base; const uint32_t* level_begin;
     const uint32_t* level_offsets; const uint32_t* level_offsets_start;
+    /* the other two vertex normals, {n1.xyz, -}, {n2.xyz, -} per triangle in tri_orig's order (2 float4s a triangle): the device keeps them
+     * behind tri_normal's n0 records, in the same allocation */
+    const float* tri_normal12; size_t n_tri_normal12;
 } cgpth_scene_layout_view;
 int cgpth_scene_layout(const cgpt_scene_desc* scene, cgpth_scene_layout_view* out);
 
