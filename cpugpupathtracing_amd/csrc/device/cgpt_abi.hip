@@ -15,22 +15,23 @@
 
 #include "cpugpupt_abi.h"
 #include "device_scene.h"
+#include "launch_common.h"
 #include "scene_layout.h"
 
 namespace cgpt {
-hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, uint32_t lobe_level, bool ris, hipStream_t stream);       // path_kernels.hip
+hipError_t LaunchMegakernel(const DevRenderArgs& args, ShadeVariant v, hipStream_t stream);                                  // path_kernels.hip
 hipError_t LaunchIntersectRays(const DevScene& sc, const float* origins, const float* dirs, const float* tmax, uint32_t n, float* out_t,
                                uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, DevCounters* counters, hipStream_t stream);
-int LaunchWavefront(struct ::cgpt_ctx* ctx, const DevRenderArgs& args, bool count, uint32_t lobe_level, bool ris);          // wavefront_kernels.hip
+int LaunchWavefront(struct ::cgpt_ctx* ctx, const DevRenderArgs& args, ShadeVariant v);                                     // wavefront_kernels.hip
 void WavefrontFree(void* state);
 void WavefrontCollectTiming(void* state, double* trace_ms, uint32_t* trace_launches, double* round0_ms, uint32_t* round0_launches);
 int WavefrontSetTuning(struct ::cgpt_ctx* ctx, const char* name, uint32_t value);
 uint32_t WavefrontTraceWavesPerSimd(void* state);
-int LaunchPersistent(struct ::cgpt_ctx* ctx, const DevRenderArgs& args, bool count, uint32_t lobe_level, bool ris);             // persistent_kernel.hip
+int LaunchPersistent(struct ::cgpt_ctx* ctx, const DevRenderArgs& args, ShadeVariant v);                                    // persistent_kernel.hip
 void PersistentFree(void* state);
-void PersistentCollectTiming(void* state, uint32_t lobe_level, bool ris, double* ms, uint32_t* launches, uint32_t* waves_per_simd);
+void PersistentCollectTiming(void* state, ShadeVariant v, double* ms, uint32_t* launches, uint32_t* waves_per_simd);
 int PersistentSetTuning(struct ::cgpt_ctx* ctx, const char* name, uint32_t value, bool* known);
-uint32_t MegakernelWavesPerSimd(const DevRenderArgs& args, uint32_t lobe_level, bool ris);                                      // path_kernels.hip
+uint32_t MegakernelWavesPerSimd(const DevRenderArgs& args, ShadeVariant v);                                                  // path_kernels.hip
 }  // namespace cgpt
 
 using namespace cgpt;
@@ -404,12 +405,12 @@ int RenderEnqueue(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings*
     args.first_sample = p->first_sample; args.n_samples = p->n_samples; args.seed = p->seed;
     args.accumulator = ctx->fb.accumulator.p; args.pixels = ctx->fb.pixels.p; args.counters = ctx->counters.p;
 
-    const bool count = (p->flags & CGPT_RENDER_COUNTERS) != 0;
     // the RIS instantiations run only where a candidate loop can: TracePath (BRUTE_FORCE) has no NEE, and NEE may be off
     const bool ris = ctx->nee_candidates > 1u && args.settings.nee != 0u && settings->render_mode != CGPT_MODE_BRUTE_FORCE;
     // The one place where DevSettings.nee is more than a flag: the RIS instantiations read M from it, every other reader tests it for zero
     // (device_scene.h).  With one candidate the word is the caller's flag, untouched, as the parent passed it.
     if (ris) args.settings.nee = ctx->nee_candidates;
+    const ShadeVariant variant = { (p->flags & CGPT_RENDER_COUNTERS) != 0, ctx->lobe_level, ris };
     // AUTO: all three kernels give bit-identical images, so the choice is speed alone.  MI355X, glass scene, ms per call
     // (profiles/r03/small_calls_table.txt; 16 samples and more: profiles/r02/frame_time_after.txt):
     //                 64x64  1 / 2 / 8 samples     960x540  1 / 2 / 8        1920x1080  1 / 2 / 4 / 8 / 16 / 32 / 64 / 128
@@ -436,21 +437,21 @@ int RenderEnqueue(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings*
 
     if (kernel == CGPT_KERNEL_MEGAKERNEL) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev_start.e, ctx->stream));
-        HIP_TRY(ctx, LaunchMegakernel(args, count, ctx->lobe_level, ris, ctx->stream));
+        HIP_TRY(ctx, LaunchMegakernel(args, variant, ctx->stream));
         ctx->kernel_launches += 1;
     } else if (kernel == CGPT_KERNEL_WAVEFRONT) {
-        rc = LaunchWavefront(ctx, args, count, ctx->lobe_level, ris);
+        rc = LaunchWavefront(ctx, args, variant);
         if (rc < 0) return ctx->error.empty() ? CtxFail(ctx, CGPT_ERR_HIP, "wavefront launch failed") : CGPT_ERR_HIP;
         ctx->kernel_launches += (uint32_t)rc;
     } else if (kernel == CGPT_KERNEL_PERSISTENT) {
-        rc = LaunchPersistent(ctx, args, count, ctx->lobe_level, ris);
+        rc = LaunchPersistent(ctx, args, variant);
         if (rc < 0) return ctx->error.empty() ? CtxFail(ctx, CGPT_ERR_HIP, "persistent kernel launch failed") : CGPT_ERR_HIP;
         ctx->kernel_launches += (uint32_t)rc;
     } else {
         return CtxFail(ctx, CGPT_ERR_INVALID, "unknown kernel %u", p->kernel);
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_stop.e, ctx->stream));
-    ctx->pending_kernel = kernel; ctx->pending_args = args; ctx->pending_num_accumulated = p->first_sample + p->n_samples; ctx->pending_lobe_level = ctx->lobe_level; ctx->pending_ris = ris;
+    ctx->pending_kernel = kernel; ctx->pending_args = args; ctx->pending_num_accumulated = p->first_sample + p->n_samples; ctx->pending_variant = variant;
     ctx->last_debug_mode = settings->debug_render_mode;
     ctx->last_kernel = kernel;
     return CGPT_OK;
@@ -467,10 +468,10 @@ int RenderFinish(cgpt_ctx* ctx)
     float ms = 0.0f;
     HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start.e, ctx->ev_stop.e));
     ctx->kernel_ms += ms;
-    if (kernel == CGPT_KERNEL_MEGAKERNEL) { ctx->dominant_ms += ms; ctx->dominant_launches += 1; ctx->dominant_waves_per_simd = MegakernelWavesPerSimd(args, ctx->pending_lobe_level, ctx->pending_ris); }
+    if (kernel == CGPT_KERNEL_MEGAKERNEL) { ctx->dominant_ms += ms; ctx->dominant_launches += 1; ctx->dominant_waves_per_simd = MegakernelWavesPerSimd(args, ctx->pending_variant); }
     else if (kernel == CGPT_KERNEL_PERSISTENT) {
         double tms = 0.0; uint32_t tl = 0, w = 0;
-        PersistentCollectTiming(ctx->persistent_state, ctx->pending_lobe_level, ctx->pending_ris, &tms, &tl, &w);
+        PersistentCollectTiming(ctx->persistent_state, ctx->pending_variant, &tms, &tl, &w);
         ctx->dominant_ms += tms; ctx->dominant_launches += tl; ctx->dominant_waves_per_simd = w;
     } else {
         ctx->dominant_waves_per_simd = WavefrontTraceWavesPerSimd(ctx->wavefront_state);

@@ -8,6 +8,7 @@
 #include "cpugpupt_abi.h"
 #include "device_memory.h"
 #include "device_scene.h"
+#include "launch_common.h"
 #include "scene_layout.h"
 
 namespace cgpt {
@@ -93,8 +94,7 @@ struct cgpt_ctx {
     // a render that has been enqueued and not yet finished (RenderEnqueue / RenderFinish)
     uint32_t pending_kernel = 0;
     uint32_t pending_num_accumulated = 0;
-    uint32_t pending_lobe_level = 0;
-    bool pending_ris = false;
+    cgpt::ShadeVariant pending_variant{};
     cgpt::DevRenderArgs pending_args{};
     uint32_t last_debug_mode = 0;
     uint32_t last_kernel = 0;                     // cgpt_kernel the last render ran (AUTO resolved)

@@ -1,5 +1,5 @@
 // launch_common.h -- host plumbing shared by the voted launchers, LaunchWavefront (wavefront_kernels.hip) and LaunchPersistent
-// (persistent_kernel.hip).  Host code only.
+// (persistent_kernel.hip), and the ShadeVariant every render launcher takes.  Host code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -14,6 +14,10 @@
 #include "device_memory.h"
 
 namespace cgpt {
+
+// Which instantiation of its render kernels a launcher runs: with the counters of cgpt_stats, the lobe level (ctx_internal.h: GLOSSY) and
+// resampled NEE (shade_device.hpp, above shade_bounce).  The render mode and the call's size pick the rest inside the launcher.
+struct ShadeVariant { bool count; uint32_t lobe_level; bool ris; };
 
 // a HIP call of a launcher: on failure the context's error names the call (as HIP_TRY's does) and the launcher returns -1
 #define LAUNCH_TRY(expr)                                                     \

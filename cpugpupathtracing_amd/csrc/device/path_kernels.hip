@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "device_scene.h"
+#include "launch_common.h"
 #include "rt_device.hpp"
 #include "shade_device.hpp"
 
@@ -27,9 +28,7 @@ extern __shared__ uint32_t lds_stack[];
 // Block shape: 256 threads = a 16x16-pixel tile (the reference's job size, ref: Main.cpp:705-711), or -- one-sample calls -- 64 threads =
 // one 8x8 tile per single-wave block: the wave's slot and its LDS are free the moment its own longest path ends instead of its block's,
 // and the dispatcher places single waves (1080p, one sample: 1.71 -> 1.68 ms, profiles/r03/one_sample.md).
-// GLOSSY (the lobe level): 0 no rough lobe; 1 the scene has a rough specular material (shade_device.hpp: ggx_sample); 2 it has a rough dielectric (rough_glass_sample; carries the rough specular lobe too); 3 it has an object with smooth normals (get_hit's SMOOTH, cgpt_scene_update_smooth_normals; carries both rough lobes too).
-// The scenes without a rough lobe keep the code without it.
-// RIS: the render resamples its NEE light sample (cgpt_set_nee_candidates > 1, shade_device.hpp); the renders with one candidate keep the code without it.
+// GLOSSY (the lobe level) and RIS: shade_device.hpp, above shade_bounce.
 template <bool COUNT, bool BRUTE, int GLOSSY, bool RIS>
 __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
 {
@@ -68,8 +67,7 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
         Ray sray = make_ray(mk(0.0f), mk(0.0f), 0.0f);                       // pending NEE connection
         V3 pending = mk(0.0f);
         const bool use_brute = BRUTE && (st.render_mode == 1u || (st.render_mode == 0u && px < args.width / 2u));
-        BruteLevel levels[BRUTE ? kMaxBruteLevels : 1u];
-        uint32_t n_levels = 0;
+        BruteLevel levels[BRUTE ? kMaxBruteLevels : 1u];                      // the TracePath chain: level k at [k]
 
         for (;;) {
             if (need_new) {
@@ -78,7 +76,6 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
                 ray = camera_ray(args.camera, screen_u, screen_v);            // no jitter: SURVEY A-14
                 ps.throughput = mk(1.0f); ps.energy = mk(0.0f);
                 ps.depth = 0; ps.is_specular = false; need_new = false; shadow_kind = false; dead = false;
-                n_levels = 0;
             }
 
             // ---- one ray per iteration: the extend ray or the pending shadow ray ----
@@ -88,18 +85,8 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
             bool finalize;
             if (BRUTE && use_brute) {
                 ray.t = cur.t; ray.obj = cur.obj; ray.tri = cur.tri; ray.bvh_depth = cur.bvh_depth;
-                BruteLevel lv; V3 leaf = mk(0.0f);
-                finalize = brute_bounce<COUNT, GLOSSY>(sc, st, ray, ps.rng, ps.depth, lv, leaf, cnt) == kBruteLeaf;
-                if (!finalize) {
-                    levels[n_levels++] = lv;
-                    ps.depth++;
-                    if ((int32_t)ps.depth > st.max_ray_depth) finalize = true;   // the child returns black before tracing (ref: Main.cpp:589-590)
-                }
-                if (finalize) {
-                    V3 L = leaf;
-                    for (uint32_t k = n_levels; k-- > 0u;) L = brute_apply(levels[k], L);
-                    ps.energy = L;
-                }
+                finalize = brute_level<COUNT, GLOSSY>(sc, st, ray, ps.rng, ps.depth, [&](uint32_t k, const BruteLevel& lv) { levels[k] = lv; },
+                                                      [&](uint32_t k) { return levels[k]; }, ps.energy, cnt);
             } else if (shadow_kind) {
                 if (cur.obj == kNoHit) ps.energy = ps.energy + pending;       // ref: Main.cpp:454-463
                 shadow_kind = false;
@@ -160,7 +147,7 @@ static uint32_t MegakernelBlockThreads(const DevRenderArgs& args)
 static decltype(&megakernel<false, false, 0, false>) const kMegakernels[2][2][2][4] = { CGPT_MEGAKERNELS(false), CGPT_MEGAKERNELS(true) };
 #undef CGPT_MEGAKERNELS
 
-hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, uint32_t lobe_level, bool ris, hipStream_t stream)
+hipError_t LaunchMegakernel(const DevRenderArgs& args, ShadeVariant v, hipStream_t stream)
 {
     const bool brute = args.settings.render_mode != 2u;
     const uint32_t bt = MegakernelBlockThreads(args);
@@ -168,16 +155,16 @@ hipError_t LaunchMegakernel(const DevRenderArgs& args, bool count, uint32_t lobe
     const uint32_t tiles_x = (args.width + edge - 1u) / edge, tiles_y = (args.n_rows + edge - 1u) / edge;
     const dim3 grid(tiles_x * tiles_y), block(bt);
     const size_t lds = (size_t)args.scene.stack_depth * bt * sizeof(uint32_t);
-    hipLaunchKernelGGL(kMegakernels[ris][count][brute][lobe_level], grid, block, lds, stream, args);
+    hipLaunchKernelGGL(kMegakernels[v.ris][v.count][brute][v.lobe_level], grid, block, lds, stream, args);
     return hipGetLastError();
 }
 
-uint32_t MegakernelWavesPerSimd(const DevRenderArgs& args, uint32_t lobe_level, bool ris)
+uint32_t MegakernelWavesPerSimd(const DevRenderArgs& args, ShadeVariant v)
 {
     int b = 0;
     const uint32_t bt = MegakernelBlockThreads(args);
     const size_t lds = (size_t)args.scene.stack_depth * bt * sizeof(uint32_t);
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kMegakernels[ris][0][args.settings.render_mode != 2u][lobe_level], (int)bt, lds);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kMegakernels[v.ris][0][args.settings.render_mode != 2u][v.lobe_level], (int)bt, lds);
     return e == hipSuccess && b > 0 ? std::max(1u, (uint32_t)b * bt / 256u) : 1u;    // blocks per CU -> waves per SIMD (4 SIMDs)
 }
 

@@ -64,8 +64,7 @@ enum : uint32_t {                      // per-lane path flags
 // Main.cpp:702,825-942), which are mostly drain: once nothing is left to fetch, a wave with few busy lanes runs their rays in the lean
 // per-lane loop (trace_steps.hpp: lean_traverse) instead of voted steps, because the call ends when its longest chain does (1080p, one
 // sample: 2.47 -> 2.21 ms).  Kept out of the throughput instantiations, which it costs registers and SGPR spills (profiles/r03/one_sample.md).
-// GLOSSY (the lobe level): 0 no rough lobe; 1 the scene has a rough specular material (shade_device.hpp: ggx_sample); 2 it has a rough dielectric (rough_glass_sample; carries the rough specular lobe too); 3 it has an object with smooth normals (get_hit's SMOOTH, cgpt_scene_update_smooth_normals; carries both rough lobes too).
-// The scenes without a rough lobe keep the code without it.
+// GLOSSY (the lobe level) and RIS: shade_device.hpp, above shade_bounce.
 template <bool COUNT, bool BRUTE, bool TAIL, int GLOSSY, bool RIS>
 __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderArgs args, const PtDev pt, uint32_t batch_first, const TraceTune tune)
 {
@@ -119,30 +118,19 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
         Ray ray;
         ray.o = trav_origin(r); ray.d = r.d; ray.t = r.t; ray.obj = r.obj; ray.tri = r.tri; ray.bvh_depth = trav_depth(r);
         if (BRUTE && (pf & kPfBrute)) {
-            // TracePath level (ref: Main.cpp:581-689): record this level's operation, go on with the child ray, or fold
-            // the recorded chain over the leaf's radiance, innermost level first
+            // one TracePath level (shade_device.hpp: brute_level), the chain in this thread's column of pt.brute
             uint32_t depth = pf & kPfDepthMask;
-            BruteLevel lv; V3 leaf = mk(0.0f);
-            bool fold = brute_bounce<COUNT, GLOSSY>(sc, st, ray, rng, depth, lv, leaf, cnt) == kBruteLeaf;
-            if (!fold) {
-                float4* rec = pt.brute + ((size_t)depth * grid_threads + tid) * 2u;
-                float4 r0, r1;
-                r0.x = __uint_as_float(lv.kind); r0.y = lv.a.x; r0.z = lv.a.y; r0.w = lv.a.z;
-                r1.x = lv.cosi; r1.y = lv.absorb.x; r1.z = lv.absorb.y; r1.w = lv.absorb.z;
-                rec[0] = r0; rec[1] = r1;
-                depth++;
-                pf = (pf & ~kPfDepthMask) | (depth & kPfDepthMask);
-                if ((int32_t)depth > st.max_ray_depth) fold = true;   // the child returns black before tracing (ref: Main.cpp:589-590)
-            }
-            if (fold) {
-                V3 L = leaf;
-                for (uint32_t k = depth; k-- > 0u;) {
-                    const float4* rec = pt.brute + ((size_t)k * grid_threads + tid) * 2u;
-                    const float4 r0 = rec[0], r1 = rec[1];
-                    BruteLevel b;
-                    b.kind = __float_as_uint(r0.x); b.a = mk(r0.y, r0.z, r0.w); b.cosi = r1.x; b.absorb = mk(r1.y, r1.z, r1.w);
-                    L = brute_apply(b, L);
-                }
+            V3 L;
+            const bool done = brute_level<COUNT, GLOSSY>(sc, st, ray, rng, depth,
+                [&](uint32_t k, const BruteLevel& lv) {
+                    float4* rec = pt.brute + ((size_t)k * grid_threads + tid) * 2u;
+                    float4 r0, r1;
+                    brute_pack(lv, r0, r1);
+                    rec[0] = r0; rec[1] = r1;
+                },
+                [&](uint32_t k) { const float4* rec = pt.brute + ((size_t)k * grid_threads + tid) * 2u; return brute_unpack(rec[0], rec[1]); }, L, cnt);
+            pf = (pf & ~kPfDepthMask) | (depth & kPfDepthMask);
+            if (done) {
                 finish_path(L);
             } else {
                 trav_start(ctx, r, ray.o, ray.d, ray.t, ray.obj, ray.tri, ray.bvh_depth);
@@ -272,6 +260,7 @@ static decltype(&pt_persistent<false, false, false, 0, false>) const kPtKernels[
     { CGPT_PT_LEVEL(0, true), CGPT_PT_LEVEL(1, true), CGPT_PT_LEVEL(2, true), CGPT_PT_LEVEL(3, true) },
 };
 #undef CGPT_PT_LEVEL
+static constexpr size_t kPtKernelCount = sizeof(kPtKernels) / sizeof(kPtKernels[0][0][0][0][0]);
 
 struct PtHost {
     PtTuning tune;
@@ -284,6 +273,7 @@ struct PtHost {
     EventPairs ev;
     uint32_t n_cus = 0;
     uint32_t blocks_per_cu[2][4][2][2][2] = {};  // [RIS][GLOSSY][COUNT][BRUTE][TAIL]
+    static_assert(sizeof(blocks_per_cu) / sizeof(uint32_t) == kPtKernelCount, "one occupancy entry per instantiation");
     size_t occupancy_lds = 0;
 };
 
@@ -342,16 +332,16 @@ void PersistentFree(void* state)
     delete h;                                                                 // and its buffers
 }
 
-void PersistentCollectTiming(void* state, uint32_t lobe_level, bool ris, double* ms, uint32_t* launches, uint32_t* waves_per_simd)
+void PersistentCollectTiming(void* state, ShadeVariant v, double* ms, uint32_t* launches, uint32_t* waves_per_simd)
 {
     *ms = 0.0; *launches = 0; *waves_per_simd = 0;
     if (!state) return;
     PtHost* h = static_cast<PtHost*>(state);
     ForEachPair(h->ev, [&](uint32_t, float t) { *ms += t; *launches += 1; });
-    *waves_per_simd = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[ris][lobe_level][0][0][0]) * (kTraceBlock / 256u);
+    *waves_per_simd = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[v.ris][v.lobe_level][0][0][0]) * (kTraceBlock / 256u);
 }
 
-int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, uint32_t lobe_level, bool ris)
+int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
 {
     hipStream_t stream = CtxStream(ctx);
     PtHost* h = PtGetHost(ctx);
@@ -362,11 +352,11 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, ui
     const uint32_t top_records = std::min(h->tune.top_records, args_in.scene.n_top_records);
     const size_t lds = trace_lds_bytes(top_records);
     if (h->occupancy_lds != lds) {
-        LAUNCH_TRY(QueryOccupancy(&kPtKernels[0][0][0][0][0], &h->blocks_per_cu[0][0][0][0][0], 64, kTraceBlock, lds));
+        LAUNCH_TRY(QueryOccupancy(&kPtKernels[0][0][0][0][0], &h->blocks_per_cu[0][0][0][0][0], kPtKernelCount, kTraceBlock, lds));
         h->occupancy_lds = lds;
     }
     const bool tail = args_in.n_samples <= h->tune.tail_samples;              // a small call: mostly drain
-    const uint32_t blocks_per_cu = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[ris][lobe_level][count][brute][tail]);
+    const uint32_t blocks_per_cu = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[v.ris][v.lobe_level][v.count][brute][tail]);
     // the resident capacity of the chip, or fewer blocks when there are fewer than 64 paths per wave (a small call ends sooner when
     // its paths are spread thin than when the tail of a launch waits for 4 096 waves to find out that there is nothing to do)
     const uint32_t n_tiles = ((args_in.width + 7u) / 8u) * ((args_in.n_rows + 7u) / 8u);
@@ -375,7 +365,7 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, ui
     const dim3 grid(blocks_wanted), block(256), trace_block(kTraceBlock);
     uint32_t max_blocks = 1;
     // every instantiation (the loop used to stop after lobe level 1; levels 2 and 3 and RIS never have the higher occupancy, so the sizes below are what they were)
-    for (int i = 0; i < 64; ++i) max_blocks = std::max(max_blocks, (&h->blocks_per_cu[0][0][0][0][0])[i]);
+    for (size_t i = 0; i < kPtKernelCount; ++i) max_blocks = std::max(max_blocks, (&h->blocks_per_cu[0][0][0][0][0])[i]);
     const uint32_t max_threads = h->n_cus * max_blocks * kTraceBlock;
 
     const uint32_t tiles_x = (args_in.width + 7u) / 8u;
@@ -434,7 +424,7 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, ui
         work_sizes(pt.n_paths, grid.x * (kTraceBlock / 64u), h->tune.fine_rounds, h->tune.chunk, pt.coarse, pt.fine_below);
         // the buffer's previous batch must have been accumulated (same stream: implicit)
         LAUNCH_TRY(hipEventRecord(NextEvent(h->ev), st));
-        hipLaunchKernelGGL(kPtKernels[ris][lobe_level][count][brute][tail], grid, trace_block, lds, st, args_in, pt, bfirst, tt);
+        hipLaunchKernelGGL(kPtKernels[v.ris][v.lobe_level][v.count][brute][tail], grid, trace_block, lds, st, args_in, pt, bfirst, tt);
         LAUNCH_TRY(hipEventRecord(NextEvent(h->ev), st));
         // accumulate in sample order: batch k after batch k-1
         if (n_streams == 2 && k > 0) LAUNCH_TRY(hipStreamWaitEvent(st, h->acc_done[(k - 1u) & 1u], 0));

@@ -114,6 +114,61 @@ __device__ __forceinline__ LightSample sample_light(const DevScene& sc, uint32_t
     return ls;
 }
 
+// The unshadowed contribution of light sample ls to a hit with cosines NdotL, NLdotL (ref: Main.cpp:446-462): the one-sample NEE's
+// `pending`, a RIS candidate's c_j.  The caller decides whether the cosines are tested first.
+__device__ __forceinline__ V3 nee_unshadowed(const DevScene& sc, const Mat& mat, V3 throughput, const LightSample& ls, float NdotL, float NLdotL,
+                                             float diffuse_weight)
+{
+    const V3 brdf_diffuse = mat.albedo * kInvPi;
+    const float solid_angle = (NLdotL * ls.area) / (ls.distance * ls.distance);
+    const float light_pdf = 1.0f / solid_angle;
+    return throughput * (NdotL / light_pdf) * brdf_diffuse * ls.emission * (float)sc.n_lights * diffuse_weight;
+}
+
+// the ray a bounce goes on with: direction dir from the hit, nudged off the surface (ref: Main.cpp:49)
+__device__ __forceinline__ Ray next_ray(const Hit& hit, V3 dir) { return make_ray(hit.pos + dir * kNudge, dir, 1e34f); }
+
+// Beer's law over the distance t travelled inside the medium; applied on the way out only (SURVEY A-4)
+__device__ __forceinline__ V3 beer_absorption(const Mat& mat, float t)
+{
+    V3 ab;
+    ab.x = expf(-mat.absorption.x * t);
+    ab.y = expf(-mat.absorption.y * t);
+    ab.z = expf(-mat.absorption.z * t);
+    return ab;
+}
+
+// BVH-depth debug view of a primary ray (ref: Main.cpp:408-412, 594-597)
+__device__ __forceinline__ V3 bvh_depth_colour(const Ray& ray)
+{
+    return lerp(mk(0.0f, 1.0f, 0.0f), mk(1.0f, 0.0f, 0.0f), (float)ray.bvh_depth / 30.0f);
+}
+
+// The smooth dielectric interface (ref: Main.cpp:488-546 and 621-675): sides and indices from dot(normal, d); k < 0 is total internal
+// reflection (no draw, dir not set); otherwise one float is drawn against fresnel() and dir is the refracted direction when it is greater,
+// else the mirror lobe's.  `inside`: the ray travelled in the medium (Beer's law applies to a refraction out of it).  What each outcome
+// does to the path is the integrator's business.
+enum : uint32_t { kGlassTir = 0u, kGlassRefract = 1u, kGlassReflect = 2u };
+__device__ __forceinline__ uint32_t smooth_glass(const Mat& mat, const Hit& hit, const Ray& ray, uint32_t& rng, V3& dir, bool& inside)
+{
+    V3 N = hit.normal;
+    float cosi = clamp_std(dot(N, ray.d), -1.0f, 1.0f);
+    float etai = 1.0f, etat = mat.ior;
+    inside = true;
+    if (cosi < 0.0f) { cosi = -cosi; inside = false; }
+    else { float tmp = etai; etai = etat; etat = tmp; N = -N; }
+    const float eta = etai / etat;
+    const float k = 1.0f - eta * eta * (1.0f - cosi * cosi);
+    if (!(k >= 0.0f)) return kGlassTir;
+    const V3 rd = refract(ray.d, N, eta, cosi, k);
+    const float angle_in = dot(ray.d, hit.normal);
+    const float angle_out = dot(rd, hit.normal);
+    const float Fr = fresnel(angle_in, angle_out, etai, etat);
+    if (random_float(rng) > Fr) { dir = rd; return kGlassRefract; }
+    dir = reflect(ray.d, hit.normal);
+    return kGlassReflect;
+}
+
 // ---- rough lobes (GLOSSY instantiations) ------------------------------------------------------------------
 // Smith L(w) = (-1 + sqrt(1 + alpha^2 tan^2(theta_w))) / 2 of a direction whose cosine to n is z (a2 = alpha^2).
 __device__ __forceinline__ float ggx_lambda(float a2, float z)
@@ -227,7 +282,7 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
                                                  V3& pending, Counters& cnt)
 {
     if (ps.depth == 0 && st.debug_mode == 2u) {                               // BVH-depth view, ref: Main.cpp:408-412
-        ps.energy = ps.energy + lerp(mk(0.0f, 1.0f, 0.0f), mk(1.0f, 0.0f, 0.0f), (float)ray.bvh_depth / 30.0f);
+        ps.energy = ps.energy + bvh_depth_colour(ray);
         return kBounceTerminate | kBounceEnergy;
     }
     if (ray.obj == kNoHit) return kBounceTerminate;                           // ref: Main.cpp:415-416
@@ -253,7 +308,6 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
         // of j + 1 comes from the RNG state after j, whose draw count depends on objects[].kind (and ball_sample rejects), so a lane pays
         // about M x the dependent chain lights[] -> objects[] -> materials[] (+ three triangle records for a mesh light) per bounce.
         const uint32_t M = st.nee;
-        const V3 brdf_diffuse = mat.albedo * kInvPi;
         float wsum = 0.0f, w_y = 0.0f, dist_y = 0.0f;
         V3 c_y = mk(0.0f), dir_y = mk(0.0f);
         for (uint32_t j = 0; j < M; ++j) {
@@ -261,9 +315,7 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
             const float u = random_float(ps.rng);
             const float NdotL = dot(hit.normal, ls.to_light);
             const float NLdotL = dot(ls.normal, -ls.to_light);
-            const float solid_angle = (NLdotL * ls.area) / (ls.distance * ls.distance);
-            const float light_pdf = 1.0f / solid_angle;
-            const V3 c = ps.throughput * (NdotL / light_pdf) * brdf_diffuse * ls.emission * (float)sc.n_lights * diffuse_weight;
+            const V3 c = nee_unshadowed(sc, mat, ps.throughput, ls, NdotL, NLdotL, diffuse_weight);
             const float w = (NdotL > 0.0f && NLdotL > 0.0f) ? c.x + c.y + c.z : 0.0f;
             wsum += w;
             if (w > 0.0f && (w_y == 0.0f || u * wsum < w)) { c_y = c; w_y = w; dir_y = ls.to_light; dist_y = ls.distance; }   // w_y == 0: empty
@@ -279,10 +331,7 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
         const float NLdotL = dot(ls.normal, -ls.to_light);
         if (NdotL > 0.0f && NLdotL > 0.0f) {
             shadow = make_ray(hit.pos + ls.to_light * kNudge, ls.to_light, ls.distance - 2.0f * kNudge);
-            const V3 brdf_diffuse = mat.albedo * kInvPi;
-            const float solid_angle = (NLdotL * ls.area) / (ls.distance * ls.distance);
-            const float light_pdf = 1.0f / solid_angle;
-            pending = ps.throughput * (NdotL / light_pdf) * brdf_diffuse * ls.emission * (float)sc.n_lights * diffuse_weight;
+            pending = nee_unshadowed(sc, mat, ps.throughput, ls, NdotL, NLdotL, diffuse_weight);
             result |= kBounceShadow;
         }
     }
@@ -298,12 +347,11 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
     if (GLOSSY >= 1 && r < mat.specular && mat.alpha > 0.0f) {                     // rough specular lobe
         V3 gd; float g;
         if (!ggx_sample(ps.rng, ray.d, hit.normal, mat.alpha, gd, g)) return result | kBounceTerminate;   // below the horizon: ends as RR ends it
-        ray = make_ray(hit.pos + gd * kNudge, gd, 1e34f);
+        ray = next_ray(hit, gd);
         ps.throughput = ps.throughput * (mat.albedo * g);
         ps.is_specular = true;                                                // light hits count, as after the mirror; chain choice 0
     } else if (r < mat.specular) {                                            // mirror, ref: Main.cpp:480-487
-        const V3 sd = reflect(ray.d, hit.normal);
-        ray = make_ray(hit.pos + sd * kNudge, sd, 1e34f);
+        ray = next_ray(hit, reflect(ray.d, hit.normal));
         ps.throughput = ps.throughput * mat.albedo;
         ps.is_specular = true;
         result |= kChainReflect << kBounceChainShift;
@@ -312,51 +360,25 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
         const uint32_t kind = rough_glass_sample(ps.rng, ray.d, hit.normal, mat.alpha_t, mat.ior, gd, g, inside);
         if (kind == kRoughGlassNone) return result | kBounceTerminate;       // the wrong side: ends as RR ends it
         ps.throughput = ps.throughput * (mat.albedo * g);
-        if (kind == kRoughGlassRefract && inside) {                           // Beer's law on the way out only, as in the smooth lobe
-            V3 ab;
-            ab.x = expf(-mat.absorption.x * ray.t);
-            ab.y = expf(-mat.absorption.y * ray.t);
-            ab.z = expf(-mat.absorption.z * ray.t);
-            ps.throughput = ps.throughput * ab;
-        }
-        ray = make_ray(hit.pos + gd * kNudge, gd, 1e34f);
+        if (kind == kRoughGlassRefract && inside) ps.throughput = ps.throughput * beer_absorption(mat, ray.t);   // on the way out only, as in the smooth lobe
+        ray = next_ray(hit, gd);
         ps.is_specular = true;                                                // chain choice 0
     } else if (r < mat.specular + mat.refractivity) {                         // dielectric, ref: Main.cpp:488-546
-        V3 N = hit.normal;
-        float cosi = clamp_std(dot(N, ray.d), -1.0f, 1.0f);
-        float etai = 1.0f, etat = mat.ior;
-        bool inside = true;
-        if (cosi < 0.0f) { cosi = -cosi; inside = false; }
-        else { float tmp = etai; etai = etat; etat = tmp; N = -N; }
-        const float eta = etai / etat;
-        const float k = 1.0f - eta * eta * (1.0f - cosi * cosi);
-        if (k >= 0.0f) {
-            const V3 rd = refract(ray.d, N, eta, cosi, k);
-            const float angle_in = dot(ray.d, hit.normal);
-            const float angle_out = dot(rd, hit.normal);
-            const float Fr = fresnel(angle_in, angle_out, etai, etat);
-            if (random_float(ps.rng) > Fr) {
-                ps.throughput = ps.throughput * mat.albedo;
-                if (inside) {                                                 // Beer's law on the way out only (SURVEY A-4)
-                    V3 ab;
-                    ab.x = expf(-mat.absorption.x * ray.t);
-                    ab.y = expf(-mat.absorption.y * ray.t);
-                    ab.z = expf(-mat.absorption.z * ray.t);
-                    ps.throughput = ps.throughput * ab;
-                }
-                ray = make_ray(hit.pos + rd * kNudge, rd, 1e34f);
-                ps.is_specular = true;
-                result |= kChainRefract << kBounceChainShift;
-            } else {                                                          // the same ray as the mirror lobe's
-                const V3 sd = reflect(ray.d, hit.normal);
-                ray = make_ray(hit.pos + sd * kNudge, sd, 1e34f);
-                ps.throughput = ps.throughput * mat.albedo;
-                ps.is_specular = true;
-                result |= kChainReflect << kBounceChainShift;
-            }
+        V3 gd; bool inside;
+        const uint32_t kind = smooth_glass(mat, hit, ray, ps.rng, gd, inside);
+        if (kind == kGlassRefract) {
+            ps.throughput = ps.throughput * mat.albedo;
+            if (inside) ps.throughput = ps.throughput * beer_absorption(mat, ray.t);
+            ray = next_ray(hit, gd);
+            ps.is_specular = true;
+            result |= kChainRefract << kBounceChainShift;
+        } else if (kind == kGlassReflect) {                                   // the same ray as the mirror lobe's
+            ray = next_ray(hit, gd);
+            ps.throughput = ps.throughput * mat.albedo;
+            ps.is_specular = true;
+            result |= kChainReflect << kBounceChainShift;
         } else {
-            // k < 0 (total internal reflection): the ray is left as it is -- t, obj, tri included -- and is traced again
-            // next iteration (SURVEY A-3)
+            // total internal reflection: the ray is left as it is -- t, obj, tri included -- and is traced again next iteration (SURVEY A-3)
             result |= kChainTir << kBounceChainShift;
         }
     } else {                                                                  // diffuse, ref: Main.cpp:547-570
@@ -370,7 +392,7 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
             NdotR = dot(dd, hit.normal);
             pdf = NdotR / kPi;
         }
-        ray = make_ray(hit.pos + dd * kNudge, dd, 1e34f);
+        ray = next_ray(hit, dd);
         ps.throughput = ps.throughput * ((NdotR / pdf) * (mat.albedo * kInvPi));
         ps.is_specular = false;
     }
@@ -402,7 +424,7 @@ __device__ __forceinline__ uint32_t brute_bounce(const DevScene& sc, const DevSe
                                                  BruteLevel& level, V3& leaf, Counters& cnt)
 {
     if (depth == 0 && st.debug_mode == 2u) {                                  // ref: Main.cpp:594-597
-        leaf = lerp(mk(0.0f, 1.0f, 0.0f), mk(1.0f, 0.0f, 0.0f), (float)ray.bvh_depth / 30.0f);
+        leaf = bvh_depth_colour(ray);
         return kBruteLeaf;
     }
     if (ray.obj == kNoHit) { leaf = mk(0.0f); return kBruteLeaf; }            // ref: Main.cpp:600-601
@@ -415,56 +437,31 @@ __device__ __forceinline__ uint32_t brute_bounce(const DevScene& sc, const DevSe
     if (GLOSSY >= 1 && r < mat.specular && mat.alpha > 0.0f) {                     // rough specular lobe: L = 0 + (albedo * G2/G1) * L
         V3 gd; float g;
         if (!ggx_sample(rng, ray.d, hit.normal, mat.alpha, gd, g)) { leaf = mk(0.0f); return kBruteLeaf; }
-        ray = make_ray(hit.pos + gd * kNudge, gd, 1e34f);
+        ray = next_ray(hit, gd);
         level.kind = 0u; level.a = mat.albedo * g;
     } else if (r < mat.specular) {                                            // ref: Main.cpp:614-619
-        const V3 sd = reflect(ray.d, hit.normal);
-        ray = make_ray(hit.pos + sd * kNudge, sd, 1e34f);
+        ray = next_ray(hit, reflect(ray.d, hit.normal));
         level.kind = 0u; level.a = mat.albedo;
     } else if (GLOSSY >= 2 && r < mat.specular + mat.refractivity && mat.alpha_t > 0.0f) {   // rough dielectric lobe
         V3 gd; float g; bool inside;
         const uint32_t kind = rough_glass_sample(rng, ray.d, hit.normal, mat.alpha_t, mat.ior, gd, g, inside);
         if (kind == kRoughGlassNone) { leaf = mk(0.0f); return kBruteLeaf; }
         level.kind = kind == kRoughGlassRefract && inside ? 1u : 0u; level.a = mat.albedo * g;
-        if (level.kind == 1u) {
-            level.absorb.x = expf(-mat.absorption.x * ray.t);
-            level.absorb.y = expf(-mat.absorption.y * ray.t);
-            level.absorb.z = expf(-mat.absorption.z * ray.t);
-        }
-        ray = make_ray(hit.pos + gd * kNudge, gd, 1e34f);
+        if (level.kind == 1u) level.absorb = beer_absorption(mat, ray.t);
+        ray = next_ray(hit, gd);
     } else if (r < mat.specular + mat.refractivity) {                         // ref: Main.cpp:621-675
-        V3 N = hit.normal;
-        float cosi = clamp_std(dot(N, ray.d), -1.0f, 1.0f);
-        float etai = 1.0f, etat = mat.ior;
-        bool inside = true;
-        if (cosi < 0.0f) { cosi = -cosi; inside = false; }
-        else { float tmp = etai; etai = etat; etat = tmp; N = -N; }
-        const float eta = etai / etat;
-        const float k = 1.0f - eta * eta * (1.0f - cosi * cosi);
-        if (!(k >= 0.0f)) { leaf = mk(0.0f); return kBruteLeaf; }             // total internal reflection: black (ref: Main.cpp:645)
-        const V3 rd = refract(ray.d, N, eta, cosi, k);
-        const float angle_in = dot(ray.d, hit.normal);
-        const float angle_out = dot(rd, hit.normal);
-        const float Fr = fresnel(angle_in, angle_out, etai, etat);
-        if (random_float(rng) > Fr) {
-            level.kind = inside ? 1u : 0u; level.a = mat.albedo;
-            if (inside) {
-                level.absorb.x = expf(-mat.absorption.x * ray.t);
-                level.absorb.y = expf(-mat.absorption.y * ray.t);
-                level.absorb.z = expf(-mat.absorption.z * ray.t);
-            }
-            ray = make_ray(hit.pos + rd * kNudge, rd, 1e34f);
-        } else {
-            const V3 sd = reflect(ray.d, hit.normal);
-            ray = make_ray(hit.pos + sd * kNudge, sd, 1e34f);
-            level.kind = 0u; level.a = mat.albedo;
-        }
+        V3 gd; bool inside;
+        const uint32_t kind = smooth_glass(mat, hit, ray, rng, gd, inside);
+        if (kind == kGlassTir) { leaf = mk(0.0f); return kBruteLeaf; }        // total internal reflection: black (ref: Main.cpp:645)
+        level.kind = kind == kGlassRefract && inside ? 1u : 0u; level.a = mat.albedo;
+        if (level.kind == 1u) level.absorb = beer_absorption(mat, ray.t);
+        ray = next_ray(hit, gd);
     } else {                                                                  // ref: Main.cpp:677-686
         const V3 dd = uniform_hemisphere_sample(rng, hit.normal);
         level.kind = 2u;
         level.cosi = dot(dd, hit.normal);
         level.a = (2.0f * kPi) * (mat.albedo * kInvPi);
-        ray = make_ray(hit.pos + dd * kNudge, dd, 1e34f);
+        ray = next_ray(hit, dd);
     }
     return kBruteContinue;
 }
@@ -479,6 +476,41 @@ __device__ __forceinline__ V3 brute_apply(const BruteLevel& lv, V3 L)
     V3 out = mk(0.0f) + lv.a * L;
     if (lv.kind == 1u) out = out * lv.absorb;
     return out;
+}
+
+// a BruteLevel as the two float4 the kernels that keep the chain in HBM store per level
+__device__ __forceinline__ void brute_pack(const BruteLevel& lv, float4& r0, float4& r1)
+{
+    r0.x = __uint_as_float(lv.kind); r0.y = lv.a.x; r0.z = lv.a.y; r0.w = lv.a.z;
+    r1.x = lv.cosi; r1.y = lv.absorb.x; r1.z = lv.absorb.y; r1.w = lv.absorb.z;
+}
+__device__ __forceinline__ BruteLevel brute_unpack(float4 r0, float4 r1)
+{
+    BruteLevel b;
+    b.kind = __float_as_uint(r0.x); b.a = mk(r0.y, r0.z, r0.w); b.cosi = r1.x; b.absorb = mk(r1.y, r1.z, r1.w);
+    return b;
+}
+
+// One TracePath level of a path at `depth` on the hit of `ray` (ref: Main.cpp:581-689), for every render kernel: the bounce's operation is
+// recorded with store(depth, level) and the path goes on with the child ray (returns false; depth is one more), or the path is finished
+// (returns true): the recorded chain, load(k) for k = depth-1 .. 0, is folded over the leaf's radiance, innermost level first, into L.
+// Where the chain lives is the caller's business.  When the depth cut-off fires -- the child returns black before tracing (ref:
+// Main.cpp:589-590) -- the level just made is applied from registers instead of being stored and loaded back: brute_apply(level, 0) is what
+// the fold's first step would compute.
+template <bool COUNT, int GLOSSY, class Store, class Load>
+__device__ __forceinline__ bool brute_level(const DevScene& sc, const DevSettings& st, Ray& ray, uint32_t& rng, uint32_t& depth, Store store, Load load,
+                                            V3& L, Counters& cnt)
+{
+    BruteLevel lv;
+    L = mk(0.0f);
+    uint32_t stored = depth;                                                  // levels 0 .. stored-1 are recorded
+    if (brute_bounce<COUNT, GLOSSY>(sc, st, ray, rng, depth, lv, L, cnt) != kBruteLeaf) {
+        depth++;
+        if ((int32_t)depth <= st.max_ray_depth) { store(stored, lv); return false; }
+        L = brute_apply(lv, mk(0.0f));
+    }
+    while (stored-- > 0u) L = brute_apply(load(stored), L);
+    return true;
 }
 
 // final colour of a finished path (ray-depth debug view, ref: Main.cpp:575-576)

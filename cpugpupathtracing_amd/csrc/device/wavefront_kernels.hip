@@ -309,9 +309,8 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
 
 // ---- K3 shade: one bounce per extend hit; survivors compacted into this wave's output segment ---------------------------
 // BRUTE: the render has TracePath paths (RENDER_MODE_BRUTE_FORCE / COMPARISON); a separate instantiation, so the TracePathAdvanced
-// renders carry neither its code nor its registers.  GLOSSY (the lobe level): 0 no rough lobe; 1 the scene has a rough specular material (shade_device.hpp: ggx_sample); 2 it has a rough dielectric (rough_glass_sample; carries the rough specular lobe too); 3 it has an object with smooth normals (get_hit's SMOOTH, cgpt_scene_update_smooth_normals; carries both rough lobes too).
+// renders carry neither its code nor its registers.  GLOSSY (the lobe level) and RIS: shade_device.hpp, above shade_bounce.
 // A rough bounce reports lobe choice 0, so its ray is never elected or followed as a specular chain.
-// RIS: the render resamples its NEE light sample (cgpt_set_nee_candidates > 1, shade_device.hpp); one shadow ray and one pending contribution per bounce either way.
 template <bool COUNT, bool FIRST, bool BRUTE = false, int GLOSSY = 0, bool RIS = false>
 __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, const WfDev wf, uint32_t batch_first)
 {
@@ -440,39 +439,18 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
 
             uint32_t flags = kBounceTerminate;
             if (BRUTE && brute_path) {
-                // One TracePath level (ref: Main.cpp:581-689): record this level's operation and go on with the child ray, or fold the
-                // recorded chain over the leaf's radiance, innermost level first.  The level just made is applied from registers.
+                // one TracePath level (shade_device.hpp: brute_level), the chain in this path's column of wf.brute
                 if (is_pixel) {
-                    BruteLevel lv; V3 leaf = mk(0.0f);
-                    bool fold = brute_bounce<COUNT, GLOSSY>(sc, args.settings, ray, ps.rng, ps.depth, lv, leaf, cnt) == kBruteLeaf;
-                    uint32_t stored = ps.depth;                               // levels 0 .. stored-1 are in memory
-                    if (!fold) {
-                        ps.depth++;
-                        if ((int32_t)ps.depth > args.settings.max_ray_depth) {   // the child returns black before tracing (ref: Main.cpp:589-590)
-                            fold = true;
-                            leaf = brute_apply(lv, mk(0.0f));
-                        } else {
-                            float4* rec = wf.brute + ((size_t)stored * wf.cap + pid) * 2u;
+                    const bool done = brute_level<COUNT, GLOSSY>(sc, args.settings, ray, ps.rng, ps.depth,
+                        [&](uint32_t k, const BruteLevel& lv) {
+                            float4* rec = wf.brute + ((size_t)k * wf.cap + pid) * 2u;
                             float4 r0, r1;
-                            r0.x = __uint_as_float(lv.kind); r0.y = lv.a.x; r0.z = lv.a.y; r0.w = lv.a.z;
-                            r1.x = lv.cosi; r1.y = lv.absorb.x; r1.z = lv.absorb.y; r1.w = lv.absorb.z;
+                            brute_pack(lv, r0, r1);
                             st_stream(&rec[0], r0); st_stream(&rec[1], r1);
-                        }
-                    }
-                    if (fold) {
-                        V3 L = leaf;
-                        for (uint32_t k = stored; k-- > 0u;) {
-                            const float4* rec = wf.brute + ((size_t)k * wf.cap + pid) * 2u;
-                            const float4 r0 = ld_stream(&rec[0]), r1 = ld_stream(&rec[1]);
-                            BruteLevel b;
-                            b.kind = __float_as_uint(r0.x); b.a = mk(r0.y, r0.z, r0.w); b.cosi = r1.x; b.absorb = mk(r1.y, r1.z, r1.w);
-                            L = brute_apply(b, L);
-                        }
-                        ps.energy = L;
-                        flags = kBounceTerminate | kBounceBruteDone;
-                    } else {
-                        flags = 0u;
-                    }
+                        },
+                        [&](uint32_t k) { const float4* rec = wf.brute + ((size_t)k * wf.cap + pid) * 2u; return brute_unpack(ld_stream(&rec[0]), ld_stream(&rec[1])); },
+                        ps.energy, cnt);
+                    flags = done ? kBounceTerminate | kBounceBruteDone : 0u;
                 }
             } else if (is_pixel) flags = shade_bounce<COUNT, GLOSSY, RIS>(sc, args.settings, ray, ps, shadow, pending, cnt);
             emit_ext = (flags & kBounceTerminate) == 0u;
@@ -885,11 +863,12 @@ int WavefrontSetTuning(cgpt_ctx* ctx, const char* name, uint32_t value)
     return h ? SetKnob(ctx, FindKnob(kKnobs, name), h->tune, name, value) : CGPT_ERR_HIP;
 }
 
-int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, uint32_t lobe_level, bool ris)
+int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
 {
     hipStream_t stream = CtxStream(ctx);
     WfHost* h = WfGetHost(ctx);
     if (!h) return -1;
+    const bool count = v.count;
     const uint32_t rows = args_in.n_rows;
     const uint32_t tiles_x = (args_in.width + 7u) / 8u, tiles_y = (rows + 7u) / 8u;
     const uint64_t n_pixels64 = (uint64_t)tiles_x * tiles_y * 64u;             // padded to whole 8x8 tiles
@@ -919,7 +898,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, uin
     const dim3 trace_grid_later(n_cus * std::min(h->tune.max_trace_blocks, h->trace_blocks_per_cu[count][0]));
     const bool brute = args_in.settings.render_mode != 2u;                    // the render has TracePath paths (ref: Main.cpp:719-729)
     const uint32_t brute_levels = brute ? (uint32_t)args_in.settings.max_ray_depth + 1u : 0u;
-    const uint32_t (&shade_blocks)[2][2] = h->shade_blocks_per_cu[ris][lobe_level];   // every lobe level's shade kernels, with and without RIS, have grids of their own
+    const uint32_t (&shade_blocks)[2][2] = h->shade_blocks_per_cu[v.ris][v.lobe_level];   // every lobe level's shade kernels, with and without RIS, have grids of their own
     const dim3 shade_grid(n_cus * shade_blocks[count][brute]);
     // one output segment per shade wave, sized for the most 64-item blocks a wave can be handed
     const uint32_t n_segs = n_cus * std::max({ shade_blocks[0][0], shade_blocks[1][0], shade_blocks[0][1], shade_blocks[1][1] }) * 4u;
@@ -1034,7 +1013,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, bool count, uin
                     }
                     wf.spec_epoch = h->spec_epoch[p];
                 }
-                hipLaunchKernelGGL(kShadeKernels[ris][lobe_level][count][first][brute], shade_grid, block, 0, st, args, wf, bfirst);
+                hipLaunchKernelGGL(kShadeKernels[v.ris][v.lobe_level][count][first][brute], shade_grid, block, 0, st, args, wf, bfirst);
                 hipLaunchKernelGGL(wf_plan, dim3(2u * wf.n_bands), dim3(256), 0, st, wf);
                 hipLaunchKernelGGL(wf_gather, dim3(std::min(2u * wf.n_segs, n_cus * 16u)), block, 0, st, wf);
                 launches += 3;
