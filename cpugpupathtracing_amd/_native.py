@@ -110,7 +110,8 @@ class SceneLayoutView(C.Structure):
                 ("record_perm", _up), ("n_record_perm", C.c_size_t),
                 ("stack_depth", C.c_uint32), ("n_top_records", C.c_uint32), ("n_pair_records", C.c_uint32), ("n_small_tris", C.c_uint32),
                 ("leaf_base", _up), ("pair_base", _up), ("level_begin", _up), ("level_offsets", _up), ("level_offsets_start", _up),
-                ("tri_normal12", _fp), ("n_tri_normal12", C.c_size_t)]
+                ("tri_normal12", _fp), ("n_tri_normal12", C.c_size_t),
+                ("obj_xform", _fp), ("n_obj_xform", C.c_size_t)]
 
 
 # name -> (restype, argtypes).  Every symbol declared in include/*.h is listed; tests check the list against the headers.
@@ -127,6 +128,7 @@ PROTOTYPES = {
     "cgpt_scene_update_roughness": (C.c_int, [_vp, _fp, C.c_uint32]),
     "cgpt_scene_update_transmission_roughness": (C.c_int, [_vp, _fp, C.c_uint32]),
     "cgpt_scene_update_smooth_normals": (C.c_int, [_vp, _up, C.c_uint32]),
+    "cgpt_scene_update_transforms": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_uint32]),
     "cgpt_scene_refit_mesh": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), C.c_uint32, _fp]),
     "cgpt_scene_export_bvh": (C.c_int, [_vp, C.c_uint32, C.POINTER(BvhNode), C.c_uint32]),
     "cgpt_scene_update_primitive": (C.c_int, [_vp, C.c_uint32, C.POINTER(Object)]),
@@ -179,6 +181,8 @@ PROTOTYPES = {
     "cgpth_scene_add_light": (C.c_int, [_vp, C.c_uint32]),
     "cgpth_scene_set_smooth_normals": (C.c_int, [_vp, C.c_uint32, C.c_uint32]),
     "cgpth_scene_get_smooth_normals": (C.c_int, [_vp, _up, C.c_uint32]),
+    "cgpth_scene_set_transform": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_float)]),
+    "cgpth_scene_get_transforms": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_uint32]),
     "cgpth_scene_set_camera": (C.c_int, [_vp, _fp, _fp, C.c_float, C.c_float]),
     "cgpth_scene_set_settings": (C.c_int, [_vp, C.POINTER(Settings)]),
     "cgpth_scene_rebuild_bvh": (C.c_int, [_vp, C.c_uint32, C.c_int]),
@@ -195,6 +199,7 @@ PROTOTYPES = {
     "cgpth_read_accumulator": (C.c_int, [C.c_char_p, _fp, _up, C.c_uint32, C.c_uint32]),
     "cgpth_fast_div": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "cgpth_scene_layout": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(SceneLayoutView)]),
+    "cgpth_scene_layout_transformed": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(C.c_float), C.c_uint32, C.POINTER(SceneLayoutView)]),
 }
 
 # exported for the tests, declared in csrc/device/ctx_internal.h: not part of the ABI that include/*.h declares

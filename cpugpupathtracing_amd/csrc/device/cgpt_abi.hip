@@ -21,7 +21,7 @@
 namespace cgpt {
 hipError_t LaunchMegakernel(const DevRenderArgs& args, ShadeVariant v, hipStream_t stream);                                  // path_kernels.hip
 hipError_t LaunchIntersectRays(const DevScene& sc, const float* origins, const float* dirs, const float* tmax, uint32_t n, float* out_t,
-                               uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, DevCounters* counters, hipStream_t stream);
+                               uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, DevCounters* counters, bool xform, hipStream_t stream);
 int LaunchWavefront(struct ::cgpt_ctx* ctx, const DevRenderArgs& args, ShadeVariant v);                                     // wavefront_kernels.hip
 void WavefrontFree(void* state);
 void WavefrontCollectTiming(void* state, double* trace_ms, uint32_t* trace_launches, double* round0_ms, uint32_t* round0_launches);
@@ -75,7 +75,7 @@ void FreeScene(cgpt_ctx* ctx)
     ctx->sb = SceneBuffers{};
     ctx->h_objects.clear(); ctx->refit_objects.clear(); ctx->record_perm.clear();
     ctx->h_roughness.clear(); ctx->h_transmission_roughness.clear(); ctx->h_materials.clear(); ctx->lobe_level = 0;
-    ctx->any_smooth = false; ctx->h_lights.clear();
+    ctx->any_smooth = false; ctx->any_xform = false; ctx->h_lights.clear();
     ctx->has_scene = false;
 }
 
@@ -118,13 +118,13 @@ int ResolveBand(cgpt_ctx* ctx, const cgpt_render_params& p, Band& b)
     return CGPT_OK;
 }
 
-// the GLOSSY instantiation the renders run (ctx_internal.h: lobe_level), from the two roughness arrays and the smooth flags
+// the GLOSSY instantiation the renders run (ctx_internal.h: lobe_level), from the two roughness arrays, the smooth flags and the transforms
 void UpdateLobeLevel(cgpt_ctx* ctx)
 {
     bool specular = false, glass = false;
     for (const float v : ctx->h_roughness) specular = specular || v > 0.0f;
     for (const float v : ctx->h_transmission_roughness) glass = glass || v > 0.0f;
-    ctx->lobe_level = ctx->any_smooth ? 3u : (glass ? 2u : (specular ? 1u : 0u));
+    ctx->lobe_level = ctx->any_xform ? 4u : (ctx->any_smooth ? 3u : (glass ? 2u : (specular ? 1u : 0u)));
 }
 
 // cgpt_scene_update_roughness (transmission false: PackMaterial's alpha, materials[4i+3].z) and cgpt_scene_update_transmission_roughness
@@ -179,6 +179,40 @@ int UpdateSmoothNormals(cgpt_ctx* ctx, const uint32_t* smooth, uint32_t n_object
     }
     ctx->h_objects.swap(objects);
     ctx->any_smooth = any;
+    UpdateLobeLevel(ctx);
+    return CGPT_OK;
+}
+
+// cgpt_scene_update_transforms of a one-device context: the flag in every object's obj_trace record and the transform records behind them,
+// one write.  Everything is refused before it (scene_layout.h: LayoutTransforms).
+int UpdateTransforms(cgpt_ctx* ctx, const float* object_to_world, uint32_t n_objects)
+{
+    if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
+    std::vector<float4> trace;                                                 // the whole obj_trace allocation: 2 n records, then 3 n
+    bool any = false;
+    const int rc = Guarded(ctx, "transform update", [&] {
+        std::vector<float4> records;
+        std::vector<uint32_t> flags;
+        const int rl = LayoutTransforms(object_to_world, n_objects, ctx->h_objects, ctx->h_lights, records, flags, ctx->error);
+        if (rl != CGPT_OK) return rl;
+        trace.resize(5 * (size_t)n_objects);
+        for (uint32_t i = 0; i < n_objects; ++i) {
+            any = any || flags[i] != 0u;
+            PackObjTrace(ctx->h_objects[i], trace[2 * (size_t)i], trace[2 * (size_t)i + 1], flags[i]);
+        }
+        std::copy(records.begin(), records.end(), trace.begin() + 2 * (size_t)n_objects);
+        return (int)CGPT_OK;
+    });
+    if (rc != CGPT_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->scene_generation++;                                                   // the denoiser's guides hold position and normal (denoise.hip)
+    const hipError_t e = trace.empty() ? hipSuccess : hipMemcpy(ctx->sb.obj_trace.p, trace.data(), trace.size() * sizeof(float4), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {                                                     // the records may be half written: drop the scene (refit.hip: SceneLost)
+        ctx->has_scene = false;
+        return CtxFail(ctx, CGPT_ERR_HIP, "hipMemcpy of the transform records failed: %s (the device scene is dropped; upload it again)", hipGetErrorString(e));
+    }
+    ctx->any_xform = any;
     UpdateLobeLevel(ctx);
     return CGPT_OK;
 }
@@ -312,6 +346,13 @@ int cgpt_scene_update_smooth_normals(cgpt_ctx* ctx, const uint32_t* smooth, uint
     return UpdateSmoothNormals(ctx, smooth, n_objects);
 }
 
+int cgpt_scene_update_transforms(cgpt_ctx* ctx, const float* object_to_world, uint32_t n_objects)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupUpdateTransforms(ctx, object_to_world, n_objects); });
+    return UpdateTransforms(ctx, object_to_world, n_objects);
+}
+
 int cgpt_camera_from_view(const float pos[3], const float view_dir[3], float fov_deg, float aspect, cgpt_camera* out)
 {
     if (!pos || !view_dir || !out) return CGPT_ERR_INVALID;
@@ -348,12 +389,19 @@ int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout)
     }
     if ((rc = UploadArray(ctx, ctx->sb.materials, layout.materials)) != CGPT_OK) return rc;
     if ((rc = UploadArray(ctx, ctx->sb.objects, layout.objects)) != CGPT_OK) return rc;
-    if ((rc = UploadArray(ctx, ctx->sb.obj_trace, layout.obj_trace)) != CGPT_OK) return rc;
+    // obj_trace: the 2 n trace records, then the 3 n transform records (device_scene.h)
+    const size_t n_obj = layout.objects.size();
+    if (layout.obj_trace.size() != 2 * n_obj || layout.obj_xform.size() != 3 * n_obj) return CtxFail(ctx, CGPT_ERR_INVALID, "layout: %zu trace and %zu transform records for %zu objects", layout.obj_trace.size(), layout.obj_xform.size(), n_obj);
+    HIP_TRY(ctx, ctx->sb.obj_trace.Alloc(n_obj ? 5 * n_obj : 1));
+    if (n_obj) {
+        HIP_TRY(ctx, hipMemcpy(ctx->sb.obj_trace.p, layout.obj_trace.data(), sizeof(float4) * 2 * n_obj, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(ctx->sb.obj_trace.p + 2 * n_obj, layout.obj_xform.data(), sizeof(float4) * 3 * n_obj, hipMemcpyHostToDevice));
+    }
     if ((rc = UploadArray(ctx, ctx->sb.lights, layout.lights)) != CGPT_OK) return rc;
     if ((rc = UploadArray(ctx, ctx->sb.refit_levels, layout.refit_levels)) != CGPT_OK) return rc;
     ctx->h_objects = layout.objects; ctx->refit_objects = layout.refit_objects; ctx->record_perm = layout.record_perm;
     ctx->h_roughness.assign(layout.n_materials, 0.0f); ctx->h_transmission_roughness.assign(layout.n_materials, 0.0f); ctx->h_materials = layout.materials; ctx->lobe_level = 0;
-    ctx->any_smooth = false; ctx->h_lights = layout.lights;                    // an upload resets every smooth-normal flag (LayoutScene writes 0)
+    ctx->any_smooth = false; ctx->any_xform = false; ctx->h_lights = layout.lights;   // an upload resets every smooth-normal flag and transform (LayoutScene writes 0 and the identity)
 
     ctx->scene.node_pairs = ctx->sb.node_pairs.p; ctx->scene.tri_leaf = ctx->sb.tri_leaf.p; ctx->scene.tri_orig = ctx->sb.tri_orig.p; ctx->scene.tri_normal = ctx->sb.tri_normal.p;
     ctx->scene.materials = ctx->sb.materials.p; ctx->scene.objects = ctx->sb.objects.p; ctx->scene.obj_trace = ctx->sb.obj_trace.p; ctx->scene.lights = ctx->sb.lights.p;
@@ -642,7 +690,7 @@ int cgpt_intersect_rays(cgpt_ctx* ctx, const float* origins, const float* dirs, 
     HIP_TRY(ctx, hipMemcpyAsync(d_o.p, origins, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_d.p, dirs, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     if (tmax) HIP_TRY(ctx, hipMemcpyAsync(d_tm.p, tmax, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, LaunchIntersectRays(ctx->scene, d_o.p, d_d.p, d_tm.p, n, d_t.p, d_obj.p, d_tri.p, d_dep.p, ctx->counters.p, ctx->stream));
+    HIP_TRY(ctx, LaunchIntersectRays(ctx->scene, d_o.p, d_d.p, d_tm.p, n, d_t.p, d_obj.p, d_tri.p, d_dep.p, ctx->counters.p, ctx->any_xform, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out_t, d_t.p, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out_obj, d_obj.p, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out_tri, d_tri.p, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));

@@ -52,8 +52,8 @@ struct cgpt_ctx {
     bool has_scene = false;
     // the specular lobe's roughness and the dielectric lobe's transmission roughness per material (cgpt_scene_update_roughness,
     // cgpt_scene_update_transmission_roughness; 0 after every upload), the packed material records as they are on the device (a roughness
-    // or material update re-packs them), and the lobe level = the GLOSSY instantiation of the render kernels the renders run: 3 when any
-    // object has smooth normals, else 2 when any transmission roughness is > 0, else 1 when any roughness is > 0, else 0 (UpdateLobeLevel,
+    // or material update re-packs them), and the lobe level = the GLOSSY instantiation of the render kernels the renders run: 4 when any
+    // object has a transform (any_xform: level 3 plus transforms), else 3 when any object has smooth normals, else 2 when any transmission roughness is > 0, else 1 when any roughness is > 0, else 0 (UpdateLobeLevel,
     // cgpt_abi.hip)
     std::vector<float> h_roughness, h_transmission_roughness;
     std::vector<float4> h_materials;
@@ -62,6 +62,10 @@ struct cgpt_ctx {
     // selects lobe level 3 and the guide kernel's SMOOTH instantiation; h_lights is the uploaded light_indices (a light cannot be smooth)
     bool any_smooth = false;
     std::vector<uint32_t> h_lights;
+    // cgpt_scene_update_transforms: the flags live in the objects' obj_trace records, the inverses behind those
+    // records (device_scene.h; identity and 0 after every upload, the other edits keep them); any_xform selects lobe level 4 and the XFORM
+    // instantiations of wf_trace, the guide kernel and intersect_rays_kernel
+    bool any_xform = false;
     // cgpt_set_nee_candidates: context state like the stream (an upload keeps it).  A render with more than one candidate, NEE on and
     // TracePathAdvanced paths runs the RIS instantiations of the render kernels
     uint32_t nee_candidates = 1;
@@ -129,6 +133,7 @@ int GroupUpdateMaterials(cgpt_ctx* ctx, const cgpt_material* materials, uint32_t
 int GroupUpdateRoughness(cgpt_ctx* ctx, const float* roughness, uint32_t n);
 int GroupUpdateTransmissionRoughness(cgpt_ctx* ctx, const float* roughness, uint32_t n);
 int GroupUpdateSmoothNormals(cgpt_ctx* ctx, const uint32_t* smooth, uint32_t n);
+int GroupUpdateTransforms(cgpt_ctx* ctx, const float* object_to_world, uint32_t n);
 int GroupSetNeeCandidates(cgpt_ctx* ctx, uint32_t candidates);
 int GroupRefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris, float* total_area_out);
 int GroupUpdatePrimitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_object* obj);

@@ -38,6 +38,17 @@
 //                                   trace kernel tests it with the leaf step it already runs -- IntersectTriangle with no bounds
 //                                   test and no bvh_depth increment, as a leaf-rooted mesh is walked (ref: BVH.cpp:68-90).
 //                                   DevObject.kind keeps CGPT_OBJECT_TRIANGLE for shading and the COUNT walks.
+//                                   A mesh or triangle object with a transform (cgpt_scene_update_transforms) has bits(1) in p1, else 0.
+//  obj_trace   float4[3 * n]        behind those, in the same allocation: record 2 n + 3 i + r = {Ainv row r, binv_r} of object i, the inverse
+//   (transforms)                    of its object-to-world matrix [A | b]: Ainv = A^-1, binv = -A^-1 b, formed in double on the host and rounded
+//                                   to float once (scene_layout.h: InvertTransform).  Identity rows after an upload.  Read only by the XFORM
+//                                   instantiations (lobe level 4), for an object whose obj_trace record carries the flag (DevObject has no
+//                                   word for it and keeps its 72 bytes: every existing kernel indexes it as before): the ray enters the mesh as
+//                                   o' = Ainv o + binv, d' = Ainv d (rt_device.hpp: xform_ray; d' is not renormalised, so t is the same number
+//                                   in both spaces), the hit's normal leaves it as normalize(Ainv^T n) (shade_device.hpp: get_hit).
+//                                   Everything else of a transformed mesh -- tree, triangles, normals, total_area -- stays in object space.
+//                                   The reference's absolute determinant epsilon (|a| < 0.001 in intersect_triangle, SURVEY A-9) is therefore
+//                                   applied to object-space numbers: scaling an object by its transform moves the epsilon with it.
 //
 // record order: a child-pair record's index is only a name (the codes inside the records and the root codes are the only
 // references to it), so the upload renumbers them: records [0, n_top_records) are the top levels of all meshes' trees in
@@ -88,7 +99,7 @@ struct DevScene {
     const float4* tri_normal;
     const float4* materials;
     const DevObject* objects;
-    const float4* obj_trace;
+    const float4* obj_trace;   // 2 n trace records, then 3 n transform records
     const uint32_t* lights;
     uint32_t n_objects;
     uint32_t n_lights;

@@ -384,6 +384,11 @@ int GroupUpdateSmoothNormals(cgpt_ctx* ctx, const uint32_t* smooth, uint32_t n)
     return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_update_smooth_normals(m, smooth, n); });
 }
 
+int GroupUpdateTransforms(cgpt_ctx* ctx, const float* object_to_world, uint32_t n)
+{
+    return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_update_transforms(m, object_to_world, n); });
+}
+
 int GroupSetNeeCandidates(cgpt_ctx* ctx, uint32_t candidates)              // the range was checked: no member can refuse, none is left behind
 {
     for (cgpt_ctx* m : ctx->group->members) { const int rc = cgpt_set_nee_candidates(m, candidates); if (rc != CGPT_OK) return Propagate(ctx, m, rc); }

@@ -80,7 +80,7 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
 
             // ---- one ray per iteration: the extend ray or the pending shadow ray ----
             Ray cur = shadow_kind ? sray : ray;
-            intersect_scene<COUNT>(sc, cur, stack, stride, cnt);
+            intersect_scene<COUNT, (GLOSSY >= 4)>(sc, cur, stack, stride, cnt);
 
             bool finalize;
             if (BRUTE && use_brute) {
@@ -140,11 +140,11 @@ static uint32_t MegakernelBlockThreads(const DevRenderArgs& args)
 
 // every instantiation, [RIS][COUNT][BRUTE][GLOSSY]
 #define CGPT_MEGAKERNELS(R) \
-    { { { megakernel<false, false, 0, R>, megakernel<false, false, 1, R>, megakernel<false, false, 2, R>, megakernel<false, false, 3, R> },     \
-        { megakernel<false, true, 0, R>, megakernel<false, true, 1, R>, megakernel<false, true, 2, R>, megakernel<false, true, 3, R> } },         \
-      { { megakernel<true, false, 0, R>, megakernel<true, false, 1, R>, megakernel<true, false, 2, R>, megakernel<true, false, 3, R> },         \
-        { megakernel<true, true, 0, R>, megakernel<true, true, 1, R>, megakernel<true, true, 2, R>, megakernel<true, true, 3, R> } } }
-static decltype(&megakernel<false, false, 0, false>) const kMegakernels[2][2][2][4] = { CGPT_MEGAKERNELS(false), CGPT_MEGAKERNELS(true) };
+    { { { megakernel<false, false, 0, R>, megakernel<false, false, 1, R>, megakernel<false, false, 2, R>, megakernel<false, false, 3, R>, megakernel<false, false, 4, R> },     \
+        { megakernel<false, true, 0, R>, megakernel<false, true, 1, R>, megakernel<false, true, 2, R>, megakernel<false, true, 3, R>, megakernel<false, true, 4, R> } },         \
+      { { megakernel<true, false, 0, R>, megakernel<true, false, 1, R>, megakernel<true, false, 2, R>, megakernel<true, false, 3, R>, megakernel<true, false, 4, R> },         \
+        { megakernel<true, true, 0, R>, megakernel<true, true, 1, R>, megakernel<true, true, 2, R>, megakernel<true, true, 3, R>, megakernel<true, true, 4, R> } } }
+static decltype(&megakernel<false, false, 0, false>) const kMegakernels[2][2][2][5] = { CGPT_MEGAKERNELS(false), CGPT_MEGAKERNELS(true) };
 #undef CGPT_MEGAKERNELS
 
 hipError_t LaunchMegakernel(const DevRenderArgs& args, ShadeVariant v, hipStream_t stream)
@@ -185,7 +185,9 @@ hipError_t LaunchPackPixels(const float4* accumulator, uint32_t* pixels, size_t 
     return hipGetLastError();
 }
 
-// IntersectScene on a batch of rays (ref: Main.cpp:299-316)
+// IntersectScene on a batch of rays (ref: Main.cpp:299-316).  XFORM: the scene has a transformed object (rt_device.hpp: intersect_scene);
+// the rays and the returned t are the world's either way
+template <bool XFORM>
 __global__ void __launch_bounds__(256) intersect_rays_kernel(const DevScene sc, const float* __restrict__ origins,
                                                              const float* __restrict__ dirs, const float* __restrict__ tmax,
                                                              uint32_t n, float* __restrict__ out_t, uint32_t* __restrict__ out_obj,
@@ -197,7 +199,7 @@ __global__ void __launch_bounds__(256) intersect_rays_kernel(const DevScene sc, 
     Counters cnt = { 0, 0, 0, 0, 0 };
     if (i < n) {
         Ray ray = make_ray(mk(origins + 3 * (size_t)i), mk(dirs + 3 * (size_t)i), tmax ? tmax[i] : 1e34f);
-        intersect_scene<true>(sc, ray, stack, blockDim.x, cnt);
+        intersect_scene<true, XFORM>(sc, ray, stack, blockDim.x, cnt);
         out_t[i] = ray.t; out_obj[i] = ray.obj; out_tri[i] = ray.tri; out_depth[i] = ray.bvh_depth;
     }
     wave_add_u64(&counters->traced_rays, cnt.rays);
@@ -207,10 +209,10 @@ __global__ void __launch_bounds__(256) intersect_rays_kernel(const DevScene sc, 
 }
 
 hipError_t LaunchIntersectRays(const DevScene& sc, const float* origins, const float* dirs, const float* tmax, uint32_t n, float* out_t,
-                               uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, DevCounters* counters, hipStream_t stream)
+                               uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, DevCounters* counters, bool xform, hipStream_t stream)
 {
     const size_t lds = (size_t)sc.stack_depth * 256 * sizeof(uint32_t);
-    hipLaunchKernelGGL(intersect_rays_kernel, dim3((n + 255u) / 256u), dim3(256), lds, stream, sc, origins, dirs, tmax, n, out_t, out_obj,
+    hipLaunchKernelGGL(xform ? intersect_rays_kernel<true> : intersect_rays_kernel<false>, dim3((n + 255u) / 256u), dim3(256), lds, stream, sc, origins, dirs, tmax, n, out_t, out_obj,
                        out_tri, out_depth, counters);
     return hipGetLastError();
 }

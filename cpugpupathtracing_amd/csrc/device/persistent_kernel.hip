@@ -68,6 +68,7 @@ enum : uint32_t {                      // per-lane path flags
 template <bool COUNT, bool BRUTE, bool TAIL, int GLOSSY, bool RIS>
 __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderArgs args, const PtDev pt, uint32_t batch_first, const TraceTune tune)
 {
+    constexpr bool XFORM = GLOSSY >= 4;                                       // the scene has a transformed object (trace_steps.hpp)
     const DevScene& sc = args.scene;
     const DevSettings& st = args.settings;
     const uint32_t grid_threads = gridDim.x * kTraceBlock;
@@ -82,6 +83,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
     Trav r;
     r.d = mk(0.0f); r.rs = make_ray_slab(r.d, r.d); r.t = 0.0f;
     r.obj = kNoHit; r.tri = 0; r.depth = 0; r.cur_obj = 0; r.code = kIdle; r.sp = 0; r.fast_levels = kLdsStackLevels;
+    if (XFORM) { r.wo = mk(0.0f); r.wd = mk(0.0f); trav_set_ray(r, r.wo, r.wd); }   // d, 1 / d and the slab operands of one ray, as object_step keeps them
     // the path this lane owns
     uint32_t pid = 0, rng = 0, pf = 0;
     V3 tp = mk(0.0f), en = mk(0.0f), pending = mk(0.0f);
@@ -104,7 +106,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
             if (pf & kPfDead) {
                 finish_path(en);
             } else {
-                trav_start(ctx, r, park_o, park_d, park_t, park_obj, park_tri, park_depth);
+                trav_start<XFORM>(ctx, r, park_o, park_d, park_t, park_obj, park_tri, park_depth);
                 cnt.rays++;
             }
         } else if (r.obj == kNoHit && !(BRUTE && (pf & kPfBrute)) && !(st.debug_mode == 2u && (pf & kPfDepthMask) == 0u)) {
@@ -116,7 +118,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
     // one bounce of the path on the hit of its extend ray: the lanes with r.code == kShade
     auto shade_hit = [&]() {
         Ray ray;
-        ray.o = trav_origin(r); ray.d = r.d; ray.t = r.t; ray.obj = r.obj; ray.tri = r.tri; ray.bvh_depth = trav_depth(r);
+        ray.o = trav_world_origin<XFORM>(r); ray.d = trav_world_dir<XFORM>(r); ray.t = r.t; ray.obj = r.obj; ray.tri = r.tri; ray.bvh_depth = trav_depth(r);
         if (BRUTE && (pf & kPfBrute)) {
             // one TracePath level (shade_device.hpp: brute_level), the chain in this thread's column of pt.brute
             uint32_t depth = pf & kPfDepthMask;
@@ -133,7 +135,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
             if (done) {
                 finish_path(L);
             } else {
-                trav_start(ctx, r, ray.o, ray.d, ray.t, ray.obj, ray.tri, ray.bvh_depth);
+                trav_start<XFORM>(ctx, r, ray.o, ray.d, ray.t, ray.obj, ray.tri, ray.bvh_depth);
                 cnt.rays++;
             }
         } else {
@@ -149,10 +151,10 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
                 pending = pend;
                 pf |= kPfShadow | (dead ? kPfDead : 0u);
                 park_o = ray.o; park_d = ray.d; park_t = ray.t; park_obj = ray.obj; park_tri = ray.tri; park_depth = ray.bvh_depth;
-                trav_start(ctx, r, shadow.o, shadow.d, shadow.t, kNoHit, 0u, 0u);
+                trav_start<XFORM>(ctx, r, shadow.o, shadow.d, shadow.t, kNoHit, 0u, 0u);
                 cnt.rays++;
             } else if (!dead) {
-                trav_start(ctx, r, ray.o, ray.d, ray.t, ray.obj, ray.tri, ray.bvh_depth);
+                trav_start<XFORM>(ctx, r, ray.o, ray.d, ray.t, ray.obj, ray.tri, ray.bvh_depth);
                 cnt.rays++;
             } else {
                 finish_path(en);
@@ -174,7 +176,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
                 if (primary_ray(args, pt.g, pid, batch_first, pr, rng, px)) {  // false: padding of an edge tile, the lane stays idle
                     tp = mk(1.0f); en = mk(0.0f); pf = 0u;                    // ref: Main.cpp:398-402
                     if (BRUTE && (st.render_mode == 1u || (st.render_mode == 0u && px < args.width / 2u))) pf = kPfBrute;   // ref: Main.cpp:719-729
-                    trav_start(ctx, r, pr.o, pr.d, pr.t, kNoHit, 0u, 0u);
+                    trav_start<XFORM>(ctx, r, pr.o, pr.d, pr.t, kNoHit, 0u, 0u);
                     cnt.rays++;
                 }
             }
@@ -198,21 +200,21 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
             // ---- the tail of the launch: a few rays left in this wave and no path to hand to the idle lanes: every lane runs its ray to
             //      the next object boundary in the lean loop (trace_steps.hpp: lean_traverse) -- the launch ends when its longest chain does
             if (TAIL && !can_refill && n_busy <= tune.tail_lanes && n_inner + n_leaf != 0u) {
-                if (r.code < kStartObject || (int32_t)r.code < 0) lean_traverse<COUNT, false>(ctx, r, cnt);
+                if (r.code < kStartObject || (int32_t)r.code < 0) lean_traverse<COUNT, false, XFORM>(ctx, r, cnt);
                 continue;
             }
 
             if (n_inner >= n_leaf && n_inner >= w_obj && n_inner >= w_shade) {
                 do {
-                    if (r.code < kStartObject) inner_step<COUNT>(ctx, r, cnt);
+                    if (r.code < kStartObject) inner_step<COUNT, XFORM>(ctx, r, cnt);
                 } while ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64(r.code < kStartObject)) >= tune.inner_repeat);
             } else if (n_leaf >= w_obj && n_leaf >= w_shade) {
                 do {
-                    if ((int32_t)r.code < 0) leaf_step<COUNT, false>(ctx, r, cnt);
+                    if ((int32_t)r.code < 0) leaf_step<COUNT, false, XFORM>(ctx, r, cnt);
                 } while ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64((int32_t)r.code < 0)) >= tune.leaf_repeat);
             } else if (w_obj >= w_shade) {
                 // ---- object step; a finished ray is dispatched on the spot ----
-                if (r.code == kStartObject && object_step<COUNT, false>(ctx, r, cnt)) ray_done();
+                if (r.code == kStartObject && object_step<COUNT, false, XFORM>(ctx, r, cnt)) ray_done();
             } else {
                 // ---- shade step: one bounce of the path on the hit of its extend ray ----
                 if (r.code == kShade) shade_hit();
@@ -255,9 +257,9 @@ struct PtTuning {
 #define CGPT_PT_LEVEL(G, R) \
     { { { pt_persistent<false, false, false, G, R>, pt_persistent<false, false, true, G, R> }, { pt_persistent<false, true, false, G, R>, pt_persistent<false, true, true, G, R> } }, \
       { { pt_persistent<true, false, false, G, R>, pt_persistent<true, false, true, G, R> }, { pt_persistent<true, true, false, G, R>, pt_persistent<true, true, true, G, R> } } }
-static decltype(&pt_persistent<false, false, false, 0, false>) const kPtKernels[2][4][2][2][2] = {
-    { CGPT_PT_LEVEL(0, false), CGPT_PT_LEVEL(1, false), CGPT_PT_LEVEL(2, false), CGPT_PT_LEVEL(3, false) },
-    { CGPT_PT_LEVEL(0, true), CGPT_PT_LEVEL(1, true), CGPT_PT_LEVEL(2, true), CGPT_PT_LEVEL(3, true) },
+static decltype(&pt_persistent<false, false, false, 0, false>) const kPtKernels[2][5][2][2][2] = {
+    { CGPT_PT_LEVEL(0, false), CGPT_PT_LEVEL(1, false), CGPT_PT_LEVEL(2, false), CGPT_PT_LEVEL(3, false), CGPT_PT_LEVEL(4, false) },
+    { CGPT_PT_LEVEL(0, true), CGPT_PT_LEVEL(1, true), CGPT_PT_LEVEL(2, true), CGPT_PT_LEVEL(3, true), CGPT_PT_LEVEL(4, true) },
 };
 #undef CGPT_PT_LEVEL
 static constexpr size_t kPtKernelCount = sizeof(kPtKernels) / sizeof(kPtKernels[0][0][0][0][0]);
@@ -272,7 +274,7 @@ struct PtHost {
     hipEvent_t begin = nullptr, acc_done[2] = { nullptr, nullptr };
     EventPairs ev;
     uint32_t n_cus = 0;
-    uint32_t blocks_per_cu[2][4][2][2][2] = {};  // [RIS][GLOSSY][COUNT][BRUTE][TAIL]
+    uint32_t blocks_per_cu[2][5][2][2][2] = {};  // [RIS][GLOSSY][COUNT][BRUTE][TAIL]
     static_assert(sizeof(blocks_per_cu) / sizeof(uint32_t) == kPtKernelCount, "one occupancy entry per instantiation");
     size_t occupancy_lds = 0;
 };

@@ -319,8 +319,40 @@ __device__ __forceinline__ bool traverse_mesh(const DevScene& sc, uint32_t root_
     return result;
 }
 
+// ---- per-object transforms (cgpt_scene_update_transforms; device_scene.h: the records behind obj_trace) ------------
+// tests/transform_ref.py states the same operations in numpy and is the specification.  float32, no contraction, in this order.
+struct Xform { float4 r0, r1, r2; };                                          // {Ainv row i, binv_i}
+__device__ __forceinline__ Xform load_xform(const DevScene& sc, uint32_t obj_idx)
+{
+    const float4* rec = sc.obj_trace + 2u * (size_t)sc.n_objects + 3u * (size_t)obj_idx;
+    Xform x; x.r0 = rec[0]; x.r1 = rec[1]; x.r2 = rec[2];
+    return x;
+}
+__device__ __forceinline__ bool has_xform(const DevScene& sc, uint32_t obj_idx)   // the flag of the object's obj_trace record (meshes and triangle objects)
+{
+    return __float_as_uint(sc.obj_trace[2u * (size_t)obj_idx].z) != 0u;
+}
+// the world ray (o, d) in the object's space: o' = Ainv o + binv, d' = Ainv d.  d' is not renormalised: t is the same number in both spaces
+__device__ __forceinline__ void xform_ray(const Xform& x, V3 o, V3 d, V3& oo, V3& od)
+{
+    oo.x = ((x.r0.x * o.x + x.r0.y * o.y) + x.r0.z * o.z) + x.r0.w;
+    oo.y = ((x.r1.x * o.x + x.r1.y * o.y) + x.r1.z * o.z) + x.r1.w;
+    oo.z = ((x.r2.x * o.x + x.r2.y * o.y) + x.r2.z * o.z) + x.r2.w;
+    od.x = (x.r0.x * d.x + x.r0.y * d.y) + x.r0.z * d.z;
+    od.y = (x.r1.x * d.x + x.r1.y * d.y) + x.r1.z * d.z;
+    od.z = (x.r2.x * d.x + x.r2.y * d.y) + x.r2.z * d.z;
+}
+// an object-space normal in the world: normalize(Ainv^T n)
+__device__ __forceinline__ V3 xform_normal(const Xform& x, V3 n)
+{
+    return normalize(mk((x.r0.x * n.x + x.r1.x * n.y) + x.r2.x * n.z, (x.r0.y * n.x + x.r1.y * n.y) + x.r2.y * n.z, (x.r0.z * n.x + x.r1.z * n.y) + x.r2.z * n.z));
+}
+
 // IntersectScene (ref: Source/Main.cpp:299-316): closest hit over all objects in order; strict t < ray.t everywhere.
-template <bool COUNT>
+// XFORM: the scene has an object with the transform flag set; such a mesh or triangle object is walked with the ray in its own space (1 / d',
+// the axis-parallel decision and the slab operands from d'), the next object sees the world ray again.  The instantiations without it
+// read neither the flag nor the records: the code they had.
+template <bool COUNT, bool XFORM = false>
 __device__ __forceinline__ void intersect_scene(const DevScene& sc, Ray& ray, uint32_t* __restrict__ stack, uint32_t stack_stride, Counters& cnt)
 {
     cnt.rays++;
@@ -328,7 +360,15 @@ __device__ __forceinline__ void intersect_scene(const DevScene& sc, Ray& ray, ui
     for (uint32_t obj_idx = 0; obj_idx < sc.n_objects; ++obj_idx) {
         const DevObject& obj = sc.objects[obj_idx];
         bool hit;
-        if (obj.kind == 0u) hit = traverse_mesh<COUNT>(sc, obj.root_code, ray.o, ray.d, inv, ray.t, ray.tri, ray.bvh_depth, stack, stack_stride, cnt);
+        if (XFORM && obj.kind != 1u && obj.kind != 2u && has_xform(sc, obj_idx)) {   // a mesh or a triangle object (a sphere's or plane's record holds floats there)
+            V3 oo, od;
+            xform_ray(load_xform(sc, obj_idx), ray.o, ray.d, oo, od);
+            if (obj.kind == 0u) hit = traverse_mesh<COUNT>(sc, obj.root_code, oo, od, mk(1.0f / od.x, 1.0f / od.y, 1.0f / od.z), ray.t, ray.tri, ray.bvh_depth, stack, stack_stride, cnt);
+            else {
+                const LeafTri lt = load_leaf_tri(sc.tri_leaf, obj.root_code & ~kLeafBit);
+                hit = intersect_triangle(lt.v0, lt.e1, lt.e2, oo, od, ray.t);
+            }
+        } else if (obj.kind == 0u) hit = traverse_mesh<COUNT>(sc, obj.root_code, ray.o, ray.d, inv, ray.t, ray.tri, ray.bvh_depth, stack, stack_stride, cnt);
         else if (obj.kind == 1u) hit = intersect_sphere(mk(obj.sphere_center), obj.sphere_radius_sq, ray.o, ray.d, ray.t);
         else if (obj.kind == 2u) hit = intersect_plane(mk(obj.plane_normal), mk(obj.plane_point), ray.o, ray.d, ray.t);
         else {                                                                // triangle object: IntersectTriangle on its leaf record

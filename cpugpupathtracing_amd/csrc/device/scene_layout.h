@@ -3,12 +3,14 @@
 // multi_gpu.hip copy the result to their devices, cgpth_scene_layout (cpugpupt_host.h) shows it to the CPU tests.
 // The record packers are here too: the in-place edits (material and roughness updates, refit.hip) write the same records.
 #pragma once
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "cpugpupt_abi.h"
 #include "device_scene.h"
+#include "transform_math.h"
 
 namespace cgpt {
 
@@ -27,6 +29,7 @@ struct SceneLayout {
     std::vector<float4> tri_normal12;          // {n1.xyz, -}, {n2.xyz, -} per triangle, original order: installed behind tri_normal's n0 records
     std::vector<DevObject> objects;
     std::vector<float4> obj_trace;
+    std::vector<float4> obj_xform;             // {Ainv row r, binv_r}, 3 per object: installed behind obj_trace's 2 n records.  LayoutScene writes the identity
     std::vector<uint32_t> lights;
     std::vector<uint32_t> refit_levels;
     // host bookkeeping of the in-place edits
@@ -75,12 +78,25 @@ inline void PackNormalPair(const cgpt_triangle& tr, float4 rec[2])
 }
 
 // obj_trace entry of an object (device_scene.h): what IntersectScene's object loop reads; upload and cgpt_scene_update_primitive
-inline void PackObjTrace(const DevObject& d, float4& q0, float4& q1)
+// xform: the object has a transform (cgpt_scene_update_transforms); meshes and triangle objects only
+inline void PackObjTrace(const DevObject& d, float4& q0, float4& q1, uint32_t xform = 0u)
 {
     q0 = make_float4(AsFloat(d.kind), 0.0f, 0.0f, 0.0f); q1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (d.kind == CGPT_OBJECT_MESH || d.kind == CGPT_OBJECT_TRIANGLE) { q0.x = AsFloat(CGPT_OBJECT_MESH); q0.y = AsFloat(d.root_code); }   // a triangle: a leaf-rooted mesh
+    if (d.kind == CGPT_OBJECT_MESH || d.kind == CGPT_OBJECT_TRIANGLE) { q0.x = AsFloat(CGPT_OBJECT_MESH); q0.y = AsFloat(d.root_code); q0.z = AsFloat(xform); }   // a triangle: a leaf-rooted mesh
     else if (d.kind == CGPT_OBJECT_SPHERE) { q0.y = d.sphere_center[0]; q0.z = d.sphere_center[1]; q0.w = d.sphere_center[2]; q1.x = d.sphere_radius_sq; }
     else { q0.y = d.plane_normal[0]; q0.z = d.plane_normal[1]; q0.w = d.plane_normal[2]; q1.x = d.plane_point[0]; q1.y = d.plane_point[1]; q1.z = d.plane_point[2]; }
 }
+
+// ---- per-object transforms (cgpt_scene_update_transforms; tests/transform_ref.py states the same arithmetic in numpy) ----------------
+// An object-to-world matrix is 12 floats, the rows of [A | b]: world = A p + b.  The inverse and the identity test: transform_math.h.
+inline void IdentityTransformRecords(float4 rec[3])
+{
+    rec[0] = make_float4(1.0f, 0.0f, 0.0f, 0.0f); rec[1] = make_float4(0.0f, 1.0f, 0.0f, 0.0f); rec[2] = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
+}
+// The validation of cgpt_scene_update_transforms against the uploaded objects and lights, and the records it installs: `records` gets the
+// 3 n transform records, `flags` each object's transform flag (obj_trace; 0 for a bitwise identity).  CGPT_OK, or CGPT_ERR_INVALID with the reason
+// in `error` and the outputs meaningless.  (scene_layout.hip)
+int LayoutTransforms(const float* object_to_world, uint32_t n_objects, const std::vector<DevObject>& objects, const std::vector<uint32_t>& lights,
+                     std::vector<float4>& records, std::vector<uint32_t>& flags, std::string& error);
 
 }  // namespace cgpt

@@ -296,6 +296,34 @@ int LayoutScene(const cgpt_scene_desc& sd, SceneLayout& out, std::string& error)
     // per-object records for the trace kernel's object phase (device_scene.h: obj_trace)
     out.obj_trace.resize(2 * (size_t)sd.n_objects);
     for (uint32_t oi = 0; oi < sd.n_objects; ++oi) PackObjTrace(out.objects[oi], out.obj_trace[2 * (size_t)oi], out.obj_trace[2 * (size_t)oi + 1]);
+    out.obj_xform.resize(3 * (size_t)sd.n_objects);                            // an upload resets every transform to the identity
+    for (uint32_t oi = 0; oi < sd.n_objects; ++oi) IdentityTransformRecords(out.obj_xform.data() + 3 * (size_t)oi);
+    return CGPT_OK;
+}
+
+int LayoutTransforms(const float* object_to_world, uint32_t n_objects, const std::vector<DevObject>& objects, const std::vector<uint32_t>& lights,
+                     std::vector<float4>& records, std::vector<uint32_t>& flags, std::string& error)
+{
+    if (!object_to_world || n_objects != objects.size()) return Refuse(error, CGPT_ERR_INVALID, "expected %zu object-to-world matrices of 12 floats", objects.size());
+    records.resize(3 * (size_t)n_objects);
+    flags.assign(n_objects, 0u);
+    for (uint32_t i = 0; i < n_objects; ++i) {
+        const float* m = object_to_world + 12 * (size_t)i;
+        float4* rec = records.data() + 3 * (size_t)i;
+        if (IsIdentityTransform(m)) { IdentityTransformRecords(rec); continue; }
+        for (int k = 0; k < 12; ++k)
+            if (!std::isfinite(m[k])) return Refuse(error, CGPT_ERR_INVALID, "object %u: transform entry %d is not finite", i, k);
+        if (objects[i].kind != CGPT_OBJECT_MESH && objects[i].kind != CGPT_OBJECT_TRIANGLE)
+            return Refuse(error, CGPT_ERR_INVALID, "object %u is a %s: it takes no transform (cgpt_scene_update_primitive moves it)", i,
+                          objects[i].kind == CGPT_OBJECT_SPHERE ? "sphere" : "plane");
+        for (const uint32_t li : lights)
+            if (li == i) return Refuse(error, CGPT_ERR_INVALID, "object %u is a light: mesh-light sampling reads its object-space triangles and area, so it takes no transform", i);
+        float inv[12];
+        const bool ok = InvertTransform(m, inv);
+        if (ok) for (int r = 0; r < 3; ++r) rec[r] = make_float4(inv[4 * r], inv[4 * r + 1], inv[4 * r + 2], inv[4 * r + 3]);
+        if (!ok) return Refuse(error, CGPT_ERR_INVALID, "object %u: the transform cannot be inverted in float range", i);
+        flags[i] = 1u;
+    }
     return CGPT_OK;
 }
 
@@ -303,7 +331,7 @@ int LayoutScene(const cgpt_scene_desc& sd, SceneLayout& out, std::string& error)
 
 using namespace cgpt;
 
-extern "C" int cgpth_scene_layout(const cgpt_scene_desc* scene, cgpth_scene_layout_view* view)
+extern "C" int cgpth_scene_layout_transformed(const cgpt_scene_desc* scene, const float* object_to_world, uint32_t n_objects, cgpth_scene_layout_view* view)
 {
     // what the view points into: this thread's last layout and the per-object bookkeeping flattened
     struct Storage { SceneLayout layout; std::vector<uint32_t> leaf_base, pair_base, level_begin, level_offsets, level_offsets_start; };
@@ -313,6 +341,14 @@ extern "C" int cgpth_scene_layout(const cgpt_scene_desc* scene, cgpth_scene_layo
         std::string error;
         const int rc = LayoutScene(*scene, st.layout, error);
         if (rc != CGPT_OK) { HostSetError(error.c_str()); return rc; }
+        if (object_to_world || n_objects) {                                    // what cgpt_scene_update_transforms would install after this upload
+            std::vector<uint32_t> flags;
+            const int rt = LayoutTransforms(object_to_world, n_objects, st.layout.objects, st.layout.lights, st.layout.obj_xform, flags, error);
+            if (rt != CGPT_OK) { HostSetError(error.c_str()); return rt; }
+            for (uint32_t i = 0; i < n_objects; ++i) {
+                PackObjTrace(st.layout.objects[i], st.layout.obj_trace[2 * (size_t)i], st.layout.obj_trace[2 * (size_t)i + 1], flags[i]);
+            }
+        }
         const SceneLayout& l = st.layout;
         st.leaf_base.clear(); st.pair_base.clear(); st.level_begin.clear(); st.level_offsets.clear(); st.level_offsets_start.assign(1, 0u);
         for (const RefitObject& ro : l.refit_objects) {
@@ -335,9 +371,15 @@ extern "C" int cgpth_scene_layout(const cgpt_scene_desc* scene, cgpth_scene_layo
         view->leaf_base = st.leaf_base.data(); view->pair_base = st.pair_base.data(); view->level_begin = st.level_begin.data();
         view->level_offsets = st.level_offsets.data(); view->level_offsets_start = st.level_offsets_start.data();
         view->tri_normal12 = f4(l.tri_normal12); view->n_tri_normal12 = l.tri_normal12.size();
+        view->obj_xform = f4(l.obj_xform); view->n_obj_xform = l.obj_xform.size();
         return CGPT_OK;
     } catch (const std::exception& e) {
         HostSetError(e.what());
         return CGPT_ERR_INVALID;
     }
+}
+
+extern "C" int cgpth_scene_layout(const cgpt_scene_desc* scene, cgpth_scene_layout_view* view)
+{
+    return cgpth_scene_layout_transformed(scene, nullptr, 0u, view);
 }

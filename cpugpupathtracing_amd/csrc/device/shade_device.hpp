@@ -45,13 +45,37 @@ __device__ __forceinline__ V3 smooth_normal(V3 p0, V3 p1, V3 p2, V3 n0, V3 n1, V
 // normal is its own record's (TriangleNormal, ref: Primitives.cpp:308-321): ray.tri may be left over from an earlier mesh's hit.
 // SMOOTH: the scene has an object with DevObject.smooth set (cgpt_scene_update_smooth_normals); a hit on such a mesh or triangle object
 // gets smooth_normal() above.  The instantiations without it read neither the flag nor the {n1, n2} records: the code they had.
-template <bool COUNT, bool SMOOTH = false>
+// XFORM: the scene has an object with the transform flag set (cgpt_scene_update_transforms; rt_device.hpp: has_xform).  The hit position stays o + d t of the world ray.
+// The flat normal of a hit on such an object is xform_normal(n0) = normalize(Ainv^T n0) (an untransformed object's v0.normal is still passed
+// through unnormalised); with the smooth flag, smooth_normal runs in object space -- P' = o' + d' t, direction d', which keeps its side
+// tests' meaning: dot(d', n') = dot(d, Ainv^T n') -- and its result is mapped the same way.
+template <bool COUNT, bool SMOOTH = false, bool XFORM = false>
 __device__ __forceinline__ Hit get_hit(const DevScene& sc, const Ray& ray, Counters& cnt)
 {
     Hit h;
     h.pos = ray.o + ray.d * ray.t;
     const DevObject& obj = sc.objects[ray.obj];
-    if (obj.kind == 0u || obj.kind == CGPT_OBJECT_TRIANGLE) {
+    if (XFORM && (obj.kind == 0u || obj.kind == CGPT_OBJECT_TRIANGLE) && has_xform(sc, ray.obj)) {
+        const Xform x = load_xform(sc, ray.obj);
+        const uint32_t t = obj.tri_base + (obj.kind == 0u ? ray.tri : 0u);
+        const float4 n = sc.tri_normal[t];
+        V3 no = mk(n.x, n.y, n.z);
+        if (SMOOTH && obj.smooth != 0u) {
+            const float4* pair = sc.tri_normal + sc.n_tris_total + 2u * (size_t)t;
+            const float4 a = pair[0], b = pair[1];
+            const bool same = __float_as_uint(a.x) == __float_as_uint(n.x) && __float_as_uint(a.y) == __float_as_uint(n.y) && __float_as_uint(a.z) == __float_as_uint(n.z) &&
+                              __float_as_uint(b.x) == __float_as_uint(n.x) && __float_as_uint(b.y) == __float_as_uint(n.y) && __float_as_uint(b.z) == __float_as_uint(n.z);
+            if (!same) {
+                V3 oo, od;
+                xform_ray(x, ray.o, ray.d, oo, od);
+                const float4* rec = sc.tri_orig + 3u * (size_t)t;
+                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
+                no = smooth_normal(mk(r0.x, r0.y, r0.z), mk(r1.x, r1.y, r1.z), mk(r2.x, r2.y, r2.z), no, mk(a.x, a.y, a.z), mk(b.x, b.y, b.z), oo + od * ray.t, od);
+            }
+        }
+        h.normal = xform_normal(x, no);
+        if (COUNT) cnt.hits += obj.kind == 0u ? 1u : 0u;
+    } else if (obj.kind == 0u || obj.kind == CGPT_OBJECT_TRIANGLE) {
         const uint32_t t = obj.tri_base + (obj.kind == 0u ? ray.tri : 0u);
         const float4 n = sc.tri_normal[t];
         h.normal = mk(n.x, n.y, n.z);
@@ -274,7 +298,8 @@ enum : uint32_t { kBounceChainShift = 4u, kChainReflect = 1u, kChainRefract = 2u
 // ref: Main.cpp:452-463).  Emissive energy is added here; the final debug-view overrides are applied by the caller.
 // GLOSSY: 0 no rough lobe (the mirror-only code); 1 the scene has a material with roughness > 0 (ggx_sample); 2 it has one with a
 // transmission roughness > 0 (rough_glass_sample; this instantiation carries the rough specular lobe too); 3 it has an object with smooth
-// normals (get_hit's SMOOTH; carries both rough lobes, so the tables grow by one level and not by a factor of two -- DESIGN.md 5.14).
+// normals (get_hit's SMOOTH; carries both rough lobes, so the tables grow by one level and not by a factor of two -- DESIGN.md 5.14); 4 it has
+// an object with a transform (get_hit's XFORM and the trace side's; level 3 plus transforms -- DESIGN.md 5.16).
 // RIS: the NEE light sample is the survivor of M = st.nee > 1 candidates (resampled importance sampling); the
 // instantiations without it keep the one-sample code.
 template <bool COUNT, int GLOSSY = 0, bool RIS = false>
@@ -287,7 +312,7 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
     }
     if (ray.obj == kNoHit) return kBounceTerminate;                           // ref: Main.cpp:415-416
 
-    const Hit hit = get_hit<COUNT, (GLOSSY >= 3)>(sc, ray, cnt);
+    const Hit hit = get_hit<COUNT, (GLOSSY >= 3), (GLOSSY >= 4)>(sc, ray, cnt);
     const Mat mat = load_material(sc, hit.mat);
     if (mat.is_light) {                                                       // ref: Main.cpp:424-431
         if (!st.nee || ps.depth == 0 || ps.is_specular) {
@@ -428,7 +453,7 @@ __device__ __forceinline__ uint32_t brute_bounce(const DevScene& sc, const DevSe
         return kBruteLeaf;
     }
     if (ray.obj == kNoHit) { leaf = mk(0.0f); return kBruteLeaf; }            // ref: Main.cpp:600-601
-    const Hit hit = get_hit<COUNT, (GLOSSY >= 3)>(sc, ray, cnt);
+    const Hit hit = get_hit<COUNT, (GLOSSY >= 3), (GLOSSY >= 4)>(sc, ray, cnt);
     const Mat mat = load_material(sc, hit.mat);
     if (mat.is_light) { leaf = mat.emissive * mat.intensity; return kBruteLeaf; }   // ref: Main.cpp:606-609
 

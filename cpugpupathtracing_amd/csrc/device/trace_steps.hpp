@@ -9,6 +9,11 @@
 // the stack top unconditionally (it only counts when the stack pointer moves), and the entry below the stack pointer is read
 // next to the node, so a pop is a select.  The rare cases -- an axis-parallel ray in the wave (the NaN-exact slab test, SURVEY
 // A-18) or a stack deeper than the LDS part -- take a general step with the same results.
+// XFORM (every step's last template parameter): the scene has an object with a transform (cgpt_scene_update_transforms).
+// A lane then also keeps its ray's world origin and direction (Trav.wo, wd); object_step() begins every mesh with the ray that mesh is
+// walked with -- the object-space form (rt_device.hpp: xform_ray) for a transformed mesh, the world ray for the others -- so in these
+// instantiations EVERY object boundary goes through object_step(): the fold that sends a finishing lane straight to the next mesh's root
+// (next_object_code) is off.  The instantiations without it are the code they were.
 // ref: Source/BVH.cpp:61-127 (Traverse), Source/Main.cpp:299-316 (IntersectScene).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -298,6 +303,8 @@ struct Trav {                 // one lane's ray in flight
     uint32_t cur_obj, code, sp;
     uint32_t fast_levels;     // stack depths at which this ray may take the branch-free inner step: kLdsStackLevels, or 0 for an axis-parallel
                               // direction (NaN-exact slab test) -- one compare per step decides between the two forms of the step
+    V3 wo, wd;                // XFORM instantiations only: the ray's world origin and direction, while d / rs may hold a transformed mesh's object-space
+                              // ray (never read, and so never kept in a register, in the others)
     // Bit 31 of `depth` = "any hit": a shadow ray, whose caller only asks whether ANYTHING was hit (ref: Main.cpp:454-463), so the ray may
     // stop at its first hit; the counting kernels walk on to the end, as the reference does, to keep its step counts.  (The flag shares
     // the register of a count that never comes near 2^31; the steps only ever add to it.)
@@ -307,14 +314,26 @@ __device__ __forceinline__ bool trav_any_hit(const Trav& r) { return (int32_t)r.
 __device__ __forceinline__ uint32_t trav_depth(const Trav& r) { return r.depth & ~kAnyHitBit; }
 __device__ __forceinline__ V3 trav_origin(const Trav& r) { return mk(r.rs.oxy.x, r.rs.oxy.y, r.rs.ozi.x); }
 
+// the lane's ray as the scene sees it: in the XFORM instantiations d / rs may hold a transformed mesh's object-space ray instead
+template <bool XFORM> __device__ __forceinline__ V3 trav_world_origin(const Trav& r) { return XFORM ? r.wo : trav_origin(r); }
+template <bool XFORM> __device__ __forceinline__ V3 trav_world_dir(const Trav& r) { return XFORM ? r.wd : r.d; }
+
 // a fresh IntersectScene call for this lane (Ray ctor, ref: Primitives.h:64)
-__device__ __forceinline__ void trav_start(const TravCtx& c, Trav& r, V3 o, V3 d, float t, uint32_t obj, uint32_t tri, uint32_t depth)
+// the ray (o, d) as the steps walk it: d, 1 / d as the slab operands, and the axis-parallel decision
+__device__ __forceinline__ void trav_set_ray(Trav& r, V3 o, V3 d)
 {
     const V3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-    r.d = d; r.t = t; r.obj = obj; r.tri = tri; r.depth = depth;
+    r.d = d;
     r.fast_levels = has_infinite_component(inv) ? 0u : kLdsStackLevels;
     r.rs = make_ray_slab(o, inv);
-    r.cur_obj = 0; r.code = c.first_code; r.sp = 0;
+}
+template <bool XFORM = false>
+__device__ __forceinline__ void trav_start(const TravCtx& c, Trav& r, V3 o, V3 d, float t, uint32_t obj, uint32_t tri, uint32_t depth)
+{
+    r.t = t; r.obj = obj; r.tri = tri; r.depth = depth;
+    if (XFORM) { r.wo = o; r.wd = d; }                                        // d / rs keep the last walked ray: object_step sets them for the first mesh
+    else trav_set_ray(r, o, d);
+    r.cur_obj = 0; r.code = XFORM ? kStartObject : c.first_code; r.sp = 0;   // XFORM: object 0 may be transformed -- the object step begins it
 }
 
 __device__ __forceinline__ void load_pair_lds(const lds_u32* top_cache, uint32_t code, NodePair& n)
@@ -342,9 +361,10 @@ __device__ __forceinline__ LeafTri load_leaf_tri_lds(const lds_u32* tri_cache, u
 
 // Traversal code a lane continues with when the object it is in ends: the root of object cur_obj + 1 if that is a mesh,
 // otherwise kStartObject (analytic primitive or end of the list: the object step takes over).
+template <bool XFORM = false>
 __device__ __forceinline__ uint32_t next_object_code(const TravCtx& c, uint32_t cur_obj)
 {
-    if (!c.tab) return kStartObject;
+    if (XFORM || !c.tab) return kStartObject;                                 // XFORM: the next mesh may want its own ray, and this one may have to give the world's back
     return c.objtab[(cur_obj + 1u) * 8u + 7u];                               // word 7: trav_setup; entry n_objects is the end marker
 }
 
@@ -369,7 +389,7 @@ __device__ __forceinline__ uint32_t stack_peek_any(const TravCtx& c, uint32_t co
 }
 
 // ---- inner step: both children, near one first (ref: BVH.cpp:93-123); for the lanes with r.code < kStartObject ---------------
-template <bool COUNT>
+template <bool COUNT, bool XFORM = false>
 __device__ __forceinline__ void inner_step(const TravCtx& c, Trav& r, Counters& cnt)
 {
     const DevScene& sc = *c.sc;
@@ -382,7 +402,7 @@ __device__ __forceinline__ void inner_step(const TravCtx& c, Trav& r, Counters& 
     if (!general) {
         // the entry below the stack pointer, read next to the node (LDS is faster): a pop is then a select
         const uint32_t top = c.stack[(r.sp - (r.sp != 0u ? 1u : 0u)) * kTraceBlock];   // unused when sp == 0
-        const uint32_t next_code = next_object_code(c, r.cur_obj);            // used when this object ends here
+        const uint32_t next_code = next_object_code<XFORM>(c, r.cur_obj);     // used when this object ends here
         slab_pair(n, r.rs, r.t, false, left_dist, right_dist);
         const bool swap = left_dist > right_dist;                             // ref: BVH.cpp:101-105
         const uint32_t near_code = swap ? n.rcode : n.lcode, far_code = swap ? n.lcode : n.rcode;
@@ -415,7 +435,7 @@ __device__ __forceinline__ void inner_step(const TravCtx& c, Trav& r, Counters& 
 }
 
 // ---- leaf step: one triangle of the leaf (ref: BVH.cpp:74-90); for the lanes with bit 31 of r.code set ------------------------
-template <bool COUNT, bool ANY_HIT = true>                                    // ANY_HIT false: the caller's rays never carry the any-hit flag (round 0)
+template <bool COUNT, bool ANY_HIT = true, bool XFORM = false>                // ANY_HIT false: the caller's rays never carry the any-hit flag (round 0)
 __device__ __forceinline__ void leaf_step(const TravCtx& c, Trav& r, Counters& cnt)
 {
     LeafTri lt;
@@ -425,7 +445,7 @@ __device__ __forceinline__ void leaf_step(const TravCtx& c, Trav& r, Counters& c
     else lt = load_leaf_tri(c.sc->tri_leaf, leaf_index);
     if (__builtin_amdgcn_ballot_w64(r.sp > kLdsStackLevels) == 0ull) top = c.stack[(r.sp - (r.sp != 0u ? 1u : 0u)) * kTraceBlock];
     else top = stack_peek_any(c, r.sp);
-    next_code = next_object_code(c, r.cur_obj);
+    next_code = next_object_code<XFORM>(c, r.cur_obj);
     if (COUNT) cnt.tris += c.sc->objects[r.cur_obj].kind == CGPT_OBJECT_TRIANGLE ? 0u : 1u;   // BVH.cpp:76-77 only: a triangle object is no mesh
     float t_hit;
     const bool hit = intersect_triangle_flags(lt.v0, lt.e1, lt.e2, trav_origin(r), r.d, r.t, t_hit);
@@ -448,7 +468,7 @@ __device__ __forceinline__ void leaf_step(const TravCtx& c, Trav& r, Counters& c
 // one record fetch and ~50 instructions per step instead of a vote, and the results are the voted steps' bit for bit (same slab test,
 // same triangle arithmetic -- intersect_triangle's early returns leave the same t as the flag form, rt_device.hpp).
 // Returns with r.code == kStartObject (the lane's ray is at an analytic object or at the end of the object list).
-template <bool COUNT, bool ANY_HIT = true>
+template <bool COUNT, bool ANY_HIT = true, bool XFORM = false>
 __device__ __forceinline__ void lean_traverse(const TravCtx& c, Trav& r, Counters& cnt)
 {
     const DevScene& sc = *c.sc;
@@ -469,7 +489,7 @@ __device__ __forceinline__ void lean_traverse(const TravCtx& c, Trav& r, Counter
                 ++i;
             }
             if (occluded) { r.code = kStartObject; r.cur_obj = sc.n_objects; r.sp = 0u; break; }
-            if (r.sp == 0u) { r.code = next_object_code(c, r.cur_obj); r.cur_obj++; }
+            if (r.sp == 0u) { r.code = next_object_code<XFORM>(c, r.cur_obj); r.cur_obj++; }
             else { r.code = stack_peek_any(c, r.sp); --r.sp; }
             continue;
         }
@@ -485,7 +505,7 @@ __device__ __forceinline__ void lean_traverse(const TravCtx& c, Trav& r, Counter
             const uint32_t tc = left_code; left_code = right_code; right_code = tc;
         }
         if (left_dist == 1e30f) {                                             // ref: BVH.cpp:108-114
-            if (r.sp == 0u) { r.code = next_object_code(c, r.cur_obj); r.cur_obj++; }
+            if (r.sp == 0u) { r.code = next_object_code<XFORM>(c, r.cur_obj); r.cur_obj++; }
             else { r.code = stack_peek_any(c, r.sp); --r.sp; }
         } else {                                                              // ref: BVH.cpp:115-123
             r.depth++;
@@ -500,11 +520,15 @@ __device__ __forceinline__ void lean_traverse(const TravCtx& c, Trav& r, Counter
 //      (IntersectScene's loop, ref: Main.cpp:303-315); for the lanes with r.code == kStartObject.
 // Returns true when the scene's object list is exhausted for this lane: the ray is done and the caller runs its epilogue
 // (r.code is left at kStartObject).  Otherwise the lane continues inside a mesh.
-template <bool COUNT, bool ANY_HIT = true>
+// XFORM: the analytic primitives are tested against the lane's world ray (r.wo, r.wd).  A mesh is begun with the ray it is walked with --
+// its own (o', d') when its obj_trace record carries the transform flag, else the world ray -- and d, 1 / d and the axis-parallel decision
+// are set from it, in one place, when its bits differ from what the lane carries (a lane that comes out of a transformed mesh still
+// carries that mesh's ray).  A finished lane may therefore hold an object-space ray: the caller's epilogue reads trav_world_origin / _dir.
+template <bool COUNT, bool ANY_HIT = true, bool XFORM = false>
 __device__ __forceinline__ bool object_step(const TravCtx& c, Trav& r, Counters& cnt)
 {
     const DevScene& sc = *c.sc;
-    const V3 o = trav_origin(r);
+    const V3 o = trav_world_origin<XFORM>(r), d = trav_world_dir<XFORM>(r);
     for (;;) {
         float4 q0, q1;
         if (c.tab) {
@@ -517,10 +541,20 @@ __device__ __forceinline__ bool object_step(const TravCtx& c, Trav& r, Counters&
         }
         const uint32_t kind = __float_as_uint(q0.x);
         if (kind == kKindEnd) return true;                                    // no object left: the ray is done
-        if (kind == 0u) { r.code = __float_as_uint(q0.y); r.sp = 0u; return false; }
+        if (kind == 0u) {
+            if (XFORM) {
+                V3 oo = o, od = d;
+                if (__float_as_uint(q0.z) != 0u) xform_ray(load_xform(sc, r.cur_obj), o, d, oo, od);   // a transformed mesh: walked with (o', d')
+                const V3 co = trav_origin(r);
+                const bool same = __float_as_uint(co.x) == __float_as_uint(oo.x) && __float_as_uint(co.y) == __float_as_uint(oo.y) && __float_as_uint(co.z) == __float_as_uint(oo.z) &&
+                                  __float_as_uint(r.d.x) == __float_as_uint(od.x) && __float_as_uint(r.d.y) == __float_as_uint(od.y) && __float_as_uint(r.d.z) == __float_as_uint(od.z);
+                if (!same) trav_set_ray(r, oo, od);                           // equal bits: nothing to set, 1 / d included
+            }
+            r.code = __float_as_uint(q0.y); r.sp = 0u; return false;
+        }
         bool hit;
-        if (kind == 1u) hit = intersect_sphere(mk(q0.y, q0.z, q0.w), q1.x, o, r.d, r.t);
-        else hit = intersect_plane(mk(q0.y, q0.z, q0.w), mk(q1.x, q1.y, q1.z), o, r.d, r.t);
+        if (kind == 1u) hit = intersect_sphere(mk(q0.y, q0.z, q0.w), q1.x, o, d, r.t);
+        else hit = intersect_plane(mk(q0.y, q0.z, q0.w), mk(q1.x, q1.y, q1.z), o, d, r.t);
         if (hit) r.obj = r.cur_obj;
         if (!COUNT && ANY_HIT && trav_any_hit(r) && hit) return true;
         r.cur_obj++;

@@ -139,7 +139,9 @@ __device__ __forceinline__ uint32_t elect_chain_leader(const WfDev& wf, uint32_t
 // The traversal states, their voted steps and the LDS layout are in trace_steps.hpp.
 
 // FIRST (round 0) is a separate instantiation so the later rounds carry neither its code nor its registers.
-template <bool COUNT, bool FIRST>
+// XFORM: the scene has an object with a transform (trace_steps.hpp: the lane also keeps its world ray, six registers that only these
+// instantiations carry).
+template <bool COUNT, bool FIRST, bool XFORM = false>
 __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs args, const WfDev wf, uint32_t batch_first, const TraceTune tune)
 {
     constexpr bool first_round = FIRST;
@@ -161,6 +163,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
     Trav r;
     r.d = mk(0.0f); r.rs = make_ray_slab(r.d, r.d); r.t = 0.0f;
     r.obj = kNoHit; r.tri = 0; r.depth = 0; r.cur_obj = 0; r.code = kIdle; r.sp = 0; r.fast_levels = kLdsStackLevels;
+    if (XFORM) { r.wo = mk(0.0f); r.wd = mk(0.0f); trav_set_ray(r, r.wo, r.wd); }   // d, 1 / d and the slab operands of one ray, as object_step keeps them
     uint32_t slot_of_lane = 0;
     uint32_t wave_rays = 0;                                                   // wave-uniform: rays this wave started (later rounds)
     uint32_t wave_followers = 0;                                              // wave-uniform: of those, followers of a specular chain (not traced)
@@ -243,7 +246,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
                     }
                 }
                 if (ok) {
-                    trav_start(ctx, r, o, d, t, obj, tri, depth);
+                    trav_start<XFORM>(ctx, r, o, d, t, obj, tri, depth);
                     if (!first_round && tune.shadow_any_hit != 0u && slot >= wf.cap) r.depth |= kAnyHitBit;
                     if (first_round) cnt.rays++;                              // later rounds: every id of the lists is a ray, counted per wave below
                 }
@@ -273,22 +276,22 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
             // loop (the reference's own control flow, trace_steps.hpp: lean_traverse -- ~50 instructions per node instead of ~75 and no
             // votes), then takes the object step.  Same results, same counters.
             if (FIRST && tune.first_lean) {
-                if (r.code < kStartObject || (int32_t)r.code < 0) lean_traverse<COUNT, !FIRST>(ctx, r, cnt);
-                if (r.code == kStartObject && object_step<COUNT, !FIRST>(ctx, r, cnt)) finish_ray();
+                if (r.code < kStartObject || (int32_t)r.code < 0) lean_traverse<COUNT, !FIRST, XFORM>(ctx, r, cnt);
+                if (r.code == kStartObject && object_step<COUNT, !FIRST, XFORM>(ctx, r, cnt)) finish_ray();
                 continue;
             }
 
             if (n_inner >= n_leaf && n_inner >= w_obj) {
                 do {
-                    if (r.code < kStartObject) inner_step<COUNT>(ctx, r, cnt);
+                    if (r.code < kStartObject) inner_step<COUNT, XFORM>(ctx, r, cnt);
                 } while ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64(r.code < kStartObject)) >= tune.inner_repeat);
             } else if (n_leaf >= w_obj) {
                 do {
-                    if ((int32_t)r.code < 0) leaf_step<COUNT, !FIRST>(ctx, r, cnt);
+                    if ((int32_t)r.code < 0) leaf_step<COUNT, !FIRST, XFORM>(ctx, r, cnt);
                 } while ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64((int32_t)r.code < 0)) >= tune.leaf_repeat);
             } else {
                 do {
-                    if (r.code == kStartObject && object_step<COUNT, !FIRST>(ctx, r, cnt)) finish_ray();
+                    if (r.code == kStartObject && object_step<COUNT, !FIRST, XFORM>(ctx, r, cnt)) finish_ray();
                 } while ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64(r.code == kStartObject)) >= tune.obj_repeat);
             }
         }
@@ -707,16 +710,17 @@ static uint32_t CoprimeRotation(uint32_t n_waves, uint32_t n_tiles)
     return 0u;
 }
 
-// every instantiation: trace [COUNT][FIRST], shade [RIS][GLOSSY][COUNT][FIRST][BRUTE]
-static decltype(&wf_trace<false, false>) const kTraceKernels[2][2] = {
-    { wf_trace<false, false>, wf_trace<false, true> }, { wf_trace<true, false>, wf_trace<true, true> },
+// every instantiation: trace [XFORM][COUNT][FIRST], shade [RIS][GLOSSY][COUNT][FIRST][BRUTE]
+static decltype(&wf_trace<false, false>) const kTraceKernels[2][2][2] = {
+    { { wf_trace<false, false>, wf_trace<false, true> }, { wf_trace<true, false>, wf_trace<true, true> } },
+    { { wf_trace<false, false, true>, wf_trace<false, true, true> }, { wf_trace<true, false, true>, wf_trace<true, true, true> } },
 };
 #define CGPT_SHADE_LEVEL(G, R) \
     { { { wf_shade<false, false, false, G, R>, wf_shade<false, false, true, G, R> }, { wf_shade<false, true, false, G, R>, wf_shade<false, true, true, G, R> } }, \
       { { wf_shade<true, false, false, G, R>, wf_shade<true, false, true, G, R> }, { wf_shade<true, true, false, G, R>, wf_shade<true, true, true, G, R> } } }
-static decltype(&wf_shade<false, false>) const kShadeKernels[2][4][2][2][2] = {
-    { CGPT_SHADE_LEVEL(0, false), CGPT_SHADE_LEVEL(1, false), CGPT_SHADE_LEVEL(2, false), CGPT_SHADE_LEVEL(3, false) },
-    { CGPT_SHADE_LEVEL(0, true), CGPT_SHADE_LEVEL(1, true), CGPT_SHADE_LEVEL(2, true), CGPT_SHADE_LEVEL(3, true) },
+static decltype(&wf_shade<false, false>) const kShadeKernels[2][5][2][2][2] = {
+    { CGPT_SHADE_LEVEL(0, false), CGPT_SHADE_LEVEL(1, false), CGPT_SHADE_LEVEL(2, false), CGPT_SHADE_LEVEL(3, false), CGPT_SHADE_LEVEL(4, false) },
+    { CGPT_SHADE_LEVEL(0, true), CGPT_SHADE_LEVEL(1, true), CGPT_SHADE_LEVEL(2, true), CGPT_SHADE_LEVEL(3, true), CGPT_SHADE_LEVEL(4, true) },
 };
 #undef CGPT_SHADE_LEVEL
 
@@ -769,7 +773,8 @@ struct WfHost {
     uint32_t held_pools = 0;
     uint32_t spec_epoch[kMaxPools] = {};         // last epoch used in each pool's spec_tab
     uint32_t n_cus = 0;
-    uint32_t trace_blocks_per_cu[2][2] = {}, shade_blocks_per_cu[2][4][2][2] = {};   // trace: [COUNT][FIRST]; shade: [RIS][GLOSSY][COUNT][BRUTE]
+    uint32_t trace_blocks_per_cu[2][2][2] = {}, shade_blocks_per_cu[2][5][2][2] = {};   // trace: [XFORM][COUNT][FIRST]; shade: [RIS][GLOSSY][COUNT][BRUTE]
+    bool last_xform = false;                     // the last render ran the XFORM trace kernels (WavefrontTraceWavesPerSimd)
     size_t occupancy_lds = 0;
     // hipEvent pairs around every trace launch of the last render (roofline accounting: the dominant kernel's own duration)
     EventPairs trace_ev;
@@ -804,7 +809,7 @@ uint32_t WavefrontTraceWavesPerSimd(void* state)
 {
     if (!state) return 0;
     const WfHost* h = static_cast<const WfHost*>(state);
-    return std::min(h->tune.max_trace_blocks, h->trace_blocks_per_cu[0][0]) * (kTraceBlock / 256u);
+    return std::min(h->tune.max_trace_blocks, h->trace_blocks_per_cu[h->last_xform][0][0]) * (kTraceBlock / 256u);
 }
 
 // Sum of the trace launches' durations of the last render (and the round-0 launches' share); call after the render's device work has completed.
@@ -883,19 +888,21 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
     const size_t trace_lds = trace_lds_bytes(top_records);
     // persistent grids = the resident capacity of the chip for each kernel
     if (h->occupancy_lds != trace_lds) {
-        LAUNCH_TRY(QueryOccupancy(&kTraceKernels[0][0], &h->trace_blocks_per_cu[0][0], 4, kTraceBlock, trace_lds));
+        LAUNCH_TRY(QueryOccupancy(&kTraceKernels[0][0][0], &h->trace_blocks_per_cu[0][0][0], 8, kTraceBlock, trace_lds));
         // shade: the round-0 and later-round instantiations share one grid size (one output segment per wave)
-        uint32_t shade[2][4][2][2][2];
-        LAUNCH_TRY(QueryOccupancy(&kShadeKernels[0][0][0][0][0], &shade[0][0][0][0][0], 64, 256, 0));
+        uint32_t shade[2][5][2][2][2];
+        LAUNCH_TRY(QueryOccupancy(&kShadeKernels[0][0][0][0][0], &shade[0][0][0][0][0], 80, 256, 0));
         for (int r = 0; r < 2; ++r)
-            for (int g = 0; g < 4; ++g)
+            for (int g = 0; g < 5; ++g)
                 for (int c = 0; c < 2; ++c)
                     for (int b = 0; b < 2; ++b) h->shade_blocks_per_cu[r][g][c][b] = std::min(shade[r][g][c][0][b], shade[r][g][c][1][b]);
         h->occupancy_lds = trace_lds;
     }
     const dim3 block(256);
-    const dim3 trace_grid_first(n_cus * std::min(h->tune.max_trace_blocks, h->trace_blocks_per_cu[count][1]));
-    const dim3 trace_grid_later(n_cus * std::min(h->tune.max_trace_blocks, h->trace_blocks_per_cu[count][0]));
+    const bool xform = v.lobe_level >= 4u;                                    // the scene has a transformed object: the XFORM trace kernels
+    h->last_xform = xform;
+    const dim3 trace_grid_first(n_cus * std::min(h->tune.max_trace_blocks, h->trace_blocks_per_cu[xform][count][1]));
+    const dim3 trace_grid_later(n_cus * std::min(h->tune.max_trace_blocks, h->trace_blocks_per_cu[xform][count][0]));
     const bool brute = args_in.settings.render_mode != 2u;                    // the render has TracePath paths (ref: Main.cpp:719-729)
     const uint32_t brute_levels = brute ? (uint32_t)args_in.settings.max_ray_depth + 1u : 0u;
     const uint32_t (&shade_blocks)[2][2] = h->shade_blocks_per_cu[v.ris][v.lobe_level];   // every lobe level's shade kernels, with and without RIS, have grids of their own
@@ -905,7 +912,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
     const uint32_t min_shade_waves = n_cus * std::min({ shade_blocks[0][0], shade_blocks[1][0], shade_blocks[0][1], shade_blocks[1][1] }) * 4u;
 
     // deep end of the traversal stacks: one dword per level beyond the LDS part and per thread of the largest trace grid
-    const uint32_t max_trace_threads = n_cus * std::max({ h->trace_blocks_per_cu[0][0], h->trace_blocks_per_cu[0][1], h->trace_blocks_per_cu[1][0], h->trace_blocks_per_cu[1][1] }) * kTraceBlock;
+    const uint32_t max_trace_threads = n_cus * *std::max_element(&h->trace_blocks_per_cu[0][0][0], &h->trace_blocks_per_cu[0][0][0] + 8) * kTraceBlock;
     const uint32_t deep_levels = args_in.scene.stack_depth > kLdsStackLevels ? args_in.scene.stack_depth - kLdsStackLevels : 0u;
     const uint32_t overflow_words = std::max(1u, deep_levels * max_trace_threads);
 
@@ -995,13 +1002,14 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
         wf.retire_misses = h->tune.retire_misses && args_in.settings.debug_mode == 0u ? 1u : 0u;
         if (!chains) wf.spec_tab = nullptr;
         wf.spec_keys = h->tune.spec_keys;
-        wf.probe = h->tune.probe && !count && args_in.settings.debug_mode == 0u && args_in.scene.n_objects <= h->tune.probe_max_objects ? 1u : 0u;
+        // (probe_scene tests mesh roots against the world ray: with a transformed object in the scene the probe is off)
+        wf.probe = h->tune.probe && !count && !xform && args_in.settings.debug_mode == 0u && args_in.scene.n_objects <= h->tune.probe_max_objects ? 1u : 0u;
         // segments of waves that a smaller shade grid does not launch must read as empty
         if (k < n_pools) LAUNCH_TRY(hipMemsetAsync(wf.seg_count, 0, 2 * (size_t)kMaxBands * wf.n_segs * sizeof(uint32_t), st));
         for (uint32_t r = 0; r < rounds; ++r) {
             const bool first = r == 0u;
             if (h->tune.trace_events) LAUNCH_TRY(hipEventRecord(NextEvent(h->trace_ev), st));
-            hipLaunchKernelGGL(kTraceKernels[count][first], first ? trace_grid_first : trace_grid_later, dim3(kTraceBlock), trace_lds, st, args, wf, bfirst, tt);
+            hipLaunchKernelGGL(kTraceKernels[xform][count][first], first ? trace_grid_first : trace_grid_later, dim3(kTraceBlock), trace_lds, st, args, wf, bfirst, tt);
             if (h->tune.trace_events) LAUNCH_TRY(hipEventRecord(NextEvent(h->trace_ev), st));
             ++launches;
             if (r + 1u < rounds) {

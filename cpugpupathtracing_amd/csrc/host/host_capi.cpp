@@ -10,6 +10,7 @@
 #include "image_io.h"
 #include "mesh_gen.h"
 #include "scene.h"
+#include "transform_math.h"
 
 using namespace cgpt;
 
@@ -290,6 +291,11 @@ int cgpth_scene_add_triangle(cgpth_scene* scene, const cgpt_triangle* triangle, 
     });
 }
 
+static const char* KindName(const Object& o)
+{
+    return o.has_bvh ? "mesh" : o.kind == CGPT_OBJECT_SPHERE ? "sphere" : o.kind == CGPT_OBJECT_PLANE ? "plane" : "triangle object";
+}
+
 int cgpth_scene_add_light(cgpth_scene* scene, uint32_t obj_index)
 {
     return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
@@ -298,6 +304,7 @@ int cgpth_scene_add_light(cgpth_scene* scene, uint32_t obj_index)
         // ref: Main.cpp:371-384: only meshes and sphere primitives can be sampled, anything else EXCEPTs
         if (!o.has_bvh && o.kind != CGPT_OBJECT_SPHERE) { g_error = "only meshes and spheres can be light sources"; return CGPT_ERR_UNSUPPORTED; }
         if (o.smooth) return Fail("object " + std::to_string(obj_index) + " has smooth normals: a light's sampled normal is v0.normal");
+        if (!IsIdentityTransform(o.transform)) return Fail("object " + std::to_string(obj_index) + " has a transform: a light is sampled in object space");
         scene->scene.light_source_indices.push_back(obj_index);
         return CGPT_OK;
     });
@@ -324,6 +331,36 @@ int cgpth_scene_get_smooth_normals(const cgpth_scene* scene, uint32_t* out, uint
         if (!scene || !out) return Fail("null argument");
         if (n != scene->scene.objects.size()) return Fail("expected " + std::to_string(scene->scene.objects.size()) + " values, got " + std::to_string(n));
         for (uint32_t i = 0; i < n; ++i) out[i] = scene->scene.objects[i].smooth ? 1u : 0u;
+        return CGPT_OK;
+    });
+}
+
+int cgpth_scene_set_transform(cgpth_scene* scene, uint32_t obj_index, const float object_to_world[12])
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        if (!scene || !object_to_world) return Fail("null argument");
+        if (obj_index >= scene->scene.objects.size())
+            return Fail("object " + std::to_string(obj_index) + " out of range (" + std::to_string(scene->scene.objects.size()) + " objects)");
+        Object& o = scene->scene.objects[obj_index];
+        if (!IsIdentityTransform(object_to_world)) {
+            float inverse[12];
+            if (!InvertTransform(object_to_world, inverse)) return Fail("object " + std::to_string(obj_index) + ": the transform is not finite or cannot be inverted in float range");
+            if (!o.has_bvh && o.kind != CGPT_OBJECT_TRIANGLE)
+                return Fail("object " + std::to_string(obj_index) + " is a " + KindName(o) + ": it takes no transform (update_primitive moves it)");
+            for (const uint32_t li : scene->scene.light_source_indices)
+                if (li == obj_index) return Fail("object " + std::to_string(obj_index) + " is a light: it is sampled in object space, so it takes no transform");
+        }
+        memcpy(o.transform, object_to_world, sizeof(o.transform));
+        return CGPT_OK;
+    });
+}
+
+int cgpth_scene_get_transforms(const cgpth_scene* scene, float* out, uint32_t n)
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        if (!scene || !out) return Fail("null argument");
+        if (n != scene->scene.objects.size()) return Fail("expected " + std::to_string(scene->scene.objects.size()) + " matrices, got " + std::to_string(n));
+        for (uint32_t i = 0; i < n; ++i) memcpy(out + 12 * (size_t)i, scene->scene.objects[i].transform, sizeof(float) * 12);
         return CGPT_OK;
     });
 }
@@ -360,11 +397,6 @@ int cgpth_scene_rebuild_bvh(cgpth_scene* scene, uint32_t obj_index, int build_op
             return Fail("the binned build needs finite positions of magnitude <= 1e30 (the BVH is unchanged)");
         return CGPT_OK;
     });
-}
-
-static const char* KindName(const Object& o)
-{
-    return o.has_bvh ? "mesh" : o.kind == CGPT_OBJECT_SPHERE ? "sphere" : o.kind == CGPT_OBJECT_PLANE ? "plane" : "triangle object";
 }
 
 int cgpth_scene_refit_mesh(cgpth_scene* scene, uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris)

@@ -83,6 +83,7 @@ struct Object {  // ref: Main.cpp:245-275
     Plane plane;
     cgpt_triangle triangle{};
     bool smooth = false;      // interpolated vertex normals (cgpt_scene_update_smooth_normals); not part of cgpt_object
+    float transform[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };   // object-to-world rows of [A | b] (cgpt_scene_update_transforms); not part of cgpt_object
 };
 
 struct Settings {  // ref: Main.cpp:228-235

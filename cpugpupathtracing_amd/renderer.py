@@ -14,6 +14,15 @@ from . import _native as N
 from .scene import Scene, Settings, _triangle_ptr, _triangle_rows, primitive_abi
 
 
+_IDENTITY = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float32)
+
+
+def _all_identity(matrices) -> bool:
+    """Every matrix is the identity bit for bit (-0 is not 0): what cgpt_scene_update_transforms calls untransformed."""
+    v = np.ascontiguousarray(matrices, np.float32).reshape(-1, 12)
+    return bool(np.array_equal(v.view(np.uint32), np.broadcast_to(_IDENTITY.view(np.uint32), v.shape)))
+
+
 class DeviceError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"[cgpt status {code}] {message}")
@@ -44,6 +53,7 @@ class Renderer:
         self._rough_glass = False     # the device holds a transmission roughness > 0 (cgpt_scene_update_transmission_roughness)
         self._nee_candidates = 1      # cgpt_set_nee_candidates
         self._smooth = False          # the device holds a smooth-normal flag (cgpt_scene_update_smooth_normals)
+        self._transformed = False     # the device holds a transform that is not the identity (cgpt_scene_update_transforms)
 
     def _check(self, rc: int):
         if rc != 0:
@@ -65,10 +75,11 @@ class Renderer:
 
     def upload(self, scene: Scene):
         """cgpt_scene_upload, then the scene's roughness (cgpt_scene_update_roughness), transmission roughness
-        (cgpt_scene_update_transmission_roughness) and smooth-normal flags (cgpt_scene_update_smooth_normals) when any is nonzero."""
+        (cgpt_scene_update_transmission_roughness) and smooth-normal flags (cgpt_scene_update_smooth_normals) when any is nonzero, and
+        its transforms (cgpt_scene_update_transforms) when any is not the identity."""
         desc = scene.flatten()
         self._check(self.L.cgpt_scene_upload(self._ctx, C.byref(desc)))
-        self._glossy = self._rough_glass = self._smooth = False      # the upload reset every roughness and smooth-normal flag to 0
+        self._glossy = self._rough_glass = self._smooth = self._transformed = False   # the upload reset every roughness, flag and transform
         self.scene = scene
         self._node_counts = [desc.objects[k].node_count for k in range(desc.n_objects)]   # the uploaded trees (export_bvh)
         rough = scene.roughness(desc.n_materials)
@@ -80,6 +91,9 @@ class Renderer:
         smooth = scene.smooth_normals(desc.n_objects)
         if smooth.any():
             self.update_smooth_normals(smooth)
+        transforms = scene.transforms(desc.n_objects)
+        if not _all_identity(transforms):
+            self.update_transforms(transforms)
 
     def update_materials(self, scene: Scene):
         """cgpt_scene_update_materials, then each of the scene's two roughnesses when it or the device's is nonzero."""
@@ -112,6 +126,14 @@ class Renderer:
         v = np.ascontiguousarray(flags, np.uint32).ravel()
         self._check(self.L.cgpt_scene_update_smooth_normals(self._ctx, v.ctypes.data_as(C.POINTER(C.c_uint32)), v.size))
         self._smooth = bool(v.any())
+
+    def update_transforms(self, matrices):
+        """cgpt_scene_update_transforms: one object-to-world matrix per uploaded object, (n, 3, 4) or (n, 12) float32, the rows of
+        [A | b].  Meshes and triangle objects; spheres, planes and lights take the identity only.  Only the device copy
+        changes; call reset_accumulator() before the next frame."""
+        v = np.ascontiguousarray(matrices, np.float32).reshape(-1, 12)
+        self._check(self.L.cgpt_scene_update_transforms(self._ctx, v.ctypes.data_as(C.POINTER(C.c_float)), v.shape[0]))
+        self._transformed = not _all_identity(v)
 
     def refit_mesh(self, obj_index: int, triangles) -> float:
         """BVH refit on the device (cgpt_scene_refit_mesh): new triangles for uploaded mesh `obj_index` (or triangle object), in its

@@ -261,10 +261,24 @@ class Scene:
         _host_check(N.lib().cgpth_scene_get_smooth_normals(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), n), "get_smooth_normals")
         return out
 
-    def add_mesh(self, mesh: Mesh, mat_index: int, build_option: int = N.BUILD_SAH_INTERVALS, device_builder=None, smooth: bool = False) -> int:
+    def set_transform(self, obj_index: int, m):
+        """The object-to-world matrix of object `obj_index` (cgpth_scene_set_transform): 12 floats, the rows of [A | b]
+        (a 3x4 array), so that world = A p + b.  Meshes and triangle objects; a sphere, a plane or a light takes the identity only."""
+        v = np.ascontiguousarray(m, np.float32).reshape(12)
+        _host_check(N.lib().cgpth_scene_set_transform(self._h, obj_index, v.ctypes.data_as(C.POINTER(C.c_float))), "set_transform")
+
+    def transforms(self, n_objects=None) -> np.ndarray:
+        """Every object's object-to-world matrix, float32 (n, 3, 4) (cgpth_scene_get_transforms)."""
+        n = self.flatten().n_objects if n_objects is None else n_objects
+        out = np.zeros((n, 3, 4), np.float32)
+        _host_check(N.lib().cgpth_scene_get_transforms(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), n), "get_transforms")
+        return out
+
+    def add_mesh(self, mesh: Mesh, mat_index: int, build_option: int = N.BUILD_SAH_INTERVALS, device_builder=None, smooth: bool = False,
+                 transform=None) -> int:
         """Object ctor (ref: Main.cpp:247-251).  device_builder: a Renderer whose GPU builds the (bit-identical) tree, any option.
         build_option: BUILD_NAIVE, BUILD_SAH_INTERVALS (the reference's default), BUILD_SAH_PRIMITIVES or BUILD_SAH_BINNED.
-        smooth: shade with interpolated vertex normals (set_smooth_normals)."""
+        smooth: shade with interpolated vertex normals (set_smooth_normals).  transform: the object-to-world matrix (set_transform)."""
         if device_builder is not None:
             rc = N.lib().cgpth_scene_add_mesh_device_built_ex(self._h, mesh._h, mat_index, device_builder._ctx, build_option)
         else:
@@ -273,6 +287,8 @@ class Scene:
             raise HostError(N.lib().cgpth_last_error().decode())
         if smooth:
             self.set_smooth_normals(rc, True)
+        if transform is not None:
+            self.set_transform(rc, transform)
         return rc
 
     def add_sphere(self, center, radius: float, mat_index: int) -> int:

@@ -4,7 +4,7 @@
 //
 //   g++ -std=c++17 -Iinclude -Icpugpupathtracing_amd/csrc/host examples/render_main.cpp
 //       -Lcpugpupathtracing_amd/lib -lcpugpupt -Wl,-rpath,$PWD/cpugpupathtracing_amd/lib -o render_main   (one command line)
-//   ./render_main [--gpus N [--collective]] [--denoise] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--smooth] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
+//   ./render_main [--gpus N [--collective]] [--denoise] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--smooth] [--mesh-transform m00 .. m23] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
 // --gpus N: ONE context over the first N GPUs of the node (cgpt_ctx_create with n_devices = N): every frame is spread over them in
 // interleaved row bands and the read-back gathers the float4 bands with one RCCL exchange over xGMI; the loop below does not
 // change.  --collective: take that code path with N = 1 too (what a one-GPU box can test).
@@ -22,6 +22,8 @@
 // set before the upload: it is context state; 1, the default, is the reference's single sample).
 // --smooth: smooth shading -- every mesh object that is not a light shades with its interpolated vertex normals
 // (cgpt_scene_update_smooth_normals after the upload; without it the reference's flat v0.normal).
+// --mesh-transform m00 m01 m02 m03 m10 .. m23: the mesh (object 0, the dragon or its stand-in) is placed by this object-to-world matrix, the
+// rows of [A | b] with world = A p + b (cgpt_scene_update_transforms after the upload); the other objects keep the identity.
 // move_at > 0 scripts the input half of Update(dt) (ref: Main.cpp:277-297, Camera::Update :104-131): after that many samples the
 // camera is translated by (right, up, forward) as the A/D, Space/Shift, W/S keys would, the view changes, and the accumulator
 // is reset (ref: ResetAccumulator, Main.cpp:238-243) before the remaining samples are rendered from the new position.
@@ -48,12 +50,17 @@ using namespace cgpt;
 int main(int argc, char** argv)
 {
     int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false;
+    bool has_transform = false; float mesh_transform[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
     MeshBVH::BuildOption bvh_option = MeshBVH::BuildOption_SAHSplitIntervals;
     while (argc > 1 && std::string(argv[1]).rfind("--", 0) == 0) {
         if (std::string(argv[1]) == "--gpus" && argc > 2) { n_gpus = atoi(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--collective") { ctx_flags |= CGPT_CTX_FORCE_COLLECTIVE; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--denoise") { denoise = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--smooth") { smooth = true; argv += 1; argc -= 1; }
+        else if (std::string(argv[1]) == "--mesh-transform" && argc > 13) {
+            for (int k = 0; k < 12; ++k) mesh_transform[k] = (float)atof(argv[2 + k]);
+            has_transform = true; argv += 13; argc -= 13;
+        }
         else if (std::string(argv[1]) == "--ground-roughness" && argc > 2) { ground_roughness = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--glass-roughness" && argc > 2) { glass_roughness = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--nee-candidates" && argc > 2) { nee_candidates = (uint32_t)atoi(argv[2]); argv += 2; argc -= 2; }
@@ -101,6 +108,12 @@ int main(int argc, char** argv)
         for (const Object& o : scene.objects) flags.push_back(o.has_bvh ? 1u : 0u);
         for (const uint32_t li : scene.light_source_indices) flags[li] = 0u;
         CHECK(cgpt_scene_update_smooth_normals(ctx, flags.data(), (uint32_t)flags.size()));
+    }
+    if (has_transform) {                                                 // nor are the transforms
+        std::vector<float> matrices;
+        for (const Object& o : scene.objects) matrices.insert(matrices.end(), o.transform, o.transform + 12);
+        for (int k = 0; k < 12; ++k) matrices[k] = mesh_transform[k];    // object 0: the mesh
+        CHECK(cgpt_scene_update_transforms(ctx, matrices.data(), (uint32_t)scene.objects.size()));
     }
 
     const cgpt_settings settings = scene.AbiSettings();

@@ -31,7 +31,8 @@ extern "C" {
                                  value only; the rough dielectric lobe added one new symbol
                                  (cgpt_scene_update_transmission_roughness) only; resampled light sampling added one new symbol
                                  only (cgpt_set_nee_candidates); smooth shading added one new symbol only
-                                 (cgpt_scene_update_smooth_normals) */
+                                 (cgpt_scene_update_smooth_normals); per-object transforms added one new symbol only
+                                 (cgpt_scene_update_transforms) */
 
 enum cgpt_status {
     CGPT_OK = 0,
@@ -236,6 +237,25 @@ int cgpt_scene_update_transmission_roughness(cgpt_ctx* ctx, const float* transmi
  * disagree).  The caller resets the accumulator.  The denoiser's cached guides are recomputed: they hold the normal.  A HIP failure
  * during the write drops the scene; a multi-device context updates every device. */
 int cgpt_scene_update_smooth_normals(cgpt_ctx* ctx, const uint32_t* smooth, uint32_t n_objects);
+/* Per-object transforms: 12 floats per uploaded object, the rows of [A | b], row-major, so that world = A p + b for a point p of the
+ * object's uploaded (object-space) geometry.  Every trace and shade path honours it: a ray (o, d, t) enters a transformed mesh or
+ * stand-alone triangle object as o' = A^-1 o - A^-1 b, d' = A^-1 d (d' is not renormalised, so t is the same number in both spaces),
+ * the hit position stays o + d t of the world ray and the shading normal is normalize(A^-T n) (tests/transform_ref.py
+ * states the operations).  An object whose 12 floats are bitwise the identity (1,0,0,0, 0,1,0,0, 0,0,1,0) is untransformed and is walked
+ * exactly as without this call; with every object untransformed the renders run the kernels they ran before, bit for bit.  Mirrors
+ * (det < 0) and non-uniform scale are allowed.  The reference's absolute determinant epsilon of the triangle test applies to the
+ * object-space numbers, so scaling an object by its transform moves it.
+ * cgpt_scene_upload resets every object to the identity; the material, roughness, transmission-roughness, smooth-normal, refit and
+ * primitive edits keep the transforms.  cgpt_scene_refit_mesh takes object-space triangles (the result sits at A (new triangles) + b),
+ * cgpt_scene_export_bvh returns object-space bounds, cgpt_intersect_rays takes world rays and returns world t.
+ * Refused before any device write, with nothing changed: no scene (CGPT_ERR_NO_SCENE); object_to_world NULL or n_objects other than the
+ * uploaded count; an entry that is not finite; an A that cannot be inverted -- the inverse is computed in double from the float entries,
+ * and det == 0, a det that is not finite, or an entry of A^-1 or of -A^-1 b that is not finite once rounded to float refuses; anything
+ * but the identity on a sphere or a plane (cgpt_scene_update_primitive moves those) or on an object listed in light_indices (mesh-light
+ * sampling reads the object-space triangles and area) -- all CGPT_ERR_INVALID.  The caller resets the accumulator.  The denoiser's cached
+ * guides are recomputed: they hold position and normal.  A HIP failure during the write drops the scene; a multi-device context updates
+ * every device. */
+int cgpt_scene_update_transforms(cgpt_ctx* ctx, const float* object_to_world, uint32_t n_objects);
 
 /* ---- in-place geometry edits of the uploaded scene (no re-upload; the caller resets the accumulator, as with the materials) ----
  * Every call validates before its first device write: a refused call leaves the device scene as it was.  If a HIP call fails after

@@ -71,13 +71,20 @@ int cgpth_scene_add_plane(cgpth_scene* scene, const float normal[3], const float
 /* a stand-alone triangle object, Primitive(const Triangle&) (ref: Include/Primitives.h:84-89); returns object index.  It has no BVH
  * (bvh_info / bvh_export / rebuild_bvh refuse it) and cannot be a light (the reference EXCEPTs, Main.cpp:383) */
 int cgpth_scene_add_triangle(cgpth_scene* scene, const cgpt_triangle* triangle, uint32_t mat_index);
-int cgpth_scene_add_light(cgpth_scene* scene, uint32_t obj_index);                            /* ref: Main.cpp:817; refuses an object with smooth normals */
+int cgpth_scene_add_light(cgpth_scene* scene, uint32_t obj_index);                            /* ref: Main.cpp:817; refuses an object with smooth normals or a transform */
 /* smooth shading of object `obj_index` (cgpt_scene_update_smooth_normals holds the meaning): flag 0 or 1, a new object has 0.  Refused
  * with CGPT_ERR_INVALID and nothing changed: a bad index, a flag that is neither 0 nor 1, a 1 on a light.  Spheres and planes keep the
  * flag and ignore it.  Not part of cgpt_scene_desc: a host uploads the scene, then hands get_smooth_normals's values to the device */
 int cgpth_scene_set_smooth_normals(cgpth_scene* scene, uint32_t obj_index, uint32_t flag);
 /* out: n values, n == the scene's object count */
 int cgpth_scene_get_smooth_normals(const cgpth_scene* scene, uint32_t* out, uint32_t n);
+/* the object-to-world matrix of object `obj_index` (cgpt_scene_update_transforms holds the meaning): 12 floats, the rows of [A | b]; a new
+ * object has the identity.  Refused with CGPT_ERR_INVALID and nothing changed, as the device call refuses: a bad index, an entry that is
+ * not finite, an A that cannot be inverted, and anything but the bitwise identity on a sphere, a plane or a light.  Not part of
+ * cgpt_scene_desc: a host uploads the scene, then hands get_transforms's values to the device */
+int cgpth_scene_set_transform(cgpth_scene* scene, uint32_t obj_index, const float object_to_world[12]);
+/* out: 12 n floats, n == the scene's object count */
+int cgpth_scene_get_transforms(const cgpth_scene* scene, float* out, uint32_t n);
 int cgpth_scene_set_camera(cgpth_scene* scene, const float pos[3], const float view_dir[3], float fov_deg, float aspect);
 int cgpth_scene_set_settings(cgpth_scene* scene, const cgpt_settings* settings);
 int cgpth_scene_rebuild_bvh(cgpth_scene* scene, uint32_t obj_index, int build_option);       /* ref: BVH.cpp:47-59 */
@@ -133,8 +140,14 @@ typedef struct cgpth_scene_layout_view {
     /* the other two vertex normals, {n1.xyz, -}, {n2.xyz, -} per triangle in tri_orig's order (2 float4s a triangle): the device keeps them
      * behind tri_normal's n0 records, in the same allocation */
     const float* tri_normal12; size_t n_tri_normal12;
+    /* the transform records, {Ainv row r, binv_r}, 3 float4s an object: the device keeps them behind obj_trace's 2 n records, in the same
+     * allocation.  The identity after cgpth_scene_layout, as after an upload */
+    const float* obj_xform; size_t n_obj_xform;
 } cgpth_scene_layout_view;
 int cgpth_scene_layout(const cgpt_scene_desc* scene, cgpth_scene_layout_view* out);
+/* the same after a cgpt_scene_update_transforms(object_to_world, n_objects) on that upload, with that call's validation, status and
+ * message: obj_xform holds the inverses, `objects` the xform words and obj_trace the flags the call would install */
+int cgpth_scene_layout_transformed(const cgpt_scene_desc* scene, const float* object_to_world, uint32_t n_objects, cgpth_scene_layout_view* out);
 
 #ifdef __cplusplus
 }
