@@ -114,6 +114,11 @@ class SceneLayoutView(C.Structure):
                 ("obj_xform", _fp), ("n_obj_xform", C.c_size_t)]
 
 
+class TopLevelView(C.Structure):
+    """cgpth_top_level_view: n_nodes records of 8 floats {lo.xyz, bits(skip) | hi.xyz, bits(object)}, n_entry node indices."""
+    _fields_ = [("nodes", _fp), ("n_nodes", C.c_size_t), ("entry", _up), ("n_entry", C.c_size_t)]
+
+
 # name -> (restype, argtypes).  Every symbol declared in include/*.h is listed; tests check the list against the headers.
 PROTOTYPES = {
     # cpugpupt_abi.h
@@ -123,6 +128,7 @@ PROTOTYPES = {
     "cgpt_last_error": (C.c_char_p, [_vp]),
     "cgpt_set_stream": (C.c_int, [_vp, _vp]),
     "cgpt_set_nee_candidates": (C.c_int, [_vp, C.c_uint32]),
+    "cgpt_set_top_level": (C.c_int, [_vp, C.c_uint32]),
     "cgpt_scene_upload": (C.c_int, [_vp, C.POINTER(SceneDesc)]),
     "cgpt_scene_update_materials": (C.c_int, [_vp, C.POINTER(Material), C.c_uint32]),
     "cgpt_scene_update_roughness": (C.c_int, [_vp, _fp, C.c_uint32]),
@@ -200,6 +206,11 @@ PROTOTYPES = {
     "cgpth_fast_div": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "cgpth_scene_layout": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(SceneLayoutView)]),
     "cgpth_scene_layout_transformed": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(C.c_float), C.c_uint32, C.POINTER(SceneLayoutView)]),
+    "cgpth_scene_permute_objects": (C.c_int, [_vp, _up, C.c_uint32]),
+    "cgpth_top_level": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(TopLevelView)]),
+    "cgpth_top_level_transforms": (C.c_int, [C.POINTER(C.c_float), C.c_uint32, C.POINTER(TopLevelView)]),
+    "cgpth_top_level_refit": (C.c_int, [C.c_uint32, C.POINTER(Triangle), C.c_uint32, C.POINTER(TopLevelView)]),
+    "cgpth_top_level_primitive": (C.c_int, [C.c_uint32, C.POINTER(Object), C.POINTER(TopLevelView)]),
 }
 
 # exported for the tests, declared in csrc/device/ctx_internal.h: not part of the ABI that include/*.h declares

@@ -21,7 +21,7 @@
 namespace cgpt {
 hipError_t LaunchMegakernel(const DevRenderArgs& args, ShadeVariant v, hipStream_t stream);                                  // path_kernels.hip
 hipError_t LaunchIntersectRays(const DevScene& sc, const float* origins, const float* dirs, const float* tmax, uint32_t n, float* out_t,
-                               uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, DevCounters* counters, bool xform, hipStream_t stream);
+                               uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, DevCounters* counters, bool xform, bool tree, hipStream_t stream);
 int LaunchWavefront(struct ::cgpt_ctx* ctx, const DevRenderArgs& args, ShadeVariant v);                                     // wavefront_kernels.hip
 void WavefrontFree(void* state);
 void WavefrontCollectTiming(void* state, double* trace_ms, uint32_t* trace_launches, double* round0_ms, uint32_t* round0_launches);
@@ -76,6 +76,7 @@ void FreeScene(cgpt_ctx* ctx)
     ctx->h_objects.clear(); ctx->refit_objects.clear(); ctx->record_perm.clear();
     ctx->h_roughness.clear(); ctx->h_transmission_roughness.clear(); ctx->h_materials.clear(); ctx->lobe_level = 0;
     ctx->any_smooth = false; ctx->any_xform = false; ctx->h_lights.clear();
+    ctx->top_state = TopLevelState{};
     ctx->has_scene = false;
 }
 
@@ -188,8 +189,9 @@ int UpdateSmoothNormals(cgpt_ctx* ctx, const uint32_t* smooth, uint32_t n_object
 int UpdateTransforms(cgpt_ctx* ctx, const float* object_to_world, uint32_t n_objects)
 {
     if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
-    std::vector<float4> trace;                                                 // the whole obj_trace allocation: 2 n records, then 3 n
+    std::vector<float4> trace;                                                 // obj_trace's 2 n records, then the 3 n transform records, then (mode 1) the tree
     bool any = false;
+    TopLevelState top;
     const int rc = Guarded(ctx, "transform update", [&] {
         std::vector<float4> records;
         std::vector<uint32_t> flags;
@@ -201,6 +203,12 @@ int UpdateTransforms(cgpt_ctx* ctx, const float* object_to_world, uint32_t n_obj
             PackObjTrace(ctx->h_objects[i], trace[2 * (size_t)i], trace[2 * (size_t)i + 1], flags[i]);
         }
         std::copy(records.begin(), records.end(), trace.begin() + 2 * (size_t)n_objects);
+        top = ctx->top_state;                                                  // the boxes follow the matrices (in mode 0 too: the mode may be turned on later)
+        top.xform.assign(object_to_world, object_to_world + 12 * (size_t)n_objects);
+        if (ctx->top_level) {                                                  // still one copy: the tree sits right behind
+            const std::vector<float4> tree = PackTopLevel(ctx->h_objects, top);
+            trace.insert(trace.end(), tree.begin(), tree.end());
+        }
         return (int)CGPT_OK;
     });
     if (rc != CGPT_OK) return rc;
@@ -213,11 +221,21 @@ int UpdateTransforms(cgpt_ctx* ctx, const float* object_to_world, uint32_t n_obj
         return CtxFail(ctx, CGPT_ERR_HIP, "hipMemcpy of the transform records failed: %s (the device scene is dropped; upload it again)", hipGetErrorString(e));
     }
     ctx->any_xform = any;
+    ctx->top_state.xform.swap(top.xform);
     UpdateLobeLevel(ctx);
     return CGPT_OK;
 }
 
 }  // namespace
+
+namespace cgpt {
+hipError_t WriteTopLevel(cgpt_ctx* ctx, const std::vector<DevObject>& objects, const TopLevelState& st)
+{
+    if (!ctx->top_level || objects.empty()) return hipSuccess;
+    const std::vector<float4> tree = PackTopLevel(objects, st);
+    return hipMemcpy(ctx->sb.obj_trace.p + 5 * objects.size(), tree.data(), tree.size() * sizeof(float4), hipMemcpyHostToDevice);
+}
+}  // namespace cgpt
 
 extern "C" {
 
@@ -290,6 +308,29 @@ int cgpt_set_nee_candidates(cgpt_ctx* ctx, uint32_t candidates)
     if (candidates < 1u || candidates > 32u) return CtxFail(ctx, CGPT_ERR_INVALID, "nee candidates %u outside [1, 32]", candidates);
     if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupSetNeeCandidates(ctx, candidates); });
     ctx->nee_candidates = candidates;                                          // read by the next render; first hits do not depend on it: the guides stay
+    return CGPT_OK;
+}
+
+int cgpt_set_top_level(cgpt_ctx* ctx, uint32_t mode)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (mode > 1u) return CtxFail(ctx, CGPT_ERR_INVALID, "top-level mode %u is neither 0 (object list) nor 1 (tree)", mode);
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupSetTopLevel(ctx, mode); });
+    if (mode == ctx->top_level) return CGPT_OK;
+    if (mode == 1u && ctx->has_scene) {                                        // the tree becomes active: write it (the edits kept its source current)
+        return Guarded(ctx, __func__, [&] {
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            ctx->top_level = 1u;
+            const hipError_t e = WriteTopLevel(ctx, ctx->h_objects, ctx->top_state);
+            if (e != hipSuccess) {                                             // the records may be half written: drop the scene (refit.hip: SceneLost)
+                ctx->has_scene = false;
+                return CtxFail(ctx, CGPT_ERR_HIP, "hipMemcpy of the top-level tree failed: %s (the device scene is dropped; upload it again)", hipGetErrorString(e));
+            }
+            return (int)CGPT_OK;
+        });
+    }
+    ctx->top_level = mode;                                                     // read by the next render; the image does not depend on it: accumulator and guides stay
     return CGPT_OK;
 }
 
@@ -392,7 +433,8 @@ int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout)
     // obj_trace: the 2 n trace records, then the 3 n transform records (device_scene.h)
     const size_t n_obj = layout.objects.size();
     if (layout.obj_trace.size() != 2 * n_obj || layout.obj_xform.size() != 3 * n_obj) return CtxFail(ctx, CGPT_ERR_INVALID, "layout: %zu trace and %zu transform records for %zu objects", layout.obj_trace.size(), layout.obj_xform.size(), n_obj);
-    HIP_TRY(ctx, ctx->sb.obj_trace.Alloc(n_obj ? 5 * n_obj : 1));
+    if (layout.top_state.local_box.size() != 6 * n_obj || layout.top_state.xform.size() != 12 * n_obj) return CtxFail(ctx, CGPT_ERR_INVALID, "layout: top-level state of %zu objects", layout.top_state.local_box.size() / 6);
+    HIP_TRY(ctx, ctx->sb.obj_trace.Alloc(n_obj ? 5 * n_obj + TopLevelFloat4s(n_obj) : 1));   // ... then the top-level tree (written while cgpt_set_top_level is 1)
     if (n_obj) {
         HIP_TRY(ctx, hipMemcpy(ctx->sb.obj_trace.p, layout.obj_trace.data(), sizeof(float4) * 2 * n_obj, hipMemcpyHostToDevice));
         HIP_TRY(ctx, hipMemcpy(ctx->sb.obj_trace.p + 2 * n_obj, layout.obj_xform.data(), sizeof(float4) * 3 * n_obj, hipMemcpyHostToDevice));
@@ -402,6 +444,8 @@ int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout)
     ctx->h_objects = layout.objects; ctx->refit_objects = layout.refit_objects; ctx->record_perm = layout.record_perm;
     ctx->h_roughness.assign(layout.n_materials, 0.0f); ctx->h_transmission_roughness.assign(layout.n_materials, 0.0f); ctx->h_materials = layout.materials; ctx->lobe_level = 0;
     ctx->any_smooth = false; ctx->any_xform = false; ctx->h_lights = layout.lights;   // an upload resets every smooth-normal flag and transform (LayoutScene writes 0 and the identity)
+    ctx->top_state = layout.top_state;
+    HIP_TRY(ctx, WriteTopLevel(ctx, ctx->h_objects, ctx->top_state));          // the mode is context state: an upload keeps it
 
     ctx->scene.node_pairs = ctx->sb.node_pairs.p; ctx->scene.tri_leaf = ctx->sb.tri_leaf.p; ctx->scene.tri_orig = ctx->sb.tri_orig.p; ctx->scene.tri_normal = ctx->sb.tri_normal.p;
     ctx->scene.materials = ctx->sb.materials.p; ctx->scene.objects = ctx->sb.objects.p; ctx->scene.obj_trace = ctx->sb.obj_trace.p; ctx->scene.lights = ctx->sb.lights.p;
@@ -458,7 +502,7 @@ int RenderEnqueue(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings*
     // The one place where DevSettings.nee is more than a flag: the RIS instantiations read M from it, every other reader tests it for zero
     // (device_scene.h).  With one candidate the word is the caller's flag, untouched, as the parent passed it.
     if (ris) args.settings.nee = ctx->nee_candidates;
-    const ShadeVariant variant = { (p->flags & CGPT_RENDER_COUNTERS) != 0, ctx->lobe_level, ris };
+    const ShadeVariant variant = { (p->flags & CGPT_RENDER_COUNTERS) != 0, ctx->lobe_level, ris, ctx->top_level != 0u };
     // AUTO: all three kernels give bit-identical images, so the choice is speed alone.  MI355X, glass scene, ms per call
     // (profiles/r03/small_calls_table.txt; 16 samples and more: profiles/r02/frame_time_after.txt):
     //                 64x64  1 / 2 / 8 samples     960x540  1 / 2 / 8        1920x1080  1 / 2 / 4 / 8 / 16 / 32 / 64 / 128
@@ -690,7 +734,7 @@ int cgpt_intersect_rays(cgpt_ctx* ctx, const float* origins, const float* dirs, 
     HIP_TRY(ctx, hipMemcpyAsync(d_o.p, origins, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_d.p, dirs, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     if (tmax) HIP_TRY(ctx, hipMemcpyAsync(d_tm.p, tmax, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, LaunchIntersectRays(ctx->scene, d_o.p, d_d.p, d_tm.p, n, d_t.p, d_obj.p, d_tri.p, d_dep.p, ctx->counters.p, ctx->any_xform, ctx->stream));
+    HIP_TRY(ctx, LaunchIntersectRays(ctx->scene, d_o.p, d_d.p, d_tm.p, n, d_t.p, d_obj.p, d_tri.p, d_dep.p, ctx->counters.p, ctx->any_xform, ctx->top_level != 0u, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out_t, d_t.p, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out_obj, d_obj.p, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out_tri, d_tri.p, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));

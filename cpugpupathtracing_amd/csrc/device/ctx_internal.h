@@ -69,6 +69,11 @@ struct cgpt_ctx {
     // cgpt_set_nee_candidates: context state like the stream (an upload keeps it).  A render with more than one candidate, NEE on and
     // TracePathAdvanced paths runs the RIS instantiations of the render kernels
     uint32_t nee_candidates = 1;
+    // cgpt_set_top_level: context state too.  1: the renders, the guides and cgpt_intersect_rays reach the objects through the top-level tree
+    // behind obj_trace's 5 n records (device_scene.h).  top_state is what its boxes are computed from; every edit that moves a box keeps
+    // it current in either mode and rewrites the device tree in mode 1 (WriteTopLevel); turning the mode on writes it
+    uint32_t top_level = 0;
+    cgpt::TopLevelState top_state;
 
     // in-place edits of the uploaded scene (refit.hip): host copies of the objects, each mesh's child-pair records grouped by
     // depth, and where the renumbering put every record
@@ -120,6 +125,9 @@ namespace cgpt {
 // the device half of a scene upload (cgpt_abi.hip): frees the context's scene and installs the arrays and bookkeeping of a layout that
 // LayoutScene (scene_layout.h) accepted; the caller has selected the device and drained the stream
 int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout);
+// the top-level tree of ctx->h_objects with the boxes' source `st`, copied behind obj_trace's 5 n records (a synchronous copy: the caller
+// has selected the device and drained the stream); hipSuccess without a copy while the mode is 0
+hipError_t WriteTopLevel(cgpt_ctx* ctx, const std::vector<DevObject>& objects, const TopLevelState& st);
 // the two halves of cgpt_render: enqueue the kernels of one context without waiting, then wait and book the timings
 int RenderEnqueue(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p);
 int RenderFinish(cgpt_ctx* ctx);
@@ -135,6 +143,7 @@ int GroupUpdateTransmissionRoughness(cgpt_ctx* ctx, const float* roughness, uint
 int GroupUpdateSmoothNormals(cgpt_ctx* ctx, const uint32_t* smooth, uint32_t n);
 int GroupUpdateTransforms(cgpt_ctx* ctx, const float* object_to_world, uint32_t n);
 int GroupSetNeeCandidates(cgpt_ctx* ctx, uint32_t candidates);
+int GroupSetTopLevel(cgpt_ctx* ctx, uint32_t mode);
 int GroupRefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris, float* total_area_out);
 int GroupUpdatePrimitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_object* obj);
 int GroupRender(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p);

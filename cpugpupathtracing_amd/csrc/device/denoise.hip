@@ -47,8 +47,9 @@ __device__ __forceinline__ void tile_pixel(uint32_t width, uint32_t& px, uint32_
 // demodulation albedo (the albedo per channel where it is >= 1e-3 on a hit that is not a light, else 1).
 // SMOOTH: the scene has an object with smooth normals (cgpt_scene_update_smooth_normals): n is get_hit's interpolated normal there.
 // XFORM: it has an object with a transform (cgpt_scene_update_transforms): the trace and the normal honour it (this instantiation carries
-// SMOOTH too, as lobe level 4 does).
-template <bool SMOOTH, bool XFORM = false>
+// SMOOTH too, as lobe level 4 does).  TREE: the trace goes through the top-level tree (cgpt_set_top_level(1)); the same hit, so the cached
+// guides of one mode serve the other.
+template <bool SMOOTH, bool XFORM = false, bool TREE = false>
 __global__ void __launch_bounds__(256) guides_kernel(const DevScene sc, const DevCamera cam, uint32_t width, uint32_t height, uint32_t first_row,
                                                      uint32_t n_rows, float4* __restrict__ guides, float4* __restrict__ demod)
 {
@@ -59,7 +60,7 @@ __global__ void __launch_bounds__(256) guides_kernel(const DevScene sc, const De
     const uint32_t py = first_row + row;
     Ray ray = camera_ray(cam, (float)px * (1.0f / (float)width), (float)py * (1.0f / (float)height));   // primary_ray's u, v
     Counters cnt = { 0, 0, 0, 0, 0 };                                          // not booked: cgpt_stats does not grow
-    intersect_scene<false, XFORM>(sc, ray, stack, blockDim.x, cnt);
+    intersect_scene<false, XFORM, TREE>(sc, ray, stack, blockDim.x, cnt);
     float4 g0 = make_float4(0.0f, 0.0f, 0.0f, 1e34f);
     float4 g1 = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kNoHit));
     float4 g2 = g1;
@@ -233,7 +234,9 @@ int EnsureGuides(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera)
     memcpy(&cam, camera, sizeof(cam));
     const uint32_t tiles = ((f.width + kTile - 1u) / kTile) * ((f.n_rows + kTile - 1u) / kTile);
     const size_t lds = (size_t)d->scene.stack_depth * 256u * sizeof(uint32_t);   // intersect_rays_kernel's stack
-    if (d->any_xform) hipLaunchKernelGGL((guides_kernel<true, true>), dim3(tiles), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
+    if (d->top_level) hipLaunchKernelGGL((guides_kernel<true, true, true>), dim3(tiles), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
+                                         d->dn.guides.p, d->dn.guide_demod.p);
+    else if (d->any_xform) hipLaunchKernelGGL((guides_kernel<true, true>), dim3(tiles), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
                                          d->dn.guides.p, d->dn.guide_demod.p);
     else if (d->any_smooth) hipLaunchKernelGGL(guides_kernel<true>, dim3(tiles), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
                                           d->dn.guides.p, d->dn.guide_demod.p);

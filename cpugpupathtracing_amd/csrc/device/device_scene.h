@@ -49,6 +49,11 @@
 //                                   Everything else of a transformed mesh -- tree, triangles, normals, total_area -- stays in object space.
 //                                   The reference's absolute determinant epsilon (|a| < 0.001 in intersect_triangle, SURVEY A-9) is therefore
 //                                   applied to object-space numbers: scaling an object by its transform moves the epsilon with it.
+//  obj_trace   float4[2 (2 n - 1)]  behind those: the top-level tree (cgpt_set_top_level; tests/tlas_ref.py), nodes in preorder,
+//   (tree)      + n + 1 words       {lo.xyz, bits(skip) | hi.xyz, bits(object or 0xFFFFFFFF)}: a padded world box, the first node behind the node's
+//                                   subtree, a leaf's object index; then entry[j] = the highest node whose range starts at object j
+//                                   (entry[n] = 2 n - 1), padded to whole float4s.  Written while the mode is 1, read only by the TREE
+//                                   instantiations (rt_device.hpp: tree_nodes / tree_entry).
 //
 // record order: a child-pair record's index is only a name (the codes inside the records and the root codes are the only
 // references to it), so the upload renumbers them: records [0, n_top_records) are the top levels of all meshes' trees in

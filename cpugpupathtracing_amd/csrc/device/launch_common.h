@@ -17,7 +17,9 @@ namespace cgpt {
 
 // Which instantiation of its render kernels a launcher runs: with the counters of cgpt_stats, the lobe level (ctx_internal.h: GLOSSY) and
 // resampled NEE (shade_device.hpp, above shade_bounce).  The render mode and the call's size pick the rest inside the launcher.
-struct ShadeVariant { bool count; uint32_t lobe_level; bool ris; };
+struct ShadeVariant { bool count; uint32_t lobe_level; bool ris; bool tree; };   // tree: cgpt_set_top_level(1) -- the megakernel and the persistent kernel run level kTreeLevels + lobe_level, the wavefront pipeline its TREE trace kernels
+static constexpr uint32_t kTreeLevels = 5;  // the render kernels' level parameter G >= kTreeLevels: lobe level G - kTreeLevels with the objects reached through the top-level tree
+static inline uint32_t KernelLevel(ShadeVariant v) { return v.tree ? kTreeLevels + v.lobe_level : v.lobe_level; }
 
 // a HIP call of a launcher: on failure the context's error names the call (as HIP_TRY's does) and the launcher returns -1
 #define LAUNCH_TRY(expr)                                                     \

@@ -396,6 +396,13 @@ int GroupSetNeeCandidates(cgpt_ctx* ctx, uint32_t candidates)              // th
     return CGPT_OK;
 }
 
+int GroupSetTopLevel(cgpt_ctx* ctx, uint32_t mode)                          // the value was checked; a member fails only on a HIP error, which drops its scene
+{
+    for (cgpt_ctx* m : ctx->group->members) { const int rc = cgpt_set_top_level(m, mode); if (rc != CGPT_OK) return Propagate(ctx, m, rc); }
+    ctx->top_level = mode;
+    return CGPT_OK;
+}
+
 int GroupRender(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p)
 {
     DeviceGroup* g = ctx->group;

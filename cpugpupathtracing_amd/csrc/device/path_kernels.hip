@@ -28,10 +28,13 @@ extern __shared__ uint32_t lds_stack[];
 // Block shape: 256 threads = a 16x16-pixel tile (the reference's job size, ref: Main.cpp:705-711), or -- one-sample calls -- 64 threads =
 // one 8x8 tile per single-wave block: the wave's slot and its LDS are free the moment its own longest path ends instead of its block's,
 // and the dispatcher places single waves (1080p, one sample: 1.71 -> 1.68 ms, profiles/r03/one_sample.md).
-// GLOSSY (the lobe level) and RIS: shade_device.hpp, above shade_bounce.
-template <bool COUNT, bool BRUTE, int GLOSSY, bool RIS>
+// GLOSSY (the lobe level) and RIS: shade_device.hpp, above shade_bounce.  LEVEL: the lobe level, or kTreeLevels + the lobe level with the
+// objects reached through the top-level tree (cgpt_set_top_level(1)).
+template <bool COUNT, bool BRUTE, int LEVEL, bool RIS>
 __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
 {
+    constexpr bool TREE = LEVEL >= (int)kTreeLevels;
+    constexpr int GLOSSY = TREE ? LEVEL - (int)kTreeLevels : LEVEL;
     const DevScene& sc = args.scene;
     uint32_t* const stack = lds_stack + threadIdx.x;
     const uint32_t stride = blockDim.x;
@@ -80,7 +83,7 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
 
             // ---- one ray per iteration: the extend ray or the pending shadow ray ----
             Ray cur = shadow_kind ? sray : ray;
-            intersect_scene<COUNT, (GLOSSY >= 4)>(sc, cur, stack, stride, cnt);
+            intersect_scene<COUNT, (GLOSSY >= 4), TREE>(sc, cur, stack, stride, cnt);
 
             bool finalize;
             if (BRUTE && use_brute) {
@@ -138,13 +141,13 @@ static uint32_t MegakernelBlockThreads(const DevRenderArgs& args)
     return args.n_samples == 1u ? 64u : 256u;
 }
 
-// every instantiation, [RIS][COUNT][BRUTE][GLOSSY]
+// every instantiation, [RIS][COUNT][BRUTE][LEVEL]: the lobe levels 0-4, then the same five through the top-level tree
 #define CGPT_MEGAKERNELS(R) \
-    { { { megakernel<false, false, 0, R>, megakernel<false, false, 1, R>, megakernel<false, false, 2, R>, megakernel<false, false, 3, R>, megakernel<false, false, 4, R> },     \
-        { megakernel<false, true, 0, R>, megakernel<false, true, 1, R>, megakernel<false, true, 2, R>, megakernel<false, true, 3, R>, megakernel<false, true, 4, R> } },         \
-      { { megakernel<true, false, 0, R>, megakernel<true, false, 1, R>, megakernel<true, false, 2, R>, megakernel<true, false, 3, R>, megakernel<true, false, 4, R> },         \
-        { megakernel<true, true, 0, R>, megakernel<true, true, 1, R>, megakernel<true, true, 2, R>, megakernel<true, true, 3, R>, megakernel<true, true, 4, R> } } }
-static decltype(&megakernel<false, false, 0, false>) const kMegakernels[2][2][2][5] = { CGPT_MEGAKERNELS(false), CGPT_MEGAKERNELS(true) };
+    { { { megakernel<false, false, 0, R>, megakernel<false, false, 1, R>, megakernel<false, false, 2, R>, megakernel<false, false, 3, R>, megakernel<false, false, 4, R>, megakernel<false, false, 5, R>, megakernel<false, false, 6, R>, megakernel<false, false, 7, R>, megakernel<false, false, 8, R>, megakernel<false, false, 9, R> },     \
+        { megakernel<false, true, 0, R>, megakernel<false, true, 1, R>, megakernel<false, true, 2, R>, megakernel<false, true, 3, R>, megakernel<false, true, 4, R>, megakernel<false, true, 5, R>, megakernel<false, true, 6, R>, megakernel<false, true, 7, R>, megakernel<false, true, 8, R>, megakernel<false, true, 9, R> } },         \
+      { { megakernel<true, false, 0, R>, megakernel<true, false, 1, R>, megakernel<true, false, 2, R>, megakernel<true, false, 3, R>, megakernel<true, false, 4, R>, megakernel<true, false, 5, R>, megakernel<true, false, 6, R>, megakernel<true, false, 7, R>, megakernel<true, false, 8, R>, megakernel<true, false, 9, R> },         \
+        { megakernel<true, true, 0, R>, megakernel<true, true, 1, R>, megakernel<true, true, 2, R>, megakernel<true, true, 3, R>, megakernel<true, true, 4, R>, megakernel<true, true, 5, R>, megakernel<true, true, 6, R>, megakernel<true, true, 7, R>, megakernel<true, true, 8, R>, megakernel<true, true, 9, R> } } }
+static decltype(&megakernel<false, false, 0, false>) const kMegakernels[2][2][2][10] = { CGPT_MEGAKERNELS(false), CGPT_MEGAKERNELS(true) };
 #undef CGPT_MEGAKERNELS
 
 hipError_t LaunchMegakernel(const DevRenderArgs& args, ShadeVariant v, hipStream_t stream)
@@ -155,7 +158,7 @@ hipError_t LaunchMegakernel(const DevRenderArgs& args, ShadeVariant v, hipStream
     const uint32_t tiles_x = (args.width + edge - 1u) / edge, tiles_y = (args.n_rows + edge - 1u) / edge;
     const dim3 grid(tiles_x * tiles_y), block(bt);
     const size_t lds = (size_t)args.scene.stack_depth * bt * sizeof(uint32_t);
-    hipLaunchKernelGGL(kMegakernels[v.ris][v.count][brute][v.lobe_level], grid, block, lds, stream, args);
+    hipLaunchKernelGGL(kMegakernels[v.ris][v.count][brute][KernelLevel(v)], grid, block, lds, stream, args);
     return hipGetLastError();
 }
 
@@ -164,7 +167,7 @@ uint32_t MegakernelWavesPerSimd(const DevRenderArgs& args, ShadeVariant v)
     int b = 0;
     const uint32_t bt = MegakernelBlockThreads(args);
     const size_t lds = (size_t)args.scene.stack_depth * bt * sizeof(uint32_t);
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kMegakernels[v.ris][0][args.settings.render_mode != 2u][v.lobe_level], (int)bt, lds);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kMegakernels[v.ris][0][args.settings.render_mode != 2u][KernelLevel(v)], (int)bt, lds);
     return e == hipSuccess && b > 0 ? std::max(1u, (uint32_t)b * bt / 256u) : 1u;    // blocks per CU -> waves per SIMD (4 SIMDs)
 }
 
@@ -187,7 +190,7 @@ hipError_t LaunchPackPixels(const float4* accumulator, uint32_t* pixels, size_t 
 
 // IntersectScene on a batch of rays (ref: Main.cpp:299-316).  XFORM: the scene has a transformed object (rt_device.hpp: intersect_scene);
 // the rays and the returned t are the world's either way
-template <bool XFORM>
+template <bool XFORM, bool TREE = false>
 __global__ void __launch_bounds__(256) intersect_rays_kernel(const DevScene sc, const float* __restrict__ origins,
                                                              const float* __restrict__ dirs, const float* __restrict__ tmax,
                                                              uint32_t n, float* __restrict__ out_t, uint32_t* __restrict__ out_obj,
@@ -199,7 +202,7 @@ __global__ void __launch_bounds__(256) intersect_rays_kernel(const DevScene sc, 
     Counters cnt = { 0, 0, 0, 0, 0 };
     if (i < n) {
         Ray ray = make_ray(mk(origins + 3 * (size_t)i), mk(dirs + 3 * (size_t)i), tmax ? tmax[i] : 1e34f);
-        intersect_scene<true, XFORM>(sc, ray, stack, blockDim.x, cnt);
+        intersect_scene<true, XFORM, TREE>(sc, ray, stack, blockDim.x, cnt);
         out_t[i] = ray.t; out_obj[i] = ray.obj; out_tri[i] = ray.tri; out_depth[i] = ray.bvh_depth;
     }
     wave_add_u64(&counters->traced_rays, cnt.rays);
@@ -209,10 +212,11 @@ __global__ void __launch_bounds__(256) intersect_rays_kernel(const DevScene sc, 
 }
 
 hipError_t LaunchIntersectRays(const DevScene& sc, const float* origins, const float* dirs, const float* tmax, uint32_t n, float* out_t,
-                               uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, DevCounters* counters, bool xform, hipStream_t stream)
+                               uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, DevCounters* counters, bool xform, bool tree, hipStream_t stream)
 {
     const size_t lds = (size_t)sc.stack_depth * 256 * sizeof(uint32_t);
-    hipLaunchKernelGGL(xform ? intersect_rays_kernel<true> : intersect_rays_kernel<false>, dim3((n + 255u) / 256u), dim3(256), lds, stream, sc, origins, dirs, tmax, n, out_t, out_obj,
+    const auto kernel = tree ? intersect_rays_kernel<true, true> : (xform ? intersect_rays_kernel<true> : intersect_rays_kernel<false>);   // the tree: one instantiation, transforms honoured
+    hipLaunchKernelGGL(kernel, dim3((n + 255u) / 256u), dim3(256), lds, stream, sc, origins, dirs, tmax, n, out_t, out_obj,
                        out_tri, out_depth, counters);
     return hipGetLastError();
 }

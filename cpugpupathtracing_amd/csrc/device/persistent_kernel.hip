@@ -64,11 +64,15 @@ enum : uint32_t {                      // per-lane path flags
 // Main.cpp:702,825-942), which are mostly drain: once nothing is left to fetch, a wave with few busy lanes runs their rays in the lean
 // per-lane loop (trace_steps.hpp: lean_traverse) instead of voted steps, because the call ends when its longest chain does (1080p, one
 // sample: 2.47 -> 2.21 ms).  Kept out of the throughput instantiations, which it costs registers and SGPR spills (profiles/r03/one_sample.md).
-// GLOSSY (the lobe level) and RIS: shade_device.hpp, above shade_bounce.
-template <bool COUNT, bool BRUTE, bool TAIL, int GLOSSY, bool RIS>
+// GLOSSY (the lobe level) and RIS: shade_device.hpp, above shade_bounce.  LEVEL: the lobe level, or kTreeLevels + the lobe level with the
+// objects reached through the top-level tree (cgpt_set_top_level(1)).
+template <bool COUNT, bool BRUTE, bool TAIL, int LEVEL, bool RIS>
 __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderArgs args, const PtDev pt, uint32_t batch_first, const TraceTune tune)
 {
+    constexpr bool TREE = LEVEL >= (int)kTreeLevels;                          // the objects are reached through the top-level tree, at the scene's own lobe level
+    constexpr int GLOSSY = TREE ? LEVEL - (int)kTreeLevels : LEVEL;
     constexpr bool XFORM = GLOSSY >= 4;                                       // the scene has a transformed object (trace_steps.hpp)
+    constexpr bool STEP = XFORM || TREE;
     const DevScene& sc = args.scene;
     const DevSettings& st = args.settings;
     const uint32_t grid_threads = gridDim.x * kTraceBlock;
@@ -106,7 +110,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
             if (pf & kPfDead) {
                 finish_path(en);
             } else {
-                trav_start<XFORM>(ctx, r, park_o, park_d, park_t, park_obj, park_tri, park_depth);
+                trav_start<XFORM, TREE>(ctx, r, park_o, park_d, park_t, park_obj, park_tri, park_depth);
                 cnt.rays++;
             }
         } else if (r.obj == kNoHit && !(BRUTE && (pf & kPfBrute)) && !(st.debug_mode == 2u && (pf & kPfDepthMask) == 0u)) {
@@ -135,7 +139,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
             if (done) {
                 finish_path(L);
             } else {
-                trav_start<XFORM>(ctx, r, ray.o, ray.d, ray.t, ray.obj, ray.tri, ray.bvh_depth);
+                trav_start<XFORM, TREE>(ctx, r, ray.o, ray.d, ray.t, ray.obj, ray.tri, ray.bvh_depth);
                 cnt.rays++;
             }
         } else {
@@ -151,10 +155,10 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
                 pending = pend;
                 pf |= kPfShadow | (dead ? kPfDead : 0u);
                 park_o = ray.o; park_d = ray.d; park_t = ray.t; park_obj = ray.obj; park_tri = ray.tri; park_depth = ray.bvh_depth;
-                trav_start<XFORM>(ctx, r, shadow.o, shadow.d, shadow.t, kNoHit, 0u, 0u);
+                trav_start<XFORM, TREE>(ctx, r, shadow.o, shadow.d, shadow.t, kNoHit, 0u, 0u);
                 cnt.rays++;
             } else if (!dead) {
-                trav_start<XFORM>(ctx, r, ray.o, ray.d, ray.t, ray.obj, ray.tri, ray.bvh_depth);
+                trav_start<XFORM, TREE>(ctx, r, ray.o, ray.d, ray.t, ray.obj, ray.tri, ray.bvh_depth);
                 cnt.rays++;
             } else {
                 finish_path(en);
@@ -176,7 +180,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
                 if (primary_ray(args, pt.g, pid, batch_first, pr, rng, px)) {  // false: padding of an edge tile, the lane stays idle
                     tp = mk(1.0f); en = mk(0.0f); pf = 0u;                    // ref: Main.cpp:398-402
                     if (BRUTE && (st.render_mode == 1u || (st.render_mode == 0u && px < args.width / 2u))) pf = kPfBrute;   // ref: Main.cpp:719-729
-                    trav_start<XFORM>(ctx, r, pr.o, pr.d, pr.t, kNoHit, 0u, 0u);
+                    trav_start<XFORM, TREE>(ctx, r, pr.o, pr.d, pr.t, kNoHit, 0u, 0u);
                     cnt.rays++;
                 }
             }
@@ -200,21 +204,21 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
             // ---- the tail of the launch: a few rays left in this wave and no path to hand to the idle lanes: every lane runs its ray to
             //      the next object boundary in the lean loop (trace_steps.hpp: lean_traverse) -- the launch ends when its longest chain does
             if (TAIL && !can_refill && n_busy <= tune.tail_lanes && n_inner + n_leaf != 0u) {
-                if (r.code < kStartObject || (int32_t)r.code < 0) lean_traverse<COUNT, false, XFORM>(ctx, r, cnt);
+                if (r.code < kStartObject || (int32_t)r.code < 0) lean_traverse<COUNT, false, STEP>(ctx, r, cnt);
                 continue;
             }
 
             if (n_inner >= n_leaf && n_inner >= w_obj && n_inner >= w_shade) {
                 do {
-                    if (r.code < kStartObject) inner_step<COUNT, XFORM>(ctx, r, cnt);
+                    if (r.code < kStartObject) inner_step<COUNT, STEP>(ctx, r, cnt);
                 } while ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64(r.code < kStartObject)) >= tune.inner_repeat);
             } else if (n_leaf >= w_obj && n_leaf >= w_shade) {
                 do {
-                    if ((int32_t)r.code < 0) leaf_step<COUNT, false, XFORM>(ctx, r, cnt);
+                    if ((int32_t)r.code < 0) leaf_step<COUNT, false, STEP>(ctx, r, cnt);
                 } while ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64((int32_t)r.code < 0)) >= tune.leaf_repeat);
             } else if (w_obj >= w_shade) {
                 // ---- object step; a finished ray is dispatched on the spot ----
-                if (r.code == kStartObject && object_step<COUNT, false, XFORM>(ctx, r, cnt)) ray_done();
+                if (r.code == kStartObject && object_step<COUNT, false, XFORM, TREE>(ctx, r, cnt)) ray_done();
             } else {
                 // ---- shade step: one bounce of the path on the hit of its extend ray ----
                 if (r.code == kShade) shade_hit();
@@ -253,13 +257,13 @@ struct PtTuning {
     uint32_t fine_rounds = 2;     // fine fetches (one id per idle lane) once fewer than this many ids per lane of the grid are left
 };
 
-// every instantiation, [RIS][GLOSSY][COUNT][BRUTE][TAIL]
+// every instantiation, [RIS][LEVEL][COUNT][BRUTE][TAIL]
 #define CGPT_PT_LEVEL(G, R) \
     { { { pt_persistent<false, false, false, G, R>, pt_persistent<false, false, true, G, R> }, { pt_persistent<false, true, false, G, R>, pt_persistent<false, true, true, G, R> } }, \
       { { pt_persistent<true, false, false, G, R>, pt_persistent<true, false, true, G, R> }, { pt_persistent<true, true, false, G, R>, pt_persistent<true, true, true, G, R> } } }
-static decltype(&pt_persistent<false, false, false, 0, false>) const kPtKernels[2][5][2][2][2] = {
-    { CGPT_PT_LEVEL(0, false), CGPT_PT_LEVEL(1, false), CGPT_PT_LEVEL(2, false), CGPT_PT_LEVEL(3, false), CGPT_PT_LEVEL(4, false) },
-    { CGPT_PT_LEVEL(0, true), CGPT_PT_LEVEL(1, true), CGPT_PT_LEVEL(2, true), CGPT_PT_LEVEL(3, true), CGPT_PT_LEVEL(4, true) },
+static decltype(&pt_persistent<false, false, false, 0, false>) const kPtKernels[2][10][2][2][2] = {   // levels 5-9: 0-4 through the top-level tree
+    { CGPT_PT_LEVEL(0, false), CGPT_PT_LEVEL(1, false), CGPT_PT_LEVEL(2, false), CGPT_PT_LEVEL(3, false), CGPT_PT_LEVEL(4, false), CGPT_PT_LEVEL(5, false), CGPT_PT_LEVEL(6, false), CGPT_PT_LEVEL(7, false), CGPT_PT_LEVEL(8, false), CGPT_PT_LEVEL(9, false) },
+    { CGPT_PT_LEVEL(0, true), CGPT_PT_LEVEL(1, true), CGPT_PT_LEVEL(2, true), CGPT_PT_LEVEL(3, true), CGPT_PT_LEVEL(4, true), CGPT_PT_LEVEL(5, true), CGPT_PT_LEVEL(6, true), CGPT_PT_LEVEL(7, true), CGPT_PT_LEVEL(8, true), CGPT_PT_LEVEL(9, true) },
 };
 #undef CGPT_PT_LEVEL
 static constexpr size_t kPtKernelCount = sizeof(kPtKernels) / sizeof(kPtKernels[0][0][0][0][0]);
@@ -274,9 +278,9 @@ struct PtHost {
     hipEvent_t begin = nullptr, acc_done[2] = { nullptr, nullptr };
     EventPairs ev;
     uint32_t n_cus = 0;
-    uint32_t blocks_per_cu[2][5][2][2][2] = {};  // [RIS][GLOSSY][COUNT][BRUTE][TAIL]
+    uint32_t blocks_per_cu[2][10][2][2][2] = {}; // [RIS][LEVEL][COUNT][BRUTE][TAIL]; the tree levels are queried at the first launch with the tree on
     static_assert(sizeof(blocks_per_cu) / sizeof(uint32_t) == kPtKernelCount, "one occupancy entry per instantiation");
-    size_t occupancy_lds = 0;
+    size_t occupancy_lds = 0, tree_occupancy_lds = 0;
 };
 
 static const Knob<PtTuning> kPtKnobs[] = {
@@ -340,7 +344,7 @@ void PersistentCollectTiming(void* state, ShadeVariant v, double* ms, uint32_t* 
     if (!state) return;
     PtHost* h = static_cast<PtHost*>(state);
     ForEachPair(h->ev, [&](uint32_t, float t) { *ms += t; *launches += 1; });
-    *waves_per_simd = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[v.ris][v.lobe_level][0][0][0]) * (kTraceBlock / 256u);
+    *waves_per_simd = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[v.ris][KernelLevel(v)][0][0][0]) * (kTraceBlock / 256u);
 }
 
 int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
@@ -354,11 +358,18 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v
     const uint32_t top_records = std::min(h->tune.top_records, args_in.scene.n_top_records);
     const size_t lds = trace_lds_bytes(top_records);
     if (h->occupancy_lds != lds) {
-        LAUNCH_TRY(QueryOccupancy(&kPtKernels[0][0][0][0][0], &h->blocks_per_cu[0][0][0][0][0], kPtKernelCount, kTraceBlock, lds));
+        for (uint32_t ris = 0; ris < 2u; ++ris)                               // the list kernels: what mode 0 always queried
+            LAUNCH_TRY(QueryOccupancy(&kPtKernels[ris][0][0][0][0], &h->blocks_per_cu[ris][0][0][0][0], kPtKernelCount / 4u, kTraceBlock, lds));
         h->occupancy_lds = lds;
     }
+    if (v.tree && h->tree_occupancy_lds != lds) {
+        for (uint32_t ris = 0; ris < 2u; ++ris)
+            LAUNCH_TRY(QueryOccupancy(&kPtKernels[ris][kTreeLevels][0][0][0], &h->blocks_per_cu[ris][kTreeLevels][0][0][0], kPtKernelCount / 4u, kTraceBlock, lds));
+        h->tree_occupancy_lds = lds;
+    }
     const bool tail = args_in.n_samples <= h->tune.tail_samples;              // a small call: mostly drain
-    const uint32_t blocks_per_cu = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[v.ris][v.lobe_level][v.count][brute][tail]);
+    const uint32_t level = KernelLevel(v);                                    // cgpt_set_top_level(1): the scene's own level through the tree
+    const uint32_t blocks_per_cu = std::min(h->tune.blocks_per_cu, h->blocks_per_cu[v.ris][level][v.count][brute][tail]);
     // the resident capacity of the chip, or fewer blocks when there are fewer than 64 paths per wave (a small call ends sooner when
     // its paths are spread thin than when the tail of a launch waits for 4 096 waves to find out that there is nothing to do)
     const uint32_t n_tiles = ((args_in.width + 7u) / 8u) * ((args_in.n_rows + 7u) / 8u);
@@ -426,7 +437,7 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v
         work_sizes(pt.n_paths, grid.x * (kTraceBlock / 64u), h->tune.fine_rounds, h->tune.chunk, pt.coarse, pt.fine_below);
         // the buffer's previous batch must have been accumulated (same stream: implicit)
         LAUNCH_TRY(hipEventRecord(NextEvent(h->ev), st));
-        hipLaunchKernelGGL(kPtKernels[v.ris][v.lobe_level][v.count][brute][tail], grid, trace_block, lds, st, args_in, pt, bfirst, tt);
+        hipLaunchKernelGGL(kPtKernels[v.ris][level][v.count][brute][tail], grid, trace_block, lds, st, args_in, pt, bfirst, tt);
         LAUNCH_TRY(hipEventRecord(NextEvent(h->ev), st));
         // accumulate in sample order: batch k after batch k-1
         if (n_streams == 2 && k > 0) LAUNCH_TRY(hipStreamWaitEvent(st, h->acc_done[(k - 1u) & 1u], 0));

@@ -155,6 +155,10 @@ int RefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles,
     if (d.kind == CGPT_OBJECT_MESH)
         for (uint32_t i = 0; i < n_tris; ++i) area += HostTriangleArea(triangles[i]);
 
+    // the top-level tree's box of this object: the min / max of the new vertex positions, which is what the refit's root bounds come to
+    TopLevelState top = ctx->top_state;
+    TriangleBounds(triangles, n_tris, top.local_box.data() + 6 * (size_t)obj_index);
+
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, ctx->sb.refit_staging.Grow(n_tris));                          // the stream was just drained: nothing uses the old one
@@ -177,6 +181,8 @@ int RefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles,
         REFIT_HIP_WRITING(ctx, hipMemcpyAsync(&ctx->sb.objects.p[obj_index].total_area, &d.total_area, sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     }
     REFIT_HIP_WRITING(ctx, hipStreamSynchronize(ctx->stream));
+    REFIT_HIP_WRITING(ctx, WriteTopLevel(ctx, ctx->h_objects, top));
+    ctx->top_state.local_box.swap(top.local_box);
     if (total_area_out) *total_area_out = area;
     return CGPT_OK;
 }
@@ -285,6 +291,7 @@ int UpdatePrimitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_object* obj)
     REFIT_HIP_WRITING(ctx, hipMemcpyAsync(ctx->sb.obj_trace.p + 2 * (size_t)obj_index, q, sizeof(q), hipMemcpyHostToDevice, ctx->stream));
     REFIT_HIP_WRITING(ctx, hipStreamSynchronize(ctx->stream));
     d = nd;
+    REFIT_HIP_WRITING(ctx, WriteTopLevel(ctx, ctx->h_objects, ctx->top_state));   // a sphere's or plane's box is read from its DevObject
     return CGPT_OK;
 }
 

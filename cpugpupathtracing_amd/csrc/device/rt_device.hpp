@@ -348,35 +348,94 @@ __device__ __forceinline__ V3 xform_normal(const Xform& x, V3 n)
     return normalize(mk((x.r0.x * n.x + x.r1.x * n.y) + x.r2.x * n.z, (x.r0.y * n.x + x.r1.y * n.y) + x.r2.y * n.z, (x.r0.z * n.x + x.r1.z * n.y) + x.r2.z * n.z));
 }
 
+// ---- the top-level tree (cgpt_set_top_level; device_scene.h: the records behind the transforms) -----------------------
+// tests/tlas_ref.py states the tree, the boxes and the walk in numpy and is the specification.  A node is two float4s,
+// {lo.xyz, bits(skip) | hi.xyz, bits(object)}: `skip` is the first node behind the node's subtree in preorder, `object` the leaf's object
+// index or kTreeInner.  The walk is in preorder, never reordered by distance: objects are visited in index order and a node whose box the
+// world ray misses (slab_dist_finite's arithmetic and hit rule, against the ray's current t) only skips the objects below it.
+static constexpr uint32_t kTreeInner = 0xFFFFFFFFu;
+__device__ __forceinline__ const float4* tree_nodes(const DevScene& sc) { return sc.obj_trace + 5u * (size_t)sc.n_objects; }
+__device__ __forceinline__ const uint32_t* tree_entry(const DevScene& sc)      // entry[j]: the highest node whose range starts at object j; entry[n] = 2 n - 1
+{
+    return reinterpret_cast<const uint32_t*>(tree_nodes(sc) + 2u * (2u * (size_t)sc.n_objects - 1u));
+}
+// The box is widened, for this ray, by kTreeFarPad times its largest distance from the ray's origin along an axis: the list walk's own tests
+// err in proportion to that distance (intersect_sphere's d2 = L.L - tca^2 carries about 13 |L|^2 2^-24, a lateral sqrt(13) 2^-12 |L| =
+// 2^-10.2 |L|, so from 10^5 units away it reports hits on spheres the ray passes a hundred units from), and the tree must not skip what
+// the list walk would report.  |L| <= sqrt(3) times that distance, so the pad is at least 2^-8.8 |L|.  The pad grows from child to parent
+// as the box does, so a parent's widened box still holds its children's.
+static constexpr float kTreeFarPad = 0.00390625f;                              // 2^-8
+__device__ __forceinline__ bool tree_box_hit(float4 q0, float4 q1, V3 o, V3 inv, float ray_t)
+{
+    const float ax = q0.x - o.x, ay = q0.y - o.y, az = q0.z - o.z, bx = q1.x - o.x, by = q1.y - o.y, bz = q1.z - o.z;
+    float ma, mb;
+    asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(ma) : "v"(ax), "v"(ay), "v"(az));
+    asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(mb) : "v"(bx), "v"(by), "v"(bz));
+    const float pad = kTreeFarPad * fmaxf(ma, mb);
+    const float t1x = (ax - pad) * inv.x, t1y = (ay - pad) * inv.y, t1z = (az - pad) * inv.z;
+    const float t2x = (bx + pad) * inv.x, t2y = (by + pad) * inv.y, t2z = (bz + pad) * inv.z;
+    float hx, hy, hz, lx, ly, lz, tmax, tmin;
+    asm("v_max_f32 %0, %1, %2" : "=v"(hx) : "v"(t1x), "v"(t2x));
+    asm("v_max_f32 %0, %1, %2" : "=v"(hy) : "v"(t1y), "v"(t2y));
+    asm("v_max_f32 %0, %1, %2" : "=v"(hz) : "v"(t1z), "v"(t2z));
+    asm("v_min_f32 %0, %1, %2" : "=v"(lx) : "v"(t1x), "v"(t2x));
+    asm("v_min_f32 %0, %1, %2" : "=v"(ly) : "v"(t1y), "v"(t2y));
+    asm("v_min_f32 %0, %1, %2" : "=v"(lz) : "v"(t1z), "v"(t2z));
+    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(tmax) : "v"(hx), "v"(hy), "v"(hz));
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(tmin) : "v"(lx), "v"(ly), "v"(lz));
+    // slab_dist_finite's rule, stated as what rules a box out: a NaN (an unbounded box times a 1 / d that underflowed to zero) skips nothing
+    return !(tmax < tmin) && !(tmin >= ray_t) && !(tmax <= 0.0f);
+}
+
+// one object of IntersectScene's loop (ref: Source/Main.cpp:303-315)
+template <bool COUNT, bool XFORM>
+__device__ __forceinline__ void intersect_object(const DevScene& sc, uint32_t obj_idx, V3 inv, Ray& ray, uint32_t* __restrict__ stack, uint32_t stack_stride, Counters& cnt)
+{
+    const DevObject& obj = sc.objects[obj_idx];
+    bool hit;
+    if (XFORM && obj.kind != 1u && obj.kind != 2u && has_xform(sc, obj_idx)) {   // a mesh or a triangle object (a sphere's or plane's record holds floats there)
+        V3 oo, od;
+        xform_ray(load_xform(sc, obj_idx), ray.o, ray.d, oo, od);
+        if (obj.kind == 0u) hit = traverse_mesh<COUNT>(sc, obj.root_code, oo, od, mk(1.0f / od.x, 1.0f / od.y, 1.0f / od.z), ray.t, ray.tri, ray.bvh_depth, stack, stack_stride, cnt);
+        else {
+            const LeafTri lt = load_leaf_tri(sc.tri_leaf, obj.root_code & ~kLeafBit);
+            hit = intersect_triangle(lt.v0, lt.e1, lt.e2, oo, od, ray.t);
+        }
+    } else if (obj.kind == 0u) hit = traverse_mesh<COUNT>(sc, obj.root_code, ray.o, ray.d, inv, ray.t, ray.tri, ray.bvh_depth, stack, stack_stride, cnt);
+    else if (obj.kind == 1u) hit = intersect_sphere(mk(obj.sphere_center), obj.sphere_radius_sq, ray.o, ray.d, ray.t);
+    else if (obj.kind == 2u) hit = intersect_plane(mk(obj.plane_normal), mk(obj.plane_point), ray.o, ray.d, ray.t);
+    else {                                                                // triangle object: IntersectTriangle on its leaf record
+        const LeafTri lt = load_leaf_tri(sc.tri_leaf, obj.root_code & ~kLeafBit);   // (ref: Primitives.cpp:292-296); ray.tri keeps
+        hit = intersect_triangle(lt.v0, lt.e1, lt.e2, ray.o, ray.d, ray.t);          // what an earlier mesh wrote, as payload.tri_idx does
+    }
+    if (hit) ray.obj = obj_idx;
+}
+
 // IntersectScene (ref: Source/Main.cpp:299-316): closest hit over all objects in order; strict t < ray.t everywhere.
 // XFORM: the scene has an object with the transform flag set; such a mesh or triangle object is walked with the ray in its own space (1 / d',
 // the axis-parallel decision and the slab operands from d'), the next object sees the world ray again.  The instantiations without it
 // read neither the flag nor the records: the code they had.
-template <bool COUNT, bool XFORM = false>
+// TREE: the objects are reached through the top-level tree (cgpt_set_top_level(1)): the same objects in the same order, without the runs
+// whose union box the world ray misses.  An axis-parallel ray (1 / d with an infinite component) skips nothing.
+template <bool COUNT, bool XFORM = false, bool TREE = false>
 __device__ __forceinline__ void intersect_scene(const DevScene& sc, Ray& ray, uint32_t* __restrict__ stack, uint32_t stack_stride, Counters& cnt)
 {
     cnt.rays++;
     const V3 inv = mk(1.0f / ray.d.x, 1.0f / ray.d.y, 1.0f / ray.d.z);   // Ray ctor, ref: Primitives.h:64
-    for (uint32_t obj_idx = 0; obj_idx < sc.n_objects; ++obj_idx) {
-        const DevObject& obj = sc.objects[obj_idx];
-        bool hit;
-        if (XFORM && obj.kind != 1u && obj.kind != 2u && has_xform(sc, obj_idx)) {   // a mesh or a triangle object (a sphere's or plane's record holds floats there)
-            V3 oo, od;
-            xform_ray(load_xform(sc, obj_idx), ray.o, ray.d, oo, od);
-            if (obj.kind == 0u) hit = traverse_mesh<COUNT>(sc, obj.root_code, oo, od, mk(1.0f / od.x, 1.0f / od.y, 1.0f / od.z), ray.t, ray.tri, ray.bvh_depth, stack, stack_stride, cnt);
-            else {
-                const LeafTri lt = load_leaf_tri(sc.tri_leaf, obj.root_code & ~kLeafBit);
-                hit = intersect_triangle(lt.v0, lt.e1, lt.e2, oo, od, ray.t);
-            }
-        } else if (obj.kind == 0u) hit = traverse_mesh<COUNT>(sc, obj.root_code, ray.o, ray.d, inv, ray.t, ray.tri, ray.bvh_depth, stack, stack_stride, cnt);
-        else if (obj.kind == 1u) hit = intersect_sphere(mk(obj.sphere_center), obj.sphere_radius_sq, ray.o, ray.d, ray.t);
-        else if (obj.kind == 2u) hit = intersect_plane(mk(obj.plane_normal), mk(obj.plane_point), ray.o, ray.d, ray.t);
-        else {                                                                // triangle object: IntersectTriangle on its leaf record
-            const LeafTri lt = load_leaf_tri(sc.tri_leaf, obj.root_code & ~kLeafBit);   // (ref: Primitives.cpp:292-296); ray.tri keeps
-            hit = intersect_triangle(lt.v0, lt.e1, lt.e2, ray.o, ray.d, ray.t);          // what an earlier mesh wrote, as payload.tri_idx does
+    if (TREE) {
+        const float4* const nodes = tree_nodes(sc);
+        const uint32_t n_nodes = 2u * sc.n_objects - 1u;
+        const bool no_skip = has_infinite_component(inv);
+        for (uint32_t k = 0; k < n_nodes;) {
+            const float4 q0 = nodes[2u * k], q1 = nodes[2u * k + 1u];
+            if (!no_skip && !tree_box_hit(q0, q1, ray.o, inv, ray.t)) { k = __float_as_uint(q0.w); continue; }
+            const uint32_t obj_idx = __float_as_uint(q1.w);
+            if (obj_idx != kTreeInner) intersect_object<COUNT, XFORM>(sc, obj_idx, inv, ray, stack, stack_stride, cnt);
+            ++k;
         }
-        if (hit) ray.obj = obj_idx;
+        return;
     }
+    for (uint32_t obj_idx = 0; obj_idx < sc.n_objects; ++obj_idx) intersect_object<COUNT, XFORM>(sc, obj_idx, inv, ray, stack, stack_stride, cnt);
 }
 
 // ---- probe: the top of IntersectScene and nothing below it (wavefront shade: "Probe") ---------------------------------------

@@ -23,6 +23,15 @@ struct RefitObject {
     std::vector<uint32_t> level_offsets;       // ... records of depth d at [level_begin + level_offsets[d], level_begin + level_offsets[d + 1])
 };
 
+// What the boxes of the top-level tree (cgpt_set_top_level) are computed from, kept current on the host by every edit
+// that moves a box: per object the object-space box of a mesh or triangle object (the root node's bounds; the min / max of the vertex
+// positions for a leaf root, a triangle object and after a refit) and its object-to-world matrix.  Spheres and planes are read from
+// their DevObject.
+struct TopLevelState {
+    std::vector<float> local_box;              // 6 per object {lo.xyz, hi.xyz}
+    std::vector<float> xform;                  // 12 per object, the rows of [A | b]; the identity after an upload
+};
+
 struct SceneLayout {
     // the arrays of device_scene.h, and each mesh's child-pair records grouped by depth (refit.hip's bound pass)
     std::vector<float4> node_pairs, tri_leaf, tri_orig, tri_normal, materials;
@@ -32,6 +41,7 @@ struct SceneLayout {
     std::vector<float4> obj_xform;             // {Ainv row r, binv_r}, 3 per object: installed behind obj_trace's 2 n records.  LayoutScene writes the identity
     std::vector<uint32_t> lights;
     std::vector<uint32_t> refit_levels;
+    TopLevelState top_state;                   // the source of the top-level tree's boxes (LayoutTopLevel)
     // host bookkeeping of the in-place edits
     std::vector<RefitObject> refit_objects;
     std::vector<uint32_t> record_perm;         // record index in the reference's depth-first order -> index in node_pairs
@@ -98,5 +108,19 @@ inline void IdentityTransformRecords(float4 rec[3])
 // in `error` and the outputs meaningless.  (scene_layout.hip)
 int LayoutTransforms(const float* object_to_world, uint32_t n_objects, const std::vector<DevObject>& objects, const std::vector<uint32_t>& lights,
                      std::vector<float4>& records, std::vector<uint32_t>& flags, std::string& error);
+
+
+// ---- the top-level tree (cgpt_set_top_level; tests/tlas_ref.py is the specification) ---------------------------------
+// min / max of the vertex positions of n triangles (what CalculateNodeBounds yields for a node that holds them all)
+void TriangleBounds(const cgpt_triangle* triangles, size_t n, float box[6]);
+// The padded world box of object i.
+void TopLevelLeafBox(const DevObject& d, const float local_box[6], const float xform[12], float box[6]);
+// The balanced tree over the object index ranges in preorder, 2 n - 1 nodes of two float4s {lo.xyz, bits(skip) | hi.xyz, bits(object or
+// 0xFFFFFFFF)}, and the table entry[j] = the highest node whose range starts at object j, entry[n] = 2 n - 1.  Host only, O(n).
+void LayoutTopLevel(const std::vector<DevObject>& objects, const TopLevelState& st, std::vector<float4>& nodes, std::vector<uint32_t>& entry);
+// float4s of the tree behind obj_trace's 5 n records: the nodes, then the entry table padded to whole float4s
+inline size_t TopLevelFloat4s(size_t n) { return n ? 2 * (2 * n - 1) + (n + 1 + 3) / 4 : 0; }
+// nodes and entry table as they are copied to the device, in one piece
+std::vector<float4> PackTopLevel(const std::vector<DevObject>& objects, const TopLevelState& st);
 
 }  // namespace cgpt

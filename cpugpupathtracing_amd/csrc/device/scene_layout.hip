@@ -230,6 +230,12 @@ int LayoutScene(const cgpt_scene_desc& sd, SceneLayout& out, std::string& error)
 
     out.objects.resize(sd.n_objects);
     out.refit_objects.resize(sd.n_objects);
+    out.top_state.local_box.assign(6 * (size_t)sd.n_objects, 0.0f);
+    out.top_state.xform.resize(12 * (size_t)sd.n_objects);
+    for (uint32_t oi = 0; oi < sd.n_objects; ++oi) {
+        static const float kIdentity[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
+        memcpy(out.top_state.xform.data() + 12 * (size_t)oi, kIdentity, sizeof(kIdentity));
+    }
     uint32_t max_tree_depth = 0;
     std::vector<uint8_t> rec_depth;                                           // depth of every child-pair record (0xFF: not reached)
     for (uint32_t oi = 0; oi < sd.n_objects; ++oi) {
@@ -265,10 +271,15 @@ int LayoutScene(const cgpt_scene_desc& sd, SceneLayout& out, std::string& error)
             PackNormalPair(tr, pair);
             out.tri_normal12.push_back(pair[0]); out.tri_normal12.push_back(pair[1]);
             d.root_code = kLeafBit | leaf_base; d.tri_base = orig_base; d.n_tris = 1;
+            TriangleBounds(&tr, 1, out.top_state.local_box.data() + 6 * (size_t)oi);
             out.refit_objects[oi].tri_count = 1; out.refit_objects[oi].leaf_base = leaf_base;
         } else if (o.kind == CGPT_OBJECT_MESH) {
             const int rc = LayoutMesh(sd, oi, leaf_base_of[oi], out, rec_depth, max_tree_depth, error);
             if (rc != CGPT_OK) return rc;
+            float* box = out.top_state.local_box.data() + 6 * (size_t)oi;      // the root node's bounds; a leaf root: its triangles'
+            const cgpt_bvh_node& root = sd.nodes[o.node_offset];
+            if (root.prim_count > 0) TriangleBounds(sd.triangles + o.tri_offset, o.tri_count, box);
+            else { memcpy(box, root.aabb_min, 12); memcpy(box + 3, root.aabb_max, 12); }
         } else {
             return Refuse(error, CGPT_ERR_UNSUPPORTED, "object %u: primitive kind %u has no intersector (the reference EXCEPTs on AABB too, Primitives.cpp:302-305)", oi, o.kind);
         }
@@ -299,6 +310,89 @@ int LayoutScene(const cgpt_scene_desc& sd, SceneLayout& out, std::string& error)
     out.obj_xform.resize(3 * (size_t)sd.n_objects);                            // an upload resets every transform to the identity
     for (uint32_t oi = 0; oi < sd.n_objects; ++oi) IdentityTransformRecords(out.obj_xform.data() + 3 * (size_t)oi);
     return CGPT_OK;
+}
+
+void TriangleBounds(const cgpt_triangle* triangles, size_t n, float box[6])
+{
+    for (int a = 0; a < 3; ++a) { box[a] = INFINITY; box[3 + a] = -INFINITY; }
+    bool finite = n > 0;
+    for (size_t i = 0; i < n; ++i) {
+        const float* const p[3] = { triangles[i].v0.pos, triangles[i].v1.pos, triangles[i].v2.pos };
+        for (int v = 0; v < 3; ++v)
+            for (int a = 0; a < 3; ++a) {
+                const float x = p[v][a];
+                finite = finite && std::isfinite(x);
+                if (x < box[a]) box[a] = x;
+                if (x > box[3 + a]) box[3 + a] = x;
+            }
+    }
+    if (!finite) UnboundedBox(box);                                           // a NaN would slip through the comparisons
+}
+
+void TopLevelLeafBox(const DevObject& d, const float local_box[6], const float xform[12], float box[6])
+{
+    if (d.kind == CGPT_OBJECT_SPHERE) {
+        for (int a = 0; a < 3; ++a) { box[a] = d.sphere_center[a] - d.sphere_radius; box[3 + a] = d.sphere_center[a] + d.sphere_radius; }
+        for (int a = 0; a < 3; ++a)
+            if (!(box[a] <= box[3 + a])) { UnboundedBox(box); break; }        // a negative or NaN radius: no box to trust
+    } else if (d.kind == CGPT_OBJECT_PLANE) {
+        UnboundedBox(box);
+    } else {
+        memcpy(box, local_box, 24);
+        if (!IsFiniteBox(box)) UnboundedBox(box);
+        else if (!IsIdentityTransform(xform)) TransformBox(xform, local_box, box);
+    }
+    PadBox(box);
+}
+
+namespace {
+struct TopLevelBuilder {
+    const std::vector<float>& leaf;                                           // 6 per object
+    std::vector<float4>& nodes;
+    std::vector<uint32_t>& entry;
+    void Build(uint32_t i, uint32_t j, float box[6])
+    {
+        const size_t k = nodes.size() / 2;
+        nodes.resize(nodes.size() + 2);
+        if (entry[i] == 0xFFFFFFFFu) entry[i] = (uint32_t)k;                  // preorder: the first node that starts at i is the highest
+        uint32_t object = 0xFFFFFFFFu;
+        if (j - i == 1) { memcpy(box, leaf.data() + 6 * (size_t)i, 24); object = i; }
+        else {
+            const uint32_t m = i + (j - i + 1) / 2;
+            float right[6];
+            Build(i, m, box);
+            Build(m, j, right);
+            for (int a = 0; a < 3; ++a) { if (right[a] < box[a]) box[a] = right[a]; if (right[3 + a] > box[3 + a]) box[3 + a] = right[3 + a]; }
+        }
+        nodes[2 * k] = make_float4(box[0], box[1], box[2], AsFloat((uint32_t)(nodes.size() / 2)));   // skip: the first node behind this subtree
+        nodes[2 * k + 1] = make_float4(box[3], box[4], box[5], AsFloat(object));
+    }
+};
+}  // namespace
+
+void LayoutTopLevel(const std::vector<DevObject>& objects, const TopLevelState& st, std::vector<float4>& nodes, std::vector<uint32_t>& entry)
+{
+    const uint32_t n = (uint32_t)objects.size();
+    nodes.clear(); entry.assign((size_t)n + 1, 0xFFFFFFFFu);
+    if (n == 0) { entry[0] = 0; return; }
+    std::vector<float> leaf(6 * (size_t)n);
+    for (uint32_t i = 0; i < n; ++i) TopLevelLeafBox(objects[i], st.local_box.data() + 6 * (size_t)i, st.xform.data() + 12 * (size_t)i, leaf.data() + 6 * (size_t)i);
+    nodes.reserve(2 * (2 * (size_t)n - 1));
+    TopLevelBuilder b{ leaf, nodes, entry };
+    float box[6];
+    b.Build(0, n, box);
+    entry[n] = 2 * n - 1;
+}
+
+std::vector<float4> PackTopLevel(const std::vector<DevObject>& objects, const TopLevelState& st)
+{
+    std::vector<float4> nodes;
+    std::vector<uint32_t> entry;
+    LayoutTopLevel(objects, st, nodes, entry);
+    std::vector<float4> blob(TopLevelFloat4s(objects.size()), make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    if (!nodes.empty()) memcpy(blob.data(), nodes.data(), nodes.size() * sizeof(float4));
+    if (!blob.empty()) memcpy(blob.data() + nodes.size(), entry.data(), entry.size() * sizeof(uint32_t));
+    return blob;
 }
 
 int LayoutTransforms(const float* object_to_world, uint32_t n_objects, const std::vector<DevObject>& objects, const std::vector<uint32_t>& lights,
@@ -377,6 +471,82 @@ extern "C" int cgpth_scene_layout_transformed(const cgpt_scene_desc* scene, cons
         HostSetError(e.what());
         return CGPT_ERR_INVALID;
     }
+}
+
+// ---- the top-level tree on the host: the upload's tree, then the edits the context applies to it (cgpt_abi.hip, refit.hip call the same
+// functions on the same state) ----
+namespace {
+struct TopLevelStorage { std::vector<DevObject> objects; std::vector<uint32_t> lights; TopLevelState state; std::vector<float4> nodes; std::vector<uint32_t> entry; bool valid = false; };
+TopLevelStorage& TopStorage() { thread_local TopLevelStorage st; return st; }
+int TopLevelShow(TopLevelStorage& st, cgpth_top_level_view* view)
+{
+    LayoutTopLevel(st.objects, st.state, st.nodes, st.entry);
+    view->nodes = reinterpret_cast<const float*>(st.nodes.data()); view->n_nodes = st.nodes.size() / 2;
+    view->entry = st.entry.data(); view->n_entry = st.entry.size();
+    return CGPT_OK;
+}
+template <class F> int TopLevelCall(cgpth_top_level_view* view, bool fresh, F&& f)
+{
+    try {
+        TopLevelStorage& st = TopStorage();
+        if (!view) { HostSetError("null argument"); return CGPT_ERR_INVALID; }
+        if (!fresh && !st.valid) { HostSetError("no cgpth_top_level on this thread yet"); return CGPT_ERR_NO_SCENE; }
+        std::string error;
+        const int rc = f(st, error);
+        if (rc != CGPT_OK) { HostSetError(error.c_str()); return rc; }
+        return TopLevelShow(st, view);
+    } catch (const std::exception& e) {
+        HostSetError(e.what());
+        return CGPT_ERR_INVALID;
+    }
+}
+}  // namespace
+
+extern "C" int cgpth_top_level(const cgpt_scene_desc* scene, cgpth_top_level_view* view)
+{
+    return TopLevelCall(view, true, [&](TopLevelStorage& st, std::string& error) {
+        st.valid = false;
+        if (!scene) return Refuse(error, CGPT_ERR_INVALID, "null argument");
+        SceneLayout layout;
+        const int rc = LayoutScene(*scene, layout, error);
+        if (rc != CGPT_OK) return rc;
+        st.objects = layout.objects; st.lights = layout.lights; st.state = layout.top_state; st.valid = true;
+        return (int)CGPT_OK;
+    });
+}
+
+extern "C" int cgpth_top_level_transforms(const float* object_to_world, uint32_t n_objects, cgpth_top_level_view* view)
+{
+    return TopLevelCall(view, false, [&](TopLevelStorage& st, std::string& error) {
+        std::vector<float4> records; std::vector<uint32_t> flags;
+        const int rc = LayoutTransforms(object_to_world, n_objects, st.objects, st.lights, records, flags, error);
+        if (rc != CGPT_OK) return rc;
+        st.state.xform.assign(object_to_world, object_to_world + 12 * (size_t)n_objects);
+        return (int)CGPT_OK;
+    });
+}
+
+extern "C" int cgpth_top_level_refit(uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris, cgpth_top_level_view* view)
+{
+    return TopLevelCall(view, false, [&](TopLevelStorage& st, std::string& error) {
+        if (obj_index >= st.objects.size() || !triangles || n_tris != st.objects[obj_index].n_tris ||
+            (st.objects[obj_index].kind != CGPT_OBJECT_MESH && st.objects[obj_index].kind != CGPT_OBJECT_TRIANGLE))
+            return Refuse(error, CGPT_ERR_INVALID, "object %u: not a mesh or triangle object of %u triangles", obj_index, n_tris);
+        TriangleBounds(triangles, n_tris, st.state.local_box.data() + 6 * (size_t)obj_index);
+        return (int)CGPT_OK;
+    });
+}
+
+extern "C" int cgpth_top_level_primitive(uint32_t obj_index, const cgpt_object* obj, cgpth_top_level_view* view)
+{
+    return TopLevelCall(view, false, [&](TopLevelStorage& st, std::string& error) {
+        if (obj_index >= st.objects.size() || !obj || obj->kind != st.objects[obj_index].kind || (obj->kind != CGPT_OBJECT_SPHERE && obj->kind != CGPT_OBJECT_PLANE))
+            return Refuse(error, CGPT_ERR_INVALID, "object %u: not a sphere or plane of that kind", obj_index);
+        DevObject& d = st.objects[obj_index];
+        memcpy(d.sphere_center, obj->sphere_center, 12); d.sphere_radius = obj->sphere_radius; d.sphere_radius_sq = obj->sphere_radius * obj->sphere_radius;
+        memcpy(d.plane_normal, obj->plane_normal, 12); memcpy(d.plane_point, obj->plane_point, 12);
+        return (int)CGPT_OK;
+    });
 }
 
 extern "C" int cgpth_scene_layout(const cgpt_scene_desc* scene, cgpth_scene_layout_view* view)

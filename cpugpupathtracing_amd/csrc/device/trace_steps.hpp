@@ -14,6 +14,9 @@
 // walked with -- the object-space form (rt_device.hpp: xform_ray) for a transformed mesh, the world ray for the others -- so in these
 // instantiations EVERY object boundary goes through object_step(): the fold that sends a finishing lane straight to the next mesh's root
 // (next_object_code) is off.  The instantiations without it are the code they were.
+// TREE (object_step and trav_start only): the objects are reached through the top-level tree (cgpt_set_top_level(1), rt_device.hpp: tree_nodes,
+// DESIGN.md 5.17).  The fold is off as under XFORM -- the callers hand `XFORM || TREE` to the other steps' last parameter, which only
+// decides the fold -- and a lane keeps no cursor of its own: coming back from object o it resumes at entry[o + 1], read from a small table.
 // ref: Source/BVH.cpp:61-127 (Traverse), Source/Main.cpp:299-316 (IntersectScene).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -327,13 +330,13 @@ __device__ __forceinline__ void trav_set_ray(Trav& r, V3 o, V3 d)
     r.fast_levels = has_infinite_component(inv) ? 0u : kLdsStackLevels;
     r.rs = make_ray_slab(o, inv);
 }
-template <bool XFORM = false>
+template <bool XFORM = false, bool TREE = false>
 __device__ __forceinline__ void trav_start(const TravCtx& c, Trav& r, V3 o, V3 d, float t, uint32_t obj, uint32_t tri, uint32_t depth)
 {
     r.t = t; r.obj = obj; r.tri = tri; r.depth = depth;
     if (XFORM) { r.wo = o; r.wd = d; }                                        // d / rs keep the last walked ray: object_step sets them for the first mesh
     else trav_set_ray(r, o, d);
-    r.cur_obj = 0; r.code = XFORM ? kStartObject : c.first_code; r.sp = 0;   // XFORM: object 0 may be transformed -- the object step begins it
+    r.cur_obj = 0; r.code = (XFORM || TREE) ? kStartObject : c.first_code; r.sp = 0;   // XFORM: object 0 may be transformed; TREE: it may be skipped -- the object step begins it
 }
 
 __device__ __forceinline__ void load_pair_lds(const lds_u32* top_cache, uint32_t code, NodePair& n)
@@ -524,13 +527,39 @@ __device__ __forceinline__ void lean_traverse(const TravCtx& c, Trav& r, Counter
 // its own (o', d') when its obj_trace record carries the transform flag, else the world ray -- and d, 1 / d and the axis-parallel decision
 // are set from it, in one place, when its bits differ from what the lane carries (a lane that comes out of a transformed mesh still
 // carries that mesh's ray).  A finished lane may therefore hold an object-space ray: the caller's epilogue reads trav_world_origin / _dir.
-template <bool COUNT, bool ANY_HIT = true, bool XFORM = false>
+// TREE: the walk of rt_device.hpp: intersect_scene<.., TREE> from node entry[cur_obj] on -- a node whose box the world ray misses sends the
+// lane to the first node behind its subtree, a leaf whose box it hits is the next object, tested as in the list walk.  The node records are
+// read from HBM for every object count (2 n - 1 records of 32 bytes, shared by every ray: they stay in the vector L1 / L2); the LDS of a
+// trace block is full at five blocks per CU.  Without XFORM the lane's slab operands are the world ray's, so the node test
+// costs no register that outlives the step; with XFORM 1 / d of the world ray is formed here.
+template <bool COUNT, bool ANY_HIT = true, bool XFORM = false, bool TREE = false>
 __device__ __forceinline__ bool object_step(const TravCtx& c, Trav& r, Counters& cnt)
 {
     const DevScene& sc = *c.sc;
     const V3 o = trav_world_origin<XFORM>(r), d = trav_world_dir<XFORM>(r);
+    uint32_t node = 0;
+    V3 inv = mk(0.0f);
+    bool no_skip = false;
+    if (TREE) {
+        inv = XFORM ? mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z) : mk(r.rs.ixy.x, r.rs.ixy.y, r.rs.ozi.y);
+        no_skip = XFORM ? has_infinite_component(inv) : r.fast_levels == 0u;
+        node = tree_entry(sc)[min(r.cur_obj, sc.n_objects)];
+    }
     for (;;) {
         float4 q0, q1;
+        if (TREE) {
+            const float4* const nodes = tree_nodes(sc);
+            const uint32_t n_nodes = 2u * sc.n_objects - 1u;
+            bool end = false;
+            for (;;) {
+                if (node >= n_nodes) { end = true; break; }
+                const float4 b0 = nodes[2u * node], b1 = nodes[2u * node + 1u];
+                if (!no_skip && !tree_box_hit(b0, b1, o, inv, r.t)) { node = __float_as_uint(b0.w); continue; }
+                ++node;
+                if (__float_as_uint(b1.w) != kTreeInner) { r.cur_obj = __float_as_uint(b1.w); break; }
+            }
+            if (end) return true;                                             // no object left: the ray is done
+        }
         if (c.tab) {
             const f4v l0 = *reinterpret_cast<const lds_f4v*>(c.objtab + r.cur_obj * 8u), l1 = *reinterpret_cast<const lds_f4v*>(c.objtab + r.cur_obj * 8u + 4u);
             q0.x = l0.x; q0.y = l0.y; q0.z = l0.z; q0.w = l0.w; q1.x = l1.x; q1.y = l1.y; q1.z = l1.z; q1.w = l1.w;

@@ -43,4 +43,52 @@ inline bool InvertTransform(const float m[12], float out[12])
     return true;
 }
 
+// ---- boxes of the top-level tree (cgpt_set_top_level; tests/tlas_ref.py states the same operations in numpy) ------------------------
+// A box is 6 floats, {lo.xyz, hi.xyz}.  The unbounded box (a plane, geometry that is not finite) is (-inf, +inf) on every axis.
+inline void UnboundedBox(float box[6])
+{
+    for (int a = 0; a < 3; ++a) { box[a] = -INFINITY; box[3 + a] = INFINITY; }
+}
+inline bool IsFiniteBox(const float box[6])
+{
+    for (int i = 0; i < 6; ++i)
+        if (!std::isfinite(box[i])) return false;
+    return true;
+}
+// the largest float <= v and the smallest float >= v
+inline float FloatBelow(double v) { const float f = (float)v; return (double)f > v ? std::nextafter(f, -INFINITY) : f; }
+inline float FloatAbove(double v) { const float f = (float)v; return (double)f < v ? std::nextafter(f, INFINITY) : f; }
+// the box of the 8 corners of `local` under world = A p + b: ((a0 x + a1 y) + a2 z) + b per row in double, min / max over the corners,
+// rounded outward to float
+inline void TransformBox(const float m[12], const float local[6], float out[6])
+{
+    double lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+    for (int c = 0; c < 8; ++c) {
+        const double x = local[(c & 1) ? 3 : 0], y = local[(c & 2) ? 4 : 1], z = local[(c & 4) ? 5 : 2];
+        for (int r = 0; r < 3; ++r) {
+            const double w = (((double)m[4 * r] * x + (double)m[4 * r + 1] * y) + (double)m[4 * r + 2] * z) + (double)m[4 * r + 3];
+            if (w < lo[r]) lo[r] = w;
+            if (w > hi[r]) hi[r] = w;
+        }
+    }
+    for (int r = 0; r < 3; ++r) { out[r] = FloatBelow(lo[r]); out[3 + r] = FloatAbove(hi[r]); }
+}
+// Every leaf box is padded outward: per axis pad = kBoxPad * max(|lo|, |hi|, hi - lo) in float, then one nextafter outward.  A box with a
+// bound that is not finite (before or after) becomes the unbounded box.  tests/tlas_ref.py: PAD states the factor and why.
+static constexpr float kBoxPad = 1e-4f;
+inline void PadBox(float box[6])
+{
+    if (!IsFiniteBox(box)) { UnboundedBox(box); return; }
+    for (int a = 0; a < 3; ++a) {
+        const float lo = box[a], hi = box[3 + a];
+        const float ext = hi - lo;
+        float m = std::fabs(lo) > std::fabs(hi) ? std::fabs(lo) : std::fabs(hi);
+        if (ext > m) m = ext;
+        const float pad = kBoxPad * m;
+        box[a] = std::nextafter(lo - pad, -INFINITY);
+        box[3 + a] = std::nextafter(hi + pad, INFINITY);
+    }
+    if (!IsFiniteBox(box)) UnboundedBox(box);
+}
+
 }  // namespace cgpt

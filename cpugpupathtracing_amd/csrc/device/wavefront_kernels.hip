@@ -140,11 +140,12 @@ __device__ __forceinline__ uint32_t elect_chain_leader(const WfDev& wf, uint32_t
 
 // FIRST (round 0) is a separate instantiation so the later rounds carry neither its code nor its registers.
 // XFORM: the scene has an object with a transform (trace_steps.hpp: the lane also keeps its world ray, six registers that only these
-// instantiations carry).
-template <bool COUNT, bool FIRST, bool XFORM = false>
+// instantiations carry).  TREE: the objects are reached through the top-level tree (trace_steps.hpp: object_step<.., TREE>).
+template <bool COUNT, bool FIRST, bool XFORM = false, bool TREE = false>
 __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs args, const WfDev wf, uint32_t batch_first, const TraceTune tune)
 {
     constexpr bool first_round = FIRST;
+    constexpr bool STEP = XFORM || TREE;                                      // every object boundary goes through object_step: no fold
     const DevScene& sc = args.scene;
     DevCounters* const counters = args.counters;
     const TravCtx ctx = trav_setup(sc, lds_dyn, tune.top_records, wf.stack_overflow, gridDim.x * kTraceBlock, tune.lds_tris);
@@ -246,7 +247,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
                     }
                 }
                 if (ok) {
-                    trav_start<XFORM>(ctx, r, o, d, t, obj, tri, depth);
+                    trav_start<XFORM, TREE>(ctx, r, o, d, t, obj, tri, depth);
                     if (!first_round && tune.shadow_any_hit != 0u && slot >= wf.cap) r.depth |= kAnyHitBit;
                     if (first_round) cnt.rays++;                              // later rounds: every id of the lists is a ray, counted per wave below
                 }
@@ -276,22 +277,22 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
             // loop (the reference's own control flow, trace_steps.hpp: lean_traverse -- ~50 instructions per node instead of ~75 and no
             // votes), then takes the object step.  Same results, same counters.
             if (FIRST && tune.first_lean) {
-                if (r.code < kStartObject || (int32_t)r.code < 0) lean_traverse<COUNT, !FIRST, XFORM>(ctx, r, cnt);
-                if (r.code == kStartObject && object_step<COUNT, !FIRST, XFORM>(ctx, r, cnt)) finish_ray();
+                if (r.code < kStartObject || (int32_t)r.code < 0) lean_traverse<COUNT, !FIRST, STEP>(ctx, r, cnt);
+                if (r.code == kStartObject && object_step<COUNT, !FIRST, XFORM, TREE>(ctx, r, cnt)) finish_ray();
                 continue;
             }
 
             if (n_inner >= n_leaf && n_inner >= w_obj) {
                 do {
-                    if (r.code < kStartObject) inner_step<COUNT, XFORM>(ctx, r, cnt);
+                    if (r.code < kStartObject) inner_step<COUNT, STEP>(ctx, r, cnt);
                 } while ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64(r.code < kStartObject)) >= tune.inner_repeat);
             } else if (n_leaf >= w_obj) {
                 do {
-                    if ((int32_t)r.code < 0) leaf_step<COUNT, !FIRST, XFORM>(ctx, r, cnt);
+                    if ((int32_t)r.code < 0) leaf_step<COUNT, !FIRST, STEP>(ctx, r, cnt);
                 } while ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64((int32_t)r.code < 0)) >= tune.leaf_repeat);
             } else {
                 do {
-                    if (r.code == kStartObject && object_step<COUNT, !FIRST, XFORM>(ctx, r, cnt)) finish_ray();
+                    if (r.code == kStartObject && object_step<COUNT, !FIRST, XFORM, TREE>(ctx, r, cnt)) finish_ray();
                 } while ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64(r.code == kStartObject)) >= tune.obj_repeat);
             }
         }
@@ -715,6 +716,12 @@ static decltype(&wf_trace<false, false>) const kTraceKernels[2][2][2] = {
     { { wf_trace<false, false>, wf_trace<false, true> }, { wf_trace<true, false>, wf_trace<true, true> } },
     { { wf_trace<false, false, true>, wf_trace<false, true, true> }, { wf_trace<true, false, true>, wf_trace<true, true, true> } },
 };
+// the same with the top-level tree (cgpt_set_top_level(1)): a table of its own, so that a context that never turns the tree on queries and
+// launches what it did before
+static decltype(&wf_trace<false, false>) const kTraceTreeKernels[2][2][2] = {
+    { { wf_trace<false, false, false, true>, wf_trace<false, true, false, true> }, { wf_trace<true, false, false, true>, wf_trace<true, true, false, true> } },
+    { { wf_trace<false, false, true, true>, wf_trace<false, true, true, true> }, { wf_trace<true, false, true, true>, wf_trace<true, true, true, true> } },
+};
 #define CGPT_SHADE_LEVEL(G, R) \
     { { { wf_shade<false, false, false, G, R>, wf_shade<false, false, true, G, R> }, { wf_shade<false, true, false, G, R>, wf_shade<false, true, true, G, R> } }, \
       { { wf_shade<true, false, false, G, R>, wf_shade<true, false, true, G, R> }, { wf_shade<true, true, false, G, R>, wf_shade<true, true, true, G, R> } } }
@@ -775,7 +782,9 @@ struct WfHost {
     uint32_t n_cus = 0;
     uint32_t trace_blocks_per_cu[2][2][2] = {}, shade_blocks_per_cu[2][5][2][2] = {};   // trace: [XFORM][COUNT][FIRST]; shade: [RIS][GLOSSY][COUNT][BRUTE]
     bool last_xform = false;                     // the last render ran the XFORM trace kernels (WavefrontTraceWavesPerSimd)
-    size_t occupancy_lds = 0;
+    uint32_t trace_tree_blocks_per_cu[2][2][2] = {};   // kTraceTreeKernels: queried by the first render with the tree on
+    bool last_tree = false;
+    size_t occupancy_lds = 0, tree_occupancy_lds = 0;
     // hipEvent pairs around every trace launch of the last render (roofline accounting: the dominant kernel's own duration)
     EventPairs trace_ev;
     uint32_t trace_rounds = 0;
@@ -809,7 +818,7 @@ uint32_t WavefrontTraceWavesPerSimd(void* state)
 {
     if (!state) return 0;
     const WfHost* h = static_cast<const WfHost*>(state);
-    return std::min(h->tune.max_trace_blocks, h->trace_blocks_per_cu[h->last_xform][0][0]) * (kTraceBlock / 256u);
+    return std::min(h->tune.max_trace_blocks, (h->last_tree ? h->trace_tree_blocks_per_cu : h->trace_blocks_per_cu)[h->last_xform][0][0]) * (kTraceBlock / 256u);
 }
 
 // Sum of the trace launches' durations of the last render (and the round-0 launches' share); call after the render's device work has completed.
@@ -901,8 +910,16 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
     const dim3 block(256);
     const bool xform = v.lobe_level >= 4u;                                    // the scene has a transformed object: the XFORM trace kernels
     h->last_xform = xform;
-    const dim3 trace_grid_first(n_cus * std::min(h->tune.max_trace_blocks, h->trace_blocks_per_cu[xform][count][1]));
-    const dim3 trace_grid_later(n_cus * std::min(h->tune.max_trace_blocks, h->trace_blocks_per_cu[xform][count][0]));
+    const bool tree = v.tree;                                                 // cgpt_set_top_level(1): the TREE trace kernels
+    h->last_tree = tree;
+    if (tree && h->tree_occupancy_lds != trace_lds) {
+        LAUNCH_TRY(QueryOccupancy(&kTraceTreeKernels[0][0][0], &h->trace_tree_blocks_per_cu[0][0][0], 8, kTraceBlock, trace_lds));
+        h->tree_occupancy_lds = trace_lds;
+    }
+    const uint32_t (&trace_blocks)[2][2][2] = tree ? h->trace_tree_blocks_per_cu : h->trace_blocks_per_cu;
+    const auto& trace_kernels = tree ? kTraceTreeKernels : kTraceKernels;
+    const dim3 trace_grid_first(n_cus * std::min(h->tune.max_trace_blocks, trace_blocks[xform][count][1]));
+    const dim3 trace_grid_later(n_cus * std::min(h->tune.max_trace_blocks, trace_blocks[xform][count][0]));
     const bool brute = args_in.settings.render_mode != 2u;                    // the render has TracePath paths (ref: Main.cpp:719-729)
     const uint32_t brute_levels = brute ? (uint32_t)args_in.settings.max_ray_depth + 1u : 0u;
     const uint32_t (&shade_blocks)[2][2] = h->shade_blocks_per_cu[v.ris][v.lobe_level];   // every lobe level's shade kernels, with and without RIS, have grids of their own
@@ -912,7 +929,8 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
     const uint32_t min_shade_waves = n_cus * std::min({ shade_blocks[0][0], shade_blocks[1][0], shade_blocks[0][1], shade_blocks[1][1] }) * 4u;
 
     // deep end of the traversal stacks: one dword per level beyond the LDS part and per thread of the largest trace grid
-    const uint32_t max_trace_threads = n_cus * *std::max_element(&h->trace_blocks_per_cu[0][0][0], &h->trace_blocks_per_cu[0][0][0] + 8) * kTraceBlock;
+    const uint32_t max_trace_threads = n_cus * std::max(*std::max_element(&h->trace_blocks_per_cu[0][0][0], &h->trace_blocks_per_cu[0][0][0] + 8),
+                                                        *std::max_element(&h->trace_tree_blocks_per_cu[0][0][0], &h->trace_tree_blocks_per_cu[0][0][0] + 8)) * kTraceBlock;   // (the tree's entries are 0 until it is used)
     const uint32_t deep_levels = args_in.scene.stack_depth > kLdsStackLevels ? args_in.scene.stack_depth - kLdsStackLevels : 0u;
     const uint32_t overflow_words = std::max(1u, deep_levels * max_trace_threads);
 
@@ -1002,14 +1020,15 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
         wf.retire_misses = h->tune.retire_misses && args_in.settings.debug_mode == 0u ? 1u : 0u;
         if (!chains) wf.spec_tab = nullptr;
         wf.spec_keys = h->tune.spec_keys;
-        // (probe_scene tests mesh roots against the world ray: with a transformed object in the scene the probe is off)
-        wf.probe = h->tune.probe && !count && !xform && args_in.settings.debug_mode == 0u && args_in.scene.n_objects <= h->tune.probe_max_objects ? 1u : 0u;
+        // (probe_scene tests mesh roots against the world ray: with a transformed object in the scene the probe is off; it walks the object
+        // list, not the tree: off with the tree as well)
+        wf.probe = h->tune.probe && !count && !xform && !tree && args_in.settings.debug_mode == 0u && args_in.scene.n_objects <= h->tune.probe_max_objects ? 1u : 0u;
         // segments of waves that a smaller shade grid does not launch must read as empty
         if (k < n_pools) LAUNCH_TRY(hipMemsetAsync(wf.seg_count, 0, 2 * (size_t)kMaxBands * wf.n_segs * sizeof(uint32_t), st));
         for (uint32_t r = 0; r < rounds; ++r) {
             const bool first = r == 0u;
             if (h->tune.trace_events) LAUNCH_TRY(hipEventRecord(NextEvent(h->trace_ev), st));
-            hipLaunchKernelGGL(kTraceKernels[xform][count][first], first ? trace_grid_first : trace_grid_later, dim3(kTraceBlock), trace_lds, st, args, wf, bfirst, tt);
+            hipLaunchKernelGGL(trace_kernels[xform][count][first], first ? trace_grid_first : trace_grid_later, dim3(kTraceBlock), trace_lds, st, args, wf, bfirst, tt);
             if (h->tune.trace_events) LAUNCH_TRY(hipEventRecord(NextEvent(h->trace_ev), st));
             ++launches;
             if (r + 1u < rounds) {

@@ -310,6 +310,25 @@ int cgpth_scene_add_light(cgpth_scene* scene, uint32_t obj_index)
     });
 }
 
+int cgpth_scene_permute_objects(cgpth_scene* scene, const uint32_t* order, uint32_t n_objects)
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        if (!scene || !order || n_objects != scene->scene.objects.size()) return Fail("expected one index per object");
+        std::vector<uint32_t> new_index(n_objects, 0xFFFFFFFFu);
+        for (uint32_t k = 0; k < n_objects; ++k) {
+            if (order[k] >= n_objects || new_index[order[k]] != 0xFFFFFFFFu) return Fail("order is not a permutation of the object indices");
+            new_index[order[k]] = k;
+        }
+        auto& objects = scene->scene.objects;
+        std::remove_reference_t<decltype(objects)> moved;
+        moved.reserve(n_objects);
+        for (uint32_t k = 0; k < n_objects; ++k) moved.push_back(std::move(objects[order[k]]));   // smooth flag and transform travel inside the object
+        objects.swap(moved);
+        for (auto& li : scene->scene.light_source_indices) li = new_index[li];
+        return CGPT_OK;
+    });
+}
+
 int cgpth_scene_set_smooth_normals(cgpth_scene* scene, uint32_t obj_index, uint32_t flag)
 {
     return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {

@@ -52,6 +52,7 @@ class Renderer:
         self._glossy = False          # the device holds a roughness > 0 (cgpt_scene_update_roughness)
         self._rough_glass = False     # the device holds a transmission roughness > 0 (cgpt_scene_update_transmission_roughness)
         self._nee_candidates = 1      # cgpt_set_nee_candidates
+        self._top_level = False       # cgpt_set_top_level
         self._smooth = False          # the device holds a smooth-normal flag (cgpt_scene_update_smooth_normals)
         self._transformed = False     # the device holds a transform that is not the identity (cgpt_scene_update_transforms)
 
@@ -72,6 +73,18 @@ class Renderer:
     @property
     def nee_candidates(self) -> int:
         return self._nee_candidates
+
+    def set_top_level(self, on: bool):
+        """cgpt_set_top_level: True walks a tree over the objects' world boxes instead of the object list.  The image,
+        the guides and every counter but inner_steps are the list walk's, bit for bit; it pays from some tens of objects on, when
+        neighbouring object indices are neighbours in space (Scene.sort_objects_spatially).  State of the renderer, kept across
+        upload(); the accumulator may be kept."""
+        self._check(self.L.cgpt_set_top_level(self._ctx, 1 if on else 0))
+        self._top_level = bool(on)
+
+    @property
+    def top_level(self) -> bool:
+        return self._top_level
 
     def upload(self, scene: Scene):
         """cgpt_scene_upload, then the scene's roughness (cgpt_scene_update_roughness), transmission roughness

@@ -274,6 +274,53 @@ class Scene:
         _host_check(N.lib().cgpth_scene_get_transforms(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), n), "get_transforms")
         return out
 
+    def top_level(self, transforms=None):
+        """The top-level tree an upload of this scene builds (cgpth_top_level), with the scene's own transforms or the
+        given ones: (nodes (2 n - 1, 8) float32 in preorder, {lo.xyz, bits(skip) | hi.xyz, bits(object or 0xFFFFFFFF)}, entry (n + 1,)
+        uint32).  Host only."""
+        L = N.lib()
+        desc = self.flatten()
+        view = N.TopLevelView()
+        _host_check(L.cgpth_top_level(C.byref(desc), C.byref(view)), "top_level")
+        m = np.ascontiguousarray(self.transforms(desc.n_objects) if transforms is None else transforms, np.float32).reshape(-1, 12)
+        _host_check(L.cgpth_top_level_transforms(m.ctypes.data_as(C.POINTER(C.c_float)), m.shape[0], C.byref(view)), "top_level")
+        nodes = np.ctypeslib.as_array(view.nodes, shape=(view.n_nodes, 8)).copy()
+        entry = np.ctypeslib.as_array(view.entry, shape=(view.n_entry,)).copy()
+        return nodes, entry
+
+    def world_boxes(self) -> np.ndarray:
+        """Every object's padded world box (n, 6) float32 {lo.xyz, hi.xyz}: the leaves of top_level().  A plane's is (-inf, +inf)."""
+        nodes, _ = self.top_level()
+        obj = nodes[:, 7].view(np.uint32)
+        leaf = obj != 0xFFFFFFFF
+        out = np.zeros((int(leaf.sum()), 6), np.float32)
+        out[obj[leaf]] = nodes[leaf][:, [0, 1, 2, 4, 5, 6]]
+        return out
+
+    def sort_objects_spatially(self) -> np.ndarray:
+        """Reorders the objects along a Morton curve through their world-box centres (10 bits per axis over the centres' bounds;
+        planes and other unbounded objects first, ties in the old order), so that the index ranges of the top-level tree
+        (Renderer.set_top_level) are compact in space.  Light indices, smooth flags and transforms follow their objects.
+        Returns `order`: the new object k is the old object order[k] -- indices the caller holds must be renamed.
+        It is the caller's choice because it CHANGES THE TIE ORDER: where two objects' surfaces lie at exactly the same distance along
+        a ray, the lower object index wins, so coincident surfaces may render with the other object's material afterwards."""
+        boxes = self.world_boxes().astype(np.float64)
+        n = boxes.shape[0]
+        finite = np.isfinite(boxes).all(-1)
+        key = np.zeros(n, np.uint64)                                  # unbounded objects keep key 0 and come first
+        if finite.any():
+            c = 0.5 * (boxes[finite, :3] + boxes[finite, 3:])
+            lo, hi = c.min(0), c.max(0)
+            q = np.floor((c - lo) / np.where(hi > lo, hi - lo, 1.0) * 1023.0 + 0.5).astype(np.uint64)
+            code = np.zeros(q.shape[0], np.uint64)
+            for bit in range(10):
+                for axis in range(3):
+                    code |= ((q[:, axis] >> np.uint64(bit)) & np.uint64(1)) << np.uint64(3 * bit + axis)
+            key[finite] = code + np.uint64(1)
+        order = np.argsort(key, kind="stable").astype(np.uint32)
+        _host_check(N.lib().cgpth_scene_permute_objects(self._h, order.ctypes.data_as(C.POINTER(C.c_uint32)), n), "sort_objects_spatially")
+        return order
+
     def add_mesh(self, mesh: Mesh, mat_index: int, build_option: int = N.BUILD_SAH_INTERVALS, device_builder=None, smooth: bool = False,
                  transform=None) -> int:
         """Object ctor (ref: Main.cpp:247-251).  device_builder: a Renderer whose GPU builds the (bit-identical) tree, any option.

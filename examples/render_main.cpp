@@ -4,7 +4,7 @@
 //
 //   g++ -std=c++17 -Iinclude -Icpugpupathtracing_amd/csrc/host examples/render_main.cpp
 //       -Lcpugpupathtracing_amd/lib -lcpugpupt -Wl,-rpath,$PWD/cpugpupathtracing_amd/lib -o render_main   (one command line)
-//   ./render_main [--gpus N [--collective]] [--denoise] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--smooth] [--mesh-transform m00 .. m23] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
+//   ./render_main [--gpus N [--collective]] [--denoise] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--smooth] [--mesh-transform m00 .. m23] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
 // --gpus N: ONE context over the first N GPUs of the node (cgpt_ctx_create with n_devices = N): every frame is spread over them in
 // interleaved row bands and the read-back gathers the float4 bands with one RCCL exchange over xGMI; the loop below does not
 // change.  --collective: take that code path with N = 1 too (what a one-GPU box can test).
@@ -18,6 +18,7 @@
 // (cgpt_scene_update_transmission_roughness after the upload; 0 is the reference's polished glass).
 // --bvh binned: build the mesh's tree with BuildOption_SAHBinned (16 bins per axis) on the host instead of the reference's
 // SAH split intervals (the default; image parity with the reference is defined on that tree).
+// --top-level: IntersectScene reaches the objects through the top-level tree (cgpt_set_top_level(1)): the same image, bit for bit.
 // --nee-candidates M: resampled light sampling -- every NEE light sample is the survivor of M candidates in 1..32 (cgpt_set_nee_candidates,
 // set before the upload: it is context state; 1, the default, is the reference's single sample).
 // --smooth: smooth shading -- every mesh object that is not a light shades with its interpolated vertex normals
@@ -49,7 +50,7 @@ using namespace cgpt;
 
 int main(int argc, char** argv)
 {
-    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false;
+    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false;
     bool has_transform = false; float mesh_transform[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
     MeshBVH::BuildOption bvh_option = MeshBVH::BuildOption_SAHSplitIntervals;
     while (argc > 1 && std::string(argv[1]).rfind("--", 0) == 0) {
@@ -63,6 +64,7 @@ int main(int argc, char** argv)
         }
         else if (std::string(argv[1]) == "--ground-roughness" && argc > 2) { ground_roughness = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--glass-roughness" && argc > 2) { glass_roughness = (float)atof(argv[2]); argv += 2; argc -= 2; }
+        else if (std::string(argv[1]) == "--top-level") { top_level = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--nee-candidates" && argc > 2) { nee_candidates = (uint32_t)atoi(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--bvh" && argc > 2 && (std::string(argv[2]) == "binned" || std::string(argv[2]) == "intervals")) {
             bvh_option = std::string(argv[2]) == "binned" ? MeshBVH::BuildOption_SAHBinned : MeshBVH::BuildOption_SAHSplitIntervals; argv += 2; argc -= 2;
@@ -89,6 +91,7 @@ int main(int argc, char** argv)
     cgpt_ctx* ctx = nullptr;
     // ThreadPool::Init: device_ids = NULL means devices 0 .. n_gpus-1
     if (cgpt_ctx_create(nullptr, n_gpus, ctx_flags, &ctx) != CGPT_OK) { fprintf(stderr, "%s\n", cgpt_last_error(nullptr)); return 1; }
+    CHECK(cgpt_set_top_level(ctx, top_level ? 1u : 0u));                  // context state too
     CHECK(cgpt_set_nee_candidates(ctx, nee_candidates));                 // context state: allowed before a scene exists, kept by every upload
     Scene::FlatStorage flat;
     cgpt_scene_desc desc = scene.Flatten(flat);

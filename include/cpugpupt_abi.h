@@ -32,7 +32,8 @@ extern "C" {
                                  (cgpt_scene_update_transmission_roughness) only; resampled light sampling added one new symbol
                                  only (cgpt_set_nee_candidates); smooth shading added one new symbol only
                                  (cgpt_scene_update_smooth_normals); per-object transforms added one new symbol only
-                                 (cgpt_scene_update_transforms) */
+                                 (cgpt_scene_update_transforms); the top-level tree added one new symbol only
+                                 (cgpt_set_top_level) */
 
 enum cgpt_status {
     CGPT_OK = 0,
@@ -202,6 +203,17 @@ int cgpt_set_stream(cgpt_ctx* ctx, void* hip_stream);
  * TracePath half of CGPT_MODE_COMPARISON).  The caller resets the accumulator; the denoiser's cached guides stay valid (first hits do
  * not depend on it); a multi-device context sets every device. */
 int cgpt_set_nee_candidates(cgpt_ctx* ctx, uint32_t candidates);
+/* How IntersectScene reaches the objects.  0 (the default): the object list is walked in order, every object tested for
+ * every ray -- every kernel is then the one it was before this call existed.  1: a balanced tree over the object index ranges with a
+ * world-space box per node is walked in preorder; objects are still visited in index order (the strict t <, the object order on ties,
+ * the BVH-depth view and the counters tri_tests, bvh_depth_sum, closest_hits are the list walk's), the tree only skips runs of objects
+ * whose union box the ray misses, which pays from some tens of objects on when neighbouring indices are neighbours in space
+ * (Scene.sort_objects_spatially in the Python package orders them).  inner_steps no longer counts the root step of a skipped mesh.
+ * Context state like cgpt_set_nee_candidates: may be set before a scene exists, cgpt_scene_upload keeps it, any other value is refused
+ * with CGPT_ERR_INVALID and nothing changed, a multi-device context sets every device.  The boxes follow cgpt_scene_upload,
+ * cgpt_scene_update_transforms, cgpt_scene_refit_mesh and cgpt_scene_update_primitive.  The image does not depend on the mode: the
+ * accumulator may be kept, and the denoiser's cached guides stay valid. */
+int cgpt_set_top_level(cgpt_ctx* ctx, uint32_t mode);
 
 /* replaces the implicit use of data.objects / materials / light_source_indices (ref: Main.cpp:209-212, 303-315) */
 int cgpt_scene_upload(cgpt_ctx* ctx, const cgpt_scene_desc* scene);

@@ -97,6 +97,10 @@ int cgpth_scene_rebuild_bvh_device(cgpth_scene* scene, uint32_t obj_index, int b
 int cgpth_scene_refit_mesh(cgpth_scene* scene, uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris);
 /* the host statement of cgpt_scene_update_primitive: a sphere's centre and radius, or a plane's normal and point */
 int cgpth_scene_update_primitive(cgpth_scene* scene, uint32_t obj_index, const cgpt_object* obj);
+/* reorders the objects: the new object k is the old object order[k] (a permutation of 0 .. n_objects - 1, else refused and nothing
+ * changed); smooth flags and transforms move with their objects, the light indices are renamed.  The object order is IntersectScene's
+ * tie order: two surfaces at exactly the same t are won by the lower index. */
+int cgpth_scene_permute_objects(cgpth_scene* scene, const uint32_t* order, uint32_t n_objects);
 int cgpth_scene_bvh_info(const cgpth_scene* scene, uint32_t obj_index, cgpth_bvh_info* out);
 /* nodes: nodes_used x cgpt_bvh_node; tri_indices: num_triangles */
 int cgpth_scene_bvh_export(const cgpth_scene* scene, uint32_t obj_index, cgpt_bvh_node* nodes, uint32_t* tri_indices);
@@ -148,6 +152,21 @@ int cgpth_scene_layout(const cgpt_scene_desc* scene, cgpth_scene_layout_view* ou
 /* the same after a cgpt_scene_update_transforms(object_to_world, n_objects) on that upload, with that call's validation, status and
  * message: obj_xform holds the inverses, `objects` the xform words and obj_trace the flags the call would install */
 int cgpth_scene_layout_transformed(const cgpt_scene_desc* scene, const float* object_to_world, uint32_t n_objects, cgpth_scene_layout_view* out);
+
+/* ---- the top-level tree of cgpt_set_top_level (csrc/device/scene_layout.h: LayoutTopLevel; tests/tlas_ref.py is its specification) ----
+ * cgpth_top_level: the tree a cgpt_scene_upload of `scene` would build, computed on the host with the upload's validation; no GPU is
+ * touched.  nodes: n_nodes = 2 n_objects - 1 records of 8 floats in preorder, {lo.xyz, bits(skip) | hi.xyz, bits(object or 0xFFFFFFFF)};
+ * entry: n_objects + 1 node indices.  The three calls behind it apply, to the state of this thread's last cgpth_top_level, what
+ * cgpt_scene_update_transforms, cgpt_scene_refit_mesh and cgpt_scene_update_primitive apply to a context's (the same functions), and
+ * show the tree again.  The arrays live in thread-local storage and stay valid until the next of these calls on the same thread. */
+typedef struct cgpth_top_level_view {
+    const float* nodes; size_t n_nodes;
+    const uint32_t* entry; size_t n_entry;
+} cgpth_top_level_view;
+int cgpth_top_level(const cgpt_scene_desc* scene, cgpth_top_level_view* out);
+int cgpth_top_level_transforms(const float* object_to_world, uint32_t n_objects, cgpth_top_level_view* out);
+int cgpth_top_level_refit(uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris, cgpth_top_level_view* out);
+int cgpth_top_level_primitive(uint32_t obj_index, const cgpt_object* obj, cgpth_top_level_view* out);
 
 #ifdef __cplusplus
 }
