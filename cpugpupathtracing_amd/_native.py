@@ -83,6 +83,7 @@ class Stats(C.Structure):
                 ("last_kernel", C.c_uint32), ("device_ms", C.c_double * 8),
                 ("dominant_round0_ms", C.c_double), ("dominant_round0_launches", C.c_uint32), ("chain_followers", C.c_uint32),
                 ("probe_resolved", C.c_uint64)]
+    retrace_unwalked = 0    # not a field of cgpt_stats (the struct keeps its size): Renderer.stats() fills it from cgpt_get_retrace_unwalked
 
 
 class DenoiseParams(C.Structure):
@@ -147,6 +148,7 @@ PROTOTYPES = {
     "cgpt_pixels_device_ptr": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "cgpt_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "cgpt_reset_stats": (C.c_int, [_vp]),
+    "cgpt_get_retrace_unwalked": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "cgpt_intersect_rays": (C.c_int, [_vp, _fp, _fp, _fp, C.c_uint32, _fp, _up, _up, _up]),
     "cgpt_bvh_build": (C.c_int, [_vp, C.POINTER(Triangle), C.c_uint32, C.POINTER(BvhNode), _up, _up, _up, _fp]),
     "cgpt_bvh_build_ex": (C.c_int, [_vp, C.POINTER(Triangle), C.c_uint32, C.c_uint32, _up, C.POINTER(BvhNode), _up, _up, _up, _fp]),

@@ -703,6 +703,18 @@ int cgpt_get_stats(cgpt_ctx* ctx, cgpt_stats* out)
     return CGPT_OK;
 }
 
+int cgpt_get_retrace_unwalked(cgpt_ctx* ctx, uint64_t* out)
+{
+    if (!ctx || !out) return CGPT_ERR_INVALID;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupGetRetraceUnwalked(ctx, out); });
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned long long v = 0;
+    HIP_TRY(ctx, hipMemcpy(&v, &ctx->counters.p->retrace_unwalked, sizeof(v), hipMemcpyDeviceToHost));
+    *out = v;
+    return CGPT_OK;
+}
+
 int cgpt_reset_stats(cgpt_ctx* ctx)
 {
     if (!ctx) return CGPT_ERR_INVALID;

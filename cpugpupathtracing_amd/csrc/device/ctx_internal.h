@@ -153,6 +153,7 @@ int GroupReadPixels(cgpt_ctx* ctx, uint32_t* dst, size_t n_pixels);
 int GroupWriteAccumulator(cgpt_ctx* ctx, const cgpt_render_params* p, const float* src, size_t n_floats, uint32_t num_accumulated);
 int GroupDevicePtr(cgpt_ctx* ctx, bool pixels, void** ptr, size_t* n_bytes);
 int GroupGetStats(cgpt_ctx* ctx, cgpt_stats* out);
+int GroupGetRetraceUnwalked(cgpt_ctx* ctx, uint64_t* out);
 int GroupResetStats(cgpt_ctx* ctx);
 int GroupSetTuning(cgpt_ctx* ctx, const char* name, uint32_t value);
 int GroupSynchronize(cgpt_ctx* ctx);

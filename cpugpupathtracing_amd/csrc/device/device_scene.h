@@ -136,6 +136,7 @@ struct DevCounters {  // device-side totals, 64-bit atomics
     double total_energy;
     unsigned long long chain_followers;   // wavefront later rounds: extend rays whose specular-chain leader traced them
     unsigned long long probe_resolved;    // wavefront shade: rays decided by probe_scene() and never listed (counted in traced_rays too)
+    unsigned long long retrace_unwalked;  // all three kernels: rays traced again after total internal reflection whose known hit was taken without a walk (counted in traced_rays too)
 };
 
 struct DevRenderArgs {

@@ -566,6 +566,18 @@ int GroupGetStats(cgpt_ctx* ctx, cgpt_stats* out)
     return CGPT_OK;
 }
 
+int GroupGetRetraceUnwalked(cgpt_ctx* ctx, uint64_t* out)
+{
+    *out = 0;
+    for (cgpt_ctx* m : ctx->group->members) {
+        uint64_t v = 0;
+        const int rc = cgpt_get_retrace_unwalked(m, &v);
+        if (rc != CGPT_OK) return Propagate(ctx, m, rc);
+        *out += v;
+    }
+    return CGPT_OK;
+}
+
 int GroupResetStats(cgpt_ctx* ctx)
 {
     for (cgpt_ctx* m : ctx->group->members) { const int rc = cgpt_reset_stats(m); if (rc != CGPT_OK) return Propagate(ctx, m, rc); }

@@ -48,7 +48,7 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
     const bool active = px < args.width && local_row < args.n_rows;
     const uint32_t py = GlobalRow(local_row, args.band_first, args.band_h, args.band_stride);
 
-    Counters cnt = { 0, 0, 0, 0, 0 };
+    Counters cnt = { 0, 0, 0, 0, 0, 0 };
     double energy_sum = 0.0;
 
     if (active) {
@@ -67,6 +67,7 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
         Ray ray = make_ray(mk(0.0f), mk(0.0f), 0.0f);
         PathState ps; ps.throughput = mk(1.0f); ps.energy = mk(0.0f); ps.rng = 0; ps.depth = 0; ps.is_specular = false;
         bool need_new = true, shadow_kind = false, dead = false;
+        bool same_ray = false;                                                // shade_bounce left `ray` as it was (total internal reflection, SURVEY A-3)
         Ray sray = make_ray(mk(0.0f), mk(0.0f), 0.0f);                       // pending NEE connection
         V3 pending = mk(0.0f);
         const bool use_brute = BRUTE && (st.render_mode == 1u || (st.render_mode == 0u && px < args.width / 2u));
@@ -78,12 +79,15 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
                 ps.rng = pcg_seed(pixel_index, s, args.seed);
                 ray = camera_ray(args.camera, screen_u, screen_v);            // no jitter: SURVEY A-14
                 ps.throughput = mk(1.0f); ps.energy = mk(0.0f);
-                ps.depth = 0; ps.is_specular = false; need_new = false; shadow_kind = false; dead = false;
+                ps.depth = 0; ps.is_specular = false; need_new = false; shadow_kind = false; dead = false; same_ray = false;
             }
 
             // ---- one ray per iteration: the extend ray or the pending shadow ray ----
+            // The same ray again: IntersectScene accepts only t < ray.t and ray.t is this ray's closest hit, so the call returns the hit it
+            // starts from.  It is counted and not walked; the counting kernels walk it, as the oracle does.
             Ray cur = shadow_kind ? sray : ray;
-            intersect_scene<COUNT, (GLOSSY >= 4), TREE>(sc, cur, stack, stride, cnt);
+            if (!COUNT && same_ray && !shadow_kind) { cnt.rays++; cnt.unwalked++; }
+            else intersect_scene<COUNT, (GLOSSY >= 4), TREE>(sc, cur, stack, stride, cnt);
 
             bool finalize;
             if (BRUTE && use_brute) {
@@ -99,6 +103,7 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
                 const uint32_t flags = shade_bounce<COUNT, GLOSSY, RIS>(sc, st, ray, ps, sray, pending, cnt);
                 dead = (flags & kBounceTerminate) != 0;
                 shadow_kind = (flags & kBounceShadow) != 0;
+                same_ray = !dead && ((flags >> kBounceChainShift) & 3u) == kChainTir;
                 finalize = dead && !shadow_kind;
             }
 
@@ -126,6 +131,7 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
     // one atomic per wave per counter
     wave_add_u64(&args.counters->traced_rays, cnt.rays);
     wave_add_f64(&args.counters->total_energy, energy_sum);
+    if (!COUNT) wave_add_u64(&args.counters->retrace_unwalked, cnt.unwalked);
     if (COUNT) {
         wave_add_u64(&args.counters->inner_steps, cnt.inner);
         wave_add_u64(&args.counters->tri_tests, cnt.tris);
@@ -199,7 +205,7 @@ __global__ void __launch_bounds__(256) intersect_rays_kernel(const DevScene sc, 
 {
     uint32_t* const stack = lds_stack + threadIdx.x;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    Counters cnt = { 0, 0, 0, 0, 0 };
+    Counters cnt = { 0, 0, 0, 0, 0, 0 };
     if (i < n) {
         Ray ray = make_ray(mk(origins + 3 * (size_t)i), mk(dirs + 3 * (size_t)i), tmax ? tmax[i] : 1e34f);
         intersect_scene<true, XFORM, TREE>(sc, ray, stack, blockDim.x, cnt);

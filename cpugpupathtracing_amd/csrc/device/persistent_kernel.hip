@@ -57,7 +57,8 @@ enum : uint32_t {                      // per-lane path flags
     kPfSpecular = 0x100u,              // is_specular_ray (ref: Main.cpp:402)
     kPfShadow = 0x200u,                // the ray in flight is the NEE shadow ray
     kPfDead = 0x400u,                  // the path ends once the shadow ray in flight is resolved
-    kPfBrute = 0x800u                  // this path runs TracePath (brute force)
+    kPfBrute = 0x800u,                 // this path runs TracePath (brute force)
+    kPfSameRay = 0x1000u               // the parked extend ray is the one just shaded (total internal reflection, SURVEY A-3): not walked again
 };
 
 // TAIL: the instantiation for small calls (few samples per call -- the reference's own main loop renders ONE per Render(), ref:
@@ -94,7 +95,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
     V3 park_o = mk(0.0f), park_d = mk(0.0f);                                  // the next extend ray, parked while the shadow ray is traced
     float park_t = 0.0f;
     uint32_t park_obj = kNoHit, park_tri = 0, park_depth = 0;                 // its payload: a ray traced again after total internal reflection keeps its hit (SURVEY A-3)
-    Counters cnt = { 0, 0, 0, 0, 0 };
+    Counters cnt = { 0, 0, 0, 0, 0, 0 };
 
     auto finish_path = [&](V3 energy) {                                       // ref: Main.cpp:575-578: the path's radiance leaves the kernel
         float4 o4; o4.x = energy.x; o4.y = energy.y; o4.z = energy.z; o4.w = __uint_as_float(pf & kPfDepthMask);
@@ -109,6 +110,12 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
             pf &= ~kPfShadow;
             if (pf & kPfDead) {
                 finish_path(en);
+            } else if (!COUNT && (pf & kPfSameRay)) {             // the parked ray is the one just shaded: its parked hit is the answer
+                r.t = park_t; r.obj = park_obj; r.tri = park_tri; r.depth = park_depth;   // (DESIGN.md 5.1); only what shade_hit reads is restored
+                if (XFORM) { r.wo = park_o; r.wd = park_d; }
+                else trav_set_ray(r, park_o, park_d);
+                r.code = kShade;
+                cnt.rays++; cnt.unwalked++;
             } else {
                 trav_start<XFORM, TREE>(ctx, r, park_o, park_d, park_t, park_obj, park_tri, park_depth);
                 cnt.rays++;
@@ -149,14 +156,20 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
             V3 pend = mk(0.0f);
             const uint32_t flags = shade_bounce<COUNT, GLOSSY, RIS>(sc, st, ray, ps, shadow, pend, cnt);
             tp = ps.throughput; en = ps.energy; rng = ps.rng;
-            pf = (ps.depth & kPfDepthMask) | (ps.is_specular ? kPfSpecular : 0u);
+            pf = (ps.depth & kPfDepthMask) | (ps.is_specular ? kPfSpecular : 0u);   // every other flag starts clear: kPfSameRay is this bounce's or none
             const bool dead = (flags & kBounceTerminate) != 0u;
+            // The same ray again: IntersectScene accepts only t < ray.t and ray.t is this ray's closest hit, so the call returns the hit it
+            // starts from.  It is counted and the lane shades again; the counting kernels walk it, as the oracle does.
+            const bool same_ray = !COUNT && !dead && ((flags >> kBounceChainShift) & 3u) == kChainTir;
+            if (same_ray) pf |= kPfSameRay;
             if (flags & kBounceShadow) {                          // the shadow ray first: its contribution precedes the next bounce's
                 pending = pend;
                 pf |= kPfShadow | (dead ? kPfDead : 0u);
                 park_o = ray.o; park_d = ray.d; park_t = ray.t; park_obj = ray.obj; park_tri = ray.tri; park_depth = ray.bvh_depth;
                 trav_start<XFORM, TREE>(ctx, r, shadow.o, shadow.d, shadow.t, kNoHit, 0u, 0u);
                 cnt.rays++;
+            } else if (same_ray) {                                // r still holds the ray and its hit: r.code stays kShade
+                cnt.rays++; cnt.unwalked++;
             } else if (!dead) {
                 trav_start<XFORM, TREE>(ctx, r, ray.o, ray.d, ray.t, ray.obj, ray.tri, ray.bvh_depth);
                 cnt.rays++;
@@ -227,6 +240,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
     }
 
     wave_add_u64(&args.counters->traced_rays, cnt.rays);
+    if (!COUNT) wave_add_u64(&args.counters->retrace_unwalked, cnt.unwalked);
     if (COUNT) {
         wave_add_u64(&args.counters->inner_steps, cnt.inner);
         wave_add_u64(&args.counters->tri_tests, cnt.tris);

@@ -173,17 +173,25 @@ __device__ __forceinline__ V3 bvh_depth_colour(const Ray& ray)
 // else the mirror lobe's.  `inside`: the ray travelled in the medium (Beer's law applies to a refraction out of it).  What each outcome
 // does to the path is the integrator's business.
 enum : uint32_t { kGlassTir = 0u, kGlassRefract = 1u, kGlassReflect = 2u };
-__device__ __forceinline__ uint32_t smooth_glass(const Mat& mat, const Hit& hit, const Ray& ray, uint32_t& rng, V3& dir, bool& inside)
+// the interface as the ray meets it: the normal turned against the ray, the cosine, the indices on either side, and k.  A function of the
+// ray's direction and the hit alone -- no draw -- so the same ray on the same hit gets the same k (shade_bounce: stuck iterations).
+__device__ __forceinline__ float glass_interface(const Mat& mat, const Hit& hit, const Ray& ray, V3& N, float& cosi, float& etai, float& etat, bool& inside)
 {
-    V3 N = hit.normal;
-    float cosi = clamp_std(dot(N, ray.d), -1.0f, 1.0f);
-    float etai = 1.0f, etat = mat.ior;
+    N = hit.normal;
+    cosi = clamp_std(dot(N, ray.d), -1.0f, 1.0f);
+    etai = 1.0f; etat = mat.ior;
     inside = true;
     if (cosi < 0.0f) { cosi = -cosi; inside = false; }
     else { float tmp = etai; etai = etat; etat = tmp; N = -N; }
     const float eta = etai / etat;
-    const float k = 1.0f - eta * eta * (1.0f - cosi * cosi);
+    return 1.0f - eta * eta * (1.0f - cosi * cosi);
+}
+__device__ __forceinline__ uint32_t smooth_glass(const Mat& mat, const Hit& hit, const Ray& ray, uint32_t& rng, V3& dir, bool& inside)
+{
+    V3 N; float cosi, etai, etat;
+    const float k = glass_interface(mat, hit, ray, N, cosi, etai, etat, inside);
     if (!(k >= 0.0f)) return kGlassTir;
+    const float eta = etai / etat;
     const V3 rd = refract(ray.d, N, eta, cosi, k);
     const float angle_in = dot(ray.d, hit.normal);
     const float angle_out = dot(rd, hit.normal);
@@ -368,7 +376,34 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
         ps.throughput = ps.throughput * mk(1.0f / p);
     }
 
-    const float r = random_float(ps.rng);                                     // ref: Main.cpp:478
+    float r = random_float(ps.rng);                                           // ref: Main.cpp:478
+
+    // Stuck iterations.  After total internal reflection the reference traces the same ray again (SURVEY A-3) and lands on
+    // the same hit: no emissive add (the material is no light), the same NEE decision, the roulette and lobe draws above and -- if the
+    // smooth dielectric is drawn again -- the same k < 0, until another lobe is drawn, the roulette ends the path or the depth runs out.
+    // Where this material samples no light such an iteration is nothing but those draws, so it runs here, in place: the same draws in the
+    // same order, the same throughput * (1 / p), the same depth++, and one IntersectScene call counted.  Whatever r ends the loop goes
+    // through the lobes below as it always did.  Not in the counting kernels, which walk every ray the oracle walks.
+    bool absorbed = false;
+    if (!COUNT && !(sc.n_lights > 0 && st.nee && diffuse_weight > 0.001f)) {
+        const bool rough_t = GLOSSY >= 2 && mat.alpha_t > 0.0f;
+        V3 N; float cosi, etai, etat; bool inside;
+        if (!rough_t && !(r < mat.specular) && r < mat.specular + mat.refractivity && !(glass_interface(mat, hit, ray, N, cosi, etai, etat, inside) >= 0.0f)) {
+            while ((int32_t)(ps.depth + 1u) <= st.max_ray_depth) {
+                ps.depth++;
+                cnt.rays++; cnt.unwalked++;
+                absorbed = true;
+                if (st.rr) {
+                    const float p = survival_probability_rr(mat.albedo);
+                    if (p < random_float(ps.rng)) return result | kBounceTerminate;
+                    ps.throughput = ps.throughput * mk(1.0f / p);
+                }
+                r = random_float(ps.rng);
+                if (r < mat.specular || !(r < mat.specular + mat.refractivity)) break;
+            }
+        }
+    }
+
     if (GLOSSY >= 1 && r < mat.specular && mat.alpha > 0.0f) {                     // rough specular lobe
         V3 gd; float g;
         if (!ggx_sample(ps.rng, ray.d, hit.normal, mat.alpha, gd, g)) return result | kBounceTerminate;   // below the horizon: ends as RR ends it
@@ -421,6 +456,7 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
         ps.throughput = ps.throughput * ((NdotR / pdf) * (mat.albedo * kInvPi));
         ps.is_specular = false;
     }
+    if (absorbed) result &= ~(3u << kBounceChainShift);                       // no longer a chain from the camera that an election could share: choice 0
     ps.depth++;
     if ((int32_t)ps.depth > st.max_ray_depth) result |= kBounceTerminate;     // loop condition, ref: Main.cpp:404
     return result;

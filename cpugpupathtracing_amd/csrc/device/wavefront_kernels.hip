@@ -20,9 +20,9 @@
 // byte per slot scanned by strided waves -- correct but waves own unequal numbers of live rays (59 % wave residency);
 // (3) the same with 64 partitioned head counters -- the atomics cost more than the imbalance they removed.
 // Slot entry (48 B, three float4 planes, extend slot = path id, shadow slot = cap + path id):
-//   A = {o.xyz, t_max}  B = {d.xyz, bits(depth | spec << 8 | brute << 9 | chain << 10 | follower << 31)}  C = extend: hit record
-//   {bits obj, tri, bvh_depth, t} written by trace (read by trace only when the same ray is traced again after total internal
-//   reflection, SURVEY A-3) | shadow: {pending.xyz, -}.  A follower's A.w is its leader's path id instead of t_max (see wf_shade).
+//   A = {o.xyz, t_max}  B = {d.xyz, bits(depth | spec << 8 | brute << 9 | chain << 10 | same ray << 30 | follower << 31)}  C = extend: hit record
+//   {bits obj, tri, bvh_depth, t} written by trace (a ray traced again after total internal reflection, SURVEY A-3, keeps it: the counting
+//   kernels walk that ray with it as payload, the others take it as the answer -- DESIGN.md 5.1) | shadow: {pending.xyz, -}.  A follower's A.w is its leader's path id instead of t_max (see wf_shade).
 // Round 0 has no generate kernel and no slot traffic for the rays: trace and shade both recompute the primary ray (ref: Main.cpp:713-716,
 // Camera::GetRay :133-140).  The reference does not jitter (SURVEY A-14), so trace walks the band's pixels, not the paths: one ray per
 // pixel, its 16-byte hit record in px_hit[pixel], counted once per sample.  Shade reads the record of the path's pixel and initialises
@@ -98,6 +98,7 @@ struct WfDev {
 // trace skips them, and the next shade reads the leader's hit record (C and hit_flag of the leader's slot: neither changes between
 // that trace and the next).  Each follower still shades with its own RNG stream, throughput and Beer factor.
 static constexpr uint32_t kChainShift = 10u, kChainMax = 0xFFFFu, kFollowerBit = 0x80000000u, kNoLeader = 0xFFFFFFFFu;
+static constexpr uint32_t kSameRayBit = 0x40000000u;   // B.w: shade_bounce left the ray as it was (total internal reflection): A.w is its hit's t, C its hit record
 
 // Called by the lanes that emit an extend ray; `chain` = 0: no election for this lane.  Returns the path id of the leader of the
 // lane's (pixel, chain) -- the lane's own when it leads -- or kNoLeader when the pixel's entries are all taken (traced as usual).
@@ -168,7 +169,8 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
     uint32_t slot_of_lane = 0;
     uint32_t wave_rays = 0;                                                   // wave-uniform: rays this wave started (later rounds)
     uint32_t wave_followers = 0;                                              // wave-uniform: of those, followers of a specular chain (not traced)
-    Counters cnt = { 0, 0, 0, 0, 0 };
+    uint32_t wave_unwalked = 0;                                               // wave-uniform: of those, traced again after total internal reflection (not walked)
+    Counters cnt = { 0, 0, 0, 0, 0, 0 };
 
     auto finish_ray = [&]() {                                                 // the ray of this lane has seen every object of the scene
         // The slot's addresses are formed here, when the ray ends: left to the optimiser they are hoisted to where the slot is assigned
@@ -225,7 +227,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
         if (n_need && ring_count) {
             const uint32_t take = min(n_need, ring_count);
             const uint32_t rank = rank_in_mask(need);
-            bool followed = false;
+            bool followed = false, unwalked = false;
             if (r.code == kIdle && rank < take) {
                 const uint32_t slot = ring[ring_count - 1u - rank];
                 slot_of_lane = slot;
@@ -238,11 +240,15 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
                 } else {
                     const float4 a = ld_stream(&wf.A[slot]), b = ld_stream(&wf.B[slot]);
                     o = mk(a.x, a.y, a.z); t = a.w; d = mk(b.x, b.y, b.z);
-                    if (!COUNT && slot < wf.cap && (__float_as_uint(b.w) & kFollowerBit)) {   // its leader traces this ray (wf_shade: specular chains)
-                        ok = false; followed = true;
-                        if (wf.retire_misses) wf.hit_flag[slot] = 1;          // shade reads the leader's hit or miss
-                    } else if (slot < wf.cap && t != 1e34f) {                 // the same ray again after total internal reflection:
-                        const float4 c = ld_stream(&wf.C[slot]);              // it keeps its previous hit as payload (SURVEY A-3)
+                    // Not walked: a follower -- its leader traces this ray (wf_shade: specular chains) and shade reads the leader's hit or miss --
+                    // and the same ray again after total internal reflection (SURVEY A-3; wf_shade marks it): that walk can only return the hit
+                    // it starts from.  C[slot] holds it, and hit_flag[slot] is 1 since that hit was found (round 0: wf_shade set it).
+                    if (!COUNT && slot < wf.cap && (__float_as_uint(b.w) & (kFollowerBit | kSameRayBit))) {
+                        ok = false;
+                        followed = (__float_as_uint(b.w) & kFollowerBit) != 0u; unwalked = !followed;
+                        if (followed && wf.retire_misses) wf.hit_flag[slot] = 1;
+                    } else if (slot < wf.cap && t != 1e34f) {                 // the counting kernels walk it, as the oracle does:
+                        const float4 c = ld_stream(&wf.C[slot]);              // it keeps its previous hit as payload
                         obj = __float_as_uint(c.x); tri = __float_as_uint(c.y); depth = __float_as_uint(c.z);
                     }
                 }
@@ -255,7 +261,10 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
             __builtin_amdgcn_wave_barrier();
             ring_count -= take;
             if (!first_round) wave_rays += take;
-            if (!COUNT && !first_round) wave_followers += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(followed));
+            if (!COUNT && !first_round) {
+                wave_followers += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(followed));
+                wave_unwalked += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(unwalked));
+            }
         }
         // Done when nothing is in flight and nothing is left to fetch.  Nothing in flight alone is not enough: every id just handed
         // out may have been padding of an edge tile (round 0: a padded row of a tile; later rounds never list one); the step loop below
@@ -304,6 +313,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
     if (first_round) wave_add_u64(&counters->traced_rays, cnt.rays, per_ray);
     else if (lane_id() == 0u && wave_rays) atomicAdd(&counters->traced_rays, (unsigned long long)wave_rays);
     if (!COUNT && !first_round && lane_id() == 0u && wave_followers) atomicAdd(&counters->chain_followers, (unsigned long long)wave_followers);
+    if (!COUNT && !first_round && lane_id() == 0u && wave_unwalked) atomicAdd(&counters->retrace_unwalked, (unsigned long long)wave_unwalked);
     if (COUNT) {
         wave_add_u64(&counters->inner_steps, cnt.inner, per_ray);
         wave_add_u64(&counters->tri_tests, cnt.tris, per_ray);
@@ -335,7 +345,7 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
     // over it, and the part of the tree they walk stays in the 4 MB L2 of every XCD.
     const bool banded = wf.n_bands > 1u;
     uint32_t cur_band = 0, band_start_ext = 0, band_start_sh = 0;             // wave-uniform
-    Counters cnt = { 0, 0, 0, 0, 0 };
+    Counters cnt = { 0, 0, 0, 0, 0, 0 };
     // Probe.  More than half of the later rounds' rays of the reference scene are decided by the top of IntersectScene alone: they miss both
     // halves of the mesh's box, the ground quad and the light spheres -- shadow rays of ground pixels towards the lights, their bounce
     // rays into the sky.  probe_scene() (rt_device.hpp) answers those here, from the registers that hold the ray, with the trace kernels'
@@ -343,9 +353,10 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
     // read-modify-write moved; occluded: dropped), an extend ray decided as a miss ends its path now instead of in the next round.  Each
     // is still one IntersectScene call of the reference and is counted as one.  Not probed: the counting kernels (they walk as the oracle
     // walks), TracePath lanes, the debug views (they read the last depth), rays of a specular chain (the election and its followers stay
-    // as they are) and a ray re-traced after total internal reflection (it carries its payload).
+    // as they are) and a ray re-traced after total internal reflection (wf_trace does not walk it at all: its hit is known).
     const bool probe = !COUNT && wf.probe != 0u;                              // wave-uniform
     uint32_t wave_probed = 0;                                                 // wave-uniform: rays this wave decided
+    uint32_t wave_absorbed = 0;                                               // wave-uniform: stuck iterations shade_bounce ran in place
 
     // The order in which a wave appends its survivors is the order of the next round's ray list.  Taking runs of `chunk`
     // consecutive blocks (the samples of one pixel and of its neighbours in round 0, and their descendants later) keeps the rays of
@@ -377,6 +388,7 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
         bool emit_ext = false, emit_sh = false;
         bool decided_sh = false, decided_ext = false;                         // probe: the ray is resolved here and not listed
         uint32_t pid = 0;
+        uint32_t absorbed = 0;                                                // at most the depth limit: eight bits
         if (!hits_only) {
             if (!more) break;
             const uint32_t i = block * 64u + lane_id();
@@ -457,6 +469,7 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
                     flags = done ? kBounceTerminate | kBounceBruteDone : 0u;
                 }
             } else if (is_pixel) flags = shade_bounce<COUNT, GLOSSY, RIS>(sc, args.settings, ray, ps, shadow, pending, cnt);
+            if (!COUNT) { absorbed = cnt.unwalked; cnt.unwalked = 0; }       // shade_bounce's stuck iterations, each an IntersectScene call of the reference
             emit_ext = (flags & kBounceTerminate) == 0u;
             emit_sh = (flags & kBounceShadow) != 0u;
             if (kChains && emit_ext) {
@@ -500,6 +513,7 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
                 na.x = ray.o.x; na.y = ray.o.y; na.z = ray.o.z; na.w = ray.t;    // 1e34 for a fresh ray, the hit t for a re-traced one
                 nb.x = ray.d.x; nb.y = ray.d.y; nb.z = ray.d.z;
                 uint32_t fl = (ps.depth & 0xFFu) | (ps.is_specular ? 0x100u : 0u) | ((BRUTE && brute_path) ? 0x200u : 0u);
+                if (((flags >> kBounceChainShift) & 3u) == kChainTir && !(BRUTE && brute_path)) fl |= kSameRayBit;
                 if (kChains) {
                     fl |= chain << kChainShift;
                     if (wf.spec_tab) {
@@ -510,8 +524,10 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
                 nb.w = __uint_as_float(fl);
                 st_stream(&wf.A[pid], na); st_stream(&wf.B[pid], nb);         // C keeps the hit record (payload of a re-traced ray)
                 if ((first_round || followed) && ray.t != 1e34f) st_stream(&wf.C[pid], c);   // round 0 kept it per pixel, a follower's came from
-                                                                              // its leader: the re-traced ray's payload goes to its slot (trace reads
-                                                                              // C exactly when A.w != 1e34)
+                                                                              // its leader: the re-traced ray's hit record goes to its slot (the
+                                                                              // counting trace reads C exactly when A.w != 1e34; the others leave it)
+                if (first_round && !COUNT && wf.retire_misses && ray.t != 1e34f) wf.hit_flag[pid] = 1;   // and its hit byte, which trace will not write: a
+                                                                              // ray traced again is not walked (later rounds: the byte is 1 from its walk)
             }
             if (emit_sh) {                                                    // NEE connection, slot cap + pid
                 const uint32_t ss = wf.cap + pid;
@@ -525,6 +541,8 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
         // active-lane compaction into the wave's own segments: __ballot + mbcnt, no atomics
         const unsigned long long m_ext = __builtin_amdgcn_ballot_w64(emit_ext), m_sh = __builtin_amdgcn_ballot_w64(emit_sh);
         if (probe) wave_probed += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(decided_sh)) + (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(decided_ext));
+        if (!COUNT && __builtin_amdgcn_ballot_w64(absorbed != 0u) != 0ull)    // summed over the wave bit by bit: no per-lane total rides through the loop
+            for (uint32_t b = 0; b < 8u; ++b) wave_absorbed += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64((absorbed >> b) & 1u)) << b;
         if (banded) {                                                         // close the runs of the bands this pass has left behind
             const uint32_t band = min(wf.n_bands - 1u, __umulhi(pid, wf.band_magic));
             const bool emits = emit_ext | emit_sh;
@@ -557,6 +575,10 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
     if (!COUNT && lane_id() == 0u && wave_probed) {                           // every decided ray is an IntersectScene call of the reference
         atomicAdd(&args.counters->traced_rays, (unsigned long long)wave_probed);
         atomicAdd(&args.counters->probe_resolved, (unsigned long long)wave_probed);
+    }
+    if (!COUNT && lane_id() == 0u && wave_absorbed) {
+        atomicAdd(&args.counters->traced_rays, (unsigned long long)wave_absorbed);
+        atomicAdd(&args.counters->retrace_unwalked, (unsigned long long)wave_absorbed);
     }
 }
 

@@ -270,6 +270,9 @@ class Renderer:
     def stats(self) -> N.Stats:
         s = N.Stats()
         self._check(self.L.cgpt_get_stats(self._ctx, C.byref(s)))
+        unwalked = C.c_uint64()                                      # cgpt_stats keeps its size: this counter has an accessor of its own
+        self._check(self.L.cgpt_get_retrace_unwalked(self._ctx, C.byref(unwalked)))
+        s.retrace_unwalked = unwalked.value
         return s
 
     def reset_stats(self):

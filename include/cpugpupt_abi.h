@@ -312,6 +312,13 @@ int cgpt_pixels_device_ptr(cgpt_ctx* ctx, void** ptr, size_t* n_bytes);
 /* replaces data.stats / total_energy_received (ref: Main.cpp:207,218-226,847-848) */
 int cgpt_get_stats(cgpt_ctx* ctx, cgpt_stats* out);
 int cgpt_reset_stats(cgpt_ctx* ctx);
+/* One more counter of the same kind, with an accessor of its own because cgpt_stats keeps the size it has at ABI version 2: the
+ * IntersectScene calls on a ray traced again after total internal reflection (SURVEY A-3) that the render kernels answered with the
+ * ray's known hit instead of a walk.  Each is counted in traced_rays too; 0 with CGPT_RENDER_COUNTERS.  Since the last
+ * cgpt_reset_stats; a multi-device context returns the sum over its devices.  An added export changes no existing symbol or layout, so
+ * CGPT_ABI_VERSION stays 2, as it did for cgpt_set_nee_candidates; the Python binding resolves every declared symbol when it loads the
+ * library, so an older library is refused there. */
+int cgpt_get_retrace_unwalked(cgpt_ctx* ctx, uint64_t* out);
 
 /* IntersectScene for a batch of host rays (ref: Main.cpp:299-316): the extend kernel on its own.
  * origins/dirs: n*3 floats; tmax: n floats or NULL (1e34f, ref: Primitives.h:75); outputs n entries each:
