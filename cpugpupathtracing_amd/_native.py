@@ -91,6 +91,20 @@ class DenoiseParams(C.Structure):
                 ("sigma_position", C.c_float)]
 
 
+class ShadeSample(C.Structure):
+    """cgpt_shade_sample: a traced ray with its hit record and the path state before the bounce (16 words)."""
+    _fields_ = [("o", f3), ("d", f3), ("t", C.c_float), ("obj", C.c_uint32), ("tri", C.c_uint32), ("bvh_depth", C.c_uint32),
+                ("throughput", f3), ("rng", C.c_uint32), ("depth", C.c_uint32), ("is_specular", C.c_uint32)]
+
+
+class ShadeResult(C.Structure):
+    """cgpt_shade_result: what one bounce left (28 words)."""
+    _fields_ = [("flags", C.c_uint32), ("o", f3), ("d", f3), ("throughput", f3), ("energy", f3),
+                ("rng", C.c_uint32), ("depth", C.c_uint32), ("is_specular", C.c_uint32),
+                ("shadow_o", f3), ("shadow_d", f3), ("shadow_tmax", C.c_float), ("pending", f3),
+                ("unwalked", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class BvhInfo(C.Structure):
     _fields_ = [("num_triangles", C.c_uint32), ("nodes_used", C.c_uint32), ("num_leaves", C.c_uint32),
                 ("max_leaf_size", C.c_uint32), ("max_depth", C.c_uint32), ("total_area", C.c_float)]
@@ -150,6 +164,7 @@ PROTOTYPES = {
     "cgpt_reset_stats": (C.c_int, [_vp]),
     "cgpt_get_retrace_unwalked": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "cgpt_intersect_rays": (C.c_int, [_vp, _fp, _fp, _fp, C.c_uint32, _fp, _up, _up, _up]),
+    "cgpt_shade_samples": (C.c_int, [_vp, C.POINTER(Settings), C.POINTER(ShadeSample), C.c_uint32, C.POINTER(ShadeResult)]),
     "cgpt_bvh_build": (C.c_int, [_vp, C.POINTER(Triangle), C.c_uint32, C.POINTER(BvhNode), _up, _up, _up, _fp]),
     "cgpt_bvh_build_ex": (C.c_int, [_vp, C.POINTER(Triangle), C.c_uint32, C.c_uint32, _up, C.POINTER(BvhNode), _up, _up, _up, _fp]),
     "cgpt_synchronize": (C.c_int, [_vp]),

@@ -208,6 +208,8 @@ __device__ __forceinline__ float ggx_lambda(float a2, float z)
     return 0.5f * (-1.0f + sqrtf(1.0f + a2 * (max_std(0.0f, 1.0f - z * z) / (z * z))));
 }
 
+static constexpr float kGgxMinCosSq = 1.17549435e-38f;                       // FLT_MIN: 1 / oz^2 stays finite from here up
+
 // A microfacet normal h from the visible normals of wo = -d (Heitz 2018, JCGT 7(4)) around n, the shading normal turned to face the ray,
 // with the two floats u1, u2.  oz = wo.n.  Returns false when wo lies at or below the horizon of n (h is then not set).
 __device__ __forceinline__ bool ggx_visible_normal(float u1, float u2, V3 d, V3 normal, float alpha, V3& n, float& oz, V3& h)
@@ -220,7 +222,9 @@ __device__ __forceinline__ bool ggx_visible_normal(float u1, float u2, V3 d, V3 
     const V3 wo = -d;
     const float ox = dot(wo, tx), oy = dot(wo, ty);
     oz = dot(wo, n);
-    if (!(oz > 0.0f)) return false;
+    // ... or so close above it that oz^2 is below the smallest normal float (oz < 1.09e-19): ggx_lambda's tan^2 = (1 - oz^2) / oz^2 would be inf
+    // and the weight inf / inf.  The lobe's limit there is a weight of 1 on a direction below the horizon: no energy, as for oz <= 0.
+    if (!(oz > 0.0f) || !(oz * oz >= kGgxMinCosSq)) return false;
     const V3 vh = normalize(mk(alpha * ox, alpha * oy, oz));                  // stretch wo to the alpha = 1 configuration
     const float lensq = vh.x * vh.x + vh.y * vh.y;
     const V3 t1 = lensq > 0.0f ? mk(-vh.y, vh.x, 0.0f) * (1.0f / sqrtf(lensq)) : mk(1.0f, 0.0f, 0.0f);

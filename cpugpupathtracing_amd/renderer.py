@@ -23,6 +23,17 @@ def _all_identity(matrices) -> bool:
     return bool(np.array_equal(v.view(np.uint32), np.broadcast_to(_IDENTITY.view(np.uint32), v.shape)))
 
 
+# cgpt_shade_sample / cgpt_shade_result as numpy records (Renderer.shade_samples)
+SHADE_SAMPLE = np.dtype([("o", np.float32, 3), ("d", np.float32, 3), ("t", np.float32), ("obj", np.uint32), ("tri", np.uint32),
+                         ("bvh_depth", np.uint32), ("throughput", np.float32, 3), ("rng", np.uint32), ("depth", np.uint32),
+                         ("is_specular", np.uint32)])
+SHADE_RESULT = np.dtype([("flags", np.uint32), ("o", np.float32, 3), ("d", np.float32, 3), ("throughput", np.float32, 3),
+                         ("energy", np.float32, 3), ("rng", np.uint32), ("depth", np.uint32), ("is_specular", np.uint32),
+                         ("shadow_o", np.float32, 3), ("shadow_d", np.float32, 3), ("shadow_tmax", np.float32),
+                         ("pending", np.float32, 3), ("unwalked", np.uint32), ("reserved", np.uint32)])
+assert SHADE_SAMPLE.itemsize == C.sizeof(N.ShadeSample) and SHADE_RESULT.itemsize == C.sizeof(N.ShadeResult)
+
+
 class DeviceError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"[cgpt status {code}] {message}")
@@ -290,6 +301,17 @@ class Renderer:
                                                tm.ctypes.data_as(fp) if tm is not None else None, n, t.ctypes.data_as(fp),
                                                obj.ctypes.data_as(up), tri.ctypes.data_as(up), dep.ctypes.data_as(up)))
         return t, obj, tri, dep
+
+    def shade_samples(self, samples, settings: Optional[Settings] = None) -> np.ndarray:
+        """cgpt_shade_samples: one bounce of TracePathAdvanced on each record of `samples` (SHADE_SAMPLE: a traced ray with its hit
+        record, obj 0xFFFFFFFF for a miss, and the path state before the bounce), in the instantiation a render of this context runs.
+        Returns SHADE_RESULT records.  settings: default the uploaded scene's.  Nothing is traced; the accumulator and stats stay."""
+        a = np.ascontiguousarray(samples, SHADE_SAMPLE).ravel()
+        out = np.zeros(a.size, SHADE_RESULT)
+        st = settings.to_abi() if settings is not None else self.scene.settings()
+        self._check(self.L.cgpt_shade_samples(self._ctx, C.byref(st), a.ctypes.data_as(C.POINTER(N.ShadeSample)), a.size,
+                                              out.ctypes.data_as(C.POINTER(N.ShadeResult))))
+        return out
 
     def build_bvh(self, triangles, n_tris: int, build_option: int = N.BUILD_SAH_INTERVALS, initial_tri_indices=None):
         """BVH::Build (or, with initial_tri_indices = the current m_tri_indices, BVH::Rebuild) on the GPU for any BuildOption

@@ -326,6 +326,35 @@ int cgpt_get_retrace_unwalked(cgpt_ctx* ctx, uint64_t* out);
 int cgpt_intersect_rays(cgpt_ctx* ctx, const float* origins, const float* dirs, const float* tmax, uint32_t n,
                         float* out_t, uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth);
 
+/* One bounce of TracePathAdvanced (ref: Main.cpp:404-573) for a batch of host samples: the shade step on its own, the counterpart of
+ * cgpt_intersect_rays.  Sample i is a traced ray -- world o, d and its hit record t, obj (~0u: a miss), tri, bvh_depth -- and the
+ * path's state before the bounce.  The kernel runs the render kernels' own bounce function once per sample, in the instantiation a
+ * render of this context would run: the context's lobe level (roughness, transmission roughness, smooth normals, transforms) and the
+ * resampled NEE when cgpt_set_nee_candidates is above 1 and settings enables NEE.  settings->render_mode selects nothing -- the bounce is
+ * TracePathAdvanced's -- but a value cgpt_render refuses is refused here too.  Out: the bounce's return word (bit 0 the path ends, bit 1 a shadow ray is pending, bit 2 energy was added,
+ * bits 4-5 the specular-chain choice), the next ray, the state after the bounce, the bounce's own energy (from 0), the shadow ray
+ * and its pending contribution (zeros while bit 1 is clear) and the number of re-traces after total internal reflection that ran in
+ * place.  No ray is traced and no random number is drawn on the host.
+ * Refusals, all before any device work (a refused call changes nothing): no scene CGPT_ERR_NO_SCENE; a NULL argument, n == 0 or
+ * n > 65536, obj neither ~0u nor an object index, a mesh hit whose tri is not below the mesh's triangle count (a triangle object
+ * ignores tri), a hit whose t, o, d or throughput is not finite, depth > 255, or settings cgpt_render refuses: CGPT_ERR_INVALID.
+ * A multi-device context runs it on its first device.  Reads the scene; the accumulator, cgpt_stats and the guides stay as they are.
+ * An added export: CGPT_ABI_VERSION stays 2. */
+typedef struct cgpt_shade_sample {
+    float o[3], d[3], t;
+    uint32_t obj, tri, bvh_depth;
+    float throughput[3];
+    uint32_t rng, depth, is_specular;   /* rng: the raw PCG state */
+} cgpt_shade_sample;
+typedef struct cgpt_shade_result {
+    uint32_t flags;
+    float o[3], d[3], throughput[3], energy[3];
+    uint32_t rng, depth, is_specular;
+    float shadow_o[3], shadow_d[3], shadow_tmax, pending[3];
+    uint32_t unwalked, reserved;        /* reserved: 0 */
+} cgpt_shade_result;
+int cgpt_shade_samples(cgpt_ctx* ctx, const cgpt_settings* settings, const cgpt_shade_sample* samples, uint32_t n, cgpt_shade_result* results);
+
 /* BVH::Build with BVHBuildOption_SAHSplitIntervals on the GPU (ref: Source/BVH.cpp:11-45,204-259,299-366; Main.cpp:789,802 use
  * this option for every mesh).  The result is the reference's tree bit for bit: same 32-byte nodes in the same allocation order,
  * same m_tri_indices permutation, same m_max_depth / m_total_area -- so it can be passed to cgpt_scene_upload (cgpt_object

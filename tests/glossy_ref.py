@@ -8,12 +8,24 @@ the directional albedo
     R(cos theta_o, alpha) = (1 / cos theta_o) * integral of D(h) G2(wo, wi(h)) (wo.h) [wo.h > 0, wi.n > 0] over the hemisphere of h,
 wi(h) = reflect(-wo, h).
 
+Horizon rule (shade_device.hpp: ggx_visible_normal; tests/shade_ref.py states it per sample): a direction wo whose cosine to n is not > 0,
+or whose squared cosine is below the smallest normal float32 (HORIZON_COS_SQ; cos < 1.09e-19), is at the horizon -- tan^2 of its angle is
+not a float32 and L(wo) would be inf.  The lobe has no energy there: its limit is a weight of 1 on a direction below the horizon.
+
 Quadrature: with x = tan(theta_h) / alpha and s = 1 / (1 + x^2), D(h) cos(theta_h) dw_h = ds dphi / (2 pi) exactly, so the peak of D at
 small alpha costs nothing: the integrand left in (s, phi) is G2 (wo.h) / cos(theta_h), smooth up to the two indicator edges.
 """
 from __future__ import annotations
 
 import numpy as np
+
+
+HORIZON_COS_SQ = float(np.float32(1.17549435e-38))
+
+
+def above_horizon(cos_o) -> bool:
+    """The horizon rule of the module docstring."""
+    return bool(cos_o > 0.0 and cos_o * cos_o >= HORIZON_COS_SQ)
 
 
 def alpha_of(roughness: float) -> float:
@@ -84,6 +96,8 @@ def sample_vndf(wo, alpha, u1, u2):
 
 def vndf_estimate(cos_o: float, alpha: float, n: int, seed: int = 1):
     """Monte Carlo of R with the kernels' estimator: G2/G1 per VNDF sample, 0 below the horizon.  Returns (mean, standard error)."""
+    if not above_horizon(cos_o):
+        return 0.0, 0.0                                              # the horizon rule: no energy
     rng = np.random.default_rng(seed)
     sin_o = np.sqrt(max(0.0, 1.0 - cos_o * cos_o))
     wo = np.array([sin_o, 0.0, cos_o])

@@ -100,13 +100,15 @@ def interface_estimate(cos_o: float, alpha: float, etai: float, etat: float, n: 
 
 
 # ---- (b) the layered slab ---------------------------------------------------------------------------------------------------------------
-def _visible_normals(wo, alpha, u1, u2):
-    """Heitz 2018 visible-normal sampling for one wo per row, local frame n = +z (glossy_ref.sample_vndf takes a single wo)."""
+def _visible_normals(wo, alpha, u1, u2, lengths=False):
+    """Heitz 2018 visible-normal sampling for one wo per row, local frame n = +z (glossy_ref.sample_vndf takes a single wo).  Every
+    operation in wo's float type (tests/shade_ref.py evaluates it in float32 too); alpha a number or one per row.  lengths: also return
+    the length of the unstretched vector before it is normalised (how well conditioned h is: nh is a unit vector with float errors)."""
     vh = np.stack([alpha * wo[:, 0], alpha * wo[:, 1], wo[:, 2]], axis=1)
     vh /= np.linalg.norm(vh, axis=1, keepdims=True)
     lensq = vh[:, 0] ** 2 + vh[:, 1] ** 2
     inv = 1.0 / np.sqrt(np.where(lensq > 0.0, lensq, 1.0))
-    t1 = np.where((lensq > 0.0)[:, None], np.stack([-vh[:, 1] * inv, vh[:, 0] * inv, np.zeros_like(inv)], axis=1), np.array([1.0, 0.0, 0.0]))
+    t1 = np.where((lensq > 0.0)[:, None], np.stack([-vh[:, 1] * inv, vh[:, 0] * inv, np.zeros_like(inv)], axis=1), np.array([1.0, 0.0, 0.0], vh.dtype))
     t2 = np.cross(vh, t1)
     r, ph = np.sqrt(u1), 2.0 * np.pi * u2
     p1 = r * np.cos(ph)
@@ -115,7 +117,8 @@ def _visible_normals(wo, alpha, u1, u2):
     p3 = np.sqrt(np.maximum(0.0, 1.0 - p1 * p1 - p2 * p2))
     nh = p1[:, None] * t1 + p2[:, None] * t2 + p3[:, None] * vh
     h = np.stack([alpha * nh[:, 0], alpha * nh[:, 1], np.maximum(0.0, nh[:, 2])], axis=1)
-    return h / np.linalg.norm(h, axis=1, keepdims=True)
+    length = np.linalg.norm(h, axis=1, keepdims=True)
+    return (h / length, length[:, 0]) if lengths else h / length
 
 
 def slab(cos_o: float, alpha: float, ior: float, albedo, sigma, thickness: float, l_up, l_down, max_ray_depth: int, n: int,

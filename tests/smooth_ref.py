@@ -37,9 +37,12 @@ def _cross(a, b):
                      a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], -1)
 
 
-def smooth_normal(p0, p1, p2, n0, n1, n2, P, d, dtype=np.float64):
+def smooth_normal(p0, p1, p2, n0, n1, n2, P, d, dtype=np.float64, margins=False, invert_side=None):
     """(normal (..., 3), rule (...)) for hits given as arrays of shape (..., 3); every operation in `dtype`.
-    The bitwise comparison of step 1 is made on the float32 values, as the device makes it."""
+    The bitwise comparison of step 1 is made on the float32 values, as the device makes it.
+    margins: also return, per hit, how far the tests of steps 4 and 5 are from their thresholds -- l2 against 1e-12 relative to the larger,
+    dot(g, ns), dn and dn * dot(d, g) against 0 relative to the sum of the magnitudes of each dot's three products -- the smallest of
+    them (inf where step 1 decided).  invert_side: hits whose step-5 outcome is taken the other way (tests/shade_ref.py: undecided hits)."""
     f32 = [np.ascontiguousarray(np.broadcast_arrays(n0, n1, n2)[k], np.float32) for k in range(3)]
     equal = np.all((f32[0].view(np.uint32) == f32[1].view(np.uint32)) & (f32[0].view(np.uint32) == f32[2].view(np.uint32)), -1)
     p0, p1, p2, n0, n1, n2, P, d = (np.asarray(a, dtype) for a in (p0, p1, p2, n0, n1, n2, P, d))
@@ -55,7 +58,10 @@ def smooth_normal(p0, p1, p2, n0, n1, n2, P, d, dtype=np.float64):
         ns = m / np.sqrt(l2)[..., None]
         g = np.where((_dot(g, ns) < 0)[..., None], -g, g)
         dn = _dot(d, ns)
-        geometric = (dn * _dot(d, g) < 0) | (dn == 0)
+        dg = _dot(d, g)
+        geometric = (dn * dg < 0) | (dn == 0)
+        if invert_side is not None:
+            geometric = geometric ^ np.asarray(invert_side, bool)
         gn = g * (one / np.sqrt(_dot(g, g)))[..., None]
     no_length = ~(l2 > dtype(L2_MIN))
     shape = np.broadcast(no_length, equal).shape
@@ -65,6 +71,15 @@ def smooth_normal(p0, p1, p2, n0, n1, n2, P, d, dtype=np.float64):
     rule[np.broadcast_to(equal, shape)] = EQUAL_NORMALS
     out = np.where((rule == GEOMETRIC)[..., None], gn, ns)
     out = np.where(((rule == NO_LENGTH) | (rule == EQUAL_NORMALS))[..., None], np.broadcast_to(n0, out.shape), out)
+    if margins:
+        def rel(x, a, b):
+            scale = (np.abs(a[..., 0] * b[..., 0]) + np.abs(a[..., 1] * b[..., 1])) + np.abs(a[..., 2] * b[..., 2])
+            return np.where(scale > 0, np.abs(x) / np.where(scale > 0, scale, 1), 0.0)
+        with np.errstate(all="ignore"):
+            m = np.minimum(np.abs(l2 - dtype(L2_MIN)) / np.maximum(np.abs(l2), dtype(L2_MIN)), rel(_dot(g, ns), g, ns))
+            m = np.minimum(m, np.minimum(rel(dn, d, ns), rel(dg, d, g)))
+        m = np.where(np.isnan(m), 0.0, m).astype(np.float64)
+        return out.astype(dtype), rule, np.where(np.broadcast_to(equal, shape), np.inf, m)
     return out.astype(dtype), rule
 
 

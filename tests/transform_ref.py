@@ -63,23 +63,23 @@ def invert(m):
     return rec if np.all(np.isfinite(rec)) else None
 
 
-def ray_to_object(rec, o, d):
-    """(o', d') of world rays o, d (..., 3) under the records rec (3, 4), float32."""
-    rec = np.asarray(rec, np.float32)
-    o = np.asarray(o, np.float32); d = np.asarray(d, np.float32)
+def ray_to_object(rec, o, d, dtype=np.float32):
+    """(o', d') of world rays o, d (..., 3) under the records rec (3, 4); every operation in `dtype` (the device's: float32)."""
+    rec = np.asarray(rec, np.float32).astype(dtype)
+    o = np.asarray(o, dtype); d = np.asarray(d, dtype)
     oo = np.stack([((rec[i, 0] * o[..., 0] + rec[i, 1] * o[..., 1]) + rec[i, 2] * o[..., 2]) + rec[i, 3] for i in range(3)], -1)
     od = np.stack([(rec[i, 0] * d[..., 0] + rec[i, 1] * d[..., 1]) + rec[i, 2] * d[..., 2] for i in range(3)], -1)
-    return oo.astype(np.float32), od.astype(np.float32)
+    return oo.astype(dtype), od.astype(dtype)
 
 
-def normal_to_world(rec, n):
-    """normalize(Ainv^T n) of object-space normals n (..., 3), float32."""
-    rec = np.asarray(rec, np.float32)
-    n = np.asarray(n, np.float32)
+def normal_to_world(rec, n, dtype=np.float32):
+    """normalize(Ainv^T n) of object-space normals n (..., 3); every operation in `dtype` (the device's: float32)."""
+    rec = np.asarray(rec, np.float32).astype(dtype)
+    n = np.asarray(n, dtype)
     with np.errstate(all="ignore"):
-        a = np.stack([(rec[0, j] * n[..., 0] + rec[1, j] * n[..., 1]) + rec[2, j] * n[..., 2] for j in range(3)], -1).astype(np.float32)
-        rcp = np.float32(1.0) / np.sqrt((a[..., 0] * a[..., 0] + a[..., 1] * a[..., 1]) + a[..., 2] * a[..., 2])
-        return (a * rcp[..., None]).astype(np.float32)
+        a = np.stack([(rec[0, j] * n[..., 0] + rec[1, j] * n[..., 1]) + rec[2, j] * n[..., 2] for j in range(3)], -1).astype(dtype)
+        rcp = dtype(1.0) / np.sqrt((a[..., 0] * a[..., 0] + a[..., 1] * a[..., 1]) + a[..., 2] * a[..., 2])
+        return (a * rcp[..., None]).astype(dtype)
 
 
 def _dot(a, b):
