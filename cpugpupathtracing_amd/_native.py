@@ -21,6 +21,7 @@ CTX_FORCE_COLLECTIVE, CTX_GATHER_PEER_COPY = 1, 2
 BUILD_NAIVE, BUILD_SAH_INTERVALS, BUILD_SAH_PRIMITIVES = 0, 1, 2
 BUILD_SAH_BINNED = 3        # not in the reference: 16 bins per axis, stable partition (include/cpugpupt_abi.h)
 DENOISE_DEMODULATE_ALBEDO = 1
+TEMPORAL_KEEP_VIEW_DEPENDENT = 1
 
 f3 = C.c_float * 3
 
@@ -89,6 +90,10 @@ class Stats(C.Structure):
 class DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("flags", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
                 ("sigma_position", C.c_float)]
+
+
+class TemporalParams(C.Structure):
+    _fields_ = [("max_history", C.c_float), ("normal_cos_min", C.c_float), ("plane_tolerance", C.c_float), ("flags", C.c_uint32)]
 
 
 class ShadeSample(C.Structure):
@@ -172,6 +177,10 @@ PROTOTYPES = {
     "cgpt_set_tuning": (C.c_int, [_vp, C.c_char_p, C.c_uint32]),
     "cgpt_read_guides": (C.c_int, [_vp, C.POINTER(Camera), _fp, C.c_size_t]),
     "cgpt_denoise": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(DenoiseParams), _fp, C.c_size_t, _up, C.c_size_t]),
+    "cgpt_denoise_temporal": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(DenoiseParams), C.POINTER(TemporalParams), _fp, C.c_size_t, _up,
+                                        C.c_size_t]),
+    "cgpt_temporal_reset": (C.c_int, [_vp]),
+    "cgpt_read_temporal_history": (C.c_int, [_vp, _fp, C.c_size_t]),
     "cgpt_measure_issue_rate": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     # cpugpupt_host.h
     "cgpth_last_error": (C.c_char_p, []),

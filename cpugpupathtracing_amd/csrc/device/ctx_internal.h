@@ -34,6 +34,8 @@ struct DenoiseBuffers {                           // denoise.hip; each group is 
     DevBuf<float4> guide_demod;                   // per pixel: the albedo the filter divides by ({1,1,1} where it does not)
     DevBuf<float4> filter[2];                     // the filter's ping-pong buffers
     DevBuf<uint32_t> filter_pixels;
+    DevBuf<float4> history[2];                    // cgpt_denoise_temporal: per pixel {merged colour, history length H}, ping-pong
+    DevBuf<float4> history_guides[2];             // 2 float4 per pixel {x.xyz, t | n.xyz, bits(obj)} of the frame each history belongs to
 };
 template <class... B> void ResetAll(B&... b) { (b.Reset(), ...); }
 }  // namespace cgpt
@@ -118,6 +120,13 @@ struct cgpt_ctx {
     uint64_t guide_generation = 0;                // what the guides were computed for
     cgpt_camera guide_camera{};
     uint32_t guide_frame[4] = { 0, 0, 0, 0 };     // width, height, first global row, rows
+    // the temporal history (cgpt_denoise_temporal): dn.history[temporal_slot] and what it was stored for
+    bool temporal_valid = false;
+    uint32_t temporal_slot = 0;
+    uint32_t temporal_demodulate = 0;
+    uint64_t temporal_generation = 0;
+    cgpt_camera temporal_camera{};
+    uint32_t temporal_frame[4] = { 0, 0, 0, 0 };  // as guide_frame
 };
 
 

@@ -1,4 +1,5 @@
-// denoise.hip -- an edge-avoiding a-trous filter guided by first-hit buffers (gfx950): cgpt_read_guides, cgpt_denoise.
+// denoise.hip -- an edge-avoiding a-trous filter guided by first-hit buffers (gfx950): cgpt_read_guides, cgpt_denoise,
+// and the temporal reprojection in front of it: cgpt_denoise_temporal, cgpt_temporal_reset, cgpt_read_temporal_history.
 //
 // Guides: the reference does not jitter primary rays (SURVEY A-14), so every sample of a pixel has the same first hit, and one primary
 // trace per camera gives each pixel's position, normal and albedo.  guides_kernel computes that hit with the render paths' own device
@@ -11,6 +12,11 @@
 // exp(-|n(q) - n(p)|^2 / sigma_n^2) exp(-(n(p).(x(q) - x(p)))^2 / sigma_x^2); a hit and a miss never mix.  denoise_prepare divides the
 // accumulator by num_accumulated (data.pixels' division) and by the albedo (demodulation); the last pass multiplies the albedo back and
 // packs the pixels as data.pixels are packed.  One launch per pass, 16x16-pixel blocks, ping-pong float4 buffers of the context.
+//
+// Temporal stage (cgpt_denoise_temporal; tests/temporal_ref.py states it in numpy): between denoise_prepare and the
+// passes, temporal_merge reprojects the history of the earlier frames -- merged colour and history length H per pixel, with that frame's
+// guides and camera -- onto the current camera through the current first hits, validates the four bilinear taps against the current hit
+// (same object, normal, tangent plane) and merges c = (He c_h + N c_0) / (He + N).  The passes then run on c.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -186,6 +192,116 @@ __global__ void __launch_bounds__(256) denoise_identity(const float4* __restrict
     pixels[i] = vec4_to_uint(r, g, b);
 }
 
+// ---- the temporal stage --------------------------------------------------------------------------------------------------------
+constexpr cgpt_temporal_params kTemporalDefaults = { 64.0f, 0.9f, 0.01f, 0u };
+enum TemporalMode : uint32_t { kNoHistory = 0, kSameCamera = 1, kReproject = 2 };   // of a whole call: wave-uniform in the kernel
+
+struct TemporalArgs {
+    const float4* guides;          // this frame's, 3 float4 per pixel
+    const float4* demod;
+    const float4* materials;       // DevScene::materials, 4 float4 per material: the view-dependent rule reads specular and refractivity
+    const float4* hist;            // the history {c, H} and its guides (2 float4 per pixel); read only when mode != kNoHistory
+    const float4* hist_guides;
+    float4* hist_out;              // the new history
+    float4* hist_guides_out;
+    float4* color;                 // in: c_0 (denoise_prepare's output); out: the merged c (FINAL: c m, w = 1)
+    uint32_t* pixels;              // FINAL
+    uint32_t width, n_rows, mode, drop_view_dependent, demodulate;
+    float n_samples, max_history, normal_cos_min, plane_tolerance;
+    float minv[9];                 // rows of the inverse of [top_left - pos | top_right - top_left | bottom_left - top_left] of the history's camera
+    float pos_prev[3];
+    float height, first_row;       // fy = (c / a) height - first_row
+};
+
+// One thread per pixel.  The geometry of the reprojection -- (a, b, c) = Minv (x - pos_prev), fx, fy, the bilinear weights and the two
+// validity tests -- is double arithmetic on the float guides: in float the sample position moved by up to 1e-4 pixel, which times the
+// difference between neighbouring history pixels at 1 spp is more than the 1e-4 the output is held to, and the accept / reject decisions
+// near a threshold differed from the float64 statement's on more pixels.  It is some 150 instructions next to 15 loads of 16 bytes.
+// All four taps' loads (colour and two guide float4s each, from positions clamped into the band) and the material's come before any
+// validity arithmetic, which masks with selects (the lesson of atrous_pass).
+// FINAL (iterations = 0): the output is c m packed as data.pixels is, with w = 1.
+template <bool FINAL>
+__global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
+{
+    uint32_t px, row;
+    tile_pixel(a.width, px, row);
+    if (px >= a.width || row >= a.n_rows) return;
+    const size_t i = (size_t)row * a.width + px;
+    const float4 g0 = a.guides[3 * i], g1 = a.guides[3 * i + 1], g2 = a.guides[3 * i + 2];
+    const float4 c0 = a.color[i];
+    float hr = 0.0f, hg = 0.0f, hb = 0.0f, H = 0.0f;                            // c_h and H; H = 0: no history
+    if (a.mode == kSameCamera) {                                               // same scene and camera: the same hit, no validation
+        const float4 h = a.hist[i];
+        hr = h.x; hg = h.y; hb = h.z; H = h.w;
+    } else if (a.mode == kReproject) {
+        const uint32_t obj = __float_as_uint(g1.w), mat = __float_as_uint(g2.w);
+        const bool hit = obj != kNoHit;
+        const double dx = (double)g0.x - (double)a.pos_prev[0], dy = (double)g0.y - (double)a.pos_prev[1], dz = (double)g0.z - (double)a.pos_prev[2];
+        const double pa = ((double)a.minv[0] * dx + (double)a.minv[1] * dy) + (double)a.minv[2] * dz;
+        const double pb = ((double)a.minv[3] * dx + (double)a.minv[4] * dy) + (double)a.minv[5] * dz;
+        const double pc = ((double)a.minv[6] * dx + (double)a.minv[7] * dy) + (double)a.minv[8] * dz;
+        const bool in_front = hit && pa > 0.0;                                 // a <= 0: behind the history's camera
+        const double pa_s = in_front ? pa : 1.0;
+        double fx = (pb / pa_s) * (double)a.width, fy = (pc / pa_s) * (double)a.height - (double)a.first_row;
+        // two pixels outside the band every tap is outside it: clamp there, so that the integer conversion is defined (a NaN goes to a bound)
+        fx = fmin(fmax(fx, -2.0), (double)a.width + 1.0);
+        fy = fmin(fmax(fy, -2.0), (double)a.n_rows + 1.0);
+        const double flx = floor(fx), fly = floor(fy);
+        const long long x0 = (long long)flx, y0 = (long long)fly;
+        const double wx = fx - flx, wy = fy - fly;
+        float4 hc[4], hx[4], hn[4];
+        bool in[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long long qx = x0 + (k & 1), qy = y0 + (k >> 1);
+            in[k] = qx >= 0 && qx < (long long)a.width && qy >= 0 && qy < (long long)a.n_rows;
+            const size_t qx_c = (size_t)(qx < 0 ? 0 : (qx < (long long)a.width ? qx : (long long)a.width - 1));
+            const size_t qy_c = (size_t)(qy < 0 ? 0 : (qy < (long long)a.n_rows ? qy : (long long)a.n_rows - 1));
+            const size_t j = qy_c * a.width + qx_c;
+            hc[k] = a.hist[j]; hx[k] = a.hist_guides[2 * j]; hn[k] = a.hist_guides[2 * j + 1];
+        }
+        const size_t m_c = hit ? (size_t)mat : 0u;                             // a miss reads material 0 and is masked below
+        const float specular = a.materials[4 * m_c].w, refractivity = a.materials[4 * m_c + 1].x;
+        const bool view_dependent = a.drop_view_dependent != 0u && (specular > 0.0f || refractivity > 0.0f);
+        const double tol = (double)a.plane_tolerance * (double)g0.w;
+        double wsum = 0.0;
+        float sr = 0.0f, sg = 0.0f, sb = 0.0f, sh = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double ndot = ((double)hn[k].x * (double)g1.x + (double)hn[k].y * (double)g1.y) + (double)hn[k].z * (double)g1.z;
+            const double dplane = ((double)g1.x * ((double)hx[k].x - (double)g0.x) + (double)g1.y * ((double)hx[k].y - (double)g0.y)) +
+                                  (double)g1.z * ((double)hx[k].z - (double)g0.z);
+            const bool valid = in[k] && __float_as_uint(hn[k].w) == obj && ndot >= (double)a.normal_cos_min && fabs(dplane) <= tol;
+            const double w = valid ? ((k & 1) ? wx : 1.0 - wx) * ((k >> 1) ? wy : 1.0 - wy) : 0.0;
+            const float wf = (float)w;
+            wsum += w;
+            sr += wf * hc[k].x; sg += wf * hc[k].y; sb += wf * hc[k].z; sh += wf * hc[k].w;
+        }
+        const bool use = in_front && !view_dependent && wsum > 0.01;         // in_front: a hit, so an equal object index is a hit's
+        const float inv = 1.0f / (use ? (float)wsum : 1.0f);
+        hr = sr * inv; hg = sg * inv; hb = sb * inv;
+        H = use ? sh * inv : 0.0f;
+    }
+    const float He = fminf(H, a.max_history), N = a.n_samples;
+    const float inv = 1.0f / (He + N);
+    float r = c0.x, g = c0.y, b = c0.z;
+    if (He > 0.0f) {                                                           // no history: c = c_0 bit for bit
+        r = (He * hr + N * c0.x) * inv; g = (He * hg + N * c0.y) * inv; b = (He * hb + N * c0.z) * inv;
+    }
+    a.hist_out[i] = make_float4(r, g, b, fminf(He + N, a.max_history));
+    a.hist_guides_out[2 * i] = g0; a.hist_guides_out[2 * i + 1] = g1;
+    if (FINAL) {
+        if (a.demodulate) {
+            const float4 m = a.demod[i];
+            r *= m.x; g *= m.y; b *= m.z;
+        }
+        a.color[i] = make_float4(r, g, b, 1.0f);
+        a.pixels[i] = vec4_to_uint(r, g, b);
+    } else {
+        a.color[i] = make_float4(r, g, b, 0.0f);
+    }
+}
+
 // what a call works on: a one-device context's contiguous band, or a multi-device context's full frame on its first member
 struct Frame {
     cgpt_ctx* dev;            // the one-device context whose device, stream, scene and buffers do the work
@@ -260,6 +376,38 @@ int EnsureFilterBuffers(cgpt_ctx* ctx, cgpt_ctx* d, size_t n)
     return CGPT_OK;
 }
 
+// the a-trous passes on filter[0] (iterations >= 1); `out` is the last pass's output
+int FilterPasses(cgpt_ctx* ctx, const Frame& f, const cgpt_denoise_params& p, float4*& out)
+{
+    cgpt_ctx* d = f.dev;
+    const uint32_t demodulate = (p.flags & CGPT_DENOISE_DEMODULATE_ALBEDO) ? 1u : 0u;
+    const uint32_t tiles = ((f.width + kTile - 1u) / kTile) * ((f.n_rows + kTile - 1u) / kTile);
+    for (uint32_t it = 0; it < p.iterations; ++it) {
+        PassArgs a;
+        a.src = d->dn.filter[it & 1u].p;
+        a.dst = out = d->dn.filter[(it + 1u) & 1u].p;
+        a.pixels = d->dn.filter_pixels.p;
+        a.guides = d->dn.guides.p; a.demod = d->dn.guide_demod.p;
+        a.width = f.width; a.n_rows = f.n_rows; a.step = 1u << it; a.demodulate = demodulate;
+        const double sc = (double)p.sigma_color / (double)(1u << it);       // sigma_c 2^-i
+        a.inv_color = (float)(1.0 / (sc * sc));
+        a.inv_normal = (float)(1.0 / ((double)p.sigma_normal * p.sigma_normal));
+        a.inv_position = (float)(1.0 / ((double)p.sigma_position * p.sigma_position));
+        if (it + 1u == p.iterations) hipLaunchKernelGGL(atrous_pass<true>, dim3(tiles), dim3(256), 0, d->stream, a);
+        else hipLaunchKernelGGL(atrous_pass<false>, dim3(tiles), dim3(256), 0, d->stream, a);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return CGPT_OK;
+}
+
+int ReadBack(cgpt_ctx* ctx, cgpt_ctx* d, size_t n, const float4* out, float* dst_rgba, uint32_t* dst_pixels)
+{
+    if (dst_rgba) HIP_TRY(ctx, hipMemcpyAsync(dst_rgba, out, n * sizeof(float4), hipMemcpyDeviceToHost, d->stream));
+    if (dst_pixels) HIP_TRY(ctx, hipMemcpyAsync(dst_pixels, d->dn.filter_pixels.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(d->stream));
+    return CGPT_OK;
+}
+
 int Denoise(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, const cgpt_denoise_params& p, const float4* acc, float* dst_rgba,
             uint32_t* dst_pixels)
 {
@@ -279,27 +427,9 @@ int Denoise(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, const cgpt
         hipLaunchKernelGGL(denoise_prepare, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, d->stream, acc, d->dn.guide_demod.p, d->dn.filter[0].p, n,
                            (float)f.num_accumulated, demodulate);
         HIP_TRY(ctx, hipGetLastError());
-        const uint32_t tiles = ((f.width + kTile - 1u) / kTile) * ((f.n_rows + kTile - 1u) / kTile);
-        for (uint32_t it = 0; it < p.iterations; ++it) {
-            PassArgs a;
-            a.src = d->dn.filter[it & 1u].p;
-            a.dst = out = d->dn.filter[(it + 1u) & 1u].p;
-            a.pixels = d->dn.filter_pixels.p;
-            a.guides = d->dn.guides.p; a.demod = d->dn.guide_demod.p;
-            a.width = f.width; a.n_rows = f.n_rows; a.step = 1u << it; a.demodulate = demodulate;
-            const double sc = (double)p.sigma_color / (double)(1u << it);       // sigma_c 2^-i
-            a.inv_color = (float)(1.0 / (sc * sc));
-            a.inv_normal = (float)(1.0 / ((double)p.sigma_normal * p.sigma_normal));
-            a.inv_position = (float)(1.0 / ((double)p.sigma_position * p.sigma_position));
-            if (it + 1u == p.iterations) hipLaunchKernelGGL(atrous_pass<true>, dim3(tiles), dim3(256), 0, d->stream, a);
-            else hipLaunchKernelGGL(atrous_pass<false>, dim3(tiles), dim3(256), 0, d->stream, a);
-            HIP_TRY(ctx, hipGetLastError());
-        }
+        if ((rc = FilterPasses(ctx, f, p, out)) != CGPT_OK) return rc;
     }
-    if (dst_rgba) HIP_TRY(ctx, hipMemcpyAsync(dst_rgba, out, n * sizeof(float4), hipMemcpyDeviceToHost, d->stream));
-    if (dst_pixels) HIP_TRY(ctx, hipMemcpyAsync(dst_pixels, d->dn.filter_pixels.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(d->stream));
-    return CGPT_OK;
+    return ReadBack(ctx, d, n, out, dst_rgba, dst_pixels);
 }
 
 int CheckParams(cgpt_ctx* ctx, const cgpt_denoise_params& p)
@@ -312,12 +442,118 @@ int CheckParams(cgpt_ctx* ctx, const cgpt_denoise_params& p)
     return CGPT_OK;
 }
 
+
+int CheckTemporalParams(cgpt_ctx* ctx, const cgpt_temporal_params& t)
+{
+    if (!std::isfinite(t.max_history) || !(t.max_history >= 1.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "max_history must be finite and >= 1, got %g", t.max_history);
+    if (!(t.normal_cos_min >= -1.0f && t.normal_cos_min <= 1.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "normal_cos_min %g outside [-1, 1]", t.normal_cos_min);
+    if (!std::isfinite(t.plane_tolerance) || !(t.plane_tolerance > 0.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "plane_tolerance must be finite and > 0, got %g", t.plane_tolerance);
+    if (t.flags & ~(uint32_t)CGPT_TEMPORAL_KEEP_VIEW_DEPENDENT) return CtxFail(ctx, CGPT_ERR_INVALID, "unknown temporal flags 0x%x", t.flags);
+    return CGPT_OK;
+}
+
+// Minv of a camera: the inverse (adjugate / determinant) of the matrix with the columns top_left - pos, top_right - top_left,
+// bottom_left - top_left, in double from the float entries, each entry rounded to float once (as InvertTransform, transform_math.h).
+// False for a singular camera or a result that is not finite.
+bool InvertCamera(const cgpt_camera& c, float out[9])
+{
+    double m[3][3];
+    for (int r = 0; r < 3; ++r) {
+        m[r][0] = (double)c.top_left[r] - (double)c.pos[r];
+        m[r][1] = (double)c.top_right[r] - (double)c.top_left[r];
+        m[r][2] = (double)c.bottom_left[r] - (double)c.top_left[r];
+    }
+    const double c00 = m[1][1] * m[2][2] - m[1][2] * m[2][1], c01 = m[1][2] * m[2][0] - m[1][0] * m[2][2], c02 = m[1][0] * m[2][1] - m[1][1] * m[2][0];
+    const double det = (m[0][0] * c00 + m[0][1] * c01) + m[0][2] * c02;
+    if (det == 0.0 || !std::isfinite(det)) return false;
+    const double inv[9] = {
+        c00 / det, (m[0][2] * m[2][1] - m[0][1] * m[2][2]) / det, (m[0][1] * m[1][2] - m[0][2] * m[1][1]) / det,
+        c01 / det, (m[0][0] * m[2][2] - m[0][2] * m[2][0]) / det, (m[0][2] * m[1][0] - m[0][0] * m[1][2]) / det,
+        c02 / det, (m[0][1] * m[2][0] - m[0][0] * m[2][1]) / det, (m[0][0] * m[1][1] - m[0][1] * m[1][0]) / det,
+    };
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite((float)inv[i])) return false;
+    for (int i = 0; i < 9; ++i) out[i] = (float)inv[i];
+    return true;
+}
+
+int EnsureHistoryBuffers(cgpt_ctx* ctx, cgpt_ctx* d, size_t n)
+{
+    if (d->dn.history_guides[1].n == 2 * n) return CGPT_OK;                    // any other size: all four anew (the last one's count is the key)
+    d->temporal_valid = false;
+    ResetAll(d->dn.history[0], d->dn.history[1], d->dn.history_guides[0], d->dn.history_guides[1]);
+    HIP_TRY(ctx, d->dn.history[0].Alloc(n));
+    HIP_TRY(ctx, d->dn.history[1].Alloc(n));
+    HIP_TRY(ctx, d->dn.history_guides[0].Alloc(2 * n));
+    HIP_TRY(ctx, d->dn.history_guides[1].Alloc(2 * n));
+    return CGPT_OK;
+}
+
+// the history a call may use: stored by a call that succeeded, for this band, scene and demodulation
+bool HistoryMatches(const cgpt_ctx* d, const uint32_t key[4], uint32_t demodulate)
+{
+    return d->temporal_valid && d->temporal_generation == d->scene_generation && d->temporal_demodulate == demodulate &&
+           memcmp(d->temporal_frame, key, sizeof(d->temporal_frame)) == 0;
+}
+
+int DenoiseTemporal(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, const cgpt_denoise_params& p, const cgpt_temporal_params& t,
+                    const float4* acc, float* dst_rgba, uint32_t* dst_pixels)
+{
+    cgpt_ctx* d = f.dev;
+    const size_t n = (size_t)f.width * f.n_rows;
+    const uint32_t key[4] = { f.width, f.height, f.first_row, f.n_rows };
+    const uint32_t demodulate = (p.flags & CGPT_DENOISE_DEMODULATE_ALBEDO) ? 1u : 0u;
+    const bool have = HistoryMatches(d, key, demodulate);
+    d->temporal_valid = false;                                                 // a call that fails from here on leaves no history
+    int rc;
+    HIP_TRY(ctx, hipSetDevice(d->device));
+    if ((rc = EnsureFilterBuffers(ctx, d, n)) != CGPT_OK) return rc;
+    if ((rc = EnsureHistoryBuffers(ctx, d, n)) != CGPT_OK) return rc;
+    if ((rc = EnsureGuides(ctx, f, camera)) != CGPT_OK) return rc;
+    hipLaunchKernelGGL(denoise_prepare, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, d->stream, acc, d->dn.guide_demod.p, d->dn.filter[0].p, n,
+                       (float)f.num_accumulated, demodulate);
+    HIP_TRY(ctx, hipGetLastError());
+    TemporalArgs a{};
+    const uint32_t src = d->temporal_slot, dst = src ^ 1u;
+    a.guides = d->dn.guides.p; a.demod = d->dn.guide_demod.p; a.materials = d->scene.materials;
+    a.hist = d->dn.history[src].p; a.hist_guides = d->dn.history_guides[src].p;
+    a.hist_out = d->dn.history[dst].p; a.hist_guides_out = d->dn.history_guides[dst].p;
+    a.color = d->dn.filter[0].p; a.pixels = d->dn.filter_pixels.p;
+    a.width = f.width; a.n_rows = f.n_rows; a.demodulate = demodulate;
+    a.drop_view_dependent = (t.flags & CGPT_TEMPORAL_KEEP_VIEW_DEPENDENT) ? 0u : 1u;
+    a.n_samples = (float)f.num_accumulated; a.max_history = t.max_history; a.normal_cos_min = t.normal_cos_min; a.plane_tolerance = t.plane_tolerance;
+    a.height = (float)f.height; a.first_row = (float)f.first_row;
+    a.mode = kNoHistory;
+    if (have) {
+        if (memcmp(&d->temporal_camera, camera, sizeof(cgpt_camera)) == 0) a.mode = kSameCamera;
+        else if (InvertCamera(d->temporal_camera, a.minv)) {                   // a singular camera: no history
+            memcpy(a.pos_prev, d->temporal_camera.pos, sizeof(a.pos_prev));
+            a.mode = kReproject;
+        }
+    }
+    const uint32_t tiles = ((f.width + kTile - 1u) / kTile) * ((f.n_rows + kTile - 1u) / kTile);
+    if (p.iterations == 0) hipLaunchKernelGGL(temporal_merge<true>, dim3(tiles), dim3(256), 0, d->stream, a);
+    else hipLaunchKernelGGL(temporal_merge<false>, dim3(tiles), dim3(256), 0, d->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    float4* out = d->dn.filter[0].p;
+    if ((rc = FilterPasses(ctx, f, p, out)) != CGPT_OK) return rc;
+    if ((rc = ReadBack(ctx, d, n, out, dst_rgba, dst_pixels)) != CGPT_OK) return rc;
+    d->temporal_slot = dst;
+    d->temporal_demodulate = demodulate;
+    d->temporal_generation = d->scene_generation;
+    memcpy(&d->temporal_camera, camera, sizeof(cgpt_camera));
+    memcpy(d->temporal_frame, key, sizeof(key));
+    d->temporal_valid = true;
+    return CGPT_OK;
+}
+
 }  // namespace
 
 void DenoiseFree(cgpt_ctx* ctx)
 {
     ctx->dn = DenoiseBuffers{};
     ctx->guides_valid = false;
+    ctx->temporal_valid = false;
 }
 
 }  // namespace cgpt
@@ -363,6 +599,50 @@ int cgpt_denoise(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_pa
     rc = Denoise(ctx, f, camera, p, acc, dst_rgba, dst_pixels);
     if (rc != CGPT_OK) f.dev->guides_valid = false;
     return rc;
+}
+
+int cgpt_denoise_temporal(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_params* params, const cgpt_temporal_params* temporal,
+                          float* dst_rgba, size_t n_floats, uint32_t* dst_pixels, size_t n_pixels)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    Frame f;
+    int rc = ResolveFrame(ctx, true, camera, f);
+    if (rc != CGPT_OK) return rc;
+    const cgpt_denoise_params p = params ? *params : kDefaults;
+    if ((rc = CheckParams(ctx, p)) != CGPT_OK) return rc;
+    const cgpt_temporal_params t = temporal ? *temporal : kTemporalDefaults;
+    if ((rc = CheckTemporalParams(ctx, t)) != CGPT_OK) return rc;
+    const size_t n = (size_t)f.width * f.n_rows;
+    if (!dst_rgba && !dst_pixels) return CtxFail(ctx, CGPT_ERR_INVALID, "both outputs are null");
+    if (dst_rgba && n_floats != 4 * n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats (4 per pixel)", 4 * n);
+    if (dst_pixels && n_pixels != n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu pixels", n);
+    const float4* acc = ctx->fb.accumulator.p;
+    if (ctx->group && (rc = GroupGatherUncounted(ctx, &acc)) != CGPT_OK) { f.dev->temporal_valid = false; return rc; }
+    rc = DenoiseTemporal(ctx, f, camera, p, t, acc, dst_rgba, dst_pixels);
+    if (rc != CGPT_OK) f.dev->guides_valid = false;
+    return rc;
+}
+
+int cgpt_temporal_reset(cgpt_ctx* ctx)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    cgpt_ctx* const first = GroupFirstMemberOrNull(ctx);
+    (first ? first : ctx)->temporal_valid = false;
+    return CGPT_OK;
+}
+
+int cgpt_read_temporal_history(cgpt_ctx* ctx, float* dst, size_t n_floats)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    cgpt_ctx* const first = GroupFirstMemberOrNull(ctx);
+    cgpt_ctx* const d = first ? first : ctx;
+    if (!d->temporal_valid || d->temporal_generation != d->scene_generation) return CtxFail(ctx, CGPT_ERR_INVALID, "no temporal history");
+    const size_t n = (size_t)d->temporal_frame[0] * d->temporal_frame[3];
+    if (!dst || n_floats != 4 * n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats (4 per pixel)", 4 * n);
+    HIP_TRY(ctx, hipSetDevice(d->device));
+    HIP_TRY(ctx, hipMemcpyAsync(dst, d->dn.history[d->temporal_slot].p, n * sizeof(float4), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(d->stream));
+    return CGPT_OK;
 }
 
 }  // extern "C"

@@ -273,6 +273,33 @@ class Renderer:
                                         px.ctypes.data_as(C.POINTER(C.c_uint32)), px.size))
         return rgba, px
 
+    def denoise_temporal(self, iterations: int = 5, sigma_color: float = 4.0, sigma_normal: float = 0.2, sigma_position: float = 0.3,
+                         demodulate: bool = True, max_history: float = 64.0, normal_cos_min: float = 0.9, plane_tolerance: float = 0.01,
+                         keep_view_dependent: bool = False, camera: Optional[N.Camera] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """denoise() with the temporal stage in front (cgpt_denoise_temporal): the history of the earlier calls is reprojected onto
+        `camera` (the one of this frame's render; default: the uploaded scene's) and merged with the accumulated frame by sample counts
+        before the filter runs.  Per frame: reset_accumulator(), render(), denoise_temporal(); each call consumes the accumulated
+        samples once.  Camera motion only: every scene edit drops the history."""
+        cam = camera if camera is not None else self.scene.camera()
+        p = N.DenoiseParams(iterations, N.DENOISE_DEMODULATE_ALBEDO if demodulate else 0, sigma_color, sigma_normal, sigma_position)
+        t = N.TemporalParams(max_history, normal_cos_min, plane_tolerance, N.TEMPORAL_KEEP_VIEW_DEPENDENT if keep_view_dependent else 0)
+        rgba = np.empty((self.n_rows, self.width, 4), np.float32)
+        px = np.empty((self.n_rows, self.width), np.uint32)
+        self._check(self.L.cgpt_denoise_temporal(self._ctx, C.byref(cam), C.byref(p), C.byref(t), rgba.ctypes.data_as(C.POINTER(C.c_float)),
+                                                 rgba.size, px.ctypes.data_as(C.POINTER(C.c_uint32)), px.size))
+        return rgba, px
+
+    def temporal_reset(self):
+        """Drops the temporal history (cgpt_temporal_reset)."""
+        self._check(self.L.cgpt_temporal_reset(self._ctx))
+
+    def temporal_history(self) -> np.ndarray:
+        """The history the last denoise_temporal() stored (cgpt_read_temporal_history): (rows, width, 4) float32 {merged colour in the
+        filter's input domain, history length in samples}."""
+        out = np.empty((self.n_rows, self.width, 4), np.float32)
+        self._check(self.L.cgpt_read_temporal_history(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
     def accumulator_device_ptr(self) -> Tuple[int, int]:
         ptr = C.c_void_p(); nbytes = C.c_size_t()
         self._check(self.L.cgpt_accumulator_device_ptr(self._ctx, C.byref(ptr), C.byref(nbytes)))

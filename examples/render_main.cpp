@@ -4,7 +4,7 @@
 //
 //   g++ -std=c++17 -Iinclude -Icpugpupathtracing_amd/csrc/host examples/render_main.cpp
 //       -Lcpugpupathtracing_amd/lib -lcpugpupt -Wl,-rpath,$PWD/cpugpupathtracing_amd/lib -o render_main   (one command line)
-//   ./render_main [--gpus N [--collective]] [--denoise] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--smooth] [--mesh-transform m00 .. m23] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
+//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--smooth] [--mesh-transform m00 .. m23] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
 // --gpus N: ONE context over the first N GPUs of the node (cgpt_ctx_create with n_devices = N): every frame is spread over them in
 // interleaved row bands and the read-back gathers the float4 bands with one RCCL exchange over xGMI; the loop below does not
 // change.  --collective: take that code path with N = 1 too (what a one-GPU box can test).
@@ -12,6 +12,10 @@
 // presenting data.pixels after every Render() (ref: Main.cpp:935-936, Source/DX12.cpp:277-322).
 // --denoise: also write the image through cgpt_denoise (default parameters) next to each preview (preview_NNNN_denoised.ppm) and at the
 // end (render_denoised.ppm) -- what a viewer with a "Denoise" toggle presents; the accumulator and the raw dumps are not affected.
+// --temporal: a moving camera instead of the accumulating loop -- 8 frames of an orbit around the scene (2 degrees a frame), each `spp` samples
+// from a reset accumulator, as a viewer renders while the camera moves; every frame is written raw (temporal_NN_raw.ppm), through
+// cgpt_denoise (temporal_NN_denoised.ppm) and through cgpt_denoise_temporal, which reprojects the frames before it (temporal_NN_temporal.ppm;
+// DESIGN.md 5.19).  Takes [width height spp] only.
 // --ground-roughness R: a glossy ground -- its material (1) gets specular 0.5 and roughness R in [0, 1] (cgpt_scene_update_roughness after
 // the upload; 0 keeps the mirror half of the lobe perfect).
 // --glass-roughness R: a frosted mesh -- its material (3, the glass) gets the transmission roughness R in [0, 1]
@@ -29,6 +33,7 @@
 // camera is translated by (right, up, forward) as the A/D, Space/Shift, W/S keys would, the view changes, and the accumulator
 // is reset (ref: ResetAccumulator, Main.cpp:238-243) before the remaining samples are rendered from the new position.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -50,13 +55,14 @@ using namespace cgpt;
 
 int main(int argc, char** argv)
 {
-    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false;
+    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false;
     bool has_transform = false; float mesh_transform[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
     MeshBVH::BuildOption bvh_option = MeshBVH::BuildOption_SAHSplitIntervals;
     while (argc > 1 && std::string(argv[1]).rfind("--", 0) == 0) {
         if (std::string(argv[1]) == "--gpus" && argc > 2) { n_gpus = atoi(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--collective") { ctx_flags |= CGPT_CTX_FORCE_COLLECTIVE; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--denoise") { denoise = true; argv += 1; argc -= 1; }
+        else if (std::string(argv[1]) == "--temporal") { temporal = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--smooth") { smooth = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--mesh-transform" && argc > 13) {
             for (int k = 0; k < 12; ++k) mesh_transform[k] = (float)atof(argv[2 + k]);
@@ -120,6 +126,29 @@ int main(int argc, char** argv)
     }
 
     const cgpt_settings settings = scene.AbiSettings();
+    if (temporal) {                                                      // the camera moves every frame: ResetAccumulator, Render, present
+        std::vector<uint32_t> px((size_t)W * H);
+        for (uint32_t frame = 0; frame < 8; ++frame) {
+            const float angle = 2.0f * (float)frame * 3.14159265f / 180.0f;
+            const float pos[3] = { 8.0f * std::sin(angle), 0.0f, 8.0f * std::cos(angle) }, dir[3] = { -std::sin(angle), 0.0f, -std::cos(angle) };   // towards the origin
+            cgpt_camera cam;
+            CHECK(cgpt_camera_from_view(pos, dir, 60.0f, (float)W / (float)H, &cam));
+            CHECK(cgpt_reset_accumulator(ctx));
+            cgpt_render_params p{};
+            p.width = W; p.height = H; p.row_begin = 0; p.row_end = H;
+            p.first_sample = 0; p.n_samples = spp; p.seed = 0x12345678u + frame; p.kernel = CGPT_KERNEL_AUTO;
+            CHECK(cgpt_render(ctx, &cam, &settings, &p));
+            char name[64]; std::string err;
+            CHECK(cgpt_read_pixels(ctx, px.data(), px.size()));
+            snprintf(name, sizeof(name), "temporal_%02u_raw.ppm", frame); WritePPM(name, px.data(), W, H, err);
+            CHECK(cgpt_denoise(ctx, &cam, nullptr, nullptr, 0, px.data(), px.size()));
+            snprintf(name, sizeof(name), "temporal_%02u_denoised.ppm", frame); WritePPM(name, px.data(), W, H, err);
+            CHECK(cgpt_denoise_temporal(ctx, &cam, nullptr, nullptr, nullptr, 0, px.data(), px.size()));   // once per rendered frame
+            snprintf(name, sizeof(name), "temporal_%02u_temporal.ppm", frame); WritePPM(name, px.data(), W, H, err);
+        }
+        cgpt_ctx_destroy(ctx);
+        return 0;
+    }
     uint32_t num_accumulated = 0;                                        // data.num_accumulated
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<uint32_t> pixels((size_t)W * H), denoised(denoise ? (size_t)W * H : 0);

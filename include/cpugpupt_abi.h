@@ -33,7 +33,8 @@ extern "C" {
                                  only (cgpt_set_nee_candidates); smooth shading added one new symbol only
                                  (cgpt_scene_update_smooth_normals); per-object transforms added one new symbol only
                                  (cgpt_scene_update_transforms); the top-level tree added one new symbol only
-                                 (cgpt_set_top_level) */
+                                 (cgpt_set_top_level); temporal reprojection added new symbols (cgpt_denoise_temporal,
+                                 cgpt_temporal_reset, cgpt_read_temporal_history) and a new struct (cgpt_temporal_params) only */
 
 enum cgpt_status {
     CGPT_OK = 0,
@@ -413,6 +414,45 @@ int cgpt_read_guides(cgpt_ctx* ctx, const cgpt_camera* camera, float* dst, size_
  * either output may be NULL, not both */
 int cgpt_denoise(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_params* params, float* dst_rgba, size_t n_floats,
                  uint32_t* dst_pixels, size_t n_pixels);
+
+/* ---- temporal reprojection for a moving camera (the temporal stage of SVGF, Schied et al. 2017) ----
+ * cgpt_denoise_temporal is cgpt_denoise with a temporal stage in front of the passes: the history of the earlier calls -- a merged
+ * colour and a history length H (in samples) per pixel, with the guides and the camera of the frame it was stored for -- is reprojected
+ * onto `camera` through the current first hits, validated, and merged with the current frame weighted by sample counts,
+ *   c = (He c_h + N c_0) / (He + N),  He = min(H, max_history),  H' = min(He + N, max_history),  N = num_accumulated,
+ * where c_0 is the accumulator / N (divided by the albedo with CGPT_DENOISE_DEMODULATE_ALBEDO).  The passes then filter c;
+ * iterations = 0 returns c (times the albedo) packed as data.pixels is.  (c, H') becomes the new history.
+ * Intended use per frame: cgpt_reset_accumulator, cgpt_render(n samples), cgpt_denoise_temporal(the camera of that render).  Each
+ * call consumes the accumulator's N samples once: a second call without a new render counts the same samples twice.
+ * Reprojection: a hit at x maps to (a, b, c) = Minv (x - pos_prev), Minv the inverse of [top_left - pos | top_right - top_left |
+ * bottom_left - top_left] of the history's camera; a <= 0 (behind it) or a singular camera: no history; the history is sampled
+ * bilinearly at (b / a width, c / a height - first_row); a tap counts when it lies in the band, hit the same object,
+ * n_prev . n >= normal_cos_min and |n . (x_prev - x)| <= plane_tolerance t; valid weights summing to <= 0.01: no history.  A camera
+ * whose bytes equal the history's maps every pixel to itself without validation.  A first hit on a material with specular > 0 or
+ * refractivity > 0 shows a reflection or refraction that does not move with the surface: after a camera change it takes no history
+ * unless CGPT_TEMPORAL_KEEP_VIEW_DEPENDENT is set.  A pixel without history: c = c_0, H' = min(N, max_history).
+ * The history is absent after cgpt_ctx_create, cgpt_temporal_reset and a call that failed, and when the band (width, height, rows), the
+ * scene (every upload and in-place edit that recomputes the guides) or the demodulate flag differ from the call's.
+ * Limits: camera motion only (moving objects are not reprojected: an edit drops the history); first-hit reprojection only (what is seen
+ * in a mirror or through glass is not followed); a multi-device context keeps the history on device_ids[0].
+ * Like cgpt_denoise it leaves the accumulator, data.pixels, num_accumulated, cgpt_stats and the guides alone, and cgpt_denoise's output
+ * does not depend on temporal calls.  Refusals (before any device work; nothing changes, the history included): every refusal of
+ * cgpt_denoise; max_history not finite or < 1; normal_cos_min outside [-1, 1] or NaN; plane_tolerance not finite or <= 0; unknown
+ * flag bits; cgpt_read_temporal_history without a history or with a wrong size -- all CGPT_ERR_INVALID. */
+enum cgpt_temporal_flags { CGPT_TEMPORAL_KEEP_VIEW_DEPENDENT = 1u };
+typedef struct cgpt_temporal_params {
+    float    max_history;      /* cap on a pixel's history length, in samples; finite, >= 1 */
+    float    normal_cos_min;   /* a tap is valid only if n_prev . n_cur >= this; in [-1, 1] */
+    float    plane_tolerance;  /* ... and |n_cur . (x_prev - x_cur)| <= this * t_cur; finite, > 0 */
+    uint32_t flags;            /* cgpt_temporal_flags */
+} cgpt_temporal_params;        /* NULL = the defaults: 64, 0.9, 0.01, 0 */
+int cgpt_denoise_temporal(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_params* params, const cgpt_temporal_params* temporal,
+                          float* dst_rgba, size_t n_floats, uint32_t* dst_pixels, size_t n_pixels);
+/* drops the history; CGPT_OK when there is none */
+int cgpt_temporal_reset(cgpt_ctx* ctx);
+/* 4 floats per pixel of the band the history was stored for: the merged colour c (the filter's input domain: demodulated when the call
+ * was) and the history length H' */
+int cgpt_read_temporal_history(cgpt_ctx* ctx, float* dst, size_t n_floats);
 
 /* ---- tuning and measurement aids (no reference counterpart) ------------------------------------------------------- */
 /* Overrides one tuning knob of the wavefront pipeline for this context (the CGPT_WF_* environment variables set the same
