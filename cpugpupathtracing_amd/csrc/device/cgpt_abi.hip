@@ -20,8 +20,8 @@
 
 namespace cgpt {
 hipError_t LaunchMegakernel(const DevRenderArgs& args, ShadeVariant v, hipStream_t stream);                                  // path_kernels.hip
-hipError_t LaunchIntersectRays(const DevScene& sc, const float* origins, const float* dirs, const float* tmax, uint32_t n, float* out_t,
-                               uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, DevCounters* counters, bool xform, bool tree, hipStream_t stream);
+hipError_t LaunchIntersectRays(const struct ::cgpt_ctx* ctx, const float* origins, const float* dirs, const float* tmax, uint32_t n, float* out_t,
+                               uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth);
 int LaunchWavefront(struct ::cgpt_ctx* ctx, const DevRenderArgs& args, ShadeVariant v);                                     // wavefront_kernels.hip
 void WavefrontFree(void* state);
 void WavefrontCollectTiming(void* state, double* trace_ms, uint32_t* trace_launches, double* round0_ms, uint32_t* round0_launches);
@@ -74,8 +74,8 @@ void FreeScene(cgpt_ctx* ctx)
 {
     ctx->sb = SceneBuffers{};
     ctx->h_objects.clear(); ctx->refit_objects.clear(); ctx->record_perm.clear();
-    ctx->h_roughness.clear(); ctx->h_transmission_roughness.clear(); ctx->h_materials.clear(); ctx->lobe_level = 0;
-    ctx->any_smooth = false; ctx->any_xform = false; ctx->h_lights.clear();
+    ctx->h_roughness.clear(); ctx->h_transmission_roughness.clear(); ctx->h_materials.clear(); ctx->h_lights.clear();
+    ctx->features = SceneFeatures{};
     ctx->top_state = TopLevelState{};
     ctx->has_scene = false;
 }
@@ -119,15 +119,6 @@ int ResolveBand(cgpt_ctx* ctx, const cgpt_render_params& p, Band& b)
     return CGPT_OK;
 }
 
-// the GLOSSY instantiation the renders run (ctx_internal.h: lobe_level), from the two roughness arrays, the smooth flags and the transforms
-void UpdateLobeLevel(cgpt_ctx* ctx)
-{
-    bool specular = false, glass = false;
-    for (const float v : ctx->h_roughness) specular = specular || v > 0.0f;
-    for (const float v : ctx->h_transmission_roughness) glass = glass || v > 0.0f;
-    ctx->lobe_level = ctx->any_xform ? 4u : (ctx->any_smooth ? 3u : (glass ? 2u : (specular ? 1u : 0u)));
-}
-
 // cgpt_scene_update_roughness (transmission false: PackMaterial's alpha, materials[4i+3].z) and cgpt_scene_update_transmission_roughness
 // (true: alpha_t, .w) of a one-device context.  Everything is refused before the device write; the other lobe's values are kept.
 int UpdateRoughnessWord(cgpt_ctx* ctx, const float* roughness, uint32_t n_materials, bool transmission)
@@ -150,8 +141,8 @@ int UpdateRoughnessWord(cgpt_ctx* ctx, const float* roughness, uint32_t n_materi
         return CtxFail(ctx, CGPT_ERR_HIP, "hipMemcpy of the material records failed: %s (the device scene is dropped; upload it again)", hipGetErrorString(e));
     }
     ctx->h_materials.swap(mats);
+    (transmission ? ctx->features.rough_dielectric : ctx->features.rough_specular) = std::any_of(values.begin(), values.end(), [](float v) { return v > 0.0f; });
     (transmission ? ctx->h_transmission_roughness : ctx->h_roughness).swap(values);
-    UpdateLobeLevel(ctx);
     return CGPT_OK;
 }
 
@@ -179,8 +170,7 @@ int UpdateSmoothNormals(cgpt_ctx* ctx, const uint32_t* smooth, uint32_t n_object
         return CtxFail(ctx, CGPT_ERR_HIP, "hipMemcpy of the object records failed: %s (the device scene is dropped; upload it again)", hipGetErrorString(e));
     }
     ctx->h_objects.swap(objects);
-    ctx->any_smooth = any;
-    UpdateLobeLevel(ctx);
+    ctx->features.smooth_normals = any;
     return CGPT_OK;
 }
 
@@ -220,9 +210,8 @@ int UpdateTransforms(cgpt_ctx* ctx, const float* object_to_world, uint32_t n_obj
         ctx->has_scene = false;
         return CtxFail(ctx, CGPT_ERR_HIP, "hipMemcpy of the transform records failed: %s (the device scene is dropped; upload it again)", hipGetErrorString(e));
     }
-    ctx->any_xform = any;
+    ctx->features.transforms = any;
     ctx->top_state.xform.swap(top.xform);
-    UpdateLobeLevel(ctx);
     return CGPT_OK;
 }
 
@@ -442,8 +431,8 @@ int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout)
     if ((rc = UploadArray(ctx, ctx->sb.lights, layout.lights)) != CGPT_OK) return rc;
     if ((rc = UploadArray(ctx, ctx->sb.refit_levels, layout.refit_levels)) != CGPT_OK) return rc;
     ctx->h_objects = layout.objects; ctx->refit_objects = layout.refit_objects; ctx->record_perm = layout.record_perm;
-    ctx->h_roughness.assign(layout.n_materials, 0.0f); ctx->h_transmission_roughness.assign(layout.n_materials, 0.0f); ctx->h_materials = layout.materials; ctx->lobe_level = 0;
-    ctx->any_smooth = false; ctx->any_xform = false; ctx->h_lights = layout.lights;   // an upload resets every smooth-normal flag and transform (LayoutScene writes 0 and the identity)
+    ctx->h_roughness.assign(layout.n_materials, 0.0f); ctx->h_transmission_roughness.assign(layout.n_materials, 0.0f); ctx->h_materials = layout.materials;
+    ctx->h_lights = layout.lights;                                             // FreeScene cleared the features: an upload resets every roughness, smooth-normal flag and transform (LayoutScene writes 0 and the identity)
     ctx->top_state = layout.top_state;
     HIP_TRY(ctx, WriteTopLevel(ctx, ctx->h_objects, ctx->top_state));          // the mode is context state: an upload keeps it
 
@@ -456,15 +445,29 @@ int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout)
     return CGPT_OK;
 }
 
+int TranslateSettings(cgpt_ctx* ctx, const cgpt_settings& settings, DevSettings& st)
+{
+    if (settings.max_ray_depth < 0 || settings.max_ray_depth > 254)
+        return CtxFail(ctx, CGPT_ERR_INVALID, "max_ray_depth %d outside [0,254] (ray_depth is a uint8_t in the reference, Main.cpp:401)", settings.max_ray_depth);
+    if (settings.render_mode > CGPT_MODE_ADVANCED || settings.debug_render_mode > CGPT_DEBUG_BVH_DEPTH)
+        return CtxFail(ctx, CGPT_ERR_INVALID, "bad render_mode/debug_render_mode");
+    st.max_ray_depth = settings.max_ray_depth;
+    st.nee = settings.next_event_estimation_enabled;
+    st.cosine = settings.cosine_weighted_diffuse_reflection_enabled;
+    st.rr = settings.russian_roulette_enabled;
+    st.render_mode = settings.render_mode;
+    st.debug_mode = settings.debug_render_mode;
+    return CGPT_OK;
+}
+
 int RenderEnqueue(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p)
 {
     ctx->pending_kernel = 0;
     if (!camera || !settings || !p) return CtxFail(ctx, CGPT_ERR_INVALID, "null argument");
     if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "cgpt_render before cgpt_scene_upload");
-    if (settings->max_ray_depth < 0 || settings->max_ray_depth > 254)
-        return CtxFail(ctx, CGPT_ERR_INVALID, "max_ray_depth %d outside [0,254] (ray_depth is a uint8_t in the reference, Main.cpp:401)", settings->max_ray_depth);
-    if (settings->render_mode > CGPT_MODE_ADVANCED || settings->debug_render_mode > CGPT_DEBUG_BVH_DEPTH)
-        return CtxFail(ctx, CGPT_ERR_INVALID, "bad render_mode/debug_render_mode");
+    DevRenderArgs args{};
+    int rc = TranslateSettings(ctx, *settings, args.settings);
+    if (rc != CGPT_OK) return rc;
     if (settings->render_mode != CGPT_MODE_ADVANCED) {
         // TracePath (brute force) keeps its per-level operations in HBM in the persistent kernel (per lane) and in the wavefront
         // pipeline (per path), any depth; the megakernel keeps them in per-lane scratch of 32 levels
@@ -474,7 +477,7 @@ int RenderEnqueue(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings*
     if ((uint64_t)p->first_sample + p->n_samples > 0xFFFFFFFFull) return CtxFail(ctx, CGPT_ERR_INVALID, "sample index overflow");
 
     Band band;
-    int rc = ResolveBand(ctx, *p, band);
+    rc = ResolveBand(ctx, *p, band);
     if (rc != CGPT_OK) return rc;
     const uint32_t n_rows = band.n_rows, band_first = band.first, band_h = band.h, band_stride = band.stride;
 
@@ -483,26 +486,14 @@ int RenderEnqueue(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings*
     if (rc != CGPT_OK) return rc;
     if (p->n_samples == 0) return CGPT_OK;
 
-    DevRenderArgs args{};
     args.scene = ctx->scene;
     memcpy(&args.camera, camera, sizeof(DevCamera));
-    args.settings.max_ray_depth = settings->max_ray_depth;
-    args.settings.nee = settings->next_event_estimation_enabled;
-    args.settings.cosine = settings->cosine_weighted_diffuse_reflection_enabled;
-    args.settings.rr = settings->russian_roulette_enabled;
-    args.settings.render_mode = settings->render_mode;
-    args.settings.debug_mode = settings->debug_render_mode;
     args.width = p->width; args.height = p->height;
     args.n_rows = n_rows; args.band_first = band_first; args.band_h = band_h; args.band_stride = band_stride;
     args.first_sample = p->first_sample; args.n_samples = p->n_samples; args.seed = p->seed;
     args.accumulator = ctx->fb.accumulator.p; args.pixels = ctx->fb.pixels.p; args.counters = ctx->counters.p;
 
-    // the RIS instantiations run only where a candidate loop can: TracePath (BRUTE_FORCE) has no NEE, and NEE may be off
-    const bool ris = ctx->nee_candidates > 1u && args.settings.nee != 0u && settings->render_mode != CGPT_MODE_BRUTE_FORCE;
-    // The one place where DevSettings.nee is more than a flag: the RIS instantiations read M from it, every other reader tests it for zero
-    // (device_scene.h).  With one candidate the word is the caller's flag, untouched, as the parent passed it.
-    if (ris) args.settings.nee = ctx->nee_candidates;
-    const ShadeVariant variant = { (p->flags & CGPT_RENDER_COUNTERS) != 0, ctx->lobe_level, ris, ctx->top_level != 0u };
+    const ShadeVariant variant = ChooseVariant(ctx, args.settings, p->flags);
     // AUTO: all three kernels give bit-identical images, so the choice is speed alone.  MI355X, glass scene, ms per call
     // (profiles/r03/small_calls_table.txt; 16 samples and more: profiles/r02/frame_time_after.txt):
     //                 64x64  1 / 2 / 8 samples     960x540  1 / 2 / 8        1920x1080  1 / 2 / 4 / 8 / 16 / 32 / 64 / 128
@@ -746,7 +737,7 @@ int cgpt_intersect_rays(cgpt_ctx* ctx, const float* origins, const float* dirs, 
     HIP_TRY(ctx, hipMemcpyAsync(d_o.p, origins, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_d.p, dirs, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     if (tmax) HIP_TRY(ctx, hipMemcpyAsync(d_tm.p, tmax, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, LaunchIntersectRays(ctx->scene, d_o.p, d_d.p, d_tm.p, n, d_t.p, d_obj.p, d_tri.p, d_dep.p, ctx->counters.p, ctx->any_xform, ctx->top_level != 0u, ctx->stream));
+    HIP_TRY(ctx, LaunchIntersectRays(ctx, d_o.p, d_d.p, d_tm.p, n, d_t.p, d_obj.p, d_tri.p, d_dep.p));
     HIP_TRY(ctx, hipMemcpyAsync(out_t, d_t.p, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out_obj, d_obj.p, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out_tri, d_tri.p, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));

@@ -38,6 +38,9 @@ struct DenoiseBuffers {                           // denoise.hip; each group is 
     DevBuf<float4> history_guides[2];             // 2 float4 per pixel {x.xyz, t | n.xyz, bits(obj)} of the frame each history belongs to
 };
 template <class... B> void ResetAll(B&... b) { (b.Reset(), ...); }
+// What the uploaded scene has that a kernel variant must carry: a roughness > 0, a transmission roughness > 0, a smooth-normal flag (they live in
+// h_objects[i].smooth), a transform that is no identity (the flags live in obj_trace).  All false after an upload, each kept by the edit that owns it.
+struct SceneFeatures { bool rough_specular = false, rough_dielectric = false, smooth_normals = false, transforms = false; };
 }  // namespace cgpt
 
 struct cgpt_ctx {
@@ -53,21 +56,12 @@ struct cgpt_ctx {
     uint32_t n_materials = 0;
     bool has_scene = false;
     // the specular lobe's roughness and the dielectric lobe's transmission roughness per material (cgpt_scene_update_roughness,
-    // cgpt_scene_update_transmission_roughness; 0 after every upload), the packed material records as they are on the device (a roughness
-    // or material update re-packs them), and the lobe level = the GLOSSY instantiation of the render kernels the renders run: 4 when any
-    // object has a transform (any_xform: level 3 plus transforms), else 3 when any object has smooth normals, else 2 when any transmission roughness is > 0, else 1 when any roughness is > 0, else 0 (UpdateLobeLevel,
-    // cgpt_abi.hip)
+    // cgpt_scene_update_transmission_roughness; 0 after every upload) and the packed material records as they are on the device (a roughness
+    // or material update re-packs them); h_lights is the uploaded light_indices (a light can be neither smooth nor transformed)
     std::vector<float> h_roughness, h_transmission_roughness;
     std::vector<float4> h_materials;
-    uint32_t lobe_level = 0;
-    // cgpt_scene_update_smooth_normals: the flags live in h_objects[i].smooth (0 after every upload; the other edits keep them); any_smooth
-    // selects lobe level 3 and the guide kernel's SMOOTH instantiation; h_lights is the uploaded light_indices (a light cannot be smooth)
-    bool any_smooth = false;
     std::vector<uint32_t> h_lights;
-    // cgpt_scene_update_transforms: the flags live in the objects' obj_trace records, the inverses behind those
-    // records (device_scene.h; identity and 0 after every upload, the other edits keep them); any_xform selects lobe level 4 and the XFORM
-    // instantiations of wf_trace, the guide kernel and intersect_rays_kernel
-    bool any_xform = false;
+    cgpt::SceneFeatures features;
     // cgpt_set_nee_candidates: context state like the stream (an upload keeps it).  A render with more than one candidate, NEE on and
     // TracePathAdvanced paths runs the RIS instantiations of the render kernels
     uint32_t nee_candidates = 1;
@@ -131,6 +125,26 @@ struct cgpt_ctx {
 
 
 namespace cgpt {
+// The choice of kernel variant (kernel_variant.h states the ladder): these three functions are the only readers of ctx->features.
+// ChooseVariant: for a render, or a cgpt_shade_samples call, with the translated settings st and the flags of cgpt_render_params.  The RIS
+// instantiations run only where a candidate loop can: TracePath (BRUTE_FORCE) has no NEE, and NEE may be off.  The one place where DevSettings.nee
+// becomes more than a flag: they read M from it, every other reader tests it for zero (device_scene.h); with one candidate it stays the caller's flag.
+inline ShadeVariant ChooseVariant(const cgpt_ctx* ctx, DevSettings& st, uint32_t render_flags)
+{
+    const SceneFeatures& f = ctx->features;
+    const bool ris = ctx->nee_candidates > 1u && st.nee != 0u && st.render_mode != CGPT_MODE_BRUTE_FORCE;
+    if (ris) st.nee = ctx->nee_candidates;
+    return { (render_flags & CGPT_RENDER_COUNTERS) != 0, (uint32_t)LobeLevel(f.rough_specular, f.rough_dielectric, f.smooth_normals, f.transforms), ris, ctx->top_level != 0u };
+}
+// guides_kernel<SMOOTH, XFORM, TREE> (denoise.hip) has a ladder of its own: 0 none, 1 SMOOTH, 2 + XFORM, 3 + TREE.  The tree has the one
+// instantiation with everything on, a transform the one with smooth normals on.
+constexpr int kGuideLevels = 4;
+inline int ChooseGuideLevel(const cgpt_ctx* ctx) { return ctx->top_level ? 3 : ctx->features.transforms ? 2 : ctx->features.smooth_normals ? 1 : 0; }
+// intersect_rays_kernel<XFORM, TREE> (path_kernels.hip): 0 none, 1 XFORM, 2 + TREE (one instantiation, transforms honoured)
+inline int ChooseIntersectLevel(const cgpt_ctx* ctx) { return ctx->top_level ? 2 : ctx->features.transforms ? 1 : 0; }
+// cgpt_settings as the kernels take them, for cgpt_render and cgpt_shade_samples: CGPT_OK, or the refusal with the context's error set
+int TranslateSettings(cgpt_ctx* ctx, const cgpt_settings& settings, DevSettings& st);
+
 // the device half of a scene upload (cgpt_abi.hip): frees the context's scene and installs the arrays and bookkeeping of a layout that
 // LayoutScene (scene_layout.h) accepted; the caller has selected the device and drained the stream
 int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout);

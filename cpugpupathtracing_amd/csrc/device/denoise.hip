@@ -331,6 +331,9 @@ int ResolveFrame(cgpt_ctx* ctx, bool denoise, const cgpt_camera* camera, Frame& 
     return CGPT_OK;
 }
 
+// [kGuideLevels - 1 - guide level] (ctx_internal.h: ChooseGuideLevel): from the top level down, the order the instantiations have in the code object
+decltype(&guides_kernel<false>) const kGuideKernels[kGuideLevels] = { guides_kernel<true, true, true>, guides_kernel<true, true>, guides_kernel<true>, guides_kernel<false> };
+
 int EnsureGuides(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera)
 {
     cgpt_ctx* d = f.dev;
@@ -350,14 +353,8 @@ int EnsureGuides(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera)
     memcpy(&cam, camera, sizeof(cam));
     const uint32_t tiles = ((f.width + kTile - 1u) / kTile) * ((f.n_rows + kTile - 1u) / kTile);
     const size_t lds = (size_t)d->scene.stack_depth * 256u * sizeof(uint32_t);   // intersect_rays_kernel's stack
-    if (d->top_level) hipLaunchKernelGGL((guides_kernel<true, true, true>), dim3(tiles), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
-                                         d->dn.guides.p, d->dn.guide_demod.p);
-    else if (d->any_xform) hipLaunchKernelGGL((guides_kernel<true, true>), dim3(tiles), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
-                                         d->dn.guides.p, d->dn.guide_demod.p);
-    else if (d->any_smooth) hipLaunchKernelGGL(guides_kernel<true>, dim3(tiles), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
-                                          d->dn.guides.p, d->dn.guide_demod.p);
-    else hipLaunchKernelGGL(guides_kernel<false>, dim3(tiles), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
-                            d->dn.guides.p, d->dn.guide_demod.p);
+    hipLaunchKernelGGL(kGuideKernels[kGuideLevels - 1 - ChooseGuideLevel(d)], dim3(tiles), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
+                       d->dn.guides.p, d->dn.guide_demod.p);
     HIP_TRY(ctx, hipGetLastError());
     memcpy(d->guide_frame, key, sizeof(key));
     memcpy(&d->guide_camera, camera, sizeof(cgpt_camera));

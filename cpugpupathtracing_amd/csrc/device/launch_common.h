@@ -9,17 +9,18 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "cpugpupt_abi.h"
 #include "device_memory.h"
+#include "kernel_variant.h"
 
 namespace cgpt {
 
-// Which instantiation of its render kernels a launcher runs: with the counters of cgpt_stats, the lobe level (ctx_internal.h: GLOSSY) and
-// resampled NEE (shade_device.hpp, above shade_bounce).  The render mode and the call's size pick the rest inside the launcher.
-struct ShadeVariant { bool count; uint32_t lobe_level; bool ris; bool tree; };   // tree: cgpt_set_top_level(1) -- the megakernel and the persistent kernel run level kTreeLevels + lobe_level, the wavefront pipeline its TREE trace kernels
-static constexpr uint32_t kTreeLevels = 5;  // the render kernels' level parameter G >= kTreeLevels: lobe level G - kTreeLevels with the objects reached through the top-level tree
-static inline uint32_t KernelLevel(ShadeVariant v) { return v.tree ? kTreeLevels + v.lobe_level : v.lobe_level; }
+// Which instantiation of its render kernels a launcher runs: counters of cgpt_stats, lobe level (kernel_variant.h), resampled NEE (shade_device.hpp,
+// above shade_bounce), top-level tree.  ChooseVariant (ctx_internal.h) makes it; the render mode and the call's size pick the rest inside the launcher.
+struct ShadeVariant { bool count; uint32_t lobe_level; bool ris; bool tree; };
+static inline uint32_t KernelLevel(ShadeVariant v) { return (uint32_t)KernelLevel((int)v.lobe_level, v.tree); }   // of the megakernel and the persistent kernel
 
 // a HIP call of a launcher: on failure the context's error names the call (as HIP_TRY's does) and the launcher returns -1
 #define LAUNCH_TRY(expr)                                                     \
@@ -69,6 +70,9 @@ inline hipError_t QueryCuCount(uint32_t& n_cus)                              // 
     if (e == hipSuccess) n_cus = (uint32_t)cus;
     return e;
 }
+
+// entries of a kernel table, of a slice of one, or of the host array that mirrors it
+template <typename A> constexpr size_t TableCount(const A& table) { return sizeof(A) / sizeof(std::remove_all_extents_t<A>); }
 
 // resident blocks per CU (at least 1) of n kernels of a table with `lds` bytes of dynamic LDS; beyond the default 48 KiB a kernel opts in
 template <typename F> hipError_t QueryOccupancy(const F* kernels, uint32_t* blocks_per_cu, size_t n, int block_threads, size_t lds)

@@ -11,6 +11,7 @@
 
 #include <algorithm>
 
+#include "ctx_internal.h"
 #include "device_scene.h"
 #include "launch_common.h"
 #include "rt_device.hpp"
@@ -28,13 +29,12 @@ extern __shared__ uint32_t lds_stack[];
 // Block shape: 256 threads = a 16x16-pixel tile (the reference's job size, ref: Main.cpp:705-711), or -- one-sample calls -- 64 threads =
 // one 8x8 tile per single-wave block: the wave's slot and its LDS are free the moment its own longest path ends instead of its block's,
 // and the dispatcher places single waves (1080p, one sample: 1.71 -> 1.68 ms, profiles/r03/one_sample.md).
-// GLOSSY (the lobe level) and RIS: shade_device.hpp, above shade_bounce.  LEVEL: the lobe level, or kTreeLevels + the lobe level with the
-// objects reached through the top-level tree (cgpt_set_top_level(1)).
+// LEVEL: the kernel level, kernel_variant.h.  RIS: shade_device.hpp, above shade_bounce.
 template <bool COUNT, bool BRUTE, int LEVEL, bool RIS>
 __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
 {
-    constexpr bool TREE = LEVEL >= (int)kTreeLevels;
-    constexpr int GLOSSY = TREE ? LEVEL - (int)kTreeLevels : LEVEL;
+    constexpr bool TREE = ThroughTree(LEVEL);
+    constexpr int LOBES = LobeOf(LEVEL);
     const DevScene& sc = args.scene;
     uint32_t* const stack = lds_stack + threadIdx.x;
     const uint32_t stride = blockDim.x;
@@ -87,12 +87,12 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
             // starts from.  It is counted and not walked; the counting kernels walk it, as the oracle does.
             Ray cur = shadow_kind ? sray : ray;
             if (!COUNT && same_ray && !shadow_kind) { cnt.rays++; cnt.unwalked++; }
-            else intersect_scene<COUNT, (GLOSSY >= 4), TREE>(sc, cur, stack, stride, cnt);
+            else intersect_scene<COUNT, HonoursTransforms(LOBES), TREE>(sc, cur, stack, stride, cnt);
 
             bool finalize;
             if (BRUTE && use_brute) {
                 ray.t = cur.t; ray.obj = cur.obj; ray.tri = cur.tri; ray.bvh_depth = cur.bvh_depth;
-                finalize = brute_level<COUNT, GLOSSY>(sc, st, ray, ps.rng, ps.depth, [&](uint32_t k, const BruteLevel& lv) { levels[k] = lv; },
+                finalize = brute_level<COUNT, LOBES>(sc, st, ray, ps.rng, ps.depth, [&](uint32_t k, const BruteLevel& lv) { levels[k] = lv; },
                                                       [&](uint32_t k) { return levels[k]; }, ps.energy, cnt);
             } else if (shadow_kind) {
                 if (cur.obj == kNoHit) ps.energy = ps.energy + pending;       // ref: Main.cpp:454-463
@@ -100,7 +100,7 @@ __global__ void __launch_bounds__(256) megakernel(const DevRenderArgs args)
                 finalize = dead;
             } else {
                 ray.t = cur.t; ray.obj = cur.obj; ray.tri = cur.tri; ray.bvh_depth = cur.bvh_depth;
-                const uint32_t flags = shade_bounce<COUNT, GLOSSY, RIS>(sc, st, ray, ps, sray, pending, cnt);
+                const uint32_t flags = shade_bounce<COUNT, LOBES, RIS>(sc, st, ray, ps, sray, pending, cnt);
                 dead = (flags & kBounceTerminate) != 0;
                 shadow_kind = (flags & kBounceShadow) != 0;
                 same_ray = !dead && ((flags >> kBounceChainShift) & 3u) == kChainTir;
@@ -147,13 +147,13 @@ static uint32_t MegakernelBlockThreads(const DevRenderArgs& args)
     return args.n_samples == 1u ? 64u : 256u;
 }
 
-// every instantiation, [RIS][COUNT][BRUTE][LEVEL]: the lobe levels 0-4, then the same five through the top-level tree
+// every instantiation, [RIS][COUNT][BRUTE][LEVEL]: the lobe levels, then the same through the top-level tree
 #define CGPT_MEGAKERNELS(R) \
     { { { megakernel<false, false, 0, R>, megakernel<false, false, 1, R>, megakernel<false, false, 2, R>, megakernel<false, false, 3, R>, megakernel<false, false, 4, R>, megakernel<false, false, 5, R>, megakernel<false, false, 6, R>, megakernel<false, false, 7, R>, megakernel<false, false, 8, R>, megakernel<false, false, 9, R> },     \
         { megakernel<false, true, 0, R>, megakernel<false, true, 1, R>, megakernel<false, true, 2, R>, megakernel<false, true, 3, R>, megakernel<false, true, 4, R>, megakernel<false, true, 5, R>, megakernel<false, true, 6, R>, megakernel<false, true, 7, R>, megakernel<false, true, 8, R>, megakernel<false, true, 9, R> } },         \
       { { megakernel<true, false, 0, R>, megakernel<true, false, 1, R>, megakernel<true, false, 2, R>, megakernel<true, false, 3, R>, megakernel<true, false, 4, R>, megakernel<true, false, 5, R>, megakernel<true, false, 6, R>, megakernel<true, false, 7, R>, megakernel<true, false, 8, R>, megakernel<true, false, 9, R> },         \
         { megakernel<true, true, 0, R>, megakernel<true, true, 1, R>, megakernel<true, true, 2, R>, megakernel<true, true, 3, R>, megakernel<true, true, 4, R>, megakernel<true, true, 5, R>, megakernel<true, true, 6, R>, megakernel<true, true, 7, R>, megakernel<true, true, 8, R>, megakernel<true, true, 9, R> } } }
-static decltype(&megakernel<false, false, 0, false>) const kMegakernels[2][2][2][10] = { CGPT_MEGAKERNELS(false), CGPT_MEGAKERNELS(true) };
+static decltype(&megakernel<false, false, 0, false>) const kMegakernels[2][2][2][kKernelLevels] = { CGPT_MEGAKERNELS(false), CGPT_MEGAKERNELS(true) };
 #undef CGPT_MEGAKERNELS
 
 hipError_t LaunchMegakernel(const DevRenderArgs& args, ShadeVariant v, hipStream_t stream)
@@ -217,13 +217,15 @@ __global__ void __launch_bounds__(256) intersect_rays_kernel(const DevScene sc, 
     wave_add_u64(&counters->bvh_depth_sum, cnt.depth);
 }
 
-hipError_t LaunchIntersectRays(const DevScene& sc, const float* origins, const float* dirs, const float* tmax, uint32_t n, float* out_t,
-                               uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, DevCounters* counters, bool xform, bool tree, hipStream_t stream)
+hipError_t LaunchIntersectRays(const cgpt_ctx* ctx, const float* origins, const float* dirs, const float* tmax, uint32_t n, float* out_t,
+                               uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth)
 {
-    const size_t lds = (size_t)sc.stack_depth * 256 * sizeof(uint32_t);
-    const auto kernel = tree ? intersect_rays_kernel<true, true> : (xform ? intersect_rays_kernel<true> : intersect_rays_kernel<false>);   // the tree: one instantiation, transforms honoured
-    hipLaunchKernelGGL(kernel, dim3((n + 255u) / 256u), dim3(256), lds, stream, sc, origins, dirs, tmax, n, out_t, out_obj,
-                       out_tri, out_depth, counters);
+    const size_t lds = (size_t)ctx->scene.stack_depth * 256 * sizeof(uint32_t);
+    // a chain of this shape and no table: the order in which the three are first named is their order in the code object, which stays as it was
+    const int level = ChooseIntersectLevel(ctx);
+    const auto kernel = level == 2 ? intersect_rays_kernel<true, true> : (level == 1 ? intersect_rays_kernel<true> : intersect_rays_kernel<false>);
+    hipLaunchKernelGGL(kernel, dim3((n + 255u) / 256u), dim3(256), lds, ctx->stream, ctx->scene, origins, dirs, tmax, n, out_t, out_obj,
+                       out_tri, out_depth, ctx->counters.p);
     return hipGetLastError();
 }
 

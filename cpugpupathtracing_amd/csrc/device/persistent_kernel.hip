@@ -65,14 +65,13 @@ enum : uint32_t {                      // per-lane path flags
 // Main.cpp:702,825-942), which are mostly drain: once nothing is left to fetch, a wave with few busy lanes runs their rays in the lean
 // per-lane loop (trace_steps.hpp: lean_traverse) instead of voted steps, because the call ends when its longest chain does (1080p, one
 // sample: 2.47 -> 2.21 ms).  Kept out of the throughput instantiations, which it costs registers and SGPR spills (profiles/r03/one_sample.md).
-// GLOSSY (the lobe level) and RIS: shade_device.hpp, above shade_bounce.  LEVEL: the lobe level, or kTreeLevels + the lobe level with the
-// objects reached through the top-level tree (cgpt_set_top_level(1)).
+// LEVEL: the kernel level, kernel_variant.h.  RIS: shade_device.hpp, above shade_bounce.
 template <bool COUNT, bool BRUTE, bool TAIL, int LEVEL, bool RIS>
 __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderArgs args, const PtDev pt, uint32_t batch_first, const TraceTune tune)
 {
-    constexpr bool TREE = LEVEL >= (int)kTreeLevels;                          // the objects are reached through the top-level tree, at the scene's own lobe level
-    constexpr int GLOSSY = TREE ? LEVEL - (int)kTreeLevels : LEVEL;
-    constexpr bool XFORM = GLOSSY >= 4;                                       // the scene has a transformed object (trace_steps.hpp)
+    constexpr bool TREE = ThroughTree(LEVEL);                                 // the objects are reached through the top-level tree, at the scene's own lobe level
+    constexpr int LOBES = LobeOf(LEVEL);
+    constexpr bool XFORM = HonoursTransforms(LOBES);                          // the scene has a transformed object (trace_steps.hpp)
     constexpr bool STEP = XFORM || TREE;
     const DevScene& sc = args.scene;
     const DevSettings& st = args.settings;
@@ -134,7 +133,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
             // one TracePath level (shade_device.hpp: brute_level), the chain in this thread's column of pt.brute
             uint32_t depth = pf & kPfDepthMask;
             V3 L;
-            const bool done = brute_level<COUNT, GLOSSY>(sc, st, ray, rng, depth,
+            const bool done = brute_level<COUNT, LOBES>(sc, st, ray, rng, depth,
                 [&](uint32_t k, const BruteLevel& lv) {
                     float4* rec = pt.brute + ((size_t)k * grid_threads + tid) * 2u;
                     float4 r0, r1;
@@ -154,7 +153,7 @@ __global__ void __launch_bounds__(kTraceBlock, 1) pt_persistent(const DevRenderA
             ps.throughput = tp; ps.energy = en; ps.rng = rng; ps.depth = pf & kPfDepthMask; ps.is_specular = (pf & kPfSpecular) != 0u;
             Ray shadow = ray;
             V3 pend = mk(0.0f);
-            const uint32_t flags = shade_bounce<COUNT, GLOSSY, RIS>(sc, st, ray, ps, shadow, pend, cnt);
+            const uint32_t flags = shade_bounce<COUNT, LOBES, RIS>(sc, st, ray, ps, shadow, pend, cnt);
             tp = ps.throughput; en = ps.energy; rng = ps.rng;
             pf = (ps.depth & kPfDepthMask) | (ps.is_specular ? kPfSpecular : 0u);   // every other flag starts clear: kPfSameRay is this bounce's or none
             const bool dead = (flags & kBounceTerminate) != 0u;
@@ -275,12 +274,13 @@ struct PtTuning {
 #define CGPT_PT_LEVEL(G, R) \
     { { { pt_persistent<false, false, false, G, R>, pt_persistent<false, false, true, G, R> }, { pt_persistent<false, true, false, G, R>, pt_persistent<false, true, true, G, R> } }, \
       { { pt_persistent<true, false, false, G, R>, pt_persistent<true, false, true, G, R> }, { pt_persistent<true, true, false, G, R>, pt_persistent<true, true, true, G, R> } } }
-static decltype(&pt_persistent<false, false, false, 0, false>) const kPtKernels[2][10][2][2][2] = {   // levels 5-9: 0-4 through the top-level tree
+static decltype(&pt_persistent<false, false, false, 0, false>) const kPtKernels[2][kKernelLevels][2][2][2] = {   // the second half of the levels: the first through the top-level tree
     { CGPT_PT_LEVEL(0, false), CGPT_PT_LEVEL(1, false), CGPT_PT_LEVEL(2, false), CGPT_PT_LEVEL(3, false), CGPT_PT_LEVEL(4, false), CGPT_PT_LEVEL(5, false), CGPT_PT_LEVEL(6, false), CGPT_PT_LEVEL(7, false), CGPT_PT_LEVEL(8, false), CGPT_PT_LEVEL(9, false) },
     { CGPT_PT_LEVEL(0, true), CGPT_PT_LEVEL(1, true), CGPT_PT_LEVEL(2, true), CGPT_PT_LEVEL(3, true), CGPT_PT_LEVEL(4, true), CGPT_PT_LEVEL(5, true), CGPT_PT_LEVEL(6, true), CGPT_PT_LEVEL(7, true), CGPT_PT_LEVEL(8, true), CGPT_PT_LEVEL(9, true) },
 };
 #undef CGPT_PT_LEVEL
-static constexpr size_t kPtKernelCount = sizeof(kPtKernels) / sizeof(kPtKernels[0][0][0][0][0]);
+static constexpr size_t kPtKernelCount = TableCount(kPtKernels);
+static constexpr size_t kPtListKernelCount = kLobeLevels * TableCount(kPtKernels[0][0]);   // per RIS: the levels without the tree, and as many with it
 
 struct PtHost {
     PtTuning tune;
@@ -292,8 +292,8 @@ struct PtHost {
     hipEvent_t begin = nullptr, acc_done[2] = { nullptr, nullptr };
     EventPairs ev;
     uint32_t n_cus = 0;
-    uint32_t blocks_per_cu[2][10][2][2][2] = {}; // [RIS][LEVEL][COUNT][BRUTE][TAIL]; the tree levels are queried at the first launch with the tree on
-    static_assert(sizeof(blocks_per_cu) / sizeof(uint32_t) == kPtKernelCount, "one occupancy entry per instantiation");
+    uint32_t blocks_per_cu[2][kKernelLevels][2][2][2] = {}; // [RIS][LEVEL][COUNT][BRUTE][TAIL]; the tree levels are queried at the first launch with the tree on
+    static_assert(sizeof(blocks_per_cu) / sizeof(uint32_t) == kPtKernelCount && 2 * 2 * kPtListKernelCount == kPtKernelCount, "one occupancy entry per instantiation");
     size_t occupancy_lds = 0, tree_occupancy_lds = 0;
 };
 
@@ -373,12 +373,12 @@ int LaunchPersistent(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v
     const size_t lds = trace_lds_bytes(top_records);
     if (h->occupancy_lds != lds) {
         for (uint32_t ris = 0; ris < 2u; ++ris)                               // the list kernels: what mode 0 always queried
-            LAUNCH_TRY(QueryOccupancy(&kPtKernels[ris][0][0][0][0], &h->blocks_per_cu[ris][0][0][0][0], kPtKernelCount / 4u, kTraceBlock, lds));
+            LAUNCH_TRY(QueryOccupancy(&kPtKernels[ris][0][0][0][0], &h->blocks_per_cu[ris][0][0][0][0], kPtListKernelCount, kTraceBlock, lds));
         h->occupancy_lds = lds;
     }
     if (v.tree && h->tree_occupancy_lds != lds) {
         for (uint32_t ris = 0; ris < 2u; ++ris)
-            LAUNCH_TRY(QueryOccupancy(&kPtKernels[ris][kTreeLevels][0][0][0], &h->blocks_per_cu[ris][kTreeLevels][0][0][0], kPtKernelCount / 4u, kTraceBlock, lds));
+            LAUNCH_TRY(QueryOccupancy(&kPtKernels[ris][KernelLevel(kLobesMirror, true)][0][0][0], &h->blocks_per_cu[ris][KernelLevel(kLobesMirror, true)][0][0][0], kPtListKernelCount, kTraceBlock, lds));
         h->tree_occupancy_lds = lds;
     }
     const bool tail = args_in.n_samples <= h->tune.tail_samples;              // a small call: mostly drain

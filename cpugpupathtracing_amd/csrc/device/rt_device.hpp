@@ -567,8 +567,8 @@ __device__ __forceinline__ V3 refract(V3 dir, V3 normal, float eta, float cosi, 
 // ---- materials ---------------------------------------------------------------------------------------------------------
 struct Mat {
     V3 albedo; float specular, refractivity; V3 absorption; float ior; V3 emissive; float intensity; bool is_light;
-    float alpha;          // GGX alpha = roughness^2 of the specular lobe (0: the mirror); read by the GLOSSY instantiations only
-    float alpha_t;        // GGX alpha = transmission roughness^2 of the dielectric lobe (0: polished); read by the GLOSSY == 2 instantiations only
+    float alpha;          // GGX alpha = roughness^2 of the specular lobe (0: the mirror); read by the HasRoughSpecular instantiations only (kernel_variant.h)
+    float alpha_t;        // GGX alpha = transmission roughness^2 of the dielectric lobe (0: polished); read by the HasRoughDielectric instantiations only
 };
 __device__ __forceinline__ Mat load_material(const DevScene& sc, uint32_t index)
 {

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_scene.h"
+#include "kernel_variant.h"
 #include "rt_device.hpp"
 
 namespace cgpt {
@@ -201,7 +202,7 @@ __device__ __forceinline__ uint32_t smooth_glass(const Mat& mat, const Hit& hit,
     return kGlassReflect;
 }
 
-// ---- rough lobes (GLOSSY instantiations) ------------------------------------------------------------------
+// ---- rough lobes (kernel_variant.h) -----------------------------------------------------------------------
 // Smith L(w) = (-1 + sqrt(1 + alpha^2 tan^2(theta_w))) / 2 of a direction whose cosine to n is z (a2 = alpha^2).
 __device__ __forceinline__ float ggx_lambda(float a2, float z)
 {
@@ -239,7 +240,7 @@ __device__ __forceinline__ bool ggx_visible_normal(float u1, float u2, V3 d, V3 
     return true;
 }
 
-// Rough specular lobe (GLOSSY >= 1): isotropic GGX reflection with the constant Fresnel `albedo` the mirror lobe has.  h is drawn with
+// Rough specular lobe (HasRoughSpecular): isotropic GGX reflection with the constant Fresnel `albedo` the mirror lobe has.  h is drawn with
 // u1, u2 -- the two draws after the lobe choice -- and wi = reflect(-wo, h).  D and the sampling pdf cancel: the estimator's factor is
 // G2 / G1 with the height-correlated Smith G2 = 1 / (1 + L(wo) + L(wi)), G1 = 1 / (1 + L(wo)).
 // Returns false when wi lies at or below the horizon of n (or wo grazes it): the lobe has no energy there.
@@ -259,7 +260,7 @@ __device__ __forceinline__ bool ggx_sample(uint32_t& rng, V3 d, V3 normal, float
     return true;
 }
 
-// Rough dielectric lobe (GLOSSY == 2, Walter et al. 2007): the smooth lobe's interface with the microfacet normal h in the role of the
+// Rough dielectric lobe (HasRoughDielectric, Walter et al. 2007): the smooth lobe's interface with the microfacet normal h in the role of the
 // normal.  Sides and indices are the smooth lobe's, from dot(normal, d); h comes from the visible normals with u1, u2; with c = wo.h and
 // k = 1 - eta^2 (1 - c^2), a facet with k >= 0 draws one more float against the reference's fresnel() and refracts when it is greater,
 // and a facet with k < 0 reflects totally (no draw) -- physical TIR, not the smooth lobe's re-traced ray or black leaf.  The factor is
@@ -308,23 +309,21 @@ enum : uint32_t { kBounceChainShift = 4u, kChainReflect = 1u, kChainRefract = 2u
 // Processes the hit of `ray` (already traced).  On return: `ray` is the next extend ray unless kBounceTerminate is set;
 // if kBounceShadow is set, `shadow` / `pending` describe the NEE connection to trace (energy += pending when unoccluded,
 // ref: Main.cpp:452-463).  Emissive energy is added here; the final debug-view overrides are applied by the caller.
-// GLOSSY: 0 no rough lobe (the mirror-only code); 1 the scene has a material with roughness > 0 (ggx_sample); 2 it has one with a
-// transmission roughness > 0 (rough_glass_sample; this instantiation carries the rough specular lobe too); 3 it has an object with smooth
-// normals (get_hit's SMOOTH; carries both rough lobes, so the tables grow by one level and not by a factor of two -- DESIGN.md 5.14); 4 it has
-// an object with a transform (get_hit's XFORM and the trace side's; level 3 plus transforms -- DESIGN.md 5.16).
+// LOBES: the lobe level, kernel_variant.h.
 // RIS: the NEE light sample is the survivor of M = st.nee > 1 candidates (resampled importance sampling); the
 // instantiations without it keep the one-sample code.
-template <bool COUNT, int GLOSSY = 0, bool RIS = false>
+template <bool COUNT, int LOBES = 0, bool RIS = false>
 __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSettings& st, Ray& ray, PathState& ps, Ray& shadow,
                                                  V3& pending, Counters& cnt)
 {
+    constexpr bool ROUGH_SPECULAR = HasRoughSpecular(LOBES), ROUGH_DIELECTRIC = HasRoughDielectric(LOBES);
     if (ps.depth == 0 && st.debug_mode == 2u) {                               // BVH-depth view, ref: Main.cpp:408-412
         ps.energy = ps.energy + bvh_depth_colour(ray);
         return kBounceTerminate | kBounceEnergy;
     }
     if (ray.obj == kNoHit) return kBounceTerminate;                           // ref: Main.cpp:415-416
 
-    const Hit hit = get_hit<COUNT, (GLOSSY >= 3), (GLOSSY >= 4)>(sc, ray, cnt);
+    const Hit hit = get_hit<COUNT, ReadsSmoothNormals(LOBES), HonoursTransforms(LOBES)>(sc, ray, cnt);
     const Mat mat = load_material(sc, hit.mat);
     if (mat.is_light) {                                                       // ref: Main.cpp:424-431
         if (!st.nee || ps.depth == 0 || ps.is_specular) {
@@ -390,7 +389,7 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
     // through the lobes below as it always did.  Not in the counting kernels, which walk every ray the oracle walks.
     bool absorbed = false;
     if (!COUNT && !(sc.n_lights > 0 && st.nee && diffuse_weight > 0.001f)) {
-        const bool rough_t = GLOSSY >= 2 && mat.alpha_t > 0.0f;
+        const bool rough_t = ROUGH_DIELECTRIC && mat.alpha_t > 0.0f;
         V3 N; float cosi, etai, etat; bool inside;
         if (!rough_t && !(r < mat.specular) && r < mat.specular + mat.refractivity && !(glass_interface(mat, hit, ray, N, cosi, etai, etat, inside) >= 0.0f)) {
             while ((int32_t)(ps.depth + 1u) <= st.max_ray_depth) {
@@ -408,7 +407,7 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
         }
     }
 
-    if (GLOSSY >= 1 && r < mat.specular && mat.alpha > 0.0f) {                     // rough specular lobe
+    if (ROUGH_SPECULAR && r < mat.specular && mat.alpha > 0.0f) {                     // rough specular lobe
         V3 gd; float g;
         if (!ggx_sample(ps.rng, ray.d, hit.normal, mat.alpha, gd, g)) return result | kBounceTerminate;   // below the horizon: ends as RR ends it
         ray = next_ray(hit, gd);
@@ -419,7 +418,7 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
         ps.throughput = ps.throughput * mat.albedo;
         ps.is_specular = true;
         result |= kChainReflect << kBounceChainShift;
-    } else if (GLOSSY >= 2 && r < mat.specular + mat.refractivity && mat.alpha_t > 0.0f) {   // rough dielectric lobe
+    } else if (ROUGH_DIELECTRIC && r < mat.specular + mat.refractivity && mat.alpha_t > 0.0f) {   // rough dielectric lobe
         V3 gd; float g; bool inside;
         const uint32_t kind = rough_glass_sample(ps.rng, ray.d, hit.normal, mat.alpha_t, mat.ior, gd, g, inside);
         if (kind == kRoughGlassNone) return result | kBounceTerminate;       // the wrong side: ends as RR ends it
@@ -481,25 +480,26 @@ static constexpr uint32_t kMaxBruteLevels = 32;   // max_ray_depth + 1 levels ar
 enum : uint32_t { kBruteContinue = 0u, kBruteLeaf = 1u };
 
 // One TracePath level after IntersectScene(ray): either a leaf (returns its radiance in `leaf`) or a bounce (fills `level`,
-// replaces `ray` by the child ray).  RNG draw order as in the reference: r, then Fresnel choice or the hemisphere sample (or, GLOSSY, the
+// replaces `ray` by the child ray).  RNG draw order as in the reference: r, then Fresnel choice or the hemisphere sample (or, a rough lobe, the
 // draws of ggx_sample / rough_glass_sample; a rough lobe on the wrong side of the horizon is a black leaf, as the smooth lobe's total
 // internal reflection is).
-template <bool COUNT, int GLOSSY = 0>
+template <bool COUNT, int LOBES = 0>
 __device__ __forceinline__ uint32_t brute_bounce(const DevScene& sc, const DevSettings& st, Ray& ray, uint32_t& rng, uint32_t depth,
                                                  BruteLevel& level, V3& leaf, Counters& cnt)
 {
+    constexpr bool ROUGH_SPECULAR = HasRoughSpecular(LOBES), ROUGH_DIELECTRIC = HasRoughDielectric(LOBES);
     if (depth == 0 && st.debug_mode == 2u) {                                  // ref: Main.cpp:594-597
         leaf = bvh_depth_colour(ray);
         return kBruteLeaf;
     }
     if (ray.obj == kNoHit) { leaf = mk(0.0f); return kBruteLeaf; }            // ref: Main.cpp:600-601
-    const Hit hit = get_hit<COUNT, (GLOSSY >= 3), (GLOSSY >= 4)>(sc, ray, cnt);
+    const Hit hit = get_hit<COUNT, ReadsSmoothNormals(LOBES), HonoursTransforms(LOBES)>(sc, ray, cnt);
     const Mat mat = load_material(sc, hit.mat);
     if (mat.is_light) { leaf = mat.emissive * mat.intensity; return kBruteLeaf; }   // ref: Main.cpp:606-609
 
     const float r = random_float(rng);                                        // ref: Main.cpp:611
     level.cosi = 0.0f; level.absorb = mk(1.0f);
-    if (GLOSSY >= 1 && r < mat.specular && mat.alpha > 0.0f) {                     // rough specular lobe: L = 0 + (albedo * G2/G1) * L
+    if (ROUGH_SPECULAR && r < mat.specular && mat.alpha > 0.0f) {                     // rough specular lobe: L = 0 + (albedo * G2/G1) * L
         V3 gd; float g;
         if (!ggx_sample(rng, ray.d, hit.normal, mat.alpha, gd, g)) { leaf = mk(0.0f); return kBruteLeaf; }
         ray = next_ray(hit, gd);
@@ -507,7 +507,7 @@ __device__ __forceinline__ uint32_t brute_bounce(const DevScene& sc, const DevSe
     } else if (r < mat.specular) {                                            // ref: Main.cpp:614-619
         ray = next_ray(hit, reflect(ray.d, hit.normal));
         level.kind = 0u; level.a = mat.albedo;
-    } else if (GLOSSY >= 2 && r < mat.specular + mat.refractivity && mat.alpha_t > 0.0f) {   // rough dielectric lobe
+    } else if (ROUGH_DIELECTRIC && r < mat.specular + mat.refractivity && mat.alpha_t > 0.0f) {   // rough dielectric lobe
         V3 gd; float g; bool inside;
         const uint32_t kind = rough_glass_sample(rng, ray.d, hit.normal, mat.alpha_t, mat.ior, gd, g, inside);
         if (kind == kRoughGlassNone) { leaf = mk(0.0f); return kBruteLeaf; }
@@ -562,14 +562,14 @@ __device__ __forceinline__ BruteLevel brute_unpack(float4 r0, float4 r1)
 // Where the chain lives is the caller's business.  When the depth cut-off fires -- the child returns black before tracing (ref:
 // Main.cpp:589-590) -- the level just made is applied from registers instead of being stored and loaded back: brute_apply(level, 0) is what
 // the fold's first step would compute.
-template <bool COUNT, int GLOSSY, class Store, class Load>
+template <bool COUNT, int LOBES, class Store, class Load>
 __device__ __forceinline__ bool brute_level(const DevScene& sc, const DevSettings& st, Ray& ray, uint32_t& rng, uint32_t& depth, Store store, Load load,
                                             V3& L, Counters& cnt)
 {
     BruteLevel lv;
     L = mk(0.0f);
     uint32_t stored = depth;                                                  // levels 0 .. stored-1 are recorded
-    if (brute_bounce<COUNT, GLOSSY>(sc, st, ray, rng, depth, lv, L, cnt) != kBruteLeaf) {
+    if (brute_bounce<COUNT, LOBES>(sc, st, ray, rng, depth, lv, L, cnt) != kBruteLeaf) {
         depth++;
         if ((int32_t)depth <= st.max_ray_depth) { store(stored, lv); return false; }
         L = brute_apply(lv, mk(0.0f));

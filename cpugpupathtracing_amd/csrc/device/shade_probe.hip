@@ -1,7 +1,7 @@
 // shade_probe.hip -- cgpt_shade_samples: shade_bounce on samples the host supplies (gfx950), the shade step's counterpart of
-// cgpt_intersect_rays.  One thread loads one sample, calls shade_bounce<false, LEVEL, RIS> once and stores what it left; nothing is traced.
-// LEVEL and RIS are chosen as RenderEnqueue chooses them (cgpt_abi.hip), so the code a sample runs through is the code a render of this
-// context inlines into its kernels.  tests/shade_ref.py states the bounce in numpy and is what the results are compared with.
+// cgpt_intersect_rays.  One thread loads one sample, calls shade_bounce<false, LOBES, RIS> once and stores what it left; nothing is traced.
+// LOBES and RIS come from the function that chooses them for a render (ctx_internal.h: ChooseVariant), so the code a sample runs through is
+// the code a render of this context inlines into its kernels.  tests/shade_ref.py states the bounce in numpy and is what the results are compared with.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -22,7 +22,7 @@ constexpr uint32_t kMaxSamples = 65536;
 
 static_assert(sizeof(cgpt_shade_sample) == 64 && sizeof(cgpt_shade_result) == 112, "the sample records are 16 and 28 words");
 
-template <int LEVEL, bool RIS>
+template <int LOBES, bool RIS>
 __global__ void __launch_bounds__(256) shade_samples_kernel(const DevScene sc, const DevSettings st, const cgpt_shade_sample* __restrict__ samples,
                                                             uint32_t n, cgpt_shade_result* __restrict__ results)
 {
@@ -36,7 +36,7 @@ __global__ void __launch_bounds__(256) shade_samples_kernel(const DevScene sc, c
     Ray shadow = make_ray(mk(0.0f), mk(0.0f), 0.0f);
     V3 pending = mk(0.0f);
     Counters cnt = { 0, 0, 0, 0, 0, 0 };
-    const uint32_t flags = shade_bounce<false, LEVEL, RIS>(sc, st, ray, ps, shadow, pending, cnt);
+    const uint32_t flags = shade_bounce<false, LOBES, RIS>(sc, st, ray, ps, shadow, pending, cnt);
     if (!(flags & kBounceShadow)) { shadow = make_ray(mk(0.0f), mk(0.0f), 0.0f); pending = mk(0.0f); }
     cgpt_shade_result r;
     r.flags = flags;
@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(256) shade_samples_kernel(const DevScene sc, c
 
 // [RIS][lobe level]
 #define CGPT_SHADE_PROBES(R) { shade_samples_kernel<0, R>, shade_samples_kernel<1, R>, shade_samples_kernel<2, R>, shade_samples_kernel<3, R>, shade_samples_kernel<4, R> }
-decltype(&shade_samples_kernel<0, false>) const kShadeProbes[2][5] = { CGPT_SHADE_PROBES(false), CGPT_SHADE_PROBES(true) };
+decltype(&shade_samples_kernel<0, false>) const kShadeProbes[2][kLobeLevels] = { CGPT_SHADE_PROBES(false), CGPT_SHADE_PROBES(true) };
 #undef CGPT_SHADE_PROBES
 
 bool Finite3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
@@ -71,10 +71,9 @@ extern "C" int cgpt_shade_samples(cgpt_ctx* ctx, const cgpt_settings* settings, 
     if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "cgpt_shade_samples before cgpt_scene_upload");
     if (!settings || !samples || !results) return CtxFail(ctx, CGPT_ERR_INVALID, "null argument");
     if (n == 0 || n > kMaxSamples) return CtxFail(ctx, CGPT_ERR_INVALID, "%u samples outside [1, %u]", n, kMaxSamples);
-    if (settings->max_ray_depth < 0 || settings->max_ray_depth > 254)
-        return CtxFail(ctx, CGPT_ERR_INVALID, "max_ray_depth %d outside [0,254] (ray_depth is a uint8_t in the reference, Main.cpp:401)", settings->max_ray_depth);
-    if (settings->render_mode > CGPT_MODE_ADVANCED || settings->debug_render_mode > CGPT_DEBUG_BVH_DEPTH)
-        return CtxFail(ctx, CGPT_ERR_INVALID, "bad render_mode/debug_render_mode");
+    DevSettings st{};
+    const int rc = TranslateSettings(ctx, *settings, st);
+    if (rc != CGPT_OK) return rc;
     // the kernel indexes objects[], the triangle records and (through objects[].mat_index, checked at upload) materials[] with these numbers
     for (uint32_t i = 0; i < n; ++i) {
         const cgpt_shade_sample& s = samples[i];
@@ -87,22 +86,15 @@ extern "C" int cgpt_shade_samples(cgpt_ctx* ctx, const cgpt_settings* settings, 
             return CtxFail(ctx, CGPT_ERR_INVALID, "sample %u: t, o, d or throughput of a hit is not finite", i);
     }
 
-    DevSettings st{};
-    st.max_ray_depth = settings->max_ray_depth;
-    st.nee = settings->next_event_estimation_enabled;
-    st.cosine = settings->cosine_weighted_diffuse_reflection_enabled;
-    st.rr = settings->russian_roulette_enabled;
-    st.render_mode = CGPT_MODE_ADVANCED;
-    st.debug_mode = settings->debug_render_mode;
-    const bool ris = ctx->nee_candidates > 1u && st.nee != 0u;                 // as RenderEnqueue decides it; M travels in nee (device_scene.h)
-    if (ris) st.nee = ctx->nee_candidates;
+    st.render_mode = CGPT_MODE_ADVANCED;                                       // the probe is shade_bounce, whatever the mode: RIS as an ADVANCED render has it
+    const ShadeVariant v = ChooseVariant(ctx, st, 0u);
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevBuf<cgpt_shade_sample> d_in;
     DevBuf<cgpt_shade_result> d_out;
     HIP_TRY(ctx, d_in.Alloc(n)); HIP_TRY(ctx, d_out.Alloc(n));
     HIP_TRY(ctx, hipMemcpyAsync(d_in.p, samples, sizeof(cgpt_shade_sample) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(kShadeProbes[ris][ctx->lobe_level], dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->scene, st, d_in.p, n, d_out.p);
+    hipLaunchKernelGGL(kShadeProbes[v.ris][v.lobe_level], dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->scene, st, d_in.p, n, d_out.p);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(results, d_out.p, sizeof(cgpt_shade_result) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

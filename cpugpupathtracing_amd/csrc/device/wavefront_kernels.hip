@@ -323,9 +323,9 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
 
 // ---- K3 shade: one bounce per extend hit; survivors compacted into this wave's output segment ---------------------------
 // BRUTE: the render has TracePath paths (RENDER_MODE_BRUTE_FORCE / COMPARISON); a separate instantiation, so the TracePathAdvanced
-// renders carry neither its code nor its registers.  GLOSSY (the lobe level) and RIS: shade_device.hpp, above shade_bounce.
+// renders carry neither its code nor its registers.  LOBES: the lobe level, kernel_variant.h.  RIS: shade_device.hpp, above shade_bounce.
 // A rough bounce reports lobe choice 0, so its ray is never elected or followed as a specular chain.
-template <bool COUNT, bool FIRST, bool BRUTE = false, int GLOSSY = 0, bool RIS = false>
+template <bool COUNT, bool FIRST, bool BRUTE = false, int LOBES = 0, bool RIS = false>
 __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, const WfDev wf, uint32_t batch_first)
 {
     constexpr bool first_round = FIRST;
@@ -457,7 +457,7 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
             if (BRUTE && brute_path) {
                 // one TracePath level (shade_device.hpp: brute_level), the chain in this path's column of wf.brute
                 if (is_pixel) {
-                    const bool done = brute_level<COUNT, GLOSSY>(sc, args.settings, ray, ps.rng, ps.depth,
+                    const bool done = brute_level<COUNT, LOBES>(sc, args.settings, ray, ps.rng, ps.depth,
                         [&](uint32_t k, const BruteLevel& lv) {
                             float4* rec = wf.brute + ((size_t)k * wf.cap + pid) * 2u;
                             float4 r0, r1;
@@ -468,7 +468,7 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
                         ps.energy, cnt);
                     flags = done ? kBounceTerminate | kBounceBruteDone : 0u;
                 }
-            } else if (is_pixel) flags = shade_bounce<COUNT, GLOSSY, RIS>(sc, args.settings, ray, ps, shadow, pending, cnt);
+            } else if (is_pixel) flags = shade_bounce<COUNT, LOBES, RIS>(sc, args.settings, ray, ps, shadow, pending, cnt);
             if (!COUNT) { absorbed = cnt.unwalked; cnt.unwalked = 0; }       // shade_bounce's stuck iterations, each an IntersectScene call of the reference
             emit_ext = (flags & kBounceTerminate) == 0u;
             emit_sh = (flags & kBounceShadow) != 0u;
@@ -733,7 +733,7 @@ static uint32_t CoprimeRotation(uint32_t n_waves, uint32_t n_tiles)
     return 0u;
 }
 
-// every instantiation: trace [XFORM][COUNT][FIRST], shade [RIS][GLOSSY][COUNT][FIRST][BRUTE]
+// every instantiation: trace [XFORM][COUNT][FIRST], shade [RIS][LOBES][COUNT][FIRST][BRUTE]
 static decltype(&wf_trace<false, false>) const kTraceKernels[2][2][2] = {
     { { wf_trace<false, false>, wf_trace<false, true> }, { wf_trace<true, false>, wf_trace<true, true> } },
     { { wf_trace<false, false, true>, wf_trace<false, true, true> }, { wf_trace<true, false, true>, wf_trace<true, true, true> } },
@@ -747,7 +747,7 @@ static decltype(&wf_trace<false, false>) const kTraceTreeKernels[2][2][2] = {
 #define CGPT_SHADE_LEVEL(G, R) \
     { { { wf_shade<false, false, false, G, R>, wf_shade<false, false, true, G, R> }, { wf_shade<false, true, false, G, R>, wf_shade<false, true, true, G, R> } }, \
       { { wf_shade<true, false, false, G, R>, wf_shade<true, false, true, G, R> }, { wf_shade<true, true, false, G, R>, wf_shade<true, true, true, G, R> } } }
-static decltype(&wf_shade<false, false>) const kShadeKernels[2][5][2][2][2] = {
+static decltype(&wf_shade<false, false>) const kShadeKernels[2][kLobeLevels][2][2][2] = {
     { CGPT_SHADE_LEVEL(0, false), CGPT_SHADE_LEVEL(1, false), CGPT_SHADE_LEVEL(2, false), CGPT_SHADE_LEVEL(3, false), CGPT_SHADE_LEVEL(4, false) },
     { CGPT_SHADE_LEVEL(0, true), CGPT_SHADE_LEVEL(1, true), CGPT_SHADE_LEVEL(2, true), CGPT_SHADE_LEVEL(3, true), CGPT_SHADE_LEVEL(4, true) },
 };
@@ -802,7 +802,7 @@ struct WfHost {
     uint32_t held_pools = 0;
     uint32_t spec_epoch[kMaxPools] = {};         // last epoch used in each pool's spec_tab
     uint32_t n_cus = 0;
-    uint32_t trace_blocks_per_cu[2][2][2] = {}, shade_blocks_per_cu[2][5][2][2] = {};   // trace: [XFORM][COUNT][FIRST]; shade: [RIS][GLOSSY][COUNT][BRUTE]
+    uint32_t trace_blocks_per_cu[2][2][2] = {}, shade_blocks_per_cu[2][kLobeLevels][2][2] = {};   // trace: [XFORM][COUNT][FIRST]; shade: [RIS][LOBES][COUNT][BRUTE]
     bool last_xform = false;                     // the last render ran the XFORM trace kernels (WavefrontTraceWavesPerSimd)
     uint32_t trace_tree_blocks_per_cu[2][2][2] = {};   // kTraceTreeKernels: queried by the first render with the tree on
     bool last_tree = false;
@@ -919,23 +919,25 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
     const size_t trace_lds = trace_lds_bytes(top_records);
     // persistent grids = the resident capacity of the chip for each kernel
     if (h->occupancy_lds != trace_lds) {
-        LAUNCH_TRY(QueryOccupancy(&kTraceKernels[0][0][0], &h->trace_blocks_per_cu[0][0][0], 8, kTraceBlock, trace_lds));
+        static_assert(TableCount(kTraceKernels) == sizeof(h->trace_blocks_per_cu) / sizeof(uint32_t) && TableCount(kTraceTreeKernels) == sizeof(h->trace_tree_blocks_per_cu) / sizeof(uint32_t), "one occupancy entry per trace kernel");
+        LAUNCH_TRY(QueryOccupancy(&kTraceKernels[0][0][0], &h->trace_blocks_per_cu[0][0][0], TableCount(kTraceKernels), kTraceBlock, trace_lds));
         // shade: the round-0 and later-round instantiations share one grid size (one output segment per wave)
-        uint32_t shade[2][5][2][2][2];
-        LAUNCH_TRY(QueryOccupancy(&kShadeKernels[0][0][0][0][0], &shade[0][0][0][0][0], 80, 256, 0));
+        uint32_t shade[2][kLobeLevels][2][2][2];
+        static_assert(sizeof(shade) / sizeof(uint32_t) == TableCount(kShadeKernels), "one occupancy entry per shade kernel");
+        LAUNCH_TRY(QueryOccupancy(&kShadeKernels[0][0][0][0][0], &shade[0][0][0][0][0], TableCount(kShadeKernels), 256, 0));
         for (int r = 0; r < 2; ++r)
-            for (int g = 0; g < 5; ++g)
+            for (int g = 0; g < kLobeLevels; ++g)
                 for (int c = 0; c < 2; ++c)
                     for (int b = 0; b < 2; ++b) h->shade_blocks_per_cu[r][g][c][b] = std::min(shade[r][g][c][0][b], shade[r][g][c][1][b]);
         h->occupancy_lds = trace_lds;
     }
     const dim3 block(256);
-    const bool xform = v.lobe_level >= 4u;                                    // the scene has a transformed object: the XFORM trace kernels
+    const bool xform = HonoursTransforms((int)v.lobe_level);                  // the scene has a transformed object: the XFORM trace kernels
     h->last_xform = xform;
     const bool tree = v.tree;                                                 // cgpt_set_top_level(1): the TREE trace kernels
     h->last_tree = tree;
     if (tree && h->tree_occupancy_lds != trace_lds) {
-        LAUNCH_TRY(QueryOccupancy(&kTraceTreeKernels[0][0][0], &h->trace_tree_blocks_per_cu[0][0][0], 8, kTraceBlock, trace_lds));
+        LAUNCH_TRY(QueryOccupancy(&kTraceTreeKernels[0][0][0], &h->trace_tree_blocks_per_cu[0][0][0], TableCount(kTraceTreeKernels), kTraceBlock, trace_lds));
         h->tree_occupancy_lds = trace_lds;
     }
     const uint32_t (&trace_blocks)[2][2][2] = tree ? h->trace_tree_blocks_per_cu : h->trace_blocks_per_cu;
@@ -951,8 +953,8 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
     const uint32_t min_shade_waves = n_cus * std::min({ shade_blocks[0][0], shade_blocks[1][0], shade_blocks[0][1], shade_blocks[1][1] }) * 4u;
 
     // deep end of the traversal stacks: one dword per level beyond the LDS part and per thread of the largest trace grid
-    const uint32_t max_trace_threads = n_cus * std::max(*std::max_element(&h->trace_blocks_per_cu[0][0][0], &h->trace_blocks_per_cu[0][0][0] + 8),
-                                                        *std::max_element(&h->trace_tree_blocks_per_cu[0][0][0], &h->trace_tree_blocks_per_cu[0][0][0] + 8)) * kTraceBlock;   // (the tree's entries are 0 until it is used)
+    const uint32_t max_trace_threads = n_cus * std::max(*std::max_element(&h->trace_blocks_per_cu[0][0][0], &h->trace_blocks_per_cu[0][0][0] + TableCount(h->trace_blocks_per_cu)),
+                                                        *std::max_element(&h->trace_tree_blocks_per_cu[0][0][0], &h->trace_tree_blocks_per_cu[0][0][0] + TableCount(h->trace_tree_blocks_per_cu))) * kTraceBlock;   // (the tree's entries are 0 until it is used)
     const uint32_t deep_levels = args_in.scene.stack_depth > kLdsStackLevels ? args_in.scene.stack_depth - kLdsStackLevels : 0u;
     const uint32_t overflow_words = std::max(1u, deep_levels * max_trace_threads);
 

@@ -134,7 +134,7 @@ class ModelScene:
         return len(self.objects) - 1
 
     def lobe_level(self):
-        """UpdateLobeLevel (cgpt_abi.hip)."""
+        """LobeLevel (csrc/device/kernel_variant.h)."""
         if any(o.get("transform") is not None and not TR.is_identity(o["transform"]) for o in self.objects):
             return 4
         if any(o.get("smooth") for o in self.objects):
