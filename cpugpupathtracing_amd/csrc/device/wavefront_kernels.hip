@@ -37,8 +37,10 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstddef>
 #include <cstdlib>
 #include <new>
+#include <type_traits>
 
 #include "cpugpupt_abi.h"
 #include "device_scene.h"
@@ -325,25 +327,42 @@ __global__ void __launch_bounds__(kTraceBlock, 1) wf_trace(const DevRenderArgs a
 // BRUTE: the render has TracePath paths (RENDER_MODE_BRUTE_FORCE / COMPARISON); a separate instantiation, so the TracePathAdvanced
 // renders carry neither its code nor its registers.  LOBES: the lobe level, kernel_variant.h.  RIS: shade_device.hpp, above shade_bounce.
 // A rough bounce reports lobe choice 0, so its ray is never elected or followed as a specular chain.
+// Registers.  The kernel's arguments are two structs of ~100 dwords together, nearly all of them read once per pass: as by-value arguments
+// they are loaded at the kernel's entry, and what does not fit beside the probe's scalar records is parked in VGPR lanes and fetched back
+// with a vector instruction at every use -- in a kernel whose limit is vector issue.  So wf_shade names its arguments only
+// for the launch: each part of a pass reads the fields it needs from the kernel-argument segment itself, through shade_kernargs() -- a
+// scalar load where the field is used, with no register held across the probes.  The view's address passes through an empty asm
+// statement, as the slot addresses of wf_trace's finish_ray do: to the optimiser every call is a new pointer, so nothing read through
+// one is hoisted out of the pass loop or kept for the next part.
+// ShadeKernArgs IS wf_shade's parameter list, field for field, as the argument segment lays it out: change both together (the
+// static_assert behind the kernel holds the signature to these three types in this order).  The view is returned as a generic reference
+// because shade_bounce, probe_scene and the other shared helpers take generic ones; after inlining the address space is inferred back
+// from the constant-address-space pointer the view starts from, and the reads are scalar loads (scripts/shade_static_counts.sh shows it).
+struct ShadeKernArgs { DevRenderArgs args; WfDev wf; uint32_t batch_first; };
+static_assert(alignof(DevRenderArgs) == 8 && alignof(WfDev) == 8 && sizeof(DevRenderArgs) % 8 == 0, "ShadeKernArgs mirrors the argument segment: every parameter at its natural alignment");
+__device__ __forceinline__ const ShadeKernArgs& shade_kernargs()
+{
+    const CGPT_UNIFORM ShadeKernArgs* p = (const CGPT_UNIFORM ShadeKernArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(const ShadeKernArgs*)p;
+}
+
 template <bool COUNT, bool FIRST, bool BRUTE = false, int LOBES = 0, bool RIS = false>
-__global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, const WfDev wf, uint32_t batch_first)
+__global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs, const WfDev, uint32_t)   // read through shade_kernargs(): "Registers" above
 {
     constexpr bool first_round = FIRST;
     constexpr bool kChains = !COUNT && !BRUTE;                                // specular chains are tracked (and elected when wf.spec_tab is set)
-    const DevScene& sc = args.scene;
-    const uint32_t n_ext = first_round ? wf.n_paths : wf.plan[0];
+    uint32_t n_ext;
+    { const WfDev& wf = shade_kernargs().wf; n_ext = first_round ? wf.n_paths : wf.plan[0]; }
     const uint32_t n_blocks = (n_ext + 63u) / 64u;
     const uint32_t n_waves = gridDim.x * 4u;
-    const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6);              // = this wave's segment
-    uint32_t* const out_ext = wf.seg_ext + (size_t)wave * wf.seg_cap;
-    uint32_t* const out_sh = wf.seg_sh + (size_t)wave * wf.seg_cap;
+    const uint32_t wave = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // = this wave's segment (wave-uniform: a scalar register)
     uint32_t count_ext = 0, count_sh = 0;                                     // wave-uniform
     // Image bands: a wave walks its chunks in ascending list order and the lists are band-major (round 0: path ids in image order), so
     // the entries it appends are already grouped by the band of their pixel -- contiguous runs inside its segment, with no per-entry key.
     // The wave only notes where each band's run ends; plan + gather then put all segments' runs of band 0 first, then band 1, ...
     // The rays trace works on at any one time (a contiguous piece of the list) then come from ONE strip of the image instead of from all
     // over it, and the part of the tree they walk stays in the 4 MB L2 of every XCD.
-    const bool banded = wf.n_bands > 1u;
     uint32_t cur_band = 0, band_start_ext = 0, band_start_sh = 0;             // wave-uniform
     Counters cnt = { 0, 0, 0, 0, 0, 0 };
     // Probe.  More than half of the later rounds' rays of the reference scene are decided by the top of IntersectScene alone: they miss both
@@ -354,7 +373,6 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
     // is still one IntersectScene call of the reference and is counted as one.  Not probed: the counting kernels (they walk as the oracle
     // walks), TracePath lanes, the debug views (they read the last depth), rays of a specular chain (the election and its followers stay
     // as they are) and a ray re-traced after total internal reflection (wf_trace does not walk it at all: its hit is known).
-    const bool probe = !COUNT && wf.probe != 0u;                              // wave-uniform
     uint32_t wave_probed = 0;                                                 // wave-uniform: rays this wave decided
     uint32_t wave_absorbed = 0;                                               // wave-uniform: stuck iterations shade_bounce ran in place
 
@@ -362,17 +380,16 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
     // consecutive blocks (the samples of one pixel and of its neighbours in round 0, and their descendants later) keeps the rays of
     // a 64-ray block of every later round from one neighbourhood of the image rather than from unrelated ones (measured +1.3 % with
     // sample-major ids; flat between 1 and 16 blocks with the pixel-major ones, profiles/r02/experiments.md).
-    const uint32_t chunk = wf.shade_chunk;
-    const uint32_t n_chunks = (n_blocks + chunk - 1u) / chunk;
+    // Wave-uniform loop state: the walk and the block.  The chunk's end and "the list has a block left for this wave" follow from them.
     BlockWalk walk = first_block(wave);
-    uint32_t ci = wave, block = ci * chunk, block_end = min((ci + 1u) * chunk, n_blocks);
-    bool more = ci < n_chunks;                                                // wave-uniform: the list has a block left for this wave
+    uint32_t block = wave * shade_kernargs().wf.shade_chunk;
+    auto more = [&]() { return block < n_blocks; };                           // chunks start at whole multiples of the chunk: past the last one, past the list
     auto advance = [&]() {
-        if (++block >= block_end) {
+        const WfDev& wf = shade_kernargs().wf;
+        const uint32_t chunk = wf.shade_chunk;
+        if (++block >= min((block_of(walk) + 1u) * chunk, n_blocks)) {
             next_block(walk, n_waves, wf.rot_shade);
-            ci = block_of(walk);
-            more = ci < n_chunks;
-            block = ci * chunk; block_end = min((ci + 1u) * chunk, n_blocks);
+            block = block_of(walk) * chunk;
         }
     };
     // Later rounds with retire_misses: the wave reads one hit byte per ray of its blocks and queues the path ids of the hits (in list
@@ -381,7 +398,7 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
     __shared__ uint32_t s_queue[4][128];
     uint32_t* const queue = s_queue[threadIdx.x >> 6];
     uint32_t queued = 0;                                                      // wave-uniform
-    const bool hits_only = !first_round && wf.retire_misses != 0u;
+    const bool hits_only = !first_round && shade_kernargs().wf.retire_misses != 0u;
 
     for (;;) {
         bool active = false;
@@ -390,13 +407,14 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
         uint32_t pid = 0;
         uint32_t absorbed = 0;                                                // at most the depth limit: eight bits
         if (!hits_only) {
-            if (!more) break;
+            if (!more()) break;
             const uint32_t i = block * 64u + lane_id();
             active = i < n_ext;
-            if (active) pid = first_round ? i : ld_stream(&wf.list_ext[i]);
+            if (active) pid = first_round ? i : ld_stream(&shade_kernargs().wf.list_ext[i]);
             advance();
         } else {
-            while (queued < 64u && more) {
+            while (queued < 64u && more()) {
+                const WfDev& wf = shade_kernargs().wf;
                 const uint32_t i = block * 64u + lane_id();
                 uint32_t p = 0; bool hit = false;
                 if (i < n_ext) { p = ld_stream(&wf.list_ext[i]); hit = wf.hit_flag[p] != 0; }
@@ -416,23 +434,45 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
             __builtin_amdgcn_wave_barrier();
             queued = rest;
         }
+        float4 c;                                                             // hit record written by trace
+        bool brute_path = false;                                              // this path runs TracePath
+        uint32_t sample = 0, px = 0, py = 0;                                  // round 0: the path's sample of the batch and its pixel
+        if (first_round && active) {
+            // Round 0 begins with the hit record of the path's pixel (one record for all its samples, cached: with pixel-major ids a wave's
+            // lanes share a few records).  A pixel whose primary ray left the scene ends all its paths here with the zero energy record that
+            // the pass below would write: shade_bounce returns on a miss before it reads the ray or draws a number, so such a lane needs no
+            // camera ray and no RNG seed, emits nothing and elects nothing -- with pixel-major ids whole waves are such lanes.  Not taken by
+            // the BVH-depth view (it colours the misses too) and by TracePath lanes; a padded index still writes nothing.
+            const ShadeKernArgs& ka = shade_kernargs();
+            const DevRenderArgs& args = ka.args;
+            uint32_t pixel, local_row;
+            path_split(ka.wf.g, pid, sample, pixel);
+            active = pixel_of_index(args, ka.wf.g, pixel, px, py, local_row);
+            if (active) {
+                c = ka.wf.px_hit[pixel];
+                if (BRUTE) brute_path = args.settings.render_mode == 1u || (args.settings.render_mode == 0u && px < args.width / 2u);   // ref: Main.cpp:719-729
+                if (__float_as_uint(c.x) == kNoHit && args.settings.debug_mode != 2u && !(BRUTE && brute_path)) {
+                    float4 en; en.x = 0.0f; en.y = 0.0f; en.z = 0.0f; en.w = __uint_as_float(0u);   // {no energy, depth 0}
+                    st_stream(&ka.wf.st_en[pid], en);
+                    active = false;
+                }
+            }
+        }
         if (active) {
-            float4 c;                                                         // hit record written by trace
             Ray ray, shadow;
             PathState ps;
-            bool is_pixel = true;
-            bool brute_path = false;                                          // this path runs TracePath
+            constexpr bool is_pixel = true;                                   // (round 0's padded indices have left above; later rounds list none)
             uint32_t chain = 0;                                               // kChains: the specular-chain code of the path's ray
             bool followed = false;                                            // c is the leader's: this path's own C slot is stale
-            if (first_round) {                                                // primary ray and fresh path state from the path id
-                uint32_t px = 0, pixel = 0;
-                is_pixel = primary_ray(args, wf.g, pid, batch_first, ray, ps.rng, px, pixel);
-                c = wf.px_hit[pixel];                                         // the pixel's hit, one record for all its samples (cached:
-                                                                              // with pixel-major ids a wave's lanes share a few records)
+            if (first_round) {                                                // primary ray and fresh path state (ref: Main.cpp:713-716, Camera::GetRay :133-140)
+                const ShadeKernArgs& ka = shade_kernargs();
+                const DevRenderArgs& args = ka.args;
+                ps.rng = pcg_seed(py * args.width + px, ka.batch_first + sample, args.seed);
+                ray = camera_ray(args.camera, (float)px * (1.0f / (float)args.width), (float)py * (1.0f / (float)args.height));
                 ps.throughput = mk(1.0f); ps.energy = mk(0.0f); ps.depth = 0; ps.is_specular = false;
                 chain = 1u;
-                if (BRUTE) brute_path = args.settings.render_mode == 1u || (args.settings.render_mode == 0u && px < args.width / 2u);   // ref: Main.cpp:719-729
             } else {
+                const WfDev& wf = shade_kernargs().wf;
                 const float4 a = ld_stream(&wf.A[pid]), b = ld_stream(&wf.B[pid]);
                 ray.o = mk(a.x, a.y, a.z); ray.d = mk(b.x, b.y, b.z);
                 const float4 tp = ld_stream(&wf.st_tp[pid]);
@@ -457,6 +497,10 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
             if (BRUTE && brute_path) {
                 // one TracePath level (shade_device.hpp: brute_level), the chain in this path's column of wf.brute
                 if (is_pixel) {
+                    const ShadeKernArgs& ka = shade_kernargs();
+                    const DevScene& sc = ka.args.scene;
+                    const DevRenderArgs& args = ka.args;
+                    const WfDev& wf = ka.wf;
                     const bool done = brute_level<COUNT, LOBES>(sc, args.settings, ray, ps.rng, ps.depth,
                         [&](uint32_t k, const BruteLevel& lv) {
                             float4* rec = wf.brute + ((size_t)k * wf.cap + pid) * 2u;
@@ -468,7 +512,10 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
                         ps.energy, cnt);
                     flags = done ? kBounceTerminate | kBounceBruteDone : 0u;
                 }
-            } else if (is_pixel) flags = shade_bounce<COUNT, LOBES, RIS>(sc, args.settings, ray, ps, shadow, pending, cnt);
+            } else if (is_pixel) {
+                const DevRenderArgs& args = shade_kernargs().args;
+                flags = shade_bounce<COUNT, LOBES, RIS>(args.scene, args.settings, ray, ps, shadow, pending, cnt);
+            }
             if (!COUNT) { absorbed = cnt.unwalked; cnt.unwalked = 0; }       // shade_bounce's stuck iterations, each an IntersectScene call of the reference
             emit_ext = (flags & kBounceTerminate) == 0u;
             emit_sh = (flags & kBounceShadow) != 0u;
@@ -477,23 +524,24 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
                 chain = choice != 0u && chain != 0u && chain <= (kChainMax - 2u) / 3u ? chain * 3u + choice - 1u : 0u;
             }
             bool connect = false;                                             // the shadow ray is decided and reaches its light
-            if (probe && !(BRUTE && brute_path)) {
-                if (emit_sh) {
-                    float t = shadow.t;
-                    const uint32_t seen = probe_scene(sc, shadow.o, shadow.d, t);
+            if (!COUNT && shade_kernargs().wf.probe != 0u && !(BRUTE && brute_path)) {
+                if (emit_sh) {                                                // (each probe reads the scene through a view of its own: what the shadow probe
+                    float t = shadow.t;                                       // holds in scalar registers is dead before the extend probe starts)
+                    const uint32_t seen = probe_scene(shade_kernargs().args.scene, shadow.o, shadow.d, t);
                     decided_sh = seen != kProbeUndecided;
                     connect = seen == kProbeMiss;
                 }
                 if (emit_ext && !(kChains && chain != 0u) && ray.t == 1e34f) {
                     float t = ray.t;
-                    decided_ext = probe_scene(sc, ray.o, ray.d, t) == kProbeMiss;
+                    decided_ext = probe_scene(shade_kernargs().args.scene, ray.o, ray.d, t) == kProbeMiss;
                 }
                 emit_sh = emit_sh && !decided_sh;
                 emit_ext = emit_ext && !decided_ext;
             }
 
             // radiance added by this bounce (emissive hit / BVH-depth view): energy_old + x, the reference's single addition
-            const bool final_depth_needed = args.settings.debug_mode == 1u && !emit_ext;      // ray-depth view reads the last depth
+            const WfDev& wf = shade_kernargs().wf;                            // the stores: slot and state addresses formed here, not before the probes
+            const bool final_depth_needed = shade_kernargs().args.settings.debug_mode == 1u && !emit_ext;      // ray-depth view reads the last depth
             const bool own_energy = is_pixel && (first_round || (flags & (kBounceEnergy | kBounceBruteDone)) || final_depth_needed);
             if (own_energy || connect) {
                 float4 en;
@@ -540,10 +588,11 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
         }
         // active-lane compaction into the wave's own segments: __ballot + mbcnt, no atomics
         const unsigned long long m_ext = __builtin_amdgcn_ballot_w64(emit_ext), m_sh = __builtin_amdgcn_ballot_w64(emit_sh);
-        if (probe) wave_probed += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(decided_sh)) + (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(decided_ext));
+        if (!COUNT) wave_probed += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(decided_sh)) + (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(decided_ext));
         if (!COUNT && __builtin_amdgcn_ballot_w64(absorbed != 0u) != 0ull)    // summed over the wave bit by bit: no per-lane total rides through the loop
             for (uint32_t b = 0; b < 8u; ++b) wave_absorbed += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64((absorbed >> b) & 1u)) << b;
-        if (banded) {                                                         // close the runs of the bands this pass has left behind
+        const WfDev& wf = shade_kernargs().wf;                                // the appends: segment addresses and band table, formed here
+        if (wf.n_bands > 1u) {                                                // close the runs of the bands this pass has left behind
             const uint32_t band = min(wf.n_bands - 1u, __umulhi(pid, wf.band_magic));
             const bool emits = emit_ext | emit_sh;
             while (__builtin_amdgcn_ballot_w64(emits && band > cur_band) != 0ull) {
@@ -557,12 +606,15 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
                 ++cur_band;
             }
         }
-        if (emit_ext) st_stream(&out_ext[count_ext + rank_in_mask(m_ext)], pid);
-        if (emit_sh) st_stream(&out_sh[count_sh + rank_in_mask(m_sh)], pid);
+        if (emit_ext) st_stream(&wf.seg_ext[(size_t)wave * wf.seg_cap + count_ext + rank_in_mask(m_ext)], pid);
+        if (emit_sh) st_stream(&wf.seg_sh[(size_t)wave * wf.seg_cap + count_sh + rank_in_mask(m_sh)], pid);
         count_ext += (uint32_t)__popcll(m_ext);
         count_sh += (uint32_t)__popcll(m_sh);
     }
-    if (banded) {                                                             // the last band this wave reached takes the rest; later bands are empty
+    const ShadeKernArgs& ka = shade_kernargs();
+    const WfDev& wf = ka.wf;
+    const DevRenderArgs& args = ka.args;
+    if (wf.n_bands > 1u) {                                                    // the last band this wave reached takes the rest; later bands are empty
         if (lane_id() == 0u)
             for (uint32_t b = cur_band; b < wf.n_bands; ++b) {
                 wf.seg_count[b * wf.n_segs + wave] = b == cur_band ? count_ext - band_start_ext : 0u;
@@ -581,6 +633,11 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs args, con
         atomicAdd(&args.counters->retrace_unwalked, (unsigned long long)wave_absorbed);
     }
 }
+
+static_assert(std::is_same<decltype(&wf_shade<false, false>), void (*)(DevRenderArgs, WfDev, uint32_t)>::value &&
+              offsetof(ShadeKernArgs, args) == 0 && offsetof(ShadeKernArgs, wf) == sizeof(DevRenderArgs) &&
+              offsetof(ShadeKernArgs, batch_first) == sizeof(DevRenderArgs) + sizeof(WfDev),
+              "wf_shade reads its arguments through ShadeKernArgs: the struct and the parameter list change together");
 
 // ---- plan: exclusive scan of the segment counts -------------------------------------------------------------------------------
 // One 256-thread block per (kind, band): the exclusive prefix of that band's n_segs counts (a few thousand) goes to seg_prefix, the
@@ -701,6 +758,10 @@ struct WfTuning {               // defaults measured on MI355X (profiles/r01); o
     uint32_t obj_shift = 0;           // lanes at an object boundary count 2^shift times in the vote
     uint32_t top_records = kLdsTopMax;   // records of the top of the tree mirrored in LDS
     uint32_t max_trace_blocks = 64;   // cap on trace blocks per CU (occupancy experiments)
+    uint32_t max_shade_blocks = 5;    // cap on shade blocks per CU.  Without spilled scalars the production shade kernels take 70 VGPRs and seven blocks would
+                                      // fit; five stay: beside five trace waves a SIMD holds two shade waves either way, a larger grid is more segments to plan
+                                      // and gather, and 6 / 7 measured 50.2 against 50.8 ms on the default frame but 58.7 against 57.8 ms in COMPARISON and
+                                      // 4.16 against 4.06 ms at 8 samples (profiles/r20/ab_shade_diet.txt)
     uint32_t shade_chunk = 4;         // consecutive blocks per shade work item
     uint32_t shade_chunk_banded = 32; // the same when the lists are ordered by image band: a longer piece of one band per work item (C3 86.8-87.3 -> 85.8-86.0 ms,
                                       // C4 rank share 33.7-34.4 -> 33.4-33.6 ms; 8: 86.4-87.0, 16: 86.4-86.9, 64: 86.1, 128: 86.8-87.3, 256: 91.8-92.0).  Plain lists
@@ -863,6 +924,7 @@ static const Knob<WfTuning> kKnobs[] = {
     { "leaf_repeat", &WfTuning::leaf_repeat, 1, 65 },      { "inner_repeat", &WfTuning::inner_repeat, 1, 65 },
     { "obj_repeat", &WfTuning::obj_repeat, 1, 65 },        { "obj_shift", &WfTuning::obj_shift, 0, 6 },
     { "top_records", &WfTuning::top_records, 0, 4096 },     { "trace_blocks", &WfTuning::max_trace_blocks, 1, 64 },
+    { "shade_blocks", &WfTuning::max_shade_blocks, 1, 64 },
     { "shade_chunk", &WfTuning::shade_chunk, 1, 256 },     { "shade_chunk_banded", &WfTuning::shade_chunk_banded, 1, 256 },
     { "shadow_any_hit", &WfTuning::shadow_any_hit, 0, 1 },     { "trace_events", &WfTuning::trace_events, 0, 1 },
     { "path_order", &WfTuning::path_order, 0, 2 },         { "retire_misses", &WfTuning::retire_misses, 0, 1 },
@@ -946,7 +1008,9 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
     const dim3 trace_grid_later(n_cus * std::min(h->tune.max_trace_blocks, trace_blocks[xform][count][0]));
     const bool brute = args_in.settings.render_mode != 2u;                    // the render has TracePath paths (ref: Main.cpp:719-729)
     const uint32_t brute_levels = brute ? (uint32_t)args_in.settings.max_ray_depth + 1u : 0u;
-    const uint32_t (&shade_blocks)[2][2] = h->shade_blocks_per_cu[v.ris][v.lobe_level];   // every lobe level's shade kernels, with and without RIS, have grids of their own
+    uint32_t shade_blocks[2][2];                                              // every lobe level's shade kernels, with and without RIS, have grids of their own
+    for (int c = 0; c < 2; ++c)
+        for (int b = 0; b < 2; ++b) shade_blocks[c][b] = std::min(h->tune.max_shade_blocks, h->shade_blocks_per_cu[v.ris][v.lobe_level][c][b]);
     const dim3 shade_grid(n_cus * shade_blocks[count][brute]);
     // one output segment per shade wave, sized for the most 64-item blocks a wave can be handed
     const uint32_t n_segs = n_cus * std::max({ shade_blocks[0][0], shade_blocks[1][0], shade_blocks[0][1], shade_blocks[1][1] }) * 4u;
