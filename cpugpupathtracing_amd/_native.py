@@ -21,6 +21,7 @@ CTX_FORCE_COLLECTIVE, CTX_GATHER_PEER_COPY = 1, 2
 BUILD_NAIVE, BUILD_SAH_INTERVALS, BUILD_SAH_PRIMITIVES = 0, 1, 2
 BUILD_SAH_BINNED = 3        # not in the reference: 16 bins per axis, stable partition (include/cpugpupt_abi.h)
 DENOISE_DEMODULATE_ALBEDO = 1
+TRACE_COUNTERS, TRACE_REVERSED = 1, 2
 TEMPORAL_KEEP_VIEW_DEPENDENT = 1
 
 f3 = C.c_float * 3
@@ -170,6 +171,8 @@ PROTOTYPES = {
     "cgpt_get_retrace_unwalked": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "cgpt_intersect_rays": (C.c_int, [_vp, _fp, _fp, _fp, C.c_uint32, _fp, _up, _up, _up]),
     "cgpt_shade_samples": (C.c_int, [_vp, C.POINTER(Settings), C.POINTER(ShadeSample), C.c_uint32, C.POINTER(ShadeResult)]),
+    "cgpt_trace_rays": (C.c_int, [_vp, _fp, _fp, _fp, C.c_uint32, _fp, _fp, _fp, C.c_uint32, C.c_uint32, _fp, _up, _up, _up, C.POINTER(C.c_uint8)]),
+    "cgpt_trace_first_hits": (C.c_int, [_vp, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _up, _up, _up, _fp]),
     "cgpt_bvh_build": (C.c_int, [_vp, C.POINTER(Triangle), C.c_uint32, C.POINTER(BvhNode), _up, _up, _up, _fp]),
     "cgpt_bvh_build_ex": (C.c_int, [_vp, C.POINTER(Triangle), C.c_uint32, C.c_uint32, _up, C.POINTER(BvhNode), _up, _up, _up, _fp]),
     "cgpt_synchronize": (C.c_int, [_vp]),

@@ -39,10 +39,13 @@
 #include <cstdint>
 #include <cstddef>
 #include <cstdlib>
+#include <cstring>
 #include <new>
 #include <type_traits>
+#include <vector>
 
 #include "cpugpupt_abi.h"
+#include "ctx_internal.h"
 #include "device_scene.h"
 #include "fast_div.h"
 #include "rt_device.hpp"
@@ -961,23 +964,24 @@ int WavefrontSetTuning(cgpt_ctx* ctx, const char* name, uint32_t value)
     return h ? SetKnob(ctx, FindKnob(kKnobs, name), h->tune, name, value) : CGPT_ERR_HIP;
 }
 
-int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
-{
-    hipStream_t stream = CtxStream(ctx);
-    WfHost* h = WfGetHost(ctx);
-    if (!h) return -1;
-    const bool count = v.count;
-    const uint32_t rows = args_in.n_rows;
-    const uint32_t tiles_x = (args_in.width + 7u) / 8u, tiles_y = (rows + 7u) / 8u;
-    const uint64_t n_pixels64 = (uint64_t)tiles_x * tiles_y * 64u;             // padded to whole 8x8 tiles
-    const uint32_t pool_paths = h->tune.pool_paths_mi << 20;
-    if (n_pixels64 > pool_paths) { CtxFail(ctx, CGPT_ERR_UNSUPPORTED, "band of %llu pixels exceeds the wavefront pool", (unsigned long long)n_pixels64); return -1; }
-    const uint32_t n_pixels = (uint32_t)n_pixels64;
-    const uint32_t rounds = (uint32_t)args_in.settings.max_ray_depth + 2u;    // extend rounds 0..max_depth, + the trailing shadow rays
+// ---- what a trace launch is made of: shared by the renders (LaunchWavefront) and the trace probe (cgpt_trace_rays, cgpt_trace_first_hits) ----
+// The kernel table, the two persistent grids (round 0 and the later rounds: the resident capacity of the chip for each kernel, capped by the
+// trace_blocks knob), the dynamic LDS, the TraceTune of the context's knobs and the words of stack_overflow.
+struct TraceLaunch {
+    const decltype(&wf_trace<false, false>) (*kernels)[2][2];   // [XFORM][COUNT][FIRST]: kTraceKernels, or kTraceTreeKernels with the tree
+    dim3 grid_first, grid_later;
+    size_t lds = 0;
+    TraceTune tune{};
+    uint32_t overflow_words = 0;       // deep end of the traversal stacks: one dword per level beyond the LDS part and per thread of the largest trace grid
+};
 
+// Fills `tl` for the scene `sc` and the chosen instantiations; queries (once per LDS size, cached in h) the occupancy of every trace kernel --
+// and of the shade kernels, whose cache shares the key.  0, or -1 with the context's error set.
+static int PrepareTraceLaunch(cgpt_ctx* ctx, WfHost* h, const DevScene& sc, bool xform, bool count, bool tree, TraceLaunch& tl)
+{
     LAUNCH_TRY(QueryCuCount(h->n_cus));
     const uint32_t n_cus = h->n_cus;
-    const uint32_t top_records = std::min(h->tune.top_records, args_in.scene.n_top_records);
+    const uint32_t top_records = std::min(h->tune.top_records, sc.n_top_records);
     const size_t trace_lds = trace_lds_bytes(top_records);
     // persistent grids = the resident capacity of the chip for each kernel
     if (h->occupancy_lds != trace_lds) {
@@ -993,19 +997,57 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
                     for (int b = 0; b < 2; ++b) h->shade_blocks_per_cu[r][g][c][b] = std::min(shade[r][g][c][0][b], shade[r][g][c][1][b]);
         h->occupancy_lds = trace_lds;
     }
-    const dim3 block(256);
-    const bool xform = HonoursTransforms((int)v.lobe_level);                  // the scene has a transformed object: the XFORM trace kernels
-    h->last_xform = xform;
-    const bool tree = v.tree;                                                 // cgpt_set_top_level(1): the TREE trace kernels
-    h->last_tree = tree;
     if (tree && h->tree_occupancy_lds != trace_lds) {
         LAUNCH_TRY(QueryOccupancy(&kTraceTreeKernels[0][0][0], &h->trace_tree_blocks_per_cu[0][0][0], TableCount(kTraceTreeKernels), kTraceBlock, trace_lds));
         h->tree_occupancy_lds = trace_lds;
     }
     const uint32_t (&trace_blocks)[2][2][2] = tree ? h->trace_tree_blocks_per_cu : h->trace_blocks_per_cu;
-    const auto& trace_kernels = tree ? kTraceTreeKernels : kTraceKernels;
-    const dim3 trace_grid_first(n_cus * std::min(h->tune.max_trace_blocks, trace_blocks[xform][count][1]));
-    const dim3 trace_grid_later(n_cus * std::min(h->tune.max_trace_blocks, trace_blocks[xform][count][0]));
+    tl.kernels = tree ? kTraceTreeKernels : kTraceKernels;
+    tl.grid_first = dim3(n_cus * std::min(h->tune.max_trace_blocks, trace_blocks[xform][count][1]));
+    tl.grid_later = dim3(n_cus * std::min(h->tune.max_trace_blocks, trace_blocks[xform][count][0]));
+    tl.lds = trace_lds;
+    tl.tune = TraceTune{ h->tune.refill_idle, h->tune.inner_repeat, h->tune.leaf_repeat, h->tune.obj_repeat, h->tune.obj_shift, top_records, h->tune.shadow_any_hit, h->tune.lds_tris, 0u, h->tune.first_lean };
+    const uint32_t max_trace_threads = n_cus * std::max(*std::max_element(&h->trace_blocks_per_cu[0][0][0], &h->trace_blocks_per_cu[0][0][0] + TableCount(h->trace_blocks_per_cu)),
+                                                        *std::max_element(&h->trace_tree_blocks_per_cu[0][0][0], &h->trace_tree_blocks_per_cu[0][0][0] + TableCount(h->trace_tree_blocks_per_cu))) * kTraceBlock;   // (the tree's entries are 0 until it is used)
+    const uint32_t deep_levels = sc.stack_depth > kLdsStackLevels ? sc.stack_depth - kLdsStackLevels : 0u;
+    tl.overflow_words = std::max(1u, deep_levels * max_trace_threads);
+    return 0;
+}
+
+// path id <-> pixel of a band of n_pixels padded pixel indices in tiles_x tiles per row, for a batch of n_samples samples
+static PathGrid MakePathGrid(uint32_t n_pixels, uint32_t tiles_x, uint32_t n_samples, uint32_t order)
+{
+    PathGrid g{};
+    g.n_pixels = n_pixels; g.tiles_x = tiles_x; g.div_tiles_x = MakeFastDiv(tiles_x); g.div_n_pixels = MakeFastDiv(n_pixels);
+    g.n_samples = n_samples; g.div_samples = MakeFastDiv(n_samples); g.order = order;
+    return g;
+}
+
+int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
+{
+    hipStream_t stream = CtxStream(ctx);
+    WfHost* h = WfGetHost(ctx);
+    if (!h) return -1;
+    const bool count = v.count;
+    const uint32_t rows = args_in.n_rows;
+    const uint32_t tiles_x = (args_in.width + 7u) / 8u, tiles_y = (rows + 7u) / 8u;
+    const uint64_t n_pixels64 = (uint64_t)tiles_x * tiles_y * 64u;             // padded to whole 8x8 tiles
+    const uint32_t pool_paths = h->tune.pool_paths_mi << 20;
+    if (n_pixels64 > pool_paths) { CtxFail(ctx, CGPT_ERR_UNSUPPORTED, "band of %llu pixels exceeds the wavefront pool", (unsigned long long)n_pixels64); return -1; }
+    const uint32_t n_pixels = (uint32_t)n_pixels64;
+    const uint32_t rounds = (uint32_t)args_in.settings.max_ray_depth + 2u;    // extend rounds 0..max_depth, + the trailing shadow rays
+
+    const bool xform = HonoursTransforms((int)v.lobe_level);                  // the scene has a transformed object: the XFORM trace kernels
+    h->last_xform = xform;
+    const bool tree = v.tree;                                                 // cgpt_set_top_level(1): the TREE trace kernels
+    h->last_tree = tree;
+    TraceLaunch tl;
+    if (PrepareTraceLaunch(ctx, h, args_in.scene, xform, count, tree, tl) != 0) return -1;
+    const uint32_t n_cus = h->n_cus;
+    const dim3 block(256);
+    const auto& trace_kernels = tl.kernels;
+    const size_t trace_lds = tl.lds;
+    const dim3 trace_grid_first = tl.grid_first, trace_grid_later = tl.grid_later;
     const bool brute = args_in.settings.render_mode != 2u;                    // the render has TracePath paths (ref: Main.cpp:719-729)
     const uint32_t brute_levels = brute ? (uint32_t)args_in.settings.max_ray_depth + 1u : 0u;
     uint32_t shade_blocks[2][2];                                              // every lobe level's shade kernels, with and without RIS, have grids of their own
@@ -1016,11 +1058,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
     const uint32_t n_segs = n_cus * std::max({ shade_blocks[0][0], shade_blocks[1][0], shade_blocks[0][1], shade_blocks[1][1] }) * 4u;
     const uint32_t min_shade_waves = n_cus * std::min({ shade_blocks[0][0], shade_blocks[1][0], shade_blocks[0][1], shade_blocks[1][1] }) * 4u;
 
-    // deep end of the traversal stacks: one dword per level beyond the LDS part and per thread of the largest trace grid
-    const uint32_t max_trace_threads = n_cus * std::max(*std::max_element(&h->trace_blocks_per_cu[0][0][0], &h->trace_blocks_per_cu[0][0][0] + TableCount(h->trace_blocks_per_cu)),
-                                                        *std::max_element(&h->trace_tree_blocks_per_cu[0][0][0], &h->trace_tree_blocks_per_cu[0][0][0] + TableCount(h->trace_tree_blocks_per_cu))) * kTraceBlock;   // (the tree's entries are 0 until it is used)
-    const uint32_t deep_levels = args_in.scene.stack_depth > kLdsStackLevels ? args_in.scene.stack_depth - kLdsStackLevels : 0u;
-    const uint32_t overflow_words = std::max(1u, deep_levels * max_trace_threads);
+    const uint32_t overflow_words = tl.overflow_words;
 
     uint32_t shade_chunk = h->tune.shade_chunk;                              // set with the batch size below (banded lists take longer chunks)
     // ---- samples per batch and batches in flight ----
@@ -1087,7 +1125,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
 
     int launches = 0;
     DevRenderArgs args = args_in;
-    const TraceTune tt = { h->tune.refill_idle, h->tune.inner_repeat, h->tune.leaf_repeat, h->tune.obj_repeat, h->tune.obj_shift, top_records, h->tune.shadow_any_hit, h->tune.lds_tris, 0u, h->tune.first_lean };
+    const TraceTune tt = tl.tune;
     uint32_t k = 0;
     for (uint32_t done = 0; done < args_in.n_samples; done += batch, ++k) {
         const uint32_t p = k % n_pools;
@@ -1095,13 +1133,12 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
         const uint32_t bn = std::min(batch, args_in.n_samples - done);
         const uint32_t bfirst = args_in.first_sample + done;
         WfDev wf = h->dev[p];
-        wf.cap = h->held.cap; wf.g.n_pixels = n_pixels; wf.n_paths = n_pixels * bn;
+        wf.cap = h->held.cap; wf.n_paths = n_pixels * bn;
         wf.rot_trace[0] = CoprimeRotation(trace_grid_later.x * (kTraceBlock / 64u), tiles_x * tiles_y);
         wf.rot_trace[1] = CoprimeRotation(trace_grid_first.x * (kTraceBlock / 64u), tiles_x * tiles_y);
         wf.rot_shade = CoprimeRotation(shade_grid.x * 4u, std::max(1u, tiles_x * tiles_y / shade_chunk));
         wf.shade_chunk = shade_chunk;
-        wf.g.tiles_x = tiles_x; wf.g.div_tiles_x = MakeFastDiv(tiles_x); wf.g.div_n_pixels = MakeFastDiv(n_pixels);
-        wf.g.n_samples = bn; wf.g.div_samples = MakeFastDiv(bn); wf.g.order = h->tune.path_order; wf.n_segs = h->held.n_segs; wf.seg_cap = h->held.seg_cap;
+        wf.g = MakePathGrid(n_pixels, tiles_x, bn, h->tune.path_order); wf.n_segs = h->held.n_segs; wf.seg_cap = h->held.seg_cap;
         wf.n_bands = h->tune.bands > 1u && wf.n_paths >= h->tune.bands_min_paths ? h->tune.bands : 1u;   // short lists: nothing to order, and every band is a run per segment to plan and copy
         if (wf.n_bands > 1u)
             wf.band_magic = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, (((uint64_t)wf.n_bands << 32) + wf.n_paths - 1u) / wf.n_paths);   // ceil(2^32 * bands / paths)
@@ -1146,4 +1183,194 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
     return launches;
 }
 
+// ---- the trace probe: the pipeline's own trace launches on rays the host supplies (cgpt_trace_rays, cgpt_trace_first_hits) ---------------
+// The trace step's counterpart of cgpt_shade_samples (shade_probe.hip).  No kernel of its own: a private WfDev in allocations of its own
+// (never the render pools of WfHost::dev, so a context's held pools and its next render are untouched), filled as wf_shade and wf_gather
+// leave a pool before a trace launch, then the launch a render makes -- PrepareTraceLaunch's kernel table, grid, LDS bytes, TraceTune and
+// overflow words -- on the context's stream.  Neither kernel_launches nor the timings of cgpt_stats move.
+namespace {
+
+constexpr uint32_t kMaxProbeRays = 1u << 22;       // per kind, and padded pixels of a round-0 band
+constexpr uint32_t kTraceProbeFlags = CGPT_TRACE_COUNTERS | CGPT_TRACE_REVERSED;
+
+float4 F4(float x, float y, float z, float w) { float4 v; v.x = x; v.y = y; v.z = z; v.w = w; return v; }
+float BitsToFloat(uint32_t u) { float f; memcpy(&f, &u, sizeof(f)); return f; }
+uint32_t FloatToBits(float f) { uint32_t u; memcpy(&u, &f, sizeof(u)); return u; }
+
+// what both modes start with: the variant a render of this context would run, the launch, and the kernel arguments that name the scene
+struct ProbeSetup { WfHost* h; ShadeVariant v; bool xform; TraceLaunch tl; DevRenderArgs args; };
+int ProbeBegin(cgpt_ctx* ctx, uint32_t flags, ProbeSetup& s)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    s.h = WfGetHost(ctx);
+    if (!s.h) return CGPT_ERR_HIP;
+    s.args = DevRenderArgs{};
+    s.args.settings.render_mode = CGPT_MODE_ADVANCED;
+    s.v = ChooseVariant(ctx, s.args.settings, (flags & CGPT_TRACE_COUNTERS) ? (uint32_t)CGPT_RENDER_COUNTERS : 0u);
+    s.xform = HonoursTransforms((int)s.v.lobe_level);
+    if (PrepareTraceLaunch(ctx, s.h, ctx->scene, s.xform, s.v.count, s.v.tree, s.tl) != 0) return CGPT_ERR_HIP;
+    s.args.scene = ctx->scene;
+    s.args.counters = ctx->counters.p;
+    return CGPT_OK;
+}
+
+int TraceProbeRays(cgpt_ctx* ctx, const float* ext_o, const float* ext_d, const float* ext_tmax, uint32_t n_ext, const float* sh_o, const float* sh_d,
+                   const float* sh_tmax, uint32_t n_sh, uint32_t flags, float* out_t, uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, uint8_t* out_occluded)
+{
+    ProbeSetup s;
+    int rc = ProbeBegin(ctx, flags, s);
+    if (rc != CGPT_OK) return rc;
+    const bool reversed = (flags & CGPT_TRACE_REVERSED) != 0u;
+    const uint32_t cap = std::max(n_ext, n_sh);
+    auto ext_slot = [&](uint32_t i) { return reversed ? n_ext - 1u - i : i; };           // the slot of extend ray i = entry i of its list
+    auto sh_slot = [&](uint32_t j) { return reversed ? n_sh - 1u - j : j; };             // (+ cap)
+
+    // the slots as wf_shade leaves them (the follower and same-ray bits of B.w are pipeline state: 0) and the lists as wf_gather does
+    std::vector<float4> A(2 * (size_t)cap, F4(0, 0, 0, 0)), B(A), C(A);
+    std::vector<uint32_t> list_ext(cap, 0u), list_sh(cap, 0u);
+    for (uint32_t i = 0; i < n_ext; ++i) {
+        const uint32_t slot = ext_slot(i);
+        const float tm = ext_tmax ? ext_tmax[i] : 1e34f;
+        A[slot] = F4(ext_o[3 * (size_t)i], ext_o[3 * (size_t)i + 1], ext_o[3 * (size_t)i + 2], tm);
+        B[slot] = F4(ext_d[3 * (size_t)i], ext_d[3 * (size_t)i + 1], ext_d[3 * (size_t)i + 2], 0.0f);
+        // "no hit": what a slot that retire_misses leaves unwritten reads as, and the payload a ray with tmax != 1e34f starts from
+        C[slot] = F4(BitsToFloat(kNoHit), 0.0f, 0.0f, tm);
+        list_ext[i] = slot;
+    }
+    for (uint32_t j = 0; j < n_sh; ++j) {
+        const uint32_t slot = sh_slot(j);
+        A[cap + slot] = F4(sh_o[3 * (size_t)j], sh_o[3 * (size_t)j + 1], sh_o[3 * (size_t)j + 2], sh_tmax ? sh_tmax[j] : 1e34f);
+        B[cap + slot] = F4(sh_d[3 * (size_t)j], sh_d[3 * (size_t)j + 1], sh_d[3 * (size_t)j + 2], 0.0f);
+        C[cap + slot] = F4(1.0f, 1.0f, 1.0f, 0.0f);                                      // the pending energy: arrives in st_en iff the ray is not occluded
+        list_sh[j] = slot;
+    }
+    const uint32_t plan[2] = { n_ext, n_sh };
+    std::vector<float4> en(n_sh);                                                        // the host ends of the copies back: declared before the device
+    std::vector<uint8_t> flag(n_ext);                                                    // buffers, so that on any return they outlive the frees, which wait for the device
+
+    DevBuf<float4> dA, dB, dC, d_en;
+    DevBuf<uint8_t> d_flag;
+    DevBuf<uint32_t> d_list_ext, d_list_sh, d_plan, d_overflow;
+    HIP_TRY(ctx, dA.Alloc(2 * (size_t)cap)); HIP_TRY(ctx, dB.Alloc(2 * (size_t)cap)); HIP_TRY(ctx, dC.Alloc(2 * (size_t)cap));
+    HIP_TRY(ctx, d_en.Alloc(cap)); HIP_TRY(ctx, d_flag.Alloc(cap));
+    HIP_TRY(ctx, d_list_ext.Alloc(cap)); HIP_TRY(ctx, d_list_sh.Alloc(cap));
+    HIP_TRY(ctx, d_plan.Alloc(2 + 2 * (size_t)kMaxBands)); HIP_TRY(ctx, d_overflow.Alloc(s.tl.overflow_words));
+    hipStream_t st = ctx->stream;
+    const size_t slot_bytes = 2 * (size_t)cap * sizeof(float4);
+    HIP_TRY(ctx, hipMemcpyAsync(dA.p, A.data(), slot_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(dB.p, B.data(), slot_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(dC.p, C.data(), slot_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemsetAsync(d_en.p, 0, (size_t)cap * sizeof(float4), st));
+    HIP_TRY(ctx, hipMemsetAsync(d_flag.p, 0, cap, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_list_ext.p, list_ext.data(), (size_t)cap * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_list_sh.p, list_sh.data(), (size_t)cap * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemsetAsync(d_plan.p, 0, (2 + 2 * (size_t)kMaxBands) * sizeof(uint32_t), st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_plan.p, plan, sizeof(plan), hipMemcpyHostToDevice, st));
+
+    WfDev wf{};
+    wf.A = dA.p; wf.B = dB.p; wf.C = dC.p; wf.st_en = d_en.p; wf.hit_flag = d_flag.p;
+    wf.list_ext = d_list_ext.p; wf.list_sh = d_list_sh.p; wf.plan = d_plan.p; wf.stack_overflow = d_overflow.p;
+    wf.cap = cap; wf.n_paths = n_ext; wf.n_bands = 1u;
+    wf.g = MakePathGrid(64u, 1u, 1u, s.h->tune.path_order);                              // no frame: never read by a later round's trace
+    wf.retire_misses = s.h->tune.retire_misses;                                          // the knob alone: a render also turns it off for the debug views, which the probe has none of
+    const uint32_t n_blocks = (n_ext + 63u) / 64u + (n_sh + 63u) / 64u;                  // the lists' 64-ray blocks stand in for the band's tiles
+    wf.rot_trace[0] = CoprimeRotation(s.tl.grid_later.x * (kTraceBlock / 64u), n_blocks);
+    hipLaunchKernelGGL(s.tl.kernels[s.xform][s.v.count][0], s.tl.grid_later, dim3(kTraceBlock), s.tl.lds, st, s.args, wf, 0u, s.tl.tune);
+    HIP_TRY(ctx, hipGetLastError());
+
+    if (n_ext) HIP_TRY(ctx, hipMemcpyAsync(C.data(), dC.p, (size_t)n_ext * sizeof(float4), hipMemcpyDeviceToHost, st));
+    if (n_ext) HIP_TRY(ctx, hipMemcpyAsync(flag.data(), d_flag.p, n_ext, hipMemcpyDeviceToHost, st));
+    if (n_sh) HIP_TRY(ctx, hipMemcpyAsync(en.data(), d_en.p, (size_t)n_sh * sizeof(float4), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < n_ext; ++i) {
+        const float4 c = C[ext_slot(i)];
+        out_obj[i] = FloatToBits(c.x); out_tri[i] = FloatToBits(c.y); out_depth[i] = FloatToBits(c.z); out_t[i] = c.w;
+        // wf_shade takes the rays whose byte is 1: the byte and the record must tell the same story
+        if (wf.retire_misses && (flag[ext_slot(i)] != 0) != (out_obj[i] != kNoHit))
+            return CtxFail(ctx, CGPT_ERR_HIP, "extend ray %u: hit_flag %u beside the record of object %u", i, (unsigned)flag[ext_slot(i)], out_obj[i]);
+    }
+    for (uint32_t j = 0; j < n_sh; ++j) {
+        const float4 e = en[sh_slot(j)];
+        out_occluded[j] = (e.x != 0.0f || e.y != 0.0f || e.z != 0.0f) ? (uint8_t)0 : (uint8_t)1;
+    }
+    return CGPT_OK;
+}
+
+int TraceProbeFirstHits(cgpt_ctx* ctx, const cgpt_camera* camera, uint32_t width, uint32_t height, uint32_t row_begin, uint32_t row_end, uint32_t flags,
+                        uint32_t tiles_x, uint32_t n_pixels, uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, float* out_t)
+{
+    ProbeSetup s;
+    int rc = ProbeBegin(ctx, flags, s);
+    if (rc != CGPT_OK) return rc;
+    const uint32_t rows = row_end - row_begin;
+    memcpy(&s.args.camera, camera, sizeof(DevCamera));
+    s.args.width = width; s.args.height = height;
+    s.args.n_rows = rows; s.args.band_first = row_begin; s.args.band_h = rows; s.args.band_stride = 0u;
+    s.args.n_samples = 1u;
+
+    std::vector<float4> hit(n_pixels);                                                   // before the device buffers: see TraceProbeRays
+    DevBuf<float4> d_hit;
+    DevBuf<uint32_t> d_overflow;
+    HIP_TRY(ctx, d_hit.Alloc(n_pixels)); HIP_TRY(ctx, d_overflow.Alloc(s.tl.overflow_words));
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx, hipMemsetAsync(d_hit.p, 0, (size_t)n_pixels * sizeof(float4), st));    // (the padded indices stay unwritten)
+    WfDev wf{};
+    wf.px_hit = d_hit.p; wf.stack_overflow = d_overflow.p;
+    wf.cap = n_pixels; wf.n_paths = n_pixels; wf.n_bands = 1u;
+    wf.g = MakePathGrid(n_pixels, tiles_x, 1u, s.h->tune.path_order);                    // one sample: every pixel ray counts once
+    wf.rot_trace[1] = CoprimeRotation(s.tl.grid_first.x * (kTraceBlock / 64u), n_pixels / 64u);
+    hipLaunchKernelGGL(s.tl.kernels[s.xform][s.v.count][1], s.tl.grid_first, dim3(kTraceBlock), s.tl.lds, st, s.args, wf, 0u, s.tl.tune);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(hit.data(), d_hit.p, (size_t)n_pixels * sizeof(float4), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    // pixel indices run over 8x8 tiles in row-major tile order, row-major inside a tile (trace_steps.hpp: pixel_of_index)
+    for (uint32_t p = 0; p < n_pixels; ++p) {
+        const uint32_t tile = p >> 6, l = p & 63u, ty = tile / tiles_x, tx = tile - ty * tiles_x;
+        const uint32_t px = tx * 8u + (l & 7u), row = ty * 8u + (l >> 3);
+        if (px >= width || row >= rows) continue;
+        const size_t k = (size_t)row * width + px;
+        out_obj[k] = FloatToBits(hit[p].x); out_tri[k] = FloatToBits(hit[p].y); out_depth[k] = FloatToBits(hit[p].z); out_t[k] = hit[p].w;
+    }
+    return CGPT_OK;
+}
+
+}  // namespace
+
 }  // namespace cgpt
+
+using namespace cgpt;
+
+extern "C" int cgpt_trace_rays(cgpt_ctx* ctx, const float* ext_origins, const float* ext_dirs, const float* ext_tmax, uint32_t n_extend,
+                               const float* sh_origins, const float* sh_dirs, const float* sh_tmax, uint32_t n_shadow, uint32_t flags,
+                               float* out_t, uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, uint8_t* out_occluded)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return CtxFail(ctx, CGPT_ERR_UNSUPPORTED, "cgpt_trace_rays: a one-device context only");
+    if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "cgpt_trace_rays before cgpt_scene_upload");
+    if (flags & ~kTraceProbeFlags) return CtxFail(ctx, CGPT_ERR_INVALID, "unknown flag bits 0x%x", flags & ~kTraceProbeFlags);
+    if (n_extend > kMaxProbeRays || n_shadow > kMaxProbeRays) return CtxFail(ctx, CGPT_ERR_INVALID, "%u extend and %u shadow rays: at most %u of each", n_extend, n_shadow, kMaxProbeRays);
+    if (n_extend && (!ext_origins || !ext_dirs || !out_t || !out_obj || !out_tri || !out_depth)) return CtxFail(ctx, CGPT_ERR_INVALID, "null argument of the extend rays");
+    if (n_shadow && (!sh_origins || !sh_dirs || !out_occluded)) return CtxFail(ctx, CGPT_ERR_INVALID, "null argument of the shadow rays");
+    if (n_extend == 0u && n_shadow == 0u) return CGPT_OK;
+    return Guarded(ctx, __func__, [&] {
+        return TraceProbeRays(ctx, ext_origins, ext_dirs, ext_tmax, n_extend, sh_origins, sh_dirs, sh_tmax, n_shadow, flags, out_t, out_obj, out_tri, out_depth, out_occluded);
+    });
+}
+
+extern "C" int cgpt_trace_first_hits(cgpt_ctx* ctx, const cgpt_camera* camera, uint32_t width, uint32_t height, uint32_t row_begin, uint32_t row_end,
+                                     uint32_t flags, uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, float* out_t)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return CtxFail(ctx, CGPT_ERR_UNSUPPORTED, "cgpt_trace_first_hits: a one-device context only");
+    if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "cgpt_trace_first_hits before cgpt_scene_upload");
+    if (flags & ~(uint32_t)CGPT_TRACE_COUNTERS) return CtxFail(ctx, CGPT_ERR_INVALID, "unknown flag bits 0x%x", flags & ~(uint32_t)CGPT_TRACE_COUNTERS);
+    if (!camera || !out_obj || !out_tri || !out_depth || !out_t) return CtxFail(ctx, CGPT_ERR_INVALID, "null argument");
+    if (width == 0 || height == 0 || row_begin >= row_end || row_end > height)
+        return CtxFail(ctx, CGPT_ERR_INVALID, "bad frame/rows: %ux%u rows [%u,%u)", width, height, row_begin, row_end);
+    const uint64_t tiles_x = ((uint64_t)width + 7u) / 8u, tiles_y = ((uint64_t)(row_end - row_begin) + 7u) / 8u;
+    if ((uint64_t)width * height > 0xFFFFFFFFull || tiles_x * tiles_y * 64u > kMaxProbeRays)
+        return CtxFail(ctx, CGPT_ERR_INVALID, "a band of %llu padded pixels: at most %u", (unsigned long long)(tiles_x * tiles_y * 64u), kMaxProbeRays);
+    return Guarded(ctx, __func__, [&] {
+        return TraceProbeFirstHits(ctx, camera, width, height, row_begin, row_end, flags, (uint32_t)tiles_x, (uint32_t)(tiles_x * tiles_y * 64u), out_obj, out_tri, out_depth, out_t);
+    });
+}

@@ -340,6 +340,49 @@ class Renderer:
                                               out.ctypes.data_as(C.POINTER(N.ShadeResult))))
         return out
 
+    def trace_rays(self, origins=None, dirs=None, tmax=None, shadow_origins=None, shadow_dirs=None, shadow_tmax=None,
+                   counters: bool = False, reverse: bool = False):
+        """cgpt_trace_rays: the wavefront pipeline's later-round trace launch on host rays, extend rays (closest hit) and shadow rays
+        (occlusion) in one launch, in the instantiation and with the knobs a render of this context runs.  Returns t, obj_idx, tri_idx,
+        bvh_depth per extend ray (a miss's bvh_depth is 0 while the retire_misses knob is 1) and one uint8 per shadow ray, 1 = occluded.
+        counters: the counting instantiation; reverse: slots and lists laid out back to front (CGPT_TRACE_REVERSED; same results)."""
+        fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+
+        def rays(o, d, tm):
+            if o is None:
+                return None, None, None, 0
+            o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+            d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+            assert o.shape == d.shape
+            tm = None if tm is None else np.ascontiguousarray(tm, np.float32).reshape(o.shape[0])
+            return o, d, tm, o.shape[0]
+
+        def ptr(a):
+            return a.ctypes.data_as(fp) if a is not None and a.size else None
+        eo, ed, et, n = rays(origins, dirs, tmax)
+        so, sd, st, m = rays(shadow_origins, shadow_dirs, shadow_tmax)
+        t = np.empty(n, np.float32); obj = np.empty(n, np.uint32); tri = np.empty(n, np.uint32); dep = np.empty(n, np.uint32)
+        occ = np.empty(m, np.uint8)
+        flags = (N.TRACE_COUNTERS if counters else 0) | (N.TRACE_REVERSED if reverse else 0)
+        self._check(self.L.cgpt_trace_rays(self._ctx, ptr(eo), ptr(ed), ptr(et), n, ptr(so), ptr(sd), ptr(st), m, flags,
+                                           t.ctypes.data_as(fp), obj.ctypes.data_as(up), tri.ctypes.data_as(up), dep.ctypes.data_as(up),
+                                           occ.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return t, obj, tri, dep, occ
+
+    def trace_first_hits(self, width: int, height: int, rows: Optional[Tuple[int, int]] = None, camera: Optional[N.Camera] = None,
+                         counters: bool = False):
+        """cgpt_trace_first_hits: the wavefront pipeline's round-0 trace launch on the primary rays of a band: obj_idx, tri_idx, bvh_depth
+        and t, each (rows, width).  camera: default the uploaded scene's."""
+        r0, r1 = rows if rows is not None else (0, height)
+        cam = camera if camera is not None else self.scene.camera()
+        shape = (max(r1 - r0, 0), width)
+        obj = np.empty(shape, np.uint32); tri = np.empty(shape, np.uint32); dep = np.empty(shape, np.uint32); t = np.empty(shape, np.float32)
+        up = C.POINTER(C.c_uint32)
+        self._check(self.L.cgpt_trace_first_hits(self._ctx, C.byref(cam), width, height, r0, r1, N.TRACE_COUNTERS if counters else 0,
+                                                 obj.ctypes.data_as(up), tri.ctypes.data_as(up), dep.ctypes.data_as(up),
+                                                 t.ctypes.data_as(C.POINTER(C.c_float))))
+        return obj, tri, dep, t
+
     def build_bvh(self, triangles, n_tris: int, build_option: int = N.BUILD_SAH_INTERVALS, initial_tri_indices=None):
         """BVH::Build (or, with initial_tri_indices = the current m_tri_indices, BVH::Rebuild) on the GPU for any BuildOption
         (ref: Source/BVH.cpp:11-59,204-297) and for BUILD_SAH_BINNED (not in the reference: DESIGN.md 5.10; finite positions of magnitude

@@ -356,6 +356,37 @@ typedef struct cgpt_shade_result {
 } cgpt_shade_result;
 int cgpt_shade_samples(cgpt_ctx* ctx, const cgpt_settings* settings, const cgpt_shade_sample* samples, uint32_t n, cgpt_shade_result* results);
 
+/* The trace step of the wavefront pipeline (CGPT_KERNEL_WAVEFRONT) on rays the host supplies: the production traversal on its own, as
+ * cgpt_intersect_rays is the megakernel's.  No kernel of its own runs: each call makes the trace launch a render of this context makes --
+ * the same instantiation (transforms, cgpt_set_top_level, counters), the same persistent grid, LDS layout and cgpt_set_tuning knobs
+ * (refill, inner_repeat, leaf_repeat, obj_repeat, obj_shift, top_records, trace_blocks, shadow_any_hit, lds_tris, retire_misses,
+ * first_lean) -- on ray slots and lists of its own, filled as the pipeline's other kernels leave them.
+ * cgpt_trace_rays is the launch of a later bounce round: n_extend extend rays (closest hit) and n_shadow shadow rays (occlusion) in one
+ * launch.  origins / dirs: 3 floats per ray; tmax: one float per ray or NULL (1e34f).  Per extend ray t, obj (~0u on a miss), tri and
+ * bvh_depth as cgpt_intersect_rays returns them, with two differences.  While the retire_misses knob is 1 (the default; the probe takes the
+ * knob alone, a render also turns it off for the debug views) the kernel stores no record for a ray that misses, and such a ray's
+ * bvh_depth is returned as 0.  And tri means something for a hit on a mesh only: on a ray that met a stand-alone triangle object on its
+ * way, a final hit on anything but a mesh may carry another stale tri than cgpt_intersect_rays's.
+ * Per shadow ray one byte: 1 occluded (something was hit below tmax), 0 not.  flags: CGPT_TRACE_COUNTERS runs the counting instantiation,
+ * as CGPT_RENDER_COUNTERS does for a render (shadow rays then walk to the end); CGPT_TRACE_REVERSED lays the rays out in their slots and
+ * lists back to front (entry i of a list names slot n - 1 - i); the results come back in the caller's order either way.
+ * cgpt_trace_first_hits is the launch of round 0: the primary ray of every pixel of rows [row_begin, row_end) of a width x height frame
+ * seen from `camera`, in the lean per-lane walk or the voted one as the first_lean knob says.  Out, per pixel of the band in row-major
+ * order: obj (~0u on a miss), tri, bvh_depth and t (1e34f on a miss).  flags: CGPT_TRACE_COUNTERS only.
+ * Both add the rays they trace to traced_rays (one per ray and per pixel) and, with CGPT_TRACE_COUNTERS, their steps to inner_steps,
+ * tri_tests and bvh_depth_sum; nothing else changes: the accumulator, data.pixels, num_accumulated, the guides, the temporal history,
+ * the other fields of cgpt_stats and the memory a render holds stay as they are.
+ * Refusals, all before any device work (a refused call changes nothing): no scene CGPT_ERR_NO_SCENE; a NULL argument that a count above 0
+ * needs, unknown flag bits, more than 4194304 rays of a kind or padded pixels (the band in whole 8 x 8 tiles), width or height 0 or rows
+ * outside the frame: CGPT_ERR_INVALID; a multi-device context: CGPT_ERR_UNSUPPORTED.  No ray at all is CGPT_OK and launches nothing.
+ * Every direction must be finite and not zero.  Added exports: CGPT_ABI_VERSION stays 2. */
+enum cgpt_trace_flags { CGPT_TRACE_COUNTERS = 1u, CGPT_TRACE_REVERSED = 2u };
+int cgpt_trace_rays(cgpt_ctx* ctx, const float* ext_origins, const float* ext_dirs, const float* ext_tmax, uint32_t n_extend,
+                    const float* sh_origins, const float* sh_dirs, const float* sh_tmax, uint32_t n_shadow, uint32_t flags,
+                    float* out_t, uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, uint8_t* out_occluded);
+int cgpt_trace_first_hits(cgpt_ctx* ctx, const cgpt_camera* camera, uint32_t width, uint32_t height, uint32_t row_begin, uint32_t row_end,
+                          uint32_t flags, uint32_t* out_obj, uint32_t* out_tri, uint32_t* out_depth, float* out_t);
+
 /* BVH::Build with BVHBuildOption_SAHSplitIntervals on the GPU (ref: Source/BVH.cpp:11-45,204-259,299-366; Main.cpp:789,802 use
  * this option for every mesh).  The result is the reference's tree bit for bit: same 32-byte nodes in the same allocation order,
  * same m_tri_indices permutation, same m_max_depth / m_total_area -- so it can be passed to cgpt_scene_upload (cgpt_object

@@ -8,7 +8,7 @@ import pytest
 
 import oracle as O
 import cpugpupathtracing_amd as P
-from scenes import MAT_SPEC_DIFFUSE, reference_layout_pair, rmse, standin_mesh
+from scenes import MAT_SPEC_DIFFUSE, forty_object_pair, pair_from as _pair_from, quad_stack as _quad_stack, reference_layout_pair, rmse, standin_mesh
 
 pytestmark = pytest.mark.gpu
 
@@ -483,29 +483,6 @@ def test_cpp_example_main_loop(tmp_path):
 
 # ---- edge cases of the scene description -------------------------------------------------------------------------------------
 
-def _pair_from(objects, mats, lights, camera=((0, 0, 8), (0, 0, -1), 60.0, 1.0), settings=None):
-    o = O.OracleScene(); s = P.Scene()
-    for m in mats:
-        o.add_material(m.albedo, m.specular, m.refractivity, m.absorption, m.ior, m.emissive, m.intensity, m.is_light); s.add_material(m)
-    for kind, *a in objects:
-        if kind == "mesh":
-            v, i, mat, opt = a
-            o.add_mesh(v, i, mat, opt); s.add_mesh(P.Mesh.from_arrays(v, i), mat, opt)
-        elif kind == "sphere":
-            c, r, mat = a
-            o.add_sphere(c, r, mat); s.add_sphere(c, r, mat)
-        else:
-            n, p, mat = a
-            o.add_plane(n, p, mat); s.add_plane(n, p, mat)
-    for li in lights:
-        o.add_light(li); s.add_light(li)
-    o.set_camera(*camera); s.set_camera(*camera)
-    st = settings or P.Settings()
-    o.set_settings(st.max_ray_depth, st.next_event_estimation_enabled, st.cosine_weighted_diffuse_reflection_enabled, st.russian_roulette_enabled)
-    s.set_settings(st)
-    return o, s
-
-
 @pytest.mark.parametrize("kernel", [P.KERNEL_MEGAKERNEL, P.KERNEL_WAVEFRONT, P.KERNEL_PERSISTENT])
 def test_scene_edge_cases(renderer, kernel):
     v, i = standin_mesh(2)
@@ -536,20 +513,6 @@ def test_scene_edge_cases(renderer, kernel):
 
 # ---- rarely taken paths of the trace kernel ---------------------------------------------------------------------------------------
 
-def _quad_stack(n_quads, spacing=0.01, half=1.0):
-    """n_quads camera-facing quads behind each other along -z: a ray down the axis crosses every node's bounds, so the ordered
-    traversal pushes a far child at every level and the stack gets as deep as the tree."""
-    z = -(np.arange(n_quads, dtype=np.float32) * np.float32(spacing))
-    corners = np.array([[-half, -half], [half, -half], [half, half], [-half, half]], np.float32)
-    v = np.zeros((n_quads, 4, 6), np.float32)
-    v[:, :, 0:2] = corners[None]
-    v[:, :, 2] = z[:, None]
-    v[:, :, 5] = 1.0
-    base = (np.arange(n_quads, dtype=np.uint32) * 4)[:, None]
-    idx = (base + np.array([0, 1, 2, 2, 3, 0], np.uint32)[None]).reshape(-1)
-    return v.reshape(-1, 6), idx.astype(np.uint32)
-
-
 @pytest.mark.parametrize("kernel", [P.KERNEL_MEGAKERNEL, P.KERNEL_WAVEFRONT, P.KERNEL_PERSISTENT])
 def test_traversal_stack_deeper_than_lds_part(renderer, kernel):
     """2^17 quads (2^18 triangles, tree depth >= 18): stacks outgrow the 16 LDS levels of the wavefront trace kernel and
@@ -571,20 +534,7 @@ def test_traversal_stack_deeper_than_lds_part(renderer, kernel):
 def test_more_objects_than_the_lds_object_table(renderer, kernel):
     """40 objects (small meshes, spheres, a plane, in mixed order): beyond the 31 object records the trace kernel mirrors in
     LDS, so its object step reads them from HBM and mesh-to-mesh transitions are not folded into the steps."""
-    v, i = standin_mesh(1)
-    grey, light, mirror = P.Material(albedo=(0.6, 0.6, 0.6)), P.Material(emissive=(1, 1, 1), intensity=4.0, is_light=True), P.Material(albedo=(0.9, 0.9, 0.9), specular=0.7)
-    objs = []
-    rng = np.random.default_rng(5)
-    for k in range(38):
-        c = (float(rng.uniform(-9, 9)), float(rng.uniform(-2, 6)), float(rng.uniform(-12, 0)))
-        if k % 3 == 0:
-            vv = v.copy(); vv[:, :3] = vv[:, :3] * np.float32(0.15) + np.array(c, np.float32)
-            objs.append(("mesh", vv, i, 2 if k % 2 else 0, O.BUILD_SAH_INTERVALS))
-        else:
-            objs.append(("sphere", c, float(rng.uniform(0.3, 0.9)), 2 if k % 4 == 1 else 0))
-    objs.append(("plane", (0, 1, 0), (0, -3, 0), 0))
-    objs.append(("sphere", (0, 14, 2), 4.0, 1))
-    o, s = _pair_from(objs, [grey, light, mirror], [39])
+    o, s = forty_object_pair()
     a0, a1 = _render_pair(renderer, o, s, 72, 48, 3, kernel=kernel)
     so, sg = o.stats(), renderer.stats()
     assert (so.traced_rays, so.inner_steps, so.tri_tests, so.closest_hits) == (sg.traced_rays, sg.inner_steps, sg.tri_tests, sg.closest_hits)

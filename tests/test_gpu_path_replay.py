@@ -21,6 +21,7 @@ import pytest
 import cpugpupathtracing_amd as P
 from cpugpupathtracing_amd.distributed import interleaved_rows
 import replay_ref as RP
+from replay_ref import assert_render_is as _assert_render_is, expected as _expected, render_view as _render
 import shade_cases as CASES
 import shade_ref as S
 import test_gpu_shade_step as STEP
@@ -28,7 +29,7 @@ import test_gpu_shade_step as STEP
 pytestmark = pytest.mark.gpu
 
 W, H = RP.W, RP.H
-KERNELS = (P.KERNEL_MEGAKERNEL, P.KERNEL_PERSISTENT, P.KERNEL_WAVEFRONT)
+KERNELS = RP.KERNELS
 BAND = (5, 23)                                                                    # neither end on a tile edge
 INTERLEAVE = (4, 3, 1)                                                             # bands of 4 rows, every third, starting at the second
 MAX_UNDECIDED = 0.02
@@ -80,40 +81,6 @@ def _replays(level, m):
         _state["replays"][level, m] = out
         _state["scenes"].setdefault(level, copy.deepcopy(sc))                   # the model's scene at this level, for test B after the context has moved on
     return _state["replays"][level, m]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _render(r, view, cam, st, kernel, counters, rows=None, interleave=None):
-    """(accumulator, pixels, stats) of the view's samples on a band whose earlier samples summed to zero."""
-    n_rows = H if rows is None and interleave is None else (rows[1] - rows[0] if rows else len(interleaved_rows(H, interleave[2], interleave[1], interleave[0])))
-    r.reset_accumulator()
-    if view["first_sample"]:
-        r.load_accumulator(np.zeros((n_rows, W, 4), np.float32), view["first_sample"], W, H, rows=rows, interleave=interleave)
-    r.reset_stats()
-    r.render(W, H, view["n_samples"], seed=RP.SEED, rows=rows, interleave=interleave, kernel=kernel, counters=counters, settings=st, camera=cam)
-    return r.accumulator().copy(), r.pixels().copy(), r.stats()
-
-
-def _expected(rep, view, local_rows):
-    """The replay's accumulator (the w of the earlier samples is not in it: they were loaded as zeros), pixels and counters on some rows."""
-    acc = rep["accumulator"][local_rows].copy()
-    return dict(acc=acc, pixels=RP.pack_pixels(acc, view["first_sample"] + view["n_samples"]), rays=int(rep["path_rays"][local_rows].sum()),
-                unwalked=int(rep["path_unwalked"][local_rows].sum()), energy=float(rep["path_energy_sum"][local_rows].sum()))
-
-
-def _assert_render_is(got, exp, counters, what, columns=slice(None), count=True):
-    acc, pixels, stats = got
-    differ = _bits(acc[:, columns]) != _bits(exp["acc"][:, columns])
-    assert not differ.any(), (what, "accumulator words differ at (row, px, channel)", np.argwhere(differ)[:8].tolist(),
-                              acc[:, columns][differ][:4], exp["acc"][:, columns][differ][:4])
-    assert np.array_equal(pixels[:, columns], exp["pixels"][:, columns]), (what, "packed pixels")
-    if count:
-        assert stats.traced_rays == exp["rays"], (what, "traced_rays", stats.traced_rays, exp["rays"])
-        assert stats.retrace_unwalked == (0 if counters else exp["unwalked"]), (what, "retrace_unwalked", stats.retrace_unwalked, exp["unwalked"])
-        assert abs(stats.total_energy_received - exp["energy"]) <= 1e-12 * abs(exp["energy"]), (what, "total_energy_received", stats.total_energy_received, exp["energy"])
 
 
 # ---- A ------------------------------------------------------------------------------------------------------------------------------------------
