@@ -233,6 +233,8 @@ PROTOTYPES = {
     "cgpth_write_accumulator": (C.c_int, [C.c_char_p, _fp, C.c_uint32, C.c_uint32, C.c_uint32]),
     "cgpth_read_accumulator": (C.c_int, [C.c_char_p, _fp, _up, C.c_uint32, C.c_uint32]),
     "cgpth_fast_div": (C.c_uint32, [C.c_uint32, C.c_uint32]),
+    "cgpth_shade_item_blocks": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "cgpth_shade_segment_blocks": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "cgpth_scene_layout": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(SceneLayoutView)]),
     "cgpth_scene_layout_transformed": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(C.c_float), C.c_uint32, C.POINTER(SceneLayoutView)]),
     "cgpth_scene_permute_objects": (C.c_int, [_vp, _up, C.c_uint32]),

@@ -15,13 +15,29 @@ namespace dev {
 
 static constexpr uint32_t kAccChunk = 8;                 // samples staged per pixel and pass in the pixel-major path
 
+// A pixel whose primary ray left the scene gives every one of its paths the record {0, 0, 0, bits(depth 0)} (shade_bounce returns on
+// a miss before it draws a number, ref: Main.cpp:415-416).  In the wavefront pipeline that record is not stored and not loaded: where this
+// predicate holds, round 0 of wf_shade writes nothing to st_en for the pixel's paths and accumulate_batch<true> feeds add_sample the
+// record itself, once per sample.  Both evaluate it on the same operands -- the launch arguments of the batch and the pixel's
+// px_hit record, which the batch's own round-0 trace wrote before either kernel starts -- so the writer and the reader always agree
+// (DESIGN.md 5.1).  False for the debug views (the ray-depth view reads the stored depth, the BVH-depth view colours the misses) and for
+// TracePath pixels (they run brute_level).
+__device__ __forceinline__ bool pixel_adds_nothing(const DevRenderArgs& args, float4 first_hit, uint32_t px)
+{
+    const DevSettings& st = args.settings;
+    const bool trace_path = st.render_mode == 1u || (st.render_mode == 0u && px < args.width / 2u);   // ref: Main.cpp:719-729
+    return __float_as_uint(first_hit.x) == kNoHit && st.debug_mode == 0u && !trace_path;
+}
+
 // All 256 threads of the block call it (ends in a block-level reduction).  One thread = one pixel, grid-stride over the band.
 // st_en[path id] = {radiance.xyz, bits(final ray depth)}.  With pixel-major path ids a pixel's samples are one contiguous run: read
 // directly, the 64 lanes of a wave would touch 64 different lines per load (measured: 9.3 ms instead of 1.3 per 256-spp frame),
 // so the wave loads 64 pixels x kAccChunk samples in memory order (eight full 128-byte lines per load instruction) into LDS and
 // every lane then reads its own pixel's samples from there, in order.
+// SKIP (the wavefront pipeline): px_hit holds the band's first-hit records and the samples of a pixel that adds nothing are not read.
+template <bool SKIP = false>
 __device__ __forceinline__ void accumulate_batch(const DevRenderArgs& args, const float4* __restrict__ st_en, const PathGrid& g,
-                                                 uint32_t batch_first, uint32_t batch_n)
+                                                 uint32_t batch_first, uint32_t batch_n, const float4* __restrict__ px_hit = nullptr)
 {
     __shared__ float4 stage[4][64 * (kAccChunk + 1u)];                         // per wave: [pixel][sample], one float4 of padding per pixel
     const DevSettings& st = args.settings;
@@ -44,22 +60,26 @@ __device__ __forceinline__ void accumulate_batch(const DevRenderArgs& args, cons
             if (st.debug_mode == 0u) { acc.x += e.x; acc.y += e.y; acc.z += e.z; acc.w += 1.0f; }
             else last = e;
         };
+        bool nothing = false;                                                 // SKIP: this pixel's samples are the zero record, unread
+        if (SKIP && is_pixel) nothing = pixel_adds_nothing(args, px_hit[p], px);
+        const float4 zero_record = float4{ 0.0f, 0.0f, 0.0f, __uint_as_float(0u) };   // {no energy, depth 0}
         if (g.order == kPixelMajor) {
             const uint32_t p_base = p - lane;                                 // the wave's 64 pixels: one 8x8 tile
+            const unsigned long long unread = SKIP ? __builtin_amdgcn_ballot_w64(nothing) : 0ull;   // bit i: pixel p_base + i (the whole wave is in the loop)
             for (uint32_t s0 = 0; s0 < batch_n; s0 += kAccChunk) {
                 const uint32_t cnt = min(kAccChunk, batch_n - s0);
 #pragma unroll
                 for (uint32_t k = 0; k < kAccChunk; ++k) {
                     const uint32_t e = k * 64u + lane, pix = e / kAccChunk, smp = e % kAccChunk;
-                    if (smp < cnt) my_stage[pix * (kAccChunk + 1u) + smp] = st_en[(size_t)(p_base + pix) * g.n_samples + s0 + smp];
+                    if (smp < cnt && !(SKIP && ((unread >> pix) & 1ull))) my_stage[pix * (kAccChunk + 1u) + smp] = st_en[(size_t)(p_base + pix) * g.n_samples + s0 + smp];
                 }
                 __builtin_amdgcn_wave_barrier();
                 if (is_pixel)
-                    for (uint32_t j = 0; j < cnt; ++j) add_sample(my_stage[lane * (kAccChunk + 1u) + j]);
+                    for (uint32_t j = 0; j < cnt; ++j) add_sample(SKIP && nothing ? zero_record : my_stage[lane * (kAccChunk + 1u) + j]);   // (its staged entries are stale)
                 __builtin_amdgcn_wave_barrier();
             }
         } else if (is_pixel) {
-            for (uint32_t s = 0; s < batch_n; ++s) add_sample(ld_stream(&st_en[path_id(g, s, p)]));
+            for (uint32_t s = 0; s < batch_n; ++s) add_sample(SKIP && nothing ? zero_record : ld_stream(&st_en[path_id(g, s, p)]));
         }
         if (is_pixel) {
             if (st.debug_mode == 0u) {

@@ -50,6 +50,7 @@
 #include "fast_div.h"
 #include "rt_device.hpp"
 #include "shade_device.hpp"
+#include "shade_items.h"
 #include "trace_steps.hpp"
 #include "accumulate.hpp"
 #include "launch_common.h"
@@ -84,7 +85,7 @@ struct WfDev {
     uint32_t n_paths;                  // paths of this batch (path ids 0 .. n_paths-1, all valid)
     PathGrid g;                        // path id <-> pixel of the band (trace_steps.hpp)
     uint32_t n_segs, seg_cap;
-    uint32_t shade_chunk;              // consecutive 64-path blocks a shade wave takes at a time
+    uint32_t shade_chunk;              // most consecutive 64-path blocks a shade wave takes at a time (shorter lists: shade_items.h)
     uint32_t retire_misses;            // later rounds: trace leaves one byte per extend ray (hit or not) and shade takes only the hits (off for the debug views)
     uint32_t rot_trace[2], rot_shade;  // rotation of the wave order from one row of blocks to the next ([FIRST] for trace): see next_block()
     unsigned long long* spec_tab;      // specular-chain election (wf_shade): spec_keys entries {bits(epoch << 16 | chain), leader path id << 32} per
@@ -384,14 +385,16 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs, const Wf
     // a 64-ray block of every later round from one neighbourhood of the image rather than from unrelated ones (measured +1.3 % with
     // sample-major ids; flat between 1 and 16 blocks with the pixel-major ones, profiles/r02/experiments.md).
     // Wave-uniform loop state: the walk and the block.  The chunk's end and "the list has a block left for this wave" follow from them.
+    // wf.shade_chunk is the most a work item takes: a list too short to give every wave a whole one is dealt in shorter items, down to four
+    // blocks, so that a late round's few thousand blocks spread over the waves instead of sitting 32 deep in a few dozen (shade_items.h,
+    // with the bound that keeps a wave inside its segment).  What a wave appends is still in ascending list order.
     BlockWalk walk = first_block(wave);
-    uint32_t block = wave * shade_kernargs().wf.shade_chunk;
+    const uint32_t chunk = shade_item_blocks(n_blocks, n_waves, shade_kernargs().wf.shade_chunk);   // wave-uniform
+    uint32_t block = wave * chunk;
     auto more = [&]() { return block < n_blocks; };                           // chunks start at whole multiples of the chunk: past the last one, past the list
     auto advance = [&]() {
-        const WfDev& wf = shade_kernargs().wf;
-        const uint32_t chunk = wf.shade_chunk;
         if (++block >= min((block_of(walk) + 1u) * chunk, n_blocks)) {
-            next_block(walk, n_waves, wf.rot_shade);
+            next_block(walk, n_waves, shade_kernargs().wf.rot_shade);
             block = block_of(walk) * chunk;
         }
     };
@@ -455,8 +458,10 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs, const Wf
                 c = ka.wf.px_hit[pixel];
                 if (BRUTE) brute_path = args.settings.render_mode == 1u || (args.settings.render_mode == 0u && px < args.width / 2u);   // ref: Main.cpp:719-729
                 if (__float_as_uint(c.x) == kNoHit && args.settings.debug_mode != 2u && !(BRUTE && brute_path)) {
-                    float4 en; en.x = 0.0f; en.y = 0.0f; en.z = 0.0f; en.w = __uint_as_float(0u);   // {no energy, depth 0}
-                    st_stream(&ka.wf.st_en[pid], en);
+                    if (!pixel_adds_nothing(args, c, px)) {                   // (the ray-depth view: its record is read)
+                        float4 en; en.x = 0.0f; en.y = 0.0f; en.z = 0.0f; en.w = __uint_as_float(0u);   // {no energy, depth 0}
+                        st_stream(&ka.wf.st_en[pid], en);
+                    }                                                         // else wf_accumulate supplies the record itself and reads nothing: accumulate.hpp
                     active = false;
                 }
             }
@@ -738,7 +743,7 @@ __global__ void __launch_bounds__(256) wf_gather(const WfDev wf)
 // ---- K5 accumulate + pack: samples of the batch in order (ref: Main.cpp:735-746, MathLib.h:144-152) ------------------------
 __global__ void __launch_bounds__(256) wf_accumulate(const DevRenderArgs args, const WfDev wf, uint32_t batch_first, uint32_t batch_n)
 {
-    accumulate_batch(args, wf.st_en, wf.g, batch_first, batch_n);
+    accumulate_batch<true>(args, wf.st_en, wf.g, batch_first, batch_n, wf.px_hit);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
@@ -1095,7 +1100,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
         }
         const bool banded = h->tune.bands > 1u && need.cap >= h->tune.bands_min_paths;   // (the last, shorter batch of a render may still fall below: it keeps this chunk)
         shade_chunk = banded ? h->tune.shade_chunk_banded : h->tune.shade_chunk;
-        need.seg_cap = ((((need.cap + 63u) / 64u + shade_chunk - 1u) / shade_chunk + min_shade_waves - 1u) / min_shade_waves) * shade_chunk * 64u;   // whole chunks per wave
+        need.seg_cap = shade_segment_blocks((need.cap + 63u) / 64u, min_shade_waves, shade_chunk) * 64u;   // whole chunks per wave; shorter items stay inside (shade_items.h)
         if (h->held_pools >= n_pools && h->held.Holds(need)) break;
         LAUNCH_TRY(hipDeviceSynchronize());
         WfRelease(h);

@@ -10,6 +10,7 @@
 #include "image_io.h"
 #include "mesh_gen.h"
 #include "scene.h"
+#include "shade_items.h"
 #include "transform_math.h"
 
 using namespace cgpt;
@@ -543,5 +544,8 @@ int cgpth_read_accumulator(const char* path, float* acc, uint32_t* n, uint32_t w
 }
 
 uint32_t cgpth_fast_div(uint32_t n, uint32_t d) { return d == 0u ? 0u : fast_div(n, MakeFastDiv(d)); }
+
+uint32_t cgpth_shade_item_blocks(uint32_t n_blocks, uint32_t n_waves, uint32_t chunk) { return n_waves == 0u || chunk == 0u ? 0u : shade_item_blocks(n_blocks, n_waves, chunk); }
+uint32_t cgpth_shade_segment_blocks(uint32_t cap_blocks, uint32_t min_waves, uint32_t chunk) { return min_waves == 0u || chunk == 0u ? 0u : shade_segment_blocks(cap_blocks, min_waves, chunk); }
 
 }  // extern "C"

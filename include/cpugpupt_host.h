@@ -120,6 +120,14 @@ int cgpth_read_accumulator(const char* path, float* accumulator_rgba, uint32_t* 
  * the host: equals n / d for every 32-bit n and every d >= 1 (tests/test_host.py checks it against integer division) */
 uint32_t cgpth_fast_div(uint32_t n, uint32_t d);
 
+/* the work-item rule of the wavefront pipeline's shade kernel (csrc/device/shade_items.h), evaluated on the host.  cgpth_shade_item_blocks:
+ * the consecutive 64-path blocks a shade wave takes at a time from a list of n_blocks blocks walked by n_waves waves, at most `chunk`.
+ * cgpth_shade_segment_blocks: the blocks the launcher sizes a wave's output segment for, from the pool's capacity in blocks, the
+ * smallest shade grid in waves and the configured chunk.  tests/test_host_shade_items.py checks that no wave is ever dealt more.
+ * 0 for n_waves, min_waves or chunk == 0. */
+uint32_t cgpth_shade_item_blocks(uint32_t n_blocks, uint32_t n_waves, uint32_t chunk);
+uint32_t cgpth_shade_segment_blocks(uint32_t cap_blocks, uint32_t min_waves, uint32_t chunk);
+
 /* the device layout a cgpt_scene_upload of `scene` would install (csrc/device/device_scene.h), computed on the host with the same
  * validation, status and message (from cgpth_last_error()) as the upload; no GPU is touched.  tests/test_host_scene_layout.py checks
  * it against the layout's documentation.  The arrays live in thread-local storage of the library and stay valid until the next
