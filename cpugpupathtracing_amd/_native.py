@@ -23,6 +23,7 @@ BUILD_SAH_BINNED = 3        # not in the reference: 16 bins per axis, stable par
 DENOISE_DEMODULATE_ALBEDO = 1
 TRACE_COUNTERS, TRACE_REVERSED = 1, 2
 TEMPORAL_KEEP_VIEW_DEPENDENT = 1
+VARIANCE_TEMPORAL = 1
 
 f3 = C.c_float * 3
 
@@ -95,6 +96,10 @@ class DenoiseParams(C.Structure):
 
 class TemporalParams(C.Structure):
     _fields_ = [("max_history", C.c_float), ("normal_cos_min", C.c_float), ("plane_tolerance", C.c_float), ("flags", C.c_uint32)]
+
+
+class VarianceParams(C.Structure):
+    _fields_ = [("sigma_luminance", C.c_float), ("min_history_frames", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class ShadeSample(C.Structure):
@@ -184,6 +189,9 @@ PROTOTYPES = {
                                         C.c_size_t]),
     "cgpt_temporal_reset": (C.c_int, [_vp]),
     "cgpt_read_temporal_history": (C.c_int, [_vp, _fp, C.c_size_t]),
+    "cgpt_denoise_variance_guided": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(DenoiseParams), C.POINTER(TemporalParams),
+                                               C.POINTER(VarianceParams), _fp, C.c_size_t, _up, C.c_size_t]),
+    "cgpt_read_variance": (C.c_int, [_vp, _fp, C.c_size_t]),
     "cgpt_measure_issue_rate": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     # cpugpupt_host.h
     "cgpth_last_error": (C.c_char_p, []),

@@ -36,6 +36,8 @@ struct DenoiseBuffers {                           // denoise.hip; each group is 
     DevBuf<uint32_t> filter_pixels;
     DevBuf<float4> history[2];                    // cgpt_denoise_temporal: per pixel {merged colour, history length H}, ping-pong
     DevBuf<float4> history_guides[2];             // 2 float4 per pixel {x.xyz, t | n.xyz, bits(obj)} of the frame each history belongs to
+    DevBuf<float> variance;                       // cgpt_denoise_variance_guided: per pixel, the variance pass 0 read (cgpt_read_variance)
+    DevBuf<float4> moments[2];                    // ... per pixel {mu, v, K, 0} of the luminance, beside history[] (the same slot)
 };
 template <class... B> void ResetAll(B&... b) { (b.Reset(), ...); }
 // What the uploaded scene has that a kernel variant must carry: a roughness > 0, a transmission roughness > 0, a smooth-normal flag (they live in
@@ -121,6 +123,11 @@ struct cgpt_ctx {
     uint64_t temporal_generation = 0;
     cgpt_camera temporal_camera{};
     uint32_t temporal_frame[4] = { 0, 0, 0, 0 };  // as guide_frame
+    // the variance-guided filter (cgpt_denoise_variance_guided): dn.moments[temporal_slot] belongs to the temporal history when
+    // moments_valid (a cgpt_denoise_temporal call updates the colour without them); dn.variance is the last successful call's map
+    bool moments_valid = false;
+    bool variance_valid = false;
+    uint32_t variance_frame[4] = { 0, 0, 0, 0 };  // as guide_frame
 };
 
 

@@ -1,5 +1,6 @@
 // denoise.hip -- an edge-avoiding a-trous filter guided by first-hit buffers (gfx950): cgpt_read_guides, cgpt_denoise,
-// and the temporal reprojection in front of it: cgpt_denoise_temporal, cgpt_temporal_reset, cgpt_read_temporal_history.
+// the temporal reprojection in front of it: cgpt_denoise_temporal, cgpt_temporal_reset, cgpt_read_temporal_history,
+// and its variance-guided form: cgpt_denoise_variance_guided, cgpt_read_variance.
 //
 // Guides: the reference does not jitter primary rays (SURVEY A-14), so every sample of a pixel has the same first hit, and one primary
 // trace per camera gives each pixel's position, normal and albedo.  guides_kernel computes that hit with the render paths' own device
@@ -17,6 +18,12 @@
 // passes, temporal_merge reprojects the history of the earlier frames -- merged colour and history length H per pixel, with that frame's
 // guides and camera -- onto the current camera through the current first hits, validates the four bilinear taps against the current hit
 // (same object, normal, tangent plane) and merges c = (He c_h + N c_0) / (He + N).  The passes then run on c.
+//
+// Variance-guided edge stopping (cgpt_denoise_variance_guided, cgpt_read_variance; tests/variance_ref.py states it in
+// numpy): the colour edge-stop of the passes becomes exp(-|l(c_q) - l(c_p)| / (sigma_l sqrt(gbar(p)) + 1e-6)), l the luminance and gbar
+// a 3x3 Gaussian of the pixel's variance.  variance_estimate puts that variance into the .w lane of pass 0's input: the weighted variance
+// of l over a 7x7 window, or -- with the temporal stage in front, where temporal_merge<false, true> keeps {mean, variance, samples} of l
+// beside the colour history -- the temporal estimate once a pixel's history is long enough.  variance_pass filters it along with the colour.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -117,6 +124,9 @@ __global__ void __launch_bounds__(256) denoise_prepare(const float4* __restrict_
 // h(d) of the B3 spline 1/16 (1, 4, 6, 4, 1): 3/8, 1/4, 1/16
 __device__ __forceinline__ constexpr float tap(int d) { return d == 0 ? 0.375f : (d == 1 || d == -1 ? 0.25f : 0.0625f); }
 
+// l(c), the luminance the variance-guided filter measures
+__device__ __forceinline__ float luminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+
 template <bool LAST>
 __global__ void __launch_bounds__(256) atrous_pass(const PassArgs a)
 {
@@ -211,6 +221,12 @@ struct TemporalArgs {
     float minv[9];                 // rows of the inverse of [top_left - pos | top_right - top_left | bottom_left - top_left] of the history's camera
     float pos_prev[3];
     float height, first_row;       // fy = (c / a) height - first_row
+    // MOMENTS only (cgpt_denoise_variance_guided)
+    const float4* moments;         // {mu, v, K, 0} beside hist; read only when have_moments != 0
+    float4* moments_out;
+    float* variance;               // out: var_t or -1
+    uint32_t have_moments;         // the moments belong to hist (no cgpt_denoise_temporal call updated the colour since)
+    float min_history_n;           // min_history_frames N
 };
 
 // One thread per pixel.  The geometry of the reprojection -- (a, b, c) = Minv (x - pos_prev), fx, fy, the bilinear weights and the two
@@ -220,7 +236,11 @@ struct TemporalArgs {
 // All four taps' loads (colour and two guide float4s each, from positions clamped into the band) and the material's come before any
 // validity arithmetic, which masks with selects (the lesson of atrous_pass).
 // FINAL (iterations = 0): the output is c m packed as data.pixels is, with w = 1.
-template <bool FINAL>
+// MOMENTS (cgpt_denoise_variance_guided with CGPT_VARIANCE_TEMPORAL; tests/variance_ref.py): the luminance moments
+// {mu, v, K} kept beside the colour history go through the same four taps, validity tests and weights, and merge with the N samples of
+// l0 = l(c_0) by the pooled-variance update; the pixel's entry of the variance map becomes var_t = v' N / (Ke + N), or -1 where
+// Ke + N < min_history_frames N (variance_estimate then puts var_s there).  The colour's arithmetic is the same instructions either way.
+template <bool FINAL, bool MOMENTS = false>
 __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
 {
     uint32_t px, row;
@@ -230,9 +250,16 @@ __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
     const float4 g0 = a.guides[3 * i], g1 = a.guides[3 * i + 1], g2 = a.guides[3 * i + 2];
     const float4 c0 = a.color[i];
     float hr = 0.0f, hg = 0.0f, hb = 0.0f, H = 0.0f;                            // c_h and H; H = 0: no history
+    float mu_h = 0.0f, v_h = 0.0f, K_h = 0.0f;                                 // MOMENTS; K_h = 0: no moments
     if (a.mode == kSameCamera) {                                               // same scene and camera: the same hit, no validation
         const float4 h = a.hist[i];
         hr = h.x; hg = h.y; hb = h.z; H = h.w;
+        if constexpr (MOMENTS) {
+            if (a.have_moments != 0u) {
+                const float4 m = a.moments[i];
+                mu_h = m.x; v_h = m.y; K_h = H > 0.0f ? m.z : 0.0f;
+            }
+        }
     } else if (a.mode == kReproject) {
         const uint32_t obj = __float_as_uint(g1.w), mat = __float_as_uint(g2.w);
         const bool hit = obj != kNoHit;
@@ -249,7 +276,7 @@ __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
         const double flx = floor(fx), fly = floor(fy);
         const long long x0 = (long long)flx, y0 = (long long)fly;
         const double wx = fx - flx, wy = fy - fly;
-        float4 hc[4], hx[4], hn[4];
+        float4 hc[4], hx[4], hn[4], hm[4];
         bool in[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -259,6 +286,7 @@ __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
             const size_t qy_c = (size_t)(qy < 0 ? 0 : (qy < (long long)a.n_rows ? qy : (long long)a.n_rows - 1));
             const size_t j = qy_c * a.width + qx_c;
             hc[k] = a.hist[j]; hx[k] = a.hist_guides[2 * j]; hn[k] = a.hist_guides[2 * j + 1];
+            if constexpr (MOMENTS) hm[k] = a.have_moments != 0u ? a.moments[j] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         }
         const size_t m_c = hit ? (size_t)mat : 0u;                             // a miss reads material 0 and is masked below
         const float specular = a.materials[4 * m_c].w, refractivity = a.materials[4 * m_c + 1].x;
@@ -266,6 +294,7 @@ __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
         const double tol = (double)a.plane_tolerance * (double)g0.w;
         double wsum = 0.0;
         float sr = 0.0f, sg = 0.0f, sb = 0.0f, sh = 0.0f;
+        float smu = 0.0f, sv = 0.0f, sk = 0.0f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const double ndot = ((double)hn[k].x * (double)g1.x + (double)hn[k].y * (double)g1.y) + (double)hn[k].z * (double)g1.z;
@@ -276,11 +305,13 @@ __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
             const float wf = (float)w;
             wsum += w;
             sr += wf * hc[k].x; sg += wf * hc[k].y; sb += wf * hc[k].z; sh += wf * hc[k].w;
+            if constexpr (MOMENTS) { smu += wf * hm[k].x; sv += wf * hm[k].y; sk += wf * hm[k].z; }
         }
         const bool use = in_front && !view_dependent && wsum > 0.01;         // in_front: a hit, so an equal object index is a hit's
         const float inv = 1.0f / (use ? (float)wsum : 1.0f);
         hr = sr * inv; hg = sg * inv; hb = sb * inv;
         H = use ? sh * inv : 0.0f;
+        if constexpr (MOMENTS) { mu_h = smu * inv; v_h = sv * inv; K_h = use ? sk * inv : 0.0f; }   // no colour history: no moments
     }
     const float He = fminf(H, a.max_history), N = a.n_samples;
     const float inv = 1.0f / (He + N);
@@ -290,6 +321,19 @@ __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
     }
     a.hist_out[i] = make_float4(r, g, b, fminf(He + N, a.max_history));
     a.hist_guides_out[2 * i] = g0; a.hist_guides_out[2 * i + 1] = g1;
+    if constexpr (MOMENTS) {
+        const float l0 = luminance(c0.x, c0.y, c0.z);
+        const float Ke = fminf(K_h, a.max_history), tot = Ke + N;
+        float mu = l0, v = 0.0f, K = N;
+        if (Ke > 0.0f) {
+            mu = (Ke * mu_h + N * l0) / tot;
+            const float dm = mu_h - mu, dl = l0 - mu;
+            v = (Ke * (v_h + dm * dm) + N * (dl * dl)) / tot;
+            K = fminf(tot, a.max_history);
+        }
+        a.moments_out[i] = make_float4(mu, v, K, 0.0f);
+        a.variance[i] = tot >= a.min_history_n ? v * N / tot : -1.0f;
+    }
     if (FINAL) {
         if (a.demodulate) {
             const float4 m = a.demod[i];
@@ -300,6 +344,185 @@ __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
     } else {
         a.color[i] = make_float4(r, g, b, 0.0f);
     }
+}
+
+// ---- the variance-guided filter (cgpt_denoise_variance_guided; tests/variance_ref.py states it in numpy) ----------
+constexpr cgpt_variance_params kVarianceDefaults = { 4.0f, 4u, 0u };
+
+struct VarianceArgs {
+    float4* color;             // the image the passes will read (c_0 or the merged c); out: .w = var
+    const float4* guides;
+    float* variance;           // in (have_temporal): var_t or -1 of temporal_merge<false, true>; out: var
+    uint32_t width, n_rows, have_temporal;
+    float inv_normal, inv_position;   // 1 / sigma^2 of pass 0
+};
+
+// var_s of a pixel: the weighted variance of the luminance over the 7x7 window around it, d_q = l(c_q) - l(c_p) shifted by the centre so
+// that a smooth region does not cancel; the weights are the filter's geometry term (two hits), 1 (two misses), none (a hit and a miss, or
+// outside the band).  A row of seven taps at a time, loads first, selects for the masks (atrous_pass's lessons).  A pixel that has its
+// var_t skips the window: after a few static frames that is the whole frame, and the kernel is one load and two stores per pixel.
+__global__ void __launch_bounds__(256) variance_estimate(const VarianceArgs a)
+{
+    uint32_t px, row;
+    tile_pixel(a.width, px, row);
+    if (px >= a.width || row >= a.n_rows) return;
+    const size_t i = (size_t)row * a.width + px;
+    float var = a.have_temporal != 0u ? a.variance[i] : -1.0f;
+    if (var < 0.0f) {
+        const float4 xp4 = a.guides[3 * i], np4 = a.guides[3 * i + 1];
+        const V3 x_p = mk(xp4.x, xp4.y, xp4.z), n_p = mk(np4.x, np4.y, np4.z);
+        const bool hit_p = __float_as_uint(np4.w) != kNoHit;
+        const float4 cp4 = a.color[i];
+        const float l_p = luminance(cp4.x, cp4.y, cp4.z);
+        float sw = 0.0f, swd = 0.0f, swd2 = 0.0f;
+#pragma unroll
+        for (int dy = -3; dy <= 3; ++dy) {
+            const int qy = (int)row + dy;
+            const bool row_in = qy >= 0 && qy < (int)a.n_rows;
+            const size_t qy_c = (size_t)(qy < 0 ? 0 : (row_in ? qy : (int)a.n_rows - 1));
+            float4 xq[7], nq[7], cq[7];
+            bool in[7];
+#pragma unroll
+            for (int t = 0; t < 7; ++t) {
+                const int qx = (int)px + t - 3;
+                in[t] = row_in && qx >= 0 && qx < (int)a.width;
+                const size_t j = qy_c * a.width + (size_t)(qx < 0 ? 0 : (qx < (int)a.width ? qx : (int)a.width - 1));
+                xq[t] = a.guides[3 * j]; nq[t] = a.guides[3 * j + 1]; cq[t] = a.color[j];
+            }
+#pragma unroll
+            for (int t = 0; t < 7; ++t) {
+                const bool hit_q = __float_as_uint(nq[t].w) != kNoHit;
+                const V3 dn = mk(nq[t].x, nq[t].y, nq[t].z) - n_p;
+                const float dplane = dot(n_p, mk(xq[t].x, xq[t].y, xq[t].z) - x_p);
+                const float e_geo = dot(dn, dn) * a.inv_normal + dplane * dplane * a.inv_position;
+                const float w = hit_p && hit_q ? __expf(-e_geo) : 1.0f;       // the centre tap: e = 0, w = 1
+                const float d = luminance(cq[t].x, cq[t].y, cq[t].z) - l_p;
+                const bool use = in[t] && hit_q == hit_p;
+                sw = use ? sw + w : sw;
+                swd = use ? swd + w * d : swd;
+                swd2 = use ? swd2 + (w * d) * d : swd2;
+            }
+            __builtin_amdgcn_sched_barrier(0);                                // one row's loads in flight at a time
+        }
+        const float m1 = swd / sw;
+        var = fmaxf(0.0f, swd2 / sw - m1 * m1);
+    }
+    a.variance[i] = var;
+    reinterpret_cast<float*>(a.color)[4 * i + 3] = var;                       // the .w lane the passes carry it in
+}
+
+struct VarPassArgs {
+    const float4* src;        // {c, var}: the previous pass's output (pass 0: variance_estimate's)
+    float4* dst;
+    uint32_t* pixels;         // last pass
+    const float4* guides;
+    const float4* demod;
+    uint32_t width, n_rows, step, demodulate;
+    float sigma_luminance, inv_normal, inv_position;
+};
+
+// atrous_pass with the colour edge-stop in standard deviations of the pixel: exp(-|l(c_q) - l(c_p)| / (sigma_l sqrt(gbar(p)) + 1e-6)),
+// gbar the 3x3 Gaussian of the variance over p's immediate neighbours (step 1 in every pass; over the taps in the band with p's hit /
+// miss state, renormalised), and the variance filtered along with the colour: var' = sum w^2 var_q / (sum w)^2 in the .w lane.
+// 1 / (sigma_l sqrt(gbar) + 1e-6) once per pixel, from nine loads of their own in front of the rows; the luminance term joins the
+// geometry term in one exponent, so a tap still costs one __expf.
+template <bool LAST>
+__global__ void __launch_bounds__(256) variance_pass(const VarPassArgs a)
+{
+    uint32_t px, row;
+    tile_pixel(a.width, px, row);
+    if (px >= a.width || row >= a.n_rows) return;
+    const size_t i = (size_t)row * a.width + px;
+    const float4 xp4 = a.guides[3 * i], np4 = a.guides[3 * i + 1];
+    const V3 x_p = mk(xp4.x, xp4.y, xp4.z), n_p = mk(np4.x, np4.y, np4.z);
+    const bool hit_p = __float_as_uint(np4.w) != kNoHit;
+    const float4 cp4 = a.src[i];
+    const float l_p = luminance(cp4.x, cp4.y, cp4.z);
+    float inv_l;
+    {
+        float vq[9], hq[9];
+        bool in[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const int qx = (int)px + k % 3 - 1, qy = (int)row + k / 3 - 1;
+            in[k] = qx >= 0 && qx < (int)a.width && qy >= 0 && qy < (int)a.n_rows;
+            const size_t j = (size_t)(qy < 0 ? 0 : (qy < (int)a.n_rows ? qy : (int)a.n_rows - 1)) * a.width +
+                             (size_t)(qx < 0 ? 0 : (qx < (int)a.width ? qx : (int)a.width - 1));
+            vq[k] = reinterpret_cast<const float*>(a.src)[4 * j + 3];
+            hq[k] = reinterpret_cast<const float*>(a.guides)[12 * j + 7];
+        }
+        float num = 0.0f, den = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const float g = ((k % 3 == 1 ? 2.0f : 1.0f) * (k / 3 == 1 ? 2.0f : 1.0f)) * 0.0625f;
+            const bool use = in[k] && (__float_as_uint(hq[k]) != kNoHit) == hit_p;
+            num = use ? num + g * vq[k] : num;
+            den = use ? den + g : den;
+        }
+        inv_l = 1.0f / (a.sigma_luminance * sqrtf(num / den) + 1e-6f);
+    }
+    __builtin_amdgcn_sched_barrier(0);                                        // gbar's loads are done before the rows' begin
+    float sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f, wsum = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const long long qy = (long long)row + (long long)dy * a.step;
+        const bool row_in = qy >= 0 && qy < (long long)a.n_rows;
+        const size_t qy_c = (size_t)(qy < 0 ? 0 : (row_in ? qy : (long long)a.n_rows - 1));
+        float4 xq[5], nq[5], cq[5];
+        bool in[5];
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+            const long long qx = (long long)px + (long long)(t - 2) * a.step;
+            in[t] = row_in && qx >= 0 && qx < (long long)a.width;
+            const size_t j = qy_c * a.width + (size_t)(qx < 0 ? 0 : (qx < (long long)a.width ? qx : (long long)a.width - 1));
+            xq[t] = a.guides[3 * j]; nq[t] = a.guides[3 * j + 1]; cq[t] = a.src[j];
+        }
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+            const bool hit_q = __float_as_uint(nq[t].w) != kNoHit;
+            const float dl = fabsf(luminance(cq[t].x, cq[t].y, cq[t].z) - l_p);
+            const V3 dn = mk(nq[t].x, nq[t].y, nq[t].z) - n_p;
+            const float dplane = dot(n_p, mk(xq[t].x, xq[t].y, xq[t].z) - x_p);
+            const float e_geo = dot(dn, dn) * a.inv_normal + dplane * dplane * a.inv_position;
+            const float e = dl * inv_l + (hit_p && hit_q ? e_geo : 0.0f);
+            const float w = (tap(t - 2) * tap(dy)) * __expf(-e);                // the centre tap: e = 0, w = h
+            const bool use = in[t] && hit_q == hit_p;
+            sr = use ? sr + cq[t].x * w : sr;
+            sg = use ? sg + cq[t].y * w : sg;
+            sb = use ? sb + cq[t].z * w : sb;
+            sv += (use ? w * w : 0.0f) * cq[t].w;                              // the weight masked, not the sum: a select on the sum
+                                                                              // let the compiler put this lane's load behind a branch
+            wsum = use ? wsum + w : wsum;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    V3 r = mk(sr / wsum, sg / wsum, sb / wsum);
+    if (LAST) {
+        if (a.demodulate) {
+            const float4 m = a.demod[i];
+            r = mk(r.x * m.x, r.y * m.y, r.z * m.z);
+        }
+        a.dst[i] = make_float4(r.x, r.y, r.z, 1.0f);
+        a.pixels[i] = vec4_to_uint(r.x, r.y, r.z);
+    } else {
+        a.dst[i] = make_float4(r.x, r.y, r.z, sv / (wsum * wsum));
+    }
+}
+
+// iterations = 0 behind the temporal stage: the merged c times the albedo, packed, w = 1 -- temporal_merge<true>'s output
+__global__ void __launch_bounds__(256) variance_identity(const float4* __restrict__ src, const float4* __restrict__ demod, float4* __restrict__ dst,
+                                                         uint32_t* __restrict__ pixels, size_t n_pixels, uint32_t demodulate)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pixels) return;
+    const float4 c = src[i];
+    float r = c.x, g = c.y, b = c.z;
+    if (demodulate) {
+        const float4 m = demod[i];
+        r *= m.x; g *= m.y; b *= m.z;
+    }
+    dst[i] = make_float4(r, g, b, 1.0f);
+    pixels[i] = vec4_to_uint(r, g, b);
 }
 
 // what a call works on: a one-device context's contiguous band, or a multi-device context's full frame on its first member
@@ -493,24 +716,10 @@ bool HistoryMatches(const cgpt_ctx* d, const uint32_t key[4], uint32_t demodulat
            memcmp(d->temporal_frame, key, sizeof(d->temporal_frame)) == 0;
 }
 
-int DenoiseTemporal(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, const cgpt_denoise_params& p, const cgpt_temporal_params& t,
-                    const float4* acc, float* dst_rgba, uint32_t* dst_pixels)
+// the arguments of the temporal stage of a frame: from dn.history[temporal_slot] (when `have`) into the other slot, on filter[0]
+void FillTemporalArgs(const Frame& f, const cgpt_camera* camera, const cgpt_temporal_params& t, uint32_t demodulate, bool have, TemporalArgs& a)
 {
     cgpt_ctx* d = f.dev;
-    const size_t n = (size_t)f.width * f.n_rows;
-    const uint32_t key[4] = { f.width, f.height, f.first_row, f.n_rows };
-    const uint32_t demodulate = (p.flags & CGPT_DENOISE_DEMODULATE_ALBEDO) ? 1u : 0u;
-    const bool have = HistoryMatches(d, key, demodulate);
-    d->temporal_valid = false;                                                 // a call that fails from here on leaves no history
-    int rc;
-    HIP_TRY(ctx, hipSetDevice(d->device));
-    if ((rc = EnsureFilterBuffers(ctx, d, n)) != CGPT_OK) return rc;
-    if ((rc = EnsureHistoryBuffers(ctx, d, n)) != CGPT_OK) return rc;
-    if ((rc = EnsureGuides(ctx, f, camera)) != CGPT_OK) return rc;
-    hipLaunchKernelGGL(denoise_prepare, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, d->stream, acc, d->dn.guide_demod.p, d->dn.filter[0].p, n,
-                       (float)f.num_accumulated, demodulate);
-    HIP_TRY(ctx, hipGetLastError());
-    TemporalArgs a{};
     const uint32_t src = d->temporal_slot, dst = src ^ 1u;
     a.guides = d->dn.guides.p; a.demod = d->dn.guide_demod.p; a.materials = d->scene.materials;
     a.hist = d->dn.history[src].p; a.hist_guides = d->dn.history_guides[src].p;
@@ -528,6 +737,39 @@ int DenoiseTemporal(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, co
             a.mode = kReproject;
         }
     }
+}
+
+// what a successful temporal stage leaves: the history in the other slot, and what it was stored for
+void StoreTemporalKey(cgpt_ctx* d, const cgpt_camera* camera, const uint32_t key[4], uint32_t demodulate)
+{
+    d->temporal_slot ^= 1u;
+    d->temporal_demodulate = demodulate;
+    d->temporal_generation = d->scene_generation;
+    memcpy(&d->temporal_camera, camera, sizeof(cgpt_camera));
+    memcpy(d->temporal_frame, key, sizeof(d->temporal_frame));
+    d->temporal_valid = true;
+}
+
+int DenoiseTemporal(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, const cgpt_denoise_params& p, const cgpt_temporal_params& t,
+                    const float4* acc, float* dst_rgba, uint32_t* dst_pixels)
+{
+    cgpt_ctx* d = f.dev;
+    const size_t n = (size_t)f.width * f.n_rows;
+    const uint32_t key[4] = { f.width, f.height, f.first_row, f.n_rows };
+    const uint32_t demodulate = (p.flags & CGPT_DENOISE_DEMODULATE_ALBEDO) ? 1u : 0u;
+    const bool have = HistoryMatches(d, key, demodulate);
+    d->temporal_valid = false;                                                 // a call that fails from here on leaves no history
+    d->moments_valid = false;                                                  // the colour moves on without the luminance moments
+    int rc;
+    HIP_TRY(ctx, hipSetDevice(d->device));
+    if ((rc = EnsureFilterBuffers(ctx, d, n)) != CGPT_OK) return rc;
+    if ((rc = EnsureHistoryBuffers(ctx, d, n)) != CGPT_OK) return rc;
+    if ((rc = EnsureGuides(ctx, f, camera)) != CGPT_OK) return rc;
+    hipLaunchKernelGGL(denoise_prepare, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, d->stream, acc, d->dn.guide_demod.p, d->dn.filter[0].p, n,
+                       (float)f.num_accumulated, demodulate);
+    HIP_TRY(ctx, hipGetLastError());
+    TemporalArgs a{};
+    FillTemporalArgs(f, camera, t, demodulate, have, a);
     const uint32_t tiles = ((f.width + kTile - 1u) / kTile) * ((f.n_rows + kTile - 1u) / kTile);
     if (p.iterations == 0) hipLaunchKernelGGL(temporal_merge<true>, dim3(tiles), dim3(256), 0, d->stream, a);
     else hipLaunchKernelGGL(temporal_merge<false>, dim3(tiles), dim3(256), 0, d->stream, a);
@@ -535,12 +777,100 @@ int DenoiseTemporal(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, co
     float4* out = d->dn.filter[0].p;
     if ((rc = FilterPasses(ctx, f, p, out)) != CGPT_OK) return rc;
     if ((rc = ReadBack(ctx, d, n, out, dst_rgba, dst_pixels)) != CGPT_OK) return rc;
-    d->temporal_slot = dst;
-    d->temporal_demodulate = demodulate;
-    d->temporal_generation = d->scene_generation;
-    memcpy(&d->temporal_camera, camera, sizeof(cgpt_camera));
-    memcpy(d->temporal_frame, key, sizeof(key));
-    d->temporal_valid = true;
+    StoreTemporalKey(d, camera, key, demodulate);
+    return CGPT_OK;
+}
+
+int CheckVarianceParams(cgpt_ctx* ctx, const cgpt_variance_params& v)
+{
+    if (!std::isfinite(v.sigma_luminance) || !(v.sigma_luminance > 0.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "sigma_luminance must be finite and > 0, got %g", v.sigma_luminance);
+    if (v.min_history_frames == 0u) return CtxFail(ctx, CGPT_ERR_INVALID, "min_history_frames must be >= 1");
+    if (v.flags & ~(uint32_t)CGPT_VARIANCE_TEMPORAL) return CtxFail(ctx, CGPT_ERR_INVALID, "unknown variance flags 0x%x", v.flags);
+    return CGPT_OK;
+}
+
+int EnsureVarianceBuffers(cgpt_ctx* ctx, cgpt_ctx* d, size_t n, bool temporal)
+{
+    if (d->dn.variance.n != n) {
+        d->variance_valid = false;
+        HIP_TRY(ctx, d->dn.variance.Alloc(n));
+    }
+    if (temporal && d->dn.moments[1].n != n) {                                 // any other size: both anew (the second one's count is the key)
+        d->moments_valid = false;
+        ResetAll(d->dn.moments[0], d->dn.moments[1]);
+        HIP_TRY(ctx, d->dn.moments[0].Alloc(n));
+        HIP_TRY(ctx, d->dn.moments[1].Alloc(n));
+    }
+    return CGPT_OK;
+}
+
+// cgpt_denoise_variance_guided: denoise_prepare, the temporal stage with the moments (flag), variance_estimate, the passes
+int DenoiseVariance(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, const cgpt_denoise_params& p, const cgpt_temporal_params& t,
+                    const cgpt_variance_params& v, const float4* acc, float* dst_rgba, uint32_t* dst_pixels)
+{
+    cgpt_ctx* d = f.dev;
+    const size_t n = (size_t)f.width * f.n_rows;
+    const uint32_t key[4] = { f.width, f.height, f.first_row, f.n_rows };
+    const uint32_t demodulate = (p.flags & CGPT_DENOISE_DEMODULATE_ALBEDO) ? 1u : 0u;
+    const bool temporal = (v.flags & CGPT_VARIANCE_TEMPORAL) != 0u;
+    const bool have = temporal && HistoryMatches(d, key, demodulate);
+    const bool have_moments = have && d->moments_valid;
+    d->variance_valid = false;                                                 // a call that fails from here on leaves no map
+    if (temporal) d->temporal_valid = d->moments_valid = false;                // ... and no history
+    int rc;
+    HIP_TRY(ctx, hipSetDevice(d->device));
+    if ((rc = EnsureFilterBuffers(ctx, d, n)) != CGPT_OK) return rc;
+    if (temporal && (rc = EnsureHistoryBuffers(ctx, d, n)) != CGPT_OK) return rc;
+    if ((rc = EnsureVarianceBuffers(ctx, d, n, temporal)) != CGPT_OK) return rc;
+    if ((rc = EnsureGuides(ctx, f, camera)) != CGPT_OK) return rc;
+    const uint32_t blocks = (uint32_t)((n + 255u) / 256u);
+    const uint32_t tiles = ((f.width + kTile - 1u) / kTile) * ((f.n_rows + kTile - 1u) / kTile);
+    hipLaunchKernelGGL(denoise_prepare, dim3(blocks), dim3(256), 0, d->stream, acc, d->dn.guide_demod.p, d->dn.filter[0].p, n, (float)f.num_accumulated,
+                       demodulate);
+    HIP_TRY(ctx, hipGetLastError());
+    if (temporal) {
+        TemporalArgs a{};
+        FillTemporalArgs(f, camera, t, demodulate, have, a);
+        a.moments = d->dn.moments[d->temporal_slot].p; a.moments_out = d->dn.moments[d->temporal_slot ^ 1u].p;
+        a.variance = d->dn.variance.p;
+        a.have_moments = have_moments ? 1u : 0u;
+        a.min_history_n = (float)v.min_history_frames * (float)f.num_accumulated;
+        hipLaunchKernelGGL((temporal_merge<false, true>), dim3(tiles), dim3(256), 0, d->stream, a);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    VarianceArgs va{};
+    va.color = d->dn.filter[0].p; va.guides = d->dn.guides.p; va.variance = d->dn.variance.p;
+    va.width = f.width; va.n_rows = f.n_rows; va.have_temporal = temporal ? 1u : 0u;
+    va.inv_normal = (float)(1.0 / ((double)p.sigma_normal * p.sigma_normal));
+    va.inv_position = (float)(1.0 / ((double)p.sigma_position * p.sigma_position));
+    hipLaunchKernelGGL(variance_estimate, dim3(tiles), dim3(256), 0, d->stream, va);
+    HIP_TRY(ctx, hipGetLastError());
+    float4* out = d->dn.filter[1].p;
+    if (p.iterations == 0) {                                                   // the unfiltered image: cgpt_denoise's, or the merged c
+        if (temporal) hipLaunchKernelGGL(variance_identity, dim3(blocks), dim3(256), 0, d->stream, d->dn.filter[0].p, d->dn.guide_demod.p, out,
+                                         d->dn.filter_pixels.p, n, demodulate);
+        else hipLaunchKernelGGL(denoise_identity, dim3(blocks), dim3(256), 0, d->stream, acc, out, d->dn.filter_pixels.p, n, (float)f.num_accumulated);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    for (uint32_t it = 0; it < p.iterations; ++it) {
+        VarPassArgs a;
+        a.src = d->dn.filter[it & 1u].p;
+        a.dst = out = d->dn.filter[(it + 1u) & 1u].p;
+        a.pixels = d->dn.filter_pixels.p;
+        a.guides = d->dn.guides.p; a.demod = d->dn.guide_demod.p;
+        a.width = f.width; a.n_rows = f.n_rows; a.step = 1u << it; a.demodulate = demodulate;
+        a.sigma_luminance = v.sigma_luminance; a.inv_normal = va.inv_normal; a.inv_position = va.inv_position;
+        if (it + 1u == p.iterations) hipLaunchKernelGGL(variance_pass<true>, dim3(tiles), dim3(256), 0, d->stream, a);
+        else hipLaunchKernelGGL(variance_pass<false>, dim3(tiles), dim3(256), 0, d->stream, a);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if ((rc = ReadBack(ctx, d, n, out, dst_rgba, dst_pixels)) != CGPT_OK) return rc;
+    if (temporal) {
+        StoreTemporalKey(d, camera, key, demodulate);
+        d->moments_valid = true;
+    }
+    memcpy(d->variance_frame, key, sizeof(key));
+    d->variance_valid = true;
     return CGPT_OK;
 }
 
@@ -551,6 +881,8 @@ void DenoiseFree(cgpt_ctx* ctx)
     ctx->dn = DenoiseBuffers{};
     ctx->guides_valid = false;
     ctx->temporal_valid = false;
+    ctx->moments_valid = false;
+    ctx->variance_valid = false;
 }
 
 }  // namespace cgpt
@@ -618,6 +950,56 @@ int cgpt_denoise_temporal(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_d
     rc = DenoiseTemporal(ctx, f, camera, p, t, acc, dst_rgba, dst_pixels);
     if (rc != CGPT_OK) f.dev->guides_valid = false;
     return rc;
+}
+
+int cgpt_denoise_variance_guided(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_params* params, const cgpt_temporal_params* temporal,
+                                 const cgpt_variance_params* variance, float* dst_rgba, size_t n_floats, uint32_t* dst_pixels, size_t n_pixels)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    Frame f;
+    int rc = ResolveFrame(ctx, true, camera, f);
+    if (rc != CGPT_OK) return rc;
+    const cgpt_denoise_params p = params ? *params : kDefaults;
+    if ((rc = CheckParams(ctx, p)) != CGPT_OK) return rc;
+    const cgpt_variance_params v = variance ? *variance : kVarianceDefaults;
+    if ((rc = CheckVarianceParams(ctx, v)) != CGPT_OK) return rc;
+    const bool with_temporal = (v.flags & CGPT_VARIANCE_TEMPORAL) != 0u;
+    const cgpt_temporal_params t = with_temporal && temporal ? *temporal : kTemporalDefaults;   // read only with the flag
+    if ((rc = CheckTemporalParams(ctx, t)) != CGPT_OK) return rc;
+    const size_t n = (size_t)f.width * f.n_rows;
+    if (!dst_rgba && !dst_pixels) return CtxFail(ctx, CGPT_ERR_INVALID, "both outputs are null");
+    if (dst_rgba && n_floats != 4 * n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats (4 per pixel)", 4 * n);
+    if (dst_pixels && n_pixels != n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu pixels", n);
+    const float4* acc = ctx->fb.accumulator.p;
+    if (ctx->group && (rc = GroupGatherUncounted(ctx, &acc)) != CGPT_OK) {
+        f.dev->variance_valid = false;
+        if (with_temporal) f.dev->temporal_valid = false;
+        return rc;
+    }
+    rc = DenoiseVariance(ctx, f, camera, p, t, v, acc, dst_rgba, dst_pixels);
+    if (rc != CGPT_OK) f.dev->guides_valid = false;
+    return rc;
+}
+
+int cgpt_read_variance(cgpt_ctx* ctx, float* dst, size_t n_floats)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    cgpt_ctx* const first = GroupFirstMemberOrNull(ctx);
+    cgpt_ctx* const d = first ? first : ctx;
+    uint32_t key[4] = { ctx->width, ctx->height, ctx->band_key[0], ctx->n_rows };       // the current band
+    if (ctx->group) {
+        uint32_t num_accumulated, debug;
+        GroupFrameInfo(ctx, &key[0], &key[1], &num_accumulated, &debug);
+        key[2] = 0; key[3] = key[1];
+    }
+    if (!d->variance_valid || memcmp(d->variance_frame, key, sizeof(key)) != 0)
+        return CtxFail(ctx, CGPT_ERR_INVALID, "no variance map: no cgpt_denoise_variance_guided call succeeded for this band");
+    const size_t n = (size_t)key[0] * key[3];
+    if (!dst || n_floats != n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats (1 per pixel)", n);
+    HIP_TRY(ctx, hipSetDevice(d->device));
+    HIP_TRY(ctx, hipMemcpyAsync(dst, d->dn.variance.p, n * sizeof(float), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(d->stream));
+    return CGPT_OK;
 }
 
 int cgpt_temporal_reset(cgpt_ctx* ctx)

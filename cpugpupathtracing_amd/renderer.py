@@ -300,6 +300,32 @@ class Renderer:
         self._check(self.L.cgpt_read_temporal_history(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
         return out
 
+    def denoise_variance_guided(self, iterations: int = 5, sigma_luminance: float = 4.0, sigma_normal: float = 0.2, sigma_position: float = 0.3,
+                                demodulate: bool = True, temporal: bool = False, min_history_frames: int = 4, camera: Optional[N.Camera] = None,
+                                max_history: float = 64.0, normal_cos_min: float = 0.9, plane_tolerance: float = 0.01,
+                                keep_view_dependent: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """denoise() with the colour edge-stop in standard deviations of each pixel's luminance (cgpt_denoise_variance_guided): the
+        variance is estimated over a 7x7 window, or -- temporal=True: denoise_temporal()'s stage runs in front, with its keywords, and
+        luminance moments are kept with its history -- over time once a pixel has min_history_frames frames' worth of samples.
+        Returns what denoise() returns; variance() reads the map the first pass used."""
+        cam = camera if camera is not None else self.scene.camera()
+        p = N.DenoiseParams(iterations, N.DENOISE_DEMODULATE_ALBEDO if demodulate else 0, 4.0, sigma_normal, sigma_position)
+        t = N.TemporalParams(max_history, normal_cos_min, plane_tolerance, N.TEMPORAL_KEEP_VIEW_DEPENDENT if keep_view_dependent else 0)
+        v = N.VarianceParams(sigma_luminance, min_history_frames, N.VARIANCE_TEMPORAL if temporal else 0)
+        rgba = np.empty((self.n_rows, self.width, 4), np.float32)
+        px = np.empty((self.n_rows, self.width), np.uint32)
+        self._check(self.L.cgpt_denoise_variance_guided(self._ctx, C.byref(cam), C.byref(p), C.byref(t), C.byref(v),
+                                                        rgba.ctypes.data_as(C.POINTER(C.c_float)), rgba.size,
+                                                        px.ctypes.data_as(C.POINTER(C.c_uint32)), px.size))
+        return rgba, px
+
+    def variance(self) -> np.ndarray:
+        """The per-pixel luminance variance the first pass of the last denoise_variance_guided() read (cgpt_read_variance):
+        (rows, width) float32."""
+        out = np.empty((self.n_rows, self.width), np.float32)
+        self._check(self.L.cgpt_read_variance(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
     def accumulator_device_ptr(self) -> Tuple[int, int]:
         ptr = C.c_void_p(); nbytes = C.c_size_t()
         self._check(self.L.cgpt_accumulator_device_ptr(self._ctx, C.byref(ptr), C.byref(nbytes)))

@@ -4,7 +4,7 @@
 //
 //   g++ -std=c++17 -Iinclude -Icpugpupathtracing_amd/csrc/host examples/render_main.cpp
 //       -Lcpugpupathtracing_amd/lib -lcpugpupt -Wl,-rpath,$PWD/cpugpupathtracing_amd/lib -o render_main   (one command line)
-//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--smooth] [--mesh-transform m00 .. m23] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
+//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--smooth] [--mesh-transform m00 .. m23] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
 // --gpus N: ONE context over the first N GPUs of the node (cgpt_ctx_create with n_devices = N): every frame is spread over them in
 // interleaved row bands and the read-back gathers the float4 bands with one RCCL exchange over xGMI; the loop below does not
 // change.  --collective: take that code path with N = 1 too (what a one-GPU box can test).
@@ -16,6 +16,10 @@
 // from a reset accumulator, as a viewer renders while the camera moves; every frame is written raw (temporal_NN_raw.ppm), through
 // cgpt_denoise (temporal_NN_denoised.ppm) and through cgpt_denoise_temporal, which reprojects the frames before it (temporal_NN_temporal.ppm;
 // DESIGN.md 5.19).  Takes [width height spp] only.
+// --variance-guided: the filter with the colour edge-stop in standard deviations of each pixel (cgpt_denoise_variance_guided).
+// With --denoise it is written next to every denoised image (preview_NNNN_variance_guided.ppm, render_variance_guided.ppm); with --temporal
+// it takes cgpt_denoise_temporal's place with CGPT_VARIANCE_TEMPORAL set (temporal_NN_variance_guided.ppm instead of temporal_NN_temporal.ppm:
+// one call per rendered frame may consume its samples).
 // --ground-roughness R: a glossy ground -- its material (1) gets specular 0.5 and roughness R in [0, 1] (cgpt_scene_update_roughness after
 // the upload; 0 keeps the mirror half of the lobe perfect).
 // --glass-roughness R: a frosted mesh -- its material (3, the glass) gets the transmission roughness R in [0, 1]
@@ -55,7 +59,7 @@ using namespace cgpt;
 
 int main(int argc, char** argv)
 {
-    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false;
+    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false;
     bool has_transform = false; float mesh_transform[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
     MeshBVH::BuildOption bvh_option = MeshBVH::BuildOption_SAHSplitIntervals;
     while (argc > 1 && std::string(argv[1]).rfind("--", 0) == 0) {
@@ -63,6 +67,7 @@ int main(int argc, char** argv)
         else if (std::string(argv[1]) == "--collective") { ctx_flags |= CGPT_CTX_FORCE_COLLECTIVE; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--denoise") { denoise = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--temporal") { temporal = true; argv += 1; argc -= 1; }
+        else if (std::string(argv[1]) == "--variance-guided") { variance_guided = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--smooth") { smooth = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--mesh-transform" && argc > 13) {
             for (int k = 0; k < 12; ++k) mesh_transform[k] = (float)atof(argv[2 + k]);
@@ -143,6 +148,12 @@ int main(int argc, char** argv)
             snprintf(name, sizeof(name), "temporal_%02u_raw.ppm", frame); WritePPM(name, px.data(), W, H, err);
             CHECK(cgpt_denoise(ctx, &cam, nullptr, nullptr, 0, px.data(), px.size()));
             snprintf(name, sizeof(name), "temporal_%02u_denoised.ppm", frame); WritePPM(name, px.data(), W, H, err);
+            if (variance_guided) {                                       // the temporal stage with the luminance moments, once per rendered frame
+                const cgpt_variance_params vp = { 4.0f, 4u, CGPT_VARIANCE_TEMPORAL };
+                CHECK(cgpt_denoise_variance_guided(ctx, &cam, nullptr, nullptr, &vp, nullptr, 0, px.data(), px.size()));
+                snprintf(name, sizeof(name), "temporal_%02u_variance_guided.ppm", frame); WritePPM(name, px.data(), W, H, err);
+                continue;
+            }
             CHECK(cgpt_denoise_temporal(ctx, &cam, nullptr, nullptr, nullptr, 0, px.data(), px.size()));   // once per rendered frame
             snprintf(name, sizeof(name), "temporal_%02u_temporal.ppm", frame); WritePPM(name, px.data(), W, H, err);
         }
@@ -176,6 +187,11 @@ int main(int argc, char** argv)
                 CHECK(cgpt_denoise(ctx, &scene.camera.Abi(), nullptr, nullptr, 0, denoised.data(), denoised.size()));
                 snprintf(name, sizeof(name), "preview_%04u_denoised.ppm", num_accumulated);
                 WritePPM(name, denoised.data(), W, H, err);
+                if (variance_guided) {
+                    CHECK(cgpt_denoise_variance_guided(ctx, &scene.camera.Abi(), nullptr, nullptr, nullptr, nullptr, 0, denoised.data(), denoised.size()));
+                    snprintf(name, sizeof(name), "preview_%04u_variance_guided.ppm", num_accumulated);
+                    WritePPM(name, denoised.data(), W, H, err);
+                }
             }
         }
     }
@@ -195,6 +211,10 @@ int main(int argc, char** argv)
     if (denoise) {
         CHECK(cgpt_denoise(ctx, &scene.camera.Abi(), nullptr, nullptr, 0, denoised.data(), denoised.size()));
         WritePPM("render_denoised.ppm", denoised.data(), W, H, err);
+        if (variance_guided) {
+            CHECK(cgpt_denoise_variance_guided(ctx, &scene.camera.Abi(), nullptr, nullptr, nullptr, nullptr, 0, denoised.data(), denoised.size()));
+            WritePPM("render_variance_guided.ppm", denoised.data(), W, H, err);
+        }
     }
     cgpt_ctx_destroy(ctx);                                               // ThreadPool::Exit
     return 0;

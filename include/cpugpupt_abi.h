@@ -34,7 +34,9 @@ extern "C" {
                                  (cgpt_scene_update_smooth_normals); per-object transforms added one new symbol only
                                  (cgpt_scene_update_transforms); the top-level tree added one new symbol only
                                  (cgpt_set_top_level); temporal reprojection added new symbols (cgpt_denoise_temporal,
-                                 cgpt_temporal_reset, cgpt_read_temporal_history) and a new struct (cgpt_temporal_params) only */
+                                 cgpt_temporal_reset, cgpt_read_temporal_history) and a new struct (cgpt_temporal_params) only;
+                                 variance-guided edge stopping added new symbols (cgpt_denoise_variance_guided,
+                                 cgpt_read_variance) and a new struct (cgpt_variance_params) only */
 
 enum cgpt_status {
     CGPT_OK = 0,
@@ -484,6 +486,44 @@ int cgpt_temporal_reset(cgpt_ctx* ctx);
 /* 4 floats per pixel of the band the history was stored for: the merged colour c (the filter's input domain: demodulated when the call
  * was) and the history length H' */
 int cgpt_read_temporal_history(cgpt_ctx* ctx, float* dst, size_t n_floats);
+
+/* ---- variance-guided edge stopping (the third part of SVGF, Schied et al. 2017) ----
+ * cgpt_denoise_variance_guided is cgpt_denoise with the colour edge-stop measured in standard deviations of each pixel instead of
+ * by the constant sigma_color: pass i weighs a tap by
+ *   h(dx) h(dy) exp(-|l(c_q) - l(c_p)| / (sigma_luminance sqrt(gbar(p)) + 1e-6)) times cgpt_denoise's geometry term,
+ * l(c) = 0.2126 r + 0.7152 g + 0.0722 b in the filter's input domain, gbar(p) the 3x3 Gaussian (1 2 1; 2 4 2; 1 2 1) / 16 of the
+ * variance over p's immediate neighbours.  The variance travels with the colour, var' = sum w^2 var_q / (sum w)^2, so later passes
+ * tighten by themselves: sigma_luminance is the same in every pass.  `params` means what it means for cgpt_denoise: iterations, the
+ * demodulate flag, sigma_normal and sigma_position apply; sigma_color is validated and not used.
+ * The variance pass 0 reads is estimated per pixel.  Spatially: the variance of l over a 7x7 window of the image the passes read, each
+ * tap weighted by the geometry term (two misses: 1; a hit and a miss never mix), var_s = max(0, sum w d^2 / sum w - (sum w d / sum w)^2)
+ * with d = l(c_q) - l(c_p).  With CGPT_VARIANCE_TEMPORAL the call runs cgpt_denoise_temporal's stage in front -- the colour merge and
+ * the stored history are that call's bit for bit, either call may continue the other's colour history, `temporal` NULL means its
+ * defaults -- and keeps luminance moments {mu, v, K} (mean, population variance, samples covered) beside the colour history,
+ * reprojected with the colour's taps, validity tests and weights and merged by the pooled-variance update
+ *   mu' = (Ke mu_h + N l0) / (Ke + N),  v' = (Ke (v_h + (mu_h - mu')^2) + N (l0 - mu')^2) / (Ke + N),  K' = min(Ke + N, max_history),
+ * Ke = min(K_h, max_history), l0 = l(c_0); without moments mu' = l0, v' = 0, K' = N.  A pixel with Ke + N >= min_history_frames N
+ * takes var_t = v' N / (Ke + N), every other pixel var_s.  The moments are absent wherever and whenever the colour history is, and
+ * after a cgpt_denoise_temporal call (which updates the colour without them).  Without the flag no history is read or written.
+ * iterations = 0 returns the unfiltered image (cgpt_denoise's, or with the flag cgpt_denoise_temporal's) and still estimates the variance.
+ * Bands, multi-device contexts, stream and blocking are cgpt_denoise's.  The call leaves the accumulator, data.pixels, num_accumulated,
+ * cgpt_stats and the guides alone, and the outputs of cgpt_denoise and cgpt_denoise_temporal do not depend on it.
+ * Refusals (before any device work; nothing changes, the histories and the variance map included): every refusal of cgpt_denoise;
+ * with the flag every refusal of cgpt_denoise_temporal's parameters; sigma_luminance not finite or <= 0, min_history_frames == 0,
+ * unknown flag bits; cgpt_read_variance without an earlier successful call for the current band or with a wrong size -- all
+ * CGPT_ERR_INVALID.  Added exports: CGPT_ABI_VERSION stays 2. */
+enum cgpt_variance_flags { CGPT_VARIANCE_TEMPORAL = 1u };   /* run cgpt_denoise_temporal's stage in front, and keep luminance moments with its history */
+typedef struct cgpt_variance_params {
+    float    sigma_luminance;      /* the luminance edge-stop, in standard deviations; finite, > 0 */
+    uint32_t min_history_frames;   /* temporal variance is used from this many frames' worth of samples on; >= 1 */
+    uint32_t flags;                /* cgpt_variance_flags */
+} cgpt_variance_params;            /* NULL = the defaults: 4.0, 4, 0 */
+int cgpt_denoise_variance_guided(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_params* params,
+                                 const cgpt_temporal_params* temporal, const cgpt_variance_params* variance,
+                                 float* dst_rgba, size_t n_floats, uint32_t* dst_pixels, size_t n_pixels);
+/* one float per pixel of the band: the variance pass 0 of the last successful cgpt_denoise_variance_guided read (its input, before any
+ * pass) */
+int cgpt_read_variance(cgpt_ctx* ctx, float* dst, size_t n_floats);
 
 /* ---- tuning and measurement aids (no reference counterpart) ------------------------------------------------------- */
 /* Overrides one tuning knob of the wavefront pipeline for this context (the CGPT_WF_* environment variables set the same
