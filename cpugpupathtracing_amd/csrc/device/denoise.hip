@@ -102,8 +102,10 @@ struct PassArgs {
     const float4* guides;
     const float4* demod;
     uint32_t width, n_rows, step, demodulate;
-    float inv_color, inv_normal, inv_position;   // 1 / sigma^2 of this pass
+    float color_scale;        // atrous_pass: 1 / (sigma_c 2^-i)^2 of this pass; variance_pass: sigma_luminance
+    float inv_normal, inv_position;   // 1 / sigma^2
 };
+struct VarPassArgs : PassArgs {};   // src is {c, var}: the same layout under the name variance_pass has in the code object
 
 // c_0 = acc / num_accumulated (data.pixels' division, ref: Main.cpp:741), divided by the albedo with demodulation.  Once per pixel here
 // rather than in each of pass 0's 25 taps: 150 IEEE divisions per pixel took that pass to 256 VGPRs, one wave per SIMD.
@@ -127,6 +129,29 @@ __device__ __forceinline__ constexpr float tap(int d) { return d == 0 ? 0.375f :
 // l(c), the luminance the variance-guided filter measures
 __device__ __forceinline__ float luminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 
+// a tap's coordinate clamped into [0, n): a tap outside the band is loaded from the nearest pixel inside it and masked by a select.
+// (A row's clamp is written on its row_in instead: through this helper the kernels' instruction streams moved.)
+template <typename T> __device__ __forceinline__ size_t clamp_tap(T q, T n) { return (size_t)(q < 0 ? 0 : (q < n ? q : n - 1)); }
+
+// the geometry term of a tap's exponent, for two hits: |n_q - n_p|^2 / sigma_n^2 + (n_p . (x_q - x_p))^2 / sigma_x^2
+__device__ __forceinline__ float geometry_exponent(const float4& xq, const float4& nq, const V3& x_p, const V3& n_p, float inv_normal, float inv_position)
+{
+    const V3 dn = mk(nq.x, nq.y, nq.z) - n_p;
+    const float dplane = dot(n_p, mk(xq.x, xq.y, xq.z) - x_p);               // distance to p's tangent plane
+    return dot(dn, dn) * inv_normal + dplane * dplane * inv_position;
+}
+
+// what a call's last kernel writes: the albedo multiplied back (demodulation), w = 1, and the pixel packed as data.pixels is
+__device__ __forceinline__ void write_output(float r, float g, float b, uint32_t demodulate, const float4* demod, float4* dst, uint32_t* pixels, size_t i)
+{
+    if (demodulate) {
+        const float4 m = demod[i];
+        r *= m.x; g *= m.y; b *= m.z;
+    }
+    dst[i] = make_float4(r, g, b, 1.0f);
+    pixels[i] = vec4_to_uint(r, g, b);
+}
+
 template <bool LAST>
 __global__ void __launch_bounds__(256) atrous_pass(const PassArgs a)
 {
@@ -147,7 +172,7 @@ __global__ void __launch_bounds__(256) atrous_pass(const PassArgs a)
     for (int dy = -2; dy <= 2; ++dy) {
         const long long qy = (long long)row + (long long)dy * a.step;
         const bool row_in = qy >= 0 && qy < (long long)a.n_rows;
-        const size_t qy_c = (size_t)(qy < 0 ? 0 : (row_in ? qy : (long long)a.n_rows - 1));
+        const size_t qy_c = (size_t)(qy < 0 ? 0 : (row_in ? qy : (long long)a.n_rows - 1));   // clamp_tap on row_in's comparison
         float4 xq[5], nq[5];
         V3 cq[5];
         bool in[5];
@@ -155,7 +180,7 @@ __global__ void __launch_bounds__(256) atrous_pass(const PassArgs a)
         for (int t = 0; t < 5; ++t) {
             const long long qx = (long long)px + (long long)(t - 2) * a.step;
             in[t] = row_in && qx >= 0 && qx < (long long)a.width;
-            const size_t j = qy_c * a.width + (size_t)(qx < 0 ? 0 : (qx < (long long)a.width ? qx : (long long)a.width - 1));
+            const size_t j = qy_c * a.width + clamp_tap(qx, (long long)a.width);
             xq[t] = a.guides[3 * j]; nq[t] = a.guides[3 * j + 1];
             const float4 c4 = a.src[j];
             cq[t] = mk(c4.x, c4.y, c4.z);
@@ -164,10 +189,8 @@ __global__ void __launch_bounds__(256) atrous_pass(const PassArgs a)
         for (int t = 0; t < 5; ++t) {
             const bool hit_q = __float_as_uint(nq[t].w) != kNoHit;
             const V3 dc = cq[t] - c_p;
-            const V3 dn = mk(nq[t].x, nq[t].y, nq[t].z) - n_p;
-            const float dplane = dot(n_p, mk(xq[t].x, xq[t].y, xq[t].z) - x_p);   // distance to p's tangent plane
-            const float e_geo = dot(dn, dn) * a.inv_normal + dplane * dplane * a.inv_position;
-            const float e = dot(dc, dc) * a.inv_color + (hit_p && hit_q ? e_geo : 0.0f);
+            const float e_geo = geometry_exponent(xq[t], nq[t], x_p, n_p, a.inv_normal, a.inv_position);
+            const float e = dot(dc, dc) * a.color_scale + (hit_p && hit_q ? e_geo : 0.0f);
             const float w = (tap(t - 2) * tap(dy)) * __expf(-e);                // the centre tap: e = 0, w = h
             const bool use = in[t] && hit_q == hit_p;                         // a hit and a miss never mix
             sr = use ? sr + cq[t].x * w : sr;
@@ -177,17 +200,9 @@ __global__ void __launch_bounds__(256) atrous_pass(const PassArgs a)
         }
         __builtin_amdgcn_sched_barrier(0);                                    // one row's loads in flight at a time: the registers of five taps
     }
-    V3 r = mk(sr / wsum, sg / wsum, sb / wsum);
-    if (LAST) {
-        if (a.demodulate) {
-            const float4 m = a.demod[i];
-            r = mk(r.x * m.x, r.y * m.y, r.z * m.z);
-        }
-        a.dst[i] = make_float4(r.x, r.y, r.z, 1.0f);
-        a.pixels[i] = vec4_to_uint(r.x, r.y, r.z);
-    } else {
-        a.dst[i] = make_float4(r.x, r.y, r.z, 0.0f);
-    }
+    const V3 r = mk(sr / wsum, sg / wsum, sb / wsum);
+    if (LAST) write_output(r.x, r.y, r.z, a.demodulate, a.demod, a.dst, a.pixels, i);
+    else a.dst[i] = make_float4(r.x, r.y, r.z, 0.0f);
 }
 
 // iterations = 0: the accumulator / num_accumulated, packed as data.pixels is (the same division and packing: the same bits)
@@ -282,8 +297,7 @@ __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
         for (int k = 0; k < 4; ++k) {
             const long long qx = x0 + (k & 1), qy = y0 + (k >> 1);
             in[k] = qx >= 0 && qx < (long long)a.width && qy >= 0 && qy < (long long)a.n_rows;
-            const size_t qx_c = (size_t)(qx < 0 ? 0 : (qx < (long long)a.width ? qx : (long long)a.width - 1));
-            const size_t qy_c = (size_t)(qy < 0 ? 0 : (qy < (long long)a.n_rows ? qy : (long long)a.n_rows - 1));
+            const size_t qx_c = clamp_tap(qx, (long long)a.width), qy_c = clamp_tap(qy, (long long)a.n_rows);
             const size_t j = qy_c * a.width + qx_c;
             hc[k] = a.hist[j]; hx[k] = a.hist_guides[2 * j]; hn[k] = a.hist_guides[2 * j + 1];
             if constexpr (MOMENTS) hm[k] = a.have_moments != 0u ? a.moments[j] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -334,16 +348,8 @@ __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
         a.moments_out[i] = make_float4(mu, v, K, 0.0f);
         a.variance[i] = tot >= a.min_history_n ? v * N / tot : -1.0f;
     }
-    if (FINAL) {
-        if (a.demodulate) {
-            const float4 m = a.demod[i];
-            r *= m.x; g *= m.y; b *= m.z;
-        }
-        a.color[i] = make_float4(r, g, b, 1.0f);
-        a.pixels[i] = vec4_to_uint(r, g, b);
-    } else {
-        a.color[i] = make_float4(r, g, b, 0.0f);
-    }
+    if (FINAL) write_output(r, g, b, a.demodulate, a.demod, a.color, a.pixels, i);
+    else a.color[i] = make_float4(r, g, b, 0.0f);
 }
 
 // ---- the variance-guided filter (cgpt_denoise_variance_guided; tests/variance_ref.py states it in numpy) ----------
@@ -386,15 +392,13 @@ __global__ void __launch_bounds__(256) variance_estimate(const VarianceArgs a)
             for (int t = 0; t < 7; ++t) {
                 const int qx = (int)px + t - 3;
                 in[t] = row_in && qx >= 0 && qx < (int)a.width;
-                const size_t j = qy_c * a.width + (size_t)(qx < 0 ? 0 : (qx < (int)a.width ? qx : (int)a.width - 1));
+                const size_t j = qy_c * a.width + clamp_tap(qx, (int)a.width);
                 xq[t] = a.guides[3 * j]; nq[t] = a.guides[3 * j + 1]; cq[t] = a.color[j];
             }
 #pragma unroll
             for (int t = 0; t < 7; ++t) {
                 const bool hit_q = __float_as_uint(nq[t].w) != kNoHit;
-                const V3 dn = mk(nq[t].x, nq[t].y, nq[t].z) - n_p;
-                const float dplane = dot(n_p, mk(xq[t].x, xq[t].y, xq[t].z) - x_p);
-                const float e_geo = dot(dn, dn) * a.inv_normal + dplane * dplane * a.inv_position;
+                const float e_geo = geometry_exponent(xq[t], nq[t], x_p, n_p, a.inv_normal, a.inv_position);
                 const float w = hit_p && hit_q ? __expf(-e_geo) : 1.0f;       // the centre tap: e = 0, w = 1
                 const float d = luminance(cq[t].x, cq[t].y, cq[t].z) - l_p;
                 const bool use = in[t] && hit_q == hit_p;
@@ -410,16 +414,6 @@ __global__ void __launch_bounds__(256) variance_estimate(const VarianceArgs a)
     a.variance[i] = var;
     reinterpret_cast<float*>(a.color)[4 * i + 3] = var;                       // the .w lane the passes carry it in
 }
-
-struct VarPassArgs {
-    const float4* src;        // {c, var}: the previous pass's output (pass 0: variance_estimate's)
-    float4* dst;
-    uint32_t* pixels;         // last pass
-    const float4* guides;
-    const float4* demod;
-    uint32_t width, n_rows, step, demodulate;
-    float sigma_luminance, inv_normal, inv_position;
-};
 
 // atrous_pass with the colour edge-stop in standard deviations of the pixel: exp(-|l(c_q) - l(c_p)| / (sigma_l sqrt(gbar(p)) + 1e-6)),
 // gbar the 3x3 Gaussian of the variance over p's immediate neighbours (step 1 in every pass; over the taps in the band with p's hit /
@@ -446,8 +440,7 @@ __global__ void __launch_bounds__(256) variance_pass(const VarPassArgs a)
         for (int k = 0; k < 9; ++k) {
             const int qx = (int)px + k % 3 - 1, qy = (int)row + k / 3 - 1;
             in[k] = qx >= 0 && qx < (int)a.width && qy >= 0 && qy < (int)a.n_rows;
-            const size_t j = (size_t)(qy < 0 ? 0 : (qy < (int)a.n_rows ? qy : (int)a.n_rows - 1)) * a.width +
-                             (size_t)(qx < 0 ? 0 : (qx < (int)a.width ? qx : (int)a.width - 1));
+            const size_t j = clamp_tap(qy, (int)a.n_rows) * a.width + clamp_tap(qx, (int)a.width);
             vq[k] = reinterpret_cast<const float*>(a.src)[4 * j + 3];
             hq[k] = reinterpret_cast<const float*>(a.guides)[12 * j + 7];
         }
@@ -459,7 +452,7 @@ __global__ void __launch_bounds__(256) variance_pass(const VarPassArgs a)
             num = use ? num + g * vq[k] : num;
             den = use ? den + g : den;
         }
-        inv_l = 1.0f / (a.sigma_luminance * sqrtf(num / den) + 1e-6f);
+        inv_l = 1.0f / (a.color_scale * sqrtf(num / den) + 1e-6f);
     }
     __builtin_amdgcn_sched_barrier(0);                                        // gbar's loads are done before the rows' begin
     float sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f, wsum = 0.0f;
@@ -467,23 +460,21 @@ __global__ void __launch_bounds__(256) variance_pass(const VarPassArgs a)
     for (int dy = -2; dy <= 2; ++dy) {
         const long long qy = (long long)row + (long long)dy * a.step;
         const bool row_in = qy >= 0 && qy < (long long)a.n_rows;
-        const size_t qy_c = (size_t)(qy < 0 ? 0 : (row_in ? qy : (long long)a.n_rows - 1));
+        const size_t qy_c = (size_t)(qy < 0 ? 0 : (row_in ? qy : (long long)a.n_rows - 1));   // clamp_tap on row_in's comparison
         float4 xq[5], nq[5], cq[5];
         bool in[5];
 #pragma unroll
         for (int t = 0; t < 5; ++t) {
             const long long qx = (long long)px + (long long)(t - 2) * a.step;
             in[t] = row_in && qx >= 0 && qx < (long long)a.width;
-            const size_t j = qy_c * a.width + (size_t)(qx < 0 ? 0 : (qx < (long long)a.width ? qx : (long long)a.width - 1));
+            const size_t j = qy_c * a.width + clamp_tap(qx, (long long)a.width);
             xq[t] = a.guides[3 * j]; nq[t] = a.guides[3 * j + 1]; cq[t] = a.src[j];
         }
 #pragma unroll
         for (int t = 0; t < 5; ++t) {
             const bool hit_q = __float_as_uint(nq[t].w) != kNoHit;
             const float dl = fabsf(luminance(cq[t].x, cq[t].y, cq[t].z) - l_p);
-            const V3 dn = mk(nq[t].x, nq[t].y, nq[t].z) - n_p;
-            const float dplane = dot(n_p, mk(xq[t].x, xq[t].y, xq[t].z) - x_p);
-            const float e_geo = dot(dn, dn) * a.inv_normal + dplane * dplane * a.inv_position;
+            const float e_geo = geometry_exponent(xq[t], nq[t], x_p, n_p, a.inv_normal, a.inv_position);
             const float e = dl * inv_l + (hit_p && hit_q ? e_geo : 0.0f);
             const float w = (tap(t - 2) * tap(dy)) * __expf(-e);                // the centre tap: e = 0, w = h
             const bool use = in[t] && hit_q == hit_p;
@@ -496,17 +487,9 @@ __global__ void __launch_bounds__(256) variance_pass(const VarPassArgs a)
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    V3 r = mk(sr / wsum, sg / wsum, sb / wsum);
-    if (LAST) {
-        if (a.demodulate) {
-            const float4 m = a.demod[i];
-            r = mk(r.x * m.x, r.y * m.y, r.z * m.z);
-        }
-        a.dst[i] = make_float4(r.x, r.y, r.z, 1.0f);
-        a.pixels[i] = vec4_to_uint(r.x, r.y, r.z);
-    } else {
-        a.dst[i] = make_float4(r.x, r.y, r.z, sv / (wsum * wsum));
-    }
+    const V3 r = mk(sr / wsum, sg / wsum, sb / wsum);
+    if (LAST) write_output(r.x, r.y, r.z, a.demodulate, a.demod, a.dst, a.pixels, i);
+    else a.dst[i] = make_float4(r.x, r.y, r.z, sv / (wsum * wsum));
 }
 
 // iterations = 0 behind the temporal stage: the merged c times the albedo, packed, w = 1 -- temporal_merge<true>'s output
@@ -516,13 +499,7 @@ __global__ void __launch_bounds__(256) variance_identity(const float4* __restric
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pixels) return;
     const float4 c = src[i];
-    float r = c.x, g = c.y, b = c.z;
-    if (demodulate) {
-        const float4 m = demod[i];
-        r *= m.x; g *= m.y; b *= m.z;
-    }
-    dst[i] = make_float4(r, g, b, 1.0f);
-    pixels[i] = vec4_to_uint(r, g, b);
+    write_output(c.x, c.y, c.z, demodulate, demod, dst, pixels, i);
 }
 
 // what a call works on: a one-device context's contiguous band, or a multi-device context's full frame on its first member
@@ -554,6 +531,9 @@ int ResolveFrame(cgpt_ctx* ctx, bool denoise, const cgpt_camera* camera, Frame& 
     return CGPT_OK;
 }
 
+// the frame's 16x16 tiles: the grid of every kernel that tile_pixel places
+uint32_t Tiles(const Frame& f) { return ((f.width + kTile - 1u) / kTile) * ((f.n_rows + kTile - 1u) / kTile); }
+
 // [kGuideLevels - 1 - guide level] (ctx_internal.h: ChooseGuideLevel): from the top level down, the order the instantiations have in the code object
 decltype(&guides_kernel<false>) const kGuideKernels[kGuideLevels] = { guides_kernel<true, true, true>, guides_kernel<true, true>, guides_kernel<true>, guides_kernel<false> };
 
@@ -574,9 +554,8 @@ int EnsureGuides(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera)
     DevCamera cam;
     static_assert(sizeof(DevCamera) == sizeof(cgpt_camera), "camera layouts");
     memcpy(&cam, camera, sizeof(cam));
-    const uint32_t tiles = ((f.width + kTile - 1u) / kTile) * ((f.n_rows + kTile - 1u) / kTile);
     const size_t lds = (size_t)d->scene.stack_depth * 256u * sizeof(uint32_t);   // intersect_rays_kernel's stack
-    hipLaunchKernelGGL(kGuideKernels[kGuideLevels - 1 - ChooseGuideLevel(d)], dim3(tiles), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
+    hipLaunchKernelGGL(kGuideKernels[kGuideLevels - 1 - ChooseGuideLevel(d)], dim3(Tiles(f)), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
                        d->dn.guides.p, d->dn.guide_demod.p);
     HIP_TRY(ctx, hipGetLastError());
     memcpy(d->guide_frame, key, sizeof(key));
@@ -596,60 +575,12 @@ int EnsureFilterBuffers(cgpt_ctx* ctx, cgpt_ctx* d, size_t n)
     return CGPT_OK;
 }
 
-// the a-trous passes on filter[0] (iterations >= 1); `out` is the last pass's output
-int FilterPasses(cgpt_ctx* ctx, const Frame& f, const cgpt_denoise_params& p, float4*& out)
-{
-    cgpt_ctx* d = f.dev;
-    const uint32_t demodulate = (p.flags & CGPT_DENOISE_DEMODULATE_ALBEDO) ? 1u : 0u;
-    const uint32_t tiles = ((f.width + kTile - 1u) / kTile) * ((f.n_rows + kTile - 1u) / kTile);
-    for (uint32_t it = 0; it < p.iterations; ++it) {
-        PassArgs a;
-        a.src = d->dn.filter[it & 1u].p;
-        a.dst = out = d->dn.filter[(it + 1u) & 1u].p;
-        a.pixels = d->dn.filter_pixels.p;
-        a.guides = d->dn.guides.p; a.demod = d->dn.guide_demod.p;
-        a.width = f.width; a.n_rows = f.n_rows; a.step = 1u << it; a.demodulate = demodulate;
-        const double sc = (double)p.sigma_color / (double)(1u << it);       // sigma_c 2^-i
-        a.inv_color = (float)(1.0 / (sc * sc));
-        a.inv_normal = (float)(1.0 / ((double)p.sigma_normal * p.sigma_normal));
-        a.inv_position = (float)(1.0 / ((double)p.sigma_position * p.sigma_position));
-        if (it + 1u == p.iterations) hipLaunchKernelGGL(atrous_pass<true>, dim3(tiles), dim3(256), 0, d->stream, a);
-        else hipLaunchKernelGGL(atrous_pass<false>, dim3(tiles), dim3(256), 0, d->stream, a);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    return CGPT_OK;
-}
-
 int ReadBack(cgpt_ctx* ctx, cgpt_ctx* d, size_t n, const float4* out, float* dst_rgba, uint32_t* dst_pixels)
 {
     if (dst_rgba) HIP_TRY(ctx, hipMemcpyAsync(dst_rgba, out, n * sizeof(float4), hipMemcpyDeviceToHost, d->stream));
     if (dst_pixels) HIP_TRY(ctx, hipMemcpyAsync(dst_pixels, d->dn.filter_pixels.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(ctx, hipStreamSynchronize(d->stream));
     return CGPT_OK;
-}
-
-int Denoise(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, const cgpt_denoise_params& p, const float4* acc, float* dst_rgba,
-            uint32_t* dst_pixels)
-{
-    cgpt_ctx* d = f.dev;
-    const size_t n = (size_t)f.width * f.n_rows;
-    int rc;
-    HIP_TRY(ctx, hipSetDevice(d->device));
-    if ((rc = EnsureFilterBuffers(ctx, d, n)) != CGPT_OK) return rc;
-    float4* out = d->dn.filter[0].p;
-    if (p.iterations == 0) {
-        hipLaunchKernelGGL(denoise_identity, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, d->stream, acc, out, d->dn.filter_pixels.p, n,
-                           (float)f.num_accumulated);
-        HIP_TRY(ctx, hipGetLastError());
-    } else {
-        if ((rc = EnsureGuides(ctx, f, camera)) != CGPT_OK) return rc;
-        const uint32_t demodulate = (p.flags & CGPT_DENOISE_DEMODULATE_ALBEDO) ? 1u : 0u;
-        hipLaunchKernelGGL(denoise_prepare, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, d->stream, acc, d->dn.guide_demod.p, d->dn.filter[0].p, n,
-                           (float)f.num_accumulated, demodulate);
-        HIP_TRY(ctx, hipGetLastError());
-        if ((rc = FilterPasses(ctx, f, p, out)) != CGPT_OK) return rc;
-    }
-    return ReadBack(ctx, d, n, out, dst_rgba, dst_pixels);
 }
 
 int CheckParams(cgpt_ctx* ctx, const cgpt_denoise_params& p)
@@ -661,7 +592,6 @@ int CheckParams(cgpt_ctx* ctx, const cgpt_denoise_params& p)
         if (!std::isfinite(v) || !(v > 0.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "sigmas must be finite and > 0, got %g, %g, %g", s[0], s[1], s[2]);
     return CGPT_OK;
 }
-
 
 int CheckTemporalParams(cgpt_ctx* ctx, const cgpt_temporal_params& t)
 {
@@ -750,37 +680,6 @@ void StoreTemporalKey(cgpt_ctx* d, const cgpt_camera* camera, const uint32_t key
     d->temporal_valid = true;
 }
 
-int DenoiseTemporal(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, const cgpt_denoise_params& p, const cgpt_temporal_params& t,
-                    const float4* acc, float* dst_rgba, uint32_t* dst_pixels)
-{
-    cgpt_ctx* d = f.dev;
-    const size_t n = (size_t)f.width * f.n_rows;
-    const uint32_t key[4] = { f.width, f.height, f.first_row, f.n_rows };
-    const uint32_t demodulate = (p.flags & CGPT_DENOISE_DEMODULATE_ALBEDO) ? 1u : 0u;
-    const bool have = HistoryMatches(d, key, demodulate);
-    d->temporal_valid = false;                                                 // a call that fails from here on leaves no history
-    d->moments_valid = false;                                                  // the colour moves on without the luminance moments
-    int rc;
-    HIP_TRY(ctx, hipSetDevice(d->device));
-    if ((rc = EnsureFilterBuffers(ctx, d, n)) != CGPT_OK) return rc;
-    if ((rc = EnsureHistoryBuffers(ctx, d, n)) != CGPT_OK) return rc;
-    if ((rc = EnsureGuides(ctx, f, camera)) != CGPT_OK) return rc;
-    hipLaunchKernelGGL(denoise_prepare, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, d->stream, acc, d->dn.guide_demod.p, d->dn.filter[0].p, n,
-                       (float)f.num_accumulated, demodulate);
-    HIP_TRY(ctx, hipGetLastError());
-    TemporalArgs a{};
-    FillTemporalArgs(f, camera, t, demodulate, have, a);
-    const uint32_t tiles = ((f.width + kTile - 1u) / kTile) * ((f.n_rows + kTile - 1u) / kTile);
-    if (p.iterations == 0) hipLaunchKernelGGL(temporal_merge<true>, dim3(tiles), dim3(256), 0, d->stream, a);
-    else hipLaunchKernelGGL(temporal_merge<false>, dim3(tiles), dim3(256), 0, d->stream, a);
-    HIP_TRY(ctx, hipGetLastError());
-    float4* out = d->dn.filter[0].p;
-    if ((rc = FilterPasses(ctx, f, p, out)) != CGPT_OK) return rc;
-    if ((rc = ReadBack(ctx, d, n, out, dst_rgba, dst_pixels)) != CGPT_OK) return rc;
-    StoreTemporalKey(d, camera, key, demodulate);
-    return CGPT_OK;
-}
-
 int CheckVarianceParams(cgpt_ctx* ctx, const cgpt_variance_params& v)
 {
     if (!std::isfinite(v.sigma_luminance) || !(v.sigma_luminance > 0.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "sigma_luminance must be finite and > 0, got %g", v.sigma_luminance);
@@ -804,73 +703,139 @@ int EnsureVarianceBuffers(cgpt_ctx* ctx, cgpt_ctx* d, size_t n, bool temporal)
     return CGPT_OK;
 }
 
-// cgpt_denoise_variance_guided: denoise_prepare, the temporal stage with the moments (flag), variance_estimate, the passes
-int DenoiseVariance(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, const cgpt_denoise_params& p, const cgpt_temporal_params& t,
-                    const cgpt_variance_params& v, const float4* acc, float* dst_rgba, uint32_t* dst_pixels)
+// what runs in front of the passes: temporal_merge; variance_estimate, with variance_pass for atrous_pass
+struct Stages { bool temporal, variance; };
+
+// One filtering call's launches: denoise_prepare, the temporal merge, the variance estimate, the passes (or, iterations = 0, an
+// identity), the read-back.
+//
+// The validity flags, T the temporal stage and V the variance stage of the call:
+//                    cleared before the first launch    set after ReadBack succeeded
+//   temporal_valid   T                                  T, with the temporal key (StoreTemporalKey)
+//   moments_valid    T                                  T and V: cgpt_denoise_temporal moves the colour on without the moments
+//   variance_valid   V                                  V, with variance_frame
+//   guides_valid     EnsureGuides' own; FilterCall clears it when this function fails
+// `have` and `have_moments` are sampled before the clearing.  Ensure*Buffers clear the flag of what they reallocate.  A group's failed
+// gather (FilterCall) clears temporal_valid (T) and variance_valid (V) alone.  cgpt_denoise (neither stage) touches none of the three.
+int RunStages(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, Stages st, const cgpt_denoise_params& p, const cgpt_temporal_params& t,
+              const cgpt_variance_params& v, const float4* acc, float* dst_rgba, uint32_t* dst_pixels)
 {
     cgpt_ctx* d = f.dev;
     const size_t n = (size_t)f.width * f.n_rows;
     const uint32_t key[4] = { f.width, f.height, f.first_row, f.n_rows };
     const uint32_t demodulate = (p.flags & CGPT_DENOISE_DEMODULATE_ALBEDO) ? 1u : 0u;
-    const bool temporal = (v.flags & CGPT_VARIANCE_TEMPORAL) != 0u;
-    const bool have = temporal && HistoryMatches(d, key, demodulate);
+    const uint32_t blocks = (uint32_t)((n + 255u) / 256u), tiles = Tiles(f);
+    const float n_samples = (float)f.num_accumulated;
+    const float inv_normal = (float)(1.0 / ((double)p.sigma_normal * p.sigma_normal));
+    const float inv_position = (float)(1.0 / ((double)p.sigma_position * p.sigma_position));
+    const bool have = st.temporal && HistoryMatches(d, key, demodulate);
     const bool have_moments = have && d->moments_valid;
-    d->variance_valid = false;                                                 // a call that fails from here on leaves no map
-    if (temporal) d->temporal_valid = d->moments_valid = false;                // ... and no history
+    if (st.variance) d->variance_valid = false;                                // a call that fails from here on leaves no map
+    if (st.temporal) d->temporal_valid = d->moments_valid = false;             // ... and no history
     int rc;
     HIP_TRY(ctx, hipSetDevice(d->device));
     if ((rc = EnsureFilterBuffers(ctx, d, n)) != CGPT_OK) return rc;
-    if (temporal && (rc = EnsureHistoryBuffers(ctx, d, n)) != CGPT_OK) return rc;
-    if ((rc = EnsureVarianceBuffers(ctx, d, n, temporal)) != CGPT_OK) return rc;
-    if ((rc = EnsureGuides(ctx, f, camera)) != CGPT_OK) return rc;
-    const uint32_t blocks = (uint32_t)((n + 255u) / 256u);
-    const uint32_t tiles = ((f.width + kTile - 1u) / kTile) * ((f.n_rows + kTile - 1u) / kTile);
-    hipLaunchKernelGGL(denoise_prepare, dim3(blocks), dim3(256), 0, d->stream, acc, d->dn.guide_demod.p, d->dn.filter[0].p, n, (float)f.num_accumulated,
-                       demodulate);
-    HIP_TRY(ctx, hipGetLastError());
-    if (temporal) {
+    if (st.temporal && (rc = EnsureHistoryBuffers(ctx, d, n)) != CGPT_OK) return rc;
+    if (st.variance && (rc = EnsureVarianceBuffers(ctx, d, n, st.temporal)) != CGPT_OK) return rc;
+    float4* const c0 = d->dn.filter[0].p;
+    uint32_t* const pixels = d->dn.filter_pixels.p;
+    if (st.temporal || st.variance || p.iterations != 0) {                     // cgpt_denoise with iterations = 0 needs no guides
+        if ((rc = EnsureGuides(ctx, f, camera)) != CGPT_OK) return rc;
+        hipLaunchKernelGGL(denoise_prepare, dim3(blocks), dim3(256), 0, d->stream, acc, d->dn.guide_demod.p, c0, n, n_samples, demodulate);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (st.temporal) {
         TemporalArgs a{};
         FillTemporalArgs(f, camera, t, demodulate, have, a);
-        a.moments = d->dn.moments[d->temporal_slot].p; a.moments_out = d->dn.moments[d->temporal_slot ^ 1u].p;
-        a.variance = d->dn.variance.p;
-        a.have_moments = have_moments ? 1u : 0u;
-        a.min_history_n = (float)v.min_history_frames * (float)f.num_accumulated;
-        hipLaunchKernelGGL((temporal_merge<false, true>), dim3(tiles), dim3(256), 0, d->stream, a);
+        if (st.variance) {
+            a.moments = d->dn.moments[d->temporal_slot].p; a.moments_out = d->dn.moments[d->temporal_slot ^ 1u].p;
+            a.variance = d->dn.variance.p;
+            a.have_moments = have_moments ? 1u : 0u;
+            a.min_history_n = (float)v.min_history_frames * n_samples;
+            hipLaunchKernelGGL((temporal_merge<false, true>), dim3(tiles), dim3(256), 0, d->stream, a);
+        } else if (p.iterations == 0) hipLaunchKernelGGL(temporal_merge<true>, dim3(tiles), dim3(256), 0, d->stream, a);
+        else hipLaunchKernelGGL(temporal_merge<false>, dim3(tiles), dim3(256), 0, d->stream, a);
         HIP_TRY(ctx, hipGetLastError());
     }
-    VarianceArgs va{};
-    va.color = d->dn.filter[0].p; va.guides = d->dn.guides.p; va.variance = d->dn.variance.p;
-    va.width = f.width; va.n_rows = f.n_rows; va.have_temporal = temporal ? 1u : 0u;
-    va.inv_normal = (float)(1.0 / ((double)p.sigma_normal * p.sigma_normal));
-    va.inv_position = (float)(1.0 / ((double)p.sigma_position * p.sigma_position));
-    hipLaunchKernelGGL(variance_estimate, dim3(tiles), dim3(256), 0, d->stream, va);
-    HIP_TRY(ctx, hipGetLastError());
-    float4* out = d->dn.filter[1].p;
-    if (p.iterations == 0) {                                                   // the unfiltered image: cgpt_denoise's, or the merged c
-        if (temporal) hipLaunchKernelGGL(variance_identity, dim3(blocks), dim3(256), 0, d->stream, d->dn.filter[0].p, d->dn.guide_demod.p, out,
-                                         d->dn.filter_pixels.p, n, demodulate);
-        else hipLaunchKernelGGL(denoise_identity, dim3(blocks), dim3(256), 0, d->stream, acc, out, d->dn.filter_pixels.p, n, (float)f.num_accumulated);
+    if (st.variance) {
+        VarianceArgs a{};
+        a.color = c0; a.guides = d->dn.guides.p; a.variance = d->dn.variance.p;
+        a.width = f.width; a.n_rows = f.n_rows; a.have_temporal = st.temporal ? 1u : 0u;
+        a.inv_normal = inv_normal; a.inv_position = inv_position;
+        hipLaunchKernelGGL(variance_estimate, dim3(tiles), dim3(256), 0, d->stream, a);
         HIP_TRY(ctx, hipGetLastError());
     }
-    for (uint32_t it = 0; it < p.iterations; ++it) {
-        VarPassArgs a;
+    float4* out = c0;                                                          // iterations = 0 behind the temporal stage alone: temporal_merge<true>'s, in place
+    if (p.iterations == 0 && (st.variance || !st.temporal)) {                  // the unfiltered image: the accumulator's, or the merged c
+        if (st.variance) out = d->dn.filter[1].p;                              // filter[0] is variance_estimate's
+        if (st.temporal) hipLaunchKernelGGL(variance_identity, dim3(blocks), dim3(256), 0, d->stream, c0, d->dn.guide_demod.p, out, pixels, n, demodulate);
+        else hipLaunchKernelGGL(denoise_identity, dim3(blocks), dim3(256), 0, d->stream, acc, out, pixels, n, n_samples);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    for (uint32_t it = 0; it < p.iterations; ++it) {                           // from filter[0], ping-pong
+        PassArgs a;
         a.src = d->dn.filter[it & 1u].p;
         a.dst = out = d->dn.filter[(it + 1u) & 1u].p;
-        a.pixels = d->dn.filter_pixels.p;
+        a.pixels = pixels;
         a.guides = d->dn.guides.p; a.demod = d->dn.guide_demod.p;
         a.width = f.width; a.n_rows = f.n_rows; a.step = 1u << it; a.demodulate = demodulate;
-        a.sigma_luminance = v.sigma_luminance; a.inv_normal = va.inv_normal; a.inv_position = va.inv_position;
-        if (it + 1u == p.iterations) hipLaunchKernelGGL(variance_pass<true>, dim3(tiles), dim3(256), 0, d->stream, a);
-        else hipLaunchKernelGGL(variance_pass<false>, dim3(tiles), dim3(256), 0, d->stream, a);
+        const double sc = (double)p.sigma_color / (double)(1u << it);       // sigma_c 2^-i
+        a.color_scale = st.variance ? v.sigma_luminance : (float)(1.0 / (sc * sc));
+        a.inv_normal = inv_normal; a.inv_position = inv_position;
+        const bool last = it + 1u == p.iterations;
+        if (st.variance) hipLaunchKernelGGL((last ? variance_pass<true> : variance_pass<false>), dim3(tiles), dim3(256), 0, d->stream, VarPassArgs{ a });
+        else hipLaunchKernelGGL((last ? atrous_pass<true> : atrous_pass<false>), dim3(tiles), dim3(256), 0, d->stream, a);
         HIP_TRY(ctx, hipGetLastError());
     }
     if ((rc = ReadBack(ctx, d, n, out, dst_rgba, dst_pixels)) != CGPT_OK) return rc;
-    if (temporal) {
+    if (st.temporal) {
         StoreTemporalKey(d, camera, key, demodulate);
-        d->moments_valid = true;
+        d->moments_valid = st.variance;
     }
-    memcpy(d->variance_frame, key, sizeof(key));
-    d->variance_valid = true;
+    if (st.variance) {
+        memcpy(d->variance_frame, key, sizeof(key));
+        d->variance_valid = true;
+    }
+    return CGPT_OK;
+}
+
+// The three filtering calls.  Refused, in this order: no context; the frame (ResolveFrame); `params`; with want.variance
+// (cgpt_denoise_variance_guided) `variance`, whose CGPT_VARIANCE_TEMPORAL then decides the temporal stage; `temporal`, read only with
+// that stage; the output buffers.  A NULL parameter block is its defaults.  Then a group's frame is gathered and the stages run.
+int FilterCall(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_params* params, const cgpt_temporal_params* temporal,
+               const cgpt_variance_params* variance, Stages want, float* dst_rgba, size_t n_floats, uint32_t* dst_pixels, size_t n_pixels)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    Frame f;
+    int rc = ResolveFrame(ctx, true, camera, f);
+    if (rc != CGPT_OK) return rc;
+    const cgpt_denoise_params p = params ? *params : kDefaults;
+    if ((rc = CheckParams(ctx, p)) != CGPT_OK) return rc;
+    const cgpt_variance_params v = want.variance && variance ? *variance : kVarianceDefaults;
+    if (want.variance && (rc = CheckVarianceParams(ctx, v)) != CGPT_OK) return rc;
+    const Stages st = { want.variance ? (v.flags & CGPT_VARIANCE_TEMPORAL) != 0u : want.temporal, want.variance };
+    const cgpt_temporal_params t = st.temporal && temporal ? *temporal : kTemporalDefaults;
+    if ((rc = CheckTemporalParams(ctx, t)) != CGPT_OK) return rc;
+    const size_t n = (size_t)f.width * f.n_rows;
+    if (!dst_rgba && !dst_pixels) return CtxFail(ctx, CGPT_ERR_INVALID, "both outputs are null");
+    if (dst_rgba && n_floats != 4 * n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats (4 per pixel)", 4 * n);
+    if (dst_pixels && n_pixels != n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu pixels", n);
+    const float4* acc = ctx->fb.accumulator.p;
+    if (ctx->group && (rc = GroupGatherUncounted(ctx, &acc)) != CGPT_OK) {
+        if (st.variance) f.dev->variance_valid = false;
+        if (st.temporal) f.dev->temporal_valid = false;
+        return rc;
+    }
+    if ((rc = RunStages(ctx, f, camera, st, p, t, v, acc, dst_rgba, dst_pixels)) != CGPT_OK) f.dev->guides_valid = false;
+    return rc;
+}
+
+// set the device, copy, wait: the tail of the read-outs
+int CopyToHost(cgpt_ctx* ctx, cgpt_ctx* d, void* dst, const void* src, size_t bytes)
+{
+    HIP_TRY(ctx, hipSetDevice(d->device));
+    HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(d->stream));
     return CGPT_OK;
 }
 
@@ -913,72 +878,19 @@ int cgpt_read_guides(cgpt_ctx* ctx, const cgpt_camera* camera, float* dst, size_
 int cgpt_denoise(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_params* params, float* dst_rgba, size_t n_floats,
                  uint32_t* dst_pixels, size_t n_pixels)
 {
-    if (!ctx) return CGPT_ERR_INVALID;
-    Frame f;
-    int rc = ResolveFrame(ctx, true, camera, f);
-    if (rc != CGPT_OK) return rc;
-    const cgpt_denoise_params p = params ? *params : kDefaults;
-    if ((rc = CheckParams(ctx, p)) != CGPT_OK) return rc;
-    const size_t n = (size_t)f.width * f.n_rows;
-    if (!dst_rgba && !dst_pixels) return CtxFail(ctx, CGPT_ERR_INVALID, "both outputs are null");
-    if (dst_rgba && n_floats != 4 * n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats (4 per pixel)", 4 * n);
-    if (dst_pixels && n_pixels != n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu pixels", n);
-    const float4* acc = ctx->fb.accumulator.p;
-    if (ctx->group && (rc = GroupGatherUncounted(ctx, &acc)) != CGPT_OK) return rc;
-    rc = Denoise(ctx, f, camera, p, acc, dst_rgba, dst_pixels);
-    if (rc != CGPT_OK) f.dev->guides_valid = false;
-    return rc;
+    return FilterCall(ctx, camera, params, nullptr, nullptr, Stages{ false, false }, dst_rgba, n_floats, dst_pixels, n_pixels);
 }
 
 int cgpt_denoise_temporal(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_params* params, const cgpt_temporal_params* temporal,
                           float* dst_rgba, size_t n_floats, uint32_t* dst_pixels, size_t n_pixels)
 {
-    if (!ctx) return CGPT_ERR_INVALID;
-    Frame f;
-    int rc = ResolveFrame(ctx, true, camera, f);
-    if (rc != CGPT_OK) return rc;
-    const cgpt_denoise_params p = params ? *params : kDefaults;
-    if ((rc = CheckParams(ctx, p)) != CGPT_OK) return rc;
-    const cgpt_temporal_params t = temporal ? *temporal : kTemporalDefaults;
-    if ((rc = CheckTemporalParams(ctx, t)) != CGPT_OK) return rc;
-    const size_t n = (size_t)f.width * f.n_rows;
-    if (!dst_rgba && !dst_pixels) return CtxFail(ctx, CGPT_ERR_INVALID, "both outputs are null");
-    if (dst_rgba && n_floats != 4 * n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats (4 per pixel)", 4 * n);
-    if (dst_pixels && n_pixels != n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu pixels", n);
-    const float4* acc = ctx->fb.accumulator.p;
-    if (ctx->group && (rc = GroupGatherUncounted(ctx, &acc)) != CGPT_OK) { f.dev->temporal_valid = false; return rc; }
-    rc = DenoiseTemporal(ctx, f, camera, p, t, acc, dst_rgba, dst_pixels);
-    if (rc != CGPT_OK) f.dev->guides_valid = false;
-    return rc;
+    return FilterCall(ctx, camera, params, temporal, nullptr, Stages{ true, false }, dst_rgba, n_floats, dst_pixels, n_pixels);
 }
 
 int cgpt_denoise_variance_guided(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_params* params, const cgpt_temporal_params* temporal,
                                  const cgpt_variance_params* variance, float* dst_rgba, size_t n_floats, uint32_t* dst_pixels, size_t n_pixels)
 {
-    if (!ctx) return CGPT_ERR_INVALID;
-    Frame f;
-    int rc = ResolveFrame(ctx, true, camera, f);
-    if (rc != CGPT_OK) return rc;
-    const cgpt_denoise_params p = params ? *params : kDefaults;
-    if ((rc = CheckParams(ctx, p)) != CGPT_OK) return rc;
-    const cgpt_variance_params v = variance ? *variance : kVarianceDefaults;
-    if ((rc = CheckVarianceParams(ctx, v)) != CGPT_OK) return rc;
-    const bool with_temporal = (v.flags & CGPT_VARIANCE_TEMPORAL) != 0u;
-    const cgpt_temporal_params t = with_temporal && temporal ? *temporal : kTemporalDefaults;   // read only with the flag
-    if ((rc = CheckTemporalParams(ctx, t)) != CGPT_OK) return rc;
-    const size_t n = (size_t)f.width * f.n_rows;
-    if (!dst_rgba && !dst_pixels) return CtxFail(ctx, CGPT_ERR_INVALID, "both outputs are null");
-    if (dst_rgba && n_floats != 4 * n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats (4 per pixel)", 4 * n);
-    if (dst_pixels && n_pixels != n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu pixels", n);
-    const float4* acc = ctx->fb.accumulator.p;
-    if (ctx->group && (rc = GroupGatherUncounted(ctx, &acc)) != CGPT_OK) {
-        f.dev->variance_valid = false;
-        if (with_temporal) f.dev->temporal_valid = false;
-        return rc;
-    }
-    rc = DenoiseVariance(ctx, f, camera, p, t, v, acc, dst_rgba, dst_pixels);
-    if (rc != CGPT_OK) f.dev->guides_valid = false;
-    return rc;
+    return FilterCall(ctx, camera, params, temporal, variance, Stages{ false, true }, dst_rgba, n_floats, dst_pixels, n_pixels);   // temporal: by the flag
 }
 
 int cgpt_read_variance(cgpt_ctx* ctx, float* dst, size_t n_floats)
@@ -996,10 +908,7 @@ int cgpt_read_variance(cgpt_ctx* ctx, float* dst, size_t n_floats)
         return CtxFail(ctx, CGPT_ERR_INVALID, "no variance map: no cgpt_denoise_variance_guided call succeeded for this band");
     const size_t n = (size_t)key[0] * key[3];
     if (!dst || n_floats != n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats (1 per pixel)", n);
-    HIP_TRY(ctx, hipSetDevice(d->device));
-    HIP_TRY(ctx, hipMemcpyAsync(dst, d->dn.variance.p, n * sizeof(float), hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(d->stream));
-    return CGPT_OK;
+    return CopyToHost(ctx, d, dst, d->dn.variance.p, n * sizeof(float));
 }
 
 int cgpt_temporal_reset(cgpt_ctx* ctx)
@@ -1018,10 +927,7 @@ int cgpt_read_temporal_history(cgpt_ctx* ctx, float* dst, size_t n_floats)
     if (!d->temporal_valid || d->temporal_generation != d->scene_generation) return CtxFail(ctx, CGPT_ERR_INVALID, "no temporal history");
     const size_t n = (size_t)d->temporal_frame[0] * d->temporal_frame[3];
     if (!dst || n_floats != 4 * n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats (4 per pixel)", 4 * n);
-    HIP_TRY(ctx, hipSetDevice(d->device));
-    HIP_TRY(ctx, hipMemcpyAsync(dst, d->dn.history[d->temporal_slot].p, n * sizeof(float4), hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(d->stream));
-    return CGPT_OK;
+    return CopyToHost(ctx, d, dst, d->dn.history[d->temporal_slot].p, n * sizeof(float4));
 }
 
 }  // extern "C"

@@ -326,6 +326,44 @@ def test_nothing_else_moves_and_the_other_denoisers_are_unchanged(pairs, group):
         r.close()
 
 
+def test_interleaved_calls_equal_calls_made_alone():
+    """The three filtering calls share a context's buffers and validity flags: on one context (A) they are interleaved -- D cgpt_denoise,
+    T cgpt_denoise_temporal, V cgpt_denoise_variance_guided, VT with the temporal flag -- and every call's output, variance map and
+    colour history must be the bytes of the same call where only the history's calls are made (B: A's T and VT calls) or only the
+    others (C: A's D and V calls).  37x21: partial tiles both ways and step-2 taps outside the band; the diffuse reference layout."""
+    w, h, spp = 37, 21, 2
+    _, s = reference_layout_pair(*standin_mesh(2), 1, aspect=w / h)
+    cam = s.camera()
+    a, b, c = new_renderer(s), new_renderer(s), new_renderer(s)
+    try:
+        a.render(w, h, spp, seed=SEED, camera=cam)
+        acc = a.accumulator()
+        for q in (a, b, c):
+            q.load_accumulator(acc, spp, w, h)
+        calls = {"D": lambda q, it: q.denoise(iterations=it, camera=cam),
+                 "T": lambda q, it: q.denoise_temporal(iterations=it, camera=cam),
+                 "V": lambda q, it: q.denoise_variance_guided(iterations=it, camera=cam),
+                 "VT": lambda q, it: q.denoise_variance_guided(iterations=it, temporal=True, min_history_frames=2, camera=cam)}
+
+        def state(q, kind, it):
+            out = list(calls[kind](q, it))
+            if kind in ("V", "VT"):
+                out.append(q.variance())
+            if kind in ("T", "VT"):
+                out.append(q.temporal_history())
+            return [bits(x).copy() for x in out]
+
+        for k, kind in enumerate(("T", "D", "V", "T", "V", "D", "VT", "D", "V", "VT", "T", "VT")):
+            it = 2 * (k % 2)
+            got, want = state(a, kind, it), state(b if kind in ("T", "VT") else c, kind, it)
+            assert len(got) == len(want) >= 2
+            for x, y in zip(got, want):
+                assert np.array_equal(x, y), f"call {k} ({kind}, {it} iterations)"
+    finally:
+        for q in (a, b, c):
+            q.close()
+
+
 # ---- 5. refusals ----------------------------------------------------------------------------------------------------------------------
 
 def raw_call(r, cam, params, temporal, variance, rgba_n=None, px_n=None, rgba=True, px=True):
