@@ -140,6 +140,12 @@ class SceneLayoutView(C.Structure):
                 ("obj_xform", _fp), ("n_obj_xform", C.c_size_t)]
 
 
+class SceneFootprint(C.Structure):
+    """cgpt_scene_footprint"""
+    _fields_ = [("device_bytes", C.c_uint64), ("n_objects", C.c_uint32), ("n_mesh_objects", C.c_uint32), ("n_mesh_copies", C.c_uint32),
+                ("n_leaf_records", C.c_uint32), ("n_pair_records", C.c_uint32), ("n_orig_triangles", C.c_uint32)]
+
+
 class TopLevelView(C.Structure):
     """cgpth_top_level_view: n_nodes records of 8 floats {lo.xyz, bits(skip) | hi.xyz, bits(object)}, n_entry node indices."""
     _fields_ = [("nodes", _fp), ("n_nodes", C.c_size_t), ("entry", _up), ("n_entry", C.c_size_t)]
@@ -156,6 +162,8 @@ PROTOTYPES = {
     "cgpt_set_nee_candidates": (C.c_int, [_vp, C.c_uint32]),
     "cgpt_set_top_level": (C.c_int, [_vp, C.c_uint32]),
     "cgpt_scene_upload": (C.c_int, [_vp, C.POINTER(SceneDesc)]),
+    "cgpt_scene_upload_instanced": (C.c_int, [_vp, C.POINTER(SceneDesc)]),
+    "cgpt_get_scene_footprint": (C.c_int, [_vp, C.POINTER(SceneFootprint)]),
     "cgpt_scene_update_materials": (C.c_int, [_vp, C.POINTER(Material), C.c_uint32]),
     "cgpt_scene_update_roughness": (C.c_int, [_vp, _fp, C.c_uint32]),
     "cgpt_scene_update_transmission_roughness": (C.c_int, [_vp, _fp, C.c_uint32]),
@@ -215,6 +223,7 @@ PROTOTYPES = {
     "cgpth_scene_set_transmission_roughness": (C.c_int, [_vp, C.c_uint32, C.c_float]),
     "cgpth_scene_get_transmission_roughness": (C.c_int, [_vp, _fp, C.c_uint32]),
     "cgpth_scene_add_mesh": (C.c_int, [_vp, _vp, C.c_uint32, C.c_int]),
+    "cgpth_scene_add_instance": (C.c_int, [_vp, C.c_uint32, C.c_uint32]),
     "cgpth_scene_add_mesh_device_built": (C.c_int, [_vp, _vp, C.c_uint32, _vp]),
     "cgpth_scene_add_mesh_device_built_ex": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_int]),
     "cgpth_scene_rebuild_bvh_device": (C.c_int, [_vp, C.c_uint32, C.c_int, _vp]),
@@ -244,6 +253,7 @@ PROTOTYPES = {
     "cgpth_shade_item_blocks": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "cgpth_shade_segment_blocks": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "cgpth_scene_layout": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(SceneLayoutView)]),
+    "cgpth_scene_layout_instanced": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(SceneLayoutView)]),
     "cgpth_scene_layout_transformed": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(C.c_float), C.c_uint32, C.POINTER(SceneLayoutView)]),
     "cgpth_scene_permute_objects": (C.c_int, [_vp, _up, C.c_uint32]),
     "cgpth_top_level": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(TopLevelView)]),

@@ -73,7 +73,8 @@ int UploadArray(cgpt_ctx* ctx, DevBuf<T>& dst, const std::vector<T>& src)   // a
 void FreeScene(cgpt_ctx* ctx)
 {
     ctx->sb = SceneBuffers{};
-    ctx->h_objects.clear(); ctx->refit_objects.clear(); ctx->record_perm.clear();
+    ctx->h_objects.clear(); ctx->refit_objects.clear(); ctx->record_perm.clear(); ctx->mesh_group.clear();
+    ctx->footprint = cgpt_scene_footprint{};
     ctx->h_roughness.clear(); ctx->h_transmission_roughness.clear(); ctx->h_materials.clear(); ctx->h_lights.clear();
     ctx->features = SceneFeatures{};
     ctx->top_state = TopLevelState{};
@@ -323,19 +324,34 @@ int cgpt_set_top_level(cgpt_ctx* ctx, uint32_t mode)
     return CGPT_OK;
 }
 
-int cgpt_scene_upload(cgpt_ctx* ctx, const cgpt_scene_desc* scene)
+// cgpt_scene_upload (instanced false: every object laid out) and cgpt_scene_upload_instanced (true: one copy per mesh group): one body, so
+// the two validate, refuse, reset and keep alike
+static int SceneUpload(cgpt_ctx* ctx, const cgpt_scene_desc* scene, bool instanced, const char* func)
 {
     if (!ctx) return CGPT_ERR_INVALID;
-    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupSceneUpload(ctx, scene); });
+    if (ctx->group) return Guarded(ctx, func, [&] { return GroupSceneUpload(ctx, scene, instanced); });
     if (!scene) return CtxFail(ctx, CGPT_ERR_INVALID, "scene is null");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->scene_generation++;                                                   // the denoiser's guides are stale (denoise.hip)
     return Guarded(ctx, "scene upload", [&] {                                  // the re-layout allocates host vectors
         SceneLayout layout;
-        const int rc = LayoutScene(*scene, layout, ctx->error);
+        const int rc = LayoutScene(*scene, layout, ctx->error, instanced);
         return rc != CGPT_OK ? rc : SceneInstall(ctx, layout);
     });
+}
+
+int cgpt_scene_upload(cgpt_ctx* ctx, const cgpt_scene_desc* scene) { return SceneUpload(ctx, scene, false, __func__); }
+
+int cgpt_scene_upload_instanced(cgpt_ctx* ctx, const cgpt_scene_desc* scene) { return SceneUpload(ctx, scene, true, __func__); }
+
+int cgpt_get_scene_footprint(cgpt_ctx* ctx, cgpt_scene_footprint* out)
+{
+    if (!ctx || !out) return CGPT_ERR_INVALID;
+    if (ctx->group) return GroupForwarded(ctx, cgpt_get_scene_footprint(GroupFirstMember(ctx), out));   // every device holds the same arrays
+    if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
+    *out = ctx->footprint;
+    return CGPT_OK;
 }
 
 int cgpt_scene_update_materials(cgpt_ctx* ctx, const cgpt_material* materials, uint32_t n_materials)
@@ -422,6 +438,7 @@ int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout)
     // obj_trace: the 2 n trace records, then the 3 n transform records (device_scene.h)
     const size_t n_obj = layout.objects.size();
     if (layout.obj_trace.size() != 2 * n_obj || layout.obj_xform.size() != 3 * n_obj) return CtxFail(ctx, CGPT_ERR_INVALID, "layout: %zu trace and %zu transform records for %zu objects", layout.obj_trace.size(), layout.obj_xform.size(), n_obj);
+    if (layout.mesh_group.size() != n_obj) return CtxFail(ctx, CGPT_ERR_INVALID, "layout: mesh groups of %zu objects", layout.mesh_group.size());
     if (layout.top_state.local_box.size() != 6 * n_obj || layout.top_state.xform.size() != 12 * n_obj) return CtxFail(ctx, CGPT_ERR_INVALID, "layout: top-level state of %zu objects", layout.top_state.local_box.size() / 6);
     HIP_TRY(ctx, ctx->sb.obj_trace.Alloc(n_obj ? 5 * n_obj + TopLevelFloat4s(n_obj) : 1));   // ... then the top-level tree (written while cgpt_set_top_level is 1)
     if (n_obj) {
@@ -434,7 +451,18 @@ int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout)
     ctx->h_roughness.assign(layout.n_materials, 0.0f); ctx->h_transmission_roughness.assign(layout.n_materials, 0.0f); ctx->h_materials = layout.materials;
     ctx->h_lights = layout.lights;                                             // FreeScene cleared the features: an upload resets every roughness, smooth-normal flag and transform (LayoutScene writes 0 and the identity)
     ctx->top_state = layout.top_state;
+    ctx->mesh_group = layout.mesh_group;
     HIP_TRY(ctx, WriteTopLevel(ctx, ctx->h_objects, ctx->top_state));          // the mode is context state: an upload keeps it
+
+    cgpt_scene_footprint& fp = ctx->footprint;
+    const SceneBuffers& sb = ctx->sb;
+    fp = cgpt_scene_footprint{};
+    fp.device_bytes = sizeof(float4) * (uint64_t)(sb.node_pairs.n + sb.tri_leaf.n + sb.tri_orig.n + sb.tri_normal.n + sb.materials.n + sb.obj_trace.n) +
+                      sizeof(DevObject) * (uint64_t)sb.objects.n + sizeof(uint32_t) * (uint64_t)(sb.lights.n + sb.refit_levels.n);
+    fp.n_objects = (uint32_t)n_obj;
+    for (size_t i = 0; i < n_obj; ++i)
+        if (layout.objects[i].kind == CGPT_OBJECT_MESH) { fp.n_mesh_objects++; if (layout.mesh_group[i] == i) fp.n_mesh_copies++; }
+    fp.n_leaf_records = (uint32_t)(layout.tri_leaf.size() / 3); fp.n_pair_records = layout.n_pair_records; fp.n_orig_triangles = (uint32_t)n_tris_total;
 
     ctx->scene.node_pairs = ctx->sb.node_pairs.p; ctx->scene.tri_leaf = ctx->sb.tri_leaf.p; ctx->scene.tri_orig = ctx->sb.tri_orig.p; ctx->scene.tri_normal = ctx->sb.tri_normal.p;
     ctx->scene.materials = ctx->sb.materials.p; ctx->scene.objects = ctx->sb.objects.p; ctx->scene.obj_trace = ctx->sb.obj_trace.p; ctx->scene.lights = ctx->sb.lights.p;

@@ -78,6 +78,11 @@ struct cgpt_ctx {
     std::vector<cgpt::DevObject> h_objects;
     std::vector<cgpt::RefitObject> refit_objects;
     std::vector<uint32_t> record_perm;            // record index in the reference's depth-first order -> index in node_pairs
+    // mesh instancing (cgpt_scene_upload_instanced): SceneLayout::mesh_group of the installed layout -- the objects that share object i's
+    // one device copy are those with mesh_group[j] == mesh_group[i]; the identity after cgpt_scene_upload -- and what
+    // cgpt_get_scene_footprint reports, filled by SceneInstall (no edit changes it)
+    std::vector<uint32_t> mesh_group;
+    cgpt_scene_footprint footprint{};
 
     // framebuffer band
     cgpt::FrameBuffers fb;
@@ -166,7 +171,7 @@ hipError_t LaunchPackPixels(const float4* accumulator, uint32_t* pixels, size_t 
 // multi_gpu.hip: the group behind a multi-device context
 int GroupCreate(const int* device_ids, int n_devices, uint32_t flags, cgpt_ctx** out);
 void GroupDestroy(cgpt_ctx* ctx);
-int GroupSceneUpload(cgpt_ctx* ctx, const cgpt_scene_desc* scene);
+int GroupSceneUpload(cgpt_ctx* ctx, const cgpt_scene_desc* scene, bool instanced);
 int GroupUpdateMaterials(cgpt_ctx* ctx, const cgpt_material* materials, uint32_t n);
 int GroupUpdateRoughness(cgpt_ctx* ctx, const float* roughness, uint32_t n);
 int GroupUpdateTransmissionRoughness(cgpt_ctx* ctx, const float* roughness, uint32_t n);

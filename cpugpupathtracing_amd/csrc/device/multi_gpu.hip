@@ -317,13 +317,13 @@ void GroupDestroy(cgpt_ctx* ctx)
     ctx->group = nullptr;
 }
 
-int GroupSceneUpload(cgpt_ctx* ctx, const cgpt_scene_desc* scene)
+int GroupSceneUpload(cgpt_ctx* ctx, const cgpt_scene_desc* scene, bool instanced)
 {
     // laid out once (a refusal touches no member's scene), installed on every member in rank order as its cgpt_scene_upload would
     cgpt_ctx* first = ctx->group->members[0];
     if (!scene) return Propagate(ctx, first, CtxFail(first, CGPT_ERR_INVALID, "scene is null"));
     SceneLayout layout;
-    int rc = LayoutScene(*scene, layout, first->error);
+    int rc = LayoutScene(*scene, layout, first->error, instanced);
     if (rc != CGPT_OK) return Propagate(ctx, first, rc);
     for (cgpt_ctx* m : ctx->group->members) {
         if ((rc = cgpt_synchronize(m)) != CGPT_OK) return Propagate(ctx, m, rc);   // selects the member's device and drains its stream

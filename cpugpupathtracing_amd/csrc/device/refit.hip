@@ -15,6 +15,8 @@
 //     synchronisation).  The codes float4 is not written.
 // total_area is the sequential float sum of GetTriangleArea in original order (ref: BVH.cpp:22), summed on the host while the input is
 // read, and written into the object's DevObject (mesh-light sampling reads it).
+// After cgpt_scene_upload_instanced the objects of a mesh group share the one copy these passes edit: the refit goes through any member's
+// RefitObject (they are equal), and the area and the top-level box, which are per object, are written for every member.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -155,9 +157,15 @@ int RefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles,
     if (d.kind == CGPT_OBJECT_MESH)
         for (uint32_t i = 0; i < n_tris; ++i) area += HostTriangleArea(triangles[i]);
 
-    // the top-level tree's box of this object: the min / max of the new vertex positions, which is what the refit's root bounds come to
+    // the top-level tree's box of this object: the min / max of the new vertex positions, which is what the refit's root bounds come to;
+    // every object of its mesh group moves with it (ctx->mesh_group: obj_index alone after a plain upload)
     TopLevelState top = ctx->top_state;
+    std::vector<uint32_t> members;
+    for (uint32_t j = 0; j < ctx->mesh_group.size(); ++j)
+        if (ctx->mesh_group[j] == ctx->mesh_group[obj_index]) members.push_back(j);
     TriangleBounds(triangles, n_tris, top.local_box.data() + 6 * (size_t)obj_index);
+    for (const uint32_t j : members)
+        if (j != obj_index) memcpy(top.local_box.data() + 6 * (size_t)j, top.local_box.data() + 6 * (size_t)obj_index, 24);
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -177,8 +185,10 @@ int RefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles,
         REFIT_HIP_WRITING(ctx, hipGetLastError());
     }
     if (d.kind == CGPT_OBJECT_MESH) {
-        d.total_area = area;
-        REFIT_HIP_WRITING(ctx, hipMemcpyAsync(&ctx->sb.objects.p[obj_index].total_area, &d.total_area, sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        for (const uint32_t j : members) {
+            ctx->h_objects[j].total_area = area;
+            REFIT_HIP_WRITING(ctx, hipMemcpyAsync(&ctx->sb.objects.p[j].total_area, &ctx->h_objects[j].total_area, sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        }
     }
     REFIT_HIP_WRITING(ctx, hipStreamSynchronize(ctx->stream));
     REFIT_HIP_WRITING(ctx, WriteTopLevel(ctx, ctx->h_objects, top));

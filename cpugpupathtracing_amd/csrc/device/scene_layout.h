@@ -45,12 +45,18 @@ struct SceneLayout {
     // host bookkeeping of the in-place edits
     std::vector<RefitObject> refit_objects;
     std::vector<uint32_t> record_perm;         // record index in the reference's depth-first order -> index in node_pairs
+    // mesh instancing (cgpt_scene_upload_instanced): per object the first object laid out with the same four slice words,
+    // the object itself where it shares with nobody -- every object of the plain layout.  The members of a group hold equal root_code,
+    // tri_base, n_tris and RefitObject; everything else of an object is its own
+    std::vector<uint32_t> mesh_group;
     uint32_t stack_depth = 0, n_top_records = 0, n_pair_records = 0, n_small_tris = 0, n_materials = 0;
 };
 
 // Validates everything a kernel will index with (a malformed tree must fail here, not fault on the GPU) and fills `out`.
 // CGPT_OK, or CGPT_ERR_INVALID / CGPT_ERR_UNSUPPORTED with the reason in `error`; `out` is only meaningful on CGPT_OK.
-int LayoutScene(const cgpt_scene_desc& sd, SceneLayout& out, std::string& error);
+// instanced: mesh objects that name the same node and triangle slices are laid out once (SceneLayout::mesh_group); false lays out every
+// object, as cgpt_scene_upload always has.
+int LayoutScene(const cgpt_scene_desc& sd, SceneLayout& out, std::string& error, bool instanced = false);
 
 inline float AsFloat(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 

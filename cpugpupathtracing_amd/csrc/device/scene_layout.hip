@@ -6,6 +6,8 @@
 #include <cstdarg>
 #include <cstdio>
 #include <exception>
+#include <map>
+#include <tuple>
 
 #include "cpugpupt_host.h"
 
@@ -27,21 +29,38 @@ uint32_t LeafRecords(const cgpt_object& o)                                    //
     return o.kind == CGPT_OBJECT_MESH ? o.tri_count : (o.kind == CGPT_OBJECT_TRIANGLE ? 1u : 0u);
 }
 
-// leaf-record order (device_scene.h): the triangles of the small meshes first, then the rest in object order.  Returns the first
-// tri_leaf record of every object, sets n_small_tris and returns the number of records in `total`.
-std::vector<uint32_t> LeafRecordOrder(const cgpt_scene_desc& sd, uint32_t& n_small_tris, uint64_t& total)
+// The mesh groups of an instanced layout (cgpt_scene_upload_instanced): mesh objects whose four slice words are all equal share one copy,
+// laid out from the first of them.  group[oi] is that first object, oi itself for every object that shares with nobody -- which is every
+// object of the plain layout.  Slices that overlap only in part are different keys: separate meshes.
+std::vector<uint32_t> MeshGroups(const cgpt_scene_desc& sd, bool instanced)
+{
+    std::vector<uint32_t> group(sd.n_objects);
+    std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>, uint32_t> first;
+    for (uint32_t oi = 0; oi < sd.n_objects; ++oi) {
+        const cgpt_object& o = sd.objects[oi];
+        group[oi] = oi;
+        if (instanced && o.kind == CGPT_OBJECT_MESH) group[oi] = first.emplace(std::make_tuple(o.node_offset, o.node_count, o.tri_offset, o.tri_count), oi).first->second;
+    }
+    return group;
+}
+
+// leaf-record order (device_scene.h): the triangles of the small meshes first, then the rest in object order; a mesh group counts once,
+// at its first member.  Returns the first tri_leaf record of every object, sets n_small_tris and returns the number of records in `total`.
+std::vector<uint32_t> LeafRecordOrder(const cgpt_scene_desc& sd, const std::vector<uint32_t>& group, uint32_t& n_small_tris, uint64_t& total)
 {
     std::vector<uint32_t> leaf_base_of(sd.n_objects, 0);
     std::vector<uint8_t> small(sd.n_objects, 0);
     n_small_tris = 0; total = 0;
     for (uint32_t oi = 0; oi < sd.n_objects; ++oi) {
+        if (group[oi] != oi) continue;
         const uint32_t n = LeafRecords(sd.objects[oi]);
         total += n;
         if (n > 0 && n <= kSmallMeshTris && n_small_tris + n <= kLdsTrisMax) { small[oi] = 1; leaf_base_of[oi] = n_small_tris; n_small_tris += n; }
     }
     uint32_t next = n_small_tris;
     for (uint32_t oi = 0; oi < sd.n_objects; ++oi)
-        if (!small[oi]) { leaf_base_of[oi] = next; next += LeafRecords(sd.objects[oi]); }
+        if (group[oi] == oi && !small[oi]) { leaf_base_of[oi] = next; next += LeafRecords(sd.objects[oi]); }
+    for (uint32_t oi = 0; oi < sd.n_objects; ++oi) leaf_base_of[oi] = leaf_base_of[group[oi]];
     return leaf_base_of;
 }
 
@@ -152,6 +171,7 @@ bool HasRecords(const DevObject& d) { return d.kind == CGPT_OBJECT_MESH && (d.ro
 // record order (device_scene.h: "record order").  The reference allocates nodes depth-first; a record's index is only a name here
 // (codes are rewritten), so the records are renumbered: the first kTopRecords in breadth-first order over all meshes (the top of
 // every tree, which every ray walks: the trace kernel mirrors records [0, n_top_records) in LDS), the rest in the reference's order.
+// The breadth-first queue starts with one root per mesh group: the members of a group hold the same root, and a record is queued once.
 void RenumberRecords(SceneLayout& out)
 {
     std::vector<float4>& pairs = out.node_pairs;
@@ -159,8 +179,8 @@ void RenumberRecords(SceneLayout& out)
     std::vector<uint32_t>& perm = out.record_perm;
     perm.assign(n_records, 0xFFFFFFFFu);
     std::vector<uint32_t> bfs; bfs.reserve(n_records);
-    for (const DevObject& d : out.objects)
-        if (HasRecords(d)) bfs.push_back(d.root_code);
+    for (size_t oi = 0; oi < out.objects.size(); ++oi)
+        if (out.mesh_group[oi] == oi && HasRecords(out.objects[oi])) bfs.push_back(out.objects[oi].root_code);
     const size_t bfs_limit = std::min<size_t>(n_records, kTopRecords);
     for (size_t head = 0; head < bfs.size() && bfs.size() < n_records; ++head) {
         if (bfs.size() >= bfs_limit + 2 * kTopRecords) break;                  // enough: only the first bfs_limit are used
@@ -190,14 +210,15 @@ void RenumberRecords(SceneLayout& out)
 }
 
 // each mesh's child-pair records grouped by depth, in their final numbering: the refit's bound pass runs one level after the other,
-// deepest first (refit.hip)
+// deepest first (refit.hip).  Once per mesh group: every member carries the group's bases and levels, so a refit through any of them
+// runs over the one copy.
 void GroupRecordsByDepth(SceneLayout& out, const std::vector<uint8_t>& rec_depth)
 {
     std::vector<uint32_t>& levels = out.refit_levels;
     levels.reserve(out.n_pair_records);
     for (size_t oi = 0; oi < out.objects.size(); ++oi) {
         RefitObject& ro = out.refit_objects[oi];
-        if (out.objects[oi].kind != CGPT_OBJECT_MESH || ro.node_count < 3) continue;   // a leaf-rooted mesh has no records
+        if (out.mesh_group[oi] != oi || out.objects[oi].kind != CGPT_OBJECT_MESH || ro.node_count < 3) continue;   // a leaf-rooted mesh has no records
         uint32_t count[66] = { 0 };
         uint32_t n_levels = 0;
         const uint32_t r0 = ro.pair_base, r1 = ro.pair_base + ro.node_count / 2;
@@ -211,19 +232,22 @@ void GroupRecordsByDepth(SceneLayout& out, const std::vector<uint8_t>& rec_depth
         for (uint32_t r = r0; r < r1; ++r)
             if (rec_depth[r] != 0xFF) dst[count[rec_depth[r]]++] = out.record_perm[r];
     }
+    for (size_t oi = 0; oi < out.objects.size(); ++oi)
+        if (out.mesh_group[oi] != oi) out.refit_objects[oi] = out.refit_objects[out.mesh_group[oi]];
 }
 
 }  // namespace
 
-int LayoutScene(const cgpt_scene_desc& sd, SceneLayout& out, std::string& error)
+int LayoutScene(const cgpt_scene_desc& sd, SceneLayout& out, std::string& error, bool instanced)
 {
     out = SceneLayout();
     if (sd.n_objects == 0 || !sd.objects) return Refuse(error, CGPT_ERR_INVALID, "scene has no objects");
     if (sd.n_materials == 0 || !sd.materials) return Refuse(error, CGPT_ERR_INVALID, "scene has no materials");
     if (sd.n_lights && !sd.light_indices) return Refuse(error, CGPT_ERR_INVALID, "light_indices is null");
 
-    uint64_t n_leaf_records = 0;
-    const std::vector<uint32_t> leaf_base_of = LeafRecordOrder(sd, out.n_small_tris, n_leaf_records);
+    out.mesh_group = MeshGroups(sd, instanced);
+    uint64_t n_leaf_records = 0;                                              // laid-out records: a mesh group counts once
+    const std::vector<uint32_t> leaf_base_of = LeafRecordOrder(sd, out.mesh_group, out.n_small_tris, n_leaf_records);
     if (n_leaf_records >= (1u << 26)) return Refuse(error, CGPT_ERR_INVALID, "scene too large: more than 2^26 triangles or inner nodes");
     out.tri_leaf.resize(3 * (size_t)n_leaf_records);
     out.tri_normal12.reserve(2 * (size_t)n_leaf_records);                      // one {n1, n2} pair per leaf record: no regrowth while the objects are laid out
@@ -273,6 +297,13 @@ int LayoutScene(const cgpt_scene_desc& sd, SceneLayout& out, std::string& error)
             d.root_code = kLeafBit | leaf_base; d.tri_base = orig_base; d.n_tris = 1;
             TriangleBounds(&tr, 1, out.top_state.local_box.data() + 6 * (size_t)oi);
             out.refit_objects[oi].tri_count = 1; out.refit_objects[oi].leaf_base = leaf_base;
+        } else if (o.kind == CGPT_OBJECT_MESH && out.mesh_group[oi] != oi) {
+            // an instance: the copy its group's first member laid out (the same four slice words, so the same validation passed)
+            const uint32_t first = out.mesh_group[oi];
+            d.root_code = out.objects[first].root_code; d.tri_base = out.objects[first].tri_base; d.n_tris = out.objects[first].n_tris;
+            d.total_area = o.total_area;
+            out.refit_objects[oi] = out.refit_objects[first];                  // the levels follow in GroupRecordsByDepth
+            memcpy(out.top_state.local_box.data() + 6 * (size_t)oi, out.top_state.local_box.data() + 6 * (size_t)first, 24);
         } else if (o.kind == CGPT_OBJECT_MESH) {
             const int rc = LayoutMesh(sd, oi, leaf_base_of[oi], out, rec_depth, max_tree_depth, error);
             if (rc != CGPT_OK) return rc;
@@ -425,7 +456,7 @@ int LayoutTransforms(const float* object_to_world, uint32_t n_objects, const std
 
 using namespace cgpt;
 
-extern "C" int cgpth_scene_layout_transformed(const cgpt_scene_desc* scene, const float* object_to_world, uint32_t n_objects, cgpth_scene_layout_view* view)
+static int SceneLayoutView(const cgpt_scene_desc* scene, const float* object_to_world, uint32_t n_objects, bool instanced, cgpth_scene_layout_view* view)
 {
     // what the view points into: this thread's last layout and the per-object bookkeeping flattened
     struct Storage { SceneLayout layout; std::vector<uint32_t> leaf_base, pair_base, level_begin, level_offsets, level_offsets_start; };
@@ -433,7 +464,7 @@ extern "C" int cgpth_scene_layout_transformed(const cgpt_scene_desc* scene, cons
     try {
         if (!scene || !view) { HostSetError("null argument"); return CGPT_ERR_INVALID; }
         std::string error;
-        const int rc = LayoutScene(*scene, st.layout, error);
+        const int rc = LayoutScene(*scene, st.layout, error, instanced);
         if (rc != CGPT_OK) { HostSetError(error.c_str()); return rc; }
         if (object_to_world || n_objects) {                                    // what cgpt_scene_update_transforms would install after this upload
             std::vector<uint32_t> flags;
@@ -507,8 +538,10 @@ extern "C" int cgpth_top_level(const cgpt_scene_desc* scene, cgpth_top_level_vie
     return TopLevelCall(view, true, [&](TopLevelStorage& st, std::string& error) {
         st.valid = false;
         if (!scene) return Refuse(error, CGPT_ERR_INVALID, "null argument");
+        // the instanced layout: the boxes are per object and the same under either upload, and a scene whose copies would pass the record
+        // limit (uploaded with cgpt_scene_upload_instanced) still shows its tree
         SceneLayout layout;
-        const int rc = LayoutScene(*scene, layout, error);
+        const int rc = LayoutScene(*scene, layout, error, true);
         if (rc != CGPT_OK) return rc;
         st.objects = layout.objects; st.lights = layout.lights; st.state = layout.top_state; st.valid = true;
         return (int)CGPT_OK;
@@ -549,7 +582,17 @@ extern "C" int cgpth_top_level_primitive(uint32_t obj_index, const cgpt_object* 
     });
 }
 
+extern "C" int cgpth_scene_layout_transformed(const cgpt_scene_desc* scene, const float* object_to_world, uint32_t n_objects, cgpth_scene_layout_view* view)
+{
+    return SceneLayoutView(scene, object_to_world, n_objects, false, view);
+}
+
 extern "C" int cgpth_scene_layout(const cgpt_scene_desc* scene, cgpth_scene_layout_view* view)
 {
-    return cgpth_scene_layout_transformed(scene, nullptr, 0u, view);
+    return SceneLayoutView(scene, nullptr, 0u, false, view);
+}
+
+extern "C" int cgpth_scene_layout_instanced(const cgpt_scene_desc* scene, cgpth_scene_layout_view* view)
+{
+    return SceneLayoutView(scene, nullptr, 0u, true, view);
 }

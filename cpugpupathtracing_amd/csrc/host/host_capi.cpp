@@ -221,6 +221,23 @@ int cgpth_scene_add_mesh(cgpth_scene* scene, const cgpth_mesh* mesh, uint32_t ma
     });
 }
 
+int cgpth_scene_add_instance(cgpth_scene* scene, uint32_t of_obj_index, uint32_t mat_index)
+{
+    return Guarded<int>(-CGPT_ERR_INVALID, [&]() -> int {
+        if (!scene) return -Fail("scene is null");
+        if (of_obj_index >= scene->scene.objects.size())
+            return -Fail("object " + std::to_string(of_obj_index) + " out of range (" + std::to_string(scene->scene.objects.size()) + " objects)");
+        if (!scene->scene.objects[of_obj_index].has_bvh) {
+            const Object& of = scene->scene.objects[of_obj_index];
+            const char* kind = of.kind == CGPT_OBJECT_SPHERE ? "sphere" : of.kind == CGPT_OBJECT_PLANE ? "plane" : "triangle object";
+            return -Fail("object " + std::to_string(of_obj_index) + " is a " + kind + ": only a mesh has instances");
+        }
+        Object instance("mesh instance", scene->scene.objects[of_obj_index], mat_index);   // built first: emplace_back may move the original
+        scene->scene.objects.push_back(std::move(instance));
+        return (int)scene->scene.objects.size() - 1;
+    });
+}
+
 // the device builder behind MeshBVH::BuildWith / RebuildWith: cgpt_bvh_build_ex on ctx; keeps the device's message
 static MeshBVH::TreeBuilder DeviceBuilder(cgpt_ctx* ctx, std::string& device_error)
 {
@@ -259,7 +276,7 @@ int cgpth_scene_rebuild_bvh_device(cgpth_scene* scene, uint32_t obj_index, int b
         if (!scene || !ctx || obj_index >= scene->scene.objects.size() || !scene->scene.objects[obj_index].has_bvh || !ValidOption(build_option))
             return Fail("bad argument to cgpth_scene_rebuild_bvh_device");
         std::string device_error;
-        if (!scene->scene.objects[obj_index].bvh.RebuildWith((MeshBVH::BuildOption)build_option, DeviceBuilder(ctx, device_error)))
+        if (!scene->scene.objects[obj_index].bvh->RebuildWith((MeshBVH::BuildOption)build_option, DeviceBuilder(ctx, device_error)))
             return Fail(device_error.empty() ? std::string("the device returned a malformed tree (the BVH is unchanged)") : "device BVH rebuild failed: " + device_error);
         return CGPT_OK;
     });
@@ -413,7 +430,7 @@ int cgpth_scene_rebuild_bvh(cgpth_scene* scene, uint32_t obj_index, int build_op
     return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
         if (!scene || obj_index >= scene->scene.objects.size() || !scene->scene.objects[obj_index].has_bvh || !ValidOption(build_option))
             return Fail("bad argument to cgpth_scene_rebuild_bvh");
-        if (!scene->scene.objects[obj_index].bvh.Rebuild((MeshBVH::BuildOption)build_option))
+        if (!scene->scene.objects[obj_index].bvh->Rebuild((MeshBVH::BuildOption)build_option))
             return Fail("the binned build needs finite positions of magnitude <= 1e30 (the BVH is unchanged)");
         return CGPT_OK;
     });
@@ -429,10 +446,10 @@ int cgpth_scene_refit_mesh(cgpth_scene* scene, uint32_t obj_index, const cgpt_tr
         if (!o.has_bvh && o.kind != CGPT_OBJECT_TRIANGLE)
             return Fail("object " + std::to_string(obj_index) + " is a " + KindName(o) + ": it has no triangles (update_primitive edits it)");
         if (!triangles) return Fail("triangles is null");
-        const uint32_t n = o.has_bvh ? o.bvh.NumTriangles() : 1u;
+        const uint32_t n = o.has_bvh ? o.bvh->NumTriangles() : 1u;
         if (n_tris != n)
             return Fail("object " + std::to_string(obj_index) + " has " + std::to_string(n) + " triangles, got " + std::to_string(n_tris) + " (a refit keeps the topology)");
-        if (o.has_bvh) { if (!o.bvh.Refit(triangles, n_tris)) return Fail("refit failed"); }
+        if (o.has_bvh) { if (!o.bvh->Refit(triangles, n_tris)) return Fail("refit failed"); }
         else o.triangle = triangles[0];
         return CGPT_OK;
     });
@@ -461,7 +478,7 @@ int cgpth_scene_bvh_info(const cgpth_scene* scene, uint32_t obj_index, cgpth_bvh
 {
     return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
         if (!scene || !out || obj_index >= scene->scene.objects.size() || !scene->scene.objects[obj_index].has_bvh) return Fail("not a mesh object");
-        const MeshBVH& b = scene->scene.objects[obj_index].bvh;
+        const MeshBVH& b = *scene->scene.objects[obj_index].bvh;
         *out = cgpth_bvh_info{};
         out->num_triangles = b.NumTriangles(); out->nodes_used = b.NumNodes(); out->max_depth = b.GetMaxDepth(); out->total_area = b.GetTotalArea();
         for (uint32_t i = 0; i < b.NumNodes(); ++i) {
@@ -476,7 +493,7 @@ int cgpth_scene_bvh_export(const cgpth_scene* scene, uint32_t obj_index, cgpt_bv
 {
     return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
         if (!scene || !nodes || !tri_indices || obj_index >= scene->scene.objects.size() || !scene->scene.objects[obj_index].has_bvh) return Fail("not a mesh object");
-        const MeshBVH& b = scene->scene.objects[obj_index].bvh;
+        const MeshBVH& b = *scene->scene.objects[obj_index].bvh;
         memcpy(nodes, b.Nodes(), sizeof(cgpt_bvh_node) * b.NumNodes());
         memcpy(tri_indices, b.TriIndices(), sizeof(uint32_t) * b.NumTriangles());
         return CGPT_OK;

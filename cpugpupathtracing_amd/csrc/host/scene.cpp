@@ -2,6 +2,7 @@
 #include "scene.h"
 
 #include <cstring>
+#include <map>
 
 namespace cgpt {
 
@@ -45,20 +46,26 @@ bool Camera::Move(float right, float up, float forward)
 cgpt_scene_desc Scene::Flatten(FlatStorage& st) const
 {
     st = FlatStorage{};
+    std::map<const MeshBVH*, size_t> packed;                                 // a shared mesh -> the first object that packed it
     for (const Object& o : objects) {
         cgpt_object d{};
         d.mat_index = o.mat_index;
-        if (o.has_bvh) {
+        if (o.has_bvh && packed.count(o.bvh.get())) {                        // an instance: the owner's slices
+            d = st.objects[packed[o.bvh.get()]];
+            d.mat_index = o.mat_index;
+        } else if (o.has_bvh) {
+            const MeshBVH& bvh = *o.bvh;
+            packed[o.bvh.get()] = st.objects.size();
             d.kind = CGPT_OBJECT_MESH;
             d.node_offset = (uint32_t)st.nodes.size();
-            d.node_count = o.bvh.NumNodes();
+            d.node_count = bvh.NumNodes();
             d.tri_offset = (uint32_t)st.triangles.size();
-            d.tri_count = o.bvh.NumTriangles();
-            d.max_depth = o.bvh.GetMaxDepth();
-            d.total_area = o.bvh.GetTotalArea();
-            st.nodes.insert(st.nodes.end(), o.bvh.Nodes(), o.bvh.Nodes() + d.node_count);
-            st.triangles.insert(st.triangles.end(), o.bvh.Triangles(), o.bvh.Triangles() + d.tri_count);
-            st.tri_indices.insert(st.tri_indices.end(), o.bvh.TriIndices(), o.bvh.TriIndices() + d.tri_count);
+            d.tri_count = bvh.NumTriangles();
+            d.max_depth = bvh.GetMaxDepth();
+            d.total_area = bvh.GetTotalArea();
+            st.nodes.insert(st.nodes.end(), bvh.Nodes(), bvh.Nodes() + d.node_count);
+            st.triangles.insert(st.triangles.end(), bvh.Triangles(), bvh.Triangles() + d.tri_count);
+            st.tri_indices.insert(st.tri_indices.end(), bvh.TriIndices(), bvh.TriIndices() + d.tri_count);
         } else if (o.kind == CGPT_OBJECT_TRIANGLE) {
             d.kind = CGPT_OBJECT_TRIANGLE;                                   // one entry of the scene-wide triangle array
             d.tri_offset = (uint32_t)st.triangles.size();

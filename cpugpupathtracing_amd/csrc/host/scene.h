@@ -6,6 +6,7 @@
 // POD cgpt_scene_desc the device library uploads.
 #pragma once
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -65,9 +66,11 @@ private:
 
 struct Object {  // ref: Main.cpp:245-275
     Object(const char* name_, const Mesh& mesh, uint32_t mat, MeshBVH::BuildOption option)
-        : name(name_), mat_index(mat), has_bvh(true) { valid = bvh.Build(mesh.vertices, mesh.indices, option); }
+        : name(name_), mat_index(mat), has_bvh(true), bvh(std::make_shared<MeshBVH>()) { valid = bvh->Build(mesh.vertices, mesh.indices, option); }
     Object(const char* name_, const Mesh& mesh, uint32_t mat, MeshBVH::BuildOption build_option, const MeshBVH::TreeBuilder& builder)
-        : name(name_), mat_index(mat), has_bvh(true) { valid = bvh.BuildWith(mesh.vertices, mesh.indices, build_option, builder); }
+        : name(name_), mat_index(mat), has_bvh(true), bvh(std::make_shared<MeshBVH>()) { valid = bvh->BuildWith(mesh.vertices, mesh.indices, build_option, builder); }
+    // an instance (cgpth_scene_add_instance): the mesh of `of` shared, not copied; material, smooth flag and transform are its own
+    Object(const char* name_, const Object& of, uint32_t mat) : name(name_), mat_index(mat), has_bvh(true), bvh(of.bvh) {}
     Object(const char* name_, const Sphere& s, uint32_t mat) : name(name_), mat_index(mat), kind(CGPT_OBJECT_SPHERE), sphere(s) {}
     Object(const char* name_, const Plane& p, uint32_t mat) : name(name_), mat_index(mat), kind(CGPT_OBJECT_PLANE), plane(p) {}
     // Primitive(const Triangle&) (ref: Include/Primitives.h:84-89): a stand-alone triangle, no BVH
@@ -77,7 +80,7 @@ struct Object {  // ref: Main.cpp:245-275
     uint32_t mat_index = 0;
     bool has_bvh = false;
     bool valid = true;
-    MeshBVH bvh;
+    std::shared_ptr<MeshBVH> bvh;   // a mesh object's triangles and tree; the instances of a mesh hold the same one (null without has_bvh)
     uint32_t kind = CGPT_OBJECT_MESH;
     Sphere sphere;
     Plane plane;
@@ -103,7 +106,7 @@ struct Scene {  // ref: Main.cpp:209-216,228-235
     uint32_t debug_render_mode = CGPT_DEBUG_NONE;
 
     // Packs objects/BVHs/materials/lights into the POD arrays of cgpt_scene_desc.  The returned desc points
-    // into `storage`, which must outlive its use.
+    // into `storage`, which must outlive its use.  A mesh that several objects share is packed once, and every sharer names its slices.
     struct FlatStorage {
         std::vector<cgpt_object> objects;
         std::vector<cgpt_bvh_node> nodes;

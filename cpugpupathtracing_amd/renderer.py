@@ -66,6 +66,7 @@ class Renderer:
         self._top_level = False       # cgpt_set_top_level
         self._smooth = False          # the device holds a smooth-normal flag (cgpt_scene_update_smooth_normals)
         self._transformed = False     # the device holds a transform that is not the identity (cgpt_scene_update_transforms)
+        self.instanced = False        # the last upload was cgpt_scene_upload_instanced
 
     def _check(self, rc: int):
         if rc != 0:
@@ -97,12 +98,18 @@ class Renderer:
     def top_level(self) -> bool:
         return self._top_level
 
-    def upload(self, scene: Scene):
+    def upload(self, scene: Scene, instanced: Optional[bool] = None):
         """cgpt_scene_upload, then the scene's roughness (cgpt_scene_update_roughness), transmission roughness
         (cgpt_scene_update_transmission_roughness) and smooth-normal flags (cgpt_scene_update_smooth_normals) when any is nonzero, and
-        its transforms (cgpt_scene_update_transforms) when any is not the identity."""
+        its transforms (cgpt_scene_update_transforms) when any is not the identity.
+        instanced: True uploads with cgpt_scene_upload_instanced -- one device copy for the mesh objects that share a mesh
+        (Scene.add_instance), same image bit for bit, and a refit_mesh then moves every sharer -- False with
+        cgpt_scene_upload, None (the default) instanced exactly when the scene has an instance."""
         desc = scene.flatten()
-        self._check(self.L.cgpt_scene_upload(self._ctx, C.byref(desc)))
+        if instanced is None:
+            instanced = scene.has_instances(desc)
+        self._check((self.L.cgpt_scene_upload_instanced if instanced else self.L.cgpt_scene_upload)(self._ctx, C.byref(desc)))
+        self.instanced = bool(instanced)
         self._glossy = self._rough_glass = self._smooth = self._transformed = False   # the upload reset every roughness, flag and transform
         self.scene = scene
         self._node_counts = [desc.objects[k].node_count for k in range(desc.n_objects)]   # the uploaded trees (export_bvh)
@@ -118,6 +125,13 @@ class Renderer:
         transforms = scene.transforms(desc.n_objects)
         if not _all_identity(transforms):
             self.update_transforms(transforms)
+
+    def scene_footprint(self) -> N.SceneFootprint:
+        """cgpt_get_scene_footprint: what the uploaded scene occupies on one device -- device_bytes, n_objects, n_mesh_objects,
+        n_mesh_copies (the meshes actually laid out), n_leaf_records, n_pair_records, n_orig_triangles."""
+        fp = N.SceneFootprint()
+        self._check(self.L.cgpt_get_scene_footprint(self._ctx, C.byref(fp)))
+        return fp
 
     def update_materials(self, scene: Scene):
         """cgpt_scene_update_materials, then each of the scene's two roughnesses when it or the device's is nonzero."""

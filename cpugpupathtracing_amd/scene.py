@@ -338,6 +338,33 @@ class Scene:
             self.set_transform(rc, transform)
         return rc
 
+    def add_instance(self, obj_index: int, mat_index: int, transform=None, smooth: bool = False) -> int:
+        """An instance of mesh object `obj_index` (cgpth_scene_add_instance): a new mesh object that shares that object's
+        triangles and BVH -- one device copy under Renderer.upload(instanced=True) -- with its own material, transform and smooth flag.
+        refit_mesh and rebuild_bvh through either index act on the shared tree.  Spheres, planes and triangle objects are refused.
+        Returns the object index."""
+        rc = N.lib().cgpth_scene_add_instance(self._h, obj_index, mat_index)
+        if rc < 0:
+            raise HostError(N.lib().cgpth_last_error().decode())
+        if smooth:
+            self.set_smooth_normals(rc, True)
+        if transform is not None:
+            self.set_transform(rc, transform)
+        return rc
+
+    def has_instances(self, desc=None) -> bool:
+        """Two mesh objects of the flattened scene name the same node and triangle slices (add_instance makes such objects)."""
+        desc = self.flatten() if desc is None else desc
+        seen = set()
+        for k in range(desc.n_objects):
+            o = desc.objects[k]
+            if o.kind == N.OBJECT_MESH:
+                key = (o.node_offset, o.node_count, o.tri_offset, o.tri_count)
+                if key in seen:
+                    return True
+                seen.add(key)
+        return False
+
     def add_sphere(self, center, radius: float, mat_index: int) -> int:
         return N.lib().cgpth_scene_add_sphere(self._h, _f3(center), radius, mat_index)
 

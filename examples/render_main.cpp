@@ -4,7 +4,7 @@
 //
 //   g++ -std=c++17 -Iinclude -Icpugpupathtracing_amd/csrc/host examples/render_main.cpp
 //       -Lcpugpupathtracing_amd/lib -lcpugpupt -Wl,-rpath,$PWD/cpugpupathtracing_amd/lib -o render_main   (one command line)
-//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--smooth] [--mesh-transform m00 .. m23] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
+//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
 // --gpus N: ONE context over the first N GPUs of the node (cgpt_ctx_create with n_devices = N): every frame is spread over them in
 // interleaved row bands and the read-back gathers the float4 bands with one RCCL exchange over xGMI; the loop below does not
 // change.  --collective: take that code path with N = 1 too (what a one-GPU box can test).
@@ -27,6 +27,9 @@
 // --bvh binned: build the mesh's tree with BuildOption_SAHBinned (16 bins per axis) on the host instead of the reference's
 // SAH split intervals (the default; image parity with the reference is defined on that tree).
 // --top-level: IntersectScene reaches the objects through the top-level tree (cgpt_set_top_level(1)): the same image, bit for bit.
+// --instances N: mesh instancing -- N more placements of the mesh (object 0) stand behind it on a jittered grid over the ground, each a third
+// of its size under a rotation and shift of its own; they share the mesh's triangles and tree on the host, and the scene is uploaded with
+// cgpt_scene_upload_instanced, so the device holds the mesh once however large N is.  The footprint is printed.
 // --nee-candidates M: resampled light sampling -- every NEE light sample is the survivor of M candidates in 1..32 (cgpt_set_nee_candidates,
 // set before the upload: it is context state; 1, the default, is the reference's single sample).
 // --smooth: smooth shading -- every mesh object that is not a light shades with its interpolated vertex normals
@@ -59,7 +62,7 @@ using namespace cgpt;
 
 int main(int argc, char** argv)
 {
-    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false;
+    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false; uint32_t n_instances = 0;
     bool has_transform = false; float mesh_transform[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
     MeshBVH::BuildOption bvh_option = MeshBVH::BuildOption_SAHSplitIntervals;
     while (argc > 1 && std::string(argv[1]).rfind("--", 0) == 0) {
@@ -76,6 +79,7 @@ int main(int argc, char** argv)
         else if (std::string(argv[1]) == "--ground-roughness" && argc > 2) { ground_roughness = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--glass-roughness" && argc > 2) { glass_roughness = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--top-level") { top_level = true; argv += 1; argc -= 1; }
+        else if (std::string(argv[1]) == "--instances" && argc > 2) { n_instances = (uint32_t)atoi(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--nee-candidates" && argc > 2) { nee_candidates = (uint32_t)atoi(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--bvh" && argc > 2 && (std::string(argv[2]) == "binned" || std::string(argv[2]) == "intervals")) {
             bvh_option = std::string(argv[2]) == "binned" ? MeshBVH::BuildOption_SAHBinned : MeshBVH::BuildOption_SAHSplitIntervals; argv += 2; argc -= 2;
@@ -98,6 +102,20 @@ int main(int argc, char** argv)
     if (!scene.objects[0].valid) { fprintf(stderr, "the mesh is empty, or (--bvh binned) has a position that is not finite or beyond 1e30\n"); return 1; }
     if (ground_roughness >= 0.0f) { scene.materials[1].specular = 0.5f; scene.materials[1].roughness = ground_roughness; }
     if (glass_roughness >= 0.0f) scene.materials[3].transmission_roughness = glass_roughness;
+    if (has_transform) for (int k = 0; k < 12; ++k) scene.objects[0].transform[k] = mesh_transform[k];
+    if (n_instances) {                                                   // a jittered grid behind the mesh, rows of `side`
+        const uint32_t side = (uint32_t)std::ceil(std::sqrt((double)n_instances));
+        uint32_t rng = 0x2545F491u;
+        auto jitter = [&rng]() { rng = rng * 1664525u + 1013904223u; return (float)(rng >> 8) / 16777216.0f - 0.5f; };   // [-0.5, 0.5)
+        for (uint32_t k = 0; k < n_instances; ++k) {
+            Object instance("Instance", scene.objects[0], k % 2 ? 0u : 3u);  // shares the mesh; built before the vector may move object 0
+            const float angle = 6.2831853f * jitter(), scale = 0.33f, c = scale * std::cos(angle), sn = scale * std::sin(angle);
+            const float x = 2.5f * ((float)(k % side) - 0.5f * (float)(side - 1)) + 0.8f * jitter(), z = -6.0f - 2.5f * (float)(k / side) + 0.8f * jitter();
+            const float m[12] = { c, 0.0f, sn, x, 0.0f, scale, 0.0f, -2.0f, -sn, 0.0f, c, z };
+            for (int i = 0; i < 12; ++i) instance.transform[i] = m[i];
+            scene.objects.push_back(std::move(instance));
+        }
+    }
 
     cgpt_ctx* ctx = nullptr;
     // ThreadPool::Init: device_ids = NULL means devices 0 .. n_gpus-1
@@ -106,7 +124,13 @@ int main(int argc, char** argv)
     CHECK(cgpt_set_nee_candidates(ctx, nee_candidates));                 // context state: allowed before a scene exists, kept by every upload
     Scene::FlatStorage flat;
     cgpt_scene_desc desc = scene.Flatten(flat);
-    CHECK(cgpt_scene_upload(ctx, &desc));
+    CHECK(n_instances ? cgpt_scene_upload_instanced(ctx, &desc) : cgpt_scene_upload(ctx, &desc));
+    if (n_instances) {
+        cgpt_scene_footprint fp{};
+        CHECK(cgpt_get_scene_footprint(ctx, &fp));
+        printf("%u objects, %u mesh objects in %u device copies: %u triangles, %.1f MB on the device\n", fp.n_objects, fp.n_mesh_objects, fp.n_mesh_copies,
+               fp.n_orig_triangles, (double)fp.device_bytes / 1e6);
+    }
     if (ground_roughness >= 0.0f) {                                      // roughness is not part of the scene description: set after the upload
         std::vector<float> roughness;
         for (const Material& m : scene.materials) roughness.push_back(m.roughness);
@@ -123,10 +147,9 @@ int main(int argc, char** argv)
         for (const uint32_t li : scene.light_source_indices) flags[li] = 0u;
         CHECK(cgpt_scene_update_smooth_normals(ctx, flags.data(), (uint32_t)flags.size()));
     }
-    if (has_transform) {                                                 // nor are the transforms
+    if (has_transform || n_instances) {                                  // nor are the transforms: object 0 (the mesh) and the instances
         std::vector<float> matrices;
         for (const Object& o : scene.objects) matrices.insert(matrices.end(), o.transform, o.transform + 12);
-        for (int k = 0; k < 12; ++k) matrices[k] = mesh_transform[k];    // object 0: the mesh
         CHECK(cgpt_scene_update_transforms(ctx, matrices.data(), (uint32_t)scene.objects.size()));
     }
 

@@ -220,6 +220,31 @@ int cgpt_set_top_level(cgpt_ctx* ctx, uint32_t mode);
 
 /* replaces the implicit use of data.objects / materials / light_source_indices (ref: Main.cpp:209-212, 303-315) */
 int cgpt_scene_upload(cgpt_ctx* ctx, const cgpt_scene_desc* scene);
+/* Mesh instancing: cgpt_scene_upload with one device copy for the mesh objects that name the same geometry.  Mesh objects
+ * whose node_offset, node_count, tri_offset and tri_count are all equal form a mesh group; the group's triangles and tree are laid out
+ * once, from its first member, and every member reaches that copy.  Each member keeps its own material, total_area (as given), smooth
+ * flag, transform and top-level box, so n placements of a mesh cost n object records and one mesh.  Slices that overlap only in part are
+ * separate meshes; triangle objects, spheres and planes are laid out per object.  Validation, refusals, messages, what is reset
+ * (roughnesses, smooth flags and transforms to 0 and the identity, the denoiser's guides and history) and what is kept
+ * (cgpt_set_nee_candidates, cgpt_set_top_level) are cgpt_scene_upload's, on every device of a multi-device context; the 2^26 limit applies
+ * to the records laid out, not to the sum over the objects.  No kernel differs: every render, probe and guide of an instanced upload
+ * equals that of cgpt_scene_upload of the same scene bit for bit, counters included.
+ * THE ONE DIFFERENCE: cgpt_scene_refit_mesh through any member moves EVERY instance of the group -- the one copy is refitted, and each
+ * member's total_area and top-level box follow.  After cgpt_scene_upload a refit moves the named object alone, as it always has.
+ * cgpt_scene_export_bvh through any member returns the group's tree.  The other edits (transforms, smooth normals, materials, roughness,
+ * primitives) stay per object with their refusals: a light may share a group with objects that are no lights, and only the light itself
+ * is held to the identity and to flat normals.  A later cgpt_scene_upload of the same scene returns to per-object copies.
+ * An added export: CGPT_ABI_VERSION stays 2. */
+int cgpt_scene_upload_instanced(cgpt_ctx* ctx, const cgpt_scene_desc* scene);
+/* What the uploaded scene occupies, after either upload (CGPT_ERR_NO_SCENE without one; a multi-device context reports one device, and
+ * every device holds the same).  No edit changes it.  An added export: CGPT_ABI_VERSION stays 2. */
+typedef struct cgpt_scene_footprint {
+    uint64_t device_bytes;       /* bytes of the scene's allocations on one device: the triangle, node, normal, material, object and light
+                                  * arrays, the refit levels and the room of the top-level tree (not the framebuffer, not a refit's staging) */
+    uint32_t n_objects, n_mesh_objects, n_mesh_copies;   /* copies: the meshes actually laid out (== n_mesh_objects after cgpt_scene_upload) */
+    uint32_t n_leaf_records, n_pair_records, n_orig_triangles;
+} cgpt_scene_footprint;
+int cgpt_get_scene_footprint(cgpt_ctx* ctx, cgpt_scene_footprint* out);
 /* replaces Material::RenderImGui edits (ref: Main.cpp:71-91,263-265); the caller resets the accumulator as the reference does */
 int cgpt_scene_update_materials(cgpt_ctx* ctx, const cgpt_material* materials, uint32_t n_materials);
 /* Microfacet BRDF (reference README, "Planned"): the roughness in [0, 1] of every material's specular lobe (the `r < specular` branch),
@@ -281,7 +306,8 @@ int cgpt_scene_update_transforms(cgpt_ctx* ctx, const float* object_to_world, ui
  * current leaf range of the new triangles, and total_area the sum of GetTriangleArea in original order (ref: BVH.cpp:22).
  * triangles: n_tris == the uploaded tri_count, in the object's original order.  A triangle object takes n_tris = 1 (it has no bounds
  * and no total_area: 0 is reported).  Spheres and planes: CGPT_ERR_INVALID.  total_area_out may be NULL.
- * The tree was built for the old positions: after a large deformation rebuild on the host and upload instead. */
+ * The tree was built for the old positions: after a large deformation rebuild on the host and upload instead.
+ * After cgpt_scene_upload_instanced the refit moves every object that shares `obj_index`'s copy (see there). */
 int cgpt_scene_refit_mesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris, float* total_area_out);
 /* the mesh's tree as it is now on the device, in the reference's 32-byte layout and node numbering (n_nodes == the uploaded node_count):
  * what a host that keeps its own BVH (the BVH panel, a later Rebuild) copies back after a refit */

@@ -63,6 +63,12 @@ int cgpth_scene_get_transmission_roughness(const cgpth_scene* scene, float* out,
 int cgpth_scene_add_mesh(cgpth_scene* scene, const cgpth_mesh* mesh, uint32_t mat_index, int build_option);  /* Object ctor, ref: Main.cpp:247-251; returns object index */
 /* same result as cgpth_scene_add_mesh(..., CGPTH_BUILD_SAH_INTERVALS) with the tree built on the GPU by cgpt_bvh_build
  * (bit-identical tree; the host keeps validating and owning it) */
+/* an instance of mesh object `of_obj_index` (mesh instancing, cgpt_scene_upload_instanced): a new mesh object that SHARES that object's
+ * triangles and BVH and has its own material, smooth flag and transform; returns its index.  An instance of an instance shares the same
+ * mesh.  cgpth_scene_flatten emits the shared slices once and names them from every sharer, so cgpt_scene_upload_instanced keeps one
+ * device copy (cgpt_scene_upload copies per object, as it does for any scene).  cgpth_scene_refit_mesh and the rebuilds through any sharer
+ * act on the one tree.  Refused (negative): a bad index, or a sphere, a plane or a triangle object */
+int cgpth_scene_add_instance(cgpth_scene* scene, uint32_t of_obj_index, uint32_t mat_index);
 int cgpth_scene_add_mesh_device_built(cgpth_scene* scene, const cgpth_mesh* mesh, uint32_t mat_index, cgpt_ctx* ctx);
 /* any BuildOption on the GPU (cgpt_bvh_build_ex; ref: BVH.cpp:208-297) */
 int cgpth_scene_add_mesh_device_built_ex(cgpth_scene* scene, const cgpth_mesh* mesh, uint32_t mat_index, cgpt_ctx* ctx, int build_option);
@@ -157,12 +163,16 @@ typedef struct cgpth_scene_layout_view {
     const float* obj_xform; size_t n_obj_xform;
 } cgpth_scene_layout_view;
 int cgpth_scene_layout(const cgpt_scene_desc* scene, cgpth_scene_layout_view* out);
+/* the layout a cgpt_scene_upload_instanced would install: the same view; the objects of a mesh group show equal root_code, tri_base,
+ * leaf_base, pair_base and levels */
+int cgpth_scene_layout_instanced(const cgpt_scene_desc* scene, cgpth_scene_layout_view* out);
 /* the same after a cgpt_scene_update_transforms(object_to_world, n_objects) on that upload, with that call's validation, status and
  * message: obj_xform holds the inverses, `objects` the xform words and obj_trace the flags the call would install */
 int cgpth_scene_layout_transformed(const cgpt_scene_desc* scene, const float* object_to_world, uint32_t n_objects, cgpth_scene_layout_view* out);
 
 /* ---- the top-level tree of cgpt_set_top_level (csrc/device/scene_layout.h: LayoutTopLevel; tests/tlas_ref.py is its specification) ----
- * cgpth_top_level: the tree a cgpt_scene_upload of `scene` would build, computed on the host with the upload's validation; no GPU is
+ * cgpth_top_level: the tree a cgpt_scene_upload of `scene` would build (cgpt_scene_upload_instanced builds the same: the boxes are per
+ * object; the record limit that is checked is the instanced upload's), computed on the host with the upload's validation; no GPU is
  * touched.  nodes: n_nodes = 2 n_objects - 1 records of 8 floats in preorder, {lo.xyz, bits(skip) | hi.xyz, bits(object or 0xFFFFFFFF)};
  * entry: n_objects + 1 node indices.  The three calls behind it apply, to the state of this thread's last cgpth_top_level, what
  * cgpt_scene_update_transforms, cgpt_scene_refit_mesh and cgpt_scene_update_primitive apply to a context's (the same functions), and
