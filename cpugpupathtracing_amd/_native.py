@@ -23,6 +23,7 @@ BUILD_SAH_BINNED = 3        # not in the reference: 16 bins per axis, stable par
 DENOISE_DEMODULATE_ALBEDO = 1
 TRACE_COUNTERS, TRACE_REVERSED = 1, 2
 TEMPORAL_KEEP_VIEW_DEPENDENT = 1
+TEMPORAL_FOLLOW_TRANSFORMS = 4
 VARIANCE_TEMPORAL = 1
 
 f3 = C.c_float * 3
@@ -250,6 +251,7 @@ PROTOTYPES = {
     "cgpth_write_accumulator": (C.c_int, [C.c_char_p, _fp, C.c_uint32, C.c_uint32, C.c_uint32]),
     "cgpth_read_accumulator": (C.c_int, [C.c_char_p, _fp, _up, C.c_uint32, C.c_uint32]),
     "cgpth_fast_div": (C.c_uint32, [C.c_uint32, C.c_uint32]),
+    "cgpth_motion_records": (C.c_uint32, [_fp, C.c_uint32, _fp, C.c_uint32, _fp]),
     "cgpth_shade_item_blocks": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "cgpth_shade_segment_blocks": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "cgpth_scene_layout": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(SceneLayoutView)]),

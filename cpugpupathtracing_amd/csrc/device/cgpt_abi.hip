@@ -164,7 +164,7 @@ int UpdateSmoothNormals(cgpt_ctx* ctx, const uint32_t* smooth, uint32_t n_object
     for (uint32_t i = 0; i < n_objects; ++i) objects[i].smooth = smooth[i];
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->scene_generation++;                                                   // the denoiser's guides hold the normal (denoise.hip)
+    ctx->scene_generation++; ctx->shape_generation++;                          // the denoiser's guides hold the normal (denoise.hip)
     const hipError_t e = hipMemcpy(ctx->sb.objects.p, objects.data(), objects.size() * sizeof(DevObject), hipMemcpyHostToDevice);
     if (e != hipSuccess) {                                                     // the records may be half written: drop the scene (refit.hip: SceneLost)
         ctx->has_scene = false;
@@ -205,7 +205,8 @@ int UpdateTransforms(cgpt_ctx* ctx, const float* object_to_world, uint32_t n_obj
     if (rc != CGPT_OK) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->scene_generation++;                                                   // the denoiser's guides hold position and normal (denoise.hip)
+    ctx->scene_generation++;                                                   // the denoiser's guides hold position and normal (denoise.hip); shape_generation
+                                                                               // stays: a temporal call may follow the matrices (CGPT_TEMPORAL_FOLLOW_TRANSFORMS)
     const hipError_t e = trace.empty() ? hipSuccess : hipMemcpy(ctx->sb.obj_trace.p, trace.data(), trace.size() * sizeof(float4), hipMemcpyHostToDevice);
     if (e != hipSuccess) {                                                     // the records may be half written: drop the scene (refit.hip: SceneLost)
         ctx->has_scene = false;
@@ -333,7 +334,7 @@ static int SceneUpload(cgpt_ctx* ctx, const cgpt_scene_desc* scene, bool instanc
     if (!scene) return CtxFail(ctx, CGPT_ERR_INVALID, "scene is null");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->scene_generation++;                                                   // the denoiser's guides are stale (denoise.hip)
+    ctx->scene_generation++; ctx->shape_generation++;                          // the denoiser's guides are stale (denoise.hip)
     return Guarded(ctx, "scene upload", [&] {                                  // the re-layout allocates host vectors
         SceneLayout layout;
         const int rc = LayoutScene(*scene, layout, ctx->error, instanced);
@@ -365,7 +366,7 @@ int cgpt_scene_update_materials(cgpt_ctx* ctx, const cgpt_material* materials, u
     for (uint32_t i = 0; i < n_materials; ++i) PackMaterial(materials[i], ctx->h_roughness[i], ctx->h_transmission_roughness[i], mats.data() + 4 * (size_t)i);   // both roughnesses are kept
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->scene_generation++;
+    ctx->scene_generation++; ctx->shape_generation++;
     HIP_TRY(ctx, hipMemcpy(ctx->sb.materials.p, mats.data(), mats.size() * sizeof(float4), hipMemcpyHostToDevice));
     ctx->h_materials.swap(mats);
     return CGPT_OK;

@@ -10,6 +10,7 @@
 #include "device_scene.h"
 #include "launch_common.h"
 #include "scene_layout.h"
+#include "transform_math.h"
 
 namespace cgpt {
 struct DeviceGroup;
@@ -38,6 +39,8 @@ struct DenoiseBuffers {                           // denoise.hip; each group is 
     DevBuf<float4> history_guides[2];             // 2 float4 per pixel {x.xyz, t | n.xyz, bits(obj)} of the frame each history belongs to
     DevBuf<float> variance;                       // cgpt_denoise_variance_guided: per pixel, the variance pass 0 read (cgpt_read_variance)
     DevBuf<float4> moments[2];                    // ... per pixel {mu, v, K, 0} of the luminance, beside history[] (the same slot)
+    DevBuf<float4> motion;                        // CGPT_TEMPORAL_FOLLOW_TRANSFORMS: 6 float4 per object (transform_math.h: MotionRecord), grown on
+                                                  // demand and written only by a call in which an object moved
 };
 template <class... B> void ResetAll(B&... b) { (b.Reset(), ...); }
 // What the uploaded scene has that a kernel variant must carry: a roughness > 0, a transmission roughness > 0, a smooth-normal flag (they live in
@@ -116,6 +119,7 @@ struct cgpt_ctx {
 
     // the denoiser (denoise.hip): first-hit guides cached per camera, band and scene, and the filter's ping-pong buffers
     uint64_t scene_generation = 0;                // bumped by every scene upload and in-place edit
+    uint64_t shape_generation = 0;                // ... by each of them but cgpt_scene_update_transforms: what a history that follows the transforms is kept across
     cgpt::DenoiseBuffers dn;
     bool guides_valid = false;
     uint64_t guide_generation = 0;                // what the guides were computed for
@@ -128,6 +132,11 @@ struct cgpt_ctx {
     uint64_t temporal_generation = 0;
     cgpt_camera temporal_camera{};
     uint32_t temporal_frame[4] = { 0, 0, 0, 0 };  // as guide_frame
+    // CGPT_TEMPORAL_FOLLOW_TRANSFORMS: the shape generation and top_state.xform (12 floats per object) the history was stored for, and
+    // the host copy of dn.motion of the last call in which an object moved (it outlives the asynchronous copy)
+    uint64_t temporal_shape_generation = 0;
+    std::vector<float> temporal_xform;
+    std::vector<cgpt::MotionRecord> motion_records;
     // the variance-guided filter (cgpt_denoise_variance_guided): dn.moments[temporal_slot] belongs to the temporal history when
     // moments_valid (a cgpt_denoise_temporal call updates the colour without them); dn.variance is the last successful call's map
     bool moments_valid = false;

@@ -18,6 +18,8 @@
 // passes, temporal_merge reprojects the history of the earlier frames -- merged colour and history length H per pixel, with that frame's
 // guides and camera -- onto the current camera through the current first hits, validates the four bilinear taps against the current hit
 // (same object, normal, tangent plane) and merges c = (He c_h + N c_0) / (He + N).  The passes then run on c.
+// With CGPT_TEMPORAL_FOLLOW_TRANSFORMS (tests/motion_ref.py) a history outlives cgpt_scene_update_transforms calls: the
+// hits on the objects whose matrices changed are first carried back through M_prev M_cur^-1 (temporal_merge<.., MOTION = true>).
 //
 // Variance-guided edge stopping (cgpt_denoise_variance_guided, cgpt_read_variance; tests/variance_ref.py states it in
 // numpy): the colour edge-stop of the passes becomes exp(-|l(c_q) - l(c_p)| / (sigma_l sqrt(gbar(p)) + 1e-6)), l the luminance and gbar
@@ -242,6 +244,8 @@ struct TemporalArgs {
     float* variance;               // out: var_t or -1
     uint32_t have_moments;         // the moments belong to hist (no cgpt_denoise_temporal call updated the colour since)
     float min_history_n;           // min_history_frames N
+    // MOTION only (CGPT_TEMPORAL_FOLLOW_TRANSFORMS)
+    const float4* motion;          // 6 float4 per object: transform_math.h's MotionRecord
 };
 
 // One thread per pixel.  The geometry of the reprojection -- (a, b, c) = Minv (x - pos_prev), fx, fy, the bilinear weights and the two
@@ -255,7 +259,13 @@ struct TemporalArgs {
 // {mu, v, K} kept beside the colour history go through the same four taps, validity tests and weights, and merge with the N samples of
 // l0 = l(c_0) by the pooled-variance update; the pixel's entry of the variance map becomes var_t = v' N / (Ke + N), or -1 where
 // Ke + N < min_history_frames N (variance_estimate then puts var_s there).  The colour's arithmetic is the same instructions either way.
-template <bool FINAL, bool MOMENTS = false>
+// MOTION (CGPT_TEMPORAL_FOLLOW_TRANSFORMS, a call in which an object moved; always mode kReproject; tests/motion_ref.py):
+// the pixel's record -- gathered by its object index, a miss reads record 0 and is masked -- carries the hit back to where the object
+// was when the history was stored, x' = D x and n' = normalize(N n) in double, each rounded to float once, and the arithmetic below runs
+// on x', n', the unchanged t and object index.  A pixel of an unmoved object takes x and n untouched by a select (an identity product
+// would change bits), one of a dropped object takes no history.  The record's six loads are issued as soon as the object index is
+// known and before anything waits for them; the taps' addresses depend on them.  The new history stores the frame's own guides.
+template <bool FINAL, bool MOMENTS = false, bool MOTION = false>
 __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
 {
     uint32_t px, row;
@@ -278,7 +288,27 @@ __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
     } else if (a.mode == kReproject) {
         const uint32_t obj = __float_as_uint(g1.w), mat = __float_as_uint(g2.w);
         const bool hit = obj != kNoHit;
-        const double dx = (double)g0.x - (double)a.pos_prev[0], dy = (double)g0.y - (double)a.pos_prev[1], dz = (double)g0.z - (double)a.pos_prev[2];
+        float4 x4 = g0, n4 = g1;                                               // the hit the reprojection runs on: MOTION carries it back
+        bool dropped = false;
+        if constexpr (MOTION) {
+            const float4* const rec = a.motion + 6u * (hit ? (size_t)obj : 0u);
+            const float4 d0 = rec[0], d1 = rec[1], d2 = rec[2], n0 = rec[3], n1 = rec[4], n2 = rec[5];
+            const uint32_t state = hit ? __float_as_uint(n0.w) : 0u;           // transform_math.h: 0 unmoved, 1 moved, 2 drop
+            const double x = (double)g0.x, y = (double)g0.y, z = (double)g0.z;
+            const double cx = (((double)d0.x * x + (double)d0.y * y) + (double)d0.z * z) + (double)d0.w;
+            const double cy = (((double)d1.x * x + (double)d1.y * y) + (double)d1.z * z) + (double)d1.w;
+            const double cz = (((double)d2.x * x + (double)d2.y * y) + (double)d2.z * z) + (double)d2.w;
+            const double nx = (double)g1.x, ny = (double)g1.y, nz = (double)g1.z;
+            const double vx = ((double)n0.x * nx + (double)n0.y * ny) + (double)n0.z * nz;
+            const double vy = ((double)n1.x * nx + (double)n1.y * ny) + (double)n1.z * nz;
+            const double vz = ((double)n2.x * nx + (double)n2.y * ny) + (double)n2.z * nz;
+            const double len = sqrt((vx * vx + vy * vy) + vz * vz);
+            const bool moved = state == 1u;
+            dropped = state == 2u;
+            x4.x = moved ? (float)cx : g0.x; x4.y = moved ? (float)cy : g0.y; x4.z = moved ? (float)cz : g0.z;
+            n4.x = moved ? (float)(vx / len) : g1.x; n4.y = moved ? (float)(vy / len) : g1.y; n4.z = moved ? (float)(vz / len) : g1.z;
+        }
+        const double dx = (double)x4.x - (double)a.pos_prev[0], dy = (double)x4.y - (double)a.pos_prev[1], dz = (double)x4.z - (double)a.pos_prev[2];
         const double pa = ((double)a.minv[0] * dx + (double)a.minv[1] * dy) + (double)a.minv[2] * dz;
         const double pb = ((double)a.minv[3] * dx + (double)a.minv[4] * dy) + (double)a.minv[5] * dz;
         const double pc = ((double)a.minv[6] * dx + (double)a.minv[7] * dy) + (double)a.minv[8] * dz;
@@ -311,9 +341,9 @@ __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
         float smu = 0.0f, sv = 0.0f, sk = 0.0f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const double ndot = ((double)hn[k].x * (double)g1.x + (double)hn[k].y * (double)g1.y) + (double)hn[k].z * (double)g1.z;
-            const double dplane = ((double)g1.x * ((double)hx[k].x - (double)g0.x) + (double)g1.y * ((double)hx[k].y - (double)g0.y)) +
-                                  (double)g1.z * ((double)hx[k].z - (double)g0.z);
+            const double ndot = ((double)hn[k].x * (double)n4.x + (double)hn[k].y * (double)n4.y) + (double)hn[k].z * (double)n4.z;
+            const double dplane = ((double)n4.x * ((double)hx[k].x - (double)x4.x) + (double)n4.y * ((double)hx[k].y - (double)x4.y)) +
+                                  (double)n4.z * ((double)hx[k].z - (double)x4.z);
             const bool valid = in[k] && __float_as_uint(hn[k].w) == obj && ndot >= (double)a.normal_cos_min && fabs(dplane) <= tol;
             const double w = valid ? ((k & 1) ? wx : 1.0 - wx) * ((k >> 1) ? wy : 1.0 - wy) : 0.0;
             const float wf = (float)w;
@@ -321,7 +351,7 @@ __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
             sr += wf * hc[k].x; sg += wf * hc[k].y; sb += wf * hc[k].z; sh += wf * hc[k].w;
             if constexpr (MOMENTS) { smu += wf * hm[k].x; sv += wf * hm[k].y; sk += wf * hm[k].z; }
         }
-        const bool use = in_front && !view_dependent && wsum > 0.01;         // in_front: a hit, so an equal object index is a hit's
+        const bool use = in_front && !view_dependent && wsum > 0.01 && !(MOTION && dropped);   // in_front: a hit, so an equal object index is a hit's
         const float inv = 1.0f / (use ? (float)wsum : 1.0f);
         hr = sr * inv; hg = sg * inv; hb = sb * inv;
         H = use ? sh * inv : 0.0f;
@@ -598,7 +628,7 @@ int CheckTemporalParams(cgpt_ctx* ctx, const cgpt_temporal_params& t)
     if (!std::isfinite(t.max_history) || !(t.max_history >= 1.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "max_history must be finite and >= 1, got %g", t.max_history);
     if (!(t.normal_cos_min >= -1.0f && t.normal_cos_min <= 1.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "normal_cos_min %g outside [-1, 1]", t.normal_cos_min);
     if (!std::isfinite(t.plane_tolerance) || !(t.plane_tolerance > 0.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "plane_tolerance must be finite and > 0, got %g", t.plane_tolerance);
-    if (t.flags & ~(uint32_t)CGPT_TEMPORAL_KEEP_VIEW_DEPENDENT) return CtxFail(ctx, CGPT_ERR_INVALID, "unknown temporal flags 0x%x", t.flags);
+    if (t.flags & ~(uint32_t)(CGPT_TEMPORAL_KEEP_VIEW_DEPENDENT | CGPT_TEMPORAL_FOLLOW_TRANSFORMS)) return CtxFail(ctx, CGPT_ERR_INVALID, "unknown temporal flags 0x%x", t.flags);
     return CGPT_OK;
 }
 
@@ -639,15 +669,34 @@ int EnsureHistoryBuffers(cgpt_ctx* ctx, cgpt_ctx* d, size_t n)
     return CGPT_OK;
 }
 
-// the history a call may use: stored by a call that succeeded, for this band, scene and demodulation
-bool HistoryMatches(const cgpt_ctx* d, const uint32_t key[4], uint32_t demodulate)
+// the history a call may use: stored by a call that succeeded, for this band, scene and demodulation.  `follow`
+// (CGPT_TEMPORAL_FOLLOW_TRANSFORMS): or for a scene that only cgpt_scene_update_transforms calls have changed since.
+bool HistoryMatches(const cgpt_ctx* d, const uint32_t key[4], uint32_t demodulate, bool follow)
 {
-    return d->temporal_valid && d->temporal_generation == d->scene_generation && d->temporal_demodulate == demodulate &&
-           memcmp(d->temporal_frame, key, sizeof(d->temporal_frame)) == 0;
+    const bool scene = d->temporal_generation == d->scene_generation || (follow && d->temporal_shape_generation == d->shape_generation);
+    return d->temporal_valid && scene && d->temporal_demodulate == demodulate && memcmp(d->temporal_frame, key, sizeof(d->temporal_frame)) == 0;
 }
 
-// the arguments of the temporal stage of a frame: from dn.history[temporal_slot] (when `have`) into the other slot, on filter[0]
-void FillTemporalArgs(const Frame& f, const cgpt_camera* camera, const cgpt_temporal_params& t, uint32_t demodulate, bool have, TemporalArgs& a)
+// CGPT_TEMPORAL_FOLLOW_TRANSFORMS with a usable history: the records of every object against the matrices the history was stored for,
+// in d->motion_records and -- when an object moved -- in d->dn.motion (an asynchronous copy on the stream: motion_records lives on).
+// `moved`: an object is not unmoved, so the call reprojects through temporal_merge<.., MOTION = true>.
+int PrepareMotion(cgpt_ctx* ctx, cgpt_ctx* d, bool& moved)
+{
+    moved = false;
+    const size_t n = d->top_state.xform.size() / 12;
+    if (n == 0) return CGPT_OK;
+    try { d->motion_records.resize(n); } catch (const std::exception& e) { return CtxFail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
+    if (CompareTransforms(d->temporal_xform.data(), d->temporal_xform.size() / 12, d->top_state.xform.data(), n, d->motion_records.data()) == 0) return CGPT_OK;
+    HIP_TRY(ctx, d->dn.motion.Grow(6 * n));                                    // hipFree waits for the device
+    static_assert(sizeof(MotionRecord) == 6 * sizeof(float4), "6 float4 per object");
+    HIP_TRY(ctx, hipMemcpyAsync(d->dn.motion.p, d->motion_records.data(), n * sizeof(MotionRecord), hipMemcpyHostToDevice, d->stream));
+    moved = true;
+    return CGPT_OK;
+}
+
+// the arguments of the temporal stage of a frame: from dn.history[temporal_slot] (when `have`) into the other slot, on filter[0].
+// `moved` (PrepareMotion): the hits are carried back through dn.motion, so equal camera bytes do not mean equal hits -- the call reprojects.
+void FillTemporalArgs(const Frame& f, const cgpt_camera* camera, const cgpt_temporal_params& t, uint32_t demodulate, bool have, bool moved, TemporalArgs& a)
 {
     cgpt_ctx* d = f.dev;
     const uint32_t src = d->temporal_slot, dst = src ^ 1u;
@@ -661,20 +710,24 @@ void FillTemporalArgs(const Frame& f, const cgpt_camera* camera, const cgpt_temp
     a.height = (float)f.height; a.first_row = (float)f.first_row;
     a.mode = kNoHistory;
     if (have) {
-        if (memcmp(&d->temporal_camera, camera, sizeof(cgpt_camera)) == 0) a.mode = kSameCamera;
+        if (!moved && memcmp(&d->temporal_camera, camera, sizeof(cgpt_camera)) == 0) a.mode = kSameCamera;
         else if (InvertCamera(d->temporal_camera, a.minv)) {                   // a singular camera: no history
             memcpy(a.pos_prev, d->temporal_camera.pos, sizeof(a.pos_prev));
             a.mode = kReproject;
         }
     }
+    a.motion = moved ? d->dn.motion.p : nullptr;
 }
 
-// what a successful temporal stage leaves: the history in the other slot, and what it was stored for
-void StoreTemporalKey(cgpt_ctx* d, const cgpt_camera* camera, const uint32_t key[4], uint32_t demodulate)
+// what a successful temporal stage leaves: the history in the other slot, and what it was stored for (`xform`: the call's snapshot
+// of top_state.xform, swapped in)
+void StoreTemporalKey(cgpt_ctx* d, const cgpt_camera* camera, const uint32_t key[4], uint32_t demodulate, std::vector<float>& xform)
 {
     d->temporal_slot ^= 1u;
     d->temporal_demodulate = demodulate;
     d->temporal_generation = d->scene_generation;
+    d->temporal_shape_generation = d->shape_generation;
+    d->temporal_xform.swap(xform);
     memcpy(&d->temporal_camera, camera, sizeof(cgpt_camera));
     memcpy(d->temporal_frame, key, sizeof(d->temporal_frame));
     d->temporal_valid = true;
@@ -728,8 +781,14 @@ int RunStages(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, Stages s
     const float n_samples = (float)f.num_accumulated;
     const float inv_normal = (float)(1.0 / ((double)p.sigma_normal * p.sigma_normal));
     const float inv_position = (float)(1.0 / ((double)p.sigma_position * p.sigma_position));
-    const bool have = st.temporal && HistoryMatches(d, key, demodulate);
+    const bool follow = (t.flags & CGPT_TEMPORAL_FOLLOW_TRANSFORMS) != 0u;
+    const bool have = st.temporal && HistoryMatches(d, key, demodulate, follow);
     const bool have_moments = have && d->moments_valid;
+    std::vector<float> xform;                                                  // the matrices this call's history is stored for
+    if (st.temporal) {
+        try { xform.resize(d->top_state.xform.size()); } catch (const std::exception& e) { return CtxFail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
+        SnapshotTransforms(d->top_state.xform.data(), xform.size() / 12, xform.data());
+    }
     if (st.variance) d->variance_valid = false;                                // a call that fails from here on leaves no map
     if (st.temporal) d->temporal_valid = d->moments_valid = false;             // ... and no history
     int rc;
@@ -745,14 +804,21 @@ int RunStages(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, Stages s
         HIP_TRY(ctx, hipGetLastError());
     }
     if (st.temporal) {
+        bool moved = false;                                                    // an object moved since the history was stored, and the call follows it
+        if (have && follow && (rc = PrepareMotion(ctx, d, moved)) != CGPT_OK) return rc;
         TemporalArgs a{};
-        FillTemporalArgs(f, camera, t, demodulate, have, a);
+        FillTemporalArgs(f, camera, t, demodulate, have, moved, a);
+        moved = moved && a.mode == kReproject;                                 // a singular history camera: no history, the existing kernel
         if (st.variance) {
             a.moments = d->dn.moments[d->temporal_slot].p; a.moments_out = d->dn.moments[d->temporal_slot ^ 1u].p;
             a.variance = d->dn.variance.p;
             a.have_moments = have_moments ? 1u : 0u;
             a.min_history_n = (float)v.min_history_frames * n_samples;
-            hipLaunchKernelGGL((temporal_merge<false, true>), dim3(tiles), dim3(256), 0, d->stream, a);
+            if (moved) hipLaunchKernelGGL((temporal_merge<false, true, true>), dim3(tiles), dim3(256), 0, d->stream, a);
+            else hipLaunchKernelGGL((temporal_merge<false, true>), dim3(tiles), dim3(256), 0, d->stream, a);
+        } else if (moved) {
+            if (p.iterations == 0) hipLaunchKernelGGL((temporal_merge<true, false, true>), dim3(tiles), dim3(256), 0, d->stream, a);
+            else hipLaunchKernelGGL((temporal_merge<false, false, true>), dim3(tiles), dim3(256), 0, d->stream, a);
         } else if (p.iterations == 0) hipLaunchKernelGGL(temporal_merge<true>, dim3(tiles), dim3(256), 0, d->stream, a);
         else hipLaunchKernelGGL(temporal_merge<false>, dim3(tiles), dim3(256), 0, d->stream, a);
         HIP_TRY(ctx, hipGetLastError());
@@ -789,7 +855,7 @@ int RunStages(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, Stages s
     }
     if ((rc = ReadBack(ctx, d, n, out, dst_rgba, dst_pixels)) != CGPT_OK) return rc;
     if (st.temporal) {
-        StoreTemporalKey(d, camera, key, demodulate);
+        StoreTemporalKey(d, camera, key, demodulate, xform);
         d->moments_valid = st.variance;
     }
     if (st.variance) {

@@ -327,7 +327,7 @@ int GroupSceneUpload(cgpt_ctx* ctx, const cgpt_scene_desc* scene, bool instanced
     if (rc != CGPT_OK) return Propagate(ctx, first, rc);
     for (cgpt_ctx* m : ctx->group->members) {
         if ((rc = cgpt_synchronize(m)) != CGPT_OK) return Propagate(ctx, m, rc);   // selects the member's device and drains its stream
-        m->scene_generation++;
+        m->scene_generation++; m->shape_generation++;
         if ((rc = SceneInstall(m, layout)) != CGPT_OK) return Propagate(ctx, m, rc);
     }
     ctx->has_scene = true;

@@ -316,7 +316,7 @@ int cgpt_scene_refit_mesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle
 {
     if (!ctx) return CGPT_ERR_INVALID;
     if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupRefitMesh(ctx, obj_index, triangles, n_tris, total_area_out); });
-    ctx->scene_generation++;                                                   // the denoiser's guides are stale (denoise.hip)
+    ctx->scene_generation++; ctx->shape_generation++;                          // the denoiser's guides are stale (denoise.hip)
     return Guarded(ctx, __func__, [&] { return RefitMesh(ctx, obj_index, triangles, n_tris, total_area_out); });
 }
 
@@ -331,7 +331,7 @@ int cgpt_scene_update_primitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_ob
 {
     if (!ctx) return CGPT_ERR_INVALID;
     if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupUpdatePrimitive(ctx, obj_index, obj); });
-    ctx->scene_generation++;
+    ctx->scene_generation++; ctx->shape_generation++;
     return Guarded(ctx, __func__, [&] { return UpdatePrimitive(ctx, obj_index, obj); });
 }
 

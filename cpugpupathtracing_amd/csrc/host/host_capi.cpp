@@ -565,4 +565,11 @@ uint32_t cgpth_fast_div(uint32_t n, uint32_t d) { return d == 0u ? 0u : fast_div
 uint32_t cgpth_shade_item_blocks(uint32_t n_blocks, uint32_t n_waves, uint32_t chunk) { return n_waves == 0u || chunk == 0u ? 0u : shade_item_blocks(n_blocks, n_waves, chunk); }
 uint32_t cgpth_shade_segment_blocks(uint32_t cap_blocks, uint32_t min_waves, uint32_t chunk) { return min_waves == 0u || chunk == 0u ? 0u : shade_segment_blocks(cap_blocks, min_waves, chunk); }
 
+uint32_t cgpth_motion_records(const float* prev, uint32_t n_prev, const float* cur, uint32_t n_objects, float* records_out)
+{
+    if (!prev || !cur || !records_out) return 0u;
+    static_assert(sizeof(MotionRecord) == 24 * sizeof(float), "24 words per object");
+    return (uint32_t)CompareTransforms(prev, n_prev, cur, n_objects, reinterpret_cast<MotionRecord*>(records_out));
+}
+
 }  // extern "C"

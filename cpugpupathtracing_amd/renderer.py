@@ -289,14 +289,17 @@ class Renderer:
 
     def denoise_temporal(self, iterations: int = 5, sigma_color: float = 4.0, sigma_normal: float = 0.2, sigma_position: float = 0.3,
                          demodulate: bool = True, max_history: float = 64.0, normal_cos_min: float = 0.9, plane_tolerance: float = 0.01,
-                         keep_view_dependent: bool = False, camera: Optional[N.Camera] = None) -> Tuple[np.ndarray, np.ndarray]:
+                         keep_view_dependent: bool = False, camera: Optional[N.Camera] = None,
+                         follow_transforms: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         """denoise() with the temporal stage in front (cgpt_denoise_temporal): the history of the earlier calls is reprojected onto
         `camera` (the one of this frame's render; default: the uploaded scene's) and merged with the accumulated frame by sample counts
         before the filter runs.  Per frame: reset_accumulator(), render(), denoise_temporal(); each call consumes the accumulated
-        samples once.  Camera motion only: every scene edit drops the history."""
+        samples once.  Every scene edit drops the history; follow_transforms=True (CGPT_TEMPORAL_FOLLOW_TRANSFORMS) keeps it across
+        update_transforms() calls and carries the hits on the moved objects back to where they were."""
         cam = camera if camera is not None else self.scene.camera()
         p = N.DenoiseParams(iterations, N.DENOISE_DEMODULATE_ALBEDO if demodulate else 0, sigma_color, sigma_normal, sigma_position)
-        t = N.TemporalParams(max_history, normal_cos_min, plane_tolerance, N.TEMPORAL_KEEP_VIEW_DEPENDENT if keep_view_dependent else 0)
+        t = N.TemporalParams(max_history, normal_cos_min, plane_tolerance, (N.TEMPORAL_KEEP_VIEW_DEPENDENT if keep_view_dependent else 0) |
+                             (N.TEMPORAL_FOLLOW_TRANSFORMS if follow_transforms else 0))
         rgba = np.empty((self.n_rows, self.width, 4), np.float32)
         px = np.empty((self.n_rows, self.width), np.uint32)
         self._check(self.L.cgpt_denoise_temporal(self._ctx, C.byref(cam), C.byref(p), C.byref(t), rgba.ctypes.data_as(C.POINTER(C.c_float)),

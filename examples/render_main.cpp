@@ -4,7 +4,7 @@
 //
 //   g++ -std=c++17 -Iinclude -Icpugpupathtracing_amd/csrc/host examples/render_main.cpp
 //       -Lcpugpupathtracing_amd/lib -lcpugpupt -Wl,-rpath,$PWD/cpugpupathtracing_amd/lib -o render_main   (one command line)
-//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
+//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--spin DEG] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
 // --gpus N: ONE context over the first N GPUs of the node (cgpt_ctx_create with n_devices = N): every frame is spread over them in
 // interleaved row bands and the read-back gathers the float4 bands with one RCCL exchange over xGMI; the loop below does not
 // change.  --collective: take that code path with N = 1 too (what a one-GPU box can test).
@@ -16,6 +16,11 @@
 // from a reset accumulator, as a viewer renders while the camera moves; every frame is written raw (temporal_NN_raw.ppm), through
 // cgpt_denoise (temporal_NN_denoised.ppm) and through cgpt_denoise_temporal, which reprojects the frames before it (temporal_NN_temporal.ppm;
 // DESIGN.md 5.19).  Takes [width height spp] only.
+// --spin DEG: a moving object instead -- 8 frames under the scene's camera in which the mesh (object 0) turns by DEG degrees a frame about the
+// vertical axis through its centre (cgpt_scene_update_transforms, on top of --mesh-transform), each `spp` samples from a reset accumulator;
+// every frame is written raw (spin_NN_raw.ppm), through cgpt_denoise (spin_NN_denoised.ppm) and through cgpt_denoise_temporal with
+// CGPT_TEMPORAL_FOLLOW_TRANSFORMS, which carries the mesh's pixels back through the turn and keeps everyone's history (spin_NN_temporal.ppm;
+// DESIGN.md 5.25).  Takes [width height spp] only.
 // --variance-guided: the filter with the colour edge-stop in standard deviations of each pixel (cgpt_denoise_variance_guided).
 // With --denoise it is written next to every denoised image (preview_NNNN_variance_guided.ppm, render_variance_guided.ppm); with --temporal
 // it takes cgpt_denoise_temporal's place with CGPT_VARIANCE_TEMPORAL set (temporal_NN_variance_guided.ppm instead of temporal_NN_temporal.ppm:
@@ -62,7 +67,7 @@ using namespace cgpt;
 
 int main(int argc, char** argv)
 {
-    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false; uint32_t n_instances = 0;
+    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool spin = false; float spin_deg = 0.0f; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false; uint32_t n_instances = 0;
     bool has_transform = false; float mesh_transform[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
     MeshBVH::BuildOption bvh_option = MeshBVH::BuildOption_SAHSplitIntervals;
     while (argc > 1 && std::string(argv[1]).rfind("--", 0) == 0) {
@@ -70,6 +75,7 @@ int main(int argc, char** argv)
         else if (std::string(argv[1]) == "--collective") { ctx_flags |= CGPT_CTX_FORCE_COLLECTIVE; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--denoise") { denoise = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--temporal") { temporal = true; argv += 1; argc -= 1; }
+        else if (std::string(argv[1]) == "--spin" && argc > 2) { spin = true; spin_deg = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--variance-guided") { variance_guided = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--smooth") { smooth = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--mesh-transform" && argc > 13) {
@@ -179,6 +185,42 @@ int main(int argc, char** argv)
             }
             CHECK(cgpt_denoise_temporal(ctx, &cam, nullptr, nullptr, nullptr, 0, px.data(), px.size()));   // once per rendered frame
             snprintf(name, sizeof(name), "temporal_%02u_temporal.ppm", frame); WritePPM(name, px.data(), W, H, err);
+        }
+        cgpt_ctx_destroy(ctx);
+        return 0;
+    }
+    if (spin) {                                                          // the mesh moves every frame: UpdateTransforms, ResetAccumulator, Render, present
+        std::vector<uint32_t> px((size_t)W * H);
+        std::vector<float> matrices;
+        for (const Object& o : scene.objects) matrices.insert(matrices.end(), o.transform, o.transform + 12);
+        float lo[3] = { 1e30f, 1e30f, 1e30f }, hi[3] = { -1e30f, -1e30f, -1e30f };
+        for (const cgpt_vertex& v : mesh.vertices)
+            for (int a = 0; a < 3; ++a) { lo[a] = std::fmin(lo[a], v.pos[a]); hi[a] = std::fmax(hi[a], v.pos[a]); }
+        const float* const m0 = scene.objects[0].transform;               // the mesh's placement; the turn is about its centre in the world
+        double centre[3];
+        for (int r = 0; r < 3; ++r) centre[r] = m0[4 * r] * 0.5 * (lo[0] + hi[0]) + m0[4 * r + 1] * 0.5 * (lo[1] + hi[1]) + m0[4 * r + 2] * 0.5 * (lo[2] + hi[2]) + m0[4 * r + 3];
+        const cgpt_camera cam = scene.camera.Abi();
+        const cgpt_temporal_params tp = { 64.0f, 0.9f, 0.01f, CGPT_TEMPORAL_FOLLOW_TRANSFORMS };
+        for (uint32_t frame = 0; frame < 8; ++frame) {
+            const double angle = (double)spin_deg * (double)frame * 3.14159265358979 / 180.0, c = std::cos(angle), sn = std::sin(angle);
+            const double rot[3][3] = { { c, 0.0, sn }, { 0.0, 1.0, 0.0 }, { -sn, 0.0, c } };
+            for (int r = 0; r < 3; ++r) {                                // R (M0 p - centre) + centre
+                for (int k = 0; k < 3; ++k) matrices[4 * r + k] = (float)(rot[r][0] * m0[k] + rot[r][1] * m0[4 + k] + rot[r][2] * m0[8 + k]);
+                matrices[4 * r + 3] = (float)(rot[r][0] * (m0[3] - centre[0]) + rot[r][1] * (m0[7] - centre[1]) + rot[r][2] * (m0[11] - centre[2]) + centre[r]);
+            }
+            CHECK(cgpt_scene_update_transforms(ctx, matrices.data(), (uint32_t)scene.objects.size()));
+            CHECK(cgpt_reset_accumulator(ctx));
+            cgpt_render_params p{};
+            p.width = W; p.height = H; p.row_begin = 0; p.row_end = H;
+            p.first_sample = 0; p.n_samples = spp; p.seed = 0x12345678u + frame; p.kernel = CGPT_KERNEL_AUTO;
+            CHECK(cgpt_render(ctx, &cam, &settings, &p));
+            char name[64]; std::string err;
+            CHECK(cgpt_read_pixels(ctx, px.data(), px.size()));
+            snprintf(name, sizeof(name), "spin_%02u_raw.ppm", frame); WritePPM(name, px.data(), W, H, err);
+            CHECK(cgpt_denoise(ctx, &cam, nullptr, nullptr, 0, px.data(), px.size()));
+            snprintf(name, sizeof(name), "spin_%02u_denoised.ppm", frame); WritePPM(name, px.data(), W, H, err);
+            CHECK(cgpt_denoise_temporal(ctx, &cam, nullptr, &tp, nullptr, 0, px.data(), px.size()));   // once per rendered frame
+            snprintf(name, sizeof(name), "spin_%02u_temporal.ppm", frame); WritePPM(name, px.data(), W, H, err);
         }
         cgpt_ctx_destroy(ctx);
         return 0;

@@ -36,7 +36,8 @@ extern "C" {
                                  (cgpt_set_top_level); temporal reprojection added new symbols (cgpt_denoise_temporal,
                                  cgpt_temporal_reset, cgpt_read_temporal_history) and a new struct (cgpt_temporal_params) only;
                                  variance-guided edge stopping added new symbols (cgpt_denoise_variance_guided,
-                                 cgpt_read_variance) and a new struct (cgpt_variance_params) only */
+                                 cgpt_read_variance) and a new struct (cgpt_variance_params) only; following object transforms in
+                                 the temporal stage is a new enum value only (CGPT_TEMPORAL_FOLLOW_TRANSFORMS) */
 
 enum cgpt_status {
     CGPT_OK = 0,
@@ -293,8 +294,10 @@ int cgpt_scene_update_smooth_normals(cgpt_ctx* ctx, const uint32_t* smooth, uint
  * and det == 0, a det that is not finite, or an entry of A^-1 or of -A^-1 b that is not finite once rounded to float refuses; anything
  * but the identity on a sphere or a plane (cgpt_scene_update_primitive moves those) or on an object listed in light_indices (mesh-light
  * sampling reads the object-space triangles and area) -- all CGPT_ERR_INVALID.  The caller resets the accumulator.  The denoiser's cached
- * guides are recomputed: they hold position and normal.  A HIP failure during the write drops the scene; a multi-device context updates
- * every device. */
+ * guides are recomputed: they hold position and normal.  The temporal history (cgpt_denoise_temporal) is dropped, unless the next
+ * temporal call sets CGPT_TEMPORAL_FOLLOW_TRANSFORMS: that call carries the hits on the moved objects back through M_prev M_cur^-1 and
+ * keeps the history; until it has succeeded cgpt_read_temporal_history refuses.  A HIP failure during the write drops the scene; a
+ * multi-device context updates every device. */
 int cgpt_scene_update_transforms(cgpt_ctx* ctx, const float* object_to_world, uint32_t n_objects);
 
 /* ---- in-place geometry edits of the uploaded scene (no re-upload; the caller resets the accumulator, as with the materials) ----
@@ -492,13 +495,27 @@ int cgpt_denoise(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_pa
  * unless CGPT_TEMPORAL_KEEP_VIEW_DEPENDENT is set.  A pixel without history: c = c_0, H' = min(N, max_history).
  * The history is absent after cgpt_ctx_create, cgpt_temporal_reset and a call that failed, and when the band (width, height, rows), the
  * scene (every upload and in-place edit that recomputes the guides) or the demodulate flag differ from the call's.
- * Limits: camera motion only (moving objects are not reprojected: an edit drops the history); first-hit reprojection only (what is seen
+ * Moving objects (CGPT_TEMPORAL_FOLLOW_TRANSFORMS): without the flag every scene edit drops the history.  With it a
+ * history stored before one or more cgpt_scene_update_transforms calls stays usable as long as nothing else changed the scene (an
+ * upload, a material, smooth-normal, refit or primitive edit still drops it; the roughness setters keep it, as they do without the
+ * flag).  A pixel whose first hit lies on an object whose 12 matrix floats differ bytewise from those in force when the history was
+ * stored is carried back before the map above is applied: x' = D x with D = M_prev M_cur^-1 (a 3x4 affine) and n' = normalize(N n) with
+ * N = A_prev^-T A_cur^T, both matrices formed in double from the float entries and rounded to float once per entry, x' and n' evaluated
+ * in double and rounded to float once; the map, the four taps, the validity tests, the 0.01 floor and the merge then run on x', n', the
+ * unchanged t and object index.  A pixel on an unmoved object takes x and n untouched.  A call in which no object moved is the call
+ * without the flag bit for bit; one in which an object moved reprojects (and applies the view-dependent rule) even when the camera
+ * bytes equal the history's.  An object whose D or N has an entry that is not finite takes no history.  The stored history holds the
+ * current frame's own guides.  Limits: only mesh and stand-alone triangle objects can move (spheres, planes and lights take the
+ * identity only, and a sphere moved by cgpt_scene_update_primitive drops the history); a refit, also through an instanced placement,
+ * drops it; the light carried by the history is the old frames', so a moving object's shadow and the shading of a turning surface lag
+ * by up to max_history samples.
+ * Limits: without the flag camera motion only (an edit drops the history); first-hit reprojection only (what is seen
  * in a mirror or through glass is not followed); a multi-device context keeps the history on device_ids[0].
  * Like cgpt_denoise it leaves the accumulator, data.pixels, num_accumulated, cgpt_stats and the guides alone, and cgpt_denoise's output
  * does not depend on temporal calls.  Refusals (before any device work; nothing changes, the history included): every refusal of
  * cgpt_denoise; max_history not finite or < 1; normal_cos_min outside [-1, 1] or NaN; plane_tolerance not finite or <= 0; unknown
  * flag bits; cgpt_read_temporal_history without a history or with a wrong size -- all CGPT_ERR_INVALID. */
-enum cgpt_temporal_flags { CGPT_TEMPORAL_KEEP_VIEW_DEPENDENT = 1u };
+enum cgpt_temporal_flags { CGPT_TEMPORAL_KEEP_VIEW_DEPENDENT = 1u, CGPT_TEMPORAL_FOLLOW_TRANSFORMS = 4u };   /* 2u is no flag: it stays refused as an unknown bit, as before */
 typedef struct cgpt_temporal_params {
     float    max_history;      /* cap on a pixel's history length, in samples; finite, >= 1 */
     float    normal_cos_min;   /* a tap is valid only if n_prev . n_cur >= this; in [-1, 1] */
@@ -531,6 +548,8 @@ int cgpt_read_temporal_history(cgpt_ctx* ctx, float* dst, size_t n_floats);
  * Ke = min(K_h, max_history), l0 = l(c_0); without moments mu' = l0, v' = 0, K' = N.  A pixel with Ke + N >= min_history_frames N
  * takes var_t = v' N / (Ke + N), every other pixel var_s.  The moments are absent wherever and whenever the colour history is, and
  * after a cgpt_denoise_temporal call (which updates the colour without them).  Without the flag no history is read or written.
+ * CGPT_TEMPORAL_FOLLOW_TRANSFORMS in `temporal` means what it means for cgpt_denoise_temporal: the moments ride on the taps and weights
+ * of the carried-back hits.
  * iterations = 0 returns the unfiltered image (cgpt_denoise's, or with the flag cgpt_denoise_temporal's) and still estimates the variance.
  * Bands, multi-device contexts, stream and blocking are cgpt_denoise's.  The call leaves the accumulator, data.pixels, num_accumulated,
  * cgpt_stats and the guides alone, and the outputs of cgpt_denoise and cgpt_denoise_temporal do not depend on it.

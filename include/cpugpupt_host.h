@@ -134,6 +134,13 @@ uint32_t cgpth_fast_div(uint32_t n, uint32_t d);
 uint32_t cgpth_shade_item_blocks(uint32_t n_blocks, uint32_t n_waves, uint32_t chunk);
 uint32_t cgpth_shade_segment_blocks(uint32_t cap_blocks, uint32_t min_waves, uint32_t chunk);
 
+/* the per-object motion records of CGPT_TEMPORAL_FOLLOW_TRANSFORMS (csrc/device/transform_math.h), evaluated on the host: for
+ * n_objects matrices of 12 floats each as they were when the history was stored (`prev`, n_prev objects) and as they are now (`cur`),
+ * 24 words per object -- the rows {D row, translation} of D = M_prev M_cur^-1, then the rows {N row, 0} of N = A_prev^-T A_cur^T,
+ * with the state word (0 unmoved, 1 moved, 2 drop) in place of the fourth row's last float.  Returns the number of objects that are
+ * not unmoved.  tests/test_host_motion.py checks it word for word against tests/motion_ref.py. */
+uint32_t cgpth_motion_records(const float* prev, uint32_t n_prev, const float* cur, uint32_t n_objects, float* records_out);
+
 /* the device layout a cgpt_scene_upload of `scene` would install (csrc/device/device_scene.h), computed on the host with the same
  * validation, status and message (from cgpth_last_error()) as the upload; no GPU is touched.  tests/test_host_scene_layout.py checks
  * it against the layout's documentation.  The arrays live in thread-local storage of the library and stay valid until the next
