@@ -25,6 +25,7 @@ TRACE_COUNTERS, TRACE_REVERSED = 1, 2
 TEMPORAL_KEEP_VIEW_DEPENDENT = 1
 TEMPORAL_FOLLOW_TRANSFORMS = 4
 VARIANCE_TEMPORAL = 1
+SKIN_MAX_JOINTS = 1024      # cgpt_scene_set_skin
 
 f3 = C.c_float * 3
 
@@ -125,6 +126,7 @@ class BvhInfo(C.Structure):
 _vp = C.c_void_p
 _fp = C.POINTER(C.c_float)
 _up = C.POINTER(C.c_uint32)
+_u16p = C.POINTER(C.c_uint16)
 
 
 class SceneLayoutView(C.Structure):
@@ -173,6 +175,9 @@ PROTOTYPES = {
     "cgpt_scene_refit_mesh": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), C.c_uint32, _fp]),
     "cgpt_scene_export_bvh": (C.c_int, [_vp, C.c_uint32, C.POINTER(BvhNode), C.c_uint32]),
     "cgpt_scene_update_primitive": (C.c_int, [_vp, C.c_uint32, C.POINTER(Object)]),
+    "cgpt_scene_set_skin": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), _u16p, _fp, C.c_uint32, C.c_uint32]),
+    "cgpt_scene_skin_mesh": (C.c_int, [_vp, C.c_uint32, _fp, C.c_uint32]),
+    "cgpt_scene_clear_skin": (C.c_int, [_vp, C.c_uint32]),
     "cgpt_camera_from_view": (C.c_int, [_fp, _fp, C.c_float, C.c_float, C.POINTER(Camera)]),
     "cgpt_render": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(Settings), C.POINTER(RenderParams)]),
     "cgpt_reset_accumulator": (C.c_int, [_vp]),
@@ -240,6 +245,8 @@ PROTOTYPES = {
     "cgpth_scene_set_settings": (C.c_int, [_vp, C.POINTER(Settings)]),
     "cgpth_scene_rebuild_bvh": (C.c_int, [_vp, C.c_uint32, C.c_int]),
     "cgpth_scene_refit_mesh": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), C.c_uint32]),
+    "cgpth_skin_triangles": (C.c_int, [C.POINTER(Triangle), _u16p, _fp, C.c_uint32, _fp, C.c_uint32, C.POINTER(Triangle)]),
+    "cgpth_scene_skin_mesh": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), _u16p, _fp, C.c_uint32, _fp, C.c_uint32]),
     "cgpth_scene_update_primitive": (C.c_int, [_vp, C.c_uint32, C.POINTER(Object)]),
     "cgpth_scene_bvh_info": (C.c_int, [_vp, C.c_uint32, C.POINTER(BvhInfo)]),
     "cgpth_scene_bvh_export": (C.c_int, [_vp, C.c_uint32, C.POINTER(BvhNode), _up]),

@@ -73,6 +73,7 @@ int UploadArray(cgpt_ctx* ctx, DevBuf<T>& dst, const std::vector<T>& src)   // a
 void FreeScene(cgpt_ctx* ctx)
 {
     ctx->sb = SceneBuffers{};
+    ctx->skins.clear();                                                        // an upload drops every skin
     ctx->h_objects.clear(); ctx->refit_objects.clear(); ctx->record_perm.clear(); ctx->mesh_group.clear();
     ctx->footprint = cgpt_scene_footprint{};
     ctx->h_roughness.clear(); ctx->h_transmission_roughness.clear(); ctx->h_materials.clear(); ctx->h_lights.clear();
@@ -678,6 +679,11 @@ int cgpt_set_tuning(cgpt_ctx* ctx, const char* name, uint32_t value)
     if (!name) return CtxFail(ctx, CGPT_ERR_INVALID, "null knob name");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (strcmp(name, "skin_joints_lds") == 0) {                                // cgpt_scene_skin_mesh: where the kernel reads the joint matrices
+        if (value > 1u) return CtxFail(ctx, CGPT_ERR_INVALID, "skin_joints_lds %u is neither 0 (vector cache) nor 1 (LDS)", value);
+        ctx->skin_joints_lds = value;
+        return CGPT_OK;
+    }
     bool known = false;
     const int rc = PersistentSetTuning(ctx, name, value, &known);              // "pt_*" knobs
     if (known) return rc;

@@ -25,6 +25,16 @@ struct SceneBuffers {                             // cgpt_scene_upload installs 
     DevBuf<uint32_t> lights;
     DevBuf<uint32_t> refit_levels;
     DevBuf<cgpt_triangle> refit_staging;          // host triangles of the last refit, grown on demand
+    DevBuf<uint32_t> skin_scratch;                // cgpt_scene_skin_mesh: 8 words a pose reads back (refit.hip: kSkinScratchWords), allocated with the first skin
+};
+// The skin of one object (cgpt_scene_set_skin): the bind pose, 12 joint indices and 12 weights a triangle, and the room of a pose's
+// joint matrices.  Not part of the scene's footprint; an upload drops every skin.
+struct SkinBuffers {
+    DevBuf<cgpt_triangle> bind;
+    DevBuf<uint16_t> joints;
+    DevBuf<float> weights;
+    DevBuf<float> matrices;                       // 12 n_joints floats, written by every cgpt_scene_skin_mesh
+    uint32_t n_joints = 0;                        // 0: no skin
 };
 struct FrameBuffers {                             // the framebuffer band (EnsureFramebuffer)
     DevBuf<float4> accumulator;
@@ -86,6 +96,11 @@ struct cgpt_ctx {
     // cgpt_get_scene_footprint reports, filled by SceneInstall (no edit changes it)
     std::vector<uint32_t> mesh_group;
     cgpt_scene_footprint footprint{};
+    // skinning (cgpt_scene_set_skin): per object, empty or as long as h_objects; cleared with the scene.  skin_joints_lds is the
+    // cgpt_set_tuning knob "skin_joints_lds": 1 (default) the skin kernel stages the joint matrices in LDS, 0 it reads them through the
+    // vector cache (same results; DESIGN.md 5.26 has both timings)
+    std::vector<cgpt::SkinBuffers> skins;
+    uint32_t skin_joints_lds = 1;
 
     // framebuffer band
     cgpt::FrameBuffers fb;
@@ -190,6 +205,9 @@ int GroupSetNeeCandidates(cgpt_ctx* ctx, uint32_t candidates);
 int GroupSetTopLevel(cgpt_ctx* ctx, uint32_t mode);
 int GroupRefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris, float* total_area_out);
 int GroupUpdatePrimitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_object* obj);
+int GroupSetSkin(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* bind_triangles, const uint16_t* joints, const float* weights, uint32_t n_tris, uint32_t n_joints);
+int GroupSkinMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uint32_t n_joints);
+int GroupClearSkin(cgpt_ctx* ctx, uint32_t obj_index);
 int GroupRender(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p);
 int GroupResetAccumulator(cgpt_ctx* ctx);
 int GroupReadAccumulator(cgpt_ctx* ctx, float* dst, size_t n_floats);

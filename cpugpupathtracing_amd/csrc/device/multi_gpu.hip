@@ -369,6 +369,22 @@ int GroupUpdatePrimitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_object* o
     return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_update_primitive(m, obj_index, obj); });
 }
 
+// every member keeps its own skin buffers and poses its own copy
+int GroupSetSkin(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* bind_triangles, const uint16_t* joints, const float* weights, uint32_t n_tris, uint32_t n_joints)
+{
+    return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_set_skin(m, obj_index, bind_triangles, joints, weights, n_tris, n_joints); });
+}
+
+int GroupSkinMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uint32_t n_joints)
+{
+    return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_skin_mesh(m, obj_index, joint_matrices, n_joints); });
+}
+
+int GroupClearSkin(cgpt_ctx* ctx, uint32_t obj_index)
+{
+    return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_clear_skin(m, obj_index); });
+}
+
 int GroupUpdateRoughness(cgpt_ctx* ctx, const float* roughness, uint32_t n)
 {
     return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_update_roughness(m, roughness, n); });

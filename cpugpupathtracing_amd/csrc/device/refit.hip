@@ -15,6 +15,10 @@
 //     synchronisation).  The codes float4 is not written.
 // total_area is the sequential float sum of GetTriangleArea in original order (ref: BVH.cpp:22), summed on the host while the input is
 // read, and written into the object's DevObject (mesh-light sampling reads it).
+// Skinning (cgpt_scene_set_skin / cgpt_scene_skin_mesh): the same refit with the triangle pass fed from a bind pose, joint
+// indices and weights that stay on the device (skin_triangles poses each triangle by the arithmetic of csrc/host/skinning.h and writes the
+// records through the function refit_triangles writes them with), then the same bound pass.  No staging copy and no per-triangle host work:
+// the top-level box comes back from the refitted root record (or a one-block fold), and total_area is left as uploaded.
 // After cgpt_scene_upload_instanced the objects of a mesh group share the one copy these passes edit: the refit goes through any member's
 // RefitObject (they are equal), and the area and the top-level box, which are per object, are written for every member.
 #include <hip/hip_runtime.h>
@@ -31,6 +35,7 @@
 #include "device_scene.h"
 #include "minmax_std.h"
 #include "scene_layout.h"
+#include "skinning.h"
 
 namespace cgpt {
 
@@ -40,17 +45,11 @@ namespace {
 
 constexpr uint32_t kRefitThreads = 256;
 
-__global__ __launch_bounds__(kRefitThreads) void refit_triangles(const float* __restrict__ staging, float4* __restrict__ tri_leaf,
-                                                                 float4* __restrict__ tri_orig, float4* __restrict__ tri_normal,
-                                                                 uint32_t leaf_base, uint32_t tri_base, uint32_t n, uint32_t n_tris_total)
+// The records of one triangle, stated once for the refit's and the skin's triangle pass: tr is the cgpt_triangle (v0 {pos, normal}, v1, v2),
+// `leaf` its tri_leaf record with `keep` = leaf[2] as it was ({pad, e2.z, tri_idx, last_in_leaf}: pad, tri_idx and last_in_leaf stay), t = tri_idx
+__device__ __forceinline__ void write_triangle_records(const float (&tr)[18], float4* __restrict__ leaf, const float4 keep, float4* __restrict__ tri_orig,
+                                                       float4* __restrict__ tri_normal, uint32_t tri_base, uint32_t t, uint32_t n_tris_total)
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float4* leaf = tri_leaf + 3 * (size_t)(leaf_base + i);
-    const float4 keep = leaf[2];                                              // {pad, e2.z, tri_idx, last_in_leaf}
-    const uint32_t t = __float_as_uint(keep.z);
-    if (t >= n) return;                                                       // validated at upload
-    const float* tr = staging + 18 * (size_t)t;                               // cgpt_triangle: v0 {pos, normal}, v1, v2 (72 B, 8-byte aligned)
     const float p0x = tr[0], p0y = tr[1], p0z = tr[2], n0x = tr[3], n0y = tr[4], n0z = tr[5];
     const float p1x = tr[6], p1y = tr[7], p1z = tr[8], n1x = tr[9], n1y = tr[10], n1z = tr[11];
     const float p2x = tr[12], p2y = tr[13], p2z = tr[14], n2x = tr[15], n2y = tr[16], n2z = tr[17];
@@ -67,6 +66,112 @@ __global__ __launch_bounds__(kRefitThreads) void refit_triangles(const float* __
     float4* pair = tri_normal + n_tris_total + 2 * (size_t)(tri_base + t);    // PackNormalPair (device_scene.h: tri_normal)
     pair[0] = make_float4(n1x, n1y, n1z, 0.0f);
     pair[1] = make_float4(n2x, n2y, n2z, 0.0f);
+}
+
+__global__ __launch_bounds__(kRefitThreads) void refit_triangles(const float* __restrict__ staging, float4* __restrict__ tri_leaf,
+                                                                 float4* __restrict__ tri_orig, float4* __restrict__ tri_normal,
+                                                                 uint32_t leaf_base, uint32_t tri_base, uint32_t n, uint32_t n_tris_total)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float4* leaf = tri_leaf + 3 * (size_t)(leaf_base + i);
+    const float4 keep = leaf[2];                                              // {pad, e2.z, tri_idx, last_in_leaf}
+    const uint32_t t = __float_as_uint(keep.z);
+    if (t >= n) return;                                                       // validated at upload
+    const float* src = staging + 18 * (size_t)t;                              // cgpt_triangle: v0 {pos, normal}, v1, v2 (72 B, 8-byte aligned)
+    float tr[18];
+    for (int k = 0; k < 18; ++k) tr[k] = src[k];
+    write_triangle_records(tr, leaf, keep, tri_orig, tri_normal, tri_base, t, n_tris_total);
+}
+
+// The skin's triangle pass (cgpt_scene_skin_mesh; skinning.h states the arithmetic): refit_triangles with the posed triangle computed
+// here from the resident bind pose instead of gathered from a staging copy.  A thread per leaf slot, blocks striding over the slots so
+// that a block stages the joint matrices once: LDS true keeps the n_joints x 3 float4 rows in LDS (dynamic, 48 n_joints bytes: 48 KB at
+// the 1024-joint limit), false reads them through the vector cache.  The joint indices are per lane and were validated by
+// cgpt_scene_set_skin.  *range_flag is set when a posed position is not finite or lies beyond 1e30, where the refitted root bounds (a
+// fold from +-1e30) no longer give the top-level box.
+constexpr uint32_t kSkinMaxBlocks = 1024;                                     // 4 blocks a CU
+template <bool LDS>
+__global__ __launch_bounds__(kRefitThreads) void skin_triangles(const float2* __restrict__ bind, const uint2* __restrict__ joints, const float4* __restrict__ weights,
+                                                                const float4* __restrict__ matrices, uint32_t n_joints, float4* __restrict__ tri_leaf,
+                                                                float4* __restrict__ tri_orig, float4* __restrict__ tri_normal, uint32_t* __restrict__ range_flag,
+                                                                uint32_t leaf_base, uint32_t tri_base, uint32_t n, uint32_t n_tris_total)
+{
+    extern __shared__ float4 s_matrices[];
+    const float4* mat = matrices;
+    if (LDS) {
+        for (uint32_t k = threadIdx.x; k < 3 * n_joints; k += blockDim.x) s_matrices[k] = matrices[k];
+        __syncthreads();
+        mat = s_matrices;
+    }
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        float4* leaf = tri_leaf + 3 * (size_t)(leaf_base + i);
+        const float4 keep = leaf[2];                                          // {pad, e2.z, tri_idx, last_in_leaf}
+        const uint32_t t = __float_as_uint(keep.z);
+        if (t >= n) continue;                                                 // validated at upload
+        float tr[18];
+        bool in_range = true;
+        for (int c = 0; c < 3; ++c) {
+            const uint2 jw = joints[3 * (size_t)t + c];                       // four uint16_t: the corner's joints
+            const float4 w = weights[3 * (size_t)t + c];
+            const uint32_t j0 = jw.x & 0xFFFFu, j1 = jw.x >> 16, j2 = jw.y & 0xFFFFu, j3 = jw.y >> 16;
+            float m[12];
+            for (int r = 0; r < 3; ++r) {
+                const float4 a0 = mat[3 * j0 + r], a1 = mat[3 * j1 + r], a2 = mat[3 * j2 + r], a3 = mat[3 * j3 + r];
+                m[4 * r] = SkinBlend(w.x, a0.x, w.y, a1.x, w.z, a2.x, w.w, a3.x);
+                m[4 * r + 1] = SkinBlend(w.x, a0.y, w.y, a1.y, w.z, a2.y, w.w, a3.y);
+                m[4 * r + 2] = SkinBlend(w.x, a0.z, w.y, a1.z, w.z, a2.z, w.w, a3.z);
+                m[4 * r + 3] = SkinBlend(w.x, a0.w, w.y, a1.w, w.z, a2.w, w.w, a3.w);
+            }
+            const float2 b0 = bind[9 * (size_t)t + 3 * c], b1 = bind[9 * (size_t)t + 3 * c + 1], b2 = bind[9 * (size_t)t + 3 * c + 2];
+            const float pn[6] = { b0.x, b0.y, b1.x, b1.y, b2.x, b2.y };
+            SkinCorner(m, pn, tr + 6 * c);
+            in_range = in_range && fabsf(tr[6 * c]) <= 1e30f && fabsf(tr[6 * c + 1]) <= 1e30f && fabsf(tr[6 * c + 2]) <= 1e30f;   // false for a NaN too
+        }
+        write_triangle_records(tr, leaf, keep, tri_orig, tri_normal, tri_base, t, n_tris_total);
+        if (!in_range) atomicOr(range_flag, 1u);
+    }
+}
+
+// TriangleBounds (scene_layout.hip) of an object's n triangles as tri_orig holds them: words 1..6 of `out` get min / max of the vertex
+// positions by < and >, word 7 is 1 where a position is not finite.  One block: the top-level box of a leaf-rooted mesh or a triangle
+// object, which has no root record to read, and of a pose that set the range flag.
+constexpr uint32_t kSkinScratchWords = 8;                                     // {range flag, lo.xyz, hi.xyz, not finite}
+__global__ __launch_bounds__(kRefitThreads) void fold_object_box(const float4* __restrict__ tri_orig, uint32_t tri_base, uint32_t n, uint32_t* __restrict__ out)
+{
+    __shared__ float s_box[kRefitThreads][6];
+    __shared__ uint32_t s_bad[kRefitThreads];
+    float box[6] = { INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY };
+    uint32_t bad = 0u;
+    for (uint32_t t = threadIdx.x; t < n; t += blockDim.x) {
+        const float4* o = tri_orig + 3 * (size_t)(tri_base + t);
+        for (int v = 0; v < 3; ++v) {
+            const float4 q = o[v];
+            const float x[3] = { q.x, q.y, q.z };
+            for (int a = 0; a < 3; ++a) {
+                if (!(fabsf(x[a]) < INFINITY)) bad = 1u;
+                if (x[a] < box[a]) box[a] = x[a];
+                if (x[a] > box[3 + a]) box[3 + a] = x[a];
+            }
+        }
+    }
+    for (int a = 0; a < 6; ++a) s_box[threadIdx.x][a] = box[a];
+    s_bad[threadIdx.x] = bad;
+    __syncthreads();
+    for (uint32_t stride = blockDim.x / 2; stride > 0; stride /= 2) {
+        if (threadIdx.x < stride) {
+            for (int a = 0; a < 3; ++a) {
+                if (s_box[threadIdx.x + stride][a] < s_box[threadIdx.x][a]) s_box[threadIdx.x][a] = s_box[threadIdx.x + stride][a];
+                if (s_box[threadIdx.x + stride][3 + a] > s_box[threadIdx.x][3 + a]) s_box[threadIdx.x][3 + a] = s_box[threadIdx.x + stride][3 + a];
+            }
+            s_bad[threadIdx.x] |= s_bad[threadIdx.x + stride];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        for (int a = 0; a < 6; ++a) out[1 + a] = __float_as_uint(s_box[0][a]);
+        out[7] = s_bad[0];
+    }
 }
 
 struct Box { float lo[3], hi[3]; };
@@ -141,6 +246,20 @@ int SceneLost(cgpt_ctx* ctx, const char* what, hipError_t e)
         if (e_ != hipSuccess) return SceneLost((ctx), #expr, e_);                                                       \
     } while (0)
 
+// the bound pass behind either triangle pass: one launch per level of the object's tree, deepest first, in stream order
+hipError_t LaunchRefitLevels(cgpt_ctx* ctx, const RefitObject& ro, uint32_t tri_base)
+{
+    for (size_t level = ro.level_offsets.empty() ? 0 : ro.level_offsets.size() - 1; level-- > 0;) {
+        const uint32_t first = ro.level_offsets[level], n = ro.level_offsets[level + 1] - first;
+        if (n == 0) continue;
+        hipLaunchKernelGGL(refit_level, dim3((n + kRefitThreads - 1) / kRefitThreads), dim3(kRefitThreads), 0, ctx->stream,
+                           ctx->sb.node_pairs.p, ctx->sb.tri_leaf.p, ctx->sb.tri_orig.p, ctx->sb.refit_levels.p + ro.level_begin + first, n, tri_base);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 int RefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris, float* total_area_out)
 {
     int rc = CheckObject(ctx, obj_index);
@@ -177,13 +296,7 @@ int RefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles,
     hipLaunchKernelGGL(refit_triangles, dim3((n_tris + kRefitThreads - 1) / kRefitThreads), dim3(kRefitThreads), 0, ctx->stream,
                        reinterpret_cast<const float*>(ctx->sb.refit_staging.p), ctx->sb.tri_leaf.p, ctx->sb.tri_orig.p, ctx->sb.tri_normal.p, ro.leaf_base, tri_base, n_tris, ctx->scene.n_tris_total);
     REFIT_HIP_WRITING(ctx, hipGetLastError());
-    for (size_t level = ro.level_offsets.empty() ? 0 : ro.level_offsets.size() - 1; level-- > 0;) {
-        const uint32_t first = ro.level_offsets[level], n = ro.level_offsets[level + 1] - first;
-        if (n == 0) continue;
-        hipLaunchKernelGGL(refit_level, dim3((n + kRefitThreads - 1) / kRefitThreads), dim3(kRefitThreads), 0, ctx->stream,
-                           ctx->sb.node_pairs.p, ctx->sb.tri_leaf.p, ctx->sb.tri_orig.p, ctx->sb.refit_levels.p + ro.level_begin + first, n, tri_base);
-        REFIT_HIP_WRITING(ctx, hipGetLastError());
-    }
+    REFIT_HIP_WRITING(ctx, LaunchRefitLevels(ctx, ro, tri_base));
     if (d.kind == CGPT_OBJECT_MESH) {
         for (const uint32_t j : members) {
             ctx->h_objects[j].total_area = area;
@@ -194,6 +307,115 @@ int RefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles,
     REFIT_HIP_WRITING(ctx, WriteTopLevel(ctx, ctx->h_objects, top));
     ctx->top_state.local_box.swap(top.local_box);
     if (total_area_out) *total_area_out = area;
+    return CGPT_OK;
+}
+
+// ---- skinning (cgpt_scene_set_skin / cgpt_scene_skin_mesh / cgpt_scene_clear_skin) -----------------------------------
+int SetSkin(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* bind, const uint16_t* joints, const float* weights, uint32_t n_tris, uint32_t n_joints)
+{
+    int rc = CheckObject(ctx, obj_index);
+    if (rc != CGPT_OK) return rc;
+    const DevObject& d = ctx->h_objects[obj_index];
+    const RefitObject& ro = ctx->refit_objects[obj_index];
+    if (d.kind != CGPT_OBJECT_MESH && d.kind != CGPT_OBJECT_TRIANGLE)
+        return CtxFail(ctx, CGPT_ERR_INVALID, "object %u is a %s: it has no triangles to skin", obj_index, KindName(d.kind));
+    for (const uint32_t li : ctx->h_lights)
+        if (li == obj_index) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u is a light: a pose does not recompute the area its sampling reads, so it takes no skin", obj_index);
+    if (!bind || !joints || !weights) return CtxFail(ctx, CGPT_ERR_INVALID, "%s is null", !bind ? "bind_triangles" : !joints ? "joints" : "weights");
+    if (n_tris != ro.tri_count) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u has %u triangles, got %u (a skin keeps the topology)", obj_index, ro.tri_count, n_tris);
+    std::string why;
+    if (!CheckSkin(bind, joints, weights, n_tris, n_joints, why)) return CtxFail(ctx, CGPT_ERR_INVALID, "%s", why.c_str());
+
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                           // nothing uses the skin this one replaces
+    SkinBuffers sk;                                                            // installed whole, or not at all
+    HIP_TRY(ctx, sk.bind.Alloc(n_tris));
+    HIP_TRY(ctx, sk.joints.Alloc(12 * (size_t)n_tris));
+    HIP_TRY(ctx, sk.weights.Alloc(12 * (size_t)n_tris));
+    HIP_TRY(ctx, sk.matrices.Alloc(12 * (size_t)n_joints));
+    HIP_TRY(ctx, ctx->sb.skin_scratch.Grow(kSkinScratchWords));
+    HIP_TRY(ctx, hipMemcpy(sk.bind.p, bind, sizeof(cgpt_triangle) * (size_t)n_tris, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(sk.joints.p, joints, sizeof(uint16_t) * 12 * (size_t)n_tris, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(sk.weights.p, weights, sizeof(float) * 12 * (size_t)n_tris, hipMemcpyHostToDevice));
+    sk.n_joints = n_joints;
+    if (ctx->skins.size() != ctx->h_objects.size()) ctx->skins.resize(ctx->h_objects.size());
+    ctx->skins[obj_index] = std::move(sk);
+    return CGPT_OK;
+}
+
+int SkinMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uint32_t n_joints)
+{
+    int rc = CheckObject(ctx, obj_index);
+    if (rc != CGPT_OK) return rc;
+    if (obj_index >= ctx->skins.size() || ctx->skins[obj_index].n_joints == 0u)
+        return CtxFail(ctx, CGPT_ERR_INVALID, "object %u has no skin (cgpt_scene_set_skin installs one)", obj_index);
+    const SkinBuffers& sk = ctx->skins[obj_index];
+    if (n_joints != sk.n_joints) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u's skin has %u joints, got %u", obj_index, sk.n_joints, n_joints);
+    std::string why;
+    if (!CheckJointMatrices(joint_matrices, n_joints, why)) return CtxFail(ctx, CGPT_ERR_INVALID, "%s", why.c_str());
+    const DevObject& d = ctx->h_objects[obj_index];
+    const RefitObject& ro = ctx->refit_objects[obj_index];
+    const uint32_t n_tris = ro.tri_count, tri_base = d.tri_base;
+    TopLevelState top = ctx->top_state;                                        // may throw: before the first write
+
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(sk.matrices.p, joint_matrices, sizeof(float) * 12 * (size_t)n_joints, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->sb.skin_scratch.p, 0, sizeof(uint32_t) * kSkinScratchWords, ctx->stream));
+
+    // from here on the scene changes
+    const dim3 grid(std::min((n_tris + kRefitThreads - 1) / kRefitThreads, kSkinMaxBlocks)), block(kRefitThreads);
+    const auto launch = [&](auto kernel, size_t lds_bytes) {
+        hipLaunchKernelGGL(kernel, grid, block, lds_bytes, ctx->stream, reinterpret_cast<const float2*>(sk.bind.p), reinterpret_cast<const uint2*>(sk.joints.p),
+                           reinterpret_cast<const float4*>(sk.weights.p), reinterpret_cast<const float4*>(sk.matrices.p), n_joints, ctx->sb.tri_leaf.p,
+                           ctx->sb.tri_orig.p, ctx->sb.tri_normal.p, ctx->sb.skin_scratch.p, ro.leaf_base, tri_base, n_tris, ctx->scene.n_tris_total);
+    };
+    if (ctx->skin_joints_lds) launch(skin_triangles<true>, 3 * sizeof(float4) * (size_t)n_joints);
+    else launch(skin_triangles<false>, 0);
+    REFIT_HIP_WRITING(ctx, hipGetLastError());
+    REFIT_HIP_WRITING(ctx, LaunchRefitLevels(ctx, ro, tri_base));
+
+    // The top-level tree's box of the object, TriangleBounds of the pose (what RefitMesh computes on the host): the refitted root record's two
+    // sides where the object has one and every position lies within the +-1e30 its fold starts from, else a fold of tri_orig on the device
+    uint32_t scratch[kSkinScratchWords];
+    float4 root[3];
+    const bool leaf_root = (d.root_code & kLeafBit) != 0u;
+    const auto fold = [&]() -> hipError_t {
+        hipLaunchKernelGGL(fold_object_box, dim3(1), dim3(kRefitThreads), 0, ctx->stream, ctx->sb.tri_orig.p, tri_base, n_tris, ctx->sb.skin_scratch.p);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipMemcpy(scratch, ctx->sb.skin_scratch.p, sizeof(scratch), hipMemcpyDeviceToHost);
+        return e;
+    };
+    if (leaf_root) {
+        REFIT_HIP_WRITING(ctx, fold());
+    } else {
+        REFIT_HIP_WRITING(ctx, hipStreamSynchronize(ctx->stream));
+        REFIT_HIP_WRITING(ctx, hipMemcpy(scratch, ctx->sb.skin_scratch.p, sizeof(scratch), hipMemcpyDeviceToHost));
+        if (scratch[0] != 0u) REFIT_HIP_WRITING(ctx, fold());
+        else REFIT_HIP_WRITING(ctx, hipMemcpy(root, ctx->sb.node_pairs.p + 4 * (size_t)d.root_code, sizeof(root), hipMemcpyDeviceToHost));
+    }
+    float* box = top.local_box.data() + 6 * (size_t)obj_index;
+    if (leaf_root || scratch[0] != 0u) {
+        if (scratch[7] != 0u) UnboundedBox(box);
+        else memcpy(box, scratch + 1, 24);
+    } else {
+        box[0] = min_std(root[0].x, root[0].y); box[1] = min_std(root[0].z, root[0].w); box[2] = min_std(root[1].x, root[1].y);
+        box[3] = max_std(root[1].z, root[1].w); box[4] = max_std(root[2].x, root[2].y); box[5] = max_std(root[2].z, root[2].w);
+    }
+    for (uint32_t j = 0; j < ctx->mesh_group.size(); ++j)                      // every placement of the group moves (RefitMesh)
+        if (j != obj_index && ctx->mesh_group[j] == ctx->mesh_group[obj_index]) memcpy(top.local_box.data() + 6 * (size_t)j, box, 24);
+    REFIT_HIP_WRITING(ctx, WriteTopLevel(ctx, ctx->h_objects, top));
+    ctx->top_state.local_box.swap(top.local_box);
+    return CGPT_OK;
+}
+
+int ClearSkin(cgpt_ctx* ctx, uint32_t obj_index)
+{
+    if (obj_index >= ctx->skins.size() || ctx->skins[obj_index].n_joints == 0u) return CGPT_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->skins[obj_index] = SkinBuffers{};
     return CGPT_OK;
 }
 
@@ -318,6 +540,29 @@ int cgpt_scene_refit_mesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle
     if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupRefitMesh(ctx, obj_index, triangles, n_tris, total_area_out); });
     ctx->scene_generation++; ctx->shape_generation++;                          // the denoiser's guides are stale (denoise.hip)
     return Guarded(ctx, __func__, [&] { return RefitMesh(ctx, obj_index, triangles, n_tris, total_area_out); });
+}
+
+int cgpt_scene_set_skin(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* bind_triangles, const uint16_t* joints, const float* weights,
+                        uint32_t n_tris, uint32_t n_joints)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupSetSkin(ctx, obj_index, bind_triangles, joints, weights, n_tris, n_joints); });
+    return Guarded(ctx, __func__, [&] { return SetSkin(ctx, obj_index, bind_triangles, joints, weights, n_tris, n_joints); });   // the scene does not change
+}
+
+int cgpt_scene_skin_mesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uint32_t n_joints)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupSkinMesh(ctx, obj_index, joint_matrices, n_joints); });
+    ctx->scene_generation++; ctx->shape_generation++;                          // as a refit: guides and temporal history are stale
+    return Guarded(ctx, __func__, [&] { return SkinMesh(ctx, obj_index, joint_matrices, n_joints); });
+}
+
+int cgpt_scene_clear_skin(cgpt_ctx* ctx, uint32_t obj_index)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupClearSkin(ctx, obj_index); });
+    return Guarded(ctx, __func__, [&] { return ClearSkin(ctx, obj_index); });
 }
 
 int cgpt_scene_export_bvh(cgpt_ctx* ctx, uint32_t obj_index, cgpt_bvh_node* nodes_out, uint32_t n_nodes)

@@ -3,6 +3,7 @@
 #include <exception>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "cpugpupt_host.h"
 #include "fast_div.h"
@@ -11,6 +12,7 @@
 #include "mesh_gen.h"
 #include "scene.h"
 #include "shade_items.h"
+#include "skinning.h"
 #include "transform_math.h"
 
 using namespace cgpt;
@@ -452,6 +454,41 @@ int cgpth_scene_refit_mesh(cgpth_scene* scene, uint32_t obj_index, const cgpt_tr
         if (o.has_bvh) { if (!o.bvh->Refit(triangles, n_tris)) return Fail("refit failed"); }
         else o.triangle = triangles[0];
         return CGPT_OK;
+    });
+}
+
+int cgpth_skin_triangles(const cgpt_triangle* bind_triangles, const uint16_t* joints, const float* weights, uint32_t n_tris,
+                         const float* joint_matrices, uint32_t n_joints, cgpt_triangle* out_triangles)
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        std::string err;
+        if (!CheckSkin(bind_triangles, joints, weights, n_tris, n_joints, err) || !CheckJointMatrices(joint_matrices, n_joints, err)) return Fail(err);
+        if (!out_triangles) return Fail("out_triangles is null");
+        SkinTriangles(bind_triangles, joints, weights, n_tris, joint_matrices, out_triangles);
+        return CGPT_OK;
+    });
+}
+
+int cgpth_scene_skin_mesh(cgpth_scene* scene, uint32_t obj_index, const cgpt_triangle* bind_triangles, const uint16_t* joints, const float* weights,
+                          uint32_t n_tris, const float* joint_matrices, uint32_t n_joints)
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        if (!scene) return Fail("scene is null");
+        if (obj_index >= scene->scene.objects.size())
+            return Fail("object " + std::to_string(obj_index) + " out of range (" + std::to_string(scene->scene.objects.size()) + " objects)");
+        const Object& o = scene->scene.objects[obj_index];
+        if (!o.has_bvh && o.kind != CGPT_OBJECT_TRIANGLE)
+            return Fail("object " + std::to_string(obj_index) + " is a " + KindName(o) + ": it has no triangles to skin");
+        for (const uint32_t li : scene->scene.light_source_indices)
+            if (li == obj_index) return Fail("object " + std::to_string(obj_index) + " is a light: a pose does not recompute the area its sampling reads, so it takes no skin");
+        const uint32_t n = o.has_bvh ? o.bvh->NumTriangles() : 1u;
+        if (n_tris != n)
+            return Fail("object " + std::to_string(obj_index) + " has " + std::to_string(n) + " triangles, got " + std::to_string(n_tris) + " (a skin keeps the topology)");
+        std::string err;
+        if (!CheckSkin(bind_triangles, joints, weights, n_tris, n_joints, err) || !CheckJointMatrices(joint_matrices, n_joints, err)) return Fail(err);
+        std::vector<cgpt_triangle> posed(n_tris);
+        SkinTriangles(bind_triangles, joints, weights, n_tris, joint_matrices, posed.data());
+        return cgpth_scene_refit_mesh(scene, obj_index, posed.data(), n_tris);
     });
 }
 

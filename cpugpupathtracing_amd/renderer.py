@@ -11,7 +11,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _native as N
-from .scene import Scene, Settings, _triangle_ptr, _triangle_rows, primitive_abi
+from .scene import Scene, Settings, _joint_matrices, _skin_arrays, _triangle_ptr, _triangle_rows, primitive_abi
 
 
 _IDENTITY = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float32)
@@ -182,6 +182,28 @@ class Renderer:
         area = C.c_float()
         self._check(self.L.cgpt_scene_refit_mesh(self._ctx, obj_index, _triangle_ptr(rows), rows.shape[0], C.byref(area)))
         return area.value
+
+    def set_skin(self, obj_index: int, bind_triangles, joints, weights, n_joints: int):
+        """cgpt_scene_set_skin: keeps a skin for uploaded mesh (or triangle object) `obj_index` on the device -- its bind pose ((n, 18)
+        triangles in the object's original order, as refit_mesh takes them), four joint indices and four weights per triangle corner
+        ((n, 3, 4) each) -- for skin_mesh to pose from.  The scene does not change until the first skin_mesh.  A second
+        call replaces the skin; upload() drops every skin; a light, a sphere or a plane takes none.  n_joints: 1..1024."""
+        rows, j, w = _skin_arrays(bind_triangles, joints, weights)
+        self._check(self.L.cgpt_scene_set_skin(self._ctx, obj_index, _triangle_ptr(rows), j.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                               w.ctypes.data_as(C.POINTER(C.c_float)), rows.shape[0], int(n_joints)))
+
+    def skin_mesh(self, obj_index: int, matrices):
+        """cgpt_scene_skin_mesh: poses skinned object `obj_index` on the device from its joint matrices, (n_joints, 3, 4) or
+        (n_joints, 12) float32, the rows of [A | b] of each joint's object-space skinning matrix (glTF: jointGlobal x inverseBind).
+        Always from the bind pose; the tree is kept and its bounds follow, as after refit_mesh(obj_index, scene.skin_triangles(...)),
+        except that total_area keeps its uploaded value.  Only the device copy changes: the host Scene is not touched (Scene.skin_mesh
+        is the mirror).  Call reset_accumulator() before the next frame."""
+        m = _joint_matrices(matrices)
+        self._check(self.L.cgpt_scene_skin_mesh(self._ctx, obj_index, m.ctypes.data_as(C.POINTER(C.c_float)), m.shape[0]))
+
+    def clear_skin(self, obj_index: int):
+        """cgpt_scene_clear_skin: frees the skin of object `obj_index`; the geometry stays at the last pose.  No skin: nothing happens."""
+        self._check(self.L.cgpt_scene_clear_skin(self._ctx, obj_index))
 
     def export_bvh(self, obj_index: int) -> np.ndarray:
         """The device's tree of mesh `obj_index` as it is now (after refits): nodes[n,8] uint32 words in the reference's 32-byte layout

@@ -101,6 +101,41 @@ def _triangle_ptr(rows: np.ndarray):
     return rows.ctypes.data_as(C.POINTER(N.Triangle))
 
 
+def _skin_arrays(bind_triangles, joints, weights):
+    """A skin as the library takes it: (n, 18) float32 bind triangles, 12 n uint16 joint indices, 12 n float32 weights."""
+    rows = _triangle_rows(bind_triangles)
+    j = np.ascontiguousarray(joints)
+    if j.dtype != np.uint16:
+        if j.size and (j.min() < 0 or j.max() > 0xFFFF):
+            raise ValueError("joint indices must fit uint16")
+        j = j.astype(np.uint16)
+    j = np.ascontiguousarray(j.ravel())
+    w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
+    if j.size != 12 * rows.shape[0] or w.size != 12 * rows.shape[0]:
+        raise ValueError("joints and weights hold 12 entries per triangle: four per corner")
+    return rows, j, w
+
+
+def _joint_matrices(matrices) -> np.ndarray:
+    m = np.ascontiguousarray(matrices, dtype=np.float32)
+    if m.size % 12:
+        raise ValueError("joint matrices are (n_joints, 3, 4) or (n_joints, 12)")
+    return m.reshape(-1, 12)
+
+
+def skin_triangles(bind_triangles, joints, weights, matrices) -> np.ndarray:
+    """Linear blend skinning on the host (cgpth_skin_triangles): the (n, 18) float32 triangles of the pose.
+    bind_triangles: (n, 18) as triangles_from_arrays returns them; joints / weights: (n, 3, 4) -- four influences per corner;
+    matrices: (n_joints, 3, 4) or (n_joints, 12) float32, the rows of [A | b] of each joint's object-space skinning matrix.
+    It is what Renderer.skin_mesh computes on the device, to the bit."""
+    rows, j, w = _skin_arrays(bind_triangles, joints, weights)
+    m = _joint_matrices(matrices)
+    out = np.empty_like(rows)
+    _host_check(N.lib().cgpth_skin_triangles(_triangle_ptr(rows), j.ctypes.data_as(C.POINTER(C.c_uint16)), w.ctypes.data_as(C.POINTER(C.c_float)),
+                                             rows.shape[0], m.ctypes.data_as(C.POINTER(C.c_float)), m.shape[0], _triangle_ptr(out)), "skin_triangles")
+    return out
+
+
 def primitive_abi(kind: int, mat_index: int, center=None, radius=None, normal=None, point=None) -> N.Object:
     """A cgpt_object for update_primitive: a sphere (center, radius) or a plane (normal, point)."""
     o = N.Object()
@@ -410,6 +445,16 @@ class Scene:
         (triangles_from_arrays).  The tree is kept; node bounds, total_area, centroids follow the new triangles (cgpth_scene_refit_mesh)."""
         rows = _triangle_rows(triangles)
         _host_check(N.lib().cgpth_scene_refit_mesh(self._h, obj_index, _triangle_ptr(rows), rows.shape[0]), "refit_mesh")
+
+    def skin_mesh(self, obj_index: int, bind_triangles, joints, weights, matrices):
+        """The host mirror of Renderer.set_skin + Renderer.skin_mesh (cgpth_scene_skin_mesh): refit_mesh of
+        skin_triangles(bind_triangles, joints, weights, matrices).  The host scene keeps no skin: every call takes it whole.  A light, a
+        sphere or a plane is refused, as on the device."""
+        rows, j, w = _skin_arrays(bind_triangles, joints, weights)
+        m = _joint_matrices(matrices)
+        _host_check(N.lib().cgpth_scene_skin_mesh(self._h, obj_index, _triangle_ptr(rows), j.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                                  w.ctypes.data_as(C.POINTER(C.c_float)), rows.shape[0], m.ctypes.data_as(C.POINTER(C.c_float)),
+                                                  m.shape[0]), "skin_mesh")
 
     def update_primitive(self, obj_index: int, center=None, radius=None, normal=None, point=None):
         """Primitive::RenderImGui's sliders (ref: Primitives.cpp:385-410): a sphere's center / radius or a plane's normal / point;

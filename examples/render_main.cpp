@@ -4,7 +4,7 @@
 //
 //   g++ -std=c++17 -Iinclude -Icpugpupathtracing_amd/csrc/host examples/render_main.cpp
 //       -Lcpugpupathtracing_amd/lib -lcpugpupt -Wl,-rpath,$PWD/cpugpupathtracing_amd/lib -o render_main   (one command line)
-//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--spin DEG] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
+//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--spin DEG] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [--bend DEG] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
 // --gpus N: ONE context over the first N GPUs of the node (cgpt_ctx_create with n_devices = N): every frame is spread over them in
 // interleaved row bands and the read-back gathers the float4 bands with one RCCL exchange over xGMI; the loop below does not
 // change.  --collective: take that code path with N = 1 too (what a one-GPU box can test).
@@ -41,6 +41,10 @@
 // (cgpt_scene_update_smooth_normals after the upload; without it the reference's flat v0.normal).
 // --mesh-transform m00 m01 m02 m03 m10 .. m23: the mesh (object 0, the dragon or its stand-in) is placed by this object-to-world matrix, the
 // rows of [A | b] with world = A p + b (cgpt_scene_update_transforms after the upload); the other objects keep the identity.
+// --bend DEG: a deforming mesh -- the mesh (object 0) gets a procedural two-joint skin on the device (cgpt_scene_set_skin: the weights come from a
+// vertex's height between the mesh's lowest and highest point) and is posed once per frame of the loop below (cgpt_scene_skin_mesh; joint 1 turns
+// about the x axis through the middle of the mesh, a little further every frame up to DEG degrees), each frame from a reset accumulator
+// (DESIGN.md 5.26).  A demonstration of the device calls, not a loader feature: glTF skins are not imported.
 // move_at > 0 scripts the input half of Update(dt) (ref: Main.cpp:277-297, Camera::Update :104-131): after that many samples the
 // camera is translated by (right, up, forward) as the A/D, Space/Shift, W/S keys would, the view changes, and the accumulator
 // is reset (ref: ResetAccumulator, Main.cpp:238-243) before the remaining samples are rendered from the new position.
@@ -67,7 +71,7 @@ using namespace cgpt;
 
 int main(int argc, char** argv)
 {
-    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool spin = false; float spin_deg = 0.0f; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false; uint32_t n_instances = 0;
+    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool spin = false; float spin_deg = 0.0f; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false; uint32_t n_instances = 0; bool bend = false; float bend_deg = 0.0f;
     bool has_transform = false; float mesh_transform[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
     MeshBVH::BuildOption bvh_option = MeshBVH::BuildOption_SAHSplitIntervals;
     while (argc > 1 && std::string(argv[1]).rfind("--", 0) == 0) {
@@ -76,6 +80,7 @@ int main(int argc, char** argv)
         else if (std::string(argv[1]) == "--denoise") { denoise = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--temporal") { temporal = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--spin" && argc > 2) { spin = true; spin_deg = (float)atof(argv[2]); argv += 2; argc -= 2; }
+        else if (std::string(argv[1]) == "--bend" && argc > 2) { bend = true; bend_deg = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--variance-guided") { variance_guided = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--smooth") { smooth = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--mesh-transform" && argc > 13) {
@@ -225,6 +230,29 @@ int main(int argc, char** argv)
         cgpt_ctx_destroy(ctx);
         return 0;
     }
+    // --bend: a procedural two-joint skin of the mesh (object 0).  A corner's weight on joint 1 is its height between the mesh's lowest and
+    // highest point; joint 0 stays, joint 1 turns about the x axis through the middle of the mesh.  The skin goes to the device once.
+    float bend_pivot[3] = { 0.0f, 0.0f, 0.0f };
+    if (bend) {
+        const cgpt_object& o = desc.objects[0];
+        const cgpt_triangle* bind = desc.triangles + o.tri_offset;      // original order, as cgpt_scene_refit_mesh takes them
+        float lo[3] = { 1e30f, 1e30f, 1e30f }, hi[3] = { -1e30f, -1e30f, -1e30f };
+        for (uint32_t t = 0; t < o.tri_count; ++t)
+            for (const cgpt_vertex* v : { &bind[t].v0, &bind[t].v1, &bind[t].v2 })
+                for (int a = 0; a < 3; ++a) { lo[a] = std::fmin(lo[a], v->pos[a]); hi[a] = std::fmax(hi[a], v->pos[a]); }
+        for (int a = 0; a < 3; ++a) bend_pivot[a] = 0.5f * (lo[a] + hi[a]);
+        std::vector<uint16_t> joints(12 * (size_t)o.tri_count, 0);
+        std::vector<float> weights(12 * (size_t)o.tri_count, 0.0f);
+        for (uint32_t t = 0; t < o.tri_count; ++t) {
+            const cgpt_vertex* const corner[3] = { &bind[t].v0, &bind[t].v1, &bind[t].v2 };
+            for (int c = 0; c < 3; ++c) {
+                const float h = hi[1] > lo[1] ? (corner[c]->pos[1] - lo[1]) / (hi[1] - lo[1]) : 0.0f;
+                joints[12 * (size_t)t + 4 * c + 1] = 1;
+                weights[12 * (size_t)t + 4 * c] = 1.0f - h; weights[12 * (size_t)t + 4 * c + 1] = h;
+            }
+        }
+        CHECK(cgpt_scene_set_skin(ctx, 0, bind, joints.data(), weights.data(), o.tri_count, 2));
+    }
     uint32_t num_accumulated = 0;                                        // data.num_accumulated
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<uint32_t> pixels((size_t)W * H), denoised(denoise ? (size_t)W * H : 0);
@@ -237,6 +265,17 @@ int main(int argc, char** argv)
                 CHECK(cgpt_reset_accumulator(ctx));
                 num_accumulated = 0;
             }
+        }
+        if (bend) {                                                      // the pose of this frame: 48 bytes a joint go to the device
+            const uint32_t n_frames = (spp + chunk - 1) / chunk;
+            const double angle = (double)bend_deg * (double)(frame / chunk + 1) / (double)n_frames * 3.14159265358979 / 180.0, c = std::cos(angle), sn = std::sin(angle);
+            const float py = bend_pivot[1], pz = bend_pivot[2];
+            const float joint_matrices[24] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0,                                    // joint 0 stays
+                                               1, 0, 0, 0, 0, (float)c, (float)-sn, (float)(py - c * py + sn * pz),    // joint 1: R_x (p - pivot) + pivot
+                                               0, (float)sn, (float)c, (float)(pz - sn * py - c * pz) };
+            CHECK(cgpt_scene_skin_mesh(ctx, 0, joint_matrices, 2));
+            CHECK(cgpt_reset_accumulator(ctx));
+            num_accumulated = 0;
         }
         cgpt_render_params p{};
         p.width = W; p.height = H; p.row_begin = 0; p.row_end = H;

@@ -37,7 +37,8 @@ extern "C" {
                                  cgpt_temporal_reset, cgpt_read_temporal_history) and a new struct (cgpt_temporal_params) only;
                                  variance-guided edge stopping added new symbols (cgpt_denoise_variance_guided,
                                  cgpt_read_variance) and a new struct (cgpt_variance_params) only; following object transforms in
-                                 the temporal stage is a new enum value only (CGPT_TEMPORAL_FOLLOW_TRANSFORMS) */
+                                 the temporal stage is a new enum value only (CGPT_TEMPORAL_FOLLOW_TRANSFORMS); skinning added new
+                                 symbols only (cgpt_scene_set_skin, cgpt_scene_skin_mesh, cgpt_scene_clear_skin) */
 
 enum cgpt_status {
     CGPT_OK = 0,
@@ -238,7 +239,8 @@ int cgpt_scene_upload(cgpt_ctx* ctx, const cgpt_scene_desc* scene);
  * An added export: CGPT_ABI_VERSION stays 2. */
 int cgpt_scene_upload_instanced(cgpt_ctx* ctx, const cgpt_scene_desc* scene);
 /* What the uploaded scene occupies, after either upload (CGPT_ERR_NO_SCENE without one; a multi-device context reports one device, and
- * every device holds the same).  No edit changes it.  An added export: CGPT_ABI_VERSION stays 2. */
+ * every device holds the same).  No edit changes it; the skin buffers of cgpt_scene_set_skin are not counted.  An added export:
+ * CGPT_ABI_VERSION stays 2. */
 typedef struct cgpt_scene_footprint {
     uint64_t device_bytes;       /* bytes of the scene's allocations on one device: the triangle, node, normal, material, object and light
                                   * arrays, the refit levels and the room of the top-level tree (not the framebuffer, not a refit's staging) */
@@ -318,6 +320,42 @@ int cgpt_scene_export_bvh(cgpt_ctx* ctx, uint32_t obj_index, cgpt_bvh_node* node
 /* Primitive::RenderImGui's sliders (ref: Primitives.cpp:385-410): a sphere's centre and radius (radius^2 = r*r, as at upload) or a
  * plane's normal and point.  obj->kind and obj->mat_index must equal the uploaded ones; the other fields of *obj are ignored. */
 int cgpt_scene_update_primitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_object* obj);
+
+/* ---- skinning: pose a mesh on the device from joint matrices (linear blend skinning, four influences per triangle corner) ----
+ * The bind pose, the joint indices and the weights stay on the device; a pose is a write of n_joints x 48 bytes and one kernel in
+ * front of the refit's bound pass, with no per-triangle work on the host (csrc/host/skinning.h states the arithmetic
+ * and cgpth_skin_triangles evaluates it on the host, tests/skin_ref.py in numpy).  Added exports: CGPT_ABI_VERSION stays 2.
+ *
+ * cgpt_scene_set_skin: copies bind_triangles (n_tris triangles in the object's original order, as cgpt_scene_refit_mesh takes them),
+ * joints and weights (12 n_tris entries each: corner c of triangle t has joints[12 t + 4 c + k] and weights[12 t + 4 c + k], k < 4) to
+ * device buffers the context owns (72 + 24 + 48 bytes a triangle, on every device of a multi-device context).  THE SCENE DOES NOT
+ * CHANGE: the geometry moves at the first cgpt_scene_skin_mesh.  A second call on the same object replaces its skin.  Meshes and
+ * stand-alone triangle objects (n_tris = 1).  Refused before any device write, with nothing changed: no scene (CGPT_ERR_NO_SCENE); a
+ * NULL array, an object out of range, a sphere or a plane, an object listed in light_indices (mesh-light sampling reads total_area,
+ * which a pose does not recompute), n_tris other than the uploaded count, n_joints 0 or above 1024, a joint index >= n_joints, a weight
+ * or a bind float that is not finite (CGPT_ERR_INVALID).
+ *
+ * cgpt_scene_skin_mesh: poses the object from joint_matrices -- n_joints (the skin's) x 12 floats, the rows of [A | b], row-major, the
+ * layout of cgpt_scene_update_transforms: object-space skinning matrices (for glTF, jointGlobal * inverseBind).  A pose is always
+ * computed from the bind pose, never from the previous pose.  Afterwards the device scene is what
+ * cgpt_scene_refit_mesh(obj_index, <cgpth_skin_triangles of the skin and the matrices>) would have left, bit for bit -- the triangle
+ * records, both normal records, every node's bounds, the top-level box -- WITH ONE EXCEPTION: the object's total_area keeps its
+ * uploaded value.  Only mesh-light sampling reads it, and a skinned object cannot be a light.  Weights are used as given (never
+ * renormalised, a zero weight's joint is still read); the blended A moves the normal, not its inverse transpose (exact for rigid
+ * joints and uniform scale).  Everything else follows the refit: the caller resets the accumulator; the denoiser's guides are
+ * recomputed and the temporal history is dropped, CGPT_TEMPORAL_FOLLOW_TRANSFORMS included; transforms (the pose is in object space:
+ * it appears at A pose + b), smooth flags, materials and roughnesses are kept; after cgpt_scene_upload_instanced every placement of
+ * the object's group moves; a multi-device context poses every device's copy from that device's skin buffers; a HIP failure after the
+ * first write drops the scene.  Refused, with nothing changed: no scene (CGPT_ERR_NO_SCENE); an object out of range or without a
+ * skin, n_joints other than the skin's, joint_matrices NULL or an entry that is not finite (CGPT_ERR_INVALID).
+ *
+ * cgpt_scene_clear_skin: frees the object's skin buffers; the geometry stays at the last pose.  CGPT_OK without a skin on the object.
+ * cgpt_scene_upload and cgpt_scene_upload_instanced drop every skin.  cgpt_scene_refit_mesh on a skinned object works as before and
+ * keeps the skin; the next pose overwrites what it wrote. */
+int cgpt_scene_set_skin(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* bind_triangles, const uint16_t* joints, const float* weights,
+                        uint32_t n_tris, uint32_t n_joints);
+int cgpt_scene_skin_mesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uint32_t n_joints);
+int cgpt_scene_clear_skin(cgpt_ctx* ctx, uint32_t obj_index);
 
 /* UpdateScreenPlane (ref: Main.cpp:98-102,143-149): fov in degrees, plane at distance fov-in-radians (SURVEY A-13) */
 int cgpt_camera_from_view(const float pos[3], const float view_dir[3], float fov_deg, float aspect, cgpt_camera* out);
@@ -573,7 +611,9 @@ int cgpt_read_variance(cgpt_ctx* ctx, float* dst, size_t n_floats);
 /* ---- tuning and measurement aids (no reference counterpart) ------------------------------------------------------- */
 /* Overrides one tuning knob of the wavefront pipeline for this context (the CGPT_WF_* environment variables set the same
  * knobs process-wide; names are the variable names without the prefix, lower case: "pools", "batch", "max_batch",
- * "refill", "inner_repeat", ...; DESIGN.md 5.1 lists them).  Results never depend on a knob, only speed does. */
+ * "refill", "inner_repeat", ...; DESIGN.md 5.1 lists them).  Results never depend on a knob, only speed does.
+ * "skin_joints_lds" (0 | 1, default 1) is cgpt_scene_skin_mesh's: whether its kernel stages the joint matrices in LDS or reads them
+ * through the vector cache. */
 int cgpt_set_tuning(cgpt_ctx* ctx, const char* name, uint32_t value);
 /* Measures the vector-instruction issue rate of the device -- the roof bench.py prices the trace kernel against: every
  * SIMD of every CU runs `iters` x 64 independent instructions of one kind per wave at `waves_per_simd` resident waves.

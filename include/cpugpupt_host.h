@@ -101,6 +101,20 @@ int cgpth_scene_rebuild_bvh_device(cgpth_scene* scene, uint32_t obj_index, int b
  * bounds and centroids (a later Rebuild re-splits on them), total_area and node bounds follow the new triangles; a triangle object
  * (n_tris = 1) is replaced.  On failure the scene is unchanged. */
 int cgpth_scene_refit_mesh(cgpth_scene* scene, uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris);
+/* Linear blend skinning, the host statement of cgpt_scene_skin_mesh's triangle pass (csrc/host/skinning.h states the operations and
+ * their order; tests/skin_ref.py the same in numpy): out_triangles[t] is bind_triangles[t] with every corner moved by
+ * the blend of its four joints -- joints[12 t + 4 c + k] and weights[12 t + 4 c + k] for corner c, influence k -- of joint_matrices
+ * (n_joints x 12 floats, the rows of [A | b]).  No influence is skipped and weights are never renormalised; the blended A moves the
+ * normal (renormalised; the bind normal where the result has no finite positive length).  Refused with CGPT_ERR_INVALID and nothing
+ * written: a NULL array, n_joints 0 or above 1024, a joint index >= n_joints, a weight, bind float or matrix entry that is not finite. */
+int cgpth_skin_triangles(const cgpt_triangle* bind_triangles, const uint16_t* joints, const float* weights, uint32_t n_tris,
+                         const float* joint_matrices, uint32_t n_joints, cgpt_triangle* out_triangles);
+/* cgpth_skin_triangles followed by cgpth_scene_refit_mesh of the result: the host statement of cgpt_scene_set_skin +
+ * cgpt_scene_skin_mesh (the host scene keeps no skin; unlike the device call total_area follows the pose, as after any host refit).
+ * Refused as the two device calls refuse, with the scene unchanged: a bad index, a sphere or a plane, a light, n_tris other than the
+ * object's count, and what cgpth_skin_triangles refuses. */
+int cgpth_scene_skin_mesh(cgpth_scene* scene, uint32_t obj_index, const cgpt_triangle* bind_triangles, const uint16_t* joints, const float* weights,
+                          uint32_t n_tris, const float* joint_matrices, uint32_t n_joints);
 /* the host statement of cgpt_scene_update_primitive: a sphere's centre and radius, or a plane's normal and point */
 int cgpth_scene_update_primitive(cgpth_scene* scene, uint32_t obj_index, const cgpt_object* obj);
 /* reorders the objects: the new object k is the old object order[k] (a permutation of 0 .. n_objects - 1, else refused and nothing
