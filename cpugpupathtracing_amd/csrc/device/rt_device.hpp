@@ -479,10 +479,17 @@ __device__ __forceinline__ bool probe_leaf(const DevScene& sc, uint32_t code, V3
     }
     return hit;
 }
+// The closest hit of a decided ray, where it is a light (LIGHTS): the intersectors accept only t < ray_t and the walk is in object order, so
+// the object of the last accepted hit is IntersectScene's ray.obj.  Its material sits at a wave-uniform address too: read inside the walk,
+// with scalar loads, and only for an object that some lane hit.
+struct ProbeLight { bool is_light; V3 emissive; float intensity; };
 // The walk's control flow is wave-uniform (object kinds, root codes and leaf ends are scalars): a lane that turns undecided walks on
 // with the others and its answer is dropped; the wave stops early once every lane is undecided.
-__device__ __forceinline__ uint32_t probe_scene(const DevScene& sc, V3 o, V3 d, float& ray_t)
+// LIGHTS with `lights` (wave-uniform) set: `light` describes the closest hit's material as far as a hit on a light needs it.
+template <bool LIGHTS = false>
+__device__ __forceinline__ uint32_t probe_scene(const DevScene& sc, V3 o, V3 d, float& ray_t, ProbeLight* light = nullptr, bool lights = false)
 {
+    if (LIGHTS) { light->is_light = false; light->emissive = mk(0.0f); light->intensity = 0.0f; }
     const V3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);                    // Ray ctor, ref: Primitives.h:64
     bool undecided = has_infinite_component(inv);
     const RaySlab rs = make_ray_slab(o, inv);
@@ -521,6 +528,16 @@ __device__ __forceinline__ uint32_t probe_scene(const DevScene& sc, V3 o, V3 d, 
             hit = intersect_triangle(lt.v0, lt.e1, lt.e2, o, d, ray_t);
         }
         any = any || hit;
+        if (LIGHTS && lights && __builtin_amdgcn_ballot_w64(hit) != 0ull) {
+            const CGPT_UNIFORM f4v* const m = (const CGPT_UNIFORM f4v*)sc.materials + 4u * (size_t)obj.mat_index;   // load_material's c and d
+            const f4v md = m[3];
+            const bool lit = __float_as_uint(md.y) != 0u;
+            if (hit) light->is_light = lit;
+            if (lit) {
+                const f4v mc = m[2];
+                if (hit) { light->emissive = mk(mc.y, mc.z, mc.w); light->intensity = md.x; }
+            }
+        }
     }
     return undecided ? kProbeUndecided : (any ? kProbeHit : kProbeMiss);
 }

@@ -306,6 +306,14 @@ enum : uint32_t { kBounceTerminate = 1u, kBounceShadow = 2u, kBounceEnergy = 4u,
 // bits 4-5: the lobe that made the next ray when it is a function of the traced ray and its hit alone (wavefront shade: specular chains)
 enum : uint32_t { kBounceChainShift = 4u, kChainReflect = 1u, kChainRefract = 2u, kChainTir = 3u };
 
+// A hit on a light ends the path and draws no number; its emission counts where NEE has not sampled it already (ref: Main.cpp:424-431).
+// True: ps.energy was added to.  (wavefront shade calls it too, for an extend ray its probe decides as a hit on a light.)
+__device__ __forceinline__ bool add_light_hit(const DevSettings& st, PathState& ps, V3 emissive, float intensity)
+{
+    if (!st.nee || ps.depth == 0 || ps.is_specular) { ps.energy = ps.energy + ps.throughput * emissive * intensity; return true; }
+    return false;
+}
+
 // Processes the hit of `ray` (already traced).  On return: `ray` is the next extend ray unless kBounceTerminate is set;
 // if kBounceShadow is set, `shadow` / `pending` describe the NEE connection to trace (energy += pending when unoccluded,
 // ref: Main.cpp:452-463).  Emissive energy is added here; the final debug-view overrides are applied by the caller.
@@ -325,13 +333,7 @@ __device__ __forceinline__ uint32_t shade_bounce(const DevScene& sc, const DevSe
 
     const Hit hit = get_hit<COUNT, ReadsSmoothNormals(LOBES), HonoursTransforms(LOBES)>(sc, ray, cnt);
     const Mat mat = load_material(sc, hit.mat);
-    if (mat.is_light) {                                                       // ref: Main.cpp:424-431
-        if (!st.nee || ps.depth == 0 || ps.is_specular) {
-            ps.energy = ps.energy + ps.throughput * mat.emissive * mat.intensity;
-            return kBounceTerminate | kBounceEnergy;
-        }
-        return kBounceTerminate;
-    }
+    if (mat.is_light) return add_light_hit(st, ps, mat.emissive, mat.intensity) ? kBounceTerminate | kBounceEnergy : kBounceTerminate;   // ref: Main.cpp:424-431
 
     uint32_t result = 0;
     const float diffuse_weight = max_std(0.0f, 1.0f - mat.specular - mat.refractivity);

@@ -93,6 +93,7 @@ struct WfDev {
     uint32_t spec_keys;                // entries per pixel
     uint32_t spec_epoch;               // 1..0xFFFF, new for every shade launch: entries of other epochs are free
     uint32_t probe;                    // wf_shade resolves the rays that probe_scene() decides itself (wf_shade: "Probe")
+    uint32_t probe_lights;             // ... and ends the path of a fresh extend ray that it decides as a hit on a light (wf_shade: "Probe")
 };
 
 // Specular chains.  The reference does not jitter (SURVEY A-14), so all samples of a pixel share the primary ray and its hit, and
@@ -373,7 +374,8 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs, const Wf
     // halves of the mesh's box, the ground quad and the light spheres -- shadow rays of ground pixels towards the lights, their bounce
     // rays into the sky.  probe_scene() (rt_device.hpp) answers those here, from the registers that hold the ray, with the trace kernels'
     // own intersectors: a decided shadow ray is never listed (unoccluded: its pending radiance goes to st_en now, the connect epilogue's
-    // read-modify-write moved; occluded: dropped), an extend ray decided as a miss ends its path now instead of in the next round.  Each
+    // read-modify-write moved; occluded: dropped), an extend ray decided as a miss ends its path now instead of in the next round, and so
+    // does one decided as a hit whose closest object is a light (probe_lights; the emission the next round would add is added here).  Each
     // is still one IntersectScene call of the reference and is counted as one.  Not probed: the counting kernels (they walk as the oracle
     // walks), TracePath lanes, the debug views (they read the last depth), rays of a specular chain (the election and its followers stay
     // as they are) and a ray re-traced after total internal reflection (wf_trace does not walk it at all: its hit is known).
@@ -532,6 +534,8 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs, const Wf
                 chain = choice != 0u && chain != 0u && chain <= (kChainMax - 2u) / 3u ? chain * 3u + choice - 1u : 0u;
             }
             bool connect = false;                                             // the shadow ray is decided and reaches its light
+            bool light_added = false;                                         // the extend ray is decided as a hit on a light whose emission counts:
+            V3 light_energy = mk(0.0f);                                       // the next round's addition (0 + throughput * emissive * intensity)
             if (!COUNT && shade_kernargs().wf.probe != 0u && !(BRUTE && brute_path)) {
                 if (emit_sh) {                                                // (each probe reads the scene through a view of its own: what the shadow probe
                     float t = shadow.t;                                       // holds in scalar registers is dead before the extend probe starts)
@@ -541,7 +545,20 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs, const Wf
                 }
                 if (emit_ext && !(kChains && chain != 0u) && ray.t == 1e34f) {
                     float t = ray.t;
-                    decided_ext = probe_scene(shade_kernargs().args.scene, ray.o, ray.d, t) == kProbeMiss;
+                    ProbeLight pl;
+                    const uint32_t seen = probe_scene<true>(shade_kernargs().args.scene, ray.o, ray.d, t, &pl, shade_kernargs().wf.probe_lights != 0u);
+                    decided_ext = seen == kProbeMiss;
+                    // Decided as a hit on a light: the next round's pass would do nothing for this path but shade_bounce's light branch -- no
+                    // number drawn, the emission added or not by ps as this bounce leaves it -- so that happens here and the path ends: no slot,
+                    // no state, no list entry.  One case stays with the lists: the emission would be added and this bounce's shadow ray is listed.
+                    // The next trace adds that ray's pending radiance before the next shade adds the emission, and the sum keeps that order (a
+                    // shadow ray decided here is added below, before the emission).  Only a specular lobe of a material with a diffuse part gets there.
+                    if (seen == kProbeHit && pl.is_light) {
+                        PathState next = ps;                                      // the state that pass would start from
+                        next.energy = mk(0.0f);
+                        const bool adds = add_light_hit(shade_kernargs().args.settings, next, pl.emissive, pl.intensity);
+                        if (!(adds && emit_sh && !decided_sh)) { decided_ext = true; light_added = adds; light_energy = next.energy; }
+                    }
                 }
                 emit_sh = emit_sh && !decided_sh;
                 emit_ext = emit_ext && !decided_ext;
@@ -551,14 +568,15 @@ __global__ void __launch_bounds__(256, 1) wf_shade(const DevRenderArgs, const Wf
             const WfDev& wf = shade_kernargs().wf;                            // the stores: slot and state addresses formed here, not before the probes
             const bool final_depth_needed = shade_kernargs().args.settings.debug_mode == 1u && !emit_ext;      // ray-depth view reads the last depth
             const bool own_energy = is_pixel && (first_round || (flags & (kBounceEnergy | kBounceBruteDone)) || final_depth_needed);
-            if (own_energy || connect) {
+            if (own_energy || connect || light_added) {
                 float4 en;
                 if (first_round || (BRUTE && (flags & kBounceBruteDone))) { en.x = 0.0f; en.y = 0.0f; en.z = 0.0f; en.w = 0.0f; }
                 else en = ld_stream(&wf.st_en[pid]);
                 if (BRUTE && (flags & kBounceBruteDone)) { en.x = ps.energy.x; en.y = ps.energy.y; en.z = ps.energy.z; }   // TracePath's return value, as it is
                 if (flags & kBounceEnergy) { en.x += ps.energy.x; en.y += ps.energy.y; en.z += ps.energy.z; }
-                if (own_energy) en.w = __uint_as_float(ps.depth & 0xFFu);
+                if (own_energy || light_added) en.w = __uint_as_float(ps.depth & 0xFFu);   // (the next round's pass leaves the depth this bounce ends with)
                 if (connect) { en.x += pending.x; en.y += pending.y; en.z += pending.z; }   // ref: Main.cpp:454-463, as wf_trace's connect epilogue adds it
+                if (light_added) { en.x += light_energy.x; en.y += light_energy.y; en.z += light_energy.z; }   // the record that pass would have stored
                 st_stream(&wf.st_en[pid], en);
             }
             if (emit_ext) {                                                   // the path lives on: state + next extend ray, same slot
@@ -791,6 +809,7 @@ struct WfTuning {               // defaults measured on MI355X (profiles/r01); o
     uint32_t probe_max_objects = 128; // ... in scenes of at most this many objects: the probe walks all of them for every ray, as trace does; with 4 to
                                       // 128 objects (the bench scene + far-away spheres) probe 1 took 0.87-0.91 of probe 0's time at every count
                                       // (profiles/r10/probe_objects.txt), so the default is the largest count measured
+    uint32_t probe_lights = 1;        // a fresh extend ray the probe decides as a hit on a light ends its path in that pass (0: listed, traced and shaded)
 };
 
 static uint32_t Gcd(uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; }
@@ -939,7 +958,7 @@ static const Knob<WfTuning> kKnobs[] = {
     { "lds_tris", &WfTuning::lds_tris, 0, 1 },             { "first_lean", &WfTuning::first_lean, 0, 1 },                     { "bands", &WfTuning::bands, 1, kMaxBands },             { "bands_min_paths", &WfTuning::bands_min_paths, 0, 0x7FFFFFFF },
     { "spec_dedupe", &WfTuning::spec_dedupe, 0, 1 },       { "spec_keys", &WfTuning::spec_keys, 1, 16 },
     { "spec_epochs", &WfTuning::spec_epochs, 1, 0xFFFF },   { "probe", &WfTuning::probe, 0, 1 },
-    { "probe_max_objects", &WfTuning::probe_max_objects, 0, 4096 },
+    { "probe_max_objects", &WfTuning::probe_max_objects, 0, 4096 }, { "probe_lights", &WfTuning::probe_lights, 0, 1 },
 };
 
 static WfHost* WfGetHost(cgpt_ctx* ctx)
@@ -1153,6 +1172,7 @@ int LaunchWavefront(cgpt_ctx* ctx, const DevRenderArgs& args_in, ShadeVariant v)
         // (probe_scene tests mesh roots against the world ray: with a transformed object in the scene the probe is off; it walks the object
         // list, not the tree: off with the tree as well)
         wf.probe = h->tune.probe && !count && !xform && !tree && args_in.settings.debug_mode == 0u && args_in.scene.n_objects <= h->tune.probe_max_objects ? 1u : 0u;
+        wf.probe_lights = h->tune.probe_lights;
         // segments of waves that a smaller shade grid does not launch must read as empty
         if (k < n_pools) LAUNCH_TRY(hipMemsetAsync(wf.seg_count, 0, 2 * (size_t)kMaxBands * wf.n_segs * sizeof(uint32_t), st));
         for (uint32_t r = 0; r < rounds; ++r) {
