@@ -24,6 +24,7 @@ DENOISE_DEMODULATE_ALBEDO = 1
 TRACE_COUNTERS, TRACE_REVERSED = 1, 2
 TEMPORAL_KEEP_VIEW_DEPENDENT = 1
 TEMPORAL_FOLLOW_TRANSFORMS = 4
+TEMPORAL_FOLLOW_POSES = 16
 VARIANCE_TEMPORAL = 1
 SKIN_MAX_JOINTS = 1024      # cgpt_scene_set_skin
 
@@ -203,6 +204,7 @@ PROTOTYPES = {
                                         C.c_size_t]),
     "cgpt_temporal_reset": (C.c_int, [_vp]),
     "cgpt_read_temporal_history": (C.c_int, [_vp, _fp, C.c_size_t]),
+    "cgpt_read_previous_hits": (C.c_int, [_vp, _fp, C.c_size_t]),
     "cgpt_denoise_variance_guided": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(DenoiseParams), C.POINTER(TemporalParams),
                                                C.POINTER(VarianceParams), _fp, C.c_size_t, _up, C.c_size_t]),
     "cgpt_read_variance": (C.c_int, [_vp, _fp, C.c_size_t]),

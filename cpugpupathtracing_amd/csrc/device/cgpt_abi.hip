@@ -73,7 +73,7 @@ int UploadArray(cgpt_ctx* ctx, DevBuf<T>& dst, const std::vector<T>& src)   // a
 void FreeScene(cgpt_ctx* ctx)
 {
     ctx->sb = SceneBuffers{};
-    ctx->skins.clear();                                                        // an upload drops every skin
+    ctx->skins.clear(); ctx->pose_stamp.clear();                               // an upload drops every skin
     ctx->h_objects.clear(); ctx->refit_objects.clear(); ctx->record_perm.clear(); ctx->mesh_group.clear();
     ctx->footprint = cgpt_scene_footprint{};
     ctx->h_roughness.clear(); ctx->h_transmission_roughness.clear(); ctx->h_materials.clear(); ctx->h_lights.clear();

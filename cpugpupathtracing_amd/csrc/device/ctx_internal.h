@@ -35,7 +35,32 @@ struct SkinBuffers {
     DevBuf<float> weights;
     DevBuf<float> matrices;                       // 12 n_joints floats, written by every cgpt_scene_skin_mesh
     uint32_t n_joints = 0;                        // 0: no skin
+    // CGPT_TEMPORAL_FOLLOW_POSES (denoise.hip): the joint matrices of the last successful cgpt_scene_skin_mesh through this skin, or
+    // pose_known = false ("no pose known": before the first pose, after a cgpt_scene_refit_mesh of the object or of a placement that shares
+    // its copy, and after a pose through another skin of the same copy); serial names this installation among all of the context's
+    std::vector<float> pose;
+    bool pose_known = false;
+    uint64_t serial = 0;
 };
+// What the temporal history keeps of the poses it was stored under (StoreTemporalKey): per object the index of the object whose skin
+// posed its copy (-1: no pose known) and, at that index, the skin's serial and matrices.
+struct PoseSnapshot {
+    std::vector<int32_t> owner;
+    std::vector<uint64_t> serial;
+    std::vector<std::vector<float>> matrices;
+};
+// One object's entry of the table the carry-back kernel reads (denoise.hip: pose_carry_back): 96 bytes, six float4
+struct PoseRecord {
+    uint32_t state;                               // transform_math.h: MotionState -- 0 unposed since the history, 1 re-posed, 2 drop
+    uint32_t matrix_base;                         // state 1: the history's joint matrices start at float4 3 * matrix_base of dn.pose_matrices
+    uint32_t tri_base, smooth;                    // DevObject::tri_base and ::smooth of the object
+    const float2* bind;                           // state 1: the skin's arrays, as skin_triangles reads them
+    const uint2* joints;
+    const float4* weights;
+    uint32_t n_tris, pad;                         // the object's triangle count
+    float xform[12];                              // the object's current object-to-world matrix (top_state.xform)
+};
+static_assert(sizeof(PoseRecord) == 96, "six float4 per object");
 struct FrameBuffers {                             // the framebuffer band (EnsureFramebuffer)
     DevBuf<float4> accumulator;
     DevBuf<uint32_t> pixels;
@@ -51,6 +76,12 @@ struct DenoiseBuffers {                           // denoise.hip; each group is 
     DevBuf<float4> moments[2];                    // ... per pixel {mu, v, K, 0} of the luminance, beside history[] (the same slot)
     DevBuf<float4> motion;                        // CGPT_TEMPORAL_FOLLOW_TRANSFORMS: 6 float4 per object (transform_math.h: MotionRecord), grown on
                                                   // demand and written only by a call in which an object moved
+    // CGPT_TEMPORAL_FOLLOW_POSES
+    DevBuf<uint32_t> guide_tri;                   // per pixel, beside guides: the first hit's triangle in the object's original order (0: a miss, a
+                                                  // sphere, a plane, a triangle object); written by guides_tri_kernel, which runs while a skin exists
+    DevBuf<float4> pose_table;                    // 6 float4 per object (PoseRecord), grown on demand, written by a call in which a pose changed
+    DevBuf<float4> pose_matrices;                 // ... the history's joint matrices of every re-posed skin, 3 float4 per joint
+    DevBuf<float4> previous_hits;                 // 2 float4 per pixel {x_p.xyz, bits(state) | n_p.xyz, 0}: pose_carry_back's output (cgpt_read_previous_hits)
 };
 template <class... B> void ResetAll(B&... b) { (b.Reset(), ...); }
 // What the uploaded scene has that a kernel variant must carry: a roughness > 0, a transmission roughness > 0, a smooth-normal flag (they live in
@@ -101,6 +132,12 @@ struct cgpt_ctx {
     // vector cache (same results; DESIGN.md 5.26 has both timings)
     std::vector<cgpt::SkinBuffers> skins;
     uint32_t skin_joints_lds = 1;
+    // CGPT_TEMPORAL_FOLLOW_POSES: pose_generation counts the cgpt_scene_skin_mesh calls (they bump the other two generations as well);
+    // pose_stamp[i] is its value at the last pose that wrote object i's copy (empty or as long as h_objects; cleared with the scene);
+    // skin_serial numbers the cgpt_scene_set_skin installations
+    uint64_t pose_generation = 0;
+    std::vector<uint64_t> pose_stamp;
+    uint64_t skin_serial = 0;
 
     // framebuffer band
     cgpt::FrameBuffers fb;
@@ -135,11 +172,13 @@ struct cgpt_ctx {
     // the denoiser (denoise.hip): first-hit guides cached per camera, band and scene, and the filter's ping-pong buffers
     uint64_t scene_generation = 0;                // bumped by every scene upload and in-place edit
     uint64_t shape_generation = 0;                // ... by each of them but cgpt_scene_update_transforms: what a history that follows the transforms is kept across
+                                                  // (pose_generation, with the skins above: ... by cgpt_scene_skin_mesh alone)
     cgpt::DenoiseBuffers dn;
     bool guides_valid = false;
     uint64_t guide_generation = 0;                // what the guides were computed for
     cgpt_camera guide_camera{};
     uint32_t guide_frame[4] = { 0, 0, 0, 0 };     // width, height, first global row, rows
+    bool guide_tri_valid = false;                 // dn.guide_tri belongs to the cached guides (guides_tri_kernel computed them)
     // the temporal history (cgpt_denoise_temporal): dn.history[temporal_slot] and what it was stored for
     bool temporal_valid = false;
     uint32_t temporal_slot = 0;
@@ -152,6 +191,15 @@ struct cgpt_ctx {
     uint64_t temporal_shape_generation = 0;
     std::vector<float> temporal_xform;
     std::vector<cgpt::MotionRecord> motion_records;
+    // CGPT_TEMPORAL_FOLLOW_POSES: the pose generation and the poses the history was stored for; the host copies of dn.pose_table and
+    // dn.pose_matrices of the last call in which a pose changed (they outlive the asynchronous copies); previous_hits_valid:
+    // dn.previous_hits holds the records of the last successful flagged call that launched pose_carry_back, for previous_hits_frame
+    uint64_t temporal_pose_generation = 0;
+    cgpt::PoseSnapshot temporal_poses;
+    std::vector<cgpt::PoseRecord> pose_records;
+    std::vector<float> pose_matrices;
+    bool previous_hits_valid = false;
+    uint32_t previous_hits_frame[4] = { 0, 0, 0, 0 };
     // the variance-guided filter (cgpt_denoise_variance_guided): dn.moments[temporal_slot] belongs to the temporal history when
     // moments_valid (a cgpt_denoise_temporal call updates the colour without them); dn.variance is the last successful call's map
     bool moments_valid = false;

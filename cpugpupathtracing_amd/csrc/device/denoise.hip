@@ -20,6 +20,9 @@
 // (same object, normal, tangent plane) and merges c = (He c_h + N c_0) / (He + N).  The passes then run on c.
 // With CGPT_TEMPORAL_FOLLOW_TRANSFORMS (tests/motion_ref.py) a history outlives cgpt_scene_update_transforms calls: the
 // hits on the objects whose matrices changed are first carried back through M_prev M_cur^-1 (temporal_merge<.., MOTION = true>).
+// With CGPT_TEMPORAL_FOLLOW_POSES (tests/pose_motion_ref.py) it outlives cgpt_scene_skin_mesh calls: pose_carry_back
+// computes, per pixel, where the hit's surface point was under the pose the history was stored with (cgpt_read_previous_hits), from
+// the first hit's triangle (guides_tri_kernel) and the history's joint matrices, and temporal_merge<.., POSE = true> reprojects from there.
 //
 // Variance-guided edge stopping (cgpt_denoise_variance_guided, cgpt_read_variance; tests/variance_ref.py states it in
 // numpy): the colour edge-stop of the passes becomes exp(-|l(c_q) - l(c_p)| / (sigma_l sqrt(gbar(p)) + 1e-6)), l the luminance and gbar
@@ -36,6 +39,7 @@
 #include "device_scene.h"
 #include "rt_device.hpp"
 #include "shade_device.hpp"
+#include "skinning.h"
 
 namespace cgpt {
 
@@ -64,38 +68,60 @@ __device__ __forceinline__ void tile_pixel(uint32_t width, uint32_t& px, uint32_
 // XFORM: it has an object with a transform (cgpt_scene_update_transforms): the trace and the normal honour it (this instantiation carries
 // SMOOTH too, as lobe level 4 does).  TREE: the trace goes through the top-level tree (cgpt_set_top_level(1)); the same hit, so the cached
 // guides of one mode serve the other.
+// The body is stated once, as text: shared through a device function, guides_kernel's instantiations did not keep their instruction
+// streams.  TRI_STATEMENT runs on a hit, WRITE_TRI after the stores.
+#define CGPT_GUIDES_BODY(SMOOTH_, XFORM_, TREE_, TRI_STATEMENT, WRITE_TRI)                                                                     \
+    uint32_t px, row;                                                                                                                          \
+    tile_pixel(width, px, row);                                                                                                                \
+    if (px >= width || row >= n_rows) return;                                                                                                  \
+    uint32_t* const stack = denoise_lds + threadIdx.x;                                                                                         \
+    const uint32_t py = first_row + row;                                                                                                       \
+    Ray ray = camera_ray(cam, (float)px * (1.0f / (float)width), (float)py * (1.0f / (float)height));   /* primary_ray's u, v */                \
+    Counters cnt = { 0, 0, 0, 0, 0 };                                          /* not booked: cgpt_stats does not grow */                      \
+    intersect_scene<false, XFORM_, TREE_>(sc, ray, stack, blockDim.x, cnt);                                                                    \
+    float4 g0 = make_float4(0.0f, 0.0f, 0.0f, 1e34f);                                                                                          \
+    float4 g1 = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kNoHit));                                                                        \
+    float4 g2 = g1;                                                                                                                            \
+    float4 m = make_float4(1.0f, 1.0f, 1.0f, 0.0f);                                                                                            \
+    if (ray.obj != kNoHit) {                                                                                                                   \
+        const Hit h = get_hit<false, SMOOTH_, XFORM_>(sc, ray, cnt);                                                                           \
+        const Mat mat = load_material(sc, h.mat);                                                                                              \
+        TRI_STATEMENT;                                                                                                                         \
+        g0 = make_float4(h.pos.x, h.pos.y, h.pos.z, ray.t);                                                                                    \
+        g1 = make_float4(h.normal.x, h.normal.y, h.normal.z, __uint_as_float(ray.obj));                                                        \
+        g2 = make_float4(mat.albedo.x, mat.albedo.y, mat.albedo.z, __uint_as_float(h.mat));                                                    \
+        if (!mat.is_light) {                                                                                                                   \
+            m.x = mat.albedo.x >= 1e-3f ? mat.albedo.x : 1.0f;                                                                                 \
+            m.y = mat.albedo.y >= 1e-3f ? mat.albedo.y : 1.0f;                                                                                 \
+            m.z = mat.albedo.z >= 1e-3f ? mat.albedo.z : 1.0f;                                                                                 \
+        }                                                                                                                                      \
+    }                                                                                                                                          \
+    const size_t i = (size_t)row * width + px;                                                                                                 \
+    guides[3 * i] = g0; guides[3 * i + 1] = g1; guides[3 * i + 2] = g2;                                                                        \
+    demod[i] = m;                                                                                                                              \
+    WRITE_TRI
+
 template <bool SMOOTH, bool XFORM = false, bool TREE = false>
 __global__ void __launch_bounds__(256) guides_kernel(const DevScene sc, const DevCamera cam, uint32_t width, uint32_t height, uint32_t first_row,
                                                      uint32_t n_rows, float4* __restrict__ guides, float4* __restrict__ demod)
 {
-    uint32_t px, row;
-    tile_pixel(width, px, row);
-    if (px >= width || row >= n_rows) return;
-    uint32_t* const stack = denoise_lds + threadIdx.x;
-    const uint32_t py = first_row + row;
-    Ray ray = camera_ray(cam, (float)px * (1.0f / (float)width), (float)py * (1.0f / (float)height));   // primary_ray's u, v
-    Counters cnt = { 0, 0, 0, 0, 0 };                                          // not booked: cgpt_stats does not grow
-    intersect_scene<false, XFORM, TREE>(sc, ray, stack, blockDim.x, cnt);
-    float4 g0 = make_float4(0.0f, 0.0f, 0.0f, 1e34f);
-    float4 g1 = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kNoHit));
-    float4 g2 = g1;
-    float4 m = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-    if (ray.obj != kNoHit) {
-        const Hit h = get_hit<false, SMOOTH, XFORM>(sc, ray, cnt);
-        const Mat mat = load_material(sc, h.mat);
-        g0 = make_float4(h.pos.x, h.pos.y, h.pos.z, ray.t);
-        g1 = make_float4(h.normal.x, h.normal.y, h.normal.z, __uint_as_float(ray.obj));
-        g2 = make_float4(mat.albedo.x, mat.albedo.y, mat.albedo.z, __uint_as_float(h.mat));
-        if (!mat.is_light) {
-            m.x = mat.albedo.x >= 1e-3f ? mat.albedo.x : 1.0f;
-            m.y = mat.albedo.y >= 1e-3f ? mat.albedo.y : 1.0f;
-            m.z = mat.albedo.z >= 1e-3f ? mat.albedo.z : 1.0f;
-        }
-    }
-    const size_t i = (size_t)row * width + px;
-    guides[3 * i] = g0; guides[3 * i + 1] = g1; guides[3 * i + 2] = g2;
-    demod[i] = m;
+    CGPT_GUIDES_BODY(SMOOTH, XFORM, TREE, (void)0, (void)0);
 }
+
+// The guides of a context that holds a skin (cgpt_scene_set_skin), whichever features its scene has: guides_kernel<true, true, TREE> -- it
+// reads the smooth and transform flags per object, so a scene without either gets the bits of its own instantiation; TREE follows
+// cgpt_set_top_level as it does there -- which also writes the first hit's triangle, in its object's original order, beside the
+// guides: what CGPT_TEMPORAL_FOLLOW_POSES carries a hit back through.  0 for anything but a mesh: a stand-alone triangle object's
+// Ray::tri is whatever an earlier mesh left there, and get_hit reads 0 for it.  A kernel of its own name: guides_kernel's
+// instantiations keep their signature.
+template <bool TREE>
+__global__ void __launch_bounds__(256) guides_tri_kernel(const DevScene sc, const DevCamera cam, uint32_t width, uint32_t height, uint32_t first_row,
+                                                         uint32_t n_rows, float4* __restrict__ guides, float4* __restrict__ demod, uint32_t* __restrict__ tri_out)
+{
+    uint32_t tri = 0u;
+    CGPT_GUIDES_BODY(true, true, TREE, tri = sc.objects[ray.obj].kind == 0u ? ray.tri : 0u, tri_out[i] = tri);
+}
+#undef CGPT_GUIDES_BODY
 
 struct PassArgs {
     const float4* src;        // the previous pass's output (pass 0: denoise_prepare's)
@@ -246,6 +272,8 @@ struct TemporalArgs {
     float min_history_n;           // min_history_frames N
     // MOTION only (CGPT_TEMPORAL_FOLLOW_TRANSFORMS)
     const float4* motion;          // 6 float4 per object: transform_math.h's MotionRecord
+    // POSE only (CGPT_TEMPORAL_FOLLOW_POSES)
+    const float4* pose;            // 2 float4 per pixel: pose_carry_back's records
 };
 
 // One thread per pixel.  The geometry of the reprojection -- (a, b, c) = Minv (x - pos_prev), fx, fy, the bilinear weights and the two
@@ -265,7 +293,11 @@ struct TemporalArgs {
 // on x', n', the unchanged t and object index.  A pixel of an unmoved object takes x and n untouched by a select (an identity product
 // would change bits), one of a dropped object takes no history.  The record's six loads are issued as soon as the object index is
 // known and before anything waits for them; the taps' addresses depend on them.  The new history stores the frame's own guides.
-template <bool FINAL, bool MOMENTS = false, bool MOTION = false>
+// POSE (CGPT_TEMPORAL_FOLLOW_POSES, a call in which a skinned object was re-posed; always mode kReproject; DESIGN.md 5.27;
+// tests/pose_motion_ref.py): the pixel's record of pose_carry_back (below) names where its hit was under the history's pose.  State 1
+// takes x and n from the record, state 0 the guides' untouched by a select, state 2 no history.  MOTION then runs on that x and n:
+// an object that was re-posed and moved is carried back through its pose and then through D, two roundings to float.
+template <bool FINAL, bool MOMENTS = false, bool MOTION = false, bool POSE = false>
 __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
 {
     uint32_t px, row;
@@ -288,25 +320,34 @@ __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
     } else if (a.mode == kReproject) {
         const uint32_t obj = __float_as_uint(g1.w), mat = __float_as_uint(g2.w);
         const bool hit = obj != kNoHit;
-        float4 x4 = g0, n4 = g1;                                               // the hit the reprojection runs on: MOTION carries it back
+        float4 x4 = g0, n4 = g1;                                               // the hit the reprojection runs on: POSE and MOTION carry it back
         bool dropped = false;
+        if constexpr (POSE) {
+            const float4 p0 = a.pose[2 * i], p1 = a.pose[2 * i + 1];
+            const uint32_t state = __float_as_uint(p0.w);                      // pose_carry_back: 0 for a miss and for every object without a new pose
+            const bool posed = state == 1u;
+            dropped = state == 2u;
+            x4.x = posed ? p0.x : g0.x; x4.y = posed ? p0.y : g0.y; x4.z = posed ? p0.z : g0.z;
+            n4.x = posed ? p1.x : g1.x; n4.y = posed ? p1.y : g1.y; n4.z = posed ? p1.z : g1.z;
+        }
         if constexpr (MOTION) {
+            const float4 xs = x4, ns = n4;                                     // the guides' own without POSE
             const float4* const rec = a.motion + 6u * (hit ? (size_t)obj : 0u);
             const float4 d0 = rec[0], d1 = rec[1], d2 = rec[2], n0 = rec[3], n1 = rec[4], n2 = rec[5];
             const uint32_t state = hit ? __float_as_uint(n0.w) : 0u;           // transform_math.h: 0 unmoved, 1 moved, 2 drop
-            const double x = (double)g0.x, y = (double)g0.y, z = (double)g0.z;
+            const double x = (double)xs.x, y = (double)xs.y, z = (double)xs.z;
             const double cx = (((double)d0.x * x + (double)d0.y * y) + (double)d0.z * z) + (double)d0.w;
             const double cy = (((double)d1.x * x + (double)d1.y * y) + (double)d1.z * z) + (double)d1.w;
             const double cz = (((double)d2.x * x + (double)d2.y * y) + (double)d2.z * z) + (double)d2.w;
-            const double nx = (double)g1.x, ny = (double)g1.y, nz = (double)g1.z;
+            const double nx = (double)ns.x, ny = (double)ns.y, nz = (double)ns.z;
             const double vx = ((double)n0.x * nx + (double)n0.y * ny) + (double)n0.z * nz;
             const double vy = ((double)n1.x * nx + (double)n1.y * ny) + (double)n1.z * nz;
             const double vz = ((double)n2.x * nx + (double)n2.y * ny) + (double)n2.z * nz;
             const double len = sqrt((vx * vx + vy * vy) + vz * vz);
             const bool moved = state == 1u;
-            dropped = state == 2u;
-            x4.x = moved ? (float)cx : g0.x; x4.y = moved ? (float)cy : g0.y; x4.z = moved ? (float)cz : g0.z;
-            n4.x = moved ? (float)(vx / len) : g1.x; n4.y = moved ? (float)(vy / len) : g1.y; n4.z = moved ? (float)(vz / len) : g1.z;
+            dropped = dropped || state == 2u;
+            x4.x = moved ? (float)cx : xs.x; x4.y = moved ? (float)cy : xs.y; x4.z = moved ? (float)cz : xs.z;
+            n4.x = moved ? (float)(vx / len) : ns.x; n4.y = moved ? (float)(vy / len) : ns.y; n4.z = moved ? (float)(vz / len) : ns.z;
         }
         const double dx = (double)x4.x - (double)a.pos_prev[0], dy = (double)x4.y - (double)a.pos_prev[1], dz = (double)x4.z - (double)a.pos_prev[2];
         const double pa = ((double)a.minv[0] * dx + (double)a.minv[1] * dy) + (double)a.minv[2] * dz;
@@ -351,7 +392,7 @@ __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
             sr += wf * hc[k].x; sg += wf * hc[k].y; sb += wf * hc[k].z; sh += wf * hc[k].w;
             if constexpr (MOMENTS) { smu += wf * hm[k].x; sv += wf * hm[k].y; sk += wf * hm[k].z; }
         }
-        const bool use = in_front && !view_dependent && wsum > 0.01 && !(MOTION && dropped);   // in_front: a hit, so an equal object index is a hit's
+        const bool use = in_front && !view_dependent && wsum > 0.01 && !((MOTION || POSE) && dropped);   // in_front: a hit, so an equal object index is a hit's
         const float inv = 1.0f / (use ? (float)wsum : 1.0f);
         hr = sr * inv; hg = sg * inv; hb = sb * inv;
         H = use ? sh * inv : 0.0f;
@@ -380,6 +421,149 @@ __global__ void __launch_bounds__(256) temporal_merge(const TemporalArgs a)
     }
     if (FINAL) write_output(r, g, b, a.demodulate, a.demod, a.color, a.pixels, i);
     else a.color[i] = make_float4(r, g, b, 0.0f);
+}
+
+// ---- following poses (CGPT_TEMPORAL_FOLLOW_POSES; tests/pose_motion_ref.py states it in numpy) ----------------------
+struct PoseArgs {
+    const float4* guides;          // this frame's
+    const uint32_t* tri;           // the first hit's triangle, beside the guides (guides_tri_kernel)
+    const PoseRecord* table;       // one record per object (ctx_internal.h), built by PreparePoses
+    const float4* matrices;        // the history's joint matrices of every re-posed skin, 3 float4 per joint
+    float4* out;                   // 2 float4 per pixel {x_p.xyz, bits(state) | n_p.xyz, 0}
+    uint32_t width, n_rows;
+};
+
+__device__ __forceinline__ double dot3(double ax, double ay, double az, double bx, double by, double bz) { return (ax * bx + ay * by) + az * bz; }
+
+// One thread per pixel: where the pixel's first hit was under the pose the temporal history was stored with.  A pose is always computed
+// from the bind pose, so that place is a function of the history's joint matrices alone: the hit's barycentric coordinates on the
+// current triangle (tri_orig), applied to the same triangle posed -- by skinning.h's float arithmetic, the bits skin_triangles wrote
+// then -- with the history's matrices.  Everything around that is double on the float inputs and rounded to float once, as
+// temporal_merge's geometry is and for its reason.  In order:
+//  1. P, the hit in object space: x, or Ainv x + binv with the scene's float inverse for an object with a transform;
+//  2. e1 = p1 - p0, e2 = p2 - p0, w = P - p0, g = e1 x e2, gg = g.g, u = ((w x e2).g) / gg, v = ((e1 x w).g) / gg (smooth_normal's
+//     steps 2-3, not clamped); gg zero or not finite: state 2;
+//  3. q_c, m_c: SkinBlend / SkinCorner on bind[tri], joints[tri], weights[tri] and the history's matrices;
+//  4. x' = (q0 + u (q1 - q0)) + v (q2 - q0);
+//  5. n' = m0, or with the smooth flag ((1 - u - v) m0 + u m1) + v m2 over its length (m0 where the squared length is not > 1e-12);
+//     smooth_normal's side fallback (its step 5) is not replayed: n' only feeds temporal_merge's two validity tests;
+//  6. x_p = A x' + b, n_p = normalize(Ainv^T n') through the object's current transform; an object without one takes x', n' as they are;
+//     anything not finite: state 2.
+// A miss, a hit on an object that was not re-posed and a state-2 pixel write their own x and n.
+// The joint matrices are read through the vector cache, not staged in LDS as skin_triangles stages them: a frame can hold several
+// skins, a 16x16 tile would stage up to 48 KB to use a handful of rows, and the pixels of a tile hit neighbouring triangles that share
+// their joints, so the rows a tile reads are few and stay in L1.  The gathers of a pixel -- the table record, then the triangle's
+// corners, skin and current positions, then the 36 matrix rows -- are each issued together before anything reads them.
+__global__ void __launch_bounds__(256) pose_carry_back(const DevScene sc, const PoseArgs a)
+{
+    uint32_t px, row;
+    tile_pixel(a.width, px, row);
+    if (px >= a.width || row >= a.n_rows) return;
+    const size_t i = (size_t)row * a.width + px;
+    const float4 g0 = a.guides[3 * i], g1 = a.guides[3 * i + 1];
+    const uint32_t obj = __float_as_uint(g1.w);
+    const bool hit = obj != kNoHit;
+    const PoseRecord* const rec = a.table + (hit ? (size_t)obj : 0u);           // a miss reads record 0 and is masked
+    uint32_t state = hit ? rec->state : 0u;
+    float ox = g0.x, oy = g0.y, oz = g0.z, onx = g1.x, ony = g1.y, onz = g1.z;
+    if (state == 1u) {
+        const uint32_t tri_base = rec->tri_base, smooth = rec->smooth, n_tris = rec->n_tris;
+        const float2* const bind = rec->bind;
+        const uint2* const joints = rec->joints;
+        const float4* const weights = rec->weights;
+        const float4* const mat = a.matrices + 3u * (size_t)rec->matrix_base;
+        float A[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) A[k] = rec->xform[k];
+        const bool xf = has_xform(sc, obj);
+        const Xform inv = load_xform(sc, obj);
+        const uint32_t tau = a.tri[i];                                         // read here only: a call without a state-1 object may have no index buffer
+        const size_t t = tau < n_tris ? tau : n_tris - 1u;                      // a mesh's tri_idx was validated at upload
+        const float4* const orig = sc.tri_orig + 3u * ((size_t)tri_base + t);
+        const float4 c0 = orig[0], c1 = orig[1], c2 = orig[2];
+        uint2 jw[3];
+        float4 w[3];
+        float2 b[3][3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            jw[c] = joints[3 * t + c];
+            w[c] = weights[3 * t + c];
+            b[c][0] = bind[9 * t + 3 * c]; b[c][1] = bind[9 * t + 3 * c + 1]; b[c][2] = bind[9 * t + 3 * c + 2];
+        }
+        float4 rows[3][4][3];                                                  // [corner][influence][row]
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const uint32_t j[4] = { jw[c].x & 0xFFFFu, jw[c].x >> 16, jw[c].y & 0xFFFFu, jw[c].y >> 16 };
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int r = 0; r < 3; ++r) rows[c][k][r] = mat[3u * j[k] + r];
+        }
+        float q[3][6];                                                         // the history pose's corners {pos, normal}: skin_triangles' arithmetic
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float m[12];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const float4 a0 = rows[c][0][r], a1 = rows[c][1][r], a2 = rows[c][2][r], a3 = rows[c][3][r];
+                m[4 * r] = SkinBlend(w[c].x, a0.x, w[c].y, a1.x, w[c].z, a2.x, w[c].w, a3.x);
+                m[4 * r + 1] = SkinBlend(w[c].x, a0.y, w[c].y, a1.y, w[c].z, a2.y, w[c].w, a3.y);
+                m[4 * r + 2] = SkinBlend(w[c].x, a0.z, w[c].y, a1.z, w[c].z, a2.z, w[c].w, a3.z);
+                m[4 * r + 3] = SkinBlend(w[c].x, a0.w, w[c].y, a1.w, w[c].z, a2.w, w[c].w, a3.w);
+            }
+            const float pn[6] = { b[c][0].x, b[c][0].y, b[c][1].x, b[c][1].y, b[c][2].x, b[c][2].y };
+            SkinCorner(m, pn, q[c]);
+        }
+        // 1. the hit in object space
+        const double gx = (double)g0.x, gy = (double)g0.y, gz = (double)g0.z;
+        const double Px = xf ? dot3((double)inv.r0.x, (double)inv.r0.y, (double)inv.r0.z, gx, gy, gz) + (double)inv.r0.w : gx;
+        const double Py = xf ? dot3((double)inv.r1.x, (double)inv.r1.y, (double)inv.r1.z, gx, gy, gz) + (double)inv.r1.w : gy;
+        const double Pz = xf ? dot3((double)inv.r2.x, (double)inv.r2.y, (double)inv.r2.z, gx, gy, gz) + (double)inv.r2.w : gz;
+        // 2. its coordinates on the current triangle
+        const double e1x = (double)c1.x - (double)c0.x, e1y = (double)c1.y - (double)c0.y, e1z = (double)c1.z - (double)c0.z;
+        const double e2x = (double)c2.x - (double)c0.x, e2y = (double)c2.y - (double)c0.y, e2z = (double)c2.z - (double)c0.z;
+        const double wx = Px - (double)c0.x, wy = Py - (double)c0.y, wz = Pz - (double)c0.z;
+        const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;   // g = e1 x e2
+        const double gg = dot3(nx, ny, nz, nx, ny, nz);
+        const double u = dot3(wy * e2z - wz * e2y, wz * e2x - wx * e2z, wx * e2y - wy * e2x, nx, ny, nz) / gg;
+        const double v = dot3(e1y * wz - e1z * wy, e1z * wx - e1x * wz, e1x * wy - e1y * wx, nx, ny, nz) / gg;
+        // 4. the same point of the history pose's triangle
+        const double xx = ((double)q[0][0] + u * ((double)q[1][0] - (double)q[0][0])) + v * ((double)q[2][0] - (double)q[0][0]);
+        const double xy = ((double)q[0][1] + u * ((double)q[1][1] - (double)q[0][1])) + v * ((double)q[2][1] - (double)q[0][1]);
+        const double xz = ((double)q[0][2] + u * ((double)q[1][2] - (double)q[0][2])) + v * ((double)q[2][2] - (double)q[0][2]);
+        // 5. and its normal
+        double mx = (double)q[0][3], my = (double)q[0][4], mz = (double)q[0][5];
+        if (smooth != 0u) {
+            const double w0 = 1.0 - u - v;
+            const double sx = (w0 * mx + u * (double)q[1][3]) + v * (double)q[2][3];
+            const double sy = (w0 * my + u * (double)q[1][4]) + v * (double)q[2][4];
+            const double sz = (w0 * mz + u * (double)q[1][5]) + v * (double)q[2][5];
+            const double l2 = dot3(sx, sy, sz, sx, sy, sz);
+            if (l2 > 1e-12) {
+                const double len = sqrt(l2);
+                mx = sx / len; my = sy / len; mz = sz / len;
+            }
+        }
+        // 6. back into the world
+        double wxp = xx, wyp = xy, wzp = xz, wnx = mx, wny = my, wnz = mz;
+        if (xf) {
+            wxp = dot3((double)A[0], (double)A[1], (double)A[2], xx, xy, xz) + (double)A[3];
+            wyp = dot3((double)A[4], (double)A[5], (double)A[6], xx, xy, xz) + (double)A[7];
+            wzp = dot3((double)A[8], (double)A[9], (double)A[10], xx, xy, xz) + (double)A[11];
+            const double tx = dot3((double)inv.r0.x, (double)inv.r1.x, (double)inv.r2.x, mx, my, mz);
+            const double ty = dot3((double)inv.r0.y, (double)inv.r1.y, (double)inv.r2.y, mx, my, mz);
+            const double tz = dot3((double)inv.r0.z, (double)inv.r1.z, (double)inv.r2.z, mx, my, mz);
+            const double len = sqrt(dot3(tx, ty, tz, tx, ty, tz));
+            wnx = tx / len; wny = ty / len; wnz = tz / len;
+        }
+        const float fx = (float)wxp, fy = (float)wyp, fz = (float)wzp, fnx = (float)wnx, fny = (float)wny, fnz = (float)wnz;
+        const bool ok = gg != 0.0 && isfinite(gg) && isfinite(fx) && isfinite(fy) && isfinite(fz) && isfinite(fnx) && isfinite(fny) && isfinite(fnz);
+        state = ok ? 1u : 2u;
+        ox = ok ? fx : ox; oy = ok ? fy : oy; oz = ok ? fz : oz;
+        onx = ok ? fnx : onx; ony = ok ? fny : ony; onz = ok ? fnz : onz;
+    }
+    a.out[2 * i] = make_float4(ox, oy, oz, __uint_as_float(state));
+    a.out[2 * i + 1] = make_float4(onx, ony, onz, 0.0f);
 }
 
 // ---- the variance-guided filter (cgpt_denoise_variance_guided; tests/variance_ref.py states it in numpy) ----------
@@ -567,14 +751,23 @@ uint32_t Tiles(const Frame& f) { return ((f.width + kTile - 1u) / kTile) * ((f.n
 // [kGuideLevels - 1 - guide level] (ctx_internal.h: ChooseGuideLevel): from the top level down, the order the instantiations have in the code object
 decltype(&guides_kernel<false>) const kGuideKernels[kGuideLevels] = { guides_kernel<true, true, true>, guides_kernel<true, true>, guides_kernel<true>, guides_kernel<false> };
 
+// the context holds a skin: its guides come with the triangle index (guides_tri_kernel)
+bool HoldsSkin(const cgpt_ctx* d)
+{
+    for (const SkinBuffers& sk : d->skins)
+        if (sk.n_joints != 0u) return true;
+    return false;
+}
+
 int EnsureGuides(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera)
 {
     cgpt_ctx* d = f.dev;
     const uint32_t key[4] = { f.width, f.height, f.first_row, f.n_rows };
+    const bool with_tri = HoldsSkin(d);                                        // guides cached without the index are stale for a context that now needs it
     if (d->guides_valid && d->guide_generation == d->scene_generation && memcmp(d->guide_frame, key, sizeof(key)) == 0 &&
-        memcmp(&d->guide_camera, camera, sizeof(cgpt_camera)) == 0)
+        memcmp(&d->guide_camera, camera, sizeof(cgpt_camera)) == 0 && (d->guide_tri_valid || !with_tri))
         return CGPT_OK;
-    d->guides_valid = false;
+    d->guides_valid = d->guide_tri_valid = false;
     const size_t n = (size_t)f.width * f.n_rows;
     if (d->dn.guide_demod.n != n) {                                            // any other size: both anew (the second one's count is the key)
         ResetAll(d->dn.guides, d->dn.guide_demod);
@@ -585,13 +778,19 @@ int EnsureGuides(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera)
     static_assert(sizeof(DevCamera) == sizeof(cgpt_camera), "camera layouts");
     memcpy(&cam, camera, sizeof(cam));
     const size_t lds = (size_t)d->scene.stack_depth * 256u * sizeof(uint32_t);   // intersect_rays_kernel's stack
-    hipLaunchKernelGGL(kGuideKernels[kGuideLevels - 1 - ChooseGuideLevel(d)], dim3(Tiles(f)), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
-                       d->dn.guides.p, d->dn.guide_demod.p);
+    if (with_tri) {
+        if (d->dn.guide_tri.n != n) HIP_TRY(ctx, d->dn.guide_tri.Alloc(n));
+        hipLaunchKernelGGL((d->top_level ? guides_tri_kernel<true> : guides_tri_kernel<false>), dim3(Tiles(f)), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
+                           d->dn.guides.p, d->dn.guide_demod.p, d->dn.guide_tri.p);
+    } else
+        hipLaunchKernelGGL(kGuideKernels[kGuideLevels - 1 - ChooseGuideLevel(d)], dim3(Tiles(f)), dim3(256), lds, d->stream, d->scene, cam, f.width, f.height, f.first_row, f.n_rows,
+                           d->dn.guides.p, d->dn.guide_demod.p);
     HIP_TRY(ctx, hipGetLastError());
     memcpy(d->guide_frame, key, sizeof(key));
     memcpy(&d->guide_camera, camera, sizeof(cgpt_camera));
     d->guide_generation = d->scene_generation;
     d->guides_valid = true;
+    d->guide_tri_valid = with_tri;
     return CGPT_OK;
 }
 
@@ -628,7 +827,7 @@ int CheckTemporalParams(cgpt_ctx* ctx, const cgpt_temporal_params& t)
     if (!std::isfinite(t.max_history) || !(t.max_history >= 1.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "max_history must be finite and >= 1, got %g", t.max_history);
     if (!(t.normal_cos_min >= -1.0f && t.normal_cos_min <= 1.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "normal_cos_min %g outside [-1, 1]", t.normal_cos_min);
     if (!std::isfinite(t.plane_tolerance) || !(t.plane_tolerance > 0.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "plane_tolerance must be finite and > 0, got %g", t.plane_tolerance);
-    if (t.flags & ~(uint32_t)(CGPT_TEMPORAL_KEEP_VIEW_DEPENDENT | CGPT_TEMPORAL_FOLLOW_TRANSFORMS)) return CtxFail(ctx, CGPT_ERR_INVALID, "unknown temporal flags 0x%x", t.flags);
+    if (t.flags & ~(uint32_t)(CGPT_TEMPORAL_KEEP_VIEW_DEPENDENT | CGPT_TEMPORAL_FOLLOW_TRANSFORMS | CGPT_TEMPORAL_FOLLOW_POSES)) return CtxFail(ctx, CGPT_ERR_INVALID, "unknown temporal flags 0x%x", t.flags);
     return CGPT_OK;
 }
 
@@ -669,11 +868,15 @@ int EnsureHistoryBuffers(cgpt_ctx* ctx, cgpt_ctx* d, size_t n)
     return CGPT_OK;
 }
 
-// the history a call may use: stored by a call that succeeded, for this band, scene and demodulation.  `follow`
-// (CGPT_TEMPORAL_FOLLOW_TRANSFORMS): or for a scene that only cgpt_scene_update_transforms calls have changed since.
-bool HistoryMatches(const cgpt_ctx* d, const uint32_t key[4], uint32_t demodulate, bool follow)
+// the history a call may use: stored by a call that succeeded, for this band, scene and demodulation.  The edits since it was stored
+// fall into three classes, counted by the three generations: cgpt_scene_update_transforms calls (scene - shape), kept with `follow`
+// (CGPT_TEMPORAL_FOLLOW_TRANSFORMS); cgpt_scene_skin_mesh calls (pose), kept with `follow_poses` (CGPT_TEMPORAL_FOLLOW_POSES); every
+// other edit (shape - pose), never kept.
+bool HistoryMatches(const cgpt_ctx* d, const uint32_t key[4], uint32_t demodulate, bool follow, bool follow_poses)
 {
-    const bool scene = d->temporal_generation == d->scene_generation || (follow && d->temporal_shape_generation == d->shape_generation);
+    const uint64_t edits = d->scene_generation - d->temporal_generation, shape_edits = d->shape_generation - d->temporal_shape_generation;
+    const uint64_t poses = d->pose_generation - d->temporal_pose_generation;
+    const bool scene = edits == 0 || (shape_edits == poses && (edits == shape_edits || follow) && (poses == 0 || follow_poses));
     return d->temporal_valid && scene && d->temporal_demodulate == demodulate && memcmp(d->temporal_frame, key, sizeof(d->temporal_frame)) == 0;
 }
 
@@ -694,9 +897,91 @@ int PrepareMotion(cgpt_ctx* ctx, cgpt_ctx* d, bool& moved)
     return CGPT_OK;
 }
 
+// which object's skin posed the copy object j shows, per object: -1 where no pose is known.  A pose through one skin makes every
+// other skin of the copy unknown (refit.hip: SkinMesh), so a copy has at most one.
+void PoseOwners(const cgpt_ctx* d, std::vector<int32_t>& owner)
+{
+    owner.assign(d->h_objects.size(), -1);
+    for (size_t k = 0; k < d->skins.size(); ++k) {
+        if (d->skins[k].n_joints == 0u || !d->skins[k].pose_known) continue;
+        for (size_t j = 0; j < owner.size(); ++j)
+            if (d->mesh_group[j] == d->mesh_group[k]) owner[j] = (int32_t)k;
+    }
+}
+
+// the poses a call's history is stored for (empty for a context without a skin)
+void SnapshotPoses(const cgpt_ctx* d, PoseSnapshot& snap)
+{
+    snap = PoseSnapshot{};
+    if (!HoldsSkin(d)) return;
+    PoseOwners(d, snap.owner);
+    snap.serial.assign(snap.owner.size(), 0);
+    snap.matrices.resize(snap.owner.size());
+    for (const int32_t k : snap.owner)
+        if (k >= 0 && snap.serial[k] == 0) { snap.serial[k] = d->skins[k].serial; snap.matrices[k] = d->skins[k].pose; }
+}
+
+// CGPT_TEMPORAL_FOLLOW_POSES with a usable history that cgpt_scene_skin_mesh calls have happened since: the record of every object
+// (ctx_internal.h: PoseRecord) in d->pose_records and, when an object is not in state 0, in dn.pose_table, with the history's matrices of
+// the re-posed skins in dn.pose_matrices (asynchronous copies on the stream: the host vectors live on).  An object whose copy no pose
+// has written since the history is in state 0 whatever its skin; one that was posed is in state 0 when the matrices equal the
+// snapshot's bytewise (A -> B -> A), 1 when they differ, 2 when either side knows no pose or the skin is another installation (or, which
+// a skin's presence rules out, the guides came without the triangle index: a state-1 record is the only reader of dn.guide_tri).
+// `posed`: an object is not in state 0, so the call runs pose_carry_back and reprojects through temporal_merge<.., POSE = true>.
+int PreparePoses(cgpt_ctx* ctx, cgpt_ctx* d, bool& posed)
+{
+    posed = false;
+    const bool have_tri = d->guide_tri_valid;                                  // EnsureGuides ran: the index buffer belongs to this call's guides
+    const size_t n = d->h_objects.size();
+    const PoseSnapshot& snap = d->temporal_poses;
+    std::vector<int32_t> owner;
+    size_t changed = 0;
+    try {
+        PoseOwners(d, owner);
+        d->pose_records.assign(n, PoseRecord{});
+        d->pose_matrices.clear();
+        std::vector<int64_t> base(n, -1);                                      // where skin k's history matrices start, in joints
+        for (size_t j = 0; j < n; ++j) {
+            PoseRecord& r = d->pose_records[j];
+            if (d->top_state.xform.size() == 12 * n) memcpy(r.xform, d->top_state.xform.data() + 12 * j, sizeof(r.xform));
+            r.tri_base = d->h_objects[j].tri_base; r.smooth = d->h_objects[j].smooth; r.n_tris = d->refit_objects[j].tri_count;
+            if (j >= d->pose_stamp.size() || d->pose_stamp[j] <= d->temporal_pose_generation) continue;   // not posed since: state 0
+            r.state = kMotionDrop;
+            const int32_t k = owner[j];
+            if (have_tri && k >= 0 && j < snap.owner.size() && snap.owner[j] == k && snap.serial[k] == d->skins[k].serial && snap.matrices[k].size() == d->skins[k].pose.size()) {
+                const SkinBuffers& sk = d->skins[k];
+                if (memcmp(snap.matrices[k].data(), sk.pose.data(), sk.pose.size() * sizeof(float)) == 0) r.state = kMotionUnmoved;
+                else {
+                    if (base[k] < 0) {
+                        base[k] = (int64_t)(d->pose_matrices.size() / 12);
+                        d->pose_matrices.insert(d->pose_matrices.end(), snap.matrices[k].begin(), snap.matrices[k].end());
+                    }
+                    r.state = kMotionMoved;
+                    r.matrix_base = (uint32_t)base[k];
+                    r.bind = reinterpret_cast<const float2*>(sk.bind.p);
+                    r.joints = reinterpret_cast<const uint2*>(sk.joints.p);
+                    r.weights = reinterpret_cast<const float4*>(sk.weights.p);
+                }
+            }
+            if (r.state != kMotionUnmoved) ++changed;
+        }
+    } catch (const std::exception& e) { return CtxFail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
+    if (changed == 0) return CGPT_OK;
+    static_assert(sizeof(PoseRecord) == 6 * sizeof(float4), "6 float4 per object");
+    HIP_TRY(ctx, d->dn.pose_table.Grow(6 * n));                                // hipFree waits for the device
+    HIP_TRY(ctx, hipMemcpyAsync(d->dn.pose_table.p, d->pose_records.data(), n * sizeof(PoseRecord), hipMemcpyHostToDevice, d->stream));
+    if (!d->pose_matrices.empty()) {
+        HIP_TRY(ctx, d->dn.pose_matrices.Grow(d->pose_matrices.size() / 4));
+        HIP_TRY(ctx, hipMemcpyAsync(d->dn.pose_matrices.p, d->pose_matrices.data(), d->pose_matrices.size() * sizeof(float), hipMemcpyHostToDevice, d->stream));
+    }
+    posed = true;
+    return CGPT_OK;
+}
+
 // the arguments of the temporal stage of a frame: from dn.history[temporal_slot] (when `have`) into the other slot, on filter[0].
-// `moved` (PrepareMotion): the hits are carried back through dn.motion, so equal camera bytes do not mean equal hits -- the call reprojects.
-void FillTemporalArgs(const Frame& f, const cgpt_camera* camera, const cgpt_temporal_params& t, uint32_t demodulate, bool have, bool moved, TemporalArgs& a)
+// `carried` (PrepareMotion, PreparePoses): hits are carried back through dn.motion or dn.previous_hits, so equal camera bytes do not mean
+// equal hits -- the call reprojects.
+void FillTemporalArgs(const Frame& f, const cgpt_camera* camera, const cgpt_temporal_params& t, uint32_t demodulate, bool have, bool carried, TemporalArgs& a)
 {
     cgpt_ctx* d = f.dev;
     const uint32_t src = d->temporal_slot, dst = src ^ 1u;
@@ -710,24 +995,25 @@ void FillTemporalArgs(const Frame& f, const cgpt_camera* camera, const cgpt_temp
     a.height = (float)f.height; a.first_row = (float)f.first_row;
     a.mode = kNoHistory;
     if (have) {
-        if (!moved && memcmp(&d->temporal_camera, camera, sizeof(cgpt_camera)) == 0) a.mode = kSameCamera;
+        if (!carried && memcmp(&d->temporal_camera, camera, sizeof(cgpt_camera)) == 0) a.mode = kSameCamera;
         else if (InvertCamera(d->temporal_camera, a.minv)) {                   // a singular camera: no history
             memcpy(a.pos_prev, d->temporal_camera.pos, sizeof(a.pos_prev));
             a.mode = kReproject;
         }
     }
-    a.motion = moved ? d->dn.motion.p : nullptr;
 }
 
 // what a successful temporal stage leaves: the history in the other slot, and what it was stored for (`xform`: the call's snapshot
-// of top_state.xform, swapped in)
-void StoreTemporalKey(cgpt_ctx* d, const cgpt_camera* camera, const uint32_t key[4], uint32_t demodulate, std::vector<float>& xform)
+// of top_state.xform, swapped in; `poses`: its snapshot of the poses, likewise)
+void StoreTemporalKey(cgpt_ctx* d, const cgpt_camera* camera, const uint32_t key[4], uint32_t demodulate, std::vector<float>& xform, PoseSnapshot& poses)
 {
     d->temporal_slot ^= 1u;
     d->temporal_demodulate = demodulate;
     d->temporal_generation = d->scene_generation;
     d->temporal_shape_generation = d->shape_generation;
     d->temporal_xform.swap(xform);
+    d->temporal_pose_generation = d->pose_generation;
+    std::swap(d->temporal_poses, poses);
     memcpy(&d->temporal_camera, camera, sizeof(cgpt_camera));
     memcpy(d->temporal_frame, key, sizeof(d->temporal_frame));
     d->temporal_valid = true;
@@ -759,6 +1045,14 @@ int EnsureVarianceBuffers(cgpt_ctx* ctx, cgpt_ctx* d, size_t n, bool temporal)
 // what runs in front of the passes: temporal_merge; variance_estimate, with variance_pass for atrous_pass
 struct Stages { bool temporal, variance; };
 
+// temporal_merge<FINAL, MOMENTS, MOTION, POSE> for a call in which an object moved (PrepareMotion) or was re-posed (PreparePoses)
+template <bool FINAL, bool MOMENTS>
+decltype(&temporal_merge<FINAL, MOMENTS>) PickMerge(bool moved, bool posed)
+{
+    if (posed) return moved ? temporal_merge<FINAL, MOMENTS, true, true> : temporal_merge<FINAL, MOMENTS, false, true>;
+    return moved ? temporal_merge<FINAL, MOMENTS, true> : temporal_merge<FINAL, MOMENTS>;
+}
+
 // One filtering call's launches: denoise_prepare, the temporal merge, the variance estimate, the passes (or, iterations = 0, an
 // identity), the read-back.
 //
@@ -781,12 +1075,17 @@ int RunStages(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, Stages s
     const float n_samples = (float)f.num_accumulated;
     const float inv_normal = (float)(1.0 / ((double)p.sigma_normal * p.sigma_normal));
     const float inv_position = (float)(1.0 / ((double)p.sigma_position * p.sigma_position));
-    const bool follow = (t.flags & CGPT_TEMPORAL_FOLLOW_TRANSFORMS) != 0u;
-    const bool have = st.temporal && HistoryMatches(d, key, demodulate, follow);
+    const bool follow = (t.flags & CGPT_TEMPORAL_FOLLOW_TRANSFORMS) != 0u, follow_poses = (t.flags & CGPT_TEMPORAL_FOLLOW_POSES) != 0u;
+    const bool have = st.temporal && HistoryMatches(d, key, demodulate, follow, follow_poses);
     const bool have_moments = have && d->moments_valid;
+    bool wrote_previous_hits = false;                                          // this call launched pose_carry_back
     std::vector<float> xform;                                                  // the matrices this call's history is stored for
+    PoseSnapshot poses;                                                        // ... and the poses
     if (st.temporal) {
-        try { xform.resize(d->top_state.xform.size()); } catch (const std::exception& e) { return CtxFail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
+        try {
+            xform.resize(d->top_state.xform.size());
+            SnapshotPoses(d, poses);
+        } catch (const std::exception& e) { return CtxFail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
         SnapshotTransforms(d->top_state.xform.data(), xform.size() / 12, xform.data());
     }
     if (st.variance) d->variance_valid = false;                                // a call that fails from here on leaves no map
@@ -805,22 +1104,33 @@ int RunStages(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, Stages s
     }
     if (st.temporal) {
         bool moved = false;                                                    // an object moved since the history was stored, and the call follows it
+        bool posed = false;                                                    // ... was re-posed
         if (have && follow && (rc = PrepareMotion(ctx, d, moved)) != CGPT_OK) return rc;
+        if (have && follow_poses && d->pose_generation != d->temporal_pose_generation && (rc = PreparePoses(ctx, d, posed)) != CGPT_OK) return rc;
         TemporalArgs a{};
-        FillTemporalArgs(f, camera, t, demodulate, have, moved, a);
+        FillTemporalArgs(f, camera, t, demodulate, have, moved || posed, a);
         moved = moved && a.mode == kReproject;                                 // a singular history camera: no history, the existing kernel
+        posed = posed && a.mode == kReproject;
+        a.motion = moved ? d->dn.motion.p : nullptr;
+        if (posed) {
+            if (d->dn.previous_hits.n != 2 * n) HIP_TRY(ctx, d->dn.previous_hits.Alloc(2 * n));
+            d->previous_hits_valid = false;                                    // overwritten from here on
+            PoseArgs pa{};
+            pa.guides = d->dn.guides.p; pa.tri = d->guide_tri_valid ? d->dn.guide_tri.p : nullptr; pa.table = reinterpret_cast<const PoseRecord*>(d->dn.pose_table.p);
+            pa.matrices = d->dn.pose_matrices.p; pa.out = d->dn.previous_hits.p; pa.width = f.width; pa.n_rows = f.n_rows;
+            hipLaunchKernelGGL(pose_carry_back, dim3(tiles), dim3(256), 0, d->stream, d->scene, pa);
+            HIP_TRY(ctx, hipGetLastError());
+            a.pose = d->dn.previous_hits.p;
+        }
+        wrote_previous_hits = posed;
         if (st.variance) {
             a.moments = d->dn.moments[d->temporal_slot].p; a.moments_out = d->dn.moments[d->temporal_slot ^ 1u].p;
             a.variance = d->dn.variance.p;
             a.have_moments = have_moments ? 1u : 0u;
             a.min_history_n = (float)v.min_history_frames * n_samples;
-            if (moved) hipLaunchKernelGGL((temporal_merge<false, true, true>), dim3(tiles), dim3(256), 0, d->stream, a);
-            else hipLaunchKernelGGL((temporal_merge<false, true>), dim3(tiles), dim3(256), 0, d->stream, a);
-        } else if (moved) {
-            if (p.iterations == 0) hipLaunchKernelGGL((temporal_merge<true, false, true>), dim3(tiles), dim3(256), 0, d->stream, a);
-            else hipLaunchKernelGGL((temporal_merge<false, false, true>), dim3(tiles), dim3(256), 0, d->stream, a);
-        } else if (p.iterations == 0) hipLaunchKernelGGL(temporal_merge<true>, dim3(tiles), dim3(256), 0, d->stream, a);
-        else hipLaunchKernelGGL(temporal_merge<false>, dim3(tiles), dim3(256), 0, d->stream, a);
+            hipLaunchKernelGGL((PickMerge<false, true>(moved, posed)), dim3(tiles), dim3(256), 0, d->stream, a);
+        } else if (p.iterations == 0) hipLaunchKernelGGL((PickMerge<true, false>(moved, posed)), dim3(tiles), dim3(256), 0, d->stream, a);
+        else hipLaunchKernelGGL((PickMerge<false, false>(moved, posed)), dim3(tiles), dim3(256), 0, d->stream, a);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (st.variance) {
@@ -855,8 +1165,12 @@ int RunStages(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, Stages s
     }
     if ((rc = ReadBack(ctx, d, n, out, dst_rgba, dst_pixels)) != CGPT_OK) return rc;
     if (st.temporal) {
-        StoreTemporalKey(d, camera, key, demodulate, xform);
+        StoreTemporalKey(d, camera, key, demodulate, xform, poses);
         d->moments_valid = st.variance;
+        if (wrote_previous_hits) {
+            memcpy(d->previous_hits_frame, key, sizeof(key));
+            d->previous_hits_valid = true;
+        }
     }
     if (st.variance) {
         memcpy(d->variance_frame, key, sizeof(key));
@@ -914,6 +1228,8 @@ void DenoiseFree(cgpt_ctx* ctx)
     ctx->temporal_valid = false;
     ctx->moments_valid = false;
     ctx->variance_valid = false;
+    ctx->guide_tri_valid = false;
+    ctx->previous_hits_valid = false;
 }
 
 }  // namespace cgpt
@@ -994,6 +1310,17 @@ int cgpt_read_temporal_history(cgpt_ctx* ctx, float* dst, size_t n_floats)
     const size_t n = (size_t)d->temporal_frame[0] * d->temporal_frame[3];
     if (!dst || n_floats != 4 * n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats (4 per pixel)", 4 * n);
     return CopyToHost(ctx, d, dst, d->dn.history[d->temporal_slot].p, n * sizeof(float4));
+}
+
+int cgpt_read_previous_hits(cgpt_ctx* ctx, float* dst, size_t n_floats)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    cgpt_ctx* const first = GroupFirstMemberOrNull(ctx);
+    cgpt_ctx* const d = first ? first : ctx;
+    if (!d->previous_hits_valid) return CtxFail(ctx, CGPT_ERR_INVALID, "no previous hits: no temporal call with CGPT_TEMPORAL_FOLLOW_POSES has carried a pose back");
+    const size_t n = (size_t)d->previous_hits_frame[0] * d->previous_hits_frame[3];
+    if (!dst || n_floats != 8 * n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats (8 per pixel)", 8 * n);
+    return CopyToHost(ctx, d, dst, d->dn.previous_hits.p, n * sizeof(float4) * 2);
 }
 
 }  // extern "C"

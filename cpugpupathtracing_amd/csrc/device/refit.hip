@@ -18,7 +18,8 @@
 // Skinning (cgpt_scene_set_skin / cgpt_scene_skin_mesh): the same refit with the triangle pass fed from a bind pose, joint
 // indices and weights that stay on the device (skin_triangles poses each triangle by the arithmetic of csrc/host/skinning.h and writes the
 // records through the function refit_triangles writes them with), then the same bound pass.  No staging copy and no per-triangle host work:
-// the top-level box comes back from the refitted root record (or a one-block fold), and total_area is left as uploaded.
+// the top-level box comes back from the refitted root record (or a one-block fold), and total_area is left as uploaded.  A skin remembers
+// the matrices of its last pose on the host (SkinBuffers::pose): what a temporal call with CGPT_TEMPORAL_FOLLOW_POSES compares (denoise.hip).
 // After cgpt_scene_upload_instanced the objects of a mesh group share the one copy these passes edit: the refit goes through any member's
 // RefitObject (they are equal), and the area and the top-level box, which are per object, are written for every member.
 #include <hip/hip_runtime.h>
@@ -292,6 +293,8 @@ int RefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles,
     HIP_TRY(ctx, hipMemcpyAsync(ctx->sb.refit_staging.p, triangles, sizeof(cgpt_triangle) * (size_t)n_tris, hipMemcpyHostToDevice, ctx->stream));
 
     // from here on the scene changes
+    for (const uint32_t j : members)                                           // the copy is no pose of any skin now (CGPT_TEMPORAL_FOLLOW_POSES: "no pose known")
+        if (j < ctx->skins.size()) ctx->skins[j].pose_known = false;
     const uint32_t tri_base = d.tri_base;
     hipLaunchKernelGGL(refit_triangles, dim3((n_tris + kRefitThreads - 1) / kRefitThreads), dim3(kRefitThreads), 0, ctx->stream,
                        reinterpret_cast<const float*>(ctx->sb.refit_staging.p), ctx->sb.tri_leaf.p, ctx->sb.tri_orig.p, ctx->sb.tri_normal.p, ro.leaf_base, tri_base, n_tris, ctx->scene.n_tris_total);
@@ -338,6 +341,7 @@ int SetSkin(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* bind, const 
     HIP_TRY(ctx, hipMemcpy(sk.joints.p, joints, sizeof(uint16_t) * 12 * (size_t)n_tris, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(sk.weights.p, weights, sizeof(float) * 12 * (size_t)n_tris, hipMemcpyHostToDevice));
     sk.n_joints = n_joints;
+    sk.serial = ++ctx->skin_serial;                                            // no pose known yet
     if (ctx->skins.size() != ctx->h_objects.size()) ctx->skins.resize(ctx->h_objects.size());
     ctx->skins[obj_index] = std::move(sk);
     return CGPT_OK;
@@ -349,7 +353,7 @@ int SkinMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uin
     if (rc != CGPT_OK) return rc;
     if (obj_index >= ctx->skins.size() || ctx->skins[obj_index].n_joints == 0u)
         return CtxFail(ctx, CGPT_ERR_INVALID, "object %u has no skin (cgpt_scene_set_skin installs one)", obj_index);
-    const SkinBuffers& sk = ctx->skins[obj_index];
+    SkinBuffers& sk = ctx->skins[obj_index];
     if (n_joints != sk.n_joints) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u's skin has %u joints, got %u", obj_index, sk.n_joints, n_joints);
     std::string why;
     if (!CheckJointMatrices(joint_matrices, n_joints, why)) return CtxFail(ctx, CGPT_ERR_INVALID, "%s", why.c_str());
@@ -357,6 +361,8 @@ int SkinMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uin
     const RefitObject& ro = ctx->refit_objects[obj_index];
     const uint32_t n_tris = ro.tri_count, tri_base = d.tri_base;
     TopLevelState top = ctx->top_state;                                        // may throw: before the first write
+    std::vector<float> pose(joint_matrices, joint_matrices + 12 * (size_t)n_joints);   // what a temporal call that follows poses compares (denoise.hip)
+    if (ctx->pose_stamp.size() != ctx->h_objects.size()) ctx->pose_stamp.resize(ctx->h_objects.size(), 0);
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -364,6 +370,11 @@ int SkinMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uin
     HIP_TRY(ctx, hipMemsetAsync(ctx->sb.skin_scratch.p, 0, sizeof(uint32_t) * kSkinScratchWords, ctx->stream));
 
     // from here on the scene changes
+    for (uint32_t j = 0; j < ctx->mesh_group.size(); ++j)                      // every placement of the copy: posed now, and by no other skin
+        if (ctx->mesh_group[j] == ctx->mesh_group[obj_index]) {
+            ctx->pose_stamp[j] = ctx->pose_generation;
+            if (j < ctx->skins.size()) ctx->skins[j].pose_known = false;
+        }
     const dim3 grid(std::min((n_tris + kRefitThreads - 1) / kRefitThreads, kSkinMaxBlocks)), block(kRefitThreads);
     const auto launch = [&](auto kernel, size_t lds_bytes) {
         hipLaunchKernelGGL(kernel, grid, block, lds_bytes, ctx->stream, reinterpret_cast<const float2*>(sk.bind.p), reinterpret_cast<const uint2*>(sk.joints.p),
@@ -407,6 +418,8 @@ int SkinMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uin
         if (j != obj_index && ctx->mesh_group[j] == ctx->mesh_group[obj_index]) memcpy(top.local_box.data() + 6 * (size_t)j, box, 24);
     REFIT_HIP_WRITING(ctx, WriteTopLevel(ctx, ctx->h_objects, top));
     ctx->top_state.local_box.swap(top.local_box);
+    sk.pose.swap(pose);
+    sk.pose_known = true;
     return CGPT_OK;
 }
 
@@ -554,7 +567,8 @@ int cgpt_scene_skin_mesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_m
 {
     if (!ctx) return CGPT_ERR_INVALID;
     if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupSkinMesh(ctx, obj_index, joint_matrices, n_joints); });
-    ctx->scene_generation++; ctx->shape_generation++;                          // as a refit: guides and temporal history are stale
+    ctx->scene_generation++; ctx->shape_generation++; ctx->pose_generation++;   // as a refit: guides and temporal history are stale (a call with
+                                                                               // CGPT_TEMPORAL_FOLLOW_POSES keeps the history: pose_generation tells a pose from a refit)
     return Guarded(ctx, __func__, [&] { return SkinMesh(ctx, obj_index, joint_matrices, n_joints); });
 }
 

@@ -312,16 +312,18 @@ class Renderer:
     def denoise_temporal(self, iterations: int = 5, sigma_color: float = 4.0, sigma_normal: float = 0.2, sigma_position: float = 0.3,
                          demodulate: bool = True, max_history: float = 64.0, normal_cos_min: float = 0.9, plane_tolerance: float = 0.01,
                          keep_view_dependent: bool = False, camera: Optional[N.Camera] = None,
-                         follow_transforms: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+                         follow_transforms: bool = False, follow_poses: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         """denoise() with the temporal stage in front (cgpt_denoise_temporal): the history of the earlier calls is reprojected onto
         `camera` (the one of this frame's render; default: the uploaded scene's) and merged with the accumulated frame by sample counts
         before the filter runs.  Per frame: reset_accumulator(), render(), denoise_temporal(); each call consumes the accumulated
         samples once.  Every scene edit drops the history; follow_transforms=True (CGPT_TEMPORAL_FOLLOW_TRANSFORMS) keeps it across
-        update_transforms() calls and carries the hits on the moved objects back to where they were."""
+        update_transforms() calls and carries the hits on the moved objects back to where they were; follow_poses=True
+        (CGPT_TEMPORAL_FOLLOW_POSES) keeps it across skin_mesh() calls and carries the hits on the re-posed objects back to where the
+        same surface points were under the history's pose (previous_hits() reads those records)."""
         cam = camera if camera is not None else self.scene.camera()
         p = N.DenoiseParams(iterations, N.DENOISE_DEMODULATE_ALBEDO if demodulate else 0, sigma_color, sigma_normal, sigma_position)
         t = N.TemporalParams(max_history, normal_cos_min, plane_tolerance, (N.TEMPORAL_KEEP_VIEW_DEPENDENT if keep_view_dependent else 0) |
-                             (N.TEMPORAL_FOLLOW_TRANSFORMS if follow_transforms else 0))
+                             (N.TEMPORAL_FOLLOW_TRANSFORMS if follow_transforms else 0) | (N.TEMPORAL_FOLLOW_POSES if follow_poses else 0))
         rgba = np.empty((self.n_rows, self.width, 4), np.float32)
         px = np.empty((self.n_rows, self.width), np.uint32)
         self._check(self.L.cgpt_denoise_temporal(self._ctx, C.byref(cam), C.byref(p), C.byref(t), rgba.ctypes.data_as(C.POINTER(C.c_float)),
@@ -337,6 +339,14 @@ class Renderer:
         filter's input domain, history length in samples}."""
         out = np.empty((self.n_rows, self.width, 4), np.float32)
         self._check(self.L.cgpt_read_temporal_history(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
+    def previous_hits(self) -> np.ndarray:
+        """The carry-back records of the last denoise_temporal(follow_poses=True) in which an object was re-posed
+        (cgpt_read_previous_hits): (rows, width, 8) float32 {x_p.xyz, bits(state), n_p.xyz, 0} -- where each pixel's first hit was under
+        the history's pose; state 0 (not re-posed: the pixel's own x, n), 1 (re-posed) or 2 (no history)."""
+        out = np.empty((self.n_rows, self.width, 8), np.float32)
+        self._check(self.L.cgpt_read_previous_hits(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
         return out
 
     def denoise_variance_guided(self, iterations: int = 5, sigma_luminance: float = 4.0, sigma_normal: float = 0.2, sigma_position: float = 0.3,

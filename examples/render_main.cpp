@@ -42,9 +42,12 @@
 // --mesh-transform m00 m01 m02 m03 m10 .. m23: the mesh (object 0, the dragon or its stand-in) is placed by this object-to-world matrix, the
 // rows of [A | b] with world = A p + b (cgpt_scene_update_transforms after the upload); the other objects keep the identity.
 // --bend DEG: a deforming mesh -- the mesh (object 0) gets a procedural two-joint skin on the device (cgpt_scene_set_skin: the weights come from a
-// vertex's height between the mesh's lowest and highest point) and is posed once per frame of the loop below (cgpt_scene_skin_mesh; joint 1 turns
-// about the x axis through the middle of the mesh, a little further every frame up to DEG degrees), each frame from a reset accumulator
-// (DESIGN.md 5.26).  A demonstration of the device calls, not a loader feature: glTF skins are not imported.
+// vertex's height between the mesh's lowest and highest point) and is posed once per frame (cgpt_scene_skin_mesh; joint 1 turns about the x axis
+// through the middle of the mesh, DEG degrees further every frame): 8 frames under the scene's camera, each `spp` samples from a
+// reset accumulator; every frame is written raw (bend_NN_raw.ppm), through cgpt_denoise (bend_NN_denoised.ppm) and through cgpt_denoise_temporal
+// with CGPT_TEMPORAL_FOLLOW_POSES, which carries the mesh's pixels back to where the same surface points were under the frame before and keeps
+// everyone's history (bend_NN_temporal.ppm).  Takes [width height spp] only.  A demonstration of the device calls, not a loader
+// feature: glTF skins are not imported.
 // move_at > 0 scripts the input half of Update(dt) (ref: Main.cpp:277-297, Camera::Update :104-131): after that many samples the
 // camera is translated by (right, up, forward) as the A/D, Space/Shift, W/S keys would, the view changes, and the accumulator
 // is reset (ref: ResetAccumulator, Main.cpp:238-243) before the remaining samples are rendered from the new position.
@@ -232,8 +235,8 @@ int main(int argc, char** argv)
     }
     // --bend: a procedural two-joint skin of the mesh (object 0).  A corner's weight on joint 1 is its height between the mesh's lowest and
     // highest point; joint 0 stays, joint 1 turns about the x axis through the middle of the mesh.  The skin goes to the device once.
-    float bend_pivot[3] = { 0.0f, 0.0f, 0.0f };
     if (bend) {
+        float bend_pivot[3] = { 0.0f, 0.0f, 0.0f };
         const cgpt_object& o = desc.objects[0];
         const cgpt_triangle* bind = desc.triangles + o.tri_offset;      // original order, as cgpt_scene_refit_mesh takes them
         float lo[3] = { 1e30f, 1e30f, 1e30f }, hi[3] = { -1e30f, -1e30f, -1e30f };
@@ -252,6 +255,32 @@ int main(int argc, char** argv)
             }
         }
         CHECK(cgpt_scene_set_skin(ctx, 0, bind, joints.data(), weights.data(), o.tri_count, 2));
+
+        std::vector<uint32_t> px((size_t)W * H);                         // the mesh bends every frame: SkinMesh, ResetAccumulator, Render, present
+        const cgpt_camera cam = scene.camera.Abi();
+        const cgpt_temporal_params tp = { 64.0f, 0.9f, 0.01f, CGPT_TEMPORAL_FOLLOW_POSES };
+        for (uint32_t frame = 0; frame < 8; ++frame) {                   // the pose of this frame: 48 bytes a joint go to the device
+            const double angle = (double)bend_deg * (double)frame * 3.14159265358979 / 180.0, c = std::cos(angle), sn = std::sin(angle);
+            const float py = bend_pivot[1], pz = bend_pivot[2];
+            const float joint_matrices[24] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0,                                    // joint 0 stays
+                                               1, 0, 0, 0, 0, (float)c, (float)-sn, (float)(py - c * py + sn * pz),    // joint 1: R_x (p - pivot) + pivot
+                                               0, (float)sn, (float)c, (float)(pz - sn * py - c * pz) };
+            CHECK(cgpt_scene_skin_mesh(ctx, 0, joint_matrices, 2));
+            CHECK(cgpt_reset_accumulator(ctx));
+            cgpt_render_params p{};
+            p.width = W; p.height = H; p.row_begin = 0; p.row_end = H;
+            p.first_sample = 0; p.n_samples = spp; p.seed = 0x12345678u + frame; p.kernel = CGPT_KERNEL_AUTO;
+            CHECK(cgpt_render(ctx, &cam, &settings, &p));
+            char name[64]; std::string err;
+            CHECK(cgpt_read_pixels(ctx, px.data(), px.size()));
+            snprintf(name, sizeof(name), "bend_%02u_raw.ppm", frame); WritePPM(name, px.data(), W, H, err);
+            CHECK(cgpt_denoise(ctx, &cam, nullptr, nullptr, 0, px.data(), px.size()));
+            snprintf(name, sizeof(name), "bend_%02u_denoised.ppm", frame); WritePPM(name, px.data(), W, H, err);
+            CHECK(cgpt_denoise_temporal(ctx, &cam, nullptr, &tp, nullptr, 0, px.data(), px.size()));   // once per rendered frame
+            snprintf(name, sizeof(name), "bend_%02u_temporal.ppm", frame); WritePPM(name, px.data(), W, H, err);
+        }
+        cgpt_ctx_destroy(ctx);
+        return 0;
     }
     uint32_t num_accumulated = 0;                                        // data.num_accumulated
     const auto t0 = std::chrono::steady_clock::now();
@@ -265,17 +294,6 @@ int main(int argc, char** argv)
                 CHECK(cgpt_reset_accumulator(ctx));
                 num_accumulated = 0;
             }
-        }
-        if (bend) {                                                      // the pose of this frame: 48 bytes a joint go to the device
-            const uint32_t n_frames = (spp + chunk - 1) / chunk;
-            const double angle = (double)bend_deg * (double)(frame / chunk + 1) / (double)n_frames * 3.14159265358979 / 180.0, c = std::cos(angle), sn = std::sin(angle);
-            const float py = bend_pivot[1], pz = bend_pivot[2];
-            const float joint_matrices[24] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0,                                    // joint 0 stays
-                                               1, 0, 0, 0, 0, (float)c, (float)-sn, (float)(py - c * py + sn * pz),    // joint 1: R_x (p - pivot) + pivot
-                                               0, (float)sn, (float)c, (float)(pz - sn * py - c * pz) };
-            CHECK(cgpt_scene_skin_mesh(ctx, 0, joint_matrices, 2));
-            CHECK(cgpt_reset_accumulator(ctx));
-            num_accumulated = 0;
         }
         cgpt_render_params p{};
         p.width = W; p.height = H; p.row_begin = 0; p.row_end = H;

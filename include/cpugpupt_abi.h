@@ -38,7 +38,9 @@ extern "C" {
                                  variance-guided edge stopping added new symbols (cgpt_denoise_variance_guided,
                                  cgpt_read_variance) and a new struct (cgpt_variance_params) only; following object transforms in
                                  the temporal stage is a new enum value only (CGPT_TEMPORAL_FOLLOW_TRANSFORMS); skinning added new
-                                 symbols only (cgpt_scene_set_skin, cgpt_scene_skin_mesh, cgpt_scene_clear_skin) */
+                                 symbols only (cgpt_scene_set_skin, cgpt_scene_skin_mesh, cgpt_scene_clear_skin); following poses in the
+                                 temporal stage is a new enum value (CGPT_TEMPORAL_FOLLOW_POSES) and one new symbol
+                                 (cgpt_read_previous_hits) only */
 
 enum cgpt_status {
     CGPT_OK = 0,
@@ -343,7 +345,8 @@ int cgpt_scene_update_primitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_ob
  * uploaded value.  Only mesh-light sampling reads it, and a skinned object cannot be a light.  Weights are used as given (never
  * renormalised, a zero weight's joint is still read); the blended A moves the normal, not its inverse transpose (exact for rigid
  * joints and uniform scale).  Everything else follows the refit: the caller resets the accumulator; the denoiser's guides are
- * recomputed and the temporal history is dropped, CGPT_TEMPORAL_FOLLOW_TRANSFORMS included; transforms (the pose is in object space:
+ * recomputed and the temporal history is dropped, CGPT_TEMPORAL_FOLLOW_TRANSFORMS included, unless the next temporal call sets
+ * CGPT_TEMPORAL_FOLLOW_POSES (below: it carries the hits on the re-posed objects back and keeps the history); transforms (the pose is in object space:
  * it appears at A pose + b), smooth flags, materials and roughnesses are kept; after cgpt_scene_upload_instanced every placement of
  * the object's group moves; a multi-device context poses every device's copy from that device's skin buffers; a HIP failure after the
  * first write drops the scene.  Refused, with nothing changed: no scene (CGPT_ERR_NO_SCENE); an object out of range or without a
@@ -547,13 +550,39 @@ int cgpt_denoise(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_pa
  * identity only, and a sphere moved by cgpt_scene_update_primitive drops the history); a refit, also through an instanced placement,
  * drops it; the light carried by the history is the old frames', so a moving object's shadow and the shading of a turning surface lag
  * by up to max_history samples.
+ * Skinned poses (CGPT_TEMPORAL_FOLLOW_POSES): with this flag a history stored before one or more cgpt_scene_skin_mesh calls
+ * stays usable as long as nothing but poses changed the scene (and transforms, when CGPT_TEMPORAL_FOLLOW_TRANSFORMS is set as well; each
+ * flag alone keeps the history across its own kind of edit only).  Per skinned object the context remembers the joint matrices of the last
+ * pose, or that no pose is known (before the first pose of a skin, after a cgpt_scene_refit_mesh of the object or of a placement sharing
+ * its copy); the history remembers the same.  An object whose copy no pose has written since the history was stored, or whose matrices
+ * equal the history's bytewise (A -> B -> A), is unposed; one whose matrices differ is re-posed; one where either side knows no pose, or
+ * the skin was installed anew, takes no history.  After cgpt_scene_upload_instanced every placement of the posed copy follows.  A pixel
+ * whose first hit lies on triangle tri of a re-posed object is carried back before anything else, in double on the float inputs:
+ *   P = x, or Ainv x + binv with the float inverse the scene holds for an object with a transform;
+ *   e1 = p1 - p0, e2 = p2 - p0, w = P - p0, g = e1 x e2, u = ((w x e2) . g) / (g . g), v = ((e1 x w) . g) / (g . g), with p0, p1, p2 the
+ *   current pose's corners; not clamped; g . g zero or not finite: no history;
+ *   q_c, m_c = the corners and normals cgpt_scene_skin_mesh's float arithmetic gives bind[tri], joints[tri], weights[tri] under the
+ *   history's matrices: bit for bit the triangle the history's pose wrote;
+ *   x' = (q0 + u (q1 - q0)) + v (q2 - q0);  n' = m0, or for an object with the smooth flag ((1 - u - v) m0 + u m1) + v m2 over its
+ *   length (m0 where the squared length is not > 1e-12);
+ *   x_p = A x' + b and n_p = normalize(Ainv^T n') through the object's current transform (x', n' themselves for an object without one),
+ *   each rounded to float once; anything not finite: no history.
+ * The reprojection then runs on x_p, n_p, the unchanged t and object index; with both flags an object that was re-posed and moved goes
+ * through its pose and then through D, two roundings to float.  A call in which no object was re-posed is the call without the flag bit for
+ * bit; one in which an object was reprojects (and applies the view-dependent rule) even when the camera bytes equal the history's.
+ * cgpt_read_previous_hits returns the records of the last successful call that carried a pose back, 8 floats per pixel of its band:
+ * {x_p.xyz, bits(state), n_p.xyz, 0}, state 0 (a miss, an object that was not re-posed: the pixel's own x, n), 1 (re-posed) or 2 (no
+ * history: its own x, n) -- with the guides, what a caller needs for motion vectors.  Limits: the light carried by the history lags, as
+ * for a moved object; the tree a posed mesh is traced through is the bind pose's, refitted; the side fallback of smooth normals (the
+ * geometric normal where the ray sees the interpolated one from behind) is not replayed for n', which only feeds the two validity tests;
+ * the pixels a pose uncovers start again; skinned lights do not exist.
  * Limits: without the flag camera motion only (an edit drops the history); first-hit reprojection only (what is seen
  * in a mirror or through glass is not followed); a multi-device context keeps the history on device_ids[0].
  * Like cgpt_denoise it leaves the accumulator, data.pixels, num_accumulated, cgpt_stats and the guides alone, and cgpt_denoise's output
  * does not depend on temporal calls.  Refusals (before any device work; nothing changes, the history included): every refusal of
  * cgpt_denoise; max_history not finite or < 1; normal_cos_min outside [-1, 1] or NaN; plane_tolerance not finite or <= 0; unknown
  * flag bits; cgpt_read_temporal_history without a history or with a wrong size -- all CGPT_ERR_INVALID. */
-enum cgpt_temporal_flags { CGPT_TEMPORAL_KEEP_VIEW_DEPENDENT = 1u, CGPT_TEMPORAL_FOLLOW_TRANSFORMS = 4u };   /* 2u is no flag: it stays refused as an unknown bit, as before */
+enum cgpt_temporal_flags { CGPT_TEMPORAL_KEEP_VIEW_DEPENDENT = 1u, CGPT_TEMPORAL_FOLLOW_TRANSFORMS = 4u, CGPT_TEMPORAL_FOLLOW_POSES = 16u };   /* 2u and 8u are no flags: they stay refused as unknown bits, as before */
 typedef struct cgpt_temporal_params {
     float    max_history;      /* cap on a pixel's history length, in samples; finite, >= 1 */
     float    normal_cos_min;   /* a tap is valid only if n_prev . n_cur >= this; in [-1, 1] */
@@ -567,6 +596,9 @@ int cgpt_temporal_reset(cgpt_ctx* ctx);
 /* 4 floats per pixel of the band the history was stored for: the merged colour c (the filter's input domain: demodulated when the call
  * was) and the history length H' */
 int cgpt_read_temporal_history(cgpt_ctx* ctx, float* dst, size_t n_floats);
+/* 8 floats per pixel of the band of the last successful temporal call with CGPT_TEMPORAL_FOLLOW_POSES in which an object was re-posed:
+ * {x_p.xyz, bits(state), n_p.xyz, 0} (above).  CGPT_ERR_INVALID when no such call has happened, or for a wrong size. */
+int cgpt_read_previous_hits(cgpt_ctx* ctx, float* dst, size_t n_floats);
 
 /* ---- variance-guided edge stopping (the third part of SVGF, Schied et al. 2017) ----
  * cgpt_denoise_variance_guided is cgpt_denoise with the colour edge-stop measured in standard deviations of each pixel instead of
