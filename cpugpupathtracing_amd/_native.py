@@ -27,6 +27,7 @@ TEMPORAL_FOLLOW_TRANSFORMS = 4
 TEMPORAL_FOLLOW_POSES = 16
 VARIANCE_TEMPORAL = 1
 SKIN_MAX_JOINTS = 1024      # cgpt_scene_set_skin
+MORPH_MAX_TARGETS = 256     # cgpt_scene_set_morph_targets
 
 f3 = C.c_float * 3
 
@@ -179,6 +180,9 @@ PROTOTYPES = {
     "cgpt_scene_set_skin": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), _u16p, _fp, C.c_uint32, C.c_uint32]),
     "cgpt_scene_skin_mesh": (C.c_int, [_vp, C.c_uint32, _fp, C.c_uint32]),
     "cgpt_scene_clear_skin": (C.c_int, [_vp, C.c_uint32]),
+    "cgpt_scene_set_morph_targets": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), C.POINTER(Triangle), C.c_uint32, C.c_uint32]),
+    "cgpt_scene_morph_mesh": (C.c_int, [_vp, C.c_uint32, _fp, C.c_uint32]),
+    "cgpt_scene_clear_morph_targets": (C.c_int, [_vp, C.c_uint32]),
     "cgpt_camera_from_view": (C.c_int, [_fp, _fp, C.c_float, C.c_float, C.POINTER(Camera)]),
     "cgpt_render": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(Settings), C.POINTER(RenderParams)]),
     "cgpt_reset_accumulator": (C.c_int, [_vp]),
@@ -249,6 +253,8 @@ PROTOTYPES = {
     "cgpth_scene_refit_mesh": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), C.c_uint32]),
     "cgpth_skin_triangles": (C.c_int, [C.POINTER(Triangle), _u16p, _fp, C.c_uint32, _fp, C.c_uint32, C.POINTER(Triangle)]),
     "cgpth_scene_skin_mesh": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), _u16p, _fp, C.c_uint32, _fp, C.c_uint32]),
+    "cgpth_morph_triangles": (C.c_int, [C.POINTER(Triangle), C.POINTER(Triangle), C.c_uint32, C.c_uint32, _fp, C.POINTER(Triangle)]),
+    "cgpth_scene_morph_mesh": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), C.POINTER(Triangle), C.c_uint32, C.c_uint32, _fp]),
     "cgpth_scene_update_primitive": (C.c_int, [_vp, C.c_uint32, C.POINTER(Object)]),
     "cgpth_scene_bvh_info": (C.c_int, [_vp, C.c_uint32, C.POINTER(BvhInfo)]),
     "cgpth_scene_bvh_export": (C.c_int, [_vp, C.c_uint32, C.POINTER(BvhNode), _up]),

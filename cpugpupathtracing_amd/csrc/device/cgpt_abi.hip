@@ -74,6 +74,7 @@ void FreeScene(cgpt_ctx* ctx)
 {
     ctx->sb = SceneBuffers{};
     ctx->skins.clear(); ctx->pose_stamp.clear();                               // an upload drops every skin
+    ctx->morphs.clear();                                                       // ... and every object's morph targets
     ctx->h_objects.clear(); ctx->refit_objects.clear(); ctx->record_perm.clear(); ctx->mesh_group.clear();
     ctx->footprint = cgpt_scene_footprint{};
     ctx->h_roughness.clear(); ctx->h_transmission_roughness.clear(); ctx->h_materials.clear(); ctx->h_lights.clear();
@@ -682,6 +683,16 @@ int cgpt_set_tuning(cgpt_ctx* ctx, const char* name, uint32_t value)
     if (strcmp(name, "skin_joints_lds") == 0) {                                // cgpt_scene_skin_mesh: where the kernel reads the joint matrices
         if (value > 1u) return CtxFail(ctx, CGPT_ERR_INVALID, "skin_joints_lds %u is neither 0 (vector cache) nor 1 (LDS)", value);
         ctx->skin_joints_lds = value;
+        return CGPT_OK;
+    }
+    if (strcmp(name, "morph_leaf_order") == 0) {                               // cgpt_scene_set_morph_targets: how the next set stores the targets
+        if (value > 1u) return CtxFail(ctx, CGPT_ERR_INVALID, "morph_leaf_order %u is neither 0 (as given) nor 1 (leaf-slot order)", value);
+        ctx->morph_leaf_order = value;
+        return CGPT_OK;
+    }
+    if (strcmp(name, "morph_max_blocks") == 0) {                               // cgpt_scene_morph_mesh: the cap of the kernel's grid
+        if (value < 1u || value > 1024u) return CtxFail(ctx, CGPT_ERR_INVALID, "morph_max_blocks %u outside [1, 1024]", value);
+        ctx->morph_max_blocks = value;
         return CGPT_OK;
     }
     bool known = false;

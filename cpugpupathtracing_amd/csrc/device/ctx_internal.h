@@ -42,6 +42,18 @@ struct SkinBuffers {
     bool pose_known = false;
     uint64_t serial = 0;
 };
+// The morph targets of one object (cgpt_scene_set_morph_targets): the base triangle and the n_targets displacement
+// records of every triangle in one buffer of float2 -- set 0 is the base, set 1 + k is target k.  leaf_order: set s, plane p (0..8, two of
+// a record's 18 floats), leaf slot i at data[(9 s + p) n_tris + i]; otherwise as given, triangle t's record at data[9 (s n_tris + t)].
+// `active` is the table a pose compacts its nonzero weights into, {target index, bits(weight)} each.  Not part of the scene's footprint;
+// an upload drops every object's targets.
+struct MorphBuffers {
+    DevBuf<float2> data;
+    DevBuf<uint2> active;                         // n_targets entries of room, written by every pose of the object (from `weights` by a skin's)
+    uint32_t n_targets = 0;                       // 0: no targets
+    uint32_t leaf_order = 1;                      // the knob "morph_leaf_order" as cgpt_scene_set_morph_targets read it
+    std::vector<float> weights;                   // the last weights given: all zero after the set
+};
 // What the temporal history keeps of the poses it was stored under (StoreTemporalKey): per object the index of the object whose skin
 // posed its copy (-1: no pose known) and, at that index, the skin's serial and matrices.
 struct PoseSnapshot {
@@ -132,6 +144,12 @@ struct cgpt_ctx {
     // vector cache (same results; DESIGN.md 5.26 has both timings)
     std::vector<cgpt::SkinBuffers> skins;
     uint32_t skin_joints_lds = 1;
+    // morph targets (cgpt_scene_set_morph_targets): per object, empty or as long as h_objects; cleared with the scene.  The knobs
+    // "morph_leaf_order" (what the next set stores: 1 leaf-slot order in component planes, 0 as given) and "morph_max_blocks" (the cap of
+    // the morph kernel's grid, 1..1024: a small mesh can be made to stride)
+    std::vector<cgpt::MorphBuffers> morphs;
+    uint32_t morph_leaf_order = 1;
+    uint32_t morph_max_blocks = 1024;
     // CGPT_TEMPORAL_FOLLOW_POSES: pose_generation counts the cgpt_scene_skin_mesh calls (they bump the other two generations as well);
     // pose_stamp[i] is its value at the last pose that wrote object i's copy (empty or as long as h_objects; cleared with the scene);
     // skin_serial numbers the cgpt_scene_set_skin installations
@@ -256,6 +274,9 @@ int GroupUpdatePrimitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_object* o
 int GroupSetSkin(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* bind_triangles, const uint16_t* joints, const float* weights, uint32_t n_tris, uint32_t n_joints);
 int GroupSkinMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uint32_t n_joints);
 int GroupClearSkin(cgpt_ctx* ctx, uint32_t obj_index);
+int GroupSetMorphTargets(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* base_triangles, const cgpt_triangle* target_deltas, uint32_t n_tris, uint32_t n_targets);
+int GroupMorphMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* weights, uint32_t n_targets);
+int GroupClearMorphTargets(cgpt_ctx* ctx, uint32_t obj_index);
 int GroupRender(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p);
 int GroupResetAccumulator(cgpt_ctx* ctx);
 int GroupReadAccumulator(cgpt_ctx* ctx, float* dst, size_t n_floats);

@@ -385,6 +385,22 @@ int GroupClearSkin(cgpt_ctx* ctx, uint32_t obj_index)
     return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_clear_skin(m, obj_index); });
 }
 
+// ... and its own morph targets
+int GroupSetMorphTargets(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* base_triangles, const cgpt_triangle* target_deltas, uint32_t n_tris, uint32_t n_targets)
+{
+    return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_set_morph_targets(m, obj_index, base_triangles, target_deltas, n_tris, n_targets); });
+}
+
+int GroupMorphMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* weights, uint32_t n_targets)
+{
+    return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_morph_mesh(m, obj_index, weights, n_targets); });
+}
+
+int GroupClearMorphTargets(cgpt_ctx* ctx, uint32_t obj_index)
+{
+    return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_clear_morph_targets(m, obj_index); });
+}
+
 int GroupUpdateRoughness(cgpt_ctx* ctx, const float* roughness, uint32_t n)
 {
     return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_update_roughness(m, roughness, n); });

@@ -20,6 +20,9 @@
 // records through the function refit_triangles writes them with), then the same bound pass.  No staging copy and no per-triangle host work:
 // the top-level box comes back from the refitted root record (or a one-block fold), and total_area is left as uploaded.  A skin remembers
 // the matrices of its last pose on the host (SkinBuffers::pose): what a temporal call with CGPT_TEMPORAL_FOLLOW_POSES compares (denoise.hip).
+// Morph targets (cgpt_scene_set_morph_targets / cgpt_scene_morph_mesh): the base triangles and the targets' displacements
+// stay on the device too, in leaf-slot order; morph_triangles blends them by the arithmetic of csrc/host/morph.h and, for an object that also
+// has a posed skin, hands each morphed corner to SkinCorner in registers.  Either call poses through PoseObject.
 // After cgpt_scene_upload_instanced the objects of a mesh group share the one copy these passes edit: the refit goes through any member's
 // RefitObject (they are equal), and the area and the top-level box, which are per object, are written for every member.
 #include <hip/hip_runtime.h>
@@ -35,6 +38,7 @@
 #include "ctx_internal.h"
 #include "device_scene.h"
 #include "minmax_std.h"
+#include "morph.h"
 #include "scene_layout.h"
 #include "skinning.h"
 
@@ -92,6 +96,20 @@ __global__ __launch_bounds__(kRefitThreads) void refit_triangles(const float* __
 // cgpt_scene_set_skin.  *range_flag is set when a posed position is not finite or lies beyond 1e30, where the refitted root bounds (a
 // fold from +-1e30) no longer give the top-level box.
 constexpr uint32_t kSkinMaxBlocks = 1024;                                     // 4 blocks a CU
+// the 12 blended entries of corner c of triangle t (skinning.h: SkinBlend), for the skin's and the morph's triangle pass
+__device__ __forceinline__ void blend_corner_joints(const float4* mat, const uint2* __restrict__ joints, const float4* __restrict__ weights, uint32_t t, int c, float (&m)[12])
+{
+    const uint2 jw = joints[3 * (size_t)t + c];                               // four uint16_t: the corner's joints
+    const float4 w = weights[3 * (size_t)t + c];
+    const uint32_t j0 = jw.x & 0xFFFFu, j1 = jw.x >> 16, j2 = jw.y & 0xFFFFu, j3 = jw.y >> 16;
+    for (int r = 0; r < 3; ++r) {
+        const float4 a0 = mat[3 * j0 + r], a1 = mat[3 * j1 + r], a2 = mat[3 * j2 + r], a3 = mat[3 * j3 + r];
+        m[4 * r] = SkinBlend(w.x, a0.x, w.y, a1.x, w.z, a2.x, w.w, a3.x);
+        m[4 * r + 1] = SkinBlend(w.x, a0.y, w.y, a1.y, w.z, a2.y, w.w, a3.y);
+        m[4 * r + 2] = SkinBlend(w.x, a0.z, w.y, a1.z, w.z, a2.z, w.w, a3.z);
+        m[4 * r + 3] = SkinBlend(w.x, a0.w, w.y, a1.w, w.z, a2.w, w.w, a3.w);
+    }
+}
 template <bool LDS>
 __global__ __launch_bounds__(kRefitThreads) void skin_triangles(const float2* __restrict__ bind, const uint2* __restrict__ joints, const float4* __restrict__ weights,
                                                                 const float4* __restrict__ matrices, uint32_t n_joints, float4* __restrict__ tri_leaf,
@@ -113,22 +131,73 @@ __global__ __launch_bounds__(kRefitThreads) void skin_triangles(const float2* __
         float tr[18];
         bool in_range = true;
         for (int c = 0; c < 3; ++c) {
-            const uint2 jw = joints[3 * (size_t)t + c];                       // four uint16_t: the corner's joints
-            const float4 w = weights[3 * (size_t)t + c];
-            const uint32_t j0 = jw.x & 0xFFFFu, j1 = jw.x >> 16, j2 = jw.y & 0xFFFFu, j3 = jw.y >> 16;
             float m[12];
-            for (int r = 0; r < 3; ++r) {
-                const float4 a0 = mat[3 * j0 + r], a1 = mat[3 * j1 + r], a2 = mat[3 * j2 + r], a3 = mat[3 * j3 + r];
-                m[4 * r] = SkinBlend(w.x, a0.x, w.y, a1.x, w.z, a2.x, w.w, a3.x);
-                m[4 * r + 1] = SkinBlend(w.x, a0.y, w.y, a1.y, w.z, a2.y, w.w, a3.y);
-                m[4 * r + 2] = SkinBlend(w.x, a0.z, w.y, a1.z, w.z, a2.z, w.w, a3.z);
-                m[4 * r + 3] = SkinBlend(w.x, a0.w, w.y, a1.w, w.z, a2.w, w.w, a3.w);
-            }
+            blend_corner_joints(mat, joints, weights, t, c, m);
             const float2 b0 = bind[9 * (size_t)t + 3 * c], b1 = bind[9 * (size_t)t + 3 * c + 1], b2 = bind[9 * (size_t)t + 3 * c + 2];
             const float pn[6] = { b0.x, b0.y, b1.x, b1.y, b2.x, b2.y };
             SkinCorner(m, pn, tr + 6 * c);
             in_range = in_range && fabsf(tr[6 * c]) <= 1e30f && fabsf(tr[6 * c + 1]) <= 1e30f && fabsf(tr[6 * c + 2]) <= 1e30f;   // false for a NaN too
         }
+        write_triangle_records(tr, leaf, keep, tri_orig, tri_normal, tri_base, t, n_tris_total);
+        if (!in_range) atomicOr(range_flag, 1u);
+    }
+}
+
+// The morph's triangle pass (cgpt_scene_morph_mesh, and cgpt_scene_skin_mesh on an object with targets; morph.h states the arithmetic):
+// skin_triangles with the bind corner computed here -- the base record plus the active targets' records, which stay in registers and are
+// the pn of SkinCorner when SKIN is set (no intermediate triangle exists), or the written triangle when it is not.  A thread per leaf
+// slot i, striding.  LEAF: `data` holds component planes in leaf-slot order -- float2 plane p of set s at data[(9 s + p) n + i], so the
+// lanes of a wave read consecutive 8-byte pieces (512 B an instruction); otherwise records as given, triangle t's at data[9 (s n + t)],
+// a 72-byte gather per lane as skin_triangles' bind read is.  `active` holds the pose's n_active nonzero weights in ascending target
+// order, {target, bits(weight)}: uniform reads.  The skin's joints and weights are in original order (by t) either way.
+template <bool SKIN, bool LDS, bool LEAF>
+__global__ __launch_bounds__(kRefitThreads) void morph_triangles(const float2* __restrict__ data, const uint2* __restrict__ active, uint32_t n_active,
+                                                                 const uint2* __restrict__ joints, const float4* __restrict__ weights,
+                                                                 const float4* __restrict__ matrices, uint32_t n_joints, float4* __restrict__ tri_leaf,
+                                                                 float4* __restrict__ tri_orig, float4* __restrict__ tri_normal, uint32_t* __restrict__ range_flag,
+                                                                 uint32_t leaf_base, uint32_t tri_base, uint32_t n, uint32_t n_tris_total)
+{
+    extern __shared__ float4 s_matrices[];
+    const float4* mat = matrices;
+    if (SKIN && LDS) {
+        for (uint32_t k = threadIdx.x; k < 3 * n_joints; k += blockDim.x) s_matrices[k] = matrices[k];
+        __syncthreads();
+        mat = s_matrices;
+    }
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        float4* leaf = tri_leaf + 3 * (size_t)(leaf_base + i);
+        const float4 keep = leaf[2];                                          // {pad, e2.z, tri_idx, last_in_leaf}
+        const uint32_t t = __float_as_uint(keep.z);
+        if (t >= n) continue;                                                 // validated at upload
+        const auto record = [&](uint32_t set, float (&out)[18]) {
+            for (int p = 0; p < 9; ++p) {
+                const float2 v = LEAF ? data[(9 * (size_t)set + p) * n + i] : data[9 * ((size_t)set * n + t) + p];
+                out[2 * p] = v.x; out[2 * p + 1] = v.y;
+            }
+        };
+        float base[18], x[18];
+        record(0u, base);
+        for (int j = 0; j < 18; ++j) x[j] = base[j];
+        for (uint32_t a = 0; a < n_active; ++a) {
+            const uint2 kw = active[a];
+            float d[18];
+            record(1u + kw.x, d);
+            MorphAccumulate(x, __uint_as_float(kw.y), d);
+        }
+        if (n_active != 0u) MorphNormalise(base, x);
+        float tr[18];
+        if (SKIN) {
+            for (int c = 0; c < 3; ++c) {
+                float m[12];
+                blend_corner_joints(mat, joints, weights, t, c, m);
+                SkinCorner(m, x + 6 * c, tr + 6 * c);
+            }
+        } else {
+            for (int j = 0; j < 18; ++j) tr[j] = x[j];
+        }
+        bool in_range = true;
+        for (int c = 0; c < 3; ++c)
+            in_range = in_range && fabsf(tr[6 * c]) <= 1e30f && fabsf(tr[6 * c + 1]) <= 1e30f && fabsf(tr[6 * c + 2]) <= 1e30f;   // false for a NaN too
         write_triangle_records(tr, leaf, keep, tri_orig, tri_normal, tri_base, t, n_tris_total);
         if (!in_range) atomicOr(range_flag, 1u);
     }
@@ -347,26 +416,42 @@ int SetSkin(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* bind, const 
     return CGPT_OK;
 }
 
-int SkinMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uint32_t n_joints)
+bool HasMorphTargets(const cgpt_ctx* ctx, uint32_t obj_index) { return obj_index < ctx->morphs.size() && ctx->morphs[obj_index].n_targets != 0u; }
+
+// the active targets of a pose's weights, {target, bits(weight)} in ascending order: a zero weight of either sign is skipped (morph.h)
+std::vector<uint2> ActiveTable(const float* weights, uint32_t n_targets)
 {
-    int rc = CheckObject(ctx, obj_index);
-    if (rc != CGPT_OK) return rc;
-    if (obj_index >= ctx->skins.size() || ctx->skins[obj_index].n_joints == 0u)
-        return CtxFail(ctx, CGPT_ERR_INVALID, "object %u has no skin (cgpt_scene_set_skin installs one)", obj_index);
-    SkinBuffers& sk = ctx->skins[obj_index];
-    if (n_joints != sk.n_joints) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u's skin has %u joints, got %u", obj_index, sk.n_joints, n_joints);
-    std::string why;
-    if (!CheckJointMatrices(joint_matrices, n_joints, why)) return CtxFail(ctx, CGPT_ERR_INVALID, "%s", why.c_str());
+    std::vector<uint2> table;
+    for (uint32_t k = 0; k < n_targets; ++k)
+        if (weights[k] != 0.0f) { uint32_t w; memcpy(&w, &weights[k], 4); table.push_back(make_uint2(k, w)); }
+    return table;
+}
+
+// Every pose writes both small inputs its kernel reads -- the active table and, with a skin, the joint matrices -- from the host values
+// it poses with, never trusting what an earlier call left on the device: a call that failed between its upload and its first scene write
+// keeps the scene and its committed weights / matrices, and the next pose through either call must use those.
+hipError_t UploadActiveTable(cgpt_ctx* ctx, const MorphBuffers& mb, const std::vector<uint2>& table)
+{
+    return table.empty() ? hipSuccess : hipMemcpyAsync(mb.active.p, table.data(), sizeof(uint2) * table.size(), hipMemcpyHostToDevice, ctx->stream);
+}
+
+// A device pose of object obj_index, shared by cgpt_scene_skin_mesh and cgpt_scene_morph_mesh: the triangle pass -- skin_triangles for an
+// object without morph targets, else morph_triangles over the n_active entries of its active table, through the skin's joints when
+// `skinned` -- the refit's bound pass and the top-level box.  The caller has validated; `upload` queues its own small copy (the joint
+// matrices or the active table) once nothing before the first write can fail any more.
+template <class Upload>
+int PoseObject(cgpt_ctx* ctx, uint32_t obj_index, bool skinned, uint32_t n_active, Upload&& upload)
+{
     const DevObject& d = ctx->h_objects[obj_index];
     const RefitObject& ro = ctx->refit_objects[obj_index];
     const uint32_t n_tris = ro.tri_count, tri_base = d.tri_base;
+    const bool morphed = HasMorphTargets(ctx, obj_index);
     TopLevelState top = ctx->top_state;                                        // may throw: before the first write
-    std::vector<float> pose(joint_matrices, joint_matrices + 12 * (size_t)n_joints);   // what a temporal call that follows poses compares (denoise.hip)
     if (ctx->pose_stamp.size() != ctx->h_objects.size()) ctx->pose_stamp.resize(ctx->h_objects.size(), 0);
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(sk.matrices.p, joint_matrices, sizeof(float) * 12 * (size_t)n_joints, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, upload());
     HIP_TRY(ctx, hipMemsetAsync(ctx->sb.skin_scratch.p, 0, sizeof(uint32_t) * kSkinScratchWords, ctx->stream));
 
     // from here on the scene changes
@@ -375,14 +460,34 @@ int SkinMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uin
             ctx->pose_stamp[j] = ctx->pose_generation;
             if (j < ctx->skins.size()) ctx->skins[j].pose_known = false;
         }
-    const dim3 grid(std::min((n_tris + kRefitThreads - 1) / kRefitThreads, kSkinMaxBlocks)), block(kRefitThreads);
-    const auto launch = [&](auto kernel, size_t lds_bytes) {
-        hipLaunchKernelGGL(kernel, grid, block, lds_bytes, ctx->stream, reinterpret_cast<const float2*>(sk.bind.p), reinterpret_cast<const uint2*>(sk.joints.p),
-                           reinterpret_cast<const float4*>(sk.weights.p), reinterpret_cast<const float4*>(sk.matrices.p), n_joints, ctx->sb.tri_leaf.p,
-                           ctx->sb.tri_orig.p, ctx->sb.tri_normal.p, ctx->sb.skin_scratch.p, ro.leaf_base, tri_base, n_tris, ctx->scene.n_tris_total);
-    };
-    if (ctx->skin_joints_lds) launch(skin_triangles<true>, 3 * sizeof(float4) * (size_t)n_joints);
-    else launch(skin_triangles<false>, 0);
+    const SkinBuffers none;
+    const SkinBuffers& sk = skinned ? ctx->skins[obj_index] : none;
+    const uint32_t n_joints = sk.n_joints;
+    const uint32_t blocks = (n_tris + kRefitThreads - 1) / kRefitThreads;
+    const dim3 block(kRefitThreads);
+    const size_t lds_bytes = skinned && ctx->skin_joints_lds ? 3 * sizeof(float4) * (size_t)n_joints : 0;
+    if (!morphed) {
+        const dim3 grid(std::min(blocks, kSkinMaxBlocks));
+        const auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, lds_bytes, ctx->stream, reinterpret_cast<const float2*>(sk.bind.p), reinterpret_cast<const uint2*>(sk.joints.p),
+                               reinterpret_cast<const float4*>(sk.weights.p), reinterpret_cast<const float4*>(sk.matrices.p), n_joints, ctx->sb.tri_leaf.p,
+                               ctx->sb.tri_orig.p, ctx->sb.tri_normal.p, ctx->sb.skin_scratch.p, ro.leaf_base, tri_base, n_tris, ctx->scene.n_tris_total);
+        };
+        if (ctx->skin_joints_lds) launch(skin_triangles<true>);
+        else launch(skin_triangles<false>);
+    } else {
+        const MorphBuffers& mb = ctx->morphs[obj_index];
+        const dim3 grid(std::min(blocks, ctx->morph_max_blocks));
+        const auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, lds_bytes, ctx->stream, mb.data.p, mb.active.p, n_active, reinterpret_cast<const uint2*>(sk.joints.p),
+                               reinterpret_cast<const float4*>(sk.weights.p), reinterpret_cast<const float4*>(sk.matrices.p), n_joints, ctx->sb.tri_leaf.p,
+                               ctx->sb.tri_orig.p, ctx->sb.tri_normal.p, ctx->sb.skin_scratch.p, ro.leaf_base, tri_base, n_tris, ctx->scene.n_tris_total);
+        };
+        const bool leaf = mb.leaf_order != 0u;
+        if (!skinned) { if (leaf) launch(morph_triangles<false, false, true>); else launch(morph_triangles<false, false, false>); }
+        else if (ctx->skin_joints_lds) { if (leaf) launch(morph_triangles<true, true, true>); else launch(morph_triangles<true, true, false>); }
+        else { if (leaf) launch(morph_triangles<true, false, true>); else launch(morph_triangles<true, false, false>); }
+    }
     REFIT_HIP_WRITING(ctx, hipGetLastError());
     REFIT_HIP_WRITING(ctx, LaunchRefitLevels(ctx, ro, tri_base));
 
@@ -418,8 +523,30 @@ int SkinMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uin
         if (j != obj_index && ctx->mesh_group[j] == ctx->mesh_group[obj_index]) memcpy(top.local_box.data() + 6 * (size_t)j, box, 24);
     REFIT_HIP_WRITING(ctx, WriteTopLevel(ctx, ctx->h_objects, top));
     ctx->top_state.local_box.swap(top.local_box);
+    return CGPT_OK;
+}
+
+int SkinMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uint32_t n_joints)
+{
+    int rc = CheckObject(ctx, obj_index);
+    if (rc != CGPT_OK) return rc;
+    if (obj_index >= ctx->skins.size() || ctx->skins[obj_index].n_joints == 0u)
+        return CtxFail(ctx, CGPT_ERR_INVALID, "object %u has no skin (cgpt_scene_set_skin installs one)", obj_index);
+    SkinBuffers& sk = ctx->skins[obj_index];
+    if (n_joints != sk.n_joints) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u's skin has %u joints, got %u", obj_index, sk.n_joints, n_joints);
+    std::string why;
+    if (!CheckJointMatrices(joint_matrices, n_joints, why)) return CtxFail(ctx, CGPT_ERR_INVALID, "%s", why.c_str());
+    std::vector<float> pose(joint_matrices, joint_matrices + 12 * (size_t)n_joints);   // what a temporal call that follows poses compares (denoise.hip)
+    const bool morphed = HasMorphTargets(ctx, obj_index);                      // the morphed base is the bind pose then: one kernel does both
+    std::vector<uint2> table;                                                  // ... of the last weights given, written again: see UploadActiveTable
+    if (morphed) table = ActiveTable(ctx->morphs[obj_index].weights.data(), ctx->morphs[obj_index].n_targets);
+    rc = PoseObject(ctx, obj_index, true, (uint32_t)table.size(), [&] {
+        const hipError_t e = hipMemcpyAsync(sk.matrices.p, joint_matrices, sizeof(float) * 12 * (size_t)n_joints, hipMemcpyHostToDevice, ctx->stream);
+        return e != hipSuccess || !morphed ? e : UploadActiveTable(ctx, ctx->morphs[obj_index], table);
+    });
+    if (rc != CGPT_OK) return rc;
     sk.pose.swap(pose);
-    sk.pose_known = true;
+    sk.pose_known = !morphed;                                                  // the matrices alone do not tell a morphed pose: "no pose known"
     return CGPT_OK;
 }
 
@@ -429,6 +556,96 @@ int ClearSkin(cgpt_ctx* ctx, uint32_t obj_index)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->skins[obj_index] = SkinBuffers{};
+    return CGPT_OK;
+}
+
+// ---- morph targets (cgpt_scene_set_morph_targets / cgpt_scene_morph_mesh / cgpt_scene_clear_morph_targets) ------------
+int SetMorphTargets(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* base, const cgpt_triangle* deltas, uint32_t n_tris, uint32_t n_targets)
+{
+    int rc = CheckObject(ctx, obj_index);
+    if (rc != CGPT_OK) return rc;
+    const DevObject& d = ctx->h_objects[obj_index];
+    const RefitObject& ro = ctx->refit_objects[obj_index];
+    if (d.kind != CGPT_OBJECT_MESH && d.kind != CGPT_OBJECT_TRIANGLE)
+        return CtxFail(ctx, CGPT_ERR_INVALID, "object %u is a %s: it has no triangles to morph", obj_index, KindName(d.kind));
+    for (const uint32_t li : ctx->h_lights)
+        if (li == obj_index) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u is a light: a pose does not recompute the area its sampling reads, so it takes no morph targets", obj_index);
+    if (!base || !deltas) return CtxFail(ctx, CGPT_ERR_INVALID, "%s is null", !base ? "base_triangles" : "target_deltas");
+    if (n_tris != ro.tri_count) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u has %u triangles, got %u (a morph keeps the topology)", obj_index, ro.tri_count, n_tris);
+    std::string why;
+    if (!CheckMorphTargets(base, deltas, n_tris, n_targets, why)) return CtxFail(ctx, CGPT_ERR_INVALID, "%s", why.c_str());
+
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                           // nothing uses the targets this set replaces
+    const size_t n = n_tris, per_set = 9 * n;                                  // float2 a set
+    MorphBuffers mb;                                                           // installed whole, or not at all
+    mb.leaf_order = ctx->morph_leaf_order;
+    mb.weights.assign(n_targets, 0.0f);
+    HIP_TRY(ctx, mb.data.Alloc(per_set * ((size_t)n_targets + 1)));
+    HIP_TRY(ctx, mb.active.Alloc(n_targets));
+    HIP_TRY(ctx, ctx->sb.skin_scratch.Grow(kSkinScratchWords));
+    if (mb.leaf_order) {
+        // The slot -> triangle map is fixed while the targets live (an upload drops them, a refit keeps the tree): every set goes up as nine
+        // float2 planes in leaf-slot order, permuted here, one set at a time
+        std::vector<float4> leaf_tail(n);                                      // {pad, e2.z, tri_idx, last_in_leaf} of every leaf slot
+        HIP_TRY(ctx, hipMemcpy2D(leaf_tail.data(), sizeof(float4), ctx->sb.tri_leaf.p + 3 * (size_t)ro.leaf_base + 2, 3 * sizeof(float4),
+                                   sizeof(float4), n, hipMemcpyDeviceToHost));
+        std::vector<uint32_t> slot_tri(n);
+        for (size_t i = 0; i < n; ++i) {
+            memcpy(&slot_tri[i], &leaf_tail[i].z, 4);
+            if (slot_tri[i] >= n_tris) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u: leaf slot %zu names triangle %u", obj_index, i, slot_tri[i]);
+        }
+        std::vector<float2> planes(per_set);
+        for (uint32_t s = 0; s <= n_targets; ++s) {
+            const float* src = reinterpret_cast<const float*>(s == 0 ? base : deltas + (size_t)(s - 1) * n);
+            for (size_t i = 0; i < n; ++i) {
+                const float* rec = src + 18 * (size_t)slot_tri[i];
+                for (int p = 0; p < 9; ++p) planes[p * n + i] = make_float2(rec[2 * p], rec[2 * p + 1]);
+            }
+            HIP_TRY(ctx, hipMemcpy(mb.data.p + per_set * s, planes.data(), sizeof(float2) * per_set, hipMemcpyHostToDevice));
+        }
+    } else {
+        HIP_TRY(ctx, hipMemcpy(mb.data.p, base, sizeof(cgpt_triangle) * n, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(mb.data.p + per_set, deltas, sizeof(cgpt_triangle) * n * n_targets, hipMemcpyHostToDevice));
+    }
+    mb.n_targets = n_targets;
+    if (ctx->morphs.size() != ctx->h_objects.size()) ctx->morphs.resize(ctx->h_objects.size());
+    ctx->morphs[obj_index] = std::move(mb);
+    return CGPT_OK;
+}
+
+int MorphMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* weights, uint32_t n_targets)
+{
+    int rc = CheckObject(ctx, obj_index);
+    if (rc != CGPT_OK) return rc;
+    if (!HasMorphTargets(ctx, obj_index))
+        return CtxFail(ctx, CGPT_ERR_INVALID, "object %u has no morph targets (cgpt_scene_set_morph_targets installs them)", obj_index);
+    MorphBuffers& mb = ctx->morphs[obj_index];
+    if (n_targets != mb.n_targets) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u has %u morph targets, got %u", obj_index, mb.n_targets, n_targets);
+    std::string why;
+    if (!CheckMorphWeights(weights, n_targets, why)) return CtxFail(ctx, CGPT_ERR_INVALID, "%s", why.c_str());
+    std::vector<float> kept(weights, weights + n_targets);
+    const std::vector<uint2> table = ActiveTable(weights, n_targets);
+    // a skin that has been posed since it was installed takes part with the matrices of its last pose (sk.pose, written again: see UploadActiveTable)
+    const bool skinned = obj_index < ctx->skins.size() && ctx->skins[obj_index].n_joints != 0u && !ctx->skins[obj_index].pose.empty();
+    ctx->scene_generation++; ctx->shape_generation++;                          // accepted -- as a refit: guides and temporal history are stale, CGPT_TEMPORAL_FOLLOW_POSES included
+    rc = PoseObject(ctx, obj_index, skinned, (uint32_t)table.size(), [&] {
+        const hipError_t e = UploadActiveTable(ctx, mb, table);
+        if (e != hipSuccess || !skinned) return e;
+        const SkinBuffers& sk = ctx->skins[obj_index];
+        return hipMemcpyAsync(sk.matrices.p, sk.pose.data(), sizeof(float) * sk.pose.size(), hipMemcpyHostToDevice, ctx->stream);
+    });
+    if (rc != CGPT_OK) return rc;
+    mb.weights.swap(kept);
+    return CGPT_OK;
+}
+
+int ClearMorphTargets(cgpt_ctx* ctx, uint32_t obj_index)
+{
+    if (!HasMorphTargets(ctx, obj_index)) return CGPT_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->morphs[obj_index] = MorphBuffers{};
     return CGPT_OK;
 }
 
@@ -577,6 +794,28 @@ int cgpt_scene_clear_skin(cgpt_ctx* ctx, uint32_t obj_index)
     if (!ctx) return CGPT_ERR_INVALID;
     if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupClearSkin(ctx, obj_index); });
     return Guarded(ctx, __func__, [&] { return ClearSkin(ctx, obj_index); });
+}
+
+int cgpt_scene_set_morph_targets(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* base_triangles, const cgpt_triangle* target_deltas,
+                                 uint32_t n_tris, uint32_t n_targets)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupSetMorphTargets(ctx, obj_index, base_triangles, target_deltas, n_tris, n_targets); });
+    return Guarded(ctx, __func__, [&] { return SetMorphTargets(ctx, obj_index, base_triangles, target_deltas, n_tris, n_targets); });   // the scene does not change
+}
+
+int cgpt_scene_morph_mesh(cgpt_ctx* ctx, uint32_t obj_index, const float* weights, uint32_t n_targets)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupMorphMesh(ctx, obj_index, weights, n_targets); });
+    return Guarded(ctx, __func__, [&] { return MorphMesh(ctx, obj_index, weights, n_targets); });   // bumps the generations once the call is accepted
+}
+
+int cgpt_scene_clear_morph_targets(cgpt_ctx* ctx, uint32_t obj_index)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupClearMorphTargets(ctx, obj_index); });
+    return Guarded(ctx, __func__, [&] { return ClearMorphTargets(ctx, obj_index); });
 }
 
 int cgpt_scene_export_bvh(cgpt_ctx* ctx, uint32_t obj_index, cgpt_bvh_node* nodes_out, uint32_t n_nodes)

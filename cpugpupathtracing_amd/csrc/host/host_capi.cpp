@@ -10,6 +10,7 @@
 #include "gltf_loader.h"
 #include "image_io.h"
 #include "mesh_gen.h"
+#include "morph.h"
 #include "scene.h"
 #include "shade_items.h"
 #include "skinning.h"
@@ -488,6 +489,41 @@ int cgpth_scene_skin_mesh(cgpth_scene* scene, uint32_t obj_index, const cgpt_tri
         if (!CheckSkin(bind_triangles, joints, weights, n_tris, n_joints, err) || !CheckJointMatrices(joint_matrices, n_joints, err)) return Fail(err);
         std::vector<cgpt_triangle> posed(n_tris);
         SkinTriangles(bind_triangles, joints, weights, n_tris, joint_matrices, posed.data());
+        return cgpth_scene_refit_mesh(scene, obj_index, posed.data(), n_tris);
+    });
+}
+
+int cgpth_morph_triangles(const cgpt_triangle* base_triangles, const cgpt_triangle* target_deltas, uint32_t n_tris, uint32_t n_targets,
+                          const float* weights, cgpt_triangle* out_triangles)
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        std::string err;
+        if (!CheckMorphTargets(base_triangles, target_deltas, n_tris, n_targets, err) || !CheckMorphWeights(weights, n_targets, err)) return Fail(err);
+        if (!out_triangles) return Fail("out_triangles is null");
+        MorphTriangles(base_triangles, target_deltas, n_tris, n_targets, weights, out_triangles);
+        return CGPT_OK;
+    });
+}
+
+int cgpth_scene_morph_mesh(cgpth_scene* scene, uint32_t obj_index, const cgpt_triangle* base_triangles, const cgpt_triangle* target_deltas,
+                           uint32_t n_tris, uint32_t n_targets, const float* weights)
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        if (!scene) return Fail("scene is null");
+        if (obj_index >= scene->scene.objects.size())
+            return Fail("object " + std::to_string(obj_index) + " out of range (" + std::to_string(scene->scene.objects.size()) + " objects)");
+        const Object& o = scene->scene.objects[obj_index];
+        if (!o.has_bvh && o.kind != CGPT_OBJECT_TRIANGLE)
+            return Fail("object " + std::to_string(obj_index) + " is a " + KindName(o) + ": it has no triangles to morph");
+        for (const uint32_t li : scene->scene.light_source_indices)
+            if (li == obj_index) return Fail("object " + std::to_string(obj_index) + " is a light: a pose does not recompute the area its sampling reads, so it takes no morph targets");
+        const uint32_t n = o.has_bvh ? o.bvh->NumTriangles() : 1u;
+        if (n_tris != n)
+            return Fail("object " + std::to_string(obj_index) + " has " + std::to_string(n) + " triangles, got " + std::to_string(n_tris) + " (a morph keeps the topology)");
+        std::string err;
+        if (!CheckMorphTargets(base_triangles, target_deltas, n_tris, n_targets, err) || !CheckMorphWeights(weights, n_targets, err)) return Fail(err);
+        std::vector<cgpt_triangle> posed(n_tris);
+        MorphTriangles(base_triangles, target_deltas, n_tris, n_targets, weights, posed.data());
         return cgpth_scene_refit_mesh(scene, obj_index, posed.data(), n_tris);
     });
 }

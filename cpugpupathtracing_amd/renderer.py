@@ -11,7 +11,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _native as N
-from .scene import Scene, Settings, _joint_matrices, _skin_arrays, _triangle_ptr, _triangle_rows, primitive_abi
+from .scene import Scene, Settings, _joint_matrices, _morph_arrays, _morph_weights, _skin_arrays, _triangle_ptr, _triangle_rows, primitive_abi
 
 
 _IDENTITY = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float32)
@@ -204,6 +204,28 @@ class Renderer:
     def clear_skin(self, obj_index: int):
         """cgpt_scene_clear_skin: frees the skin of object `obj_index`; the geometry stays at the last pose.  No skin: nothing happens."""
         self._check(self.L.cgpt_scene_clear_skin(self._ctx, obj_index))
+
+    def set_morph_targets(self, obj_index: int, base_triangles, deltas):
+        """cgpt_scene_set_morph_targets: keeps morph targets for uploaded mesh (or triangle object) `obj_index` on the device -- its base
+        triangles ((n, 18) in the object's original order, as refit_mesh takes them) and deltas (n_targets, n, 18), displacement records of
+        the same layout -- for morph_mesh to pose from.  The scene does not change until the first pose; the weights start
+        at zero.  While they are installed the morphed base is also the bind pose of the object's skin (skin_mesh).  A second call replaces
+        them; upload() drops them; a light, a sphere or a plane takes none.  n_targets: 1..256."""
+        rows, d = _morph_arrays(base_triangles, deltas)
+        self._check(self.L.cgpt_scene_set_morph_targets(self._ctx, obj_index, _triangle_ptr(rows), _triangle_ptr(d), rows.shape[0], d.shape[0]))
+
+    def morph_mesh(self, obj_index: int, weights):
+        """cgpt_scene_morph_mesh: poses object `obj_index` on the device from one weight per installed target (used as given; a zero of
+        either sign skips its target).  Always from the base; the tree is kept and its bounds follow, as after
+        refit_mesh(obj_index, morph_triangles(...)) -- or, with a posed skin, refit_mesh(obj_index, skin_triangles(morph_triangles(...), ...))
+        -- except that total_area keeps its uploaded value.  Only the device copy changes.  Call reset_accumulator() before the next frame."""
+        w = _morph_weights(weights)
+        self._check(self.L.cgpt_scene_morph_mesh(self._ctx, obj_index, w.ctypes.data_as(C.POINTER(C.c_float)), w.size))
+
+    def clear_morph_targets(self, obj_index: int):
+        """cgpt_scene_clear_morph_targets: frees the targets of object `obj_index`; the geometry stays where it is and a skin goes back to
+        its own bind pose at its next skin_mesh.  No targets: nothing happens."""
+        self._check(self.L.cgpt_scene_clear_morph_targets(self._ctx, obj_index))
 
     def export_bvh(self, obj_index: int) -> np.ndarray:
         """The device's tree of mesh `obj_index` as it is now (after refits): nodes[n,8] uint32 words in the reference's 32-byte layout

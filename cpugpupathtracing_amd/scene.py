@@ -136,6 +136,37 @@ def skin_triangles(bind_triangles, joints, weights, matrices) -> np.ndarray:
     return out
 
 
+def _morph_arrays(base_triangles, deltas, weights=None):
+    """Morph targets as the library takes them: (n, 18) float32 base triangles, (n_targets, n, 18) float32 deltas, n_targets weights."""
+    rows = _triangle_rows(base_triangles)
+    d = np.ascontiguousarray(deltas, dtype=np.float32)
+    if rows.shape[0] == 0 or d.size % rows.size:
+        raise ValueError("deltas are (n_targets, n_tris, 18): one record per base triangle and target")
+    d = d.reshape(d.size // rows.size, rows.shape[0], 18)
+    if weights is None:
+        return rows, d
+    return rows, d, _morph_weights(weights, d.shape[0])
+
+
+def _morph_weights(weights, n_targets=None) -> np.ndarray:
+    w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
+    if n_targets is not None and w.size != n_targets:
+        raise ValueError(f"{n_targets} targets take {n_targets} weights, got {w.size}")
+    return w
+
+
+def morph_triangles(base_triangles, deltas, weights) -> np.ndarray:
+    """Morph targets on the host (cgpth_morph_triangles): the (n, 18) float32 triangles of the pose.
+    base_triangles: (n, 18) as triangles_from_arrays returns them; deltas: (n_targets, n, 18) displacements in the same layout (per corner
+    a position delta and a normal delta); weights: n_targets float32, used as given, a zero of either sign skipped.
+    It is what Renderer.morph_mesh computes on the device, to the bit; the bind pose of a skin that follows it."""
+    rows, d, w = _morph_arrays(base_triangles, deltas, weights)
+    out = np.empty_like(rows)
+    _host_check(N.lib().cgpth_morph_triangles(_triangle_ptr(rows), _triangle_ptr(d), rows.shape[0], d.shape[0], w.ctypes.data_as(C.POINTER(C.c_float)),
+                                              _triangle_ptr(out)), "morph_triangles")
+    return out
+
+
 def primitive_abi(kind: int, mat_index: int, center=None, radius=None, normal=None, point=None) -> N.Object:
     """A cgpt_object for update_primitive: a sphere (center, radius) or a plane (normal, point)."""
     o = N.Object()
@@ -455,6 +486,14 @@ class Scene:
         _host_check(N.lib().cgpth_scene_skin_mesh(self._h, obj_index, _triangle_ptr(rows), j.ctypes.data_as(C.POINTER(C.c_uint16)),
                                                   w.ctypes.data_as(C.POINTER(C.c_float)), rows.shape[0], m.ctypes.data_as(C.POINTER(C.c_float)),
                                                   m.shape[0]), "skin_mesh")
+
+    def morph_mesh(self, obj_index: int, base_triangles, deltas, weights):
+        """The host mirror of Renderer.set_morph_targets + Renderer.morph_mesh (cgpth_scene_morph_mesh): refit_mesh of
+        morph_triangles(base_triangles, deltas, weights).  The host scene keeps no targets: every call takes them whole.  A light, a
+        sphere or a plane is refused, as on the device."""
+        rows, d, w = _morph_arrays(base_triangles, deltas, weights)
+        _host_check(N.lib().cgpth_scene_morph_mesh(self._h, obj_index, _triangle_ptr(rows), _triangle_ptr(d), rows.shape[0], d.shape[0],
+                                                   w.ctypes.data_as(C.POINTER(C.c_float))), "morph_mesh")
 
     def update_primitive(self, obj_index: int, center=None, radius=None, normal=None, point=None):
         """Primitive::RenderImGui's sliders (ref: Primitives.cpp:385-410): a sphere's center / radius or a plane's normal / point;

@@ -4,7 +4,7 @@
 //
 //   g++ -std=c++17 -Iinclude -Icpugpupathtracing_amd/csrc/host examples/render_main.cpp
 //       -Lcpugpupathtracing_amd/lib -lcpugpupt -Wl,-rpath,$PWD/cpugpupathtracing_amd/lib -o render_main   (one command line)
-//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--spin DEG] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [--bend DEG] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
+//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--spin DEG] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [--bend DEG] [--bulge W] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
 // --gpus N: ONE context over the first N GPUs of the node (cgpt_ctx_create with n_devices = N): every frame is spread over them in
 // interleaved row bands and the read-back gathers the float4 bands with one RCCL exchange over xGMI; the loop below does not
 // change.  --collective: take that code path with N = 1 too (what a one-GPU box can test).
@@ -48,6 +48,10 @@
 // with CGPT_TEMPORAL_FOLLOW_POSES, which carries the mesh's pixels back to where the same surface points were under the frame before and keeps
 // everyone's history (bend_NN_temporal.ppm).  Takes [width height spp] only.  A demonstration of the device calls, not a loader
 // feature: glTF skins are not imported.
+// --bulge W: a morphing mesh -- the mesh (object 0) gets one procedural morph target on the device (cgpt_scene_set_morph_targets: every corner
+// pushed out along its normal by its height between the mesh's lowest and highest point) and is posed once per frame with weight W * frame / 7
+// (cgpt_scene_morph_mesh); frames as for --bend, named bulge_NN_*.ppm.  With --bend DEG as well the mesh has both and one
+// kernel morphs and skins it (the frames keep the bend_ names); a morph is not followed by the temporal stage, which starts a new history.
 // move_at > 0 scripts the input half of Update(dt) (ref: Main.cpp:277-297, Camera::Update :104-131): after that many samples the
 // camera is translated by (right, up, forward) as the A/D, Space/Shift, W/S keys would, the view changes, and the accumulator
 // is reset (ref: ResetAccumulator, Main.cpp:238-243) before the remaining samples are rendered from the new position.
@@ -74,7 +78,7 @@ using namespace cgpt;
 
 int main(int argc, char** argv)
 {
-    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool spin = false; float spin_deg = 0.0f; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false; uint32_t n_instances = 0; bool bend = false; float bend_deg = 0.0f;
+    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool spin = false; float spin_deg = 0.0f; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false; uint32_t n_instances = 0; bool bend = false; float bend_deg = 0.0f; bool bulge = false; float bulge_w = 0.0f;
     bool has_transform = false; float mesh_transform[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
     MeshBVH::BuildOption bvh_option = MeshBVH::BuildOption_SAHSplitIntervals;
     while (argc > 1 && std::string(argv[1]).rfind("--", 0) == 0) {
@@ -84,6 +88,7 @@ int main(int argc, char** argv)
         else if (std::string(argv[1]) == "--temporal") { temporal = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--spin" && argc > 2) { spin = true; spin_deg = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--bend" && argc > 2) { bend = true; bend_deg = (float)atof(argv[2]); argv += 2; argc -= 2; }
+        else if (std::string(argv[1]) == "--bulge" && argc > 2) { bulge = true; bulge_w = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--variance-guided") { variance_guided = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--smooth") { smooth = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--mesh-transform" && argc > 13) {
@@ -235,7 +240,8 @@ int main(int argc, char** argv)
     }
     // --bend: a procedural two-joint skin of the mesh (object 0).  A corner's weight on joint 1 is its height between the mesh's lowest and
     // highest point; joint 0 stays, joint 1 turns about the x axis through the middle of the mesh.  The skin goes to the device once.
-    if (bend) {
+    // --bulge: one procedural morph target of the same mesh, a push along the normal by the same height; it goes to the device once too.
+    if (bend || bulge) {
         float bend_pivot[3] = { 0.0f, 0.0f, 0.0f };
         const cgpt_object& o = desc.objects[0];
         const cgpt_triangle* bind = desc.triangles + o.tri_offset;      // original order, as cgpt_scene_refit_mesh takes them
@@ -254,7 +260,17 @@ int main(int argc, char** argv)
                 weights[12 * (size_t)t + 4 * c] = 1.0f - h; weights[12 * (size_t)t + 4 * c + 1] = h;
             }
         }
-        CHECK(cgpt_scene_set_skin(ctx, 0, bind, joints.data(), weights.data(), o.tri_count, 2));
+        if (bend) CHECK(cgpt_scene_set_skin(ctx, 0, bind, joints.data(), weights.data(), o.tri_count, 2));
+        if (bulge) {
+            std::vector<cgpt_triangle> target(o.tri_count);              // displacements in the cgpt_triangle layout: position delta = height * normal, no normal delta
+            for (uint32_t t = 0; t < o.tri_count; ++t) {
+                const cgpt_vertex* const corner[3] = { &bind[t].v0, &bind[t].v1, &bind[t].v2 };
+                cgpt_vertex* const d[3] = { &target[t].v0, &target[t].v1, &target[t].v2 };
+                for (int c = 0; c < 3; ++c)
+                    for (int a = 0; a < 3; ++a) { d[c]->pos[a] = weights[12 * (size_t)t + 4 * c + 1] * corner[c]->normal[a]; d[c]->normal[a] = 0.0f; }
+            }
+            CHECK(cgpt_scene_set_morph_targets(ctx, 0, bind, target.data(), o.tri_count, 1));
+        }
 
         std::vector<uint32_t> px((size_t)W * H);                         // the mesh bends every frame: SkinMesh, ResetAccumulator, Render, present
         const cgpt_camera cam = scene.camera.Abi();
@@ -265,7 +281,9 @@ int main(int argc, char** argv)
             const float joint_matrices[24] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0,                                    // joint 0 stays
                                                1, 0, 0, 0, 0, (float)c, (float)-sn, (float)(py - c * py + sn * pz),    // joint 1: R_x (p - pivot) + pivot
                                                0, (float)sn, (float)c, (float)(pz - sn * py - c * pz) };
-            CHECK(cgpt_scene_skin_mesh(ctx, 0, joint_matrices, 2));
+            const float morph_weight = bulge_w * (float)frame / 7.0f;
+            if (bulge) CHECK(cgpt_scene_morph_mesh(ctx, 0, &morph_weight, 1));       // 4 bytes a target go to the device
+            if (bend) CHECK(cgpt_scene_skin_mesh(ctx, 0, joint_matrices, 2));        // on a mesh with targets: the morphed base through the joints, one kernel
             CHECK(cgpt_reset_accumulator(ctx));
             cgpt_render_params p{};
             p.width = W; p.height = H; p.row_begin = 0; p.row_end = H;
@@ -273,11 +291,12 @@ int main(int argc, char** argv)
             CHECK(cgpt_render(ctx, &cam, &settings, &p));
             char name[64]; std::string err;
             CHECK(cgpt_read_pixels(ctx, px.data(), px.size()));
-            snprintf(name, sizeof(name), "bend_%02u_raw.ppm", frame); WritePPM(name, px.data(), W, H, err);
+            const char* tag = bend ? "bend" : "bulge";
+            snprintf(name, sizeof(name), "%s_%02u_raw.ppm", tag, frame); WritePPM(name, px.data(), W, H, err);
             CHECK(cgpt_denoise(ctx, &cam, nullptr, nullptr, 0, px.data(), px.size()));
-            snprintf(name, sizeof(name), "bend_%02u_denoised.ppm", frame); WritePPM(name, px.data(), W, H, err);
+            snprintf(name, sizeof(name), "%s_%02u_denoised.ppm", tag, frame); WritePPM(name, px.data(), W, H, err);
             CHECK(cgpt_denoise_temporal(ctx, &cam, nullptr, &tp, nullptr, 0, px.data(), px.size()));   // once per rendered frame
-            snprintf(name, sizeof(name), "bend_%02u_temporal.ppm", frame); WritePPM(name, px.data(), W, H, err);
+            snprintf(name, sizeof(name), "%s_%02u_temporal.ppm", tag, frame); WritePPM(name, px.data(), W, H, err);
         }
         cgpt_ctx_destroy(ctx);
         return 0;

@@ -40,7 +40,8 @@ extern "C" {
                                  the temporal stage is a new enum value only (CGPT_TEMPORAL_FOLLOW_TRANSFORMS); skinning added new
                                  symbols only (cgpt_scene_set_skin, cgpt_scene_skin_mesh, cgpt_scene_clear_skin); following poses in the
                                  temporal stage is a new enum value (CGPT_TEMPORAL_FOLLOW_POSES) and one new symbol
-                                 (cgpt_read_previous_hits) only */
+                                 (cgpt_read_previous_hits) only; morph targets added new symbols only
+                                 (cgpt_scene_set_morph_targets, cgpt_scene_morph_mesh, cgpt_scene_clear_morph_targets) */
 
 enum cgpt_status {
     CGPT_OK = 0,
@@ -241,7 +242,8 @@ int cgpt_scene_upload(cgpt_ctx* ctx, const cgpt_scene_desc* scene);
  * An added export: CGPT_ABI_VERSION stays 2. */
 int cgpt_scene_upload_instanced(cgpt_ctx* ctx, const cgpt_scene_desc* scene);
 /* What the uploaded scene occupies, after either upload (CGPT_ERR_NO_SCENE without one; a multi-device context reports one device, and
- * every device holds the same).  No edit changes it; the skin buffers of cgpt_scene_set_skin are not counted.  An added export:
+ * every device holds the same).  No edit changes it; the skin buffers of cgpt_scene_set_skin and the target buffers of
+ * cgpt_scene_set_morph_targets are not counted.  An added export:
  * CGPT_ABI_VERSION stays 2. */
 typedef struct cgpt_scene_footprint {
     uint64_t device_bytes;       /* bytes of the scene's allocations on one device: the triangle, node, normal, material, object and light
@@ -359,6 +361,50 @@ int cgpt_scene_set_skin(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* 
                         uint32_t n_tris, uint32_t n_joints);
 int cgpt_scene_skin_mesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uint32_t n_joints);
 int cgpt_scene_clear_skin(cgpt_ctx* ctx, uint32_t obj_index);
+
+/* ---- morph targets (blend shapes): pose a mesh on the device from a few weights, fused with its skin ----
+ * The base triangles and the targets' displacements stay on the device; a pose is a write of the active (index, weight) pairs and one
+ * kernel in front of the refit's bound pass (csrc/host/morph.h states the arithmetic and cgpth_morph_triangles
+ * evaluates it on the host, tests/morph_ref.py in numpy).  Added exports: CGPT_ABI_VERSION stays 2.
+ *
+ * cgpt_scene_set_morph_targets: copies base_triangles (n_tris triangles in the object's original order, as cgpt_scene_refit_mesh takes
+ * them) and target_deltas (n_targets x n_tris records, target-major: target_deltas[k * n_tris + t]; a record has the cgpt_triangle
+ * layout but holds displacements, per corner a position delta and a normal delta -- glTF's POSITION / NORMAL target accessors expanded
+ * to unindexed corners) to device buffers the context owns (72 (n_targets + 1) bytes a triangle, on every device of a multi-device
+ * context; stored in the order of the object's leaf slots, or in the given order with the cgpt_set_tuning knob "morph_leaf_order" 0).
+ * THE SCENE DOES NOT CHANGE: the geometry moves at the first pose; the weights start at all zero.  A second call on the same object
+ * replaces its targets.  Meshes and stand-alone triangle objects (n_tris = 1).  Refused before any device write, with nothing changed:
+ * no scene (CGPT_ERR_NO_SCENE); a NULL array, an object out of range, a sphere or a plane, an object listed in light_indices (mesh-light
+ * sampling reads total_area, which a pose does not recompute), n_tris other than the uploaded count, n_targets 0 or above 256, any
+ * float that is not finite (CGPT_ERR_INVALID).
+ *
+ * cgpt_scene_morph_mesh: stores weights (n_targets, the installed count) and poses the object: each of a triangle's 18 floats is
+ * x = base; x = x + weights[k] * delta_k for k ascending, a target whose weight is +0 or -0 skipped; with no active target the triangle
+ * is the base triangle bit for bit, otherwise every corner's normal is renormalised (the base normal where the blend has no finite
+ * positive length).  Weights are used as given: negative and above 1 are allowed.  A pose is always computed from the base, never from
+ * the previous pose.  Afterwards the device scene is what cgpt_scene_refit_mesh(obj_index, <cgpth_morph_triangles of the targets and
+ * the weights>) would have left, bit for bit, except that total_area keeps its uploaded value.  Everything else follows
+ * cgpt_scene_skin_mesh: the caller resets the accumulator; guides are recomputed; transforms, smooth flags and materials are kept; every
+ * placement of an instanced group moves; every device of a multi-device context is posed; a HIP failure after the first write drops the
+ * scene.  The temporal history is dropped, CGPT_TEMPORAL_FOLLOW_POSES included (a morph is not followed).  Refused, with nothing
+ * changed: no scene (CGPT_ERR_NO_SCENE); an object out of range or without targets, n_targets other than the installed count, weights
+ * NULL or a weight that is not finite (CGPT_ERR_INVALID).
+ *
+ * WITH A SKIN (glTF order: morph, then skin): while an object has morph targets installed, the morphed base takes the place of the
+ * skin's bind pose (the skin's own bind array is not read).  After either cgpt_scene_morph_mesh or cgpt_scene_skin_mesh on such an
+ * object the scene is skin_triangles(morph_triangles(base, deltas, w_last), joints, skin_weights, M_last) of the two host mirrors --
+ * w_last the last weights given (zeros if none), M_last the matrices of the skin's last cgpt_scene_skin_mesh since it was installed;
+ * while the skin has not been posed the morph alone applies.  The order of the two calls does not matter; one kernel does both.  For
+ * such an object a temporal call with CGPT_TEMPORAL_FOLLOW_POSES knows no pose: its history is dropped.
+ *
+ * cgpt_scene_clear_morph_targets: frees the object's target buffers; the geometry stays where it is, and a skin goes back to its own
+ * bind pose at its next cgpt_scene_skin_mesh.  CGPT_OK without targets on the object.  cgpt_scene_upload and
+ * cgpt_scene_upload_instanced drop every object's targets.  cgpt_scene_refit_mesh on a morphed object works as before and keeps the
+ * targets; the next pose overwrites what it wrote. */
+int cgpt_scene_set_morph_targets(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* base_triangles, const cgpt_triangle* target_deltas,
+                                 uint32_t n_tris, uint32_t n_targets);
+int cgpt_scene_morph_mesh(cgpt_ctx* ctx, uint32_t obj_index, const float* weights, uint32_t n_targets);
+int cgpt_scene_clear_morph_targets(cgpt_ctx* ctx, uint32_t obj_index);
 
 /* UpdateScreenPlane (ref: Main.cpp:98-102,143-149): fov in degrees, plane at distance fov-in-radians (SURVEY A-13) */
 int cgpt_camera_from_view(const float pos[3], const float view_dir[3], float fov_deg, float aspect, cgpt_camera* out);
@@ -645,7 +691,9 @@ int cgpt_read_variance(cgpt_ctx* ctx, float* dst, size_t n_floats);
  * knobs process-wide; names are the variable names without the prefix, lower case: "pools", "batch", "max_batch",
  * "refill", "inner_repeat", ...; DESIGN.md 5.1 lists them).  Results never depend on a knob, only speed does.
  * "skin_joints_lds" (0 | 1, default 1) is cgpt_scene_skin_mesh's: whether its kernel stages the joint matrices in LDS or reads them
- * through the vector cache. */
+ * through the vector cache.  "morph_leaf_order" (0 | 1, default 1), read by cgpt_scene_set_morph_targets: whether
+ * the targets are stored in the order of the object's leaf slots as component planes, or as given; "morph_max_blocks" (1..1024,
+ * default 1024): the cap of the morph kernel's grid. */
 int cgpt_set_tuning(cgpt_ctx* ctx, const char* name, uint32_t value);
 /* Measures the vector-instruction issue rate of the device -- the roof bench.py prices the trace kernel against: every
  * SIMD of every CU runs `iters` x 64 independent instructions of one kind per wave at `waves_per_simd` resident waves.

@@ -115,6 +115,20 @@ int cgpth_skin_triangles(const cgpt_triangle* bind_triangles, const uint16_t* jo
  * object's count, and what cgpth_skin_triangles refuses. */
 int cgpth_scene_skin_mesh(cgpth_scene* scene, uint32_t obj_index, const cgpt_triangle* bind_triangles, const uint16_t* joints, const float* weights,
                           uint32_t n_tris, const float* joint_matrices, uint32_t n_joints);
+/* Morph targets (blend shapes), the host statement of cgpt_scene_morph_mesh's triangle pass (csrc/host/morph.h states the operations
+ * and their order; tests/morph_ref.py the same in numpy): every one of the 18 floats of out_triangles[t] is
+ * base_triangles[t]'s plus weights[k] * target_deltas[k * n_tris + t]'s, k ascending, a target whose weight is +0 or -0 skipped; with
+ * no active target the triangle is the base's bit for bit, otherwise the corners' normals are renormalised (the base normal where the
+ * blend has no finite positive length).  Refused with CGPT_ERR_INVALID and nothing written: a NULL array, n_targets 0 or above 256, a
+ * base float, delta float or weight that is not finite. */
+int cgpth_morph_triangles(const cgpt_triangle* base_triangles, const cgpt_triangle* target_deltas, uint32_t n_tris, uint32_t n_targets,
+                          const float* weights, cgpt_triangle* out_triangles);
+/* cgpth_morph_triangles followed by cgpth_scene_refit_mesh of the result: the host statement of cgpt_scene_set_morph_targets +
+ * cgpt_scene_morph_mesh (the host scene keeps no targets; unlike the device call total_area follows the pose).  Refused as the two
+ * device calls refuse, with the scene unchanged: a bad index, a sphere or a plane, a light, n_tris other than the object's count, and
+ * what cgpth_morph_triangles refuses.  A morphed and skinned object is cgpth_scene_skin_mesh with the morphed triangles as its bind pose. */
+int cgpth_scene_morph_mesh(cgpth_scene* scene, uint32_t obj_index, const cgpt_triangle* base_triangles, const cgpt_triangle* target_deltas,
+                           uint32_t n_tris, uint32_t n_targets, const float* weights);
 /* the host statement of cgpt_scene_update_primitive: a sphere's centre and radius, or a plane's normal and point */
 int cgpth_scene_update_primitive(cgpth_scene* scene, uint32_t obj_index, const cgpt_object* obj);
 /* reorders the objects: the new object k is the old object order[k] (a permutation of 0 .. n_objects - 1, else refused and nothing
