@@ -25,6 +25,7 @@ TRACE_COUNTERS, TRACE_REVERSED = 1, 2
 TEMPORAL_KEEP_VIEW_DEPENDENT = 1
 TEMPORAL_FOLLOW_TRANSFORMS = 4
 TEMPORAL_FOLLOW_POSES = 16
+TEMPORAL_FOLLOW_MORPHS = 32
 VARIANCE_TEMPORAL = 1
 SKIN_MAX_JOINTS = 1024      # cgpt_scene_set_skin
 MORPH_MAX_TARGETS = 256     # cgpt_scene_set_morph_targets

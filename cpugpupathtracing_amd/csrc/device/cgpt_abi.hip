@@ -74,7 +74,7 @@ void FreeScene(cgpt_ctx* ctx)
 {
     ctx->sb = SceneBuffers{};
     ctx->skins.clear(); ctx->pose_stamp.clear();                               // an upload drops every skin
-    ctx->morphs.clear();                                                       // ... and every object's morph targets
+    ctx->morphs.clear(); ctx->morph_stamp.clear();                             // ... and every object's morph targets
     ctx->h_objects.clear(); ctx->refit_objects.clear(); ctx->record_perm.clear(); ctx->mesh_group.clear();
     ctx->footprint = cgpt_scene_footprint{};
     ctx->h_roughness.clear(); ctx->h_transmission_roughness.clear(); ctx->h_materials.clear(); ctx->h_lights.clear();

@@ -53,6 +53,16 @@ struct MorphBuffers {
     uint32_t n_targets = 0;                       // 0: no targets
     uint32_t leaf_order = 1;                      // the knob "morph_leaf_order" as cgpt_scene_set_morph_targets read it
     std::vector<float> weights;                   // the last weights given: all zero after the set
+    // CGPT_TEMPORAL_FOLLOW_MORPHS (denoise.hip).  slot_of_tri: with leaf_order, the leaf slot of every triangle (the inverse
+    // of the map the planes were permuted by; 4 B a triangle, empty otherwise).  The pose the copy shows, when it was made through these
+    // targets: `weights` above and, if a skin took part, that skin's serial and matrices -- or pose_known = false ("no pose known": from
+    // the set until the first accepted pose, after a cgpt_scene_refit_mesh of the object or of a placement that shares its copy, after a
+    // pose of the copy through another placement's targets or skin).  serial names this installation among all of the context's
+    DevBuf<uint32_t> slot_of_tri;
+    bool pose_known = false;
+    uint64_t serial = 0;
+    uint64_t pose_skin_serial = 0;                // 0: the pose is the morph alone
+    std::vector<float> pose_matrices;             // 12 floats a joint of that skin's pose
 };
 // What the temporal history keeps of the poses it was stored under (StoreTemporalKey): per object the index of the object whose skin
 // posed its copy (-1: no pose known) and, at that index, the skin's serial and matrices.
@@ -60,6 +70,16 @@ struct PoseSnapshot {
     std::vector<int32_t> owner;
     std::vector<uint64_t> serial;
     std::vector<std::vector<float>> matrices;
+};
+// ... and of the morphed poses (CGPT_TEMPORAL_FOLLOW_MORPHS): per object the index of the object whose targets posed its copy (-1: none
+// known) and, at that index, the key of the pose: the installation, the weights, and the skin part (serial 0: none)
+struct MorphSnapshot {
+    struct Key {
+        uint64_t serial = 0, skin_serial = 0;
+        std::vector<float> weights, matrices;
+    };
+    std::vector<int32_t> owner;
+    std::vector<Key> key;
 };
 // One object's entry of the table the carry-back kernel reads (denoise.hip: pose_carry_back): 96 bytes, six float4
 struct PoseRecord {
@@ -73,6 +93,17 @@ struct PoseRecord {
     float xform[12];                              // the object's current object-to-world matrix (top_state.xform)
 };
 static_assert(sizeof(PoseRecord) == 96, "six float4 per object");
+// ... and of the second table morph_carry_back reads beside it (PoseRecord keeps its layout): 32 bytes, two float4.  A state-1 object
+// with kMorphRecordMorph takes its bind corner from `data` and the history's active table; with kMorphRecordSkin that corner goes
+// through PoseRecord's joints and weights, without it PoseRecord's skin pointers are null.
+enum : uint32_t { kMorphRecordMorph = 1u, kMorphRecordLeaf = 2u, kMorphRecordSkin = 4u };
+struct MorphRecord {
+    const float2* data;                           // MorphBuffers::data of the copy's owner
+    const uint32_t* slot_of_tri;                  // kMorphRecordLeaf: MorphBuffers::slot_of_tri
+    uint32_t active_base, n_active;               // the history's active table: entries active_base .. of dn.morph_active
+    uint32_t flags, pad;
+};
+static_assert(sizeof(MorphRecord) == 32, "two float4 per object");
 struct FrameBuffers {                             // the framebuffer band (EnsureFramebuffer)
     DevBuf<float4> accumulator;
     DevBuf<uint32_t> pixels;
@@ -90,10 +121,13 @@ struct DenoiseBuffers {                           // denoise.hip; each group is 
                                                   // demand and written only by a call in which an object moved
     // CGPT_TEMPORAL_FOLLOW_POSES
     DevBuf<uint32_t> guide_tri;                   // per pixel, beside guides: the first hit's triangle in the object's original order (0: a miss, a
-                                                  // sphere, a plane, a triangle object); written by guides_tri_kernel, which runs while a skin exists
+                                                  // sphere, a plane, a triangle object); written by guides_tri_kernel, which runs while a skin or morph targets exist
     DevBuf<float4> pose_table;                    // 6 float4 per object (PoseRecord), grown on demand, written by a call in which a pose changed
     DevBuf<float4> pose_matrices;                 // ... the history's joint matrices of every re-posed skin, 3 float4 per joint
     DevBuf<float4> previous_hits;                 // 2 float4 per pixel {x_p.xyz, bits(state) | n_p.xyz, 0}: pose_carry_back's output (cgpt_read_previous_hits)
+    // CGPT_TEMPORAL_FOLLOW_MORPHS: written by a call in which an object with targets is in state 1 (it runs morph_carry_back)
+    DevBuf<float4> morph_table;                   // 2 float4 per object (MorphRecord), beside pose_table
+    DevBuf<uint2> morph_active;                   // the history's active tables {target, bits(weight)} of every re-posed owner, one after the other
 };
 template <class... B> void ResetAll(B&... b) { (b.Reset(), ...); }
 // What the uploaded scene has that a kernel variant must carry: a roughness > 0, a transmission roughness > 0, a smooth-normal flag (they live in
@@ -156,6 +190,12 @@ struct cgpt_ctx {
     uint64_t pose_generation = 0;
     std::vector<uint64_t> pose_stamp;
     uint64_t skin_serial = 0;
+    // CGPT_TEMPORAL_FOLLOW_MORPHS: morph_generation counts the accepted cgpt_scene_morph_mesh calls (they bump scene_generation and
+    // shape_generation as well, not pose_generation); morph_stamp[i] is its value at the last of them that wrote object i's copy (as
+    // pose_stamp); morph_serial numbers the cgpt_scene_set_morph_targets installations
+    uint64_t morph_generation = 0;
+    std::vector<uint64_t> morph_stamp;
+    uint64_t morph_serial = 0;
 
     // framebuffer band
     cgpt::FrameBuffers fb;
@@ -190,7 +230,8 @@ struct cgpt_ctx {
     // the denoiser (denoise.hip): first-hit guides cached per camera, band and scene, and the filter's ping-pong buffers
     uint64_t scene_generation = 0;                // bumped by every scene upload and in-place edit
     uint64_t shape_generation = 0;                // ... by each of them but cgpt_scene_update_transforms: what a history that follows the transforms is kept across
-                                                  // (pose_generation, with the skins above: ... by cgpt_scene_skin_mesh alone)
+                                                  // (pose_generation, with the skins above: ... by cgpt_scene_skin_mesh alone;
+                                                  // morph_generation: ... by an accepted cgpt_scene_morph_mesh alone)
     cgpt::DenoiseBuffers dn;
     bool guides_valid = false;
     uint64_t guide_generation = 0;                // what the guides were computed for
@@ -218,6 +259,12 @@ struct cgpt_ctx {
     std::vector<float> pose_matrices;
     bool previous_hits_valid = false;
     uint32_t previous_hits_frame[4] = { 0, 0, 0, 0 };
+    // CGPT_TEMPORAL_FOLLOW_MORPHS: the morph generation and the morphed poses the history was stored for; the host copies of
+    // dn.morph_table and dn.morph_active, as pose_records
+    uint64_t temporal_morph_generation = 0;
+    cgpt::MorphSnapshot temporal_morphs;
+    std::vector<cgpt::MorphRecord> morph_records;
+    std::vector<uint2> morph_active;
     // the variance-guided filter (cgpt_denoise_variance_guided): dn.moments[temporal_slot] belongs to the temporal history when
     // moments_valid (a cgpt_denoise_temporal call updates the colour without them); dn.variance is the last successful call's map
     bool moments_valid = false;
@@ -296,6 +343,7 @@ int GroupForwarded(cgpt_ctx* ctx, int rc);     // a call forwarded to the first 
 void GroupFrameInfo(cgpt_ctx* ctx, uint32_t* width, uint32_t* height, uint32_t* num_accumulated, uint32_t* last_debug_mode);
 int GroupGatherUncounted(cgpt_ctx* ctx, const float4** frame);
 
+std::vector<uint2> ActiveTable(const float* weights, uint32_t n_targets);   // refit.hip: a pose's nonzero weights {target, bits(weight)}, ascending
 void DenoiseFree(cgpt_ctx* ctx);               // denoise.hip: the guide cache and filter buffers of a one-device context
 }  // namespace cgpt
 

@@ -23,6 +23,8 @@
 // With CGPT_TEMPORAL_FOLLOW_POSES (tests/pose_motion_ref.py) it outlives cgpt_scene_skin_mesh calls: pose_carry_back
 // computes, per pixel, where the hit's surface point was under the pose the history was stored with (cgpt_read_previous_hits), from
 // the first hit's triangle (guides_tri_kernel) and the history's joint matrices, and temporal_merge<.., POSE = true> reprojects from there.
+// With CGPT_TEMPORAL_FOLLOW_MORPHS (tests/morph_motion_ref.py) it outlives cgpt_scene_morph_mesh calls, and poses of an
+// object that has both targets and a skin: morph_carry_back computes the same records from the history's weights (and matrices).
 //
 // Variance-guided edge stopping (cgpt_denoise_variance_guided, cgpt_read_variance; tests/variance_ref.py states it in
 // numpy): the colour edge-stop of the passes becomes exp(-|l(c_q) - l(c_p)| / (sigma_l sqrt(gbar(p)) + 1e-6)), l the luminance and gbar
@@ -37,6 +39,7 @@
 #include "cpugpupt_abi.h"
 #include "ctx_internal.h"
 #include "device_scene.h"
+#include "morph.h"
 #include "rt_device.hpp"
 #include "shade_device.hpp"
 #include "skinning.h"
@@ -108,10 +111,10 @@ __global__ void __launch_bounds__(256) guides_kernel(const DevScene sc, const De
     CGPT_GUIDES_BODY(SMOOTH, XFORM, TREE, (void)0, (void)0);
 }
 
-// The guides of a context that holds a skin (cgpt_scene_set_skin), whichever features its scene has: guides_kernel<true, true, TREE> -- it
+// The guides of a context that holds a skin (cgpt_scene_set_skin) or morph targets (cgpt_scene_set_morph_targets), whichever features its scene has: guides_kernel<true, true, TREE> -- it
 // reads the smooth and transform flags per object, so a scene without either gets the bits of its own instantiation; TREE follows
 // cgpt_set_top_level as it does there -- which also writes the first hit's triangle, in its object's original order, beside the
-// guides: what CGPT_TEMPORAL_FOLLOW_POSES carries a hit back through.  0 for anything but a mesh: a stand-alone triangle object's
+// guides: what CGPT_TEMPORAL_FOLLOW_POSES and CGPT_TEMPORAL_FOLLOW_MORPHS carry a hit back through.  0 for anything but a mesh: a stand-alone triangle object's
 // Ray::tri is whatever an earlier mesh left there, and get_hit reads 0 for it.  A kernel of its own name: guides_kernel's
 // instantiations keep their signature.
 template <bool TREE>
@@ -566,6 +569,186 @@ __global__ void __launch_bounds__(256) pose_carry_back(const DevScene sc, const 
     a.out[2 * i + 1] = make_float4(onx, ony, onz, 0.0f);
 }
 
+// ---- following morphs (CGPT_TEMPORAL_FOLLOW_MORPHS; tests/morph_motion_ref.py states it in numpy) -------------------
+struct MorphCarryArgs {
+    PoseArgs pose;                 // as pose_carry_back's
+    const MorphRecord* morph_table;   // one record per object beside pose.table (ctx_internal.h), built by PreparePoses
+    const uint2* active;           // the history's active tables {target, bits(weight)} of every re-posed object with targets
+};
+
+// pose_carry_back for a call in which an object with morph targets was re-posed; it runs in that kernel's place (one pass and one record
+// buffer for a frame that has both kinds), and a kernel of its own name so that pose_carry_back keeps its instruction stream.  The six
+// steps are that kernel's and so is their arithmetic; step 3, the history pose's corners of triangle tau, depends on the object's
+// MorphRecord:
+//   kMorphRecordMorph  x[18] = the base record of tau; for each entry {k, w} of the history's active table in order MorphAccumulate(x, w,
+//                      target k's record); with a non-empty table MorphNormalise(base, x) -- morph.h's float arithmetic, contraction off,
+//                      the bits morph_triangles held in registers then.  LEAF: the record's nine float2 planes lie at
+//                      data[(9 s + p) n + slot_of_tri[tau]], otherwise at data[9 (s n + tau) + p].  Without the flag x is the skin's bind record;
+//   kMorphRecordSkin   each corner of x goes through SkinBlend / SkinCorner with the history's matrices (morph_triangles<SKIN>'s order:
+//                      the morph first); without the flag the corners are x.
+// The active table's length is per lane (a tile mostly shares one object).  Two targets are in flight at a time: their eighteen float2
+// loads are issued before the first accumulate; a lane whose table has an odd length loads its last entry twice and accumulates it once
+// (a zero weight must not be accumulated: -0 + 0 d is +0).  The morph runs first, into x; only then are the 36 matrix rows fetched.
+__global__ void __launch_bounds__(256) morph_carry_back(const DevScene sc, const MorphCarryArgs ma)
+{
+    const PoseArgs& a = ma.pose;
+    uint32_t px, row;
+    tile_pixel(a.width, px, row);
+    if (px >= a.width || row >= a.n_rows) return;
+    const size_t i = (size_t)row * a.width + px;
+    const float4 g0 = a.guides[3 * i], g1 = a.guides[3 * i + 1];
+    const uint32_t obj = __float_as_uint(g1.w);
+    const bool hit = obj != kNoHit;
+    const PoseRecord* const rec = a.table + (hit ? (size_t)obj : 0u);           // a miss reads record 0 and is masked
+    const MorphRecord* const mrec = ma.morph_table + (hit ? (size_t)obj : 0u);
+    uint32_t state = hit ? rec->state : 0u;
+    float ox = g0.x, oy = g0.y, oz = g0.z, onx = g1.x, ony = g1.y, onz = g1.z;
+    if (state == 1u) {
+        const uint32_t tri_base = rec->tri_base, smooth = rec->smooth, n_tris = rec->n_tris;
+        const uint32_t mflags = mrec->flags;
+        float A[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) A[k] = rec->xform[k];
+        const bool xf = has_xform(sc, obj);
+        const Xform inv = load_xform(sc, obj);
+        const uint32_t tau = a.tri[i];
+        const size_t t = tau < n_tris ? tau : n_tris - 1u;                      // a mesh's tri_idx was validated at upload
+        const float4* const orig = sc.tri_orig + 3u * ((size_t)tri_base + t);
+        const float4 c0 = orig[0], c1 = orig[1], c2 = orig[2];
+        // 3. the history pose's corners: the morph ...
+        float x[18];
+        if (mflags & kMorphRecordMorph) {
+            const float2* const data = mrec->data;
+            const uint2* const active = ma.active + mrec->active_base;
+            const uint32_t n_active = mrec->n_active;
+            const bool leaf = (mflags & kMorphRecordLeaf) != 0u;
+            const size_t n = n_tris;
+            const size_t first = leaf ? (size_t)mrec->slot_of_tri[t] : 9u * t, plane = leaf ? n : 1u;   // plane p of set s: data[9 s n + first + p plane]
+            float base[18];
+#pragma unroll
+            for (int p = 0; p < 9; ++p) {
+                const float2 v = data[first + (size_t)p * plane];
+                base[2 * p] = v.x; base[2 * p + 1] = v.y;
+            }
+#pragma unroll
+            for (int j = 0; j < 18; ++j) x[j] = base[j];
+            for (uint32_t e = 0; e < n_active; e += 2u) {
+                const bool two = e + 1u < n_active;
+                const uint2 k0 = active[e], k1 = active[two ? e + 1u : e];
+                const float2* const s0 = data + 9u * n * ((size_t)k0.x + 1u) + first;
+                const float2* const s1 = data + 9u * n * ((size_t)k1.x + 1u) + first;
+                float2 v0[9], v1[9];
+#pragma unroll
+                for (int p = 0; p < 9; ++p) { v0[p] = s0[(size_t)p * plane]; v1[p] = s1[(size_t)p * plane]; }
+                float d[18];
+#pragma unroll
+                for (int p = 0; p < 9; ++p) { d[2 * p] = v0[p].x; d[2 * p + 1] = v0[p].y; }
+                MorphAccumulate(x, __uint_as_float(k0.y), d);
+                if (two) {
+#pragma unroll
+                    for (int p = 0; p < 9; ++p) { d[2 * p] = v1[p].x; d[2 * p + 1] = v1[p].y; }
+                    MorphAccumulate(x, __uint_as_float(k1.y), d);
+                }
+            }
+            if (n_active != 0u) MorphNormalise(base, x);
+        } else {
+            const float2* const bind = rec->bind;
+#pragma unroll
+            for (int p = 0; p < 9; ++p) {
+                const float2 v = bind[9 * t + p];
+                x[2 * p] = v.x; x[2 * p + 1] = v.y;
+            }
+        }
+        // ... and the skin
+        float q[3][6];
+        if (mflags & kMorphRecordSkin) {
+            const uint2* const joints = rec->joints;
+            const float4* const weights = rec->weights;
+            const float4* const mat = a.matrices + 3u * (size_t)rec->matrix_base;
+            uint2 jw[3];
+            float4 w[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { jw[c] = joints[3 * t + c]; w[c] = weights[3 * t + c]; }
+            float4 rows[3][4][3];                                              // [corner][influence][row]
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const uint32_t j[4] = { jw[c].x & 0xFFFFu, jw[c].x >> 16, jw[c].y & 0xFFFFu, jw[c].y >> 16 };
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) rows[c][k][r] = mat[3u * j[k] + r];
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float m[12];
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    const float4 a0 = rows[c][0][r], a1 = rows[c][1][r], a2 = rows[c][2][r], a3 = rows[c][3][r];
+                    m[4 * r] = SkinBlend(w[c].x, a0.x, w[c].y, a1.x, w[c].z, a2.x, w[c].w, a3.x);
+                    m[4 * r + 1] = SkinBlend(w[c].x, a0.y, w[c].y, a1.y, w[c].z, a2.y, w[c].w, a3.y);
+                    m[4 * r + 2] = SkinBlend(w[c].x, a0.z, w[c].y, a1.z, w[c].z, a2.z, w[c].w, a3.z);
+                    m[4 * r + 3] = SkinBlend(w[c].x, a0.w, w[c].y, a1.w, w[c].z, a2.w, w[c].w, a3.w);
+                }
+                SkinCorner(m, x + 6 * c, q[c]);
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int k = 0; k < 6; ++k) q[c][k] = x[6 * c + k];
+        }
+        // 1. the hit in object space
+        const double gx = (double)g0.x, gy = (double)g0.y, gz = (double)g0.z;
+        const double Px = xf ? dot3((double)inv.r0.x, (double)inv.r0.y, (double)inv.r0.z, gx, gy, gz) + (double)inv.r0.w : gx;
+        const double Py = xf ? dot3((double)inv.r1.x, (double)inv.r1.y, (double)inv.r1.z, gx, gy, gz) + (double)inv.r1.w : gy;
+        const double Pz = xf ? dot3((double)inv.r2.x, (double)inv.r2.y, (double)inv.r2.z, gx, gy, gz) + (double)inv.r2.w : gz;
+        // 2. its coordinates on the current triangle
+        const double e1x = (double)c1.x - (double)c0.x, e1y = (double)c1.y - (double)c0.y, e1z = (double)c1.z - (double)c0.z;
+        const double e2x = (double)c2.x - (double)c0.x, e2y = (double)c2.y - (double)c0.y, e2z = (double)c2.z - (double)c0.z;
+        const double wx = Px - (double)c0.x, wy = Py - (double)c0.y, wz = Pz - (double)c0.z;
+        const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;   // g = e1 x e2
+        const double gg = dot3(nx, ny, nz, nx, ny, nz);
+        const double u = dot3(wy * e2z - wz * e2y, wz * e2x - wx * e2z, wx * e2y - wy * e2x, nx, ny, nz) / gg;
+        const double v = dot3(e1y * wz - e1z * wy, e1z * wx - e1x * wz, e1x * wy - e1y * wx, nx, ny, nz) / gg;
+        // 4. the same point of the history pose's triangle
+        const double xx = ((double)q[0][0] + u * ((double)q[1][0] - (double)q[0][0])) + v * ((double)q[2][0] - (double)q[0][0]);
+        const double xy = ((double)q[0][1] + u * ((double)q[1][1] - (double)q[0][1])) + v * ((double)q[2][1] - (double)q[0][1]);
+        const double xz = ((double)q[0][2] + u * ((double)q[1][2] - (double)q[0][2])) + v * ((double)q[2][2] - (double)q[0][2]);
+        // 5. and its normal
+        double mx = (double)q[0][3], my = (double)q[0][4], mz = (double)q[0][5];
+        if (smooth != 0u) {
+            const double w0 = 1.0 - u - v;
+            const double sx = (w0 * mx + u * (double)q[1][3]) + v * (double)q[2][3];
+            const double sy = (w0 * my + u * (double)q[1][4]) + v * (double)q[2][4];
+            const double sz = (w0 * mz + u * (double)q[1][5]) + v * (double)q[2][5];
+            const double l2 = dot3(sx, sy, sz, sx, sy, sz);
+            if (l2 > 1e-12) {
+                const double len = sqrt(l2);
+                mx = sx / len; my = sy / len; mz = sz / len;
+            }
+        }
+        // 6. back into the world
+        double wxp = xx, wyp = xy, wzp = xz, wnx = mx, wny = my, wnz = mz;
+        if (xf) {
+            wxp = dot3((double)A[0], (double)A[1], (double)A[2], xx, xy, xz) + (double)A[3];
+            wyp = dot3((double)A[4], (double)A[5], (double)A[6], xx, xy, xz) + (double)A[7];
+            wzp = dot3((double)A[8], (double)A[9], (double)A[10], xx, xy, xz) + (double)A[11];
+            const double tx = dot3((double)inv.r0.x, (double)inv.r1.x, (double)inv.r2.x, mx, my, mz);
+            const double ty = dot3((double)inv.r0.y, (double)inv.r1.y, (double)inv.r2.y, mx, my, mz);
+            const double tz = dot3((double)inv.r0.z, (double)inv.r1.z, (double)inv.r2.z, mx, my, mz);
+            const double len = sqrt(dot3(tx, ty, tz, tx, ty, tz));
+            wnx = tx / len; wny = ty / len; wnz = tz / len;
+        }
+        const float fx = (float)wxp, fy = (float)wyp, fz = (float)wzp, fnx = (float)wnx, fny = (float)wny, fnz = (float)wnz;
+        const bool ok = gg != 0.0 && isfinite(gg) && isfinite(fx) && isfinite(fy) && isfinite(fz) && isfinite(fnx) && isfinite(fny) && isfinite(fnz);
+        state = ok ? 1u : 2u;
+        ox = ok ? fx : ox; oy = ok ? fy : oy; oz = ok ? fz : oz;
+        onx = ok ? fnx : onx; ony = ok ? fny : ony; onz = ok ? fnz : onz;
+    }
+    a.out[2 * i] = make_float4(ox, oy, oz, __uint_as_float(state));
+    a.out[2 * i + 1] = make_float4(onx, ony, onz, 0.0f);
+}
+
 // ---- the variance-guided filter (cgpt_denoise_variance_guided; tests/variance_ref.py states it in numpy) ----------
 constexpr cgpt_variance_params kVarianceDefaults = { 4.0f, 4u, 0u };
 
@@ -758,12 +941,19 @@ bool HoldsSkin(const cgpt_ctx* d)
         if (sk.n_joints != 0u) return true;
     return false;
 }
+// ... or morph targets: likewise (CGPT_TEMPORAL_FOLLOW_MORPHS carries a hit back through the same index)
+bool HoldsMorphTargets(const cgpt_ctx* d)
+{
+    for (const MorphBuffers& mb : d->morphs)
+        if (mb.n_targets != 0u) return true;
+    return false;
+}
 
 int EnsureGuides(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera)
 {
     cgpt_ctx* d = f.dev;
     const uint32_t key[4] = { f.width, f.height, f.first_row, f.n_rows };
-    const bool with_tri = HoldsSkin(d);                                        // guides cached without the index are stale for a context that now needs it
+    const bool with_tri = HoldsSkin(d) || HoldsMorphTargets(d);                                      // guides cached without the index are stale for a context that now needs it
     if (d->guides_valid && d->guide_generation == d->scene_generation && memcmp(d->guide_frame, key, sizeof(key)) == 0 &&
         memcmp(&d->guide_camera, camera, sizeof(cgpt_camera)) == 0 && (d->guide_tri_valid || !with_tri))
         return CGPT_OK;
@@ -827,7 +1017,7 @@ int CheckTemporalParams(cgpt_ctx* ctx, const cgpt_temporal_params& t)
     if (!std::isfinite(t.max_history) || !(t.max_history >= 1.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "max_history must be finite and >= 1, got %g", t.max_history);
     if (!(t.normal_cos_min >= -1.0f && t.normal_cos_min <= 1.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "normal_cos_min %g outside [-1, 1]", t.normal_cos_min);
     if (!std::isfinite(t.plane_tolerance) || !(t.plane_tolerance > 0.0f)) return CtxFail(ctx, CGPT_ERR_INVALID, "plane_tolerance must be finite and > 0, got %g", t.plane_tolerance);
-    if (t.flags & ~(uint32_t)(CGPT_TEMPORAL_KEEP_VIEW_DEPENDENT | CGPT_TEMPORAL_FOLLOW_TRANSFORMS | CGPT_TEMPORAL_FOLLOW_POSES)) return CtxFail(ctx, CGPT_ERR_INVALID, "unknown temporal flags 0x%x", t.flags);
+    if (t.flags & ~(uint32_t)(CGPT_TEMPORAL_KEEP_VIEW_DEPENDENT | CGPT_TEMPORAL_FOLLOW_TRANSFORMS | CGPT_TEMPORAL_FOLLOW_POSES | CGPT_TEMPORAL_FOLLOW_MORPHS)) return CtxFail(ctx, CGPT_ERR_INVALID, "unknown temporal flags 0x%x", t.flags);
     return CGPT_OK;
 }
 
@@ -869,14 +1059,15 @@ int EnsureHistoryBuffers(cgpt_ctx* ctx, cgpt_ctx* d, size_t n)
 }
 
 // the history a call may use: stored by a call that succeeded, for this band, scene and demodulation.  The edits since it was stored
-// fall into three classes, counted by the three generations: cgpt_scene_update_transforms calls (scene - shape), kept with `follow`
-// (CGPT_TEMPORAL_FOLLOW_TRANSFORMS); cgpt_scene_skin_mesh calls (pose), kept with `follow_poses` (CGPT_TEMPORAL_FOLLOW_POSES); every
-// other edit (shape - pose), never kept.
-bool HistoryMatches(const cgpt_ctx* d, const uint32_t key[4], uint32_t demodulate, bool follow, bool follow_poses)
+// fall into four classes, counted by the four generations: cgpt_scene_update_transforms calls (scene - shape), kept with `follow`
+// (CGPT_TEMPORAL_FOLLOW_TRANSFORMS); cgpt_scene_skin_mesh calls (pose), kept with `follow_poses` (CGPT_TEMPORAL_FOLLOW_POSES); accepted
+// cgpt_scene_morph_mesh calls (morph), kept with `follow_morphs` (CGPT_TEMPORAL_FOLLOW_MORPHS); every other edit (shape - pose - morph),
+// never kept.  Each flag keeps its own class only.
+bool HistoryMatches(const cgpt_ctx* d, const uint32_t key[4], uint32_t demodulate, bool follow, bool follow_poses, bool follow_morphs)
 {
     const uint64_t edits = d->scene_generation - d->temporal_generation, shape_edits = d->shape_generation - d->temporal_shape_generation;
-    const uint64_t poses = d->pose_generation - d->temporal_pose_generation;
-    const bool scene = edits == 0 || (shape_edits == poses && (edits == shape_edits || follow) && (poses == 0 || follow_poses));
+    const uint64_t poses = d->pose_generation - d->temporal_pose_generation, morphs = d->morph_generation - d->temporal_morph_generation;
+    const bool scene = edits == 0 || (shape_edits == poses + morphs && (edits == shape_edits || follow) && (poses == 0 || follow_poses) && (morphs == 0 || follow_morphs));
     return d->temporal_valid && scene && d->temporal_demodulate == demodulate && memcmp(d->temporal_frame, key, sizeof(d->temporal_frame)) == 0;
 }
 
@@ -921,6 +1112,34 @@ void SnapshotPoses(const cgpt_ctx* d, PoseSnapshot& snap)
         if (k >= 0 && snap.serial[k] == 0) { snap.serial[k] = d->skins[k].serial; snap.matrices[k] = d->skins[k].pose; }
 }
 
+// which object's morph targets posed the copy object j shows, per object: -1 where none did or no pose is known.  A pose through one
+// object's targets makes every other placement's targets and skin unknown (refit.hip: PoseObject), so a copy has at most one, and none
+// beside a skin that PoseOwners names.
+void MorphOwners(const cgpt_ctx* d, std::vector<int32_t>& owner)
+{
+    owner.assign(d->h_objects.size(), -1);
+    for (size_t k = 0; k < d->morphs.size(); ++k) {
+        if (d->morphs[k].n_targets == 0u || !d->morphs[k].pose_known) continue;
+        for (size_t j = 0; j < owner.size(); ++j)
+            if (d->mesh_group[j] == d->mesh_group[k]) owner[j] = (int32_t)k;
+    }
+}
+
+// the morphed poses a call's history is stored for (empty for a context without targets)
+void SnapshotMorphs(const cgpt_ctx* d, MorphSnapshot& snap)
+{
+    snap = MorphSnapshot{};
+    if (!HoldsMorphTargets(d)) return;
+    MorphOwners(d, snap.owner);
+    snap.key.resize(snap.owner.size());
+    for (const int32_t k : snap.owner)
+        if (k >= 0 && snap.key[k].serial == 0) {
+            const MorphBuffers& mb = d->morphs[k];
+            snap.key[k].serial = mb.serial; snap.key[k].weights = mb.weights;
+            snap.key[k].skin_serial = mb.pose_skin_serial; snap.key[k].matrices = mb.pose_matrices;
+        }
+}
+
 // CGPT_TEMPORAL_FOLLOW_POSES with a usable history that cgpt_scene_skin_mesh calls have happened since: the record of every object
 // (ctx_internal.h: PoseRecord) in d->pose_records and, when an object is not in state 0, in dn.pose_table, with the history's matrices of
 // the re-posed skins in dn.pose_matrices (asynchronous copies on the stream: the host vectors live on).  An object whose copy no pose
@@ -928,25 +1147,80 @@ void SnapshotPoses(const cgpt_ctx* d, PoseSnapshot& snap)
 // snapshot's bytewise (A -> B -> A), 1 when they differ, 2 when either side knows no pose or the skin is another installation (or, which
 // a skin's presence rules out, the guides came without the triangle index: a state-1 record is the only reader of dn.guide_tri).
 // `posed`: an object is not in state 0, so the call runs pose_carry_back and reprojects through temporal_merge<.., POSE = true>.
-int PreparePoses(cgpt_ctx* ctx, cgpt_ctx* d, bool& posed)
+// With `follow_morphs` (CGPT_TEMPORAL_FOLLOW_MORPHS) the same for the accepted cgpt_scene_morph_mesh calls since the
+// history, and for the copies that were posed through an object's morph targets by either call: such a copy's key is the targets'
+// installation, the weights and -- if a skin took part -- that skin's installation and matrices (ctx_internal.h: MorphBuffers).  Equal
+// keys bytewise: state 0; the same installations and counts with other weights or matrices: state 1, with the object's MorphRecord in
+// d->morph_records / dn.morph_table and the history's active table -- ActiveTable of the history's weights -- in dn.morph_active;
+// anything else, and any such copy without the flag: state 2.  `morphed`: an object with targets is in state 1, so the call runs
+// morph_carry_back in pose_carry_back's place.
+int PreparePoses(cgpt_ctx* ctx, cgpt_ctx* d, bool follow_morphs, bool& posed, bool& morphed)
 {
-    posed = false;
+    posed = morphed = false;
     const bool have_tri = d->guide_tri_valid;                                  // EnsureGuides ran: the index buffer belongs to this call's guides
     const size_t n = d->h_objects.size();
     const PoseSnapshot& snap = d->temporal_poses;
-    std::vector<int32_t> owner;
+    const MorphSnapshot& msnap = d->temporal_morphs;
+    std::vector<int32_t> owner, morph_owner;
     size_t changed = 0;
     try {
         PoseOwners(d, owner);
+        MorphOwners(d, morph_owner);
         d->pose_records.assign(n, PoseRecord{});
+        d->morph_records.assign(n, MorphRecord{});
         d->pose_matrices.clear();
+        d->morph_active.clear();
         std::vector<int64_t> base(n, -1);                                      // where skin k's history matrices start, in joints
+        std::vector<int64_t> active_base(n, -1), active_count(n, 0);           // ... and morph owner k's history active table, in entries
         for (size_t j = 0; j < n; ++j) {
             PoseRecord& r = d->pose_records[j];
             if (d->top_state.xform.size() == 12 * n) memcpy(r.xform, d->top_state.xform.data() + 12 * j, sizeof(r.xform));
             r.tri_base = d->h_objects[j].tri_base; r.smooth = d->h_objects[j].smooth; r.n_tris = d->refit_objects[j].tri_count;
-            if (j >= d->pose_stamp.size() || d->pose_stamp[j] <= d->temporal_pose_generation) continue;   // not posed since: state 0
+            const bool posed_since = j < d->pose_stamp.size() && d->pose_stamp[j] > d->temporal_pose_generation;
+            const bool morphed_since = j < d->morph_stamp.size() && d->morph_stamp[j] > d->temporal_morph_generation;
+            if (!posed_since && !morphed_since) continue;                       // not posed since: state 0
             r.state = kMotionDrop;
+            const int32_t mk = follow_morphs ? morph_owner[j] : -1;
+            if (mk >= 0) {                                                     // the copy shows a pose made through mk's targets
+                const MorphBuffers& mb = d->morphs[mk];
+                const bool same = have_tri && j < msnap.owner.size() && msnap.owner[j] == mk && msnap.key[mk].serial == mb.serial &&
+                                  msnap.key[mk].weights.size() == mb.weights.size() && mb.weights.size() == mb.n_targets &&
+                                  msnap.key[mk].skin_serial == mb.pose_skin_serial && msnap.key[mk].matrices.size() == mb.pose_matrices.size();
+                const bool skinned = mb.pose_skin_serial != 0;                 // ... and through mk's skin, which must still be the installation that took part
+                const bool skin_there = !skinned || ((size_t)mk < d->skins.size() && d->skins[mk].serial == mb.pose_skin_serial &&
+                                                     12 * (size_t)d->skins[mk].n_joints == mb.pose_matrices.size());
+                if (same && skin_there) {
+                    const MorphSnapshot::Key& hk = msnap.key[mk];
+                    if (memcmp(hk.weights.data(), mb.weights.data(), mb.weights.size() * sizeof(float)) == 0 &&
+                        (!skinned || memcmp(hk.matrices.data(), mb.pose_matrices.data(), mb.pose_matrices.size() * sizeof(float)) == 0)) r.state = kMotionUnmoved;
+                    else {
+                        if (active_base[mk] < 0) {
+                            active_base[mk] = (int64_t)d->morph_active.size();
+                            const std::vector<uint2> table = ActiveTable(hk.weights.data(), mb.n_targets);
+                            d->morph_active.insert(d->morph_active.end(), table.begin(), table.end());
+                            active_count[mk] = (int64_t)table.size();
+                        }
+                        MorphRecord& m = d->morph_records[j];
+                        m.data = mb.data.p; m.slot_of_tri = mb.slot_of_tri.p;
+                        m.active_base = (uint32_t)active_base[mk]; m.n_active = (uint32_t)active_count[mk];
+                        m.flags = kMorphRecordMorph | (mb.leaf_order ? kMorphRecordLeaf : 0u) | (skinned ? kMorphRecordSkin : 0u);
+                        r.state = kMotionMoved;
+                        if (skinned) {
+                            const SkinBuffers& sk = d->skins[mk];
+                            if (base[mk] < 0) {                                // morph and skin owners are disjoint: base[] serves both
+                                base[mk] = (int64_t)(d->pose_matrices.size() / 12);
+                                d->pose_matrices.insert(d->pose_matrices.end(), hk.matrices.begin(), hk.matrices.end());
+                            }
+                            r.matrix_base = (uint32_t)base[mk];
+                            r.joints = reinterpret_cast<const uint2*>(sk.joints.p);
+                            r.weights = reinterpret_cast<const float4*>(sk.weights.p);
+                        }
+                        morphed = true;
+                    }
+                }
+                if (r.state != kMotionUnmoved) ++changed;
+                continue;
+            }
             const int32_t k = owner[j];
             if (have_tri && k >= 0 && j < snap.owner.size() && snap.owner[j] == k && snap.serial[k] == d->skins[k].serial && snap.matrices[k].size() == d->skins[k].pose.size()) {
                 const SkinBuffers& sk = d->skins[k];
@@ -961,18 +1235,27 @@ int PreparePoses(cgpt_ctx* ctx, cgpt_ctx* d, bool& posed)
                     r.bind = reinterpret_cast<const float2*>(sk.bind.p);
                     r.joints = reinterpret_cast<const uint2*>(sk.joints.p);
                     r.weights = reinterpret_cast<const float4*>(sk.weights.p);
+                    d->morph_records[j].flags = kMorphRecordSkin;              // read by morph_carry_back alone
                 }
             }
             if (r.state != kMotionUnmoved) ++changed;
         }
     } catch (const std::exception& e) { return CtxFail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
-    if (changed == 0) return CGPT_OK;
+    if (changed == 0) { morphed = false; return CGPT_OK; }
     static_assert(sizeof(PoseRecord) == 6 * sizeof(float4), "6 float4 per object");
     HIP_TRY(ctx, d->dn.pose_table.Grow(6 * n));                                // hipFree waits for the device
     HIP_TRY(ctx, hipMemcpyAsync(d->dn.pose_table.p, d->pose_records.data(), n * sizeof(PoseRecord), hipMemcpyHostToDevice, d->stream));
     if (!d->pose_matrices.empty()) {
         HIP_TRY(ctx, d->dn.pose_matrices.Grow(d->pose_matrices.size() / 4));
         HIP_TRY(ctx, hipMemcpyAsync(d->dn.pose_matrices.p, d->pose_matrices.data(), d->pose_matrices.size() * sizeof(float), hipMemcpyHostToDevice, d->stream));
+    }
+    if (morphed) {
+        static_assert(sizeof(MorphRecord) == 2 * sizeof(float4), "2 float4 per object");
+        HIP_TRY(ctx, d->dn.morph_table.Grow(2 * n));
+        HIP_TRY(ctx, hipMemcpyAsync(d->dn.morph_table.p, d->morph_records.data(), n * sizeof(MorphRecord), hipMemcpyHostToDevice, d->stream));
+        HIP_TRY(ctx, d->dn.morph_active.Grow(d->morph_active.size() + 1));       // never empty: a table of all-zero history weights has no entry
+        if (!d->morph_active.empty())
+            HIP_TRY(ctx, hipMemcpyAsync(d->dn.morph_active.p, d->morph_active.data(), d->morph_active.size() * sizeof(uint2), hipMemcpyHostToDevice, d->stream));
     }
     posed = true;
     return CGPT_OK;
@@ -1004,8 +1287,9 @@ void FillTemporalArgs(const Frame& f, const cgpt_camera* camera, const cgpt_temp
 }
 
 // what a successful temporal stage leaves: the history in the other slot, and what it was stored for (`xform`: the call's snapshot
-// of top_state.xform, swapped in; `poses`: its snapshot of the poses, likewise)
-void StoreTemporalKey(cgpt_ctx* d, const cgpt_camera* camera, const uint32_t key[4], uint32_t demodulate, std::vector<float>& xform, PoseSnapshot& poses)
+// of top_state.xform, swapped in; `poses`, `morphs`: its snapshots of the poses, likewise)
+void StoreTemporalKey(cgpt_ctx* d, const cgpt_camera* camera, const uint32_t key[4], uint32_t demodulate, std::vector<float>& xform, PoseSnapshot& poses,
+                      MorphSnapshot& morphs)
 {
     d->temporal_slot ^= 1u;
     d->temporal_demodulate = demodulate;
@@ -1014,6 +1298,8 @@ void StoreTemporalKey(cgpt_ctx* d, const cgpt_camera* camera, const uint32_t key
     d->temporal_xform.swap(xform);
     d->temporal_pose_generation = d->pose_generation;
     std::swap(d->temporal_poses, poses);
+    d->temporal_morph_generation = d->morph_generation;
+    std::swap(d->temporal_morphs, morphs);
     memcpy(&d->temporal_camera, camera, sizeof(cgpt_camera));
     memcpy(d->temporal_frame, key, sizeof(d->temporal_frame));
     d->temporal_valid = true;
@@ -1076,15 +1362,18 @@ int RunStages(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, Stages s
     const float inv_normal = (float)(1.0 / ((double)p.sigma_normal * p.sigma_normal));
     const float inv_position = (float)(1.0 / ((double)p.sigma_position * p.sigma_position));
     const bool follow = (t.flags & CGPT_TEMPORAL_FOLLOW_TRANSFORMS) != 0u, follow_poses = (t.flags & CGPT_TEMPORAL_FOLLOW_POSES) != 0u;
-    const bool have = st.temporal && HistoryMatches(d, key, demodulate, follow, follow_poses);
+    const bool follow_morphs = (t.flags & CGPT_TEMPORAL_FOLLOW_MORPHS) != 0u;
+    const bool have = st.temporal && HistoryMatches(d, key, demodulate, follow, follow_poses, follow_morphs);
     const bool have_moments = have && d->moments_valid;
     bool wrote_previous_hits = false;                                          // this call launched pose_carry_back
     std::vector<float> xform;                                                  // the matrices this call's history is stored for
     PoseSnapshot poses;                                                        // ... and the poses
+    MorphSnapshot morphs;                                                      // ... those made through morph targets
     if (st.temporal) {
         try {
             xform.resize(d->top_state.xform.size());
             SnapshotPoses(d, poses);
+            SnapshotMorphs(d, morphs);
         } catch (const std::exception& e) { return CtxFail(ctx, CGPT_ERR_INVALID, "out of host memory: %s", e.what()); }
         SnapshotTransforms(d->top_state.xform.data(), xform.size() / 12, xform.data());
     }
@@ -1105,8 +1394,11 @@ int RunStages(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, Stages s
     if (st.temporal) {
         bool moved = false;                                                    // an object moved since the history was stored, and the call follows it
         bool posed = false;                                                    // ... was re-posed
+        bool morphed = false;                                                  // ... through morph targets: morph_carry_back carries the frame's poses back
         if (have && follow && (rc = PrepareMotion(ctx, d, moved)) != CGPT_OK) return rc;
-        if (have && follow_poses && d->pose_generation != d->temporal_pose_generation && (rc = PreparePoses(ctx, d, posed)) != CGPT_OK) return rc;
+        const bool pose_edits = follow_poses && d->pose_generation != d->temporal_pose_generation;
+        const bool morph_edits = follow_morphs && d->morph_generation != d->temporal_morph_generation;
+        if (have && (pose_edits || morph_edits) && (rc = PreparePoses(ctx, d, follow_morphs, posed, morphed)) != CGPT_OK) return rc;
         TemporalArgs a{};
         FillTemporalArgs(f, camera, t, demodulate, have, moved || posed, a);
         moved = moved && a.mode == kReproject;                                 // a singular history camera: no history, the existing kernel
@@ -1118,7 +1410,12 @@ int RunStages(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, Stages s
             PoseArgs pa{};
             pa.guides = d->dn.guides.p; pa.tri = d->guide_tri_valid ? d->dn.guide_tri.p : nullptr; pa.table = reinterpret_cast<const PoseRecord*>(d->dn.pose_table.p);
             pa.matrices = d->dn.pose_matrices.p; pa.out = d->dn.previous_hits.p; pa.width = f.width; pa.n_rows = f.n_rows;
-            hipLaunchKernelGGL(pose_carry_back, dim3(tiles), dim3(256), 0, d->stream, d->scene, pa);
+            if (morphed) {
+                MorphCarryArgs ma{};
+                ma.pose = pa; ma.morph_table = reinterpret_cast<const MorphRecord*>(d->dn.morph_table.p); ma.active = d->dn.morph_active.p;
+                hipLaunchKernelGGL(morph_carry_back, dim3(tiles), dim3(256), 0, d->stream, d->scene, ma);
+            } else
+                hipLaunchKernelGGL(pose_carry_back, dim3(tiles), dim3(256), 0, d->stream, d->scene, pa);
             HIP_TRY(ctx, hipGetLastError());
             a.pose = d->dn.previous_hits.p;
         }
@@ -1165,7 +1462,7 @@ int RunStages(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, Stages s
     }
     if ((rc = ReadBack(ctx, d, n, out, dst_rgba, dst_pixels)) != CGPT_OK) return rc;
     if (st.temporal) {
-        StoreTemporalKey(d, camera, key, demodulate, xform, poses);
+        StoreTemporalKey(d, camera, key, demodulate, xform, poses, morphs);
         d->moments_valid = st.variance;
         if (wrote_previous_hits) {
             memcpy(d->previous_hits_frame, key, sizeof(key));
@@ -1317,7 +1614,7 @@ int cgpt_read_previous_hits(cgpt_ctx* ctx, float* dst, size_t n_floats)
     if (!ctx) return CGPT_ERR_INVALID;
     cgpt_ctx* const first = GroupFirstMemberOrNull(ctx);
     cgpt_ctx* const d = first ? first : ctx;
-    if (!d->previous_hits_valid) return CtxFail(ctx, CGPT_ERR_INVALID, "no previous hits: no temporal call with CGPT_TEMPORAL_FOLLOW_POSES has carried a pose back");
+    if (!d->previous_hits_valid) return CtxFail(ctx, CGPT_ERR_INVALID, "no previous hits: no temporal call with CGPT_TEMPORAL_FOLLOW_POSES or CGPT_TEMPORAL_FOLLOW_MORPHS has carried a pose back");
     const size_t n = (size_t)d->previous_hits_frame[0] * d->previous_hits_frame[3];
     if (!dst || n_floats != 8 * n) return CtxFail(ctx, CGPT_ERR_INVALID, "expected a buffer of %zu floats (8 per pixel)", 8 * n);
     return CopyToHost(ctx, d, dst, d->dn.previous_hits.p, n * sizeof(float4) * 2);

@@ -46,6 +46,16 @@ namespace cgpt {
 
 float HostTriangleArea(const cgpt_triangle& t);                               // bvh_build.hip
 
+// the active targets of a pose's weights, {target, bits(weight)} in ascending order: a zero weight of either sign is skipped (morph.h).
+// Declared in ctx_internal.h: denoise.hip compacts a history's weights by the same rule.
+std::vector<uint2> ActiveTable(const float* weights, uint32_t n_targets)
+{
+    std::vector<uint2> table;
+    for (uint32_t k = 0; k < n_targets; ++k)
+        if (weights[k] != 0.0f) { uint32_t w; memcpy(&w, &weights[k], 4); table.push_back(make_uint2(k, w)); }
+    return table;
+}
+
 namespace {
 
 constexpr uint32_t kRefitThreads = 256;
@@ -362,8 +372,10 @@ int RefitMesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles,
     HIP_TRY(ctx, hipMemcpyAsync(ctx->sb.refit_staging.p, triangles, sizeof(cgpt_triangle) * (size_t)n_tris, hipMemcpyHostToDevice, ctx->stream));
 
     // from here on the scene changes
-    for (const uint32_t j : members)                                           // the copy is no pose of any skin now (CGPT_TEMPORAL_FOLLOW_POSES: "no pose known")
+    for (const uint32_t j : members) {                                         // the copy is no pose of any skin or targets now (CGPT_TEMPORAL_FOLLOW_POSES, _MORPHS: "no pose known")
         if (j < ctx->skins.size()) ctx->skins[j].pose_known = false;
+        if (j < ctx->morphs.size()) ctx->morphs[j].pose_known = false;
+    }
     const uint32_t tri_base = d.tri_base;
     hipLaunchKernelGGL(refit_triangles, dim3((n_tris + kRefitThreads - 1) / kRefitThreads), dim3(kRefitThreads), 0, ctx->stream,
                        reinterpret_cast<const float*>(ctx->sb.refit_staging.p), ctx->sb.tri_leaf.p, ctx->sb.tri_orig.p, ctx->sb.tri_normal.p, ro.leaf_base, tri_base, n_tris, ctx->scene.n_tris_total);
@@ -418,15 +430,6 @@ int SetSkin(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* bind, const 
 
 bool HasMorphTargets(const cgpt_ctx* ctx, uint32_t obj_index) { return obj_index < ctx->morphs.size() && ctx->morphs[obj_index].n_targets != 0u; }
 
-// the active targets of a pose's weights, {target, bits(weight)} in ascending order: a zero weight of either sign is skipped (morph.h)
-std::vector<uint2> ActiveTable(const float* weights, uint32_t n_targets)
-{
-    std::vector<uint2> table;
-    for (uint32_t k = 0; k < n_targets; ++k)
-        if (weights[k] != 0.0f) { uint32_t w; memcpy(&w, &weights[k], 4); table.push_back(make_uint2(k, w)); }
-    return table;
-}
-
 // Every pose writes both small inputs its kernel reads -- the active table and, with a skin, the joint matrices -- from the host values
 // it poses with, never trusting what an earlier call left on the device: a call that failed between its upload and its first scene write
 // keeps the scene and its committed weights / matrices, and the next pose through either call must use those.
@@ -455,10 +458,11 @@ int PoseObject(cgpt_ctx* ctx, uint32_t obj_index, bool skinned, uint32_t n_activ
     HIP_TRY(ctx, hipMemsetAsync(ctx->sb.skin_scratch.p, 0, sizeof(uint32_t) * kSkinScratchWords, ctx->stream));
 
     // from here on the scene changes
-    for (uint32_t j = 0; j < ctx->mesh_group.size(); ++j)                      // every placement of the copy: posed now, and by no other skin
+    for (uint32_t j = 0; j < ctx->mesh_group.size(); ++j)                      // every placement of the copy: posed now, and by no other skin or targets
         if (ctx->mesh_group[j] == ctx->mesh_group[obj_index]) {
             ctx->pose_stamp[j] = ctx->pose_generation;
             if (j < ctx->skins.size()) ctx->skins[j].pose_known = false;
+            if (j < ctx->morphs.size()) ctx->morphs[j].pose_known = false;
         }
     const SkinBuffers none;
     const SkinBuffers& sk = skinned ? ctx->skins[obj_index] : none;
@@ -547,6 +551,12 @@ int SkinMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uin
     if (rc != CGPT_OK) return rc;
     sk.pose.swap(pose);
     sk.pose_known = !morphed;                                                  // the matrices alone do not tell a morphed pose: "no pose known"
+    if (morphed) {                                                             // ... the targets' state does (CGPT_TEMPORAL_FOLLOW_MORPHS): the last weights through this skin
+        MorphBuffers& mb = ctx->morphs[obj_index];
+        mb.pose_matrices = sk.pose;
+        mb.pose_skin_serial = sk.serial;
+        mb.pose_known = true;
+    }
     return CGPT_OK;
 }
 
@@ -595,6 +605,10 @@ int SetMorphTargets(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* base
             memcpy(&slot_tri[i], &leaf_tail[i].z, 4);
             if (slot_tri[i] >= n_tris) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u: leaf slot %zu names triangle %u", obj_index, i, slot_tri[i]);
         }
+        std::vector<uint32_t> slot_of_tri(n, 0u);                              // the inverse: where CGPT_TEMPORAL_FOLLOW_MORPHS finds a triangle's planes
+        for (size_t i = 0; i < n; ++i) slot_of_tri[slot_tri[i]] = (uint32_t)i;
+        HIP_TRY(ctx, mb.slot_of_tri.Alloc(n));
+        HIP_TRY(ctx, hipMemcpy(mb.slot_of_tri.p, slot_of_tri.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
         std::vector<float2> planes(per_set);
         for (uint32_t s = 0; s <= n_targets; ++s) {
             const float* src = reinterpret_cast<const float*>(s == 0 ? base : deltas + (size_t)(s - 1) * n);
@@ -609,6 +623,7 @@ int SetMorphTargets(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* base
         HIP_TRY(ctx, hipMemcpy(mb.data.p + per_set, deltas, sizeof(cgpt_triangle) * n * n_targets, hipMemcpyHostToDevice));
     }
     mb.n_targets = n_targets;
+    mb.serial = ++ctx->morph_serial;                                           // no pose known yet: the scene holds the uploaded triangles, which need not be the base
     if (ctx->morphs.size() != ctx->h_objects.size()) ctx->morphs.resize(ctx->h_objects.size());
     ctx->morphs[obj_index] = std::move(mb);
     return CGPT_OK;
@@ -628,7 +643,11 @@ int MorphMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* weights, uint32_t 
     const std::vector<uint2> table = ActiveTable(weights, n_targets);
     // a skin that has been posed since it was installed takes part with the matrices of its last pose (sk.pose, written again: see UploadActiveTable)
     const bool skinned = obj_index < ctx->skins.size() && ctx->skins[obj_index].n_joints != 0u && !ctx->skins[obj_index].pose.empty();
-    ctx->scene_generation++; ctx->shape_generation++;                          // accepted -- as a refit: guides and temporal history are stale, CGPT_TEMPORAL_FOLLOW_POSES included
+    if (ctx->morph_stamp.size() != ctx->h_objects.size()) ctx->morph_stamp.resize(ctx->h_objects.size(), 0);
+    std::vector<float> pose_matrices;                                          // the skin part of this pose's key
+    if (skinned) pose_matrices = ctx->skins[obj_index].pose;
+    ctx->scene_generation++; ctx->shape_generation++; ctx->morph_generation++;   // accepted -- as a refit: guides and temporal history are stale, CGPT_TEMPORAL_FOLLOW_POSES
+                                                                               // included (a call with CGPT_TEMPORAL_FOLLOW_MORPHS keeps the history: morph_generation tells a morph from a refit)
     rc = PoseObject(ctx, obj_index, skinned, (uint32_t)table.size(), [&] {
         const hipError_t e = UploadActiveTable(ctx, mb, table);
         if (e != hipSuccess || !skinned) return e;
@@ -637,6 +656,11 @@ int MorphMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* weights, uint32_t 
     });
     if (rc != CGPT_OK) return rc;
     mb.weights.swap(kept);
+    for (uint32_t j = 0; j < ctx->mesh_group.size(); ++j)                      // every placement of the copy: morphed now
+        if (ctx->mesh_group[j] == ctx->mesh_group[obj_index]) ctx->morph_stamp[j] = ctx->morph_generation;
+    mb.pose_matrices.swap(pose_matrices);
+    mb.pose_skin_serial = skinned ? ctx->skins[obj_index].serial : 0;
+    mb.pose_known = true;
     return CGPT_OK;
 }
 

@@ -341,11 +341,30 @@ class Renderer:
         samples once.  Every scene edit drops the history; follow_transforms=True (CGPT_TEMPORAL_FOLLOW_TRANSFORMS) keeps it across
         update_transforms() calls and carries the hits on the moved objects back to where they were; follow_poses=True
         (CGPT_TEMPORAL_FOLLOW_POSES) keeps it across skin_mesh() calls and carries the hits on the re-posed objects back to where the
-        same surface points were under the history's pose (previous_hits() reads those records)."""
+        same surface points were under the history's pose (previous_hits() reads those records).  denoise_temporal_following() also
+        follows morph_mesh() calls."""
+        return self._denoise_temporal(iterations, sigma_color, sigma_normal, sigma_position, demodulate, max_history, normal_cos_min, plane_tolerance,
+                                      keep_view_dependent, camera, (N.TEMPORAL_FOLLOW_TRANSFORMS if follow_transforms else 0) |
+                                      (N.TEMPORAL_FOLLOW_POSES if follow_poses else 0))
+
+    def denoise_temporal_following(self, iterations: int = 5, sigma_color: float = 4.0, sigma_normal: float = 0.2, sigma_position: float = 0.3,
+                                   demodulate: bool = True, max_history: float = 64.0, normal_cos_min: float = 0.9, plane_tolerance: float = 0.01,
+                                   keep_view_dependent: bool = False, camera: Optional[N.Camera] = None,
+                                   transforms: bool = False, poses: bool = False, morphs: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """denoise_temporal() with one keyword per kind of edit the history is kept across: transforms (update_transforms();
+        CGPT_TEMPORAL_FOLLOW_TRANSFORMS), poses (skin_mesh(); CGPT_TEMPORAL_FOLLOW_POSES) and morphs (morph_mesh();
+        CGPT_TEMPORAL_FOLLOW_MORPHS).  Each keeps its own kind only: a character with a skeleton and blend shapes needs
+        poses=True and morphs=True.  The hits on an object that was re-posed through its morph targets are carried back to where the same
+        surface points were under the history's weights (and joint matrices); previous_hits() reads those records too."""
+        return self._denoise_temporal(iterations, sigma_color, sigma_normal, sigma_position, demodulate, max_history, normal_cos_min, plane_tolerance,
+                                      keep_view_dependent, camera, (N.TEMPORAL_FOLLOW_TRANSFORMS if transforms else 0) |
+                                      (N.TEMPORAL_FOLLOW_POSES if poses else 0) | (N.TEMPORAL_FOLLOW_MORPHS if morphs else 0))
+
+    def _denoise_temporal(self, iterations, sigma_color, sigma_normal, sigma_position, demodulate, max_history, normal_cos_min, plane_tolerance,
+                          keep_view_dependent, camera, follow_flags) -> Tuple[np.ndarray, np.ndarray]:
         cam = camera if camera is not None else self.scene.camera()
         p = N.DenoiseParams(iterations, N.DENOISE_DEMODULATE_ALBEDO if demodulate else 0, sigma_color, sigma_normal, sigma_position)
-        t = N.TemporalParams(max_history, normal_cos_min, plane_tolerance, (N.TEMPORAL_KEEP_VIEW_DEPENDENT if keep_view_dependent else 0) |
-                             (N.TEMPORAL_FOLLOW_TRANSFORMS if follow_transforms else 0) | (N.TEMPORAL_FOLLOW_POSES if follow_poses else 0))
+        t = N.TemporalParams(max_history, normal_cos_min, plane_tolerance, (N.TEMPORAL_KEEP_VIEW_DEPENDENT if keep_view_dependent else 0) | follow_flags)
         rgba = np.empty((self.n_rows, self.width, 4), np.float32)
         px = np.empty((self.n_rows, self.width), np.uint32)
         self._check(self.L.cgpt_denoise_temporal(self._ctx, C.byref(cam), C.byref(p), C.byref(t), rgba.ctypes.data_as(C.POINTER(C.c_float)),
@@ -364,8 +383,8 @@ class Renderer:
         return out
 
     def previous_hits(self) -> np.ndarray:
-        """The carry-back records of the last denoise_temporal(follow_poses=True) in which an object was re-posed
-        (cgpt_read_previous_hits): (rows, width, 8) float32 {x_p.xyz, bits(state), n_p.xyz, 0} -- where each pixel's first hit was under
+        """The carry-back records of the last denoise_temporal(follow_poses=True) or denoise_temporal_following(poses / morphs=True) in
+        which an object was re-posed (cgpt_read_previous_hits): (rows, width, 8) float32 {x_p.xyz, bits(state), n_p.xyz, 0} -- where each pixel's first hit was under
         the history's pose; state 0 (not re-posed: the pixel's own x, n), 1 (re-posed) or 2 (no history)."""
         out = np.empty((self.n_rows, self.width, 8), np.float32)
         self._check(self.L.cgpt_read_previous_hits(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))

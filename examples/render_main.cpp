@@ -51,7 +51,9 @@
 // --bulge W: a morphing mesh -- the mesh (object 0) gets one procedural morph target on the device (cgpt_scene_set_morph_targets: every corner
 // pushed out along its normal by its height between the mesh's lowest and highest point) and is posed once per frame with weight W * frame / 7
 // (cgpt_scene_morph_mesh); frames as for --bend, named bulge_NN_*.ppm.  With --bend DEG as well the mesh has both and one
-// kernel morphs and skins it (the frames keep the bend_ names); a morph is not followed by the temporal stage, which starts a new history.
+// kernel morphs and skins it (the frames keep the bend_ names).  With --bulge the temporal call sets CGPT_TEMPORAL_FOLLOW_POSES |
+// CGPT_TEMPORAL_FOLLOW_MORPHS: the mesh's pixels are carried back to where the same surface points were under the weight (and the bend) of the
+// frame before, and everyone keeps their history.
 // move_at > 0 scripts the input half of Update(dt) (ref: Main.cpp:277-297, Camera::Update :104-131): after that many samples the
 // camera is translated by (right, up, forward) as the A/D, Space/Shift, W/S keys would, the view changes, and the accumulator
 // is reset (ref: ResetAccumulator, Main.cpp:238-243) before the remaining samples are rendered from the new position.
@@ -274,7 +276,7 @@ int main(int argc, char** argv)
 
         std::vector<uint32_t> px((size_t)W * H);                         // the mesh bends every frame: SkinMesh, ResetAccumulator, Render, present
         const cgpt_camera cam = scene.camera.Abi();
-        const cgpt_temporal_params tp = { 64.0f, 0.9f, 0.01f, CGPT_TEMPORAL_FOLLOW_POSES };
+        const cgpt_temporal_params tp = { 64.0f, 0.9f, 0.01f, CGPT_TEMPORAL_FOLLOW_POSES | (bulge ? (uint32_t)CGPT_TEMPORAL_FOLLOW_MORPHS : 0u) };   // each flag keeps its own kind of edit
         for (uint32_t frame = 0; frame < 8; ++frame) {                   // the pose of this frame: 48 bytes a joint go to the device
             const double angle = (double)bend_deg * (double)frame * 3.14159265358979 / 180.0, c = std::cos(angle), sn = std::sin(angle);
             const float py = bend_pivot[1], pz = bend_pivot[2];

@@ -41,7 +41,8 @@ extern "C" {
                                  symbols only (cgpt_scene_set_skin, cgpt_scene_skin_mesh, cgpt_scene_clear_skin); following poses in the
                                  temporal stage is a new enum value (CGPT_TEMPORAL_FOLLOW_POSES) and one new symbol
                                  (cgpt_read_previous_hits) only; morph targets added new symbols only
-                                 (cgpt_scene_set_morph_targets, cgpt_scene_morph_mesh, cgpt_scene_clear_morph_targets) */
+                                 (cgpt_scene_set_morph_targets, cgpt_scene_morph_mesh, cgpt_scene_clear_morph_targets); following
+                                 morphs in the temporal stage is a new enum value only (CGPT_TEMPORAL_FOLLOW_MORPHS) */
 
 enum cgpt_status {
     CGPT_OK = 0,
@@ -386,7 +387,8 @@ int cgpt_scene_clear_skin(cgpt_ctx* ctx, uint32_t obj_index);
  * the weights>) would have left, bit for bit, except that total_area keeps its uploaded value.  Everything else follows
  * cgpt_scene_skin_mesh: the caller resets the accumulator; guides are recomputed; transforms, smooth flags and materials are kept; every
  * placement of an instanced group moves; every device of a multi-device context is posed; a HIP failure after the first write drops the
- * scene.  The temporal history is dropped, CGPT_TEMPORAL_FOLLOW_POSES included (a morph is not followed).  Refused, with nothing
+ * scene.  The temporal history is dropped, CGPT_TEMPORAL_FOLLOW_POSES included, unless the next temporal call sets
+ * CGPT_TEMPORAL_FOLLOW_MORPHS (below: it carries the hits on the morphed objects back and keeps the history).  Refused, with nothing
  * changed: no scene (CGPT_ERR_NO_SCENE); an object out of range or without targets, n_targets other than the installed count, weights
  * NULL or a weight that is not finite (CGPT_ERR_INVALID).
  *
@@ -395,7 +397,8 @@ int cgpt_scene_clear_skin(cgpt_ctx* ctx, uint32_t obj_index);
  * object the scene is skin_triangles(morph_triangles(base, deltas, w_last), joints, skin_weights, M_last) of the two host mirrors --
  * w_last the last weights given (zeros if none), M_last the matrices of the skin's last cgpt_scene_skin_mesh since it was installed;
  * while the skin has not been posed the morph alone applies.  The order of the two calls does not matter; one kernel does both.  For
- * such an object a temporal call with CGPT_TEMPORAL_FOLLOW_POSES knows no pose: its history is dropped.
+ * such an object a temporal call with CGPT_TEMPORAL_FOLLOW_POSES alone knows no pose: its history is dropped; with
+ * CGPT_TEMPORAL_FOLLOW_MORPHS as well its pose is known by the weights and the matrices together.
  *
  * cgpt_scene_clear_morph_targets: frees the object's target buffers; the geometry stays where it is, and a skin goes back to its own
  * bind pose at its next cgpt_scene_skin_mesh.  CGPT_OK without targets on the object.  cgpt_scene_upload and
@@ -616,6 +619,22 @@ int cgpt_denoise(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_pa
  * The reprojection then runs on x_p, n_p, the unchanged t and object index; with both flags an object that was re-posed and moved goes
  * through its pose and then through D, two roundings to float.  A call in which no object was re-posed is the call without the flag bit for
  * bit; one in which an object was reprojects (and applies the view-dependent rule) even when the camera bytes equal the history's.
+ * Morph targets (CGPT_TEMPORAL_FOLLOW_MORPHS): with this flag a history stored before one or more accepted
+ * cgpt_scene_morph_mesh calls stays usable as long as nothing but morphs changed the scene (and poses or transforms, when their flags are
+ * set as well: each flag keeps the history across its own kind of edit only, so a character with a skeleton and blend shapes needs
+ * CGPT_TEMPORAL_FOLLOW_POSES | CGPT_TEMPORAL_FOLLOW_MORPHS).  For an object with morph targets the context remembers the pose its copy
+ * shows as the targets' installation, the weights of the last accepted pose and -- if a skin took part in it -- that skin's installation
+ * and matrices; or that no pose is known (from cgpt_scene_set_morph_targets until the first accepted pose through either call, after a
+ * cgpt_scene_refit_mesh of the object or of a placement sharing its copy, after a pose of the copy through another placement).  The
+ * history remembers the same.  An object whose copy was not posed since the history, or whose key is bytewise equal (A -> B -> A), is
+ * treated as without the flag; the same installations and counts with other weights or matrices: the hit is carried back as above,
+ * with step 3 = the base triangle morphed by the history's weights (morph.h's float arithmetic: MorphAccumulate over its nonzero
+ * weights in ascending order, then MorphNormalise) and then, if the history's pose had a skin part, skinned by the history's matrices
+ * -- the bits that pose wrote; anything else (no pose known on either side, targets or skin installed anew, a skin part that came or
+ * went, targets cleared): no history on that object's pixels.  Such an object reaches the first two states only in a call with this
+ * flag; objects without targets follow the rules above.  Every placement of an instanced copy takes the state of the copy.  Both
+ * layouts of the knob "morph_leaf_order" are followed.  Limits, beyond those below: recomputing the history's pose costs 72 bytes of
+ * gathers per history-active target and re-posed pixel; a cgpt_scene_refit_mesh is not followed; morphed lights do not exist.
  * cgpt_read_previous_hits returns the records of the last successful call that carried a pose back, 8 floats per pixel of its band:
  * {x_p.xyz, bits(state), n_p.xyz, 0}, state 0 (a miss, an object that was not re-posed: the pixel's own x, n), 1 (re-posed) or 2 (no
  * history: its own x, n) -- with the guides, what a caller needs for motion vectors.  Limits: the light carried by the history lags, as
@@ -628,7 +647,7 @@ int cgpt_denoise(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_pa
  * does not depend on temporal calls.  Refusals (before any device work; nothing changes, the history included): every refusal of
  * cgpt_denoise; max_history not finite or < 1; normal_cos_min outside [-1, 1] or NaN; plane_tolerance not finite or <= 0; unknown
  * flag bits; cgpt_read_temporal_history without a history or with a wrong size -- all CGPT_ERR_INVALID. */
-enum cgpt_temporal_flags { CGPT_TEMPORAL_KEEP_VIEW_DEPENDENT = 1u, CGPT_TEMPORAL_FOLLOW_TRANSFORMS = 4u, CGPT_TEMPORAL_FOLLOW_POSES = 16u };   /* 2u and 8u are no flags: they stay refused as unknown bits, as before */
+enum cgpt_temporal_flags { CGPT_TEMPORAL_KEEP_VIEW_DEPENDENT = 1u, CGPT_TEMPORAL_FOLLOW_TRANSFORMS = 4u, CGPT_TEMPORAL_FOLLOW_POSES = 16u, CGPT_TEMPORAL_FOLLOW_MORPHS = 32u };   /* 2u, 8u and everything above 32u are no flags: they stay refused as unknown bits, as before */
 typedef struct cgpt_temporal_params {
     float    max_history;      /* cap on a pixel's history length, in samples; finite, >= 1 */
     float    normal_cos_min;   /* a tap is valid only if n_prev . n_cur >= this; in [-1, 1] */
@@ -642,7 +661,8 @@ int cgpt_temporal_reset(cgpt_ctx* ctx);
 /* 4 floats per pixel of the band the history was stored for: the merged colour c (the filter's input domain: demodulated when the call
  * was) and the history length H' */
 int cgpt_read_temporal_history(cgpt_ctx* ctx, float* dst, size_t n_floats);
-/* 8 floats per pixel of the band of the last successful temporal call with CGPT_TEMPORAL_FOLLOW_POSES in which an object was re-posed:
+/* 8 floats per pixel of the band of the last successful temporal call with CGPT_TEMPORAL_FOLLOW_POSES or CGPT_TEMPORAL_FOLLOW_MORPHS in
+ * which an object was re-posed:
  * {x_p.xyz, bits(state), n_p.xyz, 0} (above).  CGPT_ERR_INVALID when no such call has happened, or for a wrong size. */
 int cgpt_read_previous_hits(cgpt_ctx* ctx, float* dst, size_t n_floats);
 
