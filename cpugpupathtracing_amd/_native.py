@@ -146,6 +146,18 @@ class SceneLayoutView(C.Structure):
                 ("obj_xform", _fp), ("n_obj_xform", C.c_size_t)]
 
 
+class PosePlanView(C.Structure):
+    """cgpth_pose_plan_view: rows of 32-bit words -- entries 16, launches 5, segments 4, levels 4 a row"""
+    _fields_ = [("entries", _up), ("n_entries", C.c_size_t), ("launches", _up), ("n_launches", C.c_size_t),
+                ("segments", _up), ("n_segments", C.c_size_t), ("levels", _up), ("n_levels", C.c_size_t),
+                ("n_matrix_joints", C.c_uint32), ("n_active", C.c_uint32)]
+
+
+class Pose(C.Structure):
+    """cgpt_pose: one entry of cgpt_scene_pose_objects"""
+    _fields_ = [("obj_index", C.c_uint32), ("n_joints", C.c_uint32), ("joint_matrices", _fp), ("n_targets", C.c_uint32), ("weights", _fp)]
+
+
 class SceneFootprint(C.Structure):
     """cgpt_scene_footprint"""
     _fields_ = [("device_bytes", C.c_uint64), ("n_objects", C.c_uint32), ("n_mesh_objects", C.c_uint32), ("n_mesh_copies", C.c_uint32),
@@ -184,6 +196,7 @@ PROTOTYPES = {
     "cgpt_scene_set_morph_targets": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), C.POINTER(Triangle), C.c_uint32, C.c_uint32]),
     "cgpt_scene_morph_mesh": (C.c_int, [_vp, C.c_uint32, _fp, C.c_uint32]),
     "cgpt_scene_clear_morph_targets": (C.c_int, [_vp, C.c_uint32]),
+    "cgpt_scene_pose_objects": (C.c_int, [_vp, C.POINTER(Pose), C.c_uint32]),
     "cgpt_camera_from_view": (C.c_int, [_fp, _fp, C.c_float, C.c_float, C.POINTER(Camera)]),
     "cgpt_render": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(Settings), C.POINTER(RenderParams)]),
     "cgpt_reset_accumulator": (C.c_int, [_vp]),
@@ -273,7 +286,8 @@ PROTOTYPES = {
     "cgpth_scene_layout": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(SceneLayoutView)]),
     "cgpth_scene_layout_instanced": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(SceneLayoutView)]),
     "cgpth_scene_layout_transformed": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(C.c_float), C.c_uint32, C.POINTER(SceneLayoutView)]),
-    "cgpth_scene_permute_objects": (C.c_int, [_vp, _up, C.c_uint32]),
+    "cgpth_pose_batch_plan": (C.c_int, [C.POINTER(SceneDesc), C.c_int, _up, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PosePlanView)]),
+    "cgpth_scene_permute_objects":(C.c_int, [_vp, _up, C.c_uint32]),
     "cgpth_top_level": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(TopLevelView)]),
     "cgpth_top_level_transforms": (C.c_int, [C.POINTER(C.c_float), C.c_uint32, C.POINTER(TopLevelView)]),
     "cgpth_top_level_refit": (C.c_int, [C.c_uint32, C.POINTER(Triangle), C.c_uint32, C.POINTER(TopLevelView)]),

@@ -26,6 +26,7 @@ struct SceneBuffers {                             // cgpt_scene_upload installs 
     DevBuf<uint32_t> refit_levels;
     DevBuf<cgpt_triangle> refit_staging;          // host triangles of the last refit, grown on demand
     DevBuf<uint32_t> skin_scratch;                // cgpt_scene_skin_mesh: 8 words a pose reads back (refit.hip: kSkinScratchWords), allocated with the first skin
+    DevBuf<uint32_t> pose_batch;                  // cgpt_scene_pose_objects: the tables and scratch of the last batch (refit.hip: PoseObjects), grown on demand
 };
 // The skin of one object (cgpt_scene_set_skin): the bind pose, 12 joint indices and 12 weights a triangle, and the room of a pose's
 // joint matrices.  Not part of the scene's footprint; an upload drops every skin.
@@ -324,6 +325,7 @@ int GroupClearSkin(cgpt_ctx* ctx, uint32_t obj_index);
 int GroupSetMorphTargets(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* base_triangles, const cgpt_triangle* target_deltas, uint32_t n_tris, uint32_t n_targets);
 int GroupMorphMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* weights, uint32_t n_targets);
 int GroupClearMorphTargets(cgpt_ctx* ctx, uint32_t obj_index);
+int GroupPoseObjects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_poses);
 int GroupRender(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p);
 int GroupResetAccumulator(cgpt_ctx* ctx);
 int GroupReadAccumulator(cgpt_ctx* ctx, float* dst, size_t n_floats);

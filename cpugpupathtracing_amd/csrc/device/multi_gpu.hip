@@ -401,6 +401,12 @@ int GroupClearMorphTargets(cgpt_ctx* ctx, uint32_t obj_index)
     return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_clear_morph_targets(m, obj_index); });
 }
 
+// ... and a batch of poses: every member plans and runs it on its own copy
+int GroupPoseObjects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_poses)
+{
+    return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_pose_objects(m, poses, n_poses); });
+}
+
 int GroupUpdateRoughness(cgpt_ctx* ctx, const float* roughness, uint32_t n)
 {
     return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_update_roughness(m, roughness, n); });

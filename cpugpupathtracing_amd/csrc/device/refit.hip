@@ -23,6 +23,8 @@
 // Morph targets (cgpt_scene_set_morph_targets / cgpt_scene_morph_mesh): the base triangles and the targets' displacements
 // stay on the device too, in leaf-slot order; morph_triangles blends them by the arithmetic of csrc/host/morph.h and, for an object that also
 // has a posed skin, hands each morphed corner to SkinCorner in registers.  Either call poses through PoseObject.
+// Many objects in one call (cgpt_scene_pose_objects): the same poses for any number of objects with launches that do not
+// grow with their count -- pose_plan.h plans the batch on the host, PoseObjects runs it through batched shells of the kernels above.
 // After cgpt_scene_upload_instanced the objects of a mesh group share the one copy these passes edit: the refit goes through any member's
 // RefitObject (they are equal), and the area and the top-level box, which are per object, are written for every member.
 #include <hip/hip_runtime.h>
@@ -39,6 +41,7 @@
 #include "device_scene.h"
 #include "minmax_std.h"
 #include "morph.h"
+#include "pose_plan.h"
 #include "scene_layout.h"
 #include "skinning.h"
 
@@ -59,6 +62,7 @@ std::vector<uint2> ActiveTable(const float* weights, uint32_t n_targets)
 namespace {
 
 constexpr uint32_t kRefitThreads = 256;
+static_assert(kRefitThreads == kPoseThreads, "pose_plan.h deals blocks of this size");
 
 // The records of one triangle, stated once for the refit's and the skin's triangle pass: tr is the cgpt_triangle (v0 {pos, normal}, v1, v2),
 // `leaf` its tri_leaf record with `keep` = leaf[2] as it was ({pad, e2.z, tri_idx, last_in_leaf}: pad, tri_idx and last_in_leaf stay), t = tri_idx
@@ -105,7 +109,7 @@ __global__ __launch_bounds__(kRefitThreads) void refit_triangles(const float* __
 // the 1024-joint limit), false reads them through the vector cache.  The joint indices are per lane and were validated by
 // cgpt_scene_set_skin.  *range_flag is set when a posed position is not finite or lies beyond 1e30, where the refitted root bounds (a
 // fold from +-1e30) no longer give the top-level box.
-constexpr uint32_t kSkinMaxBlocks = 1024;                                     // 4 blocks a CU
+// (the cap of its grid, kSkinMaxBlocks, is stated in pose_plan.h: the batch planner applies it per entry)
 // the 12 blended entries of corner c of triangle t (skinning.h: SkinBlend), for the skin's and the morph's triangle pass
 __device__ __forceinline__ void blend_corner_joints(const float4* mat, const uint2* __restrict__ joints, const float4* __restrict__ weights, uint32_t t, int c, float (&m)[12])
 {
@@ -298,6 +302,159 @@ __global__ __launch_bounds__(kRefitThreads) void refit_level(float4* node_pairs,
     rec[0] = make_float4(l.lo[0], r.lo[0], l.lo[1], r.lo[1]);                 // device_scene.h: node_pairs
     rec[1] = make_float4(l.lo[2], r.lo[2], l.hi[0], r.hi[0]);
     rec[2] = make_float4(l.hi[1], r.hi[1], l.hi[2], r.hi[2]);
+}
+
+// ---- the kernels of a batch (cgpt_scene_pose_objects; pose_plan.h plans it) --------------------------------------------
+// The shells above once more, with what was a kernel argument of one object read from a table: a block belongs to one entry (or one
+// entry's records of the launch's depth), found from blockIdx.x through the ascending first_block words, so everything it reads of the
+// table is block-uniform and comes through scalar loads.  The arithmetic is the shared device functions'.
+// One entry as the triangle pass and the box kernel read it: 72 bytes
+struct PoseEntryRecord {
+    const float2* data;                                                       // MORPH: MorphBuffers::data; otherwise the skin's bind pose
+    const uint2* joints;                                                      // SKIN: the skin's joints and weights
+    const float4* weights;
+    uint32_t leaf_base, tri_base, n_tris, n_joints;
+    uint32_t matrix_base, active_base, n_active, first_block;                 // PosePlanEntry's
+    uint32_t blocks, root_code, leaf_root, pad;
+};
+// per entry {range flag, lo.xyz, hi.xyz, not finite} as kSkinScratchWords, then the 12 floats of the refitted root record's bounds
+constexpr uint32_t kPoseScratchWords = 20;
+
+// the last of table[0 .. n) whose first_block is not after `block` (first_block ascends from 0)
+template <class T>
+__device__ __forceinline__ uint32_t last_not_after(const T* __restrict__ table, uint32_t n, uint32_t block)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) / 2u;
+        if (table[mid].first_block <= block) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// skin_triangles<LDS> (MORPH false: SKIN is set and LEAF is not) and morph_triangles<SKIN, LDS, LEAF> over the entries of one
+// instantiation.  `entries` and `scratch` start at the launch's first entry; an entry's blocks stride over its leaf slots by its own
+// block count, stage its own joint matrices (dynamic LDS: 48 B x the launch's largest joint count) and flag its own scratch.
+template <bool MORPH, bool SKIN, bool LDS, bool LEAF>
+__global__ __launch_bounds__(kRefitThreads) void pose_triangles_batch(const PoseEntryRecord* __restrict__ entries, uint32_t n_entries, const uint2* __restrict__ active_tables,
+                                                                      const float4* __restrict__ matrices, float4* __restrict__ tri_leaf, float4* __restrict__ tri_orig,
+                                                                      float4* __restrict__ tri_normal, uint32_t* __restrict__ scratch, uint32_t n_tris_total)
+{
+    extern __shared__ float4 s_matrices[];
+    const uint32_t k = last_not_after(entries, n_entries, blockIdx.x);
+    const PoseEntryRecord e = entries[k];
+    const float4* mat = matrices + 3 * (size_t)e.matrix_base;
+    if (SKIN && LDS) {
+        for (uint32_t j = threadIdx.x; j < 3 * e.n_joints; j += blockDim.x) s_matrices[j] = mat[j];
+        __syncthreads();
+        mat = s_matrices;
+    }
+    const float2* __restrict__ data = e.data;
+    const uint2* __restrict__ active = active_tables + e.active_base;
+    uint32_t* range_flag = scratch + kPoseScratchWords * (size_t)k;
+    const uint32_t n = e.n_tris;
+    for (uint32_t i = (blockIdx.x - e.first_block) * blockDim.x + threadIdx.x; i < n; i += e.blocks * blockDim.x) {
+        float4* leaf = tri_leaf + 3 * (size_t)(e.leaf_base + i);
+        const float4 keep = leaf[2];                                          // {pad, e2.z, tri_idx, last_in_leaf}
+        const uint32_t t = __float_as_uint(keep.z);
+        if (t >= n) continue;                                                 // validated at upload
+        const auto record = [&](uint32_t set, float (&out)[18]) {
+            for (int p = 0; p < 9; ++p) {
+                const float2 v = LEAF ? data[(9 * (size_t)set + p) * n + i] : data[9 * ((size_t)set * n + t) + p];
+                out[2 * p] = v.x; out[2 * p + 1] = v.y;
+            }
+        };
+        float base[18], x[18];
+        record(0u, base);                                                     // the skin's bind record where nothing is morphed
+        for (int j = 0; j < 18; ++j) x[j] = base[j];
+        if (MORPH) {
+            for (uint32_t a = 0; a < e.n_active; ++a) {
+                const uint2 kw = active[a];
+                float d[18];
+                record(1u + kw.x, d);
+                MorphAccumulate(x, __uint_as_float(kw.y), d);
+            }
+            if (e.n_active != 0u) MorphNormalise(base, x);
+        }
+        float tr[18];
+        if (SKIN) {
+            for (int c = 0; c < 3; ++c) {
+                float m[12];
+                blend_corner_joints(mat, e.joints, e.weights, t, c, m);
+                SkinCorner(m, x + 6 * c, tr + 6 * c);
+            }
+        } else {
+            for (int j = 0; j < 18; ++j) tr[j] = x[j];
+        }
+        bool in_range = true;
+        for (int c = 0; c < 3; ++c)
+            in_range = in_range && fabsf(tr[6 * c]) <= 1e30f && fabsf(tr[6 * c + 1]) <= 1e30f && fabsf(tr[6 * c + 2]) <= 1e30f;   // false for a NaN too
+        write_triangle_records(tr, leaf, keep, tri_orig, tri_normal, e.tri_base, t, n_tris_total);
+        if (!in_range) atomicOr(range_flag, 1u);
+    }
+}
+
+// refit_level over the records of one depth of every entry whose tree reaches it: a segment takes whole blocks, a thread a record
+__global__ __launch_bounds__(kRefitThreads) void refit_level_batch(float4* node_pairs, const float4* __restrict__ tri_leaf, const float4* __restrict__ tri_orig,
+                                                                   const uint32_t* __restrict__ refit_levels, const PosePlanSegment* __restrict__ segments, uint32_t n_segments)
+{
+    const PosePlanSegment s = segments[last_not_after(segments, n_segments, blockIdx.x)];
+    const uint32_t i = (blockIdx.x - s.first_block) * blockDim.x + threadIdx.x;
+    if (i >= s.count) return;
+    float4* rec = node_pairs + 4 * (size_t)refit_levels[s.records_begin + i];
+    const float4 codes = rec[3];
+    const Box l = side_bounds(node_pairs, tri_leaf, tri_orig, s.tri_base, __float_as_uint(codes.z));
+    const Box r = side_bounds(node_pairs, tri_leaf, tri_orig, s.tri_base, __float_as_uint(codes.w));
+    rec[0] = make_float4(l.lo[0], r.lo[0], l.lo[1], r.lo[1]);                 // device_scene.h: node_pairs
+    rec[1] = make_float4(l.lo[2], r.lo[2], l.hi[0], r.hi[0]);
+    rec[2] = make_float4(l.hi[1], r.hi[1], l.hi[2], r.hi[2]);
+}
+
+// What the host reads back of every entry, a block an entry: the refitted root record's bounds behind the entry's scratch words, and
+// fold_object_box's fold into them for an entry without a root record or with its range flag set.  (The fold is that kernel's body once
+// more: called from here as a function it compiles to another instruction stream there, and the single calls keep theirs.)
+__global__ __launch_bounds__(kRefitThreads) void pose_boxes_batch(const PoseEntryRecord* __restrict__ entries, const float4* __restrict__ node_pairs,
+                                                                  const float4* __restrict__ tri_orig, uint32_t* scratch)
+{
+    __shared__ float s_box[kRefitThreads][6];
+    __shared__ uint32_t s_bad[kRefitThreads];
+    const PoseEntryRecord e = entries[blockIdx.x];
+    uint32_t* out = scratch + kPoseScratchWords * (size_t)blockIdx.x;
+    if (e.leaf_root == 0u) {
+        if (threadIdx.x < 12u) out[kSkinScratchWords + threadIdx.x] = reinterpret_cast<const uint32_t*>(node_pairs + 4 * (size_t)e.root_code)[threadIdx.x];
+        if (out[0] == 0u) return;                                             // block-uniform: the triangle pass finished before this launch
+    }
+    float box[6] = { INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY };
+    uint32_t bad = 0u;
+    for (uint32_t t = threadIdx.x; t < e.n_tris; t += blockDim.x) {
+        const float4* o = tri_orig + 3 * (size_t)(e.tri_base + t);
+        for (int v = 0; v < 3; ++v) {
+            const float4 q = o[v];
+            const float x[3] = { q.x, q.y, q.z };
+            for (int a = 0; a < 3; ++a) {
+                if (!(fabsf(x[a]) < INFINITY)) bad = 1u;
+                if (x[a] < box[a]) box[a] = x[a];
+                if (x[a] > box[3 + a]) box[3 + a] = x[a];
+            }
+        }
+    }
+    for (int a = 0; a < 6; ++a) s_box[threadIdx.x][a] = box[a];
+    s_bad[threadIdx.x] = bad;
+    __syncthreads();
+    for (uint32_t stride = blockDim.x / 2; stride > 0; stride /= 2) {
+        if (threadIdx.x < stride) {
+            for (int a = 0; a < 3; ++a) {
+                if (s_box[threadIdx.x + stride][a] < s_box[threadIdx.x][a]) s_box[threadIdx.x][a] = s_box[threadIdx.x + stride][a];
+                if (s_box[threadIdx.x + stride][3 + a] > s_box[threadIdx.x][3 + a]) s_box[threadIdx.x][3 + a] = s_box[threadIdx.x + stride][3 + a];
+            }
+            s_bad[threadIdx.x] |= s_bad[threadIdx.x + stride];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        for (int a = 0; a < 6; ++a) out[1 + a] = __float_as_uint(s_box[0][a]);
+        out[7] = s_bad[0];
+    }
 }
 
 const char* KindName(uint32_t kind)
@@ -530,16 +687,25 @@ int PoseObject(cgpt_ctx* ctx, uint32_t obj_index, bool skinned, uint32_t n_activ
     return CGPT_OK;
 }
 
-int SkinMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uint32_t n_joints)
+// what cgpt_scene_skin_mesh refuses, for it and for an entry of cgpt_scene_pose_objects
+int CheckSkinPose(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uint32_t n_joints)
 {
     int rc = CheckObject(ctx, obj_index);
     if (rc != CGPT_OK) return rc;
     if (obj_index >= ctx->skins.size() || ctx->skins[obj_index].n_joints == 0u)
         return CtxFail(ctx, CGPT_ERR_INVALID, "object %u has no skin (cgpt_scene_set_skin installs one)", obj_index);
-    SkinBuffers& sk = ctx->skins[obj_index];
+    const SkinBuffers& sk = ctx->skins[obj_index];
     if (n_joints != sk.n_joints) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u's skin has %u joints, got %u", obj_index, sk.n_joints, n_joints);
     std::string why;
     if (!CheckJointMatrices(joint_matrices, n_joints, why)) return CtxFail(ctx, CGPT_ERR_INVALID, "%s", why.c_str());
+    return CGPT_OK;
+}
+
+int SkinMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uint32_t n_joints)
+{
+    int rc = CheckSkinPose(ctx, obj_index, joint_matrices, n_joints);
+    if (rc != CGPT_OK) return rc;
+    SkinBuffers& sk = ctx->skins[obj_index];
     std::vector<float> pose(joint_matrices, joint_matrices + 12 * (size_t)n_joints);   // what a temporal call that follows poses compares (denoise.hip)
     const bool morphed = HasMorphTargets(ctx, obj_index);                      // the morphed base is the bind pose then: one kernel does both
     std::vector<uint2> table;                                                  // ... of the last weights given, written again: see UploadActiveTable
@@ -629,16 +795,25 @@ int SetMorphTargets(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* base
     return CGPT_OK;
 }
 
-int MorphMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* weights, uint32_t n_targets)
+// what cgpt_scene_morph_mesh refuses, for it and for an entry of cgpt_scene_pose_objects
+int CheckMorphPose(cgpt_ctx* ctx, uint32_t obj_index, const float* weights, uint32_t n_targets)
 {
     int rc = CheckObject(ctx, obj_index);
     if (rc != CGPT_OK) return rc;
     if (!HasMorphTargets(ctx, obj_index))
         return CtxFail(ctx, CGPT_ERR_INVALID, "object %u has no morph targets (cgpt_scene_set_morph_targets installs them)", obj_index);
-    MorphBuffers& mb = ctx->morphs[obj_index];
+    const MorphBuffers& mb = ctx->morphs[obj_index];
     if (n_targets != mb.n_targets) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u has %u morph targets, got %u", obj_index, mb.n_targets, n_targets);
     std::string why;
     if (!CheckMorphWeights(weights, n_targets, why)) return CtxFail(ctx, CGPT_ERR_INVALID, "%s", why.c_str());
+    return CGPT_OK;
+}
+
+int MorphMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* weights, uint32_t n_targets)
+{
+    int rc = CheckMorphPose(ctx, obj_index, weights, n_targets);
+    if (rc != CGPT_OK) return rc;
+    MorphBuffers& mb = ctx->morphs[obj_index];
     std::vector<float> kept(weights, weights + n_targets);
     const std::vector<uint2> table = ActiveTable(weights, n_targets);
     // a skin that has been posed since it was installed takes part with the matrices of its last pose (sk.pose, written again: see UploadActiveTable)
@@ -670,6 +845,190 @@ int ClearMorphTargets(cgpt_ctx* ctx, uint32_t obj_index)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->morphs[obj_index] = MorphBuffers{};
+    return CGPT_OK;
+}
+
+// ---- many objects in one call (cgpt_scene_pose_objects) ---------------------------------------------------------------
+// What the single calls would do entry by entry -- MorphMesh for an entry with weights, then SkinMesh for one with matrices -- with the
+// launches of PlanPoseBatch: one triangle launch an instantiation in use, one bound launch a depth, one box launch; one upload (the
+// zeroed scratch, the entry table, the segments, every entry's matrices and active table in one piece), one synchronise, one readback
+// and one WriteTopLevel.  The per-skin `matrices` and per-object `active` buffers are not written: only the single calls' kernels read
+// them, and those calls upload them again themselves.
+int PoseObjects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_poses)
+{
+    if (n_poses == 0u) return CGPT_OK;
+    if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!poses) return CtxFail(ctx, CGPT_ERR_INVALID, "poses is null");
+
+    // the single calls' refusals, entry by entry, and what each entry poses with: its own arrays, or what the object's last pose left
+    struct Resolved { const float* matrices = nullptr; const float* weights = nullptr; bool morphed = false; std::vector<uint2> table; };
+    std::vector<Resolved> resolved(n_poses);
+    std::vector<PosePlanInput> in(n_poses);
+    for (uint32_t i = 0; i < n_poses; ++i) {
+        const cgpt_pose& p = poses[i];
+        const uint32_t o = p.obj_index;
+        int rc = CheckObject(ctx, o);
+        if (rc == CGPT_OK && p.n_joints == 0u && p.n_targets == 0u) rc = CtxFail(ctx, CGPT_ERR_INVALID, "object %u: neither joint matrices nor morph weights are given", o);
+        if (rc == CGPT_OK && p.n_targets != 0u) rc = CheckMorphPose(ctx, o, p.weights, p.n_targets);
+        if (rc == CGPT_OK && p.n_joints != 0u) rc = CheckSkinPose(ctx, o, p.joint_matrices, p.n_joints);
+        if (rc != CGPT_OK) { ctx->error = "entry " + std::to_string(i) + ": " + ctx->error; return rc; }
+        Resolved& r = resolved[i];
+        r.morphed = HasMorphTargets(ctx, o);
+        const bool posed_skin = o < ctx->skins.size() && ctx->skins[o].n_joints != 0u && !ctx->skins[o].pose.empty();   // MorphMesh: takes part with its last matrices
+        r.matrices = p.n_joints != 0u ? p.joint_matrices : posed_skin ? ctx->skins[o].pose.data() : nullptr;
+        if (r.morphed) {
+            const MorphBuffers& mb = ctx->morphs[o];
+            r.weights = p.n_targets != 0u ? p.weights : mb.weights.data();    // SkinMesh: the last weights given
+            r.table = ActiveTable(r.weights, mb.n_targets);
+        }
+        in[i] = { o, r.matrices ? ctx->skins[o].n_joints : 0u, r.morphed ? 1u : 0u, r.morphed ? ctx->morphs[o].leaf_order : 0u, (uint32_t)r.table.size() };
+    }
+    PosePlan plan;
+    std::string why;
+    const int planned = PlanPoseBatch(ctx->h_objects, ctx->refit_objects, ctx->mesh_group, in.data(), n_poses, ctx->skin_joints_lds, ctx->morph_max_blocks, plan, why);
+    if (planned != CGPT_OK) return CtxFail(ctx, planned, "%s", why.c_str());
+
+    // the upload, in 32-bit words, every part at a multiple of 16 bytes: scratch | entries | segments | matrices | active tables
+    static_assert(sizeof(PoseEntryRecord) == 72 && sizeof(PosePlanSegment) == 16, "the upload's parts");
+    const auto round4 = [](size_t words) { return (words + 3) / 4 * 4; };
+    const size_t n = plan.entries.size();
+    const size_t entries_at = round4(kPoseScratchWords * n), segments_at = entries_at + round4(sizeof(PoseEntryRecord) / 4 * n);
+    const size_t matrices_at = segments_at + 4 * plan.segments.size(), active_at = matrices_at + 12 * (size_t)plan.n_matrix_joints;
+    const size_t total = active_at + round4(2 * (size_t)plan.n_active) + 4;   // never empty
+    std::vector<uint32_t> blob(total, 0u);
+    for (size_t k = 0; k < n; ++k) {
+        const PosePlanEntry& e = plan.entries[k];
+        const Resolved& r = resolved[e.source];
+        PoseEntryRecord rec{};
+        if (r.matrices) {
+            const SkinBuffers& sk = ctx->skins[e.obj_index];
+            rec.joints = reinterpret_cast<const uint2*>(sk.joints.p); rec.weights = reinterpret_cast<const float4*>(sk.weights.p);
+            if (!r.morphed) rec.data = reinterpret_cast<const float2*>(sk.bind.p);
+            memcpy(blob.data() + matrices_at + 12 * (size_t)e.matrix_base, r.matrices, sizeof(float) * 12 * (size_t)e.n_joints);
+        }
+        if (r.morphed) rec.data = ctx->morphs[e.obj_index].data.p;
+        if (!r.table.empty()) memcpy(blob.data() + active_at + 2 * (size_t)e.active_base, r.table.data(), sizeof(uint2) * r.table.size());
+        rec.leaf_base = e.leaf_base; rec.tri_base = e.tri_base; rec.n_tris = e.n_tris; rec.n_joints = e.n_joints;
+        rec.matrix_base = e.matrix_base; rec.active_base = e.active_base; rec.n_active = e.n_active; rec.first_block = e.first_block;
+        rec.blocks = e.blocks; rec.root_code = e.root_code; rec.leaf_root = e.leaf_root;
+        memcpy(blob.data() + entries_at + sizeof(PoseEntryRecord) / 4 * k, &rec, sizeof(rec));
+    }
+    if (!plan.segments.empty()) memcpy(blob.data() + segments_at, plan.segments.data(), sizeof(PosePlanSegment) * plan.segments.size());
+    std::vector<uint32_t> back(kPoseScratchWords * n);
+    TopLevelState top = ctx->top_state;                                        // may throw: before the first write
+    if (ctx->pose_stamp.size() != ctx->h_objects.size()) ctx->pose_stamp.resize(ctx->h_objects.size(), 0);
+    if (ctx->morph_stamp.size() != ctx->h_objects.size()) ctx->morph_stamp.resize(ctx->h_objects.size(), 0);
+    std::vector<std::vector<float>> kept_matrices(n_poses), kept_weights(n_poses);   // what the commit below installs: allocated while a refusal is still possible
+    for (uint32_t i = 0; i < n_poses; ++i) {
+        if (poses[i].n_joints != 0u) kept_matrices[i].assign(poses[i].joint_matrices, poses[i].joint_matrices + 12 * (size_t)poses[i].n_joints);
+        if (poses[i].n_targets != 0u) kept_weights[i].assign(poses[i].weights, poses[i].weights + poses[i].n_targets);
+    }
+
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, ctx->sb.pose_batch.Grow(total));                              // the stream was just drained: nothing uses the old one
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->sb.pose_batch.p, blob.data(), sizeof(uint32_t) * total, hipMemcpyHostToDevice, ctx->stream));
+
+    // from here on the scene changes.  The generations and stamps move as the single calls move them, entry by entry: an accepted morph
+    // counts one scene, shape and morph edit, a pose one scene, shape and pose edit (denoise.hip: HistoryMatches)
+    const auto each_placement = [&](uint32_t obj, auto&& f) {
+        for (uint32_t j = 0; j < ctx->mesh_group.size(); ++j)
+            if (ctx->mesh_group[j] == ctx->mesh_group[obj]) f(j);
+    };
+    for (uint32_t i = 0; i < n_poses; ++i) {
+        const uint32_t o = poses[i].obj_index;
+        if (poses[i].n_targets != 0u) {
+            ctx->scene_generation++; ctx->shape_generation++; ctx->morph_generation++;
+            each_placement(o, [&](uint32_t j) { ctx->pose_stamp[j] = ctx->pose_generation; ctx->morph_stamp[j] = ctx->morph_generation; });
+        }
+        if (poses[i].n_joints != 0u) {
+            ctx->scene_generation++; ctx->shape_generation++; ctx->pose_generation++;
+            each_placement(o, [&](uint32_t j) { ctx->pose_stamp[j] = ctx->pose_generation; });
+        }
+        each_placement(o, [&](uint32_t j) {                                    // posed now, and by no other skin or targets
+            if (j < ctx->skins.size()) ctx->skins[j].pose_known = false;
+            if (j < ctx->morphs.size()) ctx->morphs[j].pose_known = false;
+        });
+    }
+
+    uint32_t* const dev = ctx->sb.pose_batch.p;
+    const PoseEntryRecord* const d_entries = reinterpret_cast<const PoseEntryRecord*>(dev + entries_at);
+    const PosePlanSegment* const d_segments = reinterpret_cast<const PosePlanSegment*>(dev + segments_at);
+    const float4* const d_matrices = reinterpret_cast<const float4*>(dev + matrices_at);
+    const uint2* const d_active = reinterpret_cast<const uint2*>(dev + active_at);
+    const dim3 block(kRefitThreads);
+    for (const PosePlanLaunch& l : plan.launches) {
+        const bool lds = l.kernel == kPoseSkinLds || l.kernel == kPoseMorphSkinLds || l.kernel == kPoseMorphSkinLdsLeaf;
+        const size_t lds_bytes = lds ? 3 * sizeof(float4) * (size_t)l.max_joints : 0;
+        const auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(l.n_blocks), block, lds_bytes, ctx->stream, d_entries + l.first_entry, l.n_entries, d_active, d_matrices, ctx->sb.tri_leaf.p,
+                               ctx->sb.tri_orig.p, ctx->sb.tri_normal.p, dev + kPoseScratchWords * (size_t)l.first_entry, ctx->scene.n_tris_total);
+        };
+        switch (l.kernel) {
+        case kPoseSkin: launch(pose_triangles_batch<false, true, false, false>); break;
+        case kPoseSkinLds: launch(pose_triangles_batch<false, true, true, false>); break;
+        case kPoseMorph: launch(pose_triangles_batch<true, false, false, false>); break;
+        case kPoseMorphLeaf: launch(pose_triangles_batch<true, false, false, true>); break;
+        case kPoseMorphSkin: launch(pose_triangles_batch<true, true, false, false>); break;
+        case kPoseMorphSkinLeaf: launch(pose_triangles_batch<true, true, false, true>); break;
+        case kPoseMorphSkinLds: launch(pose_triangles_batch<true, true, true, false>); break;
+        default: launch(pose_triangles_batch<true, true, true, true>); break;
+        }
+        REFIT_HIP_WRITING(ctx, hipGetLastError());
+    }
+    for (const PosePlanLevel& lv : plan.levels) {
+        hipLaunchKernelGGL(refit_level_batch, dim3(lv.n_blocks), block, 0, ctx->stream, ctx->sb.node_pairs.p, ctx->sb.tri_leaf.p, ctx->sb.tri_orig.p,
+                           ctx->sb.refit_levels.p, d_segments + lv.first_segment, lv.n_segments);
+        REFIT_HIP_WRITING(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(pose_boxes_batch, dim3((uint32_t)n), block, 0, ctx->stream, d_entries, ctx->sb.node_pairs.p, ctx->sb.tri_orig.p, dev);
+    REFIT_HIP_WRITING(ctx, hipGetLastError());
+    REFIT_HIP_WRITING(ctx, hipStreamSynchronize(ctx->stream));
+    REFIT_HIP_WRITING(ctx, hipMemcpy(back.data(), dev, sizeof(uint32_t) * back.size(), hipMemcpyDeviceToHost));
+
+    // the top-level boxes, as PoseObject reads them: the fold where there is no root record or the range flag is set, else the root record's two sides
+    for (size_t k = 0; k < n; ++k) {
+        const PosePlanEntry& e = plan.entries[k];
+        const uint32_t* scratch = back.data() + kPoseScratchWords * k;
+        float* box = top.local_box.data() + 6 * (size_t)e.obj_index;
+        if (e.leaf_root != 0u || scratch[0] != 0u) {
+            if (scratch[7] != 0u) UnboundedBox(box);
+            else memcpy(box, scratch + 1, 24);
+        } else {
+            float4 root[3];
+            memcpy(root, scratch + kSkinScratchWords, sizeof(root));
+            box[0] = min_std(root[0].x, root[0].y); box[1] = min_std(root[0].z, root[0].w); box[2] = min_std(root[1].x, root[1].y);
+            box[3] = max_std(root[1].z, root[1].w); box[4] = max_std(root[2].x, root[2].y); box[5] = max_std(root[2].z, root[2].w);
+        }
+        each_placement(e.obj_index, [&](uint32_t j) { if (j != e.obj_index) memcpy(top.local_box.data() + 6 * (size_t)j, box, 24); });
+    }
+    REFIT_HIP_WRITING(ctx, WriteTopLevel(ctx, ctx->h_objects, top));
+    ctx->top_state.local_box.swap(top.local_box);
+
+    // what a temporal call that follows poses or morphs compares, as MorphMesh and then SkinMesh leave it
+    for (uint32_t i = 0; i < n_poses; ++i) {
+        const uint32_t o = poses[i].obj_index;
+        const bool morphed = resolved[i].morphed;
+        if (poses[i].n_targets != 0u) {
+            MorphBuffers& mb = ctx->morphs[o];
+            const bool skinned = o < ctx->skins.size() && ctx->skins[o].n_joints != 0u && !ctx->skins[o].pose.empty();
+            mb.weights.swap(kept_weights[i]);
+            if (skinned) mb.pose_matrices = ctx->skins[o].pose; else mb.pose_matrices.clear();
+            mb.pose_skin_serial = skinned ? ctx->skins[o].serial : 0;
+            mb.pose_known = true;
+        }
+        if (poses[i].n_joints != 0u) {
+            SkinBuffers& sk = ctx->skins[o];
+            sk.pose.swap(kept_matrices[i]);
+            sk.pose_known = !morphed;
+            if (morphed) {
+                MorphBuffers& mb = ctx->morphs[o];
+                mb.pose_matrices = sk.pose;
+                mb.pose_skin_serial = sk.serial;
+                mb.pose_known = true;
+            }
+        }
+    }
     return CGPT_OK;
 }
 
@@ -840,6 +1199,13 @@ int cgpt_scene_clear_morph_targets(cgpt_ctx* ctx, uint32_t obj_index)
     if (!ctx) return CGPT_ERR_INVALID;
     if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupClearMorphTargets(ctx, obj_index); });
     return Guarded(ctx, __func__, [&] { return ClearMorphTargets(ctx, obj_index); });
+}
+
+int cgpt_scene_pose_objects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_poses)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupPoseObjects(ctx, poses, n_poses); });
+    return Guarded(ctx, __func__, [&] { return PoseObjects(ctx, poses, n_poses); });   // bumps the generations once the batch is accepted
 }
 
 int cgpt_scene_export_bvh(cgpt_ctx* ctx, uint32_t obj_index, cgpt_bvh_node* nodes_out, uint32_t n_nodes)

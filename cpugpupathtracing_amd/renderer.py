@@ -227,6 +227,22 @@ class Renderer:
         its own bind pose at its next skin_mesh.  No targets: nothing happens."""
         self._check(self.L.cgpt_scene_clear_morph_targets(self._ctx, obj_index))
 
+    def pose_objects(self, entries):
+        """cgpt_scene_pose_objects: poses many objects in one call.  `entries` is an iterable of (obj_index, matrices or
+        None, weights or None) with the array shapes skin_mesh and morph_mesh accept; the device scene afterwards is what
+        morph_mesh(obj_index, weights) and then skin_mesh(obj_index, matrices) of every entry in turn would leave, bit for bit, for a
+        number of kernel launches that does not grow with the number of entries.  An object (or an instanced mesh group) may be named
+        once; a refused batch changes nothing.  Only the device copy changes.  Call reset_accumulator() before the next frame."""
+        keep, rows = [], []
+        for obj_index, matrices, weights in entries:
+            m = _joint_matrices(matrices) if matrices is not None else None
+            w = _morph_weights(weights) if weights is not None else None
+            keep.append((m, w))
+            rows.append(N.Pose(int(obj_index), 0 if m is None else m.shape[0], None if m is None else m.ctypes.data_as(C.POINTER(C.c_float)),
+                               0 if w is None else w.size, None if w is None else w.ctypes.data_as(C.POINTER(C.c_float))))
+        poses = (N.Pose * max(1, len(rows)))(*rows)
+        self._check(self.L.cgpt_scene_pose_objects(self._ctx, poses, len(rows)))
+
     def export_bvh(self, obj_index: int) -> np.ndarray:
         """The device's tree of mesh `obj_index` as it is now (after refits): nodes[n,8] uint32 words in the reference's 32-byte layout
         and numbering, as Scene.bvh_export returns them.  Reads the device only; the host Scene is not touched."""

@@ -4,7 +4,7 @@
 //
 //   g++ -std=c++17 -Iinclude -Icpugpupathtracing_amd/csrc/host examples/render_main.cpp
 //       -Lcpugpupathtracing_amd/lib -lcpugpupt -Wl,-rpath,$PWD/cpugpupathtracing_amd/lib -o render_main   (one command line)
-//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--spin DEG] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [--bend DEG] [--bulge W] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
+//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--spin DEG] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [--bend DEG] [--bulge W] [--crowd N] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
 // --gpus N: ONE context over the first N GPUs of the node (cgpt_ctx_create with n_devices = N): every frame is spread over them in
 // interleaved row bands and the read-back gathers the float4 bands with one RCCL exchange over xGMI; the loop below does not
 // change.  --collective: take that code path with N = 1 too (what a one-GPU box can test).
@@ -54,6 +54,11 @@
 // kernel morphs and skins it (the frames keep the bend_ names).  With --bulge the temporal call sets CGPT_TEMPORAL_FOLLOW_POSES |
 // CGPT_TEMPORAL_FOLLOW_MORPHS: the mesh's pixels are carried back to where the same surface points were under the weight (and the bend) of the
 // frame before, and everyone keeps their history.
+// --crowd N: many deforming meshes -- N separate copies of the mesh stand in a row (each its own triangles and tree on the device, unlike
+// --instances; without a model the stand-in is built at level 4, 5120 triangles a copy), every one with the skin of --bend (and, with
+// --bulge W, its morph target), bent by an angle of its own: copy k by DEG (k + 1) / N degrees a frame (DEG from --bend, 10 without it).  All of
+// them are posed by ONE call a frame (cgpt_scene_pose_objects): the launches do not grow with N.  Frames and the temporal
+// call as for --bend (crowd_NN_*.ppm).
 // move_at > 0 scripts the input half of Update(dt) (ref: Main.cpp:277-297, Camera::Update :104-131): after that many samples the
 // camera is translated by (right, up, forward) as the A/D, Space/Shift, W/S keys would, the view changes, and the accumulator
 // is reset (ref: ResetAccumulator, Main.cpp:238-243) before the remaining samples are rendered from the new position.
@@ -80,7 +85,7 @@ using namespace cgpt;
 
 int main(int argc, char** argv)
 {
-    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool spin = false; float spin_deg = 0.0f; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false; uint32_t n_instances = 0; bool bend = false; float bend_deg = 0.0f; bool bulge = false; float bulge_w = 0.0f;
+    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool spin = false; float spin_deg = 0.0f; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false; uint32_t n_instances = 0; bool bend = false; float bend_deg = 0.0f; bool bulge = false; float bulge_w = 0.0f; uint32_t crowd = 0;
     bool has_transform = false; float mesh_transform[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
     MeshBVH::BuildOption bvh_option = MeshBVH::BuildOption_SAHSplitIntervals;
     while (argc > 1 && std::string(argv[1]).rfind("--", 0) == 0) {
@@ -91,6 +96,7 @@ int main(int argc, char** argv)
         else if (std::string(argv[1]) == "--spin" && argc > 2) { spin = true; spin_deg = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--bend" && argc > 2) { bend = true; bend_deg = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--bulge" && argc > 2) { bulge = true; bulge_w = (float)atof(argv[2]); argv += 2; argc -= 2; }
+        else if (std::string(argv[1]) == "--crowd" && argc > 2) { crowd = (uint32_t)atoi(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--variance-guided") { variance_guided = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--smooth") { smooth = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--mesh-transform" && argc > 13) {
@@ -117,9 +123,30 @@ int main(int argc, char** argv)
     const float move_forward = move_at ? (float)atof(argv[base + 7]) : 0.0f;
 
     Mesh mesh;
-    if (model.empty()) mesh = MakeDragonStandIn(6);
+    if (crowd && !bend) { bend = true; bend_deg = 10.0f; }
+    if (model.empty()) mesh = MakeDragonStandIn(crowd ? 4 : 6);
     else { std::string err; if (!GLTFLoader::Load(model, mesh, err)) { fprintf(stderr, "%s\n", err.c_str()); return 1; } }   // ref: Main.cpp:785
+    std::vector<Mesh> crowd_meshes;                                      // --crowd: copy k of the mesh, shrunk about its centre and shifted along x
+    if (crowd) {
+        float lo[3] = { 1e30f, 1e30f, 1e30f }, hi[3] = { -1e30f, -1e30f, -1e30f };
+        for (const cgpt_vertex& v : mesh.vertices)
+            for (int a = 0; a < 3; ++a) { lo[a] = std::fmin(lo[a], v.pos[a]); hi[a] = std::fmax(hi[a], v.pos[a]); }
+        const float scale = std::fmin(1.0f, 3.0f / (float)crowd), step = 1.1f * scale * (hi[0] - lo[0]);
+        for (uint32_t k = 0; k < crowd; ++k) {
+            Mesh copy = mesh;
+            for (cgpt_vertex& v : copy.vertices)
+                for (int a = 0; a < 3; ++a) v.pos[a] = 0.5f * (lo[a] + hi[a]) + scale * (v.pos[a] - 0.5f * (lo[a] + hi[a])) + (a == 0 ? step * ((float)k - 0.5f * (float)(crowd - 1)) : 0.0f);
+            crowd_meshes.push_back(std::move(copy));
+        }
+        mesh = crowd_meshes[0];
+    }
     Scene scene = MakeReferenceScene(mesh, 3, (float)W / (float)H, bvh_option);            // ref: Main.cpp:777-819
+    std::vector<uint32_t> posed(1, 0u);                                  // the objects --bend / --bulge pose: the mesh, and with --crowd its copies
+    for (uint32_t k = 1; k < crowd; ++k) {
+        posed.push_back((uint32_t)scene.objects.size());
+        scene.objects.push_back(Object("Crowd", crowd_meshes[k], k % 2 ? 0u : 3u, bvh_option));
+        if (!scene.objects.back().valid) { fprintf(stderr, "copy %u of the mesh could not be built\n", k); return 1; }
+    }
     if (!scene.objects[0].valid) { fprintf(stderr, "the mesh is empty, or (--bvh binned) has a position that is not finite or beyond 1e30\n"); return 1; }
     if (ground_roughness >= 0.0f) { scene.materials[1].specular = 0.5f; scene.materials[1].roughness = ground_roughness; }
     if (glass_roughness >= 0.0f) scene.materials[3].transmission_roughness = glass_roughness;
@@ -244,48 +271,61 @@ int main(int argc, char** argv)
     // highest point; joint 0 stays, joint 1 turns about the x axis through the middle of the mesh.  The skin goes to the device once.
     // --bulge: one procedural morph target of the same mesh, a push along the normal by the same height; it goes to the device once too.
     if (bend || bulge) {
-        float bend_pivot[3] = { 0.0f, 0.0f, 0.0f };
-        const cgpt_object& o = desc.objects[0];
-        const cgpt_triangle* bind = desc.triangles + o.tri_offset;      // original order, as cgpt_scene_refit_mesh takes them
-        float lo[3] = { 1e30f, 1e30f, 1e30f }, hi[3] = { -1e30f, -1e30f, -1e30f };
-        for (uint32_t t = 0; t < o.tri_count; ++t)
-            for (const cgpt_vertex* v : { &bind[t].v0, &bind[t].v1, &bind[t].v2 })
-                for (int a = 0; a < 3; ++a) { lo[a] = std::fmin(lo[a], v->pos[a]); hi[a] = std::fmax(hi[a], v->pos[a]); }
-        for (int a = 0; a < 3; ++a) bend_pivot[a] = 0.5f * (lo[a] + hi[a]);
-        std::vector<uint16_t> joints(12 * (size_t)o.tri_count, 0);
-        std::vector<float> weights(12 * (size_t)o.tri_count, 0.0f);
-        for (uint32_t t = 0; t < o.tri_count; ++t) {
-            const cgpt_vertex* const corner[3] = { &bind[t].v0, &bind[t].v1, &bind[t].v2 };
-            for (int c = 0; c < 3; ++c) {
-                const float h = hi[1] > lo[1] ? (corner[c]->pos[1] - lo[1]) / (hi[1] - lo[1]) : 0.0f;
-                joints[12 * (size_t)t + 4 * c + 1] = 1;
-                weights[12 * (size_t)t + 4 * c] = 1.0f - h; weights[12 * (size_t)t + 4 * c + 1] = h;
-            }
-        }
-        if (bend) CHECK(cgpt_scene_set_skin(ctx, 0, bind, joints.data(), weights.data(), o.tri_count, 2));
-        if (bulge) {
-            std::vector<cgpt_triangle> target(o.tri_count);              // displacements in the cgpt_triangle layout: position delta = height * normal, no normal delta
+        std::vector<float> pivots;                                       // y and z of every posed object's middle
+        for (const uint32_t obj : posed) {
+            const cgpt_object& o = desc.objects[obj];
+            const cgpt_triangle* bind = desc.triangles + o.tri_offset;  // original order, as cgpt_scene_refit_mesh takes them
+            float lo[3] = { 1e30f, 1e30f, 1e30f }, hi[3] = { -1e30f, -1e30f, -1e30f };
+            for (uint32_t t = 0; t < o.tri_count; ++t)
+                for (const cgpt_vertex* v : { &bind[t].v0, &bind[t].v1, &bind[t].v2 })
+                    for (int a = 0; a < 3; ++a) { lo[a] = std::fmin(lo[a], v->pos[a]); hi[a] = std::fmax(hi[a], v->pos[a]); }
+            pivots.push_back(0.5f * (lo[1] + hi[1])); pivots.push_back(0.5f * (lo[2] + hi[2]));
+            std::vector<uint16_t> joints(12 * (size_t)o.tri_count, 0);
+            std::vector<float> weights(12 * (size_t)o.tri_count, 0.0f);
             for (uint32_t t = 0; t < o.tri_count; ++t) {
                 const cgpt_vertex* const corner[3] = { &bind[t].v0, &bind[t].v1, &bind[t].v2 };
-                cgpt_vertex* const d[3] = { &target[t].v0, &target[t].v1, &target[t].v2 };
-                for (int c = 0; c < 3; ++c)
-                    for (int a = 0; a < 3; ++a) { d[c]->pos[a] = weights[12 * (size_t)t + 4 * c + 1] * corner[c]->normal[a]; d[c]->normal[a] = 0.0f; }
+                for (int c = 0; c < 3; ++c) {
+                    const float h = hi[1] > lo[1] ? (corner[c]->pos[1] - lo[1]) / (hi[1] - lo[1]) : 0.0f;
+                    joints[12 * (size_t)t + 4 * c + 1] = 1;
+                    weights[12 * (size_t)t + 4 * c] = 1.0f - h; weights[12 * (size_t)t + 4 * c + 1] = h;
+                }
             }
-            CHECK(cgpt_scene_set_morph_targets(ctx, 0, bind, target.data(), o.tri_count, 1));
+            if (bend) CHECK(cgpt_scene_set_skin(ctx, obj, bind, joints.data(), weights.data(), o.tri_count, 2));
+            if (bulge) {
+                std::vector<cgpt_triangle> target(o.tri_count);          // displacements in the cgpt_triangle layout: position delta = height * normal, no normal delta
+                for (uint32_t t = 0; t < o.tri_count; ++t) {
+                    const cgpt_vertex* const corner[3] = { &bind[t].v0, &bind[t].v1, &bind[t].v2 };
+                    cgpt_vertex* const d[3] = { &target[t].v0, &target[t].v1, &target[t].v2 };
+                    for (int c = 0; c < 3; ++c)
+                        for (int a = 0; a < 3; ++a) { d[c]->pos[a] = weights[12 * (size_t)t + 4 * c + 1] * corner[c]->normal[a]; d[c]->normal[a] = 0.0f; }
+                }
+                CHECK(cgpt_scene_set_morph_targets(ctx, obj, bind, target.data(), o.tri_count, 1));
+            }
         }
 
         std::vector<uint32_t> px((size_t)W * H);                         // the mesh bends every frame: SkinMesh, ResetAccumulator, Render, present
         const cgpt_camera cam = scene.camera.Abi();
         const cgpt_temporal_params tp = { 64.0f, 0.9f, 0.01f, CGPT_TEMPORAL_FOLLOW_POSES | (bulge ? (uint32_t)CGPT_TEMPORAL_FOLLOW_MORPHS : 0u) };   // each flag keeps its own kind of edit
         for (uint32_t frame = 0; frame < 8; ++frame) {                   // the pose of this frame: 48 bytes a joint go to the device
-            const double angle = (double)bend_deg * (double)frame * 3.14159265358979 / 180.0, c = std::cos(angle), sn = std::sin(angle);
-            const float py = bend_pivot[1], pz = bend_pivot[2];
-            const float joint_matrices[24] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0,                                    // joint 0 stays
-                                               1, 0, 0, 0, 0, (float)c, (float)-sn, (float)(py - c * py + sn * pz),    // joint 1: R_x (p - pivot) + pivot
-                                               0, (float)sn, (float)c, (float)(pz - sn * py - c * pz) };
+            std::vector<float> joint_matrices(24 * posed.size());
+            for (size_t k = 0; k < posed.size(); ++k) {                  // copy k of a crowd bends by its own share of the angle
+                const double share = crowd ? (double)(k + 1) / (double)crowd : 1.0;
+                const double angle = share * (double)bend_deg * (double)frame * 3.14159265358979 / 180.0, c = std::cos(angle), sn = std::sin(angle);
+                const float py = pivots[2 * k], pz = pivots[2 * k + 1];
+                const float m[24] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0,                                    // joint 0 stays
+                                      1, 0, 0, 0, 0, (float)c, (float)-sn, (float)(py - c * py + sn * pz),    // joint 1: R_x (p - pivot) + pivot
+                                      0, (float)sn, (float)c, (float)(pz - sn * py - c * pz) };
+                for (int i = 0; i < 24; ++i) joint_matrices[24 * k + i] = m[i];
+            }
             const float morph_weight = bulge_w * (float)frame / 7.0f;
-            if (bulge) CHECK(cgpt_scene_morph_mesh(ctx, 0, &morph_weight, 1));       // 4 bytes a target go to the device
-            if (bend) CHECK(cgpt_scene_skin_mesh(ctx, 0, joint_matrices, 2));        // on a mesh with targets: the morphed base through the joints, one kernel
+            if (crowd) {                                                 // every copy in one call: an entry with both arrays is posed once, by the fused kernel
+                std::vector<cgpt_pose> poses(posed.size());
+                for (size_t k = 0; k < posed.size(); ++k) poses[k] = { posed[k], 2u, joint_matrices.data() + 24 * k, bulge ? 1u : 0u, bulge ? &morph_weight : nullptr };
+                CHECK(cgpt_scene_pose_objects(ctx, poses.data(), (uint32_t)poses.size()));
+            } else {
+                if (bulge) CHECK(cgpt_scene_morph_mesh(ctx, 0, &morph_weight, 1));       // 4 bytes a target go to the device
+                if (bend) CHECK(cgpt_scene_skin_mesh(ctx, 0, joint_matrices.data(), 2)); // on a mesh with targets: the morphed base through the joints, one kernel
+            }
             CHECK(cgpt_reset_accumulator(ctx));
             cgpt_render_params p{};
             p.width = W; p.height = H; p.row_begin = 0; p.row_end = H;
@@ -293,7 +333,7 @@ int main(int argc, char** argv)
             CHECK(cgpt_render(ctx, &cam, &settings, &p));
             char name[64]; std::string err;
             CHECK(cgpt_read_pixels(ctx, px.data(), px.size()));
-            const char* tag = bend ? "bend" : "bulge";
+            const char* tag = crowd ? "crowd" : bend ? "bend" : "bulge";
             snprintf(name, sizeof(name), "%s_%02u_raw.ppm", tag, frame); WritePPM(name, px.data(), W, H, err);
             CHECK(cgpt_denoise(ctx, &cam, nullptr, nullptr, 0, px.data(), px.size()));
             snprintf(name, sizeof(name), "%s_%02u_denoised.ppm", tag, frame); WritePPM(name, px.data(), W, H, err);

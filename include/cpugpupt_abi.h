@@ -42,7 +42,8 @@ extern "C" {
                                  temporal stage is a new enum value (CGPT_TEMPORAL_FOLLOW_POSES) and one new symbol
                                  (cgpt_read_previous_hits) only; morph targets added new symbols only
                                  (cgpt_scene_set_morph_targets, cgpt_scene_morph_mesh, cgpt_scene_clear_morph_targets); following
-                                 morphs in the temporal stage is a new enum value only (CGPT_TEMPORAL_FOLLOW_MORPHS) */
+                                 morphs in the temporal stage is a new enum value only (CGPT_TEMPORAL_FOLLOW_MORPHS); posing many
+                                 objects in one call added one new symbol (cgpt_scene_pose_objects) and a new struct (cgpt_pose) only */
 
 enum cgpt_status {
     CGPT_OK = 0,
@@ -409,6 +410,30 @@ int cgpt_scene_set_morph_targets(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_t
 int cgpt_scene_morph_mesh(cgpt_ctx* ctx, uint32_t obj_index, const float* weights, uint32_t n_targets);
 int cgpt_scene_clear_morph_targets(cgpt_ctx* ctx, uint32_t obj_index);
 
+/* ---- posing many objects in one call ----
+ * cgpt_scene_pose_objects: what cgpt_scene_morph_mesh (an entry with weights) and then cgpt_scene_skin_mesh (an entry with matrices)
+ * would do for each of n_poses entries in array order, with a number of kernel launches that does not grow with n_poses: one launch per
+ * kernel instantiation in use, one per depth of the deepest tree among the entries, one for the boxes -- and one synchronise, one
+ * readback and one rebuild of the top-level tree for the whole batch.  Afterwards the device scene is what those single calls leave, bit
+ * for bit: triangle records, both normal records, every node's bounds, the top-level boxes, every placement of an instanced group, on
+ * every device of a multi-device context; total_area stays untouched.  What a later cgpt_denoise_temporal call with
+ * CGPT_TEMPORAL_FOLLOW_POSES / _MORPHS makes of its history is what it makes of it after the single calls.  An entry with both arrays is
+ * posed once (the fused kernel); an entry with weights alone on an object whose skin has been posed takes that skin's last matrices, an
+ * entry with matrices alone on an object with targets its last weights.
+ * Everything is validated before the first device write: a refused call changes nothing, the denoiser's guides and temporal history
+ * included.  CGPT_ERR_INVALID, with the entry's index in the message, for whatever the single call refuses of an entry, and for: poses
+ * NULL; an entry with n_joints == 0 and n_targets == 0; a count with a NULL array; two entries that name one object; two entries that
+ * name objects of one instanced mesh group (they share the copy: sequentially the last would win).  n_poses == 0: CGPT_OK, nothing
+ * happens.  A HIP failure after the first write drops the scene, as in the single calls. */
+typedef struct cgpt_pose {
+    uint32_t obj_index;
+    uint32_t n_joints;            /* 0: this entry gives no joint matrices */
+    const float* joint_matrices;  /* n_joints x 12, as cgpt_scene_skin_mesh takes them */
+    uint32_t n_targets;           /* 0: this entry gives no morph weights */
+    const float* weights;         /* n_targets, as cgpt_scene_morph_mesh takes them */
+} cgpt_pose;
+int cgpt_scene_pose_objects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_poses);
+
 /* UpdateScreenPlane (ref: Main.cpp:98-102,143-149): fov in degrees, plane at distance fov-in-radians (SURVEY A-13) */
 int cgpt_camera_from_view(const float pos[3], const float view_dir[3], float fov_deg, float aspect, cgpt_camera* out);
 
@@ -713,7 +738,8 @@ int cgpt_read_variance(cgpt_ctx* ctx, float* dst, size_t n_floats);
  * "skin_joints_lds" (0 | 1, default 1) is cgpt_scene_skin_mesh's: whether its kernel stages the joint matrices in LDS or reads them
  * through the vector cache.  "morph_leaf_order" (0 | 1, default 1), read by cgpt_scene_set_morph_targets: whether
  * the targets are stored in the order of the object's leaf slots as component planes, or as given; "morph_max_blocks" (1..1024,
- * default 1024): the cap of the morph kernel's grid. */
+ * default 1024): the cap of the morph kernel's grid.  cgpt_scene_pose_objects reads "skin_joints_lds" the same way
+ * and applies "morph_max_blocks" to every entry's share of a launch. */
 int cgpt_set_tuning(cgpt_ctx* ctx, const char* name, uint32_t value);
 /* Measures the vector-instruction issue rate of the device -- the roof bench.py prices the trace kernel against: every
  * SIMD of every CU runs `iters` x 64 independent instructions of one kind per wave at `waves_per_simd` resident waves.

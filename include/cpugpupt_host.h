@@ -205,6 +205,31 @@ int cgpth_scene_layout_instanced(const cgpt_scene_desc* scene, cgpth_scene_layou
  * message: obj_xform holds the inverses, `objects` the xform words and obj_trace the flags the call would install */
 int cgpth_scene_layout_transformed(const cgpt_scene_desc* scene, const float* object_to_world, uint32_t n_objects, cgpth_scene_layout_view* out);
 
+/* ---- the plan of cgpt_scene_pose_objects (csrc/device/pose_plan.h), computed on the host; no GPU is touched ----
+ * The batch is n_entries rows of five words {obj_index, n_joints of the skin that takes part (0: none), 1 if the object has morph
+ * targets, 1 if they are stored in leaf-slot order, active targets} over the layout a cgpt_scene_upload of `scene` installs
+ * (cgpt_scene_upload_instanced with instanced != 0), under the knobs skin_joints_lds and morph_max_blocks.  The view shows the tables
+ * the launcher walks, as rows of 32-bit words:
+ *   entries   16 words {source row, obj_index, kernel, leaf_base, tri_base, n_tris, n_joints, matrix_base, active_base, n_active,
+ *             first_block, blocks, root_code, leaf_root, n_levels, 0}, grouped by kernel, the batch's order kept within one --
+ *             0 skin_triangles<LDS = 0>, 1 <1>; morph_triangles<SKIN, LDS, LEAF>: 2 <0,0,0>, 3 <0,0,1>, 4 <1,0,0>, 5 <1,0,1>, 6 <1,1,0>, 7 <1,1,1>;
+ *   launches  5 words {kernel, first_entry, n_entries, n_blocks, max_joints}: block b of a launch belongs to the last of its entries
+ *             with first_block <= b, is block b - first_block of it, and its lanes take leaf slots (b - first_block) 256 + lane,
+ *             + 256 blocks, ... below n_tris;
+ *   segments  4 words {records_begin, count, tri_base, first_block}: refit_levels[records_begin .. records_begin + count);
+ *   levels    4 words {depth, first_segment, n_segments, n_blocks}, one launch of the bound pass each, in launch order.
+ * The refusals are the planner's (two entries naming one object or one instanced mesh group among them), with the message in
+ * cgpth_last_error().  The arrays live in thread-local storage and stay valid until the next call on the same thread. */
+typedef struct cgpth_pose_plan_view {
+    const uint32_t* entries; size_t n_entries;
+    const uint32_t* launches; size_t n_launches;
+    const uint32_t* segments; size_t n_segments;
+    const uint32_t* levels; size_t n_levels;
+    uint32_t n_matrix_joints, n_active;
+} cgpth_pose_plan_view;
+int cgpth_pose_batch_plan(const cgpt_scene_desc* scene, int instanced, const uint32_t* batch, uint32_t n_entries, uint32_t skin_joints_lds,
+                          uint32_t morph_max_blocks, cgpth_pose_plan_view* out);
+
 /* ---- the top-level tree of cgpt_set_top_level (csrc/device/scene_layout.h: LayoutTopLevel; tests/tlas_ref.py is its specification) ----
  * cgpth_top_level: the tree a cgpt_scene_upload of `scene` would build (cgpt_scene_upload_instanced builds the same: the boxes are per
  * object; the record limit that is checked is the instanced upload's), computed on the host with the upload's validation; no GPU is
