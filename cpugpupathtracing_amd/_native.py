@@ -29,6 +29,7 @@ TEMPORAL_FOLLOW_MORPHS = 32
 VARIANCE_TEMPORAL = 1
 SKIN_MAX_JOINTS = 1024      # cgpt_scene_set_skin
 MORPH_MAX_TARGETS = 256     # cgpt_scene_set_morph_targets
+HIP_STREAM_LEGACY, HIP_STREAM_PER_THREAD = 1, 2   # hipStreamLegacy, hipStreamPerThread (hip_runtime_api.h): refused by cgpt_set_stream
 
 f3 = C.c_float * 3
 

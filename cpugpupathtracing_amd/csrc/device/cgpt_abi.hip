@@ -290,6 +290,10 @@ int cgpt_set_stream(cgpt_ctx* ctx, void* hip_stream)
 {
     if (!ctx) return CGPT_ERR_INVALID;
     if (ctx->group) return CtxFail(ctx, CGPT_ERR_UNSUPPORTED, "cgpt_set_stream: a multi-device context owns its streams");
+    // the renders fork onto pool streams and join back through event waits on this stream: that needs a stream object
+    if ((hipStream_t)hip_stream == hipStreamLegacy || (hipStream_t)hip_stream == hipStreamPerThread)
+        return CtxFail(ctx, CGPT_ERR_UNSUPPORTED, "cgpt_set_stream: %s names a default stream; use a non-default stream (hipStreamCreate)",
+                       (hipStream_t)hip_stream == hipStreamLegacy ? "hipStreamLegacy" : "hipStreamPerThread");
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream.s;
     return CGPT_OK;

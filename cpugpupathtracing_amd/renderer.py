@@ -72,8 +72,20 @@ class Renderer:
         if rc != 0:
             raise DeviceError(rc, self.L.cgpt_last_error(self._ctx).decode())
 
-    def set_stream(self, hip_stream: int):
-        self._check(self.L.cgpt_set_stream(self._ctx, C.c_void_p(hip_stream)))
+    def set_stream(self, hip_stream):
+        """cgpt_set_stream: the calls that follow run on the caller's stream, behind whatever the caller queued on it, and return
+        once their own work is done ("Streams").  hip_stream: a hipStream_t as an int, or an object with a
+        cuda_stream attribute (torch.cuda.Stream, torch.cuda.current_stream()); None restores the context's own stream.  A handle
+        of 0 is the device's default stream -- torch's current stream on ROCm unless another was made current -- which the library
+        cannot run on (include/cpugpupt_abi.h) and which the C ABI would read as "the context's own stream", unordered against the
+        caller's work: ValueError, and nothing changed."""
+        handle = None
+        if hip_stream is not None:
+            handle = int(hip_stream.cuda_stream if hasattr(hip_stream, "cuda_stream") else hip_stream)
+            if handle == 0:
+                raise ValueError("set_stream: handle 0 is the default stream, which this library cannot run on; use a non-default stream "
+                                 "(torch.cuda.Stream()), or None for the context's own stream")
+        self._check(self.L.cgpt_set_stream(self._ctx, C.c_void_p(handle)))
 
     def set_nee_candidates(self, m: int):
         """cgpt_set_nee_candidates: the NEE light sample of the renders that follow is the survivor of m candidates (resampled importance
@@ -435,6 +447,13 @@ class Renderer:
     def accumulator_device_ptr(self) -> Tuple[int, int]:
         ptr = C.c_void_p(); nbytes = C.c_size_t()
         self._check(self.L.cgpt_accumulator_device_ptr(self._ctx, C.byref(ptr), C.byref(nbytes)))
+        return ptr.value, nbytes.value
+
+    def pixels_device_ptr(self) -> Tuple[int, int]:
+        """cgpt_pixels_device_ptr: the packed uint32 pixels of this context's band on the device, (pointer, bytes = rows * width * 4);
+        on a multi-device context the gathered frame on the first device, as accumulator_device_ptr()."""
+        ptr = C.c_void_p(); nbytes = C.c_size_t()
+        self._check(self.L.cgpt_pixels_device_ptr(self._ctx, C.byref(ptr), C.byref(nbytes)))
         return ptr.value, nbytes.value
 
     def stats(self) -> N.Stats:

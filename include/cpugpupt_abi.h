@@ -202,7 +202,15 @@ int cgpt_ctx_destroy(cgpt_ctx* ctx);
 /* replaces EXCEPT/LOG_ERR (ref: Common.h:9): message of the last failing call on ctx (or of the last failing
  * cgpt_ctx_create when ctx is NULL). Never NULL. */
 const char* cgpt_last_error(const cgpt_ctx* ctx);
-/* run on a caller-provided hipStream_t (e.g. torch's current stream); NULL restores the context's own stream */
+/* run on a caller-provided hipStream_t (e.g. torch's current stream): the calls that follow are ordered behind what the caller queued
+ * on it, and each still returns with its own work done.  NULL restores the context's own stream (non-blocking: it waits for nobody's
+ * queued work).  NULL therefore never names the device's default stream -- which is what torch's current stream is on ROCm unless the
+ * caller made another one current -- and the default stream cannot be named at all: hipStreamLegacy and hipStreamPerThread are refused
+ * with CGPT_ERR_UNSUPPORTED and nothing changed (the renders join their pool streams back through event waits on this stream, which
+ * the HIP runtime does not take on hipStreamLegacy: DESIGN.md 5.31).  Use a non-default stream (hipStreamCreate, torch.cuda.Stream);
+ * Renderer.set_stream raises ValueError for a handle of 0 so that torch's default stream is never silently read as "own stream".
+ * The previous stream is drained first; the stream stays the caller's (cgpt_ctx_destroy drains it and leaves it alone); a
+ * multi-device context owns its streams and refuses with CGPT_ERR_UNSUPPORTED. */
 int cgpt_set_stream(cgpt_ctx* ctx, void* hip_stream);
 /* Resampled importance sampling of the NEE light sample (Talbot et al. 2005): at every bounce that samples a light,
  * `candidates` light samples are drawn as the reference draws its one, each is weighed by its unshadowed contribution, and one survivor
