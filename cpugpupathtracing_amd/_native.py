@@ -154,6 +154,17 @@ class PosePlanView(C.Structure):
                 ("n_matrix_joints", C.c_uint32), ("n_active", C.c_uint32)]
 
 
+class RebuildPlanView(C.Structure):
+    """cgpth_rebuild_plan_view"""
+    _fields_ = [("members", _up), ("n_members", C.c_size_t), ("top_slots", _up), ("n_top_slots", C.c_size_t),
+                ("level_offsets", _up), ("n_level_offsets", C.c_size_t), ("names", _up), ("n_names", C.c_size_t),
+                ("record_perm", _up), ("n_record_perm", C.c_size_t),
+                ("root_codes", _up), ("span_bases", _up), ("node_counts", _up), ("n_objects", C.c_size_t),
+                ("span_base", C.c_uint32), ("level_begin", C.c_uint32), ("pair_base", C.c_uint32), ("leaf_base", C.c_uint32),
+                ("n_nodes", C.c_uint32), ("n_pairs", C.c_uint32), ("max_depth", C.c_uint32), ("grow", C.c_uint32),
+                ("n_pair_records", C.c_uint32), ("n_refit_levels", C.c_uint32), ("stack_depth", C.c_uint32), ("n_top_records", C.c_uint32)]
+
+
 class Pose(C.Structure):
     """cgpt_pose: one entry of cgpt_scene_pose_objects"""
     _fields_ = [("obj_index", C.c_uint32), ("n_joints", C.c_uint32), ("joint_matrices", _fp), ("n_targets", C.c_uint32), ("weights", _fp)]
@@ -189,6 +200,7 @@ PROTOTYPES = {
     "cgpt_scene_update_smooth_normals": (C.c_int, [_vp, _up, C.c_uint32]),
     "cgpt_scene_update_transforms": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_uint32]),
     "cgpt_scene_refit_mesh": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), C.c_uint32, _fp]),
+    "cgpt_scene_rebuild_mesh": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _up, _up]),
     "cgpt_scene_export_bvh": (C.c_int, [_vp, C.c_uint32, C.POINTER(BvhNode), C.c_uint32]),
     "cgpt_scene_update_primitive": (C.c_int, [_vp, C.c_uint32, C.POINTER(Object)]),
     "cgpt_scene_set_skin": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), _u16p, _fp, C.c_uint32, C.c_uint32]),
@@ -288,6 +300,7 @@ PROTOTYPES = {
     "cgpth_scene_layout_instanced": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(SceneLayoutView)]),
     "cgpth_scene_layout_transformed": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(C.c_float), C.c_uint32, C.POINTER(SceneLayoutView)]),
     "cgpth_pose_batch_plan": (C.c_int, [C.POINTER(SceneDesc), C.c_int, _up, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PosePlanView)]),
+    "cgpth_rebuild_plan": (C.c_int, [C.POINTER(SceneDesc), C.c_int, C.c_uint32, _up, C.c_uint32, C.c_uint32, C.POINTER(RebuildPlanView)]),
     "cgpth_scene_permute_objects":(C.c_int, [_vp, _up, C.c_uint32]),
     "cgpth_top_level": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(TopLevelView)]),
     "cgpth_top_level_transforms": (C.c_int, [C.POINTER(C.c_float), C.c_uint32, C.POINTER(TopLevelView)]),

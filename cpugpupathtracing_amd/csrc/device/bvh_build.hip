@@ -22,6 +22,8 @@
 //     sum of the "left" flags;
 //   * nodes are created in breadth-first order with an atomic counter and renumbered at the end into the reference's
 //     allocation order (children of the k-th splitting node in depth-first preorder get indices 2k+1, 2k+2).
+// cgpt_scene_rebuild_mesh (at the end of this file) runs the same level loop over a mesh of the uploaded scene, fed from
+// the scene's own triangle arrays, and writes the tree as the scene's child-pair and leaf-triangle records: a Rebuild in place.
 #include <hip/hip_runtime.h>
 
 #include <exception>
@@ -34,8 +36,10 @@
 #include <vector>
 
 #include "cpugpupt_abi.h"
+#include "ctx_internal.h"
 #include "device_memory.h"
 #include "minmax_std.h"
+#include "rebuild_layout.h"
 
 namespace cgpt {
 
@@ -913,6 +917,147 @@ __global__ void __launch_bounds__(kBuildThreads) root_bounds(BuildArrays A, uint
     }
 }
 
+// ---- cgpt_scene_rebuild_mesh: the builder fed from the device scene, and its tree written as the scene's own records (device_scene.h;
+//      the names of the records: rebuild_layout.h) ------------------------------------------------------------------------------------
+// report words the host reads back: {flags, root lo.xyz, root hi.xyz, top slots used, then the rank that took each used top slot}
+constexpr uint32_t kReportRanks = 8;
+constexpr uint32_t kTopScan = 2u * kTopRecords;              // the K-th splitting node of a level-ordered array sits at position 2 (K - 1) at most
+constexpr uint32_t kFlagDomain = 1u;                         // a position that is not finite or exceeds 1e30 in magnitude (the binned build's domain)
+constexpr uint32_t kFlagSlot = 2u;                           // a leaf slot that names no triangle of the mesh
+constexpr uint32_t kFlagEmit = 4u;                           // an emit kernel met a node or an index that the checks in front of the first write rule out:
+                                                             // it skipped the write, and the host drops the half-written scene
+
+// The front end: index i is leaf slot i and triangle i at once.  Slot i's tri_leaf tail gives the Rebuild's starting order; triangle i's
+// box and centroid come from tri_orig with prepare_triangles' arithmetic.  Both reads are consecutive across a wave: no gather.
+__global__ void __launch_bounds__(256) prepare_from_scene(const float4* __restrict__ tri_leaf, const float4* __restrict__ tri_orig, uint32_t leaf_base, uint32_t tri_base,
+                                                          uint32_t n, F3* lo, F3* hi, F3* centroid, uint32_t* idx, uint32_t* flags)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t t = __float_as_uint(tri_leaf[3 * (size_t)(leaf_base + i) + 2].z);
+    uint32_t flag = 0u;
+    if (t >= n) { flag |= kFlagSlot; t = 0u; }                // validated at upload; the kernels index with it
+    idx[i] = t;
+    const float4* o = tri_orig + 3 * (size_t)(tri_base + i);
+    const float4 a = o[0], b = o[1], c = o[2];
+    const F3 p0 = { a.x, a.y, a.z }, p1 = { b.x, b.y, b.z }, p2 = { c.x, c.y, c.z };
+    lo[i] = f3min(f3min(p0, p1), p2);
+    hi[i] = f3max(f3max(p0, p1), p2);
+    centroid[i] = { ((p0.x + p1.x) + p2.x) * 0.3333f, ((p0.y + p1.y) + p2.y) * 0.3333f, ((p0.z + p1.z) + p2.z) * 0.3333f };
+    const float m = fmaxf(fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(b.x))), fmaxf(fmaxf(fabsf(b.y), fabsf(b.z)), fmaxf(fmaxf(fabsf(c.x), fabsf(c.y)), fabsf(c.z))));
+    const bool nan = a.x != a.x || a.y != a.y || a.z != a.z || b.x != b.x || b.y != b.y || b.z != b.z || c.x != c.x || c.y != c.y || c.z != c.z;   // fmaxf drops a NaN
+    if (nan || !(m <= 1e30f)) flag |= kFlagDomain;
+    if (flag) atomicOr(flags, flag);
+}
+
+// The first K splitting nodes of the level-ordered array take the mesh's top slots (rebuild_layout.h).  One block over the first kTopScan
+// nodes, a thread a run of consecutive nodes, so the prefix of the splitting flags is the array's order.  top_name[i] = the slot of node
+// i, 0xFFFFFFFF for every other node below kTopScan; the report gets the ranks in slot order and the root's bounds.
+__global__ void __launch_bounds__(kBuildThreads) assign_top_slots(const BuildNode* __restrict__ nodes, uint32_t n_nodes, const uint32_t* __restrict__ top_slots, uint32_t K,
+                                                                  uint32_t* top_name, uint32_t* report)
+{
+    __shared__ uint32_t s_u32[5];
+    constexpr uint32_t per = (kTopScan + kBuildThreads - 1u) / kBuildThreads;
+    const uint32_t i0 = threadIdx.x * per;
+    uint32_t mine = 0;
+    for (uint32_t k = 0; k < per; ++k) { const uint32_t i = i0 + k; if (i < kTopScan && i < n_nodes && nodes[i].left != 0u) ++mine; }
+    uint32_t total = 0;
+    uint32_t j = block_exclusive_scan(mine, s_u32, &total);
+    for (uint32_t k = 0; k < per; ++k) {
+        const uint32_t i = i0 + k;
+        if (i >= kTopScan) break;
+        uint32_t name = 0xFFFFFFFFu;
+        if (i < n_nodes && nodes[i].left != 0u) {
+            if (j < K) { name = top_slots[j]; report[kReportRanks + j] = nodes[i].rank; }
+            ++j;
+        }
+        top_name[i] = name;
+    }
+    if (threadIdx.x == 0) {
+        const BuildNode root = nodes[0];
+        report[1] = __float_as_uint(root.lo.x); report[2] = __float_as_uint(root.lo.y); report[3] = __float_as_uint(root.lo.z);
+        report[4] = __float_as_uint(root.hi.x); report[5] = __float_as_uint(root.hi.y); report[6] = __float_as_uint(root.hi.z);
+        report[7] = min(total, K);
+    }
+}
+
+// One thread per leaf slot: PackLeafTri (scene_layout.h) of the triangle the new order puts there, last_in_leaf cleared -- emit_pair_records
+// sets it on every leaf's last slot.  The one gather of the call: neighbouring slots name scattered tri_orig records.
+__global__ void __launch_bounds__(256) emit_leaf_triangles(const uint32_t* __restrict__ idx, const float4* __restrict__ tri_orig, float4* __restrict__ tri_leaf,
+                                                           uint32_t leaf_base, uint32_t tri_base, uint32_t n, uint32_t* flags)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t t = idx[i];
+    if (t >= n) { atomicOr(flags, kFlagEmit); return; }
+    const float4* o = tri_orig + 3 * (size_t)(tri_base + t);
+    const float4 a = o[0], b = o[1], c = o[2];
+    const float e1x = b.x - a.x, e1y = b.y - a.y, e1z = b.z - a.z;            // ref: Primitives.cpp:9
+    const float e2x = c.x - a.x, e2y = c.y - a.y, e2z = c.z - a.z;            // ref: Primitives.cpp:10
+    float4* leaf = tri_leaf + 3 * (size_t)(leaf_base + i);
+    leaf[0] = make_float4(a.x, a.y, a.z, e1x);
+    leaf[1] = make_float4(e1y, e1z, e2x, e2y);
+    leaf[2] = make_float4(0.0f, e2z, __uint_as_float(t), __uint_as_float(0u));
+}
+
+__device__ inline uint32_t record_name(const BuildNode& n, uint32_t id, const uint32_t* __restrict__ top_name, uint32_t span_base)
+{
+    if (id < kTopScan) { const uint32_t slot = top_name[id]; if (slot != 0xFFFFFFFFu) return slot; }
+    return span_base + n.rank;
+}
+
+// One thread per node of the builder's array.  A leaf ends its slot range (last_in_leaf).  A splitting node writes its 64-byte record --
+// the two children's bounds straight from their BuildNodes, interleaved per component, and their traversal codes -- and its name into
+// the mesh's slice of refit_levels: the children of level L are level L + 1 and were allocated in pairs, so (left - 1) / 2 is the node's
+// place among the splitting nodes in level order, depth by depth (rebuild_layout.h: level_offsets).
+__global__ void __launch_bounds__(256) emit_pair_records(const BuildNode* __restrict__ nodes, uint32_t n_nodes, const uint32_t* __restrict__ top_name, uint32_t span_base,
+                                                         uint32_t span_room, uint32_t leaf_base, uint32_t n_tris, float4* __restrict__ node_pairs,
+                                                         float4* __restrict__ tri_leaf, uint32_t* __restrict__ levels, uint32_t* flags)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_nodes) return;
+    const BuildNode n = nodes[i];
+    if (n.left == 0u) {
+        if (n.count == 0u || (uint64_t)n.first + n.count > n_tris) { atomicOr(flags, kFlagEmit); return; }
+        reinterpret_cast<uint32_t*>(tri_leaf + 3 * (size_t)(leaf_base + n.first + n.count - 1u) + 2)[3] = 1u;
+        return;
+    }
+    if (n.left + 1u >= n_nodes || n.rank >= span_room) { atomicOr(flags, kFlagEmit); return; }
+    const BuildNode l = nodes[n.left], r = nodes[n.left + 1u];
+    if ((l.left != 0u && l.rank >= span_room) || (r.left != 0u && r.rank >= span_room)) { atomicOr(flags, kFlagEmit); return; }
+    const uint32_t name = record_name(n, i, top_name, span_base);
+    const uint32_t lc = l.left ? record_name(l, n.left, top_name, span_base) : (kLeafBit | (leaf_base + l.first));
+    const uint32_t rc = r.left ? record_name(r, n.left + 1u, top_name, span_base) : (kLeafBit | (leaf_base + r.first));
+    float4* rec = node_pairs + 4 * (size_t)name;
+    rec[0] = make_float4(l.lo.x, r.lo.x, l.lo.y, r.lo.y);                     // device_scene.h: node_pairs
+    rec[1] = make_float4(l.lo.z, r.lo.z, l.hi.x, r.hi.x);
+    rec[2] = make_float4(l.hi.y, r.hi.y, l.hi.z, r.hi.z);
+    rec[3] = make_float4(0.0f, 0.0f, __uint_as_float(lc), __uint_as_float(rc));
+    levels[(n.left - 1u) / 2u] = name;
+}
+
+// Morph targets in leaf-slot order (MorphBuffers): the rebuild permutes the slots.  from[i] = the old slot of the triangle now at slot i,
+// and the triangle's slot_of_tri entry moves to i; then every set's nine planes are gathered through `from` into a scratch and copied back.
+__global__ void __launch_bounds__(256) morph_slot_map(const uint32_t* __restrict__ idx, uint32_t* slot_of_tri, uint32_t* from, uint32_t n, uint32_t* flags)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t t = idx[i];
+    if (t >= n) { from[i] = i; atomicOr(flags, kFlagEmit); return; }
+    const uint32_t old = slot_of_tri[t];                      // every thread reads and writes its own triangle's entry only
+    if (old >= n) atomicOr(flags, kFlagEmit);
+    from[i] = old < n ? old : i;
+    slot_of_tri[t] = i;
+}
+__global__ void __launch_bounds__(256) morph_gather_set(const float2* __restrict__ set, const uint32_t* __restrict__ from, float2* __restrict__ out, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t s = from[i];
+#pragma unroll
+    for (uint32_t p = 0; p < 9u; ++p) out[(size_t)p * n + i] = set[(size_t)p * n + s];
+}
+
 }  // namespace
 
 float HostTriangleArea(const cgpt_triangle& t)                                // Heron, ref: Primitives.cpp:270-278 (also refit.hip)
@@ -927,102 +1072,74 @@ float HostTriangleArea(const cgpt_triangle& t)                                //
 
 using namespace cgpt;
 
-static int BuildOnDevice(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t n_tris, uint32_t build_option, const uint32_t* initial_tri_indices,
-                         cgpt_bvh_node* nodes_out, uint32_t* n_nodes_out, uint32_t* tri_indices_out, uint32_t* max_depth_out, float* total_area_out);
-
-extern "C" int cgpt_bvh_build_ex(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t n_tris, uint32_t build_option, const uint32_t* initial_tri_indices,
-                                 cgpt_bvh_node* nodes_out, uint32_t* n_nodes_out, uint32_t* tri_indices_out, uint32_t* max_depth_out, float* total_area_out)
-{
-    if (!ctx) return CGPT_ERR_INVALID;
-    cgpt_ctx* const first = GroupFirstMemberOrNull(ctx);                       // a multi-device context builds on its first device
-    cgpt_ctx* const target = first ? first : ctx;
-    const int rc = Guarded(target, "cgpt_bvh_build", [&] {                    // host vectors
-        return BuildOnDevice(target, triangles, n_tris, build_option, initial_tri_indices, nodes_out, n_nodes_out, tri_indices_out, max_depth_out, total_area_out);
-    });
-    return first ? GroupForwarded(ctx, rc) : rc;
-}
-
-extern "C" int cgpt_bvh_build(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t n_tris, cgpt_bvh_node* nodes_out, uint32_t* n_nodes_out,
-                              uint32_t* tri_indices_out, uint32_t* max_depth_out, float* total_area_out)
-{
-    return cgpt_bvh_build_ex(ctx, triangles, n_tris, CGPT_BUILD_SAH_SPLIT_INTERVALS, nullptr, nodes_out, n_nodes_out, tri_indices_out, max_depth_out, total_area_out);
-}
-
-static int BuildOnDevice(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t n_tris, uint32_t build_option, const uint32_t* initial_tri_indices,
-                         cgpt_bvh_node* nodes_out, uint32_t* n_nodes_out, uint32_t* tri_indices_out, uint32_t* max_depth_out, float* total_area_out)
-{
-    if (!triangles || n_tris == 0 || !nodes_out || !n_nodes_out || !tri_indices_out || !max_depth_out || !total_area_out)
-        return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: null argument or empty mesh");
-    if (n_tris > 0x3FFFFFFFu) return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: too many triangles");
-    if (build_option > CGPT_BUILD_SAH_BINNED) return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: unknown build option %u", build_option);
-    const bool binned = build_option == CGPT_BUILD_SAH_BINNED;
-    if (binned) {                                                             // its input domain (include/cpugpupt_abi.h): the bin index must stay defined
-        for (uint32_t i = 0; i < n_tris; ++i) {
-            const cgpt_vertex* const v[3] = { &triangles[i].v0, &triangles[i].v1, &triangles[i].v2 };
-            for (int k = 0; k < 3; ++k)
-                for (int a = 0; a < 3; ++a)
-                    if (!(fabsf(v[k]->pos[a]) <= 1e30f))
-                        return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: the binned build needs finite positions of magnitude <= 1e30 (triangle %u)", i);
-        }
-    }
-    if (initial_tri_indices) {                                                // a Rebuild's starting order must be a permutation: the kernels index with it
-        std::vector<uint8_t> seen(n_tris, 0);
-        for (uint32_t i = 0; i < n_tris; ++i) {
-            const uint32_t t = initial_tri_indices[i];
-            if (t >= n_tris || seen[t]) return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: initial_tri_indices[%u] = %u: not a permutation of 0..%u", i, t, n_tris - 1u);
-            seen[t] = 1;
-        }
-    }
-    hipStream_t stream = CtxStream(ctx);
-    if (hipSetDevice(CtxDevice(ctx)) != hipSuccess) return CtxFail(ctx, CGPT_ERR_HIP, "cgpt_bvh_build: hipSetDevice failed");
-
-    DevBuf<cgpt_triangle> d_tris; DevBuf<F3> d_lo, d_hi, d_c;
-    DevBuf<uint32_t> d_idx, d_scratch, d_sa, d_sb, d_counters;
-    DevBuf<BuildNode> d_nodes; DevBuf<cgpt_bvh_node> d_out;
-    DevBuf<WidePartial> d_partial; DevBuf<WideDecision> d_decision; DevBuf<uint32_t> d_piece_left, d_piece_front; DevBuf<WideChild> d_piece_child;
-    DevBuf<Bounds> d_cbounds; DevBuf<uint32_t> d_root_keys, d_gbins, d_piece_count; DevBuf<BinnedDecision> d_bdecision;
+// ---- the driver in three parts: the work arrays, the level loop with the renumbering passes, and an emit.  cgpt_bvh_build_ex emits the
+//      reference's node array to the host; cgpt_scene_rebuild_mesh (below) writes the device scene's own records instead ------------------
+struct BuildWork {
+    DevBuf<F3> lo, hi, c;
+    DevBuf<uint32_t> idx, scratch, sa, sb, counters;
+    DevBuf<BuildNode> nodes;
+    DevBuf<WidePartial> partial; DevBuf<WideDecision> decision; DevBuf<uint32_t> piece_left, piece_front; DevBuf<WideChild> piece_child;
+    DevBuf<Bounds> cbounds; DevBuf<uint32_t> root_keys, gbins, piece_count; DevBuf<BinnedDecision> bdecision;
+    BuildArrays A{};
     BinnedArrays Bn{};
+    uint32_t n_tris = 0, build_option = 0;
+    bool binned = false;
     uint32_t quarter_tris = 32;                                               // ... and one quarter wavefront per node
     uint32_t wave_tris = 2048;                                                // average triangles per node up to which a level runs one wavefront per node
     uint32_t piece_tris = 512;                                                // average triangles per piece below which a level goes to one workgroup per node
-    const uint32_t max_nodes = 2u * n_tris - 1u;
-    std::vector<uint32_t> level_first;     // breadth-first ranges of the levels
-    uint32_t counters[2] = { 0, 0 };
+    std::vector<uint32_t> level_first;                                        // breadth-first ranges of the levels; after the loop closed by n_nodes
+    uint32_t counters_h[2] = { 0, 0 };
     uint32_t n_nodes = 0;
-    BuildArrays A{};
-    HIP_TRY(ctx, d_tris.Alloc(n_tris));
-    HIP_TRY(ctx, d_lo.Alloc(n_tris));
-    HIP_TRY(ctx, d_hi.Alloc(n_tris));
-    HIP_TRY(ctx, d_c.Alloc(n_tris));
-    HIP_TRY(ctx, d_idx.Alloc(n_tris)); HIP_TRY(ctx, d_scratch.Alloc(n_tris));
-    if (!binned) { HIP_TRY(ctx, d_sa.Alloc(n_tris)); HIP_TRY(ctx, d_sb.Alloc(n_tris)); }
-    HIP_TRY(ctx, d_counters.Alloc(2));
-    HIP_TRY(ctx, d_nodes.Alloc(max_nodes));
-    HIP_TRY(ctx, d_out.Alloc(max_nodes));
-    HIP_TRY(ctx, d_piece_left.Alloc(kWideBlocks));
+};
+
+static int AllocBuildWork(cgpt_ctx* ctx, uint32_t n_tris, uint32_t build_option, BuildWork& w)
+{
+    w.n_tris = n_tris; w.build_option = build_option; w.binned = build_option == CGPT_BUILD_SAH_BINNED;
+    const bool binned = w.binned;
+    const uint32_t max_nodes = 2u * n_tris - 1u;
+    HIP_TRY(ctx, w.lo.Alloc(n_tris));
+    HIP_TRY(ctx, w.hi.Alloc(n_tris));
+    HIP_TRY(ctx, w.c.Alloc(n_tris));
+    HIP_TRY(ctx, w.idx.Alloc(n_tris)); HIP_TRY(ctx, w.scratch.Alloc(n_tris));
+    if (!binned) { HIP_TRY(ctx, w.sa.Alloc(n_tris)); HIP_TRY(ctx, w.sb.Alloc(n_tris)); }
+    HIP_TRY(ctx, w.counters.Alloc(2));
+    HIP_TRY(ctx, w.nodes.Alloc(max_nodes));
+    HIP_TRY(ctx, w.piece_left.Alloc(kWideBlocks));
     if (!binned) {
-        HIP_TRY(ctx, d_partial.Alloc((size_t)kWideBlocks * kCandidates));
-        HIP_TRY(ctx, d_decision.Alloc(kWideBlocks));
-        HIP_TRY(ctx, d_piece_front.Alloc(kWideBlocks));
-        HIP_TRY(ctx, d_piece_child.Alloc(kWideBlocks));
+        HIP_TRY(ctx, w.partial.Alloc((size_t)kWideBlocks * kCandidates));
+        HIP_TRY(ctx, w.decision.Alloc(kWideBlocks));
+        HIP_TRY(ctx, w.piece_front.Alloc(kWideBlocks));
+        HIP_TRY(ctx, w.piece_child.Alloc(kWideBlocks));
     } else {
-        HIP_TRY(ctx, d_cbounds.Alloc(max_nodes));
-        HIP_TRY(ctx, d_root_keys.Alloc(12));
-        HIP_TRY(ctx, d_gbins.Alloc((size_t)kWideBlocks * kNodeBinWords));
-        HIP_TRY(ctx, d_piece_count.Alloc((size_t)kWideBlocks * 3 * kBins));
-        HIP_TRY(ctx, d_bdecision.Alloc(kWideBlocks));
+        HIP_TRY(ctx, w.cbounds.Alloc(max_nodes));
+        HIP_TRY(ctx, w.root_keys.Alloc(12));
+        HIP_TRY(ctx, w.gbins.Alloc((size_t)kWideBlocks * kNodeBinWords));
+        HIP_TRY(ctx, w.piece_count.Alloc((size_t)kWideBlocks * 3 * kBins));
+        HIP_TRY(ctx, w.bdecision.Alloc(kWideBlocks));
     }
-    if (const char* e = getenv("CGPT_BVH_WAVE_TRIS")) wave_tris = (uint32_t)std::max(0l, strtol(e, nullptr, 10));     // tests: 0 = workgroups only
-    if (const char* e = getenv("CGPT_BVH_QUARTER_TRIS")) quarter_tris = (uint32_t)std::max(0l, strtol(e, nullptr, 10));
-    if (const char* e = getenv("CGPT_BVH_PIECE_TRIS")) piece_tris = (uint32_t)std::max(1l, strtol(e, nullptr, 10));   // tests: the wide path on small meshes
-    HIP_TRY(ctx, hipMemcpyAsync(d_tris.p, triangles, (size_t)n_tris * sizeof(cgpt_triangle), hipMemcpyHostToDevice, stream));
-    if (initial_tri_indices) HIP_TRY(ctx, hipMemcpyAsync(d_idx.p, initial_tri_indices, (size_t)n_tris * 4, hipMemcpyHostToDevice, stream));   // Rebuild: the current order
+    if (const char* e = getenv("CGPT_BVH_WAVE_TRIS")) w.wave_tris = (uint32_t)std::max(0l, strtol(e, nullptr, 10));     // tests: 0 = workgroups only
+    if (const char* e = getenv("CGPT_BVH_QUARTER_TRIS")) w.quarter_tris = (uint32_t)std::max(0l, strtol(e, nullptr, 10));
+    if (const char* e = getenv("CGPT_BVH_PIECE_TRIS")) w.piece_tris = (uint32_t)std::max(1l, strtol(e, nullptr, 10));   // tests: the wide path on small meshes
+    BuildArrays& A = w.A; BinnedArrays& Bn = w.Bn;
     A.naive = build_option == CGPT_BUILD_NAIVE_SPLIT ? 1u : 0u;
-    A.tri_lo = d_lo.p; A.tri_hi = d_hi.p; A.centroid = d_c.p; A.tri_indices = d_idx.p; A.scratch_idx = d_scratch.p; A.sel_a = d_sa.p; A.sel_b = d_sb.p;
-    A.nodes = d_nodes.p; A.counters = d_counters.p;
-    A.partial = d_partial.p; A.decision = d_decision.p; A.piece_left = d_piece_left.p; A.piece_front = d_piece_front.p; A.piece_child = d_piece_child.p;
-    hipLaunchKernelGGL(prepare_triangles, dim3((n_tris + 255u) / 256u), dim3(256), 0, stream, d_tris.p, n_tris, d_lo.p, d_hi.p, d_c.p, d_idx.p, initial_tri_indices ? 0u : 1u);
-    Bn.cbounds = d_cbounds.p; Bn.root_keys = d_root_keys.p; Bn.gbins = d_gbins.p; Bn.piece_count = d_piece_count.p; Bn.piece_left = d_piece_left.p; Bn.decision = d_bdecision.p;
+    A.tri_lo = w.lo.p; A.tri_hi = w.hi.p; A.centroid = w.c.p; A.tri_indices = w.idx.p; A.scratch_idx = w.scratch.p; A.sel_a = w.sa.p; A.sel_b = w.sb.p;
+    A.nodes = w.nodes.p; A.counters = w.counters.p;
+    A.partial = w.partial.p; A.decision = w.decision.p; A.piece_left = w.piece_left.p; A.piece_front = w.piece_front.p; A.piece_child = w.piece_child.p;
+    Bn.cbounds = w.cbounds.p; Bn.root_keys = w.root_keys.p; Bn.gbins = w.gbins.p; Bn.piece_count = w.piece_count.p; Bn.piece_left = w.piece_left.p; Bn.decision = w.bdecision.p;
+    return CGPT_OK;
+}
+
+// The root's bounds, the level loop and the renumbering passes over triangles prepared in w (bounds, centroids, starting order).
+static int RunBuildLevels(cgpt_ctx* ctx, BuildWork& w, hipStream_t stream)
+{
+    const uint32_t n_tris = w.n_tris, build_option = w.build_option;
+    const bool binned = w.binned;
+    const uint32_t quarter_tris = w.quarter_tris, wave_tris = w.wave_tris, piece_tris = w.piece_tris;
+    BuildArrays& A = w.A; BinnedArrays& Bn = w.Bn;
+    DevBuf<BuildNode>& d_nodes = w.nodes; DevBuf<uint32_t>& d_counters = w.counters; DevBuf<uint32_t>& d_root_keys = w.root_keys; DevBuf<uint32_t>& d_gbins = w.gbins;
+    std::vector<uint32_t>& level_first = w.level_first;
+    uint32_t (&counters)[2] = w.counters_h;
+    level_first.clear(); counters[0] = counters[1] = 0;
     if (binned) {
         HIP_TRY(ctx, hipMemsetAsync(d_root_keys.p, 0, 12 * 4, stream));
         hipLaunchKernelGGL(binned_root_fold, dim3(std::min(1024u, (n_tris + kBuildThreads - 1u) / kBuildThreads)), dim3(kBuildThreads), 0, stream, A, Bn, n_tris);
@@ -1088,7 +1205,8 @@ static int BuildOnDevice(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t
         count = counters[0] - first;
         if (level_first.size() > 4096) return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: tree deeper than 4096 levels");
     }
-    n_nodes = counters[0];
+    const uint32_t n_nodes = w.n_nodes = counters[0];
+    if (n_nodes == 0u || n_nodes > 2u * n_tris - 1u) return CtxFail(ctx, CGPT_ERR_HIP, "cgpt_bvh_build: the node counter reads %u for %u triangles", n_nodes, n_tris);
     level_first.push_back(n_nodes);
     // splitting-node counts bottom-up, preorder ranks and final ids top-down
     for (size_t l = level_first.size() - 1; l-- > 0;) {
@@ -1099,6 +1217,73 @@ static int BuildOnDevice(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t
         const uint32_t c = level_first[l + 1] - level_first[l];
         hipLaunchKernelGGL(assign_ids_level, dim3((c + 255u) / 256u), dim3(256), 0, stream, d_nodes.p, level_first[l], c);
     }
+    return CGPT_OK;
+}
+
+static int BuildOnDevice(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t n_tris, uint32_t build_option, const uint32_t* initial_tri_indices,
+                         cgpt_bvh_node* nodes_out, uint32_t* n_nodes_out, uint32_t* tri_indices_out, uint32_t* max_depth_out, float* total_area_out);
+
+extern "C" int cgpt_bvh_build_ex(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t n_tris, uint32_t build_option, const uint32_t* initial_tri_indices,
+                                 cgpt_bvh_node* nodes_out, uint32_t* n_nodes_out, uint32_t* tri_indices_out, uint32_t* max_depth_out, float* total_area_out)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    cgpt_ctx* const first = GroupFirstMemberOrNull(ctx);                       // a multi-device context builds on its first device
+    cgpt_ctx* const target = first ? first : ctx;
+    const int rc = Guarded(target, "cgpt_bvh_build", [&] {                    // host vectors
+        return BuildOnDevice(target, triangles, n_tris, build_option, initial_tri_indices, nodes_out, n_nodes_out, tri_indices_out, max_depth_out, total_area_out);
+    });
+    return first ? GroupForwarded(ctx, rc) : rc;
+}
+
+extern "C" int cgpt_bvh_build(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t n_tris, cgpt_bvh_node* nodes_out, uint32_t* n_nodes_out,
+                              uint32_t* tri_indices_out, uint32_t* max_depth_out, float* total_area_out)
+{
+    return cgpt_bvh_build_ex(ctx, triangles, n_tris, CGPT_BUILD_SAH_SPLIT_INTERVALS, nullptr, nodes_out, n_nodes_out, tri_indices_out, max_depth_out, total_area_out);
+}
+
+static int BuildOnDevice(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t n_tris, uint32_t build_option, const uint32_t* initial_tri_indices,
+                         cgpt_bvh_node* nodes_out, uint32_t* n_nodes_out, uint32_t* tri_indices_out, uint32_t* max_depth_out, float* total_area_out)
+{
+    if (!triangles || n_tris == 0 || !nodes_out || !n_nodes_out || !tri_indices_out || !max_depth_out || !total_area_out)
+        return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: null argument or empty mesh");
+    if (n_tris > 0x3FFFFFFFu) return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: too many triangles");
+    if (build_option > CGPT_BUILD_SAH_BINNED) return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: unknown build option %u", build_option);
+    const bool binned = build_option == CGPT_BUILD_SAH_BINNED;
+    if (binned) {                                                             // its input domain (include/cpugpupt_abi.h): the bin index must stay defined
+        for (uint32_t i = 0; i < n_tris; ++i) {
+            const cgpt_vertex* const v[3] = { &triangles[i].v0, &triangles[i].v1, &triangles[i].v2 };
+            for (int k = 0; k < 3; ++k)
+                for (int a = 0; a < 3; ++a)
+                    if (!(fabsf(v[k]->pos[a]) <= 1e30f))
+                        return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: the binned build needs finite positions of magnitude <= 1e30 (triangle %u)", i);
+        }
+    }
+    if (initial_tri_indices) {                                                // a Rebuild's starting order must be a permutation: the kernels index with it
+        std::vector<uint8_t> seen(n_tris, 0);
+        for (uint32_t i = 0; i < n_tris; ++i) {
+            const uint32_t t = initial_tri_indices[i];
+            if (t >= n_tris || seen[t]) return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_bvh_build: initial_tri_indices[%u] = %u: not a permutation of 0..%u", i, t, n_tris - 1u);
+            seen[t] = 1;
+        }
+    }
+    hipStream_t stream = CtxStream(ctx);
+    if (hipSetDevice(CtxDevice(ctx)) != hipSuccess) return CtxFail(ctx, CGPT_ERR_HIP, "cgpt_bvh_build: hipSetDevice failed");
+
+    DevBuf<cgpt_triangle> d_tris; DevBuf<cgpt_bvh_node> d_out;
+    BuildWork w;
+    int rc = AllocBuildWork(ctx, n_tris, build_option, w);
+    if (rc != CGPT_OK) return rc;
+    HIP_TRY(ctx, d_tris.Alloc(n_tris));
+    HIP_TRY(ctx, d_out.Alloc(2u * n_tris - 1u));
+    HIP_TRY(ctx, hipMemcpyAsync(d_tris.p, triangles, (size_t)n_tris * sizeof(cgpt_triangle), hipMemcpyHostToDevice, stream));
+    if (initial_tri_indices) HIP_TRY(ctx, hipMemcpyAsync(w.idx.p, initial_tri_indices, (size_t)n_tris * 4, hipMemcpyHostToDevice, stream));   // Rebuild: the current order
+    hipLaunchKernelGGL(prepare_triangles, dim3((n_tris + 255u) / 256u), dim3(256), 0, stream, d_tris.p, n_tris, w.lo.p, w.hi.p, w.c.p, w.idx.p, initial_tri_indices ? 0u : 1u);
+    rc = RunBuildLevels(ctx, w, stream);
+    if (rc != CGPT_OK) return rc;
+    const uint32_t n_nodes = w.n_nodes;
+    const std::vector<uint32_t>& level_first = w.level_first;
+    const uint32_t* const counters = w.counters_h;
+    DevBuf<BuildNode>& d_nodes = w.nodes; DevBuf<uint32_t>& d_idx = w.idx;
     hipLaunchKernelGGL(emit_nodes, dim3((n_nodes + 255u) / 256u), dim3(256), 0, stream, d_nodes.p, n_nodes, d_out.p);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(nodes_out, d_out.p, (size_t)n_nodes * sizeof(cgpt_bvh_node), hipMemcpyDeviceToHost, stream));
@@ -1110,4 +1295,159 @@ static int BuildOnDevice(cgpt_ctx* ctx, const cgpt_triangle* triangles, uint32_t
     for (uint32_t i = 0; i < n_tris; ++i) area += HostTriangleArea(triangles[i]);
     *total_area_out = area;
     return CGPT_OK;
+}
+
+// ---- cgpt_scene_rebuild_mesh -----------------------------------------------------------------------------------------
+// The three parts above around the device scene: prepare_from_scene instead of an upload, the level loop, and the emit kernels instead of
+// the host emit.  Everything up to the plan runs in scratch buffers; the scene is written after the last refusal.
+static int RebuildLost(cgpt_ctx* ctx, const char* what, hipError_t e)        // refit.hip: SceneLost
+{
+    ctx->has_scene = false;
+    return CtxFail(ctx, CGPT_ERR_HIP, "%s failed: %s (the device scene is dropped; upload it again)", what, hipGetErrorString(e));
+}
+#define REBUILD_HIP_WRITING(ctx, expr)                                                                                  \
+    do {                                                                                                                \
+        hipError_t e_ = (expr);                                                                                         \
+        if (e_ != hipSuccess) return RebuildLost((ctx), #expr, e_);                                                     \
+    } while (0)
+
+static int RebuildMesh(cgpt_ctx* ctx, uint32_t obj_index, uint32_t build_option, uint32_t* n_nodes_out, uint32_t* max_depth_out)
+{
+    if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
+    if (obj_index >= ctx->h_objects.size()) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u out of range (%zu objects)", obj_index, ctx->h_objects.size());
+    const DevObject d = ctx->h_objects[obj_index];
+    if (d.kind != CGPT_OBJECT_MESH) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u is no mesh: only a mesh has a tree to rebuild", obj_index);
+    if (build_option > CGPT_BUILD_SAH_BINNED) return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_scene_rebuild_mesh: unknown build option %u", build_option);
+    if (build_option == CGPT_BUILD_SAH_SPLIT_PRIMITIVES)
+        return CtxFail(ctx, CGPT_ERR_UNSUPPORTED, "cgpt_scene_rebuild_mesh: SAH-split-primitives never splits (SURVEY A-5): nothing to rebuild with");
+    const RefitObject old = ctx->refit_objects[obj_index];
+    const uint32_t n_tris = old.tri_count, tri_base = d.tri_base, leaf_base = old.leaf_base;
+    if (n_tris == 0u || n_tris != d.n_tris) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u: the layout's triangle counts disagree", obj_index);
+    hipStream_t stream = ctx->stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+
+    // ---- in scratch: the build ----
+    BuildWork w;
+    int rc = AllocBuildWork(ctx, n_tris, build_option, w);
+    if (rc != CGPT_OK) return rc;
+    DevBuf<uint32_t> d_report, d_top_name, d_top_slots;
+    HIP_TRY(ctx, d_report.Alloc(kReportRanks + kTopRecords));
+    HIP_TRY(ctx, d_top_name.Alloc(kTopScan));
+    HIP_TRY(ctx, d_top_slots.Alloc(kTopRecords));
+    HIP_TRY(ctx, hipMemsetAsync(d_report.p, 0, sizeof(uint32_t) * (kReportRanks + kTopRecords), stream));
+    const dim3 per_tri((n_tris + 255u) / 256u), block(256);
+    hipLaunchKernelGGL(prepare_from_scene, per_tri, block, 0, stream, ctx->sb.tri_leaf.p, ctx->sb.tri_orig.p, leaf_base, tri_base, n_tris, w.lo.p, w.hi.p, w.c.p, w.idx.p, d_report.p);
+    HIP_TRY(ctx, hipGetLastError());
+    uint32_t flags = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&flags, d_report.p, sizeof(flags), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));                               // before a level kernel sees a position outside its domain
+    if (flags & kFlagSlot) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u: a leaf slot names a triangle outside the mesh", obj_index);
+    if (w.binned && (flags & kFlagDomain))
+        return CtxFail(ctx, CGPT_ERR_INVALID, "cgpt_scene_rebuild_mesh: the binned build needs finite positions of magnitude <= 1e30 (object %u)", obj_index);
+    rc = RunBuildLevels(ctx, w, stream);
+    if (rc != CGPT_OK) return rc;
+
+    // ---- on the host: where the records go (rebuild_layout.h) ----
+    RebuildPlan plan;
+    std::string why;
+    rc = PlanRebuild(ctx->h_objects, ctx->refit_objects, ctx->record_perm, ctx->mesh_group, ctx->scene.n_top_records, ctx->footprint.n_pair_records, ctx->n_refit_levels,
+                     obj_index, w.level_first, plan, why);
+    if (rc != CGPT_OK) return CtxFail(ctx, rc, "%s", why.c_str());
+    const uint32_t K = (uint32_t)plan.top_slots.size(), room = n_tris - 1u;
+    if (K > kTopRecords) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u owns %u top records", obj_index, K);
+    if (K) HIP_TRY(ctx, hipMemcpyAsync(d_top_slots.p, plan.top_slots.data(), sizeof(uint32_t) * K, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(assign_top_slots, dim3(1), dim3(kBuildThreads), 0, stream, w.nodes.p, w.n_nodes, d_top_slots.p, K, d_top_name.p, d_report.p);
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<uint32_t> report(kReportRanks + kTopRecords);
+    HIP_TRY(ctx, hipMemcpyAsync(report.data(), d_report.p, sizeof(uint32_t) * report.size(), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    const uint32_t n_ranks = report[7];
+    const uint32_t* const ranks = report.data() + kReportRanks;
+    if (n_ranks > K || !CheckTopRanks(plan, ranks, n_ranks)) return CtxFail(ctx, CGPT_ERR_HIP, "object %u: the builder's ranks do not fit the plan", obj_index);
+
+    // the top-level box: the new root's bounds, or TriangleBounds for a root that stays a leaf (LayoutScene)
+    TopLevelState top = ctx->top_state;
+    float* box = top.local_box.data() + 6 * (size_t)obj_index;
+    if (plan.n_pairs == 0u) {
+        uint32_t fold[8];
+        HIP_TRY(ctx, FoldObjectBoxToHost(ctx, tri_base, n_tris, fold));
+        if (fold[7] != 0u) UnboundedBox(box); else memcpy(box, fold + 1, 24);
+    } else {
+        memcpy(box, report.data() + 1, 24);
+    }
+    for (const uint32_t j : plan.members)
+        if (j != obj_index) memcpy(top.local_box.data() + 6 * (size_t)j, box, 24);
+
+    // the room: grown copies of the two record tables at a first rebuild, the scratch of the morph targets' permutation
+    DevBuf<float4> grown_pairs; DevBuf<uint32_t> grown_levels;
+    if (plan.grow && room != 0u) {
+        HIP_TRY(ctx, grown_pairs.Alloc(4 * (size_t)plan.n_pair_records));
+        HIP_TRY(ctx, grown_levels.Alloc(plan.n_refit_levels));
+        if (ctx->footprint.n_pair_records) HIP_TRY(ctx, hipMemcpyAsync(grown_pairs.p, ctx->sb.node_pairs.p, sizeof(float4) * 4 * (size_t)ctx->footprint.n_pair_records, hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(ctx, hipMemsetAsync(grown_pairs.p + 4 * (size_t)ctx->footprint.n_pair_records, 0, sizeof(float4) * 4 * (size_t)room, stream));
+        if (ctx->n_refit_levels) HIP_TRY(ctx, hipMemcpyAsync(grown_levels.p, ctx->sb.refit_levels.p, sizeof(uint32_t) * ctx->n_refit_levels, hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(ctx, hipMemsetAsync(grown_levels.p + ctx->n_refit_levels, 0, sizeof(uint32_t) * room, stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+    }
+    std::vector<uint32_t> leaf_morphs;                                         // the members whose targets are stored in leaf-slot order
+    for (const uint32_t j : plan.members)
+        if (j < ctx->morphs.size() && ctx->morphs[j].n_targets != 0u && ctx->morphs[j].leaf_order != 0u) leaf_morphs.push_back(j);
+    DevBuf<float2> d_planes; DevBuf<uint32_t> d_from;
+    if (!leaf_morphs.empty()) { HIP_TRY(ctx, d_planes.Alloc(9 * (size_t)n_tris)); HIP_TRY(ctx, d_from.Alloc(n_tris)); }
+    ctx->record_perm.reserve(plan.n_record_perm);                              // may throw: before the first write (the slice is then written in place)
+    std::vector<DevObject> new_objects = ctx->h_objects;                       // a word and a RefitObject an object: not by the record
+    std::vector<RefitObject> new_refit = ctx->refit_objects;
+    ApplyRebuildObjects(plan, RebuildRootCode(plan, ranks, n_ranks), new_objects, new_refit);
+
+    // ---- from here on the scene changes ----
+    ctx->scene_generation++; ctx->shape_generation++;                          // as a refit: the guides are stale and the temporal history is dropped
+    if (plan.grow && room != 0u) {
+        const uint64_t before = sizeof(float4) * (uint64_t)ctx->sb.node_pairs.n + sizeof(uint32_t) * (uint64_t)ctx->sb.refit_levels.n;
+        ctx->sb.node_pairs = std::move(grown_pairs); ctx->sb.refit_levels = std::move(grown_levels);
+        ctx->scene.node_pairs = ctx->sb.node_pairs.p;
+        ctx->footprint.device_bytes += sizeof(float4) * (uint64_t)ctx->sb.node_pairs.n + sizeof(uint32_t) * (uint64_t)ctx->sb.refit_levels.n - before;
+    }
+    ctx->footprint.n_pair_records = plan.n_pair_records; ctx->n_refit_levels = plan.n_refit_levels;
+    hipLaunchKernelGGL(emit_leaf_triangles, per_tri, block, 0, stream, w.idx.p, ctx->sb.tri_orig.p, ctx->sb.tri_leaf.p, leaf_base, tri_base, n_tris, d_report.p);
+    REBUILD_HIP_WRITING(ctx, hipGetLastError());
+    hipLaunchKernelGGL(emit_pair_records, dim3((w.n_nodes + 255u) / 256u), block, 0, stream, w.nodes.p, w.n_nodes, d_top_name.p, plan.refit.span_base, room, leaf_base, n_tris,
+                       ctx->sb.node_pairs.p, ctx->sb.tri_leaf.p, ctx->sb.refit_levels.p + plan.refit.level_begin, d_report.p);
+    REBUILD_HIP_WRITING(ctx, hipGetLastError());
+    for (const uint32_t j : leaf_morphs) {
+        MorphBuffers& mb = ctx->morphs[j];
+        hipLaunchKernelGGL(morph_slot_map, per_tri, block, 0, stream, w.idx.p, mb.slot_of_tri.p, d_from.p, n_tris, d_report.p);
+        REBUILD_HIP_WRITING(ctx, hipGetLastError());
+        for (uint32_t s = 0; s <= mb.n_targets; ++s) {                         // one set of nine planes at a time through the scratch
+            float2* set = mb.data.p + 9 * (size_t)n_tris * s;
+            hipLaunchKernelGGL(morph_gather_set, per_tri, block, 0, stream, set, d_from.p, d_planes.p, n_tris);
+            REBUILD_HIP_WRITING(ctx, hipGetLastError());
+            REBUILD_HIP_WRITING(ctx, hipMemcpyAsync(set, d_planes.p, sizeof(float2) * 9 * (size_t)n_tris, hipMemcpyDeviceToDevice, stream));
+        }
+    }
+    for (const uint32_t j : plan.members) {                                    // every placement of the copy: its root code, where a kernel reads it
+        REBUILD_HIP_WRITING(ctx, hipMemcpyAsync(&ctx->sb.objects.p[j].root_code, &new_objects[j].root_code, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        REBUILD_HIP_WRITING(ctx, hipMemcpyAsync(reinterpret_cast<uint32_t*>(ctx->sb.obj_trace.p + 2 * (size_t)j) + 1, &new_objects[j].root_code, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    }
+    REBUILD_HIP_WRITING(ctx, hipMemcpyAsync(&flags, d_report.p, sizeof(flags), hipMemcpyDeviceToHost, stream));
+    REBUILD_HIP_WRITING(ctx, hipStreamSynchronize(stream));
+    if (flags & kFlagEmit) {                                                   // an emit kernel skipped a write: the tree on the device is not whole
+        ctx->has_scene = false;
+        return CtxFail(ctx, CGPT_ERR_HIP, "cgpt_scene_rebuild_mesh: object %u: the builder's node array is inconsistent (the device scene is dropped; upload it again)", obj_index);
+    }
+    ctx->h_objects.swap(new_objects); ctx->refit_objects.swap(new_refit);
+    ApplyRebuildPerm(plan, ranks, n_ranks, ctx->record_perm);                  // the one host pass over the mesh's own records: n_pairs names
+    ctx->scene.stack_depth = plan.stack_depth;
+    REBUILD_HIP_WRITING(ctx, WriteTopLevel(ctx, ctx->h_objects, top));
+    ctx->top_state.local_box.swap(top.local_box);
+    if (n_nodes_out) *n_nodes_out = plan.n_nodes;
+    if (max_depth_out) *max_depth_out = plan.max_depth;
+    return CGPT_OK;
+}
+
+extern "C" int cgpt_scene_rebuild_mesh(cgpt_ctx* ctx, uint32_t obj_index, uint32_t build_option, uint32_t* n_nodes_out, uint32_t* max_depth_out)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupRebuildMesh(ctx, obj_index, build_option, n_nodes_out, max_depth_out); });
+    return Guarded(ctx, __func__, [&] { return RebuildMesh(ctx, obj_index, build_option, n_nodes_out, max_depth_out); });   // bumps the generations once the call is accepted
 }

@@ -459,6 +459,7 @@ int SceneInstall(cgpt_ctx* ctx, const SceneLayout& layout)
     ctx->h_lights = layout.lights;                                             // FreeScene cleared the features: an upload resets every roughness, smooth-normal flag and transform (LayoutScene writes 0 and the identity)
     ctx->top_state = layout.top_state;
     ctx->mesh_group = layout.mesh_group;
+    ctx->n_refit_levels = (uint32_t)layout.refit_levels.size();
     HIP_TRY(ctx, WriteTopLevel(ctx, ctx->h_objects, ctx->top_state));          // the mode is context state: an upload keeps it
 
     cgpt_scene_footprint& fp = ctx->footprint;

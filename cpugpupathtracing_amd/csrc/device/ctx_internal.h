@@ -171,9 +171,11 @@ struct cgpt_ctx {
     std::vector<uint32_t> record_perm;            // record index in the reference's depth-first order -> index in node_pairs
     // mesh instancing (cgpt_scene_upload_instanced): SceneLayout::mesh_group of the installed layout -- the objects that share object i's
     // one device copy are those with mesh_group[j] == mesh_group[i]; the identity after cgpt_scene_upload -- and what
-    // cgpt_get_scene_footprint reports, filled by SceneInstall (no edit changes it)
+    // cgpt_get_scene_footprint reports, filled by SceneInstall (of the edits only a mesh's first cgpt_scene_rebuild_mesh changes it);
+    // n_refit_levels: the entries of sb.refit_levels in use (an empty table still has one element of room)
     std::vector<uint32_t> mesh_group;
     cgpt_scene_footprint footprint{};
+    uint32_t n_refit_levels = 0;
     // skinning (cgpt_scene_set_skin): per object, empty or as long as h_objects; cleared with the scene.  skin_joints_lds is the
     // cgpt_set_tuning knob "skin_joints_lds": 1 (default) the skin kernel stages the joint matrices in LDS, 0 it reads them through the
     // vector cache (same results; DESIGN.md 5.26 has both timings)
@@ -326,6 +328,7 @@ int GroupSetMorphTargets(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle*
 int GroupMorphMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* weights, uint32_t n_targets);
 int GroupClearMorphTargets(cgpt_ctx* ctx, uint32_t obj_index);
 int GroupPoseObjects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_poses);
+int GroupRebuildMesh(cgpt_ctx* ctx, uint32_t obj_index, uint32_t build_option, uint32_t* n_nodes_out, uint32_t* max_depth_out);
 int GroupRender(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p);
 int GroupResetAccumulator(cgpt_ctx* ctx);
 int GroupReadAccumulator(cgpt_ctx* ctx, float* dst, size_t n_floats);
@@ -346,6 +349,9 @@ void GroupFrameInfo(cgpt_ctx* ctx, uint32_t* width, uint32_t* height, uint32_t* 
 int GroupGatherUncounted(cgpt_ctx* ctx, const float4** frame);
 
 std::vector<uint2> ActiveTable(const float* weights, uint32_t n_targets);   // refit.hip: a pose's nonzero weights {target, bits(weight)}, ascending
+// refit.hip: TriangleBounds of an object's n triangles as tri_orig holds them, folded on the device: out = {-, lo.xyz, hi.xyz, 1 where a position is
+// not finite} (fold_object_box); the caller has selected the device
+hipError_t FoldObjectBoxToHost(cgpt_ctx* ctx, uint32_t tri_base, uint32_t n_tris, uint32_t out[8]);
 void DenoiseFree(cgpt_ctx* ctx);               // denoise.hip: the guide cache and filter buffers of a one-device context
 }  // namespace cgpt
 

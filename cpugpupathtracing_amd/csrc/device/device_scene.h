@@ -58,7 +58,9 @@
 // record order: a child-pair record's index is only a name (the codes inside the records and the root codes are the only
 // references to it), so the upload renumbers them: records [0, n_top_records) are the top levels of all meshes' trees in
 // breadth-first order -- the part of the tree every ray walks; the trace kernel keeps a copy of them in LDS -- and the rest
-// follow in the reference's depth-first allocation order (a parent next to its left subtree).
+// follow in the reference's depth-first allocation order (a parent next to its left subtree).  A mesh that cgpt_scene_rebuild_mesh has
+// rebuilt keeps the top records it had and holds the others in a span of n_tris - 1 records at the end of the array, by preorder rank
+// (rebuild_layout.h).
 // Leaf-triangle records: the triangles of SMALL meshes (at most kSmallMeshTris triangles each, kLdsTrisMax in total -- the ground quad
 // of the reference scene, ref: Main.cpp:789-800, whose two triangles every ray of the scene tests; a triangle object counts as a
 // one-triangle mesh) come first, records [0, n_small_tris); the voted trace kernels read those from an LDS copy, which takes two of

@@ -407,6 +407,12 @@ int GroupPoseObjects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_poses)
     return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_pose_objects(m, poses, n_poses); });
 }
 
+// every member rebuilds its own copy: the builder is deterministic, so the trees stay equal (the record names may differ, and are no one's business)
+int GroupRebuildMesh(cgpt_ctx* ctx, uint32_t obj_index, uint32_t build_option, uint32_t* n_nodes_out, uint32_t* max_depth_out)
+{
+    return GroupEdit(ctx, [&](cgpt_ctx* m, bool first) { return cgpt_scene_rebuild_mesh(m, obj_index, build_option, first ? n_nodes_out : nullptr, first ? max_depth_out : nullptr); });
+}
+
 int GroupUpdateRoughness(cgpt_ctx* ctx, const float* roughness, uint32_t n)
 {
     return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_update_roughness(m, roughness, n); });

@@ -1043,24 +1043,37 @@ int ExportBvh(cgpt_ctx* ctx, uint32_t obj_index, cgpt_bvh_node* nodes_out, uint3
     if (n_nodes != ro.node_count) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u has %u nodes, got room for %u", obj_index, ro.node_count, n_nodes);
     const uint32_t n_pairs = ro.node_count / 2, n_tris = ro.tri_count;
 
-    // where the records are now: the renumbering put the top ones at the front, the rest keep their depth-first order
+    // where the records are now: the renumbering put the top ones at the front, the rest keep their depth-first order -- or, after a
+    // cgpt_scene_rebuild_mesh, sit in the mesh's span at the end of the array.  Two ranges are read: the mesh's names below n_top_records
+    // and its others, so that a rebuilt mesh's export does not copy every record that lies between the two
     std::vector<uint32_t> stored(n_pairs);
-    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+    struct Range { uint32_t lo = 0xFFFFFFFFu, hi = 0; std::vector<float4> rec; std::vector<uint32_t> pair_of; };
+    Range range[2];                                                           // [0] names below n_top_records, [1] the others
+    const uint32_t n_top = ctx->scene.n_top_records;
     for (uint32_t k = 0; k < n_pairs; ++k) {
-        const uint32_t r = ro.pair_base + k;
-        stored[k] = ctx->record_perm[r];
-        lo = std::min(lo, stored[k]); hi = std::max(hi, stored[k]);
+        stored[k] = ctx->record_perm[ro.pair_base + k];
+        Range& g = range[stored[k] < n_top ? 0 : 1];
+        g.lo = std::min(g.lo, stored[k]); g.hi = std::max(g.hi, stored[k]);
     }
-    std::vector<float4> span(n_pairs ? 4 * (size_t)(hi - lo + 1) : 0);
+    for (Range& g : range)
+        if (g.lo <= g.hi) { g.rec.resize(4 * (size_t)(g.hi - g.lo + 1)); g.pair_of.assign(g.hi - g.lo + 1, 0xFFFFFFFFu); }   // stored record -> depth-first pair index k (nodes 2k+1, 2k+2)
+    for (uint32_t k = 0; k < n_pairs; ++k) { Range& g = range[stored[k] < n_top ? 0 : 1]; g.pair_of[stored[k] - g.lo] = k; }
     std::vector<float4> leaf_tail(n_tris);                                    // {pad, e2.z, tri_idx, last_in_leaf} of every leaf slot
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (n_pairs) HIP_TRY(ctx, hipMemcpy(span.data(), ctx->sb.node_pairs.p + 4 * (size_t)lo, span.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    for (Range& g : range)
+        if (!g.rec.empty()) HIP_TRY(ctx, hipMemcpy(g.rec.data(), ctx->sb.node_pairs.p + 4 * (size_t)g.lo, g.rec.size() * sizeof(float4), hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemcpy2D(leaf_tail.data(), sizeof(float4), ctx->sb.tri_leaf.p + 3 * (size_t)ro.leaf_base + 2, 3 * sizeof(float4),
                                sizeof(float4), n_tris, hipMemcpyDeviceToHost));
+    const auto record_of = [&](uint32_t name) -> const float4* {             // a stored record's copy, null for a name outside both ranges
+        const Range& g = range[name < n_top ? 0 : 1];
+        return g.rec.empty() || name < g.lo || name > g.hi ? nullptr : g.rec.data() + 4 * (size_t)(name - g.lo);
+    };
+    const auto pair_index = [&](uint32_t name) -> uint32_t {
+        const Range& g = range[name < n_top ? 0 : 1];
+        return g.rec.empty() || name < g.lo || name > g.hi ? 0xFFFFFFFFu : g.pair_of[name - g.lo];
+    };
 
-    std::vector<uint32_t> pair_of(n_pairs ? hi - lo + 1 : 0, 0xFFFFFFFFu);    // stored record -> depth-first pair index k (nodes 2k+1, 2k+2)
-    for (uint32_t k = 0; k < n_pairs; ++k) pair_of[stored[k] - lo] = k;
     auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
     auto words = [&](uint32_t code, cgpt_bvh_node& out) -> bool {            // {left_first, prim_count} behind a traversal code
         if (code & kLeafBit) {
@@ -1071,15 +1084,15 @@ int ExportBvh(cgpt_ctx* ctx, uint32_t obj_index, cgpt_bvh_node* nodes_out, uint3
             out.left_first = first; out.prim_count = last - first + 1;
             return true;
         }
-        if (code < lo || code > hi || pair_of[code - lo] == 0xFFFFFFFFu) return false;
-        out.left_first = 2 * pair_of[code - lo] + 1; out.prim_count = 0;
+        if (pair_index(code) == 0xFFFFFFFFu) return false;
+        out.left_first = 2 * pair_index(code) + 1; out.prim_count = 0;
         return true;
     };
     auto set_bounds = [](cgpt_bvh_node& n, float x0, float y0, float z0, float x1, float y1, float z1) {
         n.aabb_min[0] = x0; n.aabb_min[1] = y0; n.aabb_min[2] = z0; n.aabb_max[0] = x1; n.aabb_max[1] = y1; n.aabb_max[2] = z1;
     };
     for (uint32_t k = 0; k < n_pairs; ++k) {
-        const float4* rec = span.data() + 4 * (size_t)(stored[k] - lo);
+        const float4* rec = record_of(stored[k]);
         cgpt_bvh_node& l = nodes_out[2 * k + 1];
         cgpt_bvh_node& r = nodes_out[2 * k + 2];
         set_bounds(l, rec[0].x, rec[0].z, rec[1].x, rec[1].z, rec[2].x, rec[2].z);
@@ -1102,7 +1115,7 @@ int ExportBvh(cgpt_ctx* ctx, uint32_t obj_index, cgpt_bvh_node* nodes_out, uint3
         }
         set_bounds(root, b[0], b[1], b[2], b[3], b[4], b[5]);
     } else {                                                                  // the union of the root record's two sides
-        const float4* rec = span.data() + 4 * (size_t)(d.root_code - lo);
+        const float4* rec = record_of(d.root_code);                            // words() accepted the root: the name lies in a range
         set_bounds(root, min_std(rec[0].x, rec[0].y), min_std(rec[0].z, rec[0].w), min_std(rec[1].x, rec[1].y),
                    max_std(rec[1].z, rec[1].w), max_std(rec[2].x, rec[2].y), max_std(rec[2].z, rec[2].w));
     }
@@ -1141,6 +1154,19 @@ int UpdatePrimitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_object* obj)
 }
 
 }  // namespace
+
+hipError_t FoldObjectBoxToHost(cgpt_ctx* ctx, uint32_t tri_base, uint32_t n_tris, uint32_t out[8])
+{
+    hipError_t e = hipStreamSynchronize(ctx->stream);                          // before the scratch may be replaced
+    if (e == hipSuccess) e = ctx->sb.skin_scratch.Grow(kSkinScratchWords);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fold_object_box, dim3(1), dim3(kRefitThreads), 0, ctx->stream, ctx->sb.tri_orig.p, tri_base, n_tris, ctx->sb.skin_scratch.p);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = hipMemcpy(out, ctx->sb.skin_scratch.p, sizeof(uint32_t) * kSkinScratchWords, hipMemcpyDeviceToHost);
+    return e;
+}
+
 }  // namespace cgpt
 
 using namespace cgpt;

@@ -21,7 +21,11 @@ struct RefitObject {
     uint32_t pair_base = 0;                    // first child-pair record of the object before the renumbering (index into record_perm)
     uint32_t level_begin = 0;                  // first entry of the object's records in refit_levels ...
     std::vector<uint32_t> level_offsets;       // ... records of depth d at [level_begin + level_offsets[d], level_begin + level_offsets[d + 1])
+    // cgpt_scene_rebuild_mesh (rebuild_layout.h): the first record of the span the mesh's first rebuild gave it at the end of node_pairs,
+    // with room for tri_count - 1 records (as have its slices of refit_levels and record_perm from then on); kNoSpan: as uploaded
+    uint32_t span_base = 0xFFFFFFFFu;
 };
+static constexpr uint32_t kNoSpan = 0xFFFFFFFFu;
 
 // What the boxes of the top-level tree (cgpt_set_top_level) are computed from, kept current on the host by every edit
 // that moves a box: per object the object-space box of a mesh or triangle object (the root node's bounds; the min / max of the vertex

@@ -55,6 +55,7 @@ class Renderer:
         self.is_group = len(devices) > 1 or bool(flags & N.CTX_FORCE_COLLECTIVE)
         self.scene: Optional[Scene] = None
         self._node_counts = []
+        self._copy_of = []
         self.width = self.height = 0
         self.rows: Tuple[int, int] = (0, 0)
         self.interleave: Optional[Tuple[int, int, int]] = None
@@ -125,6 +126,9 @@ class Renderer:
         self._glossy = self._rough_glass = self._smooth = self._transformed = False   # the upload reset every roughness, flag and transform
         self.scene = scene
         self._node_counts = [desc.objects[k].node_count for k in range(desc.n_objects)]   # the uploaded trees (export_bvh)
+        # the objects that share a device copy (rebuild_mesh): the same four slice words under an instanced upload, else every object alone
+        slices = [(o.kind, o.node_offset, o.node_count, o.tri_offset, o.tri_count) for o in (desc.objects[k] for k in range(desc.n_objects))]
+        self._copy_of = [slices.index(x) if instanced and x[0] == N.OBJECT_MESH else k for k, x in enumerate(slices)]
         rough = scene.roughness(desc.n_materials)
         if rough.any():
             self.update_roughness(rough)
@@ -254,6 +258,19 @@ class Renderer:
                                0 if w is None else w.size, None if w is None else w.ctypes.data_as(C.POINTER(C.c_float))))
         poses = (N.Pose * max(1, len(rows)))(*rows)
         self._check(self.L.cgpt_scene_pose_objects(self._ctx, poses, len(rows)))
+
+    def rebuild_mesh(self, obj_index: int, build_option: int = N.BUILD_SAH_BINNED):
+        """cgpt_scene_rebuild_mesh: splits the tree of uploaded mesh `obj_index` again, in place on the device, over the triangles its
+        copy holds now (after refits, skins, morphs) and from its current leaf order -- what Scene.rebuild_bvh(obj_index, build_option)
+        does on the host, without the triangles leaving the device.  Skins, morph targets, transforms, materials and
+        total_area are kept.  Returns (n_nodes, max_depth) of the new tree; export_bvh follows.  Only the device copy changes.  Call
+        reset_accumulator() before the next frame."""
+        n_nodes, depth = C.c_uint32(), C.c_uint32()
+        self._check(self.L.cgpt_scene_rebuild_mesh(self._ctx, obj_index, int(build_option), C.byref(n_nodes), C.byref(depth)))
+        for k in range(len(self._node_counts)):                          # every placement of the copy shows the new tree
+            if self._copy_of[k] == self._copy_of[obj_index]:
+                self._node_counts[k] = n_nodes.value
+        return n_nodes.value, depth.value
 
     def export_bvh(self, obj_index: int) -> np.ndarray:
         """The device's tree of mesh `obj_index` as it is now (after refits): nodes[n,8] uint32 words in the reference's 32-byte layout

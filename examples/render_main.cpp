@@ -4,7 +4,7 @@
 //
 //   g++ -std=c++17 -Iinclude -Icpugpupathtracing_amd/csrc/host examples/render_main.cpp
 //       -Lcpugpupathtracing_amd/lib -lcpugpupt -Wl,-rpath,$PWD/cpugpupathtracing_amd/lib -o render_main   (one command line)
-//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--spin DEG] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [--bend DEG] [--bulge W] [--crowd N] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
+//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--spin DEG] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [--bend DEG] [--bulge W] [--crowd N] [--rebuild [naive|intervals|binned]] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
 // --gpus N: ONE context over the first N GPUs of the node (cgpt_ctx_create with n_devices = N): every frame is spread over them in
 // interleaved row bands and the read-back gathers the float4 bands with one RCCL exchange over xGMI; the loop below does not
 // change.  --collective: take that code path with N = 1 too (what a one-GPU box can test).
@@ -59,6 +59,10 @@
 // --bulge W, its morph target), bent by an angle of its own: copy k by DEG (k + 1) / N degrees a frame (DEG from --bend, 10 without it).  All of
 // them are posed by ONE call a frame (cgpt_scene_pose_objects): the launches do not grow with N.  Frames and the temporal
 // call as for --bend (crowd_NN_*.ppm).
+// --rebuild [OPTION]: with --bend / --bulge / --crowd, every posed mesh's tree is split again in place on the device after each frame's pose
+// (cgpt_scene_rebuild_mesh), with the binned builder unless OPTION says otherwise: the refit keeps a tree that was split
+// for the bind pose, and after a large bend its boxes overlap.  The triangles never leave the device.  A rebuild drops the temporal
+// history, as a refit does.
 // move_at > 0 scripts the input half of Update(dt) (ref: Main.cpp:277-297, Camera::Update :104-131): after that many samples the
 // camera is translated by (right, up, forward) as the A/D, Space/Shift, W/S keys would, the view changes, and the accumulator
 // is reset (ref: ResetAccumulator, Main.cpp:238-243) before the remaining samples are rendered from the new position.
@@ -86,6 +90,7 @@ using namespace cgpt;
 int main(int argc, char** argv)
 {
     int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool spin = false; float spin_deg = 0.0f; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false; uint32_t n_instances = 0; bool bend = false; float bend_deg = 0.0f; bool bulge = false; float bulge_w = 0.0f; uint32_t crowd = 0;
+    bool rebuild = false; uint32_t rebuild_option = CGPT_BUILD_SAH_BINNED;
     bool has_transform = false; float mesh_transform[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
     MeshBVH::BuildOption bvh_option = MeshBVH::BuildOption_SAHSplitIntervals;
     while (argc > 1 && std::string(argv[1]).rfind("--", 0) == 0) {
@@ -97,6 +102,14 @@ int main(int argc, char** argv)
         else if (std::string(argv[1]) == "--bend" && argc > 2) { bend = true; bend_deg = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--bulge" && argc > 2) { bulge = true; bulge_w = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--crowd" && argc > 2) { crowd = (uint32_t)atoi(argv[2]); argv += 2; argc -= 2; }
+        else if (std::string(argv[1]) == "--rebuild") {
+            rebuild = true; argv += 1; argc -= 1;
+            const std::string opt = argc > 1 ? argv[1] : "";
+            if (opt == "naive" || opt == "intervals" || opt == "binned") {
+                rebuild_option = opt == "naive" ? CGPT_BUILD_NAIVE_SPLIT : opt == "intervals" ? CGPT_BUILD_SAH_SPLIT_INTERVALS : CGPT_BUILD_SAH_BINNED;
+                argv += 1; argc -= 1;
+            }
+        }
         else if (std::string(argv[1]) == "--variance-guided") { variance_guided = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--smooth") { smooth = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--mesh-transform" && argc > 13) {
@@ -325,6 +338,13 @@ int main(int argc, char** argv)
             } else {
                 if (bulge) CHECK(cgpt_scene_morph_mesh(ctx, 0, &morph_weight, 1));       // 4 bytes a target go to the device
                 if (bend) CHECK(cgpt_scene_skin_mesh(ctx, 0, joint_matrices.data(), 2)); // on a mesh with targets: the morphed base through the joints, one kernel
+            }
+            if (rebuild) {                                               // the trees follow the pose: split again on the device, from the current leaf order
+                for (const uint32_t obj : posed) {
+                    uint32_t n_nodes = 0, depth = 0;
+                    CHECK(cgpt_scene_rebuild_mesh(ctx, obj, rebuild_option, &n_nodes, &depth));
+                    printf("frame %u: object %u rebuilt, %u nodes, depth %u\n", frame, obj, n_nodes, depth);
+                }
             }
             CHECK(cgpt_reset_accumulator(ctx));
             cgpt_render_params p{};

@@ -252,7 +252,7 @@ int cgpt_scene_upload(cgpt_ctx* ctx, const cgpt_scene_desc* scene);
  * An added export: CGPT_ABI_VERSION stays 2. */
 int cgpt_scene_upload_instanced(cgpt_ctx* ctx, const cgpt_scene_desc* scene);
 /* What the uploaded scene occupies, after either upload (CGPT_ERR_NO_SCENE without one; a multi-device context reports one device, and
- * every device holds the same).  No edit changes it; the skin buffers of cgpt_scene_set_skin and the target buffers of
+ * every device holds the same).  Of the edits only cgpt_scene_rebuild_mesh changes it, at a mesh's first rebuild; the skin buffers of cgpt_scene_set_skin and the target buffers of
  * cgpt_scene_set_morph_targets are not counted.  An added export:
  * CGPT_ABI_VERSION stays 2. */
 typedef struct cgpt_scene_footprint {
@@ -325,10 +325,30 @@ int cgpt_scene_update_transforms(cgpt_ctx* ctx, const float* object_to_world, ui
  * current leaf range of the new triangles, and total_area the sum of GetTriangleArea in original order (ref: BVH.cpp:22).
  * triangles: n_tris == the uploaded tri_count, in the object's original order.  A triangle object takes n_tris = 1 (it has no bounds
  * and no total_area: 0 is reported).  Spheres and planes: CGPT_ERR_INVALID.  total_area_out may be NULL.
- * The tree was built for the old positions: after a large deformation rebuild on the host and upload instead.
+ * The tree was built for the old positions: after a large deformation cgpt_scene_rebuild_mesh splits it again, in place.
  * After cgpt_scene_upload_instanced the refit moves every object that shares `obj_index`'s copy (see there). */
 int cgpt_scene_refit_mesh(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle* triangles, uint32_t n_tris, float* total_area_out);
-/* the mesh's tree as it is now on the device, in the reference's 32-byte layout and node numbering (n_nodes == the uploaded node_count):
+/* BVH::Rebuild (ref: BVH.cpp:47-59) of uploaded mesh `obj_index`, in place on the device: the tree is split again over
+ * the triangles the device copy holds now -- whatever last wrote them: an upload, a refit, a skin, a morph or a batch pose -- starting
+ * from the mesh's current leaf order, as cgpth_scene_rebuild_bvh does on the host.  The triangles do not leave the device and the host
+ * does no per-triangle work; of the nodes it keeps one word of bookkeeping each, for this mesh only.  Afterwards the device scene is what an upload of the host mirror after the same edits and
+ * cgpth_scene_rebuild_bvh(scene, obj_index, build_option) would hold: cgpt_scene_export_bvh returns that tree word for word (its node
+ * count in *n_nodes_out, its depth in *max_depth_out; either may be NULL), and renders, probes and guides are bit-identical to that
+ * upload's, before and after any later edit applied to both.  total_area, materials, smooth flags, transforms, skins and morph targets
+ * are kept.  The image may differ from the one before the call only where two triangles of the mesh tie in t (the visiting order
+ * changes); the caller resets the accumulator.  The denoiser's guides are recomputed and the temporal history is dropped, with every
+ * CGPT_TEMPORAL_FOLLOW_* flag, as after a refit -- but the triangles did not change, so a skin's or the targets' known pose stays known.
+ * build_option: CGPT_BUILD_NAIVE_SPLIT, CGPT_BUILD_SAH_SPLIT_INTERVALS or CGPT_BUILD_SAH_BINNED; CGPT_BUILD_SAH_SPLIT_PRIMITIVES never
+ * splits (SURVEY A-5): CGPT_ERR_UNSUPPORTED.  Refused before the first write to the scene, with nothing changed: no scene
+ * (CGPT_ERR_NO_SCENE); an object out of range, a sphere, a plane or a triangle object, an unknown option (CGPT_ERR_INVALID); with
+ * CGPT_BUILD_SAH_BINNED a position that is not finite or exceeds 1e30 in magnitude (CGPT_ERR_INVALID; checked on the device); a new
+ * tree deeper than the 64-entry traversal stack (CGPT_ERR_UNSUPPORTED); a record span that would pass 2^26 records (CGPT_ERR_INVALID).
+ * A mesh's first rebuild moves its records to a span of tri_count - 1 records at the end of the record array, which grows
+ * (cgpt_get_scene_footprint); later rebuilds reuse the span.  After cgpt_scene_upload_instanced a rebuild through any placement
+ * rebuilds the group's one copy.  An added export: CGPT_ABI_VERSION stays 2. */
+int cgpt_scene_rebuild_mesh(cgpt_ctx* ctx, uint32_t obj_index, uint32_t build_option, uint32_t* n_nodes_out, uint32_t* max_depth_out);
+/* the mesh's tree as it is now on the device, in the reference's 32-byte layout and node numbering (n_nodes == the uploaded node_count,
+ * or what the last cgpt_scene_rebuild_mesh reported):
  * what a host that keeps its own BVH (the BVH panel, a later Rebuild) copies back after a refit */
 int cgpt_scene_export_bvh(cgpt_ctx* ctx, uint32_t obj_index, cgpt_bvh_node* nodes_out, uint32_t n_nodes);
 /* Primitive::RenderImGui's sliders (ref: Primitives.cpp:385-410): a sphere's centre and radius (radius^2 = r*r, as at upload) or a

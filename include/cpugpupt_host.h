@@ -230,6 +230,31 @@ typedef struct cgpth_pose_plan_view {
 int cgpth_pose_batch_plan(const cgpt_scene_desc* scene, int instanced, const uint32_t* batch, uint32_t n_entries, uint32_t skin_joints_lds,
                           uint32_t morph_max_blocks, cgpth_pose_plan_view* out);
 
+/* ---- the bookkeeping of cgpt_scene_rebuild_mesh (csrc/device/rebuild_layout.h: PlanRebuild, RebuildNames, ApplyRebuild; tests/rebuild_ref.py
+ * restates it) ----
+ * Rebuilds of mesh obj_index, one after the other, over the layout a cgpt_scene_upload of `scene` installs (cgpt_scene_upload_instanced
+ * with instanced != 0); no GPU is involved.  `trees` is n_trees runs of words {n, level_first[n], m, top_ranks[m]}: the builder's level
+ * ranges of a new tree (level L = nodes [level_first[L], level_first[L + 1]), closed by the node count) and the preorder ranks of the
+ * first m = min(K, pairs) splitting nodes of its level-ordered array, K = the top slots the mesh owns at that point.  assume_pair_records,
+ * when not 0, stands for the current number of child-pair records (the tests of the 2^26 limit).  The view shows the last rebuild's plan --
+ * members of the mesh group, top_slots, the new level_offsets, names[k] = record of the splitting node of rank k -- and the bookkeeping
+ * after all of them: record_perm, and per object root_codes, span_bases (0xFFFFFFFF: never rebuilt) and node_counts.  The refusals are
+ * the planner's (CGPT_ERR_UNSUPPORTED: deeper than the traversal stack; CGPT_ERR_INVALID: the span would pass 2^26 records), with the
+ * message in cgpth_last_error().  The arrays live in thread-local storage and stay valid until the next call on the same thread. */
+typedef struct cgpth_rebuild_plan_view {
+    const uint32_t* members; size_t n_members;
+    const uint32_t* top_slots; size_t n_top_slots;
+    const uint32_t* level_offsets; size_t n_level_offsets;
+    const uint32_t* names; size_t n_names;
+    const uint32_t* record_perm; size_t n_record_perm;
+    const uint32_t* root_codes; const uint32_t* span_bases; const uint32_t* node_counts; size_t n_objects;
+    uint32_t span_base, level_begin, pair_base, leaf_base;
+    uint32_t n_nodes, n_pairs, max_depth, grow;
+    uint32_t n_pair_records, n_refit_levels, stack_depth, n_top_records;
+} cgpth_rebuild_plan_view;
+int cgpth_rebuild_plan(const cgpt_scene_desc* scene, int instanced, uint32_t obj_index, const uint32_t* trees, uint32_t n_trees,
+                       uint32_t assume_pair_records, cgpth_rebuild_plan_view* out);
+
 /* ---- the top-level tree of cgpt_set_top_level (csrc/device/scene_layout.h: LayoutTopLevel; tests/tlas_ref.py is its specification) ----
  * cgpth_top_level: the tree a cgpt_scene_upload of `scene` would build (cgpt_scene_upload_instanced builds the same: the boxes are per
  * object; the record limit that is checked is the instanced upload's), computed on the host with the upload's validation; no GPU is
