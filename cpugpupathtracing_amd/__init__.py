@@ -8,11 +8,11 @@ from ._native import (CTX_FORCE_COLLECTIVE, CTX_GATHER_PEER_COPY, BUILD_NAIVE, B
                       KERNEL_AUTO, KERNEL_MEGAKERNEL, KERNEL_PERSISTENT, KERNEL_WAVEFRONT, MODE_ADVANCED, MODE_BRUTE_FORCE, MODE_COMPARISON,
                       NativeLibraryError)
 from .renderer import DeviceError, Renderer
-from .scene import REFERENCE_MATERIALS, HostError, Material, Mesh, Scene, Settings, morph_triangles, skin_triangles, triangles_from_arrays
+from .scene import REFERENCE_MATERIALS, HostError, Material, Mesh, Scene, Settings, animate_joints, morph_triangles, skin_triangles, triangles_from_arrays
 
 __all__ = [
     "Renderer", "DeviceError", "Scene", "Mesh", "Material", "Settings", "HostError", "NativeLibraryError", "REFERENCE_MATERIALS",
-    "triangles_from_arrays", "skin_triangles", "morph_triangles",
+    "triangles_from_arrays", "skin_triangles", "morph_triangles", "animate_joints",
     "BUILD_NAIVE", "BUILD_SAH_INTERVALS", "BUILD_SAH_PRIMITIVES", "BUILD_SAH_BINNED", "MODE_COMPARISON", "MODE_BRUTE_FORCE", "MODE_ADVANCED",
     "DEBUG_NONE", "DEBUG_RAY_DEPTH", "DEBUG_BVH_DEPTH", "KERNEL_AUTO", "KERNEL_MEGAKERNEL", "KERNEL_WAVEFRONT", "KERNEL_PERSISTENT", "CTX_FORCE_COLLECTIVE", "CTX_GATHER_PEER_COPY",
 ]

@@ -29,6 +29,8 @@ TEMPORAL_FOLLOW_MORPHS = 32
 VARIANCE_TEMPORAL = 1
 SKIN_MAX_JOINTS = 1024      # cgpt_scene_set_skin
 MORPH_MAX_TARGETS = 256     # cgpt_scene_set_morph_targets
+ANIM_PATH_TRANSLATION, ANIM_PATH_ROTATION, ANIM_PATH_SCALE = 0, 1, 2   # cgpt_clip_channel.path
+ANIM_STEP, ANIM_LINEAR, ANIM_CUBICSPLINE = 0, 1, 2                     # cgpt_clip_channel.interpolation
 HIP_STREAM_LEGACY, HIP_STREAM_PER_THREAD = 1, 2   # hipStreamLegacy, hipStreamPerThread (hip_runtime_api.h): refused by cgpt_set_stream
 
 f3 = C.c_float * 3
@@ -170,6 +172,28 @@ class Pose(C.Structure):
     _fields_ = [("obj_index", C.c_uint32), ("n_joints", C.c_uint32), ("joint_matrices", _fp), ("n_targets", C.c_uint32), ("weights", _fp)]
 
 
+class SkeletonDesc(C.Structure):
+    """cgpt_skeleton_desc"""
+    _fields_ = [("parents", C.POINTER(C.c_int32)), ("inverse_bind", _fp), ("rest", _fp), ("root", _fp), ("n_joints", C.c_uint32)]
+
+
+class ClipChannel(C.Structure):
+    """cgpt_clip_channel"""
+    _fields_ = [("joint", C.c_uint32), ("path", C.c_uint32), ("interpolation", C.c_uint32), ("n_keys", C.c_uint32),
+                ("first_time", C.c_uint32), ("first_value", C.c_uint32)]
+
+
+class ClipDesc(C.Structure):
+    """cgpt_clip_desc"""
+    _fields_ = [("n_joints", C.c_uint32), ("n_channels", C.c_uint32), ("channels", C.POINTER(ClipChannel)), ("times", _fp),
+                ("n_times", C.c_uint32), ("values", _fp), ("n_values", C.c_uint32)]
+
+
+class Animation(C.Structure):
+    """cgpt_animation: one entry of cgpt_scene_animate_objects"""
+    _fields_ = [("obj_index", C.c_uint32), ("clip", C.c_uint32), ("time", C.c_float), ("n_targets", C.c_uint32), ("weights", _fp)]
+
+
 class SceneFootprint(C.Structure):
     """cgpt_scene_footprint"""
     _fields_ = [("device_bytes", C.c_uint64), ("n_objects", C.c_uint32), ("n_mesh_objects", C.c_uint32), ("n_mesh_copies", C.c_uint32),
@@ -210,6 +234,11 @@ PROTOTYPES = {
     "cgpt_scene_morph_mesh": (C.c_int, [_vp, C.c_uint32, _fp, C.c_uint32]),
     "cgpt_scene_clear_morph_targets": (C.c_int, [_vp, C.c_uint32]),
     "cgpt_scene_pose_objects": (C.c_int, [_vp, C.POINTER(Pose), C.c_uint32]),
+    "cgpt_scene_set_skeleton": (C.c_int, [_vp, C.c_uint32, C.POINTER(SkeletonDesc)]),
+    "cgpt_clip_create": (C.c_int, [_vp, C.POINTER(ClipDesc), _up]),
+    "cgpt_clip_destroy": (C.c_int, [_vp, C.c_uint32]),
+    "cgpt_scene_animate_objects": (C.c_int, [_vp, C.POINTER(Animation), C.c_uint32]),
+    "cgpt_scene_get_joint_matrices": (C.c_int, [_vp, C.c_uint32, _fp, C.c_uint32]),
     "cgpt_camera_from_view": (C.c_int, [_fp, _fp, C.c_float, C.c_float, C.POINTER(Camera)]),
     "cgpt_render": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(Settings), C.POINTER(RenderParams)]),
     "cgpt_reset_accumulator": (C.c_int, [_vp]),
@@ -282,6 +311,7 @@ PROTOTYPES = {
     "cgpth_scene_skin_mesh": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), _u16p, _fp, C.c_uint32, _fp, C.c_uint32]),
     "cgpth_morph_triangles": (C.c_int, [C.POINTER(Triangle), C.POINTER(Triangle), C.c_uint32, C.c_uint32, _fp, C.POINTER(Triangle)]),
     "cgpth_scene_morph_mesh": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), C.POINTER(Triangle), C.c_uint32, C.c_uint32, _fp]),
+    "cgpth_animate_joints": (C.c_int, [C.POINTER(SkeletonDesc), C.POINTER(ClipDesc), C.c_float, _fp, C.c_uint32]),
     "cgpth_scene_update_primitive": (C.c_int, [_vp, C.c_uint32, C.POINTER(Object)]),
     "cgpth_scene_bvh_info": (C.c_int, [_vp, C.c_uint32, C.POINTER(BvhInfo)]),
     "cgpth_scene_bvh_export": (C.c_int, [_vp, C.c_uint32, C.POINTER(BvhNode), _up]),

@@ -27,6 +27,7 @@ struct SceneBuffers {                             // cgpt_scene_upload installs 
     DevBuf<cgpt_triangle> refit_staging;          // host triangles of the last refit, grown on demand
     DevBuf<uint32_t> skin_scratch;                // cgpt_scene_skin_mesh: 8 words a pose reads back (refit.hip: kSkinScratchWords), allocated with the first skin
     DevBuf<uint32_t> pose_batch;                  // cgpt_scene_pose_objects: the tables and scratch of the last batch (refit.hip: PoseObjects), grown on demand
+    DevBuf<uint32_t> anim_batch;                  // cgpt_scene_animate_objects: per entry a flag word, then the entry records animate_joints_batch reads, grown on demand
 };
 // The skin of one object (cgpt_scene_set_skin): the bind pose, 12 joint indices and 12 weights a triangle, and the room of a pose's
 // joint matrices.  Not part of the scene's footprint; an upload drops every skin.
@@ -42,6 +43,18 @@ struct SkinBuffers {
     std::vector<float> pose;
     bool pose_known = false;
     uint64_t serial = 0;
+    // the skin's skeleton (cgpt_scene_set_skeleton), n_joints joints as the skin: parents, 12 floats of inverse bind and 10
+    // of rest {T.xyz, R.xyzw, S.xyz} a joint, 12 floats of root matrix when has_root.  Lives and dies with the skin
+    DevBuf<int32_t> parents;
+    DevBuf<float> inverse_bind, rest, root;
+    bool has_skeleton = false, has_root = false;
+};
+// An animation clip (cgpt_clip_create): what animation.h's sampler reads -- the (joint, path) -> channel table, the channels
+// (animation.h: AnimChannel, four words each), the key times and values.  Belongs to the context, not to a scene
+struct ClipBuffers {
+    DevBuf<uint32_t> map, channels;
+    DevBuf<float> times, values;
+    uint32_t n_joints = 0;                        // 0: a destroyed clip's slot
 };
 // The morph targets of one object (cgpt_scene_set_morph_targets): the base triangle and the n_targets displacement
 // records of every triangle in one buffer of float2 -- set 0 is the base, set 1 + k is target k.  leaf_order: set s, plane p (0..8, two of
@@ -199,6 +212,8 @@ struct cgpt_ctx {
     uint64_t morph_generation = 0;
     std::vector<uint64_t> morph_stamp;
     uint64_t morph_serial = 0;
+    // animation clips (cgpt_clip_create): handle k is clips[k - 1]; an upload keeps them
+    std::vector<cgpt::ClipBuffers> clips;
 
     // framebuffer band
     cgpt::FrameBuffers fb;
@@ -328,6 +343,10 @@ int GroupSetMorphTargets(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_triangle*
 int GroupMorphMesh(cgpt_ctx* ctx, uint32_t obj_index, const float* weights, uint32_t n_targets);
 int GroupClearMorphTargets(cgpt_ctx* ctx, uint32_t obj_index);
 int GroupPoseObjects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_poses);
+int GroupSetSkeleton(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_skeleton_desc* skeleton);
+int GroupClipCreate(cgpt_ctx* ctx, const cgpt_clip_desc* clip, uint32_t* clip_out);
+int GroupClipDestroy(cgpt_ctx* ctx, uint32_t clip);
+int GroupAnimateObjects(cgpt_ctx* ctx, const cgpt_animation* entries, uint32_t n_entries);
 int GroupRebuildMesh(cgpt_ctx* ctx, uint32_t obj_index, uint32_t build_option, uint32_t* n_nodes_out, uint32_t* max_depth_out);
 int GroupRender(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p);
 int GroupResetAccumulator(cgpt_ctx* ctx);

@@ -407,6 +407,43 @@ int GroupPoseObjects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_poses)
     return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_pose_objects(m, poses, n_poses); });
 }
 
+// ... and a batch of animated poses: every member evaluates the matrices on its own device from its own copy of the clip and skeleton
+int GroupSetSkeleton(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_skeleton_desc* skeleton)
+{
+    return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_set_skeleton(m, obj_index, skeleton); });
+}
+
+int GroupAnimateObjects(cgpt_ctx* ctx, const cgpt_animation* entries, uint32_t n_entries)
+{
+    return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_animate_objects(m, entries, n_entries); });
+}
+
+// a clip is no part of the scene: every member holds a copy under the same handle (the members' handles advance in step), and a member
+// that cannot take it leaves the others without it
+int GroupClipCreate(cgpt_ctx* ctx, const cgpt_clip_desc* clip, uint32_t* clip_out)
+{
+    std::vector<cgpt_ctx*>& ms = ctx->group->members;
+    uint32_t handle = 0;
+    for (size_t r = 0; r < ms.size(); ++r) {
+        uint32_t h = 0;
+        int rc = cgpt_clip_create(ms[r], clip, &h);
+        if (rc == CGPT_OK && r > 0 && h != handle) { (void)cgpt_clip_destroy(ms[r], h); rc = CtxFail(ms[r], CGPT_ERR_INVALID, "the members' clip handles differ (%u, %u)", handle, h); }
+        if (rc != CGPT_OK) {
+            for (size_t q = 0; q < r; ++q) (void)cgpt_clip_destroy(ms[q], handle);
+            return Propagate(ctx, ms[r], rc);
+        }
+        handle = h;
+    }
+    if (clip_out) *clip_out = handle;
+    return CGPT_OK;
+}
+
+int GroupClipDestroy(cgpt_ctx* ctx, uint32_t clip)
+{
+    for (cgpt_ctx* m : ctx->group->members) { const int rc = cgpt_clip_destroy(m, clip); if (rc != CGPT_OK) return Propagate(ctx, m, rc); }
+    return CGPT_OK;
+}
+
 // every member rebuilds its own copy: the builder is deterministic, so the trees stay equal (the record names may differ, and are no one's business)
 int GroupRebuildMesh(cgpt_ctx* ctx, uint32_t obj_index, uint32_t build_option, uint32_t* n_nodes_out, uint32_t* max_depth_out)
 {

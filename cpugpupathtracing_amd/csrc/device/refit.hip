@@ -25,6 +25,9 @@
 // has a posed skin, hands each morphed corner to SkinCorner in registers.  Either call poses through PoseObject.
 // Many objects in one call (cgpt_scene_pose_objects): the same poses for any number of objects with launches that do not
 // grow with their count -- pose_plan.h plans the batch on the host, PoseObjects runs it through batched shells of the kernels above.
+// Animation clips (cgpt_scene_animate_objects): that batch with every entry's joint matrices evaluated on the device first, by
+// the arithmetic of csrc/host/animation.h, from a resident skeleton and clip (animate_joints_batch); PoseObjects then reads them where
+// the kernel wrote them.
 // After cgpt_scene_upload_instanced the objects of a mesh group share the one copy these passes edit: the refit goes through any member's
 // RefitObject (they are equal), and the area and the top-level box, which are per object, are written for every member.
 #include <hip/hip_runtime.h>
@@ -36,6 +39,7 @@
 #include <exception>
 #include <vector>
 
+#include "animation.h"
 #include "cpugpupt_abi.h"
 #include "ctx_internal.h"
 #include "device_scene.h"
@@ -457,6 +461,53 @@ __global__ __launch_bounds__(kRefitThreads) void pose_boxes_batch(const PoseEntr
     }
 }
 
+// ---- joint matrices from a clip (cgpt_scene_animate_objects; animation.h states the arithmetic) -----------------------
+// One entry as animate_joints_batch reads it: 80 bytes, block-uniform, so it comes through scalar loads
+struct AnimEntryRecord {
+    const int32_t* parents;                                                   // the skin's skeleton (SkinBuffers)
+    const float* inverse_bind;
+    const float* rest;
+    const float* root;                                                        // null: no root multiply
+    const uint32_t* map;                                                      // the clip (ClipBuffers)
+    const AnimChannel* channels;
+    const float* times;
+    const float* values;
+    uint32_t n_joints, matrix_base;                                           // the entry's matrices start at float4 3 * matrix_base of `matrices`
+    float time;
+    uint32_t pad;
+};
+// A block an entry, a lane the joints tid, tid + 256, ...: it samples T, R and S and writes L_j to LDS (dynamic, 48 B a joint, sized to
+// the launch's largest joint count: 48 KB at the 1024-joint limit); after one barrier it walks its joint's ancestors through LDS
+// (the parents were validated by cgpt_scene_set_skeleton: in range, no cycle) and writes M_j as three float4.  flags[entry] is set when
+// a matrix entry is not finite.  Nothing else is written: the scene is not touched.
+// The 48-byte records are three 16-byte stores a lane, 12 dwords apart: the eight lanes a store is served in cover dwords 0, 12, 24,
+// 36 = 4, 16, 28, 8, 20 (mod 32) + 0..3, every bank once; a wave that walks a chain (parents[j] = j - 1) reads sixteen records 12 dwords
+// apart a group, sixteen different 16-byte slots of the 64 banks: neither conflicts, so the records stay whole.
+__global__ __launch_bounds__(kRefitThreads) void animate_joints_batch(const AnimEntryRecord* __restrict__ entries, float4* __restrict__ matrices, uint32_t* __restrict__ flags)
+{
+    extern __shared__ float4 s_locals[];
+    const AnimEntryRecord e = entries[blockIdx.x];
+    for (uint32_t j = threadIdx.x; j < e.n_joints; j += blockDim.x) {
+        float L[12];
+        AnimLocalMatrix(e.map, e.channels, e.times, e.values, e.rest, j, e.time, L);
+        s_locals[3 * j] = make_float4(L[0], L[1], L[2], L[3]);
+        s_locals[3 * j + 1] = make_float4(L[4], L[5], L[6], L[7]);
+        s_locals[3 * j + 2] = make_float4(L[8], L[9], L[10], L[11]);
+    }
+    __syncthreads();
+    float4* out = matrices + 3 * (size_t)e.matrix_base;
+    bool finite = true;
+    for (uint32_t j = threadIdx.x; j < e.n_joints; j += blockDim.x) {
+        float M[12];
+        AnimJointMatrix(reinterpret_cast<const float*>(s_locals), e.parents, e.inverse_bind, e.root, j, M);
+        for (int i = 0; i < 12; ++i) finite = finite && fabsf(M[i]) < INFINITY;   // false for a NaN too
+        out[3 * j] = make_float4(M[0], M[1], M[2], M[3]);
+        out[3 * j + 1] = make_float4(M[4], M[5], M[6], M[7]);
+        out[3 * j + 2] = make_float4(M[8], M[9], M[10], M[11]);
+    }
+    if (!finite) atomicOr(flags + blockIdx.x, 1u);
+}
+
 const char* KindName(uint32_t kind)
 {
     return kind == CGPT_OBJECT_MESH ? "mesh" : kind == CGPT_OBJECT_SPHERE ? "sphere" : kind == CGPT_OBJECT_PLANE ? "plane" : "triangle object";
@@ -687,8 +738,9 @@ int PoseObject(cgpt_ctx* ctx, uint32_t obj_index, bool skinned, uint32_t n_activ
     return CGPT_OK;
 }
 
-// what cgpt_scene_skin_mesh refuses, for it and for an entry of cgpt_scene_pose_objects
-int CheckSkinPose(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uint32_t n_joints)
+// what cgpt_scene_skin_mesh refuses, for it and for an entry of cgpt_scene_pose_objects: of the object and its skin (all an entry of
+// cgpt_scene_animate_objects can be refused for: its matrices do not exist yet), and of the matrices
+int CheckSkinJoints(cgpt_ctx* ctx, uint32_t obj_index, uint32_t n_joints)
 {
     int rc = CheckObject(ctx, obj_index);
     if (rc != CGPT_OK) return rc;
@@ -696,6 +748,13 @@ int CheckSkinPose(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices
         return CtxFail(ctx, CGPT_ERR_INVALID, "object %u has no skin (cgpt_scene_set_skin installs one)", obj_index);
     const SkinBuffers& sk = ctx->skins[obj_index];
     if (n_joints != sk.n_joints) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u's skin has %u joints, got %u", obj_index, sk.n_joints, n_joints);
+    return CGPT_OK;
+}
+
+int CheckSkinPose(cgpt_ctx* ctx, uint32_t obj_index, const float* joint_matrices, uint32_t n_joints)
+{
+    int rc = CheckSkinJoints(ctx, obj_index, n_joints);
+    if (rc != CGPT_OK) return rc;
     std::string why;
     if (!CheckJointMatrices(joint_matrices, n_joints, why)) return CtxFail(ctx, CGPT_ERR_INVALID, "%s", why.c_str());
     return CGPT_OK;
@@ -854,14 +913,20 @@ int ClearMorphTargets(cgpt_ctx* ctx, uint32_t obj_index)
 // zeroed scratch, the entry table, the segments, every entry's matrices and active table in one piece), one synchronise, one readback
 // and one WriteTopLevel.  The per-skin `matrices` and per-object `active` buffers are not written: only the single calls' kernels read
 // them, and those calls upload them again themselves.
-int PoseObjects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_poses)
+// `anim` (cgpt_scene_animate_objects): entry i's joint_matrices is null and its matrices are those of anim[i], evaluated on the device
+// between the upload and the first write (AnimateEntries) and read by the triangle pass where they were written.
+struct AnimResolved { const SkinBuffers* skin; const ClipBuffers* clip; float time; };
+int AnimateEntries(cgpt_ctx* ctx, const AnimResolved* anim, const cgpt_pose* poses, uint32_t n_poses, const PosePlan& plan, float* d_matrices,
+                   std::vector<std::vector<float>>& kept_matrices);
+
+int PoseObjects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_poses, const AnimResolved* anim = nullptr)
 {
     if (n_poses == 0u) return CGPT_OK;
     if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
     if (!poses) return CtxFail(ctx, CGPT_ERR_INVALID, "poses is null");
 
     // the single calls' refusals, entry by entry, and what each entry poses with: its own arrays, or what the object's last pose left
-    struct Resolved { const float* matrices = nullptr; const float* weights = nullptr; bool morphed = false; std::vector<uint2> table; };
+    struct Resolved { const float* matrices = nullptr; const float* weights = nullptr; bool morphed = false, skinned = false; std::vector<uint2> table; };
     std::vector<Resolved> resolved(n_poses);
     std::vector<PosePlanInput> in(n_poses);
     for (uint32_t i = 0; i < n_poses; ++i) {
@@ -870,18 +935,19 @@ int PoseObjects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_poses)
         int rc = CheckObject(ctx, o);
         if (rc == CGPT_OK && p.n_joints == 0u && p.n_targets == 0u) rc = CtxFail(ctx, CGPT_ERR_INVALID, "object %u: neither joint matrices nor morph weights are given", o);
         if (rc == CGPT_OK && p.n_targets != 0u) rc = CheckMorphPose(ctx, o, p.weights, p.n_targets);
-        if (rc == CGPT_OK && p.n_joints != 0u) rc = CheckSkinPose(ctx, o, p.joint_matrices, p.n_joints);
+        if (rc == CGPT_OK && p.n_joints != 0u) rc = anim ? CheckSkinJoints(ctx, o, p.n_joints) : CheckSkinPose(ctx, o, p.joint_matrices, p.n_joints);
         if (rc != CGPT_OK) { ctx->error = "entry " + std::to_string(i) + ": " + ctx->error; return rc; }
         Resolved& r = resolved[i];
         r.morphed = HasMorphTargets(ctx, o);
         const bool posed_skin = o < ctx->skins.size() && ctx->skins[o].n_joints != 0u && !ctx->skins[o].pose.empty();   // MorphMesh: takes part with its last matrices
         r.matrices = p.n_joints != 0u ? p.joint_matrices : posed_skin ? ctx->skins[o].pose.data() : nullptr;
+        r.skinned = r.matrices != nullptr || (anim && p.n_joints != 0u);
         if (r.morphed) {
             const MorphBuffers& mb = ctx->morphs[o];
             r.weights = p.n_targets != 0u ? p.weights : mb.weights.data();    // SkinMesh: the last weights given
             r.table = ActiveTable(r.weights, mb.n_targets);
         }
-        in[i] = { o, r.matrices ? ctx->skins[o].n_joints : 0u, r.morphed ? 1u : 0u, r.morphed ? ctx->morphs[o].leaf_order : 0u, (uint32_t)r.table.size() };
+        in[i] = { o, r.skinned ? ctx->skins[o].n_joints : 0u, r.morphed ? 1u : 0u, r.morphed ? ctx->morphs[o].leaf_order : 0u, (uint32_t)r.table.size() };
     }
     PosePlan plan;
     std::string why;
@@ -900,11 +966,11 @@ int PoseObjects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_poses)
         const PosePlanEntry& e = plan.entries[k];
         const Resolved& r = resolved[e.source];
         PoseEntryRecord rec{};
-        if (r.matrices) {
+        if (r.skinned) {
             const SkinBuffers& sk = ctx->skins[e.obj_index];
             rec.joints = reinterpret_cast<const uint2*>(sk.joints.p); rec.weights = reinterpret_cast<const float4*>(sk.weights.p);
             if (!r.morphed) rec.data = reinterpret_cast<const float2*>(sk.bind.p);
-            memcpy(blob.data() + matrices_at + 12 * (size_t)e.matrix_base, r.matrices, sizeof(float) * 12 * (size_t)e.n_joints);
+            if (r.matrices) memcpy(blob.data() + matrices_at + 12 * (size_t)e.matrix_base, r.matrices, sizeof(float) * 12 * (size_t)e.n_joints);
         }
         if (r.morphed) rec.data = ctx->morphs[e.obj_index].data.p;
         if (!r.table.empty()) memcpy(blob.data() + active_at + 2 * (size_t)e.active_base, r.table.data(), sizeof(uint2) * r.table.size());
@@ -920,7 +986,7 @@ int PoseObjects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_poses)
     if (ctx->morph_stamp.size() != ctx->h_objects.size()) ctx->morph_stamp.resize(ctx->h_objects.size(), 0);
     std::vector<std::vector<float>> kept_matrices(n_poses), kept_weights(n_poses);   // what the commit below installs: allocated while a refusal is still possible
     for (uint32_t i = 0; i < n_poses; ++i) {
-        if (poses[i].n_joints != 0u) kept_matrices[i].assign(poses[i].joint_matrices, poses[i].joint_matrices + 12 * (size_t)poses[i].n_joints);
+        if (poses[i].n_joints != 0u && !anim) kept_matrices[i].assign(poses[i].joint_matrices, poses[i].joint_matrices + 12 * (size_t)poses[i].n_joints);
         if (poses[i].n_targets != 0u) kept_weights[i].assign(poses[i].weights, poses[i].weights + poses[i].n_targets);
     }
 
@@ -928,6 +994,10 @@ int PoseObjects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_poses)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, ctx->sb.pose_batch.Grow(total));                              // the stream was just drained: nothing uses the old one
     HIP_TRY(ctx, hipMemcpyAsync(ctx->sb.pose_batch.p, blob.data(), sizeof(uint32_t) * total, hipMemcpyHostToDevice, ctx->stream));
+    if (anim) {                                                                // the matrices: computed where the triangle pass reads them, and kept as the caller's would be
+        const int rc = AnimateEntries(ctx, anim, poses, n_poses, plan, reinterpret_cast<float*>(ctx->sb.pose_batch.p + matrices_at), kept_matrices);
+        if (rc != CGPT_OK) return rc;
+    }
 
     // from here on the scene changes.  The generations and stamps move as the single calls move them, entry by entry: an accepted morph
     // counts one scene, shape and morph edit, a pose one scene, shape and pose edit (denoise.hip: HistoryMatches)
@@ -1029,6 +1099,155 @@ int PoseObjects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_poses)
             }
         }
     }
+    return CGPT_OK;
+}
+
+// ---- animation clips (cgpt_scene_set_skeleton / cgpt_clip_create / cgpt_scene_animate_objects) -----------------------
+// Phase 1 of cgpt_scene_animate_objects, behind the batch's upload: the entry records go up, animate_joints_batch writes every entry's
+// matrices at its matrix_base of the batch's matrix array, and after one synchronise the matrices and the flags come back.  A flagged
+// entry refuses the call; nothing of the scene has been written yet.
+int AnimateEntries(cgpt_ctx* ctx, const AnimResolved* anim, const cgpt_pose* poses, uint32_t n_poses, const PosePlan& plan, float* d_matrices,
+                   std::vector<std::vector<float>>& kept_matrices)
+{
+    static_assert(sizeof(AnimEntryRecord) == 80 && sizeof(AnimChannel) == 16, "the entry table's parts");
+    const size_t n = plan.entries.size();
+    const size_t records_at = (n + 3) / 4 * 4, total = records_at + sizeof(AnimEntryRecord) / 4 * n;
+    std::vector<uint32_t> blob(total, 0u);                                     // flags | records
+    uint32_t max_joints = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const PosePlanEntry& e = plan.entries[k];
+        const AnimResolved& a = anim[e.source];
+        AnimEntryRecord rec{};
+        rec.parents = a.skin->parents.p; rec.inverse_bind = a.skin->inverse_bind.p; rec.rest = a.skin->rest.p;
+        rec.root = a.skin->has_root ? a.skin->root.p : nullptr;
+        rec.map = a.clip->map.p; rec.channels = reinterpret_cast<const AnimChannel*>(a.clip->channels.p); rec.times = a.clip->times.p; rec.values = a.clip->values.p;
+        rec.n_joints = e.n_joints; rec.matrix_base = e.matrix_base; rec.time = a.time;
+        memcpy(blob.data() + records_at + sizeof(AnimEntryRecord) / 4 * k, &rec, sizeof(rec));
+        max_joints = std::max(max_joints, e.n_joints);
+    }
+    std::vector<float> back(12 * (size_t)plan.n_matrix_joints);
+    std::vector<uint32_t> flags(n);
+    HIP_TRY(ctx, ctx->sb.anim_batch.Grow(total));                              // the caller drained the stream: nothing uses the old one
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->sb.anim_batch.p, blob.data(), sizeof(uint32_t) * total, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(animate_joints_batch, dim3((uint32_t)n), dim3(kRefitThreads), 3 * sizeof(float4) * (size_t)max_joints, ctx->stream,
+                       reinterpret_cast<const AnimEntryRecord*>(ctx->sb.anim_batch.p + records_at), reinterpret_cast<float4*>(d_matrices), ctx->sb.anim_batch.p);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(back.data(), d_matrices, sizeof(float) * back.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(flags.data(), ctx->sb.anim_batch.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    uint32_t refused = n_poses;                                                // the first flagged entry in the caller's order
+    for (size_t k = 0; k < n; ++k)
+        if (flags[k] != 0u) refused = std::min(refused, plan.entries[k].source);
+    if (refused != n_poses)
+        return CtxFail(ctx, CGPT_ERR_INVALID, "entry %u: object %u: a joint matrix of the clip at time %g is not finite", refused, poses[refused].obj_index, (double)anim[refused].time);
+    for (size_t k = 0; k < n; ++k) {
+        const PosePlanEntry& e = plan.entries[k];
+        const float* m = back.data() + 12 * (size_t)e.matrix_base;
+        kept_matrices[e.source].assign(m, m + 12 * (size_t)e.n_joints);
+    }
+    return CGPT_OK;
+}
+
+int SetSkeleton(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_skeleton_desc* s)
+{
+    int rc = CheckObject(ctx, obj_index);
+    if (rc != CGPT_OK) return rc;
+    if (obj_index >= ctx->skins.size() || ctx->skins[obj_index].n_joints == 0u)
+        return CtxFail(ctx, CGPT_ERR_INVALID, "object %u has no skin (cgpt_scene_set_skin installs one)", obj_index);
+    std::string why;
+    if (!CheckSkeleton(s, why)) return CtxFail(ctx, CGPT_ERR_INVALID, "%s", why.c_str());
+    SkinBuffers& sk = ctx->skins[obj_index];
+    if (s->n_joints != sk.n_joints) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u's skin has %u joints, the skeleton %u", obj_index, sk.n_joints, s->n_joints);
+
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                           // nothing uses the skeleton this one replaces
+    const size_t n = s->n_joints;
+    DevBuf<int32_t> parents;                                                   // installed whole, or not at all
+    DevBuf<float> inverse_bind, rest, root;
+    HIP_TRY(ctx, parents.Alloc(n));
+    HIP_TRY(ctx, inverse_bind.Alloc(12 * n));
+    HIP_TRY(ctx, rest.Alloc(10 * n));
+    HIP_TRY(ctx, root.Alloc(12));
+    HIP_TRY(ctx, hipMemcpy(parents.p, s->parents, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(inverse_bind.p, s->inverse_bind, sizeof(float) * 12 * n, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(rest.p, s->rest, sizeof(float) * 10 * n, hipMemcpyHostToDevice));
+    if (s->root) HIP_TRY(ctx, hipMemcpy(root.p, s->root, sizeof(float) * 12, hipMemcpyHostToDevice));
+    sk.parents = std::move(parents); sk.inverse_bind = std::move(inverse_bind); sk.rest = std::move(rest); sk.root = std::move(root);
+    sk.has_root = s->root != nullptr;
+    sk.has_skeleton = true;
+    return CGPT_OK;
+}
+
+int ClipCreate(cgpt_ctx* ctx, const cgpt_clip_desc* desc, uint32_t* clip_out)
+{
+    if (!clip_out) return CtxFail(ctx, CGPT_ERR_INVALID, "clip_out is null");
+    ClipTable table;
+    std::string why;
+    bool unsupported = false;
+    if (!CheckClip(desc, table, why, unsupported)) return CtxFail(ctx, unsupported ? CGPT_ERR_UNSUPPORTED : CGPT_ERR_INVALID, "%s", why.c_str());
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ClipBuffers cb;                                                            // one element of room where an array is empty: no kernel argument is null
+    const auto up = [&](auto& buf, const void* src, size_t count, size_t elem) -> hipError_t {
+        const hipError_t e = buf.Alloc(std::max<size_t>(count, 1));
+        return e != hipSuccess || count == 0 ? e : hipMemcpy(buf.p, src, count * elem, hipMemcpyHostToDevice);
+    };
+    HIP_TRY(ctx, up(cb.map, table.map.data(), table.map.size(), sizeof(uint32_t)));
+    HIP_TRY(ctx, up(cb.channels, table.channels.data(), 4 * table.channels.size(), sizeof(uint32_t)));
+    HIP_TRY(ctx, up(cb.times, table.times.data(), table.times.size(), sizeof(float)));
+    HIP_TRY(ctx, up(cb.values, table.values.data(), table.values.size(), sizeof(float)));
+    cb.n_joints = table.n_joints;
+    ctx->clips.push_back(std::move(cb));                                       // a handle is never given twice
+    *clip_out = (uint32_t)ctx->clips.size();
+    return CGPT_OK;
+}
+
+const ClipBuffers* FindClip(const cgpt_ctx* ctx, uint32_t clip)
+{
+    return clip == 0u || clip > ctx->clips.size() || ctx->clips[clip - 1].n_joints == 0u ? nullptr : &ctx->clips[clip - 1];
+}
+
+int ClipDestroy(cgpt_ctx* ctx, uint32_t clip)
+{
+    if (!FindClip(ctx, clip)) return CtxFail(ctx, CGPT_ERR_INVALID, "clip %u is unknown or destroyed", clip);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->clips[clip - 1] = ClipBuffers{};
+    return CGPT_OK;
+}
+
+int AnimateObjects(cgpt_ctx* ctx, const cgpt_animation* entries, uint32_t n)
+{
+    if (n == 0u) return CGPT_OK;
+    if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!entries) return CtxFail(ctx, CGPT_ERR_INVALID, "entries is null");
+    std::vector<cgpt_pose> poses(n);
+    std::vector<AnimResolved> anim(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const cgpt_animation& a = entries[i];
+        const uint32_t o = a.obj_index;
+        int rc = CheckObject(ctx, o);
+        if (rc == CGPT_OK && (o >= ctx->skins.size() || ctx->skins[o].n_joints == 0u || !ctx->skins[o].has_skeleton))
+            rc = CtxFail(ctx, CGPT_ERR_INVALID, "object %u has no skeleton (cgpt_scene_set_skeleton installs one on its skin)", o);
+        const ClipBuffers* clip = FindClip(ctx, a.clip);
+        if (rc == CGPT_OK && !clip) rc = CtxFail(ctx, CGPT_ERR_INVALID, "clip %u is unknown or destroyed", a.clip);
+        if (rc == CGPT_OK && clip->n_joints != ctx->skins[o].n_joints)
+            rc = CtxFail(ctx, CGPT_ERR_INVALID, "clip %u animates %u joints, object %u's skeleton has %u", a.clip, clip->n_joints, o, ctx->skins[o].n_joints);
+        if (rc == CGPT_OK && !std::isfinite(a.time)) rc = CtxFail(ctx, CGPT_ERR_INVALID, "time is not finite");
+        if (rc != CGPT_OK) { ctx->error = "entry " + std::to_string(i) + ": " + ctx->error; return rc; }
+        poses[i] = cgpt_pose{ o, ctx->skins[o].n_joints, nullptr, a.n_targets, a.weights };
+        anim[i] = { &ctx->skins[o], clip, a.time };
+    }
+    return PoseObjects(ctx, poses.data(), n, anim.data());
+}
+
+int GetJointMatrices(cgpt_ctx* ctx, uint32_t obj_index, float* out, uint32_t n_joints)
+{
+    int rc = CheckSkinJoints(ctx, obj_index, n_joints);
+    if (rc != CGPT_OK) return rc;
+    if (!out) return CtxFail(ctx, CGPT_ERR_INVALID, "out is null");
+    const SkinBuffers& sk = ctx->skins[obj_index];
+    if (sk.pose.empty()) return CtxFail(ctx, CGPT_ERR_INVALID, "object %u's skin has not been posed", obj_index);
+    memcpy(out, sk.pose.data(), sizeof(float) * sk.pose.size());
     return CGPT_OK;
 }
 
@@ -1232,6 +1451,41 @@ int cgpt_scene_pose_objects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_po
     if (!ctx) return CGPT_ERR_INVALID;
     if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupPoseObjects(ctx, poses, n_poses); });
     return Guarded(ctx, __func__, [&] { return PoseObjects(ctx, poses, n_poses); });   // bumps the generations once the batch is accepted
+}
+
+int cgpt_scene_set_skeleton(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_skeleton_desc* skeleton)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupSetSkeleton(ctx, obj_index, skeleton); });
+    return Guarded(ctx, __func__, [&] { return SetSkeleton(ctx, obj_index, skeleton); });   // the scene does not change
+}
+
+int cgpt_clip_create(cgpt_ctx* ctx, const cgpt_clip_desc* clip, uint32_t* clip_out)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupClipCreate(ctx, clip, clip_out); });
+    return Guarded(ctx, __func__, [&] { return ClipCreate(ctx, clip, clip_out); });
+}
+
+int cgpt_clip_destroy(cgpt_ctx* ctx, uint32_t clip)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupClipDestroy(ctx, clip); });
+    return Guarded(ctx, __func__, [&] { return ClipDestroy(ctx, clip); });
+}
+
+int cgpt_scene_animate_objects(cgpt_ctx* ctx, const cgpt_animation* entries, uint32_t n_entries)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupAnimateObjects(ctx, entries, n_entries); });
+    return Guarded(ctx, __func__, [&] { return AnimateObjects(ctx, entries, n_entries); });   // bumps the generations once the batch is accepted
+}
+
+int cgpt_scene_get_joint_matrices(cgpt_ctx* ctx, uint32_t obj_index, float* out, uint32_t n_joints)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return GroupForwarded(ctx, cgpt_scene_get_joint_matrices(GroupFirstMember(ctx), obj_index, out, n_joints));
+    return Guarded(ctx, __func__, [&] { return GetJointMatrices(ctx, obj_index, out, n_joints); });
 }
 
 int cgpt_scene_export_bvh(cgpt_ctx* ctx, uint32_t obj_index, cgpt_bvh_node* nodes_out, uint32_t n_nodes)

@@ -7,6 +7,7 @@
 
 #include "cpugpupt_host.h"
 #include "fast_div.h"
+#include "animation.h"
 #include "gltf_loader.h"
 #include "image_io.h"
 #include "mesh_gen.h"
@@ -525,6 +526,24 @@ int cgpth_scene_morph_mesh(cgpth_scene* scene, uint32_t obj_index, const cgpt_tr
         std::vector<cgpt_triangle> posed(n_tris);
         MorphTriangles(base_triangles, target_deltas, n_tris, n_targets, weights, posed.data());
         return cgpth_scene_refit_mesh(scene, obj_index, posed.data(), n_tris);
+    });
+}
+
+int cgpth_animate_joints(const cgpt_skeleton_desc* skeleton, const cgpt_clip_desc* clip, float time, float* out, uint32_t n_joints)
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        std::string err;
+        ClipTable table;
+        bool unsupported = false;
+        if (!CheckSkeleton(skeleton, err)) return Fail(err);
+        if (!CheckClip(clip, table, err, unsupported)) { Fail(err); return unsupported ? (int)CGPT_ERR_UNSUPPORTED : (int)CGPT_ERR_INVALID; }
+        if (table.n_joints != skeleton->n_joints)
+            return Fail("the clip animates " + std::to_string(table.n_joints) + " joints, the skeleton has " + std::to_string(skeleton->n_joints));
+        if (n_joints != skeleton->n_joints) return Fail("the skeleton has " + std::to_string(skeleton->n_joints) + " joints, got room for " + std::to_string(n_joints));
+        if (!std::isfinite(time)) return Fail("time is not finite");
+        if (!out) return Fail("out is null");
+        AnimateJoints(*skeleton, table, time, out);
+        return CGPT_OK;
     });
 }
 

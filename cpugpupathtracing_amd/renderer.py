@@ -11,7 +11,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _native as N
-from .scene import Scene, Settings, _joint_matrices, _morph_arrays, _morph_weights, _skin_arrays, _triangle_ptr, _triangle_rows, primitive_abi
+from .scene import Scene, Settings, _clip_desc, _joint_matrices, _skeleton_desc, _morph_arrays, _morph_weights, _skin_arrays, _triangle_ptr, _triangle_rows, primitive_abi
 
 
 _IDENTITY = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float32)
@@ -68,6 +68,7 @@ class Renderer:
         self._smooth = False          # the device holds a smooth-normal flag (cgpt_scene_update_smooth_normals)
         self._transformed = False     # the device holds a transform that is not the identity (cgpt_scene_update_transforms)
         self.instanced = False        # the last upload was cgpt_scene_upload_instanced
+        self._skin_joints = {}        # object -> joint count of the skin set_skin installed (joint_matrices)
 
     def _check(self, rc: int):
         if rc != 0:
@@ -207,6 +208,7 @@ class Renderer:
         rows, j, w = _skin_arrays(bind_triangles, joints, weights)
         self._check(self.L.cgpt_scene_set_skin(self._ctx, obj_index, _triangle_ptr(rows), j.ctypes.data_as(C.POINTER(C.c_uint16)),
                                                w.ctypes.data_as(C.POINTER(C.c_float)), rows.shape[0], int(n_joints)))
+        self._skin_joints[int(obj_index)] = int(n_joints)
 
     def skin_mesh(self, obj_index: int, matrices):
         """cgpt_scene_skin_mesh: poses skinned object `obj_index` on the device from its joint matrices, (n_joints, 3, 4) or
@@ -258,6 +260,51 @@ class Renderer:
                                0 if w is None else w.size, None if w is None else w.ctypes.data_as(C.POINTER(C.c_float))))
         poses = (N.Pose * max(1, len(rows)))(*rows)
         self._check(self.L.cgpt_scene_pose_objects(self._ctx, poses, len(rows)))
+
+    def set_skeleton(self, obj_index: int, parents, inverse_bind, rest, root=None):
+        """cgpt_scene_set_skeleton: keeps a skeleton for the skin of object `obj_index` on the device -- parents (n_joints int32, -1 a
+        root, any order), inverse_bind (n_joints, 12) or (n_joints, 3, 4), rest (n_joints, 10) {T.xyz, R.xyzw, S.xyz} and an optional
+        root matrix (12 floats) -- for animate_objects to pose from.  The object needs a skin with the same joint
+        count; the skeleton is replaced, cleared and dropped with that skin."""
+        desc, keep = _skeleton_desc(parents, inverse_bind, rest, root)
+        self._check(self.L.cgpt_scene_set_skeleton(self._ctx, obj_index, C.byref(desc)))
+
+    def create_clip(self, n_joints: int, channels, times, values) -> int:
+        """cgpt_clip_create: copies an animation clip to the device(s) and returns its handle.  channels: rows of six words {joint,
+        path N.ANIM_PATH_*, interpolation N.ANIM_STEP | N.ANIM_LINEAR, n_keys, first_time, first_value}; key i of a channel is
+        times[first_time + i] with 3 (translation, scale) or 4 (rotation xyzw) floats at values[first_value + width * i].  A clip
+        belongs to the renderer, is shared by any number of objects and survives upload()."""
+        desc, keep = _clip_desc(n_joints, channels, times, values)
+        handle = C.c_uint32()
+        self._check(self.L.cgpt_clip_create(self._ctx, C.byref(desc), C.byref(handle)))
+        return handle.value
+
+    def destroy_clip(self, clip: int):
+        """cgpt_clip_destroy: frees a clip."""
+        self._check(self.L.cgpt_clip_destroy(self._ctx, int(clip)))
+
+    def animate_objects(self, entries):
+        """cgpt_scene_animate_objects: pose_objects with every entry's joint matrices computed on the device.
+        `entries` is an iterable of (obj_index, clip, time, weights or None); the device scene afterwards is what
+        pose_objects([(obj_index, animate_joints(skeleton, clip, time), weights), ...]) leaves, bit for bit, without the matrices
+        being evaluated or uploaded by the host.  A refused call changes nothing.  Call reset_accumulator() before the next frame."""
+        keep, rows = [], []
+        for obj_index, clip, time, weights in entries:
+            w = _morph_weights(weights) if weights is not None else None
+            keep.append(w)
+            rows.append(N.Animation(int(obj_index), int(clip), float(time), 0 if w is None else w.size,
+                                    None if w is None else w.ctypes.data_as(C.POINTER(C.c_float))))
+        table = (N.Animation * max(1, len(rows)))(*rows)
+        self._check(self.L.cgpt_scene_animate_objects(self._ctx, table, len(rows)))
+
+    def joint_matrices(self, obj_index: int, n_joints: Optional[int] = None) -> np.ndarray:
+        """cgpt_scene_get_joint_matrices: the (n_joints, 12) float32 matrices of the last pose of object `obj_index`'s skin, however
+        given (skin_mesh, pose_objects, animate_objects).  n_joints: the skin's count; None takes what set_skin was given."""
+        if n_joints is None:
+            n_joints = self._skin_joints.get(int(obj_index), 1)
+        out = np.empty((int(n_joints), 12), np.float32)
+        self._check(self.L.cgpt_scene_get_joint_matrices(self._ctx, obj_index, out.ctypes.data_as(C.POINTER(C.c_float)), int(n_joints)))
+        return out
 
     def rebuild_mesh(self, obj_index: int, build_option: int = N.BUILD_SAH_BINNED):
         """cgpt_scene_rebuild_mesh: splits the tree of uploaded mesh `obj_index` again, in place on the device, over the triangles its

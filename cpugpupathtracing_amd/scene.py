@@ -167,6 +167,48 @@ def morph_triangles(base_triangles, deltas, weights) -> np.ndarray:
     return out
 
 
+def _skeleton_desc(parents, inverse_bind, rest, root=None):
+    """cgpt_skeleton_desc and the arrays it points into: parents n int32, inverse_bind (n, 12) or (n, 3, 4), rest (n, 10) float32
+    {T.xyz, R.xyzw, S.xyz}, root None or 12 floats."""
+    par = np.ascontiguousarray(parents, np.int32).ravel()
+    ib = np.ascontiguousarray(inverse_bind, np.float32).reshape(-1, 12)
+    rs = np.ascontiguousarray(rest, np.float32).reshape(-1, 10)
+    if ib.shape[0] != par.size or rs.shape[0] != par.size:
+        raise ValueError("a skeleton has one parent, 12 inverse bind floats and 10 rest floats per joint")
+    rt = None if root is None else np.ascontiguousarray(root, np.float32).reshape(12)
+    fp = C.POINTER(C.c_float)
+    desc = N.SkeletonDesc(par.ctypes.data_as(C.POINTER(C.c_int32)), ib.ctypes.data_as(fp), rs.ctypes.data_as(fp),
+                          None if rt is None else rt.ctypes.data_as(fp), par.size)
+    return desc, (par, ib, rs, rt)
+
+
+def _clip_desc(n_joints, channels, times, values):
+    """cgpt_clip_desc and the arrays it points into: channels rows of six words {joint, path, interpolation, n_keys, first_time,
+    first_value} (N.ANIM_*), times and values float32."""
+    ch = np.ascontiguousarray(channels, np.uint32).reshape(-1, 6)
+    t = np.ascontiguousarray(times, np.float32).ravel()
+    v = np.ascontiguousarray(values, np.float32).ravel()
+    fp = C.POINTER(C.c_float)
+    desc = N.ClipDesc(int(n_joints), ch.shape[0], ch.ctypes.data_as(C.POINTER(N.ClipChannel)), t.ctypes.data_as(fp), t.size, v.ctypes.data_as(fp), v.size)
+    return desc, (ch, t, v)
+
+
+def animate_joints(skeleton, clip, time) -> np.ndarray:
+    """Joint matrices from an animation clip on the host (cgpth_animate_joints): the (n_joints, 12) float32 matrices
+    of skeleton = (parents, inverse_bind, rest[, root]) under clip = (n_joints, channels, times, values) at `time` -- sampled (STEP,
+    LINEAR; rotations by normalised lerp), composed up the hierarchy, times the inverse bind matrices.  It is what
+    Renderer.animate_objects computes on the device, to the bit, and what Renderer.pose_objects takes."""
+    sd, keep_s = _skeleton_desc(*skeleton)
+    cd, keep_c = _clip_desc(*clip)
+    out = np.empty((sd.n_joints, 12), np.float32)
+    rc = N.lib().cgpth_animate_joints(C.byref(sd), C.byref(cd), float(time), out.ctypes.data_as(C.POINTER(C.c_float)), sd.n_joints)
+    if rc != 0:
+        e = HostError(f"animate_joints: {N.lib().cgpth_last_error().decode()}")
+        e.code = rc
+        raise e
+    return out
+
+
 def primitive_abi(kind: int, mat_index: int, center=None, radius=None, normal=None, point=None) -> N.Object:
     """A cgpt_object for update_primitive: a sphere (center, radius) or a plane (normal, point)."""
     o = N.Object()

@@ -4,7 +4,7 @@
 //
 //   g++ -std=c++17 -Iinclude -Icpugpupathtracing_amd/csrc/host examples/render_main.cpp
 //       -Lcpugpupathtracing_amd/lib -lcpugpupt -Wl,-rpath,$PWD/cpugpupathtracing_amd/lib -o render_main   (one command line)
-//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--spin DEG] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [--bend DEG] [--bulge W] [--crowd N] [--rebuild [naive|intervals|binned]] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
+//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--spin DEG] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [--bend DEG] [--animate T] [--bulge W] [--crowd N] [--rebuild [naive|intervals|binned]] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
 // --gpus N: ONE context over the first N GPUs of the node (cgpt_ctx_create with n_devices = N): every frame is spread over them in
 // interleaved row bands and the read-back gathers the float4 bands with one RCCL exchange over xGMI; the loop below does not
 // change.  --collective: take that code path with N = 1 too (what a one-GPU box can test).
@@ -59,6 +59,11 @@
 // --bulge W, its morph target), bent by an angle of its own: copy k by DEG (k + 1) / N degrees a frame (DEG from --bend, 10 without it).  All of
 // them are posed by ONE call a frame (cgpt_scene_pose_objects): the launches do not grow with N.  Frames and the temporal
 // call as for --bend (crowd_NN_*.ppm).
+// --animate T: with --bend DEG (and --crowd N), the bend is played from an animation clip on the device instead of from matrices the host
+// computes: every posed mesh gets a two-joint skeleton under its skin (cgpt_scene_set_skeleton) and they all share one generated clip
+// (cgpt_clip_create) whose rotation channel takes joint 1 from 0 to DEG over one second; ONE frame is rendered, at clip time T, posed by
+// cgpt_scene_animate_objects -- with --crowd N character k plays at its own phase, T (k + 1) / N.  The joint matrices
+// never exist on the host.  Frames are named animate_00_*.ppm.
 // --rebuild [OPTION]: with --bend / --bulge / --crowd, every posed mesh's tree is split again in place on the device after each frame's pose
 // (cgpt_scene_rebuild_mesh), with the binned builder unless OPTION says otherwise: the refit keeps a tree that was split
 // for the bind pose, and after a large bend its boxes overlap.  The triangles never leave the device.  A rebuild drops the temporal
@@ -89,7 +94,7 @@ using namespace cgpt;
 
 int main(int argc, char** argv)
 {
-    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool spin = false; float spin_deg = 0.0f; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false; uint32_t n_instances = 0; bool bend = false; float bend_deg = 0.0f; bool bulge = false; float bulge_w = 0.0f; uint32_t crowd = 0;
+    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool spin = false; float spin_deg = 0.0f; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false; uint32_t n_instances = 0; bool bend = false; float bend_deg = 0.0f; bool bulge = false; float bulge_w = 0.0f; uint32_t crowd = 0; bool animate = false; float animate_t = 0.0f;
     bool rebuild = false; uint32_t rebuild_option = CGPT_BUILD_SAH_BINNED;
     bool has_transform = false; float mesh_transform[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
     MeshBVH::BuildOption bvh_option = MeshBVH::BuildOption_SAHSplitIntervals;
@@ -101,6 +106,7 @@ int main(int argc, char** argv)
         else if (std::string(argv[1]) == "--spin" && argc > 2) { spin = true; spin_deg = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--bend" && argc > 2) { bend = true; bend_deg = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--bulge" && argc > 2) { bulge = true; bulge_w = (float)atof(argv[2]); argv += 2; argc -= 2; }
+        else if (std::string(argv[1]) == "--animate" && argc > 2) { animate = true; animate_t = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--crowd" && argc > 2) { crowd = (uint32_t)atoi(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--rebuild") {
             rebuild = true; argv += 1; argc -= 1;
@@ -136,7 +142,7 @@ int main(int argc, char** argv)
     const float move_forward = move_at ? (float)atof(argv[base + 7]) : 0.0f;
 
     Mesh mesh;
-    if (crowd && !bend) { bend = true; bend_deg = 10.0f; }
+    if ((crowd || animate) && !bend) { bend = true; bend_deg = 10.0f; }
     if (model.empty()) mesh = MakeDragonStandIn(crowd ? 4 : 6);
     else { std::string err; if (!GLTFLoader::Load(model, mesh, err)) { fprintf(stderr, "%s\n", err.c_str()); return 1; } }   // ref: Main.cpp:785
     std::vector<Mesh> crowd_meshes;                                      // --crowd: copy k of the mesh, shrunk about its centre and shifted along x
@@ -316,10 +322,29 @@ int main(int argc, char** argv)
             }
         }
 
+        // --animate: the same bend as a clip.  Joint 0 is the root at the origin, joint 1 its child at the pivot; the inverse bind matrices
+        // undo the rest pose, so M_1 = T(pivot) R_x T(-pivot) as below.  One clip for everyone: joint 1's rotation, 0 -> DEG over a second.
+        uint32_t clip = 0;
+        if (animate) {
+            const double half = 0.5 * (double)bend_deg * 3.14159265358979 / 180.0;
+            const cgpt_clip_channel channel = { 1u, CGPT_ANIM_PATH_ROTATION, CGPT_ANIM_LINEAR, 2u, 0u, 0u };
+            const float key_times[2] = { 0.0f, 1.0f };
+            const float key_values[8] = { 0.0f, 0.0f, 0.0f, 1.0f, (float)std::sin(half), 0.0f, 0.0f, (float)std::cos(half) };
+            const cgpt_clip_desc cd = { 2u, 1u, &channel, key_times, 2u, key_values, 8u };
+            CHECK(cgpt_clip_create(ctx, &cd, &clip));
+            for (size_t k = 0; k < posed.size(); ++k) {
+                const float py = pivots[2 * k], pz = pivots[2 * k + 1];
+                const int32_t parents[2] = { -1, 0 };
+                const float inverse_bind[24] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1, 0, 0, 0, 0, 1, 0, -py, 0, 0, 1, -pz };
+                const float rest[20] = { 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 0, py, pz, 0, 0, 0, 1, 1, 1, 1 };
+                const cgpt_skeleton_desc sd = { parents, inverse_bind, rest, nullptr, 2u };
+                CHECK(cgpt_scene_set_skeleton(ctx, posed[k], &sd));
+            }
+        }
         std::vector<uint32_t> px((size_t)W * H);                         // the mesh bends every frame: SkinMesh, ResetAccumulator, Render, present
         const cgpt_camera cam = scene.camera.Abi();
         const cgpt_temporal_params tp = { 64.0f, 0.9f, 0.01f, CGPT_TEMPORAL_FOLLOW_POSES | (bulge ? (uint32_t)CGPT_TEMPORAL_FOLLOW_MORPHS : 0u) };   // each flag keeps its own kind of edit
-        for (uint32_t frame = 0; frame < 8; ++frame) {                   // the pose of this frame: 48 bytes a joint go to the device
+        for (uint32_t frame = 0; frame < (animate ? 1u : 8u); ++frame) {  // the pose of this frame: 48 bytes a joint go to the device
             std::vector<float> joint_matrices(24 * posed.size());
             for (size_t k = 0; k < posed.size(); ++k) {                  // copy k of a crowd bends by its own share of the angle
                 const double share = crowd ? (double)(k + 1) / (double)crowd : 1.0;
@@ -331,7 +356,12 @@ int main(int argc, char** argv)
                 for (int i = 0; i < 24; ++i) joint_matrices[24 * k + i] = m[i];
             }
             const float morph_weight = bulge_w * (float)frame / 7.0f;
-            if (crowd) {                                                 // every copy in one call: an entry with both arrays is posed once, by the fused kernel
+            if (animate) {                                               // a clip and a time per object: nothing else goes to the device
+                std::vector<cgpt_animation> entries(posed.size());
+                for (size_t k = 0; k < posed.size(); ++k)
+                    entries[k] = { posed[k], clip, crowd ? animate_t * (float)(k + 1) / (float)crowd : animate_t, bulge ? 1u : 0u, bulge ? &morph_weight : nullptr };
+                CHECK(cgpt_scene_animate_objects(ctx, entries.data(), (uint32_t)entries.size()));
+            } else if (crowd) {                                          // every copy in one call: an entry with both arrays is posed once, by the fused kernel
                 std::vector<cgpt_pose> poses(posed.size());
                 for (size_t k = 0; k < posed.size(); ++k) poses[k] = { posed[k], 2u, joint_matrices.data() + 24 * k, bulge ? 1u : 0u, bulge ? &morph_weight : nullptr };
                 CHECK(cgpt_scene_pose_objects(ctx, poses.data(), (uint32_t)poses.size()));
@@ -353,7 +383,7 @@ int main(int argc, char** argv)
             CHECK(cgpt_render(ctx, &cam, &settings, &p));
             char name[64]; std::string err;
             CHECK(cgpt_read_pixels(ctx, px.data(), px.size()));
-            const char* tag = crowd ? "crowd" : bend ? "bend" : "bulge";
+            const char* tag = animate ? "animate" : crowd ? "crowd" : bend ? "bend" : "bulge";
             snprintf(name, sizeof(name), "%s_%02u_raw.ppm", tag, frame); WritePPM(name, px.data(), W, H, err);
             CHECK(cgpt_denoise(ctx, &cam, nullptr, nullptr, 0, px.data(), px.size()));
             snprintf(name, sizeof(name), "%s_%02u_denoised.ppm", tag, frame); WritePPM(name, px.data(), W, H, err);

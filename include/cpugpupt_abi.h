@@ -462,6 +462,66 @@ typedef struct cgpt_pose {
 } cgpt_pose;
 int cgpt_scene_pose_objects(cgpt_ctx* ctx, const cgpt_pose* poses, uint32_t n_poses);
 
+/* ---- animation clips: joint matrices computed on the device from keyframes ----
+ * cgpt_scene_animate_objects is cgpt_scene_pose_objects with each entry's joint matrices computed on the device: the clip, the skeleton
+ * and the skin are resident, a frame of an animated scene is one call with a clip and a time per object.  csrc/host/animation.h states
+ * the arithmetic -- sampling (STEP, LINEAR; rotations by normalised lerp, not slerp), the local matrices, the bottom-up walk, the
+ * inverse bind matrix, the root -- cgpth_animate_joints evaluates it on the host, tests/anim_ref.py in numpy, and the device agrees
+ * with both bit for bit.  The data layout is glTF's.  Added exports: CGPT_ABI_VERSION stays 2.
+ *
+ * cgpt_scene_set_skeleton: copies a skeleton for the skin of object obj_index: parents (one per joint, -1 a root, any order),
+ * inverse_bind (12 floats a joint, the rows of [A | b]), rest (10 floats a joint: T.xyz, R.xyzw, S.xyz) and an optional root matrix
+ * (NULL: no multiply).  The object needs a skin with the same n_joints; the skeleton is replaced, cleared and dropped with that skin.
+ * Refused (CGPT_ERR_INVALID): no skin, another joint count, a NULL array, a parent out of range, a cycle, a float that is not finite.
+ *
+ * cgpt_clip_create: copies a clip to every device of the context and returns its handle.  A clip belongs to the context, is shared by
+ * any number of objects and survives uploads.  A channel animates one path of one joint: key i is times[first_time + i] with the 3
+ * floats (translation, scale) or 4 floats (rotation xyzw) at values[first_value + width i].  At most one channel per (joint, path);
+ * n_keys >= 1; times finite and strictly increasing; values finite; counts within times / values: otherwise CGPT_ERR_INVALID.
+ * CGPT_ANIM_CUBICSPLINE: CGPT_ERR_UNSUPPORTED.  glTF `weights` channels are not built: morph weights come from the caller.
+ * cgpt_clip_destroy: frees it; an unknown handle is CGPT_ERR_INVALID.
+ *
+ * cgpt_scene_animate_objects: phase 1 refuses whatever cgpt_scene_pose_objects refuses, and: an object without a skeleton, an unknown
+ * or destroyed clip, a clip whose n_joints differs from the skeleton's, a time that is not finite; then one kernel evaluates every
+ * entry's matrices and, after one synchronise, the host reads them back.  An entry with a matrix entry that is not finite refuses the
+ * whole call (CGPT_ERR_INVALID with the entry's index): scene, guides, history and generations stay untouched.  Phase 2 is
+ * cgpt_scene_pose_objects' own, reading the matrices where the kernel wrote them; they become the skin's last pose exactly as if the
+ * caller had passed them, so the single calls, CGPT_TEMPORAL_FOLLOW_POSES / _MORPHS, cgpt_read_previous_hits, instanced groups and
+ * cgpt_scene_rebuild_mesh follow without further work.  weights / n_targets are cgpt_pose's.
+ *
+ * cgpt_scene_get_joint_matrices: the n_joints x 12 matrices of the skin's last pose, however given.  CGPT_ERR_INVALID before one. */
+enum { CGPT_ANIM_PATH_TRANSLATION = 0, CGPT_ANIM_PATH_ROTATION = 1, CGPT_ANIM_PATH_SCALE = 2 };
+enum { CGPT_ANIM_STEP = 0, CGPT_ANIM_LINEAR = 1, CGPT_ANIM_CUBICSPLINE = 2 };
+typedef struct cgpt_skeleton_desc {
+    const int32_t* parents;
+    const float* inverse_bind;
+    const float* rest;
+    const float* root;
+    uint32_t n_joints;
+} cgpt_skeleton_desc;
+typedef struct cgpt_clip_channel {
+    uint32_t joint, path, interpolation, n_keys, first_time, first_value;
+} cgpt_clip_channel;
+typedef struct cgpt_clip_desc {
+    uint32_t n_joints, n_channels;
+    const cgpt_clip_channel* channels;
+    const float* times;
+    uint32_t n_times;
+    const float* values;
+    uint32_t n_values;
+} cgpt_clip_desc;
+typedef struct cgpt_animation {
+    uint32_t obj_index, clip;
+    float time;
+    uint32_t n_targets;           /* 0: this entry gives no morph weights */
+    const float* weights;         /* n_targets, as cgpt_scene_morph_mesh takes them */
+} cgpt_animation;
+int cgpt_scene_set_skeleton(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_skeleton_desc* skeleton);
+int cgpt_clip_create(cgpt_ctx* ctx, const cgpt_clip_desc* clip, uint32_t* clip_out);
+int cgpt_clip_destroy(cgpt_ctx* ctx, uint32_t clip);
+int cgpt_scene_animate_objects(cgpt_ctx* ctx, const cgpt_animation* entries, uint32_t n_entries);
+int cgpt_scene_get_joint_matrices(cgpt_ctx* ctx, uint32_t obj_index, float* out, uint32_t n_joints);
+
 /* UpdateScreenPlane (ref: Main.cpp:98-102,143-149): fov in degrees, plane at distance fov-in-radians (SURVEY A-13) */
 int cgpt_camera_from_view(const float pos[3], const float view_dir[3], float fov_deg, float aspect, cgpt_camera* out);
 

@@ -129,6 +129,13 @@ int cgpth_morph_triangles(const cgpt_triangle* base_triangles, const cgpt_triang
  * what cgpth_morph_triangles refuses.  A morphed and skinned object is cgpth_scene_skin_mesh with the morphed triangles as its bind pose. */
 int cgpth_scene_morph_mesh(cgpth_scene* scene, uint32_t obj_index, const cgpt_triangle* base_triangles, const cgpt_triangle* target_deltas,
                            uint32_t n_tris, uint32_t n_targets, const float* weights);
+/* Joint matrices from an animation clip, the host statement of cgpt_scene_animate_objects' kernel (csrc/host/animation.h states the
+ * operations and their order; tests/anim_ref.py the same in numpy): out gets the skeleton's n_joints x 12 floats, the
+ * rows of [A | b] of every joint's skinning matrix under `clip` at time t -- what cgpt_scene_pose_objects takes.  Refused with nothing
+ * written: whatever cgpt_scene_set_skeleton refuses of a skeleton and cgpt_clip_create of a clip (CGPT_ERR_UNSUPPORTED for
+ * CUBICSPLINE, else CGPT_ERR_INVALID), a clip whose n_joints differs from the skeleton's, n_joints other than the skeleton's, a time
+ * that is not finite, out NULL. */
+int cgpth_animate_joints(const cgpt_skeleton_desc* skeleton, const cgpt_clip_desc* clip, float time, float* out, uint32_t n_joints);
 /* the host statement of cgpt_scene_update_primitive: a sphere's centre and radius, or a plane's normal and point */
 int cgpth_scene_update_primitive(cgpth_scene* scene, uint32_t obj_index, const cgpt_object* obj);
 /* reorders the objects: the new object k is the old object order[k] (a permutation of 0 .. n_objects - 1, else refused and nothing
