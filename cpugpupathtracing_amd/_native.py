@@ -31,6 +31,8 @@ SKIN_MAX_JOINTS = 1024      # cgpt_scene_set_skin
 MORPH_MAX_TARGETS = 256     # cgpt_scene_set_morph_targets
 ANIM_PATH_TRANSLATION, ANIM_PATH_ROTATION, ANIM_PATH_SCALE = 0, 1, 2   # cgpt_clip_channel.path
 ANIM_STEP, ANIM_LINEAR, ANIM_CUBICSPLINE = 0, 1, 2                     # cgpt_clip_channel.interpolation
+ANIM_WRAP_CLAMP, ANIM_WRAP_LOOP, ANIM_WRAP_PINGPONG = 0, 1, 2          # cgpt_clip_layer.wrap
+ANIM_MAX_LAYERS = 4
 HIP_STREAM_LEGACY, HIP_STREAM_PER_THREAD = 1, 2   # hipStreamLegacy, hipStreamPerThread (hip_runtime_api.h): refused by cgpt_set_stream
 
 f3 = C.c_float * 3
@@ -194,6 +196,16 @@ class Animation(C.Structure):
     _fields_ = [("obj_index", C.c_uint32), ("clip", C.c_uint32), ("time", C.c_float), ("n_targets", C.c_uint32), ("weights", _fp)]
 
 
+class ClipLayer(C.Structure):
+    """cgpt_clip_layer: one clip of a blend, its time, weight and wrap mode"""
+    _fields_ = [("clip", C.c_uint32), ("time", C.c_float), ("weight", C.c_float), ("wrap", C.c_uint32)]
+
+
+class LayeredAnimation(C.Structure):
+    """cgpt_layered_animation: one entry of cgpt_scene_animate_layers"""
+    _fields_ = [("obj_index", C.c_uint32), ("n_layers", C.c_uint32), ("layers", C.POINTER(ClipLayer)), ("n_targets", C.c_uint32), ("weights", _fp)]
+
+
 class SceneFootprint(C.Structure):
     """cgpt_scene_footprint"""
     _fields_ = [("device_bytes", C.c_uint64), ("n_objects", C.c_uint32), ("n_mesh_objects", C.c_uint32), ("n_mesh_copies", C.c_uint32),
@@ -238,6 +250,8 @@ PROTOTYPES = {
     "cgpt_clip_create": (C.c_int, [_vp, C.POINTER(ClipDesc), _up]),
     "cgpt_clip_destroy": (C.c_int, [_vp, C.c_uint32]),
     "cgpt_scene_animate_objects": (C.c_int, [_vp, C.POINTER(Animation), C.c_uint32]),
+    "cgpt_scene_animate_layers": (C.c_int, [_vp, C.POINTER(LayeredAnimation), C.c_uint32]),
+    "cgpt_clip_get_range": (C.c_int, [_vp, C.c_uint32, _fp, _fp]),
     "cgpt_scene_get_joint_matrices": (C.c_int, [_vp, C.c_uint32, _fp, C.c_uint32]),
     "cgpt_camera_from_view": (C.c_int, [_fp, _fp, C.c_float, C.c_float, C.POINTER(Camera)]),
     "cgpt_render": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(Settings), C.POINTER(RenderParams)]),
@@ -312,6 +326,9 @@ PROTOTYPES = {
     "cgpth_morph_triangles": (C.c_int, [C.POINTER(Triangle), C.POINTER(Triangle), C.c_uint32, C.c_uint32, _fp, C.POINTER(Triangle)]),
     "cgpth_scene_morph_mesh": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), C.POINTER(Triangle), C.c_uint32, C.c_uint32, _fp]),
     "cgpth_animate_joints": (C.c_int, [C.POINTER(SkeletonDesc), C.POINTER(ClipDesc), C.c_float, _fp, C.c_uint32]),
+    "cgpth_animate_layers": (C.c_int, [C.POINTER(SkeletonDesc), C.POINTER(ClipDesc), C.POINTER(ClipLayer), C.c_uint32, _fp, C.c_uint32]),
+    "cgpth_clip_range": (C.c_int, [C.POINTER(ClipDesc), _fp, _fp]),
+    "cgpth_wrap_time": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_uint32, _fp]),
     "cgpth_scene_update_primitive": (C.c_int, [_vp, C.c_uint32, C.POINTER(Object)]),
     "cgpth_scene_bvh_info": (C.c_int, [_vp, C.c_uint32, C.POINTER(BvhInfo)]),
     "cgpth_scene_bvh_export": (C.c_int, [_vp, C.c_uint32, C.POINTER(BvhNode), _up]),

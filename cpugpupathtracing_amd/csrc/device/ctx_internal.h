@@ -27,7 +27,7 @@ struct SceneBuffers {                             // cgpt_scene_upload installs 
     DevBuf<cgpt_triangle> refit_staging;          // host triangles of the last refit, grown on demand
     DevBuf<uint32_t> skin_scratch;                // cgpt_scene_skin_mesh: 8 words a pose reads back (refit.hip: kSkinScratchWords), allocated with the first skin
     DevBuf<uint32_t> pose_batch;                  // cgpt_scene_pose_objects: the tables and scratch of the last batch (refit.hip: PoseObjects), grown on demand
-    DevBuf<uint32_t> anim_batch;                  // cgpt_scene_animate_objects: per entry a flag word, then the entry records animate_joints_batch reads, grown on demand
+    DevBuf<uint32_t> anim_batch;                  // cgpt_scene_animate_objects / _layers: per entry a flag word, then the entry records the kernel reads, grown on demand
 };
 // The skin of one object (cgpt_scene_set_skin): the bind pose, 12 joint indices and 12 weights a triangle, and the room of a pose's
 // joint matrices.  Not part of the scene's footprint; an upload drops every skin.
@@ -55,6 +55,7 @@ struct ClipBuffers {
     DevBuf<uint32_t> map, channels;
     DevBuf<float> times, values;
     uint32_t n_joints = 0;                        // 0: a destroyed clip's slot
+    float begin = 0.0f, end = 0.0f;               // the clip's range (animation.h: ClipTable), what a layer's wrap mode wraps over
 };
 // The morph targets of one object (cgpt_scene_set_morph_targets): the base triangle and the n_targets displacement
 // records of every triangle in one buffer of float2 -- set 0 is the base, set 1 + k is target k.  leaf_order: set s, plane p (0..8, two of
@@ -347,6 +348,7 @@ int GroupSetSkeleton(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_skeleton_desc
 int GroupClipCreate(cgpt_ctx* ctx, const cgpt_clip_desc* clip, uint32_t* clip_out);
 int GroupClipDestroy(cgpt_ctx* ctx, uint32_t clip);
 int GroupAnimateObjects(cgpt_ctx* ctx, const cgpt_animation* entries, uint32_t n_entries);
+int GroupAnimateLayers(cgpt_ctx* ctx, const cgpt_layered_animation* entries, uint32_t n_entries);
 int GroupRebuildMesh(cgpt_ctx* ctx, uint32_t obj_index, uint32_t build_option, uint32_t* n_nodes_out, uint32_t* max_depth_out);
 int GroupRender(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p);
 int GroupResetAccumulator(cgpt_ctx* ctx);

@@ -418,6 +418,11 @@ int GroupAnimateObjects(cgpt_ctx* ctx, const cgpt_animation* entries, uint32_t n
     return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_animate_objects(m, entries, n_entries); });
 }
 
+int GroupAnimateLayers(cgpt_ctx* ctx, const cgpt_layered_animation* entries, uint32_t n_entries)
+{
+    return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_animate_layers(m, entries, n_entries); });
+}
+
 // a clip is no part of the scene: every member holds a copy under the same handle (the members' handles advance in step), and a member
 // that cannot take it leaves the others without it
 int GroupClipCreate(cgpt_ctx* ctx, const cgpt_clip_desc* clip, uint32_t* clip_out)

@@ -27,7 +27,8 @@
 // grow with their count -- pose_plan.h plans the batch on the host, PoseObjects runs it through batched shells of the kernels above.
 // Animation clips (cgpt_scene_animate_objects): that batch with every entry's joint matrices evaluated on the device first, by
 // the arithmetic of csrc/host/animation.h, from a resident skeleton and clip (animate_joints_batch); PoseObjects then reads them where
-// the kernel wrote them.
+// the kernel wrote them.  cgpt_scene_animate_layers is the same call with each joint's T / R / S blended from up to four
+// clips at wrapped times before the hierarchy walk (animate_layers_batch).
 // After cgpt_scene_upload_instanced the objects of a mesh group share the one copy these passes edit: the refit goes through any member's
 // RefitObject (they are equal), and the area and the top-level box, which are per object, are written for every member.
 #include <hip/hip_runtime.h>
@@ -508,6 +509,51 @@ __global__ __launch_bounds__(kRefitThreads) void animate_joints_batch(const Anim
     if (!finite) atomicOr(flags + blockIdx.x, 1u);
 }
 
+// ---- ... from a blend of clips (cgpt_scene_animate_layers) -------------------------------------------------------------
+// One entry as animate_layers_batch reads it: 208 bytes, block-uniform.  The host has compacted the active layers (weight > 0), wrapped
+// their times and normalised their weights (animation.h: ResolveLayers), so layers[0 .. n_layers) are all sampled
+struct AnimLayersEntryRecord {
+    const int32_t* parents;
+    const float* inverse_bind;
+    const float* rest;
+    const float* root;                                                        // null: no root multiply
+    AnimLayer layers[CGPT_ANIM_MAX_LAYERS];
+    uint32_t n_joints, matrix_base, n_layers, pad;
+};
+// animate_joints_batch with each lane's T, q, S blended from the entry's layers in registers (animation.h: AnimBlendJoint) before L_j
+// goes to the same 48-byte LDS records; the layer loop's bound and every layer's record are block-uniform (scalar loads), so a launch
+// mixes one-layer and four-layer entries freely.  The walk, the output and the flag word are animate_joints_batch's.
+__global__ __launch_bounds__(kRefitThreads) void animate_layers_batch(const AnimLayersEntryRecord* __restrict__ entries, float4* __restrict__ matrices, uint32_t* __restrict__ flags)
+{
+    extern __shared__ float4 s_locals[];
+    const AnimLayersEntryRecord* __restrict__ e = entries + blockIdx.x;
+    const uint32_t n_joints = e->n_joints, n_layers = e->n_layers;
+    const float* rest = e->rest;
+    for (uint32_t j = threadIdx.x; j < n_joints; j += blockDim.x) {
+        float T[3], q[4], S[3], L[12];
+        AnimBlendJoint(e->layers, n_layers, rest, j, T, q, S);
+        AnimComposeLocal(T, q, S, L);
+        s_locals[3 * j] = make_float4(L[0], L[1], L[2], L[3]);
+        s_locals[3 * j + 1] = make_float4(L[4], L[5], L[6], L[7]);
+        s_locals[3 * j + 2] = make_float4(L[8], L[9], L[10], L[11]);
+    }
+    __syncthreads();
+    float4* out = matrices + 3 * (size_t)e->matrix_base;
+    const int32_t* parents = e->parents;
+    const float* inverse_bind = e->inverse_bind;
+    const float* root = e->root;
+    bool finite = true;
+    for (uint32_t j = threadIdx.x; j < n_joints; j += blockDim.x) {
+        float M[12];
+        AnimJointMatrix(reinterpret_cast<const float*>(s_locals), parents, inverse_bind, root, j, M);
+        for (int i = 0; i < 12; ++i) finite = finite && fabsf(M[i]) < INFINITY;   // false for a NaN too
+        out[3 * j] = make_float4(M[0], M[1], M[2], M[3]);
+        out[3 * j + 1] = make_float4(M[4], M[5], M[6], M[7]);
+        out[3 * j + 2] = make_float4(M[8], M[9], M[10], M[11]);
+    }
+    if (!finite) atomicOr(flags + blockIdx.x, 1u);
+}
+
 const char* KindName(uint32_t kind)
 {
     return kind == CGPT_OBJECT_MESH ? "mesh" : kind == CGPT_OBJECT_SPHERE ? "sphere" : kind == CGPT_OBJECT_PLANE ? "plane" : "triangle object";
@@ -915,7 +961,14 @@ int ClearMorphTargets(cgpt_ctx* ctx, uint32_t obj_index)
 // them, and those calls upload them again themselves.
 // `anim` (cgpt_scene_animate_objects): entry i's joint_matrices is null and its matrices are those of anim[i], evaluated on the device
 // between the upload and the first write (AnimateEntries) and read by the triangle pass where they were written.
-struct AnimResolved { const SkinBuffers* skin; const ClipBuffers* clip; float time; };
+// n_layers != 0 (cgpt_scene_animate_layers): the entry's active layers instead, compacted, times wrapped, weights normalised; a batch is
+// all of one kind
+struct AnimResolved {
+    const SkinBuffers* skin; const ClipBuffers* clip; float time;
+    uint32_t n_layers = 0;
+    const ClipBuffers* layer_clip[CGPT_ANIM_MAX_LAYERS] = {};
+    float layer_time[CGPT_ANIM_MAX_LAYERS] = {}, layer_weight[CGPT_ANIM_MAX_LAYERS] = {};
+};
 int AnimateEntries(cgpt_ctx* ctx, const AnimResolved* anim, const cgpt_pose* poses, uint32_t n_poses, const PosePlan& plan, float* d_matrices,
                    std::vector<std::vector<float>>& kept_matrices);
 
@@ -1110,27 +1163,46 @@ int AnimateEntries(cgpt_ctx* ctx, const AnimResolved* anim, const cgpt_pose* pos
                    std::vector<std::vector<float>>& kept_matrices)
 {
     static_assert(sizeof(AnimEntryRecord) == 80 && sizeof(AnimChannel) == 16, "the entry table's parts");
+    static_assert(sizeof(AnimLayer) == 40 && sizeof(AnimLayersEntryRecord) == 208, "the layered entry table's parts");
     const size_t n = plan.entries.size();
-    const size_t records_at = (n + 3) / 4 * 4, total = records_at + sizeof(AnimEntryRecord) / 4 * n;
+    const bool layered = n_poses != 0u && anim[0].n_layers != 0u;             // cgpt_scene_animate_layers: its own record and kernel
+    const size_t record_words = (layered ? sizeof(AnimLayersEntryRecord) : sizeof(AnimEntryRecord)) / 4;
+    const size_t records_at = (n + 3) / 4 * 4, total = records_at + record_words * n;
     std::vector<uint32_t> blob(total, 0u);                                     // flags | records
     uint32_t max_joints = 0;
     for (size_t k = 0; k < n; ++k) {
         const PosePlanEntry& e = plan.entries[k];
         const AnimResolved& a = anim[e.source];
-        AnimEntryRecord rec{};
-        rec.parents = a.skin->parents.p; rec.inverse_bind = a.skin->inverse_bind.p; rec.rest = a.skin->rest.p;
-        rec.root = a.skin->has_root ? a.skin->root.p : nullptr;
-        rec.map = a.clip->map.p; rec.channels = reinterpret_cast<const AnimChannel*>(a.clip->channels.p); rec.times = a.clip->times.p; rec.values = a.clip->values.p;
-        rec.n_joints = e.n_joints; rec.matrix_base = e.matrix_base; rec.time = a.time;
-        memcpy(blob.data() + records_at + sizeof(AnimEntryRecord) / 4 * k, &rec, sizeof(rec));
+        if (layered) {
+            AnimLayersEntryRecord rec{};
+            rec.parents = a.skin->parents.p; rec.inverse_bind = a.skin->inverse_bind.p; rec.rest = a.skin->rest.p;
+            rec.root = a.skin->has_root ? a.skin->root.p : nullptr;
+            for (uint32_t l = 0; l < a.n_layers; ++l) {
+                const ClipBuffers& c = *a.layer_clip[l];
+                rec.layers[l] = { c.map.p, reinterpret_cast<const AnimChannel*>(c.channels.p), c.times.p, c.values.p, a.layer_time[l], a.layer_weight[l] };
+            }
+            rec.n_joints = e.n_joints; rec.matrix_base = e.matrix_base; rec.n_layers = a.n_layers;
+            memcpy(blob.data() + records_at + record_words * k, &rec, sizeof(rec));
+        } else {
+            AnimEntryRecord rec{};
+            rec.parents = a.skin->parents.p; rec.inverse_bind = a.skin->inverse_bind.p; rec.rest = a.skin->rest.p;
+            rec.root = a.skin->has_root ? a.skin->root.p : nullptr;
+            rec.map = a.clip->map.p; rec.channels = reinterpret_cast<const AnimChannel*>(a.clip->channels.p); rec.times = a.clip->times.p; rec.values = a.clip->values.p;
+            rec.n_joints = e.n_joints; rec.matrix_base = e.matrix_base; rec.time = a.time;
+            memcpy(blob.data() + records_at + record_words * k, &rec, sizeof(rec));
+        }
         max_joints = std::max(max_joints, e.n_joints);
     }
     std::vector<float> back(12 * (size_t)plan.n_matrix_joints);
     std::vector<uint32_t> flags(n);
     HIP_TRY(ctx, ctx->sb.anim_batch.Grow(total));                              // the caller drained the stream: nothing uses the old one
     HIP_TRY(ctx, hipMemcpyAsync(ctx->sb.anim_batch.p, blob.data(), sizeof(uint32_t) * total, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(animate_joints_batch, dim3((uint32_t)n), dim3(kRefitThreads), 3 * sizeof(float4) * (size_t)max_joints, ctx->stream,
-                       reinterpret_cast<const AnimEntryRecord*>(ctx->sb.anim_batch.p + records_at), reinterpret_cast<float4*>(d_matrices), ctx->sb.anim_batch.p);
+    if (layered)
+        hipLaunchKernelGGL(animate_layers_batch, dim3((uint32_t)n), dim3(kRefitThreads), 3 * sizeof(float4) * (size_t)max_joints, ctx->stream,
+                           reinterpret_cast<const AnimLayersEntryRecord*>(ctx->sb.anim_batch.p + records_at), reinterpret_cast<float4*>(d_matrices), ctx->sb.anim_batch.p);
+    else
+        hipLaunchKernelGGL(animate_joints_batch, dim3((uint32_t)n), dim3(kRefitThreads), 3 * sizeof(float4) * (size_t)max_joints, ctx->stream,
+                           reinterpret_cast<const AnimEntryRecord*>(ctx->sb.anim_batch.p + records_at), reinterpret_cast<float4*>(d_matrices), ctx->sb.anim_batch.p);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(back.data(), d_matrices, sizeof(float) * back.size(), hipMemcpyDeviceToHost));
@@ -1139,7 +1211,8 @@ int AnimateEntries(cgpt_ctx* ctx, const AnimResolved* anim, const cgpt_pose* pos
     for (size_t k = 0; k < n; ++k)
         if (flags[k] != 0u) refused = std::min(refused, plan.entries[k].source);
     if (refused != n_poses)
-        return CtxFail(ctx, CGPT_ERR_INVALID, "entry %u: object %u: a joint matrix of the clip at time %g is not finite", refused, poses[refused].obj_index, (double)anim[refused].time);
+        return layered ? CtxFail(ctx, CGPT_ERR_INVALID, "entry %u: object %u: a joint matrix of the blended layers is not finite", refused, poses[refused].obj_index)
+                       : CtxFail(ctx, CGPT_ERR_INVALID, "entry %u: object %u: a joint matrix of the clip at time %g is not finite", refused, poses[refused].obj_index, (double)anim[refused].time);
     for (size_t k = 0; k < n; ++k) {
         const PosePlanEntry& e = plan.entries[k];
         const float* m = back.data() + 12 * (size_t)e.matrix_base;
@@ -1196,6 +1269,7 @@ int ClipCreate(cgpt_ctx* ctx, const cgpt_clip_desc* desc, uint32_t* clip_out)
     HIP_TRY(ctx, up(cb.times, table.times.data(), table.times.size(), sizeof(float)));
     HIP_TRY(ctx, up(cb.values, table.values.data(), table.values.size(), sizeof(float)));
     cb.n_joints = table.n_joints;
+    cb.begin = table.begin; cb.end = table.end;
     ctx->clips.push_back(std::move(cb));                                       // a handle is never given twice
     *clip_out = (uint32_t)ctx->clips.size();
     return CGPT_OK;
@@ -1238,6 +1312,54 @@ int AnimateObjects(cgpt_ctx* ctx, const cgpt_animation* entries, uint32_t n)
         anim[i] = { &ctx->skins[o], clip, a.time };
     }
     return PoseObjects(ctx, poses.data(), n, anim.data());
+}
+
+// cgpt_scene_animate_layers: AnimateObjects with every entry's layers checked, their times wrapped and their weights normalised here
+// (animation.h: ResolveLayers), so the kernel receives plain times as animate_joints_batch does
+int AnimateLayers(cgpt_ctx* ctx, const cgpt_layered_animation* entries, uint32_t n)
+{
+    if (n == 0u) return CGPT_OK;
+    if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "no scene uploaded");
+    if (!entries) return CtxFail(ctx, CGPT_ERR_INVALID, "entries is null");
+    std::vector<cgpt_pose> poses(n);
+    std::vector<AnimResolved> anim(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const cgpt_layered_animation& a = entries[i];
+        const uint32_t o = a.obj_index;
+        const ClipBuffers* clips[CGPT_ANIM_MAX_LAYERS] = {};
+        float ranges[CGPT_ANIM_MAX_LAYERS][2] = {};
+        int rc = CheckObject(ctx, o);
+        if (rc == CGPT_OK && (o >= ctx->skins.size() || ctx->skins[o].n_joints == 0u || !ctx->skins[o].has_skeleton))
+            rc = CtxFail(ctx, CGPT_ERR_INVALID, "object %u has no skeleton (cgpt_scene_set_skeleton installs one on its skin)", o);
+        if (rc == CGPT_OK && !a.layers) rc = CtxFail(ctx, CGPT_ERR_INVALID, "layers is null");
+        if (rc == CGPT_OK && (a.n_layers == 0u || a.n_layers > CGPT_ANIM_MAX_LAYERS)) rc = CtxFail(ctx, CGPT_ERR_INVALID, "n_layers %u outside [1, %u]", a.n_layers, CGPT_ANIM_MAX_LAYERS);
+        for (uint32_t l = 0; rc == CGPT_OK && l < a.n_layers; ++l) {           // every layer's clip, inactive ones included
+            const uint32_t handle = a.layers[l].clip;
+            clips[l] = FindClip(ctx, handle);
+            if (!clips[l]) rc = CtxFail(ctx, CGPT_ERR_INVALID, "layer %u: clip %u is unknown or destroyed", l, handle);
+            else if (clips[l]->n_joints != ctx->skins[o].n_joints)
+                rc = CtxFail(ctx, CGPT_ERR_INVALID, "layer %u: clip %u animates %u joints, object %u's skeleton has %u", l, handle, clips[l]->n_joints, o, ctx->skins[o].n_joints);
+            else { ranges[l][0] = clips[l]->begin; ranges[l][1] = clips[l]->end; }
+        }
+        AnimActiveLayers active;
+        std::string why;
+        if (rc == CGPT_OK && !ResolveLayers(a.layers, a.n_layers, ranges, active, why)) rc = CtxFail(ctx, CGPT_ERR_INVALID, "%s", why.c_str());
+        if (rc != CGPT_OK) { ctx->error = "entry " + std::to_string(i) + ": " + ctx->error; return rc; }
+        poses[i] = cgpt_pose{ o, ctx->skins[o].n_joints, nullptr, a.n_targets, a.weights };
+        AnimResolved& r = anim[i];
+        r.skin = &ctx->skins[o]; r.clip = nullptr; r.time = 0.0f; r.n_layers = active.n;
+        for (uint32_t k = 0; k < active.n; ++k) { r.layer_clip[k] = clips[active.index[k]]; r.layer_time[k] = active.time[k]; r.layer_weight[k] = active.weight[k]; }
+    }
+    return PoseObjects(ctx, poses.data(), n, anim.data());
+}
+
+int ClipGetRange(cgpt_ctx* ctx, uint32_t clip, float* begin, float* end)
+{
+    const ClipBuffers* c = FindClip(ctx, clip);
+    if (!c) return CtxFail(ctx, CGPT_ERR_INVALID, "clip %u is unknown or destroyed", clip);
+    if (begin) *begin = c->begin;
+    if (end) *end = c->end;
+    return CGPT_OK;
 }
 
 int GetJointMatrices(cgpt_ctx* ctx, uint32_t obj_index, float* out, uint32_t n_joints)
@@ -1479,6 +1601,20 @@ int cgpt_scene_animate_objects(cgpt_ctx* ctx, const cgpt_animation* entries, uin
     if (!ctx) return CGPT_ERR_INVALID;
     if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupAnimateObjects(ctx, entries, n_entries); });
     return Guarded(ctx, __func__, [&] { return AnimateObjects(ctx, entries, n_entries); });   // bumps the generations once the batch is accepted
+}
+
+int cgpt_scene_animate_layers(cgpt_ctx* ctx, const cgpt_layered_animation* entries, uint32_t n_entries)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupAnimateLayers(ctx, entries, n_entries); });
+    return Guarded(ctx, __func__, [&] { return AnimateLayers(ctx, entries, n_entries); });
+}
+
+int cgpt_clip_get_range(cgpt_ctx* ctx, uint32_t clip, float* begin, float* end)
+{
+    if (!ctx) return CGPT_ERR_INVALID;
+    if (ctx->group) return GroupForwarded(ctx, cgpt_clip_get_range(GroupFirstMember(ctx), clip, begin, end));
+    return Guarded(ctx, __func__, [&] { return ClipGetRange(ctx, clip, begin, end); });
 }
 
 int cgpt_scene_get_joint_matrices(cgpt_ctx* ctx, uint32_t obj_index, float* out, uint32_t n_joints)

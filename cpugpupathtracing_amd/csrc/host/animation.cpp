@@ -15,6 +15,48 @@ void AnimateJoints(const cgpt_skeleton_desc& s, const ClipTable& clip, float t, 
         AnimJointMatrix(locals.data(), s.parents, s.inverse_bind, s.root, j, out + 12 * (size_t)j);
 }
 
+void AnimateLayers(const cgpt_skeleton_desc& s, const ClipTable* const* clips, const AnimActiveLayers& active, float* out)
+{
+    AnimLayer layers[CGPT_ANIM_MAX_LAYERS];
+    for (uint32_t k = 0; k < active.n; ++k) {
+        const ClipTable& c = *clips[active.index[k]];
+        layers[k] = { c.map.data(), c.channels.data(), c.times.data(), c.values.data(), active.time[k], active.weight[k] };
+    }
+    std::vector<float> locals(12 * (size_t)s.n_joints);
+    for (uint32_t j = 0; j < s.n_joints; ++j) {
+        float T[3], q[4], S[3];
+        AnimBlendJoint(layers, active.n, s.rest, j, T, q, S);
+        AnimComposeLocal(T, q, S, locals.data() + 12 * (size_t)j);
+    }
+    for (uint32_t j = 0; j < s.n_joints; ++j)
+        AnimJointMatrix(locals.data(), s.parents, s.inverse_bind, s.root, j, out + 12 * (size_t)j);
+}
+
+bool ResolveLayers(const cgpt_clip_layer* layers, uint32_t n_layers, const float (*ranges)[2], AnimActiveLayers& active, std::string& error)
+{
+    AnimActiveLayers out;
+    for (uint32_t l = 0; l < n_layers; ++l) {
+        const cgpt_clip_layer& y = layers[l];
+        const std::string where = "layer " + std::to_string(l) + ": ";
+        if (!std::isfinite(y.time)) { error = where + "time is not finite"; return false; }
+        if (!std::isfinite(y.weight)) { error = where + "weight is not finite"; return false; }
+        if (y.weight < 0.0f) { error = where + "weight " + std::to_string(y.weight) + " is negative"; return false; }
+        if (y.wrap > CGPT_ANIM_WRAP_PINGPONG) { error = where + "wrap mode " + std::to_string(y.wrap) + " is none of CLAMP, LOOP, PINGPONG"; return false; }
+        if (y.weight == 0.0f) continue;                                       // inactive: never sampled
+        out.index[out.n] = l;
+        out.time[out.n] = AnimWrapTime(y.time, ranges[l][0], ranges[l][1], y.wrap);
+        out.weight[out.n] = y.weight;
+        ++out.n;
+    }
+    if (out.n == 0u) { error = "no layer has a weight above zero"; return false; }
+    float W = out.weight[0];
+    for (uint32_t k = 1; k < out.n; ++k) W = W + out.weight[k];
+    if (!std::isfinite(W)) { error = "the sum of the layers' weights is not finite"; return false; }
+    for (uint32_t k = 0; k < out.n; ++k) out.weight[k] = out.weight[k] / W;
+    active = out;
+    return true;
+}
+
 bool CheckSkeleton(const cgpt_skeleton_desc* s, std::string& error)
 {
     if (!s) { error = "skeleton is null"; return false; }
@@ -85,6 +127,8 @@ bool CheckClip(const cgpt_clip_desc* c, ClipTable& table, std::string& error, bo
         for (uint64_t k = 0; k < width * ch.n_keys; ++k)
             if (!std::isfinite(v[k])) { error = where + "key " + std::to_string(k / width) + ": value " + std::to_string(k % width) + " is not finite"; return false; }
         out.channels[i] = { ch.interpolation, ch.n_keys, ch.first_time, ch.first_value };
+        out.begin = i == 0 || t[0] < out.begin ? t[0] : out.begin;            // the range: selections, hence exact
+        out.end = i == 0 || t[ch.n_keys - 1] > out.end ? t[ch.n_keys - 1] : out.end;
     }
     if (c->n_times) out.times.assign(c->times, c->times + c->n_times);
     if (c->n_values) out.values.assign(c->values, c->values + c->n_values);

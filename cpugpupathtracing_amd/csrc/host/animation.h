@@ -1,6 +1,8 @@
 // animation.h -- joint matrices from an animation clip: the arithmetic, stated once for the host mirror (animation.cpp: AnimateJoints)
 // and the device kernel (csrc/device/refit.hip: animate_joints_batch), and the validation both sides share.  tests/anim_ref.py states
 // the same operations in numpy; DESIGN.md 5.33.  The data layout is glTF's (skins / animations), so an importer is a copy loop.
+// Further down: wrapped times and the blend of up to four clips per joint (AnimateLayers, animate_layers_batch; tests/anim_layer_ref.py;
+// DESIGN.md 5.35), stated where they are defined.
 //
 // A skeleton has n_joints joints: parents[j] (-1: a root; any order, no cycle), inverse_bind[12 j ..] the rows of [A | b], rest[10 j ..]
 // = T.xyz, R.xyzw, S.xyz, and an optional root matrix [A | b] applied last (absent: no multiply at all).  A clip has channels
@@ -88,17 +90,22 @@ CGPT_ANIM_FN void AnimSampleChannel(const AnimChannel& c, const float* times, co
     for (int i = 0; i < width; ++i) out[i] = a[i] + u * (b[i] - a[i]);
 }
 
-// L_j at time t: map holds 3 n_joints channel indices (kAnimNoChannel: take rest), rest 10 floats a joint
-CGPT_ANIM_FN void AnimLocalMatrix(const uint32_t* map, const AnimChannel* channels, const float* times, const float* values, const float* rest,
-                                  uint32_t j, float t, float L[12])
+// T, q, S of joint j at time t: map holds 3 n_joints channel indices (kAnimNoChannel: take rest), rest 10 floats a joint; q is normalised
+CGPT_ANIM_FN void AnimSampleJoint(const uint32_t* map, const AnimChannel* channels, const float* times, const float* values, const float* rest,
+                                  uint32_t j, float t, float T[3], float q[4], float S[3])
 {
     const float* r = rest + 10 * (size_t)j;
-    float T[3] = { r[0], r[1], r[2] }, q[4] = { r[3], r[4], r[5], r[6] }, S[3] = { r[7], r[8], r[9] };
+    T[0] = r[0]; T[1] = r[1]; T[2] = r[2]; q[0] = r[3]; q[1] = r[4]; q[2] = r[5]; q[3] = r[6]; S[0] = r[7]; S[1] = r[8]; S[2] = r[9];
     const uint32_t ct = map[3 * (size_t)j + CGPT_ANIM_PATH_TRANSLATION], cr = map[3 * (size_t)j + CGPT_ANIM_PATH_ROTATION], cs = map[3 * (size_t)j + CGPT_ANIM_PATH_SCALE];
     if (ct != kAnimNoChannel) AnimSampleChannel(channels[ct], times, values, t, 3, false, T);
     if (cr != kAnimNoChannel) AnimSampleChannel(channels[cr], times, values, t, 4, true, q);
     if (cs != kAnimNoChannel) AnimSampleChannel(channels[cs], times, values, t, 3, false, S);
     AnimNormaliseRotation(q);
+}
+
+// L_j = [R(q) diag(S) | T]
+CGPT_ANIM_FN void AnimComposeLocal(const float T[3], const float q[4], const float S[3], float L[12])
+{
     const float x = q[0], y = q[1], z = q[2], w = q[3];
     const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
     const float rot[9] = { 1.0f - 2.0f * (yy + zz), 2.0f * (xy - wz), 2.0f * (xz + wy),
@@ -110,6 +117,70 @@ CGPT_ANIM_FN void AnimLocalMatrix(const uint32_t* map, const AnimChannel* channe
         L[4 * row + 2] = rot[3 * row + 2] * S[2];
         L[4 * row + 3] = T[row];
     }
+}
+
+// L_j at time t
+CGPT_ANIM_FN void AnimLocalMatrix(const uint32_t* map, const AnimChannel* channels, const float* times, const float* values, const float* rest,
+                                  uint32_t j, float t, float L[12])
+{
+    float T[3], q[4], S[3];
+    AnimSampleJoint(map, channels, times, values, rest, j, t, T, q, S);
+    AnimComposeLocal(T, q, S, L);
+}
+
+// ---- layers: wrapped times and a weighted blend of up to CGPT_ANIM_MAX_LAYERS clips (cgpt_scene_animate_layers) --------
+//   range         begin = the smallest first-key time of the clip's channels, end = the largest last-key time (selections: exact); no channel: 0, 0
+//   wrap          d = end - begin;  CLAMP, or !(d > 0 and d finite): t as given (the sampler holds the end keys)
+//                 s = t - begin;  p = d (LOOP) or d + d (PINGPONG);  p not finite: t
+//                 n = floorf(s / p);  r = s - n * p;  r < 0: r = r + p;  !(r >= 0 and r < p): r = 0;  PINGPONG and r > d: r = p - r;  begin + r
+//   weights       a layer of weight 0 is inactive and never sampled; over the active ones in ascending order W = ((w0 + w1) + w2) + w3, a_l = w_l / W
+//   blend         one active layer: its T, q, S as sampled.  Otherwise, componentwise over the active layers l0 < l1 < ...:
+//                 T = a_l0 * T_l0, then T = T + a_l * T_l; S likewise; q likewise with q_l (l > l0) negated first when
+//                 ((q_l0.x*q_l.x + q_l0.y*q_l.y) + q_l0.z*q_l.z) + q_l0.w*q_l.w < 0, and normalised once at the end
+// floorf is exact, so it joins + - * / sqrtf without breaking bit equality.
+CGPT_ANIM_FN float AnimWrapTime(float t, float begin, float end, uint32_t mode)
+{
+    const float d = end - begin;
+    if (mode == CGPT_ANIM_WRAP_CLAMP || !(d > 0.0f && d < INFINITY)) return t;
+    const float s = t - begin;
+    const float p = mode == CGPT_ANIM_WRAP_LOOP ? d : d + d;
+    if (!(p < INFINITY)) return t;
+    const float n = floorf(s / p);
+    float r = s - n * p;
+    if (r < 0.0f) r = r + p;
+    if (!(r >= 0.0f && r < p)) r = 0.0f;
+    if (mode == CGPT_ANIM_WRAP_PINGPONG && r > d) r = p - r;
+    return begin + r;
+}
+
+// One clip of a blend as the sampler reads it, with its wrapped time and normalised weight: 40 bytes
+struct AnimLayer {
+    const uint32_t* map;
+    const AnimChannel* channels;
+    const float* times;
+    const float* values;
+    float time, weight;
+};
+
+// T, q, S of joint j under n >= 1 active layers
+CGPT_ANIM_FN void AnimBlendJoint(const AnimLayer* layers, uint32_t n, const float* rest, uint32_t j, float T[3], float q[4], float S[3])
+{
+    AnimSampleJoint(layers[0].map, layers[0].channels, layers[0].times, layers[0].values, rest, j, layers[0].time, T, q, S);
+    if (n == 1u) return;
+    const float q0[4] = { q[0], q[1], q[2], q[3] };
+    const float a0 = layers[0].weight;
+    for (int i = 0; i < 3; ++i) { T[i] = a0 * T[i]; S[i] = a0 * S[i]; }
+    for (int i = 0; i < 4; ++i) q[i] = a0 * q[i];
+    for (uint32_t l = 1; l < n; ++l) {
+        float Tl[3], ql[4], Sl[3];
+        AnimSampleJoint(layers[l].map, layers[l].channels, layers[l].times, layers[l].values, rest, j, layers[l].time, Tl, ql, Sl);
+        const float dot = ((q0[0] * ql[0] + q0[1] * ql[1]) + q0[2] * ql[2]) + q0[3] * ql[3];
+        if (dot < 0.0f) { ql[0] = -ql[0]; ql[1] = -ql[1]; ql[2] = -ql[2]; ql[3] = -ql[3]; }
+        const float a = layers[l].weight;
+        for (int i = 0; i < 3; ++i) { T[i] = T[i] + a * Tl[i]; S[i] = S[i] + a * Sl[i]; }
+        for (int i = 0; i < 4; ++i) q[i] = q[i] + a * ql[i];
+    }
+    AnimNormaliseRotation(q);
 }
 
 // C = A o B; C may be neither A nor B
@@ -144,6 +215,7 @@ struct ClipTable {
     std::vector<uint32_t> map;                                                // 3 n_joints
     std::vector<AnimChannel> channels;
     std::vector<float> times, values;
+    float begin = 0.0f, end = 0.0f;                                           // the smallest first-key and the largest last-key time; no channel: 0, 0
 };
 
 // What cgpt_scene_set_skeleton and cgpth_animate_joints refuse of a skeleton: NULL, n_joints 0 or above kSkinMaxJoints, a parent below -1
@@ -155,5 +227,14 @@ bool CheckSkeleton(const cgpt_skeleton_desc* s, std::string& error);
 bool CheckClip(const cgpt_clip_desc* c, ClipTable& table, std::string& error, bool& unsupported);
 // The n_joints x 12 joint matrices of the skeleton under the clip at time t (finite).  The inputs have passed the two checks.
 void AnimateJoints(const cgpt_skeleton_desc& s, const ClipTable& clip, float t, float* out);
+
+// What cgpt_scene_animate_layers and cgpth_animate_layers refuse of an entry's layers once its clips are known (ranges[l] = {begin, end}
+// of layer l's clip): n_layers outside [1, CGPT_ANIM_MAX_LAYERS], a time that is not finite, a weight that is not finite or negative, an
+// unknown wrap mode, no weight above zero, a sum of weights that is not finite.  On success the active layers (weight > 0) in ascending
+// order: index[k] their position in `layers`, time[k] wrapped, weight[k] normalised.  false with the reason ("layer l: ...")
+struct AnimActiveLayers { uint32_t n = 0, index[CGPT_ANIM_MAX_LAYERS]; float time[CGPT_ANIM_MAX_LAYERS], weight[CGPT_ANIM_MAX_LAYERS]; };
+bool ResolveLayers(const cgpt_clip_layer* layers, uint32_t n_layers, const float (*ranges)[2], AnimActiveLayers& active, std::string& error);
+// The joint matrices under the blend of `active`'s layers of clips[active.index[k]]
+void AnimateLayers(const cgpt_skeleton_desc& s, const ClipTable* const* clips, const AnimActiveLayers& active, float* out);
 
 }  // namespace cgpt

@@ -547,6 +547,60 @@ int cgpth_animate_joints(const cgpt_skeleton_desc* skeleton, const cgpt_clip_des
     });
 }
 
+int cgpth_animate_layers(const cgpt_skeleton_desc* skeleton, const cgpt_clip_desc* clips, const cgpt_clip_layer* layers, uint32_t n_layers,
+                         float* out, uint32_t n_joints)
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        std::string err;
+        if (!CheckSkeleton(skeleton, err)) return Fail(err);
+        if (!layers) return Fail("layers is null");
+        if (n_layers == 0u || n_layers > CGPT_ANIM_MAX_LAYERS) return Fail("n_layers " + std::to_string(n_layers) + " outside [1, " + std::to_string(CGPT_ANIM_MAX_LAYERS) + "]");
+        if (!clips) return Fail("clips is null");
+        std::vector<ClipTable> tables(n_layers);
+        const ClipTable* table_of[CGPT_ANIM_MAX_LAYERS];
+        float ranges[CGPT_ANIM_MAX_LAYERS][2];
+        for (uint32_t l = 0; l < n_layers; ++l) {
+            const std::string where = "layer " + std::to_string(l) + ": ";
+            bool unsupported = false;
+            if (!CheckClip(clips + l, tables[l], err, unsupported)) { Fail(where + err); return unsupported ? (int)CGPT_ERR_UNSUPPORTED : (int)CGPT_ERR_INVALID; }
+            if (tables[l].n_joints != skeleton->n_joints)
+                return Fail(where + "the clip animates " + std::to_string(tables[l].n_joints) + " joints, the skeleton has " + std::to_string(skeleton->n_joints));
+            table_of[l] = &tables[l];
+            ranges[l][0] = tables[l].begin; ranges[l][1] = tables[l].end;
+        }
+        AnimActiveLayers active;
+        if (!ResolveLayers(layers, n_layers, ranges, active, err)) return Fail(err);
+        if (n_joints != skeleton->n_joints) return Fail("the skeleton has " + std::to_string(skeleton->n_joints) + " joints, got room for " + std::to_string(n_joints));
+        if (!out) return Fail("out is null");
+        AnimateLayers(*skeleton, table_of, active, out);
+        return CGPT_OK;
+    });
+}
+
+int cgpth_clip_range(const cgpt_clip_desc* clip, float* begin, float* end)
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        std::string err;
+        ClipTable table;
+        bool unsupported = false;
+        if (!CheckClip(clip, table, err, unsupported)) { Fail(err); return unsupported ? (int)CGPT_ERR_UNSUPPORTED : (int)CGPT_ERR_INVALID; }
+        if (begin) *begin = table.begin;
+        if (end) *end = table.end;
+        return CGPT_OK;
+    });
+}
+
+int cgpth_wrap_time(float t, float begin, float end, uint32_t mode, float* out)
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        if (!out) return Fail("out is null");
+        if (mode > CGPT_ANIM_WRAP_PINGPONG) return Fail("wrap mode " + std::to_string(mode) + " is none of CLAMP, LOOP, PINGPONG");
+        if (!std::isfinite(t) || !std::isfinite(begin) || !std::isfinite(end)) return Fail("time, begin or end is not finite");
+        *out = AnimWrapTime(t, begin, end, mode);
+        return CGPT_OK;
+    });
+}
+
 int cgpth_scene_update_primitive(cgpth_scene* scene, uint32_t obj_index, const cgpt_object* obj)
 {
     return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {

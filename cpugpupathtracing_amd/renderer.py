@@ -40,6 +40,35 @@ class DeviceError(RuntimeError):
         self.code = code
 
 
+_CLIP_LAYER = np.dtype([("clip", np.uint32), ("time", np.float32), ("weight", np.float32), ("wrap", np.uint32)])
+_LAYERED_ANIMATION = np.dtype({"names": ["obj_index", "n_layers", "layers", "n_targets", "weights"],
+                               "formats": [np.uint32, np.uint32, np.uint64, np.uint32, np.uint64], "offsets": [0, 4, 8, 16, 24], "itemsize": 32})
+
+
+def _layer_tables(entries):
+    """(cgpt_layered_animation table, its length, the arrays it points into) of animate_layers' entries.  Both tables are filled as
+    numpy arrays -- every entry's layers in one array of cgpt_clip_layer rows, an entry pointing at its first -- since a ctypes object
+    per layer and per entry costs more than the device call itself for a crowd."""
+    assert C.sizeof(N.ClipLayer) == _CLIP_LAYER.itemsize and C.sizeof(N.LayeredAnimation) == _LAYERED_ANIMATION.itemsize
+    assert (N.LayeredAnimation.layers.offset, N.LayeredAnimation.n_targets.offset, N.LayeredAnimation.weights.offset) == (8, 16, 24)
+    entries = [(obj_index, None if layers is None else list(layers), None if weights is None else _morph_weights(weights)) for obj_index, layers, weights in entries]
+    n = len(entries)
+    flat = [row for _, layers, _ in entries if layers is not None for row in layers]
+    rows = np.zeros(max(1, len(flat)), _CLIP_LAYER)
+    if flat:
+        rows[:len(flat)] = flat
+    table = np.zeros(max(1, n), _LAYERED_ANIMATION)
+    if n:
+        counts = np.array([0 if layers is None else len(layers) for _, layers, _ in entries], np.uint32)
+        first = np.concatenate([[0], np.cumsum(counts[:-1], dtype=np.uint64)]).astype(np.uint64)
+        table["obj_index"][:n] = [obj_index for obj_index, _, _ in entries]
+        table["n_layers"][:n] = counts
+        table["layers"][:n] = [0 if layers is None else rows.ctypes.data + 16 * int(at) for (_, layers, _), at in zip(entries, first)]
+        table["n_targets"][:n] = [0 if w is None else w.size for _, _, w in entries]
+        table["weights"][:n] = [0 if w is None else w.ctypes.data for _, _, w in entries]
+    return table.ctypes.data_as(C.POINTER(N.LayeredAnimation)), n, (table, rows, entries)
+
+
 class Renderer:
     def __init__(self, device=0, flags: int = 0):
         """device: one HIP device id, or a sequence of up to 8 ids for ONE context that spreads every frame over those GPUs
@@ -296,6 +325,20 @@ class Renderer:
                                     None if w is None else w.ctypes.data_as(C.POINTER(C.c_float))))
         table = (N.Animation * max(1, len(rows)))(*rows)
         self._check(self.L.cgpt_scene_animate_objects(self._ctx, table, len(rows)))
+
+    def animate_layers(self, entries):
+        """cgpt_scene_animate_layers: animate_objects with every entry's joints blended from 1 .. 4 clips.  `entries`
+        is an iterable of (obj_index, [(clip, time, weight, wrap), ...], weights or None) with wrap one of N.ANIM_WRAP_CLAMP, _LOOP,
+        _PINGPONG; the device scene afterwards is what pose_objects leaves for the matrices of the host's animate_layers, bit for bit.
+        A refused call changes nothing.  Call reset_accumulator() before the next frame."""
+        table, n, keep = _layer_tables(entries)
+        self._check(self.L.cgpt_scene_animate_layers(self._ctx, table, n))
+
+    def clip_range(self, clip: int):
+        """cgpt_clip_get_range: (begin, end) of a clip, the smallest first-key and the largest last-key time of its channels."""
+        b, e = C.c_float(), C.c_float()
+        self._check(self.L.cgpt_clip_get_range(self._ctx, int(clip), C.byref(b), C.byref(e)))
+        return np.float32(b.value), np.float32(e.value)
 
     def joint_matrices(self, obj_index: int, n_joints: Optional[int] = None) -> np.ndarray:
         """cgpt_scene_get_joint_matrices: the (n_joints, 12) float32 matrices of the last pose of object `obj_index`'s skin, however

@@ -209,6 +209,52 @@ def animate_joints(skeleton, clip, time) -> np.ndarray:
     return out
 
 
+def _host_error(rc, what):
+    e = HostError(f"{what}: {N.lib().cgpth_last_error().decode()}")
+    e.code = rc
+    return e
+
+
+def animate_layers(skeleton, layers) -> np.ndarray:
+    """Joint matrices from a blend of clips on the host (cgpth_animate_layers): `layers` is a sequence of 1 .. 4
+    (clip, time, weight, wrap) with clip = (n_joints, channels, times, values) and wrap one of N.ANIM_WRAP_*.  Each layer's time is
+    wrapped over its clip's range, layers of weight 0 are left out, the others' T / R / S are blended by their weights over the
+    weights' sum before the hierarchy is walked.  It is what Renderer.animate_layers computes on the device, to the bit."""
+    sd, keep_s = _skeleton_desc(*skeleton)
+    layers = list(layers)
+    descs, keep = [], []
+    for clip, _, _, _ in layers:
+        cd, keep_c = _clip_desc(*clip)
+        descs.append(cd); keep.append(keep_c)
+    clips = (N.ClipDesc * max(1, len(descs)))(*descs)
+    rows = (N.ClipLayer * max(1, len(layers)))(*[N.ClipLayer(0, float(t), float(w), int(wrap)) for _, t, w, wrap in layers])
+    out = np.empty((sd.n_joints, 12), np.float32)
+    rc = N.lib().cgpth_animate_layers(C.byref(sd), clips, rows, len(layers), out.ctypes.data_as(C.POINTER(C.c_float)), sd.n_joints)
+    if rc != 0:
+        raise _host_error(rc, "animate_layers")
+    return out
+
+
+def clip_range(clip):
+    """(begin, end) of clip = (n_joints, channels, times, values) as float32: the smallest first-key and the largest last-key time of
+    its channels, (0, 0) without channels (cgpth_clip_range) -- what a layer's LOOP or PINGPONG wraps its time over."""
+    cd, keep = _clip_desc(*clip)
+    b, e = C.c_float(), C.c_float()
+    rc = N.lib().cgpth_clip_range(C.byref(cd), C.byref(b), C.byref(e))
+    if rc != 0:
+        raise _host_error(rc, "clip_range")
+    return np.float32(b.value), np.float32(e.value)
+
+
+def wrap_time(t, begin, end, wrap):
+    """cgpth_wrap_time: `t` over [begin, end] by N.ANIM_WRAP_CLAMP (as given), _LOOP or _PINGPONG, in float32 as the device call wraps it."""
+    out = C.c_float()
+    rc = N.lib().cgpth_wrap_time(float(t), float(begin), float(end), int(wrap), C.byref(out))
+    if rc != 0:
+        raise _host_error(rc, "wrap_time")
+    return np.float32(out.value)
+
+
 def primitive_abi(kind: int, mat_index: int, center=None, radius=None, normal=None, point=None) -> N.Object:
     """A cgpt_object for update_primitive: a sphere (center, radius) or a plane (normal, point)."""
     o = N.Object()

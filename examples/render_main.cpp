@@ -4,7 +4,7 @@
 //
 //   g++ -std=c++17 -Iinclude -Icpugpupathtracing_amd/csrc/host examples/render_main.cpp
 //       -Lcpugpupathtracing_amd/lib -lcpugpupt -Wl,-rpath,$PWD/cpugpupathtracing_amd/lib -o render_main   (one command line)
-//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--spin DEG] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [--bend DEG] [--animate T] [--bulge W] [--crowd N] [--rebuild [naive|intervals|binned]] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
+//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--spin DEG] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [--bend DEG] [--animate T [--loop] [--crossfade W]] [--bulge W] [--crowd N] [--rebuild [naive|intervals|binned]] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
 // --gpus N: ONE context over the first N GPUs of the node (cgpt_ctx_create with n_devices = N): every frame is spread over them in
 // interleaved row bands and the read-back gathers the float4 bands with one RCCL exchange over xGMI; the loop below does not
 // change.  --collective: take that code path with N = 1 too (what a one-GPU box can test).
@@ -64,6 +64,10 @@
 // (cgpt_clip_create) whose rotation channel takes joint 1 from 0 to DEG over one second; ONE frame is rendered, at clip time T, posed by
 // cgpt_scene_animate_objects -- with --crowd N character k plays at its own phase, T (k + 1) / N.  The joint matrices
 // never exist on the host.  Frames are named animate_00_*.ppm.
+// --loop: with --animate T, the clip repeats: T is wrapped over the clip's range (cgpt_clip_get_range) by CGPT_ANIM_WRAP_LOOP on the way to
+// the device, so --animate 2.25 --loop shows what --animate 0.25 shows.  The frame is posed by cgpt_scene_animate_layers.
+// --crossfade W: with --animate T, the bend clip is blended with a second clip, the opposite bend (0 to -DEG), at weight W in [0, 1] against
+// 1 - W: one cgpt_scene_animate_layers entry of two layers per mesh -- with --crowd N character k fades at its own weight, W (k + 1) / N.
 // --rebuild [OPTION]: with --bend / --bulge / --crowd, every posed mesh's tree is split again in place on the device after each frame's pose
 // (cgpt_scene_rebuild_mesh), with the binned builder unless OPTION says otherwise: the refit keeps a tree that was split
 // for the bind pose, and after a large bend its boxes overlap.  The triangles never leave the device.  A rebuild drops the temporal
@@ -94,7 +98,7 @@ using namespace cgpt;
 
 int main(int argc, char** argv)
 {
-    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool spin = false; float spin_deg = 0.0f; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false; uint32_t n_instances = 0; bool bend = false; float bend_deg = 0.0f; bool bulge = false; float bulge_w = 0.0f; uint32_t crowd = 0; bool animate = false; float animate_t = 0.0f;
+    int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool spin = false; float spin_deg = 0.0f; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false; uint32_t n_instances = 0; bool bend = false; float bend_deg = 0.0f; bool bulge = false; float bulge_w = 0.0f; uint32_t crowd = 0; bool animate = false; float animate_t = 0.0f; bool loop = false; bool crossfade = false; float crossfade_w = 0.0f;
     bool rebuild = false; uint32_t rebuild_option = CGPT_BUILD_SAH_BINNED;
     bool has_transform = false; float mesh_transform[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
     MeshBVH::BuildOption bvh_option = MeshBVH::BuildOption_SAHSplitIntervals;
@@ -107,6 +111,8 @@ int main(int argc, char** argv)
         else if (std::string(argv[1]) == "--bend" && argc > 2) { bend = true; bend_deg = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--bulge" && argc > 2) { bulge = true; bulge_w = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--animate" && argc > 2) { animate = true; animate_t = (float)atof(argv[2]); argv += 2; argc -= 2; }
+        else if (std::string(argv[1]) == "--loop") { loop = true; argv += 1; argc -= 1; }
+        else if (std::string(argv[1]) == "--crossfade" && argc > 2) { crossfade = true; crossfade_w = (float)atof(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--crowd" && argc > 2) { crowd = (uint32_t)atoi(argv[2]); argv += 2; argc -= 2; }
         else if (std::string(argv[1]) == "--rebuild") {
             rebuild = true; argv += 1; argc -= 1;
@@ -324,7 +330,7 @@ int main(int argc, char** argv)
 
         // --animate: the same bend as a clip.  Joint 0 is the root at the origin, joint 1 its child at the pivot; the inverse bind matrices
         // undo the rest pose, so M_1 = T(pivot) R_x T(-pivot) as below.  One clip for everyone: joint 1's rotation, 0 -> DEG over a second.
-        uint32_t clip = 0;
+        uint32_t clip = 0, clip_back = 0;
         if (animate) {
             const double half = 0.5 * (double)bend_deg * 3.14159265358979 / 180.0;
             const cgpt_clip_channel channel = { 1u, CGPT_ANIM_PATH_ROTATION, CGPT_ANIM_LINEAR, 2u, 0u, 0u };
@@ -332,6 +338,11 @@ int main(int argc, char** argv)
             const float key_values[8] = { 0.0f, 0.0f, 0.0f, 1.0f, (float)std::sin(half), 0.0f, 0.0f, (float)std::cos(half) };
             const cgpt_clip_desc cd = { 2u, 1u, &channel, key_times, 2u, key_values, 8u };
             CHECK(cgpt_clip_create(ctx, &cd, &clip));
+            if (crossfade) {                                             // --crossfade: the opposite bend, 0 -> -DEG over the same second
+                const float back_values[8] = { 0.0f, 0.0f, 0.0f, 1.0f, (float)-std::sin(half), 0.0f, 0.0f, (float)std::cos(half) };
+                const cgpt_clip_desc back = { 2u, 1u, &channel, key_times, 2u, back_values, 8u };
+                CHECK(cgpt_clip_create(ctx, &back, &clip_back));
+            }
             for (size_t k = 0; k < posed.size(); ++k) {
                 const float py = pivots[2 * k], pz = pivots[2 * k + 1];
                 const int32_t parents[2] = { -1, 0 };
@@ -356,7 +367,22 @@ int main(int argc, char** argv)
                 for (int i = 0; i < 24; ++i) joint_matrices[24 * k + i] = m[i];
             }
             const float morph_weight = bulge_w * (float)frame / 7.0f;
-            if (animate) {                                               // a clip and a time per object: nothing else goes to the device
+            if (animate && (loop || crossfade)) {                        // --loop / --crossfade: up to two layers per object, wrapped and blended on the device's side
+                float begin = 0.0f, end = 0.0f;
+                CHECK(cgpt_clip_get_range(ctx, clip, &begin, &end));
+                const uint32_t wrap = loop ? (uint32_t)CGPT_ANIM_WRAP_LOOP : (uint32_t)CGPT_ANIM_WRAP_CLAMP;
+                std::vector<cgpt_clip_layer> layers(2 * posed.size());
+                std::vector<cgpt_layered_animation> entries(posed.size());
+                for (size_t k = 0; k < posed.size(); ++k) {
+                    const float share = crowd ? (float)(k + 1) / (float)crowd : 1.0f;
+                    const float w = crossfade ? std::fmin(std::fmax(crossfade_w * share, 0.0f), 1.0f) : 0.0f;
+                    layers[2 * k] = { clip, animate_t * share, 1.0f - w, wrap };
+                    layers[2 * k + 1] = { crossfade ? clip_back : clip, animate_t * share, w, wrap };   // weight 0 without --crossfade: never sampled
+                    entries[k] = { posed[k], 2u, layers.data() + 2 * k, bulge ? 1u : 0u, bulge ? &morph_weight : nullptr };
+                }
+                CHECK(cgpt_scene_animate_layers(ctx, entries.data(), (uint32_t)entries.size()));
+                if (frame == 0) printf("clip range [%g, %g]%s%s\n", (double)begin, (double)end, loop ? ", looped" : "", crossfade ? ", cross-faded with the opposite bend" : "");
+            } else if (animate) {                                        // a clip and a time per object: nothing else goes to the device
                 std::vector<cgpt_animation> entries(posed.size());
                 for (size_t k = 0; k < posed.size(); ++k)
                     entries[k] = { posed[k], clip, crowd ? animate_t * (float)(k + 1) / (float)crowd : animate_t, bulge ? 1u : 0u, bulge ? &morph_weight : nullptr };

@@ -522,6 +522,37 @@ int cgpt_clip_destroy(cgpt_ctx* ctx, uint32_t clip);
 int cgpt_scene_animate_objects(cgpt_ctx* ctx, const cgpt_animation* entries, uint32_t n_entries);
 int cgpt_scene_get_joint_matrices(cgpt_ctx* ctx, uint32_t obj_index, float* out, uint32_t n_joints);
 
+/* ---- layers: up to four clips blended per object, each at a wrapped time ----
+ * cgpt_scene_animate_layers is cgpt_scene_animate_objects with every entry's joints blended from 1 .. CGPT_ANIM_MAX_LAYERS clips before
+ * the hierarchy walk: a cross-fade of a walk into a run is one entry with two layers.  csrc/host/animation.h states the arithmetic:
+ * every layer's time is wrapped over its clip's range [begin, end] (the smallest first-key and the largest last-key time of its
+ * channels) by its wrap mode -- CLAMP leaves the time as given, LOOP repeats the range, PINGPONG plays it forth and back -- on the
+ * host, once per layer; layers of weight 0 are never sampled; the others' weights are divided by their sum; T and S are the weighted
+ * sums of the layers' sampled values, R the weighted sum of the rotations aligned to the first active layer's, normalised once.  An
+ * entry with one active layer runs no blend arithmetic: with CLAMP it is cgpt_scene_animate_objects to the bit.  cgpth_animate_layers
+ * evaluates the statement on the host, tests/anim_layer_ref.py in numpy, and the device agrees with both bit for bit.
+ * The contract is cgpt_scene_animate_objects': the two phases, an entry whose matrices are not finite refusing the whole call with its
+ * index, the matrices kept as the skin's last pose, n_entries 0 is CGPT_OK.  Refused further, before any device work, naming the entry
+ * and the layer: layers NULL, n_layers 0 or above CGPT_ANIM_MAX_LAYERS, an unknown or destroyed clip or one with another joint count
+ * in any layer (inactive ones included), a time that is not finite, a weight that is not finite or negative, no weight above zero, a
+ * sum of weights that is not finite, an unknown wrap mode.
+ * cgpt_clip_get_range: a clip's begin and end (a clip without channels: 0, 0); either pointer may be NULL. */
+enum { CGPT_ANIM_WRAP_CLAMP = 0, CGPT_ANIM_WRAP_LOOP = 1, CGPT_ANIM_WRAP_PINGPONG = 2 };
+#define CGPT_ANIM_MAX_LAYERS 4u
+typedef struct cgpt_clip_layer {
+    uint32_t clip;
+    float time, weight;
+    uint32_t wrap;                /* CGPT_ANIM_WRAP_* */
+} cgpt_clip_layer;
+typedef struct cgpt_layered_animation {
+    uint32_t obj_index, n_layers;
+    const cgpt_clip_layer* layers;
+    uint32_t n_targets;           /* 0: this entry gives no morph weights */
+    const float* weights;         /* n_targets, as cgpt_scene_morph_mesh takes them */
+} cgpt_layered_animation;
+int cgpt_scene_animate_layers(cgpt_ctx* ctx, const cgpt_layered_animation* entries, uint32_t n_entries);
+int cgpt_clip_get_range(cgpt_ctx* ctx, uint32_t clip, float* begin, float* end);
+
 /* UpdateScreenPlane (ref: Main.cpp:98-102,143-149): fov in degrees, plane at distance fov-in-radians (SURVEY A-13) */
 int cgpt_camera_from_view(const float pos[3], const float view_dir[3], float fov_deg, float aspect, cgpt_camera* out);
 

@@ -136,6 +136,17 @@ int cgpth_scene_morph_mesh(cgpth_scene* scene, uint32_t obj_index, const cgpt_tr
  * CUBICSPLINE, else CGPT_ERR_INVALID), a clip whose n_joints differs from the skeleton's, n_joints other than the skeleton's, a time
  * that is not finite, out NULL. */
 int cgpth_animate_joints(const cgpt_skeleton_desc* skeleton, const cgpt_clip_desc* clip, float time, float* out, uint32_t n_joints);
+/* The host statement of cgpt_scene_animate_layers' kernel: the joint matrices of the skeleton under the blend of
+ * n_layers layers, layer l playing clips[l] (layers[l].clip is not read) at layers[l].time wrapped over that clip's range by
+ * layers[l].wrap, with weight layers[l].weight.  Refused with nothing written: what cgpth_animate_joints refuses of the skeleton, of
+ * each clip (inactive layers' included: "layer l: ...") and of out / n_joints, clips or layers NULL, and every refusal of a layer that
+ * cgpt_scene_animate_layers lists. */
+int cgpth_animate_layers(const cgpt_skeleton_desc* skeleton, const cgpt_clip_desc* clips, const cgpt_clip_layer* layers, uint32_t n_layers,
+                         float* out, uint32_t n_joints);
+/* a clip's range as cgpt_clip_get_range reports it: the smallest first-key and the largest last-key time of its channels (none: 0, 0) */
+int cgpth_clip_range(const cgpt_clip_desc* clip, float* begin, float* end);
+/* animation.h's AnimWrapTime: t over [begin, end] by a CGPT_ANIM_WRAP_* mode.  Refused: out NULL, an unknown mode, a float that is not finite */
+int cgpth_wrap_time(float t, float begin, float end, uint32_t mode, float* out);
 /* the host statement of cgpt_scene_update_primitive: a sphere's centre and radius, or a plane's normal and point */
 int cgpth_scene_update_primitive(cgpth_scene* scene, uint32_t obj_index, const cgpt_object* obj);
 /* reorders the objects: the new object k is the old object order[k] (a permutation of 0 .. n_objects - 1, else refused and nothing
