@@ -212,6 +212,22 @@ class SceneFootprint(C.Structure):
                 ("n_leaf_records", C.c_uint32), ("n_pair_records", C.c_uint32), ("n_orig_triangles", C.c_uint32)]
 
 
+class TreeCost(C.Structure):
+    """cgpt_tree_cost"""
+    _fields_ = [("cost", C.c_double), ("root_half_area", C.c_double), ("n_inner", C.c_uint32), ("n_leaves", C.c_uint32),
+                ("max_leaf_tris", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RebuildCandidate(C.Structure):
+    """cgpt_rebuild_candidate: one entry of cgpt_scene_rebuild_degraded"""
+    _fields_ = [("obj_index", C.c_uint32), ("reserved", C.c_uint32), ("reference_cost", C.c_double)]
+
+
+class RebuildResult(C.Structure):
+    """cgpt_rebuild_result"""
+    _fields_ = [("cost_before", C.c_double), ("cost_after", C.c_double), ("rebuilt", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class TopLevelView(C.Structure):
     """cgpth_top_level_view: n_nodes records of 8 floats {lo.xyz, bits(skip) | hi.xyz, bits(object)}, n_entry node indices."""
     _fields_ = [("nodes", _fp), ("n_nodes", C.c_size_t), ("entry", _up), ("n_entry", C.c_size_t)]
@@ -238,6 +254,9 @@ PROTOTYPES = {
     "cgpt_scene_refit_mesh": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), C.c_uint32, _fp]),
     "cgpt_scene_rebuild_mesh": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _up, _up]),
     "cgpt_scene_export_bvh": (C.c_int, [_vp, C.c_uint32, C.POINTER(BvhNode), C.c_uint32]),
+    "cgpt_scene_tree_costs": (C.c_int, [_vp, _up, C.c_uint32, C.c_double, C.c_double, C.POINTER(TreeCost)]),
+    "cgpt_scene_rebuild_degraded": (C.c_int, [_vp, C.POINTER(RebuildCandidate), C.c_uint32, C.c_double, C.c_uint32, C.c_double, C.c_double,
+                                              C.POINTER(RebuildResult)]),
     "cgpt_scene_update_primitive": (C.c_int, [_vp, C.c_uint32, C.POINTER(Object)]),
     "cgpt_scene_set_skin": (C.c_int, [_vp, C.c_uint32, C.POINTER(Triangle), _u16p, _fp, C.c_uint32, C.c_uint32]),
     "cgpt_scene_skin_mesh": (C.c_int, [_vp, C.c_uint32, _fp, C.c_uint32]),
@@ -332,6 +351,7 @@ PROTOTYPES = {
     "cgpth_scene_update_primitive": (C.c_int, [_vp, C.c_uint32, C.POINTER(Object)]),
     "cgpth_scene_bvh_info": (C.c_int, [_vp, C.c_uint32, C.POINTER(BvhInfo)]),
     "cgpth_scene_bvh_export": (C.c_int, [_vp, C.c_uint32, C.POINTER(BvhNode), _up]),
+    "cgpth_tree_cost": (C.c_int, [C.POINTER(BvhNode), C.c_uint32, C.c_double, C.c_double, C.POINTER(TreeCost)]),
     "cgpth_scene_flatten": (C.c_int, [_vp, C.POINTER(SceneDesc)]),
     "cgpth_scene_get_camera": (C.c_int, [_vp, C.POINTER(Camera)]),
     "cgpth_scene_get_settings": (C.c_int, [_vp, C.POINTER(Settings)]),

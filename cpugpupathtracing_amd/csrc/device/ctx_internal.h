@@ -28,6 +28,7 @@ struct SceneBuffers {                             // cgpt_scene_upload installs 
     DevBuf<uint32_t> skin_scratch;                // cgpt_scene_skin_mesh: 8 words a pose reads back (refit.hip: kSkinScratchWords), allocated with the first skin
     DevBuf<uint32_t> pose_batch;                  // cgpt_scene_pose_objects: the tables and scratch of the last batch (refit.hip: PoseObjects), grown on demand
     DevBuf<uint32_t> anim_batch;                  // cgpt_scene_animate_objects / _layers: per entry a flag word, then the entry records the kernel reads, grown on demand
+    DevBuf<uint32_t> tree_cost;                   // cgpt_scene_tree_costs: the results, entries and block partials of the last call (tree_cost.hip), grown on demand
 };
 // The skin of one object (cgpt_scene_set_skin): the bind pose, 12 joint indices and 12 weights a triangle, and the room of a pose's
 // joint matrices.  Not part of the scene's footprint; an upload drops every skin.
@@ -350,6 +351,7 @@ int GroupClipDestroy(cgpt_ctx* ctx, uint32_t clip);
 int GroupAnimateObjects(cgpt_ctx* ctx, const cgpt_animation* entries, uint32_t n_entries);
 int GroupAnimateLayers(cgpt_ctx* ctx, const cgpt_layered_animation* entries, uint32_t n_entries);
 int GroupRebuildMesh(cgpt_ctx* ctx, uint32_t obj_index, uint32_t build_option, uint32_t* n_nodes_out, uint32_t* max_depth_out);
+int GroupTreeCosts(cgpt_ctx* ctx, const uint32_t* obj_indices, uint32_t n, double c_inner, double c_tri, cgpt_tree_cost* out);
 int GroupRender(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p);
 int GroupResetAccumulator(cgpt_ctx* ctx);
 int GroupReadAccumulator(cgpt_ctx* ctx, float* dst, size_t n_floats);

@@ -455,6 +455,22 @@ int GroupRebuildMesh(cgpt_ctx* ctx, uint32_t obj_index, uint32_t build_option, u
     return GroupEdit(ctx, [&](cgpt_ctx* m, bool first) { return cgpt_scene_rebuild_mesh(m, obj_index, build_option, first ? n_nodes_out : nullptr, first ? max_depth_out : nullptr); });
 }
 
+// every member sums its own copy and all must report the same bits (tree_cost.hip: the sums' order is fixed); the first member's are returned.
+// A read: a refusal or a disagreement drops no scene
+int GroupTreeCosts(cgpt_ctx* ctx, const uint32_t* obj_indices, uint32_t n, double c_inner, double c_tri, cgpt_tree_cost* out)
+{
+    std::vector<cgpt_ctx*>& ms = ctx->group->members;
+    std::vector<cgpt_tree_cost> first(n), other(n);
+    for (size_t r = 0; r < ms.size(); ++r) {
+        const int rc = cgpt_scene_tree_costs(ms[r], obj_indices, n, c_inner, c_tri, n && out ? (r == 0 ? first.data() : other.data()) : out);
+        if (rc != CGPT_OK) return Propagate(ctx, ms[r], rc);
+        if (r > 0 && n && memcmp(first.data(), other.data(), sizeof(cgpt_tree_cost) * n) != 0)
+            return Propagate(ctx, ms[r], CtxFail(ms[r], CGPT_ERR_HIP, "cgpt_scene_tree_costs: this device's costs differ from device %d's: the copies of the scene are no longer equal", ms[0]->device));
+    }
+    if (n && out) memcpy(out, first.data(), sizeof(cgpt_tree_cost) * n);
+    return CGPT_OK;
+}
+
 int GroupUpdateRoughness(cgpt_ctx* ctx, const float* roughness, uint32_t n)
 {
     return GroupEdit(ctx, [&](cgpt_ctx* m, bool) { return cgpt_scene_update_roughness(m, roughness, n); });

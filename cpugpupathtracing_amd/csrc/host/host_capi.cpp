@@ -16,6 +16,7 @@
 #include "shade_items.h"
 #include "skinning.h"
 #include "transform_math.h"
+#include "tree_cost.h"
 
 using namespace cgpt;
 
@@ -436,6 +437,39 @@ int cgpth_scene_rebuild_bvh(cgpth_scene* scene, uint32_t obj_index, int build_op
             return Fail("bad argument to cgpth_scene_rebuild_bvh");
         if (!scene->scene.objects[obj_index].bvh->Rebuild((MeshBVH::BuildOption)build_option))
             return Fail("the binned build needs finite positions of magnitude <= 1e30 (the BVH is unchanged)");
+        return CGPT_OK;
+    });
+}
+
+int cgpth_tree_cost(const cgpt_bvh_node* nodes, uint32_t n_nodes, double c_inner, double c_tri, cgpt_tree_cost* out)
+{
+    return Guarded<int>((int)CGPT_ERR_INVALID, [&]() -> int {
+        if (!nodes || !out) return Fail("bad argument to cgpth_tree_cost: a null array");
+        if (n_nodes == 0u) return Fail("cgpth_tree_cost: no nodes");
+        if (!TreeCostConstantOk(c_inner) || !TreeCostConstantOk(c_tri)) return Fail("cgpth_tree_cost: c_inner and c_tri must be finite and > 0");
+        const cgpt_bvh_node& root = nodes[0];
+        if (root.prim_count != 0u) {                                          // a root that never split (tree_cost.h)
+            *out = { c_tri * (double)root.prim_count, 0.0, 0u, 1u, root.prim_count, 0u };
+            return CGPT_OK;
+        }
+        TreeCostSums s;
+        std::vector<uint32_t> stack{ 0u };
+        uint32_t n_inner = 0;
+        while (!stack.empty()) {
+            const uint32_t i = stack.back(); stack.pop_back();
+            const uint32_t l = nodes[i].left_first;
+            if (l == 0u || l >= n_nodes || l + 1u >= n_nodes) return Fail("cgpth_tree_cost: node " + std::to_string(i) + " names children outside the array");
+            if (++n_inner > n_nodes / 2u) return Fail("cgpth_tree_cost: the nodes form no tree");
+            for (uint32_t c = l + 1u; c + 1u > l; --c) {                      // right, then left: the left subtree is walked first
+                const cgpt_bvh_node& n = nodes[c];
+                TreeCostAddChild(s, TreeCostHalfArea(n.aabb_min[0], n.aabb_min[1], n.aabb_min[2], n.aabb_max[0], n.aabb_max[1], n.aabb_max[2]), n.prim_count);
+                if (n.prim_count == 0u) stack.push_back(c);
+            }
+        }
+        const cgpt_bvh_node& a = nodes[root.left_first];
+        const cgpt_bvh_node& b = nodes[root.left_first + 1u];
+        const double h_root = TreeCostRootHalfArea(a.aabb_min, a.aabb_max, b.aabb_min, b.aabb_max);
+        *out = { TreeCostTotal(c_inner, c_tri, h_root, s.inner, s.leaf), h_root, n_inner, s.n_leaves, s.max_leaf_tris, 0u };
         return CGPT_OK;
     });
 }

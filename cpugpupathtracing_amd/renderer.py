@@ -34,6 +34,13 @@ SHADE_RESULT = np.dtype([("flags", np.uint32), ("o", np.float32, 3), ("d", np.fl
 assert SHADE_SAMPLE.itemsize == C.sizeof(N.ShadeSample) and SHADE_RESULT.itemsize == C.sizeof(N.ShadeResult)
 
 
+# cgpt_tree_cost / cgpt_rebuild_result as numpy records (Renderer.tree_costs, Renderer.rebuild_degraded)
+TREE_COST_DTYPE = np.dtype([("cost", np.float64), ("root_half_area", np.float64), ("n_inner", np.uint32), ("n_leaves", np.uint32),
+                            ("max_leaf_tris", np.uint32), ("reserved", np.uint32)])
+REBUILD_RESULT_DTYPE = np.dtype([("cost_before", np.float64), ("cost_after", np.float64), ("rebuilt", np.uint32), ("reserved", np.uint32)])
+assert TREE_COST_DTYPE.itemsize == C.sizeof(N.TreeCost) and REBUILD_RESULT_DTYPE.itemsize == C.sizeof(N.RebuildResult)
+
+
 class DeviceError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"[cgpt status {code}] {message}")
@@ -98,6 +105,8 @@ class Renderer:
         self._transformed = False     # the device holds a transform that is not the identity (cgpt_scene_update_transforms)
         self.instanced = False        # the last upload was cgpt_scene_upload_instanced
         self._skin_joints = {}        # object -> joint count of the skin set_skin installed (joint_matrices)
+        self._cost_baseline = {}      # device copy (_copy_of) -> the tree cost rebuild_degraded compares with; dropped by upload()
+        self._cost_constants = (1.0, 1.0)   # ... and the (c_inner, c_tri) it was measured under
 
     def _check(self, rc: int):
         if rc != 0:
@@ -155,6 +164,7 @@ class Renderer:
         self.instanced = bool(instanced)
         self._glossy = self._rough_glass = self._smooth = self._transformed = False   # the upload reset every roughness, flag and transform
         self.scene = scene
+        self._cost_baseline = {}
         self._node_counts = [desc.objects[k].node_count for k in range(desc.n_objects)]   # the uploaded trees (export_bvh)
         # the objects that share a device copy (rebuild_mesh): the same four slice words under an instanced upload, else every object alone
         slices = [(o.kind, o.node_offset, o.node_count, o.tri_offset, o.tri_count) for o in (desc.objects[k] for k in range(desc.n_objects))]
@@ -360,7 +370,63 @@ class Renderer:
         for k in range(len(self._node_counts)):                          # every placement of the copy shows the new tree
             if self._copy_of[k] == self._copy_of[obj_index]:
                 self._node_counts[k] = n_nodes.value
+        if self._copy_of[obj_index] in self._cost_baseline:               # rebuild_degraded's baseline follows the new tree
+            c_inner, c_tri = self._cost_constants
+            self._cost_baseline[self._copy_of[obj_index]] = float(self.tree_costs([obj_index], c_inner, c_tri)["cost"][0])
         return n_nodes.value, depth.value
+
+    def tree_costs(self, objs, c_inner: float = 1.0, c_tri: float = 1.0) -> np.ndarray:
+        """cgpt_scene_tree_costs: the surface-area cost of the trees of the uploaded meshes `objs` as they are now on the device, one
+        call and one small readback for all of them.  A structured array with the fields cost, root_half_area,
+        n_inner, n_leaves, max_leaf_tris per entry -- what Scene.tree_cost / tree_cost(export_bvh(obj)) compute on the host, to
+        rounding.  The call only reads: the accumulator, the guides and the temporal history are kept."""
+        o = np.ascontiguousarray(objs, np.uint32).ravel()
+        out = np.zeros(o.size, TREE_COST_DTYPE)
+        self._check(self.L.cgpt_scene_tree_costs(self._ctx, o.ctypes.data_as(C.POINTER(C.c_uint32)), o.size, float(c_inner), float(c_tri),
+                                                 out.ctypes.data_as(C.POINTER(N.TreeCost))))
+        return out
+
+    def rebuild_degraded(self, objs, ratio: float, build_option: int = N.BUILD_SAH_BINNED, c_inner: float = 1.0, c_tri: float = 1.0) -> np.ndarray:
+        """cgpt_scene_rebuild_degraded with the baseline kept here: rebuilds, as rebuild_mesh does, every mesh of `objs` whose tree's
+        cost has grown past `ratio` times its baseline (DESIGN.md 5.36 has the table to choose a ratio from; there is no default).  The
+        baseline of a device copy is its cost at the first call that names it (so call it once at the bind pose), is replaced by the new
+        tree's cost after every rebuild -- this call's or rebuild_mesh's -- and is dropped by upload() and by a change of the
+        constants.  Returns a structured array with cost_before, cost_after and rebuilt per entry.  When nothing is rebuilt the scene
+        and the temporal history are untouched; otherwise call reset_accumulator() before the next frame."""
+        o = np.ascontiguousarray(objs, np.uint32).ravel()
+        if self._cost_constants != (float(c_inner), float(c_tri)):
+            self._cost_baseline = {}
+            self._cost_constants = (float(c_inner), float(c_tri))
+        copy_of = lambda k: self._copy_of[k] if k < len(self._copy_of) else ("out of range", k)   # the call refuses it
+        fresh = [int(k) for k in o if copy_of(int(k)) not in self._cost_baseline]
+        if fresh:
+            for k, c in zip(fresh, self.tree_costs(fresh, c_inner, c_tri)["cost"]):
+                self._cost_baseline.setdefault(copy_of(k), float(c))
+        rows = (N.RebuildCandidate * max(1, o.size))(*[N.RebuildCandidate(int(k), 0, self._cost_baseline[copy_of(int(k))]) for k in o])
+        out = np.zeros(o.size, REBUILD_RESULT_DTYPE)
+        rc = self.L.cgpt_scene_rebuild_degraded(self._ctx, rows, o.size, float(ratio), int(build_option), float(c_inner), float(c_tri),
+                                                out.ctypes.data_as(C.POINTER(N.RebuildResult)))
+        if rc != 0:                                                       # a refusal mid-call leaves the meshes rebuilt before it rebuilt:
+            message = self.L.cgpt_last_error(self._ctx).decode()          # follow their node counts and measure their baselines afresh next time
+            for k in sorted(set(int(k) for k in o if int(k) < len(self._copy_of))):
+                self._cost_baseline.pop(self._copy_of[k], None)
+                try:
+                    self._follow_tree(k, self.tree_costs([k], c_inner, c_tri)[0])
+                except DeviceError:
+                    pass
+            raise DeviceError(rc, message)
+        rebuilt = [int(k) for k, r in zip(o, out["rebuilt"]) if r]
+        if rebuilt:
+            for k, c in zip(rebuilt, self.tree_costs(rebuilt, c_inner, c_tri)):
+                self._follow_tree(k, c)
+                self._cost_baseline[self._copy_of[k]] = float(c["cost"])
+        return out
+
+    def _follow_tree(self, obj_index: int, cost):
+        """the node count (export_bvh) of every placement of `obj_index`'s copy, from its tree's cost record"""
+        for j in range(len(self._node_counts)):
+            if self._copy_of[j] == self._copy_of[obj_index]:
+                self._node_counts[j] = int(cost["n_inner"]) + int(cost["n_leaves"])
 
     def export_bvh(self, obj_index: int) -> np.ndarray:
         """The device's tree of mesh `obj_index` as it is now (after refits): nodes[n,8] uint32 words in the reference's 32-byte layout

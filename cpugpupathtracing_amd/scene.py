@@ -255,6 +255,18 @@ def wrap_time(t, begin, end, wrap):
     return np.float32(out.value)
 
 
+def tree_cost(nodes, c_inner: float = 1.0, c_tri: float = 1.0) -> N.TreeCost:
+    """cgpth_tree_cost: the surface-area cost of the tree in `nodes`, (n, 8) uint32 words as Scene.bvh_export and Renderer.export_bvh
+    return them: .cost, .root_half_area, .n_inner, .n_leaves, .max_leaf_tris.  It is what Renderer.tree_costs sums
+    on the device, to rounding."""
+    n = np.ascontiguousarray(nodes, np.uint32).reshape(-1, 8)
+    out = N.TreeCost()
+    rc = N.lib().cgpth_tree_cost(n.ctypes.data_as(C.POINTER(N.BvhNode)), n.shape[0], float(c_inner), float(c_tri), C.byref(out))
+    if rc != 0:
+        raise _host_error(rc, "tree_cost")
+    return out
+
+
 def primitive_abi(kind: int, mat_index: int, center=None, radius=None, normal=None, point=None) -> N.Object:
     """A cgpt_object for update_primitive: a sphere (center, radius) or a plane (normal, point)."""
     o = N.Object()
@@ -615,6 +627,10 @@ class Scene:
         _host_check(N.lib().cgpth_scene_bvh_export(self._h, obj_index, nodes.ctypes.data_as(C.POINTER(N.BvhNode)),
                                                    tri.ctypes.data_as(C.POINTER(C.c_uint32))), "bvh_export")
         return nodes, tri
+
+    def tree_cost(self, obj_index: int, c_inner: float = 1.0, c_tri: float = 1.0) -> N.TreeCost:
+        """The surface-area cost of mesh `obj_index`'s tree as the host holds it (tree_cost of its bvh_export)."""
+        return tree_cost(self.bvh_export(obj_index)[0], c_inner, c_tri)
 
     def flatten(self) -> N.SceneDesc:
         desc = N.SceneDesc()

@@ -4,7 +4,7 @@
 //
 //   g++ -std=c++17 -Iinclude -Icpugpupathtracing_amd/csrc/host examples/render_main.cpp
 //       -Lcpugpupathtracing_amd/lib -lcpugpupt -Wl,-rpath,$PWD/cpugpupathtracing_amd/lib -o render_main   (one command line)
-//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--spin DEG] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [--bend DEG] [--animate T [--loop] [--crossfade W]] [--bulge W] [--crowd N] [--rebuild [naive|intervals|binned]] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
+//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--spin DEG] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [--bend DEG] [--animate T [--loop] [--crossfade W]] [--bulge W] [--crowd N] [--rebuild [naive|intervals|binned]] [--rebuild-ratio R] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
 // --gpus N: ONE context over the first N GPUs of the node (cgpt_ctx_create with n_devices = N): every frame is spread over them in
 // interleaved row bands and the read-back gathers the float4 bands with one RCCL exchange over xGMI; the loop below does not
 // change.  --collective: take that code path with N = 1 too (what a one-GPU box can test).
@@ -72,6 +72,10 @@
 // (cgpt_scene_rebuild_mesh), with the binned builder unless OPTION says otherwise: the refit keeps a tree that was split
 // for the bind pose, and after a large bend its boxes overlap.  The triangles never leave the device.  A rebuild drops the temporal
 // history, as a refit does.
+// --rebuild-ratio R: rebuild only where it pays -- the cost of every posed mesh's tree (cgpt_scene_tree_costs) is measured once
+// at the bind pose, and after each frame's pose one cgpt_scene_rebuild_degraded call rebuilds the meshes whose cost has grown past R times
+// their reference (with --rebuild's builder; the reference of a rebuilt mesh becomes its new cost).  A line a frame and mesh gives the cost
+// before and after, and says where a mesh was rebuilt.  A frame in which nothing is rebuilt keeps the temporal history.
 // move_at > 0 scripts the input half of Update(dt) (ref: Main.cpp:277-297, Camera::Update :104-131): after that many samples the
 // camera is translated by (right, up, forward) as the A/D, Space/Shift, W/S keys would, the view changes, and the accumulator
 // is reset (ref: ResetAccumulator, Main.cpp:238-243) before the remaining samples are rendered from the new position.
@@ -100,6 +104,7 @@ int main(int argc, char** argv)
 {
     int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool spin = false; float spin_deg = 0.0f; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false; uint32_t n_instances = 0; bool bend = false; float bend_deg = 0.0f; bool bulge = false; float bulge_w = 0.0f; uint32_t crowd = 0; bool animate = false; float animate_t = 0.0f; bool loop = false; bool crossfade = false; float crossfade_w = 0.0f;
     bool rebuild = false; uint32_t rebuild_option = CGPT_BUILD_SAH_BINNED;
+    bool rebuild_degraded = false; double rebuild_ratio = 0.0;
     bool has_transform = false; float mesh_transform[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
     MeshBVH::BuildOption bvh_option = MeshBVH::BuildOption_SAHSplitIntervals;
     while (argc > 1 && std::string(argv[1]).rfind("--", 0) == 0) {
@@ -121,6 +126,10 @@ int main(int argc, char** argv)
                 rebuild_option = opt == "naive" ? CGPT_BUILD_NAIVE_SPLIT : opt == "intervals" ? CGPT_BUILD_SAH_SPLIT_INTERVALS : CGPT_BUILD_SAH_BINNED;
                 argv += 1; argc -= 1;
             }
+        }
+        else if (std::string(argv[1]) == "--rebuild-ratio" && argc > 2) {
+            rebuild_degraded = true; rebuild_ratio = atof(argv[2]); argv += 2; argc -= 2;
+            if (!(rebuild_ratio > 0.0) || !std::isfinite(rebuild_ratio)) { fprintf(stderr, "--rebuild-ratio needs a finite ratio > 0\n"); return 2; }
         }
         else if (std::string(argv[1]) == "--variance-guided") { variance_guided = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--smooth") { smooth = true; argv += 1; argc -= 1; }
@@ -352,6 +361,12 @@ int main(int argc, char** argv)
                 CHECK(cgpt_scene_set_skeleton(ctx, posed[k], &sd));
             }
         }
+        std::vector<cgpt_rebuild_candidate> candidates;                  // --rebuild-ratio: every posed mesh with its tree's cost at the bind pose
+        if (rebuild_degraded) {
+            std::vector<cgpt_tree_cost> costs(posed.size());
+            CHECK(cgpt_scene_tree_costs(ctx, posed.data(), (uint32_t)posed.size(), 1.0, 1.0, costs.data()));
+            for (size_t k = 0; k < posed.size(); ++k) candidates.push_back({ posed[k], 0u, costs[k].cost });
+        }
         std::vector<uint32_t> px((size_t)W * H);                         // the mesh bends every frame: SkinMesh, ResetAccumulator, Render, present
         const cgpt_camera cam = scene.camera.Abi();
         const cgpt_temporal_params tp = { 64.0f, 0.9f, 0.01f, CGPT_TEMPORAL_FOLLOW_POSES | (bulge ? (uint32_t)CGPT_TEMPORAL_FOLLOW_MORPHS : 0u) };   // each flag keeps its own kind of edit
@@ -400,6 +415,15 @@ int main(int argc, char** argv)
                     uint32_t n_nodes = 0, depth = 0;
                     CHECK(cgpt_scene_rebuild_mesh(ctx, obj, rebuild_option, &n_nodes, &depth));
                     printf("frame %u: object %u rebuilt, %u nodes, depth %u\n", frame, obj, n_nodes, depth);
+                }
+            }
+            if (rebuild_degraded) {                                      // ... or only the trees the pose has degraded: one call for all of them
+                std::vector<cgpt_rebuild_result> results(candidates.size());
+                CHECK(cgpt_scene_rebuild_degraded(ctx, candidates.data(), (uint32_t)candidates.size(), rebuild_ratio, rebuild_option, 1.0, 1.0, results.data()));
+                for (size_t k = 0; k < candidates.size(); ++k) {
+                    printf("frame %u: object %u tree cost %.4f -> %.4f (reference %.4f)%s\n", frame, candidates[k].obj_index, results[k].cost_before, results[k].cost_after,
+                           candidates[k].reference_cost, results[k].rebuilt ? ", rebuilt" : "");
+                    if (results[k].rebuilt) candidates[k].reference_cost = results[k].cost_after;
                 }
             }
             CHECK(cgpt_reset_accumulator(ctx));

@@ -351,6 +351,45 @@ int cgpt_scene_rebuild_mesh(cgpt_ctx* ctx, uint32_t obj_index, uint32_t build_op
  * or what the last cgpt_scene_rebuild_mesh reported):
  * what a host that keeps its own BVH (the BVH panel, a later Rebuild) copies back after a refit */
 int cgpt_scene_export_bvh(cgpt_ctx* ctx, uint32_t obj_index, cgpt_bvh_node* nodes_out, uint32_t n_nodes);
+/* The surface-area cost of uploaded meshes' trees as they are now, summed on the device (csrc/host/tree_cost.h states the
+ * metric, tests/tree_cost_ref.py the same in numpy): what tells a refitted tree that has gone bad from one that has not, without the
+ * readback of cgpt_scene_export_bvh.  For a mesh whose root split, in double from the float bounds: H(box) = dx dy + dy dz + dz dx, the
+ * root box = the union of the root's two child boxes, and
+ *   cost = (c_inner (H(root) + sum of H over inner children) + c_tri sum of H n_tris over leaf children) / H(root)
+ * over the child boxes of every splitting node -- the expected work of a ray that hits the root box, c_inner a node and c_tri a
+ * triangle; it does not change with the mesh's scale.  A mesh whose root is a leaf reports c_tri n_tris, root_half_area 0, n_inner 0 and
+ * n_leaves 1, with no device work.  n_inner counts the splitting nodes (the root among them), n_leaves the leaves.
+ * One call serves n entries with two launches and one readback on the context's stream; the same object may be named twice.  The sums
+ * have a fixed order: the same call returns the same bits, an entry returns the same bits alone or in any batch at any position, objects
+ * that share a copy (cgpt_scene_upload_instanced) report equal bits, and so does every device of a multi-device context -- each sums its
+ * own copy, the first device's numbers are returned, and a device that disagrees fails the call (CGPT_ERR_HIP; the scene is kept).
+ * The call only reads: no generation moves, the denoiser's guides and temporal history stay, renders and exports are bit-identical
+ * before and after.  Refused before any launch, with `out` unwritten and the entry named: no scene (CGPT_ERR_NO_SCENE); obj_indices or
+ * out NULL with n > 0, an object out of range, a sphere, a plane or a triangle object, a constant that is not finite and > 0
+ * (CGPT_ERR_INVALID).  n == 0 is CGPT_OK without a launch.  A cost that is not finite -- a bound that is not, or a root box without
+ * area -- is CGPT_ERR_INVALID naming the first such entry, with `out` unwritten.  An added export: CGPT_ABI_VERSION stays 2. */
+typedef struct cgpt_tree_cost {
+    double cost, root_half_area;
+    uint32_t n_inner, n_leaves, max_leaf_tris, reserved;   /* reserved: 0 */
+} cgpt_tree_cost;
+int cgpt_scene_tree_costs(cgpt_ctx* ctx, const uint32_t* obj_indices, uint32_t n, double c_inner, double c_tri, cgpt_tree_cost* out);
+/* Rebuild the meshes whose trees have degraded: one cgpt_scene_tree_costs over all entries gives cost_before; cgpt_scene_rebuild_mesh
+ * (build_option as there) then runs for every entry with cost_before > ratio * reference_cost, once per copy where several entries reach
+ * one (cgpt_scene_upload_instanced; every entry that reaches a rebuilt copy reports rebuilt = 1); one more cost call over those entries
+ * gives cost_after.  An entry whose copy was not rebuilt reports cost_after = cost_before and rebuilt = 0.  The call holds no baseline:
+ * the caller keeps cost_after as the next reference_cost.  When nothing is rebuilt nothing of the scene changes and the temporal history
+ * is kept; otherwise each rebuild acts as cgpt_scene_rebuild_mesh does.  A multi-device context decides once, from its first device's
+ * costs, and rebuilds on every device, so the copies stay equal.
+ * Refused up front, for every entry, before anything is rebuilt and with `results` unwritten: what cgpt_scene_tree_costs refuses; a
+ * ratio or a reference_cost that is not finite and > 0; and what cgpt_scene_rebuild_mesh can refuse without a launch -- an unknown
+ * build option, CGPT_BUILD_SAH_SPLIT_PRIMITIVES (CGPT_ERR_UNSUPPORTED), a first rebuild whose record span would pass 2^26 records.
+ * Its other refusals need the device and may come mid-call: the binned build's domain check, a new tree deeper than the traversal
+ * stack, and the 2^26 limit reached by the spans of several first rebuilds together.  The error then names the entry, `results` is
+ * unwritten, and the meshes already rebuilt stay rebuilt and valid.  An added export: CGPT_ABI_VERSION stays 2. */
+typedef struct cgpt_rebuild_candidate { uint32_t obj_index, reserved; double reference_cost; } cgpt_rebuild_candidate;
+typedef struct cgpt_rebuild_result { double cost_before, cost_after; uint32_t rebuilt, reserved; } cgpt_rebuild_result;
+int cgpt_scene_rebuild_degraded(cgpt_ctx* ctx, const cgpt_rebuild_candidate* entries, uint32_t n, double ratio, uint32_t build_option,
+                                double c_inner, double c_tri, cgpt_rebuild_result* results);
 /* Primitive::RenderImGui's sliders (ref: Primitives.cpp:385-410): a sphere's centre and radius (radius^2 = r*r, as at upload) or a
  * plane's normal and point.  obj->kind and obj->mat_index must equal the uploaded ones; the other fields of *obj are ignored. */
 int cgpt_scene_update_primitive(cgpt_ctx* ctx, uint32_t obj_index, const cgpt_object* obj);

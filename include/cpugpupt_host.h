@@ -156,6 +156,13 @@ int cgpth_scene_permute_objects(cgpth_scene* scene, const uint32_t* order, uint3
 int cgpth_scene_bvh_info(const cgpth_scene* scene, uint32_t obj_index, cgpth_bvh_info* out);
 /* nodes: nodes_used x cgpt_bvh_node; tri_indices: num_triangles */
 int cgpth_scene_bvh_export(const cgpth_scene* scene, uint32_t obj_index, cgpt_bvh_node* nodes, uint32_t* tri_indices);
+/* the host statement of cgpt_scene_tree_costs (csrc/host/tree_cost.h states the metric; tests/tree_cost_ref.py the same in numpy;
+ * DESIGN.md 5.36): the cost of the tree in `nodes`, n_nodes records in the layout and numbering cgpth_scene_bvh_export and
+ * cgpt_scene_export_bvh return (node 0 the root; prim_count 0: the children are left_first and left_first + 1).  The nodes are walked
+ * from the root; the device sums in another order, so the two agree to rounding, not in every bit.  Refused with CGPT_ERR_INVALID and
+ * nothing written: nodes or out NULL, n_nodes 0, a constant that is not finite and > 0, a child index outside the array, nodes that
+ * form no tree.  A cost that is not finite is returned as it is. */
+int cgpth_tree_cost(const cgpt_bvh_node* nodes, uint32_t n_nodes, double c_inner, double c_tri, cgpt_tree_cost* out);
 /* flatten for cgpt_scene_upload; pointers stay valid until the scene is changed or freed */
 int cgpth_scene_flatten(cgpth_scene* scene, cgpt_scene_desc* out);
 int cgpth_scene_get_camera(const cgpth_scene* scene, cgpt_camera* out);
