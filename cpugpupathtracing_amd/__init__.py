@@ -9,8 +9,11 @@ from ._native import (ANIM_WRAP_CLAMP, ANIM_WRAP_LOOP, ANIM_WRAP_PINGPONG, CTX_F
                       NativeLibraryError)
 from .renderer import DeviceError, Renderer
 from .scene import REFERENCE_MATERIALS, HostError, Material, Mesh, Scene, Settings, animate_joints, animate_layers, clip_range, morph_triangles, skin_triangles, tree_cost, triangles_from_arrays, wrap_time
+from ._native import ExposureInfo, ExposureState
+from .tonemap import adaptation_alpha, tonemap_host
 
 __all__ = [
+    "tonemap_host", "adaptation_alpha", "ExposureState", "ExposureInfo",
     "Renderer", "DeviceError", "Scene", "Mesh", "Material", "Settings", "HostError", "NativeLibraryError", "REFERENCE_MATERIALS",
     "triangles_from_arrays", "skin_triangles", "morph_triangles", "animate_joints", "animate_layers", "clip_range", "wrap_time", "tree_cost",
     "BUILD_NAIVE", "BUILD_SAH_INTERVALS", "BUILD_SAH_PRIMITIVES", "BUILD_SAH_BINNED", "MODE_COMPARISON", "MODE_BRUTE_FORCE", "MODE_ADVANCED",

@@ -228,6 +228,32 @@ class RebuildResult(C.Structure):
     _fields_ = [("cost_before", C.c_double), ("cost_after", C.c_double), ("rebuilt", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+TONEMAP_ACCUMULATOR, TONEMAP_DENOISED, TONEMAP_HOST = 0, 1, 2               # cgpt_tonemap_source
+CURVE_CLAMP, CURVE_REINHARD, CURVE_ACES, CURVE_HABLE = 0, 1, 2, 3           # cgpt_tonemap_curve
+TRANSFER_LINEAR, TRANSFER_SRGB = 0, 1                                       # cgpt_tonemap_transfer
+TONEMAP_AUTO_EXPOSURE = 1                                                   # cgpt_tonemap_flags
+EXPOSURE_ADAPTED, EXPOSURE_METERED = 1, 2                                   # cgpt_exposure_info.valid
+
+
+class TonemapParams(C.Structure):
+    """cgpt_tonemap_params"""
+    _fields_ = [("source", C.c_uint32), ("curve", C.c_uint32), ("transfer", C.c_uint32), ("flags", C.c_uint32),
+                ("exposure_scale", C.c_float), ("ev_bias", C.c_int32), ("white", C.c_float),
+                ("key", C.c_float), ("low_fraction", C.c_float), ("high_fraction", C.c_float), ("alpha", C.c_float),
+                ("src_rgba", C.POINTER(C.c_float)), ("src_width", C.c_uint32), ("src_height", C.c_uint32)]
+
+
+class ExposureInfo(C.Structure):
+    """cgpt_exposure_info"""
+    _fields_ = [("mean_index", C.c_double), ("adapted_index", C.c_double), ("exposure", C.c_float), ("valid", C.c_uint32),
+                ("n_counted", C.c_uint64), ("n_ignored", C.c_uint64), ("histogram", C.c_uint32 * 256)]
+
+
+class ExposureState(C.Structure):
+    """cgpth_exposure_state: what a context keeps between auto-exposure calls"""
+    _fields_ = [("adapted_index", C.c_double), ("valid", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class TopLevelView(C.Structure):
     """cgpth_top_level_view: n_nodes records of 8 floats {lo.xyz, bits(skip) | hi.xyz, bits(object)}, n_entry node indices."""
     _fields_ = [("nodes", _fp), ("n_nodes", C.c_size_t), ("entry", _up), ("n_entry", C.c_size_t)]
@@ -301,6 +327,9 @@ PROTOTYPES = {
     "cgpt_denoise_variance_guided": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(DenoiseParams), C.POINTER(TemporalParams),
                                                C.POINTER(VarianceParams), _fp, C.c_size_t, _up, C.c_size_t]),
     "cgpt_read_variance": (C.c_int, [_vp, _fp, C.c_size_t]),
+    "cgpt_tonemap": (C.c_int, [_vp, C.POINTER(TonemapParams), _fp, C.c_size_t, _up, C.c_size_t]),
+    "cgpt_read_exposure": (C.c_int, [_vp, C.POINTER(ExposureInfo)]),
+    "cgpt_exposure_reset": (C.c_int, [_vp]),
     "cgpt_measure_issue_rate": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     # cpugpupt_host.h
     "cgpth_last_error": (C.c_char_p, []),
@@ -352,6 +381,8 @@ PROTOTYPES = {
     "cgpth_scene_bvh_info": (C.c_int, [_vp, C.c_uint32, C.POINTER(BvhInfo)]),
     "cgpth_scene_bvh_export": (C.c_int, [_vp, C.c_uint32, C.POINTER(BvhNode), _up]),
     "cgpth_tree_cost": (C.c_int, [C.POINTER(BvhNode), C.c_uint32, C.c_double, C.c_double, C.POINTER(TreeCost)]),
+    "cgpth_luminance_bin": (C.c_int, [C.c_float]),
+    "cgpth_tonemap": (C.c_int, [C.POINTER(TonemapParams), C.POINTER(ExposureState), _fp, C.c_size_t, _up, C.c_size_t, C.POINTER(ExposureInfo)]),
     "cgpth_scene_flatten": (C.c_int, [_vp, C.POINTER(SceneDesc)]),
     "cgpth_scene_get_camera": (C.c_int, [_vp, C.POINTER(Camera)]),
     "cgpth_scene_get_settings": (C.c_int, [_vp, C.POINTER(Settings)]),

@@ -83,7 +83,7 @@ void FreeScene(cgpt_ctx* ctx)
     ctx->has_scene = false;
 }
 
-void FreeFramebuffer(cgpt_ctx* ctx) { ctx->fb = FrameBuffers{}; }
+void FreeFramebuffer(cgpt_ctx* ctx) { ctx->fb = FrameBuffers{}; ctx->denoised = nullptr; }   // ... and no denoised result of the old frame (CGPT_TONEMAP_DENOISED)
 
 int EnsureFramebuffer(cgpt_ctx* ctx, uint32_t W, uint32_t H, uint32_t n_rows, const uint32_t key[5])
 {
@@ -499,6 +499,7 @@ int TranslateSettings(cgpt_ctx* ctx, const cgpt_settings& settings, DevSettings&
 int RenderEnqueue(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_settings* settings, const cgpt_render_params* p)
 {
     ctx->pending_kernel = 0;
+    ctx->denoised = nullptr;                                                   // CGPT_TONEMAP_DENOISED: the last filter call's result is of an older frame
     if (!camera || !settings || !p) return CtxFail(ctx, CGPT_ERR_INVALID, "null argument");
     if (!ctx->has_scene) return CtxFail(ctx, CGPT_ERR_NO_SCENE, "cgpt_render before cgpt_scene_upload");
     DevRenderArgs args{};
@@ -621,6 +622,7 @@ int cgpt_reset_accumulator(cgpt_ctx* ctx)
     if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupResetAccumulator(ctx); });
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->num_accumulated = 0;                                                  // ref: Main.cpp:240-242
+    ctx->denoised = nullptr;
     if (ctx->fb.accumulator.p) {
         const size_t n = (size_t)ctx->width * ctx->n_rows;
         HIP_TRY(ctx, hipMemsetAsync(ctx->fb.accumulator.p, 0, n * sizeof(float4), ctx->stream));
@@ -661,6 +663,7 @@ int cgpt_write_accumulator(cgpt_ctx* ctx, const cgpt_render_params* p, const flo
 {
     if (!ctx) return CGPT_ERR_INVALID;
     if (ctx->group) return Guarded(ctx, __func__, [&] { return GroupWriteAccumulator(ctx, p, src, n_floats, num_accumulated); });
+    ctx->denoised = nullptr;
     if (!p || !src) return CtxFail(ctx, CGPT_ERR_INVALID, "null argument");
     Band band;
     int rc = ResolveBand(ctx, *p, band);

@@ -145,6 +145,14 @@ struct DenoiseBuffers {                           // denoise.hip; each group is 
     DevBuf<float4> morph_table;                   // 2 float4 per object (MorphRecord), beside pose_table
     DevBuf<uint2> morph_active;                   // the history's active tables {target, bits(weight)} of every re-posed owner, one after the other
 };
+// The display stage (tonemap.hip): buffers of its own, each grown on demand.  table: the 256 bin counts and, behind them,
+// the ignored pixels' tally -- zero between calls (exposure_resolve clears what it read); record: what exposure_resolve wrote
+struct TonemapBuffers {
+    DevBuf<float4> src, out;                      // a CGPT_TONEMAP_HOST image as uploaded; {r, g, b, 1}
+    DevBuf<uint32_t> pixels;
+    DevBuf<uint32_t> table;
+    DevBuf<cgpt_exposure_info> record;
+};
 template <class... B> void ResetAll(B&... b) { (b.Reset(), ...); }
 // What the uploaded scene has that a kernel variant must carry: a roughness > 0, a transmission roughness > 0, a smooth-normal flag (they live in
 // h_objects[i].smooth), a transform that is no identity (the flags live in obj_trace).  All false after an upload, each kept by the edit that owns it.
@@ -290,6 +298,19 @@ struct cgpt_ctx {
     bool moments_valid = false;
     bool variance_valid = false;
     uint32_t variance_frame[4] = { 0, 0, 0, 0 };  // as guide_frame
+    // CGPT_TONEMAP_DENOISED: the float4 result of the last successful filter call, one of dn.filter[] (n pixels).  Dropped when a filter
+    // call starts, by a render, cgpt_reset_accumulator, cgpt_write_accumulator, a framebuffer reallocation and DenoiseFree
+    const float4* denoised = nullptr;
+    size_t denoised_n = 0;
+
+    // the display stage (tonemap.hip).  A multi-device context keeps all of it on its first member.  m_adapted: the adapted histogram
+    // index (tonemap.h), context state that uploads and edits keep; exposure_info: the last successful auto-exposure call's reading
+    cgpt::TonemapBuffers tm;
+    uint32_t tonemap_cus = 0;                     // QueryCuCount
+    double m_adapted = 0.0;
+    bool m_adapted_valid = false;
+    cgpt_exposure_info exposure_info{};
+    bool exposure_info_valid = false;
 };
 
 

@@ -43,6 +43,7 @@
 #include "rt_device.hpp"
 #include "shade_device.hpp"
 #include "skinning.h"
+#include "tonemap.h"
 
 namespace cgpt {
 
@@ -158,7 +159,7 @@ __global__ void __launch_bounds__(256) denoise_prepare(const float4* __restrict_
 __device__ __forceinline__ constexpr float tap(int d) { return d == 0 ? 0.375f : (d == 1 || d == -1 ? 0.25f : 0.0625f); }
 
 // l(c), the luminance the variance-guided filter measures
-__device__ __forceinline__ float luminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+__device__ __forceinline__ float luminance(float r, float g, float b) { return Luminance(r, g, b); }   // tonemap.h states it
 
 // a tap's coordinate clamped into [0, n): a tap outside the band is loaded from the nearest pixel inside it and masked by a select.
 // (A row's clamp is written on its row_in instead: through this helper the kernels' instruction streams moved.)
@@ -1461,6 +1462,7 @@ int RunStages(cgpt_ctx* ctx, const Frame& f, const cgpt_camera* camera, Stages s
         HIP_TRY(ctx, hipGetLastError());
     }
     if ((rc = ReadBack(ctx, d, n, out, dst_rgba, dst_pixels)) != CGPT_OK) return rc;
+    d->denoised = out; d->denoised_n = n;                                      // CGPT_TONEMAP_DENOISED
     if (st.temporal) {
         StoreTemporalKey(d, camera, key, demodulate, xform, poses, morphs);
         d->moments_valid = st.variance;
@@ -1483,6 +1485,7 @@ int FilterCall(cgpt_ctx* ctx, const cgpt_camera* camera, const cgpt_denoise_para
                const cgpt_variance_params* variance, Stages want, float* dst_rgba, size_t n_floats, uint32_t* dst_pixels, size_t n_pixels)
 {
     if (!ctx) return CGPT_ERR_INVALID;
+    (ctx->group ? GroupFirstMember(ctx) : ctx)->denoised = nullptr;            // CGPT_TONEMAP_DENOISED: only a call that succeeds leaves a result
     Frame f;
     int rc = ResolveFrame(ctx, true, camera, f);
     if (rc != CGPT_OK) return rc;
@@ -1521,6 +1524,7 @@ int CopyToHost(cgpt_ctx* ctx, cgpt_ctx* d, void* dst, const void* src, size_t by
 void DenoiseFree(cgpt_ctx* ctx)
 {
     ctx->dn = DenoiseBuffers{};
+    ctx->denoised = nullptr;
     ctx->guides_valid = false;
     ctx->temporal_valid = false;
     ctx->moments_valid = false;

@@ -617,6 +617,37 @@ class Renderer:
         self._check(self.L.cgpt_read_variance(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
         return out
 
+    def tonemap(self, source="accumulator", curve="aces", transfer="srgb", auto: bool = True, image: Optional[np.ndarray] = None,
+                **params) -> Tuple[np.ndarray, np.ndarray]:
+        """cgpt_tonemap, the display stage: linear radiance through an exposure, a tone curve ("clamp", "reinhard",
+        "aces", "hable") and a transfer function ("linear", "srgb") on the device.  source: "accumulator" (the rendered band, divided
+        as pixels() divides it), "denoised" (the result of the last denoise*() call, still on the device) or "host" with
+        image = (rows, width, 4) float32.  auto=True meters the frame's luminance histogram and moves the renderer's adapted exposure
+        towards it by alpha (adaptation_alpha(dt, speed); exposure() reads the result, exposure_reset() forgets the adaptation);
+        auto=False applies exposure_scale 2^ev_bias.  params: exposure_scale, ev_bias, white, key, low_fraction, high_fraction, alpha
+        (tonemap.tonemap_params).  Returns (rows, width, 4) float32 {r, g, b, 1} and (rows, width) uint32 pixels packed as pixels()
+        packs them.  The accumulator, pixels(), the denoiser's state and the statistics are left as they are."""
+        from .tonemap import tonemap_params
+        p, keep = tonemap_params(source=source, curve=curve, transfer=transfer, auto=auto, image=image, **params)
+        rows, width = (keep.shape[0], keep.shape[1]) if keep is not None and p.source == N.TONEMAP_HOST else (self.n_rows, self.width)
+        rgba = np.empty((rows, width, 4), np.float32)
+        px = np.empty((rows, width), np.uint32)
+        self._check(self.L.cgpt_tonemap(self._ctx, C.byref(p), rgba.ctypes.data_as(C.POINTER(C.c_float)), rgba.size,
+                                        px.ctypes.data_as(C.POINTER(C.c_uint32)), px.size))
+        return rgba, px
+
+    def exposure(self) -> N.ExposureInfo:
+        """cgpt_read_exposure: the reading of the last successful tonemap(auto=True) -- .mean_index and .adapted_index (histogram
+        indices: eighths of an octave above 2^-16), .exposure, .valid (N.EXPOSURE_ADAPTED | N.EXPOSURE_METERED), .n_counted,
+        .n_ignored, .histogram[256]."""
+        info = N.ExposureInfo()
+        self._check(self.L.cgpt_read_exposure(self._ctx, C.byref(info)))
+        return info
+
+    def exposure_reset(self):
+        """cgpt_exposure_reset: the next auto-exposure call sets the adapted exposure instead of approaching it."""
+        self._check(self.L.cgpt_exposure_reset(self._ctx))
+
     def accumulator_device_ptr(self) -> Tuple[int, int]:
         ptr = C.c_void_p(); nbytes = C.c_size_t()
         self._check(self.L.cgpt_accumulator_device_ptr(self._ctx, C.byref(ptr), C.byref(nbytes)))

@@ -4,7 +4,7 @@
 //
 //   g++ -std=c++17 -Iinclude -Icpugpupathtracing_amd/csrc/host examples/render_main.cpp
 //       -Lcpugpupathtracing_amd/lib -lcpugpupt -Wl,-rpath,$PWD/cpugpupathtracing_amd/lib -o render_main   (one command line)
-//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--spin DEG] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [--bend DEG] [--animate T [--loop] [--crossfade W]] [--bulge W] [--crowd N] [--rebuild [naive|intervals|binned]] [--rebuild-ratio R] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
+//   ./render_main [--gpus N [--collective]] [--denoise] [--temporal] [--spin DEG] [--variance-guided] [--ground-roughness R] [--glass-roughness R] [--bvh intervals|binned] [--nee-candidates M] [--top-level] [--instances N] [--smooth] [--mesh-transform m00 .. m23] [--bend DEG] [--animate T [--loop] [--crossfade W]] [--bulge W] [--crowd N] [--rebuild [naive|intervals|binned]] [--rebuild-ratio R] [--tonemap clamp|reinhard|aces|hable] [--srgb] [--exposure auto|EV] [--adapt ALPHA] [model.gltf] [width height spp [preview_every [move_at right up forward]]]
 // --gpus N: ONE context over the first N GPUs of the node (cgpt_ctx_create with n_devices = N): every frame is spread over them in
 // interleaved row bands and the read-back gathers the float4 bands with one RCCL exchange over xGMI; the loop below does not
 // change.  --collective: take that code path with N = 1 too (what a one-GPU box can test).
@@ -76,6 +76,12 @@
 // at the bind pose, and after each frame's pose one cgpt_scene_rebuild_degraded call rebuilds the meshes whose cost has grown past R times
 // their reference (with --rebuild's builder; the reference of a rebuilt mesh becomes its new cost).  A line a frame and mesh gives the cost
 // before and after, and says where a mesh was rebuilt.  A frame in which nothing is rebuilt keeps the temporal history.
+// --tonemap CURVE, --srgb, --exposure auto|EV, --adapt ALPHA: the display stage (cgpt_tonemap).  Any of them sends every PPM
+// the run writes -- raw, --denoise, --temporal, --variance-guided, the frames of a sequence -- through an exposure, the tone curve (clamp
+// without --tonemap), and with --srgb the sRGB transfer function, on the device from the image's own source (the accumulator, or the filter's
+// result where it lies).  --exposure auto (the default) meters each frame's luminance histogram and, in a --temporal / --spin / --bend /
+// --animate sequence, moves the exposure towards it by ALPHA a frame (1, the default: every frame its own); --exposure EV is 2^EV, fixed.
+// render.pfm and render.acc stay linear.
 // move_at > 0 scripts the input half of Update(dt) (ref: Main.cpp:277-297, Camera::Update :104-131): after that many samples the
 // camera is translated by (right, up, forward) as the A/D, Space/Shift, W/S keys would, the view changes, and the accumulator
 // is reset (ref: ResetAccumulator, Main.cpp:238-243) before the remaining samples are rendered from the new position.
@@ -105,6 +111,8 @@ int main(int argc, char** argv)
     int n_gpus = 1; uint32_t ctx_flags = 0; bool denoise = false; bool temporal = false; bool spin = false; float spin_deg = 0.0f; bool variance_guided = false; float ground_roughness = -1.0f, glass_roughness = -1.0f; uint32_t nee_candidates = 1; bool smooth = false; bool top_level = false; uint32_t n_instances = 0; bool bend = false; float bend_deg = 0.0f; bool bulge = false; float bulge_w = 0.0f; uint32_t crowd = 0; bool animate = false; float animate_t = 0.0f; bool loop = false; bool crossfade = false; float crossfade_w = 0.0f;
     bool rebuild = false; uint32_t rebuild_option = CGPT_BUILD_SAH_BINNED;
     bool rebuild_degraded = false; double rebuild_ratio = 0.0;
+    bool tonemap = false;                                                // --tonemap / --srgb / --exposure / --adapt: the display stage in front of every PPM
+    cgpt_tonemap_params tm = { CGPT_TONEMAP_ACCUMULATOR, CGPT_CURVE_CLAMP, CGPT_TRANSFER_LINEAR, CGPT_TONEMAP_AUTO_EXPOSURE, 1.0f, 0, 4.0f, 0.18f, 0.5f, 0.02f, 1.0f, nullptr, 0u, 0u };
     bool has_transform = false; float mesh_transform[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
     MeshBVH::BuildOption bvh_option = MeshBVH::BuildOption_SAHSplitIntervals;
     while (argc > 1 && std::string(argv[1]).rfind("--", 0) == 0) {
@@ -130,6 +138,28 @@ int main(int argc, char** argv)
         else if (std::string(argv[1]) == "--rebuild-ratio" && argc > 2) {
             rebuild_degraded = true; rebuild_ratio = atof(argv[2]); argv += 2; argc -= 2;
             if (!(rebuild_ratio > 0.0) || !std::isfinite(rebuild_ratio)) { fprintf(stderr, "--rebuild-ratio needs a finite ratio > 0\n"); return 2; }
+        }
+        else if (std::string(argv[1]) == "--tonemap" && argc > 2) {
+            const std::string c = argv[2];
+            if (c != "clamp" && c != "reinhard" && c != "aces" && c != "hable") { fprintf(stderr, "--tonemap needs clamp, reinhard, aces or hable\n"); return 2; }
+            tonemap = true; tm.curve = c == "clamp" ? CGPT_CURVE_CLAMP : c == "reinhard" ? CGPT_CURVE_REINHARD : c == "aces" ? CGPT_CURVE_ACES : CGPT_CURVE_HABLE;
+            argv += 2; argc -= 2;
+        }
+        else if (std::string(argv[1]) == "--srgb") { tonemap = true; tm.transfer = CGPT_TRANSFER_SRGB; argv += 1; argc -= 1; }
+        else if (std::string(argv[1]) == "--exposure" && argc > 2) {
+            tonemap = true;
+            if (std::string(argv[2]) == "auto") tm.flags = CGPT_TONEMAP_AUTO_EXPOSURE;
+            else {
+                char* end = nullptr;
+                const double ev = strtod(argv[2], &end);
+                if (end == argv[2] || *end || !(std::fabs(ev) <= 64.0)) { fprintf(stderr, "--exposure needs auto or an EV in [-64, 64]\n"); return 2; }
+                tm.flags = 0u; tm.exposure_scale = (float)std::exp2(ev);
+            }
+            argv += 2; argc -= 2;
+        }
+        else if (std::string(argv[1]) == "--adapt" && argc > 2) {
+            tonemap = true; tm.alpha = (float)atof(argv[2]); argv += 2; argc -= 2;
+            if (!(tm.alpha >= 0.0f && tm.alpha <= 1.0f)) { fprintf(stderr, "--adapt needs an alpha in [0, 1]\n"); return 2; }
         }
         else if (std::string(argv[1]) == "--variance-guided") { variance_guided = true; argv += 1; argc -= 1; }
         else if (std::string(argv[1]) == "--smooth") { smooth = true; argv += 1; argc -= 1; }
@@ -202,6 +232,15 @@ int main(int argc, char** argv)
     cgpt_ctx* ctx = nullptr;
     // ThreadPool::Init: device_ids = NULL means devices 0 .. n_gpus-1
     if (cgpt_ctx_create(nullptr, n_gpus, ctx_flags, &ctx) != CGPT_OK) { fprintf(stderr, "%s\n", cgpt_last_error(nullptr)); return 1; }
+    // The display stage: with one of its options every image below goes through cgpt_tonemap on its way to a PPM -- `px`
+    // holds what the run would have written and receives the mapped pixels of the same source, still on the device.  The first image of
+    // a frame adapts the exposure by --adapt; the others of that frame keep it (alpha 0), so a frame adapts once
+    const float adapt_alpha = tm.alpha;
+    auto present = [&](uint32_t source, std::vector<uint32_t>& px, bool first_of_frame) -> int {
+        if (!tonemap) return CGPT_OK;
+        tm.source = source; tm.alpha = first_of_frame ? adapt_alpha : 0.0f;
+        return cgpt_tonemap(ctx, &tm, nullptr, 0, px.data(), px.size());
+    };
     CHECK(cgpt_set_top_level(ctx, top_level ? 1u : 0u));                  // context state too
     CHECK(cgpt_set_nee_candidates(ctx, nee_candidates));                 // context state: allowed before a scene exists, kept by every upload
     Scene::FlatStorage flat;
@@ -249,17 +288,18 @@ int main(int argc, char** argv)
             p.first_sample = 0; p.n_samples = spp; p.seed = 0x12345678u + frame; p.kernel = CGPT_KERNEL_AUTO;
             CHECK(cgpt_render(ctx, &cam, &settings, &p));
             char name[64]; std::string err;
-            CHECK(cgpt_read_pixels(ctx, px.data(), px.size()));
+            CHECK(cgpt_read_pixels(ctx, px.data(), px.size())); CHECK(present(CGPT_TONEMAP_ACCUMULATOR, px, true));
             snprintf(name, sizeof(name), "temporal_%02u_raw.ppm", frame); WritePPM(name, px.data(), W, H, err);
-            CHECK(cgpt_denoise(ctx, &cam, nullptr, nullptr, 0, px.data(), px.size()));
+            CHECK(cgpt_denoise(ctx, &cam, nullptr, nullptr, 0, px.data(), px.size())); CHECK(present(CGPT_TONEMAP_DENOISED, px, false));
             snprintf(name, sizeof(name), "temporal_%02u_denoised.ppm", frame); WritePPM(name, px.data(), W, H, err);
             if (variance_guided) {                                       // the temporal stage with the luminance moments, once per rendered frame
                 const cgpt_variance_params vp = { 4.0f, 4u, CGPT_VARIANCE_TEMPORAL };
-                CHECK(cgpt_denoise_variance_guided(ctx, &cam, nullptr, nullptr, &vp, nullptr, 0, px.data(), px.size()));
+                CHECK(cgpt_denoise_variance_guided(ctx, &cam, nullptr, nullptr, &vp, nullptr, 0, px.data(), px.size())); CHECK(present(CGPT_TONEMAP_DENOISED, px, false));
                 snprintf(name, sizeof(name), "temporal_%02u_variance_guided.ppm", frame); WritePPM(name, px.data(), W, H, err);
                 continue;
             }
             CHECK(cgpt_denoise_temporal(ctx, &cam, nullptr, nullptr, nullptr, 0, px.data(), px.size()));   // once per rendered frame
+            CHECK(present(CGPT_TONEMAP_DENOISED, px, false));
             snprintf(name, sizeof(name), "temporal_%02u_temporal.ppm", frame); WritePPM(name, px.data(), W, H, err);
         }
         cgpt_ctx_destroy(ctx);
@@ -291,11 +331,12 @@ int main(int argc, char** argv)
             p.first_sample = 0; p.n_samples = spp; p.seed = 0x12345678u + frame; p.kernel = CGPT_KERNEL_AUTO;
             CHECK(cgpt_render(ctx, &cam, &settings, &p));
             char name[64]; std::string err;
-            CHECK(cgpt_read_pixels(ctx, px.data(), px.size()));
+            CHECK(cgpt_read_pixels(ctx, px.data(), px.size())); CHECK(present(CGPT_TONEMAP_ACCUMULATOR, px, true));
             snprintf(name, sizeof(name), "spin_%02u_raw.ppm", frame); WritePPM(name, px.data(), W, H, err);
-            CHECK(cgpt_denoise(ctx, &cam, nullptr, nullptr, 0, px.data(), px.size()));
+            CHECK(cgpt_denoise(ctx, &cam, nullptr, nullptr, 0, px.data(), px.size())); CHECK(present(CGPT_TONEMAP_DENOISED, px, false));
             snprintf(name, sizeof(name), "spin_%02u_denoised.ppm", frame); WritePPM(name, px.data(), W, H, err);
             CHECK(cgpt_denoise_temporal(ctx, &cam, nullptr, &tp, nullptr, 0, px.data(), px.size()));   // once per rendered frame
+            CHECK(present(CGPT_TONEMAP_DENOISED, px, false));
             snprintf(name, sizeof(name), "spin_%02u_temporal.ppm", frame); WritePPM(name, px.data(), W, H, err);
         }
         cgpt_ctx_destroy(ctx);
@@ -432,12 +473,13 @@ int main(int argc, char** argv)
             p.first_sample = 0; p.n_samples = spp; p.seed = 0x12345678u + frame; p.kernel = CGPT_KERNEL_AUTO;
             CHECK(cgpt_render(ctx, &cam, &settings, &p));
             char name[64]; std::string err;
-            CHECK(cgpt_read_pixels(ctx, px.data(), px.size()));
+            CHECK(cgpt_read_pixels(ctx, px.data(), px.size())); CHECK(present(CGPT_TONEMAP_ACCUMULATOR, px, true));
             const char* tag = animate ? "animate" : crowd ? "crowd" : bend ? "bend" : "bulge";
             snprintf(name, sizeof(name), "%s_%02u_raw.ppm", tag, frame); WritePPM(name, px.data(), W, H, err);
-            CHECK(cgpt_denoise(ctx, &cam, nullptr, nullptr, 0, px.data(), px.size()));
+            CHECK(cgpt_denoise(ctx, &cam, nullptr, nullptr, 0, px.data(), px.size())); CHECK(present(CGPT_TONEMAP_DENOISED, px, false));
             snprintf(name, sizeof(name), "%s_%02u_denoised.ppm", tag, frame); WritePPM(name, px.data(), W, H, err);
             CHECK(cgpt_denoise_temporal(ctx, &cam, nullptr, &tp, nullptr, 0, px.data(), px.size()));   // once per rendered frame
+            CHECK(present(CGPT_TONEMAP_DENOISED, px, false));
             snprintf(name, sizeof(name), "%s_%02u_temporal.ppm", tag, frame); WritePPM(name, px.data(), W, H, err);
         }
         cgpt_ctx_destroy(ctx);
@@ -463,15 +505,15 @@ int main(int argc, char** argv)
         CHECK(cgpt_render(ctx, &scene.camera.Abi(), &settings, &p));
         num_accumulated += p.n_samples;
         if (preview_every) {                                             // DX12::CopyToBackBuffer + Present
-            CHECK(cgpt_read_pixels(ctx, pixels.data(), pixels.size()));
+            CHECK(cgpt_read_pixels(ctx, pixels.data(), pixels.size())); CHECK(present(CGPT_TONEMAP_ACCUMULATOR, pixels, true));
             char name[64]; snprintf(name, sizeof(name), "preview_%04u.ppm", num_accumulated);
             std::string err; WritePPM(name, pixels.data(), W, H, err);
             if (denoise) {                                               // the "Denoise" toggle: the filtered image instead of data.pixels
-                CHECK(cgpt_denoise(ctx, &scene.camera.Abi(), nullptr, nullptr, 0, denoised.data(), denoised.size()));
+                CHECK(cgpt_denoise(ctx, &scene.camera.Abi(), nullptr, nullptr, 0, denoised.data(), denoised.size())); CHECK(present(CGPT_TONEMAP_DENOISED, denoised, false));
                 snprintf(name, sizeof(name), "preview_%04u_denoised.ppm", num_accumulated);
                 WritePPM(name, denoised.data(), W, H, err);
                 if (variance_guided) {
-                    CHECK(cgpt_denoise_variance_guided(ctx, &scene.camera.Abi(), nullptr, nullptr, nullptr, nullptr, 0, denoised.data(), denoised.size()));
+                    CHECK(cgpt_denoise_variance_guided(ctx, &scene.camera.Abi(), nullptr, nullptr, nullptr, nullptr, 0, denoised.data(), denoised.size())); CHECK(present(CGPT_TONEMAP_DENOISED, denoised, false));
                     snprintf(name, sizeof(name), "preview_%04u_variance_guided.ppm", num_accumulated);
                     WritePPM(name, denoised.data(), W, H, err);
                 }
@@ -486,16 +528,17 @@ int main(int argc, char** argv)
 
     std::vector<float> acc((size_t)W * H * 4);
     CHECK(cgpt_read_pixels(ctx, pixels.data(), pixels.size()));          // DX12::CopyToBackBuffer(data.pixels)
+    CHECK(present(CGPT_TONEMAP_ACCUMULATOR, pixels, true));
     CHECK(cgpt_read_accumulator(ctx, acc.data(), acc.size()));
     std::string err;
     WritePPM("render.ppm", pixels.data(), W, H, err);
     WritePFM("render.pfm", acc.data(), num_accumulated, W, H, err);
     WriteAccumulator("render.acc", acc.data(), num_accumulated, W, H, err);
     if (denoise) {
-        CHECK(cgpt_denoise(ctx, &scene.camera.Abi(), nullptr, nullptr, 0, denoised.data(), denoised.size()));
+        CHECK(cgpt_denoise(ctx, &scene.camera.Abi(), nullptr, nullptr, 0, denoised.data(), denoised.size())); CHECK(present(CGPT_TONEMAP_DENOISED, denoised, false));
         WritePPM("render_denoised.ppm", denoised.data(), W, H, err);
         if (variance_guided) {
-            CHECK(cgpt_denoise_variance_guided(ctx, &scene.camera.Abi(), nullptr, nullptr, nullptr, nullptr, 0, denoised.data(), denoised.size()));
+            CHECK(cgpt_denoise_variance_guided(ctx, &scene.camera.Abi(), nullptr, nullptr, nullptr, nullptr, 0, denoised.data(), denoised.size())); CHECK(present(CGPT_TONEMAP_DENOISED, denoised, false));
             WritePPM("render_variance_guided.ppm", denoised.data(), W, H, err);
         }
     }

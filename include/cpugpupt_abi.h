@@ -889,6 +889,56 @@ int cgpt_denoise_variance_guided(cgpt_ctx* ctx, const cgpt_camera* camera, const
  * pass) */
 int cgpt_read_variance(cgpt_ctx* ctx, float* dst, size_t n_floats);
 
+/* ---- the display stage (no reference counterpart) ---------------------------------------------------- */
+/* Linear radiance to a displayable image on the device: auto exposure from a luminance histogram, a tone curve, the sRGB transfer
+ * function, and the pixel packed as data.pixels is.  csrc/host/tonemap.h states the arithmetic once for the kernels and the host mirror
+ * (cgpth_tonemap), tests/tonemap_ref.py the same in numpy; all of it but the sRGB curve's powf is bit-identical across the three.
+ *   source   ACCUMULATOR: the band of the last render divided by num_accumulated as cgpt_read_pixels divides it (any band, an interleaved
+ *            one included; a multi-device context's gathered frame, on device_ids[0]).  DENOISED: the float4 result of the context's last
+ *            successful cgpt_denoise / cgpt_denoise_temporal / cgpt_denoise_variance_guided call, still on the device; every such call drops
+ *            it when it starts and sets it when it succeeds; cgpt_render, cgpt_reset_accumulator, cgpt_write_accumulator and a framebuffer
+ *            reallocation drop it.  HOST: src_rgba, src_width x src_height float4 pixels, uploaded; needs no scene.
+ *   exposure manual: exposure_scale 2^ev_bias.  CGPT_TONEMAP_AUTO_EXPOSURE: the luminance Y = (0.2126 r + 0.7152 g) + 0.0722 b of every
+ *            source pixel is counted in 256 bins over [2^-16, 2^16), eight an octave (a Y that is <= 0, NaN or +inf is not counted but
+ *            tallied in n_ignored); the lowest low_fraction and the highest high_fraction of the counted pixels are dropped; the mean bin
+ *            index m of the rest (in eighths of an octave) is the frame's reading; the context's adapted index moves towards it,
+ *            m_adapted += (m - m_adapted) alpha (the first reading sets it; a frame without a reading keeps it); the luminance L at
+ *            m_adapted is brought to `key`: exposure = key / L  exposure_scale 2^ev_bias.  With no reading ever the metered factor is 1.
+ *            m_adapted is context state like cgpt_set_nee_candidates: uploads and edits keep it, cgpt_exposure_reset forgets it.
+ *   curve    per channel on x = max(c exposure, 0), a NaN as 0.  CLAMP: x (the reference's Vec4ToUint clamps when it packs).  REINHARD:
+ *            x (1 + x / white^2) / (1 + x).  ACES: Narkowicz's fit.  HABLE: Hable's filmic curve over its value at `white`.
+ *   transfer LINEAR: nothing.  SRGB: the sRGB encoding of min(y, 1).
+ * dst_rgba receives {r, g, b, 1} per pixel, dst_pixels Vec4ToUint of the same; either may be NULL, not both; n_floats = 4 n and
+ * n_pixels = n for the source's n pixels.  NULL params: the accumulator, ACES, SRGB, auto exposure, key 0.18, fractions 0.5 / 0.02,
+ * alpha 1, white 4, exposure_scale 1, ev_bias 0.
+ * The call blocks, runs on the context's stream (cgpt_set_stream), writes buffers of its own and leaves the accumulator, data.pixels,
+ * num_accumulated, the denoiser's outputs, guides and history and cgpt_stats as they are.
+ * Refused with nothing changed, m_adapted and the last reading included (CGPT_ERR_INVALID unless noted): an unknown enum value or flag
+ * bit; exposure_scale or white not finite and > 0; |ev_bias| > 64; with AUTO_EXPOSURE a key not finite and > 0, a fraction outside
+ * [0, 1), low + high >= 1, alpha outside [0, 1] or NaN; HOST without an image or with a zero size; both outputs NULL or a wrong size;
+ * ACCUMULATOR / DENOISED without a scene (CGPT_ERR_NO_SCENE), before a render, with num_accumulated == 0 or after a debug view; DENOISED
+ * without a valid result.  Added exports: CGPT_ABI_VERSION stays 2. */
+enum cgpt_tonemap_source   { CGPT_TONEMAP_ACCUMULATOR = 0, CGPT_TONEMAP_DENOISED = 1, CGPT_TONEMAP_HOST = 2 };
+enum cgpt_tonemap_curve    { CGPT_CURVE_CLAMP = 0, CGPT_CURVE_REINHARD = 1, CGPT_CURVE_ACES = 2, CGPT_CURVE_HABLE = 3 };
+enum cgpt_tonemap_transfer { CGPT_TRANSFER_LINEAR = 0, CGPT_TRANSFER_SRGB = 1 };
+enum cgpt_tonemap_flags    { CGPT_TONEMAP_AUTO_EXPOSURE = 1u };
+typedef struct cgpt_tonemap_params {
+    uint32_t source, curve, transfer, flags;
+    float exposure_scale; int32_t ev_bias; float white;
+    float key, low_fraction, high_fraction, alpha;           /* read with AUTO_EXPOSURE only */
+    const float* src_rgba; uint32_t src_width, src_height;   /* CGPT_TONEMAP_HOST only */
+} cgpt_tonemap_params;
+int cgpt_tonemap(cgpt_ctx* ctx, const cgpt_tonemap_params* params, float* dst_rgba, size_t n_floats, uint32_t* dst_pixels, size_t n_pixels);
+/* The reading of the last successful auto-exposure call.  valid: bit 0 (CGPT_EXPOSURE_ADAPTED) adapted_index holds a reading, this
+ * frame's or an earlier one's; bit 1 (CGPT_EXPOSURE_METERED) this frame gave one (mean_index; 0 otherwise).  n_counted is N before the
+ * trimming; histogram the 256 counts.  CGPT_ERR_INVALID before any auto-exposure call of the context. */
+enum cgpt_exposure_valid { CGPT_EXPOSURE_ADAPTED = 1u, CGPT_EXPOSURE_METERED = 2u };
+typedef struct cgpt_exposure_info { double mean_index, adapted_index; float exposure; uint32_t valid;
+                                    uint64_t n_counted, n_ignored; uint32_t histogram[256]; } cgpt_exposure_info;
+int cgpt_read_exposure(cgpt_ctx* ctx, cgpt_exposure_info* out);
+/* forgets m_adapted: the next reading sets it.  The last reading (cgpt_read_exposure) stays */
+int cgpt_exposure_reset(cgpt_ctx* ctx);
+
 /* ---- tuning and measurement aids (no reference counterpart) ------------------------------------------------------- */
 /* Overrides one tuning knob of the wavefront pipeline for this context (the CGPT_WF_* environment variables set the same
  * knobs process-wide; names are the variable names without the prefix, lower case: "pools", "batch", "max_batch",

@@ -163,6 +163,18 @@ int cgpth_scene_bvh_export(const cgpth_scene* scene, uint32_t obj_index, cgpt_bv
  * nothing written: nodes or out NULL, n_nodes 0, a constant that is not finite and > 0, a child index outside the array, nodes that
  * form no tree.  A cost that is not finite is returned as it is. */
 int cgpth_tree_cost(const cgpt_bvh_node* nodes, uint32_t n_nodes, double c_inner, double c_tri, cgpt_tree_cost* out);
+/* the host statement of cgpt_tonemap (csrc/host/tonemap.h states the arithmetic; tests/tonemap_ref.py the same in numpy)
+ * over a host image: params->source must be CGPT_TONEMAP_HOST.  `state` is what a context keeps between calls -- the adapted histogram
+ * index and whether it holds a reading (zero-initialise it; clearing `valid` is cgpt_exposure_reset) -- read and written with
+ * CGPT_TONEMAP_AUTO_EXPOSURE only and may be NULL otherwise; info_out (may be NULL) receives what cgpt_read_exposure would return after
+ * the same call.  Bit for bit the device's results except behind CGPT_TRANSFER_SRGB, where the two powf differ by a few ulp.  Refused
+ * with CGPT_ERR_INVALID and nothing written, the state included: what cgpt_tonemap refuses of its parameters and outputs, NULL params,
+ * another source, auto exposure without a state. */
+/* the histogram bin (0..255) of a luminance, or -1 for one that is not counted (<= 0, NaN, +inf) */
+int cgpth_luminance_bin(float luminance);
+typedef struct cgpth_exposure_state { double adapted_index; uint32_t valid, reserved; } cgpth_exposure_state;
+int cgpth_tonemap(const cgpt_tonemap_params* params, cgpth_exposure_state* state, float* dst_rgba, size_t n_floats, uint32_t* dst_pixels,
+                  size_t n_pixels, cgpt_exposure_info* info_out);
 /* flatten for cgpt_scene_upload; pointers stay valid until the scene is changed or freed */
 int cgpth_scene_flatten(cgpth_scene* scene, cgpt_scene_desc* out);
 int cgpth_scene_get_camera(const cgpth_scene* scene, cgpt_camera* out);
